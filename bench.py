@@ -9,31 +9,39 @@
 
 The headline dtype is h2 (split-fp16 pairs on the fp16 matrix pipe, include/vti.h): the dtype whose detections and masks meet the
 north-star tolerance against the fp32 CPU oracle (`parity.meets_north_star`).  The plain-fp16 engine (faster, but its results
-drift past the tolerance) and the exact-f32 engine are reported beside it as `fp16_engine` / `fp32_engine`.
+drift past the tolerance) and the exact-f32 engine are reported beside it as `fp16_engine` / `fp32_engine` (--full).
 
 One step = one pass of the whole predict pipeline (letterbox[identity] -> 76-conv network -> decode ->
 NMS -> mask assembly (bit-packed) -> scale_boxes) over one batch of 64 synthetic 640x640x3 uint8
 frames per GPU, inputs already resident in HBM.  Network and post-processing run in series on one stream, so the forward's
 HIP-event time in the timed region is its own.  --pipeline overlaps post-processing of batch k-1 with the network of batch k
 on a second stream (~6 % more frames/s; every batch's full output is still complete before the closing barrier); the forward
-then shares the chip, which is why `roofline.isolated` also reports the same forward timed alone right after the timed region.  N > 1: one process per GPU; frames live on rank 0
+then shares the chip, which is why `roofline.isolated` (--full) also reports the same forward timed alone right after the timed region.  N > 1: one process per GPU; frames live on rank 0
 and every step scatters the next batch / gathers the previous batch's detections + bit-packed masks
 over RCCL (xGMI) on a side stream, overlapped with compute (weak scaling: 64 frames per GPU).
 
 Before the W warm-up steps the chip is pre-heated with >= --preheat seconds of the same steps (clocks sag under sustained
 MFMA load; a 20-step run is only ~50 ms long), so the timed steps land on settled clocks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
-  parity       -- the benchmarked engine against the fp32 CPU oracle on --parity-frames of the bench frames, AFTER the timed
-                  region, through the same entry points the timed loop uses: mask IoU (min / p1 / mean), |d box| in px and
-                  normalised, kept-set equality (north_star: IoU >= 0.999, |d box| < 1e-3, same kept set).
-  fp16_engine / fp32_engine -- the same pipeline, weights and frames on the other two storage types, each with the driver's
-                  --steps / --warmup, its own roofline fraction and parity object.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, pre-heats, warms up, times the K steps and
+prints the line with
   roofline     -- the conv network (76 MFMA conv launches, >85 % of the step) against the dense fp16
                   MFMA peak: achieved = 2*MAC of all convs per forward / forward time measured with HIP
                   events on the launch stream inside the timed region.
+--full adds the measurements and checks that take runs of their own, after the timed region:
+  roofline.isolated -- the same forward timed alone on the chip.
+  parity       -- the benchmarked engine against the fp32 CPU oracle on --parity-frames of the bench frames,
+                  through the same entry points the timed loop uses: mask IoU (min / p1 / mean), |d box| in px and
+                  normalised, kept-set equality (north_star: IoU >= 0.999, |d box| < 1e-3, same kept set).
+  host_fed     -- the same step with the frames starting in pinned host memory (N = 1 only).
+  fp16_engine / fp32_engine -- the same pipeline, weights and frames on the other two storage types, each with the driver's
+                  --steps / --warmup, its own roofline fraction and parity object (N = 1 only).
   cpu_baseline -- the CPU oracle (torch-CPU fp32 restatement, kind "port") timed on this host's cores,
                   rank 0, N = 1 only, on a bounded sample.
+The --no-* options and --parity-frames switch single parts of --full off.
+
+--dump-outputs DIR writes what rank 0's last timed step computed as .npy files (see dump_outputs); the frames and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -223,6 +231,40 @@ def host_fed_line(vti_amd, eng, frames, B, H, W, cap, dev, steps, warmup):
                      "predict kernels); PCIe-inclusive rate, not the headline")
 
 
+def dump_outputs(vti_amd, d, o, B, H, W, cap, n_frames=8, n_inst=2, n_full=2, seed=0):
+    """--dump-outputs: the arrays a caller of the timed pipeline receives from one step (output set `o`), as float32 / float64 .npy in
+    `d` (~45 MB).  Rows past a frame's detection count and mask slots past the live ones are zeroed: the pipeline does not write them.
+      dets [B,max_det,6+nm] f32, xyxy [B,max_det,4] f32, counts [B] / offsets [B+1] f64 -- whole;
+      mask_area [live slots] f64 -- pixels set in every live mask (the bit-packed masks are ~50 kB each, too many to write whole);
+      frame_sample [n_frames] f64 -- a fixed seeded sample of frame indices, and for those frames
+      masks_sample [n_frames, n_inst, H, W] f32 -- the first n_inst instance masks unpacked to 0/1 (zeros where a frame has fewer),
+      pred_sample [n_full, 4+nc+nm, A] f32 / proto_sample [n_full, H/4, W/4, nm] f32 -- the forward's outputs of the first n_full."""
+    os.makedirs(d, exist_ok=True)
+    counts = o["counts"].cpu().numpy().astype(np.int64)
+    offsets = o["offsets"].cpu().numpy().astype(np.int64)
+    max_det = o["dets"].shape[1]
+    valid = (np.arange(max_det)[None, :] < counts[:, None])[..., None]
+    n_live = int(min(max(offsets[-1], 0), cap))
+    popc = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device=o["masks"].device)
+    area = torch.cat([popc[o["masks"][i:min(i + 256, n_live)].long()].sum((1, 2)) for i in range(0, n_live, 256)]) if n_live else torch.zeros(0)
+    fr = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(B, min(n_frames, B), replace=False))
+    ms = np.zeros((len(fr), n_inst, H, W), np.float32)
+    for j, b in enumerate(fr):
+        for i in range(n_inst):
+            slot = offsets[b] + i
+            if i < counts[b] and slot < n_live:
+                ms[j, i] = vti_amd.unpack_bits(o["masks"][slot], W).cpu().numpy()
+    out = {"dets": np.where(valid, o["dets"].cpu().numpy(), 0).astype(np.float32),
+           "xyxy": np.where(valid, o["xyxy"].cpu().numpy(), 0).astype(np.float32),
+           "counts": counts.astype(np.float64), "offsets": offsets.astype(np.float64),
+           "mask_area": area.cpu().numpy().astype(np.float64), "frame_sample": fr.astype(np.float64), "masks_sample": ms,
+           "pred_sample": o["pred"][torch.as_tensor(fr[:n_full])].float().cpu().numpy(),
+           "proto_sample": o["proto"][torch.as_tensor(fr[:n_full])].float().cpu().numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
+
+
 DTYPE_TAG = {"h2": "f16x2", "fp16": "f16", "fp32": "f32"}
 PEAKS = {"h2": round(H2_PEAK_TFLOPS, 1), "fp16": MFMA_PEAK_TFLOPS, "fp32": F32_MFMA_PEAK_TFLOPS}
 DTYPE_NOTE = {
@@ -347,7 +389,14 @@ def main():
                     help="overlap post-processing of batch k-1 with the network of batch k on a second stream: ~6 %% more frames/s "
                          "(24.7k vs 23.2k on one MI355X), but the forward then shares the chip and its in-region HIP-event time (the "
                          "roofline line) is inflated; default: the stages in series on one stream")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what takes runs of its own: the isolated forward (roofline.isolated), parity "
+                         "against the CPU oracle, the host-fed, fp16 / fp32 engine lines and the CPU baseline; default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64 (see dump_outputs)")
     args = ap.parse_args()
+    if args.dry and args.dump_outputs:
+        ap.error("--dump-outputs needs the GPU path (not --dry)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # plain `python bench.py --gpus N`: be the launcher (no GPU touched yet)
         sys.exit(launch_ranks(args.gpus))
@@ -501,18 +550,21 @@ def main():
     elapsed = time.perf_counter() - t0
     if grouped:
         elapsed = dp.max_over_ranks(elapsed, dev)
+    if args.dump_outputs and rank == 0:              # the last timed step wrote outs[(steps - 1) & 1]; nothing has touched it since
+        dump_outputs(vti_amd, args.dump_outputs, outs[(args.steps - 1) & 1], B, H, W, cap)
 
-    # the forward alone (nothing else on the chip), HIP events on the launch stream, right after the timed region
-    iso0, iso1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    n_iso = max(5, min(20, args.steps))
-    eng.forward(shards[0], True, pred=outs[0]["pred"], proto=outs[0]["proto"], best=None if UNSCORED else outs[0]["best"])
-    torch.cuda.synchronize()
-    iso0.record(main_stream)
-    for _ in range(n_iso):
+    if args.full:
+        # the forward alone (nothing else on the chip), HIP events on the launch stream, right after the timed region
+        iso0, iso1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        n_iso = max(5, min(20, args.steps))
         eng.forward(shards[0], True, pred=outs[0]["pred"], proto=outs[0]["proto"], best=None if UNSCORED else outs[0]["best"])
-    iso1.record(main_stream)
-    torch.cuda.synchronize()
-    iso_ms = iso0.elapsed_time(iso1) / n_iso
+        torch.cuda.synchronize()
+        iso0.record(main_stream)
+        for _ in range(n_iso):
+            eng.forward(shards[0], True, pred=outs[0]["pred"], proto=outs[0]["proto"], best=None if UNSCORED else outs[0]["best"])
+        iso1.record(main_stream)
+        torch.cuda.synchronize()
+        iso_ms = iso0.elapsed_time(iso1) / n_iso
 
     fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev_f0, ev_f1)]))
     post_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev_p0, ev_end)]))
@@ -567,24 +619,27 @@ def main():
                          "flop_per_launch": flops_per_forward, "avg_ms": round(fwd_ms, 4),
                          "flop_executed_per_launch": flops_executed,
                          "executed_note": "algebraic fold of proto.upsample into proto.cv2: the kernels issue this many flops for the same result; `achieved` and `frac` use the ALGORITHMIC count (SURVEY 8d), the matrix pipe's own utilisation follows from the executed one: "
-                                          + f"{flops_executed / (fwd_ms * 1e-3) / 1e12 * (4.0 if args.dtype == 'h2' else 1.0) / (F32_MFMA_PEAK_TFLOPS if args.dtype == 'fp32' else MFMA_PEAK_TFLOPS):.4f} of its peak",
-                         "isolated": {"avg_ms": round(iso_ms, 4), "achieved": round(flops_per_forward / (iso_ms * 1e-3) / 1e12, 2),
-                                      "frac": round(flops_per_forward / (iso_ms * 1e-3) / 1e12 / peak, 5),
-                                      "note": f"the same forward alone on the chip, {n_iso} back-to-back launches after the timed region"}},
+                                          + f"{flops_executed / (fwd_ms * 1e-3) / 1e12 * (4.0 if args.dtype == 'h2' else 1.0) / (F32_MFMA_PEAK_TFLOPS if args.dtype == 'fp32' else MFMA_PEAK_TFLOPS):.4f} of its peak"},
             "stage_ms": {"forward": round(fwd_ms, 4), "nms+masks+scale_boxes": round(post_ms, 4)},
         }
         line["config"]["preheat"] = f"{n_heat} untimed steps over >= {args.preheat:.1f} s before the {args.warmup} warm-up steps"
-        if args.parity_frames > 0:
-            line["parity"] = parity_check(eng, blob, frames, nc, H, W, min(args.parity_frames, B))
-            line["parity"]["engine"] = line["dtype"]
-            line["parity"]["tolerance"] = "north_star gate: mask IoU >= 0.999 for every instance and |d box| < 1e-3 (normalised by 640) with the same kept set and order: see meets_north_star"
-        if world == 1 and not args.no_host_fed:
-            line["host_fed"] = host_fed_line(vti_amd, eng, frames, B, H, W, cap, dev, args.steps, args.warmup)
-        for other, skip in (("fp16", args.no_fp16_line), ("fp32", args.no_fp32_line)):
-            if world == 1 and other != args.dtype and not skip:
-                line[other + "_engine"] = other_engine_line(vti_amd, other, blob, frames, B, H, W, nc, cap, dev, min(args.parity_frames, B), args.steps, args.warmup)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(blob, H, W, nc)
+        if args.full:
+            line["roofline"]["isolated"] = {"avg_ms": round(iso_ms, 4), "achieved": round(flops_per_forward / (iso_ms * 1e-3) / 1e12, 2),
+                                            "frac": round(flops_per_forward / (iso_ms * 1e-3) / 1e12 / peak, 5),
+                                            "note": f"the same forward alone on the chip, {n_iso} back-to-back launches after the timed region"}
+            if args.parity_frames > 0:
+                line["parity"] = parity_check(eng, blob, frames, nc, H, W, min(args.parity_frames, B))
+                line["parity"]["engine"] = line["dtype"]
+                line["parity"]["tolerance"] = "north_star gate: mask IoU >= 0.999 for every instance and |d box| < 1e-3 (normalised by 640) with the same kept set and order: see meets_north_star"
+            if world == 1 and not args.no_host_fed:
+                line["host_fed"] = host_fed_line(vti_amd, eng, frames, B, H, W, cap, dev, args.steps, args.warmup)
+            for other, skip in (("fp16", args.no_fp16_line), ("fp32", args.no_fp32_line)):
+                if world == 1 and other != args.dtype and not skip:
+                    line[other + "_engine"] = other_engine_line(vti_amd, other, blob, frames, B, H, W, nc, cap, dev, min(args.parity_frames, B), args.steps, args.warmup)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(blob, H, W, nc)
+        if args.dump_outputs:
+            line["dump_outputs"] = args.dump_outputs
         print(json.dumps(line), flush=True)
     if grouped:
         torch.distributed.destroy_process_group()

@@ -5,7 +5,7 @@ tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/profiles; mkdir -p $out
 export VTI_SINGLE_STREAM=1
-args="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-line --no-host-fed --no-fp16-line --parity-frames 0 --preheat 0 --dtype ${2:-h2}"
+args="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-line --no-host-fed --no-fp16-line --parity-frames 0 --preheat 0 --full --dtype ${2:-h2}"
 rm -rf gpurun_out/_sq1 gpurun_out/_sq2
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU --output-format csv -d gpurun_out/_sq1 -- python3 $args > /dev/null 2> gpurun_out/_sq1.err || exit 1
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_INSTS_MFMA --output-format csv -d gpurun_out/_sq2 -- python3 $args > /dev/null 2> gpurun_out/_sq2.err || exit 1
