@@ -40,7 +40,8 @@
  *                                          boxes in letterboxed px (vti_scale_boxes maps to frame px)
  *      counts   i32 [B]                   detections per frame
  *      masks    u8  [cap,H,W] (VTI_PACK_U8, 0/1 per byte) or u8 [cap,H,W/8] (VTI_PACK_BITS,
- *               LSB-first); instance i of frame b lives in slot offsets[b]+i
+ *               LSB-first); instance i of frame b lives in slot offsets[b]+i.  vti_masks_native: u8 [cap,H0,W0] or
+ *               u8 [cap,H0,8*ceil(W0/64)] (vti_mask_native_layout)
  *      offsets  i32 [B+1]                 exclusive prefix sum of counts (written by vti_masks)
  */
 #ifndef VTI_H
@@ -73,6 +74,8 @@ enum { VTI_F16 = 0, VTI_F32 = 1, VTI_H2 = 2 };
 enum { VTI_MASK_LOGIT = 0,     /* current Ultralytics: crop, bilinear upsample, > 0.0 */
        VTI_MASK_SIGMOID = 1 }; /* Ultralytics 8.0.x : sigmoid, crop, upsample, > 0.5  */
 enum { VTI_PACK_U8 = 0, VTI_PACK_BITS = 1 };
+/* vti_predict mask_mode flag: frame-resolution masks (Ultralytics predict(retina_masks=True)) through vti_masks_native. */
+#define VTI_MASK_NATIVE 0x10
 /* vti_masks work-list size: one call handles at most max_batch * VTI_MASK_SLOTS_PER_FRAME instances (capacity above that is
  * VTI_ERR_UNSUPPORTED); vti_workspace_bytes() is sized for it.  Ultralytics' default max_det is 300, the reference's 200. */
 #define VTI_MASK_SLOTS_PER_FRAME 512
@@ -148,11 +151,23 @@ int32_t vti_nms_scored(vti_ctx* ctx, const float* dev_pred, const float* dev_anc
 int32_t vti_masks(vti_ctx* ctx, const float* dev_dets, const int32_t* dev_counts, const void* dev_proto,
                   int32_t B, int32_t max_det, int32_t mode, int32_t packing,
                   uint8_t* dev_masks, int32_t capacity, int32_t* dev_offsets, void* stream);
+/* U7' process_mask_native + threshold (Ultralytics predict(retina_masks=True), the 8.1/8.2 scale_masks form): coefficients x
+ * prototypes, crop of the prototype grid to the frame's letterbox content [top,bottom) x [left,right) (pads computed in double,
+ * truncated), bilinear resize (align_corners=False, torch's fp32 taps; up or down) straight to H0xW0, crop to the FRAME-px boxes
+ * dev_xyxy of vti_scale_boxes (x1 <= col < x2, y1 <= row < y2), threshold as vti_masks.  Masks are u8 [cap,H0,row_bytes]:
+ * VTI_PACK_BITS row_bytes = 8*ceil(W0/64) (LSB-first, bits at columns >= W0 are 0; dev_masks 8-byte aligned), VTI_PACK_U8
+ * row_bytes = W0.  Slots, offsets and the capacity rule as vti_masks; nm must be 32 (else VTI_ERR_UNSUPPORTED). */
+int32_t vti_masks_native(vti_ctx* ctx, const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                         const void* dev_proto, int32_t B, int32_t max_det, int32_t H0, int32_t W0, int32_t mode,
+                         int32_t packing, uint8_t* dev_masks, int32_t capacity, int32_t* dev_offsets, void* stream);
+/* Host only: out[6] = {top, bottom, left, right, row_bytes, slot_bytes} of vti_masks_native for an H0xW0 frame. */
+int32_t vti_mask_native_layout(const vti_ctx* ctx, int32_t H0, int32_t W0, int32_t packing, int32_t out[6]);
 /* U8 scale_boxes + clip: letterboxed px -> frame px, writes f32 [B,max_det,4]. */
 int32_t vti_scale_boxes(vti_ctx* ctx, const float* dev_dets, const int32_t* dev_counts, int32_t B,
                         int32_t max_det, int32_t H0, int32_t W0, float* dev_xyxy, void* stream);
 /* All of the above on one stream (the scored pair of entry points, with the pairs in the workspace).  dev_input_scratch
- * (u8 [B,H,W,3]) may be NULL when H0xW0 == HxW. */
+ * (u8 [B,H,W,3]) may be NULL when H0xW0 == HxW.  mask_mode | VTI_MASK_NATIVE: dev_xyxy is required, vti_scale_boxes runs first
+ * and the masks come from vti_masks_native (frame resolution, its layout). */
 int32_t vti_predict(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t H0, int32_t W0,
                     int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic,
                     int32_t mask_mode, int32_t packing, uint8_t* dev_input_scratch,

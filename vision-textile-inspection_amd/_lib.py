@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, f"libvti_{_VARIANT}.so" if _VARIANT else "libvti.
 VTI_F16, VTI_F32, VTI_H2 = 0, 1, 2
 VTI_MASK_LOGIT, VTI_MASK_SIGMOID = 0, 1
 VTI_PACK_U8, VTI_PACK_BITS = 0, 1
+VTI_MASK_NATIVE = 0x10       # vti_predict mask_mode flag: frame-resolution masks (vti_masks_native)
 
 
 class VtiDesc(C.Structure):
@@ -58,6 +59,8 @@ SIGNATURES = {
     "vti_forward_scored": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "vti_nms_scored": (_I32, [_P, _P, _P, _I32, _F, _D, _I32, _I32, _P, _P, _P]),
     "vti_masks": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "vti_masks_native": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "vti_mask_native_layout": (_I32, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "vti_scale_boxes": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "vti_predict": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _F, _D, _I32, _I32, _I32, _I32,
                            _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),

@@ -27,7 +27,8 @@ def attach(result, engine):
 
 
 def instance_bitmaps(engine, result, h, w):
-    """All instances at once: (bitmaps u8 [N,h,w] on device, nonzero i32 [N]).  A4 batched."""
+    """All instances at once: (bitmaps u8 [N,h,w] on device, nonzero i32 [N]).  A4 batched.  Masks of a
+    predict(retina_masks=True) result are already frame-sized: the nearest resize is then the identity."""
     if result.masks is None:
         dev = engine.device
         return torch.empty((0, h, w), dtype=torch.uint8, device=dev), torch.empty((0,), dtype=torch.int32, device=dev)

@@ -883,6 +883,44 @@ constexpr int MTILES = (MPTS + 15) / 16;        // 23 column tiles
 constexpr int MJ = (MTILES + 3) / 4;            // column tiles per wave
 constexpr int MROUND = 64;                      // instances examined per list round (one per lane of wave 0)
 
+// One instance's 32 coefficients -> the 8 x 16-byte MFMA operand pieces of the coefficient side, returns the scale the products
+// are multiplied back by.  fp16 prototypes: c = s * (h + l) with h = half(c/s), l = half(c/s - h), s a power of two that is 1 unless
+// |c| >= 3e4 (pieces 0..3 = the high halves of channels 8q..8q+7, pieces 4..7 the residuals); fp32: piece q = channels 4q..4q+3.
+template <bool F16>
+__device__ __forceinline__ float mask_coef_operands(const float (&cf)[32], uint4* dst) {
+    float scale = 1.0f;
+    if constexpr (F16) {
+        float mx = 0.f;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) mx = fmaxf(mx, fabsf(cf[k]));
+        float inv = 1.0f;
+        if (!(mx < 3.0e4f)) {                              // out of half range: c = 2^e * c', |c'| < 2^14
+            const int e = (int)((__builtin_bit_cast(unsigned, mx) >> 23) & 255u) - 127 - 13;
+            const int ec = e < -100 ? -100 : (e > 100 ? 100 : e);
+            scale = __builtin_bit_cast(float, (unsigned)(ec + 127) << 23);
+            inv = __builtin_bit_cast(float, (unsigned)(127 - ec) << 23);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                      // piece q = channels 8q .. 8q+7: high halves, then the residuals
+            half8 hh, hl;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float c = cf[8 * q + k] * inv;
+                const half_t h = (half_t)c;
+                hh[k] = h;
+                hl[k] = (half_t)(c - (float)h);
+            }
+            dst[q] = __builtin_bit_cast(uint4, hh);
+            dst[4 + q] = __builtin_bit_cast(uint4, hl);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q)                        // piece q = channels 4q .. 4q+3
+            dst[q] = __builtin_bit_cast(uint4, (f32x4){cf[4 * q], cf[4 * q + 1], cf[4 * q + 2], cf[4 * q + 3]});
+    }
+    return scale;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 3) void masks_group_kernel(const float* __restrict__ dets, const int* __restrict__ offsets,
                                                           const T* __restrict__ proto, int B, int max_det, int Hp, int Wp,
@@ -991,37 +1029,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 3) void masks_group_kerne
                     float cf[32];
 #pragma unroll
                     for (int k = 0; k < 16; ++k) { cf[2 * k] = raw[3 + k].x; cf[2 * k + 1] = raw[3 + k].y; }
-                    float scale = 1.0f;
-                    if constexpr (F16) {
-                        float mx = 0.f;
-#pragma unroll
-                        for (int k = 0; k < 32; ++k) mx = fmaxf(mx, fabsf(cf[k]));
-                        float inv = 1.0f;
-                        if (!(mx < 3.0e4f)) {                              // out of half range: c = 2^e * c', |c'| < 2^14
-                            const int e = (int)((__builtin_bit_cast(unsigned, mx) >> 23) & 255u) - 127 - 13;
-                            const int ec = e < -100 ? -100 : (e > 100 ? 100 : e);
-                            scale = __builtin_bit_cast(float, (unsigned)(ec + 127) << 23);
-                            inv = __builtin_bit_cast(float, (unsigned)(127 - ec) << 23);
-                        }
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {                      // piece q = channels 8q .. 8q+7: high halves, then the residuals
-                            half8 hh, hl;
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) {
-                                const float c = cf[8 * q + k] * inv;
-                                const half_t h = (half_t)c;
-                                hh[k] = h;
-                                hl[k] = (half_t)(c - (float)h);
-                            }
-                            s_co[pos][q] = __builtin_bit_cast(uint4, hh);
-                            s_co[pos][4 + q] = __builtin_bit_cast(uint4, hl);
-                        }
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q)                        // piece q = channels 4q .. 4q+3
-                            s_co[pos][q] = __builtin_bit_cast(uint4, (f32x4){cf[4 * q], cf[4 * q + 1], cf[4 * q + 2], cf[4 * q + 3]});
-                    }
-                    s_scale[pos] = scale;
+                    s_scale[pos] = mask_coef_operands<F16>(cf, s_co[pos]);
                 }
             }
             __syncthreads();
@@ -1188,6 +1196,319 @@ hipError_t launch_masks(int dtype, const float* dets, const int* counts, const v
     else
         hipLaunchKernelGGL(masks_kernel<float>, dim3(grid), dim3(256), 0, st, dets, offsets, (const float*)proto, B, max_det, nm, Hp, Wp,
                            H, W, mode, packing, masks, items, nitems);
+    return hipGetLastError();
+}
+
+// =====================================================================================
+// U7' process_mask_native (predict(retina_masks=True)): masks at FRAME resolution
+// =====================================================================================
+// Ultralytics 8.1/8.2 (later releases round the pad differently; this form is pinned):
+//   masks = sigmoid?(coeffs @ protos)                          [n, mh, mw]
+//   scale_masks: gain = min(mh/H0, mw/W0), pad = ((mw - W0 gain)/2, (mh - H0 gain)/2) in double, top/left = int(pad),
+//                bottom/right = int(m - pad); crop the prototype grid to [top, bottom) x [left, right), then
+//                F.interpolate(bilinear, align_corners=False) straight to H0 x W0 (any scale: up or down, no antialias)
+//   crop_mask(masks, boxes in frame px): keep x1 <= col < x2, y1 <= row < y2;  threshold > 0 (logit) / > 0.5 (sigmoid)
+// Layout (native_mask_layout): VTI_PACK_BITS u8 [cap, H0, 8 ceil(W0/64)] LSB-first, bits at columns >= W0 are 0;
+// VTI_PACK_U8 u8 [cap, H0, W0].
+int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]) {
+    if (Hp < 1 || Wp < 1 || H0 < 1 || W0 < 1 || (packing != VTI_PACK_U8 && packing != VTI_PACK_BITS)) return -1;
+    const double mh = Hp, mw = Wp;
+    const double gain = std::min(mh / H0, mw / W0);
+    const double pad_w = (mw - W0 * gain) / 2, pad_h = (mh - H0 * gain) / 2;
+    const int top = (int)pad_h, left = (int)pad_w, bottom = (int)(mh - pad_h), right = (int)(mw - pad_w);
+    if (top < 0 || left < 0 || bottom <= top || right <= left || bottom > Hp || right > Wp) return -1;
+    const long long row_bytes = packing == VTI_PACK_BITS ? 8LL * ((W0 + 63) / 64) : (long long)W0;
+    const long long slot_bytes = row_bytes * H0;
+    if (slot_bytes > 0x7fffffffLL) return -1;
+    out[0] = top; out[1] = bottom; out[2] = left; out[3] = right; out[4] = (int)row_bytes; out[5] = (int)slot_bytes;
+    return 0;
+}
+
+constexpr int NTW = 64;                 // output tile width in frame px: one wave's 64 lanes, 8 bytes of a bit row
+constexpr int NPTS = 512;               // footprint points per tile (the logits of MG instances: MG x NPTS floats of LDS)
+constexpr int NJ = NPTS / 16 / 4;       // MFMA column tiles per wave
+
+struct NativeMaskParams {
+    const float* dets;                  // [B, max_det, 38]: the coefficients
+    const float* xyxy;                  // [B, max_det, 4]: boxes in frame px (vti_scale_boxes)
+    const int* offsets;
+    const void* proto;                  // [B, Hp, Wp, 32]
+    uint8_t* masks;
+    size_t slot_bytes;
+    int B, max_det, Hp, Wp, H0, W0;
+    int top, left, inH, inW;            // the cropped prototype grid
+    float sy, sx;                       // torch's fp32 scales in / out
+    int th;                             // output tile height
+    int row_contig, col_contig;         // footprint along the axis: a contiguous prototype range (1) or the two taps of every pixel (0)
+    int mode, packing, row_bytes, capacity;
+};
+
+// torch upsample_bilinear2d (align_corners=False) source taps of output index d: fp32 src = max(s (d + 0.5) - 0.5, 0),
+// i0 = int(src), i1 = min(i0 + 1, in - 1), weight of i1 = src - i0
+__device__ __forceinline__ void native_tap(int d, float s, int in, int& i0, int& i1, float& lam) {
+    float src = s * ((float)d + 0.5f) - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    i0 = (int)src;
+    i0 = i0 < in - 1 ? i0 : in - 1;
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    lam = src - (float)i0;
+}
+// prototype index (inside the cropped grid) of footprint index f along one axis of a tile that starts at output index d0
+__device__ __forceinline__ int native_src(int f, int d0, int contig, int base, float s, int in) {
+    if (contig) return base + f;
+    int i0, i1;
+    float lam;
+    native_tap(d0 + (f >> 1), s, in, i0, i1, lam);
+    return (f & 1) ? i1 : i0;
+}
+// footprint of `n` output indices from d0: its first prototype index and its length (see NativeMaskParams::*_contig)
+__device__ __forceinline__ void native_span(int d0, int n, int contig, float s, int in, int& base, int& len) {
+    if (!contig) { base = 0; len = 2 * n; return; }
+    int a0, a1, b0, b1;
+    float lam;
+    native_tap(d0, s, in, a0, a1, lam);
+    native_tap(d0 + n - 1, s, in, b0, b1, lam);
+    base = a0; len = b1 - a0 + 1;
+}
+
+// Zeroes the live slots [0, min(offsets[B], capacity)): one contiguous byte range, so any slot size works (16-byte stores for the
+// aligned body, bytes for the ends).  Slots beyond are not touched.
+__global__ __launch_bounds__(256) void mask_clear_live_kernel(const int* __restrict__ offsets, int B, int capacity, size_t slot_bytes,
+                                                              uint8_t* __restrict__ masks) {
+    const size_t total = (size_t)min(offsets[B], capacity) * slot_bytes;
+    const size_t head = min(total, (size_t)((16u - ((uintptr_t)masks & 15u)) & 15u));
+    const size_t nvec = (total - head) >> 4;
+    const size_t tail0 = head + nvec * 16;
+    uint4* body = (uint4*)(masks + head);
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (size_t)gridDim.x * 256) body[v] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < head) masks[threadIdx.x] = 0;
+        if (tail0 + threadIdx.x < total) masks[tail0 + threadIdx.x] = 0;
+    }
+}
+
+// A work item is (frame, 64 x th output tile in FRAME px): a static frame-major list walked by persistent workgroups, split over the
+// XCDs as in masks_group_kernel.  A workgroup
+//   1. lists the frame's instances whose frame-px box reaches the tile (the crop is exact in frame px: no margin),
+//   2. loads the tile's footprint in the cropped prototype grid (<= NPTS points; the launcher picks th so that it fits at every
+//      scale) straight into MFMA operand registers,
+//   3. per group of 16 listed instances: coefficient x prototype on MFMA (masks_group_kernel's operands: exact-f32 steps for fp32
+//      prototypes, the split-coefficient fp16 pair for fp16 ones), (sigmoid,) logits -> LDS,
+//   4. bilinear upsample (torch's fp32 taps and weights, its evaluation order), crop, threshold: a wave takes 16-row pieces of one
+//      instance, a lane is a column; bits: each row's ballot is 8 bytes, gathered into lane r and stored by 16 lanes at once.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p) {
+    constexpr bool F16 = sizeof(T) == 2;
+    constexpr int ROW = 6 + 32;
+    typedef typename std::conditional<F16, half8, f32x4>::type opv;
+    constexpr int NOP = F16 ? 1 : 2;
+    __shared__ uint4 s_co[MROUND][8];
+    __shared__ float4 s_box[MROUND];           // frame-px boxes
+    __shared__ float s_scale[MROUND];
+    __shared__ unsigned short s_list[MROUND];
+    __shared__ int s_n;
+    __shared__ float low[MG][NPTS];
+    const T* __restrict__ proto = (const T*)p.proto;
+    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
+    const int li = ln & 15, lg = ln >> 4;
+    const int tiles_x = (p.W0 + NTW - 1) / NTW, tiles_y = (p.H0 + p.th - 1) / p.th, tiles = tiles_x * tiles_y;
+    const int n = p.B * tiles;
+    const int nx = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jx = (int)blockIdx.x >> 3;
+    const int per = (n + 7) >> 3;
+    const int it1 = min(n, (xcd + 1) * per);
+    const float thr = p.mode == VTI_MASK_SIGMOID ? 0.5f : 0.0f;
+    for (int it = xcd * per + jx; it < it1; it += nx) {
+        const int b = it / tiles, t = it - b * tiles;
+        const int ty = t / tiles_x, tx = t - ty * tiles_x;
+        const int y0 = ty * p.th, x0 = tx * NTW;
+        const int off_b = p.offsets[b];
+        const int n_b = min(p.offsets[b + 1], p.capacity) - off_b;
+        if (n_b <= 0) continue;                                            // block-uniform
+        const int ncols = min(NTW, p.W0 - x0), nrows = min(p.th, p.H0 - y0);
+        int fcb, fw, frb, fh;
+        native_span(x0, ncols, p.col_contig, p.sx, p.inW, fcb, fw);
+        native_span(y0, nrows, p.row_contig, p.sy, p.inH, frb, fh);
+        if (fw * fh > NPTS) fh = NPTS / fw;                                // never (the launcher's bound); keeps `low` in range
+        const int npts = fw * fh;
+        // ---- footprint -> MFMA operand registers: lane (li, lg) holds point 16 m + li, channels of lane group lg
+        opv pb[NJ][NOP];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int m = wv + 4 * j;
+            if (16 * m < npts) {                                           // wave-uniform
+                int pt = 16 * m + li;
+                pt = pt < npts ? pt : npts - 1;                            // past the footprint: a valid address, never stored
+                const int fr = pt / fw, fc = pt - fr * fw;
+                const int py = p.top + native_src(fr, y0, p.row_contig, frb, p.sy, p.inH);
+                const int px = p.left + native_src(fc, x0, p.col_contig, fcb, p.sx, p.inW);
+                const T* pp = proto + ((size_t)(b * p.Hp + py) * p.Wp + px) * 32;
+                if constexpr (F16) pb[j][0] = *(const half8*)(pp + 8 * lg);
+                else { pb[j][0] = *(const f32x4*)(pp + 4 * lg); pb[j][1] = *(const f32x4*)(pp + 16 + 4 * lg); }
+            }
+        }
+        // ---- this lane's column: footprint taps and weights (lanes past the frame take the last column and store nothing)
+        const int xg = x0 + min(ln, ncols - 1);
+        const float fx = (float)(x0 + ln);
+        int k0, k1;
+        float wx1;
+        {
+            int i0, i1;
+            native_tap(xg, p.sx, p.inW, i0, i1, wx1);
+            if (p.col_contig) { k0 = i0 - fcb; k1 = i1 - fcb; }
+            else { k0 = 2 * (xg - x0); k1 = k0 + 1; }
+        }
+        const float wx0 = 1.0f - wx1;
+        // ... and, lane as row t of the tile, row t's footprint row offsets and weights (read back with readlane per row)
+        int ro0, ro1;
+        float wy1;
+        {
+            const int yt = y0 + min(ln, nrows - 1);
+            int i0, i1;
+            native_tap(yt, p.sy, p.inH, i0, i1, wy1);
+            if (p.row_contig) { ro0 = (i0 - frb) * fw; ro1 = (i1 - frb) * fw; }
+            else { ro0 = 2 * (yt - y0) * fw; ro1 = ro0 + fw; }
+        }
+        const float wy0 = 1.0f - wy1;
+        const float xe = (float)(x0 + ncols - 1), ye = (float)(y0 + nrows - 1);
+        for (int i0 = 0; i0 < n_b; i0 += MROUND) {
+            __syncthreads();                                               // previous round / item is done with the shared arrays
+            if (wv == 0) {
+                const int i = i0 + ln;
+                const size_t r = (size_t)b * p.max_det + (i < n_b ? i : n_b - 1);
+                const float4 bx = *(const float4*)(p.xyxy + r * 4);
+                const bool hit = i < n_b && bx.x <= xe && bx.z > (float)x0 && bx.y <= ye && bx.w > (float)y0;
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
+                if (ln == 0) s_n = __builtin_popcountll(bal);
+                if (hit) {
+                    const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+                    s_list[pos] = (unsigned short)ln;
+                    s_box[pos] = bx;
+                    const float* d = p.dets + r * ROW + 6;                 // rows are 152 bytes: 8-byte aligned
+                    float cf[32];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) { const float2 v = *(const float2*)(d + 2 * k); cf[2 * k] = v.x; cf[2 * k + 1] = v.y; }
+                    s_scale[pos] = mask_coef_operands<F16>(cf, s_co[pos]);
+                }
+            }
+            __syncthreads();
+            const int nlist = s_n;
+            for (int g0 = 0; g0 < nlist; g0 += MG) {
+                const int ng = min(MG, nlist - g0);
+                opv ca[2];
+                ca[0] = __builtin_bit_cast(opv, s_co[g0 + li][lg]);
+                ca[1] = __builtin_bit_cast(opv, s_co[g0 + li][4 + lg]);
+                float rs[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) rs[r] = s_scale[g0 + 4 * lg + r];
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const int m = wv + 4 * j;
+                    if (16 * m < npts) {
+                        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+                        if constexpr (F16) {
+                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ca[0], pb[j][0], acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ca[1], pb[j][0], acc, 0, 0, 0);
+                        } else {
+#pragma unroll
+                            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ca[q][k], pb[j][q][k], acc, 0, 0, 0);
+                        }
+                        const int pt = 16 * m + li;
+                        if (pt < npts) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {                  // rows >= ng hold stale instances: never read
+                                float v = F16 ? acc[r] * rs[r] : acc[r];
+                                if (p.mode == VTI_MASK_SIGMOID) v = 1.0f / (1.0f + expf(-v));
+                                low[4 * lg + r][pt] = v;
+                            }
+                        }
+                    }
+                }
+                __syncthreads();
+                // ---- upsample + crop + threshold + store: (instance, 16-row piece) pairs round-robin over the waves
+                const int npc = (nrows + 15) >> 4;
+                for (int pr = wv; pr < ng * npc; pr += 4) {
+                    const int u = pr / npc, c = pr - u * npc;
+                    const int slot = off_b + i0 + (int)s_list[g0 + u];
+                    const float4 bx = s_box[g0 + u];
+                    const bool colin = ln < ncols && fx >= bx.x && fx < bx.z;
+                    const float* L = &low[u][0];
+                    uint8_t* out = p.masks + (size_t)slot * p.slot_bytes;
+                    const int r0 = 16 * c, r1 = min(r0 + 16, nrows);
+                    unsigned wl = 0u, wh = 0u;
+                    for (int r = r0; r < r1; ++r) {
+                        const int y = y0 + r;
+                        const float fy = (float)y;
+                        if (!(fy >= bx.y && fy < bx.w)) continue;          // row outside the box: stays 0 (wave-uniform)
+                        const int o0 = __builtin_amdgcn_readlane(ro0, r), o1 = __builtin_amdgcn_readlane(ro1, r);
+                        const float h0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wy0), r));
+                        const float h1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wy1), r));
+                        // torch's order: h0 (w0 a + w1 b) + h1 (w0 c + w1 d)
+                        const float v = h0 * (wx0 * L[o0 + k0] + wx1 * L[o0 + k1]) + h1 * (wx0 * L[o1 + k0] + wx1 * L[o1 + k1]);
+                        const bool bit = colin && v > thr;
+                        if (p.packing == VTI_PACK_U8) {
+                            if (ln < ncols) out[(size_t)y * p.W0 + x0 + ln] = bit ? (uint8_t)1 : (uint8_t)0;
+                        } else {
+                            const unsigned long long m = __builtin_amdgcn_ballot_w64(bit);
+                            if (ln == r - r0) { wl = (unsigned)m; wh = (unsigned)(m >> 32); }
+                        }
+                    }
+                    if (p.packing != VTI_PACK_U8 && ln < r1 - r0)                // lane r: row r0 + r, 8 bytes (row_bytes % 8 == 0)
+                        *(uint2*)(out + (size_t)(y0 + r0 + ln) * p.row_bytes + 8 * tx) = make_uint2(wl, wh);
+                }
+                if (g0 + MG < nlist) __syncthreads();                      // the next group overwrites `low`
+            }
+        }
+    }
+}
+
+// footprint length bound along one axis for `n` output indices at scale s (see native_span), and the cheaper of the two forms
+static int native_axis(double s, int n, int in, int& contig) {
+    const int span = std::min(in, (int)std::floor(s * (n - 1) + 1e-3) + 3);
+    contig = span <= 2 * n ? 1 : 0;
+    return contig ? span : 2 * n;
+}
+
+hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto, int B, int max_det,
+                               int Hp, int Wp, int H0, int W0, int mode, int packing, uint8_t* masks, int capacity, int* offsets,
+                               void* ws, hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    int lay[6];
+    if (native_mask_layout(Hp, Wp, H0, W0, packing, lay)) return hipErrorInvalidValue;
+    if (packing == VTI_PACK_BITS && capacity > 0 && ((uintptr_t)masks & 7)) return hipErrorInvalidValue;     // 8-byte row pieces
+    NativeMaskParams p;
+    p.dets = dets; p.xyxy = xyxy; p.offsets = offsets; p.proto = proto; p.masks = masks;
+    p.slot_bytes = (size_t)lay[5];
+    p.B = B; p.max_det = max_det; p.Hp = Hp; p.Wp = Wp; p.H0 = H0; p.W0 = W0;
+    p.top = lay[0]; p.left = lay[2]; p.inH = lay[1] - lay[0]; p.inW = lay[3] - lay[2];
+    p.sy = (float)p.inH / (float)H0; p.sx = (float)p.inW / (float)W0;          // torch: (float)in / out
+    p.mode = mode; p.packing = packing; p.row_bytes = lay[4]; p.capacity = capacity;
+    // the tallest tile (<= 64 rows) whose footprint fits NPTS points: 64 rows at the reference call (14 x 14 points), 2 rows when
+    // both axes shrink (two taps per pixel: 128 x 4); one row always fits (<= 128 x 2)
+    const int fw = native_axis(p.sx, NTW, p.inW, p.col_contig);
+    p.th = 1;
+    for (int th = 64; th >= 1; th >>= 1) {
+        int rc;
+        if (fw * native_axis(p.sy, th, p.inH, rc) <= NPTS) { p.th = th; p.row_contig = rc; break; }
+    }
+    hipLaunchKernelGGL(mask_offsets_kernel, dim3(1), dim3(256), (size_t)(B + 1) * sizeof(int), st, counts, B, max_det, offsets, (int*)ws);
+    if (capacity <= 0) return hipGetLastError();
+    const size_t vecs = (size_t)capacity * p.slot_bytes / 16;
+    const int clear_grid = (int)std::max<size_t>(1, std::min<size_t>((vecs + 255) / 256, 2048));
+    hipLaunchKernelGGL(mask_clear_live_kernel, dim3(clear_grid), dim3(256), 0, st, offsets, B, capacity, p.slot_bytes, masks);
+    static int per_cu_dev[kMaxDevices][2] = {};
+    int* per_cu = per_cu_dev[current_device_slot()];
+    const int kidx = dtype == VTI_F16 ? 0 : 1;
+    if (!per_cu[kidx]) {
+        int nb = 0;
+        const void* fn = dtype == VTI_F16 ? (const void*)masks_native_kernel<half_t> : (const void*)masks_native_kernel<float>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) != hipSuccess || nb < 1) nb = 2;
+        per_cu[kidx] = nb > 4 ? 4 : nb;
+    }
+    const int grid = 256 * per_cu[kidx];
+    if (dtype == VTI_F16) hipLaunchKernelGGL(masks_native_kernel<half_t>, dim3(grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(masks_native_kernel<float>, dim3(grid), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

@@ -614,6 +614,40 @@ int32_t vti_masks(vti_ctx* c, const float* dets, const int32_t* counts, const vo
     return VTI_OK;
 }
 
+int32_t vti_mask_native_layout(const vti_ctx* c, int32_t H0, int32_t W0, int32_t packing, int32_t out[6]) {
+    vti_ctx* m = const_cast<vti_ctx*>(c);     // the error message slot
+    if (!c || !out) return fail(m, VTI_ERR_ARG, "vti_mask_native_layout: bad argument");
+    if (packing != VTI_PACK_U8 && packing != VTI_PACK_BITS) return fail(m, VTI_ERR_ARG, "vti_mask_native_layout: bad packing");
+    const vti_desc& d = c->plan.desc;
+    if (native_mask_layout(d.H / 4, d.W / 4, H0, W0, packing, out))
+        return fail(m, VTI_ERR_ARG, "vti_mask_native_layout: bad frame size (H0, W0 >= 1, slot below 2 GiB)");
+    return VTI_OK;
+}
+
+int32_t vti_masks_native(vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts, const void* proto, int32_t B,
+                         int32_t max_det, int32_t H0, int32_t W0, int32_t mode, int32_t packing, uint8_t* masks, int32_t capacity,
+                         int32_t* offsets, void* stream) {
+    if (!c || !dets || !xyxy || !counts || !proto || !offsets || B < 0 || max_det < 1 || capacity < 0 || (capacity && !masks))
+        return fail(c, VTI_ERR_ARG, "vti_masks_native: bad argument");
+    if ((mode != VTI_MASK_LOGIT && mode != VTI_MASK_SIGMOID) || (packing != VTI_PACK_U8 && packing != VTI_PACK_BITS))
+        return fail(c, VTI_ERR_ARG, "vti_masks_native: bad mode/packing");
+    const vti_desc& d = c->plan.desc;
+    int lay[6];
+    if (native_mask_layout(d.H / 4, d.W / 4, H0, W0, packing, lay)) return fail(c, VTI_ERR_ARG, "vti_masks_native: bad frame size");
+    if (packing == VTI_PACK_BITS && capacity && ((uintptr_t)masks & 7))
+        return fail(c, VTI_ERR_ARG, "vti_masks_native: bit-packed masks must be 8-byte aligned");
+    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_masks_native: workspace not set");
+    if (B > d.max_batch) return fail(c, VTI_ERR_ARG, "vti_masks_native: B out of range");
+    if (capacity > d.max_batch * kMaskSlotsPerFrame)
+        return fail(c, VTI_ERR_UNSUPPORTED, "vti_masks_native: capacity above max_batch*512 instances per call");
+    if (d.nm != 32) return fail(c, VTI_ERR_UNSUPPORTED, "vti_masks_native: only nm == 32 prototypes");
+    void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
+    if (int32_t drc = check_device(c, "vti_masks_native")) return drc;
+    VTI_HIP(c, launch_masks_native(d.dtype, dets, xyxy, counts, proto, B, max_det, d.H / 4, d.W / 4, H0, W0, mode, packing, masks,
+                                   capacity, offsets, mws, (hipStream_t)stream), "native mask kernel");
+    return VTI_OK;
+}
+
 int32_t vti_scale_boxes(vti_ctx* c, const float* dets, const int32_t* counts, int32_t B, int32_t max_det, int32_t H0,
                         int32_t W0, float* xyxy, void* stream) {
     if (!c || !dets || !counts || !xyxy || B < 0 || max_det < 1 || H0 < 1 || W0 < 1)
@@ -643,6 +677,12 @@ int32_t vti_predict(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, in
     if (!best) return fail(c, VTI_ERR_STATE, "vti_predict: workspace not set");
     if ((rc = vti_forward_scored(c, input, B, swap_rb, pred, proto, best, stream))) return rc;
     if ((rc = vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream))) return rc;
+    if (mask_mode & VTI_MASK_NATIVE) {     // frame-resolution masks need the frame-px boxes first
+        if (!xyxy) return fail(c, VTI_ERR_ARG, "vti_predict: VTI_MASK_NATIVE needs dev_xyxy");
+        if ((rc = vti_scale_boxes(c, dets, counts, B, max_det, H0, W0, xyxy, stream))) return rc;
+        return vti_masks_native(c, dets, xyxy, counts, proto, B, max_det, H0, W0, mask_mode & ~VTI_MASK_NATIVE, packing, masks,
+                                capacity, offsets, stream);
+    }
     if ((rc = vti_masks(c, dets, counts, proto, B, max_det, mask_mode, packing, masks, capacity, offsets, stream))) return rc;
     if (xyxy && (rc = vti_scale_boxes(c, dets, counts, B, max_det, H0, W0, xyxy, stream))) return rc;
     return VTI_OK;

@@ -219,6 +219,12 @@ hipError_t launch_masks(int dtype, const float* dets, const int* counts, const v
                         int nm, int Hp, int Wp, int H, int W, int mode, int packing, uint8_t* masks,
                         int capacity, int* offsets, void* ws, hipStream_t st);
 size_t masks_workspace_bytes(int capacity, int H, int W);
+// retina_masks (process_mask_native): out = {top, bottom, left, right, row_bytes, slot_bytes} of frame-size masks from Hp x Wp
+// prototypes (host only; -1 for shapes it cannot describe); the launcher needs the frame-px boxes of vti_scale_boxes
+int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]);
+hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto, int B, int max_det,
+                               int Hp, int Wp, int H0, int W0, int mode, int packing, uint8_t* masks, int capacity, int* offsets,
+                               void* ws, hipStream_t st);
 hipError_t launch_scale_boxes(const float* dets, const int* counts, int B, int max_det, int nm, int H, int W,
                               int H0, int W0, float* xyxy, hipStream_t st);
 hipError_t launch_mask_to_frame(const uint8_t* masks, int n, int H, int W, int H0, int W0, uint8_t* bitmaps,

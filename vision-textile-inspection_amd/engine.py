@@ -188,6 +188,32 @@ class Engine:
                                          _ptr(offsets), _stream()))
         return masks, offsets
 
+    # ---- retina_masks: frame-resolution masks (process_mask_native) -------------------------
+    def mask_native_layout(self, H0, W0, packing="bits"):
+        """Host only: how masks_native lays out an H0 x W0 frame's masks -> dict(top, bottom, left, right, row_bytes,
+        slot_bytes): the kept rows / columns of the prototype grid and the bytes per mask row and per slot."""
+        out = (C.c_int32 * 6)()
+        check(self._ctx, lib().vti_mask_native_layout(self._ctx, int(H0), int(W0), PACKINGS[packing], out))
+        return dict(zip(("top", "bottom", "left", "right", "row_bytes", "slot_bytes"), (int(v) for v in out)))
+
+    def masks_native(self, dets, counts, xyxy, proto, H0, W0, mode="logit", packing="bits", capacity=None, masks=None,
+                     offsets=None):
+        """Ultralytics process_mask_native (predict(retina_masks=True)): masks at the FRAME size from the frame-px boxes of
+        scale_boxes() -> (masks u8 [capacity,H0,row_bytes] (bits: row_bytes = 8*ceil(W0/64); u8: W0), offsets i32 [B+1]).
+        capacity=None reads the counts back first, as masks()."""
+        B, max_det = dets.shape[0], dets.shape[1]
+        if capacity is None:
+            capacity = int(counts.clamp(0, max_det).sum().item())
+        if masks is None:
+            rb = self.mask_native_layout(H0, W0, packing)["row_bytes"]
+            masks = torch.empty((capacity, H0, rb), dtype=torch.uint8, device=dets.device)
+        if offsets is None:
+            offsets = torch.empty((B + 1,), dtype=torch.int32, device=dets.device)
+        check(self._ctx, lib().vti_masks_native(self._ctx, _ptr(dets), _ptr(xyxy), _ptr(counts), _ptr(proto), B, max_det, int(H0),
+                                                int(W0), MASK_MODES[mode], PACKINGS[packing],
+                                                _ptr(masks) if capacity else C.c_void_p(0), capacity, _ptr(offsets), _stream()))
+        return masks, offsets
+
     def scale_boxes(self, dets, counts, H0, W0, xyxy=None):
         B, max_det = dets.shape[0], dets.shape[1]
         if xyxy is None:
@@ -195,16 +221,20 @@ class Engine:
         check(self._ctx, lib().vti_scale_boxes(self._ctx, _ptr(dets), _ptr(counts), B, max_det, H0, W0, _ptr(xyxy), _stream()))
         return xyxy
 
-    def alloc_outputs(self, B, max_det, capacity, packing="bits", device=None):
-        """Preallocated output set for predict_into (the no-sync, graph-friendly form)."""
+    def alloc_outputs(self, B, max_det, capacity, packing="bits", device=None, native_hw=None):
+        """Preallocated output set for predict_into (the no-sync, graph-friendly form).  native_hw=(H0, W0): the masks are
+        frame-resolution ones for predict_into(native=True) (mask_native_layout)."""
         dev = device or self.device
-        wb = self.W if packing == "u8" else self.W // 8
+        if native_hw is None:
+            mh, wb = self.H, (self.W if packing == "u8" else self.W // 8)
+        else:
+            mh, wb = native_hw[0], self.mask_native_layout(native_hw[0], native_hw[1], packing)["row_bytes"]
         return dict(
             pred=self.alloc_pred(B, dev),
             proto=torch.empty((B, self.H // 4, self.W // 4, self.nm), dtype=self.torch_dtype, device=dev),
             dets=torch.empty((B, max_det, 6 + self.nm), dtype=torch.float32, device=dev),
             counts=torch.empty((B,), dtype=torch.int32, device=dev),
-            masks=torch.empty((capacity, self.H, wb), dtype=torch.uint8, device=dev),
+            masks=torch.empty((capacity, mh, wb), dtype=torch.uint8, device=dev),
             offsets=torch.empty((B + 1,), dtype=torch.int32, device=dev),
             xyxy=torch.empty((B, max_det, 4), dtype=torch.float32, device=dev),
             input=torch.empty((B, self.H, self.W, 3), dtype=torch.uint8, device=dev),
@@ -212,14 +242,19 @@ class Engine:
         )
 
     def predict_into(self, frames, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True,
-                     mask_mode="logit", packing="bits"):
+                     mask_mode="logit", packing="bits", native=False):
         """Whole pipeline (letterbox -> net -> NMS -> masks -> scale_boxes) on the current stream with
-        no host synchronisation; `out` from alloc_outputs()."""
+        no host synchronisation; `out` from alloc_outputs().  native=True: scale_boxes -> frame-resolution masks
+        (retina_masks; `out` from alloc_outputs(native_hw=(H0, W0)))."""
         B, H0, W0, _ = frames.shape
         capacity = out["masks"].shape[0]
+        if native:
+            rb = self.mask_native_layout(H0, W0, packing)["row_bytes"]
+            if tuple(out["masks"].shape[1:]) != (H0, rb):
+                raise ValueError(f"native masks for {H0}x{W0} frames need alloc_outputs(native_hw=({H0}, {W0}), packing={packing!r})")
         check(self._ctx, lib().vti_predict(
             self._ctx, _ptr(frames), B, H0, W0, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
-            int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]),
+            int(bool(agnostic)), MASK_MODES[mask_mode] | (_lib.VTI_MASK_NATIVE if native else 0), PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]),
             _ptr(out["proto"]), _ptr(out["dets"]), _ptr(out["counts"]), _ptr(out["masks"]), capacity,
             _ptr(out["offsets"]), _ptr(out["xyxy"]), _stream()))
         return out
@@ -337,10 +372,12 @@ def h2_decode(t):
 
 
 def unpack_bits(bits, W):
-    """u8 [...,W/8] LSB-first -> u8 [...,W] of 0/1 (host-side convenience for bit-packed masks)."""
+    """u8 [...,R] LSB-first -> u8 [...,W] of 0/1 (host-side convenience for bit-packed masks).  R may be padded past W/8
+    (masks_native rows are 8*ceil(W/64) bytes): the columns from W on are dropped."""
     b = bits.unsqueeze(-1)
     sh = torch.arange(8, device=bits.device, dtype=torch.uint8)
-    return ((b >> sh) & 1).reshape(*bits.shape[:-1], W)
+    full = ((b >> sh) & 1).reshape(*bits.shape[:-1], bits.shape[-1] * 8)
+    return full if full.shape[-1] == W else full[..., :W]
 
 
 def to_numpy(t):

@@ -59,11 +59,12 @@ class Boxes:
 
 
 class Masks:
-    """Results.masks: `.data` is f32 0/1 [N,H,W] at the LETTERBOXED size, as Ultralytics returns it.  The engine writes
-    bit-packed masks (u8 [N,H,W/8]); they are expanded on the device the first time `.data` / `.data_u8` is read."""
+    """Results.masks: `.data` is f32 0/1 [N,H,W] at the LETTERBOXED size, as Ultralytics returns it, or [N,H0,W0] at the frame
+    size with predict(retina_masks=True).  The engine writes bit-packed masks (u8 [N,H,W/8]; retina: u8 [N,H0,8*ceil(W0/64)]);
+    they are expanded on the device the first time `.data` / `.data_u8` is read."""
 
     def __init__(self, bits, W, orig_shape):
-        self.bits = bits                 # u8 [N,H,W/8] device tensor, LSB-first
+        self.bits = bits                 # u8 [N,H,R] device tensor, LSB-first; W columns of the R*8 are real
         self._W = W
         self.orig_shape = orig_shape
         self._u8 = None
@@ -170,9 +171,10 @@ class YOLO:
 
     @torch.inference_mode()
     def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
-                agnostic_nms=False, swap_rb=True, **_ignored):
+                agnostic_nms=False, swap_rb=True, retina_masks=False, **_ignored):
         """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
-        ndarray sources."""
+        ndarray sources.  retina_masks=True: masks at the frame size, Ultralytics'
+        process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes."""
         if source is None:
             raise ValueError("predict() needs a source")
         frames = self._to_device_batch(source)
@@ -183,18 +185,22 @@ class YOLO:
         # masks for up to B * max_det instances -> scale_boxes); the counts are read once, at the end, to cut the Results.
         # The output set (~1 GB for 64 frames x 300 slots of 640x640 bit masks) is allocated once per (engine, B, max_det) and
         # reused by later calls; what a Results object keeps are COPIES of its own rows (a few KB .. MB per frame).
-        key = (id(eng), B, max_det)
+        native_hw = (H0, W0) if retina_masks else None
+        key = (id(eng), B, max_det, native_hw)
         o = self._outs.get(key)
         if o is None:
             self._outs.clear()              # one cached set at a time: a new shape replaces the old one
-            o = self._outs[key] = eng.alloc_outputs(B, max_det, B * max_det, "bits", frames.device)
-        eng.predict_into(frames, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits")
+            o = self._outs[key] = eng.alloc_outputs(B, max_det, B * max_det, "bits", frames.device, native_hw=native_hw)
+        eng.predict_into(frames, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks))
         dets, xyxy, masks = o["dets"], o["xyxy"], o["masks"]
         nonempty = None
-        if self.drop_empty_masks:           # m00 of every live slot straight from the bit-packed masks (vti_mask_stats_bits)
+        if self.drop_empty_masks and not retina_masks:     # m00 of every live slot straight from the bit-packed masks (vti_mask_stats_bits)
             nonempty = eng.mask_stats_bits(masks, H, W, offsets=o["offsets"])[:, 0] > 0
         cnt = o["counts"].cpu().tolist()
         off = o["offsets"].cpu().tolist()
+        if self.drop_empty_masks and retina_masks:         # native rows: pad bits are 0, so any set byte of a live slot is a pixel
+            live = min(off[-1], masks.shape[0])
+            nonempty = masks[:live].reshape(live, -1).amax(1) > 0
         out = []
         for b in range(B):
             n = cnt[b]
@@ -206,7 +212,7 @@ class YOLO:
                 n = int(data.shape[0])
             else:
                 mb, db = mb.clone(), db.clone()
-            m = Masks(mb, W, (H0, W0)) if n else None
+            m = Masks(mb, W0 if retina_masks else W, (H0, W0)) if n else None
             r = Results((H0, W0), self.names, Boxes(data, (H0, W0)), m, db)
             r._engine = eng
             out.append(r)
