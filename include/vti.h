@@ -218,6 +218,62 @@ int32_t vti_pixels_to_world(vti_ctx* ctx, const double* dev_uv, int32_t n, const
 int32_t vti_kmeans1d2(vti_ctx* ctx, const double* dev_values, const int32_t* dev_counts, int32_t B, int32_t max_n,
                       int32_t max_iters, int32_t* dev_labels, double* dev_centers, void* stream);
 
+/* ---- process_frame's measurement record on device (measurement.py:240-510, drawing left out) ------------------------- */
+/* Settings of vti_measure: the calibration (camera_calibration.json, extrinsics.json; R = cv2.Rodrigues(rvec), row-major) and
+ * config.py's measurement settings.  Defaults (config.py): stitch_id 0, fabric_id 1, roi_enabled 1, roi {10, 300, 1270, 760},
+ * min_stitches 3, max_px_distance 250, envelope_neighborhood 3, skip_cluster 0, two_row_threshold_px 30, kmeans_iters 10,
+ * frame_buffer 8.  drop_empty = 1 mirrors YOLO(drop_empty_masks=True): instances whose mask (as predict returns it) is empty do
+ * not exist.  frame_buffer is the host's smoothing window (the per-frame median over the last frame_buffer averages); vti_measure
+ * itself does not read it. */
+typedef struct {
+    double K[9], dist[5], R[9], t[3];
+    double max_px_distance;            /* keep a stitch when |cy - round(median envelope)| < this (measurement.py:419-420) */
+    double two_row_threshold_px;       /* skip_cluster: cy spread above this means two rows (measurement.py:378-386) */
+    int32_t stitch_id, fabric_id;      /* class ids, >= 0 and different */
+    int32_t roi_enabled;
+    int32_t roi[4];                    /* x_min, y_min, x_max, y_max in frame px; clamped to the frame, inactive if degenerate */
+    int32_t min_stitches;              /* >= 1: an average needs at least this many values */
+    int32_t envelope_neighborhood;     /* 0..64 columns either side of a stitch centre */
+    int32_t skip_cluster;              /* 0: 2-means row selection; 1: the median split */
+    int32_t kmeans_iters;              /* kmeans_1d_two_clusters' max_iters (the reference passes none: 10) */
+    int32_t drop_empty;
+    int32_t frame_buffer;
+} vti_measure_params;
+
+/* vti_measure's frame_i32 status and stitch_i32 flag bits. */
+enum { VTI_MEASURE_OK = 0, VTI_MEASURE_NO_FABRIC = 1, VTI_MEASURE_NO_STITCHES = 2 };
+enum { VTI_STITCH_KEPT = 1,       /* a stitch of stitch_meta: exists, class stitch_id, inside the ROI */
+       VTI_STITCH_MASK = 2,       /* moments / extents from its mask (else the int-box fall-backs) */
+       VTI_STITCH_SELECTED = 4,   /* in the selected row */
+       VTI_STITCH_NEAR = 8,       /* within max_px_distance of the envelope (any stitch, selected or not) */
+       VTI_STITCH_DIST = 16,      /* contributed to the edge distance (final set, edge and both points valid) */
+       VTI_STITCH_WIDTH = 32 };   /* contributed to the stitch width */
+/* Largest max_det vti_measure takes (the per-frame tables live in LDS). */
+#define VTI_MEASURE_MAX_DET 1000
+
+/* Host only: bytes of device scratch vti_measure needs for B frames, `capacity` mask slots and W0-px frames (0 on a bad argument). */
+int64_t vti_measure_scratch_bytes(const vti_ctx* ctx, int32_t B, int32_t capacity, int32_t W0);
+/* process_frame's measurement for B frames at once, from the outputs of one predict (vti_predict / vti_nms + vti_masks or
+ * vti_masks_native + vti_scale_boxes): per frame b the instances are slots offsets[b] .. offsets[b] + counts[b] in detection order,
+ * class dets[b,i,5], frame-px box dev_xyxy[b,i] (vti_scale_boxes).  native = 0: dev_masks are vti_masks' VTI_PACK_BITS slots at the
+ * ctx's H x W (16-byte aligned), nearest-resized to H0 x W0 as measurement.py:70-86 does; native = 1: the frame-size rows of
+ * vti_masks_native (8*ceil(W0/64) bytes, zero pad bits, 8-byte aligned).  A slot at or beyond `capacity` is an empty mask.  Masks
+ * are zero outside their box (grown by 8 letterbox px; frame-px rows [y1, y2) for native rows), as vti_masks writes them.
+ * dev_scratch: >= vti_measure_scratch_bytes(), 256-byte aligned.  Every argument check (VTI_ERR_ARG; a smaller scratch included)
+ * runs before the first HIP call.  Outputs (device):
+ *   frame_f64 [B,2]  avg_dist_mm, avg_width_mm (NaN for the reference's None)
+ *   frame_i32 [B,6]  status (VTI_MEASURE_*), n_stitch (stitch_meta), n_fabric (non-empty kept fabric masks), n_selected, n_dist
+ *                    (= the record's stitch_count when status is 0), n_width; n_selected, n_dist, n_width are 0 unless status is 0
+ *   stitch_f64 [capacity,7] (may be NULL)  cx, cy, left, right, width_mm, edge_y, dist_mm; NaN where not computed (widths, edges
+ *                    and distances only when status is 0, edges and distances only for the final set)
+ *   stitch_i32 [capacity,2] (may be NULL)  VTI_STITCH_* flags, rank in stitch_meta (-1: not a stitch)
+ * Per-slot rows are written for every slot offsets[b] + i (i < counts[b]) below capacity; other rows are left untouched.
+ * Three launches on `stream`; no host synchronisation.  Smoothing over frames (measurement.py:474-484) is the caller's. */
+int32_t vti_measure(vti_ctx* ctx, const vti_measure_params* params, const uint8_t* dev_masks, int32_t native, const float* dev_dets,
+                    const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets, int32_t B, int32_t max_det,
+                    int32_t capacity, int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
+                    int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
+
 /* ---- per-layer access for parity tests ------------------------------------------- */
 /* Copies the activation written by conv `i` of the last vti_forward into dev_out as
  * f32 NCHW [B,c2,h_out,w_out] (test hook; not on the hot path). */

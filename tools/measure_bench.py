@@ -1,0 +1,83 @@
+"""vti_measure cost: process_frame's measurement record for a batch, from letterbox-size bit masks (vti_masks) and from
+frame-size ones (vti_masks_native), on the SAME detections (synth_pred -> NMS -> scale_boxes), timed with device events after
+warm-up, next to the predict step it follows.
+    python3 tools/measure_bench.py [--dtype h2] [--iters 50] [--B 64] [--n-inst 50]
+Prints per mask form: us per call (the three launches), us per frame, and its share of one predict_into step (letterbox ->
+net -> NMS -> masks -> scale_boxes) at the same batch."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np
+import torch
+
+import vti_amd
+from gpu_util import frames_u8, synth_pred
+
+
+def timed(fn, iters, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(iters):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", default="h2")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--B", type=int, default=64)
+    ap.add_argument("--n-inst", type=int, default=50)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("measure_bench needs the GPU")
+    B, H0, W0, max_det = a.B, 960, 1280, 200
+    H, W = vti_amd.letterbox_shape(H0, W0, 960)
+    eng = vti_amd.Engine("n", 2, H=H, W=W, max_batch=B, dtype=a.dtype)
+    eng.load_weights(vti_amd.random_weights(eng, seed=1), 0)
+    cap = B * max_det
+    # the predict step this stage follows (reference call: conf 0.20, iou 0.25, max_det 200, imgsz 960)
+    frames = torch.from_numpy(frames_u8(B, H0, W0, 0)).cuda()
+    out = eng.alloc_outputs(B, max_det, cap, "bits", frames.device)
+    ms_pred = timed(lambda: eng.predict_into(frames, out, 0.20, 0.25, max_det), a.iters)
+    # realistic instance counts: planted detections of both classes with random-blob masks
+    rng = np.random.default_rng(0)
+    pred = torch.from_numpy(synth_pred(rng, B, 2, 32, eng.num_anchors, H=H, W=W, n_inst=a.n_inst)).cuda()
+    proto = torch.from_numpy(rng.standard_normal((B, H // 4, W // 4, 32)).astype(np.float32)).to(eng.torch_dtype).cuda()
+    dets, counts = eng.nms(pred, 0.25, 0.7, max_det)
+    xyxy = eng.scale_boxes(dets, counts, H0, W0)
+    params = vti_amd.MeasureParams.from_files(os.path.join(ROOT, "tests", "golden", "camera_calibration.json"),
+                                              os.path.join(ROOT, "tests", "golden", "extrinsics.json"))
+    live = int(counts.sum())
+    print(f"B={B} frames {W0}x{H0}, letterbox {W}x{H}, {a.dtype}; predict_into step {ms_pred * 1e3:.0f} us; "
+          f"measure on {live} instances ({live / B:.1f} per frame), capacity {cap}")
+    for native in (False, True):
+        rb = eng.mask_native_layout(H0, W0)["row_bytes"] if native else W // 8
+        masks = torch.empty((cap, H0 if native else H, rb), dtype=torch.uint8, device="cuda")
+        off = torch.empty((B + 1,), dtype=torch.int32, device="cuda")
+        if native:
+            eng.masks_native(dets, counts, xyxy, proto, H0, W0, "logit", "bits", capacity=cap, masks=masks, offsets=off)
+        else:
+            eng.masks(dets, counts, proto, "logit", "bits", capacity=cap, masks=masks, offsets=off)
+        o = dict(dets=dets, xyxy=xyxy, counts=counts, offsets=off, masks=masks)
+        res = eng.measure(o, params, H0, W0, native=native)
+        st = res["frame_i32"][:, 0].cpu().numpy()
+        ms = timed(lambda: eng.measure(o, params, H0, W0, native=native, result=res), a.iters)
+        ms_lean = timed(lambda: eng.measure(o, params, H0, W0, native=native, stitch_rows=False, result=res), a.iters)
+        name = "native (vti_masks_native rows)" if native else "letterbox (vti_masks bits)"
+        print(f"  {name:31s} {ms * 1e3:8.1f} us/call  {ms * 1e3 / B:6.2f} us/frame  {100 * ms / ms_pred:5.2f} % of the step"
+              f"  (records only: {ms_lean * 1e3:.1f} us)  status 0 in {int((st == 0).sum())}/{B} frames")
+
+
+if __name__ == "__main__":
+    main()

@@ -28,6 +28,20 @@ class VtiConvInfo(C.Structure):
                 ("lds_bytes", C.c_int32), ("fused", C.c_int32), ("persistent", C.c_int32)]
 
 
+class VtiMeasureParams(C.Structure):
+    """include/vti.h vti_measure_params."""
+    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("max_px_distance", C.c_double), ("two_row_threshold_px", C.c_double),
+                ("stitch_id", C.c_int32), ("fabric_id", C.c_int32), ("roi_enabled", C.c_int32), ("roi", C.c_int32 * 4),
+                ("min_stitches", C.c_int32), ("envelope_neighborhood", C.c_int32), ("skip_cluster", C.c_int32),
+                ("kmeans_iters", C.c_int32), ("drop_empty", C.c_int32), ("frame_buffer", C.c_int32)]
+
+
+VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES = 0, 1, 2
+VTI_STITCH_KEPT, VTI_STITCH_MASK, VTI_STITCH_SELECTED, VTI_STITCH_NEAR, VTI_STITCH_DIST, VTI_STITCH_WIDTH = 1, 2, 4, 8, 16, 32
+VTI_MEASURE_MAX_DET = 1000
+
+
 class VtiError(RuntimeError):
     """Raised for any non-zero vti_status (the reference catches every predict exception,
     measurement.py:207-216)."""
@@ -71,6 +85,9 @@ SIGNATURES = {
     "vti_envelope_bits": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "vti_pixels_to_world": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "vti_kmeans1d2": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "vti_measure_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
+    "vti_measure": (_I32, [_P, C.POINTER(VtiMeasureParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
+                           _P, _P, _P, _P, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),
     "vti_debug_conv2d": (_I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32,
                                 _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,

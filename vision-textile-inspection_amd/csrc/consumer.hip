@@ -6,6 +6,7 @@
 //     intersection, measurement.py:44-65) and the 1-D 2-means of measurement.py:88-113, in float64 as the reference.
 // All integer results are exact; the float64 ones follow the reference's operation order (-ffp-contract=off).
 #include <climits>
+#include <type_traits>
 
 #include "vti_internal.h"
 
@@ -22,13 +23,19 @@ __device__ __forceinline__ int nn_src(int d, double inv_scale, int ssize) {
 //   cx[sx] = #{x : sx(x) = sx}, xs[sx] = sum of those x, cy[sy], ys[sy] likewise,
 //   m00 = sum_set cy*cx,  m10 = sum_set cy*xs,  m01 = sum_set ys*cx,  min/max col = first/last x of the extreme set sx
 // (over set source pixels that have at least one destination row and column).  One workgroup per instance.
+// VW = 32-bit words per load (4: 16-byte loads, slots a multiple of 16 bytes; 2: 8-byte loads, for the native rows of
+// vti_masks_native, whose slots are only a multiple of 8 bytes).  RAW: raw[slot] = 1 iff any bit of the slot is set, the emptiness
+// of the mask as predict returns it (vti_measure's drop_empty), before the resize can skip set source pixels.
+template <int VW, bool RAW>
 __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ n_live,
-                                                              int H, int W, int H0, int W0, long long* __restrict__ stats) {
+                                                              int H, int W, int H0, int W0, long long* __restrict__ stats,
+                                                              int* __restrict__ raw) {
     extern __shared__ int tab[];            // cx[W] xs[W] xf[W] xl[W] cy[H] ys[H]
     int* cx = tab; int* xs = cx + W; int* xf = xs + W; int* xl = xf + W; int* cy = xl + W; int* ys = cy + H;
     const int tid = threadIdx.x, slot = blockIdx.x;
     if (n_live && slot >= *n_live) {        // a dead slot of a fixed-capacity buffer: the empty-mask answer, nothing read
         if (tid < 5) stats[(size_t)slot * 5 + tid] = tid < 3 ? 0 : -1;
+        if (RAW && tid == 0) raw[slot] = 0;
         return;
     }
     const bool ident = H0 == H && W0 == W;
@@ -51,10 +58,11 @@ __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __
     // a slot is H * W / 8 bytes, a multiple of 128 (H, W multiples of 32), and `bits` is 16-byte aligned (checked by the launcher):
     // 16-byte loads, four of them in flight per thread before the first word is looked at (the loop was one dependent 4-byte load
     // per trip: latency-bound at a third of what the masks' L2 / HBM residency gives)
-    const uint4* m4 = (const uint4*)(bits + (size_t)slot * H * wpr);
-    const int n4 = (H * wpr) >> 2;
+    using V = typename std::conditional<VW == 4, uint4, uint2>::type;
+    const V* m4 = (const V*)(bits + (size_t)slot * H * wpr);
+    const int n4 = (H * wpr) / VW;
     long long m00 = 0, m10 = 0, m01 = 0;
-    int mn = INT_MAX, mx = -1;
+    int mn = INT_MAX, mx = -1, seen = 0;
     auto word = [&](unsigned w, int sy, int x0) {
         if (!w) return;
         if (ident) {
@@ -80,20 +88,24 @@ __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __
     };
     constexpr int U = 4;
     for (int i0 = tid; i0 < n4; i0 += 256 * U) {
-        uint4 q[U];
+        V q[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i0 + 256 * u;
-            q[u] = i < n4 ? m4[i] : make_uint4(0u, 0u, 0u, 0u);
+            q[u] = i < n4 ? m4[i] : V{};
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (!(q[u].x | q[u].y | q[u].z | q[u].w)) continue;
-            const int i = (i0 + 256 * u) << 2;
-            int sy = i / wpr, c = i - sy * wpr;                           // word column inside the row; the four words may cross a row end
-            const unsigned ww[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+            const unsigned* ww = reinterpret_cast<const unsigned*>(&q[u]);
+            unsigned any = 0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < VW; ++k) any |= ww[k];
+            if (!any) continue;
+            if (RAW) seen = 1;
+            const int i = (i0 + 256 * u) * VW;
+            int sy = i / wpr, c = i - sy * wpr;                           // word column inside the row; the words may cross a row end
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
                 word(ww[k], sy, c << 5);
                 if (++c == wpr) { c = 0; ++sy; }
             }
@@ -102,15 +114,23 @@ __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __
     for (int o = 32; o > 0; o >>= 1) {
         m00 += __shfl_down(m00, o); m10 += __shfl_down(m10, o); m01 += __shfl_down(m01, o);
         mn = min(mn, __shfl_down(mn, o)); mx = max(mx, __shfl_down(mx, o));
+        if (RAW) seen |= __shfl_down(seen, o);
     }
     __shared__ long long r00[4], r10[4], r01[4];
-    __shared__ int rmn[4], rmx[4];
-    if ((tid & 63) == 0) { r00[tid >> 6] = m00; r10[tid >> 6] = m10; r01[tid >> 6] = m01; rmn[tid >> 6] = mn; rmx[tid >> 6] = mx; }
+    __shared__ int rmn[4], rmx[4], rsn[4];
+    if ((tid & 63) == 0) {
+        r00[tid >> 6] = m00; r10[tid >> 6] = m10; r01[tid >> 6] = m01; rmn[tid >> 6] = mn; rmx[tid >> 6] = mx;
+        if (RAW) rsn[tid >> 6] = seen;
+    }
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w) { m00 += r00[w]; m10 += r10[w]; m01 += r01[w]; mn = min(mn, rmn[w]); mx = max(mx, rmx[w]); }
+        for (int w = 1; w < 4; ++w) {
+            m00 += r00[w]; m10 += r10[w]; m01 += r01[w]; mn = min(mn, rmn[w]); mx = max(mx, rmx[w]);
+            if (RAW) seen |= rsn[w];
+        }
         long long* o = stats + (size_t)slot * 5;
         o[0] = m00; o[1] = m10; o[2] = m01; o[3] = m00 ? mn : -1; o[4] = mx;
+        if (RAW) raw[slot] = seen;
     }
 }
 
@@ -118,7 +138,8 @@ hipError_t launch_mask_stats_bits(const uint8_t* bits, int n, const int* n_live,
                                   hipStream_t st) {
     if (n == 0) return hipSuccess;
     if ((W & 31) || (H & 31) || ((uintptr_t)bits & 15) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024) return hipErrorInvalidValue;      // 16-byte loads
-    hipLaunchKernelGGL(mask_stats_bits_kernel, dim3(n), dim3(256), (size_t)(4 * W + 2 * H) * 4, st, (const unsigned*)bits, n_live, H, W, H0, W0, stats);
+    hipLaunchKernelGGL((mask_stats_bits_kernel<4, false>), dim3(n), dim3(256), (size_t)(4 * W + 2 * H) * 4, st, (const unsigned*)bits, n_live,
+                       H, W, H0, W0, stats, (int*)nullptr);
     return hipGetLastError();
 }
 
@@ -127,20 +148,35 @@ hipError_t launch_mask_stats_bits(const uint8_t* bits, int n, const int* n_live,
 // source pixel (sy(y), sx(x)) is set in ANY selected instance, -1 if none.  yl[sy] = last frame row that maps to sy (-1: none),
 // monotone in sy, so the answer is yl of the largest set source row.  A mask is zero outside its box grown by 8 px (two
 // prototype pixels of bilinear reach, the same bound mask_plan_kernel uses), so only those rows are read.
+// vti_measure adds two things (measurement.py:253-260, 280-289): an ROI filter on the frame-px boxes `xyxy` (roi_on = 0: none; an
+// instance is kept when the centre of its int-truncated box lies inside roi = {x_min, y_min, x_max, y_max}, bounds inclusive), and
+// the NATIVE form for the frame-size rows of vti_masks_native (wpr words per row, zero pad bits): there the resize is the identity
+// and a mask is zero outside the rows [y1, y2) of its frame-px box, so those bound the search.
+__device__ __forceinline__ bool roi_keeps(const float* bx, int4 roi) {
+    const long long x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];    // python int(): truncation
+    return 2LL * roi.x <= x1 + x2 && x1 + x2 <= 2LL * roi.z && 2LL * roi.y <= y1 + y2 && y1 + y2 <= 2LL * roi.w;
+}
+
+template <bool NATIVE>
 __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ offsets,
                                                             const float* __restrict__ dets, int max_det, int row, int capacity,
-                                                            int cls, int H, int W, int H0, int W0, int* __restrict__ envelope) {
-    extern __shared__ int yl[];             // [H]
+                                                            int cls, int H, int W, int H0, int W0, int* __restrict__ envelope,
+                                                            const float* __restrict__ xyxy, int roi_on, int4 roi, int native_wpr) {
+    extern __shared__ int yl[];             // [H] (not NATIVE)
     __shared__ int red[4][64];
     const int tid = threadIdx.x, b = blockIdx.y;
-    for (int i = tid; i < H; i += 256) yl[i] = -1;
-    __syncthreads();
-    const double ify = 1.0 / ((double)H0 / (double)H), ifx = 1.0 / ((double)W0 / (double)W);
-    for (int y = tid; y < H0; y += 256) atomicMax(&yl[nn_src(y, ify, H)], y);
-    __syncthreads();
+    if (!NATIVE) {
+        for (int i = tid; i < H; i += 256) yl[i] = -1;
+        __syncthreads();
+        const double ify = 1.0 / ((double)H0 / (double)H);
+        for (int y = tid; y < H0; y += 256) atomicMax(&yl[nn_src(y, ify, H)], y);
+        __syncthreads();
+    }
     const int x = blockIdx.x * 64 + (tid & 63), rg = tid >> 6;
-    const int sx = nn_src(x < W0 ? x : W0 - 1, ifx, W);
-    const int wpr = W >> 5;
+    const int xc = x < W0 ? x : W0 - 1;
+    const int sx = NATIVE ? xc : nn_src(xc, 1.0 / ((double)W0 / (double)W), W);
+    const int wpr = NATIVE ? native_wpr : W >> 5;
+    const int Hm = NATIVE ? H0 : H;         // rows of a mask slot
     const int s0 = offsets[b], s1 = min(offsets[b + 1], capacity);
     int env = -1;
     // the frame's instances of the wanted class, listed first (a thread per instance; the order is irrelevant to a max): the row
@@ -152,10 +188,13 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
         if (tid == 0) s_nsel = 0;
         __syncthreads();
         if (r0 + tid < s1) {
-            const float* d = dets + ((size_t)b * max_det + (r0 + tid - s0)) * row;
-            if (cls < 0 || (int)d[5] == cls) {
-                int ya = (int)floorf(d[1] - 8.f), yb = (int)ceilf(d[3] + 8.f);
-                ya = max(ya, 0); yb = min(yb, H - 1);
+            const size_t di = (size_t)b * max_det + (r0 + tid - s0);
+            const float* d = dets + di * row;
+            if ((cls < 0 || (int)d[5] == cls) && (!roi_on || roi_keeps(xyxy + di * 4, roi))) {
+                int ya, yb;
+                if (NATIVE) { ya = (int)floorf(xyxy[di * 4 + 1]); yb = (int)ceilf(xyxy[di * 4 + 3]); }
+                else { ya = (int)floorf(d[1] - 8.f); yb = (int)ceilf(d[3] + 8.f); }
+                ya = max(ya, 0); yb = min(yb, Hm - 1);
                 const int pos = atomicAdd(&s_nsel, 1);
                 s_sel[pos][0] = r0 + tid; s_sel[pos][1] = ya; s_sel[pos][2] = yb;
             }
@@ -164,9 +203,13 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
         const int nsel = s_nsel;
         for (int j = 0; j < nsel; ++j) {
             const int s = s_sel[j][0], ya = s_sel[j][1], yb = s_sel[j][2];
-            const unsigned* m = bits + (size_t)s * H * wpr + (sx >> 5);
+            const unsigned* m = bits + (size_t)s * Hm * wpr + (sx >> 5);
             for (int sy = yb - rg; sy >= ya; sy -= 4) {           // top of the search first: the first hit of a lane is its largest
-                if ((m[(size_t)sy * wpr] >> (sx & 31)) & 1u) { env = max(env, yl[sy]); if (yl[sy] >= 0) break; }
+                if ((m[(size_t)sy * wpr] >> (sx & 31)) & 1u) {
+                    const int y = NATIVE ? sy : yl[sy];
+                    env = max(env, y);
+                    if (y >= 0) break;
+                }
             }
         }
     }
@@ -179,8 +222,8 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
                                 int capacity, int cls, int H, int W, int H0, int W0, int* envelope, hipStream_t st) {
     if (B == 0) return hipSuccess;
     if ((W & 31) || ((uintptr_t)bits & 3) || (size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(envelope_bits_kernel, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)bits, offsets, dets,
-                       max_det, 6 + nm, capacity, cls, H, W, H0, W0, envelope);
+    hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)bits, offsets,
+                       dets, max_det, 6 + nm, capacity, cls, H, W, H0, W0, envelope, (const float*)nullptr, 0, make_int4(0, 0, 0, 0), 0);
     return hipGetLastError();
 }
 
@@ -192,11 +235,8 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
 //   s = -d / (n . ray); X_cam = s ray; X_world = R^T (X_cam - t); no point when |n . ray| < 1e-9.
 struct GeomParams { double fx, fy, cx, cy, k1, k2, p1, p2, k3; double R[9]; double t[3]; double n[3]; double d; };
 
-__global__ __launch_bounds__(256) void pixels_to_world_kernel(const double* __restrict__ uv, int n, GeomParams g,
-                                                               double* __restrict__ xyz, int* __restrict__ valid) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double u = uv[2 * i], v = uv[2 * i + 1];
+// One point; false where the reference returns None.  Shared by pixels_to_world_kernel and measure_frames_kernel.
+__device__ __forceinline__ bool pixel_to_world(const GeomParams& g, double u, double v, double o[3]) {
     const double ifx = 1.0 / g.fx, ify = 1.0 / g.fy;
     double x = (u - g.cx) * ifx, y = (v - g.cy) * ify;
     const double x0 = x, y0 = y;
@@ -213,23 +253,38 @@ __global__ __launch_bounds__(256) void pixels_to_world_kernel(const double* __re
     const bool ok = fabs(denom) >= 1e-9;
     const double s = -g.d / denom;
     const double c0 = s * x - g.t[0], c1 = s * y - g.t[1], c2 = s - g.t[2];
-    double* o = xyz + 3 * (size_t)i;
 #pragma unroll
     for (int k = 0; k < 3; ++k)                                          // R^T row k = column k of R
         o[k] = ok ? (g.R[k] * c0 + g.R[3 + k] * c1) + g.R[6 + k] * c2 : 0.0;
+    return ok;
+}
+
+__global__ __launch_bounds__(256) void pixels_to_world_kernel(const double* __restrict__ uv, int n, GeomParams g,
+                                                               double* __restrict__ xyz, int* __restrict__ valid) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double o[3];
+    const bool ok = pixel_to_world(g, uv[2 * i], uv[2 * i + 1], o);
+    double* out = xyz + 3 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = o[k];
     valid[i] = ok ? 1 : 0;
 }
 
-hipError_t launch_pixels_to_world(const double* uv, int n, const double* K, const double* dist, const double* R,
-                                  const double* t, double* xyz, int* valid, hipStream_t st) {
-    if (n == 0) return hipSuccess;
+static GeomParams make_geom(const double* K, const double* dist, const double* R, const double* t) {
     GeomParams g;
     g.fx = K[0]; g.fy = K[4]; g.cx = K[2]; g.cy = K[5];
     g.k1 = dist[0]; g.k2 = dist[1]; g.p1 = dist[2]; g.p2 = dist[3]; g.k3 = dist[4];
     for (int i = 0; i < 9; ++i) g.R[i] = R[i];
     for (int i = 0; i < 3; ++i) { g.t[i] = t[i]; g.n[i] = R[3 * i + 2]; }       // plane normal = third column of R (measurement.py:46)
     g.d = -((g.n[0] * g.t[0] + g.n[1] * g.t[1]) + g.n[2] * g.t[2]);            // measurement.py:47
-    hipLaunchKernelGGL(pixels_to_world_kernel, dim3((n + 255) / 256), dim3(256), 0, st, uv, n, g, xyz, valid);
+    return g;
+}
+
+hipError_t launch_pixels_to_world(const double* uv, int n, const double* K, const double* dist, const double* R,
+                                  const double* t, double* xyz, int* valid, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(pixels_to_world_kernel, dim3((n + 255) / 256), dim3(256), 0, st, uv, n, make_geom(K, dist, R, t), xyz, valid);
     return hipGetLastError();
 }
 
@@ -272,6 +327,30 @@ __device__ double np_pairwise_sum(const double* a, int n) {
     return ret;
 }
 
+// The loop of measurement.py:93-113 on one thread for n >= 2 values; lab0[0, n) must be 0 on entry (the initial `labels`).  Returns
+// 0 or 1: which of lab0 / lab1 holds the returned labels (the PREVIOUS assignment when the loop stops early); g0, g1: n doubles of
+// scratch each.  Shared by kmeans1d2_kernel and measure_frames_kernel.
+__device__ int kmeans1d2_serial(const double* vals, int n, int max_iters, int* lab0, int* lab1, double* g0, double* g1, double& c0,
+                                double& c1) {
+    c0 = vals[0]; c1 = vals[0];
+    for (int i = 1; i < n; ++i) { c0 = fmin(c0, vals[i]); c1 = fmax(c1, vals[i]); }
+    int cur = 0;                            // lab[cur] = `labels`, lab[cur ^ 1] = `new_labels`
+    for (int it = 0; it < max_iters; ++it) {
+        int* nl = cur ? lab0 : lab1;
+        int n1 = 0, k0 = 0, k1 = 0;
+        for (int i = 0; i < n; ++i) {
+            const int l = fabs(vals[i] - c1) < fabs(vals[i] - c0) ? 1 : 0;
+            nl[i] = l; n1 += l;
+            if (l) g1[k1++] = vals[i]; else g0[k0++] = vals[i];
+        }
+        if (n1 == 0 || n1 == n) break;
+        const double nc0 = np_pairwise_sum(g0, k0) / (double)k0, nc1 = np_pairwise_sum(g1, k1) / (double)k1;
+        if (nc0 == c0 && nc1 == c1) break;
+        c0 = nc0; c1 = nc1; cur ^= 1;
+    }
+    return cur;
+}
+
 __global__ __launch_bounds__(64) void kmeans1d2_kernel(const double* __restrict__ values, const int* __restrict__ counts, int max_n,
                                                        int max_iters, int* __restrict__ labels, double* __restrict__ centers) {
     extern __shared__ double sm[];          // vals[max_n] | group0[max_n] | group1[max_n]
@@ -286,28 +365,13 @@ __global__ __launch_bounds__(64) void kmeans1d2_kernel(const double* __restrict_
     for (int i = lane; i < max_n; i += 64) L[i] = 0;
     __syncthreads();
     if (lane != 0) return;                  // <= a few hundred values: the order-exact sums are serial anyway
-    double c0, c1;
     if (n < 2) {                            // measurement.py:90-91: all zeros, both centres = mean (NaN for an empty input, as numpy)
         const double m = n ? vals[0] : __builtin_nan("");
         centers[2 * b] = m; centers[2 * b + 1] = m;
         return;
     }
-    c0 = vals[0]; c1 = vals[0];
-    for (int i = 1; i < n; ++i) { c0 = fmin(c0, vals[i]); c1 = fmax(c1, vals[i]); }
-    int cur = 0;                            // lab[cur] = `labels`, lab[cur ^ 1] = `new_labels`
-    for (int it = 0; it < max_iters; ++it) {
-        int* nl = lab[cur ^ 1];
-        int n1 = 0, k0 = 0, k1 = 0;
-        for (int i = 0; i < n; ++i) {
-            const int l = fabs(vals[i] - c1) < fabs(vals[i] - c0) ? 1 : 0;
-            nl[i] = l; n1 += l;
-            if (l) g1[k1++] = vals[i]; else g0[k0++] = vals[i];
-        }
-        if (n1 == 0 || n1 == n) break;
-        const double nc0 = np_pairwise_sum(g0, k0) / (double)k0, nc1 = np_pairwise_sum(g1, k1) / (double)k1;
-        if (nc0 == c0 && nc1 == c1) break;
-        c0 = nc0; c1 = nc1; cur ^= 1;
-    }
+    double c0, c1;
+    const int cur = kmeans1d2_serial(vals, n, max_iters, lab[0], lab[1], g0, g1, c0, c1);
     for (int i = 0; i < n; ++i) L[i] = lab[cur][i];
     centers[2 * b] = c0; centers[2 * b + 1] = c1;
 }
@@ -318,6 +382,306 @@ hipError_t launch_kmeans1d2(const double* values, const int* counts, int B, int 
     if (max_n < 1 || max_n > 1024) return hipErrorInvalidValue;     // LDS tables; the reference caps detections at 200 (config.py:73)
     hipLaunchKernelGGL(kmeans1d2_kernel, dim3(B), dim3(64), (size_t)max_n * 3 * sizeof(double), st, values, counts, max_n, max_iters,
                        labels, centers);
+    return hipGetLastError();
+}
+
+// ---- process_frame's measurement record (measurement.py:240-472), one workgroup per frame -----------------------------------
+// Inputs: per-slot moments (mask_stats_bits_kernel, frame-size bitmap) and raw emptiness, and the frame's lower envelope of its
+// ROI-kept fabric masks (envelope_bits_kernel).  Steps, in the reference's order:
+//   1. instances in detection order -> the stitch list (ballot / prefix counts: the order feeds the pairwise sums and the 2-means)
+//      and the count of non-empty kept fabric masks;
+//   2. status: no fabric / empty union, then no stitches;
+//   3. a lane per stitch: centroid + extents or the int-box fall-backs, width (two points to the plane), the +-N envelope
+//      medians of the proximity test and of the edge, and the distance candidate (two more points);
+//   4. row selection: 2-means on one lane with the cluster means recomputed from the returned labels, or the median split;
+//   5. the final set (proximity, or the selected row when nothing is near), the ordered distance / width lists and their means.
+struct MeasureArgs {
+    GeomParams g;
+    const long long* stats; const int* raw; const int* envelope;
+    const float* dets; const float* xyxy; const int* counts; const int* offsets;
+    int max_det, row, capacity, W0;
+    int stitch_id, fabric_id, roi_on; int4 roi;
+    int min_stitches, nb, skip_cluster, kmeans_iters, drop_empty;
+    double max_px, two_row;
+    double* frame_f64; int* frame_i32; double* stitch_f64; int* stitch_i32;
+};
+
+// Exclusive rank of this thread's flag among the workgroup's (256 threads, thread order) and the total.
+__device__ __forceinline__ int block_rank(bool f, int* s_cnt, int& total) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long m = __ballot(f);
+    if (lane == 0) s_cnt[w] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int c = s_cnt[k]; off += k < w ? c : 0; total += c; }
+    __syncthreads();
+    return off + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// np.median of [env[clip(c + dx, 0, W0 - 1)] for |dx| <= nb if >= 0] (measurement.py:413-418, 441-445): false when empty.  At most
+// 2 nb + 1 values: the order statistics by counting (ties broken by position), no sort.
+__device__ bool env_median(const int* env, int W0, int c, int nb, double& med) {
+    int k = 0;
+    for (int dx = -nb; dx <= nb; ++dx) k += env[min(max(c + dx, 0), W0 - 1)] >= 0;
+    if (!k) return false;
+    const int q0 = (k - 1) >> 1, q1 = k >> 1;      // the two middle ranks (equal for odd k)
+    int v0 = 0, v1 = 0;
+    for (int a = -nb; a <= nb; ++a) {
+        const int va = env[min(max(c + a, 0), W0 - 1)];
+        if (va < 0) continue;
+        int r = 0;
+        for (int dx = -nb; dx <= nb; ++dx) {
+            const int v = env[min(max(c + dx, 0), W0 - 1)];
+            r += v >= 0 && (v < va || (v == va && dx < a));
+        }
+        if (r == q0) v0 = va;
+        if (r == q1) v1 = va;
+    }
+    med = (k & 1) ? (double)v1 : ((double)v0 + (double)v1) / 2.0;
+    return true;
+}
+
+__device__ __forceinline__ double dist_mm(const double* p, const double* q) {
+    const double d0 = p[0] - q[0], d1 = p[1] - q[1], d2 = p[2] - q[2];
+    return sqrt((d0 * d0 + d1 * d1) + d2 * d2) * 1000.0;
+}
+
+enum { F_FINAL = 64, F_CAND = 128 };   // kernel-internal flag bits (final set, distance computable), above the VTI_STITCH_* bits
+
+__global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
+    extern __shared__ double msm[];        // M = max_det: cy | width | dist | edge | g0 | g1 (f64), then idx | flags | lab0 | lab1 (i32)
+    const int M = a.max_det;
+    double* s_cy = msm; double* s_wd = s_cy + M; double* s_ds = s_wd + M; double* s_ed = s_ds + M; double* g0 = s_ed + M; double* g1 = g0 + M;
+    int* s_idx = (int*)(g1 + M); int* s_fl = s_idx + M; int* lab0 = s_fl + M; int* lab1 = lab0 + M;
+    __shared__ int s_cnt[4];
+    __shared__ long long s_es[4];
+    __shared__ int s_ec[4], s_pick[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
+    const int* env = a.envelope + (size_t)b * a.W0;
+    const double NaN = __builtin_nan("");
+    const int W0 = a.W0;
+
+    // 1. stitch list and fabric count (measurement.py:248-273)
+    int n_st = 0, n_fab = 0;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int i = c0 + tid, s = s0 + i;
+        bool st = false, fab = false;
+        if (i < n) {
+            const bool live = s >= 0 && s < a.capacity;
+            const long long m00 = live ? a.stats[(size_t)s * 5] : 0;
+            const bool raw = live && (a.raw ? a.raw[s] != 0 : m00 > 0);
+            const size_t di = (size_t)b * M + i;
+            const int cls = (int)a.dets[di * a.row + 5];
+            const bool keep = (!a.drop_empty || raw) && (!a.roi_on || roi_keeps(a.xyxy + di * 4, a.roi));
+            st = keep && cls == a.stitch_id;
+            fab = keep && cls == a.fabric_id && m00 > 0;
+            if (!st && live) {
+                if (a.stitch_f64) for (int k = 0; k < 7; ++k) a.stitch_f64[(size_t)s * 7 + k] = NaN;
+                if (a.stitch_i32) { a.stitch_i32[(size_t)s * 2] = 0; a.stitch_i32[(size_t)s * 2 + 1] = -1; }
+            }
+        }
+        int tot_st, tot_fab;
+        const int pos = block_rank(st, s_cnt, tot_st);
+        if (st) s_idx[n_st + pos] = i;
+        (void)block_rank(fab, s_cnt, tot_fab);
+        n_st += tot_st; n_fab += tot_fab;
+    }
+    // 2. the envelope's valid columns (their mean is fabric_mean_y, measurement.py:390-392: integer sum, exact)
+    long long es = 0;
+    int ec = 0;
+    for (int x = tid; x < W0; x += 256) { const int v = env[x]; if (v >= 0) { es += v; ++ec; } }
+    for (int o = 32; o > 0; o >>= 1) { es += __shfl_down(es, o); ec += __shfl_down(ec, o); }
+    if ((tid & 63) == 0) { s_es[tid >> 6] = es; s_ec[tid >> 6] = ec; }
+    __syncthreads();                        // also publishes s_idx
+    es = (s_es[0] + s_es[1]) + (s_es[2] + s_es[3]);
+    ec = (s_ec[0] + s_ec[1]) + (s_ec[2] + s_ec[3]);
+    const int status = (n_fab == 0 || ec == 0) ? VTI_MEASURE_NO_FABRIC : (n_st == 0 ? VTI_MEASURE_NO_STITCHES : VTI_MEASURE_OK);
+
+    // 3. per stitch (measurement.py:300-368, 408-420, 436-459)
+    for (int j = tid; j < n_st; j += 256) {
+        const int i = s_idx[j], s = s0 + i;
+        const bool live = s >= 0 && s < a.capacity;
+        const float* bx = a.xyxy + ((size_t)b * M + i) * 4;
+        const int x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];
+        double cx, cy, left, right;
+        int fl = VTI_STITCH_KEPT;
+        const long long* m = a.stats + (size_t)s * 5;
+        if (live && m[0] > 0) {
+            fl |= VTI_STITCH_MASK;
+            cx = (double)m[1] / (double)m[0]; cy = (double)m[2] / (double)m[0];
+            left = (double)m[3]; right = (double)m[4];
+        } else {
+            cx = (double)((long long)x1 + x2) / 2.0; cy = (double)((long long)y1 + y2) / 2.0;
+            left = (double)x1; right = (double)x2;
+        }
+        double wd = NaN, ds = NaN, ed = NaN;
+        if (status == VTI_MEASURE_OK) {
+            double pl[3], pr[3];
+            const bool okl = pixel_to_world(a.g, left, cy, pl), okr = pixel_to_world(a.g, right, cy, pr);
+            if (okl && okr) { wd = dist_mm(pr, pl); fl |= VTI_STITCH_WIDTH; }
+            const int c = (int)rint(cx);                                   // python round(): half to even
+            double med;
+            if (env_median(env, W0, c, a.nb, med) && fabs(cy - rint(med)) < a.max_px) fl |= VTI_STITCH_NEAR;
+            if (env_median(env, W0, min(max(c, 0), W0 - 1), a.nb, med)) {
+                ed = med;
+                double ps[3], pe[3];
+                const bool oks = pixel_to_world(a.g, cx, cy, ps), oke = pixel_to_world(a.g, cx, ed, pe);
+                if (oks && oke) { ds = dist_mm(ps, pe); fl |= F_CAND; }
+            }
+        }
+        s_cy[j] = cy; s_wd[j] = wd; s_ds[j] = ds; s_ed[j] = ed; s_fl[j] = fl;
+        lab0[j] = 0;
+        if (live && a.stitch_f64) {
+            double* o = a.stitch_f64 + (size_t)s * 7;
+            o[0] = cx; o[1] = cy; o[2] = left; o[3] = right;
+        }
+    }
+    __syncthreads();
+
+    // 4. row selection (measurement.py:370-406)
+    if (status == VTI_MEASURE_OK) {
+        if (n_st >= 2 && a.skip_cluster) {
+            for (int j = tid; j < n_st; j += 256) {                        // ranks -> the sorted centroids, in g0
+                const double v = s_cy[j];
+                int r = 0;
+                for (int k = 0; k < n_st; ++k) r += s_cy[k] < v || (s_cy[k] == v && k < j);
+                g0[r] = v;
+            }
+            __syncthreads();
+            const double med = (n_st & 1) ? g0[n_st >> 1] : (g0[(n_st >> 1) - 1] + g0[n_st >> 1]) / 2.0;
+            const bool two = g0[n_st - 1] - g0[0] > a.two_row;
+            for (int j = tid; j < n_st; j += 256)
+                if (!two || s_cy[j] >= med) s_fl[j] |= VTI_STITCH_SELECTED;
+        } else if (n_st >= 2) {
+            if (tid == 0) {
+                double c0, c1;
+                const int which = kmeans1d2_serial(s_cy, n_st, a.kmeans_iters, lab0, lab1, g0, g1, c0, c1);
+                const int* L = which ? lab1 : lab0;
+                int k0 = 0, k1 = 0;
+                for (int j = 0; j < n_st; ++j) { if (L[j]) g1[k1++] = s_cy[j]; else g0[k0++] = s_cy[j]; }
+                const double f = (double)es / (double)ec;
+                const double m0 = k0 ? np_pairwise_sum(g0, k0) / (double)k0 : 1e9, m1 = k1 ? np_pairwise_sum(g1, k1) / (double)k1 : 1e9;
+                s_pick[0] = fabs(m0 - f) < fabs(m1 - f) ? 0 : 1;
+                s_pick[1] = which;
+            }
+            __syncthreads();
+            const int* L = s_pick[1] ? lab1 : lab0;
+            for (int j = tid; j < n_st; j += 256)
+                if (L[j] == s_pick[0]) s_fl[j] |= VTI_STITCH_SELECTED;
+        } else {
+            for (int j = tid; j < n_st; j += 256) s_fl[j] |= VTI_STITCH_SELECTED;
+        }
+        __syncthreads();
+        // 5. final set (measurement.py:408-431): the selected stitches near the envelope, else all selected ones
+        bool near = false;
+        for (int j = tid; j < n_st; j += 256)
+            near |= (s_fl[j] & (VTI_STITCH_SELECTED | VTI_STITCH_NEAR)) == (VTI_STITCH_SELECTED | VTI_STITCH_NEAR);
+        near = __syncthreads_or(near);
+        for (int j = tid; j < n_st; j += 256) {
+            int fl = s_fl[j];
+            if ((fl & VTI_STITCH_SELECTED) && (!near || (fl & VTI_STITCH_NEAR))) {
+                fl |= F_FINAL;
+                if (fl & F_CAND) fl |= VTI_STITCH_DIST;
+            }
+            s_fl[j] = fl;
+        }
+        __syncthreads();
+    }
+    // ordered lists of the distances and widths (measurement.py:433-468) into g0 / g1
+    int n_d = 0, n_w = 0, n_sel = 0;
+    for (int c0 = 0; c0 < n_st; c0 += 256) {
+        const int j = c0 + tid;
+        const int fl = j < n_st ? s_fl[j] : 0;
+        int td, tw, ts;
+        const bool fd = fl & VTI_STITCH_DIST, fw = fl & VTI_STITCH_WIDTH;
+        const int pd = block_rank(fd, s_cnt, td);
+        if (fd) g0[n_d + pd] = s_ds[j];
+        const int pw = block_rank(fw, s_cnt, tw);
+        if (fw) g1[n_w + pw] = s_wd[j];
+        (void)block_rank(fl & VTI_STITCH_SELECTED, s_cnt, ts);
+        n_d += td; n_w += tw; n_sel += ts;
+        if (j < n_st) {
+            const int s = s0 + s_idx[j];
+            if (s >= 0 && s < a.capacity) {
+                if (a.stitch_f64) {
+                    double* o = a.stitch_f64 + (size_t)s * 7;
+                    o[4] = s_wd[j]; o[5] = (fl & F_FINAL) ? s_ed[j] : NaN; o[6] = (fl & VTI_STITCH_DIST) ? s_ds[j] : NaN;
+                }
+                if (a.stitch_i32) { a.stitch_i32[(size_t)s * 2] = fl & 63; a.stitch_i32[(size_t)s * 2 + 1] = j; }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.frame_f64[2 * b] = n_d >= a.min_stitches ? np_pairwise_sum(g0, n_d) / (double)n_d : NaN;      // measurement.py:469-472
+        a.frame_f64[2 * b + 1] = n_w >= a.min_stitches ? np_pairwise_sum(g1, n_w) / (double)n_w : NaN;
+        int* o = a.frame_i32 + 6 * b;
+        o[0] = status; o[1] = n_st; o[2] = n_fab; o[3] = n_sel; o[4] = n_d; o[5] = n_w;
+    }
+}
+
+void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& total) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    off[0] = 0;
+    off[1] = up((size_t)capacity * 5 * sizeof(long long));
+    off[2] = off[1] + up((size_t)capacity * sizeof(int));
+    total = off[2] + up((size_t)B * W0 * sizeof(int));
+}
+
+hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
+                          const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
+                          void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    size_t off[3], total;
+    measure_scratch_layout(B, capacity, W0, off, total);
+    long long* stats = (long long*)((char*)scratch + off[0]);
+    int* raw = (int*)((char*)scratch + off[1]);
+    int* env = (int*)((char*)scratch + off[2]);
+    const int* n_live = offsets + B;
+    // measurement.py:220-238: the ROI clamped to the frame, inactive when degenerate
+    const int rx1 = max(0, min(p.roi[0], W0 - 1)), ry1 = max(0, min(p.roi[1], H0 - 1));
+    const int rx2 = max(0, min(p.roi[2], W0 - 1)), ry2 = max(0, min(p.roi[3], H0 - 1));
+    const bool roi_on = p.roi_enabled && rx1 < rx2 && ry1 < ry2;
+    const int4 roi = make_int4(rx1, ry1, rx2, ry2);
+    const int wpr = native ? 2 * ((W0 + 63) / 64) : W / 32;
+    if (capacity > 0) {
+        if (native) {           // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
+            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
+                               32 * wpr, H0, 32 * wpr, stats, (int*)nullptr);
+        } else {
+            if ((W & 31) || (H & 31) || ((uintptr_t)masks & 15) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                               (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (native)
+        hipLaunchKernelGGL(envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets, dets,
+                           max_det, 6 + nm, capacity, p.fabric_id, H0, W0, H0, W0, env, xyxy, roi_on ? 1 : 0, roi, wpr);
+    else {
+        if ((size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
+                           offsets, dets, max_det, 6 + nm, capacity, p.fabric_id, H, W, H0, W0, env,
+                           xyxy, roi_on ? 1 : 0, roi, 0);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    MeasureArgs a;
+    a.g = make_geom(p.K, p.dist, p.R, p.t);
+    a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
+    a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
+    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.W0 = W0;
+    a.stitch_id = p.stitch_id; a.fabric_id = p.fabric_id; a.roi_on = roi_on ? 1 : 0; a.roi = roi;
+    a.min_stitches = p.min_stitches; a.nb = p.envelope_neighborhood; a.skip_cluster = p.skip_cluster;
+    a.kmeans_iters = p.kmeans_iters; a.drop_empty = p.drop_empty;
+    a.max_px = p.max_px_distance; a.two_row = p.two_row_threshold_px;
+    a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
+    const size_t lds = (size_t)max_det * (6 * sizeof(double) + 4 * sizeof(int));
+    hipLaunchKernelGGL(measure_frames_kernel, dim3(B), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

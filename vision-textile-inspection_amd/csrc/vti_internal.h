@@ -242,6 +242,11 @@ hipError_t launch_pixels_to_world(const double* uv, int n, const double* K, cons
                                   const double* t, double* xyz, int* valid, hipStream_t st);
 hipError_t launch_kmeans1d2(const double* values, const int* counts, int B, int max_n, int max_iters, int* labels,
                             double* centers, hipStream_t st);
+// vti_measure: per-slot moments, the ROI-kept fabric envelope and the per-frame record; scratch carved as measure_scratch_layout
+void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& total);    // stats i64 [cap,5] | raw i32 [cap] | env i32 [B,W0]
+hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
+                          const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
+                          void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st);
 
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
 void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,

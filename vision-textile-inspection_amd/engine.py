@@ -303,6 +303,41 @@ class Engine:
                                                  masks_bits.shape[0], int(cls), H0, W0, _ptr(envelope), _stream()))
         return envelope
 
+    # ---- process_frame's measurement record (measurement.py:240-510) -------------------------------
+    def measure_scratch_bytes(self, B, capacity, W0):
+        return int(lib().vti_measure_scratch_bytes(self._ctx, int(B), int(capacity), int(W0)))
+
+    def measure(self, out, params, H0, W0, native=False, stitch_rows=True, result=None):
+        """The per-frame measurement of measurement.py's process_frame for every frame of an alloc_outputs() set that predict_into()
+        (or nms/masks/scale_boxes) filled: vti_measure.  params: a measure.MeasureParams (or a VtiMeasureParams).  native=True: the
+        masks are frame-size rows (predict_into(native=True)).  Returns device tensors, no host synchronisation:
+        dict(frame_f64 [B,2] avg_dist_mm, avg_width_mm (NaN = None), frame_i32 [B,6] status, n_stitch, n_fabric, n_selected, n_dist,
+        n_width, and with stitch_rows the per-slot stitch_f64 [capacity,7], stitch_i32 [capacity,2]).  `result`: the same dict
+        preallocated (any of its tensors reused)."""
+        cp = params.to_c() if hasattr(params, "to_c") else params
+        dets, masks = out["dets"], out["masks"]
+        B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
+        dev = dets.device
+        r = dict(result or {})
+        if "frame_f64" not in r:
+            r["frame_f64"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        if "frame_i32" not in r:
+            r["frame_i32"] = torch.empty((B, 6), dtype=torch.int32, device=dev)
+        if stitch_rows:
+            if "stitch_f64" not in r:
+                r["stitch_f64"] = torch.empty((capacity, 7), dtype=torch.float64, device=dev)
+            if "stitch_i32" not in r:
+                r["stitch_i32"] = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+        need = self.measure_scratch_bytes(B, capacity, W0)
+        ws = getattr(self, "_measure_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._measure_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        check(self._ctx, lib().vti_measure(
+            self._ctx, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]),
+            _ptr(out["counts"]), _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(),
+            _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream()))
+        return r
+
     # ---- test hook ---------------------------------------------------------------------
     def debug_conv_output(self, i, B):
         t = self.conv_table()[i]

@@ -1,0 +1,133 @@
+"""process_frame's measurement record (measurement.py:240-510) as one batched device stage.
+
+    params = MeasureParams.from_files("camera_calibration.json", "extrinsics.json")        measurement.py:130-140
+    sm = StitchMeasurer(YOLO(path), params)
+    records = sm.process_frames(frames)          # one dict per frame, as process_frame returns (main.py:211-226)
+
+The per-frame work (ROI filter, moments, fabric envelope, widths, row selection, proximity filter, distances, averages) runs in
+libvti's vti_measure on the predict output set that is already on the device; the host reads back B small records once and keeps
+only the reference's stateful smoothing (the two frame_buffer-long deques and their medians, measurement.py:474-484).  Nothing is
+drawn: the annotated frame the reference also returns is out of scope.
+"""
+import ctypes as C
+import dataclasses
+import json
+from collections import deque
+from datetime import datetime
+
+import numpy as np
+import torch
+
+from ._lib import VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VtiMeasureParams
+from .consumer import rodrigues
+
+ERRORS = {VTI_MEASURE_NO_FABRIC: "Fabric not detected", VTI_MEASURE_NO_STITCHES: "No stitches detected"}
+
+
+@dataclasses.dataclass
+class MeasureParams:
+    """Calibration + config.py's measurement settings (the defaults are config.py's).  K f64 [3,3], dist f64 [5], R f64 [3,3]
+    (cv2.Rodrigues of the extrinsics' rvec), t f64 [3].  roi = (x_min, y_min, x_max, y_max) in frame px."""
+    K: np.ndarray
+    dist: np.ndarray
+    R: np.ndarray
+    t: np.ndarray
+    stitch_id: int = 0
+    fabric_id: int = 1
+    roi: tuple = (10, 300, 1270, 760)
+    roi_enabled: bool = True
+    min_stitches: int = 3
+    max_px_distance: float = 250
+    envelope_neighborhood: int = 3
+    skip_cluster: bool = False
+    two_row_threshold_px: float = 30
+    frame_buffer: int = 8
+    kmeans_iters: int = 10
+    drop_empty: bool = False
+
+    @classmethod
+    def from_files(cls, calib_path, extr_path, **kw):
+        """measurement.py:130-140: camera_matrix / dist_coeffs from the intrinsics file, rvec / tvec from the extrinsics file."""
+        with open(calib_path) as f:
+            calib = json.load(f)
+        with open(extr_path) as f:
+            extr = json.load(f)
+        K = np.array(calib["camera_matrix"], dtype=np.float64)
+        dist = np.array(calib["dist_coeffs"], dtype=np.float64).ravel()
+        rvec = np.array(extr["rvec"], dtype=np.float64).reshape(3, 1)
+        t = np.array(extr["tvec"], dtype=np.float64).reshape(3,)
+        return cls(K=K, dist=dist, R=rodrigues(rvec), t=t, **kw)
+
+    def to_c(self):
+        p = VtiMeasureParams()
+        for name, n in (("K", 9), ("dist", 5), ("R", 9), ("t", 3)):
+            a = np.ascontiguousarray(np.asarray(getattr(self, name), dtype=np.float64).ravel())
+            if a.size != n:
+                raise ValueError(f"MeasureParams.{name}: expected {n} values, got {a.size}")
+            setattr(p, name, (C.c_double * n)(*a.tolist()))
+        p.max_px_distance = float(self.max_px_distance)
+        p.two_row_threshold_px = float(self.two_row_threshold_px)
+        p.stitch_id, p.fabric_id = int(self.stitch_id), int(self.fabric_id)
+        p.roi_enabled = int(bool(self.roi_enabled))
+        p.roi = (C.c_int32 * 4)(*(int(v) for v in self.roi))
+        p.min_stitches = int(self.min_stitches)
+        p.envelope_neighborhood = int(self.envelope_neighborhood)
+        p.skip_cluster = int(bool(self.skip_cluster))
+        p.kmeans_iters = int(self.kmeans_iters)
+        p.drop_empty = int(bool(self.drop_empty))
+        p.frame_buffer = int(self.frame_buffer)
+        return p
+
+
+class StitchMeasurer:
+    """StitchMeasurementApp.process_frame without the camera and the drawing: model = a vti_amd YOLO, params = MeasureParams.
+    The smoothing deques live here, so consecutive calls continue one stream of frames, as the reference's app does."""
+
+    def __init__(self, model, params, frame_buffer=8):
+        self.model = model
+        self.params = dataclasses.replace(params, frame_buffer=int(frame_buffer), drop_empty=bool(model.drop_empty_masks))
+        self.frame_buf_dist = deque(maxlen=frame_buffer)
+        self.frame_buf_width = deque(maxlen=frame_buffer)
+        self._cp = self.params.to_c()
+        self._res = {}
+
+    @torch.inference_mode()
+    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
+        """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them.  The reference predicts on the RGB conversion
+        with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
+        Returns one record per frame, in frame order, with the smoothing applied frame by frame."""
+        eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks)
+        key = (id(o), B)
+        res = self._res.get(key)
+        if res is None:           # one buffer for both records: a single device -> host read
+            buf = torch.empty(B * 16 + B * 24, dtype=torch.uint8, device=o["dets"].device)
+            res = dict(buf=buf, frame_f64=buf[:B * 16].view(torch.float64).view(B, 2),
+                       frame_i32=buf[B * 16:].view(torch.int32).view(B, 6))
+            self._res = {key: res}
+        eng.measure(o, self._cp, H0, W0, native=bool(retina_masks), stitch_rows=False, result=res)
+        host = res["buf"].cpu().numpy()
+        f64 = host[:B * 16].view(np.float64).reshape(B, 2)
+        i32 = host[B * 16:].view(np.int32).reshape(B, 6)
+        return [self._record(f64[b], i32[b]) for b in range(B)]
+
+    def process_frame(self, frame, **kw):
+        """One frame: the record process_frame returns (without the annotated image)."""
+        return self.process_frames(np.asarray(frame)[None], **kw)[0]
+
+    def _record(self, f64, i32):
+        """measurement.py:285-287, 333-337 (errors: nothing appended) and 469-510 (averages -> deques -> medians)."""
+        status = int(i32[0])
+        if status in ERRORS:
+            return {'edge_distance_mm': None, 'stitch_width_mm': None, 'stitch_count': 0, 'timestamp': datetime.now(),
+                    'error': ERRORS[status]}
+        avg_dist = None if np.isnan(f64[0]) else float(f64[0])
+        avg_width = None if np.isnan(f64[1]) else float(f64[1])
+        smooth_dist = smooth_width = None
+        if avg_dist is not None:
+            self.frame_buf_dist.append(avg_dist)
+            smooth_dist = float(np.median(self.frame_buf_dist))
+        if avg_width is not None:
+            self.frame_buf_width.append(avg_width)
+            smooth_width = float(np.median(self.frame_buf_width))
+        return {'edge_distance_mm': smooth_dist, 'stitch_width_mm': smooth_width, 'stitch_count': int(i32[4]),
+                'timestamp': datetime.now()}

@@ -169,12 +169,10 @@ class YOLO:
         dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
         return t.to(dev, non_blocking=True).contiguous()
 
-    @torch.inference_mode()
-    def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
-                agnostic_nms=False, swap_rb=True, retina_masks=False, **_ignored):
-        """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
-        ndarray sources (SURVEY section 8 row A2).  retina_masks=True: masks at the frame size, Ultralytics'
-        process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes."""
+    def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks):
+        """The device half of predict(): enqueues the whole pipeline into the cached output set and returns
+        (engine, output set, (B, H0, W0), letterbox (H, W)) without reading anything back (predict() and
+        measure.StitchMeasurer both start here)."""
         if source is None:
             raise ValueError("predict() needs a source")
         frames = self._to_device_batch(source)
@@ -192,6 +190,15 @@ class YOLO:
             self._outs.clear()              # one cached set at a time: a new shape replaces the old one
             o = self._outs[key] = eng.alloc_outputs(B, max_det, B * max_det, "bits", frames.device, native_hw=native_hw)
         eng.predict_into(frames, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks))
+        return eng, o, (B, H0, W0), (H, W)
+
+    @torch.inference_mode()
+    def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
+                agnostic_nms=False, swap_rb=True, retina_masks=False, **_ignored):
+        """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
+        ndarray sources (SURVEY section 8 row A2).  retina_masks=True: masks at the frame size, Ultralytics'
+        process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes."""
+        eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
         dets, xyxy, masks = o["dets"], o["xyxy"], o["masks"]
         nonempty = None
         if self.drop_empty_masks and not retina_masks:     # m00 of every live slot straight from the bit-packed masks (vti_mask_stats_bits)
