@@ -274,6 +274,36 @@ int32_t vti_measure(vti_ctx* ctx, const vti_measure_params* params, const uint8_
                     int32_t capacity, int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
                     int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
 
+/* ---- Results.masks.xy on device: instance polygons in frame pixels ---------------------------------------------------- */
+/* Ultralytics masks2segments + scale_coords as restated by the package's polygons.py, bit for bit: per mask the outer border of
+ * every 8-connected component (traced from its top-most, then left-most pixel; pixels outside H x W, the pad bits of padded rows
+ * included, are background), CHAIN_APPROX_SIMPLE-compressed, then mapped to the H0 x W0 frame as scale_coords((H, W), pts,
+ * (H0, W0)): gain and pad in double, each rounded to f32 once, (x - pad) / gain in f32 with correctly rounded division, clipped
+ * to [0, W0] and [0, H0].  Unlike OpenCV's RETR_EXTERNAL, a component inside a hole of another one has a border of its own.
+ * VTI_POLY_LARGEST: the contour with the most vertices (ties: the first in raster order of the start pixels); VTI_POLY_CONCAT:
+ * every contour, in raster order of the start pixels.  An empty mask has 0 vertices. */
+#define VTI_POLY_LARGEST 0
+#define VTI_POLY_CONCAT  1
+/* Status word: the first int32 of dev_scratch after a vti_mask_polygons call has run (0 = ok). */
+enum { VTI_POLY_OK = 0,
+       VTI_POLY_ERR_BOUND = 1,    /* a labelling or border-following loop reached its bound (size-derived); points not written */
+       VTI_POLY_ERR_RANGE = 2 };  /* the total vertex count is above INT32_MAX; offsets saturate, points not written */
+/* Host only: device scratch bytes vti_mask_polygons needs for H x W masks with row_bytes bytes per row (0 on a bad argument).
+ * It depends on neither the mask count nor the contents: 128 labelling areas of 8 * H * ceil(W/2) + 4 * (H + 1) bytes, plus 8 * H
+ * * ceil(W/64) bytes each when the mask does not fit in LDS (H * ceil(W/64) * 8 > 156 KiB).  736 x 960: 362 MB; 960 x 1280: 630 MB. */
+int64_t vti_mask_polygons_scratch_bytes(const vti_ctx* ctx, int32_t H, int32_t W, int32_t row_bytes);
+/* dev_masks_bits: u8 [n, H, row_bytes] LSB-first bit masks, W <= 8 * row_bytes real columns: vti_masks' VTI_PACK_BITS slots
+ * (row_bytes = W/8) or vti_masks_native's rows (row_bytes = 8*ceil(W0/64), W = W0).  dev_n_live (may be NULL): slots at and beyond
+ * *dev_n_live are not read and have 0 vertices (&dev_offsets[B] of vti_masks).  1 <= H, W <= 16384, H * W <= 2^26.
+ * dev_point_offsets i32 [n+1] always receives the exclusive scan of the per-slot vertex counts; dev_points f32 [max_points, 2]
+ * (x, y) receives slot i's vertices at rows offsets[i] .. offsets[i+1] only when offsets[n] <= max_points (otherwise nothing is
+ * written there: call again with a larger buffer).  dev_scratch: >= vti_mask_polygons_scratch_bytes(), 256-byte aligned; its
+ * first int32 is the status word (VTI_POLY_*) once the work has run.  Every argument check (VTI_ERR_ARG) runs before the first
+ * HIP call.  Three launches on `stream` (count, scan, write); no host synchronisation. */
+int32_t vti_mask_polygons(vti_ctx* ctx, const uint8_t* dev_masks_bits, int32_t n, const int32_t* dev_n_live, int32_t H, int32_t W,
+                          int32_t row_bytes, int32_t H0, int32_t W0, int32_t strategy, void* dev_scratch, size_t scratch_bytes,
+                          int32_t* dev_point_offsets, float* dev_points, int64_t max_points, void* stream);
+
 /* ---- per-layer access for parity tests ------------------------------------------- */
 /* Copies the activation written by conv `i` of the last vti_forward into dev_out as
  * f32 NCHW [B,c2,h_out,w_out] (test hook; not on the hot path). */

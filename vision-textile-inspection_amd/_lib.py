@@ -41,6 +41,9 @@ VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES = 0, 1, 2
 VTI_STITCH_KEPT, VTI_STITCH_MASK, VTI_STITCH_SELECTED, VTI_STITCH_NEAR, VTI_STITCH_DIST, VTI_STITCH_WIDTH = 1, 2, 4, 8, 16, 32
 VTI_MEASURE_MAX_DET = 1000
 
+VTI_POLY_LARGEST, VTI_POLY_CONCAT = 0, 1
+VTI_POLY_OK, VTI_POLY_ERR_BOUND, VTI_POLY_ERR_RANGE = 0, 1, 2
+
 
 class VtiError(RuntimeError):
     """Raised for any non-zero vti_status (the reference catches every predict exception,
@@ -88,6 +91,8 @@ SIGNATURES = {
     "vti_measure_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_measure": (_I32, [_P, C.POINTER(VtiMeasureParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
                            _P, _P, _P, _P, _P]),
+    "vti_mask_polygons_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
+    "vti_mask_polygons": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),
     "vti_debug_conv2d": (_I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32,
                                 _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,

@@ -794,6 +794,42 @@ int32_t vti_measure(vti_ctx* c, const vti_measure_params* p, const uint8_t* mask
     return VTI_OK;
 }
 
+static bool poly_sizes_ok(int32_t H, int32_t W, int32_t row_bytes) {
+    return H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= (int64_t)1 << 26 && row_bytes >= 1 &&
+           (int64_t)row_bytes * 8 >= W;
+}
+
+int64_t vti_mask_polygons_scratch_bytes(const vti_ctx* c, int32_t H, int32_t W, int32_t row_bytes) {
+    if (!c || !poly_sizes_ok(H, W, row_bytes)) return 0;
+    PolyLayout L;
+    mask_polygons_layout(H, W, row_bytes, L);
+    return (int64_t)L.total;
+}
+
+int32_t vti_mask_polygons(vti_ctx* c, const uint8_t* masks, int32_t n, const int32_t* n_live, int32_t H, int32_t W, int32_t row_bytes,
+                          int32_t H0, int32_t W0, int32_t strategy, void* scratch, size_t scratch_bytes, int32_t* offsets,
+                          float* points, int64_t max_points, void* stream) {
+    // every check comes before the first HIP call
+    if (!c) return fail(c, VTI_ERR_ARG, "vti_mask_polygons: null ctx");
+    if (n < 0 || !poly_sizes_ok(H, W, row_bytes) || H0 < 1 || W0 < 1 || max_points < 0)
+        return fail(c, VTI_ERR_ARG, "vti_mask_polygons: bad size (n, max_points >= 0; 1 <= H, W <= 16384, H * W <= 2^26; "
+                                    "row_bytes * 8 >= W; H0, W0 >= 1)");
+    if (strategy != VTI_POLY_LARGEST && strategy != VTI_POLY_CONCAT)
+        return fail(c, VTI_ERR_ARG, "vti_mask_polygons: strategy must be VTI_POLY_LARGEST or VTI_POLY_CONCAT");
+    if (!offsets || (n && !masks) || (max_points && !points)) return fail(c, VTI_ERR_ARG, "vti_mask_polygons: null pointer");
+    if (!scratch || ((uintptr_t)scratch & 255))
+        return fail(c, VTI_ERR_ARG, "vti_mask_polygons: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_mask_polygons_scratch_bytes(c, H, W, row_bytes))
+        return fail(c, VTI_ERR_ARG, "vti_mask_polygons: scratch smaller than vti_mask_polygons_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_mask_polygons")) return drc;
+    // scale_coords' gain and pad, in double as polygons.py (Python floats); the kernels round each to f32 once
+    const double gain = std::min((double)H / (double)H0, (double)W / (double)W0);
+    const double padx = ((double)W - (double)W0 * gain) / 2, pady = ((double)H - (double)H0 * gain) / 2;
+    VTI_HIP(c, launch_mask_polygons(masks, n, n_live, H, W, row_bytes, gain, padx, pady, H0, W0, strategy, scratch, offsets, points,
+                                    (long long)max_points, (hipStream_t)stream), "mask_polygons kernels");
+    return VTI_OK;
+}
+
 int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void* stream) {
     int32_t rc = check_ready(c, B, "vti_debug_conv_output");
     if (rc) return rc;

@@ -248,6 +248,21 @@ hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int
                           const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
                           void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st);
 
+// polygons.hip: vti_mask_polygons (Results.masks.xy).  The grid is VTI_POLY_WORKGROUPS persistent workgroups, each with its own
+// labelling area of the scratch: parent i32 [R_max] | runs u32 [R_max] | row_start i32 [H+1] | image u64 [H, WW] (only when the
+// image does not fit in LDS), R_max = H * ceil(W/2) (the most runs an H x W mask can have).  The scratch starts with a 256-byte
+// header whose first int32 is the status word.
+#define VTI_POLY_WORKGROUPS 128
+struct PolyLayout {
+    int WW;                    // 64-bit words per image row
+    bool in_lds;               // the H x WW image is kept in LDS
+    size_t img_bytes, off_runs, off_rows, off_img, area_bytes, total;
+};
+void mask_polygons_layout(int H, int W, int row_bytes, PolyLayout& L);
+hipError_t launch_mask_polygons(const uint8_t* masks, int n, const int* n_live, int H, int W, int row_bytes, double gain,
+                                double padx, double pady, int H0, int W0, int strategy, void* scratch, int* offsets, float* points,
+                                long long max_points, hipStream_t st);
+
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
 void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,
                      int th = 0, int tw = 0, int wn = 0, int nrep = 0, bool allow_pk = true);

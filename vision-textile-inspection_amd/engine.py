@@ -20,6 +20,7 @@ DTYPES = {"fp16": _lib.VTI_F16, "f16": _lib.VTI_F16, "half": _lib.VTI_F16,
 _DTYPE_NAME = {_lib.VTI_F16: "fp16", _lib.VTI_F32: "fp32", _lib.VTI_H2: "h2"}
 MASK_MODES = {"logit": _lib.VTI_MASK_LOGIT, "sigmoid": _lib.VTI_MASK_SIGMOID}
 PACKINGS = {"u8": _lib.VTI_PACK_U8, "bits": _lib.VTI_PACK_BITS}
+POLY_STRATEGIES = {"largest": _lib.VTI_POLY_LARGEST, "concat": _lib.VTI_POLY_CONCAT}
 
 
 def _ptr(t):
@@ -337,6 +338,50 @@ class Engine:
             _ptr(out["counts"]), _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(),
             _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream()))
         return r
+
+    # ---- Results.masks.xy: instance polygons in frame pixels (vti_mask_polygons) -------------------------------------------
+    def mask_polygons_scratch_bytes(self, H, W, row_bytes):
+        return int(lib().vti_mask_polygons_scratch_bytes(self._ctx, int(H), int(W), int(row_bytes)))
+
+    def mask_polygons(self, masks_bits, W, H0, W0, strategy="largest", offsets=None):
+        """Ultralytics masks2segments + scale_coords (polygons.py, bit for bit) on the device.  masks_bits: u8 [n,H,row_bytes] LSB-first
+        with W real columns (masks()' bits: row_bytes = W/8; masks_native()'s rows: W = W0).  strategy "largest" (the outer contour with
+        the most vertices) or "concat" (every outer contour).  `offsets` (i32 [B+1] from masks()): slots at and beyond offsets[B] are not
+        read and have empty polygons.  -> (points f32 [P,2] (x, y) in H0 x W0 frame pixels, point_offsets i32 [n+1]): slot i's polygon
+        is points[point_offsets[i]:point_offsets[i+1]].  `points` is a view of a buffer the engine keeps and reuses: valid until the next
+        call.  One host read (the vertex total and the status word); a second launch only when the kept buffer was too small."""
+        if strategy not in POLY_STRATEGIES:
+            raise ValueError(f"strategy must be one of {sorted(POLY_STRATEGIES)}, got {strategy!r}")
+        masks_bits = masks_bits.contiguous()
+        n, H, rb = masks_bits.shape
+        dev = masks_bits.device
+        need = self.mask_polygons_scratch_bytes(H, W, rb)
+        if need <= 0:
+            raise ValueError(f"mask_polygons: bad mask geometry H={H} W={W} row_bytes={rb}")
+        ws = getattr(self, "_poly_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            self._poly_ws = None                       # free the old scratch before the new one is allocated
+            ws = self._poly_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        pts = getattr(self, "_poly_points", None)
+        if pts is None or pts.device != dev:
+            pts = self._poly_points = torch.empty((1 << 16, 2), dtype=torch.float32, device=dev)
+        point_offsets = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+        n_live = C.c_void_p(offsets.data_ptr() + 4 * (offsets.numel() - 1)) if offsets is not None else C.c_void_p(0)
+
+        def launch(buf):
+            check(self._ctx, lib().vti_mask_polygons(self._ctx, _ptr(masks_bits) if n else C.c_void_p(0), n, n_live, H, int(W), rb,
+                                                     int(H0), int(W0), POLY_STRATEGIES[strategy], _ptr(ws), ws.numel(),
+                                                     _ptr(point_offsets), _ptr(buf), buf.shape[0], _stream()))
+        launch(pts)
+        total, status = torch.cat((point_offsets[n:], ws[:4].view(torch.int32))).tolist()
+        if status != _lib.VTI_POLY_OK:
+            raise _lib.VtiError(-4, f"vti_mask_polygons: status word {status} (1: a loop reached its bound, "
+                                    f"2: more than 2^31-1 vertices)")     # -4: VTI_ERR_HIP, an error found on the device
+        if total > pts.shape[0]:                       # the kept buffer was too small: grow it and run again
+            self._poly_points = None
+            pts = self._poly_points = torch.empty((max(total, 2 * pts.shape[0]), 2), dtype=torch.float32, device=dev)
+            launch(pts)
+        return pts[:total], point_offsets
 
     # ---- test hook ---------------------------------------------------------------------
     def debug_conv_output(self, i, B):

@@ -16,7 +16,6 @@ import numpy as np
 import torch
 
 from .engine import Engine, unpack_bits
-from .polygons import masks2segments, scale_coords
 from .weights import random_weights, unpack_container
 
 
@@ -63,13 +62,15 @@ class Masks:
     size with predict(retina_masks=True).  The engine writes bit-packed masks (u8 [N,H,W/8]; retina: u8 [N,H0,8*ceil(W0/64)]);
     they are expanded on the device the first time `.data` / `.data_u8` is read."""
 
-    def __init__(self, bits, W, orig_shape):
+    def __init__(self, bits, W, orig_shape, engine=None):
         self.bits = bits                 # u8 [N,H,R] device tensor, LSB-first; W columns of the R*8 are real
         self._W = W
         self.orig_shape = orig_shape
+        self._engine = engine            # the Engine that made the masks: .xy runs its vti_mask_polygons
         self._u8 = None
         self._f = None
         self._xy = None
+        self._xyn = None
 
     @property
     def data_u8(self):
@@ -86,12 +87,26 @@ class Masks:
     @property
     def xy(self):
         """One float32 [n,2] (x, y) polygon per instance in ORIGINAL frame pixels: the largest outer contour of the mask
-        (Ultralytics masks2segments + scale_coords; Utils/check_model.py:185-188 fills it).  Host side, computed on first use."""
+        (Ultralytics masks2segments + scale_coords; Utils/check_model.py:185-188 fills it).  Computed on the device on first use
+        (Engine.mask_polygons, bit-identical to polygons.py), then one copy to the host."""
         if self._xy is None:
-            H, W = self.bits.shape[1], self._W
-            segs = masks2segments(self.data_u8.cpu().numpy())
-            self._xy = [scale_coords((H, W), s, self.orig_shape) for s in segs]
+            if self._engine is None:
+                raise RuntimeError("Masks.xy needs the Engine that made the masks (Masks(..., engine=)); there is no host path")
+            n = self.bits.shape[0]
+            pts, off = self._engine.mask_polygons(self.bits, self._W, *self.orig_shape)
+            host = torch.cat((pts.reshape(-1).view(torch.int32), off)).cpu().numpy()     # one device -> host copy, bits as int32
+            p = host[:pts.numel()].view(np.float32).reshape(-1, 2)
+            o = host[pts.numel():]
+            self._xy = [p[o[i]:o[i + 1]] for i in range(n)]
         return self._xy
+
+    @property
+    def xyn(self):
+        """Ultralytics' normalised segments: xy divided by (W0, H0) in float32 (scale_coords(..., normalize=True))."""
+        if self._xyn is None:
+            wh = np.array((self.orig_shape[1], self.orig_shape[0]), dtype=np.float32)
+            self._xyn = [s / wh for s in self.xy]
+        return self._xyn
 
     def __len__(self):
         return self.bits.shape[0]
@@ -219,7 +234,7 @@ class YOLO:
                 n = int(data.shape[0])
             else:
                 mb, db = mb.clone(), db.clone()
-            m = Masks(mb, W0 if retina_masks else W, (H0, W0)) if n else None
+            m = Masks(mb, W0 if retina_masks else W, (H0, W0), eng) if n else None
             r = Results((H0, W0), self.names, Boxes(data, (H0, W0)), m, db)
             r._engine = eng
             out.append(r)

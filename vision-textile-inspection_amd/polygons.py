@@ -1,4 +1,8 @@
-"""`Results.masks.xy`: one polygon per instance, in ORIGINAL frame pixels (host side, off the hot path).
+"""`Results.masks.xy`: one polygon per instance, in ORIGINAL frame pixels -- the host SPECIFICATION of vti_mask_polygons.
+
+The product computes `Masks.xy` on the device (libvti.so `vti_mask_polygons`, csrc/polygons.hip, Engine.mask_polygons), bit for bit
+what the functions below return; they stay as the statement of the semantics and as the reference of tests/test_gpu_polygons.py
+(they are pure Python and take seconds on a frame-size mask, so the package never calls them).
 
 The reference reads `r.masks.xy[idx]` only as a fall-back when `masks.data` cannot be used
 (Utils/check_model.py:185-188, Utils/check_stitch_distance.py:115: `cv2.fillPoly` of the polygon).  Ultralytics builds it with
