@@ -245,7 +245,7 @@ size_t convfold_lds_bytes(int TH, int TW) {
     return 4 * (size_t)((npix + 15) & ~15) * 16 + (size_t)16 * 4 * 1024;
 }
 bool convfold_supported(int c_in, int c_mid, int c_out, int ntiles2) {
-    return c_in == c_mid && c_mid % 16 == 0 && c_out == 64 && c_in % 16 == 0 && c_in <= 64 && (ntiles2 == 1 || ntiles2 == 2 || ntiles2 == 4);
+    return c_in == c_mid && c_mid % 16 == 0 && c_out == 64 && c_in % 16 == 0 && c_in <= 64 && combo_has(FoldN2{}, ntiles2);
 }
 
 // NT = 512 (the h2 plan's choice): TWO groups of four phase waves on an 8 x 20 tile share one staged weight chunk.  The composed weights are
@@ -380,46 +380,6 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void convfold_kernel(const C
     conv_stage2<T, NREP, NREP2, true>(p, acc, pvalid, opy, opx, b, lane);
 }
 
-template <typename T>
-static hipError_t launch_convfold_t(const ConvParams& p, dim3 grid, size_t lds, hipStream_t st) {
-    if (p.nt == 512) {                  // 8 x 20 tiles, two pixel groups per phase (the plan's choice for 4-byte storage)
-        if constexpr (sizeof(T) == 4) {
-#define VTI_FOLD8(N2)                                                                                                  \
-            if (p.ntiles2 == N2) {                                                                                     \
-                auto k = convfold_kernel<T, N2, 512>;                                                                  \
-                static bool done_dev[kMaxDevices] = {};                                                                \
-                bool& done = done_dev[current_device_slot()];                                                          \
-                if (!done) {                                                                                           \
-                    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                    if (e != hipSuccess) return e;                                                                     \
-                    done = true;                                                                                       \
-                }                                                                                                      \
-                hipLaunchKernelGGL(k, grid, dim3(512), lds, st, p);                                                    \
-                return hipGetLastError();                                                                              \
-            }
-            VTI_FOLD8(1) VTI_FOLD8(2) VTI_FOLD8(4)
-#undef VTI_FOLD8
-        }
-        return hipErrorInvalidValue;
-    }
-#define VTI_FOLD(N2)                                                                                                   \
-    if (p.ntiles2 == N2) {                                                                                             \
-        auto k = convfold_kernel<T, N2>;                                                                               \
-        static bool done_dev[kMaxDevices] = {};                                                                        \
-        bool& done = done_dev[current_device_slot()];                                                                  \
-        if (!done) {                                                                                                   \
-            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess) return e;                                                                             \
-            done = true;                                                                                               \
-        }                                                                                                              \
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, st, p);                                                            \
-        return hipGetLastError();                                                                                      \
-    }
-    VTI_FOLD(1) VTI_FOLD(2) VTI_FOLD(4)
-#undef VTI_FOLD
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_convfold(int dtype, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     dim3 grid((unsigned)(p.B * p.tiles_y * p.tiles_x));
     if (grid.x == 0) return hipSuccess;
@@ -427,9 +387,19 @@ hipError_t launch_convfold(int dtype, const ConvParams& p, size_t lds_bytes, hip
     const int nthr = p.nt == 512 ? 512 : 256;
     if (p.TH * p.TW > (nthr / 256) * MREP * 16 || ((p.TH + 2) * (p.TW + 2) + 7) / 8 * 32 > nthr * 8 || p.Cout != 256 || !p.out2 || !p.fold)
         return hipErrorInvalidValue;
-    if (dtype == VTI_F16) return launch_convfold_t<half_t>(p, grid, lds_bytes, st);
-    if (dtype == VTI_H2) return launch_convfold_t<h2_t>(p, grid, lds_bytes, st);
-    return launch_convfold_t<float>(p, grid, lds_bytes, st);
+    return with_conv_type(dtype, [&](auto t) -> hipError_t {
+        using T = typename decltype(t)::type;
+        if (p.nt == 512) {              // 8 x 20 tiles, two pixel groups per phase (the plan's choice for 4-byte storage)
+            if constexpr (sizeof(T) == 4)
+                return combo_dispatch(FoldN2{}, [&](auto c) {
+                    return launch_lds<convfold_kernel<T, decltype(c)::v[0], 512>>(grid, dim3(512), lds_bytes, st, p);
+                }, p.ntiles2);
+            return hipErrorInvalidValue;
+        }
+        return combo_dispatch(FoldN2{}, [&](auto c) {
+            return launch_lds<convfold_kernel<T, decltype(c)::v[0]>>(grid, dim3(256), lds_bytes, st, p);
+        }, p.ntiles2);
+    });
 }
 
 // ---- stem conv (model.0): u8 HWC3 frame -> /255 -> 3x3 stride-2 conv, K = 27 padded to 32.
@@ -851,38 +821,16 @@ hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st) {
     dim3 grid((unsigned)stem_l1_grid(dtype, p.B * p.tiles_y * p.tiles_x));
     if (grid.x == 0) return hipSuccess;
     const size_t lds = stem_l1_lds_bytes(dtype);
-    if (dtype == VTI_F16) {
-        static bool attr16_dev[kMaxDevices] = {};
-        bool& attr16 = attr16_dev[current_device_slot()];
-        if (!attr16) {
-            hipError_t e = hipFuncSetAttribute((const void*)stem_l1_kernel<half_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            attr16 = true;
-        }
-        hipLaunchKernelGGL(stem_l1_kernel<half_t>, grid, dim3(256), lds, st, p);
-    } else if (dtype == VTI_H2) {
-        static bool attrh2_dev[kMaxDevices] = {};
-        bool& attrh2 = attrh2_dev[current_device_slot()];
-        if (!attrh2) {
-            hipError_t e = hipFuncSetAttribute((const void*)stem_l1_kernel<h2_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            attrh2 = true;
-        }
-        hipLaunchKernelGGL(stem_l1_kernel<h2_t>, grid, dim3(256), lds, st, p);
-    } else {
-        static bool attr_done_dev[kMaxDevices] = {};
-        bool& attr_done = attr_done_dev[current_device_slot()];
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)stem_l1_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            attr_done = true;
-        }
-        hipLaunchKernelGGL(stem_l1_kernel<float>, grid, dim3(256), lds, st, p);
-    }
-    return hipGetLastError();
+    return with_conv_type(dtype, [&](auto t) { return launch_lds<stem_l1_kernel<typename decltype(t)::type>>(grid, dim3(256), lds, st, p); });
 }
 
 size_t stem_lds_bytes(int TH, int TW) { return 1024 + (size_t)(2 * TH + 1) * ((((2 * TW + 1) * 3 + 6) >> 2) * 4); }
+
+// conv_kernel instantiations, (NREP, WN): 3x3 (s1 and s2) where WN * NREP <= 5 (the weight prefetch array is sized by it), 1x1 for
+// every split; stem_kernel: NREP
+using ConvTile3 = Combos<Ints<1, 1>, Ints<2, 1>, Ints<3, 1>, Ints<4, 1>, Ints<5, 1>, Ints<1, 2>, Ints<2, 2>, Ints<1, 4>>;
+using ConvTile1 = decltype(concat(ConvTile3{}, Combos<Ints<3, 2>, Ints<4, 2>, Ints<5, 2>, Ints<2, 4>, Ints<3, 4>, Ints<4, 4>, Ints<5, 4>>{}));
+using StemNrep = Combos<Ints<1>, Ints<2>, Ints<3>, Ints<4>, Ints<5>>;
 
 // Host-side check that a geometry fits the kernel's fixed register staging arrays.
 bool conv_cfg_fits(int ks, int stride, int mode, int TH, int TW, int WN, int NREP, int threads) {
@@ -891,45 +839,17 @@ bool conv_cfg_fits(int ks, int stride, int mode, int TH, int TW, int WN, int NRE
     const int AR = threads == 512 ? 6 : (stride == 2 ? 12 : 8);
     const int npix = patch_dim(TH, ks, stride, mode) * patch_dim(TW, ks, stride, mode);
     if (((npix + 7) / 8) * 32 > threads * AR) return false;     // input pieces per thread
-    return ks == 1 || WN * NREP <= 5;                        // 3x3 instantiations cover WN*NREP <= 5
+    return ks == 1 ? combo_has(ConvTile1{}, NREP, WN) : combo_has(ConvTile3{}, NREP, WN);
 }
 
-template <typename T, int KS, int S, int NREP, int WN, int NREP2 = 0, int NT = 256>
-static hipError_t launch_one(const ConvParams& p, dim3 grid, size_t lds, hipStream_t st) {
-    auto k = conv_kernel<T, KS, S, NREP, WN, NREP2, NT>;
-    static size_t lds_ok_dev[kMaxDevices] = {};
-    size_t& lds_ok = lds_ok_dev[current_device_slot()];
-    if (lds > 64 * 1024 && lds > lds_ok) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        lds_ok = 160 * 1024;
-    }
-    hipLaunchKernelGGL(k, grid, dim3(NT), lds, st, p);
-    return hipGetLastError();
-}
+bool conv_fusable(int nrep, int nrep2) { return combo_has(FusedPairs{}, nrep, nrep2); }
 
-// 3x3 kernels exist for WN*NREP <= 5 (the weight prefetch array is sized by it); 1x1 for every split.
 template <typename T, int KS, int S>
-static hipError_t launch_ks(int nrep, int wn, const ConvParams& p, dim3 grid, size_t lds, hipStream_t st) {
-#define VTI_L(N, W) if (nrep == N && wn == W) return launch_one<T, KS, S, N, W>(p, grid, lds, st);
-    VTI_L(1, 1) VTI_L(2, 1) VTI_L(3, 1) VTI_L(4, 1) VTI_L(5, 1) VTI_L(1, 2) VTI_L(2, 2) VTI_L(1, 4)
-    if constexpr (KS == 1) { VTI_L(3, 2) VTI_L(4, 2) VTI_L(5, 2) VTI_L(2, 4) VTI_L(3, 4) VTI_L(4, 4) VTI_L(5, 4) }
-#undef VTI_L
-    return hipErrorInvalidValue;
-}
-
-// (3x3 s1, NREP mid tiles) + fused (1x1, NREP2 out tiles): the pairs YOLOv8-seg's heads / proto need
-bool conv_fusable(int nrep, int nrep2) {
-    return (nrep == 2 && nrep2 == 2) || (nrep == 3 && nrep2 == 2) || (nrep == 4 && (nrep2 == 1 || nrep2 == 2 || nrep2 == 4)) ||
-           (nrep == 5 && nrep2 == 5) || (nrep == 4 && nrep2 == 5);
-}
-
-template <typename T>
-static hipError_t launch_fused(int nrep, int nrep2, const ConvParams& p, dim3 grid, size_t lds, hipStream_t st) {
-#define VTI_F(N, N2) if (nrep == N && nrep2 == N2) return p.nt == 512 ? launch_one<T, 3, 1, N, 1, N2, 512>(p, grid, lds, st) : launch_one<T, 3, 1, N, 1, N2>(p, grid, lds, st);
-    VTI_F(2, 2) VTI_F(3, 2) VTI_F(4, 1) VTI_F(4, 2) VTI_F(4, 4) VTI_F(4, 5) VTI_F(5, 5)
-#undef VTI_F
-    return hipErrorInvalidValue;
+static hipError_t launch_ks(int nrep, const ConvParams& p, dim3 grid, size_t lds, hipStream_t st) {
+    return combo_dispatch(std::conditional_t<KS == 1, ConvTile1, ConvTile3>{}, [&](auto c) {
+        using C = decltype(c);
+        return launch_lds<conv_kernel<T, KS, S, C::v[0], C::v[1]>>(grid, dim3(256), lds, st, p);
+    }, nrep, p.WN);
 }
 
 template <typename T>
@@ -937,19 +857,20 @@ static hipError_t launch_t(int ks, int stride, int nrep, int mode, const ConvPar
                            hipStream_t st) {
     if (p.ntiles2 > 0) {
         if (!(ks == 3 && stride == 1 && p.WN == 1 && mode == 0)) return hipErrorInvalidValue;
-        return launch_fused<T>(nrep, p.ntiles2, p, grid, lds, st);
+        return combo_dispatch(FusedPairs{}, [&](auto c) {
+            using C = decltype(c);
+            return p.nt == 512 ? launch_lds<conv_kernel<T, 3, 1, C::v[0], 1, C::v[1], 512>>(grid, dim3(512), lds, st, p)
+                               : launch_lds<conv_kernel<T, 3, 1, C::v[0], 1, C::v[1]>>(grid, dim3(256), lds, st, p);
+        }, nrep, p.ntiles2);
     }
-    if (mode == 1) {
-        switch (nrep) {
-#define VTI_STEM(N) case N: hipLaunchKernelGGL((stem_kernel<T, N>), grid, dim3(256), lds, st, p); return hipGetLastError();
-            VTI_STEM(1) VTI_STEM(2) VTI_STEM(3) VTI_STEM(4) VTI_STEM(5)
-#undef VTI_STEM
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (ks == 1 && stride == 1) return launch_ks<T, 1, 1>(nrep, p.WN, p, grid, lds, st);
-    if (ks == 3 && stride == 1) return launch_ks<T, 3, 1>(nrep, p.WN, p, grid, lds, st);
-    if (ks == 3 && stride == 2) return launch_ks<T, 3, 2>(nrep, p.WN, p, grid, lds, st);
+    if (mode == 1)
+        return combo_dispatch(StemNrep{}, [&](auto c) {
+            hipLaunchKernelGGL((stem_kernel<T, decltype(c)::v[0]>), grid, dim3(256), lds, st, p);
+            return hipGetLastError();
+        }, nrep);
+    if (ks == 1 && stride == 1) return launch_ks<T, 1, 1>(nrep, p, grid, lds, st);
+    if (ks == 3 && stride == 1) return launch_ks<T, 3, 1>(nrep, p, grid, lds, st);
+    if (ks == 3 && stride == 2) return launch_ks<T, 3, 2>(nrep, p, grid, lds, st);
     return hipErrorInvalidValue;
 }
 
@@ -966,9 +887,7 @@ hipError_t launch_conv(int dtype, int ks, int stride, int nrep, int mode, const 
     const int nwaves = p.nt == 512 ? 8 : 4;
     if ((p.nt != 256 && p.nt != 512) || (p.nt == 512 && p.ntiles2 == 0)) return hipErrorInvalidValue;     // 512 threads: fused towers only
     if (p.TH * p.TW > (nwaves / p.WN) * MREP * 16 || (p.WN != 1 && p.WN != 2 && p.WN != 4)) return hipErrorInvalidValue;
-    if (dtype == VTI_F16) return launch_t<half_t>(ks, stride, nrep, mode, p, grid, lds_bytes, st);
-    if (dtype == VTI_H2) return launch_t<h2_t>(ks, stride, nrep, mode, p, grid, lds_bytes, st);
-    return launch_t<float>(ks, stride, nrep, mode, p, grid, lds_bytes, st);
+    return with_conv_type(dtype, [&](auto t) { return launch_t<typename decltype(t)::type>(ks, stride, nrep, mode, p, grid, lds_bytes, st); });
 }
 
 }  // namespace vti

@@ -675,4 +675,34 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
     }
 }
 
+// ---- host-side launch plumbing of the conv families (conv.hip, conv_pk.hip)
+// A family's template instantiations are written down once, as a Combos list of Ints tuples (e.g. (NREP, WN)); the launcher
+// dispatches through it (combo_dispatch) and the planner's predicate asks it (combo_has).  A key outside the list is
+// hipErrorInvalidValue.
+template <int... V> struct Ints { static constexpr int v[] = {V...}; };
+template <typename... C> struct Combos {};
+template <typename... A, typename... B> Combos<A..., B...> concat(Combos<A...>, Combos<B...>) { return {}; }
+
+template <int... V, typename... K> constexpr bool ints_eq(Ints<V...>, K... key) { return ((V == key) && ...); }
+template <typename... C, typename... K> constexpr bool combo_has(Combos<C...>, K... key) { return (... || ints_eq(C{}, key...)); }
+// f(C{}) for the entry C that equals the key (a left fold: the instantiations are emitted in list order)
+template <typename... C, typename F, typename... K> hipError_t combo_dispatch(Combos<C...>, F&& f, K... key) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)(... || (ints_eq(C{}, key...) && (e = f(C{}), true)));
+    return e;
+}
+
+// (3x3 s1, NREP mid tiles) + fused (1x1, NREP2 out tiles): the pairs YOLOv8-seg's heads / proto need (per-tile and persistent kernels)
+using FusedPairs = Combos<Ints<2, 2>, Ints<3, 2>, Ints<4, 1>, Ints<4, 2>, Ints<4, 4>, Ints<4, 5>, Ints<5, 5>>;
+// ConvTranspose2d(2,2) folded into the following 3x3 + fused 1x1 (convfold_kernel, conv3_pk<..., FOLD>): the 1x1's NREP2
+using FoldN2 = Combos<Ints<1>, Ints<2>, Ints<4>>;
+
+// The conv families' storage type of a dtype: VTI_F16 -> half_t, VTI_H2 -> h2_t, otherwise float; f(Type<T>{}) launches.
+template <typename T> struct Type { using type = T; };
+template <typename F> hipError_t with_conv_type(int dtype, F&& f) {
+    if (dtype == VTI_F16) return f(Type<half_t>{});
+    if (dtype == VTI_H2) return f(Type<h2_t>{});
+    return f(Type<float>{});
+}
+
 }  // namespace vti

@@ -39,6 +39,15 @@ constexpr int PK_ROWS = 4;        // tile rows per M-wave: 4 x 20 = 80 pixels = 
 constexpr int PK_MAXD = 9;        // patch DMA instructions per wave and step (host checks)
 constexpr int PK_MAXD2 = 13;      // ... of the stride-2 kernel (its patch is ~4x the output tile)
 
+// conv3_pk instantiations, (NREP, WN): stride 1, stride 2; conv1_pk: stride 1's and (4, 4)
+using ConvPkS1 = Combos<Ints<1, 1>, Ints<2, 1>, Ints<3, 1>, Ints<4, 1>, Ints<5, 1>, Ints<1, 2>, Ints<2, 2>, Ints<3, 2>, Ints<4, 2>, Ints<1, 4>,
+                        Ints<2, 4>>;
+using ConvPkS2 = Combos<Ints<1, 4>, Ints<2, 2>, Ints<4, 1>, Ints<2, 1>, Ints<1, 2>>;
+using Conv1Pk = decltype(concat(ConvPkS1{}, Combos<Ints<4, 4>>{}));
+bool conv_pk_instantiated(int nrep, int wn) { return combo_has(ConvPkS1{}, nrep, wn); }
+bool conv_pk2_instantiated(int nrep, int wn) { return combo_has(ConvPkS2{}, nrep, wn); }
+bool conv1_pk_instantiated(int nrep, int wn) { return combo_has(Conv1Pk{}, nrep, wn); }
+
 // `depth` patch stages (2..4): the loaders run depth - 1 steps ahead.  Weights: K <= 2 chunks stay resident (1 or 2 buffers);
 // more chunks travel with the patches, one buffer per stage.
 static size_t pk_stage_bytes(int TH, int S) { return S == 2 ? (size_t)(2 * TH + 1) * 2 * PK_PWP * 64 : (size_t)(TH + 2) * PK_PWP * 64; }
@@ -47,7 +56,6 @@ size_t conv_pk2_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int 
     const int nwbuf = wstat ? nchunks : nchunks > 2 ? depth : (nchunks > 1 ? 2 : 1);
     return depth * pk_stage_bytes(TH, 2) + (size_t)nwbuf * WN * NREP * 9 * 1024 + (size_t)WN * NREP * 16 * 4;
 }
-bool conv_pk2_instantiated(int nrep, int wn) { return (nrep == 1 && wn == 4) || (nrep == 2 && wn == 2) || (nrep == 4 && wn == 1) || (nrep == 2 && wn == 1) || (nrep == 1 && wn == 2); }
 bool conv_pk2_fits(int TH, int WN, int NREP, int nchunks, int wstat) {
     if (TH % PK_ROWS || !conv_pk2_instantiated(NREP, WN)) return false;
     const int ncomp = (TH / PK_ROWS) * WN;
@@ -778,57 +786,6 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
     }
 }
 
-template <typename T, int NREP, int WN, int NREP2 = 0, bool FOLD = false, int S = 1>
-static hipError_t launch_pk_one(const ConvParams& p, dim3 grid, int threads, size_t lds, hipStream_t st) {
-    auto k = conv3_pk<T, NREP, WN, NREP2, FOLD, S>;
-    static bool attr_done_dev[kMaxDevices] = {};
-    bool& attr_done = attr_done_dev[current_device_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(k, grid, dim3(threads), lds, st, p);
-    return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t launch_pk_t(int nrep, const ConvParams& p, dim3 grid, int threads, size_t lds, hipStream_t st) {
-    if (p.ntiles2 > 0) {
-        if (p.WN != 1) return hipErrorInvalidValue;
-#define VTI_F(N, N2) if (nrep == N && p.ntiles2 == N2) return launch_pk_one<T, N, 1, N2>(p, grid, threads, lds, st);
-        VTI_F(2, 2) VTI_F(3, 2) VTI_F(4, 1) VTI_F(4, 2) VTI_F(4, 4) VTI_F(4, 5) VTI_F(5, 5)
-#undef VTI_F
-        return hipErrorInvalidValue;
-    }
-#define VTI_L(N, W) if (nrep == N && p.WN == W) return launch_pk_one<T, N, W>(p, grid, threads, lds, st);
-    VTI_L(1, 1) VTI_L(2, 1) VTI_L(3, 1) VTI_L(4, 1) VTI_L(5, 1) VTI_L(1, 2) VTI_L(2, 2) VTI_L(3, 2) VTI_L(4, 2) VTI_L(1, 4) VTI_L(2, 4)
-#undef VTI_L
-    return hipErrorInvalidValue;
-}
-
-bool conv_pk_instantiated(int nrep, int wn) {
-    return (wn == 1 && nrep >= 1 && nrep <= 5) || (wn == 2 && nrep >= 1 && nrep <= 4) || (wn == 4 && nrep >= 1 && nrep <= 2);
-}
-
-template <typename T, int NREP, int WN>
-static hipError_t launch_pk1_one(const ConvParams& p, dim3 grid, int threads, size_t lds, hipStream_t st) {
-    constexpr int CPS = sizeof(T) == 2 ? 1 : 2;            // chunks per step: the planner sets pk_cps to the same value
-    if (p.pk_cps != CPS) return hipErrorInvalidValue;
-    auto k = conv1_pk<T, NREP, WN, CPS>;
-    static bool attr_done_dev[kMaxDevices] = {};
-    bool& attr_done = attr_done_dev[current_device_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(k, grid, dim3(threads), lds, st, p);
-    return hipGetLastError();
-}
-
-bool conv1_pk_instantiated(int nrep, int wn) { return conv_pk_instantiated(nrep, wn) || (wn == 4 && nrep == 4); }
-
 bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps) {
     const int ncomp = nwm * WN;
     if (nwm < 1 || ncomp > 4 || depth < 2 || depth > 8 || cps < 1 || cps > 2) return false;
@@ -837,14 +794,6 @@ bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat,
     const int per_step = cps * ((npieces + ncomp - 1) / ncomp + (wstat ? 0 : (WN * NREP + ncomp - 1) / ncomp));
     if (per_step * (depth - 2) > 63) return false;                     // counted s_waitcnt range
     return conv1_pk_lds_bytes(nwm, WN, NREP, nchunks, depth, wstat, cps) <= 160 * 1024;
-}
-
-template <typename T>
-static hipError_t launch_pk1_t(int nrep, const ConvParams& p, dim3 grid, int threads, size_t lds, hipStream_t st) {
-#define VTI_L(N, W) if (nrep == N && p.WN == W) return launch_pk1_one<T, N, W>(p, grid, threads, lds, st);
-    VTI_L(1, 1) VTI_L(2, 1) VTI_L(3, 1) VTI_L(4, 1) VTI_L(5, 1) VTI_L(1, 2) VTI_L(2, 2) VTI_L(3, 2) VTI_L(4, 2) VTI_L(1, 4) VTI_L(2, 4) VTI_L(4, 4)
-#undef VTI_L
-    return hipErrorInvalidValue;
 }
 
 // 1x1: p.TH = compute waves along M, p.TW = 80 (pixels per wave); workgroups as for the 3x3 kernel
@@ -856,9 +805,15 @@ hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * p.TH * p.WN * 64;
     dim3 grid((unsigned)p.pk_wgs, (unsigned)(p.ntiles_n / NTB));
-    if (dtype == VTI_F16) return launch_pk1_t<half_t>(nrep, p, grid, threads, lds_bytes, st);
-    if (dtype == VTI_H2) return launch_pk1_t<h2_t>(nrep, p, grid, threads, lds_bytes, st);
-    return launch_pk1_t<float>(nrep, p, grid, threads, lds_bytes, st);
+    return with_conv_type(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        constexpr int CPS = sizeof(T) == 2 ? 1 : 2;            // chunks per step: the planner sets pk_cps to the same value
+        if (p.pk_cps != CPS) return hipErrorInvalidValue;
+        return combo_dispatch(Conv1Pk{}, [&](auto c) {
+            using C = decltype(c);
+            return launch_lds<conv1_pk<T, C::v[0], C::v[1], CPS>>(grid, dim3(threads), lds_bytes, st, p);
+        }, nrep, p.WN);
+    });
 }
 
 // fold on the persistent schedule: 4 x 20 low-resolution pixels per tile, 4 phase waves + 4 loader waves, 2 stages of a 6 x 24 slot
@@ -878,15 +833,11 @@ hipError_t launch_conv_pk_fold(int dtype, const ConvParams& p, size_t lds_bytes,
     if (p.pk_depth < 2 || p.pk_depth > 4 || lds_bytes < conv_pk_fold_lds_bytes(p.nchunks, p.pk_depth) || lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     if (p.pk_tiles == 0) return hipSuccess;
     dim3 grid((unsigned)p.pk_wgs, 1);
-#define VTI_FP(N2)                                                                                              \
-    if (p.ntiles2 == N2) {                                                                                      \
-        if (dtype == VTI_F16) return launch_pk_one<half_t, 4, 4, N2, true>(p, grid, 512, lds_bytes, st);        \
-        if (dtype == VTI_H2) return launch_pk_one<h2_t, 4, 4, N2, true>(p, grid, 512, lds_bytes, st);           \
-        return launch_pk_one<float, 4, 4, N2, true>(p, grid, 512, lds_bytes, st);                               \
-    }
-    VTI_FP(1) VTI_FP(2) VTI_FP(4)
-#undef VTI_FP
-    return hipErrorInvalidValue;
+    return combo_dispatch(FoldN2{}, [&](auto c) {
+        return with_conv_type(dtype, [&](auto t) {
+            return launch_lds<conv3_pk<typename decltype(t)::type, 4, 4, decltype(c)::v[0], true>>(grid, dim3(512), lds_bytes, st, p);
+        });
+    }, p.ntiles2);
 }
 
 // stride-2 3x3 on the persistent schedule (p.pk == 4)
@@ -899,15 +850,12 @@ hipError_t launch_conv_pk2(int dtype, int nrep, const ConvParams& p, size_t lds_
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * (p.TH / PK_ROWS) * p.WN * 64;
     dim3 grid((unsigned)p.pk_wgs, (unsigned)(p.ntiles_n / NTB));
-#define VTI_L2(N, W)                                                                                           \
-    if (nrep == N && p.WN == W) {                                                                              \
-        if (dtype == VTI_F16) return launch_pk_one<half_t, N, W, 0, false, 2>(p, grid, threads, lds_bytes, st); \
-        if (dtype == VTI_H2) return launch_pk_one<h2_t, N, W, 0, false, 2>(p, grid, threads, lds_bytes, st);    \
-        return launch_pk_one<float, N, W, 0, false, 2>(p, grid, threads, lds_bytes, st);                        \
-    }
-    VTI_L2(1, 4) VTI_L2(2, 2) VTI_L2(4, 1) VTI_L2(2, 1) VTI_L2(1, 2)
-#undef VTI_L2
-    return hipErrorInvalidValue;
+    return combo_dispatch(ConvPkS2{}, [&](auto c) {
+        return with_conv_type(dtype, [&](auto t) {
+            using C = decltype(c);
+            return launch_lds<conv3_pk<typename decltype(t)::type, C::v[0], C::v[1], 0, false, 2>>(grid, dim3(threads), lds_bytes, st, p);
+        });
+    }, nrep, p.WN);
 }
 
 // grid.x workgroups (p.pk_wgs, a multiple of 8 when p.pk_xcd) x n-groups; (TH/4) * WN compute + as many loader waves
@@ -920,9 +868,20 @@ hipError_t launch_conv_pk(int dtype, int nrep, const ConvParams& p, size_t lds_b
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * (p.TH / PK_ROWS) * p.WN * 64;   // compute waves + as many loader waves
     dim3 grid((unsigned)p.pk_wgs, (unsigned)(p.ntiles_n / NTB));
-    if (dtype == VTI_F16) return launch_pk_t<half_t>(nrep, p, grid, threads, lds_bytes, st);
-    if (dtype == VTI_H2) return launch_pk_t<h2_t>(nrep, p, grid, threads, lds_bytes, st);
-    return launch_pk_t<float>(nrep, p, grid, threads, lds_bytes, st);
+    return with_conv_type(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (p.ntiles2 > 0) {
+            if (p.WN != 1) return hipErrorInvalidValue;
+            return combo_dispatch(FusedPairs{}, [&](auto c) {
+                using C = decltype(c);
+                return launch_lds<conv3_pk<T, C::v[0], 1, C::v[1]>>(grid, dim3(threads), lds_bytes, st, p);
+            }, nrep, p.ntiles2);
+        }
+        return combo_dispatch(ConvPkS1{}, [&](auto c) {
+            using C = decltype(c);
+            return launch_lds<conv3_pk<T, C::v[0], C::v[1]>>(grid, dim3(threads), lds_bytes, st, p);
+        }, nrep, p.WN);
+    });
 }
 
 // =====================================================================================================
@@ -1367,19 +1326,10 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
     VTI_STAMP(12);
 }
 
-template <typename T, int NREP, bool TAIL = false>
-static hipError_t launch_bneck_one(const ConvParams& p, dim3 grid, int threads, size_t lds, hipStream_t st) {
-    auto k = bneck_pk<T, NREP, TAIL>;
-    static bool done_dev[kMaxDevices] = {};
-    bool& done = done_dev[current_device_slot()];
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
-    hipLaunchKernelGGL(k, grid, dim3(threads), lds, st, p);
-    return hipGetLastError();
-}
+// bneck_pk instantiations per storage type, (NREP, TAIL): fp16 {1 + tail, 1, 2}, h2 {1 + tail, 1}, fp32 {1}
+template <typename T>
+using BneckSet = std::conditional_t<Tr<T>::H16, Combos<Ints<1, 1>, Ints<1, 0>, Ints<2, 0>>,
+                                    std::conditional_t<Tr<T>::H2, Combos<Ints<1, 1>, Ints<1, 0>>, Combos<Ints<1, 0>>>>;
 
 hipError_t launch_bneck_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     if (p.TW != PK_TW || !bneck_pk_fits(p.TH, nrep) || p.nchunks != 1 || p.Cin != 16 * nrep || p.Cout != 16 * nrep || !p.w2 || !p.bias2)
@@ -1397,16 +1347,13 @@ hipError_t launch_bneck_pk(int dtype, int nrep, const ConvParams& p, size_t lds_
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * (p.TH / PK_ROWS) * 64;
     dim3 grid((unsigned)p.pk_wgs, 1);
-    if (dtype == VTI_F16) {
-        if (nrep == 1 && tail) return launch_bneck_one<half_t, 1, true>(p, grid, threads, lds_bytes, st);
-        if (nrep == 1) return launch_bneck_one<half_t, 1>(p, grid, threads, lds_bytes, st);
-        if (nrep == 2) return launch_bneck_one<half_t, 2>(p, grid, threads, lds_bytes, st);
-    } else if (nrep == 1) {
-        if (dtype == VTI_H2 && tail) return launch_bneck_one<h2_t, 1, true>(p, grid, threads, lds_bytes, st);
-        if (dtype == VTI_H2) return launch_bneck_one<h2_t, 1>(p, grid, threads, lds_bytes, st);
-        return launch_bneck_one<float, 1>(p, grid, threads, lds_bytes, st);
-    }
-    return hipErrorInvalidValue;
+    return with_conv_type(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return combo_dispatch(BneckSet<T>{}, [&](auto c) {
+            using C = decltype(c);
+            return launch_lds<bneck_pk<T, C::v[0], C::v[1] != 0>>(grid, dim3(threads), lds_bytes, st, p);
+        }, nrep, tail);
+    });
 }
 
 

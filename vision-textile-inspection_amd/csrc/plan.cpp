@@ -139,8 +139,7 @@ static bool choose_pk_cfg(int dtype, const ConvRow& r, int max_batch, ConvCfg& c
                     const int wgpc = (int)std::min<size_t>(2, (160 * 1024) / lds);
                     const int tiles_y = (r.h_out + TH - 1) / TH;
                     const long NT = (long)max_batch * tiles_y * tiles_x;
-                    long G = std::min<long>(NT, std::max(1, 256 * wgpc / gy));
-                    if (G >= 8) G &= ~7L;
+                    const long G = pk_grid(NT, wgpc, gy);
                     const long rounds = (NT + G - 1) / G;
                     const int simd_load = (ncomp * wgpc + 3) / 4;
                     const double lds_reads = (1.0 / NREP + 0.2) / mf;
@@ -214,8 +213,7 @@ static bool choose_pk2_cfg(int dtype, const ConvRow& r, int max_batch, ConvCfg& 
                     if (ncomp > 4 || !conv_pk2_fits(TH, WN, NREP, c.nchunks, wstat)) continue;
                     const int tiles_y = (r.h_out + TH - 1) / TH;
                     const long NT = (long)max_batch * tiles_y * tiles_x;
-                    long G = std::min<long>(NT, std::max(1, 256 / gy));
-                    if (G >= 8) G &= ~7L;
+                    const long G = pk_grid(NT, 1, gy);
                     const long rounds = (NT + G - 1) / G;
                     const int simd_load = (ncomp + 3) / 4;
                     const double lds_reads = (1.0 / NREP + 0.2) / mf;
@@ -250,7 +248,7 @@ static bool choose_pk2_cfg(int dtype, const ConvRow& r, int max_batch, ConvCfg& 
 // weights stationary in LDS when all K chunks of the n-group fit in 64 KB.  These layers are HBM-bound: prefer one
 // n-group (the pixels are read once), then the deepest ring, then the fewest rounds.
 static bool choose_pk1_cfg(int esize, const ConvRow& r, int max_batch, ConvCfg& c, int fth, int fwn, int fnrep) {
-    const int cps = esize == 2 ? 1 : 2;        // K chunks per step (conv_pk.hip: launch_pk1_one instantiates the same value per type)
+    const int cps = esize == 2 ? 1 : 2;        // K chunks per step (conv_pk.hip: launch_conv1_pk instantiates the same value per type)
     const char* no = getenv("VTI_NO_PK1");
     if (no && no[0] == '1') return false;
     const bool deconv = r.kind == 2;
@@ -292,8 +290,7 @@ static bool choose_pk1_cfg(int esize, const ConvRow& r, int max_batch, ConvCfg& 
                             conv1_pk_lds_bytes(nwm, WN, NREP, c.nchunks, dd, wstat, cps) <= (size_t)(160 * 1024) / wgpc) { depth = dd; break; }
                     if (!depth) continue;
                     const long NT = (total_px + nwm * 80 - 1) / (nwm * 80);
-                    long G = std::min<long>(NT, std::max(1, 256 * wgpc / gy));
-                    if (G >= 8) G &= ~7L;
+                    const long G = pk_grid(NT, wgpc, gy);
                     const long rounds = (NT + G - 1) / G;
                     const double solo = esize == 4 ? ((ncomp * wgpc > 4) ? 1.1 : 1.45) : 1.0;
                     const double step_cyc = 5.0 * NREP * 16 * solo * (esize == 4 ? 2.0 : 1.0) + 250.0 / cps;

@@ -485,18 +485,7 @@ void mask_polygons_layout(int H, int W, int row_bytes, PolyLayout& L) {
 
 template <bool WRITE, bool IN_LDS>
 static hipError_t launch_one(const PolyArgs& a, int grid, size_t lds, hipStream_t st) {
-    auto k = mask_polygons_kernel<WRITE, IN_LDS>;
-    if (IN_LDS) {
-        static bool attr_done_dev[kMaxDevices] = {};
-        bool& attr_done = attr_done_dev[current_device_slot()];
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-            if (e != hipSuccess) return e;
-            attr_done = true;
-        }
-    }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), lds, st, a);
-    return hipGetLastError();
+    return launch_lds<mask_polygons_kernel<WRITE, IN_LDS>>(dim3(grid), dim3(kThreads), lds, st, a);
 }
 
 hipError_t launch_mask_polygons(const uint8_t* masks, int n, const int* n_live, int H, int W, int row_bytes, double gain,

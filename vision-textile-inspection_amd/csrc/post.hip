@@ -492,13 +492,6 @@ hipError_t launch_nms(const float* pred, const float* best, int B, int A, int nc
     if (B == 0) return hipSuccess;
     const size_t lds = (size_t)NMS_LDS_KEYS * 8 + (size_t)NMS_LDS_BOX * 32 + (((size_t)A + 15) & ~(size_t)15);
     if (lds > 150 * 1024) return hipErrorInvalidValue;   // > ~39k anchors: unsupported
-    static bool attr_set_dev[kMaxDevices] = {};
-    bool& attr_set = attr_set_dev[current_device_slot()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
     const NmsWsLayout L = nms_layout(A);
     int* ncand = (int*)((char*)ws + L.per_frame * (size_t)B);
     if (!best) {
@@ -507,8 +500,8 @@ hipError_t launch_nms(const float* pred, const float* best, int B, int A, int nc
         const int apb = (((4 + nc + nm) | nc) & 3) == 0 ? 64 : 256;        // anchors per block: quad-per-anchor / lane-per-anchor
         hipLaunchKernelGGL(nms_scan_kernel, dim3((A + apb - 1) / apb, B), dim3(256), 0, st, pred, A, nc, nm, conf, (char*)ws, L, ncand, (float*)nullptr);
     }
-    hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(NMS_THREADS), lds, st, pred, A, nc, nm, conf, iou, max_det, agnostic,
-                       dets, counts, (char*)ws, L, ncand, best);
+    const hipError_t e = launch_lds<nms_kernel>(dim3(B), dim3(NMS_THREADS), lds, st, pred, A, nc, nm, conf, iou, max_det, agnostic,
+                                                dets, counts, (char*)ws, L, ncand, best);
 #ifdef VTI_STAMPS
     {
         (void)hipStreamSynchronize(st);
@@ -533,7 +526,7 @@ hipError_t launch_nms(const float* pred, const float* best, int B, int A, int nc
         }
     }
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 // =====================================================================================
@@ -1153,18 +1146,10 @@ hipError_t launch_masks(int dtype, const float* dets, const int* counts, const v
     }
     // persistent blocks walk the work list: exactly as many as are resident at once (a second round of late blocks would run
     // on a mostly empty chip), a multiple of 8 for the per-XCD partition
-    static int per_cu_dev[kMaxDevices][4] = {};
-    int* per_cu = per_cu_dev[current_device_slot()];
-    const int kidx = (dtype == VTI_F16 ? 0 : 2) + (nm == 32 ? 0 : 1);
-    if (!per_cu[kidx]) {
-        int nb = 0;
-        const void* fn = dtype == VTI_F16 ? (nm == 32 ? (const void*)masks_group_kernel<half_t> : (const void*)masks_kernel<half_t>)
-                                          : (nm == 32 ? (const void*)masks_group_kernel<float> : (const void*)masks_kernel<float>);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) != hipSuccess || nb < 1) nb = 4;
-        per_cu[kidx] = nb > 8 ? 8 : nb;
-    }
-    int grid = 256 * per_cu[kidx];
-    if (const char* e = getenv("VTI_MASK_WGS_PER_CU")) grid = 256 * std::max(1, std::min(per_cu[kidx], atoi(e)));   // experiments: fewer resident workgroups
+    const int per_cu = dtype == VTI_F16 ? (nm == 32 ? resident_per_cu<masks_group_kernel<half_t>>(256, 4, 8) : resident_per_cu<masks_kernel<half_t>>(256, 4, 8))
+                                        : (nm == 32 ? resident_per_cu<masks_group_kernel<float>>(256, 4, 8) : resident_per_cu<masks_kernel<float>>(256, 4, 8));
+    int grid = 256 * per_cu;
+    if (const char* e = getenv("VTI_MASK_WGS_PER_CU")) grid = 256 * std::max(1, std::min(per_cu, atoi(e)));   // experiments: fewer resident workgroups
     if (nm == 32) {
         // the (frame, tile) list is static: no plan, no work-list memory
         if (dtype == VTI_F16)
@@ -1497,16 +1482,8 @@ hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, 
     const size_t vecs = (size_t)capacity * p.slot_bytes / 16;
     const int clear_grid = (int)std::max<size_t>(1, std::min<size_t>((vecs + 255) / 256, 2048));
     hipLaunchKernelGGL(mask_clear_live_kernel, dim3(clear_grid), dim3(256), 0, st, offsets, B, capacity, p.slot_bytes, masks);
-    static int per_cu_dev[kMaxDevices][2] = {};
-    int* per_cu = per_cu_dev[current_device_slot()];
-    const int kidx = dtype == VTI_F16 ? 0 : 1;
-    if (!per_cu[kidx]) {
-        int nb = 0;
-        const void* fn = dtype == VTI_F16 ? (const void*)masks_native_kernel<half_t> : (const void*)masks_native_kernel<float>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) != hipSuccess || nb < 1) nb = 2;
-        per_cu[kidx] = nb > 4 ? 4 : nb;
-    }
-    const int grid = 256 * per_cu[kidx];
+    const int grid = 256 * (dtype == VTI_F16 ? resident_per_cu<masks_native_kernel<half_t>>(256, 2, 4)
+                                              : resident_per_cu<masks_native_kernel<float>>(256, 2, 4));
     if (dtype == VTI_F16) hipLaunchKernelGGL(masks_native_kernel<half_t>, dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(masks_native_kernel<float>, dim3(grid), dim3(256), 0, st, p);
     return hipGetLastError();

@@ -76,6 +76,31 @@ static void report_stamps(const std::vector<unsigned long long>& h, size_t nwg, 
         if (h[w * 16 + 15] > h[w * 16 + 14]) clk.push_back((double)(h[w * 16 + 12] - h[w * 16]) / (double)(h[w * 16 + 15] - h[w * 16 + 14]) * 0.1);
     if (!clk.empty()) { std::sort(clk.begin(), clk.end()); fprintf(stderr, "[stamps] in-kernel clock    median %.3f GHz (p10 %.3f, p90 %.3f)\n", clk[clk.size() / 2], clk[clk.size() / 10], clk[clk.size() * 9 / 10]); }
 }
+
+// diagnostic build: launch() once with p.stamps pointing at nwg x 16 zeroed slots, wait, then the header line (if any) and the
+// medians to stderr.  false when the stamp buffer could not be allocated (nothing was launched).
+template <typename L>
+static bool stamped_launch(ConvParams& p, size_t nwg, bool pk, hipStream_t st, const char* header, L&& launch) {
+    unsigned long long* d_st = nullptr;
+    if (hipMalloc((void**)&d_st, nwg * 16 * 8) != hipSuccess) return false;
+    (void)hipMemset(d_st, 0, nwg * 16 * 8);
+    p.stamps = d_st;
+    (void)launch();
+    (void)hipStreamSynchronize(st);
+    std::vector<unsigned long long> h(nwg * 16);
+    (void)hipMemcpy(h.data(), d_st, nwg * 16 * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_st);
+    p.stamps = nullptr;
+    if (header) fprintf(stderr, "%s\n", header);
+    report_stamps(h, nwg, pk);
+    return true;
+}
+
+// workgroups of a conv launch (stamp slots): the persistent grid or one per tile, times the n-groups
+static size_t conv_workgroups(const ConvParams& p, const ConvCfg& g, int B) {
+    const int NTB = g.WN * g.NREP;
+    return (p.pk ? (size_t)p.pk_wgs : (size_t)B * p.tiles_y * p.tiles_x) * ((g.ntiles_n + NTB - 1) / NTB);
+}
 #endif
 
 extern "C" {
@@ -252,6 +277,9 @@ static int pk_linear_map() {       // A/B aid: VTI_PK_LINEAR_MAP=1 restores the 
     return v;
 }
 
+// Stores of n channels at channel offset coff into rows of ld channels: 16-byte vector stores need all three to be multiples of 4.
+static int scalar_store(int n, int ld, int coff) { return (n % 4 || ld % 4 || coff % 4) ? 1 : 0; }
+
 // One conv launch's parameter block from its table row + geometry + tensor views.
 static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r, const ConvCfg& g, int B, const void* in, int in_ld,
                              int in_coff, void* out, int out_ld, int out_coff, const void* res, int res_ld,
@@ -273,7 +301,7 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
     p.deconv_c = deconv ? r.c2 : 0;
     p.swap_rb = swap_rb ? 1 : 0;
     p.nchunks = g.nchunks; p.ntiles_n = g.ntiles_n;
-    p.scalar_store = (g.gemm_n % 4 || out_ld % 4 || out_coff % 4) ? 1 : 0;
+    p.scalar_store = scalar_store(g.gemm_n, out_ld, out_coff);
     const bool conv0 = r.c1 == 3;
     const int ks = deconv ? 1 : r.k, st = deconv ? 1 : r.s;
     const unsigned PW = conv0 ? (unsigned)g.TW : (unsigned)((g.TW - 1) * st + ks);
@@ -291,12 +319,8 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
         p.in_bytes = (unsigned)ib; p.out_bytes = (unsigned)ob; p.res_bytes = 0;
         p.pk_depth = g.pk_depth; p.pk_wstat = g.pk_wstat; p.pk_cps = g.pk_cps;
         p.pk_tiles = (int)((npx + (size_t)g.TH * 80 - 1) / ((size_t)g.TH * 80));
-        const int gy = g.ntiles_n / (g.WN * g.NREP);
-        int G = std::min(p.pk_tiles, std::max(1, 256 * g.pk_wgpc / gy));
-        if (const char* cap = getenv("VTI_PK_MAX_WGS")) G = std::max(1, std::min(G, atoi(cap)));
-        p.pk_xcd = G >= 8 ? 1 : 0;
-        if (p.pk_xcd) G &= ~7;
-        p.pk_wgs = G;
+        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, g.ntiles_n / (g.WN * g.NREP), getenv("VTI_PK_MAX_WGS"));
+        p.pk_xcd = p.pk_wgs >= 8 ? 1 : 0;
     } else if (g.pk) {   // persistent kernel: workgroups along x walk the B * tiles_y * tiles_x tiles
         const size_t es = conv_elem_size;
         const size_t ib = (size_t)B * r.h_in * r.w_in * in_ld * es, ob = (size_t)B * p.Hout * p.Wout * out_ld * (out_f32 ? 4 : es);
@@ -306,15 +330,26 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
         p.pk_tiles = B * p.tiles_y * p.tiles_x;
         p.pk_depth = g.pk_depth; p.pk_wstat = g.pk_wstat;
         const int gy = g.ntiles_n / (g.WN * g.NREP);
-        int G = std::min(p.pk_tiles, std::max(1, 256 * g.pk_wgpc / gy));
-        if (const char* cap = getenv("VTI_PK_MAX_WGS")) G = std::max(1, std::min(G, atoi(cap)));   // tests: force many tiles per workgroup
-        p.pk_xcd = G >= 8 ? 1 : 0;
-        if (p.pk_xcd) G &= ~7;
-        p.pk_wgs = G;
+        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, gy, getenv("VTI_PK_MAX_WGS"));      // tests: force many tiles per workgroup
+        p.pk_xcd = p.pk_wgs >= 8 ? 1 : 0;
         // launches that fill the chip start the upper half of their workgroups late (conv_pk.hip: pk_stagger_wait): eligibility here,
         // the caller scales it by stagger_units(dtype)
-        p.pk_stagger = ((g.pk == 1 || g.pk == 4) && p.pk_tiles >= std::max(1, 256 * g.pk_wgpc / gy) && G >= 16) ? 1 : 0;
+        p.pk_stagger = ((g.pk == 1 || g.pk == 4) && p.pk_tiles >= std::max(1, 256 * g.pk_wgpc / gy) && p.pk_wgs >= 16) ? 1 : 0;
     }
+}
+
+// The fused 1x1 second stage of an op (op.fused; fold ops and fused towers): its weights, where it writes and how it stores.
+static void fill_stage2(vti_ctx* c, ConvParams& p, const Op& op, const void* input, void* proto) {
+    const Plan& P = c->plan;
+    const ConvCfg& g = op.cfg;
+    const Buf& o2 = P.bufs[op.out2.buf];
+    p.w2 = (const char*)c->d_wpk + g.wpk_off2; p.bias2 = c->d_bias + g.bias_off2; p.alpha2 = c->alpha[op.fused];
+    p.out2 = buf_ptr(c, op.out2.buf, input, proto);
+    p.Cout2 = g.gemm_n2; p.ntiles2 = g.ntiles2; p.out2_ld = o2.C; p.out2_coff = op.out2.coff;
+    p.act2 = P.convs[op.fused].kind == 0; p.out2_f32 = op.out2_f32 ? 1 : 0;
+    p.scalar_store2 = scalar_store(g.gemm_n2, o2.C, op.out2.coff);
+    p.nat2 = op.nat2;           // fp32 NHWC output (e.g. the h2 engine's proto): stage-2 weights are packed with natural rows
+    p.out2_bstride = P.convs[op.conv].h_out * P.convs[op.conv].w_out;     // the op's output grid (fold: the 2x map)
 }
 
 static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t swap_rb, float* pred, void* proto, float* best, void* stream);
@@ -387,37 +422,22 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                     q.out2 = buf_ptr(c, op.out2.buf, input, proto);
                     q.Cout2 = g.gemm_n2; q.ntiles2 = g.ntiles2; q.out2_ld = o1.C; q.out2_coff = op.out2.coff;
                     q.act2 = 1; q.out2_bstride = r1.h_out * r1.w_out;
-                    q.scalar_store2 = (g.gemm_n2 % 4 || o1.C % 4 || op.out2.coff % 4) ? 1 : 0;
+                    q.scalar_store2 = scalar_store(g.gemm_n2, o1.C, op.out2.coff);
                 }
                 stem_l1_tile(&q.TH, &q.TW);
                 q.tiles_y = (q.Hout + q.TH - 1) / q.TH; q.tiles_x = (q.Wout + q.TW - 1) / q.TW; q.WN = 1;
-                q.scalar_store = (q.out_ld % 4 || q.out_coff % 4) ? 1 : 0;
+                q.scalar_store = scalar_store(q.Cout, q.out_ld, q.out_coff);
 #ifdef VTI_STAMPS
-                if (const char* so = getenv("VTI_STAMP_OP")) {
-                    if (r.name == so) {
-                        const size_t nwg = (size_t)stem_l1_grid(dt, B * q.tiles_y * q.tiles_x);
-                        unsigned long long* d_st = nullptr;
-                        if (hipMalloc((void**)&d_st, nwg * 16 * 8) == hipSuccess) {
-                            (void)hipMemset(d_st, 0, nwg * 16 * 8);
-                            q.stamps = d_st;
-                            (void)launch_stem_l1(dt, q, st);
-                            (void)hipStreamSynchronize(st);
-                            std::vector<unsigned long long> h(nwg * 16);
-                            (void)hipMemcpy(h.data(), d_st, nwg * 16 * 8, hipMemcpyDeviceToHost);
-                            (void)hipFree(d_st);
-                            fprintf(stderr, "[stamps] op %s + layer 1 (1: patch staged, 2: stem done, 3: layer-1 MFMAs done, 12: end)\n", so);
-                            report_stamps(h, nwg, false);
-                            q.stamps = nullptr;
-                        }
-                    }
-                }
+                if (const char* so = getenv("VTI_STAMP_OP"); so && r.name == so)
+                    stamped_launch(q, (size_t)stem_l1_grid(dt, B * q.tiles_y * q.tiles_x), false, st,
+                                   ("[stamps] op " + r.name + " + layer 1 (1: patch staged, 2: stem done, 3: layer-1 MFMAs done, 12: end)").c_str(),
+                                   [&] { return launch_stem_l1(dt, q, st); });
 #endif
                 VTI_HIP(c, launch_stem_l1(dt, q, st), "stem + layer 1");
                 break;
             }
             if (op.fold >= 0) {         // ConvTranspose2d(2,2) + 3x3 + fused 1x1 as four 2x2 convs on the low-resolution map
                 const ConvRow& ru = P.convs[op.fold];
-                const Buf& o2 = P.bufs[op.out2.buf];
                 ConvParams q;
                 memset(&q, 0, sizeof q);
                 q.in = buf_ptr(c, op.in.buf, input, proto); q.B = B; q.Hin = ru.h_in; q.Win = ru.w_in; q.Hout = ru.h_in; q.Wout = ru.w_in;
@@ -427,22 +447,13 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                 q.pw_magic = (unsigned)((0x100000000ull + (unsigned)(g.TW + 2) - 1) / (unsigned)(g.TW + 2));
                 q.tw_magic = (unsigned)((0x100000000ull + (unsigned)g.TW - 1) / (unsigned)g.TW);
                 q.wpk = (const char*)c->d_wpk + g.wpk_off; q.bias = c->d_bias + g.bias_off; q.wpk_bytes = (unsigned)packed_fold_bytes(g);
-                q.w2 = (const char*)c->d_wpk + g.wpk_off2; q.bias2 = c->d_bias + g.bias_off2;
-                q.alpha = c->alpha[op.conv]; q.alpha2 = c->alpha[op.fused]; q.alpha0 = 1.f;
-                q.out2 = buf_ptr(c, op.out2.buf, input, proto);
-                q.Cout2 = g.gemm_n2; q.ntiles2 = g.ntiles2; q.out2_ld = o2.C; q.out2_coff = op.out2.coff;
-                q.act2 = P.convs[op.fused].kind == 0; q.out2_f32 = op.out2_f32 ? 1 : 0;
-                q.scalar_store2 = (g.gemm_n2 % 4 || o2.C % 4 || op.out2.coff % 4) ? 1 : 0;
-                q.out2_bstride = 4 * q.Hout * q.Wout;
-                q.nat2 = op.nat2;           // f32 proto (h2 engine): stage-2 weights are packed with natural rows
+                q.alpha = c->alpha[op.conv]; q.alpha0 = 1.f;
+                fill_stage2(c, q, op, input, proto);
                 if (g.pk) {             // persistent schedule: composed weights resident in LDS, tiles walked per XCD
                     q.pk = 1; q.pk_depth = g.pk_depth; q.in_bytes = (unsigned)((size_t)B * q.Hin * q.Win * q.in_ld * P.esize);
                     q.pk_tiles = B * q.tiles_y * q.tiles_x;
-                    int G = std::min(q.pk_tiles, 256);
-                    if (const char* cap = getenv("VTI_PK_MAX_WGS")) G = std::max(1, std::min(G, atoi(cap)));
-                    q.pk_xcd = G >= 8 ? 1 : 0;
-                    if (q.pk_xcd) G &= ~7;
-                    q.pk_wgs = G;
+                    q.pk_wgs = pk_grid(q.pk_tiles, 1, 1, getenv("VTI_PK_MAX_WGS"));
+                    q.pk_xcd = q.pk_wgs >= 8 ? 1 : 0;
                     VTI_HIP(c, launch_conv_pk_fold(dt, q, g.lds, st), r.name.c_str());
                 } else {
                     VTI_HIP(c, launch_convfold(dt, q, g.lds, st), r.name.c_str());
@@ -457,24 +468,16 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                              (const char*)c->d_wpk + g.wpk_off, c->d_bias + g.bias_off, op.out_f32, swap_rb);
             p.alpha = c->alpha[op.conv]; p.alpha0 = 1.f;
             p.pk_stagger *= stagger_units(dt);
-            p.alpha2 = op.fused >= 0 ? c->alpha[op.fused] : op.pair >= 0 ? c->alpha[op.pair] : 1.f;
+            p.alpha2 = op.pair >= 0 ? c->alpha[op.pair] : 1.f;
             if (op.fused >= 0) {
-                const Buf& o2 = P.bufs[op.out2.buf];
-                p.w2 = (const char*)c->d_wpk + g.wpk_off2;
-                p.bias2 = c->d_bias + g.bias_off2;
-                p.out2 = buf_ptr(c, op.out2.buf, input, proto);
-                p.Cout2 = g.gemm_n2; p.ntiles2 = g.ntiles2; p.out2_ld = o2.C; p.out2_coff = op.out2.coff;
-                p.act2 = P.convs[op.fused].kind == 0; p.out2_f32 = op.out2_f32 ? 1 : 0;
-                p.scalar_store2 = (g.gemm_n2 % 4 || o2.C % 4 || op.out2.coff % 4) ? 1 : 0;
-                p.nat2 = op.nat2;
-                p.out2_bstride = r.h_out * r.w_out;
+                fill_stage2(c, p, op, input, proto);
                 if (op.pred_mode) {     // class / coefficient towers write their rows of the anchor-major pred [B, A, no] directly
                     const int no = 4 + P.desc.nc + P.desc.nm;
                     p.out2 = pred + (size_t)op.pred_a0 * no;
                     p.out2_ld = no; p.out2_coff = op.pred_cbase; p.out2_f32 = 1; p.out2_bstride = P.num_anchors;
                     p.act2 = op.pred_mode == 2 ? 2 : op.pred_mode == 3 ? 3 : 0;
                     p.dfl_stride = (float)op.dfl_stride;
-                    p.scalar_store2 = (g.gemm_n2 % 4 || no % 4 || op.pred_cbase % 4) ? 1 : 0;
+                    p.scalar_store2 = scalar_store(g.gemm_n2, no, op.pred_cbase);
                     p.best = (op.pred_mode == 2 && best) ? best + (size_t)op.pred_a0 * 2 : nullptr;     // class towers: (max, class) per anchor
                 }
             }
@@ -502,26 +505,11 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
             const bool deconv = r.kind == 2;
             const int ks = deconv ? 1 : r.k, s = deconv ? 1 : r.s;
 #ifdef VTI_STAMPS
-            if (const char* so = getenv("VTI_STAMP_OP")) {     // diagnostic build: stamp this op of the forward (fused ops included)
-                if (r.name == so) {
-                    const int NTBs = g.WN * g.NREP;
-                    const size_t nwg = (p.pk ? (size_t)p.pk_wgs : (size_t)B * p.tiles_y * p.tiles_x) * ((g.ntiles_n + NTBs - 1) / NTBs);
-                    unsigned long long* d_st = nullptr;
-                    if (hipMalloc((void**)&d_st, nwg * 16 * 8) == hipSuccess) {
-                        (void)hipMemset(d_st, 0, nwg * 16 * 8);
-                        p.stamps = d_st;
-                        (void)launch_conv(dt, ks, s, g.NREP, op.kind == OP_CONV0 ? 1 : 0, p, g.lds, st);
-                        (void)hipStreamSynchronize(st);
-                        std::vector<unsigned long long> h(nwg * 16);
-                        (void)hipMemcpy(h.data(), d_st, nwg * 16 * 8, hipMemcpyDeviceToHost);
-                        (void)hipFree(d_st);
-                        fprintf(stderr, "[stamps] op %s\n", so);
-                        report_stamps(h, nwg, p.pk != 0);
-                        p.stamps = nullptr;
-                        break;
-                    }
-                }
-            }
+            // diagnostic build: stamp this op of the forward (fused ops included); the stamped launch is the op's launch
+            if (const char* so = getenv("VTI_STAMP_OP"); so && r.name == so &&
+                stamped_launch(p, conv_workgroups(p, g, B), p.pk != 0, st, ("[stamps] op " + r.name).c_str(),
+                               [&] { return launch_conv(dt, ks, s, g.NREP, op.kind == OP_CONV0 ? 1 : 0, p, g.lds, st); }))
+                break;
 #endif
             VTI_HIP(c, launch_conv(dt, ks, s, g.NREP, op.kind == OP_CONV0 ? 1 : 0, p, g.lds, st), r.name.c_str());
             break;
@@ -572,28 +560,27 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
     return VTI_OK;
 }
 
-int32_t vti_nms_scored(vti_ctx* c, const float* pred, const float* anchor_best, int32_t B, float conf, double iou, int32_t max_det,
-                       int32_t agnostic, float* dets, int32_t* counts, void* stream) {
+// vti_nms (best == null: the candidate filter scans the class scores) and vti_nms_scored (the (max, class) pairs beside pred)
+static int32_t nms_impl(vti_ctx* c, const char* fn, bool scored, const float* pred, const float* best, int32_t B, float conf,
+                        double iou, int32_t max_det, int32_t agnostic, float* dets, int32_t* counts, void* stream) {
     if (!c) return VTI_ERR_ARG;
-    if (B < 0 || B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_nms_scored: B out of range");
-    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_nms_scored: workspace not set");
-    if (!pred || !anchor_best || !dets || !counts || max_det < 1) return fail(c, VTI_ERR_ARG, "vti_nms_scored: bad argument");
-    if (int32_t drc = check_device(c, "vti_nms_scored")) return drc;
-    VTI_HIP(c, launch_nms(pred, anchor_best, B, c->plan.num_anchors, c->plan.desc.nc, c->plan.desc.nm, conf, iou, max_det, agnostic,
+    if (B < 0 || B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, std::string(fn) + ": B out of range");
+    if (!c->ws) return fail(c, VTI_ERR_STATE, std::string(fn) + ": workspace not set");
+    if (!pred || (scored && !best) || !dets || !counts || max_det < 1) return fail(c, VTI_ERR_ARG, std::string(fn) + ": bad argument");
+    if (int32_t drc = check_device(c, fn)) return drc;
+    VTI_HIP(c, launch_nms(pred, best, B, c->plan.num_anchors, c->plan.desc.nc, c->plan.desc.nm, conf, iou, max_det, agnostic,
                           dets, counts, c->ws + c->act_bytes, (hipStream_t)stream), "nms kernel");
     return VTI_OK;
 }
 
+int32_t vti_nms_scored(vti_ctx* c, const float* pred, const float* anchor_best, int32_t B, float conf, double iou, int32_t max_det,
+                       int32_t agnostic, float* dets, int32_t* counts, void* stream) {
+    return nms_impl(c, "vti_nms_scored", true, pred, anchor_best, B, conf, iou, max_det, agnostic, dets, counts, stream);
+}
+
 int32_t vti_nms(vti_ctx* c, const float* pred, int32_t B, float conf, double iou, int32_t max_det, int32_t agnostic,
                 float* dets, int32_t* counts, void* stream) {
-    if (!c) return VTI_ERR_ARG;
-    if (B < 0 || B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_nms: B out of range");
-    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_nms: workspace not set");
-    if (!pred || !dets || !counts || max_det < 1) return fail(c, VTI_ERR_ARG, "vti_nms: bad argument");
-    if (int32_t drc = check_device(c, "vti_nms")) return drc;
-    VTI_HIP(c, launch_nms(pred, nullptr, B, c->plan.num_anchors, c->plan.desc.nc, c->plan.desc.nm, conf, iou, max_det, agnostic,
-                          dets, counts, c->ws + c->act_bytes, (hipStream_t)stream), "nms kernel");
-    return VTI_OK;
+    return nms_impl(c, "vti_nms", false, pred, nullptr, B, conf, iou, max_det, agnostic, dets, counts, stream);
 }
 
 int32_t vti_masks(vti_ctx* c, const float* dets, const int32_t* counts, const void* proto, int32_t B, int32_t max_det,
@@ -888,23 +875,10 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
         p.pk_stagger *= stagger_units(dtype);
         const int ks = kind == 2 ? 1 : k, ss = kind == 2 ? 1 : s;
 #ifdef VTI_STAMPS
-        {   // diagnostic build: one stamped launch, medians of the phase intervals to stderr
-            const int NTB = g.WN * g.NREP;
-            const size_t nwg = (p.pk ? (size_t)p.pk_wgs : (size_t)B * p.tiles_y * p.tiles_x) * ((g.ntiles_n + NTB - 1) / NTB);
-            unsigned long long* d_st = nullptr;
-            if (hipMalloc((void**)&d_st, nwg * 16 * 8) == hipSuccess) {
-                (void)hipMemset(d_st, 0, nwg * 16 * 8);
-                (void)launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);   // warm caches/icache
-                p.stamps = d_st;
-                (void)launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);
-                (void)hipStreamSynchronize(st);
-                std::vector<unsigned long long> h(nwg * 16);
-                (void)hipMemcpy(h.data(), d_st, nwg * 16 * 8, hipMemcpyDeviceToHost);
-                p.stamps = nullptr;
-                (void)hipFree(d_st);
-                report_stamps(h, nwg, p.pk != 0);
-            }
-        }
+        // diagnostic build: one stamped launch after a warm-up (caches, icache), medians of the phase intervals to stderr
+        (void)launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);
+        stamped_launch(p, conv_workgroups(p, g, B), p.pk != 0, st, nullptr,
+                       [&] { return launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st); });
 #endif
         e = launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);   // warm-up / the checked run
         if (e == hipSuccess) e = hipEventRecord(e0, st);

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -11,10 +13,47 @@
 
 namespace vti {
 
-// hipFuncSetAttribute (the > 64 KB dynamic-LDS opt-in) is a per-device setting: the "already done" flags of the launchers are kept
+// hipFuncSetAttribute (the > 64 KB dynamic-LDS opt-in) is a per-device setting: the "already done" state of the launchers is kept
 // per device, so a process that holds contexts on several GPUs sets it on each of them.
 constexpr int kMaxDevices = 64;
 inline int current_device_slot() { int d = 0; (void)hipGetDevice(&d); return (unsigned)d < (unsigned)kMaxDevices ? d : 0; }
+
+// Launch kernel K with `lds` bytes of dynamic LDS.  Above 64 KB the kernel has to opt in: once per (device, kernel), and again only
+// when a later launch needs more than the attribute already allows (static + dynamic LDS must fit the CU's 160 KB).
+template <auto K, typename... A>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    static size_t opted_dev[kMaxDevices] = {};
+    size_t& opted = opted_dev[current_device_slot()];
+    if (lds > 64 * 1024 && lds > opted) {
+        hipError_t e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        opted = lds;
+    }
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
+// Resident workgroups per CU of kernel K (`threads` wide, no dynamic LDS), at most `cap`; `fallback` when the query fails.
+// Cached per (device, kernel).
+template <auto K>
+int resident_per_cu(int threads, int fallback, int cap) {
+    static int per_cu_dev[kMaxDevices] = {};
+    int& per_cu = per_cu_dev[current_device_slot()];
+    if (!per_cu) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)K, threads, 0) != hipSuccess || nb < 1) nb = fallback;
+        per_cu = nb > cap ? cap : nb;
+    }
+    return per_cu;
+}
+
+// Workgroups of a persistent launch: as many as fit the chip (wgpc per CU, 256 CUs, shared by gy n-groups), at most one per tile,
+// lowered to `cap` when given (VTI_PK_MAX_WGS), and a multiple of 8 from 8 on (each XCD then walks a contiguous range of tiles).
+inline int pk_grid(long tiles, int wgpc, int gy, const char* cap = nullptr) {
+    long G = std::min<long>(tiles, std::max(1, 256 * wgpc / gy));
+    if (cap) G = std::max<long>(1, std::min<long>(G, atoi(cap)));
+    return (int)(G >= 8 ? G & ~7L : G);
+}
 
 // ---- plan ---------------------------------------------------------------------------
 enum ElemKind { EL_T = 0, EL_F32 = 1, EL_U8 = 2 };   // EL_T = ctx dtype (fp16, fp32, or h2 = split-fp16 pairs, 4 bytes)
