@@ -241,7 +241,8 @@ typedef struct {
 } vti_measure_params;
 
 /* vti_measure's frame_i32 status and stitch_i32 flag bits. */
-enum { VTI_MEASURE_OK = 0, VTI_MEASURE_NO_FABRIC = 1, VTI_MEASURE_NO_STITCHES = 2 };
+enum { VTI_MEASURE_OK = 0, VTI_MEASURE_NO_FABRIC = 1, VTI_MEASURE_NO_STITCHES = 2,
+       VTI_MEASURE_BAD_CAMERA = 3 };   /* vti_measure_cameras only: the frame's camera index is outside [0, n_cams) */
 enum { VTI_STITCH_KEPT = 1,       /* a stitch of stitch_meta: exists, class stitch_id, inside the ROI */
        VTI_STITCH_MASK = 2,       /* moments / extents from its mask (else the int-box fall-backs) */
        VTI_STITCH_SELECTED = 4,   /* in the selected row */
@@ -273,6 +274,33 @@ int32_t vti_measure(vti_ctx* ctx, const vti_measure_params* params, const uint8_
                     const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets, int32_t B, int32_t max_det,
                     int32_t capacity, int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
                     int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
+
+/* ---- vti_measure for a batch that mixes cameras: every setting of vti_measure_params per frame ------------------------------ */
+/* The settings live in a camera table in caller-owned DEVICE memory, one row per camera, and an i32 [B] device array names each
+ * frame's row.  The table is packed on the host, uploaded once and reused; it does not depend on the frame size (the ROI is clamped
+ * to H0 x W0 on the device).
+ * Host only: bytes of a table of n_cams rows (0 when n_cams < 1). */
+int64_t vti_measure_cameras_bytes(int32_t n_cams);
+/* Host only: validates params[0 .. n_cams) with exactly vti_measure's checks of its one struct (VTI_ERR_ARG; vti_last_error names
+ * the index of the first failing camera) and writes the table into host_table (nbytes >= vti_measure_cameras_bytes(n_cams)).  A
+ * row holds the struct's settings plus the plane of compute_camera_plane (measurement.py:44-48); the format is private to the
+ * library build that packed it, and equal inputs give equal bytes.  ctx only receives the error text. */
+int32_t vti_measure_pack_cameras(vti_ctx* ctx, const vti_measure_params* params, int32_t n_cams, void* host_table, size_t nbytes);
+/* vti_measure with frame b measured under row dev_camera_of_frame[b] of dev_cameras (16-byte aligned device copy of a packed
+ * table); every other argument, the scratch size (vti_measure_scratch_bytes), the outputs and the three launches are vti_measure's,
+ * and frame b's results are bit-identical to those of vti_measure called with that camera's struct on the same inputs.  Every
+ * argument check (null table or index array, n_cams < 1, then vti_measure's shape, pointer, alignment and scratch checks) runs
+ * before the first HIP call; the settings were checked when the table was packed.
+ * The index array is device data the host cannot check: the kernels compare dev_camera_of_frame[b] with [0, n_cams) BEFORE they
+ * form a table address.  A frame whose index is outside reports status VTI_MEASURE_BAD_CAMERA, NaN averages, zero counts, and
+ * flags 0 / rank -1 / NaN in the per-slot rows of its instances; the other frames are unaffected.  The table's CONTENTS are
+ * trusted to be what vti_measure_pack_cameras wrote: its validation is what bounds the kernels' loops (envelope_neighborhood <=
+ * 64, kmeans_iters >= 0), so bytes from anywhere else are undefined behaviour. */
+int32_t vti_measure_cameras(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams, const int32_t* dev_camera_of_frame,
+                            const uint8_t* dev_masks, int32_t native, const float* dev_dets, const float* dev_xyxy,
+                            const int32_t* dev_counts, const int32_t* dev_offsets, int32_t B, int32_t max_det, int32_t capacity,
+                            int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32,
+                            double* stitch_f64, int32_t* stitch_i32, void* stream);
 
 /* ---- Results.masks.xy on device: instance polygons in frame pixels ---------------------------------------------------- */
 /* Ultralytics masks2segments + scale_coords as restated by the package's polygons.py, bit for bit: per mask the outer border of

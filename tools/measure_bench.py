@@ -1,10 +1,16 @@
 """vti_measure cost: process_frame's measurement record for a batch, from letterbox-size bit masks (vti_masks) and from
 frame-size ones (vti_masks_native), on the SAME detections (synth_pred -> NMS -> scale_boxes), timed with device events after
 warm-up, next to the predict step it follows.
-    python3 tools/measure_bench.py [--dtype h2] [--iters 50] [--B 64] [--n-inst 50]
+    python3 tools/measure_bench.py [--dtype h2] [--iters 50] [--B 64] [--n-inst 50] [--cameras N [N ...]] [--groups G]
 Prints per mask form: us per call (the three launches), us per frame, and its share of one predict_into step (letterbox ->
-net -> NMS -> masks -> scale_boxes) at the same batch."""
+net -> NMS -> masks -> scale_boxes) at the same batch.
+--cameras N: also vti_measure_cameras with a table of N cameras assigned round-robin (frame b -> camera b % N; the two calibration
+files of tests/golden alternate, every row at a camera position of its own, ROI and thresholds shared so that the work is the
+one-camera call's), table and index uploaded before the timing.
+--groups G: also the work-around the table form replaces, G vti_measure calls on views of the same output set, one per contiguous
+group of B / G frames (offsets rebased per group beforehand; a real caller would also have to sort its frames by camera)."""
 import argparse
+import dataclasses
 import os
 import sys
 
@@ -38,6 +44,8 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--B", type=int, default=64)
     ap.add_argument("--n-inst", type=int, default=50)
+    ap.add_argument("--cameras", type=int, nargs="+", default=[])
+    ap.add_argument("--groups", type=int, default=0)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("measure_bench needs the GPU")
@@ -56,8 +64,14 @@ def main():
     proto = torch.from_numpy(rng.standard_normal((B, H // 4, W // 4, 32)).astype(np.float32)).to(eng.torch_dtype).cuda()
     dets, counts = eng.nms(pred, 0.25, 0.7, max_det)
     xyxy = eng.scale_boxes(dets, counts, H0, W0)
-    params = vti_amd.MeasureParams.from_files(os.path.join(ROOT, "tests", "golden", "camera_calibration.json"),
-                                              os.path.join(ROOT, "tests", "golden", "extrinsics.json"))
+    golden = os.path.join(ROOT, "tests", "golden")
+    params = vti_amd.MeasureParams.from_files(os.path.join(golden, "camera_calibration.json"), os.path.join(golden, "extrinsics.json"))
+    other = vti_amd.MeasureParams.from_files(os.path.join(golden, "camera_calibration.json"), os.path.join(golden, "camera_extrinsics.json"))
+    tables = {}
+    for n in a.cameras:     # camera 0 = `params`; every row differs (calibration file, camera position) but keeps the ROI and the
+        # thresholds, so the same instances are measured as in the one-camera call and the times compare
+        cams = [dataclasses.replace(p, t=p.t + 1e-4 * c) for c, p in ((c, other if c & 1 else params) for c in range(n))]
+        tables[n] = (eng.pack_cameras(cams, "cuda"), (torch.arange(B, dtype=torch.int32) % n).to(torch.int32).cuda())
     live = int(counts.sum())
     print(f"B={B} frames {W0}x{H0}, letterbox {W}x{H}, {a.dtype}; predict_into step {ms_pred * 1e3:.0f} us; "
           f"measure on {live} instances ({live / B:.1f} per frame), capacity {cap}")
@@ -77,6 +91,25 @@ def main():
         name = "native (vti_masks_native rows)" if native else "letterbox (vti_masks bits)"
         print(f"  {name:31s} {ms * 1e3:8.1f} us/call  {ms * 1e3 / B:6.2f} us/frame  {100 * ms / ms_pred:5.2f} % of the step"
               f"  (records only: {ms_lean * 1e3:.1f} us)  status 0 in {int((st == 0).sum())}/{B} frames")
+        for n, (table, idx) in tables.items():
+            ms = timed(lambda: eng.measure(o, table, H0, W0, native=native, result=res, cameras=idx), a.iters)
+            st = res["frame_i32"][:, 0].cpu().numpy()
+            print(f"    vti_measure_cameras, {n:3d} cameras    {ms * 1e3:8.1f} us/call  {ms * 1e3 / B:6.2f} us/frame"
+                  f"  status 0 in {int((st == 0).sum())}/{B} frames")
+        if a.groups:
+            G, per = a.groups, B // a.groups
+            oh = off.cpu()
+            views = []
+            for g in range(G):
+                b0, b1 = g * per, (g + 1) * per
+                s0, s1 = int(oh[b0]), int(oh[b1])
+                og = dict(dets=dets[b0:b1], xyxy=xyxy[b0:b1], counts=counts[b0:b1], offsets=(off[b0:b1 + 1] - s0).contiguous(),
+                          masks=masks[s0:s1])
+                rg = dict(frame_f64=res["frame_f64"][b0:b1], frame_i32=res["frame_i32"][b0:b1], stitch_f64=res["stitch_f64"][s0:s1],
+                          stitch_i32=res["stitch_i32"][s0:s1])
+                views.append((og, rg))
+            ms = timed(lambda: [eng.measure(og, params, H0, W0, native=native, result=rg) for og, rg in views], a.iters)
+            print(f"    work-around: {G} vti_measure calls    {ms * 1e3:8.1f} us/all   {ms * 1e3 / B:6.2f} us/frame")
 
 
 if __name__ == "__main__":

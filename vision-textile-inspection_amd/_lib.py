@@ -37,7 +37,7 @@ class VtiMeasureParams(C.Structure):
                 ("kmeans_iters", C.c_int32), ("drop_empty", C.c_int32), ("frame_buffer", C.c_int32)]
 
 
-VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES = 0, 1, 2
+VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_BAD_CAMERA = 0, 1, 2, 3
 VTI_STITCH_KEPT, VTI_STITCH_MASK, VTI_STITCH_SELECTED, VTI_STITCH_NEAR, VTI_STITCH_DIST, VTI_STITCH_WIDTH = 1, 2, 4, 8, 16, 32
 VTI_MEASURE_MAX_DET = 1000
 
@@ -91,6 +91,10 @@ SIGNATURES = {
     "vti_measure_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_measure": (_I32, [_P, C.POINTER(VtiMeasureParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
                            _P, _P, _P, _P, _P]),
+    "vti_measure_cameras_bytes": (_I64, [_I32]),
+    "vti_measure_pack_cameras": (_I32, [_P, C.POINTER(VtiMeasureParams), _I32, _P, _SZ]),
+    "vti_measure_cameras": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
+                                   _P, _P, _P, _P, _P]),
     "vti_mask_polygons_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_mask_polygons": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),

@@ -6,6 +6,7 @@
 //     intersection, measurement.py:44-65) and the 1-D 2-means of measurement.py:88-113, in float64 as the reference.
 // All integer results are exact; the float64 ones follow the reference's operation order (-ffp-contract=off).
 #include <climits>
+#include <cstring>
 #include <type_traits>
 
 #include "vti_internal.h"
@@ -152,6 +153,29 @@ hipError_t launch_mask_stats_bits(const uint8_t* bits, int n, const int* n_live,
 // instance is kept when the centre of its int-truncated box lies inside roi = {x_min, y_min, x_max, y_max}, bounds inclusive), and
 // the NATIVE form for the frame-size rows of vti_masks_native (wpr words per row, zero pad bits): there the resize is the identity
 // and a mask is zero outside the rows [y1, y2) of its frame-px box, so those bound the search.
+// `sel` carries the class and the ROI as given (clamped to H0 x W0 here).  With a camera table (`table` != nullptr,
+// vti_measure_cameras) they come from row cam_of_frame[b] instead, range-checked against n_cams before the row's address is formed;
+// a frame whose index is outside gets an all -1 envelope.
+struct EnvSel { int cls, roi_enabled, roi[4]; };
+// One camera of vti_measure: the pixel -> world model (section N3a below) and config.py's settings.  vti_measure passes one row by
+// value in the launch arguments; vti_measure_cameras keeps a table of rows in device memory (vti_measure_pack_cameras) and an index
+// per frame.  The ROI is stored as given: roi_clamp applies the frame size where it is known.
+struct GeomParams { double fx, fy, cx, cy, k1, k2, p1, p2, k3; double R[9]; double t[3]; double n[3]; double d; };
+struct CameraRow {
+    GeomParams g;
+    double max_px, two_row;
+    int stitch_id, fabric_id, roi_enabled, roi[4];
+    int min_stitches, nb, skip_cluster, kmeans_iters, drop_empty;
+    int pad[2];                             // rows are a multiple of 16 bytes; zero, so that equal settings pack to equal bytes
+};
+static_assert(sizeof(CameraRow) % 16 == 0, "camera table rows keep 16-byte alignment");
+
+// measurement.py:220-238: the ROI clamped to the frame, inactive (false) when disabled or degenerate
+__device__ __forceinline__ bool roi_clamp(int enabled, const int* r, int H0, int W0, int4& roi) {
+    roi = make_int4(max(0, min(r[0], W0 - 1)), max(0, min(r[1], H0 - 1)), max(0, min(r[2], W0 - 1)), max(0, min(r[3], H0 - 1)));
+    return enabled && roi.x < roi.z && roi.y < roi.w;
+}
+
 __device__ __forceinline__ bool roi_keeps(const float* bx, int4 roi) {
     const long long x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];    // python int(): truncation
     return 2LL * roi.x <= x1 + x2 && x1 + x2 <= 2LL * roi.z && 2LL * roi.y <= y1 + y2 && y1 + y2 <= 2LL * roi.w;
@@ -160,11 +184,27 @@ __device__ __forceinline__ bool roi_keeps(const float* bx, int4 roi) {
 template <bool NATIVE>
 __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ offsets,
                                                             const float* __restrict__ dets, int max_det, int row, int capacity,
-                                                            int cls, int H, int W, int H0, int W0, int* __restrict__ envelope,
-                                                            const float* __restrict__ xyxy, int roi_on, int4 roi, int native_wpr) {
+                                                            EnvSel sel, int H, int W, int H0, int W0, int* __restrict__ envelope,
+                                                            const float* __restrict__ xyxy, int native_wpr,
+                                                            const CameraRow* __restrict__ table, const int* __restrict__ cam_of_frame,
+                                                            int n_cams) {
     extern __shared__ int yl[];             // [H] (not NATIVE)
     __shared__ int red[4][64];
     const int tid = threadIdx.x, b = blockIdx.y;
+    if (table) {
+        const int ci = cam_of_frame[b];
+        if (ci < 0 || ci >= n_cams) {                           // uniform over the workgroup
+            const int xo = blockIdx.x * 64 + tid;
+            if (tid < 64 && xo < W0) envelope[(size_t)b * W0 + xo] = -1;
+            return;
+        }
+        const CameraRow* c = table + ci;
+        sel.cls = c->fabric_id; sel.roi_enabled = c->roi_enabled;
+        for (int k = 0; k < 4; ++k) sel.roi[k] = c->roi[k];
+    }
+    const int cls = sel.cls;
+    int4 roi;
+    const bool roi_on = roi_clamp(sel.roi_enabled, sel.roi, H0, W0, roi);
     if (!NATIVE) {
         for (int i = tid; i < H; i += 256) yl[i] = -1;
         __syncthreads();
@@ -223,7 +263,8 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
     if (B == 0) return hipSuccess;
     if ((W & 31) || ((uintptr_t)bits & 3) || (size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)bits, offsets,
-                       dets, max_det, 6 + nm, capacity, cls, H, W, H0, W0, envelope, (const float*)nullptr, 0, make_int4(0, 0, 0, 0), 0);
+                       dets, max_det, 6 + nm, capacity, EnvSel{cls, 0, {0, 0, 0, 0}}, H, W, H0, W0, envelope, (const float*)nullptr, 0,
+                       (const CameraRow*)nullptr, (const int*)nullptr, 0);
     return hipGetLastError();
 }
 
@@ -233,7 +274,7 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
 //   x = (x0 - dX) icdist; y = (y0 - dY) icdist          (k4..k6, s1..s4, tilt = 0 for the 5-coefficient model of
 // camera_calibration.json; OpenCV leaves the loop if icdist < 0).  Then the ray (x, y, 1) meets the plane n.X + d = 0:
 //   s = -d / (n . ray); X_cam = s ray; X_world = R^T (X_cam - t); no point when |n . ray| < 1e-9.
-struct GeomParams { double fx, fy, cx, cy, k1, k2, p1, p2, k3; double R[9]; double t[3]; double n[3]; double d; };
+// (GeomParams: with CameraRow above.)
 
 // One point; false where the reference returns None.  Shared by pixels_to_world_kernel and measure_frames_kernel.
 __device__ __forceinline__ bool pixel_to_world(const GeomParams& g, double u, double v, double o[3]) {
@@ -396,13 +437,11 @@ hipError_t launch_kmeans1d2(const double* values, const int* counts, int B, int 
 //   4. row selection: 2-means on one lane with the cluster means recomputed from the returned labels, or the median split;
 //   5. the final set (proximity, or the selected row when nothing is near), the ordered distance / width lists and their means.
 struct MeasureArgs {
-    GeomParams g;
+    CameraRow cam;                                                  // the one camera (TABLE = false)
+    const CameraRow* table; const int* cam_of_frame; int n_cams;    // or a row per frame (TABLE = true)
     const long long* stats; const int* raw; const int* envelope;
     const float* dets; const float* xyxy; const int* counts; const int* offsets;
-    int max_det, row, capacity, W0;
-    int stitch_id, fabric_id, roi_on; int4 roi;
-    int min_stitches, nb, skip_cluster, kmeans_iters, drop_empty;
-    double max_px, two_row;
+    int max_det, row, capacity, H0, W0;
     double* frame_f64; int* frame_i32; double* stitch_f64; int* stitch_i32;
 };
 
@@ -450,6 +489,9 @@ __device__ __forceinline__ double dist_mm(const double* p, const double* q) {
 
 enum { F_FINAL = 64, F_CAND = 128 };   // kernel-internal flag bits (final set, distance computable), above the VTI_STITCH_* bits
 
+// TABLE: the frame's settings are row cam_of_frame[b] of the camera table, copied once before anything is stored;
+// otherwise the row in the launch arguments.  Either way the arithmetic below sees the same values in the same order.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
     extern __shared__ double msm[];        // M = max_det: cy | width | dist | edge | g0 | g1 (f64), then idx | flags | lab0 | lab1 (i32)
     const int M = a.max_det;
@@ -463,6 +505,27 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
     const int* env = a.envelope + (size_t)b * a.W0;
     const double NaN = __builtin_nan("");
     const int W0 = a.W0;
+    int ci = 0;
+    if (TABLE) {
+        ci = a.cam_of_frame[b];
+        if (ci < 0 || ci >= a.n_cams) {         // uniform over the workgroup; no table address has been formed
+            for (int i = tid; i < n; i += 256) {
+                const int s = s0 + i;
+                if (s < 0 || s >= a.capacity) continue;
+                if (a.stitch_f64) for (int k = 0; k < 7; ++k) a.stitch_f64[(size_t)s * 7 + k] = NaN;
+                if (a.stitch_i32) { a.stitch_i32[(size_t)s * 2] = 0; a.stitch_i32[(size_t)s * 2 + 1] = -1; }
+            }
+            if (tid == 0) {
+                a.frame_f64[2 * b] = NaN; a.frame_f64[2 * b + 1] = NaN;
+                int* o = a.frame_i32 + 6 * b;
+                o[0] = VTI_MEASURE_BAD_CAMERA; o[1] = o[2] = o[3] = o[4] = o[5] = 0;
+            }
+            return;
+        }
+    }
+    const CameraRow r = TABLE ? a.table[ci] : a.cam;
+    int4 roi;
+    const bool roi_on = roi_clamp(r.roi_enabled, r.roi, a.H0, W0, roi);
 
     // 1. stitch list and fabric count (measurement.py:248-273)
     int n_st = 0, n_fab = 0;
@@ -475,9 +538,9 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
             const bool raw = live && (a.raw ? a.raw[s] != 0 : m00 > 0);
             const size_t di = (size_t)b * M + i;
             const int cls = (int)a.dets[di * a.row + 5];
-            const bool keep = (!a.drop_empty || raw) && (!a.roi_on || roi_keeps(a.xyxy + di * 4, a.roi));
-            st = keep && cls == a.stitch_id;
-            fab = keep && cls == a.fabric_id && m00 > 0;
+            const bool keep = (!r.drop_empty || raw) && (!roi_on || roi_keeps(a.xyxy + di * 4, roi));
+            st = keep && cls == r.stitch_id;
+            fab = keep && cls == r.fabric_id && m00 > 0;
             if (!st && live) {
                 if (a.stitch_f64) for (int k = 0; k < 7; ++k) a.stitch_f64[(size_t)s * 7 + k] = NaN;
                 if (a.stitch_i32) { a.stitch_i32[(size_t)s * 2] = 0; a.stitch_i32[(size_t)s * 2 + 1] = -1; }
@@ -520,15 +583,15 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
         double wd = NaN, ds = NaN, ed = NaN;
         if (status == VTI_MEASURE_OK) {
             double pl[3], pr[3];
-            const bool okl = pixel_to_world(a.g, left, cy, pl), okr = pixel_to_world(a.g, right, cy, pr);
+            const bool okl = pixel_to_world(r.g, left, cy, pl), okr = pixel_to_world(r.g, right, cy, pr);
             if (okl && okr) { wd = dist_mm(pr, pl); fl |= VTI_STITCH_WIDTH; }
             const int c = (int)rint(cx);                                   // python round(): half to even
             double med;
-            if (env_median(env, W0, c, a.nb, med) && fabs(cy - rint(med)) < a.max_px) fl |= VTI_STITCH_NEAR;
-            if (env_median(env, W0, min(max(c, 0), W0 - 1), a.nb, med)) {
+            if (env_median(env, W0, c, r.nb, med) && fabs(cy - rint(med)) < r.max_px) fl |= VTI_STITCH_NEAR;
+            if (env_median(env, W0, min(max(c, 0), W0 - 1), r.nb, med)) {
                 ed = med;
                 double ps[3], pe[3];
-                const bool oks = pixel_to_world(a.g, cx, cy, ps), oke = pixel_to_world(a.g, cx, ed, pe);
+                const bool oks = pixel_to_world(r.g, cx, cy, ps), oke = pixel_to_world(r.g, cx, ed, pe);
                 if (oks && oke) { ds = dist_mm(ps, pe); fl |= F_CAND; }
             }
         }
@@ -543,7 +606,7 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
 
     // 4. row selection (measurement.py:370-406)
     if (status == VTI_MEASURE_OK) {
-        if (n_st >= 2 && a.skip_cluster) {
+        if (n_st >= 2 && r.skip_cluster) {
             for (int j = tid; j < n_st; j += 256) {                        // ranks -> the sorted centroids, in g0
                 const double v = s_cy[j];
                 int r = 0;
@@ -552,13 +615,13 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
             }
             __syncthreads();
             const double med = (n_st & 1) ? g0[n_st >> 1] : (g0[(n_st >> 1) - 1] + g0[n_st >> 1]) / 2.0;
-            const bool two = g0[n_st - 1] - g0[0] > a.two_row;
+            const bool two = g0[n_st - 1] - g0[0] > r.two_row;
             for (int j = tid; j < n_st; j += 256)
                 if (!two || s_cy[j] >= med) s_fl[j] |= VTI_STITCH_SELECTED;
         } else if (n_st >= 2) {
             if (tid == 0) {
                 double c0, c1;
-                const int which = kmeans1d2_serial(s_cy, n_st, a.kmeans_iters, lab0, lab1, g0, g1, c0, c1);
+                const int which = kmeans1d2_serial(s_cy, n_st, r.kmeans_iters, lab0, lab1, g0, g1, c0, c1);
                 const int* L = which ? lab1 : lab0;
                 int k0 = 0, k1 = 0;
                 for (int j = 0; j < n_st; ++j) { if (L[j]) g1[k1++] = s_cy[j]; else g0[k0++] = s_cy[j]; }
@@ -616,8 +679,8 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-        a.frame_f64[2 * b] = n_d >= a.min_stitches ? np_pairwise_sum(g0, n_d) / (double)n_d : NaN;      // measurement.py:469-472
-        a.frame_f64[2 * b + 1] = n_w >= a.min_stitches ? np_pairwise_sum(g1, n_w) / (double)n_w : NaN;
+        a.frame_f64[2 * b] = n_d >= r.min_stitches ? np_pairwise_sum(g0, n_d) / (double)n_d : NaN;      // measurement.py:469-472
+        a.frame_f64[2 * b + 1] = n_w >= r.min_stitches ? np_pairwise_sum(g1, n_w) / (double)n_w : NaN;
         int* o = a.frame_i32 + 6 * b;
         o[0] = status; o[1] = n_st; o[2] = n_fab; o[3] = n_sel; o[4] = n_d; o[5] = n_w;
     }
@@ -631,9 +694,26 @@ void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& 
     total = off[2] + up((size_t)B * W0 * sizeof(int));
 }
 
-hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
-                          const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
-                          void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st) {
+size_t measure_camera_row_bytes() { return sizeof(CameraRow); }
+
+// One validated vti_measure_params -> one table row (host).
+void measure_pack_camera(const vti_measure_params& p, void* row) {
+    CameraRow c;
+    memset(&c, 0, sizeof c);
+    c.g = make_geom(p.K, p.dist, p.R, p.t);
+    c.max_px = p.max_px_distance; c.two_row = p.two_row_threshold_px;
+    c.stitch_id = p.stitch_id; c.fabric_id = p.fabric_id; c.roi_enabled = p.roi_enabled ? 1 : 0;
+    for (int k = 0; k < 4; ++k) c.roi[k] = p.roi[k];
+    c.min_stitches = p.min_stitches; c.nb = p.envelope_neighborhood; c.skip_cluster = p.skip_cluster;
+    c.kmeans_iters = p.kmeans_iters; c.drop_empty = p.drop_empty;
+    memcpy(row, &c, sizeof c);
+}
+
+// p: the one camera (vti_measure), or nullptr with a device table of n_cams rows and the frames' indices (vti_measure_cameras).
+hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
+                          int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
+                          int nm, int capacity, int H, int W, int H0, int W0, void* scratch, double* frame_f64, int* frame_i32,
+                          double* stitch_f64, int* stitch_i32, hipStream_t st) {
     if (B == 0) return hipSuccess;
     size_t off[3], total;
     measure_scratch_layout(B, capacity, W0, off, total);
@@ -641,12 +721,12 @@ hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int
     int* raw = (int*)((char*)scratch + off[1]);
     int* env = (int*)((char*)scratch + off[2]);
     const int* n_live = offsets + B;
-    // measurement.py:220-238: the ROI clamped to the frame, inactive when degenerate
-    const int rx1 = max(0, min(p.roi[0], W0 - 1)), ry1 = max(0, min(p.roi[1], H0 - 1));
-    const int rx2 = max(0, min(p.roi[2], W0 - 1)), ry2 = max(0, min(p.roi[3], H0 - 1));
-    const bool roi_on = p.roi_enabled && rx1 < rx2 && ry1 < ry2;
-    const int4 roi = make_int4(rx1, ry1, rx2, ry2);
     const int wpr = native ? 2 * ((W0 + 63) / 64) : W / 32;
+    MeasureArgs a;
+    memset(&a, 0, sizeof a);
+    if (p) measure_pack_camera(*p, &a.cam);
+    else { a.table = (const CameraRow*)table; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
+    const EnvSel sel = {a.cam.fabric_id, a.cam.roi_enabled, {a.cam.roi[0], a.cam.roi[1], a.cam.roi[2], a.cam.roi[3]}};
     if (capacity > 0) {
         if (native) {           // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
             hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
@@ -661,27 +741,22 @@ hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int
     }
     if (native)
         hipLaunchKernelGGL(envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets, dets,
-                           max_det, 6 + nm, capacity, p.fabric_id, H0, W0, H0, W0, env, xyxy, roi_on ? 1 : 0, roi, wpr);
+                           max_det, 6 + nm, capacity, sel, H0, W0, H0, W0, env, xyxy, wpr, a.table, a.cam_of_frame, a.n_cams);
     else {
         if ((size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
         hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
-                           offsets, dets, max_det, 6 + nm, capacity, p.fabric_id, H, W, H0, W0, env,
-                           xyxy, roi_on ? 1 : 0, roi, 0);
+                           offsets, dets, max_det, 6 + nm, capacity, sel, H, W, H0, W0, env, xyxy, 0, a.table, a.cam_of_frame,
+                           a.n_cams);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    MeasureArgs a;
-    a.g = make_geom(p.K, p.dist, p.R, p.t);
     a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
     a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
-    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.W0 = W0;
-    a.stitch_id = p.stitch_id; a.fabric_id = p.fabric_id; a.roi_on = roi_on ? 1 : 0; a.roi = roi;
-    a.min_stitches = p.min_stitches; a.nb = p.envelope_neighborhood; a.skip_cluster = p.skip_cluster;
-    a.kmeans_iters = p.kmeans_iters; a.drop_empty = p.drop_empty;
-    a.max_px = p.max_px_distance; a.two_row = p.two_row_threshold_px;
+    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0;
     a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
     const size_t lds = (size_t)max_det * (6 * sizeof(double) + 4 * sizeof(int));
-    hipLaunchKernelGGL(measure_frames_kernel, dim3(B), dim3(256), lds, st, a);
+    if (a.table) hipLaunchKernelGGL(measure_frames_kernel<true>, dim3(B), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(measure_frames_kernel<false>, dim3(B), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

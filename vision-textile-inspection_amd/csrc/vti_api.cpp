@@ -744,41 +744,85 @@ int64_t vti_measure_scratch_bytes(const vti_ctx* c, int32_t B, int32_t capacity,
     return (int64_t)total;
 }
 
+// The checks of one vti_measure_params (vti_measure's struct, every entry of vti_measure_pack_cameras): nullptr when it is valid.
+static const char* measure_params_error(const vti_measure_params* p) {
+    if (p->stitch_id < 0 || p->fabric_id < 0 || p->stitch_id == p->fabric_id) return "stitch_id and fabric_id must be >= 0 and different";
+    if (p->envelope_neighborhood < 0 || p->envelope_neighborhood > 64) return "envelope_neighborhood must be 0..64";
+    if (p->min_stitches < 1 || p->kmeans_iters < 0 || (p->skip_cluster != 0 && p->skip_cluster != 1) ||
+        (p->drop_empty != 0 && p->drop_empty != 1) || p->frame_buffer < 1)
+        return "bad setting (min_stitches, frame_buffer >= 1; kmeans_iters >= 0; flags 0 or 1)";
+    if (!(p->max_px_distance == p->max_px_distance) || !(p->two_row_threshold_px == p->two_row_threshold_px)) return "NaN threshold";
+    return nullptr;
+}
+
+// vti_measure / vti_measure_cameras: exactly one of p and (table, cam_of_frame) is given.  Every check comes before the first HIP call.
+static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params* p, const void* table, int32_t n_cams,
+                            const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
+                            const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity, int32_t H0,
+                            int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
+                            int32_t* stitch_i32, void* stream) {
+    char msg[200];
+    auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
+    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
+        return bad(VTI_ERR_ARG, "bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
+    if (max_det > VTI_MEASURE_MAX_DET) return bad(VTI_ERR_UNSUPPORTED, "max_det above VTI_MEASURE_MAX_DET");
+    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks)))
+        return bad(VTI_ERR_ARG, "null pointer");
+    if (p)
+        if (const char* e = measure_params_error(p)) return bad(VTI_ERR_ARG, e);
+    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
+        return bad(VTI_ERR_ARG, native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
+    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
+        return bad(VTI_ERR_UNSUPPORTED, "letterbox size too large for the resize tables");
+    if ((int64_t)B * W0 > INT32_MAX) return bad(VTI_ERR_ARG, "B * W0 out of range");
+    if (B && (!scratch || ((uintptr_t)scratch & 255))) return bad(VTI_ERR_ARG, "scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_measure_scratch_bytes(c, B, capacity, W0))
+        return bad(VTI_ERR_ARG, "scratch smaller than vti_measure_scratch_bytes()");
+    if (B == 0) return VTI_OK;
+    if (int32_t drc = check_device(c, fn)) return drc;
+    const vti_desc& d = c->plan.desc;
+    VTI_HIP(c, launch_measure(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H,
+                              d.W, H0, W0, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure kernels");
+    return VTI_OK;
+}
+
 int32_t vti_measure(vti_ctx* c, const vti_measure_params* p, const uint8_t* masks, int32_t native, const float* dets,
                     const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity,
                     int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32,
                     double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    // every check comes before the first HIP call
     if (!c || !p) return fail(c, VTI_ERR_ARG, "vti_measure: null ctx or params");
-    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
-        return fail(c, VTI_ERR_ARG, "vti_measure: bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
-    if (max_det > VTI_MEASURE_MAX_DET) return fail(c, VTI_ERR_UNSUPPORTED, "vti_measure: max_det above VTI_MEASURE_MAX_DET");
-    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks)))
-        return fail(c, VTI_ERR_ARG, "vti_measure: null pointer");
-    if (p->stitch_id < 0 || p->fabric_id < 0 || p->stitch_id == p->fabric_id)
-        return fail(c, VTI_ERR_ARG, "vti_measure: stitch_id and fabric_id must be >= 0 and different");
-    if (p->envelope_neighborhood < 0 || p->envelope_neighborhood > 64)
-        return fail(c, VTI_ERR_ARG, "vti_measure: envelope_neighborhood must be 0..64");
-    if (p->min_stitches < 1 || p->kmeans_iters < 0 || (p->skip_cluster != 0 && p->skip_cluster != 1) ||
-        (p->drop_empty != 0 && p->drop_empty != 1) || p->frame_buffer < 1)
-        return fail(c, VTI_ERR_ARG, "vti_measure: bad setting (min_stitches, frame_buffer >= 1; kmeans_iters >= 0; flags 0 or 1)");
-    if (!(p->max_px_distance == p->max_px_distance) || !(p->two_row_threshold_px == p->two_row_threshold_px))
-        return fail(c, VTI_ERR_ARG, "vti_measure: NaN threshold");
-    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
-        return fail(c, VTI_ERR_ARG, native ? "vti_measure: native masks must be 8-byte aligned" : "vti_measure: masks must be 16-byte aligned");
-    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
-        return fail(c, VTI_ERR_UNSUPPORTED, "vti_measure: letterbox size too large for the resize tables");
-    if ((int64_t)B * W0 > INT32_MAX) return fail(c, VTI_ERR_ARG, "vti_measure: B * W0 out of range");
-    if (B && (!scratch || ((uintptr_t)scratch & 255)))
-        return fail(c, VTI_ERR_ARG, "vti_measure: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_measure_scratch_bytes(c, B, capacity, W0))
-        return fail(c, VTI_ERR_ARG, "vti_measure: scratch smaller than vti_measure_scratch_bytes()");
-    if (B == 0) return VTI_OK;
-    if (int32_t drc = check_device(c, "vti_measure")) return drc;
-    const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_measure(*p, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H, d.W, H0, W0, scratch,
-                              frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure kernels");
+    return measure_impl("vti_measure", c, p, nullptr, 0, nullptr, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0,
+                        scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
+}
+
+int64_t vti_measure_cameras_bytes(int32_t n_cams) {
+    return n_cams < 1 ? 0 : (int64_t)n_cams * (int64_t)measure_camera_row_bytes();
+}
+
+int32_t vti_measure_pack_cameras(vti_ctx* c, const vti_measure_params* params, int32_t n_cams, void* host_table, size_t nbytes) {
+    if (!params || n_cams < 1 || !host_table) return fail(c, VTI_ERR_ARG, "vti_measure_pack_cameras: null list or table, or n_cams < 1");
+    if ((int64_t)nbytes < vti_measure_cameras_bytes(n_cams))
+        return fail(c, VTI_ERR_ARG, "vti_measure_pack_cameras: table smaller than vti_measure_cameras_bytes()");
+    for (int32_t k = 0; k < n_cams; ++k)
+        if (const char* e = measure_params_error(params + k)) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "vti_measure_pack_cameras: camera %d: %s", k, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    for (int32_t k = 0; k < n_cams; ++k) measure_pack_camera(params[k], (char*)host_table + (size_t)k * measure_camera_row_bytes());
     return VTI_OK;
+}
+
+int32_t vti_measure_cameras(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                            int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B,
+                            int32_t max_det, int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes,
+                            double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
+    if (!c || !cameras || !cam_of_frame) return fail(c, VTI_ERR_ARG, "vti_measure_cameras: null ctx, camera table or camera index");
+    if (n_cams < 1) return fail(c, VTI_ERR_ARG, "vti_measure_cameras: n_cams must be >= 1");
+    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
+        return fail(c, VTI_ERR_ARG, "vti_measure_cameras: the camera table must be 16-byte aligned, the index 4-byte aligned");
+    return measure_impl("vti_measure_cameras", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
+                        max_det, capacity, H0, W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
 }
 
 static bool poly_sizes_ok(int32_t H, int32_t W, int32_t row_bytes) {

@@ -283,9 +283,14 @@ hipError_t launch_kmeans1d2(const double* values, const int* counts, int B, int 
                             double* centers, hipStream_t st);
 // vti_measure: per-slot moments, the ROI-kept fabric envelope and the per-frame record; scratch carved as measure_scratch_layout
 void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& total);    // stats i64 [cap,5] | raw i32 [cap] | env i32 [B,W0]
-hipError_t launch_measure(const vti_measure_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
-                          const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
-                          void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st);
+// a camera-table row (vti_measure_pack_cameras): its size and the packing of one validated struct (host)
+size_t measure_camera_row_bytes();
+void measure_pack_camera(const vti_measure_params& p, void* row);
+// p != nullptr: one camera for every frame; else frame b uses row cam_of_frame[b] of the device table (n_cams rows)
+hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
+                          int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
+                          int nm, int capacity, int H, int W, int H0, int W0, void* scratch, double* frame_f64, int* frame_i32,
+                          double* stitch_f64, int* stitch_i32, hipStream_t st);
 
 // polygons.hip: vti_mask_polygons (Results.masks.xy).  The grid is VTI_POLY_WORKGROUPS persistent workgroups, each with its own
 // labelling area of the scratch: parent i32 [R_max] | runs u32 [R_max] | row_start i32 [H+1] | image u64 [H, WW] (only when the

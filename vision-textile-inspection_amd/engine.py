@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import VtiConvInfo, VtiDesc, check, lib
+from ._lib import VtiConvInfo, VtiDesc, VtiMeasureParams, check, lib
 
 # "h2": split-fp16 storage (every element an fp16 (hi, lo) pair, all products on the fp16 matrix pipe): the dtype whose results
 # meet the reference tolerance (mask IoU >= 0.999, |d box| < 1e-3) at a multiple of the fp32 engine's rate -- include/vti.h
@@ -308,17 +308,51 @@ class Engine:
     def measure_scratch_bytes(self, B, capacity, W0):
         return int(lib().vti_measure_scratch_bytes(self._ctx, int(B), int(capacity), int(W0)))
 
-    def measure(self, out, params, H0, W0, native=False, stitch_rows=True, result=None):
+    def pack_cameras(self, params_list, device=None):
+        """The camera table of vti_measure_cameras: one row per measure.MeasureParams (or VtiMeasureParams) of `params_list`, validated
+        and packed by vti_measure_pack_cameras (a VtiError names the failing index) and uploaded once.  -> u8 device tensor to pass as
+        measure(..., params=table, cameras=...); row k is camera k."""
+        cps = [p.to_c() if hasattr(p, "to_c") else p for p in params_list]
+        n = len(cps)
+        if n < 1:
+            raise ValueError("pack_cameras: at least one camera")
+        arr = (VtiMeasureParams * n)(*cps)
+        nbytes = int(lib().vti_measure_cameras_bytes(n))
+        host = torch.empty(nbytes, dtype=torch.uint8)
+        check(self._ctx, lib().vti_measure_pack_cameras(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
+        return host.to(device or self.device or "cuda")
+
+    def measure(self, out, params, H0, W0, native=False, stitch_rows=True, result=None, cameras=None):
         """The per-frame measurement of measurement.py's process_frame for every frame of an alloc_outputs() set that predict_into()
         (or nms/masks/scale_boxes) filled: vti_measure.  params: a measure.MeasureParams (or a VtiMeasureParams).  native=True: the
         masks are frame-size rows (predict_into(native=True)).  Returns device tensors, no host synchronisation:
         dict(frame_f64 [B,2] avg_dist_mm, avg_width_mm (NaN = None), frame_i32 [B,6] status, n_stitch, n_fabric, n_selected, n_dist,
         n_width, and with stitch_rows the per-slot stitch_f64 [capacity,7], stitch_i32 [capacity,2]).  `result`: the same dict
-        preallocated (any of its tensors reused)."""
-        cp = params.to_c() if hasattr(params, "to_c") else params
+        preallocated (any of its tensors reused).
+        cameras (vti_measure_cameras): the camera of every frame, an int32 device tensor [B] (checked on the device: a frame whose
+        index is outside the table reports status VTI_MEASURE_BAD_CAMERA) or a host sequence (range-checked here, ValueError); then
+        `params` is the table of pack_cameras() or a list of MeasureParams (packed and uploaded on every call: pack once instead)."""
         dets, masks = out["dets"], out["masks"]
         B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
         dev = dets.device
+        if cameras is not None:
+            table = params if isinstance(params, torch.Tensor) else self.pack_cameras(params, dev)
+            row = int(lib().vti_measure_cameras_bytes(1))
+            if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
+                raise ValueError("measure: params must be the u8 table of pack_cameras() on the outputs' device")
+            n_cams = table.numel() // row
+            if isinstance(cameras, torch.Tensor) and cameras.is_cuda:
+                if cameras.dtype != torch.int32 or tuple(cameras.shape) != (B,) or not cameras.is_contiguous() or cameras.device != dev:
+                    raise ValueError(f"measure: cameras must be a contiguous int32 [{B}] tensor on the outputs' device")
+            else:
+                host = np.asarray(cameras.numpy() if isinstance(cameras, torch.Tensor) else cameras)
+                if host.shape != (B,) or host.dtype.kind not in "iu":
+                    raise ValueError(f"measure: cameras must be {B} integers, one per frame")
+                if B and (host.min() < 0 or host.max() >= n_cams):
+                    raise ValueError(f"measure: camera index outside [0, {n_cams})")
+                cameras = torch.from_numpy(host.astype(np.int32)).to(dev)
+        else:
+            cp = params.to_c() if hasattr(params, "to_c") else params
         r = dict(result or {})
         if "frame_f64" not in r:
             r["frame_f64"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
@@ -333,10 +367,13 @@ class Engine:
         ws = getattr(self, "_measure_ws", None)
         if ws is None or ws.numel() < need or ws.device != dev:
             ws = self._measure_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        check(self._ctx, lib().vti_measure(
-            self._ctx, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]),
-            _ptr(out["counts"]), _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(),
-            _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream()))
+        rest = (_ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]),
+                _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(), _ptr(r["frame_f64"]),
+                _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream())
+        if cameras is not None:
+            check(self._ctx, lib().vti_measure_cameras(self._ctx, _ptr(table), n_cams, _ptr(cameras), *rest))
+        else:
+            check(self._ctx, lib().vti_measure(self._ctx, C.byref(cp), *rest))
         return r
 
     # ---- Results.masks.xy: instance polygons in frame pixels (vti_mask_polygons) -------------------------------------------

@@ -3,6 +3,8 @@
     params = MeasureParams.from_files("camera_calibration.json", "extrinsics.json")        measurement.py:130-140
     sm = StitchMeasurer(YOLO(path), params)
     records = sm.process_frames(frames)          # one dict per frame, as process_frame returns (main.py:211-226)
+    mc = MultiCameraMeasurer(YOLO(path), [params_cam0, params_cam1, ...])
+    records = mc.process_frames(frames, cameras) # a batch that mixes cameras: cameras[b] = the camera of frame b
 
 The per-frame work (ROI filter, moments, fabric envelope, widths, row selection, proximity filter, distances, averages) runs in
 libvti's vti_measure on the predict output set that is already on the device; the host reads back B small records once and keeps
@@ -18,10 +20,11 @@ from datetime import datetime
 import numpy as np
 import torch
 
-from ._lib import VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VtiMeasureParams
+from ._lib import VTI_MEASURE_BAD_CAMERA, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VtiMeasureParams
 from .consumer import rodrigues
 
-ERRORS = {VTI_MEASURE_NO_FABRIC: "Fabric not detected", VTI_MEASURE_NO_STITCHES: "No stitches detected"}
+ERRORS = {VTI_MEASURE_NO_FABRIC: "Fabric not detected", VTI_MEASURE_NO_STITCHES: "No stitches detected",
+          VTI_MEASURE_BAD_CAMERA: "Unknown camera"}     # the last one is this package's: a device-side index outside the table
 
 
 @dataclasses.dataclass
@@ -79,42 +82,14 @@ class MeasureParams:
         return p
 
 
-class StitchMeasurer:
-    """StitchMeasurementApp.process_frame without the camera and the drawing: model = a vti_amd YOLO, params = MeasureParams.
-    The smoothing deques live here, so consecutive calls continue one stream of frames, as the reference's app does."""
+class CameraStream:
+    """One camera's smoothing state: the reference's two frame_buffer-long deques (measurement.py:474-484)."""
 
-    def __init__(self, model, params, frame_buffer=8):
-        self.model = model
-        self.params = dataclasses.replace(params, frame_buffer=int(frame_buffer), drop_empty=bool(model.drop_empty_masks))
-        self.frame_buf_dist = deque(maxlen=frame_buffer)
-        self.frame_buf_width = deque(maxlen=frame_buffer)
-        self._cp = self.params.to_c()
-        self._res = {}
+    def __init__(self, frame_buffer):
+        self.dist = deque(maxlen=frame_buffer)
+        self.width = deque(maxlen=frame_buffer)
 
-    @torch.inference_mode()
-    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
-        """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them.  The reference predicts on the RGB conversion
-        with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
-        Returns one record per frame, in frame order, with the smoothing applied frame by frame."""
-        eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks)
-        key = (id(o), B)
-        res = self._res.get(key)
-        if res is None:           # one buffer for both records: a single device -> host read
-            buf = torch.empty(B * 16 + B * 24, dtype=torch.uint8, device=o["dets"].device)
-            res = dict(buf=buf, frame_f64=buf[:B * 16].view(torch.float64).view(B, 2),
-                       frame_i32=buf[B * 16:].view(torch.int32).view(B, 6))
-            self._res = {key: res}
-        eng.measure(o, self._cp, H0, W0, native=bool(retina_masks), stitch_rows=False, result=res)
-        host = res["buf"].cpu().numpy()
-        f64 = host[:B * 16].view(np.float64).reshape(B, 2)
-        i32 = host[B * 16:].view(np.int32).reshape(B, 6)
-        return [self._record(f64[b], i32[b]) for b in range(B)]
-
-    def process_frame(self, frame, **kw):
-        """One frame: the record process_frame returns (without the annotated image)."""
-        return self.process_frames(np.asarray(frame)[None], **kw)[0]
-
-    def _record(self, f64, i32):
+    def record(self, f64, i32):
         """measurement.py:285-287, 333-337 (errors: nothing appended) and 469-510 (averages -> deques -> medians)."""
         status = int(i32[0])
         if status in ERRORS:
@@ -124,10 +99,92 @@ class StitchMeasurer:
         avg_width = None if np.isnan(f64[1]) else float(f64[1])
         smooth_dist = smooth_width = None
         if avg_dist is not None:
-            self.frame_buf_dist.append(avg_dist)
-            smooth_dist = float(np.median(self.frame_buf_dist))
+            self.dist.append(avg_dist)
+            smooth_dist = float(np.median(self.dist))
         if avg_width is not None:
-            self.frame_buf_width.append(avg_width)
-            smooth_width = float(np.median(self.frame_buf_width))
+            self.width.append(avg_width)
+            smooth_width = float(np.median(self.width))
         return {'edge_distance_mm': smooth_dist, 'stitch_width_mm': smooth_width, 'stitch_count': int(i32[4]),
                 'timestamp': datetime.now()}
+
+
+class _DeviceStage:
+    """predict + one measure call + one device -> host read of the B frame records."""
+
+    def __init__(self, model):
+        self.model = model
+        self._res = {}
+
+    @torch.inference_mode()
+    def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks):
+        """-> (f64 [B,2], i32 [B,6]) on the host.  params / cameras as Engine.measure takes them; a callable `params` is called with
+        (engine, device) once the outputs exist (the camera table needs both)."""
+        eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks)
+        key = (id(o), B)
+        res = self._res.get(key)
+        if res is None:           # one buffer for both records: a single device -> host read
+            buf = torch.empty(B * 16 + B * 24, dtype=torch.uint8, device=o["dets"].device)
+            res = dict(buf=buf, frame_f64=buf[:B * 16].view(torch.float64).view(B, 2),
+                       frame_i32=buf[B * 16:].view(torch.int32).view(B, 6))
+            self._res = {key: res}
+        if callable(params):
+            params = params(eng, o["dets"].device)
+        eng.measure(o, params, H0, W0, native=bool(retina_masks), stitch_rows=False, result=res, cameras=cameras)
+        host = res["buf"].cpu().numpy()
+        return host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
+
+
+class StitchMeasurer(_DeviceStage):
+    """StitchMeasurementApp.process_frame without the camera and the drawing: model = a vti_amd YOLO, params = MeasureParams.
+    The smoothing deques live here, so consecutive calls continue one stream of frames, as the reference's app does."""
+
+    def __init__(self, model, params, frame_buffer=8):
+        super().__init__(model)
+        self.params = dataclasses.replace(params, frame_buffer=int(frame_buffer), drop_empty=bool(model.drop_empty_masks))
+        self._stream = CameraStream(frame_buffer)
+        self.frame_buf_dist, self.frame_buf_width = self._stream.dist, self._stream.width
+        self._record = self._stream.record
+        self._cp = self.params.to_c()
+
+    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
+        """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them.  The reference predicts on the RGB conversion
+        with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
+        Returns one record per frame, in frame order, with the smoothing applied frame by frame."""
+        f64, i32 = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks)
+        return [self._record(f64[b], i32[b]) for b in range(len(f64))]
+
+    def process_frame(self, frame, **kw):
+        """One frame: the record process_frame returns (without the annotated image)."""
+        return self.process_frames(np.asarray(frame)[None], **kw)[0]
+
+
+class MultiCameraMeasurer(_DeviceStage):
+    """StitchMeasurer for batches that mix cameras: params_by_camera[c] = camera c's MeasureParams (calibration, ROI, thresholds).
+    One predict, one vti_measure_cameras and one device -> host read per batch; every camera keeps its own smoothing stream, so the
+    records equal those of one StitchMeasurer per camera, each fed only its camera's frames in the same order."""
+
+    def __init__(self, model, params_by_camera, frame_buffer=8):
+        super().__init__(model)
+        self.params = [dataclasses.replace(p, frame_buffer=int(frame_buffer), drop_empty=bool(model.drop_empty_masks))
+                       for p in params_by_camera]
+        if not self.params:
+            raise ValueError("MultiCameraMeasurer: at least one camera")
+        self.streams = [CameraStream(frame_buffer) for _ in self.params]
+        self._tables = {}
+
+    def _table(self, eng, device):
+        key = (id(eng), str(device))
+        if key not in self._tables:       # packed, validated and uploaded once per engine and device
+            self._tables[key] = (eng, eng.pack_cameras(self.params, device))
+        return self._tables[key][1]
+
+    def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
+        """frames as StitchMeasurer.process_frames; cameras: one index into params_by_camera per frame (host integers).  Returns one
+        record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame order."""
+        cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
+        f64, i32 = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks)
+        return self._records(f64, i32, cams.tolist())
+
+    def _records(self, f64, i32, cams):
+        """Frame b's record from camera cams[b]'s stream, in frame order."""
+        return [dict(self.streams[c].record(f64[b], i32[b]), camera=int(c)) for b, c in enumerate(cams)]
