@@ -302,6 +302,58 @@ int32_t vti_measure_cameras(vti_ctx* ctx, const void* dev_cameras, int32_t n_cam
                             int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32,
                             double* stitch_f64, int32_t* stitch_i32, void* stream);
 
+/* ---- batches whose frames differ in size: one call for cameras of several resolutions ---------------------------------------- */
+/* Ultralytics letterboxes the sources of one predict() that do not share a shape with LetterBox(imgsz, auto=False): every frame is
+ * resized by its own gain and centred on one common H x W canvas (the ctx's), and boxes, polygons and everything else in frame
+ * pixels is mapped back with that frame's own gain and pads.  Here the B frames lie back to back in ONE device buffer (frame b:
+ * u8 [H0[b], W0[b], 3] at byte_offset[b], a multiple of 16) and a FRAME TABLE describes them: packed and validated on the host,
+ * uploaded once and reused while the same frame sizes keep the same batch positions (a fixed camera rig).  A row holds what the
+ * kernels would otherwise recompute per pixel or per box: the resized size and pads, the resize scales, the scale_boxes gain and
+ * pads (double, then one cast to f32, as vti_scale_boxes rounds them), the frame's offset and size; the header holds B, the
+ * canvas, the largest H0 and W0 and total_bytes.  The format is private to the library build that packed it.
+ * Host only: bytes of a table of B frames (0 when B < 1). */
+int64_t vti_frame_table_bytes(int32_t B);
+/* Host only: validates frame b = 0 .. B-1 for an H x W canvas (multiples of 32) -- 1 <= H0, W0 <= 16384, byte_offset >= 0 and a
+ * multiple of 16, byte_offset + 3 * H0 * W0 <= total_bytes (the size of the frame buffer), the resized frame not below 1 px --
+ * with VTI_ERR_ARG and the index of the first failing frame in vti_last_error, then writes the table into host_table (nbytes >=
+ * vti_frame_table_bytes(B)).  Equal inputs give equal bytes.  ctx only receives the error text (may be NULL). */
+int32_t vti_pack_frames(vti_ctx* ctx, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset,
+                        int32_t B, int64_t total_bytes, void* host_table, size_t nbytes);
+/* Host only: what a packed table holds.  b = -1: out_i32 = {B, H, W, max H0, max W0, 0, total_bytes lo, hi}; 0 <= b < B: out_i32 =
+ * {H0, W0, new_h, new_w, top, left, byte_offset lo, hi} and out_f64 (may be NULL) = {scale_x, scale_y, gain, padx, pady} (the
+ * resize scales 1 / (new / orig); the scale_boxes values as the f32 the kernels use). */
+int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[8], double out_f64[5]);
+/* The *_frames calls below take the table twice: host_table, the bytes vti_pack_frames wrote, and dev_table, their copy in device
+ * memory (16-byte aligned).  Every argument check runs before the first HIP call, and it includes the table: host_table must be a
+ * packed table for this ctx's canvas and for exactly B frames, and every row of it is validated again, so each value a kernel forms
+ * an address from (offset, sizes, pads) was checked by the host at the call.  The device copy's CONTENTS are trusted to be those
+ * same bytes, as the camera table's are: other bytes there are undefined behaviour.
+ * U1 for B frames of individual sizes -> u8 [B,H,W,3]; every byte of dev_input is written.  Frame b's canvas equals what
+ * vti_letterbox writes for that frame alone.  dev_frames 16-byte aligned, dev_input 4-byte aligned, B <= max_batch. */
+int32_t vti_letterbox_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t B,
+                             uint8_t* dev_input, void* stream);
+/* U8 with gain, pads and clip bounds of frame b from its row: the same expression and rounding as vti_scale_boxes(H0[b], W0[b]). */
+int32_t vti_scale_boxes_frames(vti_ctx* ctx, const float* dev_dets, const int32_t* dev_counts, const void* host_table,
+                               const void* dev_table, int32_t B, int32_t max_det, float* dev_xyxy, void* stream);
+/* vti_predict for such a batch: vti_letterbox_frames (always; dev_input_scratch is required), the scored forward, NMS, vti_masks
+ * (masks at the canvas size, as Ultralytics' masks.data) and, when dev_xyxy is given, vti_scale_boxes_frames; one stream, no host
+ * synchronisation.  mask_mode | VTI_MASK_NATIVE is VTI_ERR_UNSUPPORTED: frame-resolution masks need frames of one size. */
+int32_t vti_predict_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t B,
+                           int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
+                           int32_t packing, uint8_t* dev_input_scratch, float* dev_pred, void* dev_proto, float* dev_dets,
+                           int32_t* dev_counts, uint8_t* dev_masks, int32_t capacity, int32_t* dev_offsets, float* dev_xyxy,
+                           void* stream);
+/* vti_measure_cameras with H0, W0 of frame b from the frame table (ROI clamp, column clip, resize of the masks): frame b's results
+ * are bit-identical to those of vti_measure_cameras called with H0[b], W0[b] on the same inputs.  Letterbox bit masks only: native
+ * = 1 is VTI_ERR_UNSUPPORTED.  dev_scratch: >= vti_measure_scratch_bytes(ctx, B, capacity, largest W0 of the table) (the envelope
+ * rows are pitched by it).  The slot -> frame search of the moment kernel runs over dev_offsets[0 .. B] and ends inside [0, B)
+ * whatever they hold. */
+int32_t vti_measure_frames(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams, const int32_t* dev_camera_of_frame,
+                           const uint8_t* dev_masks, int32_t native, const float* dev_dets, const float* dev_xyxy,
+                           const int32_t* dev_counts, const int32_t* dev_offsets, const void* host_table, const void* dev_table,
+                           int32_t B, int32_t max_det, int32_t capacity, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
+                           int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
+
 /* ---- Results.masks.xy on device: instance polygons in frame pixels ---------------------------------------------------- */
 /* Ultralytics masks2segments + scale_coords as restated by the package's polygons.py, bit for bit: per mask the outer border of
  * every 8-connected component (traced from its top-most, then left-most pixel; pixels outside H x W, the pad bits of padded rows

@@ -1,0 +1,179 @@
+"""-m gpu: vti_measure_frames -- one measurement call for a batch whose frames differ in size (and mix cameras).  Frame b's rows are
+compared byte for byte with vti_measure_cameras run at frame b's size on the same inputs, and with the per-frame restatement in
+tests/measure_ref.py at the standing tolerance of this stage (counts, flags, ranks exactly; floats 1e-12 relative)."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+import measure_ref as mr
+from gpu_util import need_gpu
+from test_gpu_measure import MAX_DET, _close, _engine, pack, render, scenes
+from test_gpu_measure_cameras import CALIBS, OUT_KEYS, _host
+
+pytestmark = pytest.mark.gpu
+
+MH, MW = 736, 960                       # the canvas (mask size)
+NARROW = (481, 333)
+# camera -> (calibration file, settings): the ROI off, and a ROI wider than any frame (clamped to each frame's own size)
+CAMS = [(0, dict(roi_enabled=False)), (1, dict(roi=(5, 100, 1900, 1000), min_stitches=2, envelope_neighborhood=2))]
+BAD = 7                                 # a camera index outside the table
+
+
+def batch_plan():
+    two, one, roi, nofab, nost, empty, few, far, many, edges, two_b, mix = scenes()
+    # (scene, frame size, camera): four sizes, two cameras, an empty frame between two that have instances
+    return [(two, (960, 1280), 0), (edges, NARROW, 0), ([], (720, 960), 0), (nofab, (1080, 1920), 1), (nost, NARROW, 0),
+            (one, (720, 960), 1), (few, (1080, 1920), BAD), (two_b, (960, 1280), 1), (empty, NARROW, 1), (roi, (960, 1280), 0),
+            (mix, (1080, 1920), 1)]
+
+
+def _params(cam):
+    import vti_amd
+    return vti_amd.MeasureParams(*CALIBS[CAMS[cam][0]], **CAMS[cam][1])
+
+
+def build(plan, dead, seed=1):
+    """The output set of a predict on the mixed batch, hand-made: dets (canvas px), counts, offsets, canvas-size bit masks of
+    capacity = instances - dead (dead < 0: spare slots beyond offsets[B], poisoned)."""
+    rng = np.random.default_rng(seed)
+    B = len(plan)
+    counts = np.array([len(s) for s, _, _ in plan], np.int32)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    cap = int(offsets[-1]) - dead
+    dets = np.zeros((B, MAX_DET, 38), np.float32)
+    masks = np.full((cap, MH, MW // 8), 0xFF, np.uint8)
+    ref = []
+    for b, (insts, (h, w), _) in enumerate(plan):
+        cls, ms = [], []
+        for i, inst in enumerate(insts):
+            m, _, mbox = render(inst, h, w, MH, MW, rng)
+            dets[b, i, :4] = mbox
+            dets[b, i, 4] = 0.9 - 0.001 * i
+            dets[b, i, 5] = inst["cls"]
+            s = offsets[b] + i
+            if s < cap:
+                masks[s] = pack(m, False, MW)
+            cls.append(inst["cls"])
+            ms.append(m if s < cap else None)
+        ref.append((np.array(cls), ms))
+    dev = dict(dets=torch.from_numpy(dets).cuda(), counts=torch.from_numpy(counts).cuda(), offsets=torch.from_numpy(offsets).cuda(),
+               masks=torch.from_numpy(masks).cuda())
+    return dev, ref, offsets, cap
+
+
+def poisoned(B, rows):
+    return dict(frame_f64=torch.full((B, 2), -7.0, dtype=torch.float64, device="cuda"),
+                frame_i32=torch.full((B, 6), -7, dtype=torch.int32, device="cuda"),
+                stitch_f64=torch.full((rows, 7), -7.0, dtype=torch.float64, device="cuda"),
+                stitch_i32=torch.full((rows, 2), -7, dtype=torch.int32, device="cuda"))
+
+
+def check_frame(host, b, cls, boxes, ms, offsets, cap, h, w, cam):
+    rec, st = mr.measure_frame(h, w, cls, boxes, ms, CALIBS[CAMS[cam][0]], **CAMS[cam][1])
+    f64, i32, sf64, si32 = (host[k] for k in OUT_KEYS)
+    exp = [rec["status"], rec["n_stitch"], rec["n_fabric"], rec["n_selected"], rec["n_dist"], rec["n_width"]]
+    assert i32[b].tolist() == exp, (b, cam, i32[b].tolist(), exp)
+    assert _close(f64[b, 0], rec["avg_dist"]) and _close(f64[b, 1], rec["avg_width"]), (b, cam, f64[b], rec)
+    rank = {s["i"]: (j, s) for j, s in enumerate(st)}
+    for i in range(len(cls)):
+        slot = offsets[b] + i
+        if slot >= cap:
+            continue
+        if i not in rank:
+            assert si32[slot].tolist() == [0, -1] and np.isnan(sf64[slot]).all(), (b, i)
+            continue
+        j, s = rank[i]
+        assert si32[slot].tolist() == [s["flags"], j], (b, i, si32[slot].tolist(), s["flags"], j)
+        for k, key in enumerate(("cx", "cy", "left", "right", "width", "edge_y", "dist")):
+            assert _close(sf64[slot, k], s[key]), (b, i, key, sf64[slot, k], s[key])
+    return rec, st
+
+
+@pytest.mark.parametrize("dead", [3, -4], ids=["capacity_below_the_instances", "spare_slots"])
+def test_measure_frames_is_measure_cameras_per_frame_size_and_the_restatement(dead):
+    need_gpu()
+    eng = _engine(MH, MW, 16)
+    plan = batch_plan()
+    B = len(plan)
+    shapes = [hw for _, hw, _ in plan]
+    assert len(set(shapes)) == 4 and min(w for _, w in shapes) == NARROW[1] and plan[2][0] == [] and plan[1][0] and plan[3][0]
+    dev, ref, offsets, cap = build(plan, dead)
+    table, _, _ = eng.pack_frames(shapes, "cuda")
+    cams = eng.pack_cameras([_params(0), _params(1)], "cuda")
+    idx = torch.tensor([c for _, _, c in plan], dtype=torch.int32, device="cuda")
+    dev["xyxy"] = eng.scale_boxes(dev["dets"], dev["counts"], frames=table)
+    rows = cap + 5                                            # result rows at and beyond the capacity: never touched
+    eng.measure(dev, cams, cameras=idx, frames=table, result=poisoned(B, rows))
+    eng._measure_ws.fill_(0x55)                               # whatever the scratch holds beyond a frame's own W0 is not read
+    mixed = _host(eng.measure(dev, cams, cameras=idx, frames=table, result=poisoned(B, rows)))
+    xy = dev["xyxy"].cpu().numpy()
+    live = min(int(offsets[-1]), cap)
+    assert (mixed["stitch_i32"][live:] == -7).all() and (mixed["stitch_f64"][live:] == -7.0).all()
+    # 1. byte for byte vti_measure_cameras at each distinct size, xyxy from vti_scale_boxes(H0_b, W0_b)
+    for h, w in sorted(set(shapes)):
+        uni = dict(dev, xyxy=eng.scale_boxes(dev["dets"], dev["counts"], h, w))
+        plain = _host(eng.measure(uni, cams, h, w, cameras=idx, result=poisoned(B, rows)))
+        xu = uni["xyxy"].cpu().numpy()
+        for b in range(B):
+            if shapes[b] != (h, w):
+                continue
+            assert xu[b].tobytes() == xy[b].tobytes(), b
+            assert mixed["frame_f64"][b].tobytes() == plain["frame_f64"][b].tobytes(), (b, mixed["frame_f64"][b], plain["frame_f64"][b])
+            assert mixed["frame_i32"][b].tobytes() == plain["frame_i32"][b].tobytes(), (b, mixed["frame_i32"][b], plain["frame_i32"][b])
+            lo, hi = min(offsets[b], cap), min(offsets[b + 1], cap)
+            assert mixed["stitch_f64"][lo:hi].tobytes() == plain["stitch_f64"][lo:hi].tobytes(), b
+            assert mixed["stitch_i32"][lo:hi].tobytes() == plain["stitch_i32"][lo:hi].tobytes(), b
+    # 2. the restatement, frame by frame at the frame's own size under its own camera
+    statuses = []
+    for b, ((cls, ms), (h, w), (_, _, cam)) in enumerate(zip(ref, shapes, plan)):
+        if cam == BAD:
+            assert mixed["frame_i32"][b].tolist() == [3, 0, 0, 0, 0, 0] and np.isnan(mixed["frame_f64"][b]).all()
+            lo, hi = min(offsets[b], cap), min(offsets[b + 1], cap)
+            assert hi > lo and (mixed["stitch_i32"][lo:hi] == np.array([0, -1])).all() and np.isnan(mixed["stitch_f64"][lo:hi]).all()
+            statuses.append(3)
+            continue
+        rec, st = check_frame(mixed, b, cls, xy[b, :len(cls)], ms, offsets, cap, h, w, cam)
+        statuses.append(rec["status"])
+        if b == 1:      # the narrowest frame: a stitch whose +-N envelope window runs past ITS last column (W0 - 1 = 332)
+            nb = 3
+            assert rec["status"] == mr.OK and any(round(s["cx"]) + nb > w - 1 and round(s["cx"]) <= w - 1 for s in st), [s["cx"] for s in st]
+    print("statuses", statuses)
+    assert {0, 1, 2, 3} <= set(statuses), statuses
+    assert statuses[0] == mr.OK and statuses[3] == mr.NO_FABRIC and statuses[4] == mr.NO_STITCHES and statuses[2] == mr.NO_FABRIC
+    assert statuses.count(mr.OK) >= 5, statuses
+
+
+def test_multi_camera_measurer_takes_the_mixed_list():
+    """Two consecutive batches of differing frame sizes through MultiCameraMeasurer.process_frames == the host smoothing of one
+    stream per camera fed the per-frame device results of vti_measure_cameras at each frame's own size."""
+    need_gpu()
+    import vti_amd
+    from vti_amd.measure import CameraStream
+    model = vti_amd.YOLO(None, scale="n", nc=2, seed=3, cls_bias=-1.0)
+    params = [dataclasses.replace(_params(c), drop_empty=False) for c in range(2)]
+    mc = vti_amd.MultiCameraMeasurer(model, params, frame_buffer=8)
+    streams = [CameraStream(8) for _ in params]
+    sizes = [(960, 1280), (640, 640), (480, 640), (1080, 1920), (1920, 1920), (960, 960), (481, 333), (1200, 1600)]
+    kw = dict(conf=0.20, iou=0.25, max_det=200, imgsz=960)
+    seen = 0
+    for seed, cams in ((0, [0, 1, 0, 1, 1, 0, 0, 1]), (1, [1, 1, 0, 0, 1, 0, 1, 0])):
+        frames = [np.random.Generator(np.random.PCG64(seed * 10 + k)).integers(0, 256, (h, w, 3), dtype=np.uint8)
+                  for k, (h, w) in enumerate(sizes)]
+        got = mc.process_frames(frames, cams, **kw)
+        assert [g["camera"] for g in got] == cams
+        (eng, table), = mc._tables.values()
+        o, = model._outs.values()                                  # the output set the call measured
+        idx = torch.tensor(cams, dtype=torch.int32, device="cuda")
+        f64, i32 = np.zeros((8, 2)), np.zeros((8, 6), np.int32)
+        for b, (h, w) in enumerate(sizes):
+            uni = dict(o, xyxy=eng.scale_boxes(o["dets"], o["counts"], h, w))
+            r = eng.measure(uni, table, h, w, cameras=idx, stitch_rows=False)
+            f64[b], i32[b] = r["frame_f64"][b].cpu().numpy(), r["frame_i32"][b].cpu().numpy()
+        for b, g in enumerate(got):
+            e = streams[cams[b]].record(f64[b], i32[b])
+            print("frame", b, sizes[b], "camera", cams[b], {k: v for k, v in g.items() if k != "timestamp"})
+            assert {k: v for k, v in g.items() if k not in ("timestamp", "camera")} == {k: v for k, v in e.items() if k != "timestamp"}, b
+            seen += g["edge_distance_mm"] is not None
+    assert seen >= 2                                               # the deques are in use, or the carry-over is not tested

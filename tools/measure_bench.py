@@ -2,13 +2,18 @@
 frame-size ones (vti_masks_native), on the SAME detections (synth_pred -> NMS -> scale_boxes), timed with device events after
 warm-up, next to the predict step it follows.
     python3 tools/measure_bench.py [--dtype h2] [--iters 50] [--B 64] [--n-inst 50] [--cameras N [N ...]] [--groups G]
+                                   [--frames-table [--parent-lib PATH]]
 Prints per mask form: us per call (the three launches), us per frame, and its share of one predict_into step (letterbox ->
 net -> NMS -> masks -> scale_boxes) at the same batch.
 --cameras N: also vti_measure_cameras with a table of N cameras assigned round-robin (frame b -> camera b % N; the two calibration
 files of tests/golden alternate, every row at a camera position of its own, ROI and thresholds shared so that the work is the
 one-camera call's), table and index uploaded before the timing.
 --groups G: also the work-around the table form replaces, G vti_measure calls on views of the same output set, one per contiguous
-group of B / G frames (offsets rebased per group beforehand; a real caller would also have to sort its frames by camera)."""
+group of B / G frames (offsets rebased per group beforehand; a real caller would also have to sort its frames by camera).
+--frames-table: also vti_measure_frames with a frame table of B equal frames (the same work as vti_measure_cameras with one camera,
+letterbox masks) next to vti_measure_cameras, the two interleaved in groups of 10 calls, two runs; --parent-lib PATH (a libvti.so
+built from the parent commit) adds that build's vti_measure_cameras on the same buffers to the interleave."""
+import ctypes as C
 import argparse
 import dataclasses
 import os
@@ -38,6 +43,57 @@ def timed(fn, iters, warmup=5):
     return t0.elapsed_time(t1) / iters
 
 
+def frames_table_case(a, eng, o, res, params, B, H0, W0, cap, max_det):
+    from vti_amd import _lib
+    cams = eng.pack_cameras([params], "cuda")
+    idx = torch.zeros(B, dtype=torch.int32, device="cuda")
+    ft, _, _ = eng.pack_frames([(H0, W0)] * B, "cuda")
+    cases = {"vti_measure_cameras": lambda: eng.measure(o, cams, H0, W0, result=res, cameras=idx),
+             "vti_measure_frames ": lambda: eng.measure(o, cams, result=res, cameras=idx, frames=ft)}
+    eng.measure(o, cams, H0, W0, result=res, cameras=idx)
+    want = {k: res[k].clone() for k in ("frame_f64", "frame_i32", "stitch_f64", "stitch_i32")}
+    eng.measure(o, cams, result=res, cameras=idx, frames=ft)
+    torch.cuda.synchronize()
+    for k, v in want.items():                 # NaN-safe: compare the bytes
+        assert torch.equal(v.view(torch.uint8), res[k].view(torch.uint8)), k
+    if a.parent_lib:
+        L = C.CDLL(a.parent_lib)
+        P, I = C.c_void_p, C.c_int32
+        L.vti_create.restype, L.vti_create.argtypes = I, [C.POINTER(_lib.VtiDesc), C.POINTER(P)]
+        L.vti_measure_pack_cameras.restype, L.vti_measure_pack_cameras.argtypes = I, [P, C.POINTER(_lib.VtiMeasureParams), I, P, C.c_size_t]
+        L.vti_measure_cameras.restype, L.vti_measure_cameras.argtypes = _lib.SIGNATURES["vti_measure_cameras"]
+        ctx = P(0)
+        desc = _lib.VtiDesc(b"n", 2, 32, 16, eng.H, eng.W, B, _lib.VTI_H2)
+        assert L.vti_create(C.byref(desc), C.byref(ctx)) == 0
+        host = torch.zeros(cams.numel(), dtype=torch.uint8)
+        assert L.vti_measure_pack_cameras(ctx, C.byref(params.to_c()), 1, P(host.data_ptr()), host.numel()) == 0
+        pcams = host.cuda()
+        ws = torch.empty(eng.measure_scratch_bytes(B, cap, W0), dtype=torch.uint8, device="cuda")
+        pres = {k: torch.empty_like(v) for k, v in want.items()}
+        ptr = lambda t: P(t.data_ptr())
+
+        def parent():
+            rc = L.vti_measure_cameras(ctx, ptr(pcams), 1, ptr(idx), ptr(o["masks"]), 0, ptr(o["dets"]), ptr(o["xyxy"]), ptr(o["counts"]),
+                                       ptr(o["offsets"]), B, max_det, cap, H0, W0, ptr(ws), ws.numel(), ptr(pres["frame_f64"]),
+                                       ptr(pres["frame_i32"]), ptr(pres["stitch_f64"]), ptr(pres["stitch_i32"]),
+                                       P(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, rc
+        parent()
+        torch.cuda.synchronize()
+        for k, v in want.items():
+            assert torch.equal(v.view(torch.uint8), pres[k].view(torch.uint8)), k
+        cases = dict({"vti_measure_cameras (parent build)": parent}, **cases)
+    for fn in cases.values():
+        timed(fn, 5, warmup=2)
+    for run in range(2):
+        acc = {k: [] for k in cases}
+        for _ in range(max(a.iters // 10, 1)):
+            for k, fn in cases.items():
+                acc[k].append(timed(fn, 10, warmup=0) * 1e3)
+        for k in cases:
+            print(f"    frames-table run {run}  {k:36s} {np.mean(acc[k]):8.1f} us/call  (min group {min(acc[k]):.1f}, max {max(acc[k]):.1f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="h2")
@@ -46,6 +102,8 @@ def main():
     ap.add_argument("--n-inst", type=int, default=50)
     ap.add_argument("--cameras", type=int, nargs="+", default=[])
     ap.add_argument("--groups", type=int, default=0)
+    ap.add_argument("--frames-table", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("measure_bench needs the GPU")
@@ -96,6 +154,8 @@ def main():
             st = res["frame_i32"][:, 0].cpu().numpy()
             print(f"    vti_measure_cameras, {n:3d} cameras    {ms * 1e3:8.1f} us/call  {ms * 1e3 / B:6.2f} us/frame"
                   f"  status 0 in {int((st == 0).sum())}/{B} frames")
+        if a.frames_table and not native:
+            frames_table_case(a, eng, o, res, params, B, H0, W0, cap, max_det)
         if a.groups:
             G, per = a.groups, B // a.groups
             oh = off.cpu()

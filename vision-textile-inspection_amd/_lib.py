@@ -95,6 +95,15 @@ SIGNATURES = {
     "vti_measure_pack_cameras": (_I32, [_P, C.POINTER(VtiMeasureParams), _I32, _P, _SZ]),
     "vti_measure_cameras": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
                                    _P, _P, _P, _P, _P]),
+    "vti_frame_table_bytes": (_I64, [_I32]),
+    "vti_pack_frames": (_I32, [_P, _I32, _I32, _P, _P, _P, _I32, _I64, _P, _SZ]),
+    "vti_frame_table_info": (_I32, [_P, _I32, _P, _P]),
+    "vti_letterbox_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _P]),
+    "vti_scale_boxes_frames": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "vti_predict_frames": (_I32, [_P, _P, _P, _P, _I32, _I32, _F, _D, _I32, _I32, _I32, _I32,
+                                  _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),
+    "vti_measure_frames": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ,
+                                  _P, _P, _P, _P, _P]),
     "vti_mask_polygons_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_mask_polygons": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),

@@ -27,10 +27,14 @@ __device__ __forceinline__ int nn_src(int d, double inv_scale, int ssize) {
 // VW = 32-bit words per load (4: 16-byte loads, slots a multiple of 16 bytes; 2: 8-byte loads, for the native rows of
 // vti_masks_native, whose slots are only a multiple of 8 bytes).  RAW: raw[slot] = 1 iff any bit of the slot is set, the emptiness
 // of the mask as predict returns it (vti_measure's drop_empty), before the resize can skip set source pixels.
-template <int VW, bool RAW>
+// FRAMES (vti_measure_frames): the frames differ in size; the slot's frame is found in offsets[0 .. B] (instance i of frame b is slot
+// offsets[b] + i) and H0, W0 are that frame's, from its row of the frame table.  The search ends at an index in [0, B) whatever
+// the offsets hold, so no table address is formed outside the B rows.
+template <int VW, bool RAW, bool FRAMES = false>
 __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ n_live,
                                                               int H, int W, int H0, int W0, long long* __restrict__ stats,
-                                                              int* __restrict__ raw) {
+                                                              int* __restrict__ raw, const int* __restrict__ offsets = nullptr,
+                                                              const FrameRow* __restrict__ frames = nullptr, int B = 0) {
     extern __shared__ int tab[];            // cx[W] xs[W] xf[W] xl[W] cy[H] ys[H]
     int* cx = tab; int* xs = cx + W; int* xf = xs + W; int* xl = xf + W; int* cy = xl + W; int* ys = cy + H;
     const int tid = threadIdx.x, slot = blockIdx.x;
@@ -38,6 +42,14 @@ __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __
         if (tid < 5) stats[(size_t)slot * 5 + tid] = tid < 3 ? 0 : -1;
         if (RAW && tid == 0) raw[slot] = 0;
         return;
+    }
+    if (FRAMES) {
+        int lo = 0, hi = B;                 // the last b with offsets[b] <= slot
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (offsets[mid] <= slot) lo = mid; else hi = mid;
+        }
+        H0 = frames[lo].H0; W0 = frames[lo].W0;
     }
     const bool ident = H0 == H && W0 == W;
     if (!ident) {
@@ -140,7 +152,7 @@ hipError_t launch_mask_stats_bits(const uint8_t* bits, int n, const int* n_live,
     if (n == 0) return hipSuccess;
     if ((W & 31) || (H & 31) || ((uintptr_t)bits & 15) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024) return hipErrorInvalidValue;      // 16-byte loads
     hipLaunchKernelGGL((mask_stats_bits_kernel<4, false>), dim3(n), dim3(256), (size_t)(4 * W + 2 * H) * 4, st, (const unsigned*)bits, n_live,
-                       H, W, H0, W0, stats, (int*)nullptr);
+                       H, W, H0, W0, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
     return hipGetLastError();
 }
 
@@ -187,15 +199,20 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
                                                             EnvSel sel, int H, int W, int H0, int W0, int* __restrict__ envelope,
                                                             const float* __restrict__ xyxy, int native_wpr,
                                                             const CameraRow* __restrict__ table, const int* __restrict__ cam_of_frame,
-                                                            int n_cams) {
+                                                            int n_cams, const FrameRow* __restrict__ frames = nullptr) {
     extern __shared__ int yl[];             // [H] (not NATIVE)
     __shared__ int red[4][64];
     const int tid = threadIdx.x, b = blockIdx.y;
+    const int pitch = W0;                   // of the envelope rows: W0, or the largest W0 of a frame table (the grid covers it)
+    if (frames) {
+        H0 = frames[b].H0; W0 = frames[b].W0;
+        if ((int)blockIdx.x * 64 >= W0) return;                 // columns this frame does not have: nothing is written
+    }
     if (table) {
         const int ci = cam_of_frame[b];
         if (ci < 0 || ci >= n_cams) {                           // uniform over the workgroup
             const int xo = blockIdx.x * 64 + tid;
-            if (tid < 64 && xo < W0) envelope[(size_t)b * W0 + xo] = -1;
+            if (tid < 64 && xo < W0) envelope[(size_t)b * pitch + xo] = -1;
             return;
         }
         const CameraRow* c = table + ci;
@@ -255,7 +272,7 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
     }
     red[rg][tid & 63] = env;
     __syncthreads();
-    if (rg == 0 && x < W0) envelope[(size_t)b * W0 + x] = max(max(red[0][tid], red[1][tid]), max(red[2][tid], red[3][tid]));
+    if (rg == 0 && x < W0) envelope[(size_t)b * pitch + x] = max(max(red[0][tid], red[1][tid]), max(red[2][tid], red[3][tid]));
 }
 
 hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const float* dets, int B, int max_det, int nm,
@@ -264,7 +281,7 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
     if ((W & 31) || ((uintptr_t)bits & 3) || (size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)bits, offsets,
                        dets, max_det, 6 + nm, capacity, EnvSel{cls, 0, {0, 0, 0, 0}}, H, W, H0, W0, envelope, (const float*)nullptr, 0,
-                       (const CameraRow*)nullptr, (const int*)nullptr, 0);
+                       (const CameraRow*)nullptr, (const int*)nullptr, 0, (const FrameRow*)nullptr);
     return hipGetLastError();
 }
 
@@ -442,6 +459,7 @@ struct MeasureArgs {
     const long long* stats; const int* raw; const int* envelope;
     const float* dets; const float* xyxy; const int* counts; const int* offsets;
     int max_det, row, capacity, H0, W0;
+    const FrameRow* frames;                                         // per-frame H0, W0 (then W0 above is the envelope pitch), or nullptr
     double* frame_f64; int* frame_i32; double* stitch_f64; int* stitch_i32;
 };
 
@@ -504,7 +522,7 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
     const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
     const int* env = a.envelope + (size_t)b * a.W0;
     const double NaN = __builtin_nan("");
-    const int W0 = a.W0;
+    const int H0 = a.frames ? a.frames[b].H0 : a.H0, W0 = a.frames ? a.frames[b].W0 : a.W0;
     int ci = 0;
     if (TABLE) {
         ci = a.cam_of_frame[b];
@@ -525,7 +543,7 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(MeasureArgs a) {
     }
     const CameraRow r = TABLE ? a.table[ci] : a.cam;
     int4 roi;
-    const bool roi_on = roi_clamp(r.roi_enabled, r.roi, a.H0, W0, roi);
+    const bool roi_on = roi_clamp(r.roi_enabled, r.roi, H0, W0, roi);
 
     // 1. stitch list and fabric count (measurement.py:248-273)
     int n_st = 0, n_fab = 0;
@@ -712,9 +730,10 @@ void measure_pack_camera(const vti_measure_params& p, void* row) {
 // p: the one camera (vti_measure), or nullptr with a device table of n_cams rows and the frames' indices (vti_measure_cameras).
 hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
                           int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
-                          int nm, int capacity, int H, int W, int H0, int W0, void* scratch, double* frame_f64, int* frame_i32,
-                          double* stitch_f64, int* stitch_i32, hipStream_t st) {
+                          int nm, int capacity, int H, int W, int H0, int W0, const FrameRow* frames, void* scratch, double* frame_f64,
+                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st) {
     if (B == 0) return hipSuccess;
+    if (frames && native) return hipErrorInvalidValue;
     size_t off[3], total;
     measure_scratch_layout(B, capacity, W0, off, total);
     long long* stats = (long long*)((char*)scratch + off[0]);
@@ -730,29 +749,35 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
     if (capacity > 0) {
         if (native) {           // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
             hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
-                               32 * wpr, H0, 32 * wpr, stats, (int*)nullptr);
+                               32 * wpr, H0, 32 * wpr, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
         } else {
             if ((W & 31) || (H & 31) || ((uintptr_t)masks & 15) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
-                               (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw);
+            if (frames)
+                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, offsets, frames, B);
+            else
+                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, (const int*)nullptr,
+                                   (const FrameRow*)nullptr, 0);
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     if (native)
         hipLaunchKernelGGL(envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets, dets,
-                           max_det, 6 + nm, capacity, sel, H0, W0, H0, W0, env, xyxy, wpr, a.table, a.cam_of_frame, a.n_cams);
+                           max_det, 6 + nm, capacity, sel, H0, W0, H0, W0, env, xyxy, wpr, a.table, a.cam_of_frame, a.n_cams,
+                           (const FrameRow*)nullptr);
     else {
         if ((size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
         hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
                            offsets, dets, max_det, 6 + nm, capacity, sel, H, W, H0, W0, env, xyxy, 0, a.table, a.cam_of_frame,
-                           a.n_cams);
+                           a.n_cams, frames);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
     a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
-    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0;
+    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0; a.frames = frames;
     a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
     const size_t lds = (size_t)max_det * (6 * sizeof(double) + 4 * sizeof(int));
     if (a.table) hipLaunchKernelGGL(measure_frames_kernel<true>, dim3(B), dim3(256), lds, st, a);

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -46,61 +47,177 @@ __device__ __forceinline__ LinTap lin_tap(int d, int ssize, double scale, bool h
     return t;
 }
 
-__global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ frames, int B, int H0, int W0,
-                                                        uint8_t* __restrict__ out, int H, int W, int new_h, int new_w,
-                                                        int top, int left) {
-    const long total = (long)B * H * W;
-    const double scale_x = 1.0 / ((double)new_w / (double)W0);
-    const double scale_y = 1.0 / ((double)new_h / (double)H0);
-    const bool resize = (new_w != W0) || (new_h != H0);
+// A workgroup owns LB_ROWS canvas rows of one frame.  The resize branch (copy through, exact-2x box mean, bilinear) is chosen per
+// frame, so it is uniform over the workgroup; pad rows and pad pixels are stored without touching the source.  The frame's geometry
+// comes from the launch arguments (TABLE = false: vti_letterbox, B equal frames back to back) or from row blockIdx.y of the frame
+// table (vti_letterbox_frames); the arithmetic is the same, so both write the same bytes.
+//   copy / box mean: a thread owns four canvas columns -- 12 output bytes, one store per row -- and reads its 12 / 2 x 24 source
+//     bytes as whole dwords where every address is a multiple of 4 (else byte by byte).
+//   bilinear: a thread owns the columns tid, tid + 256, ... of a 1024-column chunk, so that the lanes of a wave read neighbouring
+//     source pixels.  What depends on the column only (the horizontal taps: a double multiply, a floor and two roundings each) is
+//     computed once per thread and kept in registers for the whole band; the vertical taps are computed once per workgroup into
+//     LDS.  The band's pixels are collected in LDS and leave as 16 bytes per lane.
+constexpr int LB_ROWS = 8, LB_CHUNK = 1024;
+
+__device__ __forceinline__ unsigned lb_byte(const unsigned* w, int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 255u; }
+
+// The six bytes at address p (two neighbouring source pixels) from three ALIGNED dword loads and two funnel shifts: lo = bytes
+// 0..3, hi = bytes 4..5.  A load address is clamped to `last`, the aligned dword that holds the frame's final byte, so nothing is
+// read beyond the frame; a clamped dword only ever supplies bytes of the second pixel where that pixel's weight is 0 (lin_tap: the
+// column clamp at the right edge sets f = 0).
+__device__ __forceinline__ void lb_six(uintptr_t p, uintptr_t last, unsigned& lo, unsigned& hi) {
+    const uintptr_t base = p & ~(uintptr_t)3;
+    const unsigned sh = (unsigned)(p & 3) * 8;
+    const unsigned d0 = *(const unsigned*)base;
+    const unsigned d1 = *(const unsigned*)(base + 4 < last ? base + 4 : last);
+    const unsigned d2 = *(const unsigned*)(base + 8 < last ? base + 8 : last);
+    lo = __funnelshift_r(d0, d1, sh);
+    hi = __funnelshift_r(d1, d2, sh);
+}
+
+template <bool TABLE>
+__global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __restrict__ frames, FrameRow one,
+                                                             const FrameRow* __restrict__ table, uint8_t* __restrict__ out,
+                                                             int H, int W) {
+    __shared__ int4 s_ty[LB_ROWS];
+    __shared__ __attribute__((aligned(16))) uint8_t s_px[LB_ROWS][LB_CHUNK * 3];
+    const int tid = threadIdx.x, b = blockIdx.y, y0 = blockIdx.x * LB_ROWS;
+    const FrameRow r = TABLE ? table[b] : one;
+    const int H0 = r.H0, W0 = r.W0, new_h = r.new_h, new_w = r.new_w, top = r.top, left = r.left;
+    const uint8_t* src = frames + (TABLE ? (size_t)r.offset : (size_t)b * H0 * W0 * 3);
+    const int rows = min(LB_ROWS, H - y0);
     // OpenCV's resize() turns INTER_LINEAR into INTER_AREA when both scales are exactly 2 (hal::resize: is_area_fast &&
     // iscale_x == 2 && iscale_y == 2): the u8 result is the rounded 2x2 box mean, not the bilinear tap pair
-    const bool area2 = W0 == 2 * new_w && H0 == 2 * new_h;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int x = (int)(i % W);
-        long r = i / W;
-        const int y = (int)(r % H);
-        const int b = (int)(r / H);
-        uint8_t* o = out + i * 3;
-        const int dy = y - top, dx = x - left;
-        if (dy < 0 || dy >= new_h || dx < 0 || dx >= new_w) {
-            o[0] = o[1] = o[2] = 114;
-            continue;
+    const bool copy = new_w == W0 && new_h == H0;
+    const bool area2 = !copy && W0 == 2 * new_w && H0 == 2 * new_h;
+    uint8_t* band = out + ((size_t)b * H + y0) * W * 3;
+    if (!copy && !area2) {
+        if (tid < rows) {
+            const int dy = min(max(y0 + tid - top, 0), new_h - 1);
+            const LinTap t = lin_tap(dy, H0, r.scale_y, false);
+            s_ty[tid] = make_int4(t.s0, t.s1, t.a0, t.a1);
         }
-        const uint8_t* src = frames + (size_t)b * H0 * W0 * 3;
-        if (!resize) {
-            const uint8_t* s = src + ((size_t)dy * W0 + dx) * 3;
-            o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
-            continue;
-        }
-        if (area2) {
-            const uint8_t* s0 = src + ((size_t)(2 * dy) * W0 + 2 * dx) * 3;
-            const uint8_t* s1 = s0 + (size_t)W0 * 3;
+        const bool out16 = ((uintptr_t)out & 15) == 0;
+        const uintptr_t last = ((uintptr_t)src + (size_t)H0 * W0 * 3 - 1) & ~(uintptr_t)3;
+        for (int xb = 0; xb < W; xb += LB_CHUNK) {
+            const int ncol = min(LB_CHUNK, W - xb);
+            int xs0[4], xa0[4], xa1[4];
+            bool in[4];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = (uint8_t)((s0[c] + s0[3 + c] + s1[c] + s1[3 + c] + 2) >> 2);
-            continue;
-        }
-        const LinTap tx = lin_tap(dx, W0, scale_x, true);
-        const LinTap ty = lin_tap(dy, H0, scale_y, false);
-        const uint8_t* r0 = src + (size_t)ty.s0 * W0 * 3;
-        const uint8_t* r1 = src + (size_t)ty.s1 * W0 * 3;
+            for (int k = 0; k < 4; ++k) {
+                const int dx = xb + tid + 256 * k - left;
+                in[k] = tid + 256 * k < ncol && dx >= 0 && dx < new_w;
+                const LinTap t = lin_tap(min(max(dx, 0), new_w - 1), W0, r.scale_x, true);
+                xs0[k] = t.s0 * 3; xa0[k] = t.a0; xa1[k] = t.a1;     // the second tap is the next pixel wherever its weight is not 0
+            }
+            __syncthreads();                                    // s_ty is there; the previous chunk has left s_px
+            for (int rr = 0; rr < rows; ++rr) {
+                const int dy = y0 + rr - top;
+                const bool row_in = dy >= 0 && dy < new_h;
+                const int4 ty = s_ty[rr];
+                const uintptr_t r0 = (uintptr_t)src + (size_t)ty.x * W0 * 3, r1 = (uintptr_t)src + (size_t)ty.y * W0 * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int h0 = r0[tx.s0 * 3 + c] * tx.a0 + r0[tx.s1 * 3 + c] * tx.a1;
-            const int h1 = r1[tx.s0 * 3 + c] * tx.a0 + r1[tx.s1 * 3 + c] * tx.a1;
-            int v = (((ty.a0 * (h0 >> 4)) >> 16) + ((ty.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
-            v = v < 0 ? 0 : (v > 255 ? 255 : v);
-            o[c] = (uint8_t)v;
+                for (int k = 0; k < 4; ++k) {
+                    if (tid + 256 * k >= ncol) continue;
+                    uint8_t* o = &s_px[rr][(tid + 256 * k) * 3];
+                    if (!(row_in && in[k])) { o[0] = o[1] = o[2] = 114; continue; }
+                    unsigned a[2], c[2];                        // the six bytes of the two taps' pixels, per source row
+                    lb_six(r0 + xs0[k], last, a[0], a[1]);
+                    lb_six(r1 + xs0[k], last, c[0], c[1]);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const int h0 = (int)lb_byte(a, ch) * xa0[k] + (int)lb_byte(a, 3 + ch) * xa1[k];
+                        const int h1 = (int)lb_byte(c, ch) * xa0[k] + (int)lb_byte(c, 3 + ch) * xa1[k];
+                        int v = (((ty.z * (h0 >> 4)) >> 16) + ((ty.w * (h1 >> 4)) >> 16) + 2) >> 2;
+                        o[ch] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+                    }
+                }
+            }
+            __syncthreads();
+            if (out16) {                                        // ncol is a multiple of 32: 3 * ncol bytes are whole 16-byte pieces
+                const int per_row = ncol * 3 / 16;
+                for (int i = tid; i < rows * per_row; i += 256) {
+                    const int rr = i / per_row, j = i - rr * per_row;
+                    *(uint4*)(band + ((size_t)rr * W + xb) * 3 + 16 * j) = *(const uint4*)&s_px[rr][16 * j];
+                }
+            } else {
+                for (int i = tid; i < rows * ncol * 3; i += 256) {
+                    const int rr = i / (ncol * 3), j = i - rr * ncol * 3;
+                    band[((size_t)rr * W + xb) * 3 + j] = s_px[rr][j];
+                }
+            }
+        }
+        return;
+    }
+    const bool src4 = ((uintptr_t)src & 3) == 0, out4 = ((uintptr_t)out & 3) == 0;
+    // whole-dword source reads where every address is a multiple of 4: copy: (dy * W0 + 4 g - left) * 3; box mean: 12 dy new_w + 6 (4 g - left)
+    const bool wide = src4 && (copy ? ((W0 | left) & 3) == 0 : (left & 1) == 0);
+    for (int g = tid; g < (W >> 2); g += 256) {
+        const int dx0 = 4 * g - left;
+        const bool inside = dx0 >= 0 && dx0 + 3 < new_w;
+        uint8_t* o = band + (size_t)g * 12;
+        for (int rr = 0; rr < rows; ++rr, o += (size_t)W * 3) {
+            const int dy = y0 + rr - top;
+            unsigned w[3] = {0x72727272u, 0x72727272u, 0x72727272u};          // 114
+            if (dy >= 0 && dy < new_h && dx0 + 3 >= 0 && dx0 < new_w) {
+                if (copy) {
+                    const uint8_t* s = src + ((long long)dy * W0 + dx0) * 3;
+                    if (wide && inside) {
+                        const unsigned* q = (const unsigned*)s;
+                        w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 12; ++i) {
+                            const int dx = dx0 + i / 3;
+                            const unsigned v = dx >= 0 && dx < new_w ? s[i] : 114u;
+                            w[i >> 2] = (w[i >> 2] & ~(255u << ((i & 3) * 8))) | (v << ((i & 3) * 8));
+                        }
+                    }
+                } else {
+                    const uint8_t* s0 = src + ((long long)(2 * dy) * W0 + 2 * dx0) * 3;
+                    const uint8_t* s1 = s0 + (size_t)W0 * 3;
+                    if (wide && inside) {
+                        unsigned q0[6], q1[6];
+#pragma unroll
+                        for (int i = 0; i < 6; ++i) { q0[i] = ((const unsigned*)s0)[i]; q1[i] = ((const unsigned*)s1)[i]; }
+#pragma unroll
+                        for (int i = 0; i < 12; ++i) {
+                            const int j = 6 * (i / 3) + i % 3;
+                            const unsigned v = (lb_byte(q0, j) + lb_byte(q0, j + 3) + lb_byte(q1, j) + lb_byte(q1, j + 3) + 2) >> 2;
+                            w[i >> 2] = (w[i >> 2] & ~(255u << ((i & 3) * 8))) | (v << ((i & 3) * 8));
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 12; ++i) {
+                            const int dx = dx0 + i / 3, j = 6 * (i / 3) + i % 3;
+                            unsigned v = 114u;
+                            if (dx >= 0 && dx < new_w) v = (s0[j] + s0[j + 3] + s1[j] + s1[j + 3] + 2) >> 2;
+                            w[i >> 2] = (w[i >> 2] & ~(255u << ((i & 3) * 8))) | (v << ((i & 3) * 8));
+                        }
+                    }
+                }
+            }
+            if (out4) {
+                *(uint3*)o = make_uint3(w[0], w[1], w[2]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 12; ++i) o[i] = (uint8_t)lb_byte(w, i);
+            }
         }
     }
 }
 
-hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, uint8_t* out, int H, int W, int new_h,
-                            int new_w, int top, int left, hipStream_t st) {
-    const long total = (long)B * H * W;
-    if (total == 0) return hipSuccess;
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(letterbox_kernel, dim3(grid), dim3(256), 0, st, frames, B, H0, W0, out, H, W, new_h, new_w, top, left);
+hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, const FrameRow* table, uint8_t* out, int H, int W,
+                            hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    if (W & 3) return hipErrorInvalidValue;
+    const dim3 grid((H + LB_ROWS - 1) / LB_ROWS, B);
+    FrameRow one = {};
+    if (table) hipLaunchKernelGGL(letterbox_rows_kernel<true>, grid, dim3(256), 0, st, frames, one, table, out, H, W);
+    else {
+        frame_row_fill(H, W, H0, W0, 0, one);
+        hipLaunchKernelGGL(letterbox_rows_kernel<false>, grid, dim3(256), 0, st, frames, one, table, out, H, W);
+    }
     return hipGetLastError();
 }
 
@@ -1492,14 +1609,20 @@ hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, 
 // =====================================================================================
 // U8 scale_boxes + clip_boxes
 // =====================================================================================
+// TABLE: gain, pads and clip bounds of frame b from row b of the frame table instead of the launch arguments
+template <bool TABLE>
 __global__ void scale_boxes_kernel(const float* __restrict__ dets, const int* __restrict__ counts, int B, int max_det,
                                    int row, float padx, float pady, float gain, float W0, float H0,
-                                   float* __restrict__ xyxy) {
+                                   const FrameRow* __restrict__ table, float* __restrict__ xyxy) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B * max_det) return;
     const int b = i / max_det, k = i - b * max_det;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (k < counts[b]) {
+        if (TABLE) {
+            const FrameRow* f = table + b;
+            padx = f->padx; pady = f->pady; gain = f->gain; W0 = (float)f->W0; H0 = (float)f->H0;
+        }
         const float* d = dets + (size_t)i * row;
         o.x = fminf(fmaxf((d[0] - padx) / gain, 0.f), W0);
         o.y = fminf(fmaxf((d[1] - pady) / gain, 0.f), H0);
@@ -1509,13 +1632,41 @@ __global__ void scale_boxes_kernel(const float* __restrict__ dets, const int* __
     ((float4*)xyxy)[i] = o;
 }
 
-hipError_t launch_scale_boxes(const float* dets, const int* counts, int B, int max_det, int nm, int H, int W, int H0,
-                              int W0, float* xyxy, hipStream_t st) {
-    if (B * max_det == 0) return hipSuccess;
+// Ultralytics LetterBox geometry (auto=False here: the model size HxW is fixed at vti_create).
+void letterbox_geom(int H0, int W0, int H, int W, int& new_h, int& new_w, int& top, int& left) {
+    const double r = std::min((double)H / H0, (double)W / W0);
+    new_w = (int)std::nearbyint(W0 * r);
+    new_h = (int)std::nearbyint(H0 * r);
+    const double dw = (W - new_w) / 2.0, dh = (H - new_h) / 2.0;
+    top = (int)std::nearbyint(dh - 0.1);
+    left = (int)std::nearbyint(dw - 0.1);
+}
+
+// One frame's row: the letterbox geometry, OpenCV's resize scales, and scale_boxes' gain and pads (double, then one cast to f32).
+void frame_row_fill(int H, int W, int H0, int W0, long long offset, FrameRow& r) {
+    memset(&r, 0, sizeof r);
+    r.offset = offset; r.H0 = H0; r.W0 = W0;
+    letterbox_geom(H0, W0, H, W, r.new_h, r.new_w, r.top, r.left);
+    r.scale_x = 1.0 / ((double)r.new_w / (double)W0);
+    r.scale_y = 1.0 / ((double)r.new_h / (double)H0);
     const double gain = std::min((double)H / H0, (double)W / W0);
     const double padx = nearbyint((W - W0 * gain) / 2 - 0.1), pady = nearbyint((H - H0 * gain) / 2 - 0.1);
-    hipLaunchKernelGGL(scale_boxes_kernel, dim3((B * max_det + 255) / 256), dim3(256), 0, st, dets, counts, B, max_det,
-                       6 + nm, (float)padx, (float)pady, (float)gain, (float)W0, (float)H0, xyxy);
+    r.gain = (float)gain; r.padx = (float)padx; r.pady = (float)pady;
+}
+
+hipError_t launch_scale_boxes(const float* dets, const int* counts, int B, int max_det, int nm, int H, int W, int H0,
+                              int W0, const FrameRow* table, float* xyxy, hipStream_t st) {
+    if (B * max_det == 0) return hipSuccess;
+    const dim3 grid((B * max_det + 255) / 256);
+    if (table) {
+        hipLaunchKernelGGL(scale_boxes_kernel<true>, grid, dim3(256), 0, st, dets, counts, B, max_det, 6 + nm, 0.f, 0.f, 1.f, 0.f, 0.f,
+                           table, xyxy);
+        return hipGetLastError();
+    }
+    FrameRow r;
+    frame_row_fill(H, W, H0, W0, 0, r);
+    hipLaunchKernelGGL(scale_boxes_kernel<false>, grid, dim3(256), 0, st, dets, counts, B, max_det, 6 + nm, r.padx, r.pady, r.gain,
+                       (float)W0, (float)H0, table, xyxy);
     return hipGetLastError();
 }
 

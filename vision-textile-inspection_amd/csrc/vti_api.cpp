@@ -239,23 +239,118 @@ static int32_t check_ready(vti_ctx* c, int32_t B, const char* fn) {
     return VTI_OK;
 }
 
-// Ultralytics LetterBox geometry (auto=False here: the model size HxW is fixed at vti_create).
-static void letterbox_geom(int H0, int W0, int H, int W, int& new_h, int& new_w, int& top, int& left) {
-    const double r = std::min((double)H / H0, (double)W / W0);
-    new_w = (int)std::nearbyint(W0 * r);
-    new_h = (int)std::nearbyint(H0 * r);
-    const double dw = (W - new_w) / 2.0, dh = (H - new_h) / 2.0;
-    top = (int)std::nearbyint(dh - 0.1);
-    left = (int)std::nearbyint(dw - 0.1);
-}
-
 int32_t vti_letterbox(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, uint8_t* out, void* stream) {
     if (!c || !frames || !out || H0 < 1 || W0 < 1 || B < 0) return fail(c, VTI_ERR_ARG, "vti_letterbox: bad argument");
-    int nh, nw, top, left;
-    letterbox_geom(H0, W0, c->plan.desc.H, c->plan.desc.W, nh, nw, top, left);
     if (int32_t drc = check_device(c, "vti_letterbox")) return drc;
-    VTI_HIP(c, launch_letterbox(frames, B, H0, W0, out, c->plan.desc.H, c->plan.desc.W, nh, nw, top, left, (hipStream_t)stream),
+    VTI_HIP(c, launch_letterbox(frames, B, H0, W0, nullptr, out, c->plan.desc.H, c->plan.desc.W, (hipStream_t)stream),
             "letterbox kernel");
+    return VTI_OK;
+}
+
+// ---- batches whose frames differ in size: the frame table ------------------------------------------------------------------
+static const int32_t kFrameMaxSide = 16384;      // vti_mask_polygons' limit
+
+int64_t vti_frame_table_bytes(int32_t B) {
+    return B < 1 ? 0 : (int64_t)sizeof(FrameTableHeader) + (int64_t)B * (int64_t)sizeof(FrameRow);
+}
+
+// What is wrong with one frame of a table for the H x W canvas (nullptr: nothing).  vti_pack_frames runs it on its arguments and
+// every *_frames call on the rows of the host table it is given, so each value a kernel forms an address from was checked by the
+// host at the call.
+static const char* frame_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int64_t offset, int64_t total_bytes) {
+    if (H0 < 1 || W0 < 1) return "H0 and W0 must be >= 1";
+    if (H0 > kFrameMaxSide || W0 > kFrameMaxSide) return "H0 and W0 must be <= 16384";
+    if (offset < 0 || (offset & 15)) return "byte_offset must be >= 0 and a multiple of 16";
+    if (offset > total_bytes || 3 * (int64_t)H0 * W0 > total_bytes - offset) return "the frame runs past total_bytes";
+    int nh, nw, top, left;
+    letterbox_geom(H0, W0, H, W, nh, nw, top, left);
+    if (nh < 1 || nw < 1) return "the resized frame would be below 1 px";
+    if (top < 0 || left < 0 || top + nh > H || left + nw > W) return "the resized frame does not fit the canvas";
+    return nullptr;
+}
+
+int32_t vti_pack_frames(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset, int32_t B,
+                        int64_t total_bytes, void* host_table, size_t nbytes) {
+    if (!H0 || !W0 || !byte_offset || !host_table || B < 1)
+        return fail(c, VTI_ERR_ARG, "vti_pack_frames: null array or table, or B < 1");
+    if (H < 32 || W < 32 || (H & 31) || (W & 31) || total_bytes < 0)
+        return fail(c, VTI_ERR_ARG, "vti_pack_frames: the canvas H, W must be multiples of 32, total_bytes >= 0");
+    if ((int64_t)nbytes < vti_frame_table_bytes(B))
+        return fail(c, VTI_ERR_ARG, "vti_pack_frames: table smaller than vti_frame_table_bytes()");
+    for (int32_t b = 0; b < B; ++b)
+        if (const char* e = frame_error(H, W, H0[b], W0[b], byte_offset[b], total_bytes)) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "vti_pack_frames: frame %d: %s", b, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    FrameTableHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = kFrameTableMagic; h.B = B; h.H = H; h.W = W; h.total_bytes = total_bytes;
+    for (int32_t b = 0; b < B; ++b) {
+        FrameRow r;
+        frame_row_fill(H, W, H0[b], W0[b], byte_offset[b], r);
+        h.max_H0 = std::max(h.max_H0, H0[b]); h.max_W0 = std::max(h.max_W0, W0[b]);
+        memcpy((char*)host_table + sizeof h + (size_t)b * sizeof r, &r, sizeof r);
+    }
+    memcpy(host_table, &h, sizeof h);
+    return VTI_OK;
+}
+
+int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[8], double out_f64[5]) {
+    if (!host_table || !out_i32) return VTI_ERR_ARG;
+    FrameTableHeader h;
+    memcpy(&h, host_table, sizeof h);
+    if (h.magic != kFrameTableMagic || h.B < 1 || b < -1 || b >= h.B) return VTI_ERR_ARG;
+    if (b < 0) {
+        const int32_t v[8] = {h.B, h.H, h.W, h.max_H0, h.max_W0, 0, (int32_t)(h.total_bytes & 0xffffffff), (int32_t)(h.total_bytes >> 32)};
+        memcpy(out_i32, v, sizeof v);
+        return VTI_OK;
+    }
+    FrameRow r;
+    memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+    const int32_t v[8] = {r.H0, r.W0, r.new_h, r.new_w, r.top, r.left, (int32_t)(r.offset & 0xffffffff), (int32_t)(r.offset >> 32)};
+    memcpy(out_i32, v, sizeof v);
+    if (out_f64) { out_f64[0] = r.scale_x; out_f64[1] = r.scale_y; out_f64[2] = r.gain; out_f64[3] = r.padx; out_f64[4] = r.pady; }
+    return VTI_OK;
+}
+
+// The checks every *_frames call makes on its table pair before anything else: the host copy is a packed table for this ctx's
+// canvas and this B whose rows still pass frame_error, and the device copy is a 16-byte aligned pointer.  `h` receives the header.
+static int32_t frames_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
+    char msg[200];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, VTI_ERR_ARG, msg); };
+    if (!c) return VTI_ERR_ARG;
+    if (!host_table || !dev_table) return bad("null frame table (host copy or device copy)");
+    if ((uintptr_t)dev_table & 15) return bad("the device frame table must be 16-byte aligned");
+    memcpy(&h, host_table, sizeof h);
+    if (h.magic != kFrameTableMagic) return bad("host_table is not a table of vti_pack_frames");
+    if (h.B != B || B < 1) return bad("the frame table was packed for another B");
+    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return bad("the frame table was packed for another canvas (H x W)");
+    for (int32_t b = 0; b < B; ++b) {
+        FrameRow r;
+        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+        const char* e = frame_error(h.H, h.W, r.H0, r.W0, r.offset, h.total_bytes);
+        if (!e && (r.H0 > h.max_H0 || r.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
+        if (e) {
+            snprintf(msg, sizeof msg, "%s: frame %d of host_table: %s", fn, b, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    }
+    return VTI_OK;
+}
+
+static const FrameRow* frame_rows(const void* dev_table) { return (const FrameRow*)((const char*)dev_table + sizeof(FrameTableHeader)); }
+
+int32_t vti_letterbox_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                             uint8_t* out, void* stream) {
+    FrameTableHeader h;
+    if (int32_t rc = frames_check("vti_letterbox_frames", c, host_table, dev_table, B, h)) return rc;
+    if (!frames || !out) return fail(c, VTI_ERR_ARG, "vti_letterbox_frames: null frames or output");
+    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 3))
+        return fail(c, VTI_ERR_ARG, "vti_letterbox_frames: dev_frames must be 16-byte aligned, dev_input 4-byte aligned");
+    if (B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_letterbox_frames: B above max_batch");
+    if (int32_t drc = check_device(c, "vti_letterbox_frames")) return drc;
+    VTI_HIP(c, launch_letterbox(frames, B, 0, 0, frame_rows(dev_table), out, h.H, h.W, (hipStream_t)stream), "letterbox kernel");
     return VTI_OK;
 }
 
@@ -641,7 +736,21 @@ int32_t vti_scale_boxes(vti_ctx* c, const float* dets, const int32_t* counts, in
         return fail(c, VTI_ERR_ARG, "vti_scale_boxes: bad argument");
     const vti_desc& d = c->plan.desc;
     if (int32_t drc = check_device(c, "vti_scale_boxes")) return drc;
-    VTI_HIP(c, launch_scale_boxes(dets, counts, B, max_det, d.nm, d.H, d.W, H0, W0, xyxy, (hipStream_t)stream), "scale_boxes kernel");
+    VTI_HIP(c, launch_scale_boxes(dets, counts, B, max_det, d.nm, d.H, d.W, H0, W0, nullptr, xyxy, (hipStream_t)stream), "scale_boxes kernel");
+    return VTI_OK;
+}
+
+int32_t vti_scale_boxes_frames(vti_ctx* c, const float* dets, const int32_t* counts, const void* host_table, const void* dev_table,
+                               int32_t B, int32_t max_det, float* xyxy, void* stream) {
+    FrameTableHeader h;
+    if (int32_t rc = frames_check("vti_scale_boxes_frames", c, host_table, dev_table, B, h)) return rc;
+    if (!dets || !counts || !xyxy || max_det < 1 || ((uintptr_t)xyxy & 15))
+        return fail(c, VTI_ERR_ARG, "vti_scale_boxes_frames: bad argument (null pointer, max_det < 1 or dev_xyxy not 16-byte aligned)");
+    if ((int64_t)B * max_det > INT32_MAX) return fail(c, VTI_ERR_ARG, "vti_scale_boxes_frames: B * max_det out of range");
+    const vti_desc& d = c->plan.desc;
+    if (int32_t drc = check_device(c, "vti_scale_boxes_frames")) return drc;
+    VTI_HIP(c, launch_scale_boxes(dets, counts, B, max_det, d.nm, d.H, d.W, 0, 0, frame_rows(dev_table), xyxy, (hipStream_t)stream),
+            "scale_boxes kernel");
     return VTI_OK;
 }
 
@@ -672,6 +781,30 @@ int32_t vti_predict(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, in
     }
     if ((rc = vti_masks(c, dets, counts, proto, B, max_det, mask_mode, packing, masks, capacity, offsets, stream))) return rc;
     if (xyxy && (rc = vti_scale_boxes(c, dets, counts, B, max_det, H0, W0, xyxy, stream))) return rc;
+    return VTI_OK;
+}
+
+int32_t vti_predict_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                           int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
+                           int32_t packing, uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts,
+                           uint8_t* masks, int32_t capacity, int32_t* offsets, float* xyxy, void* stream) {
+    FrameTableHeader h;
+    int32_t rc = frames_check("vti_predict_frames", c, host_table, dev_table, B, h);
+    if (rc) return rc;
+    if (mask_mode & VTI_MASK_NATIVE)
+        return fail(c, VTI_ERR_UNSUPPORTED, "vti_predict_frames: VTI_MASK_NATIVE needs frames of one size (vti_predict)");
+    if (!frames || !input_scratch || ((uintptr_t)frames & 15) || ((uintptr_t)input_scratch & 3))
+        return fail(c, VTI_ERR_ARG, "vti_predict_frames: dev_frames (16-byte aligned) and dev_input_scratch (4-byte aligned) are required");
+    if (xyxy && (max_det < 1 || ((uintptr_t)xyxy & 15) || !dets || !counts))
+        return fail(c, VTI_ERR_ARG, "vti_predict_frames: bad argument (max_det < 1, null dets / counts or dev_xyxy not 16-byte aligned)");
+    if ((rc = check_ready(c, B, "vti_predict_frames"))) return rc;
+    const vti_desc& d = c->plan.desc;
+    if ((rc = vti_letterbox_frames(c, frames, host_table, dev_table, B, input_scratch, stream))) return rc;
+    float* best = nms_workspace_best(c->ws + c->act_bytes, d.max_batch, c->plan.num_anchors);
+    if ((rc = vti_forward_scored(c, input_scratch, B, swap_rb, pred, proto, best, stream))) return rc;
+    if ((rc = vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream))) return rc;
+    if ((rc = vti_masks(c, dets, counts, proto, B, max_det, mask_mode, packing, masks, capacity, offsets, stream))) return rc;
+    if (xyxy && (rc = vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
     return VTI_OK;
 }
 
@@ -755,12 +888,13 @@ static const char* measure_params_error(const vti_measure_params* p) {
     return nullptr;
 }
 
-// vti_measure / vti_measure_cameras: exactly one of p and (table, cam_of_frame) is given.  Every check comes before the first HIP call.
+// vti_measure / vti_measure_cameras / vti_measure_frames: exactly one of p and (table, cam_of_frame) is given; with `frames` (the rows
+// of a device frame table, already checked against its host copy) H0 and W0 are the table's largest ones.  Every check comes before the first HIP call.
 static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params* p, const void* table, int32_t n_cams,
                             const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
                             const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity, int32_t H0,
                             int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
-                            int32_t* stitch_i32, void* stream) {
+                            int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr) {
     char msg[200];
     auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
     if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
@@ -768,6 +902,7 @@ static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params
     if (max_det > VTI_MEASURE_MAX_DET) return bad(VTI_ERR_UNSUPPORTED, "max_det above VTI_MEASURE_MAX_DET");
     if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks)))
         return bad(VTI_ERR_ARG, "null pointer");
+    if (frames && native) return bad(VTI_ERR_UNSUPPORTED, "native masks need frames of one size (vti_measure_cameras)");
     if (p)
         if (const char* e = measure_params_error(p)) return bad(VTI_ERR_ARG, e);
     if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
@@ -782,7 +917,7 @@ static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params
     if (int32_t drc = check_device(c, fn)) return drc;
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_measure(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H,
-                              d.W, H0, W0, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure kernels");
+                              d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure kernels");
     return VTI_OK;
 }
 
@@ -823,6 +958,22 @@ int32_t vti_measure_cameras(vti_ctx* c, const void* cameras, int32_t n_cams, con
         return fail(c, VTI_ERR_ARG, "vti_measure_cameras: the camera table must be 16-byte aligned, the index 4-byte aligned");
     return measure_impl("vti_measure_cameras", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
                         max_det, capacity, H0, W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
+}
+
+int32_t vti_measure_frames(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                           int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
+                           const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity, void* scratch,
+                           size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
+                           void* stream) {
+    if (!c || !cameras || !cam_of_frame) return fail(c, VTI_ERR_ARG, "vti_measure_frames: null ctx, camera table or camera index");
+    if (n_cams < 1) return fail(c, VTI_ERR_ARG, "vti_measure_frames: n_cams must be >= 1");
+    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
+        return fail(c, VTI_ERR_ARG, "vti_measure_frames: the camera table must be 16-byte aligned, the index 4-byte aligned");
+    FrameTableHeader h;
+    if (int32_t rc = frames_check("vti_measure_frames", c, host_table, dev_table, B, h)) return rc;
+    return measure_impl("vti_measure_frames", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
+                        max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
+                        frame_rows(dev_table));
 }
 
 static bool poly_sizes_ok(int32_t H, int32_t W, int32_t row_bytes) {

@@ -244,9 +244,31 @@ hipError_t launch_box_decode(const DecodeParams& p, hipStream_t st);   // DFL + 
 hipError_t launch_debug_nchw(int elem_is_f32, const void* src, int B, int H, int W, int C, int ld, int coff,
                              float* dst, hipStream_t st);
 
+// One frame of a batch whose frames differ in size (vti_pack_frames): what the kernels would otherwise recompute per pixel or per
+// box for the ctx's H x W canvas.  A frame table is a FrameTableHeader followed by B rows; vti_letterbox / vti_scale_boxes pass one
+// row by value in the launch arguments instead (the same numbers, so both forms give the same bytes).
+struct FrameRow {
+    long long offset;           // of the frame's first byte in the frame buffer (a multiple of 16)
+    int H0, W0, new_h, new_w, top, left;
+    double scale_x, scale_y;    // OpenCV resize(): 1 / (new / orig)
+    float gain, padx, pady;     // scale_boxes: computed in double, cast once
+    int pad;                    // zero: equal inputs pack to equal bytes
+};
+static_assert(sizeof(FrameRow) == 64, "frame table rows are 64 bytes");
+constexpr int kFrameTableMagic = 0x31544656;    // "VFT1"
+struct FrameTableHeader {
+    int magic, B, H, W, max_H0, max_W0;
+    long long total_bytes;      // of the frame buffer the offsets were checked against
+    int pad[8];
+};
+static_assert(sizeof(FrameTableHeader) == 64, "the rows of a frame table stay 64-byte aligned");
+void letterbox_geom(int H0, int W0, int H, int W, int& new_h, int& new_w, int& top, int& left);
+void frame_row_fill(int H, int W, int H0, int W0, long long offset, FrameRow& r);      // geometry of one frame on the H x W canvas (host)
+
 // post-processing (post.hip)
-hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, uint8_t* out, int H, int W,
-                            int new_h, int new_w, int top, int left, hipStream_t st);
+// table == nullptr: B frames of H0 x W0 back to back (vti_letterbox); else frame b is row b of the device table (vti_letterbox_frames)
+hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, const FrameRow* table, uint8_t* out, int H, int W,
+                            hipStream_t st);
 size_t nms_workspace_bytes(int B, int A);
 // `best`: optional [B, A, 2] floats (max class score, its first class index as a float) that the producer of `pred` wrote beside it
 // (vti_forward_scored): the candidate filter then reads 8 bytes per anchor instead of the nc class scores
@@ -264,8 +286,9 @@ int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]);
 hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto, int B, int max_det,
                                int Hp, int Wp, int H0, int W0, int mode, int packing, uint8_t* masks, int capacity, int* offsets,
                                void* ws, hipStream_t st);
+// table != nullptr: gain, pads and clip bounds of frame b from row b of the device table (H0, W0 unused)
 hipError_t launch_scale_boxes(const float* dets, const int* counts, int B, int max_det, int nm, int H, int W,
-                              int H0, int W0, float* xyxy, hipStream_t st);
+                              int H0, int W0, const FrameRow* table, float* xyxy, hipStream_t st);
 hipError_t launch_mask_to_frame(const uint8_t* masks, int n, int H, int W, int H0, int W0, uint8_t* bitmaps,
                                 int* nonzero, hipStream_t st);
 hipError_t launch_union_envelope(const uint8_t* bitmaps, const int* select, int nsel, int H0, int W0,
@@ -287,10 +310,12 @@ void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& 
 size_t measure_camera_row_bytes();
 void measure_pack_camera(const vti_measure_params& p, void* row);
 // p != nullptr: one camera for every frame; else frame b uses row cam_of_frame[b] of the device table (n_cams rows)
+// frames != nullptr (native = 0 only): frame b is H0 x W0 of row b of the device frame table, and the W0 passed here is the largest
+// one (the pitch of the envelope rows in the scratch)
 hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
                           int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
-                          int nm, int capacity, int H, int W, int H0, int W0, void* scratch, double* frame_f64, int* frame_i32,
-                          double* stitch_f64, int* stitch_i32, hipStream_t st);
+                          int nm, int capacity, int H, int W, int H0, int W0, const FrameRow* frames, void* scratch, double* frame_f64,
+                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st);
 
 // polygons.hip: vti_mask_polygons (Results.masks.xy).  The grid is VTI_POLY_WORKGROUPS persistent workgroups, each with its own
 // labelling area of the scratch: parent i32 [R_max] | runs u32 [R_max] | row_start i32 [H+1] | image u64 [H, WW] (only when the

@@ -31,6 +31,29 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class FrameTable:
+    """A packed frame table (vti_pack_frames) for a batch whose frames differ in size: `host` (the packed bytes, a CPU u8 tensor)
+    and `dev` (their device copy), `shapes` [(H0, W0)] per frame, the frames' `byte_offsets` in the flat frame buffer and its
+    `total_bytes`, the canvas `H`, `W` it was packed for and the largest `max_H0`, `max_W0`."""
+
+    def __init__(self, host, dev, shapes, byte_offsets, total_bytes, H, W):
+        self.host, self.dev, self.shapes, self.byte_offsets, self.total_bytes = host, dev, shapes, byte_offsets, total_bytes
+        self.H, self.W, self.B = H, W, len(shapes)
+        self.max_H0, self.max_W0 = max(h for h, _ in shapes), max(w for _, w in shapes)
+
+    def _ptrs(self):
+        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
+
+    def row(self, b):
+        """Host only: what row b holds -> dict(H0, W0, new_h, new_w, top, left, offset, scale_x, scale_y, gain, padx, pady)."""
+        i32, f64 = (C.c_int32 * 8)(), (C.c_double * 5)()
+        check(None, lib().vti_frame_table_info(C.c_void_p(self.host.data_ptr()), int(b), i32, f64))
+        d = dict(zip(("H0", "W0", "new_h", "new_w", "top", "left"), (int(v) for v in i32[:6])))
+        d["offset"] = (i32[6] & 0xFFFFFFFF) | (i32[7] << 32)
+        d.update(zip(("scale_x", "scale_y", "gain", "padx", "pady"), (float(v) for v in f64)))
+        return d
+
+
 class Engine:
     """One (model description, input size, max batch, dtype) context."""
 
@@ -111,11 +134,69 @@ class Engine:
         return self
 
     # ---- stages ------------------------------------------------------------------------
-    def letterbox(self, frames):
+    def letterbox(self, frames, out=None):
         """frames: u8 [B,H0,W0,3] on device -> u8 [B,H,W,3]."""
         B, H0, W0, _ = frames.shape
-        out = torch.empty((B, self.H, self.W, 3), dtype=torch.uint8, device=frames.device)
+        if out is None:
+            out = torch.empty((B, self.H, self.W, 3), dtype=torch.uint8, device=frames.device)
         check(self._ctx, lib().vti_letterbox(self._ctx, _ptr(frames), B, H0, W0, _ptr(out), _stream()))
+        return out
+
+    # ---- batches whose frames differ in size (vti_pack_frames and the *_frames entry points) --------------------------------
+    def pack_frames(self, shapes, device=None):
+        """shapes: one (H0, W0) per frame.  Lays the frames out back to back, each at a multiple of 16 bytes, validates and packs the
+        frame table for this engine's canvas and uploads it once.  -> (FrameTable, byte_offsets, total_bytes); a VtiError names the
+        failing frame."""
+        shapes = [(int(h), int(w)) for h, w in (tuple(x)[:2] for x in shapes)]
+        B = len(shapes)
+        if B < 1:
+            raise ValueError("pack_frames: at least one frame")
+        byte_offsets, total_bytes = [], 0
+        for h, w in shapes:
+            byte_offsets.append(total_bytes)
+            total_bytes = (total_bytes + 3 * max(h, 0) * max(w, 0) + 15) & ~15
+        total_bytes = max(total_bytes, 16)
+        H0 = (C.c_int32 * B)(*[h for h, _ in shapes])
+        W0 = (C.c_int32 * B)(*[w for _, w in shapes])
+        off = (C.c_int64 * B)(*byte_offsets)
+        nbytes = int(lib().vti_frame_table_bytes(B))
+        host = torch.zeros(nbytes, dtype=torch.uint8)
+        check(self._ctx, lib().vti_pack_frames(self._ctx, self.H, self.W, H0, W0, off, B, int(total_bytes),
+                                               C.c_void_p(host.data_ptr()), nbytes))
+        dev = host.to(device or self.device or "cuda")
+        return FrameTable(host, dev, shapes, byte_offsets, int(total_bytes), self.H, self.W), byte_offsets, int(total_bytes)
+
+    def _check_frames(self, table, B=None, buf=None):
+        if not isinstance(table, FrameTable):
+            raise ValueError("frames must be the FrameTable of Engine.pack_frames()")
+        if (table.H, table.W) != (self.H, self.W):
+            raise ValueError(f"the frame table was packed for a {table.H}x{table.W} canvas, this engine's is {self.H}x{self.W}")
+        if B is not None and table.B != B:
+            raise ValueError(f"the frame table describes {table.B} frames, the batch has {B}")
+        if buf is not None:
+            if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() < table.total_bytes:
+                raise ValueError(f"the frame buffer must be a flat contiguous uint8 tensor of >= {table.total_bytes} bytes")
+            if buf.device != table.dev.device:
+                raise ValueError("the frame buffer and the frame table must be on one device")
+
+    def letterbox_frames(self, buf, table, out=None):
+        """buf: flat u8 device buffer holding the frames of `table` (pack_frames) -> u8 [B,H,W,3]: vti_letterbox_frames."""
+        self._check_frames(table, buf=buf)
+        if out is None:
+            out = torch.empty((table.B, self.H, self.W, 3), dtype=torch.uint8, device=buf.device)
+        check(self._ctx, lib().vti_letterbox_frames(self._ctx, _ptr(buf), *table._ptrs(), table.B, _ptr(out), _stream()))
+        return out
+
+    def predict_frames_into(self, buf, table, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True,
+                            mask_mode="logit", packing="bits"):
+        """predict_into for a batch whose frames differ in size: `buf` / `table` as letterbox_frames, `out` from
+        alloc_outputs(table.B, ...).  Masks stay at the canvas size; out["xyxy"] is in each frame's own pixels."""
+        self._check_frames(table, B=out["counts"].shape[0], buf=buf)
+        check(self._ctx, lib().vti_predict_frames(
+            self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
+            int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
+            _ptr(out["dets"]), _ptr(out["counts"]), _ptr(out["masks"]), out["masks"].shape[0], _ptr(out["offsets"]), _ptr(out["xyxy"]),
+            _stream()))
         return out
 
     def alloc_pred(self, B, device):
@@ -215,10 +296,17 @@ class Engine:
                                                 _ptr(masks) if capacity else C.c_void_p(0), capacity, _ptr(offsets), _stream()))
         return masks, offsets
 
-    def scale_boxes(self, dets, counts, H0, W0, xyxy=None):
+    def scale_boxes(self, dets, counts, H0=None, W0=None, xyxy=None, frames=None):
+        """frames: a FrameTable (pack_frames) -- every frame is mapped back with its own gain, pads and bounds; else one H0 x W0."""
         B, max_det = dets.shape[0], dets.shape[1]
+        if frames is not None:
+            self._check_frames(frames, B=B)
         if xyxy is None:
             xyxy = torch.empty((B, max_det, 4), dtype=torch.float32, device=dets.device)
+        if frames is not None:
+            check(self._ctx, lib().vti_scale_boxes_frames(self._ctx, _ptr(dets), _ptr(counts), *frames._ptrs(), B, max_det, _ptr(xyxy),
+                                                          _stream()))
+            return xyxy
         check(self._ctx, lib().vti_scale_boxes(self._ctx, _ptr(dets), _ptr(counts), B, max_det, H0, W0, _ptr(xyxy), _stream()))
         return xyxy
 
@@ -322,7 +410,7 @@ class Engine:
         check(self._ctx, lib().vti_measure_pack_cameras(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
         return host.to(device or self.device or "cuda")
 
-    def measure(self, out, params, H0, W0, native=False, stitch_rows=True, result=None, cameras=None):
+    def measure(self, out, params, H0=None, W0=None, native=False, stitch_rows=True, result=None, cameras=None, frames=None):
         """The per-frame measurement of measurement.py's process_frame for every frame of an alloc_outputs() set that predict_into()
         (or nms/masks/scale_boxes) filled: vti_measure.  params: a measure.MeasureParams (or a VtiMeasureParams).  native=True: the
         masks are frame-size rows (predict_into(native=True)).  Returns device tensors, no host synchronisation:
@@ -331,10 +419,23 @@ class Engine:
         preallocated (any of its tensors reused).
         cameras (vti_measure_cameras): the camera of every frame, an int32 device tensor [B] (checked on the device: a frame whose
         index is outside the table reports status VTI_MEASURE_BAD_CAMERA) or a host sequence (range-checked here, ValueError); then
-        `params` is the table of pack_cameras() or a list of MeasureParams (packed and uploaded on every call: pack once instead)."""
+        `params` is the table of pack_cameras() or a list of MeasureParams (packed and uploaded on every call: pack once instead).
+        frames (vti_measure_frames): a FrameTable (pack_frames) in place of H0, W0 -- frame b is measured at its own size; letterbox
+        bit masks only (native=True is a ValueError).  Without `cameras` the one `params` serves every frame."""
         dets, masks = out["dets"], out["masks"]
         B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
         dev = dets.device
+        if frames is not None:
+            self._check_frames(frames, B=B)
+            if native:
+                raise ValueError("measure: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
+            if H0 is not None or W0 is not None:
+                raise ValueError("measure: give H0, W0 or frames, not both")
+            H0, W0 = frames.max_H0, frames.max_W0
+            if cameras is None:
+                params, cameras = (params if isinstance(params, (list, tuple)) else [params]), [0] * B
+        elif H0 is None or W0 is None:
+            raise ValueError("measure: H0 and W0 (or frames=) are required")
         if cameras is not None:
             table = params if isinstance(params, torch.Tensor) else self.pack_cameras(params, dev)
             row = int(lib().vti_measure_cameras_bytes(1))
@@ -367,10 +468,15 @@ class Engine:
         ws = getattr(self, "_measure_ws", None)
         if ws is None or ws.numel() < need or ws.device != dev:
             ws = self._measure_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        rest = (_ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]),
-                _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(), _ptr(r["frame_f64"]),
-                _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream())
-        if cameras is not None:
+        head = (_ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]),
+                _ptr(out["offsets"]))
+        tail = (_ptr(ws), ws.numel(), _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")),
+                _stream())
+        rest = head + (B, max_det, capacity, int(H0), int(W0)) + tail
+        if frames is not None:
+            check(self._ctx, lib().vti_measure_frames(self._ctx, _ptr(table), n_cams, _ptr(cameras), *head, *frames._ptrs(), B, max_det,
+                                                      capacity, *tail))
+        elif cameras is not None:
             check(self._ctx, lib().vti_measure_cameras(self._ctx, _ptr(table), n_cams, _ptr(cameras), *rest))
         else:
             check(self._ctx, lib().vti_measure(self._ctx, C.byref(cp), *rest))

@@ -119,7 +119,15 @@ class _DeviceStage:
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks):
         """-> (f64 [B,2], i32 [B,6]) on the host.  params / cameras as Engine.measure takes them; a callable `params` is called with
         (engine, device) once the outputs exist (the camera table needs both)."""
-        eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks)
+        shapes = self.model._differing_shapes(frames)
+        table = None
+        if shapes is not None:
+            if retina_masks:
+                raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
+            eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False)
+            B, H0, W0 = len(shapes), None, None
+        else:
+            eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks)
         key = (id(o), B)
         res = self._res.get(key)
         if res is None:           # one buffer for both records: a single device -> host read
@@ -129,7 +137,7 @@ class _DeviceStage:
             self._res = {key: res}
         if callable(params):
             params = params(eng, o["dets"].device)
-        eng.measure(o, params, H0, W0, native=bool(retina_masks), stitch_rows=False, result=res, cameras=cameras)
+        eng.measure(o, params, H0, W0, native=bool(retina_masks), stitch_rows=False, result=res, cameras=cameras, frames=table)
         host = res["buf"].cpu().numpy()
         return host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
 
@@ -179,8 +187,10 @@ class MultiCameraMeasurer(_DeviceStage):
         return self._tables[key][1]
 
     def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
-        """frames as StitchMeasurer.process_frames; cameras: one index into params_by_camera per frame (host integers).  Returns one
-        record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame order."""
+        """frames as StitchMeasurer.process_frames, or a list of frames whose sizes differ (cameras of several resolutions in one
+        batch: one predict, one vti_measure_frames, one read); cameras: one index into params_by_camera per frame (host integers).
+        Returns one record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame
+        order."""
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
         f64, i32 = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks)
         return self._records(f64, i32, cams.tolist())

@@ -153,6 +153,7 @@ class YOLO:
         self.drop_empty_masks = drop_empty_masks
         self.max_batch = max_batch
         self._outs = {}
+        self._frame_tables = {}
         self.names = names if names is not None else {i: f"class{i}" for i in range(nc)}
         self._engines = {}
 
@@ -184,6 +185,52 @@ class YOLO:
         dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
         return t.to(dev, non_blocking=True).contiguous()
 
+    @staticmethod
+    def _differing_shapes(source):
+        """[(H0, W0)] when `source` is a list / tuple of frames whose shapes are not all equal (Ultralytics then letterboxes every
+        frame onto one imgsz canvas, LetterBox(auto=False)); None for everything that keeps the stacked path."""
+        if not isinstance(source, (list, tuple)) or len(source) < 2:
+            return None
+        shapes = [tuple(s.shape) if hasattr(s, "shape") else np.shape(s) for s in source]
+        if all(x == shapes[0] for x in shapes):
+            return None
+        for x in shapes:
+            if len(x) != 3 or x[2] != 3:
+                raise ValueError(f"every frame of a list source must be uint8 HxWx3, got shape {x}")
+        return [x[:2] for x in shapes]
+
+    def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb):
+        """_predict_outputs for frames of differing sizes: the frames are flattened into one pinned staging buffer, copied with one
+        asynchronous H2D and run through one vti_predict_frames on the stride-rounded imgsz canvas.  The packed frame table, the
+        staging buffer and its device twin are cached per (engine, shapes).  -> (engine, output set, FrameTable, (H, W))."""
+        new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+        H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
+        B = len(shapes)
+        eng = self._engine(H, W, B, max_det)
+        dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
+        key = (id(eng), tuple(shapes))
+        ent = self._frame_tables.get(key)
+        if ent is None:
+            table, _, total = eng.pack_frames(shapes, dev)
+            self._frame_tables.clear()      # one rig at a time, as the output set
+            ent = self._frame_tables[key] = (table, torch.empty(total, dtype=torch.uint8, pin_memory=True),
+                                             torch.empty(total, dtype=torch.uint8, device=dev))
+        table, stage, buf = ent
+        flat = stage.numpy()
+        for f, (h, w), off in zip(source, shapes, table.byte_offsets):
+            a = f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+            if a.dtype != np.uint8:
+                raise ValueError(f"every frame of a list source must be uint8 HxWx3, got {a.dtype}")
+            flat[off:off + 3 * h * w] = a.reshape(-1)
+        buf.copy_(stage, non_blocking=True)
+        okey = (id(eng), B, max_det, None)
+        o = self._outs.get(okey)
+        if o is None:
+            self._outs.clear()
+            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev)
+        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits")
+        return eng, o, table, (H, W)
+
     def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks):
         """The device half of predict(): enqueues the whole pipeline into the cached output set and returns
         (engine, output set, (B, H0, W0), letterbox (H, W)) without reading anything back (predict() and
@@ -212,8 +259,20 @@ class YOLO:
                 agnostic_nms=False, swap_rb=True, retina_masks=False, **_ignored):
         """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
         ndarray sources.  retina_masks=True: masks at the frame size, Ultralytics'
-        process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes."""
-        eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
+        process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes.
+        A list / tuple of frames whose shapes differ is one batch too (vti_predict_frames): as Ultralytics does for such a list,
+        every frame is letterboxed by its own gain onto one stride-rounded imgsz canvas (LetterBox(auto=False)); boxes and
+        masks.xy come back in each frame's own pixels, masks.data at the canvas size.  retina_masks is a ValueError there."""
+        shapes = self._differing_shapes(source)
+        if shapes is not None:
+            if retina_masks:
+                raise ValueError("predict: retina_masks=True needs frames of one size; the frames of this list differ in shape "
+                                 "(frame-resolution masks for mixed sizes are not supported)")
+            eng, o, table, (H, W) = self._predict_outputs_frames(source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb)
+            B = len(shapes)
+        else:
+            eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
+            shapes = [(H0, W0)] * B
         dets, xyxy, masks = o["dets"], o["xyxy"], o["masks"]
         nonempty = None
         if self.drop_empty_masks and not retina_masks:     # m00 of every live slot straight from the bit-packed masks (vti_mask_stats_bits)
@@ -225,6 +284,7 @@ class YOLO:
             nonempty = masks[:live].reshape(live, -1).amax(1) > 0
         out = []
         for b in range(B):
+            H0, W0 = shapes[b]
             n = cnt[b]
             data = torch.cat((xyxy[b, :n], dets[b, :n, 4:6]), 1)
             mb, db = masks[off[b]:off[b] + n], dets[b, :n]
