@@ -218,7 +218,7 @@ int32_t vti_pixels_to_world(vti_ctx* ctx, const double* dev_uv, int32_t n, const
 int32_t vti_kmeans1d2(vti_ctx* ctx, const double* dev_values, const int32_t* dev_counts, int32_t B, int32_t max_n,
                       int32_t max_iters, int32_t* dev_labels, double* dev_centers, void* stream);
 
-/* ---- process_frame's measurement record on device (measurement.py:240-510, drawing left out) ------------------------- */
+/* ---- process_frame's measurement record on device (measurement.py:240-510; the drawing: vti_annotate below) ---------- */
 /* Settings of vti_measure: the calibration (camera_calibration.json, extrinsics.json; R = cv2.Rodrigues(rvec), row-major) and
  * config.py's measurement settings.  Defaults (config.py): stitch_id 0, fabric_id 1, roi_enabled 1, roi {10, 300, 1270, 760},
  * min_stitches 3, max_px_distance 250, envelope_neighborhood 3, skip_cluster 0, two_row_threshold_px 30, kmeans_iters 10,
@@ -383,6 +383,42 @@ int64_t vti_mask_polygons_scratch_bytes(const vti_ctx* ctx, int32_t H, int32_t W
 int32_t vti_mask_polygons(vti_ctx* ctx, const uint8_t* dev_masks_bits, int32_t n, const int32_t* dev_n_live, int32_t H, int32_t W,
                           int32_t row_bytes, int32_t H0, int32_t W0, int32_t strategy, void* dev_scratch, size_t scratch_bytes,
                           int32_t* dev_point_offsets, float* dev_points, int64_t max_points, void* stream);
+
+/* ---- process_frame's annotated frame on device (measurement.py:219-504): the overlay on a selection of the batch -------------- */
+/* The reference returns (annotated, measurements); vti_measure gives the second half, this call the first, for the n_sel frames
+ * the caller wants a picture of (the ones a limit check flagged, every k-th, ...).  dev_out[k] is frame select[k] of dev_frames
+ * (u8 [B,H0,W0,3] BGR, the batch predict consumed) with, in the reference's order and BGR colours: the clamped ROI (144,238,144) 2 px;
+ * per ROI-kept instance in detection order its int-truncated box, stitch (255,255,0) 1 px, fabric (255,0,255) 2 px; [status
+ * NO_FABRIC stops here] the lower envelope of the union of the kept fabric masks, every max(1, n / 1000)-th valid column, as an open
+ * polyline (255,128,0) 2 px; [NO_STITCHES stops here] per stitch of stitch_meta in rank order filled circles r = 3 (200,200,0) at
+ * (round(left), round(cy)) and (round(right), round(cy)), the 1-px line between them, a filled circle r = 3 (200,0,0) at (round(cx),
+ * round(cy)); per stitch with VTI_STITCH_DIST a 1-px line (0,255,0) from (clip(round(cx)), round(edge_y)) to (round(cx), round(cy))
+ * and a filled circle r = 2 (255,0,255) at the edge point; every outer contour of the union (the tracer of vti_mask_polygons,
+ * CHAIN_APPROX_SIMPLE) as a closed polyline (0,0,255) 2 px.  round = half to even.  A later primitive overwrites an earlier one.
+ * The pixels of a primitive are those of the package's annotate.py (OpenCV's LINE_8, shift = 0 drawing restated: LineIterator
+ * walk, fixed-point thick-line quad with its outline and round caps, midpoint-circle spans), byte for byte; text is the host's
+ * (annotate.text_items / put_text).  A frame with status VTI_MEASURE_BAD_CAMERA, or whose device camera index is outside [0, n_cams)
+ * (compared in the kernels before a table address is formed), is copied as it is.
+ * dev_cameras: a table of vti_measure_pack_cameras (16-byte aligned; one camera = a one-row table); dev_camera_of_frame i32 [B], or
+ * NULL: row 0 for every frame.  Masks, dets, xyxy, counts, offsets, max_det, capacity, native: as vti_measure took them; frame_i32,
+ * stitch_f64, stitch_i32: what it wrote (all three required).  The selection is given twice, as the frame table is: host_select
+ * i32 [n_sel] is checked before the first HIP call (every entry in [0, B); any order, duplicates allowed) and dev_select is its
+ * device copy, trusted to hold the same values.  1 <= H0, W0 <= 8192; 1 <= max_det <= VTI_MEASURE_MAX_DET; max_points >= 0 is the
+ * room for the outline's vertices per frame.  dev_out u8 [n_sel,H0,W0,3]: every byte is written; nothing else is (dev_frames and the
+ * frames not selected stay as they are).  dev_status i32 [n_sel]: 0, or VTI_ANNOTATE_OUTLINE_SKIPPED when the outline needed more than
+ * max_points vertices or the tracer reached its bound -- that frame is drawn without its outline, everything else stands.
+ * dev_scratch: >= vti_annotate_scratch_bytes(), 256-byte aligned.  Every argument check (VTI_ERR_ARG) runs before the first HIP call.
+ * Three launches on `stream` (display list + union, outline, raster); no host synchronisation.  Frames of differing sizes (a frame
+ * table) are not supported. */
+enum { VTI_ANNOTATE_OUTLINE_SKIPPED = 1 };
+/* Host only: bytes of device scratch vti_annotate needs (0 on a bad argument); it grows with n_sel and with max_points. */
+int64_t vti_annotate_scratch_bytes(const vti_ctx* ctx, int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points);
+int32_t vti_annotate(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t H0, int32_t W0, const void* dev_cameras,
+                     int32_t n_cams, const int32_t* dev_camera_of_frame, const uint8_t* dev_masks, int32_t native,
+                     const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets,
+                     int32_t max_det, int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                     const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points, uint8_t* dev_out,
+                     int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
 
 /* ---- per-layer access for parity tests ------------------------------------------- */
 /* Copies the activation written by conv `i` of the last vti_forward into dev_out as

@@ -43,6 +43,7 @@ VTI_MEASURE_MAX_DET = 1000
 
 VTI_POLY_LARGEST, VTI_POLY_CONCAT = 0, 1
 VTI_POLY_OK, VTI_POLY_ERR_BOUND, VTI_POLY_ERR_RANGE = 0, 1, 2
+VTI_ANNOTATE_OUTLINE_SKIPPED = 1
 
 
 class VtiError(RuntimeError):
@@ -106,6 +107,9 @@ SIGNATURES = {
                                   _P, _P, _P, _P, _P]),
     "vti_mask_polygons_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_mask_polygons": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
+    "vti_annotate_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
+    "vti_annotate": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32,
+                            _I32, _P, _P, _P, _SZ, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),
     "vti_debug_conv2d": (_I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32,
                                 _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,

@@ -1,0 +1,470 @@
+// process_frame's annotated frame on the device (vti_annotate): the overlay of measurement.py:219-504 -- ROI, boxes, fabric edge,
+// stitch markers, stitch-to-edge lines, fabric outline -- painted onto a SELECTION of the batch's frames, byte for byte what the
+// host restatement annotate.py gives (rasterise(frame, display_list(...))).  DESIGN.md section 5e.
+//
+// Three launches on the stream, ordered by the kernel boundaries only (no flags between workgroups):
+//   1. prep (one workgroup per selected frame): the frame's records are reset; then the ROI and box records, the union of the kept
+//      fabric masks as frame-size bit rows (letterbox bits nearest-resized as measurement.py:79 does), its lower envelope as a point
+//      list, and the marker records from vti_measure's per-slot rows.  A record has a FIXED place in the frame's list -- 0: ROI,
+//      1 + i: the box of instance i, 1 + M: the envelope, 2 + M + 4 j: the four markers of stitch rank j, 2 + 5 M + 2 j: its edge
+//      line and point, 2 + 7 M: the outline (M = max_det) -- which is the reference's drawing order, so nothing is sorted or scanned;
+//      what a frame does not draw stays an empty record.
+//   2. outline (one workgroup per selected frame with status OK): the outer contours of the union, traced by vti_mask_polygons'
+//      labelling and border following (polygons_dev.h); every vertex is stored with the index of the next one of its contour, so the
+//      closed polylines need no per-contour table.  More than max_points vertices (or a loop bound reached): the status bit, and the
+//      outline record stays empty.
+//   3. raster (a workgroup per 8192 consecutive pixels of an output frame): a word per pixel in LDS holds the LAST record that
+//      covers it (atomicMax of record index << 3 | colour: painter's order without ordering the work), a thread per record, envelope
+//      segment or outline edge paints the rows of its primitive that fall into the tile from the closed forms of annotate_dev.h, and
+//      the tile is then copied from the frame with the covered pixels replaced (16 pixels = three 16-byte vectors per thread).
+#include <climits>
+#include <cstring>
+
+#include "annotate_dev.h"
+#include "measure_dev.h"
+#include "polygons_dev.h"
+
+namespace vti {
+
+namespace {
+
+using poly::u64;
+
+constexpr int kThreads = 256;
+constexpr int kTile = 8192;                 // pixels per raster workgroup: 32 KB of LDS, a multiple of 16
+
+enum { K_NOP = 0, K_LINE = 1, K_RECT = 2, K_CIRCLE = 3, K_POLY = 4, K_CONTOURS = 5 };
+enum { C_ROI = 0, C_STITCH_BOX, C_FABRIC_BOX, C_ENVELOPE, C_WIDTH, C_CENTRE, C_DIST, C_OUTLINE };
+// BGR, annotate.py's COLOURS (measurement.py:268, 272, 296, 360-364, 460-462, 499; config.py ROI_BORDER_COLOR)
+static __constant__ unsigned char kColour[8][4] = {{144, 238, 144, 0}, {255, 255, 0, 0}, {255, 0, 255, 0}, {255, 128, 0, 0},
+                                                   {200, 200, 0, 0},   {200, 0, 0, 0},   {0, 255, 0, 0},   {0, 0, 255, 0}};
+
+// LINE / RECT: the two points; CIRCLE: centre (x0, y0), radius x1; POLY / CONTOURS: n points of the frame's point list
+struct Rec { int kind, colour, thick, n, x0, y0, x1, y1; };
+static_assert(sizeof(Rec) == 32, "records are two 16-byte vectors");
+enum { META_N_ENV = 0, META_N_CONT = 1, META_OUTLINE = 2, META_INTS = 16 };
+
+struct AnnArgs {
+    const uint8_t* frames; uint8_t* out; int* status_out;
+    const int* select; int B, n_sel, H0, W0, WW;
+    const CameraRow* table; const int* cam_of_frame; int n_cams;
+    const uint8_t* masks; const float* dets; const float* xyxy; const int* counts; const int* offsets;
+    int max_det, row, capacity, H, W;
+    const int* frame_i32; const double* stitch_f64; const int* stitch_i32;
+    int max_points;
+    Rec* recs; int* meta; int2* env_pts; int2* cont; u64* uni;
+    unsigned char* areas; size_t area_bytes, off_runs, off_rows;
+};
+
+__device__ __forceinline__ int nrec(int max_det) { return 3 + 7 * max_det; }
+// coordinates far outside any frame change nothing that is drawn; the clamp keeps the fixed-point arithmetic in range
+__device__ __forceinline__ int clampc(int v) { return min(max(v, -32768), 32767); }
+__device__ __forceinline__ int round_px(double v) { return (int)rint(fmin(fmax(v, -32768.0), 32767.0)); }   // python round(): half to even
+
+template <bool NATIVE>
+__global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
+    extern __shared__ int s_env[];              // [W0]: the nearest-resize column table, then the envelope
+    __shared__ int s_fab[VTI_MEASURE_MAX_DET][3];
+    __shared__ int s_nfab, s_w[kThreads / 64];
+    const int tid = threadIdx.x, k = blockIdx.x, M = a.max_det, H0 = a.H0, W0 = a.W0, WW = a.WW;
+    const int b = min(max(a.select[k], 0), a.B - 1);
+    Rec* recs = a.recs + (size_t)k * nrec(M);
+    int* meta = a.meta + (size_t)k * META_INTS;
+    for (int i = tid; i < nrec(M); i += kThreads) recs[i] = Rec{K_NOP, 0, 0, 0, 0, 0, 0, 0};
+    if (tid < META_INTS) meta[tid] = 0;
+    if (tid == 0) { a.status_out[k] = 0; s_nfab = 0; }
+    __syncthreads();
+    const int ci = a.cam_of_frame ? a.cam_of_frame[b] : 0;
+    if (ci < 0 || ci >= a.n_cams) return;       // uniform; no table address has been formed: the frame is copied as it is
+    const CameraRow* c = a.table + ci;
+    const int status = a.frame_i32[6 * (size_t)b];
+    if (status != VTI_MEASURE_OK && status != VTI_MEASURE_NO_FABRIC && status != VTI_MEASURE_NO_STITCHES) return;
+    const int stitch_id = c->stitch_id, fabric_id = c->fabric_id, drop_empty = c->drop_empty;
+    int rr[4] = {c->roi[0], c->roi[1], c->roi[2], c->roi[3]};
+    int4 roi;
+    const bool roi_on = roi_clamp(c->roi_enabled, rr, H0, W0, roi);
+    // 1. the ROI (measurement.py:222-238)
+    if (tid == 0 && roi_on) recs[0] = Rec{K_RECT, C_ROI, 2, 0, roi.x, roi.y, roi.z, roi.w};
+    // 2. boxes in detection order (measurement.py:249-272); the kept fabric instances that have a mask are listed for the union
+    const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
+    const int Hm = NATIVE ? H0 : a.H, wpr = NATIVE ? 2 * WW : a.W >> 5;       // rows and 32-bit words per row of a mask slot
+    for (int i = tid; i < n; i += kThreads) {
+        const int s = s0 + i;
+        const bool live = s >= 0 && s < a.capacity;
+        const size_t di = (size_t)b * M + i;
+        const float* d = a.dets + di * a.row;
+        const float* bx = a.xyxy + di * 4;
+        const int cls = (int)d[5];
+        const bool roi_ok = !roi_on || roi_keeps(bx, roi);
+        const int x1 = clampc((int)bx[0]), y1 = clampc((int)bx[1]), x2 = clampc((int)bx[2]), y2 = clampc((int)bx[3]);
+        if (cls == stitch_id) {
+            const bool keep = live ? (a.stitch_i32[2 * (size_t)s] & VTI_STITCH_KEPT) != 0 : (roi_ok && !drop_empty);
+            if (keep) recs[1 + i] = Rec{K_RECT, C_STITCH_BOX, 1, 0, x1, y1, x2, y2};
+        } else if (cls == fabric_id && roi_ok) {
+            if (!live) {
+                if (!drop_empty) recs[1 + i] = Rec{K_RECT, C_FABRIC_BOX, 2, 0, x1, y1, x2, y2};
+            } else {
+                int ya, yb;         // a mask is zero outside these rows of its slot (as vti_measure's envelope kernel reads it)
+                if (NATIVE) { ya = (int)floorf(bx[1]); yb = (int)ceilf(bx[3]); }
+                else { ya = (int)floorf(d[1] - 8.f); yb = (int)ceilf(d[3] + 8.f); }
+                const int pos = atomicAdd(&s_nfab, 1);
+                s_fab[pos][0] = i; s_fab[pos][1] = max(ya, 0); s_fab[pos][2] = min(yb, Hm - 1);
+            }
+        }
+    }
+    __syncthreads();
+    const int nfab = s_nfab;
+    const unsigned* bits = (const unsigned*)a.masks;
+    for (int f = 0; f < nfab; ++f) {            // drop_empty: a fabric instance whose mask has no set bit does not exist
+        const int i = s_fab[f][0], ya = s_fab[f][1], yb = s_fab[f][2];
+        int any = 1;
+        if (drop_empty) {
+            any = 0;
+            const unsigned* m = bits + ((size_t)(s0 + i) * Hm + ya) * wpr;
+            const int nw = yb >= ya ? (yb - ya + 1) * wpr : 0;
+            for (int j = tid; j < nw; j += kThreads) any |= m[j] != 0;
+            any = __syncthreads_or(any);
+        }
+        if (tid == 0) {
+            if (any) {
+                const float* bx = a.xyxy + ((size_t)b * M + i) * 4;
+                recs[1 + i] = Rec{K_RECT, C_FABRIC_BOX, 2, 0, clampc((int)bx[0]), clampc((int)bx[1]), clampc((int)bx[2]), clampc((int)bx[3])};
+            } else {
+                s_fab[f][1] = 1; s_fab[f][2] = 0;       // an empty row range: nothing for the union
+            }
+        }
+    }
+    if (status == VTI_MEASURE_NO_FABRIC) return;        // 3. the reference returns here (measurement.py:280-287)
+    __syncthreads();
+    // 4a. the union of the kept fabric masks at the frame size: u64 [H0, WW], bits at columns >= W0 clear
+    u64* uni = a.uni + (size_t)k * H0 * WW;
+    const double ify = 1.0 / ((double)H0 / (double)a.H), ifx = 1.0 / ((double)W0 / (double)a.W);
+    if (!NATIVE) {
+        for (int x = tid; x < W0; x += kThreads) s_env[x] = nn_src(x, ifx, a.W);
+        __syncthreads();
+    }
+    const u64 last_valid = (W0 & 63) ? ((1ull << (W0 & 63)) - 1) : ~0ull;
+    for (int idx = tid; idx < H0 * WW; idx += kThreads) {
+        const int y = idx / WW, w = idx - y * WW;
+        u64 acc = 0;
+        if (NATIVE) {
+            for (int f = 0; f < nfab; ++f)
+                if (y >= s_fab[f][1] && y <= s_fab[f][2]) acc |= ((const u64*)a.masks)[(size_t)(s0 + s_fab[f][0]) * H0 * WW + idx];
+        } else {
+            const int sy = nn_src(y, ify, a.H);
+            const int c0 = w * 64, c1 = min(c0 + 63, W0 - 1), w0 = s_env[c0] >> 5, w1 = s_env[c1] >> 5;
+            for (int f = 0; f < nfab; ++f) {
+                if (sy < s_fab[f][1] || sy > s_fab[f][2]) continue;
+                const unsigned* srow = bits + ((size_t)(s0 + s_fab[f][0]) * a.H + sy) * wpr;
+                unsigned any = 0;
+                for (int q = w0; q <= w1; ++q) any |= srow[q];
+                if (!any) continue;
+                for (int x = c0; x <= c1; ++x) {
+                    const int sx = s_env[x];
+                    acc |= (u64)((srow[sx >> 5] >> (sx & 31)) & 1u) << (x - c0);
+                }
+            }
+        }
+        if (w == WW - 1) acc &= last_valid;
+        uni[idx] = acc;
+    }
+    __syncthreads();
+    // 4b. the lower envelope per column (measurement.py:170-185): a thread per 64 columns and band of rows, bottom row first
+    for (int x = tid; x < W0; x += kThreads) s_env[x] = -1;
+    __syncthreads();
+    {
+        const int G = max(1, kThreads / WW), chunk = (H0 + G - 1) / G;
+        for (int t = tid; t < WW * G; t += kThreads) {
+            const int w = t % WW, g = t / WW, r_lo = g * chunk, r_hi = min(H0, r_lo + chunk);
+            const u64 full = w == WW - 1 ? last_valid : ~0ull;
+            u64 seen = 0;
+            for (int y = r_hi - 1; y >= r_lo && seen != full; --y) {
+                const u64 word = uni[(size_t)y * WW + w];
+                u64 m = word & ~seen;
+                while (m) {
+                    atomicMax(&s_env[w * 64 + __builtin_ctzll(m)], y);
+                    m &= m - 1;
+                }
+                seen |= word;
+            }
+        }
+    }
+    __syncthreads();
+    // 4c. its valid columns, every step-th of them (measurement.py:292-296), as the envelope's point list
+    int nv = 0;
+    for (int x0 = 0; x0 < W0; x0 += kThreads) {
+        int tot;
+        (void)poly::block_excl_scan(x0 + tid < W0 && s_env[x0 + tid] >= 0, s_w, tot);
+        nv += tot;
+    }
+    if (nv > 0) {
+        const int step = max(1, nv / 1000);
+        int2* pts = a.env_pts + (size_t)k * W0;
+        int carry = 0;
+        for (int x0 = 0; x0 < W0; x0 += kThreads) {
+            const int x = x0 + tid;
+            const int f = x < W0 && s_env[x] >= 0;
+            int tot;
+            const int rank = carry + poly::block_excl_scan(f, s_w, tot);
+            if (f && rank % step == 0) pts[rank / step] = make_int2(x, s_env[x]);
+            carry += tot;
+        }
+        if (tid == 0) {
+            const int ne = (nv + step - 1) / step;
+            meta[META_N_ENV] = ne;
+            recs[1 + M] = Rec{K_POLY, C_ENVELOPE, 2, ne, 0, 0, 0, 0};
+        }
+    }
+    if (status == VTI_MEASURE_NO_STITCHES) return;      // 5. (measurement.py:332-337)
+    // 6 + 7. the markers of stitch rank j and, when it gave a distance, its edge line and point (measurement.py:359-364, 460-462)
+    for (int i = tid; i < n; i += kThreads) {
+        const int s = s0 + i;
+        if (s < 0 || s >= a.capacity) continue;
+        const int fl = a.stitch_i32[2 * (size_t)s], j = a.stitch_i32[2 * (size_t)s + 1];
+        if (!(fl & VTI_STITCH_KEPT) || j < 0 || j >= M) continue;
+        const double* v = a.stitch_f64 + (size_t)s * 7;
+        const int cx = round_px(v[0]), cy = round_px(v[1]), lx = round_px(v[2]), rx = round_px(v[3]);
+        Rec* r = recs + 2 + M + 4 * j;
+        r[0] = Rec{K_CIRCLE, C_WIDTH, 0, 0, lx, cy, 3, 0};
+        r[1] = Rec{K_CIRCLE, C_WIDTH, 0, 0, rx, cy, 3, 0};
+        r[2] = Rec{K_LINE, C_WIDTH, 1, 0, lx, cy, rx, cy};
+        r[3] = Rec{K_CIRCLE, C_CENTRE, 0, 0, cx, cy, 3, 0};
+        if (fl & VTI_STITCH_DIST) {
+            const int ex = min(max(cx, 0), W0 - 1), ey = round_px(v[5]);
+            Rec* q = recs + 2 + 5 * M + 2 * j;
+            q[0] = Rec{K_LINE, C_DIST, 1, 0, ex, ey, cx, cy};
+            q[1] = Rec{K_CIRCLE, C_FABRIC_BOX, 0, 0, ex, ey, 2, 0};
+        }
+    }
+    if (tid == 0) meta[META_OUTLINE] = 1;
+}
+
+// vertex `pos` of a contour that starts at `base`: (x | y << 16, index of the next vertex)
+struct ContEmit {
+    int2* out; int base, limit;
+    __device__ __forceinline__ void operator()(int pos, int y, int x, bool& bad) const {
+        if (pos >= limit) { bad = true; return; }
+        out[base + pos] = make_int2(x | (y << 16), base + pos + 1);
+    }
+};
+
+template <bool IN_LDS>
+__global__ __launch_bounds__(kThreads) void annotate_outline_kernel(AnnArgs a) {
+    extern __shared__ u64 s_img[];
+    __shared__ int s_w[kThreads / 64];
+    __shared__ int s_bad, s_total;
+    const int tid = threadIdx.x, k = blockIdx.x, H = a.H0, W = a.W0, WW = a.WW, M = a.max_det;
+    const int* meta = a.meta + (size_t)k * META_INTS;
+    if (!meta[META_OUTLINE]) return;            // uniform: only a frame with status OK draws its outline
+    unsigned char* area = a.areas + (size_t)k * a.area_bytes;
+    int* const parent_g = (int*)area;
+    unsigned* runs = (unsigned*)(area + a.off_runs);
+    int* row_start = (int*)(area + a.off_rows);
+    const u64* uni = a.uni + (size_t)k * H * WW;
+    const u64* img = uni;
+    if (tid == 0) { s_bad = 0; s_total = 0; }
+    if (IN_LDS) {
+        for (int i = tid; i < H * WW; i += kThreads) s_img[i] = uni[i];
+        img = s_img;
+    }
+    __syncthreads();
+    int* parent;
+    bool bad;
+    (void)poly::label_runs<IN_LDS>(img, H, WW, runs, row_start, parent_g, s_img, s_w, parent, bad);
+    if (bad) s_bad = 1;
+    __threadfence();
+    __syncthreads();
+    bad = s_bad != 0;
+    const int trace_bound = 4 * (H + 2) * (W + 2);
+    int2* out = a.cont + (size_t)k * a.max_points;
+    if (!bad) {
+        for (int y = tid; y < H; y += kThreads) {
+            for (int r = row_start[y]; r < row_start[y + 1]; ++r) {
+                if (poly::ld_p(parent + r) != r) continue;      // a component's root run starts at its top-most, left-most pixel
+                const int sx = (int)(runs[r] & 0xffff);
+                int c0 = 0;
+                ContEmit none{nullptr, 0, 0};
+                const int cnt = poly::trace_outer<false>(WW, H, img, y, sx, trace_bound, c0, bad, none);
+                if (bad) break;
+                const int base = atomicAdd(&s_total, cnt);
+                if (cnt < 1 || (long long)base + cnt > a.max_points) continue;
+                ContEmit em{out, base, cnt};
+                poly::trace_outer<true>(WW, H, img, y, sx, trace_bound, c0, bad, em);
+                out[base + cnt - 1].y = base;                   // the contour closes on its first vertex
+            }
+            if (bad) break;
+        }
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (tid == 0) {
+        if (s_bad || s_total > a.max_points) {
+            a.status_out[k] = 1;
+        } else {
+            a.meta[(size_t)k * META_INTS + META_N_CONT] = s_total;
+            a.recs[(size_t)k * nrec(M) + 2 + 7 * M] = Rec{K_CONTOURS, C_OUTLINE, 2, s_total, 0, 0, 0, 0};
+        }
+    }
+}
+
+// the painter of one raster tile: pixels [p0, p1) of the frame in row-major order, rows ylo .. yhi
+struct TilePaint {
+    int ylo, yhi, W, p0, p1;
+    unsigned* prio;
+    unsigned key;
+    __device__ __forceinline__ void span(int y, ann::i64 xa, ann::i64 xb) {
+        if (y < ylo || y > yhi) return;
+        const int x0 = (int)ann::imax(xa, 0), x1 = (int)ann::imin(xb, W - 1);
+        const int q0 = max(y * W + x0, p0), q1 = min(y * W + x1, p1 - 1);
+        if (x0 > x1) return;
+        for (int q = q0; q <= q1; ++q) atomicMax(&prio[q - p0], key);
+    }
+};
+
+__global__ __launch_bounds__(kThreads) void annotate_raster_kernel(AnnArgs a) {
+    extern __shared__ unsigned s_prio[];        // [kTile]
+    const int tid = threadIdx.x, k = blockIdx.y, M = a.max_det, H0 = a.H0, W0 = a.W0;
+    const int b = min(max(a.select[k], 0), a.B - 1);
+    const int npx = H0 * W0, p0 = blockIdx.x * kTile, p1 = min(p0 + kTile, npx);
+    for (int i = tid; i < kTile; i += kThreads) s_prio[i] = 0;
+    __syncthreads();
+    const Rec* recs = a.recs + (size_t)k * nrec(M);
+    const int* meta = a.meta + (size_t)k * META_INTS;
+    const int2* env = a.env_pts + (size_t)k * W0;
+    const int2* cont = a.cont + (size_t)k * a.max_points;
+    const int n_env = min(max(meta[META_N_ENV], 0), W0), n_cont = min(max(meta[META_N_CONT], 0), a.max_points);
+    const int n_fixed = nrec(M), n_seg = max(n_env - 1, 0), total = n_fixed + n_seg + n_cont;
+    TilePaint P{p0 / W0, (p1 - 1) / W0, W0, p0, p1, s_prio, 0};
+    for (int it = tid; it < total; it += kThreads) {
+        // every work item is a circle or 1 .. 4 line segments of one thickness (one inlined copy of the segment painter)
+        int nseg = 0, thick = 2, x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+        if (it < n_fixed) {
+            const Rec r = recs[it];
+            if (r.kind == K_NOP || r.kind > K_CIRCLE) continue;
+            P.key = (unsigned)(it + 1) << 3 | (unsigned)(r.colour & 7);
+            if (r.kind == K_CIRCLE) {
+                const int rad = min(max(r.x1, 0), 64);
+                if (r.y0 + rad >= P.ylo && r.y0 - rad <= P.yhi) ann::circle(r.x0, r.y0, rad, P);
+                continue;
+            }
+            if (max(r.y0, r.y1) + 4 < P.ylo || min(r.y0, r.y1) - 4 > P.yhi) continue;
+            nseg = r.kind == K_RECT ? 4 : 1;
+            thick = r.thick; x0 = r.x0; y0 = r.y0; x1 = r.x1; y1 = r.y1;
+        } else if (it < n_fixed + n_seg) {      // the open polyline of the envelope: segment j -> j + 1
+            const int j = it - n_fixed;
+            const int2 u = env[j], v = env[j + 1];
+            P.key = (unsigned)(1 + M + 1) << 3 | C_ENVELOPE;
+            nseg = 1; x0 = u.x; y0 = u.y; x1 = v.x; y1 = v.y;
+        } else {                                // the closed polylines of the outline: vertex j -> its successor
+            const int j = it - n_fixed - n_seg;
+            const int2 u = cont[j];
+            if (u.y < 0 || u.y >= n_cont) continue;
+            const int2 v = cont[u.y];
+            P.key = (unsigned)(2 + 7 * M + 1) << 3 | C_OUTLINE;
+            nseg = 1; x0 = u.x & 0xffff; y0 = u.x >> 16; x1 = v.x & 0xffff; y1 = v.x >> 16;
+        }
+        for (int e = 0; e < nseg; ++e) {
+            // a rectangle is the closed polyline of its corners (cv::rectangle): (x0,y1)-(x0,y0)-(x1,y0)-(x1,y1)-(x0,y1)
+            int ax = x0, ay = y0, bx = x1, by = y1;
+            if (nseg == 4) {
+                ax = e < 2 ? x0 : x1; ay = (e == 0 || e == 3) ? y1 : y0;
+                bx = (e == 0 || e == 3) ? x0 : x1; by = e < 2 ? y0 : y1;
+            }
+            ann::thick_line(W0, H0, ax, ay, bx, by, thick, P);
+        }
+    }
+    __syncthreads();
+    // the tile of the frame with the covered pixels replaced
+    const uint8_t* src = a.frames + (size_t)b * npx * 3 + (size_t)p0 * 3;
+    uint8_t* dst = a.out + (size_t)k * npx * 3 + (size_t)p0 * 3;
+    const int np = p1 - p0;
+    int done = 0;
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {        // 16 pixels = 48 bytes = three 16-byte vectors per thread
+        const int units = np / 16;
+        for (int u = tid; u < units; u += kThreads) {
+            const uint4* s4 = (const uint4*)(src + (size_t)u * 48);
+            uint4 v[3] = {s4[0], s4[1], s4[2]};
+            const uint4* pr4 = (const uint4*)(s_prio + u * 16);
+            unsigned pr[16];
+            unsigned any = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint4 t = pr4[q];
+                pr[4 * q] = t.x; pr[4 * q + 1] = t.y; pr[4 * q + 2] = t.z; pr[4 * q + 3] = t.w;
+                any |= t.x | t.y | t.z | t.w;
+            }
+            if (any) {
+                unsigned char* bytes = (unsigned char*)v;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    if (!pr[q]) continue;
+                    const unsigned char* col = kColour[pr[q] & 7];
+                    bytes[3 * q] = col[0]; bytes[3 * q + 1] = col[1]; bytes[3 * q + 2] = col[2];
+                }
+            }
+            uint4* d4 = (uint4*)(dst + (size_t)u * 48);
+            d4[0] = v[0]; d4[1] = v[1]; d4[2] = v[2];
+        }
+        done = units * 16;
+    }
+    for (int q = done + tid; q < np; q += kThreads) {           // frames whose bytes are not 16-byte aligned, and the last pixels
+        const unsigned pr = s_prio[q];
+        const unsigned char* col = kColour[pr & 7];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) dst[(size_t)q * 3 + ch] = pr ? col[ch] : src[(size_t)q * 3 + ch];
+    }
+}
+
+}  // namespace
+
+void annotate_layout(int n_sel, int max_det, int H0, int W0, int max_points, AnnotateLayout& L) {
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    PolyLayout pl;
+    mask_polygons_layout(H0, W0, 8 * ((W0 + 63) / 64), pl);
+    L.WW = pl.WW;
+    L.in_lds = pl.in_lds;
+    L.off_runs = pl.off_runs; L.off_rows = pl.off_rows;
+    L.area_bytes = pl.off_rows + al((size_t)(H0 + 1) * 4);      // parent | runs | row_start: the image is the union itself
+    L.off_recs = 0;
+    L.off_meta = L.off_recs + al((size_t)n_sel * (3 + 7 * (size_t)max_det) * sizeof(Rec));
+    L.off_env = L.off_meta + al((size_t)n_sel * META_INTS * sizeof(int));
+    L.off_cont = L.off_env + al((size_t)n_sel * W0 * sizeof(int2));
+    L.off_union = L.off_cont + al((size_t)n_sel * (size_t)max_points * sizeof(int2));
+    L.off_areas = L.off_union + al((size_t)n_sel * H0 * L.WW * 8);
+    L.total = L.off_areas + (size_t)n_sel * L.area_bytes;
+}
+
+hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const void* cameras, int n_cams, const int* cam_of_frame,
+                           const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
+                           const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
+                           const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
+                           int* status, void* scratch, hipStream_t st) {
+    AnnotateLayout L;
+    annotate_layout(n_sel, max_det, H0, W0, max_points, L);
+    unsigned char* ws = (unsigned char*)scratch;
+    AnnArgs a;
+    memset(&a, 0, sizeof a);
+    a.frames = frames; a.out = out; a.status_out = status;
+    a.select = select; a.B = B; a.n_sel = n_sel; a.H0 = H0; a.W0 = W0; a.WW = L.WW;
+    a.table = (const CameraRow*)cameras; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams;
+    a.masks = masks; a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
+    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H = native ? H0 : H; a.W = native ? W0 : W;
+    a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
+    a.max_points = max_points;
+    a.recs = (Rec*)(ws + L.off_recs); a.meta = (int*)(ws + L.off_meta); a.env_pts = (int2*)(ws + L.off_env);
+    a.cont = (int2*)(ws + L.off_cont); a.uni = (u64*)(ws + L.off_union);
+    a.areas = ws + L.off_areas; a.area_bytes = L.area_bytes; a.off_runs = L.off_runs; a.off_rows = L.off_rows;
+    const size_t env_lds = (size_t)W0 * sizeof(int);
+    if (native) hipLaunchKernelGGL(annotate_prep_kernel<true>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
+    else hipLaunchKernelGGL(annotate_prep_kernel<false>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = L.in_lds ? launch_lds<annotate_outline_kernel<true>>(dim3(n_sel), dim3(kThreads), (size_t)poly::kLdsBytes, st, a)
+                 : launch_lds<annotate_outline_kernel<false>>(dim3(n_sel), dim3(kThreads), 0, st, a);
+    if (e != hipSuccess) return e;
+    const int tiles = (int)(((long long)H0 * W0 + kTile - 1) / kTile);
+    hipLaunchKernelGGL(annotate_raster_kernel, dim3(tiles, n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
+    return hipGetLastError();
+}
+
+}  // namespace vti

@@ -9,15 +9,9 @@
 #include <cstring>
 #include <type_traits>
 
-#include "vti_internal.h"
+#include "measure_dev.h"
 
 namespace vti {
-
-// cv2.resize(INTER_NEAREST): src index of destination index d = min(floor(d * (1 / (dst / src))), src - 1), in double.
-__device__ __forceinline__ int nn_src(int d, double inv_scale, int ssize) {
-    const int s = (int)floor((double)d * inv_scale);
-    return s < ssize - 1 ? s : ssize - 1;
-}
 
 // ---- A4 + A7: per-instance moments / column extents of the frame-sized bitmap, from the bit-packed mask -------------
 // Destination pixel (y, x) of the H0 x W0 bitmap copies source pixel (sy(y), sx(x)); so with
@@ -169,30 +163,6 @@ hipError_t launch_mask_stats_bits(const uint8_t* bits, int n, const int* n_live,
 // vti_measure_cameras) they come from row cam_of_frame[b] instead, range-checked against n_cams before the row's address is formed;
 // a frame whose index is outside gets an all -1 envelope.
 struct EnvSel { int cls, roi_enabled, roi[4]; };
-// One camera of vti_measure: the pixel -> world model (section N3a below) and config.py's settings.  vti_measure passes one row by
-// value in the launch arguments; vti_measure_cameras keeps a table of rows in device memory (vti_measure_pack_cameras) and an index
-// per frame.  The ROI is stored as given: roi_clamp applies the frame size where it is known.
-struct GeomParams { double fx, fy, cx, cy, k1, k2, p1, p2, k3; double R[9]; double t[3]; double n[3]; double d; };
-struct CameraRow {
-    GeomParams g;
-    double max_px, two_row;
-    int stitch_id, fabric_id, roi_enabled, roi[4];
-    int min_stitches, nb, skip_cluster, kmeans_iters, drop_empty;
-    int pad[2];                             // rows are a multiple of 16 bytes; zero, so that equal settings pack to equal bytes
-};
-static_assert(sizeof(CameraRow) % 16 == 0, "camera table rows keep 16-byte alignment");
-
-// measurement.py:220-238: the ROI clamped to the frame, inactive (false) when disabled or degenerate
-__device__ __forceinline__ bool roi_clamp(int enabled, const int* r, int H0, int W0, int4& roi) {
-    roi = make_int4(max(0, min(r[0], W0 - 1)), max(0, min(r[1], H0 - 1)), max(0, min(r[2], W0 - 1)), max(0, min(r[3], H0 - 1)));
-    return enabled && roi.x < roi.z && roi.y < roi.w;
-}
-
-__device__ __forceinline__ bool roi_keeps(const float* bx, int4 roi) {
-    const long long x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];    // python int(): truncation
-    return 2LL * roi.x <= x1 + x2 && x1 + x2 <= 2LL * roi.z && 2LL * roi.y <= y1 + y2 && y1 + y2 <= 2LL * roi.w;
-}
-
 template <bool NATIVE>
 __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ offsets,
                                                             const float* __restrict__ dets, int max_det, int row, int capacity,
@@ -291,7 +261,7 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
 //   x = (x0 - dX) icdist; y = (y0 - dY) icdist          (k4..k6, s1..s4, tilt = 0 for the 5-coefficient model of
 // camera_calibration.json; OpenCV leaves the loop if icdist < 0).  Then the ray (x, y, 1) meets the plane n.X + d = 0:
 //   s = -d / (n . ray); X_cam = s ray; X_world = R^T (X_cam - t); no point when |n . ray| < 1e-9.
-// (GeomParams: with CameraRow above.)
+// (GeomParams: with CameraRow in measure_dev.h.)
 
 // One point; false where the reference returns None.  Shared by pixels_to_world_kernel and measure_frames_kernel.
 __device__ __forceinline__ bool pixel_to_world(const GeomParams& g, double u, double v, double o[3]) {

@@ -1012,6 +1012,56 @@ int32_t vti_mask_polygons(vti_ctx* c, const uint8_t* masks, int32_t n, const int
     return VTI_OK;
 }
 
+static bool annotate_sizes_ok(int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points) {
+    return n_sel >= 1 && max_det >= 1 && max_det <= VTI_MEASURE_MAX_DET && H0 >= 1 && W0 >= 1 && H0 <= 8192 && W0 <= 8192 &&
+           max_points >= 0 && (int64_t)n_sel * H0 * W0 * 3 <= (int64_t)1 << 40;
+}
+
+int64_t vti_annotate_scratch_bytes(const vti_ctx* c, int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points) {
+    if (!c || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points)) return 0;
+    AnnotateLayout L;
+    annotate_layout(n_sel, max_det, H0, W0, max_points, L);
+    return (int64_t)L.total;
+}
+
+int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const void* cameras, int32_t n_cams,
+                     const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
+                     const int32_t* counts, const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                     const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
+                     int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_annotate: null ctx");
+    if (B < 1 || capacity < 0 || n_cams < 1 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
+        return bad("vti_annotate: bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                   "1 <= H0, W0 <= 8192; native 0 or 1)");
+    if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
+        !dev_select || !out || !status || (capacity && !masks))
+        return bad("vti_annotate: null pointer");
+    for (int32_t k = 0; k < n_sel; ++k)
+        if (host_select[k] < 0 || host_select[k] >= B) {
+            char msg[120];
+            snprintf(msg, sizeof msg, "vti_annotate: host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
+            return bad(msg);
+        }
+    if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
+        return bad("vti_annotate: the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
+    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
+        return bad(native ? "vti_annotate: native masks must be 8-byte aligned" : "vti_annotate: masks must be 16-byte aligned");
+    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
+        return bad("vti_annotate: misaligned measurement rows or status");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_annotate: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points))
+        return bad("vti_annotate: scratch smaller than vti_annotate_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_annotate")) return drc;
+    const vti_desc& d = c->plan.desc;
+    VTI_HIP(c, launch_annotate(frames, B, H0, W0, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det,
+                               d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
+                               scratch, (hipStream_t)stream), "annotate kernels");
+    return VTI_OK;
+}
+
 int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void* stream) {
     int32_t rc = check_ready(c, B, "vti_debug_conv_output");
     if (rc) return rc;

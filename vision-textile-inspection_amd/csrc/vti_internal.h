@@ -332,6 +332,22 @@ hipError_t launch_mask_polygons(const uint8_t* masks, int n, const int* n_live, 
                                 double padx, double pady, int H0, int W0, int strategy, void* scratch, int* offsets, float* points,
                                 long long max_points, hipStream_t st);
 
+// annotate.hip: vti_annotate (process_frame's annotated frame).  The scratch holds, per selected frame: the display list (3 + 7 *
+// max_det records of 32 bytes), 16 ints of counts, the envelope's points int2 [W0], the outline's vertices int2 [max_points], the
+// fabric union u64 [H0, WW] and one labelling area of the contour tracer (parent | runs | row_start, as polygons.hip's).
+struct AnnotateLayout {
+    int WW;                    // 64-bit words per union row
+    bool in_lds;               // the tracer keeps the union in LDS
+    size_t off_recs, off_meta, off_env, off_cont, off_union, off_areas, area_bytes, off_runs, off_rows, total;
+};
+void annotate_layout(int n_sel, int max_det, int H0, int W0, int max_points, AnnotateLayout& L);
+// cameras: a packed camera table in device memory; select: the device copy of the (host-checked) selection; native = 1: H, W unused
+hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const void* cameras, int n_cams, const int* cam_of_frame,
+                           const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
+                           const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
+                           const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
+                           int* status, void* scratch, hipStream_t st);
+
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
 void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,
                      int th = 0, int tw = 0, int wn = 0, int nrep = 0, bool allow_pk = true);

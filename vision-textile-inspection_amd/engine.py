@@ -482,6 +482,76 @@ class Engine:
             check(self._ctx, lib().vti_measure(self._ctx, C.byref(cp), *rest))
         return r
 
+    # ---- process_frame's annotated frame (measurement.py:219-504): the overlay on a selection of the batch ------------------
+    def annotate_scratch_bytes(self, n_sel, max_det, H0, W0, max_points):
+        return int(lib().vti_annotate_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))
+
+    def annotate(self, frames, out, meas, params_or_table, select, cameras=None, native=False, result=None, max_points=16384):
+        """The frames `select` of the batch with the reference's overlay drawn on them: vti_annotate, byte for byte
+        annotate.rasterise(frame, annotate.display_list(...)).  frames: the contiguous uint8 [B,H0,W0,3] BGR device batch predict
+        consumed; out: its output set; meas: measure(..., stitch_rows=True)'s dict on the same set; params_or_table: the
+        MeasureParams of that measure call, a list of them, or the table of pack_cameras(); cameras: as measure() took them (None:
+        the first row serves every frame); select: host integers in [0, B), any order, duplicates allowed (ValueError otherwise).
+        max_points: room for the fabric outline's vertices per frame.  Returns device tensors, no host synchronisation:
+        dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]: VTI_ANNOTATE_OUTLINE_SKIPPED where the outline did not fit).  `result`: the
+        same dict preallocated.  Text is the host's: annotate.text_items / put_text."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("annotate: frames must be a uint8 [B,H0,W0,3] tensor")
+        B, H0, W0, _ = frames.shape
+        dets, masks = out["dets"], out["masks"]
+        dev = dets.device
+        if out["counts"].shape[0] != B:
+            raise ValueError(f"annotate: {B} frames but an output set of {out['counts'].shape[0]}")
+        max_det, capacity = dets.shape[1], masks.shape[0]
+        sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
+        if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
+            raise ValueError("annotate: select must be a non-empty sequence of frame indices")
+        if sel.min() < 0 or sel.max() >= B:
+            raise ValueError(f"annotate: frame index outside [0, {B})")
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        n_sel = int(sel.size)
+        for key in ("frame_i32", "stitch_f64", "stitch_i32"):
+            if meas.get(key) is None:
+                raise ValueError(f"annotate: meas needs {key} (measure(..., stitch_rows=True))")
+        # everything above is about shapes and values; what needs a device comes from here on
+        if not frames.is_cuda or not frames.is_contiguous():
+            raise ValueError("annotate: frames must be the contiguous device batch predict consumed")
+        table = params_or_table
+        if not isinstance(table, torch.Tensor):
+            table = self.pack_cameras(table if isinstance(table, (list, tuple)) else [table], dev)
+        row = int(lib().vti_measure_cameras_bytes(1))
+        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
+            raise ValueError("annotate: params_or_table must be MeasureParams or the u8 table of pack_cameras() on the outputs' device")
+        n_cams = table.numel() // row
+        if cameras is not None and not (isinstance(cameras, torch.Tensor) and cameras.is_cuda):
+            host = np.asarray(cameras.numpy() if isinstance(cameras, torch.Tensor) else cameras)
+            if host.shape != (B,) or host.dtype.kind not in "iu":
+                raise ValueError(f"annotate: cameras must be {B} integers, one per frame")
+            if host.min() < 0 or host.max() >= n_cams:
+                raise ValueError(f"annotate: camera index outside [0, {n_cams})")
+            cameras = torch.from_numpy(host.astype(np.int32)).to(dev)
+        elif cameras is not None and (cameras.dtype != torch.int32 or tuple(cameras.shape) != (B,) or not cameras.is_contiguous()):
+            raise ValueError(f"annotate: cameras must be a contiguous int32 [{B}] tensor on the outputs' device")
+        r = dict(result or {})
+        if "frames" not in r:
+            r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
+        if "status" not in r:
+            r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
+        need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
+        if need <= 0:
+            raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+        ws = getattr(self, "_annotate_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            self._annotate_ws = None
+            ws = self._annotate_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        dev_sel = torch.from_numpy(sel).to(dev)
+        check(self._ctx, lib().vti_annotate(
+            self._ctx, _ptr(frames), B, H0, W0, _ptr(table), n_cams, _ptr(cameras), _ptr(masks) if capacity else C.c_void_p(0),
+            int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
+            _ptr(meas["frame_i32"]), _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel),
+            n_sel, int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        return r
+
     # ---- Results.masks.xy: instance polygons in frame pixels (vti_mask_polygons) -------------------------------------------
     def mask_polygons_scratch_bytes(self, H, W, row_bytes):
         return int(lib().vti_mask_polygons_scratch_bytes(self._ctx, int(H), int(W), int(row_bytes)))

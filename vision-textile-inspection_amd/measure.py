@@ -8,8 +8,11 @@
 
 The per-frame work (ROI filter, moments, fabric envelope, widths, row selection, proximity filter, distances, averages) runs in
 libvti's vti_measure on the predict output set that is already on the device; the host reads back B small records once and keeps
-only the reference's stateful smoothing (the two frame_buffer-long deques and their medians, measurement.py:474-484).  Nothing is
-drawn: the annotated frame the reference also returns is out of scope.
+only the reference's stateful smoothing (the two frame_buffer-long deques and their medians, measurement.py:474-484).
+
+The annotated frame the reference also returns is drawn on request, for a selection of the batch (`annotate=`): libvti's
+vti_annotate paints the overlay on the device batch predict consumed and the selected pictures come back in one copy; the text
+(which holds the smoothed values) is returned as annotate.text_items and drawn by annotate.put_text where OpenCV is installed.
 """
 import ctypes as C
 import dataclasses
@@ -20,6 +23,7 @@ from datetime import datetime
 import numpy as np
 import torch
 
+from . import annotate as _annotate
 from ._lib import VTI_MEASURE_BAD_CAMERA, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VtiMeasureParams
 from .consumer import rodrigues
 
@@ -116,18 +120,30 @@ class _DeviceStage:
         self._res = {}
 
     @torch.inference_mode()
-    def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks):
-        """-> (f64 [B,2], i32 [B,6]) on the host.  params / cameras as Engine.measure takes them; a callable `params` is called with
-        (engine, device) once the outputs exist (the camera table needs both)."""
+    def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None):
+        """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
+        selected frames.  params / cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the
+        outputs exist (the camera table needs both)."""
         shapes = self.model._differing_shapes(frames)
         table = None
         if shapes is not None:
+            if annotate is not None:
+                raise ValueError("process_frames: annotate needs frames of one size; the frames of this list differ in shape "
+                                 "(vti_annotate has no frame-table form)")
             if retina_masks:
                 raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
             eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False)
             B, H0, W0 = len(shapes), None, None
         else:
-            eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks)
+            eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks,
+                                                                 keep_frames=annotate is not None)
+        sel = None
+        if annotate is not None:
+            sel = np.arange(B) if isinstance(annotate, str) and annotate == "all" else np.asarray(annotate)
+            if isinstance(annotate, str) and annotate != "all":
+                raise ValueError('process_frames: annotate must be None, "all" or a sequence of frame indices')
+            if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu" or sel.min() < 0 or sel.max() >= B:
+                raise ValueError(f"process_frames: annotate must name frames in [0, {B})")
         key = (id(o), B)
         res = self._res.get(key)
         if res is None:           # one buffer for both records: a single device -> host read
@@ -137,13 +153,50 @@ class _DeviceStage:
             self._res = {key: res}
         if callable(params):
             params = params(eng, o["dets"].device)
-        eng.measure(o, params, H0, W0, native=bool(retina_masks), stitch_rows=False, result=res, cameras=cameras, frames=table)
+        r = eng.measure(o, params, H0, W0, native=bool(retina_masks), stitch_rows=sel is not None, result=res, cameras=cameras,
+                        frames=table)
+        if sel is not None:       # measure() allocated the per-slot rows into its copy of the dict: keep them for the next call
+            res.update(stitch_f64=r["stitch_f64"], stitch_i32=r["stitch_i32"])
         host = res["buf"].cpu().numpy()
-        return host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
+        f64, i32 = host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
+        if sel is None:
+            return f64, i32
+        return f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks))
+
+    def _annotated(self, eng, o, res, params, cameras, sel, native):
+        """vti_annotate on the batch predict consumed; the selected pictures in one device -> host copy, and of the per-slot rows only
+        those of the selected frames."""
+        ann = eng.annotate(self.model._last_frames, o, res, params, sel, cameras=cameras, native=native)
+        self.model._last_frames = None            # the launches are enqueued: the batch need not outlive the call
+        pics = ann["frames"].cpu().numpy()
+        dev = o["dets"].device
+        uniq = np.unique(sel)
+        cnt_off = torch.cat((o["counts"], o["offsets"])).cpu().numpy()
+        B = o["counts"].shape[0]
+        cap = o["masks"].shape[0]
+        spans = {int(b): (min(int(cnt_off[B + b]), cap), min(int(cnt_off[B + b]) + int(cnt_off[b]), cap)) for b in uniq}
+        idx = np.concatenate([np.arange(lo, hi) for lo, hi in spans.values()] + [np.zeros(0, np.int64)]).astype(np.int64)
+        di = torch.from_numpy(idx).to(dev)
+        sf = res["stitch_f64"].index_select(0, di).cpu().numpy()
+        si = res["stitch_i32"].index_select(0, di).cpu().numpy()
+        rows, at = {}, 0
+        for b, (lo, hi) in spans.items():
+            rows[b] = dict(f64=sf[at:at + hi - lo], flags=si[at:at + hi - lo, 0], rank=si[at:at + hi - lo, 1])
+            at += hi - lo
+        return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
+
+    @staticmethod
+    def _with_text(annotated, records, i32, min_stitches):
+        """[(frame index, picture, rows)] -> [(frame index, picture, text_items)] with the strings built from the frames' records."""
+        out = []
+        for b, pic, rows in annotated:
+            rows = dict(rows, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
+            out.append((b, pic, _annotate.text_items(records[b], rows, pic.shape[0], min_stitches(b))))
+        return out
 
 
 class StitchMeasurer(_DeviceStage):
-    """StitchMeasurementApp.process_frame without the camera and the drawing: model = a vti_amd YOLO, params = MeasureParams.
+    """StitchMeasurementApp.process_frame without the camera: model = a vti_amd YOLO, params = MeasureParams.
     The smoothing deques live here, so consecutive calls continue one stream of frames, as the reference's app does."""
 
     def __init__(self, model, params, frame_buffer=8):
@@ -154,16 +207,32 @@ class StitchMeasurer(_DeviceStage):
         self._record = self._stream.record
         self._cp = self.params.to_c()
 
-    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
+    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None):
         """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them.  The reference predicts on the RGB conversion
         with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
-        Returns one record per frame, in frame order, with the smoothing applied frame by frame."""
-        f64, i32 = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks)
-        return [self._record(f64[b], i32[b]) for b in range(len(f64))]
+        Returns one record per frame, in frame order, with the smoothing applied frame by frame.
+        annotate: "all" or a sequence of frame indices -> (annotated, records): annotated = [(frame index, BGR ndarray H0 x W0 x 3 with
+        the reference's overlay, text_items)] for the selection (drawn on the device, one copy to the host; the text is
+        annotate.text_items', for annotate.put_text), records exactly as without it."""
+        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate)
+        f64, i32 = got[:2]
+        records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
+        if annotate is None:
+            return records
+        return self._with_text(got[2], records, i32, lambda b: self.params.min_stitches), records
 
-    def process_frame(self, frame, **kw):
-        """One frame: the record process_frame returns (without the annotated image)."""
-        return self.process_frames(np.asarray(frame)[None], **kw)[0]
+    def process_frame(self, frame, annotate=False, **kw):
+        """One frame: the record process_frame returns; annotate=True: the reference's tuple (annotated BGR ndarray, record), the text
+        drawn too where OpenCV is installed (annotate.put_text; without it the picture carries everything but the text)."""
+        if not annotate:
+            return self.process_frames(np.asarray(frame)[None], **kw)[0]
+        annotated, records = self.process_frames(np.asarray(frame)[None], annotate=[0], **kw)
+        _, pic, items = annotated[0]
+        try:
+            _annotate.put_text(pic, items)
+        except ImportError:
+            pass
+        return pic, records[0]
 
 
 class MultiCameraMeasurer(_DeviceStage):
@@ -186,14 +255,18 @@ class MultiCameraMeasurer(_DeviceStage):
             self._tables[key] = (eng, eng.pack_cameras(self.params, device))
         return self._tables[key][1]
 
-    def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False):
+    def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None):
         """frames as StitchMeasurer.process_frames, or a list of frames whose sizes differ (cameras of several resolutions in one
         batch: one predict, one vti_measure_frames, one read); cameras: one index into params_by_camera per frame (host integers).
         Returns one record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame
-        order."""
+        order.  annotate: as StitchMeasurer.process_frames (frames of one size only) -> (annotated, records)."""
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
-        f64, i32 = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks)
-        return self._records(f64, i32, cams.tolist())
+        got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate)
+        f64, i32 = got[:2]
+        records = self._records(f64, i32, cams.tolist())
+        if annotate is None:
+            return records
+        return self._with_text(got[2], records, i32, lambda b: self.params[int(cams[b])].min_stitches), records
 
     def _records(self, f64, i32, cams):
         """Frame b's record from camera cams[b]'s stream, in frame order."""

@@ -231,7 +231,7 @@ class YOLO:
         eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits")
         return eng, o, table, (H, W)
 
-    def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks):
+    def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks, keep_frames=False):
         """The device half of predict(): enqueues the whole pipeline into the cached output set and returns
         (engine, output set, (B, H0, W0), letterbox (H, W)) without reading anything back (predict() and
         measure.StitchMeasurer both start here)."""
@@ -252,6 +252,9 @@ class YOLO:
             self._outs.clear()              # one cached set at a time: a new shape replaces the old one
             o = self._outs[key] = eng.alloc_outputs(B, max_det, B * max_det, "bits", frames.device, native_hw=native_hw)
         eng.predict_into(frames, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks))
+        # the device batch this predict consumed is kept only for a caller that draws on it (measure.py, annotate=): otherwise
+        # the model holds no reference to it once the call returns
+        self._last_frames = frames if keep_frames else None
         return eng, o, (B, H0, W0), (H, W)
 
     @torch.inference_mode()
