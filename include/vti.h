@@ -420,6 +420,32 @@ int32_t vti_annotate(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t
                      const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points, uint8_t* dev_out,
                      int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- the saved JPEG on device (cv2.imwrite(save_path, annotated): main.py:314, measurement.py:536) -------------------------------- */
+/* n frames u8 [n,H0,W0,3] (BGR as cv2's frames are; rgb = 1: RGB) -> n JPEG files, byte for byte the package's jpeg.py: libjpeg's
+ * baseline file at `quality` (jpeg_set_quality, force_baseline), 8 bit, YCbCr 4:2:0, one interleaved scan, the Annex K quantisation
+ * and Huffman tables, no restart interval; SOI, APP0 (JFIF 1.01, units 0, density 1 x 1), DQT 0, DQT 1, SOF0, DHT DC0, AC0, DC1, AC1,
+ * SOS, data, EOI.  Integer arithmetic only (jccolor.c, h2v2_downsample with its 1, 2 bias, jfdctint.c, jcdctmgr.c's division,
+ * jchuff.c); partial MCUs are completed by edge replication and by libjpeg's dummy blocks.
+ * dev_frames: any byte address (vti_annotate's dev_out feeds it directly, so does a raw batch); never written.  1 <= n, 1 <= H0,
+ * W0 <= 8192, n * ceil(H0/16) * ceil(W0/16) <= 2^28, 1 <= quality <= 100, rgb 0 or 1, max_bytes >= 0.
+ * dev_byte_offsets i64 [n+1] always receives the exclusive scan of the n file sizes, exact whatever max_bytes is; dev_out receives
+ * file k at offsets[k] .. offsets[k+1], back to back and unpadded, only when offsets[n] <= max_bytes (otherwise nothing is written
+ * there: call again with a larger buffer; dev_out may be NULL when max_bytes is 0).  Bytes of dev_out at and beyond offsets[n] are
+ * never written.  dev_scratch: >= vti_encode_jpeg_scratch_bytes(), 256-byte aligned.  Every argument check (VTI_ERR_ARG, a short
+ * scratch included) runs before the first HIP call; ctx, device and weights rules as vti_mask_polygons (no weights needed).
+ * Nine launches on `stream` (blocks, bit lengths, bit scan, zero, bits, 0xFF count, chunk scan, offsets, write), no memset, no host
+ * synchronisation.  Positions in the bit stream are 64-bit.
+ * Host only: device scratch bytes for n frames of H0 x W0 (0 on a bad argument); a function of these three only.  With M = ceil(H0/16)
+ * * ceil(W0/16) MCUs per frame and S = ceil(6 * M * 1658 / 8) bytes, the longest unstuffed scan (1658 bits per block: DC 9 + 11, 63
+ * AC coefficients of 16 + 10), rounded up to 4096-byte chunks: 1024 + 16 n + n * (768 M coefficients + 48 M bit positions + S + S /
+ * 1024), each part rounded up to 256.  960 x 1280: 9.9 MB per frame, 633 MB for 64. */
+int64_t vti_encode_jpeg_scratch_bytes(const vti_ctx* ctx, int32_t n, int32_t H0, int32_t W0);
+/* Host only: an upper bound of dev_byte_offsets[n] for any content and quality (0 on a bad argument): n * (625 + 2 S). */
+int64_t vti_encode_jpeg_max_bytes(int32_t n, int32_t H0, int32_t W0);
+int32_t vti_encode_jpeg(vti_ctx* ctx, const uint8_t* dev_frames, int32_t n, int32_t H0, int32_t W0, int32_t rgb, int32_t quality,
+                        void* dev_scratch, size_t scratch_bytes, int64_t* dev_byte_offsets, uint8_t* dev_out, int64_t max_bytes,
+                        void* stream);
+
 /* ---- per-layer access for parity tests ------------------------------------------- */
 /* Copies the activation written by conv `i` of the last vti_forward into dev_out as
  * f32 NCHW [B,c2,h_out,w_out] (test hook; not on the hot path). */

@@ -1062,6 +1062,38 @@ int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, i
     return VTI_OK;
 }
 
+int64_t vti_encode_jpeg_scratch_bytes(const vti_ctx* c, int32_t n, int32_t H0, int32_t W0) {
+    JpegLayout L;
+    if (!c || !encode_jpeg_layout(n, H0, W0, L)) return 0;
+    return (int64_t)L.total;
+}
+
+int64_t vti_encode_jpeg_max_bytes(int32_t n, int32_t H0, int32_t W0) {
+    JpegLayout L;
+    if (!encode_jpeg_layout(n, H0, W0, L)) return 0;
+    return (int64_t)n * L.max_file;
+}
+
+int32_t vti_encode_jpeg(vti_ctx* c, const uint8_t* frames, int32_t n, int32_t H0, int32_t W0, int32_t rgb, int32_t quality,
+                        void* scratch, size_t scratch_bytes, int64_t* offsets, uint8_t* out, int64_t max_bytes, void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_encode_jpeg: null ctx");
+    JpegLayout L;
+    if (!encode_jpeg_layout(n, H0, W0, L))
+        return bad("vti_encode_jpeg: bad size (n >= 1; 1 <= H0, W0 <= 8192; n * ceil(H0/16) * ceil(W0/16) <= 2^28)");
+    if (quality < 1 || quality > 100 || (rgb != 0 && rgb != 1) || max_bytes < 0)
+        return bad("vti_encode_jpeg: 1 <= quality <= 100, rgb 0 or 1, max_bytes >= 0");
+    if (!frames || !offsets || (max_bytes && !out)) return bad("vti_encode_jpeg: null pointer");
+    if ((uintptr_t)offsets & 7) return bad("vti_encode_jpeg: dev_byte_offsets must be 8-byte aligned");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_encode_jpeg: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < (int64_t)L.total) return bad("vti_encode_jpeg: scratch smaller than vti_encode_jpeg_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_encode_jpeg")) return drc;
+    VTI_HIP(c, launch_encode_jpeg(frames, n, H0, W0, rgb, quality, scratch, (long long*)offsets, out, (long long)max_bytes,
+                                  (hipStream_t)stream), "encode_jpeg kernels");
+    return VTI_OK;
+}
+
 int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void* stream) {
     int32_t rc = check_ready(c, B, "vti_debug_conv_output");
     if (rc) return rc;

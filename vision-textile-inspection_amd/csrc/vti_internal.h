@@ -348,6 +348,23 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
                            const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
                            int* status, void* scratch, hipStream_t st);
 
+// jpeg.hip: vti_encode_jpeg (the saved JPEG).  The scratch holds: the header's bytes (1 KiB) | bit total u64 [n] | file size i64 [n] |
+// coefficients i16 [n, MCUs, 6, 64] | block bit positions u64 [n, blocks] | the unstuffed stream, NC chunks of 4096 bytes per frame
+// (the worst case of 1658 bits per block) | 0xFF count u32 [n, NC].
+struct JpegLayout {
+    int mr, mc;                // MCU rows and columns of a frame
+    long long nblk;            // blocks per frame in the scan, dummy blocks included (6 per MCU)
+    long long stream_bytes;    // the most bytes a frame's unstuffed stream can have
+    long long NC;              // 4096-byte chunks that hold them
+    long long max_file;        // the most bytes one file can have
+    size_t off_fbits, off_fsize, off_coef, off_bitpos, off_stream, off_chunk, total;
+};
+// false on sizes outside 1 <= n, 1 <= H0, W0 <= 8192, n * MCUs <= 2^28
+bool encode_jpeg_layout(long long n, int H0, int W0, JpegLayout& L);
+void encode_jpeg_header(int H0, int W0, int quality, uint8_t out[624]);      // SOI .. SOS: 623 bytes and one of padding
+hipError_t launch_encode_jpeg(const uint8_t* frames, int n, int H0, int W0, int rgb, int quality, void* scratch, long long* offsets,
+                              uint8_t* out, long long max_bytes, hipStream_t st);
+
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
 void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,
                      int th = 0, int tw = 0, int wn = 0, int nrep = 0, bool allow_pk = true);

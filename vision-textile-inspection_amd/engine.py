@@ -552,6 +552,52 @@ class Engine:
             n_sel, int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         return r
 
+    # ---- the saved JPEG (cv2.imwrite(save_path, annotated), main.py:314): vti_encode_jpeg ----------------------------------
+    def encode_jpeg_scratch_bytes(self, n, H0, W0):
+        return int(lib().vti_encode_jpeg_scratch_bytes(self._ctx, int(n), int(H0), int(W0)))
+
+    def encode_jpeg(self, frames, quality=95, rgb=False, max_bytes=None):
+        """The frames as JPEG files, byte for byte jpeg.encode(frame, quality, rgb) (libjpeg's baseline 4:2:0 file): vti_encode_jpeg.
+        frames: a contiguous uint8 [n,H0,W0,3] device tensor, BGR unless rgb (annotate()'s "frames", or a raw batch); never written.
+        -> (out u8 [max_bytes], offsets i64 [n+1]) on the device: file k is out[offsets[k]:offsets[k+1]].  max_bytes: the room for
+        the n files, 3 * n * H0 * W0 + 1024 * n by default; when offsets[n] exceeds it (one host read of that value) the call runs
+        again with exactly offsets[n].  The scratch is kept per (n, H0, W0)."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("encode_jpeg: frames must be a uint8 [n,H0,W0,3] tensor")
+        n, H0, W0, _ = frames.shape
+        quality = int(quality)
+        if not 1 <= quality <= 100:
+            raise ValueError(f"encode_jpeg: quality must be in 1..100, got {quality}")
+        if max_bytes is None:
+            max_bytes = 3 * n * H0 * W0 + 1024 * n
+        max_bytes = int(max_bytes)
+        if max_bytes < 0:
+            raise ValueError("encode_jpeg: max_bytes must be >= 0")
+        need = self.encode_jpeg_scratch_bytes(n, H0, W0)
+        if need <= 0:
+            raise ValueError(f"encode_jpeg: unsupported geometry (n={n}, {H0}x{W0}; 1 <= H0, W0 <= 8192)")
+        if not frames.is_cuda or not frames.is_contiguous():
+            raise ValueError("encode_jpeg: frames must be a contiguous device tensor")
+        dev = frames.device
+        key = (n, H0, W0, str(dev))
+        ws = getattr(self, "_jpeg_ws", None)
+        if ws is None or ws[0] != key:
+            self._jpeg_ws = None                        # free the old scratch before the new one is allocated
+            ws = self._jpeg_ws = (key, torch.empty(need, dtype=torch.uint8, device=dev))
+        ws = ws[1]
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+
+        def launch(room):
+            out = torch.empty((room,), dtype=torch.uint8, device=dev)
+            check(self._ctx, lib().vti_encode_jpeg(self._ctx, _ptr(frames), n, H0, W0, int(bool(rgb)), quality, _ptr(ws), ws.numel(),
+                                                   _ptr(offsets), _ptr(out) if room else C.c_void_p(0), room, _stream()))
+            return out
+        out = launch(max_bytes)
+        total = int(offsets[n])
+        if total > max_bytes:                           # nothing was written: run again with exactly the room the files need
+            out = launch(total)
+        return out, offsets
+
     # ---- Results.masks.xy: instance polygons in frame pixels (vti_mask_polygons) -------------------------------------------
     def mask_polygons_scratch_bytes(self, H, W, row_bytes):
         return int(lib().vti_mask_polygons_scratch_bytes(self._ctx, int(H), int(W), int(row_bytes)))

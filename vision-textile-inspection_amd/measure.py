@@ -13,6 +13,8 @@ only the reference's stateful smoothing (the two frame_buffer-long deques and th
 The annotated frame the reference also returns is drawn on request, for a selection of the batch (`annotate=`): libvti's
 vti_annotate paints the overlay on the device batch predict consumed and the selected pictures come back in one copy; the text
 (which holds the smoothed values) is returned as annotate.text_items and drawn by annotate.put_text where OpenCV is installed.
+With `encode="jpeg"` the selected pictures are also encoded on the device (vti_encode_jpeg: the file cv2.imwrite would save of that
+picture, jpeg.py) and only the files' bytes come back; the text still rides along as text_items, it is not in the JPEG.
 """
 import ctypes as C
 import dataclasses
@@ -120,10 +122,19 @@ class _DeviceStage:
         self._res = {}
 
     @torch.inference_mode()
-    def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None):
+    def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
+                       jpeg_quality=95):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
-        selected frames.  params / cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the
-        outputs exist (the camera table needs both)."""
+        selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0.  params /
+        cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the outputs exist (the
+        camera table needs both)."""
+        if encode is not None:
+            if encode != "jpeg":
+                raise ValueError(f'process_frames: encode must be None or "jpeg", got {encode!r}')
+            if annotate is None:
+                raise ValueError("process_frames: encode needs annotate (the frames to encode are the annotated selection)")
+            if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, (int, np.integer)) or not 1 <= jpeg_quality <= 100:
+                raise ValueError(f"process_frames: jpeg_quality must be an integer in 1..100, got {jpeg_quality!r}")
         shapes = self.model._differing_shapes(frames)
         table = None
         if shapes is not None:
@@ -161,14 +172,22 @@ class _DeviceStage:
         f64, i32 = host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
         if sel is None:
             return f64, i32
-        return f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks))
+        return f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks),
+                                         int(jpeg_quality) if encode else None), H0
 
-    def _annotated(self, eng, o, res, params, cameras, sel, native):
+    def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None):
         """vti_annotate on the batch predict consumed; the selected pictures in one device -> host copy, and of the per-slot rows only
-        those of the selected frames."""
+        those of the selected frames.  jpeg_quality: the pictures go through vti_encode_jpeg first and the copy is of the files'
+        bytes (one read of the offsets, one of out[:offsets[n]])."""
         ann = eng.annotate(self.model._last_frames, o, res, params, sel, cameras=cameras, native=native)
         self.model._last_frames = None            # the launches are enqueued: the batch need not outlive the call
-        pics = ann["frames"].cpu().numpy()
+        if jpeg_quality is None:
+            pics = ann["frames"].cpu().numpy()
+        else:
+            data, off = eng.encode_jpeg(ann["frames"], quality=jpeg_quality)
+            off = off.cpu().numpy()
+            data = data[:int(off[-1])].cpu().numpy().tobytes()
+            pics = [data[off[k]:off[k + 1]] for k in range(len(sel))]
         dev = o["dets"].device
         uniq = np.unique(sel)
         cnt_off = torch.cat((o["counts"], o["offsets"])).cpu().numpy()
@@ -186,12 +205,13 @@ class _DeviceStage:
         return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
 
     @staticmethod
-    def _with_text(annotated, records, i32, min_stitches):
-        """[(frame index, picture, rows)] -> [(frame index, picture, text_items)] with the strings built from the frames' records."""
+    def _with_text(annotated, records, i32, min_stitches, H0):
+        """[(frame index, picture, rows)] -> [(frame index, picture, text_items)] with the strings built from the frames' records
+        (picture: the BGR ndarray of height H0, or its JPEG file's bytes)."""
         out = []
         for b, pic, rows in annotated:
             rows = dict(rows, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
-            out.append((b, pic, _annotate.text_items(records[b], rows, pic.shape[0], min_stitches(b))))
+            out.append((b, pic, _annotate.text_items(records[b], rows, H0, min_stitches(b))))
         return out
 
 
@@ -207,19 +227,23 @@ class StitchMeasurer(_DeviceStage):
         self._record = self._stream.record
         self._cp = self.params.to_c()
 
-    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None):
+    def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None, encode=None,
+                       jpeg_quality=95):
         """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them.  The reference predicts on the RGB conversion
         with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
         Returns one record per frame, in frame order, with the smoothing applied frame by frame.
         annotate: "all" or a sequence of frame indices -> (annotated, records): annotated = [(frame index, BGR ndarray H0 x W0 x 3 with
         the reference's overlay, text_items)] for the selection (drawn on the device, one copy to the host; the text is
-        annotate.text_items', for annotate.put_text), records exactly as without it."""
-        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate)
+        annotate.text_items', for annotate.put_text), records exactly as without it.
+        encode="jpeg" (with annotate): each annotated item is (frame index, bytes, text_items), the bytes being the JPEG file
+        cv2.imwrite(path, picture) saves at jpeg_quality (jpeg.encode, byte for byte), encoded on the device; the text is NOT in
+        that picture, it still comes as text_items.  Any other encode, or encode without annotate, is a ValueError."""
+        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality)
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
         if annotate is None:
             return records
-        return self._with_text(got[2], records, i32, lambda b: self.params.min_stitches), records
+        return self._with_text(got[2], records, i32, lambda b: self.params.min_stitches, got[3]), records
 
     def process_frame(self, frame, annotate=False, **kw):
         """One frame: the record process_frame returns; annotate=True: the reference's tuple (annotated BGR ndarray, record), the text
@@ -255,18 +279,19 @@ class MultiCameraMeasurer(_DeviceStage):
             self._tables[key] = (eng, eng.pack_cameras(self.params, device))
         return self._tables[key][1]
 
-    def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None):
+    def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None,
+                       encode=None, jpeg_quality=95):
         """frames as StitchMeasurer.process_frames, or a list of frames whose sizes differ (cameras of several resolutions in one
         batch: one predict, one vti_measure_frames, one read); cameras: one index into params_by_camera per frame (host integers).
         Returns one record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame
-        order.  annotate: as StitchMeasurer.process_frames (frames of one size only) -> (annotated, records)."""
+        order.  annotate, encode, jpeg_quality: as StitchMeasurer.process_frames (frames of one size only) -> (annotated, records)."""
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
-        got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate)
+        got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         if annotate is None:
             return records
-        return self._with_text(got[2], records, i32, lambda b: self.params[int(cams[b])].min_stitches), records
+        return self._with_text(got[2], records, i32, lambda b: self.params[int(cams[b])].min_stitches, got[3]), records
 
     def _records(self, f64, i32, cams):
         """Frame b's record from camera cams[b]'s stream, in frame order."""
