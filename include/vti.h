@@ -446,6 +446,45 @@ int32_t vti_encode_jpeg(vti_ctx* ctx, const uint8_t* dev_frames, int32_t n, int3
                         void* dev_scratch, size_t scratch_bytes, int64_t* dev_byte_offsets, uint8_t* dev_out, int64_t max_bytes,
                         void* stream);
 
+/* ---- JPEG files -> frames on device (cap.read() of a motion-JPEG camera, cv2.imread, Ultralytics' file sources) ----------------- */
+/* n files -> n frames u8 [H0,W0,3], byte for byte the package's jpeg.decode, which is pinned to libjpeg-turbo's output with its
+ * defaults (JDCT_ISLOW, fancy upsampling): jdhuff.c, jidctint.c with the dequantisation inside, jdsample.c, jdcolor.c; integer
+ * arithmetic only.  SUPPORTED: baseline sequential (SOF0), 8-bit samples, three components YCbCr, luma sampling 2x2 (4:2:0), 2x1
+ * (4:2:2) or 1x1 (4:4:4) with 1x1 chroma, one interleaved scan, 8-bit DQT, the file's DHT tables or Annex K's when it has none
+ * (motion-JPEG), any DRI restart interval, APPn / COM segments and 0xFF fill bytes skipped, 1 <= H0, W0 <= 8192, a scan of at most
+ * 2^28 bytes.  Everything else (progressive, greyscale, four components, Adobe transform 0, other sampling factors, 12-bit
+ * samples, 16-bit DQT, arithmetic coding, several scans) is refused by the host parser with VTI_ERR_UNSUPPORTED and a text that
+ * names the reason; a malformed or truncated header is VTI_ERR_ARG.  There is no approximate decoding.
+ * Host only: bytes of a descriptor table of n files (0 when n < 1 or n > 4096). */
+int64_t vti_decode_jpeg_table_bytes(int32_t n);
+/* Host only: parses and validates file k = host_files[host_file_offsets[k] .. host_file_offsets[k+1]) for k = 0 .. n-1 (offsets
+ * ascending from >= 0); the first failing file's index and the reason are in vti_last_error (ctx only receives the text and may be
+ * NULL).  Writes the descriptor table (nbytes >= vti_decode_jpeg_table_bytes(n); its format is private to the library build),
+ * out_H0 / out_W0 [n] from the headers, the frames' places out_byte_offsets [n+1] in dev_out and *out_scratch_bytes.  layout 0:
+ * the frames back to back, each at a multiple of 16 bytes, [n] = the buffer's size (a multiple of 16, at least 16): exactly the
+ * rule of vti_pack_frames' frame buffer, so dev_out feeds vti_predict_frames directly.  layout 1: dense u8 [n,H0,W0,3]; all files
+ * must have one size (VTI_ERR_ARG otherwise).  segment_bytes: the bytes of the scan one lane decodes at a time, a power of two from
+ * 16 to 4096, or 0 for the library's default (256).  Equal inputs give equal bytes.  The table describes the files at these very
+ * offsets of the buffer that is later copied to the device. */
+int32_t vti_decode_jpeg_plan(vti_ctx* ctx, const uint8_t* host_files, const int64_t* host_file_offsets, int32_t n,
+                             int32_t segment_bytes, int32_t layout, void* host_table, size_t nbytes, int32_t* out_H0,
+                             int32_t* out_W0, int64_t* out_byte_offsets, int64_t* out_scratch_bytes);
+/* dev_files: the device copy of the bytes the plan parsed (any byte address; never written).  host_table: the bytes the plan wrote;
+ * dev_table: their device copy (16-byte aligned), trusted to hold the same bytes, as a frame table's copy is.  rgb 1: R, G, B as
+ * PIL gives them; 0: B, G, R as cv2.imread / cap.read() do.  dev_out (>= out_byte_offsets[n] bytes, out_bytes its size): every
+ * byte of each frame is written and no other (not the gaps of layout 0).  dev_info i32 [n,4] = {status: 0 or VTI_JPEG_CORRUPT,
+ * segments, rounds of the entropy stage used, blocks decoded}.  A damaged scan (an invalid code, data that ends early, a missing or
+ * misnumbered RSTn, bytes left over) terminates, stays inside its buffers and sets the file's status; its pixels are unspecified
+ * but lie inside its own frame, and the other files of the batch are unaffected.  dev_scratch: >= *out_scratch_bytes, 256-byte
+ * aligned.  Every argument check (VTI_ERR_ARG), the table revalidated row by row included, runs before the first HIP call; ctx,
+ * device and weights rules as vti_encode_jpeg (no weights needed).  Five launches on `stream` (zero, entropy, DC, IDCT, colour), no
+ * memset, no host synchronisation.  The entropy stage decodes the scan in segments of segment_bytes, one workgroup per file, with
+ * the self-synchronising scheme (every lane starts from a guessed state and is re-run from its predecessor's exit state until no
+ * state changes, at most as many rounds as there are segments), so it waits on no other workgroup and has no unbounded loop. */
+enum { VTI_JPEG_CORRUPT = 1 };
+int32_t vti_decode_jpeg(vti_ctx* ctx, const uint8_t* dev_files, const void* host_table, const void* dev_table, int32_t n, int32_t rgb,
+                        uint8_t* dev_out, int64_t out_bytes, int32_t* dev_info, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- per-layer access for parity tests ------------------------------------------- */
 /* Copies the activation written by conv `i` of the last vti_forward into dev_out as
  * f32 NCHW [B,c2,h_out,w_out] (test hook; not on the hot path). */

@@ -44,6 +44,8 @@ VTI_MEASURE_MAX_DET = 1000
 VTI_POLY_LARGEST, VTI_POLY_CONCAT = 0, 1
 VTI_POLY_OK, VTI_POLY_ERR_BOUND, VTI_POLY_ERR_RANGE = 0, 1, 2
 VTI_ANNOTATE_OUTLINE_SKIPPED = 1
+VTI_JPEG_CORRUPT = 1
+VTI_ERR_ARG, VTI_ERR_UNSUPPORTED = -1, -6
 
 
 class VtiError(RuntimeError):
@@ -113,6 +115,9 @@ SIGNATURES = {
     "vti_encode_jpeg_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_encode_jpeg_max_bytes": (_I64, [_I32, _I32, _I32]),
     "vti_encode_jpeg": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
+    "vti_decode_jpeg_table_bytes": (_I64, [_I32]),
+    "vti_decode_jpeg_plan": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
+    "vti_decode_jpeg": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),
     "vti_debug_conv2d": (_I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32,
                                 _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,

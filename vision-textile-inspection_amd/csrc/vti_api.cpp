@@ -1094,6 +1094,96 @@ int32_t vti_encode_jpeg(vti_ctx* c, const uint8_t* frames, int32_t n, int32_t H0
     return VTI_OK;
 }
 
+int64_t vti_decode_jpeg_table_bytes(int32_t n) {
+    return n < 1 || n > kJpegDecMaxFiles ? 0 : (int64_t)sizeof(JpegDecHeader) + (int64_t)n * (int64_t)sizeof(JpegDecRow);
+}
+
+int32_t vti_decode_jpeg_plan(vti_ctx* c, const uint8_t* files, const int64_t* file_offsets, int32_t n, int32_t segment_bytes,
+                             int32_t layout, void* host_table, size_t nbytes, int32_t* out_H0, int32_t* out_W0, int64_t* out_byte_offsets,
+                             int64_t* out_scratch_bytes) {
+    auto bad = [&](const std::string& what) { return fail(c, VTI_ERR_ARG, what); };
+    if (n < 1 || n > kJpegDecMaxFiles) return bad("vti_decode_jpeg_plan: 1 <= n <= 4096");
+    if (!files || !file_offsets || !host_table || !out_H0 || !out_W0 || !out_byte_offsets || !out_scratch_bytes)
+        return bad("vti_decode_jpeg_plan: null pointer");
+    if (layout != 0 && layout != 1) return bad("vti_decode_jpeg_plan: layout 0 (frames at multiples of 16 bytes) or 1 (dense)");
+    if (segment_bytes == 0) segment_bytes = kJpegDecDefaultSegment;
+    if (segment_bytes < 16 || segment_bytes > 4096 || (segment_bytes & (segment_bytes - 1)))
+        return bad("vti_decode_jpeg_plan: segment_bytes must be 0 or a power of two from 16 to 4096");
+    if ((int64_t)nbytes < vti_decode_jpeg_table_bytes(n)) return bad("vti_decode_jpeg_plan: table smaller than vti_decode_jpeg_table_bytes()");
+    if (file_offsets[0] < 0) return bad("vti_decode_jpeg_plan: host_file_offsets[0] < 0");
+    for (int32_t k = 0; k < n; ++k)
+        if (file_offsets[k + 1] < file_offsets[k]) return bad("vti_decode_jpeg_plan: host_file_offsets must ascend (file " + std::to_string(k) + ")");
+    JpegDecHeader H;
+    memset(&H, 0, sizeof H);
+    H.magic = kJpegDecMagic;
+    H.n = n;
+    H.layout = layout;
+    H.seg_bytes = segment_bytes;
+    H.files_bytes = file_offsets[n];
+    std::vector<JpegDecRow> rows((size_t)n);
+    size_t scratch_at = 0;
+    long long out_at = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        JpegDecRow& R = rows[(size_t)k];
+        std::string why;
+        const int rc = decode_jpeg_parse(files + file_offsets[k], file_offsets[k + 1] - file_offsets[k], R, why);
+        if (rc) return fail(c, rc, "vti_decode_jpeg_plan: file " + std::to_string(k) + ": " + why);
+        if (layout == 1 && (R.H0 != rows[0].H0 || R.W0 != rows[0].W0))
+            return bad("vti_decode_jpeg_plan: file " + std::to_string(k) + ": layout 1 (dense) needs files of one size");
+        R.file_off = file_offsets[k];
+        R.scan_start += R.file_off;
+        R.scan_end += R.file_off;
+        R.seg_bytes = segment_bytes;
+        R.nseg = (int)std::max<long long>(1, (R.scan_end - R.scan_start + segment_bytes - 1) / segment_bytes);
+        scratch_at = decode_jpeg_scratch_of(R, scratch_at);
+        R.out_off = out_at;
+        out_H0[k] = R.H0;
+        out_W0[k] = R.W0;
+        out_byte_offsets[k] = out_at;
+        out_at += 3LL * R.H0 * R.W0;
+        if (layout == 0) out_at = (out_at + 15) & ~15LL;
+    }
+    if (layout == 0) out_at = std::max<long long>(out_at, 16);
+    out_byte_offsets[n] = out_at;
+    H.out_bytes = out_at;
+    H.scratch_bytes = (long long)scratch_at;
+    *out_scratch_bytes = H.scratch_bytes;
+    memcpy(host_table, &H, sizeof H);
+    memcpy((uint8_t*)host_table + sizeof H, rows.data(), (size_t)n * sizeof(JpegDecRow));
+    return VTI_OK;
+}
+
+int32_t vti_decode_jpeg(vti_ctx* c, const uint8_t* files, const void* host_table, const void* dev_table, int32_t n, int32_t rgb,
+                        uint8_t* out, int64_t out_bytes, int32_t* info, void* scratch, size_t scratch_bytes, void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const std::string& what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_decode_jpeg: null ctx");
+    if (n < 1 || n > kJpegDecMaxFiles) return bad("vti_decode_jpeg: 1 <= n <= 4096");
+    if (rgb != 0 && rgb != 1) return bad("vti_decode_jpeg: rgb 0 or 1");
+    if (!files || !host_table || !dev_table || !out || !info) return bad("vti_decode_jpeg: null pointer");
+    if (((uintptr_t)dev_table & 15) || ((uintptr_t)info & 3)) return bad("vti_decode_jpeg: dev_table must be 16-byte aligned, dev_info 4-byte aligned");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_decode_jpeg: scratch must be a 256-byte aligned device pointer");
+    JpegDecHeader H;
+    memcpy(&H, host_table, sizeof H);
+    if (H.magic != kJpegDecMagic || H.n != n || (H.layout != 0 && H.layout != 1) || H.files_bytes < 0 || H.out_bytes < 0 || H.scratch_bytes < 0)
+        return bad("vti_decode_jpeg: host_table is not a descriptor table of vti_decode_jpeg_plan for n files");
+    if (out_bytes < H.out_bytes) return bad("vti_decode_jpeg: dev_out smaller than out_byte_offsets[n]");
+    if ((int64_t)scratch_bytes < H.scratch_bytes) return bad("vti_decode_jpeg: scratch smaller than the plan's scratch_bytes");
+    size_t scratch_at = 0;
+    long long out_at = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        JpegDecRow R;
+        memcpy(&R, (const uint8_t*)host_table + sizeof H + (size_t)k * sizeof R, sizeof R);
+        std::string why;
+        if (!decode_jpeg_row_ok(R, H, scratch_at, why) || R.out_off < out_at)
+            return bad("vti_decode_jpeg: row " + std::to_string(k) + " of the table is invalid (" + (why.empty() ? "frames overlap" : why) + ")");
+        out_at = R.out_off + 3LL * R.H0 * R.W0;
+    }
+    if (int32_t drc = check_device(c, "vti_decode_jpeg")) return drc;
+    VTI_HIP(c, launch_decode_jpeg(files, host_table, dev_table, n, rgb, out, info, scratch, (hipStream_t)stream), "decode_jpeg kernels");
+    return VTI_OK;
+}
+
 int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void* stream) {
     int32_t rc = check_ready(c, B, "vti_debug_conv_output");
     if (rc) return rc;

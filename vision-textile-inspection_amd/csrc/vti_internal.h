@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vti.h"
+#include "jpeg_decode_dev.h"
 
 namespace vti {
 
@@ -364,6 +365,18 @@ bool encode_jpeg_layout(long long n, int H0, int W0, JpegLayout& L);
 void encode_jpeg_header(int H0, int W0, int quality, uint8_t out[624]);      // SOI .. SOS: 623 bytes and one of padding
 hipError_t launch_encode_jpeg(const uint8_t* frames, int n, int H0, int W0, int rgb, int quality, void* scratch, long long* offsets,
                               uint8_t* out, long long max_bytes, hipStream_t st);
+
+// jpeg_decode.hip: vti_decode_jpeg (JPEG files -> frames).  The host parses every header; a descriptor table is a JpegDecHeader
+// followed by one JpegDecRow per file.  The scratch holds per file, each part rounded up to 256 bytes: the segment states (entry u64 |
+// exit u64 | (markers, blocks) u32 x 2 | their scan u32 x 2, 32 bytes per segment), the coefficients i16 [blocks, 64] and the Y, Cb, Cr
+// planes u8 (64 bytes per block).
+// host: one file's header -> R (offsets relative to the file; layout fields zero); 0, VTI_ERR_ARG or VTI_ERR_UNSUPPORTED with the reason
+int decode_jpeg_parse(const uint8_t* d, long long n, JpegDecRow& R, std::string& err);
+size_t decode_jpeg_scratch_of(JpegDecRow& R, size_t at);      // sets R's scratch offsets from `at` on (needs nseg, nblk); -> the end
+// host: every value of a row a kernel forms an address from, against the header's sizes; scratch_at runs along the rows
+bool decode_jpeg_row_ok(const JpegDecRow& R, const JpegDecHeader& H, size_t& scratch_at, std::string& why);
+hipError_t launch_decode_jpeg(const uint8_t* files, const void* host_table, const void* dev_table, int n, int rgb, uint8_t* out, int* info,
+                              void* scratch, hipStream_t st);
 
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
 void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,

@@ -598,6 +598,83 @@ class Engine:
             out = launch(total)
         return out, offsets
 
+    # ---- JPEG files -> frames (cap.read() of a motion-JPEG camera, cv2.imread): vti_decode_jpeg ------------------------------
+    def decode_jpeg_plan(self, files, dense=None, segment_bytes=0, stage=None):
+        """Host only: parses and validates the files (vti_decode_jpeg_plan; a VtiError names the first refused file and why) ->
+        dict(n, table_bytes, files_at, used, shapes, byte_offsets, out_bytes, scratch_bytes, dense, stage): `stage` is a u8 host
+        tensor that holds the descriptor table at 0 and the concatenated files at files_at (a multiple of 256)."""
+        files = list(files)
+        n = len(files)
+        if n < 1:
+            raise ValueError("decode_jpeg: at least one file")
+        for k, f in enumerate(files):
+            if not isinstance(f, (bytes, bytearray, memoryview)):
+                raise ValueError(f"decode_jpeg: file {k} must be bytes, got {type(f).__name__}")
+        tb = int(lib().vti_decode_jpeg_table_bytes(n))
+        if tb <= 0:
+            raise ValueError(f"decode_jpeg: 1 <= n <= 4096 files, got {n}")
+        files_at = (tb + 255) & ~255
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum([len(f) for f in files], out=offs[1:])
+        used = files_at + int(offs[n])
+        if stage is None or stage.numel() < used:
+            stage = torch.empty(max(used, 1 << 16), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        flat = stage.numpy()
+        for k, f in enumerate(files):
+            flat[files_at + offs[k]:files_at + offs[k + 1]] = np.frombuffer(f, np.uint8)
+        H0, W0 = (C.c_int32 * n)(), (C.c_int32 * n)()
+        out_off, scratch = (C.c_int64 * (n + 1))(), C.c_int64(0)
+
+        def plan(layout):
+            check(self._ctx, lib().vti_decode_jpeg_plan(self._ctx, C.c_void_p(stage.data_ptr() + files_at), C.c_void_p(offs.ctypes.data), n,
+                                                        int(segment_bytes), layout, C.c_void_p(stage.data_ptr()), tb, H0, W0, out_off,
+                                                        C.byref(scratch)))
+        plan(1 if dense else 0)
+        shapes = [(int(h), int(w)) for h, w in zip(H0, W0)]
+        if dense is None:
+            dense = all(x == shapes[0] for x in shapes)
+            if dense:
+                plan(1)
+        return dict(n=n, table_bytes=tb, files_at=files_at, used=used, shapes=shapes, byte_offsets=[int(v) for v in out_off[:n]],
+                    out_bytes=int(out_off[n]), scratch_bytes=int(scratch.value), dense=bool(dense), stage=stage)
+
+    def decode_jpeg(self, files, rgb=True, dense=None, segment_bytes=0, device=None):
+        """JPEG files (a list of bytes) -> frames on the device, byte for byte jpeg.decode(file, rgb): vti_decode_jpeg.  One pinned
+        staging copy and one asynchronous H2D of the descriptor table and the concatenated files; nothing is read back.
+        dense (None: when all files have one size) -> (frames u8 [n,H0,W0,3], info); otherwise -> (buf u8 flat, shapes [(H0, W0)],
+        byte_offsets, info) with the frames laid out as pack_frames lays them, so `buf` is a frame-table buffer.  info i32 [n,4] =
+        {status (0 or VTI_JPEG_CORRUPT), segments, rounds, blocks}.  The staging buffer, its device twin and the scratch are kept and
+        grown; a refused file raises before anything is launched."""
+        st = getattr(self, "_jd", None) or {}
+        ev = st.get("event")
+        if ev is not None:
+            ev.synchronize()                # the staging buffer is free once the previous copy has left it
+        p = self.decode_jpeg_plan(files, dense, segment_bytes, st.get("stage"))
+        if not torch.cuda.is_available():
+            raise ValueError("decode_jpeg: needs a ROCm device (no CPU fallback; jpeg.decode is the host specification)")
+        dev = torch.device(device) if device is not None else (self.device or torch.device("cuda", torch.cuda.current_device()))
+        if st.get("dev") is None or st["dev"].numel() < p["used"] or st["dev"].device != dev:
+            st["dev"] = torch.empty(p["stage"].numel(), dtype=torch.uint8, device=dev)
+        if st.get("ws") is None or st["ws"].numel() < p["scratch_bytes"] or st["ws"].device != dev:
+            st["ws"] = None
+            st["ws"] = torch.empty(max(p["scratch_bytes"], 256), dtype=torch.uint8, device=dev)
+        st["stage"] = p["stage"]
+        dbuf, ws = st["dev"], st["ws"]
+        dbuf[:p["used"]].copy_(p["stage"][:p["used"]], non_blocking=True)
+        st["event"] = torch.cuda.Event()
+        st["event"].record()
+        self._jd = st
+        n = p["n"]
+        out = torch.empty(p["out_bytes"], dtype=torch.uint8, device=dev)
+        info = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        check(self._ctx, lib().vti_decode_jpeg(self._ctx, C.c_void_p(dbuf.data_ptr() + p["files_at"]), C.c_void_p(p["stage"].data_ptr()),
+                                               _ptr(dbuf), n, int(bool(rgb)), _ptr(out), out.numel(), _ptr(info), _ptr(ws), ws.numel(),
+                                               _stream()))
+        if p["dense"]:
+            h, w = p["shapes"][0]
+            return out.view(n, h, w, 3), info
+        return out, p["shapes"], p["byte_offsets"], info
+
     # ---- Results.masks.xy: instance polygons in frame pixels (vti_mask_polygons) -------------------------------------------
     def mask_polygons_scratch_bytes(self, H, W, row_bytes):
         return int(lib().vti_mask_polygons_scratch_bytes(self._ctx, int(H), int(W), int(row_bytes)))

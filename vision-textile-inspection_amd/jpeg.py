@@ -198,10 +198,12 @@ def _bit_length(a):
     return n
 
 
-def _emissions(coef, is_chroma):
-    """The scan as (table index 0..3 = dc0, ac0, dc1, ac1; symbol; extra-bit value; extra-bit count), in stream order."""
+def _emissions(coef, is_chroma, comp=None):
+    """The scan as (table index 0..3 = dc0, ac0, dc1, ac1; symbol; extra-bit value; extra-bit count), in stream order.  comp: the
+    component of every block (the 4:2:0 MCU's 0 0 0 0 1 2 unless given)."""
     nb = coef.shape[0]
-    comp = np.tile(np.array([0, 0, 0, 0, 1, 2]), nb // 6)
+    if comp is None:
+        comp = np.tile(np.array([0, 0, 0, 0, 1, 2]), nb // 6)
     dc = coef[:, 0]
     diff = dc.copy()
     for c in range(3):
@@ -248,7 +250,11 @@ def symbol_counts(frame, quality=95, rgb=False):
 
 def scan_bytes(frame, quality=95, rgb=False, stuffed=True):
     """The entropy-coded data: MSB first, the last byte padded with 1-bits, 0x00 after every 0xFF (rules 8-9)."""
-    tab, sym, ext, nex = _emissions(*scan_blocks(frame, quality, rgb))
+    return _emission_bytes(*_emissions(*scan_blocks(frame, quality, rgb)), stuffed=stuffed)
+
+
+def _emission_bytes(tab, sym, ext, nex, stuffed=True):
+    """_emissions' stream coded with the Annex K tables -> bytes."""
     code, size = np.zeros((4, 256), np.int64), np.zeros((4, 256), np.int64)
     for k, name in enumerate(("dc0", "ac0", "dc1", "ac1")):
         code[k], size[k] = huffman_codes(HUFFMAN[name])
@@ -273,3 +279,413 @@ def encode(frame, quality=95, rgb=False):
     """The JPEG file of a uint8 [H0,W0,3] frame (BGR as cv2's frames are, RGB with rgb=True) -> bytes."""
     H0, W0 = np.asarray(frame).shape[:2]
     return header(H0, W0, quality) + scan_bytes(frame, quality, rgb) + b"\xff\xd9"
+
+
+# ---- decoding: the host SPECIFICATION of vti_decode_jpeg (csrc/jpeg_decode.hip, Engine.decode_jpeg) -------------------------------
+# What cv2.imread / cap.read() of a motion-JPEG camera / PIL.Image.open do with libjpeg's defaults: jdhuff.c, jidctint.c (JDCT_ISLOW),
+# jdsample.c fancy upsampling, jdcolor.c.  PINNED against Pillow (libjpeg-turbo) by tests/test_jpeg_decode.py, every pixel; identity
+# with cv2.imread is expected (same library, same defaults) but OpenCV is not available here, so it is UNPINNED.
+MAX_DECODE_SIDE = 8192
+
+
+class UnsupportedJpeg(ValueError):
+    """A well-formed file outside the supported class (the device call answers VTI_ERR_UNSUPPORTED)."""
+
+
+def _derive_huffman(bits, vals):
+    """jpeg_make_d_derived_tbl: -> (look uint16 [512] = length << 8 | symbol for codes of <= 9 bits, 0 otherwise; maxcode int [18];
+    valoffset int [18]; huffval uint8 [256])."""
+    if sum(bits) > 256 or sum(bits) != len(vals) or not vals:
+        raise ValueError("bad Huffman table")
+    look = np.zeros(512, np.uint16)
+    maxcode = np.full(18, -1, np.int64)
+    valoff = np.zeros(18, np.int64)
+    code, k = 0, 0
+    for length in range(1, 17):
+        if bits[length - 1]:
+            valoff[length] = k - code
+            for _ in range(bits[length - 1]):
+                if code >= 1 << length:
+                    raise ValueError("bad Huffman table")
+                if length <= 9:
+                    look[code << (9 - length):(code + 1) << (9 - length)] = (length << 8) | vals[k]
+                code, k = code + 1, k + 1
+            maxcode[length] = code - 1
+        code <<= 1
+    maxcode[17] = 0xFFFFF
+    hv = np.zeros(256, np.uint8)
+    hv[:len(vals)] = vals
+    return look, maxcode, valoff, hv
+
+
+def parse(data):
+    """The header of a supported file -> dict(H0, W0, hs, vs (luma sampling), quant int64 [3, 64] zigzag order per component,
+    dc / ac: per component (bits, values), restart_interval, scan_start, scan_end (byte range of the entropy-coded data),
+    mcu_rows, mcu_cols, blocks_per_mcu, n_blocks).  Raises UnsupportedJpeg for the refused classes, ValueError for malformed headers."""
+    d = bytes(data)
+    n = len(d)
+    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
+        raise ValueError("not a JPEG file: no SOI marker")
+    qt, dc_t, ac_t = {}, {}, {}
+    sof = None
+    ri = 0
+    jfif, adobe = False, None
+    p = 2
+    while True:
+        if p >= n:
+            raise ValueError("truncated header: no SOS marker")
+        if d[p] != 0xFF:
+            raise ValueError(f"malformed header: byte {d[p]:#x} at {p} where a marker was expected")
+        while p < n and d[p] == 0xFF:        # fill bytes
+            p += 1
+        if p >= n:
+            raise ValueError("truncated header")
+        m = d[p]
+        p += 1
+        if m == 0xD8 or 0xD0 <= m <= 0xD7 or m == 0x01:
+            continue
+        if m == 0xD9:
+            raise ValueError("EOI before any scan")
+        if p + 2 > n:
+            raise ValueError("truncated header")
+        L = (d[p] << 8) | d[p + 1]
+        if L < 2 or p + L > n:
+            raise ValueError("truncated header: a segment runs past the end of the file")
+        body = d[p + 2:p + L]
+        if m == 0xC0:
+            if sof is not None:
+                raise ValueError("two SOF markers")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError("bad SOF0 length")
+            sof = body
+        elif m in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7):
+            raise UnsupportedJpeg({0xC2: "progressive", 0xC1: "extended sequential"}.get(m, "lossless or differential")
+                                  + " JPEG: only baseline sequential (SOF0) is decoded")
+        elif m in (0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF, 0xCC):
+            raise UnsupportedJpeg("arithmetic coding is not decoded")
+        elif m == 0xDB:
+            q = 0
+            while q < len(body):
+                pq, tq = body[q] >> 4, body[q] & 15
+                if pq == 1:
+                    raise UnsupportedJpeg("16-bit quantisation table")
+                if pq or tq > 3 or q + 65 > len(body):
+                    raise ValueError("bad DQT segment")
+                qt[tq] = np.frombuffer(body[q + 1:q + 65], np.uint8).astype(np.int64)
+                q += 65
+        elif m == 0xC4:
+            q = 0
+            while q < len(body):
+                if q + 17 > len(body):
+                    raise ValueError("bad DHT segment")
+                tc, th = body[q] >> 4, body[q] & 15
+                bits = list(body[q + 1:q + 17])
+                cnt = sum(bits)
+                if tc > 1 or th > 3 or cnt > 256 or q + 17 + cnt > len(body):
+                    raise ValueError("bad DHT segment")
+                vals = list(body[q + 17:q + 17 + cnt])
+                _derive_huffman(bits, vals)
+                (ac_t if tc else dc_t)[th] = (bits, vals)
+                q += 17 + cnt
+        elif m == 0xDD:
+            if len(body) != 2:
+                raise ValueError("bad DRI segment")
+            ri = (body[0] << 8) | body[1]
+        elif m == 0xE0 and body[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDA:
+            break
+        p += L
+    if sof is None:
+        raise ValueError("SOS before SOF")
+    prec, H0, W0, nc = sof[0], (sof[1] << 8) | sof[2], (sof[3] << 8) | sof[4], sof[5]
+    if prec != 8:
+        raise UnsupportedJpeg(f"{prec}-bit samples: only 8-bit is decoded")
+    if nc == 1:
+        raise UnsupportedJpeg("greyscale file: only three-component YCbCr is decoded")
+    if nc != 3:
+        raise UnsupportedJpeg(f"{nc} components: only three-component YCbCr is decoded")
+    if not (1 <= H0 <= MAX_DECODE_SIDE and 1 <= W0 <= MAX_DECODE_SIDE):
+        raise UnsupportedJpeg(f"frame size {H0}x{W0} outside 1..{MAX_DECODE_SIDE}")
+    comps = [(sof[6 + 3 * i], sof[7 + 3 * i] >> 4, sof[7 + 3 * i] & 15, sof[8 + 3 * i]) for i in range(3)]
+    if adobe is not None and adobe != 1:
+        raise UnsupportedJpeg(f"Adobe transform {adobe}: only YCbCr (transform 1) is decoded")
+    if adobe is None and not jfif and [c[0] for c in comps] == [82, 71, 66]:
+        raise UnsupportedJpeg("RGB components: only YCbCr is decoded")
+    hs, vs = comps[0][1], comps[0][2]
+    if (hs, vs) not in ((2, 2), (2, 1), (1, 1)) or any(c[1] != 1 or c[2] != 1 for c in comps[1:]):
+        raise UnsupportedJpeg("sampling factors " + ",".join(f"{c[1]}x{c[2]}" for c in comps)
+                              + ": only 2x2, 2x1 or 1x1 luma with 1x1 chroma is decoded")
+    if len(body) < 1 or len(body) != 4 + 2 * body[0]:
+        raise ValueError("bad SOS length")
+    if body[0] != 3:
+        raise UnsupportedJpeg("a scan that does not interleave all three components (multiple scans)")
+    sel = []
+    for i in range(3):
+        if body[1 + 2 * i] != comps[i][0]:
+            raise UnsupportedJpeg("scan components out of frame order")
+        sel.append((body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15))
+    if body[7] != 0 or body[8] != 63 or body[9] != 0:
+        raise UnsupportedJpeg("spectral selection or successive approximation in a sequential scan")
+    default_dc = {0: DC0, 1: DC1}
+    default_ac = {0: AC0, 1: AC1}
+    if not dc_t and not ac_t:                      # motion-JPEG: no DHT, the Annex K tables
+        dc_t, ac_t = default_dc, default_ac
+    quant, dcs, acs = [], [], []
+    for i in range(3):
+        if comps[i][3] not in qt:
+            raise ValueError(f"component {i} uses quantisation table {comps[i][3]}, which the file does not define")
+        if sel[i][0] not in dc_t or sel[i][1] not in ac_t:
+            raise ValueError(f"component {i} uses a Huffman table the file does not define")
+        quant.append(qt[comps[i][3]])
+        dcs.append(dc_t[sel[i][0]])
+        acs.append(ac_t[sel[i][1]])
+    scan_start = p + L
+    q = scan_start
+    while True:                                    # the scan ends at the first marker that is not RSTn (or at the end of the file)
+        q = d.find(b"\xff", q)
+        if q < 0 or q + 1 >= n:
+            scan_end = n
+            break
+        if d[q + 1] == 0 or 0xD0 <= d[q + 1] <= 0xD7 or d[q + 1] == 0xFF:
+            q += 1 if d[q + 1] == 0xFF else 2
+            continue
+        scan_end = q
+        break
+    r = scan_end
+    while r + 1 < n:                               # anything but EOI after the scan: another scan or tables for one
+        if d[r] == 0xFF and d[r + 1] == 0xDA:
+            raise UnsupportedJpeg("multiple scans")
+        if d[r] == 0xFF and d[r + 1] == 0xD9:
+            break
+        r += 1
+    mcu_rows, mcu_cols = -(-H0 // (8 * vs)), -(-W0 // (8 * hs))
+    bpm = hs * vs + 2
+    return dict(H0=H0, W0=W0, hs=hs, vs=vs, quant=np.stack(quant), dc=dcs, ac=acs, restart_interval=ri, scan_start=scan_start,
+                scan_end=scan_end, mcu_rows=mcu_rows, mcu_cols=mcu_cols, blocks_per_mcu=bpm, n_blocks=mcu_rows * mcu_cols * bpm)
+
+
+_LOOKUPS = {}
+
+
+def _full_lookup(table):
+    """(bits, values) -> lists [65536]: the code length (0: invalid) and the symbol of every 16-bit window."""
+    key = (tuple(table[0]), tuple(table[1]))
+    if key not in _LOOKUPS:
+        if len(_LOOKUPS) > 64:
+            _LOOKUPS.clear()
+        _LOOKUPS[key] = _build_lookup(table)
+    return _LOOKUPS[key]
+
+
+def _build_lookup(table):
+    bits, vals = table
+    ln, sy = np.zeros(65536, np.int64), np.zeros(65536, np.int64)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            ln[code << (16 - length):(code + 1) << (16 - length)] = length
+            sy[code << (16 - length):(code + 1) << (16 - length)] = vals[k]
+            code, k = code + 1, k + 1
+        code <<= 1
+    return ln.tolist(), sy.tolist()
+
+
+def decode_coefficients(data, hdr=None):
+    """jdhuff.c: -> (coef int64 [n_blocks, 64] in zigzag order with the DC values summed, in scan order; ok bool).  ok is False for
+    a damaged scan (an invalid code, data that ends early, a missing or misnumbered RSTn); the coefficients are then unspecified."""
+    d = bytes(data)
+    h = hdr or parse(d)
+    nblk, bpm, ri = h["n_blocks"], h["blocks_per_mcu"], h["restart_interval"]
+    comp_of = [0] * (bpm - 2) + [1, 2]
+    dct = [_full_lookup(t) for t in h["dc"]]
+    act = [_full_lookup(t) for t in h["ac"]]
+    coef = np.zeros((nblk, 64), np.int64)
+    raw = d[h["scan_start"]:h["scan_end"]]
+    # the restart intervals: split at RSTn, unstuffed, each a list of 32-bit windows by byte
+    parts, nums, s = [], [], 0
+    while True:
+        q = s
+        while True:
+            q = raw.find(b"\xff", q)
+            if q < 0 or q + 1 >= len(raw):
+                q = len(raw)
+                break
+            if 0xD0 <= raw[q + 1] <= 0xD7:
+                break
+            q += 2 if raw[q + 1] == 0 else 1
+        parts.append(raw[s:q].replace(b"\xff\x00", b"\xff"))
+        if q >= len(raw):
+            break
+        nums.append(raw[q + 1] & 7)
+        s = q + 2
+    ok = nums == [i & 7 for i in range(len(nums))]
+    per = ri * bpm if ri else nblk
+    blk = 0
+    for pi, part in enumerate(parts):
+        if blk >= nblk:
+            ok = ok and pi == len(parts)       # data after the last block
+            break
+        if blk != pi * per:
+            ok = False
+            blk = pi * per
+            if blk >= nblk:
+                break
+        a = np.frombuffer(part + b"\0\0\0\0", np.uint8).astype(np.int64)
+        win = ((a[:-3] << 24) | (a[1:-2] << 16) | (a[2:-1] << 8) | a[3:]).tolist()
+        nbits, pos = 8 * len(part), 0
+        pred = [0, 0, 0]
+        end = min(nblk, blk + per)
+        flat = coef.reshape(-1)
+        out = {}
+        while blk < end:
+            c = comp_of[blk % bpm]
+            ln, sy = dct[c]
+            w = (win[pos >> 3] >> (16 - (pos & 7))) & 0xFFFF if (pos >> 3) < len(win) else 0
+            n_ = ln[w]
+            if not n_ or pos + n_ > nbits:
+                ok = False
+                break
+            pos += n_
+            s_ = sy[w] & 15
+            if s_:
+                if pos + s_ > nbits:
+                    ok = False
+                    break
+                v = (win[pos >> 3] >> (32 - s_ - (pos & 7))) & ((1 << s_) - 1)
+                pos += s_
+                if v < 1 << (s_ - 1):
+                    v += 1 - (1 << s_)
+                pred[c] += v
+            base = blk * 64
+            out[base] = pred[c]
+            ln, sy = act[c]
+            k = 1
+            bad = False
+            while k < 64:
+                w = (win[pos >> 3] >> (16 - (pos & 7))) & 0xFFFF if (pos >> 3) < len(win) else 0
+                n_ = ln[w]
+                if not n_ or pos + n_ > nbits:
+                    bad = True
+                    break
+                pos += n_
+                rs = sy[w]
+                s_ = rs & 15
+                if s_:
+                    k += rs >> 4
+                    if pos + s_ > nbits:
+                        bad = True
+                        break
+                    v = (win[pos >> 3] >> (32 - s_ - (pos & 7))) & ((1 << s_) - 1)
+                    pos += s_
+                    if k > 63:
+                        bad = True
+                        break
+                    if v < 1 << (s_ - 1):
+                        v += 1 - (1 << s_)
+                    out[base + k] = v
+                    k += 1
+                elif rs == 0xF0:
+                    k += 16
+                else:
+                    break
+            if bad:
+                ok = False
+                break
+            blk += 1
+        if out:
+            flat[np.fromiter(out.keys(), np.int64, len(out))] = np.fromiter(out.values(), np.int64, len(out))
+        if blk < end:
+            break
+    if blk < nblk:
+        ok = False
+    return coef, ok
+
+
+def _idct_pass(d, n):
+    """One 1-D pass of jidctint.c along the last axis of d [..., 8], descaled by n bits."""
+    z2, z3 = d[..., 2], d[..., 6]
+    z1 = (z2 + z3) * 4433
+    t2, t3 = z1 - z3 * 15137, z1 + z2 * 6270
+    t0, t1 = (d[..., 0] + d[..., 4]) << 13, (d[..., 0] - d[..., 4]) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = d[..., 7], d[..., 5], d[..., 3], d[..., 1]
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * 9633
+    t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    r = 1 << (n - 1)
+    return np.stack([t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3], -1) + r >> n
+
+
+def idct_blocks(coef, quant):
+    """Dequantisation + jpeg_idct_islow: coef int64 [..., 64] zigzag, quant int64 [64] zigzag -> samples int64 [..., 8, 8] in 0..255."""
+    nat = np.zeros(coef.shape, np.int64)
+    nat[..., ZIGZAG] = coef * quant
+    b = nat.reshape(coef.shape[:-1] + (8, 8))
+    b = _idct_pass(b.swapaxes(-1, -2), 11).swapaxes(-1, -2)       # columns
+    b = _idct_pass(b, 18)                                         # rows
+    v = b & 1023                                                  # the range-limit table behind RANGE_MASK, centred on 128
+    return np.where(v < 128, v + 128, np.where(v < 512, 255, np.where(v < 896, 0, v - 896)))
+
+
+def _upsample_h(P, fancy):
+    """jdsample.c along the rows: [h, cw] -> [h, 2 cw]."""
+    out = np.empty((P.shape[0], 2 * P.shape[1]), np.int64)
+    if not fancy:
+        out[:, 0::2], out[:, 1::2] = P, P
+        return out
+    left, right = np.roll(P, 1, 1), np.roll(P, -1, 1)
+    out[:, 0::2], out[:, 1::2] = (3 * P + left + 1) >> 2, (3 * P + right + 2) >> 2
+    out[:, 0], out[:, -1] = P[:, 0], P[:, -1]
+    return out
+
+
+def upsample(P, hs, vs):
+    """A chroma plane of the real downsampled size [ceil(H0/vs), ceil(W0/hs)] -> [vs * ., hs * .]: fancy upsampling when the plane
+    is more than two samples wide (jinit_upsampler), sample replication otherwise."""
+    if hs == 1:
+        return P
+    fancy = P.shape[1] > 2
+    if vs == 1:
+        return _upsample_h(P, fancy)
+    if not fancy:
+        return np.repeat(_upsample_h(P, False), 2, 0)
+    up, down = np.vstack((P[:1], P[:-1])), np.vstack((P[1:], P[-1:]))
+    out = np.empty((2 * P.shape[0], 2 * P.shape[1]), np.int64)
+    for k, other in enumerate((up, down)):
+        s = 3 * P + other
+        left, right = np.roll(s, 1, 1), np.roll(s, -1, 1)
+        even, odd = (3 * s + left + 8) >> 4, (3 * s + right + 7) >> 4
+        even[:, 0], odd[:, -1] = (4 * s[:, 0] + 8) >> 4, (4 * s[:, -1] + 7) >> 4
+        out[k::2, 0::2], out[k::2, 1::2] = even, odd
+    return out
+
+
+def pixels_from_coefficients(coef, hdr, rgb=True):
+    """IDCT, upsampling and colour conversion of decode_coefficients' blocks -> uint8 [H0, W0, 3]."""
+    H0, W0, hs, vs = hdr["H0"], hdr["W0"], hdr["hs"], hdr["vs"]
+    mr, mc, bpm = hdr["mcu_rows"], hdr["mcu_cols"], hdr["blocks_per_mcu"]
+    c = coef.reshape(mr, mc, bpm, 64)
+    Y = idct_blocks(c[:, :, :hs * vs], hdr["quant"][0]).reshape(mr, mc, vs, hs, 8, 8).transpose(0, 2, 4, 1, 3, 5)
+    Y = Y.reshape(mr * vs * 8, mc * hs * 8)[:H0, :W0]
+    ch, cw = -(-H0 // vs), -(-W0 // hs)
+    chroma = []
+    for k in (1, 2):
+        P = idct_blocks(c[:, :, hs * vs + k - 1], hdr["quant"][k]).transpose(0, 2, 1, 3).reshape(mr * 8, mc * 8)[:ch, :cw]
+        chroma.append(upsample(P, hs, vs)[:H0, :W0] - 128)
+    cb, cr = chroma
+    R = Y + ((_fix(1.40200) * cr + 32768) >> 16)
+    G = Y + ((-_fix(0.34414) * cb - _fix(0.71414) * cr + 32768) >> 16)
+    B = Y + ((_fix(1.77200) * cb + 32768) >> 16)
+    return np.clip(np.stack((R, G, B) if rgb else (B, G, R), -1), 0, 255).astype(np.uint8)
+
+
+def decode(data, rgb=True):
+    """A supported JPEG file -> uint8 [H0, W0, 3], RGB as PIL.Image.open gives it (rgb=False: BGR, as cv2.imread / cap.read())."""
+    hdr = parse(data)
+    coef, _ = decode_coefficients(data, hdr)
+    return pixels_from_coefficients(coef, hdr, rgb)

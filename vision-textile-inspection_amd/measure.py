@@ -135,6 +135,10 @@ class _DeviceStage:
                 raise ValueError("process_frames: encode needs annotate (the frames to encode are the annotated selection)")
             if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, (int, np.integer)) or not 1 <= jpeg_quality <= 100:
                 raise ValueError(f"process_frames: jpeg_quality must be an integer in 1..100, got {jpeg_quality!r}")
+        files = self.model._jpeg_files(frames)
+        info = None
+        if files is not None:       # the batch cap.read() would have delivered: the files decoded to BGR on the device
+            frames, info = self.model._decode_jpeg(files, rgb=False)
         shapes = self.model._differing_shapes(frames)
         table = None
         if shapes is not None:
@@ -148,6 +152,7 @@ class _DeviceStage:
         else:
             eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks,
                                                                  keep_frames=annotate is not None)
+        self.model._raise_if_corrupt(info)
         sel = None
         if annotate is not None:
             sel = np.arange(B) if isinstance(annotate, str) and annotate == "all" else np.asarray(annotate)
@@ -229,7 +234,9 @@ class StitchMeasurer(_DeviceStage):
 
     def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None, encode=None,
                        jpeg_quality=95):
-        """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them.  The reference predicts on the RGB conversion
+        """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them, or a list of JPEG files (bytes) as a
+        motion-JPEG camera delivers them: they are decoded on the device to the BGR batch cap.read() would have returned.
+        The reference predicts on the RGB conversion
         with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
         Returns one record per frame, in frame order, with the smoothing applied frame by frame.
         annotate: "all" or a sequence of frame indices -> (annotated, records): annotated = [(frame index, BGR ndarray H0 x W0 x 3 with

@@ -124,6 +124,13 @@ class Results:
         return len(self.boxes)
 
 
+class DecodedFrames:
+    """Frames of differing sizes that Engine.decode_jpeg left on the device: `buf` is a frame-table buffer (pack_frames' layout)."""
+
+    def __init__(self, buf, shapes, byte_offsets):
+        self.buf, self.shapes, self.byte_offsets = buf, shapes, byte_offsets
+
+
 class YOLO:
     """`YOLO(path)` takes a VTIW1 container; `YOLO(None, scale=, nc=, seed=)` makes seeded random weights."""
 
@@ -186,9 +193,54 @@ class YOLO:
         return t.to(dev, non_blocking=True).contiguous()
 
     @staticmethod
+    def _jpeg_files(source):
+        """The files' bytes when `source` is JPEG data (bytes), a path to a JPEG file (str / os.PathLike), or a list / tuple of
+        these, as Ultralytics' file sources are; None for array sources."""
+        is_file = lambda s: isinstance(s, (bytes, bytearray, memoryview, str, os.PathLike))
+        if is_file(source):
+            source = [source]
+        elif not (isinstance(source, (list, tuple)) and len(source) and any(is_file(s) for s in source)):
+            return None
+        files = []
+        for k, s in enumerate(source):
+            if not is_file(s):
+                raise ValueError(f"a list source is either all frames or all JPEG files (bytes or paths); item {k} is {type(s).__name__}")
+            if isinstance(s, (str, os.PathLike)):
+                with open(s, "rb") as f:
+                    s = f.read()
+            files.append(bytes(s))
+        return files
+
+    def _decode_jpeg(self, files, rgb):
+        """JPEG files -> (a device batch u8 [n,H0,W0,3], or DecodedFrames when the sizes differ; info i32 [n,4] on the device).
+        A refused file raises here, before anything is launched."""
+        dec = getattr(self, "_decoder", None)
+        if dec is None:             # vti_decode_jpeg needs a context but no weights: the smallest plan serves every size
+            dec = self._decoder = Engine(self.scale, self.nc, self._nm, self._reg_max, 32, 32, 1, self.dtype)
+        dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
+        if dev.type == "cuda" and torch.cuda.is_available():
+            torch.cuda.set_device(dev)
+        got = dec.decode_jpeg(files, rgb=rgb, device=dev)
+        if len(got) == 2:
+            return got
+        return DecodedFrames(got[0], got[1], got[2]), got[3]
+
+    @staticmethod
+    def _raise_if_corrupt(info):
+        """After the call: one read of the decoder's status words; a damaged scan is an error that names its file."""
+        if info is None:
+            return
+        bad = torch.nonzero(info[:, 0]).flatten().cpu().tolist()
+        if bad:
+            raise ValueError(f"JPEG file {bad[0]} is damaged (its scan holds an invalid code, ends early or misses a restart marker)"
+                             + (f"; so are files {bad[1:]}" if len(bad) > 1 else ""))
+
+    @staticmethod
     def _differing_shapes(source):
         """[(H0, W0)] when `source` is a list / tuple of frames whose shapes are not all equal (Ultralytics then letterboxes every
         frame onto one imgsz canvas, LetterBox(auto=False)); None for everything that keeps the stacked path."""
+        if isinstance(source, DecodedFrames):
+            return list(source.shapes)
         if not isinstance(source, (list, tuple)) or len(source) < 2:
             return None
         shapes = [tuple(s.shape) if hasattr(s, "shape") else np.shape(s) for s in source]
@@ -216,13 +268,16 @@ class YOLO:
             ent = self._frame_tables[key] = (table, torch.empty(total, dtype=torch.uint8, pin_memory=True),
                                              torch.empty(total, dtype=torch.uint8, device=dev))
         table, stage, buf = ent
-        flat = stage.numpy()
-        for f, (h, w), off in zip(source, shapes, table.byte_offsets):
-            a = f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
-            if a.dtype != np.uint8:
-                raise ValueError(f"every frame of a list source must be uint8 HxWx3, got {a.dtype}")
-            flat[off:off + 3 * h * w] = a.reshape(-1)
-        buf.copy_(stage, non_blocking=True)
+        if isinstance(source, DecodedFrames):       # already on the device, in this very layout (vti_decode_jpeg, layout 0)
+            buf = source.buf
+        else:
+            flat = stage.numpy()
+            for f, (h, w), off in zip(source, shapes, table.byte_offsets):
+                a = f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+                if a.dtype != np.uint8:
+                    raise ValueError(f"every frame of a list source must be uint8 HxWx3, got {a.dtype}")
+                flat[off:off + 3 * h * w] = a.reshape(-1)
+            buf.copy_(stage, non_blocking=True)
         okey = (id(eng), B, max_det, None)
         o = self._outs.get(okey)
         if o is None:
@@ -265,7 +320,15 @@ class YOLO:
         process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes.
         A list / tuple of frames whose shapes differ is one batch too (vti_predict_frames): as Ultralytics does for such a list,
         every frame is letterboxed by its own gain onto one stride-rounded imgsz canvas (LetterBox(auto=False)); boxes and
-        masks.xy come back in each frame's own pixels, masks.data at the canvas size.  retina_masks is a ValueError there."""
+        masks.xy come back in each frame's own pixels, masks.data at the canvas size.  retina_masks is a ValueError there.
+        JPEG sources -- bytes, a path (str / os.PathLike) or a list / tuple of these -- are decoded on the device
+        (Engine.decode_jpeg); as with Ultralytics' file sources the network sees the file's R, G, B, so swap_rb does not apply to
+        them.  orig_shape comes from the file's header; a refused file raises before any launch, a damaged one after the call."""
+        files = self._jpeg_files(source)
+        info = None
+        if files is not None:
+            source, info = self._decode_jpeg(files, rgb=True)
+            swap_rb = False
         shapes = self._differing_shapes(source)
         if shapes is not None:
             if retina_masks:
@@ -276,6 +339,7 @@ class YOLO:
         else:
             eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
             shapes = [(H0, W0)] * B
+        self._raise_if_corrupt(info)
         dets, xyxy, masks = o["dets"], o["xyxy"], o["masks"]
         nonempty = None
         if self.drop_empty_masks and not retina_masks:     # m00 of every live slot straight from the bit-packed masks (vti_mask_stats_bits)
