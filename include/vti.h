@@ -409,7 +409,7 @@ int32_t vti_mask_polygons(vti_ctx* ctx, const uint8_t* dev_masks_bits, int32_t n
  * max_points vertices or the tracer reached its bound -- that frame is drawn without its outline, everything else stands.
  * dev_scratch: >= vti_annotate_scratch_bytes(), 256-byte aligned.  Every argument check (VTI_ERR_ARG) runs before the first HIP call.
  * Three launches on `stream` (display list + union, outline, raster); no host synchronisation.  Frames of differing sizes (a frame
- * table) are not supported. */
+ * table): vti_annotate_frames below. */
 enum { VTI_ANNOTATE_OUTLINE_SKIPPED = 1 };
 /* Host only: bytes of device scratch vti_annotate needs (0 on a bad argument); it grows with n_sel and with max_points. */
 int64_t vti_annotate_scratch_bytes(const vti_ctx* ctx, int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points);
@@ -419,6 +419,33 @@ int32_t vti_annotate(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t
                      int32_t max_det, int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
                      const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points, uint8_t* dev_out,
                      int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
+/* vti_annotate for a batch whose frames differ in size.  dev_frames / host_table / dev_table: the flat frame buffer and the frame table
+ * of vti_predict_frames / vti_measure_frames (frame b: u8 [H0[b], W0[b], 3] BGR at byte_offset[b]); masks, dets, xyxy, counts, offsets:
+ * as vti_measure_frames took them; frame_i32, stitch_f64, stitch_i32: what it wrote.  The OUTPUT is described by a second frame table,
+ * the out table: n_sel rows packed with vti_pack_frames for the same canvas, row k with the H0, W0 of input row select[k] (otherwise
+ * VTI_ERR_ARG, and vti_last_error names k); its byte offsets place picture k in dev_out and its total_bytes is the size of dev_out, so
+ * one table type describes every ragged frame buffer of the library and (dev_out, out table) feeds vti_encode_jpeg_frames and
+ * vti_predict_frames directly.  Every byte of each output picture is written and no other: not the gaps between pictures, not the
+ * bytes past the last one; dev_frames is never written.  Picture k is byte for byte what vti_annotate writes for that frame when
+ * called with H0[b], W0[b] on the same inputs; status, VTI_ANNOTATE_OUTLINE_SKIPPED, the plain copy of a frame with a bad camera,
+ * duplicates and any order of the selection are vti_annotate's.  native = 1 is VTI_ERR_UNSUPPORTED (frames of differing sizes have
+ * letterbox bit masks only); a SELECTED frame above 8192 in either dimension is VTI_ERR_ARG naming the frame (the table allows 16384,
+ * the raster's fixed point does not).  dev_frames and dev_out 16-byte aligned.  Every argument check -- both tables revalidated row by
+ * row and the selection included -- runs before the first HIP call; the device copies (tables, selection) are trusted as the other
+ * *_frames calls trust theirs.  The scratch regions are pitched by the largest selected frame; what lies in a region beyond a frame's
+ * own extent is never read.  Three launches on `stream`, or four when the selection holds both frames whose union fits the tracer's
+ * LDS image (H0 * ceil(W0 / 64) * 8 <= 156 KiB) and frames whose union does not: the outline kernel then runs in both forms, each on
+ * its own frames.
+ * Host only: scratch bytes for the pictures the out table describes (0 on a bad argument) = vti_annotate_scratch_bytes(n_sel, max_det,
+ * largest H0, largest W0 of its rows, max_points). */
+int64_t vti_annotate_frames_scratch_bytes(const vti_ctx* ctx, const void* host_out_table, int32_t max_det, int32_t max_points);
+int32_t vti_annotate_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t B,
+                            const void* dev_cameras, int32_t n_cams, const int32_t* dev_camera_of_frame, const uint8_t* dev_masks,
+                            int32_t native, const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                            const int32_t* dev_offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                            const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
+                            int32_t n_sel, int32_t max_points, const void* host_out_table, const void* dev_out_table, uint8_t* dev_out,
+                            int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the saved JPEG on device (cv2.imwrite(save_path, annotated): main.py:314, measurement.py:536) -------------------------------- */
 /* n frames u8 [n,H0,W0,3] (BGR as cv2's frames are; rgb = 1: RGB) -> n JPEG files, byte for byte the package's jpeg.py: libjpeg's
@@ -445,6 +472,24 @@ int64_t vti_encode_jpeg_max_bytes(int32_t n, int32_t H0, int32_t W0);
 int32_t vti_encode_jpeg(vti_ctx* ctx, const uint8_t* dev_frames, int32_t n, int32_t H0, int32_t W0, int32_t rgb, int32_t quality,
                         void* dev_scratch, size_t scratch_bytes, int64_t* dev_byte_offsets, uint8_t* dev_out, int64_t max_bytes,
                         void* stream);
+/* vti_encode_jpeg for n frames of differing sizes: frame k is u8 [H0[k], W0[k], 3] at byte_offset[k] of dev_frames (16-byte aligned
+ * offsets: a frame table's buffer, e.g. vti_annotate_frames' dev_out with its out table, or vti_decode_jpeg's layout 0).  File k is
+ * byte for byte vti_encode_jpeg(n = 1, H0[k], W0[k]) of that frame -- its SOF0 carries its own height and width -- and the files lie
+ * back to back and unpadded at offsets[k] .. offsets[k+1]; dev_byte_offsets i64 [n+1] is always exact, dev_out is written only when
+ * offsets[n] <= max_bytes.  Per frame 1 <= H0, W0 <= 8192, and at most 2^28 MCUs in the batch.  Every argument check -- the table
+ * revalidated for this ctx's canvas and exactly n frames included -- runs before the first HIP call.  Ten launches on `stream`:
+ * vti_encode_jpeg's nine behind a prefix launch that builds, from the device table into the scratch, the exclusive scans of the frames'
+ * MCU and stream-chunk counts (blocks: 6 per MCU); the kernels find the frame of an MCU, block or chunk by binary search over those
+ * n + 1 entries, which ends inside [0, n) whatever they hold.  DC prediction restarts at each frame's first block.
+ * Host only: the scratch is laid out per frame, not pitched by the largest one: 1024 + 2 * 8 (n + 1) for the prefixes + 16 n + 768 M +
+ * 48 M + 4096 C + 4 C, each part rounded up to 256, with M and C the MCUs and 4096-byte chunks of the whole batch -- at most the sum of
+ * vti_encode_jpeg_scratch_bytes(ctx, 1, H0[k], W0[k]) plus the prefixes.  0 on a bad argument. */
+int64_t vti_encode_jpeg_frames_scratch_bytes(const vti_ctx* ctx, const void* host_table);
+/* Host only: the sum of vti_encode_jpeg_max_bytes(1, H0[k], W0[k]) over the table's frames (0 on a bad argument). */
+int64_t vti_encode_jpeg_frames_max_bytes(const void* host_table);
+int32_t vti_encode_jpeg_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t n,
+                               int32_t rgb, int32_t quality, void* dev_scratch, size_t scratch_bytes, int64_t* dev_byte_offsets,
+                               uint8_t* dev_out, int64_t max_bytes, void* stream);
 
 /* ---- JPEG files -> frames on device (cap.read() of a motion-JPEG camera, cv2.imread, Ultralytics' file sources) ----------------- */
 /* n files -> n frames u8 [H0,W0,3], byte for byte the package's jpeg.decode, which is pinned to libjpeg-turbo's output with its

@@ -2,7 +2,10 @@
 1280 x 960, timed with device events after warm-up, next to two yardsticks measured in the same run: a device-to-device copy of the
 same frames (the floor: the call must at least read them), and what the encode is for, the device-to-host copy of the raw frames
 (what process_frames(annotate=...) reads back) against that of the JPEG bytes (what encode="jpeg" reads back), wall clock.
-    python3 tools/jpeg_bench.py [--n 1 8 64] [--quality 95] [--content smooth noise] [--rounds 5]
+    python3 tools/jpeg_bench.py [--n 1 8 64] [--quality 95] [--content smooth noise] [--rounds 5] [--size 960 1280] [--mixed]
+--size: the frame size of the uniform batch.  --mixed: vti_encode_jpeg_frames instead (ten launches), on a batch of n frames that
+cycles the four sizes of the tests (481 x 333, 720 x 960, 960 x 1280, 1080 x 1920; n = 64: 16 frames each) in one flat buffer with
+its frame table.  What it replaces is one uniform call per size (--size h w --n 16).
 `smooth` is low-pass noise with a little sensor noise on top (the bytes per pixel of a camera frame, roughly); `noise` is the worst
 case for the entropy stages.  (encode, copy) are interleaved in groups of 10 calls, `--rounds` groups each, and the whole
 measurement runs twice."""
@@ -51,15 +54,52 @@ def make_frames(content, n, h, w):
     return np.clip(np.rint(f), 0, 255).astype(np.uint8)
 
 
+MIXED_SIZES = [(481, 333), (720, 960), (960, 1280), (1080, 1920)]       # tests/test_gpu_annotate_frames.py
+
+
+def mixed(a, eng):
+    for content in a.content:
+        for n in a.n:
+            shapes = [MIXED_SIZES[k % 4] for k in range(n)]
+            table, offs, total_in = eng.pack_frames(shapes, "cuda")
+            flat = np.zeros(total_in, np.uint8)
+            per_size = {hw: make_frames(content, -(-n // 4), *hw) for hw in set(shapes)}
+            for k, ((h, w), at) in enumerate(zip(shapes, offs)):
+                flat[at:at + 3 * h * w] = per_size[(h, w)][k // 4].reshape(-1)
+            frames = torch.from_numpy(flat).cuda()
+            floor = torch.empty_like(frames)
+            enc = lambda: eng.encode_jpeg(frames, quality=a.quality, table=table)
+            cpy = lambda: floor.copy_(frames)
+            for _ in range(3):
+                out, off = enc()
+                cpy()
+            total, px = int(off[n]), sum(h * w for h, w in shapes)
+            scratch = vti_amd.lib().vti_encode_jpeg_frames_scratch_bytes(eng._ctx, table.host.data_ptr())
+            print(f"mixed {content} n {n:3d} q {a.quality}: {total} JPEG bytes = {total / px:.3f} B/px ({3 * px / total:.1f}x below the raw "
+                  f"{3 * px} bytes), scratch {scratch / 1e6:.1f} MB")
+            for run in range(2):
+                te, tc = [], []
+                for _ in range(a.rounds):
+                    te.append(group_ms(enc))
+                    tc.append(group_ms(cpy))
+                me, mc = float(np.median(te)) * 1e3, float(np.median(tc)) * 1e3
+                print(f"  run {run}: encode_frames {me:9.1f} us/call (min {min(te) * 1e3:.1f}), {me / n:8.1f} us/frame, d2d copy {mc:8.1f} us, "
+                      f"ratio {me / mc:6.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1, 8, 64])
     ap.add_argument("--quality", type=int, default=95)
     ap.add_argument("--content", nargs="+", default=["smooth", "noise"])
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--size", type=int, nargs=2, default=[960, 1280], metavar=("H0", "W0"))
+    ap.add_argument("--mixed", action="store_true")
     a = ap.parse_args()
-    h, w = 960, 1280
+    h, w = a.size
     eng = vti_amd.Engine("n", 2, H=64, W=64, max_batch=1)        # the encoder needs a context, not a model
+    if a.mixed:
+        return mixed(a, eng)
     for content in a.content:
         host = make_frames(content, max(a.n), h, w)
         for n in a.n:

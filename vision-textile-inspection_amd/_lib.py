@@ -112,9 +112,15 @@ SIGNATURES = {
     "vti_annotate_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
     "vti_annotate": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32,
                             _I32, _P, _P, _P, _SZ, _P]),
+    "vti_annotate_frames_scratch_bytes": (_I64, [_P, _P, _I32, _I32]),
+    "vti_annotate_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32,
+                                   _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "vti_encode_jpeg_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_encode_jpeg_max_bytes": (_I64, [_I32, _I32, _I32]),
     "vti_encode_jpeg": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
+    "vti_encode_jpeg_frames_scratch_bytes": (_I64, [_P, _P]),
+    "vti_encode_jpeg_frames_max_bytes": (_I64, [_P]),
+    "vti_encode_jpeg_frames": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
     "vti_decode_jpeg_table_bytes": (_I64, [_I32]),
     "vti_decode_jpeg_plan": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     "vti_decode_jpeg": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),

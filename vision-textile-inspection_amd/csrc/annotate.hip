@@ -17,6 +17,13 @@
 //      covers it (atomicMax of record index << 3 | colour: painter's order without ordering the work), a thread per record, envelope
 //      segment or outline edge paints the rows of its primitive that fall into the tile from the closed forms of annotate_dev.h, and
 //      the tile is then copied from the frame with the covered pixels replaced (16 pixels = three 16-byte vectors per thread).
+//
+// vti_annotate_frames (frames of differing sizes) runs the same kernels: with frame tables in AnnArgs a workgroup takes H0, W0, the
+// words per union row and the frame's place in dev_frames / dev_out from the table rows of its frame instead of the launch arguments.
+// The scratch regions are then PITCHED by the largest selected frame (a frame uses the head of its slice, laid out for its own size;
+// what lies beyond is never read), the outline is launched in both instantiations when the selection needs both (each leaves the
+// frames of the other alone, by the frame's own size), and the raster grid is the largest frame's: workgroups past a frame's last
+// tile leave before the first barrier.
 #include <climits>
 #include <cstring>
 
@@ -46,7 +53,8 @@ enum { META_N_ENV = 0, META_N_CONT = 1, META_OUTLINE = 2, META_INTS = 16 };
 
 struct AnnArgs {
     const uint8_t* frames; uint8_t* out; int* status_out;
-    const int* select; int B, n_sel, H0, W0, WW;
+    const int* select; int B, n_sel, H0, W0, WW;               // with frame tables: the largest selected H0, W0 and their WW (pitches)
+    const FrameRow* rows_in; const FrameRow* rows_out;          // device frame tables of dev_frames (B rows) and dev_out (n_sel rows), or null
     const CameraRow* table; const int* cam_of_frame; int n_cams;
     const uint8_t* masks; const float* dets; const float* xyxy; const int* counts; const int* offsets;
     int max_det, row, capacity, H, W;
@@ -57,6 +65,13 @@ struct AnnArgs {
 };
 
 __device__ __forceinline__ int nrec(int max_det) { return 3 + 7 * max_det; }
+// H0, W0 and the 64-bit words per union row of frame b: the launch arguments, or row b of the frame table (never above the pitches)
+struct Geo { int H0, W0, WW; };
+__device__ __forceinline__ Geo frame_geo(const AnnArgs& a, int b) {
+    if (!a.rows_in) return Geo{a.H0, a.W0, a.WW};
+    const int H0 = min(max(a.rows_in[b].H0, 1), a.H0), W0 = min(max(a.rows_in[b].W0, 1), a.W0);
+    return Geo{H0, W0, (W0 + 63) >> 6};
+}
 // coordinates far outside any frame change nothing that is drawn; the clamp keeps the fixed-point arithmetic in range
 __device__ __forceinline__ int clampc(int v) { return min(max(v, -32768), 32767); }
 __device__ __forceinline__ int round_px(double v) { return (int)rint(fmin(fmax(v, -32768.0), 32767.0)); }   // python round(): half to even
@@ -66,8 +81,10 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
     extern __shared__ int s_env[];              // [W0]: the nearest-resize column table, then the envelope
     __shared__ int s_fab[VTI_MEASURE_MAX_DET][3];
     __shared__ int s_nfab, s_w[kThreads / 64];
-    const int tid = threadIdx.x, k = blockIdx.x, M = a.max_det, H0 = a.H0, W0 = a.W0, WW = a.WW;
+    const int tid = threadIdx.x, k = blockIdx.x, M = a.max_det;
     const int b = min(max(a.select[k], 0), a.B - 1);
+    const Geo geo = frame_geo(a, b);
+    const int H0 = geo.H0, W0 = geo.W0, WW = geo.WW;
     Rec* recs = a.recs + (size_t)k * nrec(M);
     int* meta = a.meta + (size_t)k * META_INTS;
     for (int i = tid; i < nrec(M); i += kThreads) recs[i] = Rec{K_NOP, 0, 0, 0, 0, 0, 0, 0};
@@ -137,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
     if (status == VTI_MEASURE_NO_FABRIC) return;        // 3. the reference returns here (measurement.py:280-287)
     __syncthreads();
     // 4a. the union of the kept fabric masks at the frame size: u64 [H0, WW], bits at columns >= W0 clear
-    u64* uni = a.uni + (size_t)k * H0 * WW;
+    u64* uni = a.uni + (size_t)k * a.H0 * a.WW;
     const double ify = 1.0 / ((double)H0 / (double)a.H), ifx = 1.0 / ((double)W0 / (double)a.W);
     if (!NATIVE) {
         for (int x = tid; x < W0; x += kThreads) s_env[x] = nn_src(x, ifx, a.W);
@@ -199,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
     }
     if (nv > 0) {
         const int step = max(1, nv / 1000);
-        int2* pts = a.env_pts + (size_t)k * W0;
+        int2* pts = a.env_pts + (size_t)k * a.W0;
         int carry = 0;
         for (int x0 = 0; x0 < W0; x0 += kThreads) {
             const int x = x0 + tid;
@@ -253,14 +270,18 @@ __global__ __launch_bounds__(kThreads) void annotate_outline_kernel(AnnArgs a) {
     extern __shared__ u64 s_img[];
     __shared__ int s_w[kThreads / 64];
     __shared__ int s_bad, s_total;
-    const int tid = threadIdx.x, k = blockIdx.x, H = a.H0, W = a.W0, WW = a.WW, M = a.max_det;
+    const int tid = threadIdx.x, k = blockIdx.x, M = a.max_det;
+    const Geo geo = frame_geo(a, min(max(a.select[k], 0), a.B - 1));
+    const int H = geo.H0, W = geo.W0, WW = geo.WW;
     const int* meta = a.meta + (size_t)k * META_INTS;
     if (!meta[META_OUTLINE]) return;            // uniform: only a frame with status OK draws its outline
+    // frames of differing sizes: the instantiation that suits THIS frame's union traces it (annotate_layout's rule), the other leaves
+    if (a.rows_in && ((size_t)H * WW * 8 <= (size_t)poly::kLdsBytes) != IN_LDS) return;
     unsigned char* area = a.areas + (size_t)k * a.area_bytes;
     int* const parent_g = (int*)area;
     unsigned* runs = (unsigned*)(area + a.off_runs);
     int* row_start = (int*)(area + a.off_rows);
-    const u64* uni = a.uni + (size_t)k * H * WW;
+    const u64* uni = a.uni + (size_t)k * a.H0 * a.WW;
     const u64* img = uni;
     if (tid == 0) { s_bad = 0; s_total = 0; }
     if (IN_LDS) {
@@ -323,14 +344,17 @@ struct TilePaint {
 
 __global__ __launch_bounds__(kThreads) void annotate_raster_kernel(AnnArgs a) {
     extern __shared__ unsigned s_prio[];        // [kTile]
-    const int tid = threadIdx.x, k = blockIdx.y, M = a.max_det, H0 = a.H0, W0 = a.W0;
+    const int tid = threadIdx.x, k = blockIdx.y, M = a.max_det;
     const int b = min(max(a.select[k], 0), a.B - 1);
+    const Geo geo = frame_geo(a, b);
+    const int H0 = geo.H0, W0 = geo.W0;
     const int npx = H0 * W0, p0 = blockIdx.x * kTile, p1 = min(p0 + kTile, npx);
+    if (p0 >= npx) return;                      // the grid is the largest frame's: past this frame's last tile (the whole workgroup)
     for (int i = tid; i < kTile; i += kThreads) s_prio[i] = 0;
     __syncthreads();
     const Rec* recs = a.recs + (size_t)k * nrec(M);
     const int* meta = a.meta + (size_t)k * META_INTS;
-    const int2* env = a.env_pts + (size_t)k * W0;
+    const int2* env = a.env_pts + (size_t)k * a.W0;
     const int2* cont = a.cont + (size_t)k * a.max_points;
     const int n_env = min(max(meta[META_N_ENV], 0), W0), n_cont = min(max(meta[META_N_CONT], 0), a.max_points);
     const int n_fixed = nrec(M), n_seg = max(n_env - 1, 0), total = n_fixed + n_seg + n_cont;
@@ -375,8 +399,8 @@ __global__ __launch_bounds__(kThreads) void annotate_raster_kernel(AnnArgs a) {
     }
     __syncthreads();
     // the tile of the frame with the covered pixels replaced
-    const uint8_t* src = a.frames + (size_t)b * npx * 3 + (size_t)p0 * 3;
-    uint8_t* dst = a.out + (size_t)k * npx * 3 + (size_t)p0 * 3;
+    const uint8_t* src = a.frames + (a.rows_in ? (size_t)a.rows_in[b].offset : (size_t)b * npx * 3) + (size_t)p0 * 3;
+    uint8_t* dst = a.out + (a.rows_out ? (size_t)a.rows_out[k].offset : (size_t)k * npx * 3) + (size_t)p0 * 3;
     const int np = p1 - p0;
     int done = 0;
     if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {        // 16 pixels = 48 bytes = three 16-byte vectors per thread
@@ -438,7 +462,7 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
                            const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
                            const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
                            const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
-                           int* status, void* scratch, hipStream_t st) {
+                           int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr) {
     AnnotateLayout L;
     annotate_layout(n_sel, max_det, H0, W0, max_points, L);
     unsigned char* ws = (unsigned char*)scratch;
@@ -449,6 +473,7 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
     a.table = (const CameraRow*)cameras; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams;
     a.masks = masks; a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
     a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H = native ? H0 : H; a.W = native ? W0 : W;
+    if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; }
     a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
     a.max_points = max_points;
     a.recs = (Rec*)(ws + L.off_recs); a.meta = (int*)(ws + L.off_meta); a.env_pts = (int2*)(ws + L.off_env);
@@ -459,10 +484,15 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
     else hipLaunchKernelGGL(annotate_prep_kernel<false>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = L.in_lds ? launch_lds<annotate_outline_kernel<true>>(dim3(n_sel), dim3(kThreads), (size_t)poly::kLdsBytes, st, a)
-                 : launch_lds<annotate_outline_kernel<false>>(dim3(n_sel), dim3(kThreads), 0, st, a);
-    if (e != hipSuccess) return e;
-    const int tiles = (int)(((long long)H0 * W0 + kTile - 1) / kTile);
+    if (fr ? fr->any_lds : L.in_lds) {
+        e = launch_lds<annotate_outline_kernel<true>>(dim3(n_sel), dim3(kThreads), (size_t)poly::kLdsBytes, st, a);
+        if (e != hipSuccess) return e;
+    }
+    if (fr ? fr->any_global : !L.in_lds) {
+        e = launch_lds<annotate_outline_kernel<false>>(dim3(n_sel), dim3(kThreads), 0, st, a);
+        if (e != hipSuccess) return e;
+    }
+    const int tiles = (int)(((fr ? fr->max_px : (long long)H0 * W0) + kTile - 1) / kTile);
     hipLaunchKernelGGL(annotate_raster_kernel, dim3(tiles, n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
     return hipGetLastError();
 }

@@ -14,12 +14,21 @@
 //   8 offsets    the exclusive scan of the n file sizes -> dev_byte_offsets; the header bytes -> scratch
 //   9 write      per chunk: header (chunk 0), the bytes with 0x00 after every 0xFF, EOI (last chunk); nothing when
 //                dev_byte_offsets[n] > max_bytes
+//
+// vti_encode_jpeg_frames (frames of differing sizes, a frame table) runs the same nine kernels in their RAGGED instantiation behind
+// one more launch (0 prefix): the exclusive scans of the frames' MCU counts and of their stream chunk counts, built from the device
+// table into the scratch.  MCUs, blocks (6 per MCU) and chunks are numbered through the whole batch, so the scratch arrays are the
+// uniform call's with every frame's part as long as that frame needs; a wave finds the frame of its MCU, block or chunk by binary
+// search over the n + 1 prefix entries (it ends inside [0, n) whatever they hold) and takes H0, W0 and the frame's place from its row.
+#include <cstring>
+
 #include "vti_internal.h"
 
 namespace vti {
 namespace {
 
 constexpr int kHeaderBytes = 623;
+constexpr int kSofDims = 163;                 // SOI 2 + APP0 18 + DQT 2 x 69 + FF C0, length, precision: height and width, two bytes each
 constexpr int kMaxBlockBits = 1658;          // DC 9 + 11; 63 AC coefficients of 16 + 10
 constexpr int kChunkWords = 1024;            // the stuffing passes work on 4096-byte chunks of the unstuffed stream
 constexpr int kScanThreads = 1024;
@@ -132,6 +141,36 @@ __device__ inline void fdct_pass(int* d, int s) {
     d[s] = (u7 + z1 + z4 + r) >> n;
 }
 
+// Where the frames are.  Uniform (rows == nullptr): n frames of H0 x W0 back to back, mr x mc MCUs and NC chunks each.  Ragged: frame k
+// is row k of the device frame table; pm / pc [n + 1] are the exclusive scans of the frames' MCU and chunk counts (prefix kernel).
+struct JpegGeo {
+    const FrameRow* rows; const long long* pm; const long long* pc;
+    int n, H0, W0, mr, mc;
+    long long NC;
+};
+
+// the last k in [0, n) with pre[k] <= v (pre[0] = 0): always inside [0, n), whatever the array holds
+__device__ inline int find_frame(const long long* __restrict__ pre, int n, long long v) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (pre[mid] <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__host__ __device__ inline long long chunks_of_mcus(long long mcus) {      // the chunks that hold a frame's longest unstuffed stream
+    const long long bytes = (mcus * 6 * kMaxBlockBits + 7) / 8;
+    return (bytes + 4 * kChunkWords - 1) / (4 * kChunkWords);
+}
+
+// chunk `c` of the batch -> its frame and its index in that frame's stream
+template <bool RAGGED>
+__device__ inline void chunk_frame(const JpegGeo& g, long long c, long long& k, long long& t) {
+    if (RAGGED) { k = find_frame(g.pc, g.n, c); t = c - g.pc[k]; }
+    else { k = c / g.NC; t = c - k * g.NC; }
+}
+
 struct Ycc { int y, cb, cr; };
 __device__ inline Ycc load_ycc(const uint8_t* f, int W0, int y, int x, int rgb) {
     const uint8_t* p = f + ((size_t)y * W0 + x) * 3;
@@ -147,17 +186,30 @@ __device__ inline Ycc load_ycc(const uint8_t* f, int W0, int y, int x, int rgb) 
 // 1: one wave per MCU, four MCUs per workgroup.  Lane l owns the 2 x 2 cell (l >> 3, l & 7) of the MCU: four luma samples and one
 // sample of each chroma plane.  The tile is 6 blocks of 8 rows pitched by 9 ints, so the row pass (lane = block * 8 + row, address
 // 9 * lane + k) and the column pass (address 72 * block + column + 9 * k) both touch distinct banks.
-__global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restrict__ frames, long long n_mcu_all, int H0, int W0, int rgb,
-                                                          int mr, int mc, int scale, int16_t* __restrict__ coef) {
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restrict__ frames, long long n_mcu_all, JpegGeo g, int rgb,
+                                                          int scale, int16_t* __restrict__ coef) {
     __shared__ int s_tile[4][6 * 72];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     long long m = (long long)blockIdx.x * 4 + wid;
     const bool live = m < n_mcu_all;
     if (!live) m = n_mcu_all - 1;                   // the wave still runs (workgroup barriers below); it stores nothing
-    const int per = mr * mc;
-    const long long k = m / per;
-    const int r = (int)(m - k * per), my = r / mc, mx = r - my * mc;
-    const uint8_t* f = frames + (size_t)k * H0 * W0 * 3;
+    // the four MCUs of a workgroup can belong to different frames: the lookup is per wave (and every wave reaches every barrier)
+    int H0 = g.H0, W0 = g.W0, mc = g.mc, r;
+    const uint8_t* f;
+    if (RAGGED) {
+        const int k = find_frame(g.pm, g.n, m);
+        const FrameRow& row = g.rows[k];
+        H0 = row.H0; W0 = row.W0; mc = (W0 + 15) >> 4;
+        r = (int)(m - g.pm[k]);
+        f = frames + row.offset;
+    } else {
+        const int per = g.mr * mc;
+        const long long k = m / per;
+        r = (int)(m - k * per);
+        f = frames + (size_t)k * H0 * W0 * 3;
+    }
+    const int my = r / mc, mx = r - my * mc;
     int* tile = s_tile[wid];
     const int cyl = lane >> 3, cxl = lane & 7;
     const int gy = my * 8 + cyl, gx = mx * 8 + cxl;                 // the cell = the chroma sample, in the chroma plane
@@ -241,16 +293,23 @@ __device__ inline void emit_bits(unsigned* buf, unsigned v, int len, int q) {
 // 2 and 5: one wave per block of the scan, lane i = zigzag coefficient i.  WRITE = false: bitpos[block] = its bit count.
 // WRITE = true: bitpos holds the exclusive scan; the block's bits go to the frame's stream (big-endian 32-bit words: bit p of the
 // stream is bit 31 - p % 32 of word p / 32), which the zero kernel cleared.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void jpeg_entropy_kernel(const int16_t* __restrict__ coef, long long n_blk_all, long long nblk,
-                                                           unsigned long long* __restrict__ bitpos, unsigned* __restrict__ stream,
-                                                           long long SW) {
+template <bool WRITE, bool RAGGED>
+__global__ __launch_bounds__(256) void jpeg_entropy_kernel(const int16_t* __restrict__ coef, long long n_blk_all, JpegGeo g,
+                                                           unsigned long long* __restrict__ bitpos, unsigned* __restrict__ stream) {
     __shared__ unsigned s_buf[4][56];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     long long gb = (long long)blockIdx.x * 4 + wid;
     const bool live = gb < n_blk_all;
     if (!live) gb = n_blk_all - 1;
-    const long long k = gb / nblk, j = gb - k * nblk, mcu = j / 6;
+    long long k, j, nblk, first_word;                // the frame, the block's index in it, its blocks, its stream's first word
+    if (RAGGED) {
+        k = find_frame(g.pm, g.n, gb / 6);
+        j = gb - 6 * g.pm[k]; nblk = 6 * (g.pm[k + 1] - g.pm[k]); first_word = g.pc[k] * kChunkWords;
+    } else {
+        nblk = (long long)g.mr * g.mc * 6;
+        k = gb / nblk; j = gb - k * nblk; first_word = k * g.NC * kChunkWords;
+    }
+    const long long mcu = j / 6;
     const int b = (int)(j - mcu * 6), chroma = b >= 4;
     const int16_t* cf = coef + (size_t)gb * 64;
     int c = cf[lane];
@@ -315,7 +374,7 @@ __global__ __launch_bounds__(256) void jpeg_entropy_kernel(const int16_t* __rest
     const int nwords = (end + 31) >> 5;
     if (live && lane < nwords) {
         const unsigned v = buf[lane];
-        unsigned* dst = stream + (size_t)k * SW + (size_t)(P >> 5) + lane;
+        unsigned* dst = stream + (size_t)first_word + (size_t)(P >> 5) + lane;
         if (lane == 0 || lane == nwords - 1) {      // shared with the neighbouring blocks
             if (v) atomicOr(dst, v);
         } else {
@@ -346,10 +405,31 @@ __device__ inline unsigned long long block_excl_scan(unsigned long long v, unsig
     return pre + x - v;
 }
 
-// 3: frame blockIdx.x: bitpos[frame] -> its exclusive scan, fbits[frame] = the total
-__global__ __launch_bounds__(kScanThreads) void jpeg_bit_scan_kernel(unsigned long long* bitpos, long long nblk, unsigned long long* fbits) {
+// 0 (ragged only): one workgroup: pm, pc [0 .. n] = the exclusive scans of the frames' MCU and chunk counts, from the device table
+__global__ __launch_bounds__(kScanThreads) void jpeg_prefix_kernel(const FrameRow* __restrict__ rows, int n, long long* pm, long long* pc) {
     __shared__ unsigned long long s_w[kScanThreads / 64];
-    unsigned long long* p = bitpos + (size_t)blockIdx.x * nblk;
+    unsigned long long cm = 0, cc = 0;
+    for (int b0 = 0; b0 < n; b0 += kScanThreads) {
+        const int i = b0 + threadIdx.x;
+        unsigned long long mcus = 0, chunks = 0;
+        if (i < n) {
+            mcus = (unsigned long long)((rows[i].H0 + 15) >> 4) * (unsigned long long)((rows[i].W0 + 15) >> 4);
+            chunks = (unsigned long long)chunks_of_mcus((long long)mcus);
+        }
+        unsigned long long tm, tc;
+        const unsigned long long em = block_excl_scan(mcus, s_w, tm), ec = block_excl_scan(chunks, s_w, tc);
+        if (i < n) { pm[i] = (long long)(cm + em); pc[i] = (long long)(cc + ec); }
+        cm += tm; cc += tc;
+    }
+    if (threadIdx.x == 0) { pm[n] = (long long)cm; pc[n] = (long long)cc; }
+}
+
+// 3: frame blockIdx.x: bitpos[frame] -> its exclusive scan, fbits[frame] = the total
+template <bool RAGGED>
+__global__ __launch_bounds__(kScanThreads) void jpeg_bit_scan_kernel(unsigned long long* bitpos, JpegGeo g, unsigned long long* fbits) {
+    __shared__ unsigned long long s_w[kScanThreads / 64];
+    const long long nblk = RAGGED ? 6 * (g.pm[blockIdx.x + 1] - g.pm[blockIdx.x]) : (long long)g.mr * g.mc * 6;
+    unsigned long long* p = bitpos + (RAGGED ? (size_t)(6 * g.pm[blockIdx.x]) : (size_t)blockIdx.x * nblk);
     unsigned long long carry = 0;
     for (long long b0 = 0; b0 < nblk; b0 += kScanThreads) {
         const long long i = b0 + threadIdx.x;
@@ -365,10 +445,12 @@ __global__ __launch_bounds__(kScanThreads) void jpeg_bit_scan_kernel(unsigned lo
 __device__ inline unsigned long long used_bytes(const unsigned long long* fbits, long long k) { return (fbits[k] + 7) >> 3; }
 
 // 4: workgroup (frame, chunk): zero the chunk's words that the frame's stream uses
-__global__ __launch_bounds__(256) void jpeg_zero_kernel(unsigned* stream, const unsigned long long* fbits, long long NC) {
-    const long long k = blockIdx.x / NC, t = blockIdx.x - k * NC;
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void jpeg_zero_kernel(unsigned* stream, const unsigned long long* fbits, JpegGeo g) {
+    long long k, t;
+    chunk_frame<RAGGED>(g, blockIdx.x, k, t);
     const unsigned long long words = (used_bytes(fbits, k) + 3) >> 2;
-    unsigned* s = stream + ((size_t)k * NC + t) * kChunkWords;
+    unsigned* s = stream + (size_t)blockIdx.x * kChunkWords;
     for (int i = threadIdx.x; i < kChunkWords; i += 256)
         if ((unsigned long long)t * kChunkWords + i < words) s[i] = 0;
 }
@@ -378,12 +460,14 @@ __device__ inline int ff_count(unsigned w) {
 }
 
 // 6: one wave per (frame, chunk): 0xFF bytes of the chunk (the unused bytes of the last word are zero)
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void jpeg_count_kernel(const unsigned* __restrict__ stream, const unsigned long long* __restrict__ fbits,
-                                                        long long NC, unsigned* __restrict__ chunk_ff) {
-    const long long k = blockIdx.x / NC, t = blockIdx.x - k * NC;
+                                                        JpegGeo g, unsigned* __restrict__ chunk_ff) {
+    long long k, t;
+    chunk_frame<RAGGED>(g, blockIdx.x, k, t);
     const unsigned long long words = (used_bytes(fbits, k) + 3) >> 2;
     if ((unsigned long long)t * kChunkWords >= words) return;
-    const unsigned* s = stream + ((size_t)k * NC + t) * kChunkWords;
+    const unsigned* s = stream + (size_t)blockIdx.x * kChunkWords;
     int cnt = 0;
     for (int i = threadIdx.x; i < kChunkWords; i += 64)
         if ((unsigned long long)t * kChunkWords + i < words) cnt += ff_count(s[i]);
@@ -393,12 +477,13 @@ __global__ __launch_bounds__(64) void jpeg_count_kernel(const unsigned* __restri
 }
 
 // 7: frame blockIdx.x: the exclusive scan of its used chunks' counts, fsize[frame] = header + bytes + stuffing + EOI
-__global__ __launch_bounds__(kScanThreads) void jpeg_chunk_scan_kernel(unsigned* chunk_ff, const unsigned long long* fbits, long long NC,
+template <bool RAGGED>
+__global__ __launch_bounds__(kScanThreads) void jpeg_chunk_scan_kernel(unsigned* chunk_ff, const unsigned long long* fbits, JpegGeo g,
                                                                        long long* fsize) {
     __shared__ unsigned long long s_w[kScanThreads / 64];
     const unsigned long long bytes = used_bytes(fbits, blockIdx.x);
     const long long used = (long long)((bytes + 4 * kChunkWords - 1) / (4 * kChunkWords));
-    unsigned* p = chunk_ff + (size_t)blockIdx.x * NC;
+    unsigned* p = chunk_ff + (RAGGED ? (size_t)g.pc[blockIdx.x] : (size_t)blockIdx.x * g.NC);
     unsigned long long carry = 0;
     for (long long b0 = 0; b0 < used; b0 += kScanThreads) {
         const long long i = b0 + threadIdx.x;
@@ -430,21 +515,32 @@ __global__ __launch_bounds__(kScanThreads) void jpeg_offsets_kernel(const long l
 
 // 9: one wave per (frame, chunk): the chunk's bytes with 0x00 after every 0xFF at their place in the file; chunk 0 also writes the
 // header, the last used chunk the EOI marker.  Nothing when the n files do not fit in max_bytes.
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void jpeg_write_kernel(const unsigned* __restrict__ stream, const unsigned long long* __restrict__ fbits,
-                                                        long long NC, const unsigned* __restrict__ chunk_ff,
+                                                        JpegGeo g, const unsigned* __restrict__ chunk_ff,
                                                         const long long* __restrict__ offsets, long long n, long long max_bytes,
                                                         const uint8_t* __restrict__ dev_hdr, uint8_t* __restrict__ out) {
     if (offsets[n] > max_bytes) return;
-    const long long k = blockIdx.x / NC, t = blockIdx.x - k * NC;
+    long long k, t;
+    chunk_frame<RAGGED>(g, blockIdx.x, k, t);
     const unsigned long long bytes = used_bytes(fbits, k);
     const unsigned long long start = (unsigned long long)t * (4 * kChunkWords);
     if (start >= bytes) return;
     const int lane = threadIdx.x;
     uint8_t* file = out + offsets[k];
-    if (t == 0)
-        for (int i = lane; i < kHeaderBytes; i += 64) file[i] = dev_hdr[i];
+    if (t == 0) {
+        if (RAGGED) {                               // the header in the scratch is the batch's; SOF0 carries this file's height and width
+            const int H0 = g.rows[k].H0, W0 = g.rows[k].W0;
+            for (int i = lane; i < kHeaderBytes; i += 64) {
+                const int d = i - kSofDims;
+                file[i] = d == 0 ? (uint8_t)(H0 >> 8) : d == 1 ? (uint8_t)H0 : d == 2 ? (uint8_t)(W0 >> 8) : d == 3 ? (uint8_t)W0 : dev_hdr[i];
+            }
+        } else {
+            for (int i = lane; i < kHeaderBytes; i += 64) file[i] = dev_hdr[i];
+        }
+    }
     uint8_t* o = file + kHeaderBytes + start + chunk_ff[blockIdx.x];
-    const unsigned* s = stream + ((size_t)k * NC + t) * kChunkWords;
+    const unsigned* s = stream + (size_t)blockIdx.x * kChunkWords;
     const unsigned long long left = bytes - start;                      // bytes of the stream from this chunk's start on
     long long run = 0;
     for (int i0 = 0; i0 < kChunkWords && (unsigned long long)i0 * 4 < left; i0 += 64) {
@@ -511,37 +607,91 @@ void encode_jpeg_header(int H0, int W0, int quality, uint8_t out[624]) {
     *p++ = 0;                                                           // 623 bytes and one of padding
 }
 
+bool encode_jpeg_frames_layout(const void* host_table, JpegFramesLayout& L) {
+    FrameTableHeader h;
+    memcpy(&h, host_table, sizeof h);
+    if (h.magic != kFrameTableMagic || h.B < 1) return false;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    L.n = h.B; L.n_mcu = 0; L.n_chunk = 0; L.max_bytes = 0;
+    for (int k = 0; k < h.B; ++k) {
+        FrameRow r;
+        memcpy(&r, (const char*)host_table + sizeof h + (size_t)k * sizeof r, sizeof r);
+        JpegLayout one;
+        if (!encode_jpeg_layout(1, r.H0, r.W0, one)) return false;
+        L.n_mcu += (long long)one.mr * one.mc;
+        L.n_chunk += chunks_of_mcus((long long)one.mr * one.mc);
+        L.max_bytes += one.max_file;
+    }
+    if (L.n_mcu > (1LL << 28)) return false;
+    const size_t n = (size_t)h.B;
+    L.off_pm = 1024;                                                    // the header's 624 bytes come first
+    L.off_pc = L.off_pm + al((n + 1) * 8);
+    L.off_fbits = L.off_pc + al((n + 1) * 8);
+    L.off_fsize = L.off_fbits + al(n * 8);
+    L.off_coef = L.off_fsize + al(n * 8);
+    L.off_bitpos = L.off_coef + al((size_t)L.n_mcu * 6 * 128);
+    L.off_stream = L.off_bitpos + al((size_t)L.n_mcu * 6 * 8);
+    L.off_chunk = L.off_stream + al((size_t)L.n_chunk * kChunkWords * 4);
+    L.total = L.off_chunk + al((size_t)L.n_chunk * 4);
+    return true;
+}
+
+namespace {
+
+// the nine launches behind either entry point; g.rows selects the instantiation
+template <bool RAGGED>
+hipError_t encode_launches(const uint8_t* frames, const JpegGeo& g, long long n_mcu, long long n_chunk, int rgb, int quality, uint8_t* ws,
+                           unsigned long long* fbits, long long* fsize, int16_t* coef, unsigned long long* bitpos, unsigned* stream,
+                           unsigned* chunk_ff, long long* offsets, uint8_t* out, long long max_bytes, hipStream_t st) {
+    const long long n_blk = n_mcu * 6;
+    const int n = g.n, scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    JpegHeader hdr;
+    encode_jpeg_header(g.H0, g.W0, quality, hdr.b);
+    const dim3 chunks((unsigned)n_chunk);
+    hipLaunchKernelGGL(jpeg_blocks_kernel<RAGGED>, dim3((unsigned)((n_mcu + 3) / 4)), dim3(256), 0, st, frames, n_mcu, g, rgb, scale, coef);
+    hipLaunchKernelGGL((jpeg_entropy_kernel<false, RAGGED>), dim3((unsigned)((n_blk + 3) / 4)), dim3(256), 0, st, (const int16_t*)coef,
+                       n_blk, g, bitpos, stream);
+    hipLaunchKernelGGL(jpeg_bit_scan_kernel<RAGGED>, dim3(n), dim3(kScanThreads), 0, st, bitpos, g, fbits);
+    hipLaunchKernelGGL(jpeg_zero_kernel<RAGGED>, chunks, dim3(256), 0, st, stream, (const unsigned long long*)fbits, g);
+    hipLaunchKernelGGL((jpeg_entropy_kernel<true, RAGGED>), dim3((unsigned)((n_blk + 3) / 4)), dim3(256), 0, st, (const int16_t*)coef,
+                       n_blk, g, bitpos, stream);
+    hipLaunchKernelGGL(jpeg_count_kernel<RAGGED>, chunks, dim3(64), 0, st, (const unsigned*)stream, (const unsigned long long*)fbits, g,
+                       chunk_ff);
+    hipLaunchKernelGGL(jpeg_chunk_scan_kernel<RAGGED>, dim3(n), dim3(kScanThreads), 0, st, chunk_ff, (const unsigned long long*)fbits, g,
+                       fsize);
+    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(kScanThreads), 0, st, (const long long*)fsize, (long long)n, offsets, hdr, ws);
+    hipLaunchKernelGGL(jpeg_write_kernel<RAGGED>, chunks, dim3(64), 0, st, (const unsigned*)stream, (const unsigned long long*)fbits, g,
+                       (const unsigned*)chunk_ff, (const long long*)offsets, (long long)n, max_bytes, (const uint8_t*)ws, out);
+    return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t launch_encode_jpeg(const uint8_t* frames, int n, int H0, int W0, int rgb, int quality, void* scratch, long long* offsets,
                               uint8_t* out, long long max_bytes, hipStream_t st) {
     JpegLayout L;
     if (!encode_jpeg_layout(n, H0, W0, L)) return hipErrorInvalidValue;
     uint8_t* ws = (uint8_t*)scratch;
-    auto* fbits = (unsigned long long*)(ws + L.off_fbits);
-    auto* fsize = (long long*)(ws + L.off_fsize);
-    auto* coef = (int16_t*)(ws + L.off_coef);
-    auto* bitpos = (unsigned long long*)(ws + L.off_bitpos);
-    auto* stream = (unsigned*)(ws + L.off_stream);
-    auto* chunk_ff = (unsigned*)(ws + L.off_chunk);
-    const long long n_mcu = (long long)n * L.mr * L.mc, n_blk = n_mcu * 6, SW = L.NC * kChunkWords;
-    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-    JpegHeader hdr;
-    encode_jpeg_header(H0, W0, quality, hdr.b);
-    const dim3 chunks((unsigned)(n * L.NC));
-    hipLaunchKernelGGL(jpeg_blocks_kernel, dim3((unsigned)((n_mcu + 3) / 4)), dim3(256), 0, st, frames, n_mcu, H0, W0, rgb, L.mr, L.mc,
-                       scale, coef);
-    hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3((unsigned)((n_blk + 3) / 4)), dim3(256), 0, st, (const int16_t*)coef, n_blk,
-                       L.nblk, bitpos, stream, SW);
-    hipLaunchKernelGGL(jpeg_bit_scan_kernel, dim3(n), dim3(kScanThreads), 0, st, bitpos, L.nblk, fbits);
-    hipLaunchKernelGGL(jpeg_zero_kernel, chunks, dim3(256), 0, st, stream, (const unsigned long long*)fbits, L.NC);
-    hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3((unsigned)((n_blk + 3) / 4)), dim3(256), 0, st, (const int16_t*)coef, n_blk,
-                       L.nblk, bitpos, stream, SW);
-    hipLaunchKernelGGL(jpeg_count_kernel, chunks, dim3(64), 0, st, (const unsigned*)stream, (const unsigned long long*)fbits, L.NC,
-                       chunk_ff);
-    hipLaunchKernelGGL(jpeg_chunk_scan_kernel, dim3(n), dim3(kScanThreads), 0, st, chunk_ff, (const unsigned long long*)fbits, L.NC, fsize);
-    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(kScanThreads), 0, st, (const long long*)fsize, (long long)n, offsets, hdr, ws);
-    hipLaunchKernelGGL(jpeg_write_kernel, chunks, dim3(64), 0, st, (const unsigned*)stream, (const unsigned long long*)fbits, L.NC,
-                       (const unsigned*)chunk_ff, (const long long*)offsets, (long long)n, max_bytes, (const uint8_t*)ws, out);
-    return hipGetLastError();
+    const JpegGeo g{nullptr, nullptr, nullptr, n, H0, W0, L.mr, L.mc, L.NC};
+    return encode_launches<false>(frames, g, (long long)n * L.mr * L.mc, (long long)n * L.NC, rgb, quality, ws,
+                                  (unsigned long long*)(ws + L.off_fbits), (long long*)(ws + L.off_fsize), (int16_t*)(ws + L.off_coef),
+                                  (unsigned long long*)(ws + L.off_bitpos), (unsigned*)(ws + L.off_stream), (unsigned*)(ws + L.off_chunk),
+                                  offsets, out, max_bytes, st);
+}
+
+hipError_t launch_encode_jpeg_frames(const uint8_t* frames, const void* host_table, const FrameRow* rows, int rgb, int quality,
+                                     void* scratch, long long* offsets, uint8_t* out, long long max_bytes, hipStream_t st) {
+    JpegFramesLayout L;
+    if (!encode_jpeg_frames_layout(host_table, L)) return hipErrorInvalidValue;
+    uint8_t* ws = (uint8_t*)scratch;
+    long long* pm = (long long*)(ws + L.off_pm);
+    long long* pc = (long long*)(ws + L.off_pc);
+    hipLaunchKernelGGL(jpeg_prefix_kernel, dim3(1), dim3(kScanThreads), 0, st, rows, L.n, pm, pc);
+    // H0, W0 of the header in the scratch are placeholders: the write kernel patches every file's own
+    const JpegGeo g{rows, pm, pc, L.n, 1, 1, 0, 0, 0};
+    return encode_launches<true>(frames, g, L.n_mcu, L.n_chunk, rgb, quality, ws, (unsigned long long*)(ws + L.off_fbits),
+                                 (long long*)(ws + L.off_fsize), (int16_t*)(ws + L.off_coef), (unsigned long long*)(ws + L.off_bitpos),
+                                 (unsigned*)(ws + L.off_stream), (unsigned*)(ws + L.off_chunk), offsets, out, max_bytes, st);
 }
 
 }  // namespace vti

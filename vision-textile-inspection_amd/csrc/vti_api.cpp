@@ -1062,6 +1062,93 @@ int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, i
     return VTI_OK;
 }
 
+// ---- vti_annotate for frames of differing sizes ----------------------------------------------------------------------------
+// The header of a host frame table and row k of it.
+static FrameTableHeader table_header(const void* host_table) { FrameTableHeader h; memcpy(&h, host_table, sizeof h); return h; }
+static FrameRow table_row(const void* host_table, int32_t k) {
+    FrameRow r;
+    memcpy(&r, (const char*)host_table + sizeof(FrameTableHeader) + (size_t)k * sizeof r, sizeof r);
+    return r;
+}
+
+int64_t vti_annotate_frames_scratch_bytes(const vti_ctx* c, const void* host_out_table, int32_t max_det, int32_t max_points) {
+    if (!c || !host_out_table) return 0;
+    const FrameTableHeader h = table_header(host_out_table);
+    if (h.magic != kFrameTableMagic || h.B < 1) return 0;
+    int32_t mh = 0, mw = 0;                       // of the rows themselves (the header's maxima are only an upper bound)
+    for (int32_t k = 0; k < h.B; ++k) {
+        const FrameRow r = table_row(host_out_table, k);
+        mh = std::max(mh, r.H0); mw = std::max(mw, r.W0);
+    }
+    return vti_annotate_scratch_bytes(c, h.B, max_det, mh, mw, max_points);
+}
+
+int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                            const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
+                            const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
+                            int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                            const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                            const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+    // every check comes before the first HIP call
+    char msg[200];
+    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_annotate_frames: null ctx");
+    FrameTableHeader hi, ho;
+    if (int32_t rc = frames_check("vti_annotate_frames", c, host_table, dev_table, B, hi)) return rc;
+    if (n_sel < 1) return bad("vti_annotate_frames: n_sel must be >= 1");
+    if (int32_t rc = frames_check("vti_annotate_frames (out table)", c, host_out_table, dev_out_table, n_sel, ho)) return rc;
+    if (native == 1) return fail(c, VTI_ERR_UNSUPPORTED, "vti_annotate_frames: native masks need frames of one size (vti_annotate)");
+    if (capacity < 0 || n_cams < 1 || native != 0 || max_det < 1 || max_det > VTI_MEASURE_MAX_DET || max_points < 0)
+        return bad("vti_annotate_frames: bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
+    if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
+        !dev_select || !out || !status || (capacity && !masks))
+        return bad("vti_annotate_frames: null pointer");
+    int32_t mh = 0, mw = 0;
+    long long max_px = 0;
+    bool any_lds = false, any_global = false;
+    for (int32_t k = 0; k < n_sel; ++k) {
+        const int32_t b = host_select[k];
+        if (b < 0 || b >= B) {
+            snprintf(msg, sizeof msg, "vti_annotate_frames: host_select[%d] = %d is outside [0, %d)", k, b, B);
+            return bad(msg);
+        }
+        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
+        if (ri.H0 > 8192 || ri.W0 > 8192) {
+            snprintf(msg, sizeof msg, "vti_annotate_frames: frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
+            return bad(msg);
+        }
+        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
+            snprintf(msg, sizeof msg, "vti_annotate_frames: row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k,
+                     ro.H0, ro.W0, k, b, ri.H0, ri.W0);
+            return bad(msg);
+        }
+        mh = std::max(mh, ri.H0); mw = std::max(mw, ri.W0);
+        max_px = std::max(max_px, (long long)ri.H0 * ri.W0);
+        AnnotateLayout one;
+        annotate_layout(1, 1, ri.H0, ri.W0, 0, one);
+        (one.in_lds ? any_lds : any_global) = true;
+    }
+    if (!annotate_sizes_ok(n_sel, max_det, mh, mw, max_points)) return bad("vti_annotate_frames: the selection is too large");
+    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 15))
+        return bad("vti_annotate_frames: dev_frames and dev_out must be 16-byte aligned");
+    if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
+        return bad("vti_annotate_frames: the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
+    if (capacity && ((uintptr_t)masks & 15)) return bad("vti_annotate_frames: masks must be 16-byte aligned");
+    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
+        return bad("vti_annotate_frames: misaligned measurement rows or status");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_annotate_frames: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_annotate_scratch_bytes(c, n_sel, max_det, mh, mw, max_points))
+        return bad("vti_annotate_frames: scratch smaller than vti_annotate_frames_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_annotate_frames")) return drc;
+    const vti_desc& d = c->plan.desc;
+    const AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), any_lds, any_global, max_px};
+    VTI_HIP(c, launch_annotate(frames, B, mh, mw, cameras, n_cams, cam_of_frame, masks, 0, dets, xyxy, counts, offsets, max_det, d.nm,
+                               capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
+                               scratch, (hipStream_t)stream, &fr), "annotate kernels");
+    return VTI_OK;
+}
+
 int64_t vti_encode_jpeg_scratch_bytes(const vti_ctx* c, int32_t n, int32_t H0, int32_t W0) {
     JpegLayout L;
     if (!c || !encode_jpeg_layout(n, H0, W0, L)) return 0;
@@ -1091,6 +1178,55 @@ int32_t vti_encode_jpeg(vti_ctx* c, const uint8_t* frames, int32_t n, int32_t H0
     if (int32_t drc = check_device(c, "vti_encode_jpeg")) return drc;
     VTI_HIP(c, launch_encode_jpeg(frames, n, H0, W0, rgb, quality, scratch, (long long*)offsets, out, (long long)max_bytes,
                                   (hipStream_t)stream), "encode_jpeg kernels");
+    return VTI_OK;
+}
+
+// ---- vti_encode_jpeg for frames of differing sizes -------------------------------------------------------------------------
+// The header and rows of a host frame table, as far as they can be checked without a ctx: nullptr, or what is wrong.
+static const char* jpeg_table_error(const void* host_table, JpegFramesLayout& L) {
+    if (!host_table) return "null frame table";
+    const FrameTableHeader h = table_header(host_table);
+    if (h.magic != kFrameTableMagic || h.B < 1) return "host_table is not a table of vti_pack_frames";
+    if (!encode_jpeg_frames_layout(host_table, L)) return "a frame is outside 1 <= H0, W0 <= 8192, or the batch has more than 2^28 MCUs";
+    return nullptr;
+}
+
+int64_t vti_encode_jpeg_frames_scratch_bytes(const vti_ctx* c, const void* host_table) {
+    JpegFramesLayout L;
+    if (!c || jpeg_table_error(host_table, L)) return 0;
+    return (int64_t)L.total;
+}
+
+int64_t vti_encode_jpeg_frames_max_bytes(const void* host_table) {
+    JpegFramesLayout L;
+    if (jpeg_table_error(host_table, L)) return 0;
+    return (int64_t)L.max_bytes;
+}
+
+int32_t vti_encode_jpeg_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t n, int32_t rgb,
+                               int32_t quality, void* scratch, size_t scratch_bytes, int64_t* offsets, uint8_t* out, int64_t max_bytes,
+                               void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_encode_jpeg_frames: null ctx");
+    FrameTableHeader h;
+    if (int32_t rc = frames_check("vti_encode_jpeg_frames", c, host_table, dev_table, n, h)) return rc;
+    JpegFramesLayout L;
+    if (const char* e = jpeg_table_error(host_table, L)) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "vti_encode_jpeg_frames: %s", e);
+        return bad(msg);
+    }
+    if (quality < 1 || quality > 100 || (rgb != 0 && rgb != 1) || max_bytes < 0)
+        return bad("vti_encode_jpeg_frames: 1 <= quality <= 100, rgb 0 or 1, max_bytes >= 0");
+    if (!frames || !offsets || (max_bytes && !out)) return bad("vti_encode_jpeg_frames: null pointer");
+    if ((uintptr_t)offsets & 7) return bad("vti_encode_jpeg_frames: dev_byte_offsets must be 8-byte aligned");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_encode_jpeg_frames: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < (int64_t)L.total)
+        return bad("vti_encode_jpeg_frames: scratch smaller than vti_encode_jpeg_frames_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_encode_jpeg_frames")) return drc;
+    VTI_HIP(c, launch_encode_jpeg_frames(frames, host_table, frame_rows(dev_table), rgb, quality, scratch, (long long*)offsets, out,
+                                         (long long)max_bytes, (hipStream_t)stream), "encode_jpeg_frames kernels");
     return VTI_OK;
 }
 

@@ -342,12 +342,16 @@ struct AnnotateLayout {
     size_t off_recs, off_meta, off_env, off_cont, off_union, off_areas, area_bytes, off_runs, off_rows, total;
 };
 void annotate_layout(int n_sel, int max_det, int H0, int W0, int max_points, AnnotateLayout& L);
+// vti_annotate_frames: the rows of the device frame tables of dev_frames and dev_out; H0, W0 passed to launch_annotate are then the
+// largest selected ones (the pitches of the scratch), native is 0.  any_lds / any_global: a selected frame's union fits / does not fit
+// the tracer's LDS image (which outline instantiations are launched); max_px: the most pixels a selected frame has (the raster grid).
+struct AnnotateFrames { const FrameRow* rows_in; const FrameRow* rows_out; bool any_lds, any_global; long long max_px; };
 // cameras: a packed camera table in device memory; select: the device copy of the (host-checked) selection; native = 1: H, W unused
 hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const void* cameras, int n_cams, const int* cam_of_frame,
                            const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
                            const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
                            const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
-                           int* status, void* scratch, hipStream_t st);
+                           int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
 
 // jpeg.hip: vti_encode_jpeg (the saved JPEG).  The scratch holds: the header's bytes (1 KiB) | bit total u64 [n] | file size i64 [n] |
 // coefficients i16 [n, MCUs, 6, 64] | block bit positions u64 [n, blocks] | the unstuffed stream, NC chunks of 4096 bytes per frame
@@ -365,6 +369,20 @@ bool encode_jpeg_layout(long long n, int H0, int W0, JpegLayout& L);
 void encode_jpeg_header(int H0, int W0, int quality, uint8_t out[624]);      // SOI .. SOS: 623 bytes and one of padding
 hipError_t launch_encode_jpeg(const uint8_t* frames, int n, int H0, int W0, int rgb, int quality, void* scratch, long long* offsets,
                               uint8_t* out, long long max_bytes, hipStream_t st);
+// vti_encode_jpeg_frames: frame k is row k of a frame table.  MCUs, blocks and chunks are numbered through the whole batch, so the
+// scratch is the uniform call's with every frame's part as long as that frame needs, behind the two prefix arrays i64 [n + 1] (MCUs,
+// chunks) that the first launch builds from the device table: header bytes (1 KiB) | pm | pc | bit total | file size | coefficients |
+// bit positions | streams | 0xFF counts.
+struct JpegFramesLayout {
+    int n;
+    long long n_mcu, n_chunk;  // of the whole batch
+    long long max_bytes;       // the sum of the frames' max_file
+    size_t off_pm, off_pc, off_fbits, off_fsize, off_coef, off_bitpos, off_stream, off_chunk, total;
+};
+// host_table: a packed frame table (its rows already validated); false when a frame is outside vti_encode_jpeg's limits
+bool encode_jpeg_frames_layout(const void* host_table, JpegFramesLayout& L);
+hipError_t launch_encode_jpeg_frames(const uint8_t* frames, const void* host_table, const FrameRow* rows, int rgb, int quality,
+                                     void* scratch, long long* offsets, uint8_t* out, long long max_bytes, hipStream_t st);
 
 // jpeg_decode.hip: vti_decode_jpeg (JPEG files -> frames).  The host parses every header; a descriptor table is a JpegDecHeader
 // followed by one JpegDecRow per file.  The scratch holds per file, each part rounded up to 256 bytes: the segment states (entry u64 |

@@ -486,7 +486,8 @@ class Engine:
     def annotate_scratch_bytes(self, n_sel, max_det, H0, W0, max_points):
         return int(lib().vti_annotate_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))
 
-    def annotate(self, frames, out, meas, params_or_table, select, cameras=None, native=False, result=None, max_points=16384):
+    def annotate(self, frames, out, meas, params_or_table, select, cameras=None, native=False, result=None, max_points=16384,
+                 table=None):
         """The frames `select` of the batch with the reference's overlay drawn on them: vti_annotate, byte for byte
         annotate.rasterise(frame, annotate.display_list(...)).  frames: the contiguous uint8 [B,H0,W0,3] BGR device batch predict
         consumed; out: its output set; meas: measure(..., stitch_rows=True)'s dict on the same set; params_or_table: the
@@ -494,10 +495,23 @@ class Engine:
         the first row serves every frame); select: host integers in [0, B), any order, duplicates allowed (ValueError otherwise).
         max_points: room for the fabric outline's vertices per frame.  Returns device tensors, no host synchronisation:
         dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]: VTI_ANNOTATE_OUTLINE_SKIPPED where the outline did not fit).  `result`: the
-        same dict preallocated.  Text is the host's: annotate.text_items / put_text."""
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("annotate: frames must be a uint8 [B,H0,W0,3] tensor")
-        B, H0, W0, _ = frames.shape
+        same dict preallocated.  Text is the host's: annotate.text_items / put_text.
+        table (vti_annotate_frames): the FrameTable of a batch whose frames differ in size; `frames` is then the flat u8 device buffer
+        the table describes (what predict consumed, or DecodedFrames.buf) and frame select[k] is drawn at its own size.  Returns
+        dict(buf=u8 flat, table=the FrameTable of the selection (pack_frames of its shapes; the 16 latest tuples of shapes are kept), shapes,
+        byte_offsets, status): picture k is buf[byte_offsets[k]:][:3 * H0 * W0].view(H0, W0, 3), and (buf, table) is what
+        encode_jpeg(..., table=) and predict_frames_into take.  `result` may preallocate buf and status.  Letterbox masks only."""
+        if table is not None:
+            self._check_frames(table)
+            if native:
+                raise ValueError("annotate: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
+                raise ValueError("annotate: with table=, frames must be the flat uint8 frame buffer")
+            B, H0, W0 = table.B, None, None
+        else:
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError("annotate: frames must be a uint8 [B,H0,W0,3] tensor")
+            B, H0, W0, _ = frames.shape
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
@@ -516,13 +530,13 @@ class Engine:
         # everything above is about shapes and values; what needs a device comes from here on
         if not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("annotate: frames must be the contiguous device batch predict consumed")
-        table = params_or_table
-        if not isinstance(table, torch.Tensor):
-            table = self.pack_cameras(table if isinstance(table, (list, tuple)) else [table], dev)
+        table_c = params_or_table
+        if not isinstance(table_c, torch.Tensor):
+            table_c = self.pack_cameras(table_c if isinstance(table_c, (list, tuple)) else [table_c], dev)
         row = int(lib().vti_measure_cameras_bytes(1))
-        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
+        if table_c.dtype != torch.uint8 or table_c.dim() != 1 or table_c.numel() < row or table_c.numel() % row or table_c.device != dev:
             raise ValueError("annotate: params_or_table must be MeasureParams or the u8 table of pack_cameras() on the outputs' device")
-        n_cams = table.numel() // row
+        n_cams = table_c.numel() // row
         if cameras is not None and not (isinstance(cameras, torch.Tensor) and cameras.is_cuda):
             host = np.asarray(cameras.numpy() if isinstance(cameras, torch.Tensor) else cameras)
             if host.shape != (B,) or host.dtype.kind not in "iu":
@@ -533,20 +547,46 @@ class Engine:
         elif cameras is not None and (cameras.dtype != torch.int32 or tuple(cameras.shape) != (B,) or not cameras.is_contiguous()):
             raise ValueError(f"annotate: cameras must be a contiguous int32 [{B}] tensor on the outputs' device")
         r = dict(result or {})
-        if "frames" not in r:
-            r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
         if "status" not in r:
             r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
-        need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
-        if need <= 0:
-            raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+        if table is not None:
+            self._check_frames(table, buf=frames)
+            shapes = tuple(table.shapes[int(b)] for b in sel)
+            cache = self.__dict__.setdefault("_out_tables", {})          # (shapes, device) -> FrameTable, the 16 latest selections
+            out_table = cache.pop((shapes, str(dev)), None)
+            if out_table is None:
+                out_table = self.pack_frames(shapes, dev)[0]
+                while len(cache) >= 16:
+                    del cache[next(iter(cache))]
+            cache[(shapes, str(dev))] = out_table                       # (re)inserted last: the oldest entry is the first
+            if "buf" not in r:
+                r["buf"] = torch.empty(out_table.total_bytes, dtype=torch.uint8, device=dev)
+            self._check_frames(out_table, buf=r["buf"])
+            r.update(table=out_table, shapes=list(shapes), byte_offsets=list(out_table.byte_offsets))
+            need = int(lib().vti_annotate_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
+            if need <= 0:
+                raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
+                                 f"{out_table.max_H0}x{out_table.max_W0}, max_points={max_points}; a drawn frame is at most 8192 x 8192)")
+        else:
+            if "frames" not in r:
+                r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
+            need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
+            if need <= 0:
+                raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
         ws = getattr(self, "_annotate_ws", None)
         if ws is None or ws.numel() < need or ws.device != dev:
             self._annotate_ws = None
             ws = self._annotate_ws = torch.empty(need, dtype=torch.uint8, device=dev)
         dev_sel = torch.from_numpy(sel).to(dev)
+        if table is not None:
+            check(self._ctx, lib().vti_annotate_frames(
+                self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras), _ptr(masks) if capacity else C.c_void_p(0),
+                0, _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
+                _ptr(meas["frame_i32"]), _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel),
+                n_sel, int(max_points), *out_table._ptrs(), _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+            return r
         check(self._ctx, lib().vti_annotate(
-            self._ctx, _ptr(frames), B, H0, W0, _ptr(table), n_cams, _ptr(cameras), _ptr(masks) if capacity else C.c_void_p(0),
+            self._ctx, _ptr(frames), B, H0, W0, _ptr(table_c), n_cams, _ptr(cameras), _ptr(masks) if capacity else C.c_void_p(0),
             int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
             _ptr(meas["frame_i32"]), _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel),
             n_sel, int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
@@ -556,30 +596,45 @@ class Engine:
     def encode_jpeg_scratch_bytes(self, n, H0, W0):
         return int(lib().vti_encode_jpeg_scratch_bytes(self._ctx, int(n), int(H0), int(W0)))
 
-    def encode_jpeg(self, frames, quality=95, rgb=False, max_bytes=None):
+    def encode_jpeg(self, frames, quality=95, rgb=False, max_bytes=None, table=None):
         """The frames as JPEG files, byte for byte jpeg.encode(frame, quality, rgb) (libjpeg's baseline 4:2:0 file): vti_encode_jpeg.
         frames: a contiguous uint8 [n,H0,W0,3] device tensor, BGR unless rgb (annotate()'s "frames", or a raw batch); never written.
         -> (out u8 [max_bytes], offsets i64 [n+1]) on the device: file k is out[offsets[k]:offsets[k+1]].  max_bytes: the room for
         the n files, 3 * n * H0 * W0 + 1024 * n by default; when offsets[n] exceeds it (one host read of that value) the call runs
-        again with exactly offsets[n].  The scratch is kept per (n, H0, W0)."""
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("encode_jpeg: frames must be a uint8 [n,H0,W0,3] tensor")
-        n, H0, W0, _ = frames.shape
+        again with exactly offsets[n].  The scratch is kept per (n, H0, W0).
+        table (vti_encode_jpeg_frames): a FrameTable; `frames` is then the flat u8 device buffer it describes (annotate(..., table=)'s
+        buf with its table, a decoded batch, ...) and file k is frame k at its own size.  max_bytes defaults to the sum of 3 * H0 * W0
+        + 1024 over the frames; the scratch is kept per tuple of shapes."""
+        if table is not None:
+            self._check_frames(table)
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
+                raise ValueError("encode_jpeg: with table=, frames must be the flat uint8 frame buffer")
+            n = table.B
+        else:
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError("encode_jpeg: frames must be a uint8 [n,H0,W0,3] tensor")
+            n, H0, W0, _ = frames.shape
         quality = int(quality)
         if not 1 <= quality <= 100:
             raise ValueError(f"encode_jpeg: quality must be in 1..100, got {quality}")
         if max_bytes is None:
-            max_bytes = 3 * n * H0 * W0 + 1024 * n
+            max_bytes = sum(3 * h * w + 1024 for h, w in table.shapes) if table is not None else 3 * n * H0 * W0 + 1024 * n
         max_bytes = int(max_bytes)
         if max_bytes < 0:
             raise ValueError("encode_jpeg: max_bytes must be >= 0")
-        need = self.encode_jpeg_scratch_bytes(n, H0, W0)
-        if need <= 0:
-            raise ValueError(f"encode_jpeg: unsupported geometry (n={n}, {H0}x{W0}; 1 <= H0, W0 <= 8192)")
+        if table is not None:
+            need = int(lib().vti_encode_jpeg_frames_scratch_bytes(self._ctx, C.c_void_p(table.host.data_ptr())))
+            if need <= 0:
+                raise ValueError(f"encode_jpeg: unsupported geometry ({n} frames up to {table.max_H0}x{table.max_W0}; 1 <= H0, W0 <= 8192)")
+            self._check_frames(table, buf=frames)
+        else:
+            need = self.encode_jpeg_scratch_bytes(n, H0, W0)
+            if need <= 0:
+                raise ValueError(f"encode_jpeg: unsupported geometry (n={n}, {H0}x{W0}; 1 <= H0, W0 <= 8192)")
         if not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("encode_jpeg: frames must be a contiguous device tensor")
         dev = frames.device
-        key = (n, H0, W0, str(dev))
+        key = (tuple(table.shapes), str(dev)) if table is not None else (n, H0, W0, str(dev))
         ws = getattr(self, "_jpeg_ws", None)
         if ws is None or ws[0] != key:
             self._jpeg_ws = None                        # free the old scratch before the new one is allocated
@@ -589,6 +644,11 @@ class Engine:
 
         def launch(room):
             out = torch.empty((room,), dtype=torch.uint8, device=dev)
+            if table is not None:
+                check(self._ctx, lib().vti_encode_jpeg_frames(self._ctx, _ptr(frames), *table._ptrs(), n, int(bool(rgb)), quality, _ptr(ws),
+                                                              ws.numel(), _ptr(offsets), _ptr(out) if room else C.c_void_p(0), room,
+                                                              _stream()))
+                return out
             check(self._ctx, lib().vti_encode_jpeg(self._ctx, _ptr(frames), n, H0, W0, int(bool(rgb)), quality, _ptr(ws), ws.numel(),
                                                    _ptr(offsets), _ptr(out) if room else C.c_void_p(0), room, _stream()))
             return out

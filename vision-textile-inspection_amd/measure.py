@@ -15,9 +15,13 @@ vti_annotate paints the overlay on the device batch predict consumed and the sel
 (which holds the smoothed values) is returned as annotate.text_items and drawn by annotate.put_text where OpenCV is installed.
 With `encode="jpeg"` the selected pictures are also encoded on the device (vti_encode_jpeg: the file cv2.imwrite would save of that
 picture, jpeg.py) and only the files' bytes come back; the text still rides along as text_items, it is not in the JPEG.
+With `mixed=True` both also serve a list of frames whose sizes differ (vti_annotate_frames, vti_encode_jpeg_frames): every selected
+frame is drawn and encoded at its own size, and the pictures or files still come back in one copy.
 """
 import ctypes as C
 import dataclasses
+import functools
+import inspect
 import json
 from collections import deque
 from datetime import datetime
@@ -114,6 +118,25 @@ class CameraStream:
                 'timestamp': datetime.now()}
 
 
+def _mixed_keyword(public):
+    """process_frames' keyword-only `mixed`.  `public` carries the signature and the documentation -- its parameter list, which ends
+    in annotate, encode, jpeg_quality for positional callers and for inspect.signature, stays as it was -- and the work is in the
+    class's _process_frames, which takes the same parameters by name and `mixed` next to them: an argument all the way down, no
+    state on the measurer."""
+    sig = inspect.signature(public)
+
+    @functools.wraps(public)
+    def process_frames(self, *args, mixed=False, **kw):
+        if not isinstance(mixed, (bool, np.bool_)):
+            raise ValueError(f"process_frames: mixed must be True or False, got {mixed!r}")
+        bound = sig.bind(self, *args, **kw)             # a TypeError for a bad call, as calling `public` would give
+        bound.apply_defaults()
+        named = dict(bound.arguments)
+        del named["self"]
+        return self._process_frames(mixed=bool(mixed), **named)
+    return process_frames
+
+
 class _DeviceStage:
     """predict + one measure call + one device -> host read of the B frame records."""
 
@@ -123,9 +146,10 @@ class _DeviceStage:
 
     @torch.inference_mode()
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
-                       jpeg_quality=95):
+                       jpeg_quality=95, mixed=False):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
-        selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0.  params /
+        selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0 (frames of
+        differing sizes, which `mixed` allows with annotate: the list of every frame's H0).  params /
         cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the outputs exist (the
         camera table needs both)."""
         if encode is not None:
@@ -142,12 +166,13 @@ class _DeviceStage:
         shapes = self.model._differing_shapes(frames)
         table = None
         if shapes is not None:
-            if annotate is not None:
+            if annotate is not None and not mixed:
                 raise ValueError("process_frames: annotate needs frames of one size; the frames of this list differ in shape "
                                  "(vti_annotate has no frame-table form)")
             if retina_masks:
                 raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
-            eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False)
+            eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False,
+                                                                  keep_frames=annotate is not None)
             B, H0, W0 = len(shapes), None, None
         else:
             eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks,
@@ -178,18 +203,25 @@ class _DeviceStage:
         if sel is None:
             return f64, i32
         return f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks),
-                                         int(jpeg_quality) if encode else None), H0
+                                         int(jpeg_quality) if encode else None, table), H0 if table is None else [h for h, _ in shapes]
 
-    def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None):
+    def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None, table=None):
         """vti_annotate on the batch predict consumed; the selected pictures in one device -> host copy, and of the per-slot rows only
         those of the selected frames.  jpeg_quality: the pictures go through vti_encode_jpeg first and the copy is of the files'
-        bytes (one read of the offsets, one of out[:offsets[n]])."""
-        ann = eng.annotate(self.model._last_frames, o, res, params, sel, cameras=cameras, native=native)
+        bytes (one read of the offsets, one of out[:offsets[n]]).  table: the FrameTable of a batch whose frames differ in size --
+        vti_annotate_frames and vti_encode_jpeg_frames; the one copy is then of the flat buffer, sliced into [H0, W0, 3] arrays."""
+        ann = eng.annotate(self.model._last_frames, o, res, params, sel, cameras=cameras, native=native, table=table)
         self.model._last_frames = None            # the launches are enqueued: the batch need not outlive the call
-        if jpeg_quality is None:
+        if jpeg_quality is None and table is not None:
+            flat = ann["buf"].cpu().numpy()
+            pics = [flat[at:at + 3 * h * w].reshape(h, w, 3) for (h, w), at in zip(ann["shapes"], ann["byte_offsets"])]
+        elif jpeg_quality is None:
             pics = ann["frames"].cpu().numpy()
         else:
-            data, off = eng.encode_jpeg(ann["frames"], quality=jpeg_quality)
+            if table is not None:
+                data, off = eng.encode_jpeg(ann["buf"], quality=jpeg_quality, table=ann["table"])
+            else:
+                data, off = eng.encode_jpeg(ann["frames"], quality=jpeg_quality)
             off = off.cpu().numpy()
             data = data[:int(off[-1])].cpu().numpy().tobytes()
             pics = [data[off[k]:off[k + 1]] for k in range(len(sel))]
@@ -212,11 +244,12 @@ class _DeviceStage:
     @staticmethod
     def _with_text(annotated, records, i32, min_stitches, H0):
         """[(frame index, picture, rows)] -> [(frame index, picture, text_items)] with the strings built from the frames' records
-        (picture: the BGR ndarray of height H0, or its JPEG file's bytes)."""
+        (picture: the BGR ndarray of height H0, or its JPEG file's bytes).  H0: one height, or every frame's own."""
         out = []
         for b, pic, rows in annotated:
             rows = dict(rows, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
-            out.append((b, pic, _annotate.text_items(records[b], rows, H0, min_stitches(b))))
+            h0 = H0[b] if isinstance(H0, (list, tuple)) else H0
+            out.append((b, pic, _annotate.text_items(records[b], rows, h0, min_stitches(b))))
         return out
 
 
@@ -232,6 +265,7 @@ class StitchMeasurer(_DeviceStage):
         self._record = self._stream.record
         self._cp = self.params.to_c()
 
+    @_mixed_keyword
     def process_frames(self, frames, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None, encode=None,
                        jpeg_quality=95):
         """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them, or a list of JPEG files (bytes) as a
@@ -244,8 +278,15 @@ class StitchMeasurer(_DeviceStage):
         annotate.text_items', for annotate.put_text), records exactly as without it.
         encode="jpeg" (with annotate): each annotated item is (frame index, bytes, text_items), the bytes being the JPEG file
         cv2.imwrite(path, picture) saves at jpeg_quality (jpeg.encode, byte for byte), encoded on the device; the text is NOT in
-        that picture, it still comes as text_items.  Any other encode, or encode without annotate, is a ValueError."""
-        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality)
+        that picture, it still comes as text_items.  Any other encode, or encode without annotate, is a ValueError.
+        mixed (keyword only, default False): True lets a LIST of frames whose sizes differ (ndarrays or JPEG files) be combined with
+        annotate and encode: every selected frame is drawn (vti_annotate_frames) and encoded (vti_encode_jpeg_frames) at its own
+        size, a picture is the [H0, W0, 3] ndarray of its frame, and text_items are placed by each frame's own height.  Without it
+        such a list with annotate is refused, as before; on frames of one size it changes nothing.  retina_masks=True with
+        differing sizes stays refused."""
+
+    def _process_frames(self, frames, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed):
+        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed)
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
         if annotate is None:
@@ -286,14 +327,19 @@ class MultiCameraMeasurer(_DeviceStage):
             self._tables[key] = (eng, eng.pack_cameras(self.params, device))
         return self._tables[key][1]
 
+    @_mixed_keyword
     def process_frames(self, frames, cameras, conf=0.20, iou=0.25, max_det=200, imgsz=960, retina_masks=False, annotate=None,
                        encode=None, jpeg_quality=95):
         """frames as StitchMeasurer.process_frames, or a list of frames whose sizes differ (cameras of several resolutions in one
         batch: one predict, one vti_measure_frames, one read); cameras: one index into params_by_camera per frame (host integers).
         Returns one record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame
-        order.  annotate, encode, jpeg_quality: as StitchMeasurer.process_frames (frames of one size only) -> (annotated, records)."""
+        order.  annotate, encode, jpeg_quality, mixed: as StitchMeasurer.process_frames (frames of differing sizes only with
+        mixed=True) -> (annotated, records)."""
+
+    def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed):
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
-        got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality)
+        got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
+                                  mixed)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         if annotate is None:

@@ -251,10 +251,12 @@ class YOLO:
                 raise ValueError(f"every frame of a list source must be uint8 HxWx3, got shape {x}")
         return [x[:2] for x in shapes]
 
-    def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb):
+    def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, keep_frames=False):
         """_predict_outputs for frames of differing sizes: the frames are flattened into one pinned staging buffer, copied with one
         asynchronous H2D and run through one vti_predict_frames on the stride-rounded imgsz canvas.  The packed frame table, the
-        staging buffer and its device twin are cached per (engine, shapes).  -> (engine, output set, FrameTable, (H, W))."""
+        staging buffer and its device twin are cached per (engine, shapes).  -> (engine, output set, FrameTable, (H, W)).
+        keep_frames: as _predict_outputs -- the flat device buffer this predict consumed stays in _last_frames for a caller that
+        draws on it."""
         new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
         H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
         B = len(shapes)
@@ -284,6 +286,8 @@ class YOLO:
             self._outs.clear()
             o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev)
         eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits")
+        if keep_frames:
+            self._last_frames = buf
         return eng, o, table, (H, W)
 
     def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks, keep_frames=False):
