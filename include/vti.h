@@ -337,7 +337,8 @@ int32_t vti_scale_boxes_frames(vti_ctx* ctx, const float* dev_dets, const int32_
                                const void* dev_table, int32_t B, int32_t max_det, float* dev_xyxy, void* stream);
 /* vti_predict for such a batch: vti_letterbox_frames (always; dev_input_scratch is required), the scored forward, NMS, vti_masks
  * (masks at the canvas size, as Ultralytics' masks.data) and, when dev_xyxy is given, vti_scale_boxes_frames; one stream, no host
- * synchronisation.  mask_mode | VTI_MASK_NATIVE is VTI_ERR_UNSUPPORTED: frame-resolution masks need frames of one size. */
+ * synchronisation.  mask_mode | VTI_MASK_NATIVE is VTI_ERR_UNSUPPORTED here: frame-resolution masks of frames of differing sizes do
+ * not fit this call's slots of one size; they are vti_predict_frames_native's, below. */
 int32_t vti_predict_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t B,
                            int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
                            int32_t packing, uint8_t* dev_input_scratch, float* dev_pred, void* dev_proto, float* dev_dets,
@@ -345,14 +346,57 @@ int32_t vti_predict_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* 
                            void* stream);
 /* vti_measure_cameras with H0, W0 of frame b from the frame table (ROI clamp, column clip, resize of the masks): frame b's results
  * are bit-identical to those of vti_measure_cameras called with H0[b], W0[b] on the same inputs.  Letterbox bit masks only: native
- * = 1 is VTI_ERR_UNSUPPORTED.  dev_scratch: >= vti_measure_scratch_bytes(ctx, B, capacity, largest W0 of the table) (the envelope
- * rows are pitched by it).  The slot -> frame search of the moment kernel runs over dev_offsets[0 .. B] and ends inside [0, B)
- * whatever they hold. */
+ * = 1 is VTI_ERR_UNSUPPORTED (the ragged frame-size rows are vti_measure_frames_native's, below).  dev_scratch: >=
+ * vti_measure_scratch_bytes(ctx, B, capacity, largest W0 of the table) (the envelope rows are pitched by it).  The slot -> frame
+ * search of the moment kernel runs over dev_offsets[0 .. B] and ends inside [0, B) whatever they hold. */
 int32_t vti_measure_frames(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams, const int32_t* dev_camera_of_frame,
                            const uint8_t* dev_masks, int32_t native, const float* dev_dets, const float* dev_xyxy,
                            const int32_t* dev_counts, const int32_t* dev_offsets, const void* host_table, const void* dev_table,
                            int32_t B, int32_t max_det, int32_t capacity, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
                            int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
+
+/* ---- frame-resolution masks for frames of differing sizes: the ragged mask buffer --------------------------------------- */
+/* retina_masks for a batch of vti_pack_frames.  Frames of different sizes have slots of different byte sizes, so the masks of one
+ * call lie in one flat, 8-byte aligned u8 buffer, bit-packed (VTI_PACK_BITS only; VTI_PACK_U8 is VTI_ERR_UNSUPPORTED):
+ *   - a slot of frame b has the layout vti_mask_native_layout(H0[b], W0[b], VTI_PACK_BITS) gives: H0[b] rows of row_bytes[b] =
+ *     8*ceil(W0[b]/64) bytes, LSB-first, bits at columns >= W0[b] zero; slot_bytes[b] = H0[b] * row_bytes[b];
+ *   - the slots lie back to back, frame-major, in detection order.  dev_offsets i32 [B+1] is vti_masks' prefix sum of the clamped
+ *     counts (instance i of frame b is slot INDEX offsets[b] + i: the row of every per-slot output), and dev_mask_bases i64 [B+1]
+ *     holds bases[b] = sum over b' < b of clamp(counts[b']) * slot_bytes[b'], not clipped by the capacity: instance i of frame b
+ *     starts at BYTE bases[b] + i * slot_bytes[b].  Every base is a multiple of 8;
+ *   - the capacity is in bytes: an instance is live iff its slot ends at or before capacity_bytes.  The bases are monotone, so the
+ *     live instances are a prefix of the slot order; live slots are written completely and no byte after the last live slot is
+ *     touched: no byte of a slot that did not fit is written.
+ * Host only: the worst case, max_det slots for every frame of the table: sum over b of max_det * slot_bytes[b]; 0 on a bad argument
+ * (NULL, max_det < 1, not a valid packed table for this ctx's canvas, more frames than max_batch). */
+int64_t vti_mask_native_frames_bytes(const vti_ctx* ctx, const void* host_table, int32_t max_det);
+/* vti_masks_native for such a batch: frame b's live slots are byte for byte those vti_masks_native(..., H0[b], W0[b], ...) writes for
+ * frame b from the same dets, xyxy (vti_scale_boxes_frames), counts and prototypes -- one function computes a frame size's crop, scales,
+ * tile height and slot layout for both calls.  Writes dev_offsets and dev_mask_bases (also when capacity_bytes is 0, and nothing else
+ * then).  The table pair is checked as by every *_frames call; nm must be 32; every argument check runs before the first HIP call. */
+int32_t vti_masks_native_frames(vti_ctx* ctx, const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                                const void* dev_proto, const void* host_table, const void* dev_table, int32_t B, int32_t max_det,
+                                int32_t mode, int32_t packing, uint8_t* dev_masks, int64_t capacity_bytes, int32_t* dev_offsets,
+                                int64_t* dev_mask_bases, void* stream);
+/* vti_predict_frames with those masks: vti_letterbox_frames, the scored forward, NMS, vti_scale_boxes_frames (dev_xyxy is required)
+ * and vti_masks_native_frames; one stream, no host synchronisation.  mask_mode: VTI_MASK_LOGIT or VTI_MASK_SIGMOID (the
+ * VTI_MASK_NATIVE flag is implied and ignored).  dev_dets, dev_counts, dev_xyxy and dev_offsets are those of vti_predict_frames. */
+int32_t vti_predict_frames_native(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t B,
+                                  int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
+                                  int32_t packing, uint8_t* dev_input_scratch, float* dev_pred, void* dev_proto, float* dev_dets,
+                                  int32_t* dev_counts, uint8_t* dev_masks, int64_t capacity_bytes, int32_t* dev_offsets,
+                                  int64_t* dev_mask_bases, float* dev_xyxy, void* stream);
+/* vti_measure_frames on those rows (there is no `native` argument: the rows are the frame's own pixels, so the nearest resize of
+ * measurement.py:70-86 is the identity).  dev_mask_bases and capacity_bytes: as vti_masks_native_frames wrote and took them;
+ * `capacity` stays the number of rows of the per-slot outputs and the sizing of vti_measure_scratch_bytes(ctx, B, capacity, largest
+ * W0).  A slot that is not live by the byte rule, or whose index is >= capacity, is an empty mask.  Frame b's results are
+ * bit-identical to those of vti_measure_cameras(native = 1) at H0[b], W0[b] on frame b's rows. */
+int32_t vti_measure_frames_native(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams, const int32_t* dev_camera_of_frame,
+                                  const uint8_t* dev_masks, const int64_t* dev_mask_bases, int64_t capacity_bytes,
+                                  const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets,
+                                  const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity,
+                                  void* dev_scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
+                                  int32_t* stitch_i32, void* stream);
 
 /* ---- Results.masks.xy on device: instance polygons in frame pixels ---------------------------------------------------- */
 /* Ultralytics masks2segments + scale_coords as restated by the package's polygons.py, bit for bit: per mask the outer border of

@@ -107,6 +107,12 @@ SIGNATURES = {
                                   _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),
     "vti_measure_frames": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ,
                                   _P, _P, _P, _P, _P]),
+    "vti_mask_native_frames_bytes": (_I64, [_P, _P, _I32]),
+    "vti_masks_native_frames": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P]),
+    "vti_predict_frames_native": (_I32, [_P, _P, _P, _P, _I32, _I32, _F, _D, _I32, _I32, _I32, _I32,
+                                         _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "vti_measure_frames_native": (_I32, [_P, _P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ,
+                                         _P, _P, _P, _P, _P]),
     "vti_mask_polygons_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_mask_polygons": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
     "vti_annotate_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),

@@ -24,11 +24,16 @@ namespace vti {
 // FRAMES (vti_measure_frames): the frames differ in size; the slot's frame is found in offsets[0 .. B] (instance i of frame b is slot
 // offsets[b] + i) and H0, W0 are that frame's, from its row of the frame table.  The search ends at an index in [0, B) whatever
 // the offsets hold, so no table address is formed outside the B rows.
-template <int VW, bool RAW, bool FRAMES = false>
+// RAGGED (vti_measure_frames_native; with FRAMES, VW = 2): the slots are the frame-size rows of vti_masks_native_frames.  Instance i of
+// frame b starts at byte bases[b] + i * slot_bytes[b] and is H0[b] rows of 2 ceil(W0[b] / 64) words (the identity branch, as the
+// uniform native call); a slot that does not end at or before capacity_bytes -- or whose offsets / bases do not place it inside the
+// buffer at an 8-byte boundary -- is the empty mask and nothing of it is read.
+template <int VW, bool RAW, bool FRAMES = false, bool RAGGED = false>
 __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ n_live,
                                                               int H, int W, int H0, int W0, long long* __restrict__ stats,
                                                               int* __restrict__ raw, const int* __restrict__ offsets = nullptr,
-                                                              const FrameRow* __restrict__ frames = nullptr, int B = 0) {
+                                                              const FrameRow* __restrict__ frames = nullptr, int B = 0,
+                                                              const long long* __restrict__ bases = nullptr, long long capacity_bytes = 0) {
     extern __shared__ int tab[];            // cx[W] xs[W] xf[W] xl[W] cy[H] ys[H]
     int* cx = tab; int* xs = cx + W; int* xf = xs + W; int* xl = xf + W; int* cy = xl + W; int* ys = cy + H;
     const int tid = threadIdx.x, slot = blockIdx.x;
@@ -44,6 +49,17 @@ __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __
             if (offsets[mid] <= slot) lo = mid; else hi = mid;
         }
         H0 = frames[lo].H0; W0 = frames[lo].W0;
+        if (RAGGED) {
+            const int wpr_b = 2 * ((W0 + 63) / 64);
+            const long long slot_bytes = (long long)H0 * wpr_b * 4, inst = (long long)slot - offsets[lo], at = bases[lo] + inst * slot_bytes;
+            if (inst < 0 || bases[lo] < 0 || (bases[lo] & 7) || at + slot_bytes > capacity_bytes) {
+                if (tid < 5) stats[(size_t)slot * 5 + tid] = tid < 3 ? 0 : -1;
+                if (RAW && tid == 0) raw[slot] = 0;
+                return;
+            }
+            H = H0; W = W0 = 32 * wpr_b;
+            bits += at >> 2;
+        }
     }
     const bool ident = H0 == H && W0 == W;
     if (!ident) {
@@ -66,7 +82,7 @@ __global__ __launch_bounds__(256) void mask_stats_bits_kernel(const unsigned* __
     // 16-byte loads, four of them in flight per thread before the first word is looked at (the loop was one dependent 4-byte load
     // per trip: latency-bound at a third of what the masks' L2 / HBM residency gives)
     using V = typename std::conditional<VW == 4, uint4, uint2>::type;
-    const V* m4 = (const V*)(bits + (size_t)slot * H * wpr);
+    const V* m4 = (const V*)(RAGGED ? bits : bits + (size_t)slot * H * wpr);
     const int n4 = (H * wpr) / VW;
     long long m00 = 0, m10 = 0, m01 = 0;
     int mn = INT_MAX, mx = -1, seen = 0;
@@ -169,7 +185,8 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
                                                             EnvSel sel, int H, int W, int H0, int W0, int* __restrict__ envelope,
                                                             const float* __restrict__ xyxy, int native_wpr,
                                                             const CameraRow* __restrict__ table, const int* __restrict__ cam_of_frame,
-                                                            int n_cams, const FrameRow* __restrict__ frames = nullptr) {
+                                                            int n_cams, const FrameRow* __restrict__ frames = nullptr,
+                                                            const long long* __restrict__ bases = nullptr, long long capacity_bytes = 0) {
     extern __shared__ int yl[];             // [H] (not NATIVE)
     __shared__ int red[4][64];
     const int tid = threadIdx.x, b = blockIdx.y;
@@ -202,9 +219,20 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
     const int x = blockIdx.x * 64 + (tid & 63), rg = tid >> 6;
     const int xc = x < W0 ? x : W0 - 1;
     const int sx = NATIVE ? xc : nn_src(xc, 1.0 / ((double)W0 / (double)W), W);
-    const int wpr = NATIVE ? native_wpr : W >> 5;
+    const bool ragged = NATIVE && bases;    // vti_measure_frames_native: the frame's own rows, from bases[b] on
+    const int wpr = NATIVE ? (ragged ? 2 * ((W0 + 63) / 64) : native_wpr) : W >> 5;
     const int Hm = NATIVE ? H0 : H;         // rows of a mask slot
-    const int s0 = offsets[b], s1 = min(offsets[b + 1], capacity);
+    const int s0 = offsets[b];
+    int s1 = min(offsets[b + 1], capacity);
+    const unsigned* fbits = bits;           // where slot `srel` starts
+    int srel = 0;
+    if (ragged) {                           // the instances whose slot ends at or before capacity_bytes; none if the base is no offset
+        const long long base = bases[b], slot_bytes = (long long)Hm * wpr * 4;
+        const long long fit = base >= 0 && !(base & 7) && capacity_bytes > base ? (capacity_bytes - base) / slot_bytes : 0;
+        s1 = (int)min((long long)s1, (long long)s0 + fit);
+        if (s1 > s0) fbits = bits + (base >> 2);
+        srel = s0;
+    }
     int env = -1;
     // the frame's instances of the wanted class, listed first (a thread per instance; the order is irrelevant to a max): the row
     // search below then runs over those only -- walking all instances with one dependent class load each was the kernel's time
@@ -230,7 +258,7 @@ __global__ __launch_bounds__(256) void envelope_bits_kernel(const unsigned* __re
         const int nsel = s_nsel;
         for (int j = 0; j < nsel; ++j) {
             const int s = s_sel[j][0], ya = s_sel[j][1], yb = s_sel[j][2];
-            const unsigned* m = bits + (size_t)s * Hm * wpr + (sx >> 5);
+            const unsigned* m = fbits + (size_t)(s - srel) * Hm * wpr + (sx >> 5);
             for (int sy = yb - rg; sy >= ya; sy -= 4) {           // top of the search first: the first hit of a lane is its largest
                 if ((m[(size_t)sy * wpr] >> (sx & 31)) & 1u) {
                     const int y = NATIVE ? sy : yl[sy];
@@ -701,9 +729,11 @@ void measure_pack_camera(const vti_measure_params& p, void* row) {
 hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
                           int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
                           int nm, int capacity, int H, int W, int H0, int W0, const FrameRow* frames, void* scratch, double* frame_f64,
-                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st) {
+                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st, const long long* bases,
+                          long long capacity_bytes) {
     if (B == 0) return hipSuccess;
-    if (frames && native) return hipErrorInvalidValue;
+    if (frames && native && (!bases || capacity_bytes < 0)) return hipErrorInvalidValue;
+    if (!(frames && native)) bases = nullptr;
     size_t off[3], total;
     measure_scratch_layout(B, capacity, W0, off, total);
     long long* stats = (long long*)((char*)scratch + off[0]);
@@ -717,7 +747,10 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
     else { a.table = (const CameraRow*)table; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
     const EnvSel sel = {a.cam.fabric_id, a.cam.roi_enabled, {a.cam.roi[0], a.cam.roi[1], a.cam.roi[2], a.cam.roi[3]}};
     if (capacity > 0) {
-        if (native) {           // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
+        if (native && frames) { // the ragged frame-size rows: H0, W0 and the words per row of the slot's own frame
+            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false, true, true>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live,
+                               0, 0, 0, 0, stats, (int*)nullptr, offsets, frames, B, bases, capacity_bytes);
+        } else if (native) {    // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
             hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
                                32 * wpr, H0, 32 * wpr, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
         } else {
@@ -736,7 +769,7 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
     if (native)
         hipLaunchKernelGGL(envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets, dets,
                            max_det, 6 + nm, capacity, sel, H0, W0, H0, W0, env, xyxy, wpr, a.table, a.cam_of_frame, a.n_cams,
-                           (const FrameRow*)nullptr);
+                           frames, bases, capacity_bytes);
     else {
         if ((size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
         hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,

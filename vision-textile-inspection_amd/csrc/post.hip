@@ -1312,10 +1312,14 @@ hipError_t launch_masks(int dtype, const float* dets, const int* counts, const v
 //   crop_mask(masks, boxes in frame px): keep x1 <= col < x2, y1 <= row < y2;  threshold > 0 (logit) / > 0.5 (sigmoid)
 // Layout (native_mask_layout): VTI_PACK_BITS u8 [cap, H0, 8 ceil(W0/64)] LSB-first, bits at columns >= W0 are 0;
 // VTI_PACK_U8 u8 [cap, H0, W0].
-int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]) {
+// One place computes them, for the host (the uniform launcher, vti_mask_native_layout) and for the device (the prologue of
+// vti_masks_native_frames computes every frame's values from its H0, W0): the same expressions give the same values, so a frame's
+// bytes do not depend on which call wrote them.
+__host__ __device__ static inline int native_mask_layout_hd(int Hp, int Wp, int H0, int W0, int packing, int out[6]) {
     if (Hp < 1 || Wp < 1 || H0 < 1 || W0 < 1 || (packing != VTI_PACK_U8 && packing != VTI_PACK_BITS)) return -1;
     const double mh = Hp, mw = Wp;
-    const double gain = std::min(mh / H0, mw / W0);
+    const double gh = mh / H0, gw = mw / W0;
+    const double gain = gh < gw ? gh : gw;
     const double pad_w = (mw - W0 * gain) / 2, pad_h = (mh - H0 * gain) / 2;
     const int top = (int)pad_h, left = (int)pad_w, bottom = (int)(mh - pad_h), right = (int)(mw - pad_w);
     if (top < 0 || left < 0 || bottom <= top || right <= left || bottom > Hp || right > Wp) return -1;
@@ -1325,6 +1329,7 @@ int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]) 
     out[0] = top; out[1] = bottom; out[2] = left; out[3] = right; out[4] = (int)row_bytes; out[5] = (int)slot_bytes;
     return 0;
 }
+int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]) { return native_mask_layout_hd(Hp, Wp, H0, W0, packing, out); }
 
 constexpr int NTW = 64;                 // output tile width in frame px: one wave's 64 lanes, 8 bytes of a bit row
 constexpr int NPTS = 512;               // footprint points per tile (the logits of MG instances: MG x NPTS floats of LDS)
@@ -1343,7 +1348,47 @@ struct NativeMaskParams {
     int th;                             // output tile height
     int row_contig, col_contig;         // footprint along the axis: a contiguous prototype range (1) or the two taps of every pixel (0)
     int mode, packing, row_bytes, capacity;
+    // FRAMES form only (vti_masks_native_frames): the prologue's per-frame values and the prefix of the frames' tile counts
+    const struct NativeFrame* nf;       // [B]
+    const int* tile_prefix;             // [B + 1]
 };
+
+// footprint length bound along one axis for `n` output indices at scale s (see native_span), and the cheaper of the two forms
+__host__ __device__ static inline int native_axis(double s, int n, int in, int& contig) {
+    const int reach = (int)floor(s * (n - 1) + 1e-3) + 3;
+    const int span = in < reach ? in : reach;
+    contig = span <= 2 * n ? 1 : 0;
+    return contig ? span : 2 * n;
+}
+
+// What the tile kernel needs of one frame size on an Hp x Wp prototype grid: the cropped grid, torch's fp32 scales in / out, the
+// tallest tile (<= 64 rows) whose footprint fits NPTS points -- 64 rows at the reference call (14 x 14 points), 2 rows when both
+// axes shrink (two taps per pixel: 128 x 4); one row always fits (<= 128 x 2) -- and the slot's layout.  -1: native_mask_layout's.
+struct NativeGeom { int top, left, inH, inW; float sy, sx; int th, row_contig, col_contig, row_bytes, slot_bytes; };
+__host__ __device__ static inline int native_geom(int Hp, int Wp, int H0, int W0, int packing, NativeGeom& g) {
+    int lay[6];
+    if (native_mask_layout_hd(Hp, Wp, H0, W0, packing, lay)) return -1;
+    g.top = lay[0]; g.left = lay[2]; g.inH = lay[1] - lay[0]; g.inW = lay[3] - lay[2];
+    g.sy = (float)g.inH / (float)H0; g.sx = (float)g.inW / (float)W0;          // torch: (float)in / out
+    g.row_bytes = lay[4]; g.slot_bytes = lay[5];
+    const int fw = native_axis(g.sx, NTW, g.inW, g.col_contig);
+    g.th = 1; g.row_contig = 0;
+    for (int th = 64; th >= 1; th >>= 1) {
+        int rc;
+        if (fw * native_axis(g.sy, th, g.inH, rc) <= NPTS) { g.th = th; g.row_contig = rc; break; }
+    }
+    return 0;
+}
+
+// Frame b of vti_masks_native_frames as the prologue leaves it in the workspace: its NativeGeom, its size, its first slot's byte
+// offset (bases[b]) and how many of its instances are live by the byte rule (slot end <= capacity_bytes).
+struct NativeFrame {
+    long long base;
+    int H0, W0, tiles_x, n_live;
+    NativeGeom g;
+    int pad;
+};
+static_assert(sizeof(NativeFrame) % 8 == 0, "NativeFrame rows stay 8-byte aligned");
 
 // torch upsample_bilinear2d (align_corners=False) source taps of output index d: fp32 src = max(s (d + 0.5) - 0.5, 0),
 // i0 = int(src), i1 = min(i0 + 1, in - 1), weight of i1 = src - i0
@@ -1375,9 +1420,7 @@ __device__ __forceinline__ void native_span(int d0, int n, int contig, float s, 
 
 // Zeroes the live slots [0, min(offsets[B], capacity)): one contiguous byte range, so any slot size works (16-byte stores for the
 // aligned body, bytes for the ends).  Slots beyond are not touched.
-__global__ __launch_bounds__(256) void mask_clear_live_kernel(const int* __restrict__ offsets, int B, int capacity, size_t slot_bytes,
-                                                              uint8_t* __restrict__ masks) {
-    const size_t total = (size_t)min(offsets[B], capacity) * slot_bytes;
+__device__ __forceinline__ void mask_clear_range(uint8_t* __restrict__ masks, size_t total) {
     const size_t head = min(total, (size_t)((16u - ((uintptr_t)masks & 15u)) & 15u));
     const size_t nvec = (total - head) >> 4;
     const size_t tail0 = head + nvec * 16;
@@ -1386,6 +1429,61 @@ __global__ __launch_bounds__(256) void mask_clear_live_kernel(const int* __restr
     if (blockIdx.x == 0) {
         if (threadIdx.x < head) masks[threadIdx.x] = 0;
         if (tail0 + threadIdx.x < total) masks[tail0 + threadIdx.x] = 0;
+    }
+}
+__global__ __launch_bounds__(256) void mask_clear_live_kernel(const int* __restrict__ offsets, int B, int capacity, size_t slot_bytes,
+                                                              uint8_t* __restrict__ masks) {
+    mask_clear_range(masks, (size_t)min(offsets[B], capacity) * slot_bytes);
+}
+// The ragged form: [0, *live_end), the end of the last live slot as the prologue found it (<= capacity_bytes).
+__global__ __launch_bounds__(256) void mask_clear_bytes_kernel(const long long* __restrict__ live_end, long long capacity_bytes,
+                                                               uint8_t* __restrict__ masks) {
+    const long long e = *live_end;
+    mask_clear_range(masks, (size_t)(e < 0 ? 0 : (e > capacity_bytes ? capacity_bytes : e)));
+}
+
+// The prologue of vti_masks_native_frames (one workgroup, a thread per frame): mask_offsets_kernel's prefix sums of the clamped
+// counts, and beside them what makes the buffer ragged --
+//   bases[b] = sum over b' < b of clamp(counts[b']) * slot_bytes[b'] (i64, not clipped by the capacity),
+//   nf[b]: frame b's NativeGeom from its H0, W0 (native_geom, the uniform launcher's own function), its first slot's offset and the
+//          number of its instances that are live: instance i is live iff bases[b] + (i + 1) * slot_bytes[b] <= capacity_bytes,
+//   tile_prefix[b]: the prefix sums of the frames' tile counts ceil(W0 / 64) * ceil(H0 / th) (the static work list),
+//   *live_end: the end of the last live slot (the bases are monotone, so the live slots are a prefix of the slot order).
+// A frame whose size native_geom refuses (the host checked every row, so none) gets no tiles and no live slots.
+__global__ __launch_bounds__(256) void mask_frames_plan_kernel(const int* __restrict__ counts, const FrameRow* __restrict__ rows, int B,
+                                                               int max_det, int Hp, int Wp, long long capacity_bytes,
+                                                               int* __restrict__ offsets, long long* __restrict__ bases,
+                                                               int* __restrict__ tile_prefix, NativeFrame* __restrict__ nf,
+                                                               long long* __restrict__ live_end) {
+    extern __shared__ int s_plan[];     // counts [B] | slot bytes [B] | tiles [B]
+    int* s_cnt = s_plan; int* s_slot = s_cnt + B; int* s_til = s_slot + B;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const int c = counts[b];
+        NativeFrame f;
+        f.base = 0; f.H0 = rows[b].H0; f.W0 = rows[b].W0; f.n_live = 0; f.pad = 0;
+        const bool ok = native_geom(Hp, Wp, f.H0, f.W0, VTI_PACK_BITS, f.g) == 0;
+        if (!ok) { f.g = NativeGeom{0, 0, 1, 1, 1.f, 1.f, 1, 0, 0, 0, 0}; f.H0 = f.W0 = 0; }
+        f.tiles_x = (f.W0 + NTW - 1) / NTW;
+        nf[b] = f;
+        s_cnt[b] = c < 0 ? 0 : (c > max_det ? max_det : c);
+        s_slot[b] = f.g.slot_bytes;
+        s_til[b] = ok ? f.tiles_x * ((f.H0 + f.g.th - 1) / f.g.th) : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int off = 0, til = 0;
+        long long base = 0, end = 0;
+        for (int b = 0; b < B; ++b) {
+            offsets[b] = off; bases[b] = base; tile_prefix[b] = til;
+            const long long slot = s_slot[b], room = capacity_bytes - base;
+            const long long fit = slot > 0 && room > 0 ? room / slot : 0;
+            const int live = (int)(fit < s_cnt[b] ? fit : s_cnt[b]);
+            nf[b].base = base; nf[b].n_live = live;
+            if (live > 0) end = base + live * slot;
+            off += s_cnt[b]; base += s_cnt[b] * slot; til += s_til[b];
+        }
+        offsets[B] = off; bases[B] = base; tile_prefix[B] = til;
+        *live_end = end;
     }
 }
 
@@ -1398,7 +1496,7 @@ __global__ __launch_bounds__(256) void mask_clear_live_kernel(const int* __restr
 //      prototypes, the split-coefficient fp16 pair for fp16 ones), (sigmoid,) logits -> LDS,
 //   4. bilinear upsample (torch's fp32 taps and weights, its evaluation order), crop, threshold: a wave takes 16-row pieces of one
 //      instance, a lane is a column; bits: each row's ballot is 8 bytes, gathered into lane r and stored by 16 lanes at once.
-template <typename T>
+template <typename T, bool FRAMES = false>
 __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p) {
     constexpr bool F16 = sizeof(T) == 2;
     constexpr int ROW = 6 + 32;
@@ -1413,23 +1511,41 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
     const T* __restrict__ proto = (const T*)p.proto;
     const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
     const int li = ln & 15, lg = ln >> 4;
-    const int tiles_x = (p.W0 + NTW - 1) / NTW, tiles_y = (p.H0 + p.th - 1) / p.th, tiles = tiles_x * tiles_y;
-    const int n = p.B * tiles;
+    // the frame's geometry: the launch arguments, or (FRAMES) the frame's NativeFrame, read again for every work item
+    int H0 = p.H0, W0 = p.W0, top = p.top, left = p.left, inH = p.inH, inW = p.inW, th = p.th;
+    int row_contig = p.row_contig, col_contig = p.col_contig, row_bytes = p.row_bytes;
+    float sy = p.sy, sx = p.sx;
+    size_t slot_bytes = p.slot_bytes;
+    int tiles_x = (W0 + NTW - 1) / NTW;
+    const int tiles_y = (H0 + th - 1) / th, tiles = tiles_x * tiles_y;
+    const int n = FRAMES ? p.tile_prefix[p.B] : p.B * tiles;
     const int nx = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jx = (int)blockIdx.x >> 3;
     const int per = (n + 7) >> 3;
     const int it1 = min(n, (xcd + 1) * per);
     const float thr = p.mode == VTI_MASK_SIGMOID ? 0.5f : 0.0f;
     for (int it = xcd * per + jx; it < it1; it += nx) {
-        const int b = it / tiles, t = it - b * tiles;
+        int b, t, off_b = 0, n_b;
+        uint8_t* frame_slots = p.masks;                                    // slot 0 of the buffer; FRAMES: the frame's first slot
+        if constexpr (FRAMES) {
+            mask_slot_owner(p.tile_prefix, p.B, it, b, t);                 // the last b with tile_prefix[b] <= it: inside [0, B)
+            const NativeFrame& f = p.nf[b];
+            n_b = f.n_live;
+            if (n_b <= 0) continue;                                        // block-uniform
+            H0 = f.H0; W0 = f.W0; tiles_x = f.tiles_x; frame_slots += f.base;
+            top = f.g.top; left = f.g.left; inH = f.g.inH; inW = f.g.inW; sy = f.g.sy; sx = f.g.sx; th = f.g.th;
+            row_contig = f.g.row_contig; col_contig = f.g.col_contig; row_bytes = f.g.row_bytes; slot_bytes = (size_t)f.g.slot_bytes;
+        } else {
+            b = it / tiles; t = it - b * tiles;
+            off_b = p.offsets[b];
+            n_b = min(p.offsets[b + 1], p.capacity) - off_b;
+            if (n_b <= 0) continue;                                        // block-uniform
+        }
         const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        const int y0 = ty * p.th, x0 = tx * NTW;
-        const int off_b = p.offsets[b];
-        const int n_b = min(p.offsets[b + 1], p.capacity) - off_b;
-        if (n_b <= 0) continue;                                            // block-uniform
-        const int ncols = min(NTW, p.W0 - x0), nrows = min(p.th, p.H0 - y0);
+        const int y0 = ty * th, x0 = tx * NTW;
+        const int ncols = min(NTW, W0 - x0), nrows = min(th, H0 - y0);
         int fcb, fw, frb, fh;
-        native_span(x0, ncols, p.col_contig, p.sx, p.inW, fcb, fw);
-        native_span(y0, nrows, p.row_contig, p.sy, p.inH, frb, fh);
+        native_span(x0, ncols, col_contig, sx, inW, fcb, fw);
+        native_span(y0, nrows, row_contig, sy, inH, frb, fh);
         if (fw * fh > NPTS) fh = NPTS / fw;                                // never (the launcher's bound); keeps `low` in range
         const int npts = fw * fh;
         // ---- footprint -> MFMA operand registers: lane (li, lg) holds point 16 m + li, channels of lane group lg
@@ -1441,8 +1557,8 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
                 int pt = 16 * m + li;
                 pt = pt < npts ? pt : npts - 1;                            // past the footprint: a valid address, never stored
                 const int fr = pt / fw, fc = pt - fr * fw;
-                const int py = p.top + native_src(fr, y0, p.row_contig, frb, p.sy, p.inH);
-                const int px = p.left + native_src(fc, x0, p.col_contig, fcb, p.sx, p.inW);
+                const int py = top + native_src(fr, y0, row_contig, frb, sy, inH);
+                const int px = left + native_src(fc, x0, col_contig, fcb, sx, inW);
                 const T* pp = proto + ((size_t)(b * p.Hp + py) * p.Wp + px) * 32;
                 if constexpr (F16) pb[j][0] = *(const half8*)(pp + 8 * lg);
                 else { pb[j][0] = *(const f32x4*)(pp + 4 * lg); pb[j][1] = *(const f32x4*)(pp + 16 + 4 * lg); }
@@ -1455,8 +1571,8 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
         float wx1;
         {
             int i0, i1;
-            native_tap(xg, p.sx, p.inW, i0, i1, wx1);
-            if (p.col_contig) { k0 = i0 - fcb; k1 = i1 - fcb; }
+            native_tap(xg, sx, inW, i0, i1, wx1);
+            if (col_contig) { k0 = i0 - fcb; k1 = i1 - fcb; }
             else { k0 = 2 * (xg - x0); k1 = k0 + 1; }
         }
         const float wx0 = 1.0f - wx1;
@@ -1466,8 +1582,8 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
         {
             const int yt = y0 + min(ln, nrows - 1);
             int i0, i1;
-            native_tap(yt, p.sy, p.inH, i0, i1, wy1);
-            if (p.row_contig) { ro0 = (i0 - frb) * fw; ro1 = (i1 - frb) * fw; }
+            native_tap(yt, sy, inH, i0, i1, wy1);
+            if (row_contig) { ro0 = (i0 - frb) * fw; ro1 = (i1 - frb) * fw; }
             else { ro0 = 2 * (yt - y0) * fw; ro1 = ro0 + fw; }
         }
         const float wy0 = 1.0f - wy1;
@@ -1532,11 +1648,11 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
                 const int npc = (nrows + 15) >> 4;
                 for (int pr = wv; pr < ng * npc; pr += 4) {
                     const int u = pr / npc, c = pr - u * npc;
-                    const int slot = off_b + i0 + (int)s_list[g0 + u];
+                    const int slot = off_b + i0 + (int)s_list[g0 + u];         // FRAMES: off_b = 0, the instance's index in its frame
                     const float4 bx = s_box[g0 + u];
                     const bool colin = ln < ncols && fx >= bx.x && fx < bx.z;
                     const float* L = &low[u][0];
-                    uint8_t* out = p.masks + (size_t)slot * p.slot_bytes;
+                    uint8_t* out = frame_slots + (size_t)slot * slot_bytes;
                     const int r0 = 16 * c, r1 = min(r0 + 16, nrows);
                     unsigned wl = 0u, wh = 0u;
                     for (int r = r0; r < r1; ++r) {
@@ -1549,15 +1665,15 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
                         // torch's order: h0 (w0 a + w1 b) + h1 (w0 c + w1 d)
                         const float v = h0 * (wx0 * L[o0 + k0] + wx1 * L[o0 + k1]) + h1 * (wx0 * L[o1 + k0] + wx1 * L[o1 + k1]);
                         const bool bit = colin && v > thr;
-                        if (p.packing == VTI_PACK_U8) {
-                            if (ln < ncols) out[(size_t)y * p.W0 + x0 + ln] = bit ? (uint8_t)1 : (uint8_t)0;
+                        if (!FRAMES && p.packing == VTI_PACK_U8) {
+                            if (ln < ncols) out[(size_t)y * W0 + x0 + ln] = bit ? (uint8_t)1 : (uint8_t)0;
                         } else {
                             const unsigned long long m = __builtin_amdgcn_ballot_w64(bit);
                             if (ln == r - r0) { wl = (unsigned)m; wh = (unsigned)(m >> 32); }
                         }
                     }
-                    if (p.packing != VTI_PACK_U8 && ln < r1 - r0)                // lane r: row r0 + r, 8 bytes (row_bytes % 8 == 0)
-                        *(uint2*)(out + (size_t)(y0 + r0 + ln) * p.row_bytes + 8 * tx) = make_uint2(wl, wh);
+                    if ((FRAMES || p.packing != VTI_PACK_U8) && ln < r1 - r0)                // lane r: row r0 + r, 8 bytes (row_bytes % 8 == 0)
+                        *(uint2*)(out + (size_t)(y0 + r0 + ln) * row_bytes + 8 * tx) = make_uint2(wl, wh);
                 }
                 if (g0 + MG < nlist) __syncthreads();                      // the next group overwrites `low`
             }
@@ -1565,35 +1681,22 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
     }
 }
 
-// footprint length bound along one axis for `n` output indices at scale s (see native_span), and the cheaper of the two forms
-static int native_axis(double s, int n, int in, int& contig) {
-    const int span = std::min(in, (int)std::floor(s * (n - 1) + 1e-3) + 3);
-    contig = span <= 2 * n ? 1 : 0;
-    return contig ? span : 2 * n;
-}
-
 hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto, int B, int max_det,
                                int Hp, int Wp, int H0, int W0, int mode, int packing, uint8_t* masks, int capacity, int* offsets,
                                void* ws, hipStream_t st) {
     if (B == 0) return hipSuccess;
-    int lay[6];
-    if (native_mask_layout(Hp, Wp, H0, W0, packing, lay)) return hipErrorInvalidValue;
+    NativeGeom g;
+    if (native_geom(Hp, Wp, H0, W0, packing, g)) return hipErrorInvalidValue;
     if (packing == VTI_PACK_BITS && capacity > 0 && ((uintptr_t)masks & 7)) return hipErrorInvalidValue;     // 8-byte row pieces
     NativeMaskParams p;
     p.dets = dets; p.xyxy = xyxy; p.offsets = offsets; p.proto = proto; p.masks = masks;
-    p.slot_bytes = (size_t)lay[5];
+    p.slot_bytes = (size_t)g.slot_bytes;
     p.B = B; p.max_det = max_det; p.Hp = Hp; p.Wp = Wp; p.H0 = H0; p.W0 = W0;
-    p.top = lay[0]; p.left = lay[2]; p.inH = lay[1] - lay[0]; p.inW = lay[3] - lay[2];
-    p.sy = (float)p.inH / (float)H0; p.sx = (float)p.inW / (float)W0;          // torch: (float)in / out
-    p.mode = mode; p.packing = packing; p.row_bytes = lay[4]; p.capacity = capacity;
-    // the tallest tile (<= 64 rows) whose footprint fits NPTS points: 64 rows at the reference call (14 x 14 points), 2 rows when
-    // both axes shrink (two taps per pixel: 128 x 4); one row always fits (<= 128 x 2)
-    const int fw = native_axis(p.sx, NTW, p.inW, p.col_contig);
-    p.th = 1;
-    for (int th = 64; th >= 1; th >>= 1) {
-        int rc;
-        if (fw * native_axis(p.sy, th, p.inH, rc) <= NPTS) { p.th = th; p.row_contig = rc; break; }
-    }
+    p.top = g.top; p.left = g.left; p.inH = g.inH; p.inW = g.inW;
+    p.sy = g.sy; p.sx = g.sx;
+    p.mode = mode; p.packing = packing; p.row_bytes = g.row_bytes; p.capacity = capacity;
+    p.th = g.th; p.row_contig = g.row_contig; p.col_contig = g.col_contig;
+    p.nf = nullptr; p.tile_prefix = nullptr;
     hipLaunchKernelGGL(mask_offsets_kernel, dim3(1), dim3(256), (size_t)(B + 1) * sizeof(int), st, counts, B, max_det, offsets, (int*)ws);
     if (capacity <= 0) return hipGetLastError();
     const size_t vecs = (size_t)capacity * p.slot_bytes / 16;
@@ -1603,6 +1706,54 @@ hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, 
                                               : resident_per_cu<masks_native_kernel<float>>(256, 2, 4));
     if (dtype == VTI_F16) hipLaunchKernelGGL(masks_native_kernel<half_t>, dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(masks_native_kernel<float>, dim3(grid), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+// vti_masks_native_frames.  host_table: the packed frame table, its rows already validated (frames_check); the worst-case bytes of
+// max_det slots per frame, and the tiles of the static work list (-1: a frame native_mask_layout cannot describe).
+long long native_frames_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles) {
+    FrameTableHeader h;
+    memcpy(&h, host_table, sizeof h);
+    long long bytes = 0, til = 0;
+    for (int b = 0; b < h.B; ++b) {
+        FrameRow r;
+        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+        NativeGeom g;
+        if (native_geom(Hp, Wp, r.H0, r.W0, VTI_PACK_BITS, g)) return -1;
+        bytes += (long long)max_det * g.slot_bytes;
+        til += (long long)((r.W0 + NTW - 1) / NTW) * ((r.H0 + g.th - 1) / g.th);
+    }
+    if (tiles) *tiles = til;
+    return bytes;
+}
+
+size_t masks_native_frames_workspace_bytes(int B) { return 256 + align256((size_t)(B + 1) * sizeof(int)) + (size_t)B * sizeof(NativeFrame); }
+
+hipError_t launch_masks_native_frames(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
+                                      const FrameRow* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
+                                      long long capacity_bytes, int* offsets, long long* bases, void* ws, hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    if (capacity_bytes > 0 && ((uintptr_t)masks & 7)) return hipErrorInvalidValue;                            // 8-byte row pieces
+    // workspace: live_end i64 (256 bytes) | tile_prefix i32 [B + 1] | NativeFrame [B]
+    long long* live_end = (long long*)ws;
+    int* tile_prefix = (int*)((char*)ws + 256);
+    NativeFrame* nf = (NativeFrame*)((char*)ws + 256 + align256((size_t)(B + 1) * sizeof(int)));
+    hipLaunchKernelGGL(mask_frames_plan_kernel, dim3(1), dim3(256), (size_t)3 * B * sizeof(int), st, counts, rows, B, max_det, Hp, Wp,
+                       capacity_bytes, offsets, bases, tile_prefix, nf, live_end);
+    if (capacity_bytes <= 0) return hipGetLastError();
+    NativeMaskParams p;
+    memset(&p, 0, sizeof p);
+    p.dets = dets; p.xyxy = xyxy; p.offsets = offsets; p.proto = proto; p.masks = masks;
+    p.B = B; p.max_det = max_det; p.Hp = Hp; p.Wp = Wp; p.th = 1;
+    p.mode = mode; p.packing = VTI_PACK_BITS;
+    p.nf = nf; p.tile_prefix = tile_prefix;
+    const size_t vecs = (size_t)capacity_bytes / 16;
+    const int clear_grid = (int)std::max<size_t>(1, std::min<size_t>((vecs + 255) / 256, 2048));
+    hipLaunchKernelGGL(mask_clear_bytes_kernel, dim3(clear_grid), dim3(256), 0, st, live_end, capacity_bytes, masks);
+    const int grid = 256 * (dtype == VTI_F16 ? resident_per_cu<masks_native_kernel<half_t, true>>(256, 2, 4)
+                                              : resident_per_cu<masks_native_kernel<float, true>>(256, 2, 4));
+    if (dtype == VTI_F16) hipLaunchKernelGGL((masks_native_kernel<half_t, true>), dim3(grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((masks_native_kernel<float, true>), dim3(grid), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

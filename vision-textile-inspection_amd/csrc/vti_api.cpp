@@ -314,6 +314,25 @@ int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[
     return VTI_OK;
 }
 
+// What is wrong with a packed host table for this ctx (nullptr: nothing): not a table of vti_pack_frames, packed for another B (B < 0:
+// any B >= 1) or another canvas, or a row that no longer passes frame_error (`frame` then receives its index, else -1).  Fails
+// nothing and records nothing: frames_check and the host-only size queries share it.  `h` receives the header.
+static const char* frame_table_problem(const vti_ctx* c, const void* host_table, int32_t B, FrameTableHeader& h, int32_t& frame) {
+    frame = -1;
+    memcpy(&h, host_table, sizeof h);
+    if (h.magic != kFrameTableMagic) return "host_table is not a table of vti_pack_frames";
+    if (h.B < 1 || (B >= 0 && h.B != B)) return "the frame table was packed for another B";
+    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return "the frame table was packed for another canvas (H x W)";
+    for (int32_t b = 0; b < h.B; ++b) {
+        FrameRow r;
+        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+        const char* e = frame_error(h.H, h.W, r.H0, r.W0, r.offset, h.total_bytes);
+        if (!e && (r.H0 > h.max_H0 || r.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
+        if (e) { frame = b; return e; }
+    }
+    return nullptr;
+}
+
 // The checks every *_frames call makes on its table pair before anything else: the host copy is a packed table for this ctx's
 // canvas and this B whose rows still pass frame_error, and the device copy is a 16-byte aligned pointer.  `h` receives the header.
 static int32_t frames_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
@@ -322,19 +341,15 @@ static int32_t frames_check(const char* fn, vti_ctx* c, const void* host_table, 
     if (!c) return VTI_ERR_ARG;
     if (!host_table || !dev_table) return bad("null frame table (host copy or device copy)");
     if ((uintptr_t)dev_table & 15) return bad("the device frame table must be 16-byte aligned");
-    memcpy(&h, host_table, sizeof h);
-    if (h.magic != kFrameTableMagic) return bad("host_table is not a table of vti_pack_frames");
-    if (h.B != B || B < 1) return bad("the frame table was packed for another B");
-    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return bad("the frame table was packed for another canvas (H x W)");
-    for (int32_t b = 0; b < B; ++b) {
-        FrameRow r;
-        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
-        const char* e = frame_error(h.H, h.W, r.H0, r.W0, r.offset, h.total_bytes);
-        if (!e && (r.H0 > h.max_H0 || r.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
-        if (e) {
-            snprintf(msg, sizeof msg, "%s: frame %d of host_table: %s", fn, b, e);
-            return fail(c, VTI_ERR_ARG, msg);
-        }
+    int32_t frame;
+    if (B < 1) {                            // no table is packed for B < 1 (frame_table_problem reads B < 0 as "any B")
+        memcpy(&h, host_table, sizeof h);
+        return bad(h.magic != kFrameTableMagic ? "host_table is not a table of vti_pack_frames" : "the frame table was packed for another B");
+    }
+    if (const char* e = frame_table_problem(c, host_table, B, h, frame)) {
+        if (frame < 0) return bad(e);
+        snprintf(msg, sizeof msg, "%s: frame %d of host_table: %s", fn, frame, e);
+        return fail(c, VTI_ERR_ARG, msg);
     }
     return VTI_OK;
 }
@@ -784,6 +799,24 @@ int32_t vti_predict(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, in
     return VTI_OK;
 }
 
+// vti_predict_frames up to the NMS: the checks on what those stages take, then letterbox -> scored forward -> NMS.
+static int32_t predict_frames_head(const char* fn, vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table,
+                                   int32_t B, int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic,
+                                   uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts, const float* xyxy,
+                                   void* stream) {
+    int32_t rc;
+    if (!frames || !input_scratch || ((uintptr_t)frames & 15) || ((uintptr_t)input_scratch & 3))
+        return fail(c, VTI_ERR_ARG, std::string(fn) + ": dev_frames (16-byte aligned) and dev_input_scratch (4-byte aligned) are required");
+    if (xyxy && (max_det < 1 || ((uintptr_t)xyxy & 15) || !dets || !counts))
+        return fail(c, VTI_ERR_ARG, std::string(fn) + ": bad argument (max_det < 1, null dets / counts or dev_xyxy not 16-byte aligned)");
+    if ((rc = check_ready(c, B, fn))) return rc;
+    const vti_desc& d = c->plan.desc;
+    if ((rc = vti_letterbox_frames(c, frames, host_table, dev_table, B, input_scratch, stream))) return rc;
+    float* best = nms_workspace_best(c->ws + c->act_bytes, d.max_batch, c->plan.num_anchors);
+    if ((rc = vti_forward_scored(c, input_scratch, B, swap_rb, pred, proto, best, stream))) return rc;
+    return vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream);
+}
+
 int32_t vti_predict_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
                            int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
                            int32_t packing, uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts,
@@ -793,19 +826,87 @@ int32_t vti_predict_frames(vti_ctx* c, const uint8_t* frames, const void* host_t
     if (rc) return rc;
     if (mask_mode & VTI_MASK_NATIVE)
         return fail(c, VTI_ERR_UNSUPPORTED, "vti_predict_frames: VTI_MASK_NATIVE needs frames of one size (vti_predict)");
-    if (!frames || !input_scratch || ((uintptr_t)frames & 15) || ((uintptr_t)input_scratch & 3))
-        return fail(c, VTI_ERR_ARG, "vti_predict_frames: dev_frames (16-byte aligned) and dev_input_scratch (4-byte aligned) are required");
-    if (xyxy && (max_det < 1 || ((uintptr_t)xyxy & 15) || !dets || !counts))
-        return fail(c, VTI_ERR_ARG, "vti_predict_frames: bad argument (max_det < 1, null dets / counts or dev_xyxy not 16-byte aligned)");
-    if ((rc = check_ready(c, B, "vti_predict_frames"))) return rc;
-    const vti_desc& d = c->plan.desc;
-    if ((rc = vti_letterbox_frames(c, frames, host_table, dev_table, B, input_scratch, stream))) return rc;
-    float* best = nms_workspace_best(c->ws + c->act_bytes, d.max_batch, c->plan.num_anchors);
-    if ((rc = vti_forward_scored(c, input_scratch, B, swap_rb, pred, proto, best, stream))) return rc;
-    if ((rc = vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream))) return rc;
+    if ((rc = predict_frames_head("vti_predict_frames", c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic,
+                                  input_scratch, pred, proto, dets, counts, xyxy, stream)))
+        return rc;
     if ((rc = vti_masks(c, dets, counts, proto, B, max_det, mask_mode, packing, masks, capacity, offsets, stream))) return rc;
     if (xyxy && (rc = vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
     return VTI_OK;
+}
+
+// ---- frame-resolution masks for frames of differing sizes: the ragged mask buffer ---------------------------------------------
+int64_t vti_mask_native_frames_bytes(const vti_ctx* c, const void* host_table, int32_t max_det) {
+    if (!c || !host_table || max_det < 1) return 0;
+    FrameTableHeader h;
+    int32_t frame;
+    if (frame_table_problem(c, host_table, -1, h, frame) || h.B > c->plan.desc.max_batch) return 0;
+    const long long n = native_frames_bytes(host_table, h.H / 4, h.W / 4, max_det, nullptr);
+    return n < 0 ? 0 : n;
+}
+
+// The argument checks of vti_masks_native_frames (everything but the table, which frames_check has passed).
+static int32_t masks_native_frames_check(const char* fn, vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts,
+                                         const void* proto, const void* host_table, int32_t B, int32_t max_det, int32_t mode,
+                                         int32_t packing, const uint8_t* masks, int64_t capacity_bytes, const int32_t* offsets,
+                                         const int64_t* bases) {
+    char msg[200];
+    auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
+    if (!dets || !xyxy || !counts || !proto || !offsets || !bases || max_det < 1 || capacity_bytes < 0 || (capacity_bytes && !masks))
+        return bad(VTI_ERR_ARG, "bad argument (null pointer, max_det < 1 or capacity_bytes < 0)");
+    if (mode != VTI_MASK_LOGIT && mode != VTI_MASK_SIGMOID) return bad(VTI_ERR_ARG, "bad mode");
+    if (packing == VTI_PACK_U8) return bad(VTI_ERR_UNSUPPORTED, "the ragged mask buffer is bit-packed only (VTI_PACK_BITS)");
+    if (packing != VTI_PACK_BITS) return bad(VTI_ERR_ARG, "bad packing");
+    if (((uintptr_t)masks & 7) || ((uintptr_t)bases & 7) || ((uintptr_t)offsets & 3))
+        return bad(VTI_ERR_ARG, "dev_masks and dev_mask_bases must be 8-byte aligned, dev_offsets 4-byte aligned");
+    const vti_desc& d = c->plan.desc;
+    if (B > d.max_batch) return bad(VTI_ERR_ARG, "B out of range");
+    if (d.nm != 32) return bad(VTI_ERR_UNSUPPORTED, "only nm == 32 prototypes");
+    long long tiles = 0;
+    if (native_frames_bytes(host_table, d.H / 4, d.W / 4, max_det, &tiles) < 0)
+        return bad(VTI_ERR_ARG, "a frame of host_table has no native mask layout (slot below 2 GiB)");
+    if (tiles > INT32_MAX || (int64_t)B * max_det > INT32_MAX) return bad(VTI_ERR_UNSUPPORTED, "too many tiles or slots for one call");
+    return VTI_OK;
+}
+
+int32_t vti_masks_native_frames(vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts, const void* proto,
+                                const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing,
+                                uint8_t* masks, int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, void* stream) {
+    FrameTableHeader h;
+    if (int32_t rc = frames_check("vti_masks_native_frames", c, host_table, dev_table, B, h)) return rc;
+    if (int32_t rc = masks_native_frames_check("vti_masks_native_frames", c, dets, xyxy, counts, proto, host_table, B, max_det, mode, packing,
+                                               masks, capacity_bytes, offsets, mask_bases))
+        return rc;
+    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_masks_native_frames: workspace not set");
+    const vti_desc& d = c->plan.desc;
+    void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
+    if (masks_native_frames_workspace_bytes(B) > masks_workspace_bytes(d.max_batch * kMaskSlotsPerFrame, d.H, d.W))
+        return fail(c, VTI_ERR_NOMEM, "vti_masks_native_frames: workspace too small");
+    if (int32_t drc = check_device(c, "vti_masks_native_frames")) return drc;
+    VTI_HIP(c, launch_masks_native_frames(d.dtype, dets, xyxy, counts, proto, frame_rows(dev_table), B, max_det, d.H / 4, d.W / 4, mode,
+                                          masks, capacity_bytes, offsets, (long long*)mask_bases, mws, (hipStream_t)stream),
+            "native mask kernel (frames)");
+    return VTI_OK;
+}
+
+int32_t vti_predict_frames_native(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                                  int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
+                                  int32_t packing, uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts,
+                                  uint8_t* masks, int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, float* xyxy,
+                                  void* stream) {
+    FrameTableHeader h;
+    int32_t rc = frames_check("vti_predict_frames_native", c, host_table, dev_table, B, h);
+    if (rc) return rc;
+    if (!xyxy) return fail(c, VTI_ERR_ARG, "vti_predict_frames_native: dev_xyxy is required (the masks are cropped to the frame-px boxes)");
+    if (!pred) return fail(c, VTI_ERR_ARG, "vti_predict_frames_native: null dev_pred");
+    if ((rc = masks_native_frames_check("vti_predict_frames_native", c, dets, xyxy, counts, proto, host_table, B, max_det,
+                                        mask_mode & ~VTI_MASK_NATIVE, packing, masks, capacity_bytes, offsets, mask_bases)))
+        return rc;
+    if ((rc = predict_frames_head("vti_predict_frames_native", c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic,
+                                  input_scratch, pred, proto, dets, counts, xyxy, stream)))
+        return rc;
+    if ((rc = vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
+    return vti_masks_native_frames(c, dets, xyxy, counts, proto, host_table, dev_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE, packing,
+                                   masks, capacity_bytes, offsets, mask_bases, stream);
 }
 
 int32_t vti_mask_to_frame(vti_ctx* c, const uint8_t* masks, int32_t n, int32_t H, int32_t W, int32_t H0, int32_t W0,
@@ -889,12 +990,14 @@ static const char* measure_params_error(const vti_measure_params* p) {
 }
 
 // vti_measure / vti_measure_cameras / vti_measure_frames: exactly one of p and (table, cam_of_frame) is given; with `frames` (the rows
-// of a device frame table, already checked against its host copy) H0 and W0 are the table's largest ones.  Every check comes before the first HIP call.
+// of a device frame table, already checked against its host copy) H0 and W0 are the table's largest ones.  `bases` (with frames and
+// native = 1 only, vti_measure_frames_native): the masks are vti_masks_native_frames' ragged rows.  Every check comes before the first HIP call.
 static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params* p, const void* table, int32_t n_cams,
                             const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
                             const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity, int32_t H0,
                             int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
-                            int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr) {
+                            int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr, const int64_t* bases = nullptr,
+                            int64_t capacity_bytes = 0) {
     char msg[200];
     auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
     if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
@@ -902,7 +1005,8 @@ static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params
     if (max_det > VTI_MEASURE_MAX_DET) return bad(VTI_ERR_UNSUPPORTED, "max_det above VTI_MEASURE_MAX_DET");
     if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks)))
         return bad(VTI_ERR_ARG, "null pointer");
-    if (frames && native) return bad(VTI_ERR_UNSUPPORTED, "native masks need frames of one size (vti_measure_cameras)");
+    if (frames && native && !bases) return bad(VTI_ERR_UNSUPPORTED, "native masks need frames of one size (vti_measure_cameras)");
+    if (bases && (capacity_bytes < 0 || ((uintptr_t)bases & 7))) return bad(VTI_ERR_ARG, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
     if (p)
         if (const char* e = measure_params_error(p)) return bad(VTI_ERR_ARG, e);
     if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
@@ -917,7 +1021,8 @@ static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params
     if (int32_t drc = check_device(c, fn)) return drc;
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_measure(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H,
-                              d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure kernels");
+                              d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream,
+                              (const long long*)bases, capacity_bytes), "measure kernels");
     return VTI_OK;
 }
 
@@ -974,6 +1079,26 @@ int32_t vti_measure_frames(vti_ctx* c, const void* cameras, int32_t n_cams, cons
     return measure_impl("vti_measure_frames", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
                         max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
                         frame_rows(dev_table));
+}
+
+int32_t vti_measure_frames_native(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                  const int64_t* mask_bases, int64_t capacity_bytes, const float* dets, const float* xyxy,
+                                  const int32_t* counts, const int32_t* offsets, const void* host_table, const void* dev_table, int32_t B,
+                                  int32_t max_det, int32_t capacity, void* scratch, size_t scratch_bytes, double* frame_f64,
+                                  int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
+    if (!c || !cameras || !cam_of_frame) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: null ctx, camera table or camera index");
+    if (n_cams < 1) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: n_cams must be >= 1");
+    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
+        return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: the camera table must be 16-byte aligned, the index 4-byte aligned");
+    FrameTableHeader h;
+    if (int32_t rc = frames_check("vti_measure_frames_native", c, host_table, dev_table, B, h)) return rc;
+    if (!mask_bases) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: null dev_mask_bases");
+    if (capacity_bytes < 0) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: capacity_bytes must be >= 0");
+    if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
+        return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: a frame of host_table has no native mask layout (slot below 2 GiB)");
+    return measure_impl("vti_measure_frames_native", c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B,
+                        max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
+                        frame_rows(dev_table), mask_bases, capacity_bytes);
 }
 
 static bool poly_sizes_ok(int32_t H, int32_t W, int32_t row_bytes) {

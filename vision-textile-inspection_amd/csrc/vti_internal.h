@@ -287,6 +287,15 @@ int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]);
 hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto, int B, int max_det,
                                int Hp, int Wp, int H0, int W0, int mode, int packing, uint8_t* masks, int capacity, int* offsets,
                                void* ws, hipStream_t st);
+// vti_masks_native_frames: frame b's slots have the layout native_mask_layout(H0[b], W0[b], VTI_PACK_BITS) gives and lie back to back,
+// frame-major, from bases[b] on (i64 [B + 1], written with offsets by the launch's prologue); a slot is live iff it ends at or before
+// capacity_bytes.  rows: the device frame table's rows.  native_frames_bytes (host): the worst case of max_det slots per frame of a
+// packed host table whose rows were validated, and the tiles of the work list; -1 for a frame native_mask_layout cannot describe.
+long long native_frames_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles);
+size_t masks_native_frames_workspace_bytes(int B);
+hipError_t launch_masks_native_frames(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
+                                      const FrameRow* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
+                                      long long capacity_bytes, int* offsets, long long* bases, void* ws, hipStream_t st);
 // table != nullptr: gain, pads and clip bounds of frame b from row b of the device table (H0, W0 unused)
 hipError_t launch_scale_boxes(const float* dets, const int* counts, int B, int max_det, int nm, int H, int W,
                               int H0, int W0, const FrameRow* table, float* xyxy, hipStream_t st);
@@ -311,12 +320,14 @@ void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& 
 size_t measure_camera_row_bytes();
 void measure_pack_camera(const vti_measure_params& p, void* row);
 // p != nullptr: one camera for every frame; else frame b uses row cam_of_frame[b] of the device table (n_cams rows)
-// frames != nullptr (native = 0 only): frame b is H0 x W0 of row b of the device frame table, and the W0 passed here is the largest
-// one (the pitch of the envelope rows in the scratch)
+// frames != nullptr: frame b is H0 x W0 of row b of the device frame table, and the W0 passed here is the largest one (the pitch of
+// the envelope rows in the scratch); with native = 1 the masks are then the ragged rows of vti_masks_native_frames: `bases` (i64
+// [B + 1]) and capacity_bytes are required, and a slot that ends past capacity_bytes is an empty mask
 hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
                           int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
                           int nm, int capacity, int H, int W, int H0, int W0, const FrameRow* frames, void* scratch, double* frame_f64,
-                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st);
+                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st, const long long* bases = nullptr,
+                          long long capacity_bytes = 0);
 
 // polygons.hip: vti_mask_polygons (Results.masks.xy).  The grid is VTI_POLY_WORKGROUPS persistent workgroups, each with its own
 // labelling area of the scratch: parent i32 [R_max] | runs u32 [R_max] | row_start i32 [H+1] | image u64 [H, WW] (only when the

@@ -188,10 +188,21 @@ class Engine:
         return out
 
     def predict_frames_into(self, buf, table, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True,
-                            mask_mode="logit", packing="bits"):
+                            mask_mode="logit", packing="bits", native=False):
         """predict_into for a batch whose frames differ in size: `buf` / `table` as letterbox_frames, `out` from
-        alloc_outputs(table.B, ...).  Masks stay at the canvas size; out["xyxy"] is in each frame's own pixels."""
+        alloc_outputs(table.B, ...).  Masks stay at the canvas size; out["xyxy"] is in each frame's own pixels.
+        native=True (vti_predict_frames_native): frame-resolution masks in the ragged buffer of a set from
+        alloc_outputs(..., native_frames=table) -- any other set is a ValueError before any call."""
+        if native:
+            self._check_ragged(out, table, max_det, "predict_frames_into")
         self._check_frames(table, B=out["counts"].shape[0], buf=buf)
+        if native:
+            check(self._ctx, lib().vti_predict_frames_native(
+                self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
+                int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
+                _ptr(out["dets"]), _ptr(out["counts"]), _ptr(out["masks"]), out["masks"].numel(), _ptr(out["offsets"]),
+                _ptr(out["mask_bases"]), _ptr(out["xyxy"]), _stream()))
+            return out
         check(self._ctx, lib().vti_predict_frames(
             self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
             int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
@@ -296,6 +307,56 @@ class Engine:
                                                 _ptr(masks) if capacity else C.c_void_p(0), capacity, _ptr(offsets), _stream()))
         return masks, offsets
 
+    # ---- retina_masks for frames of differing sizes: the ragged mask buffer (vti_masks_native_frames) ----------------------
+    def mask_native_frames_bytes(self, table, max_det):
+        """Host only: the bytes of max_det frame-resolution slots for every frame of `table` (the worst case of the ragged buffer)."""
+        self._check_frames(table)
+        return int(lib().vti_mask_native_frames_bytes(self._ctx, C.c_void_p(table.host.data_ptr()), int(max_det)))
+
+    def _check_ragged(self, out, table, max_det, who):
+        """`out` is a ragged output set (alloc_outputs(native_frames=)) made for the shapes of `table`."""
+        if not isinstance(out, dict) or "mask_bases" not in out or out["masks"].dim() != 1:
+            raise ValueError(f"{who}: native masks for frames of differing sizes need alloc_outputs(..., native_frames=table)")
+        if isinstance(table, FrameTable) and out.get("native_shapes") != tuple(table.shapes):
+            raise ValueError(f"{who}: the output set was allocated for other frame shapes than the table's")
+
+    def masks_native_frames(self, dets, counts, xyxy, proto, table, mode="logit", masks=None, capacity_bytes=None, offsets=None,
+                            mask_bases=None):
+        """masks_native for a batch whose frames differ in size (xyxy from scale_boxes(frames=table)) -> (masks flat u8,
+        offsets i32 [B+1], mask_bases i64 [B+1]): instance i of frame b is H0[b] rows of 8*ceil(W0[b]/64) bytes from byte
+        mask_bases[b] + i * slot_bytes[b] on (frame_masks() cuts the views).  capacity_bytes=None: all of `masks`, or, when that is
+        None too, the counts are read back first to size the buffer exactly."""
+        B, max_det = dets.shape[0], dets.shape[1]
+        self._check_frames(table, B=B)
+        if masks is None:
+            if capacity_bytes is None:
+                cnt = counts.clamp(0, max_det).cpu().tolist()
+                capacity_bytes = sum(n * self.mask_native_layout(h, w)["slot_bytes"] for n, (h, w) in zip(cnt, table.shapes))
+            masks = torch.empty(int(capacity_bytes), dtype=torch.uint8, device=dets.device)
+        elif masks.dtype != torch.uint8 or masks.dim() != 1 or not masks.is_contiguous():
+            raise ValueError("masks_native_frames: masks must be a flat contiguous uint8 tensor")
+        if capacity_bytes is None:
+            capacity_bytes = masks.numel()
+        if not 0 <= int(capacity_bytes) <= masks.numel():
+            raise ValueError(f"masks_native_frames: capacity_bytes must be in [0, {masks.numel()}]")
+        if offsets is None:
+            offsets = torch.empty((B + 1,), dtype=torch.int32, device=dets.device)
+        if mask_bases is None:
+            mask_bases = torch.empty((B + 1,), dtype=torch.int64, device=dets.device)
+        check(self._ctx, lib().vti_masks_native_frames(self._ctx, _ptr(dets), _ptr(xyxy), _ptr(counts), _ptr(proto), *table._ptrs(), B,
+                                                       max_det, MASK_MODES[mode], PACKINGS["bits"],
+                                                       _ptr(masks) if int(capacity_bytes) else C.c_void_p(0), int(capacity_bytes),
+                                                       _ptr(offsets), _ptr(mask_bases), _stream()))
+        return masks, offsets, mask_bases
+
+    def frame_masks(self, masks, table, b, base, n):
+        """The view u8 [n, H0[b], row_bytes[b]] of frame b's first n slots in a ragged buffer; `base` = mask_bases[b] (host int).
+        n is cut to the slots that end inside the buffer."""
+        H0, W0 = table.shapes[b]
+        lay = self.mask_native_layout(H0, W0)
+        n = max(0, min(int(n), (masks.numel() - int(base)) // lay["slot_bytes"]))
+        return masks[int(base):int(base) + n * lay["slot_bytes"]].view(n, H0, lay["row_bytes"])
+
     def scale_boxes(self, dets, counts, H0=None, W0=None, xyxy=None, frames=None):
         """frames: a FrameTable (pack_frames) -- every frame is mapped back with its own gain, pads and bounds; else one H0 x W0."""
         B, max_det = dets.shape[0], dets.shape[1]
@@ -310,10 +371,24 @@ class Engine:
         check(self._ctx, lib().vti_scale_boxes(self._ctx, _ptr(dets), _ptr(counts), B, max_det, H0, W0, _ptr(xyxy), _stream()))
         return xyxy
 
-    def alloc_outputs(self, B, max_det, capacity, packing="bits", device=None, native_hw=None):
+    def alloc_outputs(self, B, max_det, capacity, packing="bits", device=None, native_hw=None, native_frames=None):
         """Preallocated output set for predict_into (the no-sync, graph-friendly form).  native_hw=(H0, W0): the masks are
-        frame-resolution ones for predict_into(native=True) (mask_native_layout)."""
+        frame-resolution ones for predict_into(native=True) (mask_native_layout).  native_frames=FrameTable: the ragged set of
+        predict_frames_into(native=True) -- `masks` is the flat u8 buffer of mask_native_frames_bytes(table, max_det) bytes and
+        `mask_bases` i64 [B+1] comes with it; `capacity` is not used (the per-slot rows of measure() are B * max_det)."""
         dev = device or self.device
+        if native_frames is not None:
+            if native_hw is not None or packing != "bits":
+                raise ValueError("alloc_outputs: native_frames excludes native_hw and is bit-packed only")
+            self._check_frames(native_frames, B=B)
+            nbytes = self.mask_native_frames_bytes(native_frames, max_det)
+            if nbytes <= 0:
+                raise ValueError("alloc_outputs: the frame table has no native mask layout for this engine")
+            o = self.alloc_outputs(B, max_det, 0, "bits", dev)
+            o["masks"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            o["mask_bases"] = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+            o["native_shapes"] = tuple(native_frames.shapes)
+            return o
         if native_hw is None:
             mh, wb = self.H, (self.W if packing == "u8" else self.W // 8)
         else:
@@ -421,14 +496,23 @@ class Engine:
         index is outside the table reports status VTI_MEASURE_BAD_CAMERA) or a host sequence (range-checked here, ValueError); then
         `params` is the table of pack_cameras() or a list of MeasureParams (packed and uploaded on every call: pack once instead).
         frames (vti_measure_frames): a FrameTable (pack_frames) in place of H0, W0 -- frame b is measured at its own size; letterbox
-        bit masks only (native=True is a ValueError).  Without `cameras` the one `params` serves every frame."""
+        bit masks, or with native=True the ragged frame-size rows of a set from alloc_outputs(native_frames=) that
+        predict_frames_into(native=True) filled (vti_measure_frames_native; native=True with any other set is a ValueError).
+        Without `cameras` the one `params` serves every frame."""
         dets, masks = out["dets"], out["masks"]
         B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
         dev = dets.device
+        ragged = frames is not None and native and "mask_bases" in out
         if frames is not None:
             self._check_frames(frames, B=B)
-            if native:
-                raise ValueError("measure: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
+            if native and not ragged:
+                raise ValueError("measure: frames of differing sizes have letterbox masks only (native=True needs one frame size, "
+                                 "or the ragged set of alloc_outputs(native_frames=))")
+            if ragged:
+                self._check_ragged(out, frames, max_det, "measure")
+                if not (dets.is_cuda and masks.is_cuda and out["mask_bases"].is_cuda):
+                    raise ValueError("measure: the output set must be in device memory")
+                capacity = B * max_det
             if H0 is not None or W0 is not None:
                 raise ValueError("measure: give H0, W0 or frames, not both")
             H0, W0 = frames.max_H0, frames.max_W0
@@ -473,7 +557,11 @@ class Engine:
         tail = (_ptr(ws), ws.numel(), _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")),
                 _stream())
         rest = head + (B, max_det, capacity, int(H0), int(W0)) + tail
-        if frames is not None:
+        if ragged:
+            check(self._ctx, lib().vti_measure_frames_native(
+                self._ctx, _ptr(table), n_cams, _ptr(cameras), _ptr(masks), _ptr(out["mask_bases"]), masks.numel(), *head[2:],
+                *frames._ptrs(), B, max_det, capacity, *tail))
+        elif frames is not None:
             check(self._ctx, lib().vti_measure_frames(self._ctx, _ptr(table), n_cams, _ptr(cameras), *head, *frames._ptrs(), B, max_det,
                                                       capacity, *tail))
         elif cameras is not None:

@@ -169,10 +169,10 @@ class _DeviceStage:
             if annotate is not None and not mixed:
                 raise ValueError("process_frames: annotate needs frames of one size; the frames of this list differ in shape "
                                  "(vti_annotate has no frame-table form)")
-            if retina_masks:
+            if retina_masks and (annotate is not None or not mixed):     # mixed + retina_masks measures, but has nothing to draw from
                 raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
             eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False,
-                                                                  keep_frames=annotate is not None)
+                                                                  keep_frames=annotate is not None, retina_masks=bool(retina_masks))
             B, H0, W0 = len(shapes), None, None
         else:
             eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks,
@@ -282,8 +282,9 @@ class StitchMeasurer(_DeviceStage):
         mixed (keyword only, default False): True lets a LIST of frames whose sizes differ (ndarrays or JPEG files) be combined with
         annotate and encode: every selected frame is drawn (vti_annotate_frames) and encoded (vti_encode_jpeg_frames) at its own
         size, a picture is the [H0, W0, 3] ndarray of its frame, and text_items are placed by each frame's own height.  Without it
-        such a list with annotate is refused, as before; on frames of one size it changes nothing.  retina_masks=True with
-        differing sizes stays refused."""
+        such a list with annotate is refused, as before; on frames of one size it changes nothing.  mixed=True also lets
+        retina_masks=True measure such a list (vti_predict_frames_native -> vti_measure_frames_native: every frame's masks at its own
+        size); without mixed, or together with annotate, retina_masks=True with differing sizes stays refused."""
 
     def _process_frames(self, frames, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed):
         got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed)

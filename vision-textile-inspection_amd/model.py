@@ -251,12 +251,14 @@ class YOLO:
                 raise ValueError(f"every frame of a list source must be uint8 HxWx3, got shape {x}")
         return [x[:2] for x in shapes]
 
-    def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, keep_frames=False):
+    def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, keep_frames=False,
+                                retina_masks=False):
         """_predict_outputs for frames of differing sizes: the frames are flattened into one pinned staging buffer, copied with one
         asynchronous H2D and run through one vti_predict_frames on the stride-rounded imgsz canvas.  The packed frame table, the
         staging buffer and its device twin are cached per (engine, shapes).  -> (engine, output set, FrameTable, (H, W)).
         keep_frames: as _predict_outputs -- the flat device buffer this predict consumed stays in _last_frames for a caller that
-        draws on it."""
+        draws on it.  retina_masks: vti_predict_frames_native into the ragged output set (Engine.alloc_outputs(native_frames=)),
+        cached per (engine, B, max_det, shapes) as the uniform retina set is per native_hw."""
         new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
         H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
         B = len(shapes)
@@ -280,12 +282,12 @@ class YOLO:
                     raise ValueError(f"every frame of a list source must be uint8 HxWx3, got {a.dtype}")
                 flat[off:off + 3 * h * w] = a.reshape(-1)
             buf.copy_(stage, non_blocking=True)
-        okey = (id(eng), B, max_det, None)
+        okey = (id(eng), B, max_det, tuple(shapes) if retina_masks else None)
         o = self._outs.get(okey)
         if o is None:
             self._outs.clear()
-            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev)
-        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits")
+            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=table if retina_masks else None)
+        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks))
         if keep_frames:
             self._last_frames = buf
         return eng, o, table, (H, W)
@@ -318,27 +320,35 @@ class YOLO:
 
     @torch.inference_mode()
     def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
-                agnostic_nms=False, swap_rb=True, retina_masks=False, **_ignored):
+                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, **_ignored):
         """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
         ndarray sources.  retina_masks=True: masks at the frame size, Ultralytics'
         process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes.
         A list / tuple of frames whose shapes differ is one batch too (vti_predict_frames): as Ultralytics does for such a list,
         every frame is letterboxed by its own gain onto one stride-rounded imgsz canvas (LetterBox(auto=False)); boxes and
-        masks.xy come back in each frame's own pixels, masks.data at the canvas size.  retina_masks is a ValueError there.
+        masks.xy come back in each frame's own pixels, masks.data at the canvas size.  retina_masks is a ValueError there unless
+        mixed=True (keyword only, True or False) asks for it: then every frame's masks are made at that frame's own size
+        (vti_predict_frames_native, the ragged mask buffer) and masks.data is [n, H0, W0] per frame, as Ultralytics returns for such
+        a list.  On frames of one size, or without retina_masks, mixed changes nothing.
         JPEG sources -- bytes, a path (str / os.PathLike) or a list / tuple of these -- are decoded on the device
         (Engine.decode_jpeg); as with Ultralytics' file sources the network sees the file's R, G, B, so swap_rb does not apply to
         them.  orig_shape comes from the file's header; a refused file raises before any launch, a damaged one after the call."""
+        if not isinstance(mixed, (bool, np.bool_)):
+            raise ValueError(f"predict: mixed must be True or False, got {mixed!r}")
         files = self._jpeg_files(source)
         info = None
         if files is not None:
             source, info = self._decode_jpeg(files, rgb=True)
             swap_rb = False
         shapes = self._differing_shapes(source)
+        ragged = False
         if shapes is not None:
-            if retina_masks:
+            if retina_masks and not mixed:
                 raise ValueError("predict: retina_masks=True needs frames of one size; the frames of this list differ in shape "
                                  "(frame-resolution masks for mixed sizes are not supported)")
-            eng, o, table, (H, W) = self._predict_outputs_frames(source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb)
+            ragged = bool(retina_masks)
+            eng, o, table, (H, W) = self._predict_outputs_frames(source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb,
+                                                                  retina_masks=ragged)
             B = len(shapes)
         else:
             eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
@@ -350,7 +360,8 @@ class YOLO:
             nonempty = eng.mask_stats_bits(masks, H, W, offsets=o["offsets"])[:, 0] > 0
         cnt = o["counts"].cpu().tolist()
         off = o["offsets"].cpu().tolist()
-        if self.drop_empty_masks and retina_masks:         # native rows: pad bits are 0, so any set byte of a live slot is a pixel
+        bases = o["mask_bases"].cpu().tolist() if ragged else None
+        if self.drop_empty_masks and retina_masks and not ragged:     # native rows: pad bits are 0, so any set byte of a live slot is a pixel
             live = min(off[-1], masks.shape[0])
             nonempty = masks[:live].reshape(live, -1).amax(1) > 0
         out = []
@@ -358,9 +369,16 @@ class YOLO:
             H0, W0 = shapes[b]
             n = cnt[b]
             data = torch.cat((xyxy[b, :n], dets[b, :n, 4:6]), 1)
-            mb, db = masks[off[b]:off[b] + n], dets[b, :n]
-            if nonempty is not None and n:
-                keep = nonempty[off[b]:off[b] + n]
+            keep = None
+            if ragged:                                     # the frame's own rows: a view [n, H0, row_bytes] of the flat buffer
+                mb, db = eng.frame_masks(masks, table, b, bases[b], n), dets[b, :n]
+                if self.drop_empty_masks and n:            # the same "any set byte" rule, per frame
+                    keep = mb.reshape(n, -1).amax(1) > 0
+            else:
+                mb, db = masks[off[b]:off[b] + n], dets[b, :n]
+                if nonempty is not None and n:
+                    keep = nonempty[off[b]:off[b] + n]
+            if keep is not None:
                 data, mb, db = data[keep], mb[keep], db[keep]
                 n = int(data.shape[0])
             else:
