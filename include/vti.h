@@ -574,6 +574,51 @@ enum { VTI_JPEG_CORRUPT = 1 };
 int32_t vti_decode_jpeg(vti_ctx* ctx, const uint8_t* dev_files, const void* host_table, const void* dev_table, int32_t n, int32_t rgb,
                         uint8_t* dev_out, int64_t out_bytes, int32_t* dev_info, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- raw camera frames -> frames on device (cap.read() of a V4L2 camera that delivers YUV; CSI cameras, hardware decoders) ------- */
+/* With cap.set(cv2.CAP_PROP_CONVERT_RGB, 0) cap.read() returns the camera's raw buffer instead of cvtColor(COLOR_YUV2BGR_*) of it; this
+ * call is that conversion on the device, byte for byte the package's rawframes.to_bgr, which restates OpenCV 4.x's color_yuv.simd.hpp
+ * (BT.601, limited range, 20-bit fixed point):
+ *   u' = U - 128, v' = V - 128;  ruv = 2^19 + 1673527 v';  guv = 2^19 - 852492 v' - 409993 u';  buv = 2^19 + 2116026 u'
+ *   y' = max(0, Y - 16) * 1220542;  R = clamp((y' + ruv) >> 20), G = clamp((y' + guv) >> 20), B = clamp((y' + buv) >> 20)
+ * (arithmetic shift, clamp to 0..255).  Chroma is replicated, never interpolated: one (U, V) serves a horizontal pixel pair in 4:2:2
+ * and a 2 x 2 block in 4:2:0.  Frames are tightly packed (no line padding; the caller compacts padded rows):
+ *   VTI_RAW_YUYV  2*H0*W0 bytes   per pixel pair Y0 U Y1 V                           COLOR_YUV2BGR_YUYV
+ *   VTI_RAW_UYVY  2*H0*W0         U Y0 V Y1                                          COLOR_YUV2BGR_UYVY
+ *   VTI_RAW_NV12  H0*W0*3/2       Y plane, then interleaved U V (H0/2 x W0/2 pairs)  COLOR_YUV2BGR_NV12
+ *   VTI_RAW_NV21  H0*W0*3/2       Y plane, then interleaved V U                      COLOR_YUV2BGR_NV21
+ *   VTI_RAW_I420  H0*W0*3/2       Y plane, U plane, V plane                          COLOR_YUV2BGR_I420
+ *   VTI_RAW_YV12  H0*W0*3/2       Y plane, V plane, U plane                          COLOR_YUV2BGR_YV12
+ * W0 even; H0 even too for the 4:2:0 formats; 2 <= H0, W0 <= 8192.  Every byte string of the right length is a frame. */
+enum { VTI_RAW_YUYV = 0, VTI_RAW_UYVY, VTI_RAW_NV12, VTI_RAW_NV21, VTI_RAW_I420, VTI_RAW_YV12 };
+/* Host only: bytes of one frame; 0 on a bad argument (unknown fmt, a size outside the rules above). */
+int64_t vti_raw_frame_bytes(int32_t fmt, int32_t H0, int32_t W0);
+/* B frames of one size and format, frame b at dev_raw + b * vti_raw_frame_bytes() -> dev_frames u8 [B,H0,W0,3]; rgb 0: B, G, R as
+ * cap.read() gives them, 1: R, G, B.  dev_raw and dev_frames may be any byte address (accesses at multiples of their size are 8-
+ * or 16-byte vector accesses, the others go byte by byte, both exact); dev_raw is never written, every byte of dev_frames is and no
+ * other.  1 <= B <= 4096.  Every argument check (VTI_ERR_ARG) runs before the first HIP call; ctx, device and weights rules as
+ * vti_decode_jpeg (no weights needed).  One launch on `stream`, no scratch, no memset, no host synchronisation. */
+int32_t vti_convert_raw(vti_ctx* ctx, const uint8_t* dev_raw, int32_t fmt, int32_t B, int32_t H0, int32_t W0, int32_t rgb,
+                        uint8_t* dev_frames, void* stream);
+/* Frames that differ in size and / or format: the raw table.  Host only: bytes of a table of n frames (0 when n < 1 or n > 4096). */
+int64_t vti_raw_table_bytes(int32_t n);
+/* Host only: validates the n frames (the first failing index and the reason are in vti_last_error; ctx only receives the text and may
+ * be NULL), places them back to back, each at a multiple of 16 bytes, and writes the table (nbytes >= vti_raw_table_bytes(n); its
+ * format is private to the library build).  out_raw_offsets [n+1]: frame k's first byte in the raw buffer; [n] is the buffer's size. */
+int32_t vti_pack_raw_frames(vti_ctx* ctx, const int32_t* H0, const int32_t* W0, const int32_t* fmt, int32_t n, void* host_raw_table,
+                            size_t nbytes, int64_t* out_raw_offsets);
+/* dev_raw (raw_bytes >= out_raw_offsets[n] bytes): the raw frames at the table's offsets; never written.  host_raw_table /
+ * dev_raw_table: the bytes vti_pack_raw_frames wrote and their device copy (16-byte aligned, trusted to hold the same bytes).  The
+ * OUTPUT places come from a frame table (vti_pack_frames) of the same n frames: frame b is written as u8 [H0[b],W0[b],3] at its
+ * byte_offset[b], so (dev_out, frame table) feeds vti_predict_frames, vti_annotate_frames and vti_encode_jpeg_frames as it is.
+ * Checked on the host before the first HIP call (VTI_ERR_ARG, vti_last_error names the row): the frame table as by every *_frames
+ * call, every row of the raw table again (format, size, length, offsets ascending without overlap at multiples of 16, inside the
+ * table's raw_bytes), row b of both tables having the same H0 x W0, raw_bytes, and out_bytes >= the frame table's total_bytes.
+ * Every byte of each frame is written and no other: not the gaps between frames.  One launch on `stream`: a grid as large as the
+ * biggest frame needs, times n; a workgroup past its own frame's extent leaves at once. */
+int32_t vti_convert_raw_frames(vti_ctx* ctx, const uint8_t* dev_raw, int64_t raw_bytes, const void* host_raw_table,
+                               const void* dev_raw_table, const void* host_frame_table, const void* dev_frame_table, int32_t n,
+                               int32_t rgb, uint8_t* dev_out, int64_t out_bytes, void* stream);
+
 /* ---- per-layer access for parity tests ------------------------------------------- */
 /* Copies the activation written by conv `i` of the last vti_forward into dev_out as
  * f32 NCHW [B,c2,h_out,w_out] (test hook; not on the hot path). */

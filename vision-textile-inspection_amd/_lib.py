@@ -45,6 +45,7 @@ VTI_POLY_LARGEST, VTI_POLY_CONCAT = 0, 1
 VTI_POLY_OK, VTI_POLY_ERR_BOUND, VTI_POLY_ERR_RANGE = 0, 1, 2
 VTI_ANNOTATE_OUTLINE_SKIPPED = 1
 VTI_JPEG_CORRUPT = 1
+VTI_RAW_YUYV, VTI_RAW_UYVY, VTI_RAW_NV12, VTI_RAW_NV21, VTI_RAW_I420, VTI_RAW_YV12 = range(6)
 VTI_ERR_ARG, VTI_ERR_UNSUPPORTED = -1, -6
 
 
@@ -130,6 +131,11 @@ SIGNATURES = {
     "vti_decode_jpeg_table_bytes": (_I64, [_I32]),
     "vti_decode_jpeg_plan": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     "vti_decode_jpeg": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),
+    "vti_raw_frame_bytes": (_I64, [_I32, _I32, _I32]),
+    "vti_convert_raw": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "vti_raw_table_bytes": (_I64, [_I32]),
+    "vti_pack_raw_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _SZ, _P]),
+    "vti_convert_raw_frames": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _I64, _P]),
     "vti_debug_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),
     "vti_debug_conv2d": (_I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32,
                                 _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,

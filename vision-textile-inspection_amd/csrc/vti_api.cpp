@@ -13,6 +13,7 @@
 #include <new>
 
 #include "vti_internal.h"
+#include "rawframes_dev.h"
 
 using namespace vti;
 
@@ -1442,6 +1443,105 @@ int32_t vti_decode_jpeg(vti_ctx* c, const uint8_t* files, const void* host_table
     }
     if (int32_t drc = check_device(c, "vti_decode_jpeg")) return drc;
     VTI_HIP(c, launch_decode_jpeg(files, host_table, dev_table, n, rgb, out, info, scratch, (hipStream_t)stream), "decode_jpeg kernels");
+    return VTI_OK;
+}
+
+// ---- raw camera frames -> BGR / RGB ----------------------------------------------------------------------------------------------
+int64_t vti_raw_frame_bytes(int32_t fmt, int32_t H0, int32_t W0) { return raw::frame_bytes(fmt, H0, W0); }
+
+static const char* raw_frame_error(int32_t fmt, int32_t H0, int32_t W0) {
+    if (fmt < 0 || fmt >= kRawFormats) return "fmt must be one of VTI_RAW_YUYV .. VTI_RAW_YV12";
+    if (H0 < 2 || W0 < 2 || H0 > kRawMaxSide || W0 > kRawMaxSide) return "H0 and W0 must be in 2..8192";
+    if (W0 & 1) return "W0 must be even";
+    if (raw::fmt_420(fmt) && (H0 & 1)) return "H0 must be even for a 4:2:0 format";
+    return nullptr;
+}
+
+int32_t vti_convert_raw(vti_ctx* c, const uint8_t* raw_buf, int32_t fmt, int32_t B, int32_t H0, int32_t W0, int32_t rgb, uint8_t* frames,
+                        void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const std::string& what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_convert_raw: null ctx");
+    if (const char* e = raw_frame_error(fmt, H0, W0)) return bad(std::string("vti_convert_raw: ") + e);
+    if (B < 1 || B > kRawMaxFrames) return bad("vti_convert_raw: 1 <= B <= 4096");
+    if (rgb != 0 && rgb != 1) return bad("vti_convert_raw: rgb 0 or 1");
+    if (!raw_buf || !frames) return bad("vti_convert_raw: null pointer");
+    if (int32_t drc = check_device(c, "vti_convert_raw")) return drc;
+    VTI_HIP(c, launch_convert_raw(raw_buf, fmt, B, H0, W0, rgb, frames, (hipStream_t)stream), "convert_raw kernel");
+    return VTI_OK;
+}
+
+int64_t vti_raw_table_bytes(int32_t n) {
+    return n < 1 || n > kRawMaxFrames ? 0 : (int64_t)sizeof(RawTableHeader) + (int64_t)n * (int64_t)sizeof(RawRow);
+}
+
+int32_t vti_pack_raw_frames(vti_ctx* c, const int32_t* H0, const int32_t* W0, const int32_t* fmt, int32_t n, void* host_raw_table,
+                            size_t nbytes, int64_t* out_raw_offsets) {
+    auto bad = [&](const std::string& what) { return fail(c, VTI_ERR_ARG, what); };
+    if (n < 1 || n > kRawMaxFrames) return bad("vti_pack_raw_frames: 1 <= n <= 4096");
+    if (!H0 || !W0 || !fmt || !host_raw_table || !out_raw_offsets) return bad("vti_pack_raw_frames: null pointer");
+    if ((int64_t)nbytes < vti_raw_table_bytes(n)) return bad("vti_pack_raw_frames: table smaller than vti_raw_table_bytes()");
+    for (int32_t k = 0; k < n; ++k)
+        if (const char* e = raw_frame_error(fmt[k], H0[k], W0[k]))
+            return bad("vti_pack_raw_frames: frame " + std::to_string(k) + ": " + e);
+    long long at = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        RawRow r;
+        memset(&r, 0, sizeof r);
+        r.raw_off = at;
+        r.raw_len = raw::frame_bytes(fmt[k], H0[k], W0[k]);
+        r.H0 = H0[k]; r.W0 = W0[k]; r.fmt = fmt[k];
+        memcpy((char*)host_raw_table + sizeof(RawTableHeader) + (size_t)k * sizeof r, &r, sizeof r);
+        out_raw_offsets[k] = at;
+        at = (at + r.raw_len + 15) & ~15LL;
+    }
+    out_raw_offsets[n] = at;
+    RawTableHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = kRawTableMagic; h.n = n; h.raw_bytes = at;
+    memcpy(host_raw_table, &h, sizeof h);
+    return VTI_OK;
+}
+
+int32_t vti_convert_raw_frames(vti_ctx* c, const uint8_t* raw_buf, int64_t raw_bytes, const void* host_raw_table, const void* dev_raw_table,
+                               const void* host_frame_table, const void* dev_frame_table, int32_t n, int32_t rgb, uint8_t* out,
+                               int64_t out_bytes, void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const std::string& what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_convert_raw_frames: null ctx");
+    if (n < 1 || n > kRawMaxFrames) return bad("vti_convert_raw_frames: 1 <= n <= 4096");
+    if (rgb != 0 && rgb != 1) return bad("vti_convert_raw_frames: rgb 0 or 1");
+    if (!raw_buf || !host_raw_table || !dev_raw_table || !out) return bad("vti_convert_raw_frames: null pointer");
+    if ((uintptr_t)dev_raw_table & 15) return bad("vti_convert_raw_frames: dev_raw_table must be 16-byte aligned");
+    FrameTableHeader fh;
+    if (int32_t rc = frames_check("vti_convert_raw_frames", c, host_frame_table, dev_frame_table, n, fh)) return rc;
+    RawTableHeader h;
+    memcpy(&h, host_raw_table, sizeof h);
+    if (h.magic != kRawTableMagic || h.n != n || h.raw_bytes < 0)
+        return bad("vti_convert_raw_frames: host_raw_table is not a table of vti_pack_raw_frames for n frames");
+    if (raw_bytes < h.raw_bytes) return bad("vti_convert_raw_frames: raw_bytes smaller than out_raw_offsets[n]");
+    if (out_bytes < fh.total_bytes) return bad("vti_convert_raw_frames: out_bytes smaller than the frame table's total_bytes");
+    long long at = 0;
+    int max_items = 1;
+    for (int32_t b = 0; b < n; ++b) {
+        RawRow r;
+        memcpy(&r, (const char*)host_raw_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+        const char* e = raw_frame_error(r.fmt, r.H0, r.W0);
+        if (!e && r.raw_len != raw::frame_bytes(r.fmt, r.H0, r.W0)) e = "raw_len is not the frame's size";
+        if (!e && (r.raw_off < at || (r.raw_off & 15))) e = "raw offsets must ascend without overlap, each a multiple of 16";
+        if (!e && (r.raw_off > h.raw_bytes || r.raw_len > h.raw_bytes - r.raw_off)) e = "the raw frame runs past the table's raw_bytes";
+        if (e) return bad("vti_convert_raw_frames: row " + std::to_string(b) + " of host_raw_table is invalid (" + e + ")");
+        FrameRow f;
+        memcpy(&f, (const char*)host_frame_table + sizeof fh + (size_t)b * sizeof f, sizeof f);
+        if (f.H0 != r.H0 || f.W0 != r.W0)
+            return bad("vti_convert_raw_frames: frame " + std::to_string(b) + ": the raw table says " + std::to_string(r.H0) + "x" +
+                       std::to_string(r.W0) + ", the frame table " + std::to_string(f.H0) + "x" + std::to_string(f.W0));
+        at = r.raw_off + r.raw_len;
+        max_items = std::max(max_items, raw::items_of(r.fmt, r.H0, r.W0));
+    }
+    if (int32_t drc = check_device(c, "vti_convert_raw_frames")) return drc;
+    VTI_HIP(c, launch_convert_raw_frames(raw_buf, dev_raw_table, frame_rows(dev_frame_table), n, max_items, rgb, out, (hipStream_t)stream),
+            "convert_raw_frames kernel");
     return VTI_OK;
 }
 

@@ -407,6 +407,12 @@ bool decode_jpeg_row_ok(const JpegDecRow& R, const JpegDecHeader& H, size_t& scr
 hipError_t launch_decode_jpeg(const uint8_t* files, const void* host_table, const void* dev_table, int n, int rgb, uint8_t* out, int* info,
                               void* scratch, hipStream_t st);
 
+// raw camera frames -> BGR / RGB (rawframes.hip); the arithmetic and the table rows are rawframes_dev.h's
+hipError_t launch_convert_raw(const uint8_t* raw, int fmt, int B, int H0, int W0, int rgb, uint8_t* out, hipStream_t st);
+// frame b: row b of the device raw table, written at row b's offset of the device frame table; max_items: the largest frame's
+hipError_t launch_convert_raw_frames(const uint8_t* raw, const void* dev_raw_table, const FrameRow* dev_frame_rows, int n, int max_items,
+                                     int rgb, uint8_t* out, hipStream_t st);
+
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
 void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,
                      int th = 0, int tw = 0, int wn = 0, int nrep = 0, bool allow_pk = true);

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, rawframes
 from ._lib import VtiConvInfo, VtiDesc, VtiMeasureParams, check, lib
 
 # "h2": split-fp16 storage (every element an fp16 (hi, lo) pair, all products on the fp16 matrix pipe): the dtype whose results
@@ -52,6 +52,20 @@ class FrameTable:
         d["offset"] = (i32[6] & 0xFFFFFFFF) | (i32[7] << 32)
         d.update(zip(("scale_x", "scale_y", "gain", "padx", "pady"), (float(v) for v in f64)))
         return d
+
+
+class RawTable:
+    """A packed raw table (vti_pack_raw_frames) for raw camera frames that differ in size and / or format: `host` (the packed bytes,
+    a CPU u8 tensor) and `dev` (their device copy), `shapes` [(H0, W0)] and `fmts` [VTI_RAW_*] per frame, the frames' `raw_offsets`
+    in the flat raw buffer (multiples of 16), their `frame_bytes` and the buffer's `raw_bytes`."""
+
+    def __init__(self, host, dev, shapes, fmts, raw_offsets, raw_bytes):
+        self.host, self.dev, self.shapes, self.fmts, self.raw_offsets, self.raw_bytes = host, dev, shapes, fmts, raw_offsets, raw_bytes
+        self.n = len(shapes)
+        self.frame_bytes = [rawframes.frame_bytes(f, h, w) for f, (h, w) in zip(fmts, shapes)]
+
+    def _ptrs(self):
+        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
 
 
 class Engine:
@@ -822,6 +836,83 @@ class Engine:
             h, w = p["shapes"][0]
             return out.view(n, h, w, 3), info
         return out, p["shapes"], p["byte_offsets"], info
+
+    # ---- raw camera frames -> BGR frames (cap.read() with CAP_PROP_CONVERT_RGB = 0): vti_convert_raw -------------------------------
+    def convert_raw(self, raw, fmt, H0, W0, rgb=False, out=None):
+        """n raw frames of one size and format -> u8 [n,H0,W0,3] on the device, byte for byte rawframes.to_bgr(raw, fmt, H0, W0, rgb):
+        vti_convert_raw.  raw: a uint8 tensor of any shape with n * rawframes.frame_bytes(fmt, H0, W0) bytes -- a device tensor is
+        used in place (any byte address), a CPU tensor, ndarray or bytes is copied to the device first.  fmt: a name ("yuyv", "uyvy",
+        "nv12", "nv21", "i420", "yv12") or its VTI_RAW_* value.  out: the u8 [n,H0,W0,3] device tensor to write (any byte address)."""
+        f = rawframes.format_id(fmt)
+        fb = rawframes.frame_bytes(f, H0, W0)
+        if not isinstance(raw, torch.Tensor):
+            raw = torch.from_numpy(np.array(rawframes.as_bytes(raw)))
+        if raw.dtype != torch.uint8:
+            raise ValueError(f"convert_raw: raw must be uint8, got {raw.dtype}")
+        if raw.numel() == 0 or raw.numel() % fb:
+            raise ValueError(f"convert_raw: {rawframes.NAMES[f]} {H0}x{W0} frames are {fb} bytes each, got {raw.numel()} bytes")
+        n = raw.numel() // fb
+        if n > 4096:
+            raise ValueError(f"convert_raw: at most 4096 frames per call, got {n}")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, H0, W0, 3)
+                                or not out.is_contiguous()):
+            raise ValueError(f"convert_raw: out must be a contiguous uint8 [{n},{H0},{W0},3] tensor")
+        if not torch.cuda.is_available():
+            raise ValueError("convert_raw: needs a ROCm device (no CPU fallback; rawframes.to_bgr is the host specification)")
+        if not raw.is_cuda:
+            dev = out.device if out is not None else (self.device or torch.device("cuda", torch.cuda.current_device()))
+            raw = raw.to(dev, non_blocking=True)
+        raw = raw.contiguous()
+        if out is None:
+            out = torch.empty((n, H0, W0, 3), dtype=torch.uint8, device=raw.device)
+        elif out.device != raw.device:
+            raise ValueError("convert_raw: raw and out must be on one device")
+        check(self._ctx, lib().vti_convert_raw(self._ctx, _ptr(raw), f, n, int(H0), int(W0), int(bool(rgb)), _ptr(out), _stream()))
+        return out
+
+    def pack_raw_frames(self, shapes, fmts, device=None):
+        """shapes: one (H0, W0) per raw frame, fmts: one format (name or VTI_RAW_* value) per frame, or one for all.  Validates the
+        frames, places them back to back at multiples of 16 bytes, packs the raw table and uploads it once -> RawTable (its
+        raw_offsets / raw_bytes say where the frames go in the flat raw buffer); a VtiError names the failing frame."""
+        shapes = [(int(h), int(w)) for h, w in (tuple(x)[:2] for x in shapes)]
+        n = len(shapes)
+        if isinstance(fmts, (str, int, np.integer)):
+            fmts = [fmts] * n
+        fmts = [rawframes.format_id(f) for f in fmts]
+        if len(fmts) != n:
+            raise ValueError(f"pack_raw_frames: {n} shapes but {len(fmts)} formats")
+        nbytes = int(lib().vti_raw_table_bytes(n))
+        if nbytes <= 0:
+            raise ValueError(f"pack_raw_frames: 1 <= n <= 4096 frames, got {n}")
+        host = torch.zeros(nbytes, dtype=torch.uint8)
+        off = (C.c_int64 * (n + 1))()
+        check(self._ctx, lib().vti_pack_raw_frames(self._ctx, (C.c_int32 * n)(*[h for h, _ in shapes]), (C.c_int32 * n)(*[w for _, w in shapes]),
+                                                   (C.c_int32 * n)(*fmts), n, C.c_void_p(host.data_ptr()), nbytes, off))
+        dev = host.to(device or self.device or "cuda")
+        return RawTable(host, dev, shapes, fmts, [int(v) for v in off[:n]], int(off[n]))
+
+    def convert_raw_frames(self, buf, raw_table, table, rgb=False, out=None):
+        """Raw frames that differ in size and / or format -> the frame-table buffer of `table` (pack_frames of the same shapes):
+        vti_convert_raw_frames.  buf: flat u8 device tensor of >= raw_table.raw_bytes bytes with frame k at raw_table.raw_offsets[k];
+        out: flat u8 device tensor of >= table.total_bytes bytes (allocated when None).  Frame k lands at table.byte_offsets[k], byte
+        for byte rawframes.to_bgr of it; the gaps between frames are not written.  (out, table) is what predict_frames_into,
+        annotate(table=) and encode_jpeg(table=) take."""
+        if not isinstance(raw_table, RawTable):
+            raise ValueError("convert_raw_frames: raw_table must be the RawTable of Engine.pack_raw_frames()")
+        self._check_frames(table, B=raw_table.n)
+        if list(raw_table.shapes) != list(table.shapes):
+            raise ValueError("convert_raw_frames: the raw table and the frame table describe frames of other shapes")
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() \
+                or buf.numel() < raw_table.raw_bytes:
+            raise ValueError(f"convert_raw_frames: buf must be a flat contiguous uint8 tensor of >= {raw_table.raw_bytes} bytes")
+        if buf.device != table.dev.device or raw_table.dev.device != table.dev.device:
+            raise ValueError("convert_raw_frames: the raw buffer, the raw table and the frame table must be on one device")
+        if out is None:
+            out = torch.empty(table.total_bytes, dtype=torch.uint8, device=buf.device)
+        self._check_frames(table, buf=out)
+        check(self._ctx, lib().vti_convert_raw_frames(self._ctx, _ptr(buf), buf.numel(), *raw_table._ptrs(), *table._ptrs(), table.B,
+                                                      int(bool(rgb)), _ptr(out), out.numel(), _stream()))
+        return out
 
     # ---- Results.masks.xy: instance polygons in frame pixels (vti_mask_polygons) -------------------------------------------
     def mask_polygons_scratch_bytes(self, H, W, row_bytes):

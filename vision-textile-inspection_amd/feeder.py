@@ -18,11 +18,17 @@ PyTorch is plumbing here (pinned / device allocations, streams, events); the ari
 import numpy as np
 import torch
 
+from . import rawframes
+
 
 class FrameFeeder:
-    """Ring of `depth` (pinned host, device) uint8 frame buffers [B, H0, W0, 3] in front of Engine.predict_into / YOLO."""
+    """Ring of `depth` (pinned host, device) uint8 frame buffers [B, H0, W0, 3] in front of Engine.predict_into / YOLO.
+    fmt ("yuyv", "uyvy", "nv12", "nv21", "i420", "yv12" or the VTI_RAW_* value): the camera's raw buffers cross the bus instead
+    (cap.read() with CAP_PROP_CONVERT_RGB = 0): the pinned and device rings hold [B, rawframes.frame_bytes(fmt, H0, W0)] raw bytes,
+    host_view / put take raw bytes, and frames(slot) converts them on the device (vti_convert_raw, after the copy's event) into
+    the slot's BGR buffer [B, H0, W0, 3]."""
 
-    def __init__(self, B, H0, W0, depth=3, device=0):
+    def __init__(self, B, H0, W0, depth=3, device=0, fmt=None):
         if depth < 2:
             raise ValueError("FrameFeeder needs at least two slots (one in flight, one being filled)")
         if not torch.cuda.is_available():
@@ -30,6 +36,13 @@ class FrameFeeder:
         self.B, self.H0, self.W0, self.depth = B, H0, W0, depth
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         shape = (B, H0, W0, 3)
+        self.fmt = None if fmt is None else rawframes.format_id(fmt)
+        if self.fmt is not None:
+            from .engine import Engine
+            self.frame_bytes = rawframes.frame_bytes(self.fmt, H0, W0)
+            self._converter = Engine("n", 1, H=32, W=32, max_batch=1)      # vti_convert_raw needs a context but no weights
+            self.bgr = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(depth)]
+            shape = (B, self.frame_bytes)
         self.pinned = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(depth)]
         self.dev = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(depth)]
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -72,6 +85,14 @@ class FrameFeeder:
         submit it.  (A producer that can write into host_view() directly saves this host-side memcpy.)"""
         slot = self.next_slot()
         view = self.host_view(slot)
+        if self.fmt is not None:        # raw bytes of n <= B frames, in any shape
+            a = rawframes.as_bytes(frames.numpy() if isinstance(frames, torch.Tensor) else frames, "put: frames")
+            if a.size == 0 or a.size % self.frame_bytes or a.size // self.frame_bytes > self.B:
+                raise ValueError(f"put: expected raw bytes of 1..{self.B} {rawframes.NAMES[self.fmt]} frames of {self.frame_bytes} bytes, "
+                                 f"got {a.size} bytes")
+            n = a.size // self.frame_bytes
+            view[:n] = a.reshape(n, self.frame_bytes)
+            return self.submit(slot, n)
         a = frames.numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
         if a.dtype != np.uint8 or a.ndim != 4 or a.shape[1:] != (self.H0, self.W0, 3) or a.shape[0] > self.B:
             raise ValueError(f"put: expected uint8 [<= {self.B}, {self.H0}, {self.W0}, 3], got {a.dtype} {a.shape}")
@@ -80,12 +101,16 @@ class FrameFeeder:
 
     # ---- device side -----------------------------------------------------------------------
     def frames(self, slot):
-        """Device frames of a submitted slot, ordered after its copy on the CURRENT stream."""
+        """Device frames of a submitted slot, ordered after its copy on the CURRENT stream.  With fmt: the conversion of the slot's
+        raw bytes is enqueued there, into the slot's BGR buffer (rewritten by the next frames() of this slot, in stream order)."""
         ev = self.h2d_done[slot]
         if ev is None:
             raise RuntimeError("slot was never submitted")
         torch.cuda.current_stream().wait_event(ev)
-        return self.dev[slot][:self.count[slot]]
+        n = self.count[slot]
+        if self.fmt is not None:
+            return self._converter.convert_raw(self.dev[slot][:n], self.fmt, self.H0, self.W0, out=self.bgr[slot][:n])
+        return self.dev[slot][:n]
 
     def release(self, slot):
         """Call after the last kernel that reads frames(slot) was enqueued on the current stream: the slot's device buffer may be

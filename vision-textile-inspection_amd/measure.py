@@ -163,6 +163,9 @@ class _DeviceStage:
         info = None
         if files is not None:       # the batch cap.read() would have delivered: the files decoded to BGR on the device
             frames, info = self.model._decode_jpeg(files, rgb=False)
+        raws = self.model._raw_source(frames)
+        if raws is not None:        # raw camera buffers (RawFrames): converted on the device to that same BGR batch
+            frames = self.model._convert_raw(raws)
         shapes = self.model._differing_shapes(frames)
         table = None
         if shapes is not None:
@@ -270,6 +273,7 @@ class StitchMeasurer(_DeviceStage):
                        jpeg_quality=95):
         """frames: BGR uint8 [B,H0,W0,3] (or one [H0,W0,3]) as the camera gives them, or a list of JPEG files (bytes) as a
         motion-JPEG camera delivers them: they are decoded on the device to the BGR batch cap.read() would have returned.
+        RawFrames (one, or a list of them) are a camera's raw YUV buffers, converted on the device to that same BGR batch.
         The reference predicts on the RGB conversion
         with Ultralytics' channel flip of ndarray sources, i.e. the network sees the BGR frame: swap_rb=False here does the same.
         Returns one record per frame, in frame order, with the smoothing applied frame by frame.

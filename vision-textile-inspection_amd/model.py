@@ -15,6 +15,7 @@ import os
 import numpy as np
 import torch
 
+from . import rawframes
 from .engine import Engine, unpack_bits
 from .weights import random_weights, unpack_container
 
@@ -131,6 +132,53 @@ class DecodedFrames:
         self.buf, self.shapes, self.byte_offsets = buf, shapes, byte_offsets
 
 
+class RawFrames:
+    """n raw camera frames of one size and format, as cap.read() returns them with CAP_PROP_CONVERT_RGB = 0: a source of
+    YOLO.predict and the measurers' process_frames, converted on the device (vti_convert_raw) to the BGR frames cap.read() would
+    otherwise have delivered (rawframes.to_bgr).  data: a uint8 ndarray, a CPU or device tensor, or bytes, of any shape with
+    n * rawframes.frame_bytes(fmt, H0, W0) bytes ([H0,W0,2] and [H0*3/2,W0] as OpenCV shapes them, [n,...] stacks, flat buffers);
+    fmt: "yuyv", "uyvy", "nv12", "nv21", "i420", "yv12" or the VTI_RAW_* value."""
+
+    def __init__(self, data, fmt, H0, W0):
+        self.fmt = rawframes.format_id(fmt)
+        self.frame_bytes = rawframes.frame_bytes(self.fmt, H0, W0)
+        self.H0, self.W0 = int(H0), int(W0)
+        if isinstance(data, torch.Tensor):
+            if data.dtype != torch.uint8:
+                raise ValueError(f"RawFrames: data must be uint8, got {data.dtype}")
+            flat = data.contiguous().reshape(-1)
+            count = flat.numel()
+        else:
+            flat = rawframes.as_bytes(data, "RawFrames: data")
+            count = flat.size
+        if count == 0 or count % self.frame_bytes:
+            raise ValueError(f"RawFrames: {rawframes.NAMES[self.fmt]} {self.H0}x{self.W0} frames are {self.frame_bytes} bytes each; "
+                             f"expected a multiple of {self.frame_bytes} bytes, got {count}")
+        self.data = flat                 # flat uint8: an ndarray, or the tensor (CPU or device) as it was given
+        self.n = count // self.frame_bytes
+
+    def __len__(self):
+        return self.n
+
+    def frame(self, k):
+        """Frame k's bytes (a flat view)."""
+        return self.data[k * self.frame_bytes:(k + 1) * self.frame_bytes]
+
+    def to_bgr(self, rgb=False):
+        """The host specification of what the device makes of these frames: uint8 [n,H0,W0,3]."""
+        d = self.data.cpu().numpy() if isinstance(self.data, torch.Tensor) else self.data
+        return rawframes.to_bgr(d, self.fmt, self.H0, self.W0, rgb)
+
+
+class RawBatch:
+    """Raw frames of differing sizes and / or formats on their way to one vti_convert_raw_frames: one (fmt, flat bytes) per frame."""
+
+    def __init__(self, members):
+        self.frames = [(m.fmt, m.frame(k)) for m in members for k in range(m.n)]
+        self.shapes = [(m.H0, m.W0) for m in members for _ in range(m.n)]
+        self.fmts = [f for f, _ in self.frames]
+
+
 class YOLO:
     """`YOLO(path)` takes a VTIW1 container; `YOLO(None, scale=, nc=, seed=)` makes seeded random weights."""
 
@@ -214,9 +262,7 @@ class YOLO:
     def _decode_jpeg(self, files, rgb):
         """JPEG files -> (a device batch u8 [n,H0,W0,3], or DecodedFrames when the sizes differ; info i32 [n,4] on the device).
         A refused file raises here, before anything is launched."""
-        dec = getattr(self, "_decoder", None)
-        if dec is None:             # vti_decode_jpeg needs a context but no weights: the smallest plan serves every size
-            dec = self._decoder = Engine(self.scale, self.nc, self._nm, self._reg_max, 32, 32, 1, self.dtype)
+        dec = self._aux_engine()
         dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
         if dev.type == "cuda" and torch.cuda.is_available():
             torch.cuda.set_device(dev)
@@ -224,6 +270,61 @@ class YOLO:
         if len(got) == 2:
             return got
         return DecodedFrames(got[0], got[1], got[2]), got[3]
+
+    def _aux_engine(self):
+        """The context of the calls that need no weights (vti_decode_jpeg, vti_convert_raw): the smallest plan serves every size."""
+        dec = getattr(self, "_decoder", None)
+        if dec is None:
+            dec = self._decoder = Engine(self.scale, self.nc, self._nm, self._reg_max, 32, 32, 1, self.dtype)
+        return dec
+
+    @staticmethod
+    def _raw_source(source):
+        """The members when `source` is a RawFrames or a list / tuple of them; None for every other source."""
+        if isinstance(source, RawFrames):
+            return [source]
+        if not (isinstance(source, (list, tuple)) and len(source) and any(isinstance(s, RawFrames) for s in source)):
+            return None
+        for k, s in enumerate(source):
+            if not isinstance(s, RawFrames):
+                raise ValueError(f"a list source is either all RawFrames or none; item {k} is {type(s).__name__}")
+        return list(source)
+
+    def _convert_raw(self, members):
+        """RawFrames members -> the BGR device batch u8 [N,H0,W0,3] cap.read() would have delivered (vti_convert_raw per member,
+        into one batch) when all have one size; a RawBatch for _predict_outputs_frames otherwise."""
+        if any((m.H0, m.W0) != (members[0].H0, members[0].W0) for m in members):
+            return RawBatch(members)
+        dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
+        if not torch.cuda.is_available():
+            raise RuntimeError("RawFrames sources need a ROCm GPU (no CPU fallback; rawframes.to_bgr is the host specification)")
+        torch.cuda.set_device(dev)
+        eng = self._aux_engine()
+        H0, W0 = members[0].H0, members[0].W0
+        out = torch.empty((sum(m.n for m in members), H0, W0, 3), dtype=torch.uint8, device=dev)
+        at = 0
+        for m in members:
+            d = m.data if isinstance(m.data, torch.Tensor) else torch.from_numpy(np.array(m.data))
+            eng.convert_raw(d.to(dev, non_blocking=True), m.fmt, H0, W0, rgb=False, out=out[at:at + m.n])
+            at += m.n
+        return out
+
+    def _raw_to_frame_buffer(self, eng, batch, table, buf, dev):
+        """The RawBatch's bytes through one flat pinned staging buffer and one asynchronous H2D, then vti_convert_raw_frames into
+        the frame-table buffer `buf`.  The raw table, the staging buffer and its device twin are cached per (engine, shapes, fmts)."""
+        key = (id(eng), tuple(batch.shapes), tuple(batch.fmts))
+        ent = getattr(self, "_raw_tables", {}).get(key)
+        if ent is None:
+            rt = eng.pack_raw_frames(batch.shapes, batch.fmts, dev)
+            ent = (rt, torch.empty(max(rt.raw_bytes, 16), dtype=torch.uint8, pin_memory=True),
+                   torch.empty(max(rt.raw_bytes, 16), dtype=torch.uint8, device=dev))
+            self._raw_tables = {key: ent}      # one rig at a time, as the frame table
+        rt, stage, rawbuf = ent
+        flat = stage.numpy()
+        for (_, data), off, fb in zip(batch.frames, rt.raw_offsets, rt.frame_bytes):
+            flat[off:off + fb] = data.cpu().numpy() if isinstance(data, torch.Tensor) else data
+        rawbuf.copy_(stage, non_blocking=True)
+        eng.convert_raw_frames(rawbuf, rt, table, rgb=False, out=buf)
 
     @staticmethod
     def _raise_if_corrupt(info):
@@ -239,7 +340,7 @@ class YOLO:
     def _differing_shapes(source):
         """[(H0, W0)] when `source` is a list / tuple of frames whose shapes are not all equal (Ultralytics then letterboxes every
         frame onto one imgsz canvas, LetterBox(auto=False)); None for everything that keeps the stacked path."""
-        if isinstance(source, DecodedFrames):
+        if isinstance(source, (DecodedFrames, RawBatch)):
             return list(source.shapes)
         if not isinstance(source, (list, tuple)) or len(source) < 2:
             return None
@@ -274,6 +375,8 @@ class YOLO:
         table, stage, buf = ent
         if isinstance(source, DecodedFrames):       # already on the device, in this very layout (vti_decode_jpeg, layout 0)
             buf = source.buf
+        elif isinstance(source, RawBatch):          # raw camera frames: converted on the device into this very layout
+            self._raw_to_frame_buffer(eng, source, table, buf, dev)
         else:
             flat = stage.numpy()
             for f, (h, w), off in zip(source, shapes, table.byte_offsets):
@@ -332,7 +435,11 @@ class YOLO:
         a list.  On frames of one size, or without retina_masks, mixed changes nothing.
         JPEG sources -- bytes, a path (str / os.PathLike) or a list / tuple of these -- are decoded on the device
         (Engine.decode_jpeg); as with Ultralytics' file sources the network sees the file's R, G, B, so swap_rb does not apply to
-        them.  orig_shape comes from the file's header; a refused file raises before any launch, a damaged one after the call."""
+        them.  orig_shape comes from the file's header; a refused file raises before any launch, a damaged one after the call.
+        RawFrames sources -- one, or a list / tuple of them -- are raw camera buffers (YUYV, UYVY, NV12, NV21, I420, YV12) converted
+        on the device (vti_convert_raw): the call is exactly predict on the BGR ndarray(s) rawframes.to_bgr gives, i.e. the frames
+        cap.read() delivers without CAP_PROP_CONVERT_RGB = 0, with the same swap_rb meaning.  Members of differing sizes go
+        through the frame table (vti_convert_raw_frames -> vti_predict_frames), members of one size keep the stacked path."""
         if not isinstance(mixed, (bool, np.bool_)):
             raise ValueError(f"predict: mixed must be True or False, got {mixed!r}")
         files = self._jpeg_files(source)
@@ -340,6 +447,9 @@ class YOLO:
         if files is not None:
             source, info = self._decode_jpeg(files, rgb=True)
             swap_rb = False
+        raws = self._raw_source(source)
+        if raws is not None:        # the BGR frames cap.read() would have delivered; swap_rb keeps its meaning for ndarray sources
+            source = self._convert_raw(raws)
         shapes = self._differing_shapes(source)
         ragged = False
         if shapes is not None:
