@@ -491,6 +491,39 @@ int32_t vti_annotate_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void*
                             int32_t n_sel, int32_t max_points, const void* host_out_table, const void* dev_out_table, uint8_t* dev_out,
                             int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- the model-check viewer's picture on device (Utils/check_model.py:155-256, annotate_result) ------------------------------------ */
+/* The frames dev_select[k] of the batch as the viewer shows them, byte for byte the package's overlay.py (render): per instance in
+ * detection order the mask's outer contours (thickness 2), the int-truncated box (thickness 2) and, with dev_plates, a filled label
+ * plate, all in the class colour palette[cls % n_colours]; then cv2.addWeighted(tinted frame, alpha, that picture, beta, 0), the
+ * tinted frame being the frame with every pixel in the colour of the LAST instance whose mask covers it.  The blend is OpenCV 4's
+ * v_fma form: fma(a, alpha, b * beta) in float32, rounded half to even, saturated.
+ * mode: VTI_OVERLAY_DRAW writes the drawn picture, VTI_OVERLAY_BLEND blends the tinted frame with the caller's picture dev_annotated
+ * (u8 [n_sel,H0,W0,3]; e.g. DRAW's output with the label text put on it by the host), VTI_OVERLAY_BOTH is byte for byte BLEND applied
+ * to DRAW's output, without the intermediate.  dev_annotated: non-NULL iff mode is BLEND.
+ * dev_frames, dev_masks, native, dev_dets, dev_xyxy, dev_counts, dev_offsets, max_det, capacity, host_select / dev_select and n_sel are
+ * exactly what vti_annotate takes (1 <= H0, W0 <= 8192); an instance past the capacity has no mask and no plate, its box is drawn.
+ * dev_plates: i32 [capacity,4] (xa, ya, xb, yb) per mask slot, 16-byte aligned, or NULL: every in-frame pixel with xa <= x <= xb and
+ * ya <= y <= yb; a row with xb < xa or yb < ya draws nothing.  host_palette: n_colours (1..16) BGR triplets in host memory, read
+ * during the call.  alpha, beta: finite.  max_points: room for the contour vertices of one frame.
+ * dev_out u8 [n_sel,H0,W0,3]: every byte is written and nothing else is; dev_frames and dev_annotated are never written.  In BLEND
+ * dev_out may be the very buffer dev_annotated points to (the operation is per pixel); nothing else may overlap.  dev_status i32
+ * [n_sel]: 0, or VTI_OVERLAY_OUTLINE_SKIPPED when the frame's contours needed more than max_points vertices (or the tracer reached a
+ * loop bound): none of that frame's contours is then drawn, everything else stands.  All launches go on `stream`, ordered by kernel
+ * boundaries only; no host synchronisation, nothing the caller must clear.  dev_scratch: >= vti_overlay_scratch_bytes(), 256-byte
+ * aligned.  Every argument check (VTI_ERR_ARG) runs before the first HIP call.  No weights are needed.
+ * Not covered: batches whose frames differ in size (a vti_overlay_frames), and text on the device (the label strings stay with the
+ * host: overlay.py label_items / plates / put_labels). */
+enum { VTI_OVERLAY_DRAW = 1, VTI_OVERLAY_BLEND = 2, VTI_OVERLAY_BOTH = 3 };
+enum { VTI_OVERLAY_OUTLINE_SKIPPED = 1 };
+/* Host only: bytes of device scratch vti_overlay needs (0 on a bad argument); it grows with n_sel and with max_points. */
+int64_t vti_overlay_scratch_bytes(const vti_ctx* ctx, int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points);
+int32_t vti_overlay(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t H0, int32_t W0, const uint8_t* dev_masks,
+                    int32_t native, const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                    const int32_t* dev_offsets, int32_t max_det, int32_t capacity, const int32_t* dev_plates,
+                    const uint8_t* host_palette, int32_t n_colours, float alpha, float beta, const int32_t* host_select,
+                    const int32_t* dev_select, int32_t n_sel, int32_t mode, const uint8_t* dev_annotated, int32_t max_points,
+                    uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- the saved JPEG on device (cv2.imwrite(save_path, annotated): main.py:314, measurement.py:536) -------------------------------- */
 /* n frames u8 [n,H0,W0,3] (BGR as cv2's frames are; rgb = 1: RGB) -> n JPEG files, byte for byte the package's jpeg.py: libjpeg's
  * baseline file at `quality` (jpeg_set_quality, force_baseline), 8 bit, YCbCr 4:2:0, one interleaved scan, the Annex K quantisation

@@ -44,6 +44,8 @@ VTI_MEASURE_MAX_DET = 1000
 VTI_POLY_LARGEST, VTI_POLY_CONCAT = 0, 1
 VTI_POLY_OK, VTI_POLY_ERR_BOUND, VTI_POLY_ERR_RANGE = 0, 1, 2
 VTI_ANNOTATE_OUTLINE_SKIPPED = 1
+VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND, VTI_OVERLAY_BOTH = 1, 2, 3
+VTI_OVERLAY_OUTLINE_SKIPPED = 1
 VTI_JPEG_CORRUPT = 1
 VTI_RAW_YUYV, VTI_RAW_UYVY, VTI_RAW_NV12, VTI_RAW_NV21, VTI_RAW_I420, VTI_RAW_YV12 = range(6)
 VTI_ERR_ARG, VTI_ERR_UNSUPPORTED = -1, -6
@@ -122,6 +124,9 @@ SIGNATURES = {
     "vti_annotate_frames_scratch_bytes": (_I64, [_P, _P, _I32, _I32]),
     "vti_annotate_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32,
                                    _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vti_overlay_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
+    "vti_overlay": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _F, _F, _P, _P, _I32, _I32, _P,
+                           _I32, _P, _P, _P, _SZ, _P]),
     "vti_encode_jpeg_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_encode_jpeg_max_bytes": (_I64, [_I32, _I32, _I32]),
     "vti_encode_jpeg": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),

@@ -1188,6 +1188,57 @@ int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, i
     return VTI_OK;
 }
 
+// ---- vti_overlay: the model-check viewer's picture ---------------------------------------------------------------------------
+int64_t vti_overlay_scratch_bytes(const vti_ctx* c, int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points) {
+    if (!c || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points)) return 0;
+    OverlayLayout L;
+    overlay_layout(n_sel, max_det, H0, W0, c->plan.desc.H, c->plan.desc.W, max_points, L);
+    return (int64_t)L.total;
+}
+
+int32_t vti_overlay(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const uint8_t* masks, int32_t native,
+                    const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
+                    int32_t capacity, const int32_t* plates, const uint8_t* host_palette, int32_t n_colours, float alpha, float beta,
+                    const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t mode, const uint8_t* annotated,
+                    int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream) {
+    // every check comes before the first HIP call
+    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_overlay: null ctx");
+    if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
+        return bad("vti_overlay: bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                   "1 <= H0, W0 <= 8192; native 0 or 1)");
+    if (mode != VTI_OVERLAY_DRAW && mode != VTI_OVERLAY_BLEND && mode != VTI_OVERLAY_BOTH)
+        return bad("vti_overlay: mode must be VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND or VTI_OVERLAY_BOTH");
+    if (n_colours < 1 || n_colours > 16) return bad("vti_overlay: n_colours must be 1 .. 16");
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return bad("vti_overlay: alpha and beta must be finite");
+    if ((annotated != nullptr) != (mode == VTI_OVERLAY_BLEND))
+        return bad("vti_overlay: dev_annotated must be given with VTI_OVERLAY_BLEND and only then");
+    if (!frames || !dets || !xyxy || !counts || !offsets || !host_palette || !host_select || !dev_select || !out || !status ||
+        (capacity && !masks))
+        return bad("vti_overlay: null pointer");
+    for (int32_t k = 0; k < n_sel; ++k)
+        if (host_select[k] < 0 || host_select[k] >= B) {
+            char msg[120];
+            snprintf(msg, sizeof msg, "vti_overlay: host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
+            return bad(msg);
+        }
+    if (((uintptr_t)dev_select & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)status & 3) ||
+        ((uintptr_t)dets & 3) || ((uintptr_t)xyxy & 3))
+        return bad("vti_overlay: the index arrays, rows and status must be 4-byte aligned");
+    if (plates && ((uintptr_t)plates & 15)) return bad("vti_overlay: dev_plates must be 16-byte aligned");
+    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
+        return bad(native ? "vti_overlay: native masks must be 8-byte aligned" : "vti_overlay: masks must be 16-byte aligned");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_overlay: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_overlay_scratch_bytes(c, n_sel, max_det, H0, W0, max_points))
+        return bad("vti_overlay: scratch smaller than vti_overlay_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_overlay")) return drc;
+    const vti_desc& d = c->plan.desc;
+    VTI_HIP(c, launch_overlay(frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H, d.W, plates,
+                              host_palette, n_colours, alpha, beta, dev_select, n_sel, mode, annotated, max_points, out, status, scratch,
+                              (hipStream_t)stream), "overlay kernels");
+    return VTI_OK;
+}
+
 // ---- vti_annotate for frames of differing sizes ----------------------------------------------------------------------------
 // The header of a host frame table and row k of it.
 static FrameTableHeader table_header(const void* host_table) { FrameTableHeader h; memcpy(&h, host_table, sizeof h); return h; }

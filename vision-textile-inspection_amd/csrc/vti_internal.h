@@ -364,6 +364,23 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
                            const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
                            int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
 
+// overlay.hip: vti_overlay (the model-check viewer's picture).  The scratch holds: 16 ints of counters per selected frame | the contour
+// vertices int4 [n_sel, max_points] | the owner planes (8 words per 32-bit mask word, for the larger of a native and a letterbox mask
+// slot) per selected frame | min(max_det, 16) labelling areas per selected frame (parent | runs | row_start as polygons.hip's, then
+// the instance's bitmap u64 [H0, WW]).
+struct OverlayLayout {
+    int WW, groups;            // 64-bit words per bitmap row; contour workgroups (areas) per selected frame
+    bool in_lds;               // the tracer keeps the bitmap in LDS
+    size_t off_meta, off_cont, off_planes, off_areas, plane_words, area_bytes, off_runs, off_rows, off_img, total;
+};
+void overlay_layout(int n_sel, int max_det, int H0, int W0, int Hm, int Wm, int max_points, OverlayLayout& L);
+// palette: host, 3 * n_colours bytes (BGR); select: the device copy of the (host-checked) selection; H, W: the letterbox mask size
+hipError_t launch_overlay(const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks, int native, const float* dets,
+                          const float* xyxy, const int* counts, const int* offsets, int max_det, int nm, int capacity, int H, int W,
+                          const int* plates, const uint8_t* palette, int n_colours, float alpha, float beta, const int* select,
+                          int n_sel, int mode, const uint8_t* annotated, int max_points, uint8_t* out, int* status, void* scratch,
+                          hipStream_t st);
+
 // jpeg.hip: vti_encode_jpeg (the saved JPEG).  The scratch holds: the header's bytes (1 KiB) | bit total u64 [n] | file size i64 [n] |
 // coefficients i16 [n, MCUs, 6, 64] | block bit positions u64 [n, blocks] | the unstuffed stream, NC chunks of 4096 bytes per frame
 // (the worst case of 1658 bits per block) | 0xFF count u32 [n, NC].

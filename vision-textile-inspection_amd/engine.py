@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib, rawframes
+from . import overlay as _ov
 from ._lib import VtiConvInfo, VtiDesc, VtiMeasureParams, check, lib
 
 # "h2": split-fp16 storage (every element an fp16 (hi, lo) pair, all products on the fp16 matrix pipe): the dtype whose results
@@ -692,6 +693,81 @@ class Engine:
             int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
             _ptr(meas["frame_i32"]), _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel),
             n_sel, int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        return r
+
+    # ---- the model-check viewer's picture (Utils/check_model.py:155-256): vti_overlay ------------------------------------------
+    def overlay_scratch_bytes(self, n_sel, max_det, H0, W0, max_points):
+        return int(lib().vti_overlay_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))
+
+    def overlay(self, frames, out, select, native=False, plates=None, mode="both", annotated=None, alpha=0.30, beta=0.70,
+                palette=_ov.PALETTE, max_points=16384, result=None):
+        """The frames `select` of the batch as check_model.py's annotate_result shows them (without the label text): vti_overlay,
+        byte for byte overlay.render(...).  frames: the contiguous uint8 [B,H0,W0,3] BGR device batch predict consumed; out: its
+        output set; select: host integers in [0, B), any order, duplicates allowed (ValueError otherwise); native: the masks are
+        frame-size rows (retina_masks).  plates: None, or a contiguous int32 [capacity,4] device tensor (xa, ya, xb, yb) per mask slot
+        (overlay.plates).  mode: "draw" (contours, boxes, plates), "blend" (the tinted frame blended with `annotated`, a contiguous
+        uint8 [n_sel,H0,W0,3] device tensor, which may be result["frames"] itself) or "both" ("blend" applied to "draw"'s picture).
+        palette: BGR triplets, 1..16 (overlay.PALETTE).  max_points: room for the contour vertices of one frame.  Returns device
+        tensors, no host synchronisation: dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]: VTI_OVERLAY_OUTLINE_SKIPPED where the
+        contours did not fit); "frames" feeds encode_jpeg unchanged.  `result`: the same dict preallocated.  The scratch is kept per
+        (n_sel, H0, W0)."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("overlay: frames must be a uint8 [B,H0,W0,3] tensor")
+        B, H0, W0, _ = frames.shape
+        dets, masks = out["dets"], out["masks"]
+        dev = dets.device
+        if out["counts"].shape[0] != B:
+            raise ValueError(f"overlay: {B} frames but an output set of {out['counts'].shape[0]}")
+        max_det, capacity = dets.shape[1], masks.shape[0]
+        sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
+        if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
+            raise ValueError("overlay: select must be a non-empty sequence of frame indices")
+        if sel.min() < 0 or sel.max() >= B:
+            raise ValueError(f"overlay: frame index outside [0, {B})")
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        n_sel = int(sel.size)
+        mode_i = _ov.MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if mode_i not in (_ov.DRAW, _ov.BLEND, _ov.BOTH):
+            raise ValueError(f"overlay: mode must be 'draw', 'blend' or 'both', got {mode!r}")
+        if (annotated is not None) != (mode_i == _ov.BLEND):
+            raise ValueError("overlay: annotated is the picture mode='blend' blends with (and only that mode takes one)")
+        pal = np.ascontiguousarray(palette, dtype=np.uint8)
+        if pal.ndim != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= 16:
+            raise ValueError("overlay: palette must be 1 .. 16 BGR triplets")
+        if not (np.isfinite(alpha) and np.isfinite(beta)):
+            raise ValueError("overlay: alpha and beta must be finite")
+        if capacity:
+            want = (H0, 8 * -(-W0 // 64)) if native else (self.H, self.W // 8)
+            if masks.dtype != torch.uint8 or tuple(masks.shape[1:]) != want:
+                raise ValueError(f"overlay: masks must be uint8 [capacity, {want[0]}, {want[1]}] ({'frame-size rows' if native else 'letterbox bits'})")
+        # everything above is about shapes and values; what needs a device comes from here on
+        if not frames.is_cuda or not frames.is_contiguous():
+            raise ValueError("overlay: frames must be the contiguous device batch predict consumed")
+        if plates is not None and not (isinstance(plates, torch.Tensor) and plates.dtype == torch.int32 and plates.is_contiguous()
+                                       and tuple(plates.shape) == (capacity, 4) and plates.device == dev):
+            raise ValueError(f"overlay: plates must be a contiguous int32 [{capacity},4] tensor on the outputs' device")
+        if annotated is not None and not (isinstance(annotated, torch.Tensor) and annotated.dtype == torch.uint8 and annotated.is_contiguous()
+                                          and tuple(annotated.shape) == (n_sel, H0, W0, 3) and annotated.device == dev):
+            raise ValueError(f"overlay: annotated must be a contiguous uint8 [{n_sel},{H0},{W0},3] tensor on the outputs' device")
+        r = dict(result or {})
+        if "status" not in r:
+            r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
+        if "frames" not in r:
+            r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
+        need = self.overlay_scratch_bytes(n_sel, max_det, H0, W0, max_points)
+        if need <= 0:
+            raise ValueError(f"overlay: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+        ws = getattr(self, "_overlay_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            self._overlay_ws = None
+            ws = self._overlay_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        dev_sel = torch.from_numpy(sel).to(dev)
+        check(self._ctx, lib().vti_overlay(
+            self._ctx, _ptr(frames), B, H0, W0, _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets),
+            _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
+            _ptr(plates) if plates is not None and capacity else C.c_void_p(0), C.c_void_p(pal.ctypes.data), int(pal.shape[0]),
+            float(alpha), float(beta), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(mode_i), _ptr(annotated),
+            int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         return r
 
     # ---- the saved JPEG (cv2.imwrite(save_path, annotated), main.py:314): vti_encode_jpeg ----------------------------------
