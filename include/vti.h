@@ -511,8 +511,8 @@ int32_t vti_annotate_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void*
  * loop bound): none of that frame's contours is then drawn, everything else stands.  All launches go on `stream`, ordered by kernel
  * boundaries only; no host synchronisation, nothing the caller must clear.  dev_scratch: >= vti_overlay_scratch_bytes(), 256-byte
  * aligned.  Every argument check (VTI_ERR_ARG) runs before the first HIP call.  No weights are needed.
- * Not covered: batches whose frames differ in size (a vti_overlay_frames), and text on the device (the label strings stay with the
- * host: overlay.py label_items / plates / put_labels). */
+ * Frames of differing sizes (a frame table): vti_overlay_frames below.  Not covered: text on the device (the label strings stay with
+ * the host: overlay.py label_items / plates / put_labels). */
 enum { VTI_OVERLAY_DRAW = 1, VTI_OVERLAY_BLEND = 2, VTI_OVERLAY_BOTH = 3 };
 enum { VTI_OVERLAY_OUTLINE_SKIPPED = 1 };
 /* Host only: bytes of device scratch vti_overlay needs (0 on a bad argument); it grows with n_sel and with max_points. */
@@ -523,6 +523,39 @@ int32_t vti_overlay(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t 
                     const uint8_t* host_palette, int32_t n_colours, float alpha, float beta, const int32_t* host_select,
                     const int32_t* dev_select, int32_t n_sel, int32_t mode, const uint8_t* dev_annotated, int32_t max_points,
                     uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
+/* vti_overlay for a batch whose frames differ in size.  dev_frames / host_table / dev_table: the flat frame buffer and the frame table
+ * of vti_predict_frames (frame b: u8 [H0[b], W0[b], 3] BGR at byte_offset[b]); dets, xyxy, counts, offsets, max_det: what it wrote.
+ * The OUTPUT is described by a second frame table, the out table, exactly as vti_annotate_frames' is: n_sel rows packed with
+ * vti_pack_frames for the same canvas, row k with the H0, W0 of input row select[k] (otherwise VTI_ERR_ARG, and vti_last_error names
+ * k); its byte offsets place picture k in dev_out, and in dev_annotated (BLEND: a flat buffer laid out by the same out table,
+ * typically DRAW's dev_out with the host's text on it; dev_out may be that very buffer).  Every byte of each picture is written and
+ * no other: not the gaps between pictures, not the bytes past the last one; dev_frames and dev_annotated are never written.
+ * Masks, native = 0: the letterbox bit masks [capacity, H, W/8] as vti_overlay takes them; dev_mask_bases must be NULL.
+ * Masks, native = 1: the ragged frame-size rows of vti_masks_native_frames / vti_predict_frames_native with their dev_mask_bases (i64
+ * [B + 1], 8-byte aligned) and capacity_bytes: slot i of frame b is H0[b] rows of 8 * ceil(W0[b] / 64) bytes at byte bases[b] + i *
+ * slot_bytes[b]; it is live iff it ends at or before capacity_bytes and its slot index offsets[b] + i is below `capacity`.  A slot that
+ * is not live is "no mask": no tint and no contour; the box is drawn, and the plate while the slot index is below `capacity`.
+ * dev_plates stays i32 [capacity,4] per slot index.  capacity_bytes >= 0 in either form.
+ * Picture k and dev_status[k] are byte for byte what vti_overlay writes for that frame when called with H0[b], W0[b] on the same inputs
+ * (native: that frame's slots as a uniform [n, H0, row_bytes] buffer), in each of DRAW, BLEND and BOTH; VTI_OVERLAY_OUTLINE_SKIPPED,
+ * duplicates and any order of the selection are vti_overlay's.  A SELECTED frame above 8192 in either dimension is VTI_ERR_ARG naming
+ * the frame.  dev_frames, dev_out and dev_annotated 16-byte aligned.  Every argument check -- both tables revalidated row by row, the
+ * selection, the alignments and a short scratch included -- runs before the first HIP call; the device copies (tables, selection,
+ * bases) are trusted as the other *_frames calls trust theirs.  The scratch regions are pitched by the largest selected frame; what
+ * lies in a region beyond a frame's own extent is never read.  Up to three launches on `stream` as vti_overlay's, or four when a DRAW
+ * or BOTH selection holds both frames whose bitmap fits the tracer's LDS image (H0 * ceil(W0 / 64) * 8 <= 156 KiB) and frames whose
+ * bitmap does not: the contour kernel then runs in both forms, each on its own frames.  No host synchronisation, nothing to clear.
+ * Host only: scratch bytes for the pictures the out table describes (0 on a bad argument) = vti_overlay_scratch_bytes(n_sel, max_det,
+ * largest H0, largest W0 of its rows, max_points). */
+int64_t vti_overlay_frames_scratch_bytes(const vti_ctx* ctx, const void* host_out_table, int32_t max_det, int32_t max_points);
+int32_t vti_overlay_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table, int32_t B,
+                           const uint8_t* dev_masks, int32_t native, const int64_t* dev_mask_bases, int64_t capacity_bytes,
+                           const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets,
+                           int32_t max_det, int32_t capacity, const int32_t* dev_plates, const uint8_t* host_palette,
+                           int32_t n_colours, float alpha, float beta, const int32_t* host_select, const int32_t* dev_select,
+                           int32_t n_sel, int32_t mode, const uint8_t* dev_annotated, int32_t max_points, const void* host_out_table,
+                           const void* dev_out_table, uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes,
+                           void* stream);
 
 /* ---- the saved JPEG on device (cv2.imwrite(save_path, annotated): main.py:314, measurement.py:536) -------------------------------- */
 /* n frames u8 [n,H0,W0,3] (BGR as cv2's frames are; rgb = 1: RGB) -> n JPEG files, byte for byte the package's jpeg.py: libjpeg's

@@ -127,6 +127,9 @@ SIGNATURES = {
     "vti_overlay_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
     "vti_overlay": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _F, _F, _P, _P, _I32, _I32, _P,
                            _I32, _P, _P, _P, _SZ, _P]),
+    "vti_overlay_frames_scratch_bytes": (_I64, [_P, _P, _I32, _I32]),
+    "vti_overlay_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _F, _F, _P, _P, _I32,
+                                  _I32, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "vti_encode_jpeg_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_encode_jpeg_max_bytes": (_I64, [_I32, _I32, _I32]),
     "vti_encode_jpeg": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),

@@ -18,6 +18,14 @@
 //      the LAST record that covers it (atomicMax of record index << 4 | colour index; the fixed record order is, per instance,
 //      contours, box, plate), a thread per box, plate or contour edge paints the rows of its primitive that fall into the tile --
 //      and the tile's final copy applies tint and blend in the same pass (16 pixels = three 16-byte vectors per thread).
+//
+// vti_overlay_frames (frames of differing sizes) runs the FRAMES instantiations of the same kernels: a workgroup takes H0, W0, the
+// words per bitmap row and the places of its frame in dev_frames and of its picture in dev_out / dev_annotated from the rows of the
+// two frame tables (frame_geo), and with native masks the frame's slots from bases[b] on (frame_slots).  The scratch regions are then
+// PITCHED by the largest selected frame (a frame uses the head of its slice; what lies beyond is never read), the grids of the owner
+// and the raster kernel are those of the largest mask slot and the largest frame (workgroups past a frame's own extent leave before
+// the first barrier), and the contour kernel is launched in both instantiations when the selection needs both: each leaves the frames
+// of the other alone, by the frame's own size.  The uniform instantiations read nothing of this.
 #include <climits>
 #include <cstring>
 
@@ -41,7 +49,9 @@ enum { T_CONTOUR = 0, T_RECT = 1, T_PLATE = 2 };
 
 struct OvlArgs {
     const uint8_t* frames; const uint8_t* annotated; uint8_t* out; int* status_out;
-    const int* select; int B, n_sel, H0, W0, WW;
+    const int* select; int B, n_sel, H0, W0, WW;                // FRAMES: the largest selected H0, W0 and their WW (pitches)
+    const FrameRow* rows_in; const FrameRow* rows_out;          // FRAMES: the device frame tables of dev_frames (B rows) and dev_out (n_sel rows)
+    const long long* bases; long long capacity_bytes;           // FRAMES, native: i64 [B + 1] and the bytes of the ragged mask buffer
     const uint8_t* masks; const float* dets; const float* xyxy; const int* counts; const int* offsets;
     int max_det, row, capacity, native, Hm, wpr, Wm;           // a mask slot: Hm rows of wpr 32-bit words, Wm real columns
     const int* plates;
@@ -73,6 +83,40 @@ __device__ __forceinline__ int colour_index(const OvlArgs& a, int b, int i) {
     return m < 0 ? m + a.n_colours : m;
 }
 
+// Picture k = frame b: its size, the shape of one of its mask slots (Hm rows of wpr 32-bit words, Wm real columns) and the byte
+// offsets of the frame in dev_frames and of the picture in dev_out / dev_annotated -- the launch arguments, or the table rows (never
+// above the pitches; the nearest-neighbour factors follow from H0, W0 by the expression the uniform call uses).
+struct Geo { int H0, W0, WW, Hm, wpr, Wm; size_t in, out; };
+template <bool FRAMES>
+__device__ __forceinline__ Geo frame_geo(const OvlArgs& a, int k, int b) {
+    if (!FRAMES) {
+        const size_t px = (size_t)a.H0 * a.W0 * 3;
+        return Geo{a.H0, a.W0, a.WW, a.Hm, a.wpr, a.Wm, (size_t)b * px, (size_t)k * px};
+    }
+    const int H0 = min(max(a.rows_in[b].H0, 1), a.H0), W0 = min(max(a.rows_in[b].W0, 1), a.W0), WW = (W0 + 63) >> 6;
+    const size_t in = (size_t)a.rows_in[b].offset, out = (size_t)a.rows_out[k].offset;
+    if (a.native) return Geo{H0, W0, WW, H0, 2 * WW, W0, in, out};
+    return Geo{H0, W0, WW, a.Hm, a.wpr, a.Wm, in, out};
+}
+
+// The mask slots of frame b (n instances, the first with slot index s0): the slot of instance i starts at 32-bit word
+// word0 + i * Hm * wpr of dev_masks, and the instances lo <= i < hi have one ("live": slot index in [0, capacity), and with the ragged
+// rows of vti_masks_native_frames a slot that ends at or before capacity_bytes; none if bases[b] is no offset of such a buffer).
+struct Slots { long long word0; int lo, hi; };
+template <bool FRAMES>
+__device__ __forceinline__ Slots frame_slots(const OvlArgs& a, const Geo& g, int b, int n, int s0) {
+    const long long slot_words = (long long)g.Hm * g.wpr;
+    Slots sl{(long long)s0 * slot_words, (int)min((long long)n, max(0ll, -(long long)s0)), (int)min((long long)n, (long long)a.capacity - s0)};
+    if (FRAMES && a.native) {
+        const long long base = a.bases[b];
+        const long long fit = base >= 0 && !(base & 7) && a.capacity_bytes > base ? (a.capacity_bytes - base) / (slot_words * 4) : 0;
+        sl.word0 = base >> 2;
+        sl.hi = (int)min((long long)sl.hi, fit);
+    }
+    return sl;
+}
+
+template <bool FRAMES>
 __global__ __launch_bounds__(kThreads) void overlay_owner_kernel(OvlArgs a) {
     __shared__ unsigned char s_ci[VTI_MEASURE_MAX_DET];         // colour index of the instance, 255: no mask slot
     const int tid = threadIdx.x, k = blockIdx.y, M = a.max_det;
@@ -80,20 +124,20 @@ __global__ __launch_bounds__(kThreads) void overlay_owner_kernel(OvlArgs a) {
     if (blockIdx.x == 0 && tid < META_INTS) a.meta[(size_t)k * META_INTS + tid] = 0;
     if (!(a.mode & VTI_OVERLAY_BLEND)) return;                  // uniform: DRAW tints nothing
     const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
-    for (int i = tid; i < n; i += kThreads) {
-        const int s = s0 + i;
-        s_ci[i] = (s >= 0 && s < a.capacity) ? (unsigned char)colour_index(a, b, i) : 255;
-    }
+    const Geo g = frame_geo<FRAMES>(a, k, b);
+    const int words = g.Hm * g.wpr;
+    if (FRAMES && blockIdx.x * kThreads >= words) return;       // the grid is the largest slot's: past this frame's words (the whole workgroup)
+    const Slots sl = frame_slots<FRAMES>(a, g, b, n, s0);
+    for (int i = tid; i < n; i += kThreads) s_ci[i] = (i >= sl.lo && i < sl.hi) ? (unsigned char)colour_index(a, b, i) : 255;
     __syncthreads();
-    const int words = a.Hm * a.wpr;
     const int idx = blockIdx.x * kThreads + tid;
     if (idx >= words) return;
-    const unsigned* bits = (const unsigned*)a.masks;
+    const unsigned* bits = (const unsigned*)a.masks + sl.word0;
     unsigned owned = 0, p0 = 0, p1 = 0, p2 = 0, p3 = 0;
     for (int i = n - 1; i >= 0 && owned != 0xffffffffu; --i) {
         const unsigned ci = s_ci[i];
         if (ci == 255) continue;
-        const unsigned w = bits[((size_t)(s0 + i) * a.Hm) * a.wpr + idx], fresh = w & ~owned;
+        const unsigned w = bits[(size_t)i * words + idx], fresh = w & ~owned;
         if (!fresh) continue;
         owned |= fresh;
         p0 |= (ci & 1) ? fresh : 0; p1 |= (ci & 2) ? fresh : 0; p2 |= (ci & 4) ? fresh : 0; p3 |= (ci & 8) ? fresh : 0;
@@ -103,25 +147,26 @@ __global__ __launch_bounds__(kThreads) void overlay_owner_kernel(OvlArgs a) {
     dst[1] = make_uint4(owned, 0, 0, 0);
 }
 
-// word w (columns 64 w .. 64 w + 63) of row y of an instance's bitmap at the frame size
-__device__ __forceinline__ u64 bitmap_word(const OvlArgs& a, int s, int y, int w, double ify, double ifx, u64 last_valid) {
+// word w (columns 64 w .. 64 w + 63) of row y of an instance's bitmap at the frame size; slot: the instance's mask slot
+__device__ __forceinline__ u64 bitmap_word(const OvlArgs& a, const Geo& g, const unsigned* slot, int y, int w, double ify, double ifx,
+                                           u64 last_valid) {
     u64 acc = 0;
     if (a.native) {
-        acc = ((const u64*)a.masks)[((size_t)s * a.H0 + y) * a.WW + w];
+        acc = ((const u64*)slot)[(size_t)y * g.WW + w];
     } else {
-        const int sy = nn_src(y, ify, a.Hm);
-        const unsigned* srow = (const unsigned*)a.masks + ((size_t)s * a.Hm + sy) * a.wpr;
-        const int c0 = w * 64, c1 = min(c0 + 63, a.W0 - 1);
-        const int q0 = nn_src(c0, ifx, a.Wm) >> 5, q1 = nn_src(c1, ifx, a.Wm) >> 5;
+        const int sy = nn_src(y, ify, g.Hm);
+        const unsigned* srow = slot + (size_t)sy * g.wpr;
+        const int c0 = w * 64, c1 = min(c0 + 63, g.W0 - 1);
+        const int q0 = nn_src(c0, ifx, g.Wm) >> 5, q1 = nn_src(c1, ifx, g.Wm) >> 5;
         unsigned any = 0;
         for (int q = q0; q <= q1; ++q) any |= srow[q];
         if (!any) return 0;
         for (int x = c0; x <= c1; ++x) {
-            const int sx = nn_src(x, ifx, a.Wm);
+            const int sx = nn_src(x, ifx, g.Wm);
             acc |= (u64)((srow[sx >> 5] >> (sx & 31)) & 1u) << (x - c0);
         }
     }
-    return w == a.WW - 1 ? acc & last_valid : acc;
+    return w == g.WW - 1 ? acc & last_valid : acc;
 }
 
 // vertex `pos` of a contour that starts at `base`: (x | y << 16, index of the next vertex, painter's key, 0)
@@ -133,14 +178,17 @@ struct ContEmit {
     }
 };
 
-template <bool IN_LDS>
+template <bool IN_LDS, bool FRAMES>
 __global__ __launch_bounds__(kThreads) void overlay_contour_kernel(OvlArgs a) {
     extern __shared__ u64 s_img[];
     __shared__ int s_w[kThreads / 64];
     __shared__ int s_bad;
     const int tid = threadIdx.x, g = blockIdx.x, k = blockIdx.y, M = a.max_det;
     const int b = min(max(a.select[k], 0), a.B - 1);
-    const int H = a.H0, W = a.W0, WW = a.WW;
+    const Geo geo = frame_geo<FRAMES>(a, k, b);
+    const int H = geo.H0, W = geo.W0, WW = geo.WW;
+    // frames of differing sizes: the instantiation that suits THIS frame's bitmap traces it (overlay_layout's rule), the other leaves
+    if (FRAMES && ((size_t)H * WW * 8 <= (size_t)poly::kLdsBytes) != IN_LDS) return;
     unsigned char* area = a.areas + ((size_t)k * a.groups + g) * a.area_bytes;
     int* const parent_g = (int*)area;
     unsigned* runs = (unsigned*)(area + a.off_runs);
@@ -149,18 +197,21 @@ __global__ __launch_bounds__(kThreads) void overlay_contour_kernel(OvlArgs a) {
     int* meta = a.meta + (size_t)k * META_INTS;
     int4* out = a.cont + (size_t)k * a.max_points;
     const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
-    const double ify = 1.0 / ((double)H / (double)a.Hm), ifx = 1.0 / ((double)W / (double)a.Wm);
+    const Slots sl = frame_slots<FRAMES>(a, geo, b, n, s0);
+    const unsigned* slot0 = (const unsigned*)a.masks + sl.word0;
+    const size_t slot_words = (size_t)geo.Hm * geo.wpr;
+    const double ify = 1.0 / ((double)H / (double)geo.Hm), ifx = 1.0 / ((double)W / (double)geo.Wm);
     const u64 last_valid = (W & 63) ? ((1ull << (W & 63)) - 1) : ~0ull;
     const int trace_bound = 4 * (H + 2) * (W + 2);
     if (tid == 0) s_bad = 0;
     __syncthreads();
     for (int i = g; i < n; i += a.groups) {                     // every bound and branch of this loop is uniform
-        const int s = s0 + i;
-        if (s < 0 || s >= a.capacity) continue;                 // no mask slot: no bitmap
+        if (i < sl.lo || i >= sl.hi) continue;                  // no mask slot: no bitmap
+        const unsigned* slot = slot0 + (size_t)i * slot_words;
         int any = 0;
         for (int idx = tid; idx < H * WW; idx += kThreads) {
             const int y = idx / WW, w = idx - y * WW;
-            const u64 word = bitmap_word(a, s, y, w, ify, ifx, last_valid);
+            const u64 word = bitmap_word(a, geo, slot, y, w, ify, ifx, last_valid);
             img[idx] = word;
             any |= word != 0;
         }
@@ -215,8 +266,8 @@ struct TilePaint {
 
 // the colour index that tints mask pixel (sy, sx), or -1; the planes of the last word read stay in registers
 struct OwnerWord { int idx; uint4 p; unsigned owned; };
-__device__ __forceinline__ int owner_of(const OvlArgs& a, const unsigned* planes, int sy, int sx, OwnerWord& c) {
-    const int idx = sy * a.wpr + (sx >> 5);
+__device__ __forceinline__ int owner_of(int wpr, const unsigned* planes, int sy, int sx, OwnerWord& c) {
+    const int idx = sy * wpr + (sx >> 5);
     if (idx != c.idx) {
         const uint4* src = (const uint4*)(planes + (size_t)idx * kPlaneWords);
         c.p = src[0];
@@ -240,13 +291,16 @@ __device__ __forceinline__ void out_pixel(const OvlArgs& a, const unsigned* s_pa
     }
 }
 
+template <bool FRAMES>
 __global__ __launch_bounds__(kThreads) void overlay_raster_kernel(OvlArgs a) {
     extern __shared__ unsigned s_prio[];        // [kTile]
     __shared__ unsigned s_pal[16];
     const int tid = threadIdx.x, k = blockIdx.y, M = a.max_det;
     const int b = min(max(a.select[k], 0), a.B - 1);
-    const int H0 = a.H0, W0 = a.W0;
+    const Geo g = frame_geo<FRAMES>(a, k, b);
+    const int H0 = g.H0, W0 = g.W0;
     const int npx = H0 * W0, p0 = blockIdx.x * kTile, p1 = min(p0 + kTile, npx);
+    if (FRAMES && p0 >= npx) return;            // the grid is the largest frame's: past this frame's last tile (the whole workgroup)
     const int* meta = a.meta + (size_t)k * META_INTS;
     const bool draw = (a.mode & VTI_OVERLAY_DRAW) != 0, blend = (a.mode & VTI_OVERLAY_BLEND) != 0;
     const bool skipped = draw && (meta[META_BAD] != 0 || meta[META_TOTAL] > a.max_points);
@@ -288,12 +342,12 @@ __global__ __launch_bounds__(kThreads) void overlay_raster_kernel(OvlArgs a) {
         __syncthreads();
     }
     // the tile of the output: drawn pixels over the frame (BLEND: over the caller's picture), blended with the tinted frame
-    const size_t off_in = ((size_t)b * npx + p0) * 3, off_out = ((size_t)k * npx + p0) * 3;
+    const size_t off_in = g.in + (size_t)p0 * 3, off_out = g.out + (size_t)p0 * 3;
     const uint8_t* src = a.frames + off_in;
     const uint8_t* pic = a.mode == VTI_OVERLAY_BLEND ? a.annotated + off_out : src;
     uint8_t* dst = a.out + off_out;
     const unsigned* planes = a.planes + (size_t)k * a.plane_words;
-    const double ify = 1.0 / ((double)H0 / (double)a.Hm), ifx = 1.0 / ((double)W0 / (double)a.Wm);
+    const double ify = 1.0 / ((double)H0 / (double)g.Hm), ifx = 1.0 / ((double)W0 / (double)g.Wm);
     const int np = p1 - p0;
     int done = 0;
     if ((((uintptr_t)src | (uintptr_t)pic | (uintptr_t)dst) & 15) == 0) {     // 16 pixels = 48 bytes = three 16-byte vectors per thread
@@ -313,7 +367,7 @@ __global__ __launch_bounds__(kThreads) void overlay_raster_kernel(OvlArgs a) {
             }
             const int p = p0 + u * 16;
             int y = p / W0, x = p - y * W0;
-            int sy = a.native ? y : nn_src(y, ify, a.Hm);
+            int sy = a.native ? y : nn_src(y, ify, g.Hm);
             OwnerWord cache{-1, make_uint4(0, 0, 0, 0), 0};
             const unsigned char* fb = (const unsigned char*)v;
             const unsigned char* ab = (const unsigned char*)w;
@@ -321,9 +375,9 @@ __global__ __launch_bounds__(kThreads) void overlay_raster_kernel(OvlArgs a) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 int own = -1;
-                if (blend) own = owner_of(a, planes, sy, a.native ? x : nn_src(x, ifx, a.Wm), cache);
+                if (blend) own = owner_of(g.wpr, planes, sy, a.native ? x : nn_src(x, ifx, g.Wm), cache);
                 out_pixel(a, s_pal, fb + 3 * q, ab + 3 * q, pr[q], own, ob + 3 * q);
-                if (++x == W0) { x = 0; ++y; sy = a.native ? y : nn_src(y, ify, a.Hm); }
+                if (++x == W0) { x = 0; ++y; sy = a.native ? y : nn_src(y, ify, g.Hm); }
             }
             uint4* d4 = (uint4*)(dst + (size_t)u * 48);
             d4[0] = res[0]; d4[1] = res[1]; d4[2] = res[2];
@@ -335,7 +389,7 @@ __global__ __launch_bounds__(kThreads) void overlay_raster_kernel(OvlArgs a) {
         int own = -1;
         if (blend) {
             OwnerWord cache{-1, make_uint4(0, 0, 0, 0), 0};
-            own = owner_of(a, planes, a.native ? y : nn_src(y, ify, a.Hm), a.native ? x : nn_src(x, ifx, a.Wm), cache);
+            own = owner_of(g.wpr, planes, a.native ? y : nn_src(y, ify, g.Hm), a.native ? x : nn_src(x, ifx, g.Wm), cache);
         }
         unsigned char fr[3], an[3], o[3];
 #pragma unroll
@@ -372,7 +426,7 @@ hipError_t launch_overlay(const uint8_t* frames, int B, int H0, int W0, const ui
                           const float* xyxy, const int* counts, const int* offsets, int max_det, int nm, int capacity, int H, int W,
                           const int* plates, const uint8_t* palette, int n_colours, float alpha, float beta, const int* select,
                           int n_sel, int mode, const uint8_t* annotated, int max_points, uint8_t* out, int* status, void* scratch,
-                          hipStream_t st) {
+                          hipStream_t st, const OverlayFrames* fr) {
     OverlayLayout L;
     overlay_layout(n_sel, max_det, H0, W0, H, W, max_points, L);
     unsigned char* ws = (unsigned char*)scratch;
@@ -380,6 +434,7 @@ hipError_t launch_overlay(const uint8_t* frames, int B, int H0, int W0, const ui
     memset(&a, 0, sizeof a);
     a.frames = frames; a.annotated = annotated; a.out = out; a.status_out = status;
     a.select = select; a.B = B; a.n_sel = n_sel; a.H0 = H0; a.W0 = W0; a.WW = L.WW;
+    if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; a.bases = fr->bases; a.capacity_bytes = fr->capacity_bytes; }
     a.masks = masks; a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
     a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.native = native;
     a.Hm = native ? H0 : H; a.wpr = native ? 2 * L.WW : W >> 5; a.Wm = native ? W0 : W;
@@ -392,17 +447,31 @@ hipError_t launch_overlay(const uint8_t* frames, int B, int H0, int W0, const ui
     a.plane_words = L.plane_words;
     a.areas = ws + L.off_areas; a.area_bytes = L.area_bytes; a.off_runs = L.off_runs; a.off_rows = L.off_rows; a.off_img = L.off_img;
     a.groups = L.groups;
-    const int owner_blocks = (mode & VTI_OVERLAY_BLEND) ? (a.Hm * a.wpr + kThreads - 1) / kThreads : 1;
-    hipLaunchKernelGGL(overlay_owner_kernel, dim3(owner_blocks, n_sel), dim3(kThreads), 0, st, a);
+    // the owner grid: the words of a mask slot -- with native rows of differing sizes those of the largest selected frame's
+    const long long slot_words = fr && native ? fr->max_slot_words : (long long)a.Hm * a.wpr;
+    const int owner_blocks = (mode & VTI_OVERLAY_BLEND) ? (int)((slot_words + kThreads - 1) / kThreads) : 1;
+    if (fr) hipLaunchKernelGGL(overlay_owner_kernel<true>, dim3(owner_blocks, n_sel), dim3(kThreads), 0, st, a);
+    else hipLaunchKernelGGL(overlay_owner_kernel<false>, dim3(owner_blocks, n_sel), dim3(kThreads), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (mode & VTI_OVERLAY_DRAW) {
-        if (L.in_lds) e = launch_lds<overlay_contour_kernel<true>>(dim3(L.groups, n_sel), dim3(kThreads), (size_t)poly::kLdsBytes, st, a);
-        else e = launch_lds<overlay_contour_kernel<false>>(dim3(L.groups, n_sel), dim3(kThreads), 0, st, a);
+        const dim3 grid(L.groups, n_sel);
+        if (fr) {
+            if (fr->any_lds) {
+                e = launch_lds<overlay_contour_kernel<true, true>>(grid, dim3(kThreads), (size_t)poly::kLdsBytes, st, a);
+                if (e != hipSuccess) return e;
+            }
+            if (fr->any_global) e = launch_lds<overlay_contour_kernel<false, true>>(grid, dim3(kThreads), 0, st, a);
+        } else if (L.in_lds) {
+            e = launch_lds<overlay_contour_kernel<true, false>>(grid, dim3(kThreads), (size_t)poly::kLdsBytes, st, a);
+        } else {
+            e = launch_lds<overlay_contour_kernel<false, false>>(grid, dim3(kThreads), 0, st, a);
+        }
         if (e != hipSuccess) return e;
     }
-    const int tiles = (int)(((long long)H0 * W0 + kTile - 1) / kTile);
-    hipLaunchKernelGGL(overlay_raster_kernel, dim3(tiles, n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
+    const int tiles = (int)(((fr ? fr->max_px : (long long)H0 * W0) + kTile - 1) / kTile);
+    if (fr) hipLaunchKernelGGL(overlay_raster_kernel<true>, dim3(tiles, n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
+    else hipLaunchKernelGGL(overlay_raster_kernel<false>, dim3(tiles, n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
     return hipGetLastError();
 }
 

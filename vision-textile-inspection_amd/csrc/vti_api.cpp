@@ -1326,6 +1326,98 @@ int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_
     return VTI_OK;
 }
 
+// ---- vti_overlay for frames of differing sizes -----------------------------------------------------------------------------
+int64_t vti_overlay_frames_scratch_bytes(const vti_ctx* c, const void* host_out_table, int32_t max_det, int32_t max_points) {
+    if (!c || !host_out_table) return 0;
+    const FrameTableHeader h = table_header(host_out_table);
+    if (h.magic != kFrameTableMagic || h.B < 1) return 0;
+    int32_t mh = 0, mw = 0;                       // of the rows themselves (the header's maxima are only an upper bound)
+    for (int32_t k = 0; k < h.B; ++k) {
+        const FrameRow r = table_row(host_out_table, k);
+        mh = std::max(mh, r.H0); mw = std::max(mw, r.W0);
+    }
+    return vti_overlay_scratch_bytes(c, h.B, max_det, mh, mw, max_points);
+}
+
+int32_t vti_overlay_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                           const uint8_t* masks, int32_t native, const int64_t* mask_bases, int64_t capacity_bytes, const float* dets,
+                           const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det, int32_t capacity,
+                           const int32_t* plates, const uint8_t* host_palette, int32_t n_colours, float alpha, float beta,
+                           const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t mode, const uint8_t* annotated,
+                           int32_t max_points, const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status,
+                           void* scratch, size_t scratch_bytes, void* stream) {
+    // every check comes before the first HIP call
+    char msg[200];
+    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
+    if (!c) return bad("vti_overlay_frames: null ctx");
+    FrameTableHeader hi, ho;
+    if (int32_t rc = frames_check("vti_overlay_frames", c, host_table, dev_table, B, hi)) return rc;
+    if (n_sel < 1) return bad("vti_overlay_frames: n_sel must be >= 1");
+    if (int32_t rc = frames_check("vti_overlay_frames (out table)", c, host_out_table, dev_out_table, n_sel, ho)) return rc;
+    if (capacity < 0 || (native != 0 && native != 1) || max_det < 1 || max_det > VTI_MEASURE_MAX_DET || max_points < 0)
+        return bad("vti_overlay_frames: bad size (capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0 or 1)");
+    if (mode != VTI_OVERLAY_DRAW && mode != VTI_OVERLAY_BLEND && mode != VTI_OVERLAY_BOTH)
+        return bad("vti_overlay_frames: mode must be VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND or VTI_OVERLAY_BOTH");
+    if (n_colours < 1 || n_colours > 16) return bad("vti_overlay_frames: n_colours must be 1 .. 16");
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return bad("vti_overlay_frames: alpha and beta must be finite");
+    if ((annotated != nullptr) != (mode == VTI_OVERLAY_BLEND))
+        return bad("vti_overlay_frames: dev_annotated must be given with VTI_OVERLAY_BLEND and only then");
+    if (!native && mask_bases) return bad("vti_overlay_frames: dev_mask_bases must be NULL with letterbox masks (native = 0)");
+    if (native && !mask_bases) return bad("vti_overlay_frames: native masks need dev_mask_bases (vti_masks_native_frames)");
+    if (capacity_bytes < 0) return bad("vti_overlay_frames: capacity_bytes must be >= 0");
+    const bool need_masks = capacity > 0 && (!native || capacity_bytes > 0);
+    if (!frames || !dets || !xyxy || !counts || !offsets || !host_palette || !host_select || !dev_select || !out || !status ||
+        (need_masks && !masks))
+        return bad("vti_overlay_frames: null pointer");
+    int32_t mh = 0, mw = 0;
+    long long max_px = 0, max_slot_words = 1;
+    bool any_lds = false, any_global = false;
+    for (int32_t k = 0; k < n_sel; ++k) {
+        const int32_t b = host_select[k];
+        if (b < 0 || b >= B) {
+            snprintf(msg, sizeof msg, "vti_overlay_frames: host_select[%d] = %d is outside [0, %d)", k, b, B);
+            return bad(msg);
+        }
+        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
+        if (ri.H0 > 8192 || ri.W0 > 8192) {
+            snprintf(msg, sizeof msg, "vti_overlay_frames: frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
+            return bad(msg);
+        }
+        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
+            snprintf(msg, sizeof msg, "vti_overlay_frames: row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k,
+                     ro.H0, ro.W0, k, b, ri.H0, ri.W0);
+            return bad(msg);
+        }
+        mh = std::max(mh, ri.H0); mw = std::max(mw, ri.W0);
+        max_px = std::max(max_px, (long long)ri.H0 * ri.W0);
+        OverlayLayout one;                        // the frame's own bitmap: which tracer serves it, and the words of its native slot
+        overlay_layout(1, 1, ri.H0, ri.W0, c->plan.desc.H, c->plan.desc.W, 0, one);
+        (one.in_lds ? any_lds : any_global) = true;
+        max_slot_words = std::max(max_slot_words, (long long)ri.H0 * 2 * one.WW);
+    }
+    if (!annotate_sizes_ok(n_sel, max_det, mh, mw, max_points)) return bad("vti_overlay_frames: the selection is too large");
+    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 15) || ((uintptr_t)annotated & 15))
+        return bad("vti_overlay_frames: dev_frames, dev_out and dev_annotated must be 16-byte aligned");
+    if (((uintptr_t)dev_select & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)status & 3) ||
+        ((uintptr_t)dets & 3) || ((uintptr_t)xyxy & 3))
+        return bad("vti_overlay_frames: the index arrays, rows and status must be 4-byte aligned");
+    if (mask_bases && ((uintptr_t)mask_bases & 7)) return bad("vti_overlay_frames: dev_mask_bases must be 8-byte aligned");
+    if (plates && ((uintptr_t)plates & 15)) return bad("vti_overlay_frames: dev_plates must be 16-byte aligned");
+    if (need_masks && ((uintptr_t)masks & (native ? 7 : 15)))
+        return bad(native ? "vti_overlay_frames: native masks must be 8-byte aligned" : "vti_overlay_frames: masks must be 16-byte aligned");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_overlay_frames: scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_overlay_scratch_bytes(c, n_sel, max_det, mh, mw, max_points))
+        return bad("vti_overlay_frames: scratch smaller than vti_overlay_frames_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_overlay_frames")) return drc;
+    const vti_desc& d = c->plan.desc;
+    const OverlayFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), (const long long*)mask_bases, capacity_bytes,
+                           max_slot_words, any_lds, any_global, max_px};
+    VTI_HIP(c, launch_overlay(frames, B, mh, mw, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H, d.W, plates,
+                              host_palette, n_colours, alpha, beta, dev_select, n_sel, mode, annotated, max_points, out, status, scratch,
+                              (hipStream_t)stream, &fr), "overlay kernels");
+    return VTI_OK;
+}
+
 int64_t vti_encode_jpeg_scratch_bytes(const vti_ctx* c, int32_t n, int32_t H0, int32_t W0) {
     JpegLayout L;
     if (!c || !encode_jpeg_layout(n, H0, W0, L)) return 0;

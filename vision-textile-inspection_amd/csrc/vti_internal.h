@@ -374,12 +374,21 @@ struct OverlayLayout {
     size_t off_meta, off_cont, off_planes, off_areas, plane_words, area_bytes, off_runs, off_rows, off_img, total;
 };
 void overlay_layout(int n_sel, int max_det, int H0, int W0, int Hm, int Wm, int max_points, OverlayLayout& L);
+// vti_overlay_frames: the rows of the device frame tables of dev_frames and dev_out; H0, W0 passed to launch_overlay are then the largest
+// selected ones (the pitches of the scratch).  native = 1: the masks are the ragged rows of vti_masks_native_frames -- bases (device,
+// i64 [B + 1]), capacity_bytes, and max_slot_words, the most 32-bit words a selected frame's slot has (the owner grid).  any_lds /
+// any_global: a selected frame's bitmap fits / does not fit the tracer's LDS image (which contour instantiations are launched);
+// max_px: the most pixels a selected frame has (the raster grid).
+struct OverlayFrames {
+    const FrameRow* rows_in; const FrameRow* rows_out; const long long* bases; long long capacity_bytes, max_slot_words;
+    bool any_lds, any_global; long long max_px;
+};
 // palette: host, 3 * n_colours bytes (BGR); select: the device copy of the (host-checked) selection; H, W: the letterbox mask size
 hipError_t launch_overlay(const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks, int native, const float* dets,
                           const float* xyxy, const int* counts, const int* offsets, int max_det, int nm, int capacity, int H, int W,
                           const int* plates, const uint8_t* palette, int n_colours, float alpha, float beta, const int* select,
                           int n_sel, int mode, const uint8_t* annotated, int max_points, uint8_t* out, int* status, void* scratch,
-                          hipStream_t st);
+                          hipStream_t st, const OverlayFrames* fr = nullptr);
 
 // jpeg.hip: vti_encode_jpeg (the saved JPEG).  The scratch holds: the header's bytes (1 KiB) | bit total u64 [n] | file size i64 [n] |
 // coefficients i16 [n, MCUs, 6, 64] | block bit positions u64 [n, blocks] | the unstuffed stream, NC chunks of 4096 bytes per frame

@@ -655,13 +655,7 @@ class Engine:
         if table is not None:
             self._check_frames(table, buf=frames)
             shapes = tuple(table.shapes[int(b)] for b in sel)
-            cache = self.__dict__.setdefault("_out_tables", {})          # (shapes, device) -> FrameTable, the 16 latest selections
-            out_table = cache.pop((shapes, str(dev)), None)
-            if out_table is None:
-                out_table = self.pack_frames(shapes, dev)[0]
-                while len(cache) >= 16:
-                    del cache[next(iter(cache))]
-            cache[(shapes, str(dev))] = out_table                       # (re)inserted last: the oldest entry is the first
+            out_table = self._out_table(shapes, dev)                     # the 16 latest selections are kept
             if "buf" not in r:
                 r["buf"] = torch.empty(out_table.total_bytes, dtype=torch.uint8, device=dev)
             self._check_frames(out_table, buf=r["buf"])
@@ -699,8 +693,19 @@ class Engine:
     def overlay_scratch_bytes(self, n_sel, max_det, H0, W0, max_points):
         return int(lib().vti_overlay_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))
 
+    def _out_table(self, shapes, dev):
+        """The FrameTable of a selection's pictures (pack_frames of its shapes): the 16 latest tuples of shapes are kept, per device."""
+        cache = self.__dict__.setdefault("_out_tables", {})              # (shapes, device) -> FrameTable
+        out_table = cache.pop((shapes, str(dev)), None)
+        if out_table is None:
+            out_table = self.pack_frames(shapes, dev)[0]
+            while len(cache) >= 16:
+                del cache[next(iter(cache))]
+        cache[(shapes, str(dev))] = out_table                           # (re)inserted last: the oldest entry is the first
+        return out_table
+
     def overlay(self, frames, out, select, native=False, plates=None, mode="both", annotated=None, alpha=0.30, beta=0.70,
-                palette=_ov.PALETTE, max_points=16384, result=None):
+                palette=_ov.PALETTE, max_points=16384, result=None, table=None, mask_bases=None, capacity_bytes=None):
         """The frames `select` of the batch as check_model.py's annotate_result shows them (without the label text): vti_overlay,
         byte for byte overlay.render(...).  frames: the contiguous uint8 [B,H0,W0,3] BGR device batch predict consumed; out: its
         output set; select: host integers in [0, B), any order, duplicates allowed (ValueError otherwise); native: the masks are
@@ -710,15 +715,32 @@ class Engine:
         palette: BGR triplets, 1..16 (overlay.PALETTE).  max_points: room for the contour vertices of one frame.  Returns device
         tensors, no host synchronisation: dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]: VTI_OVERLAY_OUTLINE_SKIPPED where the
         contours did not fit); "frames" feeds encode_jpeg unchanged.  `result`: the same dict preallocated.  The scratch is kept per
-        (n_sel, H0, W0)."""
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("overlay: frames must be a uint8 [B,H0,W0,3] tensor")
-        B, H0, W0, _ = frames.shape
+        (n_sel, H0, W0).
+        table (vti_overlay_frames): the FrameTable of a batch whose frames differ in size; `frames` is then the flat u8 device buffer
+        the table describes (what predict_frames_into consumed) and frame select[k] is drawn at its own size.  Returns dict(buf=u8
+        flat, table=the FrameTable of the selection (the 16 latest are kept), shapes, byte_offsets, status) as annotate(table=) does:
+        picture k is buf[byte_offsets[k]:][:3 * H0 * W0].view(H0, W0, 3), and (buf, table) is what encode_jpeg(..., table=) takes.
+        annotated: a flat u8 buffer of the out table's size (e.g. "draw"'s buf with text put on it; it may be result["buf"] itself).
+        native=True: the masks are the ragged rows of a set from alloc_outputs(native_frames=) (masks_native_frames); mask_bases and
+        capacity_bytes default to out["mask_bases"] and the whole of out["masks"], and plates are then int32 [B * max_det, 4] per
+        slot index.  `result` may preallocate buf and status."""
+        if table is not None:
+            self._check_frames(table)
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
+                raise ValueError("overlay: with table=, frames must be the flat uint8 frame buffer")
+            B, H0, W0 = table.B, None, None
+        else:
+            if mask_bases is not None or capacity_bytes is not None:
+                raise ValueError("overlay: mask_bases and capacity_bytes belong to table= (frames of differing sizes)")
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError("overlay: frames must be a uint8 [B,H0,W0,3] tensor")
+            B, H0, W0, _ = frames.shape
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
             raise ValueError(f"overlay: {B} frames but an output set of {out['counts'].shape[0]}")
         max_det, capacity = dets.shape[1], masks.shape[0]
+        ragged = table is not None and bool(native)
         sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
         if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
             raise ValueError("overlay: select must be a non-empty sequence of frame indices")
@@ -736,38 +758,85 @@ class Engine:
             raise ValueError("overlay: palette must be 1 .. 16 BGR triplets")
         if not (np.isfinite(alpha) and np.isfinite(beta)):
             raise ValueError("overlay: alpha and beta must be finite")
-        if capacity:
-            want = (H0, 8 * -(-W0 // 64)) if native else (self.H, self.W // 8)
-            if masks.dtype != torch.uint8 or tuple(masks.shape[1:]) != want:
-                raise ValueError(f"overlay: masks must be uint8 [capacity, {want[0]}, {want[1]}] ({'frame-size rows' if native else 'letterbox bits'})")
+        if ragged:
+            if mask_bases is None:
+                mask_bases = out.get("mask_bases")
+            if masks.dtype != torch.uint8 or masks.dim() != 1 or not masks.is_contiguous() or not isinstance(mask_bases, torch.Tensor) \
+                    or mask_bases.dtype != torch.int64 or tuple(mask_bases.shape) != (B + 1,) or not mask_bases.is_contiguous():
+                raise ValueError("overlay: native masks for frames of differing sizes are the flat uint8 buffer of masks_native_frames "
+                                 f"with its int64 [{B + 1}] mask_bases (alloc_outputs(..., native_frames=table))")
+            if capacity_bytes is None:
+                capacity_bytes = masks.numel()
+            if not 0 <= int(capacity_bytes) <= masks.numel():
+                raise ValueError(f"overlay: capacity_bytes must be in [0, {masks.numel()}]")
+            capacity = B * max_det                                      # slot indices: the per-slot rows (plates) are B * max_det
+        else:
+            if mask_bases is not None or capacity_bytes is not None:
+                raise ValueError("overlay: mask_bases and capacity_bytes belong to native=True (the ragged frame-size rows)")
+            if capacity:
+                want = (H0, 8 * -(-W0 // 64)) if native else (self.H, self.W // 8)
+                if masks.dtype != torch.uint8 or masks.dim() != 3 or tuple(masks.shape[1:]) != want:
+                    raise ValueError(f"overlay: masks must be uint8 [capacity, {want[0]}, {want[1]}] ({'frame-size rows' if native else 'letterbox bits'})")
+        if table is not None:
+            shapes = tuple(table.shapes[int(b)] for b in sel)
+            out_bytes = sum(-(-3 * h * w // 16) * 16 for h, w in shapes)     # pack_frames: every picture starts at a multiple of 16
+            if annotated is not None and not (isinstance(annotated, torch.Tensor) and annotated.dtype == torch.uint8 and annotated.dim() == 1
+                                              and annotated.numel() == out_bytes):
+                raise ValueError(f"overlay: with table=, annotated must be a flat uint8 buffer of the out table's {out_bytes} bytes")
         # everything above is about shapes and values; what needs a device comes from here on
         if not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("overlay: frames must be the contiguous device batch predict consumed")
         if plates is not None and not (isinstance(plates, torch.Tensor) and plates.dtype == torch.int32 and plates.is_contiguous()
                                        and tuple(plates.shape) == (capacity, 4) and plates.device == dev):
             raise ValueError(f"overlay: plates must be a contiguous int32 [{capacity},4] tensor on the outputs' device")
-        if annotated is not None and not (isinstance(annotated, torch.Tensor) and annotated.dtype == torch.uint8 and annotated.is_contiguous()
-                                          and tuple(annotated.shape) == (n_sel, H0, W0, 3) and annotated.device == dev):
-            raise ValueError(f"overlay: annotated must be a contiguous uint8 [{n_sel},{H0},{W0},3] tensor on the outputs' device")
         r = dict(result or {})
         if "status" not in r:
             r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
-        if "frames" not in r:
-            r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
-        need = self.overlay_scratch_bytes(n_sel, max_det, H0, W0, max_points)
-        if need <= 0:
-            raise ValueError(f"overlay: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+        if table is not None:
+            self._check_frames(table, buf=frames)
+            if ragged and not (masks.is_cuda and mask_bases.device == dev):
+                raise ValueError("overlay: the output set must be in device memory")
+            out_table = self._out_table(shapes, dev)
+            if out_table.total_bytes != out_bytes:
+                raise ValueError(f"overlay: the out table holds {out_table.total_bytes} bytes, {out_bytes} expected")
+            if annotated is not None and not (annotated.is_contiguous() and annotated.device == dev):
+                raise ValueError("overlay: annotated must be a contiguous buffer on the outputs' device")
+            if "buf" not in r:
+                r["buf"] = torch.empty(out_table.total_bytes, dtype=torch.uint8, device=dev)
+            self._check_frames(out_table, buf=r["buf"])
+            r.update(table=out_table, shapes=list(shapes), byte_offsets=list(out_table.byte_offsets))
+            need = int(lib().vti_overlay_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
+            if need <= 0:
+                raise ValueError(f"overlay: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
+                                 f"{out_table.max_H0}x{out_table.max_W0}, max_points={max_points}; a drawn frame is at most 8192 x 8192)")
+        else:
+            if annotated is not None and not (isinstance(annotated, torch.Tensor) and annotated.dtype == torch.uint8 and annotated.is_contiguous()
+                                              and tuple(annotated.shape) == (n_sel, H0, W0, 3) and annotated.device == dev):
+                raise ValueError(f"overlay: annotated must be a contiguous uint8 [{n_sel},{H0},{W0},3] tensor on the outputs' device")
+            if "frames" not in r:
+                r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
+            need = self.overlay_scratch_bytes(n_sel, max_det, H0, W0, max_points)
+            if need <= 0:
+                raise ValueError(f"overlay: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
         ws = getattr(self, "_overlay_ws", None)
         if ws is None or ws.numel() < need or ws.device != dev:
             self._overlay_ws = None
             ws = self._overlay_ws = torch.empty(need, dtype=torch.uint8, device=dev)
         dev_sel = torch.from_numpy(sel).to(dev)
+        have_masks = capacity and (not ragged or int(capacity_bytes))
+        tail = (_ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
+                _ptr(plates) if plates is not None and capacity else C.c_void_p(0), C.c_void_p(pal.ctypes.data), int(pal.shape[0]),
+                float(alpha), float(beta), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(mode_i), _ptr(annotated),
+                int(max_points))
+        if table is not None:
+            check(self._ctx, lib().vti_overlay_frames(
+                self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(masks) if have_masks else C.c_void_p(0), int(ragged),
+                _ptr(mask_bases) if ragged else C.c_void_p(0), int(capacity_bytes) if ragged else 0, *tail, *out_table._ptrs(),
+                _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+            return r
         check(self._ctx, lib().vti_overlay(
-            self._ctx, _ptr(frames), B, H0, W0, _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets),
-            _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
-            _ptr(plates) if plates is not None and capacity else C.c_void_p(0), C.c_void_p(pal.ctypes.data), int(pal.shape[0]),
-            float(alpha), float(beta), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(mode_i), _ptr(annotated),
-            int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+            self._ctx, _ptr(frames), B, H0, W0, _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), *tail,
+            _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         return r
 
     # ---- the saved JPEG (cv2.imwrite(save_path, annotated), main.py:314): vti_encode_jpeg ----------------------------------

@@ -31,6 +31,10 @@ import numpy as np
 
 from . import annotate, polygons
 
+__all__ = ["PALETTE", "DRAW", "BLEND", "BOTH", "MODES", "OUTLINE_SKIPPED", "ALPHA", "BETA", "FONT", "FONT_SCALE", "FONT_THICKNESS",
+           "colour", "instance_bitmap", "tint", "contours", "display_list", "fill_rect", "rasterise", "add_weighted",
+           "add_weighted_unfused", "render", "label_name", "label_items", "plates", "put_labels", "annotate_result", "annotate_results"]
+
 # BGR: build_color's palette (check_model.py:157-164), in its order
 PALETTE = ((0, 255, 0), (0, 165, 255), (255, 0, 255), (255, 255, 0), (0, 255, 255), (255, 128, 0))
 DRAW, BLEND, BOTH = 1, 2, 3
@@ -267,3 +271,100 @@ def annotate_result(frame, result, names=None, labels=None):
     pic = put_labels(drawn[0].cpu().numpy(), items)
     back = torch.from_numpy(pic).to(dev).unsqueeze(0)
     return eng.overlay(dframe, out, [0], native=native, mode="blend", annotated=back)["frames"][0].cpu().numpy()
+
+
+def annotate_results(frames, results, names=None, labels=None):
+    """The batch form of annotate_result: `frames` is the list (or [B,h,w,3] array) one YOLO.predict call took and `results` its list
+    of Results; the frames may differ in size and the masks may be letterbox ones or those of retina_masks=True (mixed=True for
+    sizes that differ).  Every frame with detections is drawn at its own size by ONE Engine.overlay(..., table=) call on the flat
+    frame buffer (vti_overlay_frames).  Without labels: BOTH and one copy to the host.  With labels (None: where cv2 is
+    importable): DRAW, one copy out, put_labels per picture, one copy back, BLEND.  -> [u8 [h,w,3] ndarray], each byte for byte
+    annotate_result(frames[b], results[b], names, labels); a frame without detections is its bare copy.  All results must come
+    from one Engine (RuntimeError without one; there is no CPU fallback)."""
+    import torch
+    frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+    results = list(results)
+    if len(frames) != len(results):
+        raise ValueError(f"annotate_results: {len(frames)} frames but {len(results)} results")
+    for f in frames:
+        if f.ndim != 3 or f.shape[2] != 3:
+            raise ValueError(f"annotate_results: every frame must be uint8 HxWx3, got shape {f.shape}")
+    counts = [len(r.boxes) if getattr(r, "boxes", None) is not None else 0 for r in results]
+    sel = [b for b, n in enumerate(counts) if n]
+    pics = [f.copy() for f in frames]
+    if not sel:
+        return pics
+    eng = getattr(results[sel[0]], "_engine", None)
+    if eng is None or any(getattr(results[b], "_engine", None) is not eng for b in sel):
+        raise RuntimeError("overlay.annotate_results needs the one Engine that made the results (one YOLO.predict call's Results); "
+                           "there is no host path")
+    if labels is None:
+        labels = _have_cv2()
+    B, M = len(frames), max(counts)
+    shapes = tuple(f.shape[:2] for f in frames)
+    dev = results[sel[0]].boxes.data.device
+    # frame-size rows or letterbox bits: a frame of the canvas's own size whose width is a multiple of 64 has the same layout in
+    # both forms (and the same picture), so it does not vote; only a real mix is refused
+    natives = set()
+    for b in sel:
+        m, (h, w) = results[b].masks, shapes[b]
+        if m is None:
+            continue
+        rows, as_native, as_letterbox = tuple(m.bits.shape[1:]), (h, 8 * -(-w // 64)), (eng.H, eng.W // 8)
+        if not (as_native == as_letterbox and m._W == w):
+            natives.add(rows == as_native and m._W == w)
+    if len(natives) > 1:
+        raise ValueError("annotate_results: the results mix letterbox masks and frame-size masks")
+    native = bool(natives and natives.pop())
+    row = results[sel[0]].dets.shape[-1]
+    dets = torch.zeros((B, M, row), dtype=torch.float32, device=dev)
+    xyxy = torch.zeros((B, M, 4), dtype=torch.float32, device=dev)
+    bits = []
+    for b in sel:
+        n = counts[b]
+        dets[b, :n] = results[b].dets.reshape(n, row)
+        xyxy[b, :n] = results[b].boxes.data[:, :4]
+        if results[b].masks is not None:
+            bits.append(results[b].masks.bits.contiguous())
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    out = dict(dets=dets, xyxy=xyxy, counts=torch.tensor(counts, dtype=torch.int32, device=dev), offsets=torch.from_numpy(offsets).to(dev))
+    if native:          # the ragged rows of masks_native_frames: frame b's n slots back to back from mask_bases[b] on
+        nbytes = [results[b].masks.bits.numel() if counts[b] and results[b].masks is not None else 0 for b in range(B)]
+        out["masks"] = torch.cat([m.reshape(-1) for m in bits]) if bits else torch.zeros(0, dtype=torch.uint8, device=dev)
+        out["mask_bases"] = torch.from_numpy(np.concatenate([[0], np.cumsum(nbytes)]).astype(np.int64)).to(dev)
+        slots = B * M
+    else:
+        out["masks"] = torch.cat(bits) if bits else torch.zeros((0, eng.H, eng.W // 8), dtype=torch.uint8, device=dev)
+        slots = int(out["masks"].shape[0])
+    table = eng.pack_frames(shapes, dev)[0]
+    flat = np.zeros(table.total_bytes, np.uint8)
+    for f, at in zip(frames, table.byte_offsets):
+        flat[at:at + f.size] = f.reshape(-1)
+    dflat = torch.from_numpy(flat).to(dev)
+
+    def cut(host, got):
+        for k, b in enumerate(sel):
+            h, w = shapes[b]
+            at = got["byte_offsets"][k]
+            pics[b] = host[at:at + 3 * h * w].reshape(h, w, 3)
+        return pics
+    if not labels:
+        got = eng.overlay(dflat, out, sel, native=native, mode="both", table=table)
+        return cut(got["buf"].cpu().numpy(), got)
+    items, rows = {}, np.zeros((max(slots, 1), 4), np.int32)
+    for b in sel:
+        host = results[b].boxes.data.cpu().numpy()
+        items[b] = label_items(host[:, 5], host[:, 4], host[:, :4], names)
+        pl = plates(items[b])
+        live = max(0, min(counts[b], slots - int(offsets[b])))
+        rows[offsets[b]:offsets[b] + live] = pl[:live]
+    got = eng.overlay(dflat, out, sel, native=native, plates=torch.from_numpy(rows[:slots]).to(dev) if slots else None, mode="draw",
+                      table=table)
+    host = got["buf"].cpu().numpy()
+    for k, b in enumerate(sel):                     # the text goes into `host` itself, whatever put_labels returns
+        h, w = shapes[b]
+        view = host[got["byte_offsets"][k]:][:3 * h * w].reshape(h, w, 3)
+        view[...] = put_labels(view, items[b])
+    back = torch.from_numpy(host).to(dev)
+    got = eng.overlay(dflat, out, sel, native=native, mode="blend", annotated=back, table=table)
+    return cut(got["buf"].cpu().numpy(), got)
