@@ -275,6 +275,46 @@ int32_t vti_measure(vti_ctx* ctx, const vti_measure_params* params, const uint8_
                     int32_t capacity, int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
                     int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
 
+/* ---- the stitch-distance checker's measurement on device (Utils/check_stitch_distance.py:281-553, the drawing left out) ------- */
+/* Settings of vti_measure_checker: the calibration as in vti_measure_params, and the checker's module constants.  Defaults
+ * (check_stitch_distance.py:20-39): stitch_id 0, fabric_id 1, min_stitches 3, max_px_distance 150, envelope_neighborhood 3,
+ * skip_cluster 0, kmeans_iters 10, frame_buffer 8.  There is no ROI and no two_row threshold: the checker has neither.  drop_empty
+ * and frame_buffer: as in vti_measure_params. */
+typedef struct {
+    double K[9], dist[5], R[9], t[3];
+    double max_px_distance;            /* keep a stitch when 0 < cy - round(median envelope) < this (:442-443) */
+    int32_t stitch_id, fabric_id;      /* class ids, >= 0 and different */
+    int32_t min_stitches;              /* >= 1: an average needs at least this many values */
+    int32_t envelope_neighborhood;     /* 0..64 columns either side of a stitch centre */
+    int32_t skip_cluster;              /* 0: 2-means row selection; 1: every stitch is selected */
+    int32_t kmeans_iters;              /* kmeans_1d_two_clusters' max_iters (the checker passes none: 10) */
+    int32_t drop_empty;
+    int32_t frame_buffer;
+} vti_checker_params;
+
+/* The checker's process_frame for B frames of one size at once, from the outputs of one predict.  Inputs, `native`, the scratch
+ * (vti_measure_scratch_bytes(), 256-byte aligned) and the four outputs' layouts are vti_measure's; every argument check (VTI_ERR_ARG,
+ * max_det above VTI_MEASURE_MAX_DET included) runs before the first HIP call.  What the checker computes differently:
+ *   - no ROI.  Every kept fabric_id instance joins the fabric union: its nearest-resized mask if that has a set pixel, else the
+ *     filled rectangle (int x1, int y1)..(int x2, int y2), corners inclusive, clipped to the frame (:329-334).  n_fabric counts
+ *     all of them.  With drop_empty = 1 an instance whose mask is empty as predict returns it does not exist, box included.
+ *     VTI_MEASURE_NO_FABRIC when the union is empty;
+ *   - the fabric edge is the UPPER envelope: the smallest set row per column, -1 where there is none (:238-251);
+ *   - row selection (:408-429): 2-means on the centroids' y with the checker's own kmeans_1d_two_clusters (:143-171, which returns
+ *     the labels of its last assignment); the chosen cluster is the one whose mean is nearer to the mean envelope row, a tie is
+ *     cluster 1; skip_cluster = 1 or fewer than 2 stitches: every stitch;
+ *   - VTI_STITCH_NEAR is the signed test 0 < cy - round(median) < max_px_distance: the stitch lies strictly below the edge
+ *     (:431-444, any stitch); the final set is the selected stitches with it, or every selected stitch when none has it;
+ *   - width_mm, edge_y, dist_mm, VTI_STITCH_WIDTH and VTI_STITCH_DIST are set for the final set only.  A width whose left or
+ *     right end has no world point is px_width / 10 * |world(cx + 10, cy) - world(cx, cy)| when those two exist (:488-507);
+ *   - n_dist = len(per_dists), n_width = len(per_widths): the `n` of the checker's info text (:515, :533-540).
+ * Three launches on `stream`; no host synchronisation.  Smoothing over frames (:519-530) is the caller's. */
+int32_t vti_measure_checker(vti_ctx* ctx, const vti_checker_params* params, const uint8_t* dev_masks, int32_t native,
+                            const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets,
+                            int32_t B, int32_t max_det, int32_t capacity, int32_t H0, int32_t W0, void* dev_scratch,
+                            size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
+                            void* stream);
+
 /* ---- vti_measure for a batch that mixes cameras: every setting of vti_measure_params per frame ------------------------------ */
 /* The settings live in a camera table in caller-owned DEVICE memory, one row per camera, and an i32 [B] device array names each
  * frame's row.  The table is packed on the host, uploaded once and reused; it does not depend on the frame size (the ROI is clamped

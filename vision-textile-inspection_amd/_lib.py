@@ -37,6 +37,14 @@ class VtiMeasureParams(C.Structure):
                 ("kmeans_iters", C.c_int32), ("drop_empty", C.c_int32), ("frame_buffer", C.c_int32)]
 
 
+class VtiCheckerParams(C.Structure):
+    """include/vti.h vti_checker_params."""
+    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("max_px_distance", C.c_double),
+                ("stitch_id", C.c_int32), ("fabric_id", C.c_int32), ("min_stitches", C.c_int32), ("envelope_neighborhood", C.c_int32),
+                ("skip_cluster", C.c_int32), ("kmeans_iters", C.c_int32), ("drop_empty", C.c_int32), ("frame_buffer", C.c_int32)]
+
+
 VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_BAD_CAMERA = 0, 1, 2, 3
 VTI_STITCH_KEPT, VTI_STITCH_MASK, VTI_STITCH_SELECTED, VTI_STITCH_NEAR, VTI_STITCH_DIST, VTI_STITCH_WIDTH = 1, 2, 4, 8, 16, 32
 VTI_MEASURE_MAX_DET = 1000
@@ -97,6 +105,8 @@ SIGNATURES = {
     "vti_measure_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_measure": (_I32, [_P, C.POINTER(VtiMeasureParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
                            _P, _P, _P, _P, _P]),
+    "vti_measure_checker": (_I32, [_P, C.POINTER(VtiCheckerParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
+                                   _P, _P, _P, _P, _P]),
     "vti_measure_cameras_bytes": (_I64, [_I32]),
     "vti_measure_pack_cameras": (_I32, [_P, C.POINTER(VtiMeasureParams), _I32, _P, _SZ]),
     "vti_measure_cameras": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,

@@ -386,6 +386,10 @@ __device__ double np_pairwise_sum(const double* a, int n) {
 // The loop of measurement.py:93-113 on one thread for n >= 2 values; lab0[0, n) must be 0 on entry (the initial `labels`).  Returns
 // 0 or 1: which of lab0 / lab1 holds the returned labels (the PREVIOUS assignment when the loop stops early); g0, g1: n doubles of
 // scratch each.  Shared by kmeans1d2_kernel and measure_frames_kernel.
+// LATEST (checker_frames_kernel): check_stitch_distance.py:143-171 is the same loop, but sets `labels = new_labels` on both early
+// exits, so the assignment just computed is the one returned.  The two texts differ when the loop stops in its first pass on
+// unchanged seeds (two tight rows whose means are their min and max): the first keeps the initial zeros, this one the split.
+template <bool LATEST = false>
 __device__ int kmeans1d2_serial(const double* vals, int n, int max_iters, int* lab0, int* lab1, double* g0, double* g1, double& c0,
                                 double& c1) {
     c0 = vals[0]; c1 = vals[0];
@@ -399,9 +403,9 @@ __device__ int kmeans1d2_serial(const double* vals, int n, int max_iters, int* l
             nl[i] = l; n1 += l;
             if (l) g1[k1++] = vals[i]; else g0[k0++] = vals[i];
         }
-        if (n1 == 0 || n1 == n) break;
+        if (n1 == 0 || n1 == n) { if (LATEST) cur ^= 1; break; }
         const double nc0 = np_pairwise_sum(g0, k0) / (double)k0, nc1 = np_pairwise_sum(g1, k1) / (double)k1;
-        if (nc0 == c0 && nc1 == c1) break;
+        if (nc0 == c0 && nc1 == c1) { if (LATEST) cur ^= 1; break; }
         c0 = nc0; c1 = nc1; cur ^= 1;
     }
     return cur;
@@ -785,6 +789,339 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
     const size_t lds = (size_t)max_det * (6 * sizeof(double) + 4 * sizeof(int));
     if (a.table) hipLaunchKernelGGL(measure_frames_kernel<true>, dim3(B), dim3(256), lds, st, a);
     else hipLaunchKernelGGL(measure_frames_kernel<false>, dim3(B), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+// ---- the stitch-distance checker's record (Utils/check_stitch_distance.py:281-553), batched ----------------------------------------
+// The bench tool measures against the UPPER fabric edge and keeps another set of stitches than process_frame does; what differs:
+//   * no ROI; every kept fabric-class instance joins the union, with its mask if the frame-size mask has a set pixel, else with the
+//     filled rectangle of its int-truncated box, corners inclusive (:329-334);
+//   * envelope[x] = the SMALLEST set row of column x (:238-251);
+//   * rows: 2-means with the labels of the last assignment (kmeans1d2_serial<true>), the cluster whose mean is nearer to the mean
+//     envelope row (strict <, so a tie is label 1); skip_cluster or a single stitch: every stitch (:408-429);
+//   * proximity: 0 < cy - rint(median) < max_px, the stitch strictly below the edge (:431-444); nothing passes: the selected set;
+//   * edge, distance and width for the final set only; a width whose end has no world point is estimated from the local scale,
+//     px_width / 10 * |world(cx + 10, cy) - world(cx, cy)| (:465-507).
+// Same inputs, scratch and output layout as vti_measure.
+
+// A4 + A5 + A6 for the checker: per frame the upper envelope of the union above.  yf[sy] = first frame row that maps to source row
+// sy (INT_MAX: none), monotone in sy, so a column's answer from one mask is yf of its smallest set source row that has a frame row;
+// a box contributes max(y1, 0) to the columns it covers: one more `min`.  Needs the per-slot stats (m00 decides mask or box) and,
+// for letterbox slots, the raw emptiness (drop_empty), so it runs after mask_stats_bits_kernel.  The instance list is walked by
+// index i < counts[b]: a slot at or beyond `capacity` is an empty mask, which still has a box.
+template <bool NATIVE>
+__global__ __launch_bounds__(256) void upper_envelope_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ offsets,
+                                                                  const int* __restrict__ counts, const float* __restrict__ dets,
+                                                                  int max_det, int row, int capacity, int cls, int drop_empty, int H,
+                                                                  int W, int H0, int W0, const long long* __restrict__ stats,
+                                                                  const int* __restrict__ raw, const float* __restrict__ xyxy,
+                                                                  int native_wpr, int* __restrict__ envelope) {
+    extern __shared__ int yf[];             // [H] (not NATIVE)
+    __shared__ int red[4][64];
+    __shared__ int s_sel[256][5];           // slot (-1: a box), first row, last row, first column, last column
+    __shared__ int s_nsel;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    if (!NATIVE) {
+        for (int i = tid; i < H; i += 256) yf[i] = INT_MAX;
+        __syncthreads();
+        const double ify = 1.0 / ((double)H0 / (double)H);
+        for (int y = tid; y < H0; y += 256) atomicMin(&yf[nn_src(y, ify, H)], y);
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 64 + (tid & 63), rg = tid >> 6;
+    const int xc = x < W0 ? x : W0 - 1;
+    const int sx = NATIVE ? xc : nn_src(xc, 1.0 / ((double)W0 / (double)W), W);
+    const int wpr = NATIVE ? native_wpr : W >> 5;
+    const int Hm = NATIVE ? H0 : H;         // rows of a mask slot
+    const int s0 = offsets[b], n = min(max(counts[b], 0), max_det);
+    int env = INT_MAX;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        __syncthreads();                                       // the previous round's list has been consumed
+        if (tid == 0) s_nsel = 0;
+        __syncthreads();
+        const int i = i0 + tid, s = s0 + i;
+        if (i < n) {
+            const size_t di = (size_t)b * max_det + i;
+            const float* d = dets + di * row;
+            const bool live = s >= 0 && s < capacity;
+            const long long m00 = live ? stats[(size_t)s * 5] : 0;
+            const bool nonempty = live && (raw ? raw[s] != 0 : m00 > 0);
+            if ((int)d[5] == cls && (!drop_empty || nonempty)) {
+                const float* bx = xyxy + di * 4;
+                int e0, e1, e2, e3, e4;
+                if (m00 > 0) {
+                    if (NATIVE) { e1 = (int)floorf(bx[1]); e2 = (int)ceilf(bx[3]); }
+                    else { e1 = (int)floorf(d[1] - 8.f); e2 = (int)ceilf(d[3] + 8.f); }
+                    e0 = s; e1 = max(e1, 0); e2 = min(e2, Hm - 1); e3 = 0; e4 = W0 - 1;
+                } else {                                        // cv2.rectangle(tmp, (x1i, y1i), (x2i, y2i), 1, -1), clipped to the frame
+                    const int x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];
+                    e0 = -1; e1 = max(min(y1, y2), 0); e2 = min(max(y1, y2), H0 - 1); e3 = max(min(x1, x2), 0); e4 = min(max(x1, x2), W0 - 1);
+                }
+                if (e1 <= e2 && e3 <= e4) {
+                    const int pos = atomicAdd(&s_nsel, 1);
+                    s_sel[pos][0] = e0; s_sel[pos][1] = e1; s_sel[pos][2] = e2; s_sel[pos][3] = e3; s_sel[pos][4] = e4;
+                }
+            }
+        }
+        __syncthreads();
+        const int nsel = s_nsel;
+        for (int j = 0; j < nsel; ++j) {
+            const int s = s_sel[j][0], ya = s_sel[j][1], yb = s_sel[j][2];
+            if (s < 0) {
+                if (xc >= s_sel[j][3] && xc <= s_sel[j][4]) env = min(env, ya);
+                continue;
+            }
+            const unsigned* m = bits + (size_t)s * Hm * wpr + (sx >> 5);
+            for (int sy = ya + rg; sy <= yb && (!NATIVE || sy < env); sy += 4) {    // top first: a lane's first hit is its smallest
+                if ((m[(size_t)sy * wpr] >> (sx & 31)) & 1u) {
+                    const int y = NATIVE ? sy : yf[sy];
+                    if (y != INT_MAX) { env = min(env, y); break; }
+                }
+            }
+        }
+    }
+    red[rg][tid & 63] = env;
+    __syncthreads();
+    if (rg == 0 && x < W0) {
+        const int e = min(min(red[0][tid], red[1][tid]), min(red[2][tid], red[3][tid]));
+        envelope[(size_t)b * W0 + x] = e == INT_MAX ? -1 : e;
+    }
+}
+
+struct CheckerArgs {
+    CameraRow cam;                                                  // the geometry and the settings the checker has (no ROI, no two_row)
+    const long long* stats; const int* raw; const int* envelope;
+    const float* dets; const float* xyxy; const int* counts; const int* offsets;
+    int max_det, row, capacity, H0, W0;
+    double* frame_f64; int* frame_i32; double* stitch_f64; int* stitch_i32;
+};
+
+// Centroid and column extent of instance i of frame b (:365-391): the mask's moments and extent, else the int box.  true: from the mask.
+__device__ __forceinline__ bool checker_stitch_geometry(const CheckerArgs& a, int b, int i, int s, double& cx, double& cy, double& left,
+                                                        double& right) {
+    const long long* m = a.stats + (size_t)s * 5;
+    if (s >= 0 && s < a.capacity && m[0] > 0) {
+        cx = (double)m[1] / (double)m[0]; cy = (double)m[2] / (double)m[0];
+        left = (double)m[3]; right = (double)m[4];
+        return true;
+    }
+    const float* bx = a.xyxy + ((size_t)b * a.max_det + i) * 4;
+    const int x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];
+    cx = (double)((long long)x1 + x2) / 2.0; cy = (double)((long long)y1 + y2) / 2.0;
+    left = (double)x1; right = (double)x2;
+    return false;
+}
+
+// One workgroup per frame, as measure_frames_kernel: 1. stitch list and fabric count, 2. status, 3. centroids and the proximity
+// flag, 4. row selection, 5. the final set, 6. a lane per final stitch: edge, distance, width, 7. the ordered lists and their means.
+__global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
+    extern __shared__ double csm[];        // M = max_det: cy | width | dist | g0 | g1 (f64), then idx | flags | lab0 | lab1 (i32)
+    const int M = a.max_det;
+    double* s_cy = csm; double* s_wd = s_cy + M; double* s_ds = s_wd + M; double* g0 = s_ds + M; double* g1 = g0 + M;
+    int* s_idx = (int*)(g1 + M); int* s_fl = s_idx + M; int* lab0 = s_fl + M; int* lab1 = lab0 + M;
+    __shared__ int s_cnt[4];
+    __shared__ long long s_es[4];
+    __shared__ int s_ec[4], s_pick[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
+    const int W0 = a.W0;
+    const int* env = a.envelope + (size_t)b * W0;
+    const double NaN = __builtin_nan("");
+    const CameraRow& r = a.cam;
+
+    // 1. stitch list and fabric count (:310-336)
+    int n_st = 0, n_fab = 0;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int i = c0 + tid, s = s0 + i;
+        bool st = false, fab = false;
+        if (i < n) {
+            const bool live = s >= 0 && s < a.capacity;
+            const bool raw = live && (a.raw ? a.raw[s] != 0 : a.stats[(size_t)s * 5] > 0);
+            const int cls = (int)a.dets[((size_t)b * M + i) * a.row + 5];
+            const bool keep = !r.drop_empty || raw;
+            st = keep && cls == r.stitch_id;
+            fab = keep && cls == r.fabric_id;
+            if (!st && live) {
+                if (a.stitch_f64) for (int k = 0; k < 7; ++k) a.stitch_f64[(size_t)s * 7 + k] = NaN;
+                if (a.stitch_i32) { a.stitch_i32[(size_t)s * 2] = 0; a.stitch_i32[(size_t)s * 2 + 1] = -1; }
+            }
+        }
+        int tot_st, tot_fab;
+        const int pos = block_rank(st, s_cnt, tot_st);
+        if (st) s_idx[n_st + pos] = i;
+        (void)block_rank(fab, s_cnt, tot_fab);
+        n_st += tot_st; n_fab += tot_fab;
+    }
+    // 2. the envelope's valid columns: none is an empty union (:345); their mean is fabric_mean_y (:414-416: integer sum, exact)
+    long long es = 0;
+    int ec = 0;
+    for (int x = tid; x < W0; x += 256) { const int v = env[x]; if (v >= 0) { es += v; ++ec; } }
+    for (int o = 32; o > 0; o >>= 1) { es += __shfl_down(es, o); ec += __shfl_down(ec, o); }
+    if ((tid & 63) == 0) { s_es[tid >> 6] = es; s_ec[tid >> 6] = ec; }
+    __syncthreads();                        // also publishes s_idx
+    es = (s_es[0] + s_es[1]) + (s_es[2] + s_es[3]);
+    ec = (s_ec[0] + s_ec[1]) + (s_ec[2] + s_ec[3]);
+    const int status = ec == 0 ? VTI_MEASURE_NO_FABRIC : (n_st == 0 ? VTI_MEASURE_NO_STITCHES : VTI_MEASURE_OK);
+
+    // 3. per stitch: centroid, extents (:365-402) and the signed proximity test (:433-444)
+    for (int j = tid; j < n_st; j += 256) {
+        const int i = s_idx[j], s = s0 + i;
+        double cx, cy, left, right;
+        int fl = VTI_STITCH_KEPT | (checker_stitch_geometry(a, b, i, s, cx, cy, left, right) ? VTI_STITCH_MASK : 0);
+        if (status == VTI_MEASURE_OK) {
+            double med;
+            if (env_median(env, W0, (int)rint(cx), r.nb, med)) {           // python round(): half to even; the centre is not clipped
+                const double d = cy - rint(med);
+                if (0.0 < d && d < r.max_px) fl |= VTI_STITCH_NEAR;
+            }
+        }
+        s_cy[j] = cy; s_wd[j] = NaN; s_ds[j] = NaN; s_fl[j] = fl;
+        lab0[j] = 0;
+        if (s >= 0 && s < a.capacity && a.stitch_f64) {
+            double* o = a.stitch_f64 + (size_t)s * 7;
+            o[0] = cx; o[1] = cy; o[2] = left; o[3] = right; o[4] = NaN; o[5] = NaN; o[6] = NaN;
+        }
+    }
+    __syncthreads();
+
+    if (status == VTI_MEASURE_OK) {
+        // 4. row selection (:408-429)
+        if (n_st >= 2 && !r.skip_cluster) {
+            if (tid == 0) {
+                double c0, c1;
+                const int which = kmeans1d2_serial<true>(s_cy, n_st, r.kmeans_iters, lab0, lab1, g0, g1, c0, c1);
+                const int* L = which ? lab1 : lab0;
+                int k0 = 0, k1 = 0;
+                for (int j = 0; j < n_st; ++j) { if (L[j]) g1[k1++] = s_cy[j]; else g0[k0++] = s_cy[j]; }
+                const double f = (double)es / (double)ec;
+                const double m0 = k0 ? np_pairwise_sum(g0, k0) / (double)k0 : 1e9, m1 = k1 ? np_pairwise_sum(g1, k1) / (double)k1 : 1e9;
+                s_pick[0] = fabs(m0 - f) < fabs(m1 - f) ? 0 : 1;
+                s_pick[1] = which;
+            }
+            __syncthreads();
+            const int* L = s_pick[1] ? lab1 : lab0;
+            for (int j = tid; j < n_st; j += 256)
+                if (L[j] == s_pick[0]) s_fl[j] |= VTI_STITCH_SELECTED;
+        } else {
+            for (int j = tid; j < n_st; j += 256) s_fl[j] |= VTI_STITCH_SELECTED;
+        }
+        __syncthreads();
+        // 5. final set (:431-454): the selected stitches below and near the edge, else all selected ones
+        bool near = false;
+        for (int j = tid; j < n_st; j += 256)
+            near |= (s_fl[j] & (VTI_STITCH_SELECTED | VTI_STITCH_NEAR)) == (VTI_STITCH_SELECTED | VTI_STITCH_NEAR);
+        near = __syncthreads_or(near);
+        // 6. per final stitch (:465-507)
+        for (int j = tid; j < n_st; j += 256) {
+            int fl = s_fl[j];
+            if (!((fl & VTI_STITCH_SELECTED) && (!near || (fl & VTI_STITCH_NEAR)))) continue;
+            const int i = s_idx[j], s = s0 + i;
+            double cx, cy, left, right, ed = NaN, ds = NaN, wd = NaN, med;
+            (void)checker_stitch_geometry(a, b, i, s, cx, cy, left, right);
+            double pc[3];
+            const bool okc = pixel_to_world(r.g, cx, cy, pc);
+            if (env_median(env, W0, min(max((int)rint(cx), 0), W0 - 1), r.nb, med)) {
+                ed = med;
+                double pe[3];
+                if (pixel_to_world(r.g, cx, ed, pe) && okc) { ds = dist_mm(pc, pe); fl |= VTI_STITCH_DIST; }
+            }
+            double pl[3], pr[3];
+            const bool okl = pixel_to_world(r.g, left, cy, pl), okr = pixel_to_world(r.g, right, cy, pr);
+            if (okl && okr) { wd = dist_mm(pr, pl); fl |= VTI_STITCH_WIDTH; }
+            else if (okc && pixel_to_world(r.g, cx + 10.0, cy, pr)) {       // the local scale: mm per 10 px at the centroid
+                wd = ((right - left) / 10.0) * dist_mm(pr, pc); fl |= VTI_STITCH_WIDTH;
+            }
+            s_wd[j] = wd; s_ds[j] = ds; s_fl[j] = fl;
+            if (s >= 0 && s < a.capacity && a.stitch_f64) {
+                double* o = a.stitch_f64 + (size_t)s * 7;
+                o[4] = wd; o[5] = ed; o[6] = ds;
+            }
+        }
+        __syncthreads();
+    }
+    // 7. ordered lists of the distances and widths (per_dists, per_widths) into g0 / g1, and the averages (:515-517)
+    int n_d = 0, n_w = 0, n_sel = 0;
+    for (int c0 = 0; c0 < n_st; c0 += 256) {
+        const int j = c0 + tid;
+        const int fl = j < n_st ? s_fl[j] : 0;
+        int td, tw, ts;
+        const bool fd = fl & VTI_STITCH_DIST, fw = fl & VTI_STITCH_WIDTH;
+        const int pd = block_rank(fd, s_cnt, td);
+        if (fd) g0[n_d + pd] = s_ds[j];
+        const int pw = block_rank(fw, s_cnt, tw);
+        if (fw) g1[n_w + pw] = s_wd[j];
+        (void)block_rank(fl & VTI_STITCH_SELECTED, s_cnt, ts);
+        n_d += td; n_w += tw; n_sel += ts;
+        if (j < n_st && a.stitch_i32) {
+            const int s = s0 + s_idx[j];
+            if (s >= 0 && s < a.capacity) { a.stitch_i32[(size_t)s * 2] = fl & 63; a.stitch_i32[(size_t)s * 2 + 1] = j; }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.frame_f64[2 * b] = n_d >= r.min_stitches ? np_pairwise_sum(g0, n_d) / (double)n_d : NaN;
+        a.frame_f64[2 * b + 1] = n_w >= r.min_stitches ? np_pairwise_sum(g1, n_w) / (double)n_w : NaN;
+        int* o = a.frame_i32 + 6 * b;
+        o[0] = status; o[1] = n_st; o[2] = n_fab; o[3] = n_sel; o[4] = n_d; o[5] = n_w;
+    }
+}
+
+// One validated vti_checker_params -> the row the kernels read (host).
+void checker_pack(const vti_checker_params& p, void* row) {
+    CameraRow c;
+    memset(&c, 0, sizeof c);
+    c.g = make_geom(p.K, p.dist, p.R, p.t);
+    c.max_px = p.max_px_distance;
+    c.stitch_id = p.stitch_id; c.fabric_id = p.fabric_id;
+    c.min_stitches = p.min_stitches; c.nb = p.envelope_neighborhood; c.skip_cluster = p.skip_cluster;
+    c.kmeans_iters = p.kmeans_iters; c.drop_empty = p.drop_empty;
+    memcpy(row, &c, sizeof c);
+}
+
+hipError_t launch_measure_checker(const vti_checker_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
+                                  const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0,
+                                  int W0, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32,
+                                  hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    size_t off[3], total;
+    measure_scratch_layout(B, capacity, W0, off, total);
+    long long* stats = (long long*)((char*)scratch + off[0]);
+    int* raw = (int*)((char*)scratch + off[1]);
+    int* env = (int*)((char*)scratch + off[2]);
+    const int* n_live = offsets + B;
+    const int wpr = native ? 2 * ((W0 + 63) / 64) : W / 32;
+    CheckerArgs a;
+    memset(&a, 0, sizeof a);
+    checker_pack(p, &a.cam);
+    if (!native && ((W & 31) || (H & 31) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024)) return hipErrorInvalidValue;
+    if (capacity > 0) {
+        if (native)             // frame-size rows: the identity branch, as vti_measure
+            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
+                               32 * wpr, H0, 32 * wpr, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
+        else {
+            if ((uintptr_t)masks & 15) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                               (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, (const int*)nullptr, (const FrameRow*)nullptr, 0);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (native)
+        hipLaunchKernelGGL(upper_envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets,
+                           counts, dets, max_det, 6 + nm, capacity, a.cam.fabric_id, a.cam.drop_empty, H0, W0, H0, W0, stats,
+                           (const int*)nullptr, xyxy, wpr, env);
+    else
+        hipLaunchKernelGGL(upper_envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
+                           offsets, counts, dets, max_det, 6 + nm, capacity, a.cam.fabric_id, a.cam.drop_empty, H, W, H0, W0, stats, raw,
+                           xyxy, 0, env);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
+    a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
+    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0;
+    a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
+    const size_t lds = (size_t)max_det * (5 * sizeof(double) + 4 * sizeof(int));
+    hipLaunchKernelGGL(checker_frames_kernel, dim3(B), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

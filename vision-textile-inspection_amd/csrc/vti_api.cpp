@@ -1036,6 +1036,44 @@ int32_t vti_measure(vti_ctx* c, const vti_measure_params* p, const uint8_t* mask
                         scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
 }
 
+// The checks of one vti_checker_params: nullptr when it is valid.
+static const char* checker_params_error(const vti_checker_params* p) {
+    if (p->stitch_id < 0 || p->fabric_id < 0 || p->stitch_id == p->fabric_id) return "stitch_id and fabric_id must be >= 0 and different";
+    if (p->envelope_neighborhood < 0 || p->envelope_neighborhood > 64) return "envelope_neighborhood must be 0..64";
+    if (p->min_stitches < 1 || p->kmeans_iters < 0 || (p->skip_cluster != 0 && p->skip_cluster != 1) ||
+        (p->drop_empty != 0 && p->drop_empty != 1) || p->frame_buffer < 1)
+        return "bad setting (min_stitches, frame_buffer >= 1; kmeans_iters >= 0; flags 0 or 1)";
+    if (!(p->max_px_distance == p->max_px_distance)) return "NaN threshold";
+    return nullptr;
+}
+
+int32_t vti_measure_checker(vti_ctx* c, const vti_checker_params* p, const uint8_t* masks, int32_t native, const float* dets,
+                            const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det,
+                            int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64,
+                            int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
+    if (!c || !p) return fail(c, VTI_ERR_ARG, "vti_measure_checker: null ctx or params");
+    char msg[200];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "vti_measure_checker: %s", what); return fail(c, VTI_ERR_ARG, msg); };
+    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
+        return bad("bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
+    if (max_det > VTI_MEASURE_MAX_DET) return bad("max_det above VTI_MEASURE_MAX_DET");
+    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks))) return bad("null pointer");
+    if (const char* e = checker_params_error(p)) return bad(e);
+    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
+        return bad(native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
+    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
+        return bad("letterbox size too large for the resize tables");
+    if ((int64_t)B * W0 > INT32_MAX) return bad("B * W0 out of range");
+    if (B && (!scratch || ((uintptr_t)scratch & 255))) return bad("scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_measure_scratch_bytes(c, B, capacity, W0)) return bad("scratch smaller than vti_measure_scratch_bytes()");
+    if (B == 0) return VTI_OK;
+    if (int32_t drc = check_device(c, "vti_measure_checker")) return drc;
+    const vti_desc& d = c->plan.desc;
+    VTI_HIP(c, launch_measure_checker(*p, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H, d.W, H0, W0, scratch,
+                                      frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure_checker kernels");
+    return VTI_OK;
+}
+
 int64_t vti_measure_cameras_bytes(int32_t n_cams) {
     return n_cams < 1 ? 0 : (int64_t)n_cams * (int64_t)measure_camera_row_bytes();
 }

@@ -329,6 +329,12 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
                           int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st, const long long* bases = nullptr,
                           long long capacity_bytes = 0);
 
+// vti_measure_checker (Utils/check_stitch_distance.py): vti_measure's inputs, scratch layout and outputs; one frame size, one camera
+hipError_t launch_measure_checker(const vti_checker_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
+                                  const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0,
+                                  int W0, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32,
+                                  hipStream_t st);
+
 // polygons.hip: vti_mask_polygons (Results.masks.xy).  The grid is VTI_POLY_WORKGROUPS persistent workgroups, each with its own
 // labelling area of the scratch: parent i32 [R_max] | runs u32 [R_max] | row_start i32 [H+1] | image u64 [H, WW] (only when the
 // image does not fit in LDS), R_max = H * ceil(W/2) (the most runs an H x W mask can have).  The scratch starts with a 256-byte

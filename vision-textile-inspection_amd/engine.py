@@ -585,6 +585,37 @@ class Engine:
             check(self._ctx, lib().vti_measure(self._ctx, C.byref(cp), *rest))
         return r
 
+    def measure_checker(self, out, params, H0=None, W0=None, native=False, stitch_rows=True, result=None):
+        """The stitch-distance checker's per-frame measurement (Utils/check_stitch_distance.py:281-553) for every frame of an output
+        set, as measure() does process_frame's: vti_measure_checker.  params: a measure.CheckerParams (or a VtiCheckerParams).  One
+        frame size (H0, W0), one camera; native, stitch_rows, result and the returned dict of device tensors are measure()'s, with
+        the checker's meanings (include/vti.h): the upper fabric edge, the signed proximity test, widths for the final set only."""
+        dets, masks = out["dets"], out["masks"]
+        B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
+        dev = dets.device
+        if H0 is None or W0 is None:
+            raise ValueError("measure_checker: H0 and W0 are required")
+        cp = params.to_c() if hasattr(params, "to_c") else params
+        r = dict(result or {})
+        if "frame_f64" not in r:
+            r["frame_f64"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        if "frame_i32" not in r:
+            r["frame_i32"] = torch.empty((B, 6), dtype=torch.int32, device=dev)
+        if stitch_rows:
+            if "stitch_f64" not in r:
+                r["stitch_f64"] = torch.empty((capacity, 7), dtype=torch.float64, device=dev)
+            if "stitch_i32" not in r:
+                r["stitch_i32"] = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+        need = self.measure_scratch_bytes(B, capacity, W0)
+        ws = getattr(self, "_measure_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._measure_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        check(self._ctx, lib().vti_measure_checker(
+            self._ctx, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]),
+            _ptr(out["counts"]), _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(),
+            _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream()))
+        return r
+
     # ---- process_frame's annotated frame (measurement.py:219-504): the overlay on a selection of the batch ------------------
     def annotate_scratch_bytes(self, n_sel, max_det, H0, W0, max_points):
         return int(lib().vti_annotate_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))

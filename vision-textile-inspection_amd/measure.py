@@ -5,6 +5,8 @@
     records = sm.process_frames(frames)          # one dict per frame, as process_frame returns (main.py:211-226)
     mc = MultiCameraMeasurer(YOLO(path), [params_cam0, params_cam1, ...])
     records = mc.process_frames(frames, cameras) # a batch that mixes cameras: cameras[b] = the camera of frame b
+    ck = StitchDistanceChecker(YOLO(path), CheckerParams.from_files(...))                  Utils/check_stitch_distance.py:176-222
+    records = ck.process_frames(frames)          # the bench tool's numbers and info text per frame (vti_measure_checker)
 
 The per-frame work (ROI filter, moments, fabric envelope, widths, row selection, proximity filter, distances, averages) runs in
 libvti's vti_measure on the predict output set that is already on the device; the host reads back B small records once and keeps
@@ -30,7 +32,8 @@ import numpy as np
 import torch
 
 from . import annotate as _annotate
-from ._lib import VTI_MEASURE_BAD_CAMERA, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VtiMeasureParams
+from ._lib import (VTI_MEASURE_BAD_CAMERA, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_OK, VTI_STITCH_KEPT,
+                   VTI_STITCH_NEAR, VTI_STITCH_SELECTED, VTI_STITCH_WIDTH, VtiCheckerParams, VtiMeasureParams)
 from .consumer import rodrigues
 
 ERRORS = {VTI_MEASURE_NO_FABRIC: "Fabric not detected", VTI_MEASURE_NO_STITCHES: "No stitches detected",
@@ -92,6 +95,48 @@ class MeasureParams:
         return p
 
 
+@dataclasses.dataclass
+class CheckerParams:
+    """Calibration + the stitch-distance checker's settings (the defaults are check_stitch_distance.py:20-39's module constants).
+    K, dist, R, t as MeasureParams.  The checker has no ROI and no two-row threshold."""
+    K: np.ndarray
+    dist: np.ndarray
+    R: np.ndarray
+    t: np.ndarray
+    stitch_id: int = 0
+    fabric_id: int = 1
+    min_stitches: int = 3
+    max_px_distance: float = 150
+    envelope_neighborhood: int = 3
+    skip_cluster: bool = False
+    frame_buffer: int = 8
+    kmeans_iters: int = 10
+    drop_empty: bool = False
+
+    @classmethod
+    def from_files(cls, calib_path, extr_path, **kw):
+        """check_stitch_distance.py:188-201: the same two files StitchMeasurementApp reads."""
+        m = MeasureParams.from_files(calib_path, extr_path)
+        return cls(K=m.K, dist=m.dist, R=m.R, t=m.t, **kw)
+
+    def to_c(self):
+        p = VtiCheckerParams()
+        for name, n in (("K", 9), ("dist", 5), ("R", 9), ("t", 3)):
+            a = np.ascontiguousarray(np.asarray(getattr(self, name), dtype=np.float64).ravel())
+            if a.size != n:
+                raise ValueError(f"CheckerParams.{name}: expected {n} values, got {a.size}")
+            setattr(p, name, (C.c_double * n)(*a.tolist()))
+        p.max_px_distance = float(self.max_px_distance)
+        p.stitch_id, p.fabric_id = int(self.stitch_id), int(self.fabric_id)
+        p.min_stitches = int(self.min_stitches)
+        p.envelope_neighborhood = int(self.envelope_neighborhood)
+        p.skip_cluster = int(bool(self.skip_cluster))
+        p.kmeans_iters = int(self.kmeans_iters)
+        p.drop_empty = int(bool(self.drop_empty))
+        p.frame_buffer = int(self.frame_buffer)
+        return p
+
+
 class CameraStream:
     """One camera's smoothing state: the reference's two frame_buffer-long deques (measurement.py:474-484)."""
 
@@ -140,18 +185,24 @@ def _mixed_keyword(public):
 class _DeviceStage:
     """predict + one measure call + one device -> host read of the B frame records."""
 
+    _mixed_sizes = True         # the stage has a frame-table form (vti_measure_frames)
+
     def __init__(self, model):
         self.model = model
         self._res = {}
 
+    def _measure(self, eng, o, params, H0, W0, **kw):
+        """The stage's one measure call on the predict outputs (Engine.measure's contract)."""
+        return eng.measure(o, params, H0, W0, **kw)
+
     @torch.inference_mode()
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
-                       jpeg_quality=95, mixed=False):
+                       jpeg_quality=95, mixed=False, rows=False):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
         selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0 (frames of
         differing sizes, which `mixed` allows with annotate: the list of every frame's H0).  params /
         cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the outputs exist (the
-        camera table needs both)."""
+        camera table needs both).  rows (without annotate): a third item, every frame's per-slot rows as `_slot_rows` gives them."""
         if encode is not None:
             if encode != "jpeg":
                 raise ValueError(f'process_frames: encode must be None or "jpeg", got {encode!r}')
@@ -169,6 +220,8 @@ class _DeviceStage:
         shapes = self.model._differing_shapes(frames)
         table = None
         if shapes is not None:
+            if not self._mixed_sizes:
+                raise ValueError(f"process_frames: {type(self).__name__} needs frames of one size; the frames of this list differ in shape")
             if annotate is not None and not mixed:
                 raise ValueError("process_frames: annotate needs frames of one size; the frames of this list differ in shape "
                                  "(vti_annotate has no frame-table form)")
@@ -197,14 +250,18 @@ class _DeviceStage:
             self._res = {key: res}
         if callable(params):
             params = params(eng, o["dets"].device)
-        r = eng.measure(o, params, H0, W0, native=bool(retina_masks), stitch_rows=sel is not None, result=res, cameras=cameras,
-                        frames=table)
-        if sel is not None:       # measure() allocated the per-slot rows into its copy of the dict: keep them for the next call
+        want_rows = sel is not None or bool(rows)
+        if table is None and cameras is None:
+            r = self._measure(eng, o, params, H0, W0, native=bool(retina_masks), stitch_rows=want_rows, result=res)
+        else:
+            r = self._measure(eng, o, params, H0, W0, native=bool(retina_masks), stitch_rows=want_rows, result=res, cameras=cameras,
+                              frames=table)
+        if want_rows:             # measure() allocated the per-slot rows into its copy of the dict: keep them for the next call
             res.update(stitch_f64=r["stitch_f64"], stitch_i32=r["stitch_i32"])
         host = res["buf"].cpu().numpy()
         f64, i32 = host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
         if sel is None:
-            return f64, i32
+            return (f64, i32, self._slot_rows(o, res, np.arange(B))) if rows else (f64, i32)
         return f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks),
                                          int(jpeg_quality) if encode else None, table), H0 if table is None else [h for h, _ in shapes]
 
@@ -228,8 +285,13 @@ class _DeviceStage:
             off = off.cpu().numpy()
             data = data[:int(off[-1])].cpu().numpy().tobytes()
             pics = [data[off[k]:off[k + 1]] for k in range(len(sel))]
+        rows = self._slot_rows(o, res, np.unique(sel))
+        return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
+
+    @staticmethod
+    def _slot_rows(o, res, uniq):
+        """{frame b: dict(f64 [n,7], flags [n], rank [n])} of the frames `uniq`: the per-slot rows of their live slots, on the host."""
         dev = o["dets"].device
-        uniq = np.unique(sel)
         cnt_off = torch.cat((o["counts"], o["offsets"])).cpu().numpy()
         B = o["counts"].shape[0]
         cap = o["masks"].shape[0]
@@ -242,7 +304,7 @@ class _DeviceStage:
         for b, (lo, hi) in spans.items():
             rows[b] = dict(f64=sf[at:at + hi - lo], flags=si[at:at + hi - lo, 0], rank=si[at:at + hi - lo, 1])
             at += hi - lo
-        return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
+        return rows
 
     @staticmethod
     def _with_text(annotated, records, i32, min_stitches, H0):
@@ -354,3 +416,97 @@ class MultiCameraMeasurer(_DeviceStage):
     def _records(self, f64, i32, cams):
         """Frame b's record from camera cams[b]'s stream, in frame order."""
         return [dict(self.streams[c].record(f64[b], i32[b]), camera=int(c)) for b, c in enumerate(cams)]
+
+
+class StitchDistanceChecker(_DeviceStage):
+    """Utils/check_stitch_distance.py's StitchMeasurementApp.process_frame without the camera and the window: model = a vti_amd YOLO,
+    params = CheckerParams.  One predict, one vti_measure_checker and one device -> host read per batch; the two smoothing deques
+    (:215-216, :519-530) live here, so consecutive calls continue one stream of frames.  Frames of one size, one camera; the
+    checker's picture is not drawn (checker_text_items gives its text)."""
+
+    _mixed_sizes = False
+
+    def __init__(self, model, params, frame_buffer=8):
+        super().__init__(model)
+        self.params = dataclasses.replace(params, frame_buffer=int(frame_buffer), drop_empty=bool(model.drop_empty_masks))
+        self.frame_buf_dist, self.frame_buf_width = deque(maxlen=int(frame_buffer)), deque(maxlen=int(frame_buffer))
+        self._cp = self.params.to_c()
+
+    def _measure(self, eng, o, params, H0, W0, **kw):
+        return eng.measure_checker(o, params, H0, W0, **kw)
+
+    def _record(self, f64, i32):
+        """:345-347, :404-406 (the two early returns: nothing appended) and :515-540 (averages -> deques -> medians -> text)."""
+        status = int(i32[0])
+        if status != VTI_MEASURE_OK:
+            text = ERRORS[status]
+            return {'edge_distance_mm': None, 'stitch_width_mm': None, 'stitch_count': 0, 'info_text': text,
+                    'timestamp': datetime.now(), 'error': text}
+        n_found = int(i32[5])
+        smooth_dist = smooth_width = None
+        if not np.isnan(f64[0]):
+            self.frame_buf_dist.append(float(f64[0]))
+            smooth_dist = float(np.median(self.frame_buf_dist))
+        if not np.isnan(f64[1]):
+            self.frame_buf_width.append(float(f64[1]))
+            smooth_width = float(np.median(self.frame_buf_width))
+        return {'edge_distance_mm': smooth_dist, 'stitch_width_mm': smooth_width, 'stitch_count': n_found,
+                'info_text': checker_info_text(smooth_dist, smooth_width, n_found, self.params.min_stitches),
+                'timestamp': datetime.now()}
+
+    def process_frames(self, frames, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False):
+        """frames: as StitchMeasurer.process_frames takes them (a BGR uint8 batch, a list of JPEG files, RawFrames), all of one size.
+        The defaults are the checker's predict call (:286: conf 0.20, iou 0.45, max_det 200, imgsz not passed: 640).  Returns one
+        record per frame, in frame order, smoothed frame by frame: edge_distance_mm, stitch_width_mm (None: no value yet),
+        stitch_count (the `n` of the info text: the number of widths), info_text (the string process_frame returns), timestamp, and
+        `error` on the two failures.  rows=True -> (records, rows): rows[b] is what checker_text_items takes for frame b (one more
+        device -> host read, of the per-slot rows)."""
+        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, rows=bool(rows))
+        f64, i32 = got[:2]
+        records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
+        if not rows:
+            return records
+        return records, [dict(got[2][b], status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
+                         for b in range(len(f64))]
+
+    def process_frame(self, frame, **kw):
+        """One frame: its record."""
+        return self.process_frames(np.asarray(frame)[None], **kw)[0]
+
+
+def checker_info_text(smooth_dist, smooth_width, n_found, min_stitches):
+    """check_stitch_distance.py:533-540."""
+    if smooth_dist is not None and smooth_width is not None:
+        return f"Edge Dist: {smooth_dist:.2f}mm | Avg Width: {smooth_width:.2f}mm (n={n_found})"
+    if smooth_dist is not None:
+        return f"Edge Distance: {smooth_dist:.2f}mm (n={n_found})"
+    if smooth_width is not None:
+        return f"Avg Width: {smooth_width:.2f}mm (n={n_found})"
+    return f"Insufficient stitches (found {n_found}, need {int(min_stitches)})"
+
+
+def checker_text_items(record, rows, h):
+    """What the checker passes to cv2.putText for one frame, in annotate.text_items' form [(text, org, fontFace name, scale, colour,
+    thickness)], for annotate.put_text.  record: the frame's StitchDistanceChecker record; rows: dict(status, n_stitch, n_fabric
+    (frame_i32[b,0], [1], [2]), flags [n], rank [n], f64 [n,7]) of the frame's slots; h: the frame's height.  Host only."""
+    font = _annotate.FONT
+    status = int(rows["status"])
+    if status != VTI_MEASURE_OK:          # :346, :405: the error text, and nothing else is written
+        return [(ERRORS[status], (10, 55), font, 0.7, (0, 0, 255), 2)] if status in ERRORS else []
+    f64 = np.asarray(rows["f64"], dtype=np.float64).reshape(-1, 7)
+    flags = [int(f) for f in rows["flags"]]
+    order = [i for _, i in sorted((int(r), i) for i, r in enumerate(rows["rank"]) if flags[i] & VTI_STITCH_KEPT and int(r) >= 0)]
+    sel_near = VTI_STITCH_SELECTED | VTI_STITCH_NEAR
+    any_near = any(flags[i] & sel_near == sel_near for i in order)
+    items, last = [], None
+    for i in order:                       # :465-512: the final set in order; the label shows per_widths[-1], the last width so far
+        if not (flags[i] & VTI_STITCH_SELECTED and (not any_near or flags[i] & VTI_STITCH_NEAR)):
+            continue
+        if flags[i] & VTI_STITCH_WIDTH:
+            last = float(f64[i, 4])
+        if last is not None:
+            items.append((f"w:{last:.1f}mm", (int(round(float(f64[i, 0]))) + 6, int(round(float(f64[i, 1]))) + 6), font, 0.45,
+                          (0, 255, 0), 1))
+    items.append((record["info_text"], (10, 30), font, 0.7, (0, 0, 255), 2))
+    items.append((f"Stitches: {int(rows['n_stitch'])} | Fabric: {int(rows['n_fabric'])}", (10, h - 10), font, 0.5, (255, 255, 255), 1))
+    return items
