@@ -25,6 +25,14 @@ SHAPES = {  # name: (c1, c2, k, s, kind, H_in, W_in)
     "sppf_cv2_512-256_20": (512, 256, 1, 1, 0, 20, 20),
     "c2f8_cv1_256-256_20": (256, 256, 1, 1, 0, 20, 20),
     "c2f8_cv2_384-256_20": (384, 256, 1, 1, 0, 20, 20),
+    # the trunk's persistent 1x1 layers (conv1_pk); run with VTI_CONV1_WREG=0 / 1 for the register-weights A/B
+    "c2f4_cv1_64-64_80": (64, 64, 1, 1, 0, 80, 80),
+    "c2f6_cv1_128-128_40": (128, 128, 1, 1, 0, 40, 40),
+    "c2f6_cv2_256-128_40": (256, 128, 1, 1, 0, 40, 40),
+    "c2f12_cv1_384-128_40": (384, 128, 1, 1, 0, 40, 40),
+    "c2f12_cv2_192-128_40": (192, 128, 1, 1, 0, 40, 40),
+    "c2f15_cv1_192-64_80": (192, 64, 1, 1, 0, 80, 80),
+    "c2f15_cv2_96-64_80": (96, 64, 1, 1, 0, 80, 80),
     "l5_64-128_s2": (64, 128, 3, 2, 0, 80, 80),
     "l16_64-64_s2": (64, 64, 3, 2, 0, 80, 80),
     "l19_128-128_s2": (128, 128, 3, 2, 0, 40, 40),

@@ -35,14 +35,20 @@ __host__ __device__ inline int patch_dim(int t, int ks, int s, int mode) { retur
 
 size_t stem_lds_bytes(int TH, int TW);
 
-size_t conv_lds_bytes(int ks, int stride, int mode, int TH, int TW, int WN, int NREP) {
+// Per-tile 1x1 kernel with the weight fragments fed to the MFMAs from the registers they were loaded into (conv_kernel<..., WREG>):
+// every wave splits N (WN == 4), so a fragment has exactly one consumer wave, and the register-prefetching instantiations only.
+bool conv_wreg_ok(int ks, int stride, int mode, int WN, int NREP, int threads) {
+    return mode == 0 && ks == 1 && stride == 1 && threads == 256 && WN == 4 && NREP <= 4;
+}
+
+size_t conv_lds_bytes(int ks, int stride, int mode, int TH, int TW, int WN, int NREP, int wreg) {
     if (mode == 1) return stem_lds_bytes(TH, TW);
     const int npix = patch_dim(TH, ks, stride, mode) * patch_dim(TW, ks, stride, mode);
     const size_t plane = (size_t)((npix + 15) & ~15) * 16;
     const int taps = mode == 1 ? 1 : ks * ks;
     size_t raw = 0;
     if (mode == 1) raw = (((size_t)(2 * TH + 1) * (2 * TW + 1) * 3) + 15) & ~(size_t)15;   // u8 input patch
-    return 4 * plane + (size_t)WN * NREP * taps * 1024 + raw;
+    return 4 * plane + (wreg ? 0 : (size_t)WN * NREP * taps * 1024) + raw;     // wreg: no weight image
 }
 
 // Register-staged operand prefetch: a thread owns up to AR input-patch pieces and BR weight pieces
@@ -52,7 +58,11 @@ size_t conv_lds_bytes(int ks, int stride, int mode, int TH, int TW, int WN, int 
 // 16 x 20 tiles -- the same 2 waves per SIMD, but a staged weight chunk (45 KB for the 80-channel class tower) now serves 640 pixels
 // instead of 320 (the towers' weights were re-staged from L2 once per 320 pixels: 690 MB per launch), and with half the weight pieces
 // per thread even the NREP = 5 kernels can prefetch them into registers under the MFMA loop instead of fetching them in commit().
-template <typename T, int KS, int S, int NREP, int WN, int NREP2 = 0, int NT = 256>
+// WREG (1x1, WN == NT / 64): the packed weights are already in MFMA fragment order, [chunk][n-tile][lane][16 B], and with every wave on
+// its own n-tiles a fragment has exactly one consumer wave.  Thread (wave, lane) then loads piece (wn * NREP + n) * 64 + lane of the
+// chunk -- rb[n] IS the operand of n-tile n -- and the weights skip LDS: no ds_write in commit(), no ds_read behind the barrier, and
+// the LDS image is the four pixel planes alone.  Chunk order, MFMA order per accumulator and the operands are unchanged.
+template <typename T, int KS, int S, int NREP, int WN, int NREP2 = 0, int NT = 256, bool WREG = false>
 __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvParams p) {   // 2 waves/SIMD: VGPR + AGPR <= 256
     using vec = typename Tr<T>::vec;
     constexpr int VEC = Tr<T>::VEC, KC = Tr<T>::KC;
@@ -61,6 +71,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
     constexpr int PP = NT / 4;                               // pixels of the input patch per staging pass (4 lanes per pixel)
     constexpr int AR = NT == 512 ? 6 : (S == 2 ? 12 : 8);
     constexpr int BR = (NTB * TAPS * 64 + NT - 1) / NT;
+    static_assert(!WREG || (KS == 1 && WN == NT / 64 && NREP2 == 0 && BR == NREP && NREP < 5), "WREG: one consumer wave per fragment");
     constexpr unsigned OOB = 0xFFFFFFFFu;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -133,8 +144,10 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
     auto loadB = [&](int c, vec (&rbs)[BR]) {
         const unsigned sB = (unsigned)(((size_t)c * p.ntiles_n + nt0) * (TAPS * 1024));
 #pragma unroll
-        for (int u = 0; u < BR; ++u)
-            if (tid + u * NT < NTB * TAPS * 64) rbs[u] = buf_load16<vec>(rsB, (unsigned)(tid + u * NT) * 16u, sB);
+        for (int u = 0; u < BR; ++u) {
+            if constexpr (WREG) rbs[u] = buf_load16<vec>(rsB, (unsigned)((wn * NREP + u) * 64 + lane) * 16u, sB);     // this wave's n-tile u
+            else if (tid + u * NT < NTB * TAPS * 64) rbs[u] = buf_load16<vec>(rsB, (unsigned)(tid + u * NT) * 16u, sB);
+        }
     };
     auto issue = [&](int c, vec (&ras)[AR], vec (&rbs)[BR]) {
         const bool qok = c < cvalid;
@@ -149,9 +162,11 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
 #pragma unroll
         for (int u = 0; u < AR; ++u)
             if (pix0 + PP * u < npix) *(vec*)(smA + ldsA0 + u * (PP * 16)) = ras[u];
+        if constexpr (!WREG) {
 #pragma unroll
-        for (int u = 0; u < BR; ++u)
-            if (tid + u * NT < NTB * TAPS * 64) *(vec*)(smB + (tid + u * NT) * 16) = rbs[u];
+            for (int u = 0; u < BR; ++u)
+                if (tid + u * NT < NTB * TAPS * 64) *(vec*)(smB + (tid + u * NT) * 16) = rbs[u];
+        }
     };
     // one K chunk: commit its operands (register set SET), refill that set with chunk c + PD, MFMA over the taps
     auto chunk = [&](int c, auto set_c) {
@@ -161,6 +176,12 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
         if (c < 2) VTI_STAMP(3 + 5 * c);
         __syncthreads();
         if (c < 2) VTI_STAMP(4 + 5 * c);
+        constexpr int WD = NREP >= 5 ? 1 : 2;                    // weight fragment sets of the MFMA loop
+        vec wq[WD][NREP];
+        if constexpr (WREG) {                                     // the chunk's operands, before their staging set is refilled
+#pragma unroll
+            for (int n = 0; n < NREP; ++n) wq[0][n] = rb[SET][n];
+        }
         if (c + PD < p.nchunks) issue(c + PD, ra[SET], rb[SET]);   // in flight during the MFMA loop(s) below
         // ---- MFMA over the taps of this chunk, software pipelined over the flat (tap, pixel-tile)
         // sequence: pixel fragments are read two steps ahead and the next tap's weight fragments one
@@ -170,9 +191,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
             // NREP == 5 (80-channel towers) sits at the register limit: it keeps one weight-fragment set and a
             // 2-deep pixel queue so that two waves still fit per SIMD (VGPR + AGPR <= 256).
             constexpr int XD = NREP >= 5 ? 2 : 3;          // pixel fragments in flight
-            constexpr int WD = NREP >= 5 ? 1 : 2;          // weight fragment sets
             vec xq[XD];
-            vec wq[WD][NREP];
             auto ldx = [&](int s_) -> vec {
                 const int tp = s_ / MREP, mm = s_ % MREP;
                 const int toff = ((tp / KS) * PW + (tp % KS)) * 16;
@@ -191,7 +210,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
                 auto ldw1 = [&](int tp, int n) -> vec { return *(const vec*)(smB + ((wn * NREP + n) * TAPS + tp) * 1024 + lane * 16); };
                 h2_taps<NREP, MREP, TAPS, 3>(acc, ldx, ldw1);
             } else {
-            ldw(0, wq[0]);
+            if constexpr (!WREG) ldw(0, wq[0]);
             xq[0] = ldx(0);
             if (XD > 2 && NSTEP > 1) xq[1] = ldx(1);
 #pragma unroll
@@ -830,6 +849,7 @@ size_t stem_lds_bytes(int TH, int TW) { return 1024 + (size_t)(2 * TH + 1) * (((
 // every split; stem_kernel: NREP
 using ConvTile3 = Combos<Ints<1, 1>, Ints<2, 1>, Ints<3, 1>, Ints<4, 1>, Ints<5, 1>, Ints<1, 2>, Ints<2, 2>, Ints<1, 4>>;
 using ConvTile1 = decltype(concat(ConvTile3{}, Combos<Ints<3, 2>, Ints<4, 2>, Ints<5, 2>, Ints<2, 4>, Ints<3, 4>, Ints<4, 4>, Ints<5, 4>>{}));
+using ConvTile1W = Combos<Ints<1, 4>, Ints<2, 4>, Ints<3, 4>, Ints<4, 4>>;       // 1x1 with register-fed weights (WREG)
 using StemNrep = Combos<Ints<1>, Ints<2>, Ints<3>, Ints<4>, Ints<5>>;
 
 // Host-side check that a geometry fits the kernel's fixed register staging arrays.
@@ -846,6 +866,12 @@ bool conv_fusable(int nrep, int nrep2) { return combo_has(FusedPairs{}, nrep, nr
 
 template <typename T, int KS, int S>
 static hipError_t launch_ks(int nrep, const ConvParams& p, dim3 grid, size_t lds, hipStream_t st) {
+    if constexpr (KS == 1) {
+        if (p.wreg)     // weight fragments stay in the registers they were loaded into: WN == 4 (conv_wreg_ok)
+            return combo_dispatch(ConvTile1W{}, [&](auto c) {
+                return launch_lds<conv_kernel<T, 1, 1, decltype(c)::v[0], 4, 0, 256, true>>(grid, dim3(256), lds, st, p);
+            }, nrep, p.WN);
+    }
     return combo_dispatch(std::conditional_t<KS == 1, ConvTile1, ConvTile3>{}, [&](auto c) {
         using C = decltype(c);
         return launch_lds<conv_kernel<T, KS, S, C::v[0], C::v[1]>>(grid, dim3(256), lds, st, p);
@@ -885,6 +911,9 @@ hipError_t launch_conv(int dtype, int ks, int stride, int nrep, int mode, const 
     if (grid.x == 0) return hipSuccess;
     // host-side shape guard: the pixel tile must fit the 4/WN waves x 5 x 16 pixels
     const int nwaves = p.nt == 512 ? 8 : 4;
+    if (p.wreg && !conv_wreg_ok(ks, stride, mode, p.WN, nrep, p.nt)) return hipErrorInvalidValue;
+    // (a persistent plan that fell back to this kernel brings the persistent kernel's LDS size: never less than this kernel's image)
+    lds_bytes = std::max(lds_bytes, conv_lds_bytes(ks, stride, mode, p.TH, p.TW, p.WN, nrep, p.wreg));
     if ((p.nt != 256 && p.nt != 512) || (p.nt == 512 && p.ntiles2 == 0)) return hipErrorInvalidValue;     // 512 threads: fused towers only
     if (p.TH * p.TW > (nwaves / p.WN) * MREP * 16 || (p.WN != 1 && p.WN != 2 && p.WN != 4)) return hipErrorInvalidValue;
     return with_conv_type(dtype, [&](auto t) { return launch_t<typename decltype(t)::type>(ks, stride, nrep, mode, p, grid, lds_bytes, st); });

@@ -47,6 +47,21 @@ using Conv1Pk = decltype(concat(ConvPkS1{}, Combos<Ints<4, 4>>{}));
 bool conv_pk_instantiated(int nrep, int wn) { return combo_has(ConvPkS1{}, nrep, wn); }
 bool conv_pk2_instantiated(int nrep, int wn) { return combo_has(ConvPkS2{}, nrep, wn); }
 bool conv1_pk_instantiated(int nrep, int wn) { return combo_has(Conv1Pk{}, nrep, wn); }
+// conv1_pk with the n-group's weights in the compute waves' registers (pk_wstat == 2), (NREP, WN, K chunks): the chunk counts of the
+// n-scale plans that stay inside the register budget of one 8-wave workgroup per CU (256 per wave) WITHOUT spilling (compiler's
+// resource-usage remarks; DESIGN section 7 lists every instantiation).  h2, 16-channel chunks: up to 8 chunks at NREP = 2 keep the
+// prepared operands WH / WL (8 registers per fragment, 247 at 8 chunks), 12 and 16 chunks keep the raw fragments (4 registers,
+// 215 / 247) and prepare them in the loop.  NREP = 4 spilled (86 registers at 4 chunks) and the fp32 engine's instantiations
+// needed a scratch segment: none of those is built -- such layers keep their weights in LDS.  fp16: 32-channel chunks, 4 registers per fragment.
+using Conv1PkWH2 = Combos<Ints<2, 2, 4>, Ints<2, 2, 6>, Ints<2, 2, 8>, Ints<2, 2, 12>, Ints<2, 2, 16>,
+                          Ints<2, 4, 4>, Ints<2, 4, 6>, Ints<2, 4, 8>, Ints<2, 4, 12>, Ints<2, 4, 16>>;
+using Conv1PkWF16 = Combos<Ints<2, 2, 2>, Ints<2, 2, 3>, Ints<2, 2, 4>, Ints<2, 2, 6>, Ints<2, 2, 8>,
+                           Ints<2, 4, 2>, Ints<2, 4, 3>, Ints<2, 4, 4>, Ints<2, 4, 6>, Ints<2, 4, 8>, Ints<4, 1, 2>>;
+using Conv1PkWF32 = Combos<>;
+template <typename T> using Conv1PkW = std::conditional_t<Tr<T>::H2, Conv1PkWH2, std::conditional_t<Tr<T>::F32, Conv1PkWF32, Conv1PkWF16>>;
+bool conv1_pk_wreg_instantiated(int dtype, int nrep, int wn, int nchunks) {
+    return dtype == VTI_H2 ? combo_has(Conv1PkWH2{}, nrep, wn, nchunks) : dtype == VTI_F16 ? combo_has(Conv1PkWF16{}, nrep, wn, nchunks) : false;
+}
 
 // `depth` patch stages (2..4): the loaders run depth - 1 steps ahead.  Weights: K <= 2 chunks stay resident (1 or 2 buffers);
 // more chunks travel with the patches, one buffer per stage.
@@ -502,10 +517,19 @@ constexpr int PK1_MAXP = 5;       // pixel DMA pieces per loader wave, chunk and
 size_t conv1_pk_lds_bytes(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps) {
     const size_t stage = (size_t)nwm * 80 * 64 * cps;
     const size_t wch = (size_t)WN * NREP * 1024;
-    return (size_t)depth * stage + (wstat ? (size_t)nchunks * wch : (size_t)depth * wch * cps) + 1024 /*dummy*/ + (size_t)WN * NREP * 64;
+    const size_t wbytes = wstat == 2 ? 0 : wstat ? (size_t)nchunks * wch : (size_t)depth * wch * cps;      // 2: weights in registers
+    return (size_t)depth * stage + wbytes + 1024 /*dummy*/ + (size_t)WN * NREP * 64;
 }
 
-template <typename T, int NREP, int WN, int CPS>
+template <typename V> __device__ __forceinline__ void reg_touch(V& v) {      // a use of v that costs nothing: the load behind it is waited for HERE
+    if constexpr (std::is_same<V, h2x4>::value) asm volatile("" : "+v"(v.u));
+    else asm volatile("" : "+v"(v));
+}
+
+// NCH > 0 (pk_wstat == 2, p.nchunks == NCH): every compute wave loads the NCH x NREP weight fragments of its n-tiles into registers
+// before the first step and keeps them for the whole launch -- the fragments are the same for every tile, and so is (h2) their
+// preparation.  A step then reads only its pixel fragments from LDS, the ring has the weights' LDS, and the loaders move no weights.
+template <typename T, int NREP, int WN, int CPS, int NCH = 0>
 __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
     using vec = typename Tr<T>::vec;
     constexpr int VEC = Tr<T>::VEC, KC = Tr<T>::KC, ES = (int)sizeof(T);
@@ -526,7 +550,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
     const int stage_bytes = img_bytes * CPS;
     const int npieces = tile_px / 16;
     const int wbuf_off = D * stage_bytes;
-    const int dummy_off = wbuf_off + (p.pk_wstat ? p.nchunks : D * CPS) * WCH;
+    const int dummy_off = wbuf_off + (NCH > 0 ? 0 : p.pk_wstat ? p.nchunks : D * CPS) * WCH;
     const int spt = (p.nchunks + CPS - 1) / CPS;            // steps per tile
     const int bias_off = dummy_off + 1024;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
@@ -557,7 +581,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)p.in_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.wpk, 0, (int)p.wpk_bytes, 0x00020000);
         const int ppl = (npieces + nld - 1) / nld;                      // pixel pieces per loader and step (<= PK1_MAXP)
-        const int wpl = p.pk_wstat ? 0 : (NTB + nld - 1) / nld;         // weight pieces per loader and step
+        const int wpl = (NCH > 0 || p.pk_wstat) ? 0 : (NTB + nld - 1) / nld;         // weight pieces per loader and step
         const int per_step = CPS * (ppl + wpl);
         const __amdgpu_buffer_rsrc_t rsA2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in2, 0, (int)p.in2_bytes, 0x00020000);
         // per-lane source offsets of this loader's pieces, recomputed when the chain moves to the next tile: vo1 = the conv's
@@ -614,7 +638,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
                 }
             }
         };
-        if (p.pk_wstat) {                                               // every chunk of this n-group, once
+        if (NCH == 0 && p.pk_wstat) {                                   // every chunk of this n-group, once
             for (int f = lw; f < p.nchunks * NTB; f += nld) {
                 const int c = f / NTB, n = f - c * NTB;
                 dma16(rsB, (unsigned)lane * 16u, (unsigned)(((size_t)c * p.ntiles_n + nt0 + n) * 1024), lds0 + wbuf_off + f * 1024);
@@ -645,15 +669,109 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
                           (sizeof(T) != 2 || NREP % 2 || (p.Cout & 7) == 0);
     const int crun = (nt0 + wn * NREP) * 16 + (lane >> 4) * 4 * NREP;
     int s = 0;
+    // ---- NCH > 0: this wave's weight fragments, loaded once (wr; h2: as the prepared MFMA operands whi = (hi, hi), wlo = (lo, 0)).
+    // The loads are waited for here, before the first step barrier, so that no step of the tile loop waits for them (vmcnt is
+    // shared with the epilogue's stores).
+    constexpr int NCHR = NCH > 0 ? NCH : 1;
+    constexpr bool PREP = Tr<T>::H2 && NCH > 0 && NCH * NREP <= 16;      // h2: prepared operands where twice the raw registers fit
+    [[maybe_unused]] vec wr[PREP ? 1 : NCHR][NREP];
+    [[maybe_unused]] u32x4 whi[PREP ? NCHR : 1][NREP], wlo[PREP ? NCHR : 1][NREP];
+    if constexpr (NCH > 0) {
+        const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.wpk, 0, (int)p.wpk_bytes, 0x00020000);
+        vec wld[NCH][NREP];
+        const unsigned wv0 = (unsigned)(nt0 + wn * NREP) * 1024u + (unsigned)lane * 16u;       // (per-fragment offsets in the vector offset: one scalar base)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int n = 0; n < NREP; ++n) wld[c][n] = buf_load16<vec>(rsW, wv0 + (unsigned)(c * p.ntiles_n + n) * 1024u, 0u);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int n = 0; n < NREP; ++n) {
+                if constexpr (PREP) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        whi[c][n][i] = __builtin_amdgcn_perm(wld[c][n].u[i], wld[c][n].u[i], 0x01000100u);
+                        wlo[c][n][i] = wld[c][n].u[i] >> 16;
+                    }
+                    reg_touch(whi[c][n]); reg_touch(wlo[c][n]);
+                } else {
+                    wr[c][n] = wld[c][n];
+                    reg_touch(wr[c][n]);
+                }
+            }
+    }
+    VTI_STAMP(0);
     for (int ti = 0; ti < ntiles_mine; ++ti) {
         f32x4 acc[MREP][NREP];
 #pragma unroll
         for (int m = 0; m < MREP; ++m)
 #pragma unroll
             for (int n = 0; n < NREP; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if constexpr (NCH > 0) {
+            constexpr int SPT = (NCH + CPS - 1) / CPS;
+#pragma unroll
+            for (int cs = 0; cs < SPT; ++cs, ++s) {
+                if (s == 2) VTI_STAMP(1);
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                if (s == 2) VTI_STAMP(2);
+                const char* sx = smem + (s % D) * stage_bytes;
+                const int ncc = NCH - cs * CPS < CPS ? NCH - cs * CPS : CPS;      // live chunks of this step (a constant once unrolled)
+                // ONE set of pixel fragments: x[m] is refilled with the next chunk's fragment right after its last MFMA of this chunk
+                vec x[MREP];
+#pragma unroll
+                for (int m = 0; m < MREP; ++m) x[m] = *(const vec*)(sx + xa[m]);
+#pragma unroll
+                for (int cc = 0; cc < CPS; ++cc) {
+                    if (cc < ncc) {
+                    const int c = cs * CPS + cc;
+                    [[maybe_unused]] const char* sxn = sx + (cc + 1) * img_bytes;
+                    // (h2 raw fragments: the selector and the shift pass through an empty asm per chunk, or the loop-invariant preparation of
+                    // ALL fragments is hoisted out of the tile loop -- twice the registers, which is what does not fit)
+                    [[maybe_unused]] unsigned sel_h = 0x01000100u, sh_l = 16u;
+                    if constexpr (Tr<T>::H2 && !PREP) asm volatile("" : "+s"(sel_h), "+s"(sh_l));
+                    if constexpr (Tr<T>::H2) {
+                        // units (chunk, n-tile) in the LDS path's order; prepared operands: nothing but MFMAs and the pixel-fragment reads
+#pragma unroll
+                        for (int n = 0; n < NREP; ++n) {
+                            u32x4 wh_, wl_;
+                            if constexpr (PREP) { wh_ = whi[c][n]; wl_ = wlo[c][n]; }
+                            else {              // raw fragment: prepared here, 8 VALU per 10 MFMAs, free to move under the previous unit's MFMAs
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) { wh_[i] = __builtin_amdgcn_perm(wr[c][n].u[i], wr[c][n].u[i], sel_h); wl_[i] = wr[c][n].u[i] >> sh_l; }
+                            }
+                            if constexpr (PREP) __builtin_amdgcn_sched_barrier(0);
+                            if (cc == 0 && n == 0 && s == 2) VTI_STAMP(3);
+#pragma unroll
+                            for (int j = 0; j < 2 * MREP; ++j) {
+                                const int m = j >> 1;
+                                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, (j & 1) ? wl_ : wh_),
+                                                                                   __builtin_bit_cast(half8, x[m].u), acc[m][n], 0, 0, 0);
+                                if (n == NREP - 1 && (j & 1) && cc + 1 < ncc) x[m] = *(const vec*)(sxn + xa[m]);
+                            }
+                            if constexpr (PREP) __builtin_amdgcn_sched_barrier(0);
+                        }
+                    } else {
+                        if (cc == 0 && s == 2) VTI_STAMP(3);
+#pragma unroll
+                        for (int m = 0; m < MREP; ++m) {
+#pragma unroll
+                            for (int n = 0; n < NREP; ++n) acc[m][n] = mma(wr[c][n], x[m], acc[m][n]);
+                            if (cc + 1 < ncc) x[m] = *(const vec*)(sxn + xa[m]);
+                        }
+                    }
+                    }
+                }
+                if (s == 2) VTI_STAMP(4);
+            }
+        } else
         for (int cs = 0; cs < spt; ++cs, ++s) {
+            // stamps (diagnostic build), third step of the chain: 1 before / 2 after the barrier, 3 first MFMA (operands read and, h2, prepared), 4 step done
+            if (s == 2) VTI_STAMP(1);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
+            if (s == 2) VTI_STAMP(2);
             const int slot = s % D;
             const int ncc = min(CPS, p.nchunks - cs * CPS);         // live chunks of this step (wave-uniform)
             if constexpr (Tr<T>::H2) {
@@ -684,6 +802,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
                         u32x4 wnext = wraw[nxt];                       // raw fragment of unit u + 1 (read at unit u - 1)
                         if (u + 2 < nu) wraw[cur] = *(const u32x4*)wptr(u + 2);
                         __builtin_amdgcn_sched_barrier(0);
+                        if (u == 0 && s == 2) VTI_STAMP(3);
 #pragma unroll
                         for (int j = 0; j < 2 * MREP; ++j) {
                             const int m = j >> 1;
@@ -713,6 +832,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
                         vec x[MREP];
 #pragma unroll
                         for (int m = 0; m < MREP; ++m) x[m] = *(const vec*)(sx + xa[m]);
+                        if (cc == 0 && s == 2) VTI_STAMP(3);
 #pragma unroll
                         for (int m = 0; m < MREP; ++m)
 #pragma unroll
@@ -720,6 +840,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
                     }
                 }
             }
+            if (s == 2) VTI_STAMP(4);
         }
         const int pix0 = (t + ti * tstride) * tile_px + wm * 80;
         if (fast_epi) {
@@ -784,6 +905,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
             conv_epilogue<T, NREP>(p, acc, pvalid, opy, opx, bfr, nt0, wn, lane);
         }
     }
+    VTI_STAMP(12);
 }
 
 bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps) {
@@ -800,6 +922,7 @@ bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat,
 hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     const int NTB = p.WN * nrep;
     if (!conv1_pk_fits(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat, p.pk_cps)) return hipErrorInvalidValue;
+    if (lds_bytes < conv1_pk_lds_bytes(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat, p.pk_cps)) return hipErrorInvalidValue;
     if (p.ntiles_n % NTB || p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8) || p.has_res) return hipErrorInvalidValue;
     if ((size_t)p.in_bytes >= 0x80000000u || (size_t)p.out_bytes >= 0x80000000u) return hipErrorInvalidValue;
     if (p.pk_tiles == 0) return hipSuccess;
@@ -809,6 +932,13 @@ hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_
         using T = typename decltype(t)::type;
         constexpr int CPS = sizeof(T) == 2 ? 1 : 2;            // chunks per step: the planner sets pk_cps to the same value
         if (p.pk_cps != CPS) return hipErrorInvalidValue;
+        if (p.pk_wstat == 2) {      // weights in registers: an instantiation per chunk count; plain convs only
+            if (p.deconv_c) return hipErrorInvalidValue;
+            return combo_dispatch(Conv1PkW<T>{}, [&](auto c) {
+                using C = decltype(c);
+                return launch_lds<conv1_pk<T, C::v[0], C::v[1], CPS, C::v[2]>>(grid, dim3(threads), lds_bytes, st, p);
+            }, nrep, p.WN, p.nchunks);
+        }
         return combo_dispatch(Conv1Pk{}, [&](auto c) {
             using C = decltype(c);
             return launch_lds<conv1_pk<T, C::v[0], C::v[1], CPS>>(grid, dim3(threads), lds_bytes, st, p);

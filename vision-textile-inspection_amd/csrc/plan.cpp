@@ -244,10 +244,18 @@ static bool choose_pk2_cfg(int dtype, const ConvRow& r, int max_batch, ConvCfg& 
     return found;
 }
 
+// VTI_CONV1_WREG=0: the 1x1 kernels stage their weights through LDS as before (A/B aid).  Read whenever a configuration is chosen, so
+// that one process can build both.
+static bool conv1_wreg_enabled() {
+    const char* e = getenv("VTI_CONV1_WREG");
+    return !(e && e[0] == '0');
+}
+
 // Geometry for the persistent 1x1 kernel (conv1_pk): tiles of (M-waves x 80) consecutive pixels, a deep stage ring,
 // weights stationary in LDS when all K chunks of the n-group fit in 64 KB.  These layers are HBM-bound: prefer one
 // n-group (the pixels are read once), then the deepest ring, then the fewest rounds.
-static bool choose_pk1_cfg(int esize, const ConvRow& r, int max_batch, ConvCfg& c, int fth, int fwn, int fnrep) {
+static bool choose_pk1_cfg(int dtype, const ConvRow& r, int max_batch, ConvCfg& c, int fth, int fwn, int fnrep) {
+    const int esize = dtype == VTI_F16 ? 2 : 4;
     const int cps = esize == 2 ? 1 : 2;        // K chunks per step (conv_pk.hip: launch_conv1_pk instantiates the same value per type)
     const char* no = getenv("VTI_NO_PK1");
     if (no && no[0] == '1') return false;
@@ -278,12 +286,18 @@ static bool choose_pk1_cfg(int esize, const ConvRow& r, int max_batch, ConvCfg& 
                 // stationary weights up to 96 KB: streaming them with the pixels takes LDS-DMA ingest from the pixels (model.12.cv1, 384 -> 128 at
                 // 40x40: 8 of every 18 KB per step; 36.5 -> 32.6 us with 96 KB stationary and a 6-deep ring).  VTI_PK1_WSTAT_KB: tools/pk1_sweep.py
                 static const size_t wstat_max = getenv("VTI_PK1_WSTAT_KB") ? (size_t)atoi(getenv("VTI_PK1_WSTAT_KB")) * 1024 : 96 * 1024;
-                const int wstat = (size_t)c.nchunks * NTB * 1024 <= wstat_max ? 1 : 0;
+                const int wstat_lds = (size_t)c.nchunks * NTB * 1024 <= wstat_max ? 1 : 0;
+                // ... or in the compute waves' registers for the whole launch (wstat = 2: an instantiation per chunk count, under the register
+                // budget of ONE workgroup per CU): no weight image in LDS -- a deeper ring -- and no weight reads or (h2) operand
+                // preparation in front of a step's MFMAs, priced as a shorter fixed part of a step
+                const bool wreg_ok = conv1_wreg_enabled() && !deconv && conv1_pk_wreg_instantiated(dtype, NREP, WN, c.nchunks);
+                for (int wreg = 0; wreg <= (wreg_ok ? 1 : 0); ++wreg) {
+                const int wstat = wreg ? 2 : wstat_lds;
                 // one workgroup per CU with the deepest ring that fits -- or (4-byte storage) two co-resident workgroups with half the LDS each:
                 // the same bytes in flight per CU, and one workgroup's MFMAs + epilogue run under the other's waits (as for conv3_pk: `solo`)
                 static const bool no_w2 = getenv("VTI_PK1_NO_WGPC2") && getenv("VTI_PK1_NO_WGPC2")[0] == '1';
                 static const bool force_w2 = getenv("VTI_PK1_FORCE_WGPC2") && getenv("VTI_PK1_FORCE_WGPC2")[0] == '1';     // A/B aid
-                for (int wgpc = (esize == 4 && force_w2) ? 2 : 1; wgpc <= ((esize == 4 && !no_w2) ? 2 : 1); ++wgpc) {
+                for (int wgpc = (esize == 4 && force_w2 && !wreg) ? 2 : 1; wgpc <= ((esize == 4 && !no_w2 && !wreg) ? 2 : 1); ++wgpc) {
                     int depth = 0;
                     for (int dd = 8; dd >= 2; --dd)
                         if (conv1_pk_fits(nwm, WN, NREP, c.nchunks, dd, wstat, cps) &&
@@ -292,8 +306,10 @@ static bool choose_pk1_cfg(int esize, const ConvRow& r, int max_batch, ConvCfg& 
                     const long NT = (total_px + nwm * 80 - 1) / (nwm * 80);
                     const long G = pk_grid(NT, wgpc, gy);
                     const long rounds = (NT + G - 1) / G;
-                    const double solo = esize == 4 ? ((ncomp * wgpc > 4) ? 1.1 : 1.45) : 1.0;
-                    const double step_cyc = 5.0 * NREP * 16 * solo * (esize == 4 ? 2.0 : 1.0) + 250.0 / cps;
+                    // (register-resident weights: nothing in front of a step's MFMAs for a second workgroup to hide -- measured, 64 -> 64 at 80x80 h2:
+                    // 47.2 us with two workgroups per CU and the weights in LDS, 42.8 with one and the weights in registers)
+                    const double solo = esize == 4 ? ((ncomp * wgpc > 4 || wreg) ? 1.1 : 1.45) : 1.0;
+                    const double step_cyc = 5.0 * NREP * 16 * solo * (esize == 4 ? 2.0 : 1.0) + (wreg ? 120.0 : 250.0) / cps;
                     const double t_comp = rounds * (c.nchunks * step_cyc + 1100.0 * NREP) * ((ncomp * wgpc + 3) / 4) / 1.9e9;
                     const double bytes = (double)total_px * ((double)gy * r.c1 + (double)c.gemm_n) * esize +
                                          (wstat ? 0.0 : (double)NT * gy * c.nchunks * NTB * 1024 * 0.25);   // streamed weights (L2)
@@ -305,7 +321,9 @@ static bool choose_pk1_cfg(int esize, const ConvRow& r, int max_batch, ConvCfg& 
                         best = cost; found = true;
                         c.TH = nwm; c.TW = 80; c.WN = WN; c.NREP = NREP; c.pk = 2; c.pk_wgpc = wgpc; c.pk_depth = depth; c.pk_wstat = wstat; c.pk_cps = cps;
                         c.lds = conv1_pk_lds_bytes(nwm, WN, NREP, c.nchunks, depth, wstat, cps);
+                        c.wreg = wreg;
                     }
+                }
                 }
             }
         }
@@ -323,7 +341,8 @@ void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, Con
     c.ntiles_n = (c.gemm_n + 15) / 16;      // rounded up to whole NREP groups once NREP is chosen (below)
     c.nchunks = conv0 ? (32 / KC) : (r.c1 + KC - 1) / KC;
     c.pk = 0;
-    if (allow_pk && !conv0 && (!ftw || ftw == 80) && (!fth || fth <= 4) && choose_pk1_cfg(f16 ? 2 : 4, r, max_batch, c, fth, fwn, fnrep)) return;
+    c.wreg = 0;
+    if (allow_pk && !conv0 && (!ftw || ftw == 80) && (!fth || fth <= 4) && choose_pk1_cfg(dtype, r, max_batch, c, fth, fwn, fnrep)) return;
     c.pk_wstat = 0;
     if (allow_pk && !conv0 && (!ftw || ftw == 20) && (!fth || fth % 4 == 0) && choose_pk_cfg(dtype, r, max_batch, c, fth, fwn, fnrep)) {
         return;
@@ -352,7 +371,8 @@ void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, Con
                 const int tiles = ((Ho + TH - 1) / TH) * ((Wo + TW - 1) / TW);
                 const double m_eff = (double)Ho * Wo / ((double)tiles * BM);
                 const int PH = conv0 ? TH : (TH - 1) * st + ks, PW = conv0 ? TW : (TW - 1) * st + ks;
-                const size_t lds = conv_lds_bytes(ks, st, conv0 ? 1 : 0, TH, TW, WN, NREP);
+                const int wreg = conv1_wreg_enabled() && conv_wreg_ok(ks, st, conv0 ? 1 : 0, WN, NREP) ? 1 : 0;
+                const size_t lds = conv_lds_bytes(ks, st, conv0 ? 1 : 0, TH, TW, WN, NREP, wreg);
                 if (lds > ((fth || ftw) ? 160u : 80u) * 1024) continue;
                 if (!conv_cfg_fits(ks, st, conv0 ? 1 : 0, TH, TW, WN, NREP)) continue;
                 // score: MFMA efficiency, mild preference for compact input patches (halo re-reads),
@@ -369,7 +389,7 @@ void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, Con
                 if (wgs < 512) score *= 0.5 + 0.5 * wgs / 512;
                 if (score > best) {
                     best = score;
-                    c.TH = TH; c.TW = TW; c.WN = WN; c.NREP = NREP; c.lds = lds;
+                    c.TH = TH; c.TW = TW; c.WN = WN; c.NREP = NREP; c.lds = lds; c.wreg = wreg;
                 }
             }
         }

@@ -407,6 +407,7 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
     p.tiles_y = (p.Hout + g.TH - 1) / g.TH; p.tiles_x = (p.Wout + g.TW - 1) / g.TW;
     p.WN = g.WN;
     p.nt = g.threads;
+    p.wreg = g.pk ? 0 : g.wreg;      // the per-tile kernel's flag; conv1_pk's register-resident weights are pk_wstat == 2
     p.pk_lin = pk_linear_map();
     p.act = r.kind == 0; p.out_f32 = out_f32 ? 1 : 0;
     p.deconv_c = deconv ? r.c2 : 0;

@@ -100,9 +100,10 @@ struct ConvCfg {         // launch geometry chosen at plan time
     size_t wpk_off3 = 0, bias_off3 = 0;   // stem_l1_kernel with a fused 1x1 third conv: that conv's stage-2 pack (offsets 2 = layer 1)
     // persistent LDS-DMA kernel (conv_pk.hip): TW = 20, TH = 4 * M-waves; wgpc = co-resident workgroups per CU
     int pk = 0, pk_wgpc = 1;         // pk: 1 = conv3_pk, 2 = conv1_pk (TH = compute waves along M, TW = 80), 3 = bneck_pk (fused 3x3 -> 3x3 pair), 4 = conv3_pk stride 2
-    int pk_depth = 2, pk_wstat = 0;  // conv1_pk: stage-ring depth, weights stationary in LDS
+    int pk_depth = 2, pk_wstat = 0;  // conv1_pk: stage-ring depth, weights stationary in LDS (1) or in the compute waves' registers (2)
     int pk_cps = 1;                  // conv1_pk: K chunks per step
     int threads = 256;               // per-tile kernel: 256, or 512 (fused towers on wide maps: one 8-wave workgroup per CU, 16 x 40 tiles)
+    int wreg = 0;                    // 1x1 kernels: weight fragments feed the MFMAs from registers, no weight image in LDS (VTI_CONV1_WREG=0: off)
 };
 
 struct Op {
@@ -163,6 +164,7 @@ struct ConvParams {
     const void* w2; const float* bias2; void* out2;
     int Cout2, ntiles2, out2_ld, out2_coff, act2 /*0 none, 1 SiLU, 2 sigmoid, 3 DFL + dist2bbox*/, out2_f32, scalar_store2, nat2, out2_bstride;
     int nt;           // threads per workgroup of the per-tile kernel (256 / 512)
+    int wreg;         // 1x1: weight fragments from registers (ConvCfg.wreg)
     float* best;      // act2 == 2 (class scores into pred): also (max score, its first class) per anchor -> best[(b * out2_bstride + pixel) * 2], or null
     float dfl_stride;
     // persistent kernel (conv_pk.hip): tile count, workgroups along x, XCD-contiguous tile ranges, tensor sizes
@@ -183,7 +185,8 @@ struct ConvParams {
 hipError_t launch_conv(int dtype, int ks, int stride, int nrep, int mode, const ConvParams& p,
                        size_t lds_bytes, hipStream_t st);
 bool conv_fusable(int nrep, int nrep2);   // is there a (3x3 NREP) + (1x1 NREP2) fused instantiation
-size_t conv_lds_bytes(int ks, int stride, int mode, int TH, int TW, int WN, int NREP);
+size_t conv_lds_bytes(int ks, int stride, int mode, int TH, int TW, int WN, int NREP, int wreg = 0);
+bool conv_wreg_ok(int ks, int stride, int mode, int WN, int NREP, int threads = 256);   // per-tile 1x1 with register-fed weights: is there an instantiation
 bool conv_cfg_fits(int ks, int stride, int mode, int TH, int TW, int WN, int NREP, int threads = 256);
 // stem (3->16, k3 s2) + layer 1 (16->32, k3 s2) in one kernel: 16 x 20 layer-1 output tiles
 hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st);
@@ -221,6 +224,7 @@ hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_
 size_t conv1_pk_lds_bytes(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps = 1);   // cps: K chunks per step
 bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps = 1);
 bool conv1_pk_instantiated(int nrep, int wn);
+bool conv1_pk_wreg_instantiated(int dtype, int nrep, int wn, int nchunks);   // wstat == 2: the n-group's weights in the compute waves' registers
 hipError_t launch_bneck_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
 size_t bneck_pk_lds_bytes(int TH, int NREP);
 size_t bneck_pk_lds_bytes(int TH, int NREP, int depth);
