@@ -275,7 +275,7 @@ int32_t vti_measure(vti_ctx* ctx, const vti_measure_params* params, const uint8_
                     int32_t capacity, int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes, double* frame_f64,
                     int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream);
 
-/* ---- the stitch-distance checker's measurement on device (Utils/check_stitch_distance.py:281-553, the drawing left out) ------- */
+/* ---- the stitch-distance checker's measurement on device (Utils/check_stitch_distance.py:281-553; the drawing: vti_annotate_checker) */
 /* Settings of vti_measure_checker: the calibration as in vti_measure_params, and the checker's module constants.  Defaults
  * (check_stitch_distance.py:20-39): stitch_id 0, fabric_id 1, min_stitches 3, max_px_distance 150, envelope_neighborhood 3,
  * skip_cluster 0, kmeans_iters 10, frame_buffer 8.  There is no ROI and no two_row threshold: the checker has neither.  drop_empty
@@ -530,6 +530,47 @@ int32_t vti_annotate_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void*
                             const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
                             int32_t n_sel, int32_t max_points, const void* host_out_table, const void* dev_out_table, uint8_t* dev_out,
                             int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
+
+/* ---- the stitch-distance checker's picture on device (Utils/check_stitch_distance.py:293-545): vti_annotate for the checker -------- */
+/* The checker returns (annotated, info_text); vti_measure_checker gives the second half, this call the first, for the n_sel frames
+ * the caller wants a picture of.  dev_out[k] is frame select[k] of dev_frames (u8 [B,H0,W0,3] BGR, one frame size) with, in the
+ * checker's order and BGR colours:
+ *   a. per existing instance in detection order its int-truncated box, stitch (255,255,0) 1 px, fabric (255,0,255) 2 px (:323-336).
+ *      There is no ROI and no keep test; "existing" is vti_measure_checker's rule: with drop_empty = 1 an instance whose mask is
+ *      empty as predict returns it, or whose slot is at or past `capacity`, does not exist and has no box; with drop_empty = 0 every
+ *      instance has one;
+ *   b. [status VTI_MEASURE_NO_FABRIC stops here (:345-347)]
+ *   c. the UPPER envelope of the fabric union -- the union of vti_measure_checker: per existing fabric instance its nearest-resized
+ *      mask when that has a set pixel, else the filled rectangle (int x1, int y1)..(int x2, int y2), corners inclusive, clipped to
+ *      the frame -- the smallest set row per column, every max(1, n / 1000)-th valid column, as an open polyline (255,128,0) 2 px
+ *      (:349-360);
+ *   d. [VTI_MEASURE_NO_STITCHES stops here (:404-406)]
+ *   e. per stitch of the FINAL set (VTI_STITCH_SELECTED and VTI_STITCH_NEAR when any selected stitch is near, else every selected
+ *      stitch) in rank order, its primitives together (:465-510): with VTI_STITCH_DIST a 1-px line (0,255,0) from (clip(round(cx), 0,
+ *      W0 - 1), round(edge_y)) to (round(cx), round(cy)) and a filled circle r = 2 (255,0,255) at the edge point; with
+ *      VTI_STITCH_WIDTH and when world(left, cy) and world(right, cy) both exist (|n . ray| >= 1e-9; a width from the local-scale
+ *      estimate sets the flag and draws nothing) filled circles r = 3 (200,200,0) at (round(left), round(cy)) and (round(right),
+ *      round(cy)) and the 1-px line between them; always a filled circle r = 4 (0,255,0) at (round(cx), round(cy));
+ *   f. every outer contour of that union, filled boxes included (the tracer of vti_mask_polygons, CHAIN_APPROX_SIMPLE), as a closed
+ *      polyline (255,128,0) 2 px (:543-545).
+ * round = half to even.  A later primitive overwrites an earlier one.  The pixels of a primitive are vti_annotate's, byte for byte the
+ * package's annotate.rasterise(frame, annotate.checker_display_list(...)); text is the host's (measure.checker_text_items /
+ * annotate.put_text; all of it is drawn last).  A frame whose status is none of OK, NO_FABRIC, NO_STITCHES is copied as it is.
+ * params: the struct vti_measure_checker took (its calibration decides the width markers; the class ids and drop_empty the boxes and
+ * the union), checked as there.  Masks, dets, xyxy, counts, offsets, max_det, capacity, native: as vti_measure_checker took them;
+ * frame_i32, stitch_f64, stitch_i32: what it wrote (all three required).  host_select / dev_select, n_sel, max_points, dev_out
+ * u8 [n_sel,H0,W0,3] (every byte is written, nothing else is; dev_frames is never written), dev_status i32 [n_sel] (0 or
+ * VTI_ANNOTATE_OUTLINE_SKIPPED: that frame is drawn without step f) and the limits 1 <= H0, W0 <= 8192, 1 <= max_det <=
+ * VTI_MEASURE_MAX_DET are vti_annotate's.  dev_scratch: >= vti_annotate_scratch_bytes(ctx, n_sel, max_det, H0, W0, max_points),
+ * 256-byte aligned: the layout is vti_annotate's.  Every argument check (VTI_ERR_ARG; vti_last_error names the argument) runs before
+ * the first HIP call.  Three launches on `stream` (the checker's display list + union, then vti_annotate's outline and raster
+ * kernels); no host synchronisation.  One frame size and one camera, as the checker stage. */
+int32_t vti_annotate_checker(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t H0, int32_t W0, const vti_checker_params* params,
+                             const uint8_t* dev_masks, int32_t native, const float* dev_dets, const float* dev_xyxy,
+                             const int32_t* dev_counts, const int32_t* dev_offsets, int32_t max_det, int32_t capacity,
+                             const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                             const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                             uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the model-check viewer's picture on device (Utils/check_model.py:155-256, annotate_result) ------------------------------------ */
 /* The frames dev_select[k] of the batch as the viewer shows them, byte for byte the package's overlay.py (render): per instance in

@@ -134,6 +134,8 @@ SIGNATURES = {
     "vti_annotate_frames_scratch_bytes": (_I64, [_P, _P, _I32, _I32]),
     "vti_annotate_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32,
                                    _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vti_annotate_checker": (_I32, [_P, _P, _I32, _I32, _I32, C.POINTER(VtiCheckerParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P,
+                                    _P, _P, _I32, _I32, _P, _P, _P, _SZ, _P]),
     "vti_overlay_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
     "vti_overlay": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _F, _F, _P, _P, _I32, _I32, _P,
                            _I32, _P, _P, _P, _SZ, _P]),

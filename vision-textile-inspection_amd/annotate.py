@@ -175,6 +175,128 @@ def display_list(h, w, cls, xyxy, masks_or_union, rows, params, live=None, nonem
     return done(prims)
 
 
+# ---- what the stitch-distance checker draws (Utils/check_stitch_distance.py:293-545) -----------------------------------------
+CHECKER_CENTRE_COLOUR = (0, 255, 0)         # :510 (the distance line's green); the checker's outline is drawn in ENVELOPE_COLOUR (:545)
+CHECKER_CENTRE_RADIUS = 4
+
+
+def world_point_exists(u, v, K, dist, R, t):
+    """Whether pixel_to_world_using_camera_plane (:477-503) returns a point for pixel (u, v): cv2.undistortPoints' five fixed-point
+    steps (5-coefficient model), then |n . ray| >= 1e-9 with n = R[:, 2].  Float64 in the order libvti's pixel_to_world evaluates it
+    (csrc/measure_dev.h), so host and device agree on the threshold to the last bit."""
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    k1, k2, p1, p2, k3 = (float(d) for d in np.asarray(dist, dtype=np.float64).ravel()[:5])
+    ifx, ify = 1.0 / float(K[0, 0]), 1.0 / float(K[1, 1])
+    x = (float(u) - float(K[0, 2])) * ifx
+    y = (float(v) - float(K[1, 2])) * ify
+    x0, y0 = x, y
+    for _ in range(5):
+        r2 = x * x + y * y
+        icdist = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        if icdist < 0:
+            x, y = x0, y0
+            break
+        dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+        x, y = (x0 - dx) * icdist, (y0 - dy) * icdist
+    denom = (float(R[0, 2]) * x + float(R[1, 2]) * y) + float(R[2, 2])
+    return abs(denom) >= 1e-9
+
+
+def checker_union(h, w, cls, xyxy, masks, params):
+    """The checker's fabric union (:310-336, :344) as vti_measure_checker defines it, and which instances exist.  Per existing
+    fabric instance: its mask at the frame size (cv2.INTER_NEAREST) when that has a set pixel, else the filled rectangle of its
+    int-truncated box, corners inclusive, clipped to the frame.  With drop_empty an instance whose mask is None (a slot past the
+    capacity) or empty as predict returns it does not exist.  -> (union u8 [h,w], exists bool [n], int boxes [n,4])."""
+    n = len(cls)
+    ib = np.trunc(np.asarray(xyxy, dtype=np.float64).reshape(-1, 4)).astype(np.int64)
+    drop, fabric_id = bool(_get(params, "drop_empty")), int(_get(params, "fabric_id"))
+    exists = np.array([not drop or (masks[i] is not None and np.count_nonzero(masks[i]) > 0) for i in range(n)], bool)
+    union = np.zeros((h, w), np.uint8)
+    for i in range(n):
+        if not exists[i] or int(cls[i]) != fabric_id:
+            continue
+        bitmap = None if masks[i] is None else frame_bitmap(masks[i], h, w)
+        if bitmap is not None and bitmap.any():
+            union |= bitmap
+            continue
+        x1, y1, x2, y2 = (int(v) for v in ib[i])
+        r0, r1, c0, c1 = max(min(y1, y2), 0), min(max(y1, y2), h - 1), max(min(x1, x2), 0), min(max(x1, x2), w - 1)
+        if r0 <= r1 and c0 <= c1:
+            union[r0:r1 + 1, c0:c1 + 1] = 1
+    return union, exists, ib
+
+
+def checker_display_list(h, w, cls, xyxy, masks, rows, params, max_points=None, with_status=False):
+    """The ordered primitives of Utils/check_stitch_distance.py:293-545 for one h x w frame, in display_list's form: rasterise(frame,
+    checker_display_list(...)) is the byte-for-byte specification of vti_annotate_checker's picture.
+    cls [n], xyxy f32 [n,4] (frame px), in detection order.  masks: the n masks as predict returns them (letterbox or frame size;
+    None for a slot past the capacity).  rows: vti_measure_checker's outputs for this frame: dict(status=frame_i32[b,0], flags [n],
+    rank [n], f64 [n,7]); entries of instances without a slot are ignored (flags 0).  params: a CheckerParams (or a dict with
+    stitch_id, fabric_id, drop_empty, K, dist, R, t).  max_points, with_status: as display_list.
+    The order: a. a box per existing instance; b. [NO_FABRIC stops]; c. the upper envelope of the union; d. [NO_STITCHES stops];
+    e. per stitch of the final set, in rank order: distance line and edge point, width ends and line, centroid; f. the outline."""
+    n = len(cls)
+    status = int(rows["status"])
+    done = lambda prims, word=0: (prims, word) if with_status else prims
+    if status not in (OK, NO_FABRIC, NO_STITCHES):
+        return done([])
+    masks = list(masks)
+    stitch_id, fabric_id = int(_get(params, "stitch_id")), int(_get(params, "fabric_id"))
+    union, exists, ib = checker_union(h, w, cls, xyxy, masks, params)
+    prims = []
+    # a. boxes in detection order (:323-336): no ROI, no keep test
+    for i in range(n):
+        if not exists[i]:
+            continue
+        box = tuple(int(v) for v in ib[i])
+        if int(cls[i]) == stitch_id:
+            prims.append(("rect", box[:2], box[2:], STITCH_BOX_COLOUR, 1))
+        elif int(cls[i]) == fabric_id:
+            prims.append(("rect", box[:2], box[2:], FABRIC_BOX_COLOUR, 2))
+    # b. no fabric (:345-347)
+    if status == NO_FABRIC:
+        return done(prims)
+    # c. the upper envelope (:349-360)
+    has = union.any(axis=0)
+    top = np.argmax(union > 0, axis=0)
+    pts = [(x, int(top[x])) for x in range(w) if has[x]]
+    if pts:
+        step = max(1, len(pts) // 1000)
+        prims.append(("polyline", np.array(pts[::step], dtype=np.int32).reshape(-1, 2), False, ENVELOPE_COLOUR, 2))
+    # d. no stitches (:404-406)
+    if status == NO_STITCHES:
+        return done(prims)
+    # e. the final set in rank order (:431-454, :465-510), as measure.checker_text_items derives it
+    f64 = np.asarray(rows["f64"], dtype=np.float64).reshape(-1, 7)
+    flags = [int(f) for f in rows["flags"]]
+    order = [i for _, i in sorted((int(rows["rank"][i]), i) for i in range(n)
+                                  if masks[i] is not None and flags[i] & KEPT and int(rows["rank"][i]) >= 0)]
+    any_near = any(flags[i] & (SELECTED | NEAR) == SELECTED | NEAR for i in order)
+    geom = tuple(params[name] if isinstance(params, dict) else getattr(params, name) for name in ("K", "dist", "R", "t"))
+    for i in order:
+        if not (flags[i] & SELECTED and (not any_near or flags[i] & NEAR)):
+            continue
+        cx, cy, left, right = (float(v) for v in f64[i, :4])
+        centre = (int(round(cx)), int(round(cy)))
+        if flags[i] & DIST:
+            e = (int(np.clip(centre[0], 0, w - 1)), int(round(float(f64[i, 5]))))
+            prims += [("line", e, centre, DIST_COLOUR, 1), ("circle", e, 2, EDGE_POINT_COLOUR)]
+        # a width from the local-scale estimate (:500-507) sets WIDTH too but draws nothing: both ends need a world point
+        if flags[i] & WIDTH and world_point_exists(left, cy, *geom) and world_point_exists(right, cy, *geom):
+            a, b = (int(round(left)), centre[1]), (int(round(right)), centre[1])
+            prims += [("circle", a, 3, WIDTH_COLOUR), ("circle", b, 3, WIDTH_COLOUR), ("line", a, b, WIDTH_COLOUR, 1)]
+        prims.append(("circle", centre, CHECKER_CENTRE_RADIUS, CHECKER_CENTRE_COLOUR))
+    # f. the outline of the same union (:543-545)
+    contours = polygons.find_external_contours(union)
+    if max_points is not None and sum(len(c) for c in contours) > max_points:
+        return done(prims, STATUS_OUTLINE)
+    for c in contours:
+        prims.append(("polyline", np.asarray(c, dtype=np.int32).reshape(-1, 2), True, ENVELOPE_COLOUR, 2))
+    return done(prims)
+
+
 # ---- which pixels: OpenCV's drawing.cpp, LINE_8, shift = 0 ----------------------------------------------------------------
 def _tdiv(a, b):
     """C's integer division (truncation towards zero)."""

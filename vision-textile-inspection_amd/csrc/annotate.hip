@@ -24,6 +24,11 @@
 // what lies beyond is never read), the outline is launched in both instantiations when the selection needs both (each leaves the
 // frames of the other alone, by the frame's own size), and the raster grid is the largest frame's: workgroups past a frame's last
 // tile leave before the first barrier.
+//
+// vti_annotate_checker (the stitch-distance checker's picture, Utils/check_stitch_distance.py:293-545) puts a prep kernel of its own,
+// annotate_checker_prep_kernel, in front of the same outline and raster kernels: the same records, meta, envelope points and union,
+// other contents (no ROI, box fall-backs filled into the union, the upper envelope, the six records of a final stitch together at
+// 2 + M + 6 j).  The one thing the shared kernels take from the caller is the colour index of the outline's polylines.
 #include <climits>
 #include <cstring>
 
@@ -59,7 +64,7 @@ struct AnnArgs {
     const uint8_t* masks; const float* dets; const float* xyxy; const int* counts; const int* offsets;
     int max_det, row, capacity, H, W;
     const int* frame_i32; const double* stitch_f64; const int* stitch_i32;
-    int max_points;
+    int max_points, outline_colour;         // the colour index of the outline's polylines (C_OUTLINE; the checker's: C_ENVELOPE)
     Rec* recs; int* meta; int2* env_pts; int2* cont; u64* uni;
     unsigned char* areas; size_t area_bytes, off_runs, off_rows;
 };
@@ -256,6 +261,235 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
     if (tid == 0) meta[META_OUTLINE] = 1;
 }
 
+// vti_annotate_checker's prep: the display list of Utils/check_stitch_distance.py:293-545 in the same records, meta, envelope points
+// and union as annotate_prep_kernel writes, so that the outline and raster kernels serve both.  What differs: no ROI and no keep test
+// (a box per existing instance); every existing fabric instance joins the union, with its mask when the mask at the frame size has a
+// set bit, else with its int-truncated box filled, corners inclusive, clipped to the frame (upper_envelope_bits_kernel's rule, from
+// the mask's own bits here: a source bit counts when some frame row AND some frame column map to it); the UPPER envelope; markers for
+// the final set only, the six records of stitch rank j together at 2 + M + 6 j: edge line, edge point, the two width ends, the width
+// line, the centroid (r = 4).  The width markers need both world points (a width from the local-scale estimate sets VTI_STITCH_WIDTH
+// too), so the two ends go through the pixel_to_world that vti_measure_checker used.  c: checker_pack's row, by value.
+template <bool NATIVE>
+__global__ __launch_bounds__(kThreads) void annotate_checker_prep_kernel(AnnArgs a, CameraRow c) {
+    extern __shared__ int s_env[];              // [W0]: the nearest-resize column table, then the envelope | hit bits [W / 32], [H / 32]
+    __shared__ int s_fab[VTI_MEASURE_MAX_DET][5];       // instance i (< 0: a filled box), first and last row, first and last column
+    __shared__ int s_nfab, s_w[kThreads / 64];
+    const int tid = threadIdx.x, k = blockIdx.x, M = a.max_det;
+    const int b = min(max(a.select[k], 0), a.B - 1);
+    const int H0 = a.H0, W0 = a.W0, WW = a.WW;
+    Rec* recs = a.recs + (size_t)k * nrec(M);
+    int* meta = a.meta + (size_t)k * META_INTS;
+    for (int i = tid; i < nrec(M); i += kThreads) recs[i] = Rec{K_NOP, 0, 0, 0, 0, 0, 0, 0};
+    if (tid < META_INTS) meta[tid] = 0;
+    if (tid == 0) { a.status_out[k] = 0; s_nfab = 0; }
+    const int status = a.frame_i32[6 * (size_t)b];
+    if (status != VTI_MEASURE_OK && status != VTI_MEASURE_NO_FABRIC && status != VTI_MEASURE_NO_STITCHES) return;   // a plain copy
+    const int stitch_id = c.stitch_id, fabric_id = c.fabric_id, drop_empty = c.drop_empty;
+    const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
+    const int Hm = NATIVE ? H0 : a.H, wpr = NATIVE ? 2 * WW : a.W >> 5;       // rows and 32-bit words per row of a mask slot
+    const double ify = 1.0 / ((double)H0 / (double)a.H), ifx = 1.0 / ((double)W0 / (double)a.W);
+    unsigned* s_col = (unsigned*)(s_env + W0);          // source columns / rows that a frame column / row is resized from
+    unsigned* s_row = s_col + ((a.W + 31) >> 5);
+    if (!NATIVE) {
+        for (int j = tid; j < ((a.W + 31) >> 5) + ((a.H + 31) >> 5); j += kThreads) s_col[j] = 0;
+        __syncthreads();
+        for (int x = tid; x < W0; x += kThreads) {
+            const int sx = nn_src(x, ifx, a.W);
+            s_env[x] = sx;
+            atomicOr(&s_col[sx >> 5], 1u << (sx & 31));
+        }
+        for (int y = tid; y < H0; y += kThreads) {
+            const int sy = nn_src(y, ify, a.H);
+            atomicOr(&s_row[sy >> 5], 1u << (sy & 31));
+        }
+    }
+    __syncthreads();
+    // cv2.rectangle(tmp, (x1i, y1i), (x2i, y2i), 1, -1) clipped to the frame (:332-333); an empty range when nothing is left
+    auto box_entry = [&](int pos, const float* bx) {
+        const int x1 = clampc((int)bx[0]), y1 = clampc((int)bx[1]), x2 = clampc((int)bx[2]), y2 = clampc((int)bx[3]);
+        s_fab[pos][0] = -1;
+        s_fab[pos][1] = max(min(y1, y2), 0); s_fab[pos][2] = min(max(y1, y2), H0 - 1);
+        s_fab[pos][3] = max(min(x1, x2), 0); s_fab[pos][4] = min(max(x1, x2), W0 - 1);
+    };
+    // a. boxes in detection order (:323-336); the fabric instances are listed for the union
+    for (int i = tid; i < n; i += kThreads) {
+        const int s = s0 + i;
+        const bool live = s >= 0 && s < a.capacity;
+        const size_t di = (size_t)b * M + i;
+        const float* d = a.dets + di * a.row;
+        const float* bx = a.xyxy + di * 4;
+        const int cls = (int)d[5];
+        const int x1 = clampc((int)bx[0]), y1 = clampc((int)bx[1]), x2 = clampc((int)bx[2]), y2 = clampc((int)bx[3]);
+        if (cls == stitch_id) {                 // a live stitch exists when vti_measure_checker listed it
+            const bool exists = live ? (a.stitch_i32[2 * (size_t)s] & VTI_STITCH_KEPT) != 0 : !drop_empty;
+            if (exists) recs[1 + i] = Rec{K_RECT, C_STITCH_BOX, 1, 0, x1, y1, x2, y2};
+        } else if (cls == fabric_id) {
+            if (!live) {                        // past the capacity: an empty mask
+                if (!drop_empty) {
+                    recs[1 + i] = Rec{K_RECT, C_FABRIC_BOX, 2, 0, x1, y1, x2, y2};
+                    box_entry(atomicAdd(&s_nfab, 1), bx);
+                }
+            } else {
+                int ya, yb;         // a mask is zero outside these rows of its slot (as vti_measure_checker's envelope kernel reads it)
+                if (NATIVE) { ya = (int)floorf(bx[1]); yb = (int)ceilf(bx[3]); }
+                else { ya = (int)floorf(d[1] - 8.f); yb = (int)ceilf(d[3] + 8.f); }
+                const int pos = atomicAdd(&s_nfab, 1);
+                s_fab[pos][0] = i; s_fab[pos][1] = max(ya, 0); s_fab[pos][2] = min(yb, Hm - 1); s_fab[pos][3] = 0; s_fab[pos][4] = 0;
+            }
+        }
+    }
+    __syncthreads();
+    const int nfab = s_nfab;
+    const unsigned* bits = (const unsigned*)a.masks;
+    for (int f = 0; f < nfab; ++f) {            // per live fabric instance: does it exist (drop_empty), and has its frame-size mask a bit
+        const int i = s_fab[f][0], ya = s_fab[f][1], yb = s_fab[f][2];
+        if (i < 0) continue;                    // uniform
+        int raw = 0, res = 0;
+        const unsigned* m = bits + ((size_t)(s0 + i) * Hm + ya) * wpr;
+        const int nw = yb >= ya ? (yb - ya + 1) * wpr : 0;
+        for (int j = tid; j < nw; j += kThreads) {
+            const unsigned word = m[j];
+            if (!word) continue;
+            raw = 1;
+            if (NATIVE) res = 1;
+            else {
+                const int r = j / wpr, q = j - r * wpr, sy = ya + r;
+                res |= ((s_row[sy >> 5] >> (sy & 31)) & 1u) != 0 && (word & s_col[q]) != 0;
+            }
+        }
+        raw = __syncthreads_or(raw);
+        res = __syncthreads_or(res);
+        if (tid == 0) {
+            const float* bx = a.xyxy + ((size_t)b * M + i) * 4;
+            const bool exists = !drop_empty || raw;
+            if (exists) recs[1 + i] = Rec{K_RECT, C_FABRIC_BOX, 2, 0, clampc((int)bx[0]), clampc((int)bx[1]), clampc((int)bx[2]), clampc((int)bx[3])};
+            if (exists && !res) box_entry(f, bx);
+            else if (!exists) { s_fab[f][0] = -1; s_fab[f][1] = 1; s_fab[f][2] = 0; }      // an empty row range: nothing for the union
+        }
+    }
+    if (status == VTI_MEASURE_NO_FABRIC) return;        // b. (:345-347)
+    __syncthreads();
+    // c. the union at the frame size: u64 [H0, WW], bits at columns >= W0 clear (annotate_prep_kernel's 4a, and the filled boxes)
+    u64* uni = a.uni + (size_t)k * a.H0 * a.WW;
+    const u64 last_valid = (W0 & 63) ? ((1ull << (W0 & 63)) - 1) : ~0ull;
+    for (int idx = tid; idx < H0 * WW; idx += kThreads) {
+        const int y = idx / WW, w = idx - y * WW;
+        const int c0 = w * 64, c1 = min(c0 + 63, W0 - 1);
+        const int sy = NATIVE ? y : nn_src(y, ify, a.H);
+        const int w0 = NATIVE ? 0 : s_env[c0] >> 5, w1 = NATIVE ? 0 : s_env[c1] >> 5;
+        u64 acc = 0;
+        for (int f = 0; f < nfab; ++f) {
+            const int i = s_fab[f][0];
+            if (i < 0) {
+                const int lo = max(s_fab[f][3], c0), hi = min(s_fab[f][4], c1);
+                if (y >= s_fab[f][1] && y <= s_fab[f][2] && lo <= hi) acc |= (~0ull >> (63 - (hi - lo))) << (lo - c0);
+                continue;
+            }
+            if (sy < s_fab[f][1] || sy > s_fab[f][2]) continue;
+            if (NATIVE) {
+                acc |= ((const u64*)a.masks)[(size_t)(s0 + i) * H0 * WW + idx];
+            } else {
+                const unsigned* srow = bits + ((size_t)(s0 + i) * a.H + sy) * wpr;
+                unsigned any = 0;
+                for (int q = w0; q <= w1; ++q) any |= srow[q];
+                if (!any) continue;
+                for (int x = c0; x <= c1; ++x) {
+                    const int sx = s_env[x];
+                    acc |= (u64)((srow[sx >> 5] >> (sx & 31)) & 1u) << (x - c0);
+                }
+            }
+        }
+        if (w == WW - 1) acc &= last_valid;
+        uni[idx] = acc;
+    }
+    __syncthreads();
+    // the upper envelope per column (:238-251): a thread per 64 columns and band of rows, top row first
+    for (int x = tid; x < W0; x += kThreads) s_env[x] = INT_MAX;
+    __syncthreads();
+    {
+        const int G = max(1, kThreads / WW), chunk = (H0 + G - 1) / G;
+        for (int t = tid; t < WW * G; t += kThreads) {
+            const int w = t % WW, g = t / WW, r_lo = g * chunk, r_hi = min(H0, r_lo + chunk);
+            const u64 full = w == WW - 1 ? last_valid : ~0ull;
+            u64 seen = 0;
+            for (int y = r_lo; y < r_hi && seen != full; ++y) {
+                const u64 word = uni[(size_t)y * WW + w];
+                u64 m = word & ~seen;
+                while (m) {
+                    atomicMin(&s_env[w * 64 + __builtin_ctzll(m)], y);
+                    m &= m - 1;
+                }
+                seen |= word;
+            }
+        }
+    }
+    __syncthreads();
+    for (int x = tid; x < W0; x += kThreads) if (s_env[x] == INT_MAX) s_env[x] = -1;
+    __syncthreads();
+    // its valid columns, every step-th of them (:352-360), as the envelope's point list
+    int nv = 0;
+    for (int x0 = 0; x0 < W0; x0 += kThreads) {
+        int tot;
+        (void)poly::block_excl_scan(x0 + tid < W0 && s_env[x0 + tid] >= 0, s_w, tot);
+        nv += tot;
+    }
+    if (nv > 0) {
+        const int step = max(1, nv / 1000);
+        int2* pts = a.env_pts + (size_t)k * a.W0;
+        int carry = 0;
+        for (int x0 = 0; x0 < W0; x0 += kThreads) {
+            const int x = x0 + tid;
+            const int f = x < W0 && s_env[x] >= 0;
+            int tot;
+            const int rank = carry + poly::block_excl_scan(f, s_w, tot);
+            if (f && rank % step == 0) pts[rank / step] = make_int2(x, s_env[x]);
+            carry += tot;
+        }
+        if (tid == 0) {
+            const int ne = (nv + step - 1) / step;
+            meta[META_N_ENV] = ne;
+            recs[1 + M] = Rec{K_POLY, C_ENVELOPE, 2, ne, 0, 0, 0, 0};
+        }
+    }
+    if (status == VTI_MEASURE_NO_STITCHES) return;      // d. (:404-406)
+    // e. the final set (:431-454): the selected stitches that are near, or every selected one when none is
+    const int sel_near = VTI_STITCH_KEPT | VTI_STITCH_SELECTED | VTI_STITCH_NEAR;
+    int near = 0;
+    for (int i = tid; i < n; i += kThreads) {
+        const int s = s0 + i;
+        if (s < 0 || s >= a.capacity) continue;
+        near |= (a.stitch_i32[2 * (size_t)s] & sel_near) == sel_near && a.stitch_i32[2 * (size_t)s + 1] >= 0;
+    }
+    near = __syncthreads_or(near);
+    for (int i = tid; i < n; i += kThreads) {
+        const int s = s0 + i;
+        if (s < 0 || s >= a.capacity) continue;
+        const int fl = a.stitch_i32[2 * (size_t)s], j = a.stitch_i32[2 * (size_t)s + 1];
+        if (!(fl & VTI_STITCH_KEPT) || j < 0 || j >= M) continue;
+        if (!(fl & VTI_STITCH_SELECTED) || (near && !(fl & VTI_STITCH_NEAR))) continue;
+        const double* v = a.stitch_f64 + (size_t)s * 7;
+        const int cx = round_px(v[0]), cy = round_px(v[1]);
+        Rec* r = recs + 2 + M + 6 * j;
+        if (fl & VTI_STITCH_DIST) {             // :485-486
+            const int ex = min(max(cx, 0), W0 - 1), ey = round_px(v[5]);
+            r[0] = Rec{K_LINE, C_DIST, 1, 0, ex, ey, cx, cy};
+            r[1] = Rec{K_CIRCLE, C_FABRIC_BOX, 0, 0, ex, ey, 2, 0};
+        }
+        if (fl & VTI_STITCH_WIDTH) {            // :493-499: only a width between two world points is drawn
+            double pl[3], pr[3];
+            const bool okl = pixel_to_world(c.g, v[2], v[1], pl), okr = pixel_to_world(c.g, v[3], v[1], pr);
+            if (okl && okr) {
+                const int lx = round_px(v[2]), rx = round_px(v[3]);
+                r[2] = Rec{K_CIRCLE, C_WIDTH, 0, 0, lx, cy, 3, 0};
+                r[3] = Rec{K_CIRCLE, C_WIDTH, 0, 0, rx, cy, 3, 0};
+                r[4] = Rec{K_LINE, C_WIDTH, 1, 0, lx, cy, rx, cy};
+            }
+        }
+        r[5] = Rec{K_CIRCLE, C_DIST, 0, 0, cx, cy, 4, 0};       // :510
+    }
+    if (tid == 0) meta[META_OUTLINE] = 1;       // f. (:543-545)
+}
+
 // vertex `pos` of a contour that starts at `base`: (x | y << 16, index of the next vertex)
 struct ContEmit {
     int2* out; int base, limit;
@@ -323,7 +557,7 @@ __global__ __launch_bounds__(kThreads) void annotate_outline_kernel(AnnArgs a) {
             a.status_out[k] = 1;
         } else {
             a.meta[(size_t)k * META_INTS + META_N_CONT] = s_total;
-            a.recs[(size_t)k * nrec(M) + 2 + 7 * M] = Rec{K_CONTOURS, C_OUTLINE, 2, s_total, 0, 0, 0, 0};
+            a.recs[(size_t)k * nrec(M) + 2 + 7 * M] = Rec{K_CONTOURS, a.outline_colour & 7, 2, s_total, 0, 0, 0, 0};
         }
     }
 }
@@ -384,7 +618,7 @@ __global__ __launch_bounds__(kThreads) void annotate_raster_kernel(AnnArgs a) {
             const int2 u = cont[j];
             if (u.y < 0 || u.y >= n_cont) continue;
             const int2 v = cont[u.y];
-            P.key = (unsigned)(2 + 7 * M + 1) << 3 | C_OUTLINE;
+            P.key = (unsigned)(2 + 7 * M + 1) << 3 | (unsigned)(a.outline_colour & 7);
             nseg = 1; x0 = u.x & 0xffff; y0 = u.x >> 16; x1 = v.x & 0xffff; y1 = v.x >> 16;
         }
         for (int e = 0; e < nseg; ++e) {
@@ -458,6 +692,42 @@ void annotate_layout(int n_sel, int max_det, int H0, int W0, int max_points, Ann
     L.total = L.off_areas + (size_t)n_sel * L.area_bytes;
 }
 
+// The launch arguments both entry points share, and the scratch carved by annotate_layout.
+static AnnArgs annotate_args(const AnnotateLayout& L, const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks, int native,
+                             const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det, int nm,
+                             int capacity, int H, int W, const int* frame_i32, const double* stitch_f64, const int* stitch_i32,
+                             const int* select, int n_sel, int max_points, int outline_colour, uint8_t* out, int* status, void* scratch) {
+    unsigned char* ws = (unsigned char*)scratch;
+    AnnArgs a;
+    memset(&a, 0, sizeof a);
+    a.frames = frames; a.out = out; a.status_out = status;
+    a.select = select; a.B = B; a.n_sel = n_sel; a.H0 = H0; a.W0 = W0; a.WW = L.WW;
+    a.masks = masks; a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
+    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H = native ? H0 : H; a.W = native ? W0 : W;
+    a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
+    a.max_points = max_points; a.outline_colour = outline_colour;
+    a.recs = (Rec*)(ws + L.off_recs); a.meta = (int*)(ws + L.off_meta); a.env_pts = (int2*)(ws + L.off_env);
+    a.cont = (int2*)(ws + L.off_cont); a.uni = (u64*)(ws + L.off_union);
+    a.areas = ws + L.off_areas; a.area_bytes = L.area_bytes; a.off_runs = L.off_runs; a.off_rows = L.off_rows;
+    return a;
+}
+
+// The outline and raster launches that follow either prep kernel.
+static hipError_t launch_outline_raster(const AnnArgs& a, const AnnotateLayout& L, const AnnotateFrames* fr, hipStream_t st) {
+    hipError_t e;
+    if (fr ? fr->any_lds : L.in_lds) {
+        e = launch_lds<annotate_outline_kernel<true>>(dim3(a.n_sel), dim3(kThreads), (size_t)poly::kLdsBytes, st, a);
+        if (e != hipSuccess) return e;
+    }
+    if (fr ? fr->any_global : !L.in_lds) {
+        e = launch_lds<annotate_outline_kernel<false>>(dim3(a.n_sel), dim3(kThreads), 0, st, a);
+        if (e != hipSuccess) return e;
+    }
+    const int tiles = (int)(((fr ? fr->max_px : (long long)a.H0 * a.W0) + kTile - 1) / kTile);
+    hipLaunchKernelGGL(annotate_raster_kernel, dim3(tiles, a.n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const void* cameras, int n_cams, const int* cam_of_frame,
                            const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
                            const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
@@ -465,36 +735,38 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
                            int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr) {
     AnnotateLayout L;
     annotate_layout(n_sel, max_det, H0, W0, max_points, L);
-    unsigned char* ws = (unsigned char*)scratch;
-    AnnArgs a;
-    memset(&a, 0, sizeof a);
-    a.frames = frames; a.out = out; a.status_out = status;
-    a.select = select; a.B = B; a.n_sel = n_sel; a.H0 = H0; a.W0 = W0; a.WW = L.WW;
+    AnnArgs a = annotate_args(L, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, nm, capacity, H, W, frame_i32,
+                              stitch_f64, stitch_i32, select, n_sel, max_points, C_OUTLINE, out, status, scratch);
     a.table = (const CameraRow*)cameras; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams;
-    a.masks = masks; a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
-    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H = native ? H0 : H; a.W = native ? W0 : W;
     if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; }
-    a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
-    a.max_points = max_points;
-    a.recs = (Rec*)(ws + L.off_recs); a.meta = (int*)(ws + L.off_meta); a.env_pts = (int2*)(ws + L.off_env);
-    a.cont = (int2*)(ws + L.off_cont); a.uni = (u64*)(ws + L.off_union);
-    a.areas = ws + L.off_areas; a.area_bytes = L.area_bytes; a.off_runs = L.off_runs; a.off_rows = L.off_rows;
     const size_t env_lds = (size_t)W0 * sizeof(int);
     if (native) hipLaunchKernelGGL(annotate_prep_kernel<true>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
     else hipLaunchKernelGGL(annotate_prep_kernel<false>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (fr ? fr->any_lds : L.in_lds) {
-        e = launch_lds<annotate_outline_kernel<true>>(dim3(n_sel), dim3(kThreads), (size_t)poly::kLdsBytes, st, a);
-        if (e != hipSuccess) return e;
+    return launch_outline_raster(a, L, fr, st);
+}
+
+hipError_t launch_annotate_checker(const vti_checker_params& p, const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
+                                   int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det,
+                                   int nm, int capacity, int H, int W, const int* frame_i32, const double* stitch_f64,
+                                   const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
+                                   void* scratch, hipStream_t st) {
+    AnnotateLayout L;
+    annotate_layout(n_sel, max_det, H0, W0, max_points, L);
+    const AnnArgs a = annotate_args(L, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, nm, capacity, H, W,
+                                    frame_i32, stitch_f64, stitch_i32, select, n_sel, max_points, C_ENVELOPE, out, status, scratch);
+    CameraRow c;
+    checker_pack(p, &c);
+    if (native) {
+        hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, dim3(n_sel), dim3(kThreads), (size_t)W0 * sizeof(int), st, a, c);
+    } else {            // the envelope table and the bits of the source columns and rows the resize reads
+        const size_t lds = ((size_t)W0 + (size_t)((W + 31) / 32) + (size_t)((H + 31) / 32)) * sizeof(int);
+        hipLaunchKernelGGL(annotate_checker_prep_kernel<false>, dim3(n_sel), dim3(kThreads), lds, st, a, c);
     }
-    if (fr ? fr->any_global : !L.in_lds) {
-        e = launch_lds<annotate_outline_kernel<false>>(dim3(n_sel), dim3(kThreads), 0, st, a);
-        if (e != hipSuccess) return e;
-    }
-    const int tiles = (int)(((fr ? fr->max_px : (long long)H0 * W0) + kTile - 1) / kTile);
-    hipLaunchKernelGGL(annotate_raster_kernel, dim3(tiles, n_sel), dim3(kThreads), (size_t)kTile * sizeof(unsigned), st, a);
-    return hipGetLastError();
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_outline_raster(a, L, nullptr, st);
 }
 
 }  // namespace vti

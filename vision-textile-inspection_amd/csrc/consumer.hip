@@ -291,29 +291,7 @@ hipError_t launch_envelope_bits(const uint8_t* bits, const int* offsets, const f
 //   s = -d / (n . ray); X_cam = s ray; X_world = R^T (X_cam - t); no point when |n . ray| < 1e-9.
 // (GeomParams: with CameraRow in measure_dev.h.)
 
-// One point; false where the reference returns None.  Shared by pixels_to_world_kernel and measure_frames_kernel.
-__device__ __forceinline__ bool pixel_to_world(const GeomParams& g, double u, double v, double o[3]) {
-    const double ifx = 1.0 / g.fx, ify = 1.0 / g.fy;
-    double x = (u - g.cx) * ifx, y = (v - g.cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; ++j) {
-        const double r2 = x * x + y * y;
-        const double icdist = 1.0 / (1.0 + ((g.k3 * r2 + g.k2) * r2 + g.k1) * r2);
-        if (icdist < 0) { x = (u - g.cx) * ifx; y = (v - g.cy) * ify; break; }
-        const double dX = 2.0 * g.p1 * x * y + g.p2 * (r2 + 2.0 * x * x);
-        const double dY = g.p1 * (r2 + 2.0 * y * y) + 2.0 * g.p2 * x * y;
-        x = (x0 - dX) * icdist;
-        y = (y0 - dY) * icdist;
-    }
-    const double denom = (g.n[0] * x + g.n[1] * y) + g.n[2];            // n . (x, y, 1)
-    const bool ok = fabs(denom) >= 1e-9;
-    const double s = -g.d / denom;
-    const double c0 = s * x - g.t[0], c1 = s * y - g.t[1], c2 = s - g.t[2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)                                          // R^T row k = column k of R
-        o[k] = ok ? (g.R[k] * c0 + g.R[3 + k] * c1) + g.R[6 + k] * c2 : 0.0;
-    return ok;
-}
+// (pixel_to_world itself: measure_dev.h, shared with vti_annotate_checker's prep kernel.)
 
 __global__ __launch_bounds__(256) void pixels_to_world_kernel(const double* __restrict__ uv, int n, GeomParams g,
                                                                double* __restrict__ xyz, int* __restrict__ valid) {

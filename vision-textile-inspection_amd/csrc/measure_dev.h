@@ -1,5 +1,6 @@
 // What vti_measure (consumer.hip) and vti_annotate (annotate.hip) share on the device: the nearest-resize index of measurement.py:79,
-// the camera-table row (private to the library build that packed it) and the ROI test of measurement.py:220-260.
+// the camera-table row (private to the library build that packed it), the ROI test of measurement.py:220-260 and the pixel -> world
+// point of measurement.py:44-65.
 #pragma once
 #include "vti_internal.h"
 
@@ -33,6 +34,31 @@ __device__ __forceinline__ bool roi_clamp(int enabled, const int* r, int H0, int
 __device__ __forceinline__ bool roi_keeps(const float* bx, int4 roi) {
     const long long x1 = (int)bx[0], y1 = (int)bx[1], x2 = (int)bx[2], y2 = (int)bx[3];    // python int(): truncation
     return 2LL * roi.x <= x1 + x2 && x1 + x2 <= 2LL * roi.z && 2LL * roi.y <= y1 + y2 && y1 + y2 <= 2LL * roi.w;
+}
+
+// One point; false where the reference returns None.  consumer.hip's section N3a has the
+// formulas.  Shared by pixels_to_world_kernel, measure_frames_kernel, checker_frames_kernel and annotate_checker_prep_kernel.
+__device__ __forceinline__ bool pixel_to_world(const GeomParams& g, double u, double v, double o[3]) {
+    const double ifx = 1.0 / g.fx, ify = 1.0 / g.fy;
+    double x = (u - g.cx) * ifx, y = (v - g.cy) * ify;
+    const double x0 = x, y0 = y;
+    for (int j = 0; j < 5; ++j) {
+        const double r2 = x * x + y * y;
+        const double icdist = 1.0 / (1.0 + ((g.k3 * r2 + g.k2) * r2 + g.k1) * r2);
+        if (icdist < 0) { x = (u - g.cx) * ifx; y = (v - g.cy) * ify; break; }
+        const double dX = 2.0 * g.p1 * x * y + g.p2 * (r2 + 2.0 * x * x);
+        const double dY = g.p1 * (r2 + 2.0 * y * y) + 2.0 * g.p2 * x * y;
+        x = (x0 - dX) * icdist;
+        y = (y0 - dY) * icdist;
+    }
+    const double denom = (g.n[0] * x + g.n[1] * y) + g.n[2];            // n . (x, y, 1)
+    const bool ok = fabs(denom) >= 1e-9;
+    const double s = -g.d / denom;
+    const double c0 = s * x - g.t[0], c1 = s * y - g.t[1], c2 = s - g.t[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)                                          // R^T row k = column k of R
+        o[k] = ok ? (g.R[k] * c0 + g.R[3 + k] * c1) + g.R[6 + k] * c2 : 0.0;
+    return ok;
 }
 
 }  // namespace vti

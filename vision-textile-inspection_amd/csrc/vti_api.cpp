@@ -1227,6 +1227,47 @@ int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, i
     return VTI_OK;
 }
 
+// ---- vti_annotate_checker: the stitch-distance checker's picture -------------------------------------------------------------
+int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const vti_checker_params* p,
+                             const uint8_t* masks, int32_t native, const float* dets, const float* xyxy, const int32_t* counts,
+                             const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                             const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
+                             int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
+                             void* stream) {
+    // every check comes before the first HIP call: vti_annotate's, and vti_measure_checker's of the params
+    if (!c || !p) return fail(c, VTI_ERR_ARG, "vti_annotate_checker: null ctx or params");
+    char msg[200];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "vti_annotate_checker: %s", what); return fail(c, VTI_ERR_ARG, msg); };
+    if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
+        return bad("bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; 1 <= H0, W0 <= 8192; "
+                   "native 0 or 1)");
+    if (!frames || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select || !dev_select ||
+        !out || !status || (capacity && !masks))
+        return bad("null pointer");
+    if (const char* e = checker_params_error(p)) return bad(e);
+    for (int32_t k = 0; k < n_sel; ++k)
+        if (host_select[k] < 0 || host_select[k] >= B) {
+            snprintf(msg, sizeof msg, "vti_annotate_checker: host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    if ((uintptr_t)dev_select & 3) return bad("the selection must be 4-byte aligned");
+    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
+        return bad(native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
+    if (!native && ((c->plan.desc.W & 31) || (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024))
+        return bad("letterbox size unsuitable for the resize tables");
+    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
+        return bad("misaligned measurement rows or status");
+    if (!scratch || ((uintptr_t)scratch & 255)) return bad("scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points))
+        return bad("scratch smaller than vti_annotate_scratch_bytes()");
+    if (int32_t drc = check_device(c, "vti_annotate_checker")) return drc;
+    const vti_desc& d = c->plan.desc;
+    VTI_HIP(c, launch_annotate_checker(*p, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H,
+                                       d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status, scratch,
+                                       (hipStream_t)stream), "annotate_checker kernels");
+    return VTI_OK;
+}
+
 // ---- vti_overlay: the model-check viewer's picture ---------------------------------------------------------------------------
 int64_t vti_overlay_scratch_bytes(const vti_ctx* c, int32_t n_sel, int32_t max_det, int32_t H0, int32_t W0, int32_t max_points) {
     if (!c || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points)) return 0;

@@ -338,6 +338,8 @@ hipError_t launch_measure_checker(const vti_checker_params& p, const uint8_t* ma
                                   const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0,
                                   int W0, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32,
                                   hipStream_t st);
+// one validated vti_checker_params -> the CameraRow (measure_dev.h) the checker's kernels take by value (host)
+void checker_pack(const vti_checker_params& p, void* row);
 
 // polygons.hip: vti_mask_polygons (Results.masks.xy).  The grid is VTI_POLY_WORKGROUPS persistent workgroups, each with its own
 // labelling area of the scratch: parent i32 [R_max] | runs u32 [R_max] | row_start i32 [H+1] | image u64 [H, WW] (only when the
@@ -373,6 +375,13 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
                            const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
                            const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
                            int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
+// vti_annotate_checker (the stitch-distance checker's picture): the same scratch and the same outline and raster kernels behind a
+// prep kernel of its own; the rows are vti_measure_checker's, the settings travel by value
+hipError_t launch_annotate_checker(const vti_checker_params& p, const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
+                                   int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det,
+                                   int nm, int capacity, int H, int W, const int* frame_i32, const double* stitch_f64,
+                                   const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
+                                   void* scratch, hipStream_t st);
 
 // overlay.hip: vti_overlay (the model-check viewer's picture).  The scratch holds: 16 ints of counters per selected frame | the contour
 // vertices int4 [n_sel, max_points] | the owner planes (8 words per 32-bit mask word, for the larger of a native and a letterbox mask

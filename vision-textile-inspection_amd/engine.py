@@ -720,6 +720,55 @@ class Engine:
             n_sel, int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         return r
 
+    # ---- the stitch-distance checker's picture (Utils/check_stitch_distance.py:293-545): vti_annotate_checker ------------------
+    def annotate_checker(self, frames, out, meas, params, select, native=False, result=None, max_points=16384):
+        """The frames `select` of the batch with the stitch-distance checker's picture drawn on them: vti_annotate_checker, byte for
+        byte annotate.rasterise(frame, annotate.checker_display_list(...)).  frames, out, select, native, result, max_points and the
+        returned dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]) of device tensors are annotate()'s uniform form (the frames feed
+        encode_jpeg as they are); meas: measure_checker(..., stitch_rows=True)'s dict on the same set; params: the CheckerParams (or
+        VtiCheckerParams) of that call.  One frame size, one camera.  Text is the host's: measure.checker_text_items / put_text."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("annotate_checker: frames must be a uint8 [B,H0,W0,3] tensor")
+        B, H0, W0, _ = frames.shape
+        dets, masks = out["dets"], out["masks"]
+        dev = dets.device
+        if out["counts"].shape[0] != B:
+            raise ValueError(f"annotate_checker: {B} frames but an output set of {out['counts'].shape[0]}")
+        max_det, capacity = dets.shape[1], masks.shape[0]
+        sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
+        if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
+            raise ValueError("annotate_checker: select must be a non-empty sequence of frame indices")
+        if sel.min() < 0 or sel.max() >= B:
+            raise ValueError(f"annotate_checker: frame index outside [0, {B})")
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        n_sel = int(sel.size)
+        for key in ("frame_i32", "stitch_f64", "stitch_i32"):
+            if meas.get(key) is None:
+                raise ValueError(f"annotate_checker: meas needs {key} (measure_checker(..., stitch_rows=True))")
+        # everything above is about shapes and values; what needs a device comes from here on
+        if not frames.is_cuda or not frames.is_contiguous():
+            raise ValueError("annotate_checker: frames must be the contiguous device batch predict consumed")
+        cp = params.to_c() if hasattr(params, "to_c") else params
+        r = dict(result or {})
+        if "status" not in r:
+            r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
+        if "frames" not in r:
+            r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
+        need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
+        if need <= 0:
+            raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+        ws = getattr(self, "_annotate_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            self._annotate_ws = None
+            ws = self._annotate_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        dev_sel = torch.from_numpy(sel).to(dev)
+        check(self._ctx, lib().vti_annotate_checker(
+            self._ctx, _ptr(frames), B, H0, W0, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets),
+            _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity, _ptr(meas["frame_i32"]),
+            _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(max_points),
+            _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        return r
+
     # ---- the model-check viewer's picture (Utils/check_model.py:155-256): vti_overlay ------------------------------------------
     def overlay_scratch_bytes(self, n_sel, max_det, H0, W0, max_points):
         return int(lib().vti_overlay_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))

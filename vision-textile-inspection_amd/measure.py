@@ -7,6 +7,7 @@
     records = mc.process_frames(frames, cameras) # a batch that mixes cameras: cameras[b] = the camera of frame b
     ck = StitchDistanceChecker(YOLO(path), CheckerParams.from_files(...))                  Utils/check_stitch_distance.py:176-222
     records = ck.process_frames(frames)          # the bench tool's numbers and info text per frame (vti_measure_checker)
+    annotated, records = ck.process_frames(frames, annotate="all")     # and its picture (vti_annotate_checker)
 
 The per-frame work (ROI filter, moments, fabric envelope, widths, row selection, proximity filter, distances, averages) runs in
 libvti's vti_measure on the predict output set that is already on the device; the host reads back B small records once and keeps
@@ -262,15 +263,16 @@ class _DeviceStage:
         f64, i32 = host[:B * 16].view(np.float64).reshape(B, 2), host[B * 16:].view(np.int32).reshape(B, 6)
         if sel is None:
             return (f64, i32, self._slot_rows(o, res, np.arange(B))) if rows else (f64, i32)
-        return f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks),
-                                         int(jpeg_quality) if encode else None, table), H0 if table is None else [h for h, _ in shapes]
+        got = (f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks),
+                                         int(jpeg_quality) if encode else None, table), H0 if table is None else [h for h, _ in shapes])
+        return got + (self._slot_rows(o, res, np.arange(B)),) if rows else got      # rows next to annotate: a fifth item, every frame's
 
     def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None, table=None):
         """vti_annotate on the batch predict consumed; the selected pictures in one device -> host copy, and of the per-slot rows only
         those of the selected frames.  jpeg_quality: the pictures go through vti_encode_jpeg first and the copy is of the files'
         bytes (one read of the offsets, one of out[:offsets[n]]).  table: the FrameTable of a batch whose frames differ in size --
         vti_annotate_frames and vti_encode_jpeg_frames; the one copy is then of the flat buffer, sliced into [H0, W0, 3] arrays."""
-        ann = eng.annotate(self.model._last_frames, o, res, params, sel, cameras=cameras, native=native, table=table)
+        ann = self._draw(eng, self.model._last_frames, o, res, params, sel, cameras, native, table)
         self.model._last_frames = None            # the launches are enqueued: the batch need not outlive the call
         if jpeg_quality is None and table is not None:
             flat = ann["buf"].cpu().numpy()
@@ -287,6 +289,10 @@ class _DeviceStage:
             pics = [data[off[k]:off[k + 1]] for k in range(len(sel))]
         rows = self._slot_rows(o, res, np.unique(sel))
         return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
+
+    def _draw(self, eng, frames, o, res, params, sel, cameras, native, table):
+        """The stage's one drawing call on the batch predict consumed (Engine.annotate's contract)."""
+        return eng.annotate(frames, o, res, params, sel, cameras=cameras, native=native, table=table)
 
     @staticmethod
     def _slot_rows(o, res, uniq):
@@ -422,7 +428,8 @@ class StitchDistanceChecker(_DeviceStage):
     """Utils/check_stitch_distance.py's StitchMeasurementApp.process_frame without the camera and the window: model = a vti_amd YOLO,
     params = CheckerParams.  One predict, one vti_measure_checker and one device -> host read per batch; the two smoothing deques
     (:215-216, :519-530) live here, so consecutive calls continue one stream of frames.  Frames of one size, one camera; the
-    checker's picture is not drawn (checker_text_items gives its text)."""
+    checker's picture (:293-545) is drawn on request, for a selection of the batch (`annotate=`): vti_annotate_checker paints it
+    on the device batch predict consumed, annotate.checker_display_list states what it holds, checker_text_items gives its text."""
 
     _mixed_sizes = False
 
@@ -434,6 +441,9 @@ class StitchDistanceChecker(_DeviceStage):
 
     def _measure(self, eng, o, params, H0, W0, **kw):
         return eng.measure_checker(o, params, H0, W0, **kw)
+
+    def _draw(self, eng, frames, o, res, params, sel, cameras, native, table):
+        return eng.annotate_checker(frames, o, res, params, sel, native=native)
 
     def _record(self, f64, i32):
         """:345-347, :404-406 (the two early returns: nothing appended) and :515-540 (averages -> deques -> medians -> text)."""
@@ -454,24 +464,42 @@ class StitchDistanceChecker(_DeviceStage):
                 'info_text': checker_info_text(smooth_dist, smooth_width, n_found, self.params.min_stitches),
                 'timestamp': datetime.now()}
 
-    def process_frames(self, frames, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False):
+    def process_frames(self, frames, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False, annotate=None,
+                       encode=None, jpeg_quality=95):
         """frames: as StitchMeasurer.process_frames takes them (a BGR uint8 batch, a list of JPEG files, RawFrames), all of one size.
         The defaults are the checker's predict call (:286: conf 0.20, iou 0.45, max_det 200, imgsz not passed: 640).  Returns one
         record per frame, in frame order, smoothed frame by frame: edge_distance_mm, stitch_width_mm (None: no value yet),
         stitch_count (the `n` of the info text: the number of widths), info_text (the string process_frame returns), timestamp, and
         `error` on the two failures.  rows=True -> (records, rows): rows[b] is what checker_text_items takes for frame b (one more
-        device -> host read, of the per-slot rows)."""
-        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, rows=bool(rows))
+        device -> host read, of the per-slot rows).
+        annotate: "all" or a sequence of frame indices -> (annotated, records): annotated = [(frame index, BGR ndarray H0 x W0 x 3 with
+        the checker's picture, text_items)] for the selection, as StitchMeasurer.process_frames returns them (drawn on the device by
+        vti_annotate_checker, one copy to the host; the text is checker_text_items', for annotate.put_text), records exactly as
+        without it.  encode="jpeg" (with annotate): the picture is the bytes of the JPEG file cv2.imwrite saves of it at
+        jpeg_quality, encoded on the device; any other encode, or encode without annotate, is a ValueError before anything is
+        predicted.  With rows=True as well: (annotated, records, rows)."""
+        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
+                                  rows=bool(rows))
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
-        if not rows:
-            return records
-        return records, [dict(got[2][b], status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
-                         for b in range(len(f64))]
+        full = lambda r, b: dict(r, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
+        if annotate is None:
+            return (records, [full(got[2][b], b) for b in range(len(f64))]) if rows else records
+        annotated = [(b, pic, checker_text_items(records[b], full(r, b), got[3])) for b, pic, r in got[2]]
+        return (annotated, records, [full(got[4][b], b) for b in range(len(f64))]) if rows else (annotated, records)
 
-    def process_frame(self, frame, **kw):
-        """One frame: its record."""
-        return self.process_frames(np.asarray(frame)[None], **kw)[0]
+    def process_frame(self, frame, annotate=False, **kw):
+        """One frame: its record; annotate=True: the checker's tuple in this package's form, (annotated BGR ndarray, record), the text
+        drawn too where OpenCV is installed (annotate.put_text; without it the picture carries everything but the text)."""
+        if not annotate:
+            return self.process_frames(np.asarray(frame)[None], **kw)[0]
+        annotated, records = self.process_frames(np.asarray(frame)[None], annotate=[0], **kw)[:2]
+        _, pic, items = annotated[0]
+        try:
+            _annotate.put_text(pic, items)
+        except ImportError:
+            pass
+        return pic, records[0]
 
 
 def checker_info_text(smooth_dist, smooth_width, n_found, min_stitches):
