@@ -1,7 +1,9 @@
 // Stand-alone program (its own main; never loaded into Python): calls every argument check of vti_annotate_checker with fake device
-// pointers that are never dereferenced and expects VTI_ERR_ARG with a message that names the function and the argument.  Every call
-// is refused, so none reaches a HIP call and the program may run anywhere.  Built with -fsanitize=address,undefined and linked
-// against libvti.so by tests/test_annotate_checker_abi.py; prints "ok <number of refusals>" and returns 0 when everything held.
+// pointers that are never dereferenced and expects VTI_ERR_ARG with a message that names the function and the argument; then a few
+// refusals of vti_measure_checker and vti_overlay_frames, which make the same checks through the same helpers (the selection walk of
+// vti_overlay_frames reads two host tables).  Every call is refused, so none reaches a HIP call and the program may run anywhere.
+// Built with -fsanitize=address,undefined and linked against libvti.so by tests/test_annotate_checker_abi.py; prints
+// "ok <number of refusals>" and returns 0 when everything held.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -29,13 +31,16 @@ static int32_t run(const Call& c) {
 
 static int failures = 0, refusals = 0;
 
-static void refused(const Call& c, const char* what, const char* needle) {
-    const int32_t rc = run(c);
-    const char* msg = c.ctx ? vti_last_error(c.ctx) : "";
-    const bool ok = rc == VTI_ERR_ARG && (!c.ctx || (strncmp(msg, "vti_annotate_checker:", 21) == 0 && (!needle || strstr(msg, needle))));
+// rc is VTI_ERR_ARG and the message of ctx (if any) begins with "<fn>:" and holds needle (if any)
+static void expect(int32_t rc, vti_ctx* ctx, const char* fn, const char* what, const char* needle) {
+    const char* msg = ctx ? vti_last_error(ctx) : "";
+    const size_t n = strlen(fn);
+    const bool ok = rc == VTI_ERR_ARG && (!ctx || (strncmp(msg, fn, n) == 0 && msg[n] == ':' && (!needle || strstr(msg, needle))));
     if (!ok) { ++failures; fprintf(stderr, "FAIL %s: rc %d, message \"%s\"\n", what, rc, msg); }
     ++refusals;
 }
+
+static void refused(const Call& c, const char* what, const char* needle) { expect(run(c), c.ctx, "vti_annotate_checker", what, needle); }
 
 int main() {
     vti_desc d;
@@ -108,6 +113,47 @@ int main() {
     BAD_PARAMS(q.drop_empty = 2, "bad setting");
     BAD_PARAMS(q.frame_buffer = 0, "bad setting");
     BAD_PARAMS(q.max_px_distance = __builtin_nan(""), "NaN");
+
+    // vti_measure_checker: the measurement's checks of the same settings, masks and scratch
+    const int64_t mneed = vti_measure_scratch_bytes(ctx, B, 800, W0);
+    auto measure = [&](const vti_checker_params* pp, const void* masks, int32_t md, void* scratch, size_t nbytes) {
+        return vti_measure_checker(ctx, pp, (const uint8_t*)masks, 0, (const float*)one, (const float*)one, (const int32_t*)one,
+                                   (const int32_t*)one, B, md, 800, H0, W0, scratch, nbytes, (double*)one, (int32_t*)one, (double*)one,
+                                   (int32_t*)one, nullptr);
+    };
+    q = p; q.frame_buffer = 0;
+    expect(measure(&q, one, max_det, ws, (size_t)mneed), ctx, "vti_measure_checker", "frame_buffer = 0", "bad setting");
+    expect(measure(&p, (void*)(uintptr_t)(4096 + 8), max_det, ws, (size_t)mneed), ctx, "vti_measure_checker", "masks + 8", "16-byte");
+    expect(measure(&p, one, VTI_MEASURE_MAX_DET + 1, ws, (size_t)mneed), ctx, "vti_measure_checker", "max_det", "VTI_MEASURE_MAX_DET");
+    expect(measure(&p, one, max_det, ws, (size_t)mneed - 1), ctx, "vti_measure_checker", "short scratch", "scratch smaller");
+
+    // vti_overlay_frames: the walk over the selection reads host_select and a row of each host table per entry
+    const int32_t fh[4] = {960, 481, 720, 1080}, fw[4] = {1280, 333, 960, 1920};
+    std::vector<int32_t> oh, ow;
+    for (int32_t b : sel) { oh.push_back(fh[b]); ow.push_back(fw[b]); }
+    auto pack = [&](const int32_t* h, const int32_t* w, int32_t n, std::vector<uint8_t>& table) {
+        std::vector<int64_t> at;
+        int64_t total = 0;
+        for (int32_t k = 0; k < n; ++k) { at.push_back(total); total = (total + 3LL * h[k] * w[k] + 15) & ~15LL; }
+        table.resize((size_t)vti_frame_table_bytes(n));     // exactly the table's bytes on the heap
+        return vti_pack_frames(ctx, d.H, d.W, h, w, at.data(), n, total, table.data(), table.size());
+    };
+    std::vector<uint8_t> t_in, t_out;
+    if (pack(fh, fw, 4, t_in) != VTI_OK || pack(oh.data(), ow.data(), n_sel, t_out) != VTI_OK) { fprintf(stderr, "vti_pack_frames failed\n"); return 2; }
+    const int64_t oneed = vti_overlay_frames_scratch_bytes(ctx, t_out.data(), max_det, max_points);
+    if (oneed <= 0) { fprintf(stderr, "vti_overlay_frames_scratch_bytes gave %lld\n", (long long)oneed); return 2; }
+    const uint8_t palette[18] = {0};
+    auto overlay = [&](const int32_t* hsel, const void* masks, size_t nbytes) {
+        return vti_overlay_frames(ctx, (const uint8_t*)one, t_in.data(), one, B, (const uint8_t*)masks, 0, nullptr, 0, (const float*)one,
+                                  (const float*)one, (const int32_t*)one, (const int32_t*)one, max_det, 800, nullptr, palette, 6, 0.3f, 0.7f,
+                                  hsel, (const int32_t*)one, n_sel, VTI_OVERLAY_BOTH, nullptr, max_points, t_out.data(), one, (uint8_t*)one,
+                                  (int32_t*)one, ws, nbytes, nullptr);
+    };
+    std::vector<int32_t> past = {3, 0, B}, other = {3, 1, 3};
+    expect(overlay(past.data(), one, (size_t)oneed), ctx, "vti_overlay_frames", "host_select[2] = B", "host_select[2] = 4");
+    expect(overlay(other.data(), one, (size_t)oneed), ctx, "vti_overlay_frames", "frame 1 for row 1", "row 1 of the out table");
+    expect(overlay(sel.data(), (void*)(uintptr_t)(4096 + 8), (size_t)oneed), ctx, "vti_overlay_frames", "masks + 8", "16-byte");
+    expect(overlay(sel.data(), one, (size_t)oneed - 1), ctx, "vti_overlay_frames", "short scratch", "scratch smaller");
 
     vti_destroy(ctx);
     if (failures) return 1;

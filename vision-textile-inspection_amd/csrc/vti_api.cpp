@@ -46,6 +46,11 @@ static int32_t fail(vti_ctx* c, int32_t code, const std::string& msg) {
 static int32_t hip_fail(vti_ctx* c, hipError_t e, const char* what) {
     return fail(c, VTI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+// A refused argument: the message is "<fn>: <what>".
+static int32_t refuse(vti_ctx* c, const char* fn, const char* what, int32_t code = VTI_ERR_ARG) {
+    return fail(c, code, std::string(fn) + ": " + what);
+}
+#define VTI_TRY(call) do { if (int32_t rc_ = (call)) return rc_; } while (0)     // a check that refused: its status is the entry point's
 #define VTI_HIP(c, call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail((c), e_, (what)); } while (0)
 
 #ifdef VTI_STAMPS
@@ -103,6 +108,18 @@ static size_t conv_workgroups(const ConvParams& p, const ConvCfg& g, int B) {
     return (p.pk ? (size_t)p.pk_wgs : (size_t)B * p.tiles_y * p.tiles_x) * ((g.ntiles_n + NTB - 1) / NTB);
 }
 #endif
+
+// The settings that vti_measure_params and vti_checker_params have in common: nullptr when they are valid.
+template <typename P>
+static const char* settings_error(const P& p) {
+    if (p.stitch_id < 0 || p.fabric_id < 0 || p.stitch_id == p.fabric_id) return "stitch_id and fabric_id must be >= 0 and different";
+    if (p.envelope_neighborhood < 0 || p.envelope_neighborhood > 64) return "envelope_neighborhood must be 0..64";
+    if (p.min_stitches < 1 || p.kmeans_iters < 0 || (p.skip_cluster != 0 && p.skip_cluster != 1) ||
+        (p.drop_empty != 0 && p.drop_empty != 1) || p.frame_buffer < 1)
+        return "bad setting (min_stitches, frame_buffer >= 1; kmeans_iters >= 0; flags 0 or 1)";
+    if (!(p.max_px_distance == p.max_px_distance)) return "NaN threshold";
+    return nullptr;
+}
 
 extern "C" {
 
@@ -270,6 +287,14 @@ static const char* frame_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int
     return nullptr;
 }
 
+// The header of a host frame table and row k of it.
+static FrameTableHeader table_header(const void* host_table) { FrameTableHeader h; memcpy(&h, host_table, sizeof h); return h; }
+static FrameRow table_row(const void* host_table, int32_t k) {
+    FrameRow r;
+    memcpy(&r, (const char*)host_table + sizeof(FrameTableHeader) + (size_t)k * sizeof r, sizeof r);
+    return r;
+}
+
 int32_t vti_pack_frames(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset, int32_t B,
                         int64_t total_bytes, void* host_table, size_t nbytes) {
     if (!H0 || !W0 || !byte_offset || !host_table || B < 1)
@@ -299,16 +324,14 @@ int32_t vti_pack_frames(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, con
 
 int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[8], double out_f64[5]) {
     if (!host_table || !out_i32) return VTI_ERR_ARG;
-    FrameTableHeader h;
-    memcpy(&h, host_table, sizeof h);
+    const FrameTableHeader h = table_header(host_table);
     if (h.magic != kFrameTableMagic || h.B < 1 || b < -1 || b >= h.B) return VTI_ERR_ARG;
     if (b < 0) {
         const int32_t v[8] = {h.B, h.H, h.W, h.max_H0, h.max_W0, 0, (int32_t)(h.total_bytes & 0xffffffff), (int32_t)(h.total_bytes >> 32)};
         memcpy(out_i32, v, sizeof v);
         return VTI_OK;
     }
-    FrameRow r;
-    memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+    const FrameRow r = table_row(host_table, b);
     const int32_t v[8] = {r.H0, r.W0, r.new_h, r.new_w, r.top, r.left, (int32_t)(r.offset & 0xffffffff), (int32_t)(r.offset >> 32)};
     memcpy(out_i32, v, sizeof v);
     if (out_f64) { out_f64[0] = r.scale_x; out_f64[1] = r.scale_y; out_f64[2] = r.gain; out_f64[3] = r.padx; out_f64[4] = r.pady; }
@@ -320,13 +343,12 @@ int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[
 // nothing and records nothing: frames_check and the host-only size queries share it.  `h` receives the header.
 static const char* frame_table_problem(const vti_ctx* c, const void* host_table, int32_t B, FrameTableHeader& h, int32_t& frame) {
     frame = -1;
-    memcpy(&h, host_table, sizeof h);
+    h = table_header(host_table);
     if (h.magic != kFrameTableMagic) return "host_table is not a table of vti_pack_frames";
     if (h.B < 1 || (B >= 0 && h.B != B)) return "the frame table was packed for another B";
     if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return "the frame table was packed for another canvas (H x W)";
     for (int32_t b = 0; b < h.B; ++b) {
-        FrameRow r;
-        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+        const FrameRow r = table_row(host_table, b);
         const char* e = frame_error(h.H, h.W, r.H0, r.W0, r.offset, h.total_bytes);
         if (!e && (r.H0 > h.max_H0 || r.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
         if (e) { frame = b; return e; }
@@ -344,7 +366,7 @@ static int32_t frames_check(const char* fn, vti_ctx* c, const void* host_table, 
     if ((uintptr_t)dev_table & 15) return bad("the device frame table must be 16-byte aligned");
     int32_t frame;
     if (B < 1) {                            // no table is packed for B < 1 (frame_table_problem reads B < 0 as "any B")
-        memcpy(&h, host_table, sizeof h);
+        h = table_header(host_table);
         return bad(h.magic != kFrameTableMagic ? "host_table is not a table of vti_pack_frames" : "the frame table was packed for another B");
     }
     if (const char* e = frame_table_problem(c, host_table, B, h, frame)) {
@@ -980,15 +1002,44 @@ int64_t vti_measure_scratch_bytes(const vti_ctx* c, int32_t B, int32_t capacity,
     return (int64_t)total;
 }
 
+// ---- argument checks that several entry points make: each returns 0, or refuse()'s status with the message "<fn>: <what>" -----
 // The checks of one vti_measure_params (vti_measure's struct, every entry of vti_measure_pack_cameras): nullptr when it is valid.
 static const char* measure_params_error(const vti_measure_params* p) {
-    if (p->stitch_id < 0 || p->fabric_id < 0 || p->stitch_id == p->fabric_id) return "stitch_id and fabric_id must be >= 0 and different";
-    if (p->envelope_neighborhood < 0 || p->envelope_neighborhood > 64) return "envelope_neighborhood must be 0..64";
-    if (p->min_stitches < 1 || p->kmeans_iters < 0 || (p->skip_cluster != 0 && p->skip_cluster != 1) ||
-        (p->drop_empty != 0 && p->drop_empty != 1) || p->frame_buffer < 1)
-        return "bad setting (min_stitches, frame_buffer >= 1; kmeans_iters >= 0; flags 0 or 1)";
-    if (!(p->max_px_distance == p->max_px_distance) || !(p->two_row_threshold_px == p->two_row_threshold_px)) return "NaN threshold";
-    return nullptr;
+    if (const char* e = settings_error(*p)) return e;
+    return p->two_row_threshold_px == p->two_row_threshold_px ? nullptr : "NaN threshold";
+}
+
+// Mask rows are read with 16-byte loads, native (frame-size) rows with 8-byte loads.
+static int32_t mask_align_check(const char* fn, vti_ctx* c, const uint8_t* masks, int32_t native) {
+    if ((uintptr_t)masks & (native ? 7 : 15))
+        return refuse(c, fn, native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
+    return VTI_OK;
+}
+
+// The caller's scratch: a 256-byte aligned pointer (`need_ptr` = 0: not looked at) to at least `need` bytes, the answer of `query`.
+static int32_t scratch_check(const char* fn, vti_ctx* c, const void* scratch, size_t scratch_bytes, int64_t need, const char* query,
+                             bool need_ptr = true) {
+    if (need_ptr && (!scratch || ((uintptr_t)scratch & 255))) return refuse(c, fn, "scratch must be a 256-byte aligned device pointer");
+    if ((int64_t)scratch_bytes < need) return refuse(c, fn, (std::string("scratch smaller than ") + query).c_str());
+    return VTI_OK;
+}
+
+// What vti_measure's family and vti_measure_checker check of the output set, the result rows and the scratch.  `limit`: the status
+// for a max_det or a letterbox size beyond what the kernels serve (include/vti.h: VTI_ERR_UNSUPPORTED in the measure family,
+// VTI_ERR_ARG in the checker).
+static int32_t measure_args_check(const char* fn, vti_ctx* c, int32_t limit, const uint8_t* masks, int32_t native, const float* dets,
+                                  const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det,
+                                  int32_t capacity, int32_t H0, int32_t W0, const void* scratch, size_t scratch_bytes,
+                                  const double* frame_f64, const int32_t* frame_i32) {
+    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
+        return refuse(c, fn, "bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
+    if (max_det > VTI_MEASURE_MAX_DET) return refuse(c, fn, "max_det above VTI_MEASURE_MAX_DET", limit);
+    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks))) return refuse(c, fn, "null pointer");
+    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
+    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
+        return refuse(c, fn, "letterbox size too large for the resize tables", limit);
+    if ((int64_t)B * W0 > INT32_MAX) return refuse(c, fn, "B * W0 out of range");
+    return scratch_check(fn, c, scratch, scratch_bytes, vti_measure_scratch_bytes(c, B, capacity, W0), "vti_measure_scratch_bytes()", B != 0);
 }
 
 // vti_measure / vti_measure_cameras / vti_measure_frames: exactly one of p and (table, cam_of_frame) is given; with `frames` (the rows
@@ -1000,27 +1051,14 @@ static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params
                             int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
                             int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr, const int64_t* bases = nullptr,
                             int64_t capacity_bytes = 0) {
-    char msg[200];
-    auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
-    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
-        return bad(VTI_ERR_ARG, "bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
-    if (max_det > VTI_MEASURE_MAX_DET) return bad(VTI_ERR_UNSUPPORTED, "max_det above VTI_MEASURE_MAX_DET");
-    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks)))
-        return bad(VTI_ERR_ARG, "null pointer");
-    if (frames && native && !bases) return bad(VTI_ERR_UNSUPPORTED, "native masks need frames of one size (vti_measure_cameras)");
-    if (bases && (capacity_bytes < 0 || ((uintptr_t)bases & 7))) return bad(VTI_ERR_ARG, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
+    if (frames && native == 1 && !bases) return refuse(c, fn, "native masks need frames of one size (vti_measure_cameras)", VTI_ERR_UNSUPPORTED);
+    if (bases && (capacity_bytes < 0 || ((uintptr_t)bases & 7))) return refuse(c, fn, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
     if (p)
-        if (const char* e = measure_params_error(p)) return bad(VTI_ERR_ARG, e);
-    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
-        return bad(VTI_ERR_ARG, native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
-    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
-        return bad(VTI_ERR_UNSUPPORTED, "letterbox size too large for the resize tables");
-    if ((int64_t)B * W0 > INT32_MAX) return bad(VTI_ERR_ARG, "B * W0 out of range");
-    if (B && (!scratch || ((uintptr_t)scratch & 255))) return bad(VTI_ERR_ARG, "scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_measure_scratch_bytes(c, B, capacity, W0))
-        return bad(VTI_ERR_ARG, "scratch smaller than vti_measure_scratch_bytes()");
+        if (const char* e = measure_params_error(p)) return refuse(c, fn, e);
+    VTI_TRY(measure_args_check(fn, c, VTI_ERR_UNSUPPORTED, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0,
+                               scratch, scratch_bytes, frame_f64, frame_i32));
     if (B == 0) return VTI_OK;
-    if (int32_t drc = check_device(c, fn)) return drc;
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_measure(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H,
                               d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream,
@@ -1032,43 +1070,22 @@ int32_t vti_measure(vti_ctx* c, const vti_measure_params* p, const uint8_t* mask
                     const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity,
                     int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32,
                     double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    if (!c || !p) return fail(c, VTI_ERR_ARG, "vti_measure: null ctx or params");
+    if (!c || !p) return refuse(c, "vti_measure", "null ctx or params");
     return measure_impl("vti_measure", c, p, nullptr, 0, nullptr, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0,
                         scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
-}
-
-// The checks of one vti_checker_params: nullptr when it is valid.
-static const char* checker_params_error(const vti_checker_params* p) {
-    if (p->stitch_id < 0 || p->fabric_id < 0 || p->stitch_id == p->fabric_id) return "stitch_id and fabric_id must be >= 0 and different";
-    if (p->envelope_neighborhood < 0 || p->envelope_neighborhood > 64) return "envelope_neighborhood must be 0..64";
-    if (p->min_stitches < 1 || p->kmeans_iters < 0 || (p->skip_cluster != 0 && p->skip_cluster != 1) ||
-        (p->drop_empty != 0 && p->drop_empty != 1) || p->frame_buffer < 1)
-        return "bad setting (min_stitches, frame_buffer >= 1; kmeans_iters >= 0; flags 0 or 1)";
-    if (!(p->max_px_distance == p->max_px_distance)) return "NaN threshold";
-    return nullptr;
 }
 
 int32_t vti_measure_checker(vti_ctx* c, const vti_checker_params* p, const uint8_t* masks, int32_t native, const float* dets,
                             const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det,
                             int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64,
                             int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    if (!c || !p) return fail(c, VTI_ERR_ARG, "vti_measure_checker: null ctx or params");
-    char msg[200];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "vti_measure_checker: %s", what); return fail(c, VTI_ERR_ARG, msg); };
-    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
-        return bad("bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
-    if (max_det > VTI_MEASURE_MAX_DET) return bad("max_det above VTI_MEASURE_MAX_DET");
-    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks))) return bad("null pointer");
-    if (const char* e = checker_params_error(p)) return bad(e);
-    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
-        return bad(native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
-    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
-        return bad("letterbox size too large for the resize tables");
-    if ((int64_t)B * W0 > INT32_MAX) return bad("B * W0 out of range");
-    if (B && (!scratch || ((uintptr_t)scratch & 255))) return bad("scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_measure_scratch_bytes(c, B, capacity, W0)) return bad("scratch smaller than vti_measure_scratch_bytes()");
+    const char* fn = "vti_measure_checker";
+    if (!c || !p) return refuse(c, fn, "null ctx or params");
+    if (const char* e = settings_error(*p)) return refuse(c, fn, e);
+    VTI_TRY(measure_args_check(fn, c, VTI_ERR_ARG, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0, scratch,
+                               scratch_bytes, frame_f64, frame_i32));
     if (B == 0) return VTI_OK;
-    if (int32_t drc = check_device(c, "vti_measure_checker")) return drc;
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_measure_checker(*p, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H, d.W, H0, W0, scratch,
                                       frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure_checker kernels");
@@ -1093,14 +1110,20 @@ int32_t vti_measure_pack_cameras(vti_ctx* c, const vti_measure_params* params, i
     return VTI_OK;
 }
 
+// The camera table and the per-frame camera index of the vti_measure_* table forms.
+static int32_t camera_table_check(const char* fn, vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame) {
+    if (!c || !cameras || !cam_of_frame) return refuse(c, fn, "null ctx, camera table or camera index");
+    if (n_cams < 1) return refuse(c, fn, "n_cams must be >= 1");
+    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
+        return refuse(c, fn, "the camera table must be 16-byte aligned, the index 4-byte aligned");
+    return VTI_OK;
+}
+
 int32_t vti_measure_cameras(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
                             int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B,
                             int32_t max_det, int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes,
                             double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    if (!c || !cameras || !cam_of_frame) return fail(c, VTI_ERR_ARG, "vti_measure_cameras: null ctx, camera table or camera index");
-    if (n_cams < 1) return fail(c, VTI_ERR_ARG, "vti_measure_cameras: n_cams must be >= 1");
-    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
-        return fail(c, VTI_ERR_ARG, "vti_measure_cameras: the camera table must be 16-byte aligned, the index 4-byte aligned");
+    VTI_TRY(camera_table_check("vti_measure_cameras", c, cameras, n_cams, cam_of_frame));
     return measure_impl("vti_measure_cameras", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
                         max_det, capacity, H0, W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
 }
@@ -1110,12 +1133,9 @@ int32_t vti_measure_frames(vti_ctx* c, const void* cameras, int32_t n_cams, cons
                            const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity, void* scratch,
                            size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
                            void* stream) {
-    if (!c || !cameras || !cam_of_frame) return fail(c, VTI_ERR_ARG, "vti_measure_frames: null ctx, camera table or camera index");
-    if (n_cams < 1) return fail(c, VTI_ERR_ARG, "vti_measure_frames: n_cams must be >= 1");
-    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
-        return fail(c, VTI_ERR_ARG, "vti_measure_frames: the camera table must be 16-byte aligned, the index 4-byte aligned");
+    VTI_TRY(camera_table_check("vti_measure_frames", c, cameras, n_cams, cam_of_frame));
     FrameTableHeader h;
-    if (int32_t rc = frames_check("vti_measure_frames", c, host_table, dev_table, B, h)) return rc;
+    VTI_TRY(frames_check("vti_measure_frames", c, host_table, dev_table, B, h));
     return measure_impl("vti_measure_frames", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
                         max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
                         frame_rows(dev_table));
@@ -1126,17 +1146,15 @@ int32_t vti_measure_frames_native(vti_ctx* c, const void* cameras, int32_t n_cam
                                   const int32_t* counts, const int32_t* offsets, const void* host_table, const void* dev_table, int32_t B,
                                   int32_t max_det, int32_t capacity, void* scratch, size_t scratch_bytes, double* frame_f64,
                                   int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    if (!c || !cameras || !cam_of_frame) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: null ctx, camera table or camera index");
-    if (n_cams < 1) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: n_cams must be >= 1");
-    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
-        return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: the camera table must be 16-byte aligned, the index 4-byte aligned");
+    const char* fn = "vti_measure_frames_native";
+    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
     FrameTableHeader h;
-    if (int32_t rc = frames_check("vti_measure_frames_native", c, host_table, dev_table, B, h)) return rc;
-    if (!mask_bases) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: null dev_mask_bases");
-    if (capacity_bytes < 0) return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: capacity_bytes must be >= 0");
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    if (!mask_bases) return refuse(c, fn, "null dev_mask_bases");
+    if (capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
     if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
-        return fail(c, VTI_ERR_ARG, "vti_measure_frames_native: a frame of host_table has no native mask layout (slot below 2 GiB)");
-    return measure_impl("vti_measure_frames_native", c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B,
+        return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
+    return measure_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B,
                         max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
                         frame_rows(dev_table), mask_bases, capacity_bytes);
 }
@@ -1164,11 +1182,9 @@ int32_t vti_mask_polygons(vti_ctx* c, const uint8_t* masks, int32_t n, const int
     if (strategy != VTI_POLY_LARGEST && strategy != VTI_POLY_CONCAT)
         return fail(c, VTI_ERR_ARG, "vti_mask_polygons: strategy must be VTI_POLY_LARGEST or VTI_POLY_CONCAT");
     if (!offsets || (n && !masks) || (max_points && !points)) return fail(c, VTI_ERR_ARG, "vti_mask_polygons: null pointer");
-    if (!scratch || ((uintptr_t)scratch & 255))
-        return fail(c, VTI_ERR_ARG, "vti_mask_polygons: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_mask_polygons_scratch_bytes(c, H, W, row_bytes))
-        return fail(c, VTI_ERR_ARG, "vti_mask_polygons: scratch smaller than vti_mask_polygons_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_mask_polygons")) return drc;
+    VTI_TRY(scratch_check("vti_mask_polygons", c, scratch, scratch_bytes, vti_mask_polygons_scratch_bytes(c, H, W, row_bytes),
+                          "vti_mask_polygons_scratch_bytes()"));
+    VTI_TRY(check_device(c, "vti_mask_polygons"));
     // scale_coords' gain and pad, in double as polygons.py (Python floats); the kernels round each to f32 once
     const double gain = std::min((double)H / (double)H0, (double)W / (double)W0);
     const double padx = ((double)W - (double)W0 * gain) / 2, pady = ((double)H - (double)H0 * gain) / 2;
@@ -1189,6 +1205,27 @@ int64_t vti_annotate_scratch_bytes(const vti_ctx* c, int32_t n_sel, int32_t max_
     return (int64_t)L.total;
 }
 
+// Every host_select[k] is a frame of the batch (select_at: entry k alone).
+static int32_t select_at(const char* fn, vti_ctx* c, const int32_t* host_select, int32_t k, int32_t B) {
+    if (host_select[k] >= 0 && host_select[k] < B) return VTI_OK;
+    char msg[120];
+    snprintf(msg, sizeof msg, "host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
+    return refuse(c, fn, msg);
+}
+static int32_t select_check(const char* fn, vti_ctx* c, const int32_t* host_select, int32_t n_sel, int32_t B) {
+    for (int32_t k = 0; k < n_sel; ++k)
+        VTI_TRY(select_at(fn, c, host_select, k, B));
+    return VTI_OK;
+}
+
+// The measurement rows a picture is drawn from, and the status it reports.
+static int32_t meas_rows_check(const char* fn, vti_ctx* c, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                               const int32_t* status) {
+    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
+        return refuse(c, fn, "misaligned measurement rows or status");
+    return VTI_OK;
+}
+
 int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const void* cameras, int32_t n_cams,
                      const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
                      const int32_t* counts, const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
@@ -1196,30 +1233,22 @@ int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, i
                      int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
                      void* stream) {
     // every check comes before the first HIP call
-    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
-    if (!c) return bad("vti_annotate: null ctx");
+    const char* fn = "vti_annotate";
+    if (!c) return refuse(c, fn, "null ctx");
     if (B < 1 || capacity < 0 || n_cams < 1 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-        return bad("vti_annotate: bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
-                   "1 <= H0, W0 <= 8192; native 0 or 1)");
+        return refuse(c, fn, "bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                             "1 <= H0, W0 <= 8192; native 0 or 1)");
     if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
         !dev_select || !out || !status || (capacity && !masks))
-        return bad("vti_annotate: null pointer");
-    for (int32_t k = 0; k < n_sel; ++k)
-        if (host_select[k] < 0 || host_select[k] >= B) {
-            char msg[120];
-            snprintf(msg, sizeof msg, "vti_annotate: host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
-            return bad(msg);
-        }
+        return refuse(c, fn, "null pointer");
+    VTI_TRY(select_check(fn, c, host_select, n_sel, B));
     if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
-        return bad("vti_annotate: the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
-    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
-        return bad(native ? "vti_annotate: native masks must be 8-byte aligned" : "vti_annotate: masks must be 16-byte aligned");
-    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
-        return bad("vti_annotate: misaligned measurement rows or status");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_annotate: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points))
-        return bad("vti_annotate: scratch smaller than vti_annotate_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_annotate")) return drc;
+        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
+    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
+    VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
+    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points),
+                          "vti_annotate_scratch_bytes()"));
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_annotate(frames, B, H0, W0, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det,
                                d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
@@ -1235,32 +1264,24 @@ int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32
                              int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
                              void* stream) {
     // every check comes before the first HIP call: vti_annotate's, and vti_measure_checker's of the params
-    if (!c || !p) return fail(c, VTI_ERR_ARG, "vti_annotate_checker: null ctx or params");
-    char msg[200];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "vti_annotate_checker: %s", what); return fail(c, VTI_ERR_ARG, msg); };
+    const char* fn = "vti_annotate_checker";
+    if (!c || !p) return refuse(c, fn, "null ctx or params");
     if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-        return bad("bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; 1 <= H0, W0 <= 8192; "
-                   "native 0 or 1)");
+        return refuse(c, fn, "bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                             "1 <= H0, W0 <= 8192; native 0 or 1)");
     if (!frames || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select || !dev_select ||
         !out || !status || (capacity && !masks))
-        return bad("null pointer");
-    if (const char* e = checker_params_error(p)) return bad(e);
-    for (int32_t k = 0; k < n_sel; ++k)
-        if (host_select[k] < 0 || host_select[k] >= B) {
-            snprintf(msg, sizeof msg, "vti_annotate_checker: host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
-            return fail(c, VTI_ERR_ARG, msg);
-        }
-    if ((uintptr_t)dev_select & 3) return bad("the selection must be 4-byte aligned");
-    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
-        return bad(native ? "native masks must be 8-byte aligned" : "masks must be 16-byte aligned");
+        return refuse(c, fn, "null pointer");
+    if (const char* e = settings_error(*p)) return refuse(c, fn, e);
+    VTI_TRY(select_check(fn, c, host_select, n_sel, B));
+    if ((uintptr_t)dev_select & 3) return refuse(c, fn, "the selection must be 4-byte aligned");
+    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
     if (!native && ((c->plan.desc.W & 31) || (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024))
-        return bad("letterbox size unsuitable for the resize tables");
-    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
-        return bad("misaligned measurement rows or status");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points))
-        return bad("scratch smaller than vti_annotate_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_annotate_checker")) return drc;
+        return refuse(c, fn, "letterbox size unsuitable for the resize tables");
+    VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
+    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points),
+                          "vti_annotate_scratch_bytes()"));
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_annotate_checker(*p, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H,
                                        d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status, scratch,
@@ -1276,42 +1297,44 @@ int64_t vti_overlay_scratch_bytes(const vti_ctx* c, int32_t n_sel, int32_t max_d
     return (int64_t)L.total;
 }
 
+// What vti_overlay and vti_overlay_frames check alike: the mode with its picture, the palette, the blend weights, and the alignment of
+// the rows the kernels index.
+static int32_t overlay_args_check(const char* fn, vti_ctx* c, int32_t mode, const uint8_t* annotated, int32_t n_colours, float alpha,
+                                  float beta, const int32_t* dev_select, const int32_t* counts, const int32_t* offsets,
+                                  const int32_t* status, const float* dets, const float* xyxy, const int32_t* plates) {
+    if (mode != VTI_OVERLAY_DRAW && mode != VTI_OVERLAY_BLEND && mode != VTI_OVERLAY_BOTH)
+        return refuse(c, fn, "mode must be VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND or VTI_OVERLAY_BOTH");
+    if (n_colours < 1 || n_colours > 16) return refuse(c, fn, "n_colours must be 1 .. 16");
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return refuse(c, fn, "alpha and beta must be finite");
+    if ((annotated != nullptr) != (mode == VTI_OVERLAY_BLEND))
+        return refuse(c, fn, "dev_annotated must be given with VTI_OVERLAY_BLEND and only then");
+    if (((uintptr_t)dev_select & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)status & 3) ||
+        ((uintptr_t)dets & 3) || ((uintptr_t)xyxy & 3))
+        return refuse(c, fn, "the index arrays, rows and status must be 4-byte aligned");
+    if (plates && ((uintptr_t)plates & 15)) return refuse(c, fn, "dev_plates must be 16-byte aligned");
+    return VTI_OK;
+}
+
 int32_t vti_overlay(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const uint8_t* masks, int32_t native,
                     const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
                     int32_t capacity, const int32_t* plates, const uint8_t* host_palette, int32_t n_colours, float alpha, float beta,
                     const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t mode, const uint8_t* annotated,
                     int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream) {
     // every check comes before the first HIP call
-    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
-    if (!c) return bad("vti_overlay: null ctx");
+    const char* fn = "vti_overlay";
+    if (!c) return refuse(c, fn, "null ctx");
     if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-        return bad("vti_overlay: bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
-                   "1 <= H0, W0 <= 8192; native 0 or 1)");
-    if (mode != VTI_OVERLAY_DRAW && mode != VTI_OVERLAY_BLEND && mode != VTI_OVERLAY_BOTH)
-        return bad("vti_overlay: mode must be VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND or VTI_OVERLAY_BOTH");
-    if (n_colours < 1 || n_colours > 16) return bad("vti_overlay: n_colours must be 1 .. 16");
-    if (!std::isfinite(alpha) || !std::isfinite(beta)) return bad("vti_overlay: alpha and beta must be finite");
-    if ((annotated != nullptr) != (mode == VTI_OVERLAY_BLEND))
-        return bad("vti_overlay: dev_annotated must be given with VTI_OVERLAY_BLEND and only then");
+        return refuse(c, fn, "bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                             "1 <= H0, W0 <= 8192; native 0 or 1)");
     if (!frames || !dets || !xyxy || !counts || !offsets || !host_palette || !host_select || !dev_select || !out || !status ||
         (capacity && !masks))
-        return bad("vti_overlay: null pointer");
-    for (int32_t k = 0; k < n_sel; ++k)
-        if (host_select[k] < 0 || host_select[k] >= B) {
-            char msg[120];
-            snprintf(msg, sizeof msg, "vti_overlay: host_select[%d] = %d is outside [0, %d)", k, host_select[k], B);
-            return bad(msg);
-        }
-    if (((uintptr_t)dev_select & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)status & 3) ||
-        ((uintptr_t)dets & 3) || ((uintptr_t)xyxy & 3))
-        return bad("vti_overlay: the index arrays, rows and status must be 4-byte aligned");
-    if (plates && ((uintptr_t)plates & 15)) return bad("vti_overlay: dev_plates must be 16-byte aligned");
-    if (capacity && ((uintptr_t)masks & (native ? 7 : 15)))
-        return bad(native ? "vti_overlay: native masks must be 8-byte aligned" : "vti_overlay: masks must be 16-byte aligned");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_overlay: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_overlay_scratch_bytes(c, n_sel, max_det, H0, W0, max_points))
-        return bad("vti_overlay: scratch smaller than vti_overlay_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_overlay")) return drc;
+        return refuse(c, fn, "null pointer");
+    VTI_TRY(overlay_args_check(fn, c, mode, annotated, n_colours, alpha, beta, dev_select, counts, offsets, status, dets, xyxy, plates));
+    VTI_TRY(select_check(fn, c, host_select, n_sel, B));
+    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
+    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_overlay_scratch_bytes(c, n_sel, max_det, H0, W0, max_points),
+                          "vti_overlay_scratch_bytes()"));
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
     VTI_HIP(c, launch_overlay(frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H, d.W, plates,
                               host_palette, n_colours, alpha, beta, dev_select, n_sel, mode, annotated, max_points, out, status, scratch,
@@ -1319,25 +1342,62 @@ int32_t vti_overlay(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, in
     return VTI_OK;
 }
 
-// ---- vti_annotate for frames of differing sizes ----------------------------------------------------------------------------
-// The header of a host frame table and row k of it.
-static FrameTableHeader table_header(const void* host_table) { FrameTableHeader h; memcpy(&h, host_table, sizeof h); return h; }
-static FrameRow table_row(const void* host_table, int32_t k) {
-    FrameRow r;
-    memcpy(&r, (const char*)host_table + sizeof(FrameTableHeader) + (size_t)k * sizeof r, sizeof r);
-    return r;
-}
-
-int64_t vti_annotate_frames_scratch_bytes(const vti_ctx* c, const void* host_out_table, int32_t max_det, int32_t max_points) {
-    if (!c || !host_out_table) return 0;
+// ---- vti_annotate and vti_overlay for frames of differing sizes --------------------------------------------------------------
+// The rows and the largest H0 and W0 of a host out table (of the rows themselves: the header's maxima are only an upper bound);
+// 0 rows when it is no table of vti_pack_frames.
+static int32_t out_table_maxima(const void* host_out_table, int32_t& mh, int32_t& mw) {
+    mh = mw = 0;
+    if (!host_out_table) return 0;
     const FrameTableHeader h = table_header(host_out_table);
     if (h.magic != kFrameTableMagic || h.B < 1) return 0;
-    int32_t mh = 0, mw = 0;                       // of the rows themselves (the header's maxima are only an upper bound)
     for (int32_t k = 0; k < h.B; ++k) {
         const FrameRow r = table_row(host_out_table, k);
         mh = std::max(mh, r.H0); mw = std::max(mw, r.W0);
     }
-    return vti_annotate_scratch_bytes(c, h.B, max_det, mh, mw, max_points);
+    return h.B;
+}
+
+int64_t vti_annotate_frames_scratch_bytes(const vti_ctx* c, const void* host_out_table, int32_t max_det, int32_t max_points) {
+    int32_t mh, mw;
+    const int32_t n = out_table_maxima(host_out_table, mh, mw);
+    return n ? vti_annotate_scratch_bytes(c, n, max_det, mh, mw, max_points) : 0;
+}
+
+int64_t vti_overlay_frames_scratch_bytes(const vti_ctx* c, const void* host_out_table, int32_t max_det, int32_t max_points) {
+    int32_t mh, mw;
+    const int32_t n = out_table_maxima(host_out_table, mh, mw);
+    return n ? vti_overlay_scratch_bytes(c, n, max_det, mh, mw, max_points) : 0;
+}
+
+// One walk over the selection of a *_frames drawing call: every host_select[k] is a frame of the batch, at most 8192 x 8192 and of
+// the size of row k of the out table.  `s` receives the largest H0, W0 and pixel count, and from `in_lds(c, row, slot_words)`, the
+// call's layout of one selected frame, which tracers serve the selection and the words of its largest native mask slot.
+struct Selection { int32_t mh = 0, mw = 0; long long max_px = 0, max_slot_words = 1; bool any_lds = false, any_global = false; };
+static int32_t selection_walk(const char* fn, vti_ctx* c, const void* host_table, const void* host_out_table, const int32_t* host_select,
+                              int32_t n_sel, int32_t B, int32_t max_det, int32_t max_points, Selection& s,
+                              bool (*in_lds)(const vti_ctx*, const FrameRow&, long long& slot_words)) {
+    char msg[200];
+    for (int32_t k = 0; k < n_sel; ++k) {
+        VTI_TRY(select_at(fn, c, host_select, k, B));
+        const int32_t b = host_select[k];
+        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
+        if (ri.H0 > 8192 || ri.W0 > 8192) {
+            snprintf(msg, sizeof msg, "frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
+            return refuse(c, fn, msg);
+        }
+        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
+            snprintf(msg, sizeof msg, "row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k, ro.H0, ro.W0, k, b,
+                     ri.H0, ri.W0);
+            return refuse(c, fn, msg);
+        }
+        s.mh = std::max(s.mh, ri.H0); s.mw = std::max(s.mw, ri.W0);
+        s.max_px = std::max(s.max_px, (long long)ri.H0 * ri.W0);
+        long long slot_words = 1;
+        (in_lds(c, ri, slot_words) ? s.any_lds : s.any_global) = true;
+        s.max_slot_words = std::max(s.max_slot_words, slot_words);
+    }
+    if (!annotate_sizes_ok(n_sel, max_det, s.mh, s.mw, max_points)) return refuse(c, fn, "the selection is too large");
+    return VTI_OK;
 }
 
 int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
@@ -1348,75 +1408,39 @@ int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_
                             const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
                             size_t scratch_bytes, void* stream) {
     // every check comes before the first HIP call
-    char msg[200];
-    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
-    if (!c) return bad("vti_annotate_frames: null ctx");
-    FrameTableHeader hi, ho;
-    if (int32_t rc = frames_check("vti_annotate_frames", c, host_table, dev_table, B, hi)) return rc;
-    if (n_sel < 1) return bad("vti_annotate_frames: n_sel must be >= 1");
-    if (int32_t rc = frames_check("vti_annotate_frames (out table)", c, host_out_table, dev_out_table, n_sel, ho)) return rc;
-    if (native == 1) return fail(c, VTI_ERR_UNSUPPORTED, "vti_annotate_frames: native masks need frames of one size (vti_annotate)");
+    const char* fn = "vti_annotate_frames";
+    if (!c) return refuse(c, fn, "null ctx");
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    if (n_sel < 1) return refuse(c, fn, "n_sel must be >= 1");
+    VTI_TRY(frames_check("vti_annotate_frames (out table)", c, host_out_table, dev_out_table, n_sel, h));
+    if (native == 1) return refuse(c, fn, "native masks need frames of one size (vti_annotate)", VTI_ERR_UNSUPPORTED);
     if (capacity < 0 || n_cams < 1 || native != 0 || max_det < 1 || max_det > VTI_MEASURE_MAX_DET || max_points < 0)
-        return bad("vti_annotate_frames: bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
+        return refuse(c, fn, "bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
     if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
         !dev_select || !out || !status || (capacity && !masks))
-        return bad("vti_annotate_frames: null pointer");
-    int32_t mh = 0, mw = 0;
-    long long max_px = 0;
-    bool any_lds = false, any_global = false;
-    for (int32_t k = 0; k < n_sel; ++k) {
-        const int32_t b = host_select[k];
-        if (b < 0 || b >= B) {
-            snprintf(msg, sizeof msg, "vti_annotate_frames: host_select[%d] = %d is outside [0, %d)", k, b, B);
-            return bad(msg);
-        }
-        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
-        if (ri.H0 > 8192 || ri.W0 > 8192) {
-            snprintf(msg, sizeof msg, "vti_annotate_frames: frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
-            return bad(msg);
-        }
-        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
-            snprintf(msg, sizeof msg, "vti_annotate_frames: row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k,
-                     ro.H0, ro.W0, k, b, ri.H0, ri.W0);
-            return bad(msg);
-        }
-        mh = std::max(mh, ri.H0); mw = std::max(mw, ri.W0);
-        max_px = std::max(max_px, (long long)ri.H0 * ri.W0);
-        AnnotateLayout one;
-        annotate_layout(1, 1, ri.H0, ri.W0, 0, one);
-        (one.in_lds ? any_lds : any_global) = true;
-    }
-    if (!annotate_sizes_ok(n_sel, max_det, mh, mw, max_points)) return bad("vti_annotate_frames: the selection is too large");
-    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 15))
-        return bad("vti_annotate_frames: dev_frames and dev_out must be 16-byte aligned");
+        return refuse(c, fn, "null pointer");
+    Selection s;
+    VTI_TRY(selection_walk(fn, c, host_table, host_out_table, host_select, n_sel, B, max_det, max_points, s,
+                           [](const vti_ctx*, const FrameRow& r, long long&) {
+                               AnnotateLayout one;                   // the frame's own bitmap: which tracer serves it
+                               annotate_layout(1, 1, r.H0, r.W0, 0, one);
+                               return one.in_lds;
+                           }));
+    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 15)) return refuse(c, fn, "dev_frames and dev_out must be 16-byte aligned");
     if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
-        return bad("vti_annotate_frames: the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
-    if (capacity && ((uintptr_t)masks & 15)) return bad("vti_annotate_frames: masks must be 16-byte aligned");
-    if (((uintptr_t)stitch_f64 & 7) || ((uintptr_t)stitch_i32 & 3) || ((uintptr_t)frame_i32 & 3) || ((uintptr_t)status & 3))
-        return bad("vti_annotate_frames: misaligned measurement rows or status");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_annotate_frames: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_annotate_scratch_bytes(c, n_sel, max_det, mh, mw, max_points))
-        return bad("vti_annotate_frames: scratch smaller than vti_annotate_frames_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_annotate_frames")) return drc;
+        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
+    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, 0));
+    VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
+    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, s.mh, s.mw, max_points),
+                          "vti_annotate_frames_scratch_bytes()"));
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
-    const AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), any_lds, any_global, max_px};
-    VTI_HIP(c, launch_annotate(frames, B, mh, mw, cameras, n_cams, cam_of_frame, masks, 0, dets, xyxy, counts, offsets, max_det, d.nm,
+    const AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), s.any_lds, s.any_global, s.max_px};
+    VTI_HIP(c, launch_annotate(frames, B, s.mh, s.mw, cameras, n_cams, cam_of_frame, masks, 0, dets, xyxy, counts, offsets, max_det, d.nm,
                                capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
                                scratch, (hipStream_t)stream, &fr), "annotate kernels");
     return VTI_OK;
-}
-
-// ---- vti_overlay for frames of differing sizes -----------------------------------------------------------------------------
-int64_t vti_overlay_frames_scratch_bytes(const vti_ctx* c, const void* host_out_table, int32_t max_det, int32_t max_points) {
-    if (!c || !host_out_table) return 0;
-    const FrameTableHeader h = table_header(host_out_table);
-    if (h.magic != kFrameTableMagic || h.B < 1) return 0;
-    int32_t mh = 0, mw = 0;                       // of the rows themselves (the header's maxima are only an upper bound)
-    for (int32_t k = 0; k < h.B; ++k) {
-        const FrameRow r = table_row(host_out_table, k);
-        mh = std::max(mh, r.H0); mw = std::max(mw, r.W0);
-    }
-    return vti_overlay_scratch_bytes(c, h.B, max_det, mh, mw, max_points);
 }
 
 int32_t vti_overlay_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
@@ -1427,72 +1451,41 @@ int32_t vti_overlay_frames(vti_ctx* c, const uint8_t* frames, const void* host_t
                            int32_t max_points, const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status,
                            void* scratch, size_t scratch_bytes, void* stream) {
     // every check comes before the first HIP call
-    char msg[200];
-    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
-    if (!c) return bad("vti_overlay_frames: null ctx");
-    FrameTableHeader hi, ho;
-    if (int32_t rc = frames_check("vti_overlay_frames", c, host_table, dev_table, B, hi)) return rc;
-    if (n_sel < 1) return bad("vti_overlay_frames: n_sel must be >= 1");
-    if (int32_t rc = frames_check("vti_overlay_frames (out table)", c, host_out_table, dev_out_table, n_sel, ho)) return rc;
+    const char* fn = "vti_overlay_frames";
+    if (!c) return refuse(c, fn, "null ctx");
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    if (n_sel < 1) return refuse(c, fn, "n_sel must be >= 1");
+    VTI_TRY(frames_check("vti_overlay_frames (out table)", c, host_out_table, dev_out_table, n_sel, h));
     if (capacity < 0 || (native != 0 && native != 1) || max_det < 1 || max_det > VTI_MEASURE_MAX_DET || max_points < 0)
-        return bad("vti_overlay_frames: bad size (capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0 or 1)");
-    if (mode != VTI_OVERLAY_DRAW && mode != VTI_OVERLAY_BLEND && mode != VTI_OVERLAY_BOTH)
-        return bad("vti_overlay_frames: mode must be VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND or VTI_OVERLAY_BOTH");
-    if (n_colours < 1 || n_colours > 16) return bad("vti_overlay_frames: n_colours must be 1 .. 16");
-    if (!std::isfinite(alpha) || !std::isfinite(beta)) return bad("vti_overlay_frames: alpha and beta must be finite");
-    if ((annotated != nullptr) != (mode == VTI_OVERLAY_BLEND))
-        return bad("vti_overlay_frames: dev_annotated must be given with VTI_OVERLAY_BLEND and only then");
-    if (!native && mask_bases) return bad("vti_overlay_frames: dev_mask_bases must be NULL with letterbox masks (native = 0)");
-    if (native && !mask_bases) return bad("vti_overlay_frames: native masks need dev_mask_bases (vti_masks_native_frames)");
-    if (capacity_bytes < 0) return bad("vti_overlay_frames: capacity_bytes must be >= 0");
+        return refuse(c, fn, "bad size (capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0 or 1)");
+    if (!native && mask_bases) return refuse(c, fn, "dev_mask_bases must be NULL with letterbox masks (native = 0)");
+    if (native && !mask_bases) return refuse(c, fn, "native masks need dev_mask_bases (vti_masks_native_frames)");
+    if (capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
     const bool need_masks = capacity > 0 && (!native || capacity_bytes > 0);
     if (!frames || !dets || !xyxy || !counts || !offsets || !host_palette || !host_select || !dev_select || !out || !status ||
         (need_masks && !masks))
-        return bad("vti_overlay_frames: null pointer");
-    int32_t mh = 0, mw = 0;
-    long long max_px = 0, max_slot_words = 1;
-    bool any_lds = false, any_global = false;
-    for (int32_t k = 0; k < n_sel; ++k) {
-        const int32_t b = host_select[k];
-        if (b < 0 || b >= B) {
-            snprintf(msg, sizeof msg, "vti_overlay_frames: host_select[%d] = %d is outside [0, %d)", k, b, B);
-            return bad(msg);
-        }
-        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
-        if (ri.H0 > 8192 || ri.W0 > 8192) {
-            snprintf(msg, sizeof msg, "vti_overlay_frames: frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
-            return bad(msg);
-        }
-        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
-            snprintf(msg, sizeof msg, "vti_overlay_frames: row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k,
-                     ro.H0, ro.W0, k, b, ri.H0, ri.W0);
-            return bad(msg);
-        }
-        mh = std::max(mh, ri.H0); mw = std::max(mw, ri.W0);
-        max_px = std::max(max_px, (long long)ri.H0 * ri.W0);
-        OverlayLayout one;                        // the frame's own bitmap: which tracer serves it, and the words of its native slot
-        overlay_layout(1, 1, ri.H0, ri.W0, c->plan.desc.H, c->plan.desc.W, 0, one);
-        (one.in_lds ? any_lds : any_global) = true;
-        max_slot_words = std::max(max_slot_words, (long long)ri.H0 * 2 * one.WW);
-    }
-    if (!annotate_sizes_ok(n_sel, max_det, mh, mw, max_points)) return bad("vti_overlay_frames: the selection is too large");
+        return refuse(c, fn, "null pointer");
+    VTI_TRY(overlay_args_check(fn, c, mode, annotated, n_colours, alpha, beta, dev_select, counts, offsets, status, dets, xyxy, plates));
+    Selection s;
+    VTI_TRY(selection_walk(fn, c, host_table, host_out_table, host_select, n_sel, B, max_det, max_points, s,
+                           [](const vti_ctx* c, const FrameRow& r, long long& slot_words) {
+                               OverlayLayout one;                    // the frame's own bitmap: which tracer serves it, and the words of its native slot
+                               overlay_layout(1, 1, r.H0, r.W0, c->plan.desc.H, c->plan.desc.W, 0, one);
+                               slot_words = (long long)r.H0 * 2 * one.WW;
+                               return one.in_lds;
+                           }));
     if (((uintptr_t)frames & 15) || ((uintptr_t)out & 15) || ((uintptr_t)annotated & 15))
-        return bad("vti_overlay_frames: dev_frames, dev_out and dev_annotated must be 16-byte aligned");
-    if (((uintptr_t)dev_select & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)status & 3) ||
-        ((uintptr_t)dets & 3) || ((uintptr_t)xyxy & 3))
-        return bad("vti_overlay_frames: the index arrays, rows and status must be 4-byte aligned");
-    if (mask_bases && ((uintptr_t)mask_bases & 7)) return bad("vti_overlay_frames: dev_mask_bases must be 8-byte aligned");
-    if (plates && ((uintptr_t)plates & 15)) return bad("vti_overlay_frames: dev_plates must be 16-byte aligned");
-    if (need_masks && ((uintptr_t)masks & (native ? 7 : 15)))
-        return bad(native ? "vti_overlay_frames: native masks must be 8-byte aligned" : "vti_overlay_frames: masks must be 16-byte aligned");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_overlay_frames: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < vti_overlay_scratch_bytes(c, n_sel, max_det, mh, mw, max_points))
-        return bad("vti_overlay_frames: scratch smaller than vti_overlay_frames_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_overlay_frames")) return drc;
+        return refuse(c, fn, "dev_frames, dev_out and dev_annotated must be 16-byte aligned");
+    if (mask_bases && ((uintptr_t)mask_bases & 7)) return refuse(c, fn, "dev_mask_bases must be 8-byte aligned");
+    VTI_TRY(mask_align_check(fn, c, need_masks ? masks : nullptr, native));
+    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_overlay_scratch_bytes(c, n_sel, max_det, s.mh, s.mw, max_points),
+                          "vti_overlay_frames_scratch_bytes()"));
+    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
     const OverlayFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), (const long long*)mask_bases, capacity_bytes,
-                           max_slot_words, any_lds, any_global, max_px};
-    VTI_HIP(c, launch_overlay(frames, B, mh, mw, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H, d.W, plates,
+                           s.max_slot_words, s.any_lds, s.any_global, s.max_px};
+    VTI_HIP(c, launch_overlay(frames, B, s.mh, s.mw, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H, d.W, plates,
                               host_palette, n_colours, alpha, beta, dev_select, n_sel, mode, annotated, max_points, out, status, scratch,
                               (hipStream_t)stream, &fr), "overlay kernels");
     return VTI_OK;
@@ -1510,21 +1503,28 @@ int64_t vti_encode_jpeg_max_bytes(int32_t n, int32_t H0, int32_t W0) {
     return (int64_t)n * L.max_file;
 }
 
+// What the two encode calls check alike: the settings, the pointers and the scratch (`need` bytes, the answer of `query`).
+static int32_t jpeg_args_check(const char* fn, vti_ctx* c, const uint8_t* frames, int32_t rgb, int32_t quality, const void* scratch,
+                               size_t scratch_bytes, int64_t need, const char* query, const int64_t* offsets, const uint8_t* out,
+                               int64_t max_bytes) {
+    if (quality < 1 || quality > 100 || (rgb != 0 && rgb != 1) || max_bytes < 0)
+        return refuse(c, fn, "1 <= quality <= 100, rgb 0 or 1, max_bytes >= 0");
+    if (!frames || !offsets || (max_bytes && !out)) return refuse(c, fn, "null pointer");
+    if ((uintptr_t)offsets & 7) return refuse(c, fn, "dev_byte_offsets must be 8-byte aligned");
+    return scratch_check(fn, c, scratch, scratch_bytes, need, query);
+}
+
 int32_t vti_encode_jpeg(vti_ctx* c, const uint8_t* frames, int32_t n, int32_t H0, int32_t W0, int32_t rgb, int32_t quality,
                         void* scratch, size_t scratch_bytes, int64_t* offsets, uint8_t* out, int64_t max_bytes, void* stream) {
     // every check comes before the first HIP call
-    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
-    if (!c) return bad("vti_encode_jpeg: null ctx");
+    const char* fn = "vti_encode_jpeg";
+    if (!c) return refuse(c, fn, "null ctx");
     JpegLayout L;
     if (!encode_jpeg_layout(n, H0, W0, L))
-        return bad("vti_encode_jpeg: bad size (n >= 1; 1 <= H0, W0 <= 8192; n * ceil(H0/16) * ceil(W0/16) <= 2^28)");
-    if (quality < 1 || quality > 100 || (rgb != 0 && rgb != 1) || max_bytes < 0)
-        return bad("vti_encode_jpeg: 1 <= quality <= 100, rgb 0 or 1, max_bytes >= 0");
-    if (!frames || !offsets || (max_bytes && !out)) return bad("vti_encode_jpeg: null pointer");
-    if ((uintptr_t)offsets & 7) return bad("vti_encode_jpeg: dev_byte_offsets must be 8-byte aligned");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_encode_jpeg: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < (int64_t)L.total) return bad("vti_encode_jpeg: scratch smaller than vti_encode_jpeg_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_encode_jpeg")) return drc;
+        return refuse(c, fn, "bad size (n >= 1; 1 <= H0, W0 <= 8192; n * ceil(H0/16) * ceil(W0/16) <= 2^28)");
+    VTI_TRY(jpeg_args_check(fn, c, frames, rgb, quality, scratch, scratch_bytes, (int64_t)L.total,
+                            "vti_encode_jpeg_scratch_bytes()", offsets, out, max_bytes));
+    VTI_TRY(check_device(c, fn));
     VTI_HIP(c, launch_encode_jpeg(frames, n, H0, W0, rgb, quality, scratch, (long long*)offsets, out, (long long)max_bytes,
                                   (hipStream_t)stream), "encode_jpeg kernels");
     return VTI_OK;
@@ -1556,24 +1556,15 @@ int32_t vti_encode_jpeg_frames(vti_ctx* c, const uint8_t* frames, const void* ho
                                int32_t quality, void* scratch, size_t scratch_bytes, int64_t* offsets, uint8_t* out, int64_t max_bytes,
                                void* stream) {
     // every check comes before the first HIP call
-    auto bad = [&](const char* what) { return fail(c, VTI_ERR_ARG, what); };
-    if (!c) return bad("vti_encode_jpeg_frames: null ctx");
+    const char* fn = "vti_encode_jpeg_frames";
+    if (!c) return refuse(c, fn, "null ctx");
     FrameTableHeader h;
-    if (int32_t rc = frames_check("vti_encode_jpeg_frames", c, host_table, dev_table, n, h)) return rc;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, n, h));
     JpegFramesLayout L;
-    if (const char* e = jpeg_table_error(host_table, L)) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "vti_encode_jpeg_frames: %s", e);
-        return bad(msg);
-    }
-    if (quality < 1 || quality > 100 || (rgb != 0 && rgb != 1) || max_bytes < 0)
-        return bad("vti_encode_jpeg_frames: 1 <= quality <= 100, rgb 0 or 1, max_bytes >= 0");
-    if (!frames || !offsets || (max_bytes && !out)) return bad("vti_encode_jpeg_frames: null pointer");
-    if ((uintptr_t)offsets & 7) return bad("vti_encode_jpeg_frames: dev_byte_offsets must be 8-byte aligned");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_encode_jpeg_frames: scratch must be a 256-byte aligned device pointer");
-    if ((int64_t)scratch_bytes < (int64_t)L.total)
-        return bad("vti_encode_jpeg_frames: scratch smaller than vti_encode_jpeg_frames_scratch_bytes()");
-    if (int32_t drc = check_device(c, "vti_encode_jpeg_frames")) return drc;
+    if (const char* e = jpeg_table_error(host_table, L)) return refuse(c, fn, e);
+    VTI_TRY(jpeg_args_check(fn, c, frames, rgb, quality, scratch, scratch_bytes, (int64_t)L.total,
+                            "vti_encode_jpeg_frames_scratch_bytes()", offsets, out, max_bytes));
+    VTI_TRY(check_device(c, fn));
     VTI_HIP(c, launch_encode_jpeg_frames(frames, host_table, frame_rows(dev_table), rgb, quality, scratch, (long long*)offsets, out,
                                          (long long)max_bytes, (hipStream_t)stream), "encode_jpeg_frames kernels");
     return VTI_OK;
@@ -1647,13 +1638,12 @@ int32_t vti_decode_jpeg(vti_ctx* c, const uint8_t* files, const void* host_table
     if (rgb != 0 && rgb != 1) return bad("vti_decode_jpeg: rgb 0 or 1");
     if (!files || !host_table || !dev_table || !out || !info) return bad("vti_decode_jpeg: null pointer");
     if (((uintptr_t)dev_table & 15) || ((uintptr_t)info & 3)) return bad("vti_decode_jpeg: dev_table must be 16-byte aligned, dev_info 4-byte aligned");
-    if (!scratch || ((uintptr_t)scratch & 255)) return bad("vti_decode_jpeg: scratch must be a 256-byte aligned device pointer");
     JpegDecHeader H;
     memcpy(&H, host_table, sizeof H);
     if (H.magic != kJpegDecMagic || H.n != n || (H.layout != 0 && H.layout != 1) || H.files_bytes < 0 || H.out_bytes < 0 || H.scratch_bytes < 0)
         return bad("vti_decode_jpeg: host_table is not a descriptor table of vti_decode_jpeg_plan for n files");
     if (out_bytes < H.out_bytes) return bad("vti_decode_jpeg: dev_out smaller than out_byte_offsets[n]");
-    if ((int64_t)scratch_bytes < H.scratch_bytes) return bad("vti_decode_jpeg: scratch smaller than the plan's scratch_bytes");
+    VTI_TRY(scratch_check("vti_decode_jpeg", c, scratch, scratch_bytes, H.scratch_bytes, "the plan's scratch_bytes"));
     size_t scratch_at = 0;
     long long out_at = 0;
     for (int32_t k = 0; k < n; ++k) {
@@ -1664,7 +1654,7 @@ int32_t vti_decode_jpeg(vti_ctx* c, const uint8_t* files, const void* host_table
             return bad("vti_decode_jpeg: row " + std::to_string(k) + " of the table is invalid (" + (why.empty() ? "frames overlap" : why) + ")");
         out_at = R.out_off + 3LL * R.H0 * R.W0;
     }
-    if (int32_t drc = check_device(c, "vti_decode_jpeg")) return drc;
+    VTI_TRY(check_device(c, "vti_decode_jpeg"));
     VTI_HIP(c, launch_decode_jpeg(files, host_table, dev_table, n, rgb, out, info, scratch, (hipStream_t)stream), "decode_jpeg kernels");
     return VTI_OK;
 }
@@ -1754,8 +1744,7 @@ int32_t vti_convert_raw_frames(vti_ctx* c, const uint8_t* raw_buf, int64_t raw_b
         if (!e && (r.raw_off < at || (r.raw_off & 15))) e = "raw offsets must ascend without overlap, each a multiple of 16";
         if (!e && (r.raw_off > h.raw_bytes || r.raw_len > h.raw_bytes - r.raw_off)) e = "the raw frame runs past the table's raw_bytes";
         if (e) return bad("vti_convert_raw_frames: row " + std::to_string(b) + " of host_raw_table is invalid (" + e + ")");
-        FrameRow f;
-        memcpy(&f, (const char*)host_frame_table + sizeof fh + (size_t)b * sizeof f, sizeof f);
+        const FrameRow f = table_row(host_frame_table, b);
         if (f.H0 != r.H0 || f.W0 != r.W0)
             return bad("vti_convert_raw_frames: frame " + std::to_string(b) + ": the raw table says " + std::to_string(r.H0) + "x" +
                        std::to_string(r.W0) + ", the frame table " + std::to_string(f.H0) + "x" + std::to_string(f.W0));

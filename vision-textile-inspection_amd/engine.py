@@ -32,6 +32,51 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---- argument checks shared by measure, measure_checker, annotate, annotate_checker and overlay (`who`: the method's name) ----------
+def _select(who, select, B):
+    """select -> the frame indices as a contiguous int32 array, each in [0, B)."""
+    sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
+    if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
+        raise ValueError(f"{who}: select must be a non-empty sequence of frame indices")
+    if sel.min() < 0 or sel.max() >= B:
+        raise ValueError(f"{who}: frame index outside [0, {B})")
+    return np.ascontiguousarray(sel, dtype=np.int32)
+
+
+def _uniform_frames(who, frames):
+    """A batch of frames of one size -> (B, H0, W0)."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"{who}: frames must be a uint8 [B,H0,W0,3] tensor")
+    return frames.shape[:3]
+
+
+def _measure_result(result, B, capacity, stitch_rows, dev):
+    """The dict a measurement returns: `result`'s tensors, and a new one for each that it lacks."""
+    r = dict(result or {})
+    rows = [("frame_f64", (B, 2), torch.float64), ("frame_i32", (B, 6), torch.int32)]
+    if stitch_rows:
+        rows += [("stitch_f64", (capacity, 7), torch.float64), ("stitch_i32", (capacity, 2), torch.int32)]
+    for key, shape, dtype in rows:
+        if key not in r:
+            r[key] = torch.empty(shape, dtype=dtype, device=dev)
+    return r
+
+
+def _camera_index(who, cameras, B, n_cams, dev, same_device=True):
+    """The camera of every frame -> int32 [B] on dev.  A device tensor is checked on the device, a host sequence is range-checked here.
+    same_device=False: a device tensor's own device is not compared with dev (annotate never did)."""
+    if isinstance(cameras, torch.Tensor) and cameras.is_cuda:
+        if cameras.dtype != torch.int32 or tuple(cameras.shape) != (B,) or not cameras.is_contiguous() or (same_device and cameras.device != dev):
+            raise ValueError(f"{who}: cameras must be a contiguous int32 [{B}] tensor on the outputs' device")
+        return cameras
+    host = np.asarray(cameras.numpy() if isinstance(cameras, torch.Tensor) else cameras)
+    if host.shape != (B,) or host.dtype.kind not in "iu":
+        raise ValueError(f"{who}: cameras must be {B} integers, one per frame")
+    if B and (host.min() < 0 or host.max() >= n_cams):
+        raise ValueError(f"{who}: camera index outside [0, {n_cams})")
+    return torch.from_numpy(host.astype(np.int32)).to(dev)
+
+
 class FrameTable:
     """A packed frame table (vti_pack_frames) for a batch whose frames differ in size: `host` (the packed bytes, a CPU u8 tensor)
     and `dev` (their device copy), `shapes` [(H0, W0)] per frame, the frames' `byte_offsets` in the flat frame buffer and its
@@ -500,6 +545,23 @@ class Engine:
         check(self._ctx, lib().vti_measure_pack_cameras(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
         return host.to(device or self.device or "cuda")
 
+    def _camera_table(self, who, what, params_or_table, dev):
+        """A list of MeasureParams or the table of pack_cameras() -> (table, n_cams); `what` names the argument in the refusal."""
+        table = params_or_table if isinstance(params_or_table, torch.Tensor) else self.pack_cameras(params_or_table, dev)
+        row = int(lib().vti_measure_cameras_bytes(1))
+        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
+            raise ValueError(f"{who}: {what} of pack_cameras() on the outputs' device")
+        return table, table.numel() // row
+
+    def _scratch(self, attr, need, dev):
+        """The scratch kept as self.<attr>: at least `need` bytes on dev, reallocated only when it is too small or elsewhere."""
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            setattr(self, attr, None)
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            setattr(self, attr, ws)
+        return ws
+
     def measure(self, out, params, H0=None, W0=None, native=False, stitch_rows=True, result=None, cameras=None, frames=None):
         """The per-frame measurement of measurement.py's process_frame for every frame of an alloc_outputs() set that predict_into()
         (or nms/masks/scale_boxes) filled: vti_measure.  params: a measure.MeasureParams (or a VtiMeasureParams).  native=True: the
@@ -536,37 +598,12 @@ class Engine:
         elif H0 is None or W0 is None:
             raise ValueError("measure: H0 and W0 (or frames=) are required")
         if cameras is not None:
-            table = params if isinstance(params, torch.Tensor) else self.pack_cameras(params, dev)
-            row = int(lib().vti_measure_cameras_bytes(1))
-            if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
-                raise ValueError("measure: params must be the u8 table of pack_cameras() on the outputs' device")
-            n_cams = table.numel() // row
-            if isinstance(cameras, torch.Tensor) and cameras.is_cuda:
-                if cameras.dtype != torch.int32 or tuple(cameras.shape) != (B,) or not cameras.is_contiguous() or cameras.device != dev:
-                    raise ValueError(f"measure: cameras must be a contiguous int32 [{B}] tensor on the outputs' device")
-            else:
-                host = np.asarray(cameras.numpy() if isinstance(cameras, torch.Tensor) else cameras)
-                if host.shape != (B,) or host.dtype.kind not in "iu":
-                    raise ValueError(f"measure: cameras must be {B} integers, one per frame")
-                if B and (host.min() < 0 or host.max() >= n_cams):
-                    raise ValueError(f"measure: camera index outside [0, {n_cams})")
-                cameras = torch.from_numpy(host.astype(np.int32)).to(dev)
+            table, n_cams = self._camera_table("measure", "params must be the u8 table", params, dev)
+            cameras = _camera_index("measure", cameras, B, n_cams, dev)
         else:
             cp = params.to_c() if hasattr(params, "to_c") else params
-        r = dict(result or {})
-        if "frame_f64" not in r:
-            r["frame_f64"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        if "frame_i32" not in r:
-            r["frame_i32"] = torch.empty((B, 6), dtype=torch.int32, device=dev)
-        if stitch_rows:
-            if "stitch_f64" not in r:
-                r["stitch_f64"] = torch.empty((capacity, 7), dtype=torch.float64, device=dev)
-            if "stitch_i32" not in r:
-                r["stitch_i32"] = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
-        need = self.measure_scratch_bytes(B, capacity, W0)
-        ws = getattr(self, "_measure_ws", None)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self._measure_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        r = _measure_result(result, B, capacity, stitch_rows, dev)
+        ws = self._scratch("_measure_ws", max(self.measure_scratch_bytes(B, capacity, W0), 256), dev)
         head = (_ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]),
                 _ptr(out["offsets"]))
         tail = (_ptr(ws), ws.numel(), _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")),
@@ -596,20 +633,8 @@ class Engine:
         if H0 is None or W0 is None:
             raise ValueError("measure_checker: H0 and W0 are required")
         cp = params.to_c() if hasattr(params, "to_c") else params
-        r = dict(result or {})
-        if "frame_f64" not in r:
-            r["frame_f64"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        if "frame_i32" not in r:
-            r["frame_i32"] = torch.empty((B, 6), dtype=torch.int32, device=dev)
-        if stitch_rows:
-            if "stitch_f64" not in r:
-                r["stitch_f64"] = torch.empty((capacity, 7), dtype=torch.float64, device=dev)
-            if "stitch_i32" not in r:
-                r["stitch_i32"] = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
-        need = self.measure_scratch_bytes(B, capacity, W0)
-        ws = getattr(self, "_measure_ws", None)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self._measure_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        r = _measure_result(result, B, capacity, stitch_rows, dev)
+        ws = self._scratch("_measure_ws", max(self.measure_scratch_bytes(B, capacity, W0), 256), dev)
         check(self._ctx, lib().vti_measure_checker(
             self._ctx, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]),
             _ptr(out["counts"]), _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(),
@@ -643,20 +668,13 @@ class Engine:
                 raise ValueError("annotate: with table=, frames must be the flat uint8 frame buffer")
             B, H0, W0 = table.B, None, None
         else:
-            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-                raise ValueError("annotate: frames must be a uint8 [B,H0,W0,3] tensor")
-            B, H0, W0, _ = frames.shape
+            B, H0, W0 = _uniform_frames("annotate", frames)
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
             raise ValueError(f"annotate: {B} frames but an output set of {out['counts'].shape[0]}")
         max_det, capacity = dets.shape[1], masks.shape[0]
-        sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
-        if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
-            raise ValueError("annotate: select must be a non-empty sequence of frame indices")
-        if sel.min() < 0 or sel.max() >= B:
-            raise ValueError(f"annotate: frame index outside [0, {B})")
-        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        sel = _select("annotate", select, B)
         n_sel = int(sel.size)
         for key in ("frame_i32", "stitch_f64", "stitch_i32"):
             if meas.get(key) is None:
@@ -664,22 +682,11 @@ class Engine:
         # everything above is about shapes and values; what needs a device comes from here on
         if not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("annotate: frames must be the contiguous device batch predict consumed")
-        table_c = params_or_table
-        if not isinstance(table_c, torch.Tensor):
-            table_c = self.pack_cameras(table_c if isinstance(table_c, (list, tuple)) else [table_c], dev)
-        row = int(lib().vti_measure_cameras_bytes(1))
-        if table_c.dtype != torch.uint8 or table_c.dim() != 1 or table_c.numel() < row or table_c.numel() % row or table_c.device != dev:
-            raise ValueError("annotate: params_or_table must be MeasureParams or the u8 table of pack_cameras() on the outputs' device")
-        n_cams = table_c.numel() // row
-        if cameras is not None and not (isinstance(cameras, torch.Tensor) and cameras.is_cuda):
-            host = np.asarray(cameras.numpy() if isinstance(cameras, torch.Tensor) else cameras)
-            if host.shape != (B,) or host.dtype.kind not in "iu":
-                raise ValueError(f"annotate: cameras must be {B} integers, one per frame")
-            if host.min() < 0 or host.max() >= n_cams:
-                raise ValueError(f"annotate: camera index outside [0, {n_cams})")
-            cameras = torch.from_numpy(host.astype(np.int32)).to(dev)
-        elif cameras is not None and (cameras.dtype != torch.int32 or tuple(cameras.shape) != (B,) or not cameras.is_contiguous()):
-            raise ValueError(f"annotate: cameras must be a contiguous int32 [{B}] tensor on the outputs' device")
+        if not isinstance(params_or_table, (list, tuple, torch.Tensor)):
+            params_or_table = [params_or_table]
+        table_c, n_cams = self._camera_table("annotate", "params_or_table must be MeasureParams or the u8 table", params_or_table, dev)
+        if cameras is not None:
+            cameras = _camera_index("annotate", cameras, B, n_cams, dev, same_device=False)
         r = dict(result or {})
         if "status" not in r:
             r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
@@ -687,10 +694,7 @@ class Engine:
             self._check_frames(table, buf=frames)
             shapes = tuple(table.shapes[int(b)] for b in sel)
             out_table = self._out_table(shapes, dev)                     # the 16 latest selections are kept
-            if "buf" not in r:
-                r["buf"] = torch.empty(out_table.total_bytes, dtype=torch.uint8, device=dev)
-            self._check_frames(out_table, buf=r["buf"])
-            r.update(table=out_table, shapes=list(shapes), byte_offsets=list(out_table.byte_offsets))
+            self._selection_out(r, out_table, shapes, dev)
             need = int(lib().vti_annotate_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
             if need <= 0:
                 raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
@@ -701,10 +705,7 @@ class Engine:
             need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
             if need <= 0:
                 raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
-        ws = getattr(self, "_annotate_ws", None)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            self._annotate_ws = None
-            ws = self._annotate_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._scratch("_annotate_ws", need, dev)
         dev_sel = torch.from_numpy(sel).to(dev)
         if table is not None:
             check(self._ctx, lib().vti_annotate_frames(
@@ -727,20 +728,13 @@ class Engine:
         returned dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]) of device tensors are annotate()'s uniform form (the frames feed
         encode_jpeg as they are); meas: measure_checker(..., stitch_rows=True)'s dict on the same set; params: the CheckerParams (or
         VtiCheckerParams) of that call.  One frame size, one camera.  Text is the host's: measure.checker_text_items / put_text."""
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("annotate_checker: frames must be a uint8 [B,H0,W0,3] tensor")
-        B, H0, W0, _ = frames.shape
+        B, H0, W0 = _uniform_frames("annotate_checker", frames)
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
             raise ValueError(f"annotate_checker: {B} frames but an output set of {out['counts'].shape[0]}")
         max_det, capacity = dets.shape[1], masks.shape[0]
-        sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
-        if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
-            raise ValueError("annotate_checker: select must be a non-empty sequence of frame indices")
-        if sel.min() < 0 or sel.max() >= B:
-            raise ValueError(f"annotate_checker: frame index outside [0, {B})")
-        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        sel = _select("annotate_checker", select, B)
         n_sel = int(sel.size)
         for key in ("frame_i32", "stitch_f64", "stitch_i32"):
             if meas.get(key) is None:
@@ -757,10 +751,7 @@ class Engine:
         need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
         if need <= 0:
             raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
-        ws = getattr(self, "_annotate_ws", None)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            self._annotate_ws = None
-            ws = self._annotate_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._scratch("_annotate_ws", need, dev)
         dev_sel = torch.from_numpy(sel).to(dev)
         check(self._ctx, lib().vti_annotate_checker(
             self._ctx, _ptr(frames), B, H0, W0, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets),
@@ -783,6 +774,14 @@ class Engine:
                 del cache[next(iter(cache))]
         cache[(shapes, str(dev))] = out_table                           # (re)inserted last: the oldest entry is the first
         return out_table
+
+    def _selection_out(self, r, out_table, shapes, dev):
+        """What a drawing call with table= returns besides status, put into r: the selection's out table, `buf` for its pictures (r's
+        own if it has one), shapes and byte_offsets."""
+        if "buf" not in r:
+            r["buf"] = torch.empty(out_table.total_bytes, dtype=torch.uint8, device=dev)
+        self._check_frames(out_table, buf=r["buf"])
+        r.update(table=out_table, shapes=list(shapes), byte_offsets=list(out_table.byte_offsets))
 
     def overlay(self, frames, out, select, native=False, plates=None, mode="both", annotated=None, alpha=0.30, beta=0.70,
                 palette=_ov.PALETTE, max_points=16384, result=None, table=None, mask_bases=None, capacity_bytes=None):
@@ -812,21 +811,14 @@ class Engine:
         else:
             if mask_bases is not None or capacity_bytes is not None:
                 raise ValueError("overlay: mask_bases and capacity_bytes belong to table= (frames of differing sizes)")
-            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-                raise ValueError("overlay: frames must be a uint8 [B,H0,W0,3] tensor")
-            B, H0, W0, _ = frames.shape
+            B, H0, W0 = _uniform_frames("overlay", frames)
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
             raise ValueError(f"overlay: {B} frames but an output set of {out['counts'].shape[0]}")
         max_det, capacity = dets.shape[1], masks.shape[0]
         ragged = table is not None and bool(native)
-        sel = np.asarray(select.cpu().numpy() if isinstance(select, torch.Tensor) else select)
-        if sel.ndim != 1 or sel.size < 1 or sel.dtype.kind not in "iu":
-            raise ValueError("overlay: select must be a non-empty sequence of frame indices")
-        if sel.min() < 0 or sel.max() >= B:
-            raise ValueError(f"overlay: frame index outside [0, {B})")
-        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        sel = _select("overlay", select, B)
         n_sel = int(sel.size)
         mode_i = _ov.MODES.get(mode, mode) if isinstance(mode, str) else mode
         if mode_i not in (_ov.DRAW, _ov.BLEND, _ov.BOTH):
@@ -881,10 +873,7 @@ class Engine:
                 raise ValueError(f"overlay: the out table holds {out_table.total_bytes} bytes, {out_bytes} expected")
             if annotated is not None and not (annotated.is_contiguous() and annotated.device == dev):
                 raise ValueError("overlay: annotated must be a contiguous buffer on the outputs' device")
-            if "buf" not in r:
-                r["buf"] = torch.empty(out_table.total_bytes, dtype=torch.uint8, device=dev)
-            self._check_frames(out_table, buf=r["buf"])
-            r.update(table=out_table, shapes=list(shapes), byte_offsets=list(out_table.byte_offsets))
+            self._selection_out(r, out_table, shapes, dev)
             need = int(lib().vti_overlay_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
             if need <= 0:
                 raise ValueError(f"overlay: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
@@ -898,10 +887,7 @@ class Engine:
             need = self.overlay_scratch_bytes(n_sel, max_det, H0, W0, max_points)
             if need <= 0:
                 raise ValueError(f"overlay: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
-        ws = getattr(self, "_overlay_ws", None)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            self._overlay_ws = None
-            ws = self._overlay_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._scratch("_overlay_ws", need, dev)
         dev_sel = torch.from_numpy(sel).to(dev)
         have_masks = capacity and (not ragged or int(capacity_bytes))
         tail = (_ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
