@@ -682,6 +682,62 @@ int32_t vti_encode_jpeg_frames(vti_ctx* ctx, const uint8_t* dev_frames, const vo
                                int32_t rgb, int32_t quality, void* dev_scratch, size_t scratch_bytes, int64_t* dev_byte_offsets,
                                uint8_t* dev_out, int64_t max_bytes, void* stream);
 
+/* ---- the text of the annotated pictures on device (cv2.putText: measurement.py:282, 333, 366-368, 501-504; main.py:302-309) ------ */
+/* cv2.putText with the default line type writes ONE solid colour on a set of pixels that does not depend on the picture under it.  The
+ * strings are the host's (they hold the smoothed values), so the host rasterises each string once into a 1-bit STAMP, the stamps
+ * cross to the device, and vti_stamp paints them onto the pictures vti_annotate, vti_annotate_frames or vti_annotate_checker drew,
+ * in place, before vti_encode_jpeg reads them.  The library holds no font: any rasteriser serves (the package's annotate.text_stamps
+ * uses cv2.putText where OpenCV is installed), and the caller's own lines go the same way.
+ * A stamp is a rectangle x, y, w, h of picture `picture`, a BGR colour and h rows of `pitch` 32-bit words in the bit buffer, the
+ * first at word_offset: bit j of word q of row r is pixel (x + 32 q + j, y + r); it is painted when set.  Bits at columns >= w are
+ * ignored, so a row may be padded with anything.  Applying a stamp sets every painted pixel to the colour; the stamps of a picture
+ * are applied in array order, a later one overwrites an earlier one: byte for byte the package's annotate.stamp.
+ * LIMITS: 1 <= n_pictures <= VTI_STAMP_MAX_PICTURES, pictures of 1 <= H0, W0 <= 8192 (vti_annotate's), at most
+ * VTI_STAMP_MAX_PER_PICTURE stamps per picture and VTI_STAMP_MAX_TOTAL in a table (0 is allowed: nothing is painted), pitch <=
+ * VTI_STAMP_MAX_PITCH words, 0 <= n_words <= 2^40. */
+enum { VTI_STAMP_MAX_PICTURES = 4096, VTI_STAMP_MAX_PER_PICTURE = 65536, VTI_STAMP_MAX_TOTAL = 1 << 24, VTI_STAMP_MAX_PITCH = 65536 };
+/* Marks the four entry points of the stamp calls; libvti.so exports them as it does every other. */
+#define VTI_STAMP_API
+typedef struct vti_stamp_desc {
+    int32_t picture;            /* index of the picture, non-decreasing along the array */
+    int32_t x, y, w, h;         /* the rectangle: w, h >= 1, inside the picture */
+    int32_t pitch;              /* 32-bit words per row, >= ceil(w / 32) */
+    uint8_t bgr[4];             /* B, G, R; the fourth byte is ignored */
+    int32_t reserved;
+    int64_t word_offset;        /* of row 0 in the bit buffer; word_offset + h * pitch <= n_words */
+} vti_stamp_desc;
+/* Host only: bytes of a stamp table (0 when a count is outside the limits): a header, a range of stamps per picture, a record per
+ * stamp; the format is private to the library build. */
+VTI_STAMP_API int64_t vti_stamp_table_bytes(int32_t n_pictures, int32_t n_stamps);
+/* Host only: validates the n_stamps stamps against the pictures' sizes H0[k], W0[k] and the length n_words of the bit buffer and writes
+ * the table (nbytes >= vti_stamp_table_bytes()).  Refused with VTI_ERR_ARG, vti_last_error naming the stamp's index (ctx only receives
+ * the text and may be NULL): picture outside [0, n_pictures) or smaller than the previous stamp's; w or h < 1; a rectangle that is
+ * not inside its picture; pitch < ceil(w / 32) or above the limit; word_offset < 0 or word_offset + h * pitch > n_words; more stamps
+ * in one picture or in the table than the limits allow.  stamps may be NULL when n_stamps is 0.  Equal inputs give equal bytes. */
+VTI_STAMP_API int32_t vti_pack_stamps(vti_ctx* ctx, const int32_t* H0, const int32_t* W0, int32_t n_pictures,
+                                      const vti_stamp_desc* stamps, int32_t n_stamps, int64_t n_words, void* host_table, size_t nbytes);
+/* Paints the table's stamps onto dev_pictures u8 [n,H0,W0,3] in place.  host_table: the whole table vti_pack_stamps wrote for these n
+ * pictures of H0 x W0 and this n_words; dev_table: its device copy (16-byte aligned); dev_bits: u32 [n_words] on the device (4-byte
+ * aligned; may be NULL when the table has no stamp).  A byte that no set bit covers keeps its value and is not even read; a picture
+ * without stamps costs no picture traffic, and a table without stamps launches nothing.  Every argument check -- the host table
+ * revalidated header, ranges and record by record, the sizes compared with H0, W0 (VTI_ERR_ARG naming the stamp or the picture) --
+ * runs before the first HIP call; ctx, device and weights rules as vti_encode_jpeg (no weights needed).  The device copies are trusted
+ * to hold the same bytes, as a frame table's copy is; the kernel still clamps every rectangle to its picture, every word address to
+ * [0, n_words) and every record index to the table, so a device table that differs may paint wrong pixels of the pictures but
+ * touches no byte outside them and reads nothing outside the bit buffer and the table.  One launch on `stream` (a workgroup per
+ * 8192 pixels of a picture; one that no stamp of its picture reaches leaves after reading the records), no scratch, no memset, no
+ * atomics on the pictures, no host synchronisation: annotate -> stamp -> encode may be captured in one graph. */
+VTI_STAMP_API int32_t vti_stamp(vti_ctx* ctx, uint8_t* dev_pictures, int32_t n, int32_t H0, int32_t W0, const void* host_table,
+                                const void* dev_table, const uint32_t* dev_bits, int64_t n_words, void* stream);
+/* vti_stamp for pictures of differing sizes: dev_buf and the frame table pair are what vti_annotate_frames returned (its dev_out and
+ * out table; any flat buffer with its frame table serves), picture k being frame k.  Picture k comes out byte for byte as vti_stamp
+ * gives it at that picture's size; the gaps between the pictures and the bytes past the last one are never written.  The frame table
+ * is checked as by every *_frames call, and the sizes in the stamp table must equal its rows (VTI_ERR_ARG naming k otherwise); a
+ * picture above 8192 in either dimension is refused.  dev_buf 16-byte aligned.  Everything else is vti_stamp's. */
+VTI_STAMP_API int32_t vti_stamp_frames(vti_ctx* ctx, uint8_t* dev_buf, const void* host_frame_table, const void* dev_frame_table,
+                                       int32_t n, const void* host_table, const void* dev_table, const uint32_t* dev_bits,
+                                       int64_t n_words, void* stream);
+
 /* ---- JPEG files -> frames on device (cap.read() of a motion-JPEG camera, cv2.imread, Ultralytics' file sources) ----------------- */
 /* n files -> n frames u8 [H0,W0,3], byte for byte the package's jpeg.decode, which is pinned to libjpeg-turbo's output with its
  * defaults (JDCT_ISLOW, fancy upsampling): jdhuff.c, jidctint.c with the dequantisation inside, jdsample.c, jdcolor.c; integer

@@ -45,6 +45,12 @@ class VtiCheckerParams(C.Structure):
                 ("skip_cluster", C.c_int32), ("kmeans_iters", C.c_int32), ("drop_empty", C.c_int32), ("frame_buffer", C.c_int32)]
 
 
+class VtiStampDesc(C.Structure):
+    """include/vti.h vti_stamp_desc."""
+    _fields_ = [("picture", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("pitch", C.c_int32),
+                ("bgr", C.c_uint8 * 4), ("reserved", C.c_int32), ("word_offset", C.c_int64)]
+
+
 VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_BAD_CAMERA = 0, 1, 2, 3
 VTI_STITCH_KEPT, VTI_STITCH_MASK, VTI_STITCH_SELECTED, VTI_STITCH_NEAR, VTI_STITCH_DIST, VTI_STITCH_WIDTH = 1, 2, 4, 8, 16, 32
 VTI_MEASURE_MAX_DET = 1000
@@ -56,6 +62,7 @@ VTI_OVERLAY_DRAW, VTI_OVERLAY_BLEND, VTI_OVERLAY_BOTH = 1, 2, 3
 VTI_OVERLAY_OUTLINE_SKIPPED = 1
 VTI_JPEG_CORRUPT = 1
 VTI_RAW_YUYV, VTI_RAW_UYVY, VTI_RAW_NV12, VTI_RAW_NV21, VTI_RAW_I420, VTI_RAW_YV12 = range(6)
+VTI_STAMP_MAX_PICTURES, VTI_STAMP_MAX_PER_PICTURE, VTI_STAMP_MAX_TOTAL, VTI_STAMP_MAX_PITCH = 4096, 65536, 1 << 24, 65536
 VTI_ERR_ARG, VTI_ERR_UNSUPPORTED = -1, -6
 
 
@@ -148,6 +155,10 @@ SIGNATURES = {
     "vti_encode_jpeg_frames_scratch_bytes": (_I64, [_P, _P]),
     "vti_encode_jpeg_frames_max_bytes": (_I64, [_P]),
     "vti_encode_jpeg_frames": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
+    "vti_stamp_table_bytes": (_I64, [_I32, _I32]),
+    "vti_pack_stamps": (_I32, [_P, _P, _P, _I32, _P, _I32, _I64, _P, _SZ]),
+    "vti_stamp": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+    "vti_stamp_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _P, _P, _I64, _P]),
     "vti_decode_jpeg_table_bytes": (_I64, [_I32]),
     "vti_decode_jpeg_plan": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     "vti_decode_jpeg": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),

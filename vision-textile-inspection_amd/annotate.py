@@ -14,6 +14,10 @@ pinned by closed-form cases in tests/test_annotate.py and compared with cv2 wher
 Text stays on the host: the strings hold the smoothed values of the host's deques and need OpenCV's Hershey glyphs.  `text_items`
 returns what the reference passes to cv2.putText, `put_text` draws it when cv2 is importable.  One deviation: the reference draws a
 stitch's width label before the next stitch's markers, so a later marker can cover an earlier label; here all text comes last.
+
+Text IN the picture on the device: `text_stamps` rasterises each item once on the host into a 1-bit stamp (cv2.putText where OpenCV
+is installed, or any rasteriser the caller passes), libvti's vti_stamp paints the stamps onto the drawn pictures before they are
+copied or encoded (process_frames(..., burn_text=True)); `stamp` is the numpy statement of what it paints.
 """
 import math
 
@@ -591,3 +595,64 @@ def put_text(img, items):
     for text, org, face, scale, colour, thickness in items:
         cv2.putText(img, text, org, getattr(cv2, face), scale, colour, thickness)
     return img
+
+
+# ---- text as 1-bit stamps: what vti_stamp paints ------------------------------------------------------------------------------
+_CANVASES = {}          # (h, w) -> the zero uint8 canvas of that frame size (the 4 latest sizes)
+
+
+def cv2_rasterise(canvas, item):
+    """The default rasteriser of text_stamps: the item drawn with cv2.putText, default line type, in 255.  ImportError without OpenCV."""
+    import cv2
+    text, org, face, scale, _, thickness = item
+    cv2.putText(canvas, text, org, getattr(cv2, face), scale, 255, thickness)
+
+
+def text_stamps(items, h, w, rasterise=None):
+    """The items of text_items / checker_text_items (and any further ones of the same form) for one picture of h x w, each as a
+    stamp (x, y, bits, colour): bits bool [bh, bw] with its top-left corner at picture pixel (x, y), colour the item's BGR triple.
+    `rasterise(canvas, item)` draws the item in any non-zero value onto a zero uint8 [h, w] canvas -- the size of the picture, so that
+    it clips exactly as it would on the picture; the stamp is the bounding box of what it drew, and an item that drew nothing gives no
+    stamp.  Default: cv2_rasterise (ImportError where OpenCV is not installed, as put_text).  The pixel set of putText with the
+    default line type does not depend on the picture under it, so stamp(picture, text_stamps(items, h, w)) is put_text(picture,
+    items).  One canvas is kept per frame size and cleared only where an item drew."""
+    if rasterise is None:
+        import cv2  # noqa: F401  (the ImportError comes before anything is drawn)
+        rasterise = cv2_rasterise
+    h, w = int(h), int(w)
+    canvas = _CANVASES.pop((h, w), None)
+    if canvas is None:
+        canvas = np.zeros((h, w), np.uint8)
+        while len(_CANVASES) >= 4:
+            del _CANVASES[next(iter(_CANVASES))]
+    _CANVASES[(h, w)] = canvas
+    stamps = []
+    try:
+        for item in items:
+            rasterise(canvas, item)
+            rows = np.flatnonzero(canvas.any(axis=1))
+            if rows.size == 0:
+                continue
+            y0, y1 = int(rows[0]), int(rows[-1]) + 1
+            cols = np.flatnonzero(canvas[y0:y1].any(axis=0))
+            x0, x1 = int(cols[0]), int(cols[-1]) + 1
+            box = canvas[y0:y1, x0:x1]
+            stamps.append((x0, y0, box != 0, tuple(int(v) for v in item[4][:3])))
+            box[...] = 0
+    except BaseException:
+        canvas[...] = 0         # a rasteriser that raised may have drawn: the kept canvas is zero again
+        raise
+    return stamps
+
+
+def stamp(picture, stamps):
+    """The specification of vti_stamp, in place: for every stamp (x, y, bits, colour) in list order, picture[y + r, x + c] = colour
+    wherever bits[r, c] is set (a later stamp overwrites an earlier one).  picture: uint8 [h, w, 3]; a stamp lies inside it.
+    -> picture."""
+    for x, y, bits, colour in stamps:
+        bits = np.asarray(bits, dtype=bool)
+        bh, bw = bits.shape
+        if x < 0 or y < 0 or y + bh > picture.shape[0] or x + bw > picture.shape[1]:
+            raise ValueError(f"stamp: a {bh} x {bw} stamp at ({x}, {y}) is not inside the {picture.shape[0]} x {picture.shape[1]} picture")
+        picture[y:y + bh, x:x + bw][bits] = colour
+    return picture

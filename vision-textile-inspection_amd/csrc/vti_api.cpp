@@ -1570,6 +1570,161 @@ int32_t vti_encode_jpeg_frames(vti_ctx* c, const uint8_t* frames, const void* ho
     return VTI_OK;
 }
 
+// ---- the text of the annotated pictures: the stamp table, vti_stamp, vti_stamp_frames -------------------------------------------
+int64_t vti_stamp_table_bytes(int32_t n_pictures, int32_t n_stamps) {
+    if (n_pictures < 1 || n_pictures > VTI_STAMP_MAX_PICTURES || n_stamps < 0 || n_stamps > VTI_STAMP_MAX_TOTAL) return 0;
+    return (int64_t)sizeof(StampHeader) + (int64_t)n_pictures * (int64_t)sizeof(StampPicture) + (int64_t)n_stamps * (int64_t)sizeof(StampRec);
+}
+
+// What is wrong with one stamp of a picture of H0 x W0 and a bit buffer of n_words words (nullptr: nothing).  vti_pack_stamps runs it
+// on its arguments, vti_stamp and vti_stamp_frames on every record of the host table they are given.
+static const char* stamp_error(int32_t H0, int32_t W0, const StampRec& r, int64_t n_words) {
+    if (r.w < 1 || r.h < 1) return "w and h must be >= 1";
+    if (r.x < 0 || r.y < 0 || r.x > W0 - r.w || r.y > H0 - r.h) return "the rectangle is not inside its picture";
+    if (r.pitch < (r.w + 31) / 32) return "pitch must be >= ceil(w / 32)";
+    if (r.pitch > VTI_STAMP_MAX_PITCH) return "pitch must be <= VTI_STAMP_MAX_PITCH";
+    if (r.offset < 0 || r.offset > n_words || (int64_t)r.h * r.pitch > n_words - r.offset) return "its rows run past n_words (or word_offset < 0)";
+    return nullptr;
+}
+
+static bool stamp_picture_ok(int32_t H0, int32_t W0) { return H0 >= 1 && W0 >= 1 && H0 <= kStampMaxSide && W0 <= kStampMaxSide; }
+
+int32_t vti_pack_stamps(vti_ctx* c, const int32_t* H0, const int32_t* W0, int32_t n_pictures, const vti_stamp_desc* stamps,
+                        int32_t n_stamps, int64_t n_words, void* host_table, size_t nbytes) {
+    const char* fn = "vti_pack_stamps";
+    char msg[200];
+    if (!H0 || !W0 || !host_table || (n_stamps > 0 && !stamps)) return refuse(c, fn, "null array or table");
+    if (n_pictures < 1 || n_pictures > VTI_STAMP_MAX_PICTURES) return refuse(c, fn, "1 <= n_pictures <= VTI_STAMP_MAX_PICTURES");
+    if (n_stamps < 0 || n_stamps > VTI_STAMP_MAX_TOTAL) return refuse(c, fn, "0 <= n_stamps <= VTI_STAMP_MAX_TOTAL");
+    if (n_words < 0 || n_words > kStampMaxWords) return refuse(c, fn, "0 <= n_words <= 2^40");
+    if ((int64_t)nbytes < vti_stamp_table_bytes(n_pictures, n_stamps)) return refuse(c, fn, "table smaller than vti_stamp_table_bytes()");
+    for (int32_t k = 0; k < n_pictures; ++k)
+        if (!stamp_picture_ok(H0[k], W0[k])) {
+            snprintf(msg, sizeof msg, "%s: picture %d: 1 <= H0, W0 <= 8192", fn, k);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    StampHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = kStampTableMagic; h.n_pictures = n_pictures; h.n_stamps = n_stamps; h.n_words = n_words;
+    char* pics = (char*)host_table + sizeof h;
+    char* recs = pics + (size_t)n_pictures * sizeof(StampPicture);
+    int32_t k = 0, begin = 0;               // the picture whose range is open, and where it began
+    auto close = [&](int32_t end) {
+        const StampPicture p{H0[k], W0[k], begin, end};
+        memcpy(pics + (size_t)k * sizeof p, &p, sizeof p);
+        ++k; begin = end;
+    };
+    for (int32_t i = 0; i < n_stamps; ++i) {
+        const vti_stamp_desc& s = stamps[i];
+        auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: stamp %d: %s", fn, i, what); return fail(c, VTI_ERR_ARG, msg); };
+        if (s.picture < 0 || s.picture >= n_pictures) return bad("picture outside [0, n_pictures)");
+        if (s.picture < k) return bad("picture must not decrease along the array");
+        while (k < s.picture) close(i);
+        StampRec r;
+        memset(&r, 0, sizeof r);
+        r.offset = s.word_offset; r.x = s.x; r.y = s.y; r.w = s.w; r.h = s.h; r.pitch = s.pitch;
+        r.colour = (unsigned)s.bgr[0] | (unsigned)s.bgr[1] << 8 | (unsigned)s.bgr[2] << 16;
+        if (const char* e = stamp_error(H0[k], W0[k], r, n_words)) return bad(e);
+        if (i - begin >= VTI_STAMP_MAX_PER_PICTURE) return bad("more than VTI_STAMP_MAX_PER_PICTURE stamps in its picture");
+        memcpy(recs + (size_t)i * sizeof r, &r, sizeof r);
+    }
+    while (k < n_pictures) close(n_stamps);
+    memcpy(host_table, &h, sizeof h);
+    return VTI_OK;
+}
+
+// The checks vti_stamp and vti_stamp_frames make on their stamp table pair and bit buffer: the host copy is a table of
+// vti_pack_stamps for n pictures and this n_words whose ranges and records still pass, picture k having the size of row k of the
+// (checked) host frame table, or H0 x W0 when there is none.
+static int32_t stamps_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, const uint32_t* bits, int32_t n,
+                            int64_t n_words, StampHeader& h, int32_t H0, int32_t W0, const void* host_frame_table) {
+    char msg[240];
+    if (!host_table || !dev_table) return refuse(c, fn, "null stamp table (host copy or device copy)");
+    if ((uintptr_t)dev_table & 15) return refuse(c, fn, "the device stamp table must be 16-byte aligned");
+    if ((uintptr_t)bits & 3) return refuse(c, fn, "dev_bits must be 4-byte aligned");
+    memcpy(&h, host_table, sizeof h);
+    if (h.magic != kStampTableMagic) return refuse(c, fn, "host_table is not a table of vti_pack_stamps");
+    if (h.n_pictures != n) return refuse(c, fn, "the stamp table was packed for another number of pictures");
+    if (h.n_stamps < 0 || h.n_stamps > VTI_STAMP_MAX_TOTAL || h.n_words < 0 || h.n_words > kStampMaxWords)
+        return refuse(c, fn, "host_table is not a table of vti_pack_stamps");
+    if (h.n_words != n_words) return refuse(c, fn, "the stamp table was packed for another n_words");
+    if (h.n_stamps > 0 && !bits) return refuse(c, fn, "null dev_bits");
+    const char* pics = (const char*)host_table + sizeof h;
+    const char* recs = pics + (size_t)n * sizeof(StampPicture);
+    int32_t at = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        StampPicture p;
+        memcpy(&p, pics + (size_t)k * sizeof p, sizeof p);
+        if (host_frame_table) {
+            const FrameRow fr = table_row(host_frame_table, k);
+            H0 = fr.H0; W0 = fr.W0;
+        }
+        if (p.H0 != H0 || p.W0 != W0) {
+            snprintf(msg, sizeof msg, "%s: picture %d of the stamp table is %d x %d, the call's is %d x %d", fn, k, p.H0, p.W0, H0, W0);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+        if (p.begin != at || p.end < p.begin || p.end > h.n_stamps || p.end - p.begin > VTI_STAMP_MAX_PER_PICTURE) {
+            snprintf(msg, sizeof msg, "%s: picture %d of host_table: its range of stamps is not the one vti_pack_stamps wrote", fn, k);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+        for (int32_t i = p.begin; i < p.end; ++i) {
+            StampRec r;
+            memcpy(&r, recs + (size_t)i * sizeof r, sizeof r);
+            if (const char* e = stamp_error(H0, W0, r, n_words)) {
+                snprintf(msg, sizeof msg, "%s: stamp %d of host_table: %s", fn, i, e);
+                return fail(c, VTI_ERR_ARG, msg);
+            }
+        }
+        at = p.end;
+    }
+    if (at != h.n_stamps) return refuse(c, fn, "host_table: the pictures' ranges do not cover its stamps");
+    return VTI_OK;
+}
+
+int32_t vti_stamp(vti_ctx* c, uint8_t* pictures, int32_t n, int32_t H0, int32_t W0, const void* host_table, const void* dev_table,
+                  const uint32_t* bits, int64_t n_words, void* stream) {
+    // every check comes before the first HIP call
+    const char* fn = "vti_stamp";
+    if (!c) return refuse(c, fn, "null ctx");
+    if (n < 1 || n > VTI_STAMP_MAX_PICTURES || !stamp_picture_ok(H0, W0))
+        return refuse(c, fn, "bad size (1 <= n <= VTI_STAMP_MAX_PICTURES; 1 <= H0, W0 <= 8192)");
+    if (!pictures) return refuse(c, fn, "null pointer");
+    StampHeader h;
+    VTI_TRY(stamps_check(fn, c, host_table, dev_table, bits, n, n_words, h, H0, W0, nullptr));
+    VTI_TRY(check_device(c, fn));
+    VTI_HIP(c, launch_stamp(pictures, n, H0, W0, nullptr, 0, (long long)H0 * W0, dev_table, h.n_stamps, bits, n_words, (hipStream_t)stream),
+            "stamp kernel");
+    return VTI_OK;
+}
+
+int32_t vti_stamp_frames(vti_ctx* c, uint8_t* buf, const void* host_frame_table, const void* dev_frame_table, int32_t n,
+                         const void* host_table, const void* dev_table, const uint32_t* bits, int64_t n_words, void* stream) {
+    // every check comes before the first HIP call
+    const char* fn = "vti_stamp_frames";
+    if (!c) return refuse(c, fn, "null ctx");
+    FrameTableHeader fh;
+    VTI_TRY(frames_check(fn, c, host_frame_table, dev_frame_table, n, fh));
+    if (n > VTI_STAMP_MAX_PICTURES) return refuse(c, fn, "bad size (1 <= n <= VTI_STAMP_MAX_PICTURES)");
+    if (!buf) return refuse(c, fn, "null pointer");
+    if ((uintptr_t)buf & 15) return refuse(c, fn, "dev_buf must be 16-byte aligned");
+    long long max_px = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        const FrameRow r = table_row(host_frame_table, k);
+        if (!stamp_picture_ok(r.H0, r.W0)) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "%s: frame %d is %d x %d; a stamped picture is at most 8192 x 8192", fn, k, r.H0, r.W0);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+        max_px = std::max(max_px, (long long)r.H0 * r.W0);
+    }
+    StampHeader h;
+    VTI_TRY(stamps_check(fn, c, host_table, dev_table, bits, n, n_words, h, 0, 0, host_frame_table));
+    VTI_TRY(check_device(c, fn));
+    VTI_HIP(c, launch_stamp(buf, n, std::min(fh.max_H0, kStampMaxSide), std::min(fh.max_W0, kStampMaxSide), frame_rows(dev_frame_table),
+                            fh.total_bytes, max_px, dev_table, h.n_stamps, bits, n_words, (hipStream_t)stream), "stamp kernel");
+    return VTI_OK;
+}
+
 int64_t vti_decode_jpeg_table_bytes(int32_t n) {
     return n < 1 || n > kJpegDecMaxFiles ? 0 : (int64_t)sizeof(JpegDecHeader) + (int64_t)n * (int64_t)sizeof(JpegDecRow);
 }

@@ -383,6 +383,31 @@ hipError_t launch_annotate_checker(const vti_checker_params& p, const uint8_t* f
                                    const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
                                    void* scratch, hipStream_t st);
 
+// stamp.hip: vti_stamp / vti_stamp_frames (the text of the annotated pictures as 1-bit stamps).  The stamp table, host and device
+// copy alike: the header | n_pictures picture rows | n_stamps records.  Picture k owns the records [begin, end); the ranges follow each
+// other without a gap, so that the records are in picture order and, within a picture, in painting order.
+constexpr int kStampTableMagic = 0x31545356;    // "VST1"
+constexpr int kStampMaxSide = 8192;             // vti_annotate's limit
+constexpr int kStampMaxPitch = 65536;           // words per stamp row
+constexpr long long kStampMaxWords = 1ll << 40;
+struct StampHeader {
+    int magic, n_pictures, n_stamps, pad0;
+    long long n_words;          // of the bit buffer the records were checked against
+    int pad[10];
+};
+static_assert(sizeof(StampHeader) == 64, "the rows of a stamp table stay 16-byte aligned");
+struct StampPicture { int H0, W0, begin, end; };
+struct StampRec {
+    long long offset;           // of the stamp's first word in the bit buffer
+    int x, y, w, h, pitch;      // the rectangle in its picture; words per row
+    unsigned colour;            // B | G << 8 | R << 16
+};
+static_assert(sizeof(StampPicture) == 16 && sizeof(StampRec) == 32, "a stamp record is two 16-byte vectors");
+// pictures: u8 [n,H0,W0,3], or with `rows` (the device frame table's rows) the flat buffer of `total_bytes` bytes whose frame k is
+// picture k (H0, W0 are then the largest frame's, max_px the most pixels a frame has).  table: the device copy of the stamp table.
+hipError_t launch_stamp(uint8_t* pictures, int n, int H0, int W0, const FrameRow* rows, long long total_bytes, long long max_px,
+                        const void* table, int n_stamps, const uint32_t* bits, long long n_words, hipStream_t st);
+
 // overlay.hip: vti_overlay (the model-check viewer's picture).  The scratch holds: 16 ints of counters per selected frame | the contour
 // vertices int4 [n_sel, max_points] | the owner planes (8 words per 32-bit mask word, for the larger of a native and a letterbox mask
 // slot) per selected frame | min(max_det, 16) labelling areas per selected frame (parent | runs | row_start as polygons.hip's, then

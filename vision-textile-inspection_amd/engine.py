@@ -114,6 +114,16 @@ class RawTable:
         return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
 
 
+class StampTable:
+    """A packed stamp table (vti_pack_stamps): `host` (the packed bytes, a CPU u8 tensor), `dev` (their device copy), `bits` (the
+    device bit buffer, u32 as int32 [n_words]), the pictures' `shapes` [(H0, W0)] and the number of stamps `n_stamps`."""
+
+    def __init__(self, host, dev, bits, n_words, shapes, n_stamps):
+        self.host, self.dev, self.bits, self.n_words, self.shapes, self.n_stamps = host, dev, bits, n_words, shapes, n_stamps
+        self.n = len(shapes)
+        self.up_bytes = host.numel() + 4 * n_words      # what crossed to the device
+
+
 class Engine:
     """One (model description, input size, max batch, dtype) context."""
 
@@ -970,6 +980,75 @@ class Engine:
         if total > max_bytes:                           # nothing was written: run again with exactly the room the files need
             out = launch(total)
         return out, offsets
+
+    # ---- the text of the annotated pictures (cv2.putText): vti_pack_stamps, vti_stamp, vti_stamp_frames -------------------------
+    def pack_stamps(self, stamps_per_picture, shapes, device=None, pitch_extra=0, pad_fill=0):
+        """stamps_per_picture: per picture the list of stamps (x, y, bits bool [h, w], BGR colour) of annotate.text_stamps, in painting
+        order; shapes: the pictures' (H0, W0).  Packs the rows of every stamp into 32-bit words (bit j of word q of a row: column
+        32 q + j), validates and packs the stamp table (vti_pack_stamps: a VtiError names the failing stamp) and uploads both, one
+        copy each.  -> StampTable (host, dev, bits).  pitch_extra: words added to every row's pitch; pad_fill: the 32-bit pattern the
+        bits at columns >= w are filled with (they are ignored)."""
+        shapes = [(int(h), int(w)) for h, w in (tuple(x)[:2] for x in shapes)]
+        if len(stamps_per_picture) != len(shapes) or not shapes:
+            raise ValueError(f"pack_stamps: {len(stamps_per_picture)} lists of stamps for {len(shapes)} pictures (at least one)")
+        descs, words, at = [], [], 0
+        for k, stamps in enumerate(stamps_per_picture):
+            for x, y, bits, colour in stamps:
+                bits = np.asarray(bits, dtype=bool)
+                if bits.ndim != 2 or bits.size == 0:
+                    raise ValueError(f"pack_stamps: picture {k}: a stamp's bits must be a non-empty 2-D array")
+                h, w = bits.shape
+                pitch = (w + 31) // 32 + int(pitch_extra)
+                row = np.zeros((h, pitch * 32), dtype=bool)
+                if pad_fill:
+                    row[:] = np.tile(np.unpackbits(np.array([pad_fill], dtype="<u4").view(np.uint8), bitorder="little"), pitch)[None]
+                row[:, :w] = bits
+                words.append(np.packbits(row, axis=1, bitorder="little").view("<u4").reshape(-1))
+                b, g, r = (int(v) for v in colour[:3])
+                descs.append(_lib.VtiStampDesc(k, int(x), int(y), w, h, pitch, (C.c_uint8 * 4)(b, g, r, 0), 0, at))
+                at += h * pitch
+        n, ns = len(shapes), len(descs)
+        nbytes = int(lib().vti_stamp_table_bytes(n, ns))
+        if nbytes <= 0:
+            raise ValueError(f"pack_stamps: {n} pictures and {ns} stamps are outside the limits of vti_stamp_table_bytes()")
+        host = torch.zeros(nbytes, dtype=torch.uint8)
+        H0 = (C.c_int32 * n)(*[h for h, _ in shapes])
+        W0 = (C.c_int32 * n)(*[w for _, w in shapes])
+        arr = (_lib.VtiStampDesc * ns)(*descs) if ns else None
+        check(self._ctx, lib().vti_pack_stamps(self._ctx, H0, W0, n, arr, ns, at, C.c_void_p(host.data_ptr()), nbytes))
+        dev = device or self.device or "cuda"
+        flat = np.concatenate(words).astype("<u4") if words else np.zeros(0, "<u4")
+        bits_dev = torch.from_numpy(flat.view(np.int32)).to(dev) if at else None
+        return StampTable(host, host.to(dev), bits_dev, at, shapes, ns)
+
+    def stamp(self, frames_or_buf, packed, table=None):
+        """Paints the stamps of `packed` (pack_stamps) onto the pictures, in place, byte for byte annotate.stamp per picture:
+        vti_stamp on a contiguous uint8 [n,H0,W0,3] device tensor (annotate()'s "frames"), or with table= (the FrameTable of
+        annotate(..., table=)) vti_stamp_frames on its flat buffer.  One launch on the current stream, no host synchronisation;
+        a byte that no stamp covers is not touched.  -> frames_or_buf."""
+        if not isinstance(packed, StampTable):
+            raise ValueError("stamp: packed must be the StampTable of Engine.pack_stamps()")
+        t = frames_or_buf
+        if table is not None:
+            self._check_frames(table, B=packed.n)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1:
+                raise ValueError("stamp: with table=, the pictures must be the flat uint8 buffer")
+            shapes = [tuple(x) for x in table.shapes]
+        else:
+            n, H0, W0 = _uniform_frames("stamp", t)
+            shapes = [(int(H0), int(W0))] * int(n)
+        if shapes != [tuple(x) for x in packed.shapes]:
+            raise ValueError("stamp: the stamps were packed for pictures of other sizes (or another number of them)")
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("stamp: the pictures must be a contiguous device tensor")
+        if table is not None:
+            self._check_frames(table, buf=t)
+            check(self._ctx, lib().vti_stamp_frames(self._ctx, _ptr(t), *table._ptrs(), packed.n, C.c_void_p(packed.host.data_ptr()),
+                                                    _ptr(packed.dev), _ptr(packed.bits), packed.n_words, _stream()))
+        else:
+            check(self._ctx, lib().vti_stamp(self._ctx, _ptr(t), packed.n, shapes[0][0], shapes[0][1], C.c_void_p(packed.host.data_ptr()),
+                                             _ptr(packed.dev), _ptr(packed.bits), packed.n_words, _stream()))
+        return t
 
     # ---- JPEG files -> frames (cap.read() of a motion-JPEG camera, cv2.imread): vti_decode_jpeg ------------------------------
     def decode_jpeg_plan(self, files, dense=None, segment_bytes=0, stage=None):

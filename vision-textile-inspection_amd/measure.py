@@ -17,9 +17,12 @@ The annotated frame the reference also returns is drawn on request, for a select
 vti_annotate paints the overlay on the device batch predict consumed and the selected pictures come back in one copy; the text
 (which holds the smoothed values) is returned as annotate.text_items and drawn by annotate.put_text where OpenCV is installed.
 With `encode="jpeg"` the selected pictures are also encoded on the device (vti_encode_jpeg: the file cv2.imwrite would save of that
-picture, jpeg.py) and only the files' bytes come back; the text still rides along as text_items, it is not in the JPEG.
+picture, jpeg.py) and only the files' bytes come back; the text still rides along as text_items; it is in the JPEG only with burn_text (below).
 With `mixed=True` both also serve a list of frames whose sizes differ (vti_annotate_frames, vti_encode_jpeg_frames): every selected
 frame is drawn and encoded at its own size, and the pictures or files still come back in one copy.
+With `burn_text=True` the text IS in the pictures and files: the host rasterises each string once into a 1-bit stamp
+(annotate.text_stamps), the stamps cross to the device and vti_stamp paints them onto the drawn pictures before they are copied or
+encoded; `extra_text` adds the caller's own lines (main.py:302-309) the same way.
 """
 import ctypes as C
 import dataclasses
@@ -165,22 +168,57 @@ class CameraStream:
 
 
 def _mixed_keyword(public):
-    """process_frames' keyword-only `mixed`.  `public` carries the signature and the documentation -- its parameter list, which ends
+    """process_frames' keyword-only `mixed`, `burn_text`, `extra_text` and `rasterise`.  `public` carries the signature and the documentation -- its parameter list, which ends
     in annotate, encode, jpeg_quality for positional callers and for inspect.signature, stays as it was -- and the work is in the
-    class's _process_frames, which takes the same parameters by name and `mixed` next to them: an argument all the way down, no
-    state on the measurer."""
+    class's _process_frames, which takes the same parameters by name and the keyword-only ones next to them: arguments all the way
+    down, no state on the measurer."""
     sig = inspect.signature(public)
 
     @functools.wraps(public)
-    def process_frames(self, *args, mixed=False, **kw):
+    def process_frames(self, *args, mixed=False, burn_text=False, extra_text=None, rasterise=None, **kw):
         if not isinstance(mixed, (bool, np.bool_)):
             raise ValueError(f"process_frames: mixed must be True or False, got {mixed!r}")
         bound = sig.bind(self, *args, **kw)             # a TypeError for a bad call, as calling `public` would give
         bound.apply_defaults()
         named = dict(bound.arguments)
         del named["self"]
-        return self._process_frames(mixed=bool(mixed), **named)
+        return self._process_frames(mixed=bool(mixed), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, **named)
     return process_frames
+
+
+class _Deferred(list):
+    """[(frame index, None, per-slot rows)] of a selection whose drawn pictures wait on the device for their text (burn_text): the
+    strings hold the smoothed values, which exist once the records are built.  shapes[k]: picture k's (H0, W0); finish(stamps per
+    picture) paints them (vti_stamp) and returns the pictures, or with encode the files, as _annotated would have."""
+    shapes = finish = None
+
+
+def _burn_refusals(annotate, burn_text, extra_text, rasterise):
+    """What process_frames refuses about the text in the pictures, before anything is predicted."""
+    if burn_text and annotate is None:
+        raise ValueError("process_frames: burn_text needs annotate (the text is burned into the annotated selection)")
+    if extra_text is not None and not burn_text:
+        raise ValueError("process_frames: extra_text needs burn_text=True (without it the text stays with the caller)")
+    if burn_text and rasterise is None:
+        import cv2  # noqa: F401  (ImportError: no OpenCV and no rasteriser of the caller's)
+
+
+def _extra_items(extra_text, b, record):
+    """The caller's own items for frame b: extra_text[b], or extra_text(b, record) when it is callable (a line that quotes the record
+    this very call built, as main.py:297-309 does)."""
+    if extra_text is None:
+        return []
+    return list(extra_text(b, record) if callable(extra_text) else extra_text.get(b, []))
+
+
+def _burned(annotated, items, rasterise):
+    """annotated with the items of picture k burned into it: [(frame index, picture or file, items[k])].  Without burn_text the
+    pictures are already there and nothing is painted."""
+    if isinstance(annotated, _Deferred):
+        pics = annotated.finish([_annotate.text_stamps(it, h, w, rasterise) for it, (h, w) in zip(items, annotated.shapes)])
+    else:
+        pics = [pic for _, pic, _ in annotated]
+    return [(a[0], pic, it) for a, pic, it in zip(annotated, pics, items)]
 
 
 class _DeviceStage:
@@ -198,12 +236,13 @@ class _DeviceStage:
 
     @torch.inference_mode()
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
-                       jpeg_quality=95, mixed=False, rows=False):
+                       jpeg_quality=95, mixed=False, rows=False, burn_text=False, extra_text=None, rasterise=None):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
         selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0 (frames of
         differing sizes, which `mixed` allows with annotate: the list of every frame's H0).  params /
         cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the outputs exist (the
-        camera table needs both).  rows (without annotate): a third item, every frame's per-slot rows as `_slot_rows` gives them."""
+        camera table needs both).  rows (without annotate): a third item, every frame's per-slot rows as `_slot_rows` gives them.
+        burn_text: the third item is a _Deferred -- the pictures are drawn but neither copied nor encoded yet."""
         if encode is not None:
             if encode != "jpeg":
                 raise ValueError(f'process_frames: encode must be None or "jpeg", got {encode!r}')
@@ -211,6 +250,7 @@ class _DeviceStage:
                 raise ValueError("process_frames: encode needs annotate (the frames to encode are the annotated selection)")
             if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, (int, np.integer)) or not 1 <= jpeg_quality <= 100:
                 raise ValueError(f"process_frames: jpeg_quality must be an integer in 1..100, got {jpeg_quality!r}")
+        _burn_refusals(annotate, burn_text, extra_text, rasterise)
         files = self.model._jpeg_files(frames)
         info = None
         if files is not None:       # the batch cap.read() would have delivered: the files decoded to BGR on the device
@@ -264,16 +304,35 @@ class _DeviceStage:
         if sel is None:
             return (f64, i32, self._slot_rows(o, res, np.arange(B))) if rows else (f64, i32)
         got = (f64, i32, self._annotated(eng, o, res, params, cameras, sel, bool(retina_masks),
-                                         int(jpeg_quality) if encode else None, table), H0 if table is None else [h for h, _ in shapes])
+                                         int(jpeg_quality) if encode else None, table, bool(burn_text)),
+               H0 if table is None else [h for h, _ in shapes])
         return got + (self._slot_rows(o, res, np.arange(B)),) if rows else got      # rows next to annotate: a fifth item, every frame's
 
-    def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None, table=None):
+    def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None, table=None, burn=False):
         """vti_annotate on the batch predict consumed; the selected pictures in one device -> host copy, and of the per-slot rows only
         those of the selected frames.  jpeg_quality: the pictures go through vti_encode_jpeg first and the copy is of the files'
         bytes (one read of the offsets, one of out[:offsets[n]]).  table: the FrameTable of a batch whose frames differ in size --
-        vti_annotate_frames and vti_encode_jpeg_frames; the one copy is then of the flat buffer, sliced into [H0, W0, 3] arrays."""
+        vti_annotate_frames and vti_encode_jpeg_frames; the one copy is then of the flat buffer, sliced into [H0, W0, 3] arrays.
+        burn: the pictures stay on the device and the per-slot rows come back in a _Deferred, whose finish() stamps, encodes and
+        copies once the caller has built the text."""
         ann = self._draw(eng, self.model._last_frames, o, res, params, sel, cameras, native, table)
         self.model._last_frames = None            # the launches are enqueued: the batch need not outlive the call
+        if burn:
+            rows = self._slot_rows(o, res, np.unique(sel))
+            later = _Deferred((int(b), None, rows[int(b)]) for b in sel)
+            later.shapes = list(ann["shapes"]) if table is not None else [tuple(int(v) for v in ann["frames"].shape[1:3])] * len(sel)
+            later.finish = lambda stamps: self._pictures(eng, ann, len(sel), jpeg_quality, table, stamps, later.shapes)
+            return later
+        pics = self._pictures(eng, ann, len(sel), jpeg_quality, table)
+        rows = self._slot_rows(o, res, np.unique(sel))
+        return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
+
+    @staticmethod
+    def _pictures(eng, ann, n, jpeg_quality, table, stamps=None, shapes=None):
+        """The n drawn pictures of `ann` on the host (jpeg_quality: their files), with `stamps` (per picture) painted first."""
+        if stamps is not None:
+            pictures = ann["buf"] if table is not None else ann["frames"]
+            eng.stamp(pictures, eng.pack_stamps(stamps, shapes, pictures.device), table=ann["table"] if table is not None else None)
         if jpeg_quality is None and table is not None:
             flat = ann["buf"].cpu().numpy()
             pics = [flat[at:at + 3 * h * w].reshape(h, w, 3) for (h, w), at in zip(ann["shapes"], ann["byte_offsets"])]
@@ -286,9 +345,8 @@ class _DeviceStage:
                 data, off = eng.encode_jpeg(ann["frames"], quality=jpeg_quality)
             off = off.cpu().numpy()
             data = data[:int(off[-1])].cpu().numpy().tobytes()
-            pics = [data[off[k]:off[k + 1]] for k in range(len(sel))]
-        rows = self._slot_rows(o, res, np.unique(sel))
-        return [(int(b), pics[k], rows[int(b)]) for k, b in enumerate(sel)]
+            pics = [data[off[k]:off[k + 1]] for k in range(n)]
+        return pics
 
     def _draw(self, eng, frames, o, res, params, sel, cameras, native, table):
         """The stage's one drawing call on the batch predict consumed (Engine.annotate's contract)."""
@@ -313,15 +371,16 @@ class _DeviceStage:
         return rows
 
     @staticmethod
-    def _with_text(annotated, records, i32, min_stitches, H0):
+    def _with_text(annotated, records, i32, min_stitches, H0, extra_text=None, rasterise=None):
         """[(frame index, picture, rows)] -> [(frame index, picture, text_items)] with the strings built from the frames' records
-        (picture: the BGR ndarray of height H0, or its JPEG file's bytes).  H0: one height, or every frame's own."""
-        out = []
+        (picture: the BGR ndarray of height H0, or its JPEG file's bytes).  H0: one height, or every frame's own.  A _Deferred
+        selection (burn_text) gets its items, followed by extra_text's for that frame, burned in before the pictures come back."""
+        items = []
         for b, pic, rows in annotated:
             rows = dict(rows, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
             h0 = H0[b] if isinstance(H0, (list, tuple)) else H0
-            out.append((b, pic, _annotate.text_items(records[b], rows, h0, min_stitches(b))))
-        return out
+            items.append(_annotate.text_items(records[b], rows, h0, min_stitches(b)) + _extra_items(extra_text, b, records[b]))
+        return _burned(annotated, items, rasterise)
 
 
 class StitchMeasurer(_DeviceStage):
@@ -356,15 +415,23 @@ class StitchMeasurer(_DeviceStage):
         size, a picture is the [H0, W0, 3] ndarray of its frame, and text_items are placed by each frame's own height.  Without it
         such a list with annotate is refused, as before; on frames of one size it changes nothing.  mixed=True also lets
         retina_masks=True measure such a list (vti_predict_frames_native -> vti_measure_frames_native: every frame's masks at its own
-        size); without mixed, or together with annotate, retina_masks=True with differing sizes stays refused."""
+        size); without mixed, or together with annotate, retina_masks=True with differing sizes stays refused.
+        burn_text (keyword only, default False; needs annotate): True burns the text into the selected pictures on the device before
+        they are copied or encoded (annotate.text_stamps -> vti_stamp), so the ndarray, or with encode="jpeg" the file, carries what
+        cv2.putText would have written; the tuple stays (frame index, picture or bytes, items).  extra_text (needs burn_text): {frame
+        index: [items in text_items' form]}, or a callable (frame index, the frame's record) -> items for lines that quote the record
+        this call builds: the caller's own lines (main.py:297-309), burned in after the frame's own and appended to its items.  rasterise (keyword only): rasterise(canvas, item) in annotate.text_stamps' sense; default cv2.putText
+        (ImportError, before anything is predicted, where OpenCV is not installed).  The records are the same with and without it."""
 
-    def _process_frames(self, frames, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed):
-        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed)
+    def _process_frames(self, frames, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed, burn_text=False,
+                        extra_text=None, rasterise=None):
+        got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
+                                  burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
         if annotate is None:
             return records
-        return self._with_text(got[2], records, i32, lambda b: self.params.min_stitches, got[3]), records
+        return self._with_text(got[2], records, i32, lambda b: self.params.min_stitches, got[3], extra_text, rasterise), records
 
     def process_frame(self, frame, annotate=False, **kw):
         """One frame: the record process_frame returns; annotate=True: the reference's tuple (annotated BGR ndarray, record), the text
@@ -407,17 +474,20 @@ class MultiCameraMeasurer(_DeviceStage):
         batch: one predict, one vti_measure_frames, one read); cameras: one index into params_by_camera per frame (host integers).
         Returns one record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame
         order.  annotate, encode, jpeg_quality, mixed: as StitchMeasurer.process_frames (frames of differing sizes only with
-        mixed=True) -> (annotated, records)."""
+        mixed=True) -> (annotated, records).  burn_text, extra_text, rasterise (keyword only): as StitchMeasurer.process_frames, with
+        mixed=True too (vti_stamp_frames: every picture gets its text at its own size)."""
 
-    def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed):
+    def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
+                        burn_text=False, extra_text=None, rasterise=None):
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
         got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
-                                  mixed)
+                                  mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         if annotate is None:
             return records
-        return self._with_text(got[2], records, i32, lambda b: self.params[int(cams[b])].min_stitches, got[3]), records
+        return self._with_text(got[2], records, i32, lambda b: self.params[int(cams[b])].min_stitches, got[3], extra_text,
+                               rasterise), records
 
     def _records(self, f64, i32, cams):
         """Frame b's record from camera cams[b]'s stream, in frame order."""
@@ -465,7 +535,7 @@ class StitchDistanceChecker(_DeviceStage):
                 'timestamp': datetime.now()}
 
     def process_frames(self, frames, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False, annotate=None,
-                       encode=None, jpeg_quality=95):
+                       encode=None, jpeg_quality=95, burn_text=False, extra_text=None, rasterise=None):
         """frames: as StitchMeasurer.process_frames takes them (a BGR uint8 batch, a list of JPEG files, RawFrames), all of one size.
         The defaults are the checker's predict call (:286: conf 0.20, iou 0.45, max_det 200, imgsz not passed: 640).  Returns one
         record per frame, in frame order, smoothed frame by frame: edge_distance_mm, stitch_width_mm (None: no value yet),
@@ -477,15 +547,18 @@ class StitchDistanceChecker(_DeviceStage):
         vti_annotate_checker, one copy to the host; the text is checker_text_items', for annotate.put_text), records exactly as
         without it.  encode="jpeg" (with annotate): the picture is the bytes of the JPEG file cv2.imwrite saves of it at
         jpeg_quality, encoded on the device; any other encode, or encode without annotate, is a ValueError before anything is
-        predicted.  With rows=True as well: (annotated, records, rows)."""
+        predicted.  With rows=True as well: (annotated, records, rows).
+        burn_text, extra_text, rasterise: as StitchMeasurer.process_frames -- the items of checker_text_items, then extra_text's,
+        burned into the selected pictures on the device (vti_stamp) before they are copied or encoded."""
         got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
-                                  rows=bool(rows))
+                                  rows=bool(rows), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
         full = lambda r, b: dict(r, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
         if annotate is None:
             return (records, [full(got[2][b], b) for b in range(len(f64))]) if rows else records
-        annotated = [(b, pic, checker_text_items(records[b], full(r, b), got[3])) for b, pic, r in got[2]]
+        annotated = _burned(got[2], [checker_text_items(records[b], full(r, b), got[3]) + _extra_items(extra_text, b, records[b])
+                                     for b, _, r in got[2]], rasterise)
         return (annotated, records, [full(got[4][b], b) for b in range(len(f64))]) if rows else (annotated, records)
 
     def process_frame(self, frame, annotate=False, **kw):
