@@ -23,7 +23,9 @@ def engine_and_oracle(scale, nc, H, W, B, dtype, seed=1, cls_bias=None, gain=1.7
     return eng, OracleModel(blob, H, W, mode="fp32" if dtype == "h2" else dtype), blob
 
 
-# planner switches (read by getenv inside vti_create, per plan): set them all and no conv is fused or persistent
+# planner switches: set them all and no conv is fused or persistent.  Every VTI_* switch, planner and launch path alike, is read
+# once when a context is created (vti_create; per call for vti_debug_conv2d) and kept in it: a change made afterwards reaches the
+# next engine, never a forward of an existing one, and no switch is frozen at the first plan of the process any more.
 PLAIN_SWITCHES = ("VTI_NO_FUSE", "VTI_NO_FOLD", "VTI_NO_BNECK", "VTI_NO_STEM_FUSE", "VTI_NO_UPFUSE", "VTI_NO_PK", "VTI_NO_PK1", "VTI_NO_PK2")
 PLAIN_PLAN = {k: "1" for k in PLAIN_SWITCHES}
 

@@ -829,15 +829,14 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
 void stem_l1_tile(int* th, int* tw) { *th = SL_TH; *tw = SL_TW; }
 
 // persistent grid: as many workgroups as fit the chip at once (one per CU; two where the LDS image fits twice: fp16)
-int stem_l1_grid(int dtype, int ntiles) {
+int stem_l1_grid(int dtype, int ntiles, bool persistent) {
     const int wgpc = (int)std::min<size_t>(2, (160 * 1024) / stem_l1_lds_bytes(dtype));
-    const char* np = getenv("VTI_STEM_NOT_PERSISTENT");          // A/B aid: one workgroup per tile, as before
-    if (np && np[0] == '1') return ntiles;
+    if (!persistent) return ntiles;          // A/B aid (VTI_STEM_NOT_PERSISTENT): one workgroup per tile, as before
     return std::min(ntiles, 256 * std::max(1, wgpc));
 }
 
-hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st) {
-    dim3 grid((unsigned)stem_l1_grid(dtype, p.B * p.tiles_y * p.tiles_x));
+hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st, bool persistent) {
+    dim3 grid((unsigned)stem_l1_grid(dtype, p.B * p.tiles_y * p.tiles_x, persistent));
     if (grid.x == 0) return hipSuccess;
     const size_t lds = stem_l1_lds_bytes(dtype);
     return with_conv_type(dtype, [&](auto t) { return launch_lds<stem_l1_kernel<typename decltype(t)::type>>(grid, dim3(256), lds, st, p); });

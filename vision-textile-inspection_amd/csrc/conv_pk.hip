@@ -65,60 +65,43 @@ bool conv1_pk_wreg_instantiated(int dtype, int nrep, int wn, int nchunks) {
 
 // `depth` patch stages (2..4): the loaders run depth - 1 steps ahead.  Weights: K <= 2 chunks stay resident (1 or 2 buffers);
 // more chunks travel with the patches, one buffer per stage.
-static size_t pk_stage_bytes(int TH, int S) { return S == 2 ? (size_t)(2 * TH + 1) * 2 * PK_PWP * 64 : (size_t)(TH + 2) * PK_PWP * 64; }
 // wstat: the weights of ALL K chunks of the workgroup's n-group stay in LDS (any chunk count; K <= 2 chunks are always resident)
-size_t conv_pk2_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat) {     // stride 2
+// The host-side geometry of conv3_pk, by stride S: one stage of the patch ring, the LDS image, whether a geometry fits, its ring depth.
+static size_t pk_stage_bytes(int TH, int S) { return S == 2 ? (size_t)(2 * TH + 1) * 2 * PK_PWP * 64 : (size_t)(TH + 2) * PK_PWP * 64; }
+static size_t pk3_lds_bytes(int S, int TH, int WN, int NREP, int nchunks, int depth, int wstat) {
     const int nwbuf = wstat ? nchunks : nchunks > 2 ? depth : (nchunks > 1 ? 2 : 1);
-    return depth * pk_stage_bytes(TH, 2) + (size_t)nwbuf * WN * NREP * 9 * 1024 + (size_t)WN * NREP * 16 * 4;
+    return depth * pk_stage_bytes(TH, S) + (size_t)nwbuf * WN * NREP * 9 * 1024 + (size_t)WN * NREP * 16 * 4;
 }
-bool conv_pk2_fits(int TH, int WN, int NREP, int nchunks, int wstat) {
-    if (TH % PK_ROWS || !conv_pk2_instantiated(NREP, WN)) return false;
-    const int ncomp = (TH / PK_ROWS) * WN;
-    if (ncomp < 1 || ncomp > 4) return false;
-    const int ndma = (int)(pk_stage_bytes(TH, 2) / 1024);
-    if ((ndma + ncomp - 1) / ncomp > PK_MAXD2) return false;
-    return conv_pk2_lds_bytes(TH, WN, NREP, nchunks, 2, wstat) <= 160 * 1024;
-}
-int conv_pk2_depth(int TH, int WN, int NREP, int nchunks, int wstat) {
-    if (!conv_pk2_fits(TH, WN, NREP, nchunks, wstat)) return 0;
-    // default 2: in an A/B on one box the deeper rings made the whole forward ~0.7 % SLOWER (VTI_PK_DEPTH=3/4 to re-measure)
-    const char* cap = getenv("VTI_PK_DEPTH");
-    const int maxd = cap ? std::max(2, std::min(4, atoi(cap))) : 2;
-    const int ncomp = (TH / PK_ROWS) * WN;
-    const int per_step = ((int)(pk_stage_bytes(TH, 2) / 1024) + ncomp - 1) / ncomp + (nchunks > 2 && !wstat ? (WN * NREP * 9 + ncomp - 1) / ncomp : 0);
-    int d = 2;
-    while (d < maxd && conv_pk2_lds_bytes(TH, WN, NREP, nchunks, d + 1, wstat) <= 160 * 1024 && per_step * (d - 1) <= 63) ++d;
-    return d;
-}
-
-size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat) {
-    const size_t stage = (size_t)(TH + 2) * PK_PWP * 64;
-    const int nwbuf = wstat ? nchunks : nchunks > 2 ? depth : (nchunks > 1 ? 2 : 1);
-    return depth * stage + (size_t)nwbuf * WN * NREP * 9 * 1024 + (size_t)WN * NREP * 16 * 4;
-}
-size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks) { return conv_pk_lds_bytes(TH, WN, NREP, nchunks, 2, 0); }
-
-// deepest ring (<= 4) that fits the 160 KiB of LDS and the counted-wait range; 0 = the geometry does not fit at all
-int conv_pk_depth(int TH, int WN, int NREP, int nchunks, int wstat) {
-    if (!conv_pk_fits(TH, WN, NREP, nchunks, wstat)) return 0;
-    // default 2: in an A/B on one box the deeper rings made the whole forward ~0.7 % SLOWER (VTI_PK_DEPTH=3/4 to re-measure)
-    const char* cap = getenv("VTI_PK_DEPTH");
-    const int maxd = cap ? std::max(2, std::min(4, atoi(cap))) : 2;
-    const int ncomp = (TH / PK_ROWS) * WN;
-    const int per_step = ((TH + 2) * PK_PWP / 16 + ncomp - 1) / ncomp + (nchunks > 2 && !wstat ? (WN * NREP * 9 + ncomp - 1) / ncomp : 0);
-    int d = 2;
-    while (d < maxd && conv_pk_lds_bytes(TH, WN, NREP, nchunks, d + 1, wstat) <= 160 * 1024 && per_step * (d - 1) <= 63) ++d;
-    return d;
-}
-
-bool conv_pk_fits(int TH, int WN, int NREP, int nchunks, int wstat) {
-    if (TH % PK_ROWS) return false;
+static bool pk3_fits(int S, int TH, int WN, int NREP, int nchunks, int wstat) {
+    if (TH % PK_ROWS || (S == 2 && !conv_pk2_instantiated(NREP, WN))) return false;
     const int ncomp = (TH / PK_ROWS) * WN;        // compute waves; as many loader waves beside them
     if (ncomp < 1 || ncomp > 4) return false;
-    const int ndma = (TH + 2) * PK_PWP / 16;
-    if ((ndma + ncomp - 1) / ncomp > PK_MAXD) return false;
-    return conv_pk_lds_bytes(TH, WN, NREP, nchunks, 2, wstat) <= 160 * 1024;
+    const int ndma = (int)(pk_stage_bytes(TH, S) / 1024);
+    if ((ndma + ncomp - 1) / ncomp > (S == 2 ? PK_MAXD2 : PK_MAXD)) return false;
+    return pk3_lds_bytes(S, TH, WN, NREP, nchunks, 2, wstat) <= 160 * 1024;
 }
+// The deepest ring, from 2 up to maxd, whose LDS image (lds_at(depth)) fits the 160 KiB and whose per_step DMA instructions per
+// loader wave and step stay inside the counted-wait range.  The default caps are 2 (in an A/B on one box the deeper rings made the
+// whole forward ~0.7 % SLOWER; VTI_PK_DEPTH=3/4 to re-measure) and, for the fold, 3.
+template <typename F>
+static int pk_ring_depth(int maxd, int per_step, F lds_at) {
+    int d = 2;
+    while (d < maxd && lds_at(d + 1) <= 160 * 1024 && per_step * (d - 1) <= 63) ++d;
+    return d;
+}
+// 0 = the geometry does not fit at all
+static int pk3_depth(int S, int TH, int WN, int NREP, int nchunks, int wstat, int maxd) {
+    if (!pk3_fits(S, TH, WN, NREP, nchunks, wstat)) return 0;
+    const int ncomp = (TH / PK_ROWS) * WN;
+    const int per_step = ((int)(pk_stage_bytes(TH, S) / 1024) + ncomp - 1) / ncomp + (nchunks > 2 && !wstat ? (WN * NREP * 9 + ncomp - 1) / ncomp : 0);
+    return pk_ring_depth(maxd, per_step, [&](int d) { return pk3_lds_bytes(S, TH, WN, NREP, nchunks, d, wstat); });
+}
+size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat) { return pk3_lds_bytes(1, TH, WN, NREP, nchunks, depth, wstat); }
+size_t conv_pk2_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat) { return pk3_lds_bytes(2, TH, WN, NREP, nchunks, depth, wstat); }
+bool conv_pk_fits(int TH, int WN, int NREP, int nchunks, int wstat) { return pk3_fits(1, TH, WN, NREP, nchunks, wstat); }
+bool conv_pk2_fits(int TH, int WN, int NREP, int nchunks, int wstat) { return pk3_fits(2, TH, WN, NREP, nchunks, wstat); }
+int conv_pk_depth(int TH, int WN, int NREP, int nchunks, int wstat, int maxd) { return pk3_depth(1, TH, WN, NREP, nchunks, wstat, maxd); }
+int conv_pk2_depth(int TH, int WN, int NREP, int nchunks, int wstat, int maxd) { return pk3_depth(2, TH, WN, NREP, nchunks, wstat, maxd); }
 
 // LDS-DMA: 64 lanes x 16 B from per-lane buffer offsets to LDS [lds_addr, lds_addr + 1 KiB), lane-linear.
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned lds_addr) {
@@ -949,12 +932,8 @@ hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_
 // fold on the persistent schedule: 4 x 20 low-resolution pixels per tile, 4 phase waves + 4 loader waves, 2 stages of a 6 x 24 slot
 // patch + both K chunks of the composed weights (2 x 16 n-tiles x 4 taps KiB) + the (unused) bias slot
 size_t conv_pk_fold_lds_bytes(int nchunks, int depth) { return depth * (size_t)6 * PK_PWP * 64 + (size_t)(nchunks > 1 ? 2 : 1) * 16 * 4 * 1024 + 16 * 16 * 4; }
-int conv_pk_fold_depth(int nchunks) {
-    const char* cap = getenv("VTI_PK_FOLD_DEPTH");          // steps here are only ~1.3 k MFMA cycles long: a third stage keeps a patch in flight
-    const int maxd = cap ? std::max(2, std::min(4, atoi(cap))) : 3;
-    int d = 2;
-    while (d < maxd && conv_pk_fold_lds_bytes(nchunks, d + 1) <= 160 * 1024) ++d;
-    return d;
+int conv_pk_fold_depth(int nchunks, int maxd) {       // steps here are only ~1.3 k MFMA cycles long: a third stage keeps a patch in flight
+    return pk_ring_depth(maxd, 0, [&](int d) { return conv_pk_fold_lds_bytes(nchunks, d); });
 }
 
 hipError_t launch_conv_pk_fold(int dtype, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
@@ -1031,18 +1010,12 @@ constexpr int BN_MREP1 = 7;
 size_t bneck_pk_lds_bytes(int TH, int NREP, int depth) {
     return depth * (size_t)(TH + 4) * PK_PWP * 64 + (size_t)(TH + 2) * PK_PWP * 64 + 2 * (size_t)NREP * 9 * 1024 + 2 * (size_t)NREP * 64;
 }
-size_t bneck_pk_lds_bytes(int TH, int NREP) { return bneck_pk_lds_bytes(TH, NREP, 2); }
 // patch stages: as many (<= 4) as fit -- these layers are HBM-bound and one 15-30 KB patch in flight per CU is ~1/3 of what
 // Little's law asks for at ~2 us of loaded latency
-int bneck_pk_depth(int TH, int NREP) {
-    // default 2: in an A/B on one box the deeper rings made the whole forward ~0.7 % SLOWER (VTI_PK_DEPTH=3/4 to re-measure)
-    const char* cap = getenv("VTI_PK_DEPTH");
-    const int maxd = cap ? std::max(2, std::min(4, atoi(cap))) : 2;
+int bneck_pk_depth(int TH, int NREP, int maxd) {
     const int nwm = TH / PK_ROWS;
     const int per_step = ((TH + 4) * PK_PWP / 16 + nwm - 1) / nwm;
-    int d = 2;
-    while (d < maxd && bneck_pk_lds_bytes(TH, NREP, d + 1) <= 160 * 1024 && per_step * (d - 1) <= 63) ++d;
-    return d;
+    return pk_ring_depth(maxd, per_step, [&](int d) { return bneck_pk_lds_bytes(TH, NREP, d); });
 }
 bool bneck_pk_fits(int TH, int NREP) {
     if (TH % PK_ROWS || TH < 8 || TH > 16 || NREP < 1 || NREP > 2) return false;

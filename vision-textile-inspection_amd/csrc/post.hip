@@ -1245,7 +1245,7 @@ size_t masks_workspace_bytes(int capacity, int H, int W) {
 
 hipError_t launch_masks(int dtype, const float* dets, const int* counts, const void* proto, int B, int max_det, int nm,
                         int Hp, int Wp, int H, int W, int mode, int packing, uint8_t* masks, int capacity,
-                        int* offsets, void* ws, hipStream_t st) {
+                        int* offsets, void* ws, hipStream_t st, int wgs_per_cu) {
     if (B == 0) return hipSuccess;
     if (Hp * 4 != H || Wp * 4 != W || nm > 64) return hipErrorInvalidValue;   // tile geometry assumes stride-4 prototypes
     int* nitems = (int*)ws;
@@ -1266,7 +1266,7 @@ hipError_t launch_masks(int dtype, const float* dets, const int* counts, const v
     const int per_cu = dtype == VTI_F16 ? (nm == 32 ? resident_per_cu<masks_group_kernel<half_t>>(256, 4, 8) : resident_per_cu<masks_kernel<half_t>>(256, 4, 8))
                                         : (nm == 32 ? resident_per_cu<masks_group_kernel<float>>(256, 4, 8) : resident_per_cu<masks_kernel<float>>(256, 4, 8));
     int grid = 256 * per_cu;
-    if (const char* e = getenv("VTI_MASK_WGS_PER_CU")) grid = 256 * std::max(1, std::min(per_cu, atoi(e)));   // experiments: fewer resident workgroups
+    if (wgs_per_cu) grid = 256 * std::max(1, std::min(per_cu, wgs_per_cu));   // experiments (VTI_MASK_WGS_PER_CU): fewer resident workgroups
     if (nm == 32) {
         // the (frame, tile) list is static: no plan, no work-list memory
         if (dtype == VTI_F16)

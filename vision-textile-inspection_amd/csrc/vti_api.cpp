@@ -18,6 +18,7 @@
 using namespace vti;
 
 struct vti_ctx {
+    Options opt;               // the VTI_* switches as vti_create found them
     Plan plan;
     std::string err;
     int device = -1;
@@ -129,7 +130,8 @@ int32_t vti_create(const vti_desc* desc, vti_ctx** out) {
     vti_ctx* c = new (std::nothrow) vti_ctx();
     if (!c) return fail(nullptr, VTI_ERR_NOMEM, "vti_create: out of host memory");
     std::string e;
-    try { e = c->plan.build(*desc); } catch (const std::exception& ex) { e = ex.what(); }
+    c->opt = options_from_env();
+    try { e = c->plan.build(*desc, c->opt.plan); } catch (const std::exception& ex) { e = ex.what(); }
     if (!e.empty()) { delete c; return fail(nullptr, VTI_ERR_ARG, "vti_create: " + e); }
     c->act_bytes = c->plan.ws_bytes;
     *out = c;
@@ -215,8 +217,7 @@ int32_t vti_load_weights(vti_ctx* c, const void* blob, size_t nbytes, int32_t de
     VTI_HIP(c, hipMemcpy(c->d_bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(bias)");
     c->device = device;
     // side streams (VTI_SINGLE_STREAM=1 keeps everything on the caller's stream)
-    const char* ss = getenv("VTI_SINGLE_STREAM");
-    if (!(ss && ss[0] == '1') && !c->side[1]) {
+    if (!c->opt.run.single_stream && !c->side[1]) {
         bool ok = true;
         for (int l = 1; l < kNumLanes && ok; ++l) {
             ok = hipStreamCreateWithFlags(&c->side[l], hipStreamNonBlocking) == hipSuccess &&
@@ -400,21 +401,13 @@ static void* buf_ptr(vti_ctx* c, int buf, const void* input, void* proto) {
 
 // Delay units (x 1024 cycles) of the staggered persistent 3x3 launches.  h2 only by default: -2.6 ... -4.2 % per forward on five of
 // seven boxes (A/B on one box at a time), +0.8 % on the two fastest; fp16: +0.2 ... +1 % on a fast box, fp32: nothing.  VTI_PK_STAGGER=n overrides.
-static int stagger_units(int dtype) {
-    static const int v = getenv("VTI_PK_STAGGER") ? std::max(0, std::min(255, atoi(getenv("VTI_PK_STAGGER")))) : -1;
-    return v >= 0 ? v : (dtype == VTI_H2 ? 10 : 0);
-}
-
-static int pk_linear_map() {       // A/B aid: VTI_PK_LINEAR_MAP=1 restores the linear pixel -> column-tile map of the persistent 3x3 kernels
-    static const int v = getenv("VTI_PK_LINEAR_MAP") && getenv("VTI_PK_LINEAR_MAP")[0] == '1';
-    return v;
-}
+static int stagger_units(const RunOptions& run, int dtype) { return run.pk_stagger >= 0 ? run.pk_stagger : (dtype == VTI_H2 ? 10 : 0); }
 
 // Stores of n channels at channel offset coff into rows of ld channels: 16-byte vector stores need all three to be multiples of 4.
 static int scalar_store(int n, int ld, int coff) { return (n % 4 || ld % 4 || coff % 4) ? 1 : 0; }
 
 // One conv launch's parameter block from its table row + geometry + tensor views.
-static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r, const ConvCfg& g, int B, const void* in, int in_ld,
+static void fill_conv_params(const RunOptions& run, int conv_elem_size, ConvParams& p, const ConvRow& r, const ConvCfg& g, int B, const void* in, int in_ld,
                              int in_coff, void* out, int out_ld, int out_coff, const void* res, int res_ld,
                              int res_coff, const void* wpk, const float* bias, bool out_f32, int swap_rb) {
     const bool deconv = r.kind == 2;
@@ -430,7 +423,7 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
     p.WN = g.WN;
     p.nt = g.threads;
     p.wreg = g.pk ? 0 : g.wreg;      // the per-tile kernel's flag; conv1_pk's register-resident weights are pk_wstat == 2
-    p.pk_lin = pk_linear_map();
+    p.pk_lin = run.pk_linear_map;       // A/B aid: the linear pixel -> column-tile map of the persistent 3x3 kernels
     p.act = r.kind == 0; p.out_f32 = out_f32 ? 1 : 0;
     p.deconv_c = deconv ? r.c2 : 0;
     p.swap_rb = swap_rb ? 1 : 0;
@@ -453,7 +446,7 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
         p.in_bytes = (unsigned)ib; p.out_bytes = (unsigned)ob; p.res_bytes = 0;
         p.pk_depth = g.pk_depth; p.pk_wstat = g.pk_wstat; p.pk_cps = g.pk_cps;
         p.pk_tiles = (int)((npx + (size_t)g.TH * 80 - 1) / ((size_t)g.TH * 80));
-        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, g.ntiles_n / (g.WN * g.NREP), getenv("VTI_PK_MAX_WGS"));
+        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, g.ntiles_n / (g.WN * g.NREP), run.pk_max_wgs);
         p.pk_xcd = p.pk_wgs >= 8 ? 1 : 0;
     } else if (g.pk) {   // persistent kernel: workgroups along x walk the B * tiles_y * tiles_x tiles
         const size_t es = conv_elem_size;
@@ -464,10 +457,10 @@ static void fill_conv_params(int conv_elem_size, ConvParams& p, const ConvRow& r
         p.pk_tiles = B * p.tiles_y * p.tiles_x;
         p.pk_depth = g.pk_depth; p.pk_wstat = g.pk_wstat;
         const int gy = g.ntiles_n / (g.WN * g.NREP);
-        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, gy, getenv("VTI_PK_MAX_WGS"));      // tests: force many tiles per workgroup
+        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, gy, run.pk_max_wgs);      // tests: force many tiles per workgroup
         p.pk_xcd = p.pk_wgs >= 8 ? 1 : 0;
         // launches that fill the chip start the upper half of their workgroups late (conv_pk.hip: pk_stagger_wait): eligibility here,
-        // the caller scales it by stagger_units(dtype)
+        // the caller scales it by stagger_units(run, dtype)
         p.pk_stagger = ((g.pk == 1 || g.pk == 4) && p.pk_tiles >= std::max(1, 256 * g.pk_wgpc / gy) && p.pk_wgs >= 16) ? 1 : 0;
     }
 }
@@ -506,8 +499,8 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
     const Plan& P = c->plan;
     hipStream_t main_st = (hipStream_t)stream;
     const int dt = P.desc.dtype;
-    static const bool list_ops = getenv("VTI_LIST_OPS") != nullptr;      // developer aid: launch order, to label a kernel trace
-    if (list_ops) {
+    const RunOptions& run = c->opt.run;
+    if (run.list_ops) {        // developer aid: launch order, to label a kernel trace
         int i = 0;
         for (const Op& op : P.ops) {
             if (op.kind == OP_FORK || op.kind == OP_JOIN) continue;
@@ -562,12 +555,12 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                 q.tiles_y = (q.Hout + q.TH - 1) / q.TH; q.tiles_x = (q.Wout + q.TW - 1) / q.TW; q.WN = 1;
                 q.scalar_store = scalar_store(q.Cout, q.out_ld, q.out_coff);
 #ifdef VTI_STAMPS
-                if (const char* so = getenv("VTI_STAMP_OP"); so && r.name == so)
-                    stamped_launch(q, (size_t)stem_l1_grid(dt, B * q.tiles_y * q.tiles_x), false, st,
+                if (r.name == run.stamp_op)
+                    stamped_launch(q, (size_t)stem_l1_grid(dt, B * q.tiles_y * q.tiles_x, !run.stem_not_persistent), false, st,
                                    ("[stamps] op " + r.name + " + layer 1 (1: patch staged, 2: stem done, 3: layer-1 MFMAs done, 12: end)").c_str(),
-                                   [&] { return launch_stem_l1(dt, q, st); });
+                                   [&] { return launch_stem_l1(dt, q, st, !run.stem_not_persistent); });
 #endif
-                VTI_HIP(c, launch_stem_l1(dt, q, st), "stem + layer 1");
+                VTI_HIP(c, launch_stem_l1(dt, q, st, !run.stem_not_persistent), "stem + layer 1");
                 break;
             }
             if (op.fold >= 0) {         // ConvTranspose2d(2,2) + 3x3 + fused 1x1 as four 2x2 convs on the low-resolution map
@@ -575,7 +568,7 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                 ConvParams q;
                 memset(&q, 0, sizeof q);
                 q.in = buf_ptr(c, op.in.buf, input, proto); q.B = B; q.Hin = ru.h_in; q.Win = ru.w_in; q.Hout = ru.h_in; q.Wout = ru.w_in;
-                q.Cin = ru.c1; q.in_ld = ib.C; q.in_coff = op.in.coff; q.Cout = g.gemm_n; q.act = 1; q.fold = 1; q.pk_lin = pk_linear_map();
+                q.Cin = ru.c1; q.in_ld = ib.C; q.in_coff = op.in.coff; q.Cout = g.gemm_n; q.act = 1; q.fold = 1; q.pk_lin = run.pk_linear_map;
                 q.TH = g.TH; q.TW = g.TW; q.tiles_y = (q.Hout + g.TH - 1) / g.TH; q.tiles_x = (q.Wout + g.TW - 1) / g.TW; q.WN = 4; q.nt = g.threads;
                 q.nchunks = g.nchunks; q.ntiles_n = g.ntiles_n;
                 q.pw_magic = (unsigned)((0x100000000ull + (unsigned)(g.TW + 2) - 1) / (unsigned)(g.TW + 2));
@@ -586,7 +579,7 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                 if (g.pk) {             // persistent schedule: composed weights resident in LDS, tiles walked per XCD
                     q.pk = 1; q.pk_depth = g.pk_depth; q.in_bytes = (unsigned)((size_t)B * q.Hin * q.Win * q.in_ld * P.esize);
                     q.pk_tiles = B * q.tiles_y * q.tiles_x;
-                    q.pk_wgs = pk_grid(q.pk_tiles, 1, 1, getenv("VTI_PK_MAX_WGS"));
+                    q.pk_wgs = pk_grid(q.pk_tiles, 1, 1, run.pk_max_wgs);
                     q.pk_xcd = q.pk_wgs >= 8 ? 1 : 0;
                     VTI_HIP(c, launch_conv_pk_fold(dt, q, g.lds, st), r.name.c_str());
                 } else {
@@ -595,13 +588,13 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
                 break;
             }
             ConvParams p;
-            fill_conv_params(P.esize, p, r, g, B, buf_ptr(c, op.in.buf, input, proto), ib.C, op.in.coff,
+            fill_conv_params(run, P.esize, p, r, g, B, buf_ptr(c, op.in.buf, input, proto), ib.C, op.in.coff,
                              buf_ptr(c, op.out.buf, input, proto), ob.C, op.out.coff,
                              op.has_res ? buf_ptr(c, op.res.buf, input, proto) : nullptr,
                              op.has_res ? P.bufs[op.res.buf].C : 0, op.res.coff,
                              (const char*)c->d_wpk + g.wpk_off, c->d_bias + g.bias_off, op.out_f32, swap_rb);
             p.alpha = c->alpha[op.conv]; p.alpha0 = 1.f;
-            p.pk_stagger *= stagger_units(dt);
+            p.pk_stagger *= stagger_units(run, dt);
             p.alpha2 = op.pair >= 0 ? c->alpha[op.pair] : 1.f;
             if (op.fused >= 0) {
                 fill_stage2(c, p, op, input, proto);
@@ -640,7 +633,7 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
             const int ks = deconv ? 1 : r.k, s = deconv ? 1 : r.s;
 #ifdef VTI_STAMPS
             // diagnostic build: stamp this op of the forward (fused ops included); the stamped launch is the op's launch
-            if (const char* so = getenv("VTI_STAMP_OP"); so && r.name == so &&
+            if (r.name == run.stamp_op &&
                 stamped_launch(p, conv_workgroups(p, g, B), p.pk != 0, st, ("[stamps] op " + r.name).c_str(),
                                [&] { return launch_conv(dt, ks, s, g.NREP, op.kind == OP_CONV0 ? 1 : 0, p, g.lds, st); }))
                 break;
@@ -731,7 +724,7 @@ int32_t vti_masks(vti_ctx* c, const float* dets, const int32_t* counts, const vo
     void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
     if (int32_t drc = check_device(c, "vti_masks")) return drc;
     VTI_HIP(c, launch_masks(d.dtype, dets, counts, proto, B, max_det, d.nm, d.H / 4, d.W / 4, d.H, d.W, mode, packing, masks,
-                            capacity, offsets, mws, (hipStream_t)stream), "mask kernel");
+                            capacity, offsets, mws, (hipStream_t)stream, c->opt.run.mask_wgs_per_cu), "mask kernel");
     return VTI_OK;
 }
 
@@ -1945,8 +1938,9 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
     r.name = "debug"; r.c1 = c1; r.c2 = c2; r.k = k; r.s = s; r.kind = kind; r.h_in = H; r.w_in = W;
     if (kind == 2) { r.h_out = 2 * H; r.w_out = 2 * W; }
     else { r.h_out = (H + 2 * (k / 2) - k) / s + 1; r.w_out = (W + 2 * (k / 2) - k) / s + 1; }
+    const Options opt = options_from_env();       // no context here: the switches are read once per call
     ConvCfg g;
-    choose_conv_cfg(dtype, r, conv0, B, g, tile_h, tile_w, waves_n, nrep);
+    choose_conv_cfg(opt.plan, dtype, r, conv0, B, g, tile_h, tile_w, waves_n, nrep);
     if (g.TH == 0) return fail(nullptr, VTI_ERR_ARG, "vti_debug_conv2d: no launch configuration fits");
     if (cfg_out) { cfg_out[0] = g.TH; cfg_out[1] = g.TW; cfg_out[2] = g.WN; cfg_out[3] = g.NREP; cfg_out[4] = (int32_t)g.lds * (g.pk ? -1 : 1); }   // negative LDS size = persistent kernel
     std::vector<uint8_t> wpk(packed_conv_bytes(r, conv0, g));
@@ -1964,10 +1958,10 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) {
         ConvParams p;
-        fill_conv_params(dtype == VTI_F16 ? 2 : 4, p, r, g, B, dev_in, in_ld, in_coff, dev_out, out_ld, out_coff, dev_res, res_ld, res_coff, d_w, d_b,
+        fill_conv_params(opt.run, dtype == VTI_F16 ? 2 : 4, p, r, g, B, dev_in, in_ld, in_coff, dev_out, out_ld, out_coff, dev_res, res_ld, res_coff, d_w, d_b,
                          out_f32 != 0, swap_rb);
         p.alpha = alpha; p.alpha2 = p.alpha0 = 1.f;
-        p.pk_stagger *= stagger_units(dtype);
+        p.pk_stagger *= stagger_units(opt.run, dtype);
         const int ks = kind == 2 ? 1 : k, ss = kind == 2 ? 1 : s;
 #ifdef VTI_STAMPS
         // diagnostic build: one stamped launch after a warm-up (caches, icache), medians of the phase intervals to stderr

@@ -49,12 +49,39 @@ int resident_per_cu(int threads, int fallback, int cap) {
 }
 
 // Workgroups of a persistent launch: as many as fit the chip (wgpc per CU, 256 CUs, shared by gy n-groups), at most one per tile,
-// lowered to `cap` when given (VTI_PK_MAX_WGS), and a multiple of 8 from 8 on (each XCD then walks a contiguous range of tiles).
-inline int pk_grid(long tiles, int wgpc, int gy, const char* cap = nullptr) {
+// lowered to `cap` when given (RunOptions.pk_max_wgs), and a multiple of 8 from 8 on (each XCD then walks a contiguous range of tiles).
+inline int pk_grid(long tiles, int wgpc, int gy, int cap = 0) {
     long G = std::min<long>(tiles, std::max(1, 256 * wgpc / gy));
-    if (cap) G = std::max<long>(1, std::min<long>(G, atoi(cap)));
+    if (cap) G = std::max<long>(1, std::min<long>(G, cap));
     return (int)(G >= 8 ? G & ~7L : G);
 }
+
+// ---- switches (options.cpp) -----------------------------------------------------------
+// The VTI_* environment switches, parsed.  options.cpp names each of them once (name, parse rule, default, meaning) and is the only
+// place that reads the environment: vti_create reads them once and keeps them in the context, vti_debug_conv2d once per call.
+struct PlanOptions {         // what the planner reads (Plan::build, choose_conv_cfg)
+    bool no_pk = false, no_pk1 = false, no_pk2 = false, pk_wide16 = false, no_pk_wstat = false, h2_no_n5 = false, pk1_all = false;
+    bool pk1_no_wgpc2 = false, pk1_force_wgpc2 = false, conv1_wreg = true, p3_lanes = false;
+    bool no_fuse = false, no_fold = false, no_bneck = false, no_bneck_tail = false, no_stem_fuse = false, no_stem_fuse3 = false;
+    bool no_pred_scatter = false, no_dfl_fuse = false, no_upfuse = false, no_pk_fold = false, no_t512 = false, no_fold512 = false;
+    int fold512 = -1;                        // -1: unset (on for h2 unless no_fold512), else 1 / 0
+    int pk_fused = -1;                       // -1: unset (h2 box towers), 1: every fused op, 2: those with NREP <= 4, 0: none
+    int pk_depth = 2, pk_fold_depth = 3;     // ring-depth caps, 2..4
+    size_t pk_limit_bytes = 0x80000000ull;   // tensors from this size on stay off the persistent kernels
+    size_t pk1_wstat_bytes = 96 * 1024;      // conv1_pk: weights stationary in LDS up to this size
+    double pk1_inflight_bytes = 50e3;        // conv1_pk cost model: bytes in flight per CU that saturate the ingest
+};
+struct RunOptions {          // what the launch path reads
+    int pk_max_wgs = 0;                      // cap of a persistent launch's workgroups (>= 1), 0: none
+    int pk_stagger = -1;                     // delay units of the staggered 3x3 launches (0..255), -1: the dtype's default
+    bool pk_linear_map = false, single_stream = false, list_ops = false, stem_not_persistent = false;
+    int mask_wgs_per_cu = 0;                 // cap of launch_masks' resident workgroups per CU (>= 1), 0: none
+    std::string stamp_op;                    // diagnostic build (VTI_STAMPS): the conv whose launch is stamped
+};
+struct Options { PlanOptions plan; RunOptions run; };
+// `get` returns a switch's text or nullptr (unset); the same parse rules whichever source it reads
+Options parse_options(const char* (*get)(const char* name, void* user), void* user);
+Options options_from_env();
 
 // ---- plan ---------------------------------------------------------------------------
 enum ElemKind { EL_T = 0, EL_F32 = 1, EL_U8 = 2 };   // EL_T = ctx dtype (fp16, fp32, or h2 = split-fp16 pairs, 4 bytes)
@@ -146,7 +173,7 @@ struct Plan {
     size_t ws_bytes = 0;
     size_t wpk_bytes = 0, bias_floats = 0;
     int64_t macs = 0, fused_params = 0;
-    std::string build(const vti_desc& d); // returns "" or an error message
+    std::string build(const vti_desc& d, const PlanOptions& opt);     // returns "" or an error message
 };
 
 // ---- kernel parameter blocks ------------------------------------------------------------
@@ -189,10 +216,10 @@ size_t conv_lds_bytes(int ks, int stride, int mode, int TH, int TW, int WN, int 
 bool conv_wreg_ok(int ks, int stride, int mode, int WN, int NREP, int threads = 256);   // per-tile 1x1 with register-fed weights: is there an instantiation
 bool conv_cfg_fits(int ks, int stride, int mode, int TH, int TW, int WN, int NREP, int threads = 256);
 // stem (3->16, k3 s2) + layer 1 (16->32, k3 s2) in one kernel: 16 x 20 layer-1 output tiles
-hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st);
+hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st, bool persistent = true);
 size_t stem_l1_lds_bytes(int dtype);
 void stem_l1_tile(int* th, int* tw);
-int stem_l1_grid(int dtype, int ntiles);     // workgroups of the (persistent) launch
+int stem_l1_grid(int dtype, int ntiles, bool persistent = true);     // workgroups of the launch (not persistent: one per tile, an A/B aid)
 void pack_stem_toeplitz(int dtype, const ConvRow& r0, const float* w, const float* b, uint8_t* dst_w, float* dst_b, float* alpha = nullptr);
 size_t packed_stem_toeplitz_bytes(int dtype);
 // ConvTranspose2d(C,C,2,2) folded into the following 3x3 conv (+ its fused 1x1): four 2x2 convs on the low-resolution map
@@ -204,20 +231,19 @@ void pack_conv_fold(int dtype, const ConvRow& rU, const ConvRow& rV, const ConvC
 size_t packed_fold_bytes(const ConvCfg& c);
 hipError_t launch_conv_pk_fold(int dtype, const ConvParams& p, size_t lds_bytes, hipStream_t st);   // the same on the persistent schedule
 size_t conv_pk_fold_lds_bytes(int nchunks, int depth);
-int conv_pk_fold_depth(int nchunks);
+int conv_pk_fold_depth(int nchunks, int maxd = 3);
 void pack_conv_l1pairs(int dtype, const ConvRow& r1, const float* w, const float* b, uint8_t* dst_w, float* dst_b, float* alpha = nullptr);
 size_t packed_l1pairs_bytes(int dtype);
 // conv_pk.hip: persistent 3x3/s1 kernel
 hipError_t launch_conv_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
-size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks);
 size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat = 0);   // wstat: all K chunks' weights resident in LDS
-int conv_pk_depth(int TH, int WN, int NREP, int nchunks, int wstat = 0);
+int conv_pk_depth(int TH, int WN, int NREP, int nchunks, int wstat = 0, int maxd = 2);     // maxd: PlanOptions.pk_depth
 // stride-2 3x3 on the persistent schedule (ConvCfg.pk == 4)
 hipError_t launch_conv_pk2(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
 size_t conv_pk2_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat = 0);
 bool conv_pk2_fits(int TH, int WN, int NREP, int nchunks, int wstat = 0);
 bool conv_pk2_instantiated(int nrep, int wn);
-int conv_pk2_depth(int TH, int WN, int NREP, int nchunks, int wstat = 0);
+int conv_pk2_depth(int TH, int WN, int NREP, int nchunks, int wstat = 0, int maxd = 2);
 bool conv_pk_fits(int TH, int WN, int NREP, int nchunks, int wstat = 0);
 bool conv_pk_instantiated(int nrep, int wn);
 hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
@@ -226,9 +252,8 @@ bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat,
 bool conv1_pk_instantiated(int nrep, int wn);
 bool conv1_pk_wreg_instantiated(int dtype, int nrep, int wn, int nchunks);   // wstat == 2: the n-group's weights in the compute waves' registers
 hipError_t launch_bneck_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
-size_t bneck_pk_lds_bytes(int TH, int NREP);
-size_t bneck_pk_lds_bytes(int TH, int NREP, int depth);
-int bneck_pk_depth(int TH, int NREP);
+size_t bneck_pk_lds_bytes(int TH, int NREP, int depth = 2);
+int bneck_pk_depth(int TH, int NREP, int maxd = 2);
 bool bneck_pk_fits(int TH, int NREP);
 
 struct PoolParams { const void* in; void* out; int B, H, W, C, ld, in_coff, out_coff; };
@@ -283,7 +308,7 @@ hipError_t launch_anchor_best(const float* pred, int B, int A, int nc, int nm, f
 float* nms_workspace_best(void* ws, int B, int A);       // [B, A, 2] floats at the end of the NMS workspace (vti_predict's own pair buffer)
 hipError_t launch_masks(int dtype, const float* dets, const int* counts, const void* proto, int B, int max_det,
                         int nm, int Hp, int Wp, int H, int W, int mode, int packing, uint8_t* masks,
-                        int capacity, int* offsets, void* ws, hipStream_t st);
+                        int capacity, int* offsets, void* ws, hipStream_t st, int wgs_per_cu = 0);      // wgs_per_cu: RunOptions.mask_wgs_per_cu
 size_t masks_workspace_bytes(int capacity, int H, int W);
 // retina_masks (process_mask_native): out = {top, bottom, left, right, row_bytes, slot_bytes} of frame-size masks from Hp x Wp
 // prototypes (host only; -1 for shapes it cannot describe); the launcher needs the frame-px boxes of vti_scale_boxes
@@ -484,7 +509,7 @@ hipError_t launch_convert_raw_frames(const uint8_t* raw, const void* dev_raw_tab
                                      int rgb, uint8_t* out, hipStream_t st);
 
 // plan.cpp: launch geometry for one conv (tile, wave split, LDS) -- th/tw/wn/nrep > 0 force a choice
-void choose_conv_cfg(int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,
+void choose_conv_cfg(const PlanOptions& opt, int dtype, const ConvRow& r, bool conv0, int max_batch, ConvCfg& c,
                      int th = 0, int tw = 0, int wn = 0, int nrep = 0, bool allow_pk = true);
 // weights.cpp: one conv's weights -> fragment order; dst_w has cfg.nchunks*ntiles_n*taps KiB, dst_b ntiles_n*16 floats
 void pack_conv(int dtype, const ConvRow& r, bool conv0, const ConvCfg& c, const float* w, const float* b,
