@@ -564,13 +564,96 @@ int32_t vti_annotate_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void*
  * VTI_MEASURE_MAX_DET are vti_annotate's.  dev_scratch: >= vti_annotate_scratch_bytes(ctx, n_sel, max_det, H0, W0, max_points),
  * 256-byte aligned: the layout is vti_annotate's.  Every argument check (VTI_ERR_ARG; vti_last_error names the argument) runs before
  * the first HIP call.  Three launches on `stream` (the checker's display list + union, then vti_annotate's outline and raster
- * kernels); no host synchronisation.  One frame size and one camera, as the checker stage. */
+ * kernels); no host synchronisation.  One frame size and one camera; several of either: vti_annotate_checker_cameras and
+ * vti_annotate_checker_frames, below. */
 int32_t vti_annotate_checker(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t H0, int32_t W0, const vti_checker_params* params,
                              const uint8_t* dev_masks, int32_t native, const float* dev_dets, const float* dev_xyxy,
                              const int32_t* dev_counts, const int32_t* dev_offsets, int32_t max_det, int32_t capacity,
                              const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
                              const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
                              uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes, void* stream);
+
+/* ---- the stitch-distance checker on a rig: a camera table of checker settings, frames of differing sizes ------------------------ */
+/* The rig forms of vti_measure_checker and vti_annotate_checker, as vti_measure and vti_annotate have theirs: the settings of every
+ * camera in one table in device memory, an i32 [B] device array that names each frame's row, and for frames of differing sizes the
+ * frame table pair of vti_pack_frames.  The arithmetic is the one-struct calls' own: frame b comes out bit for bit (measurement) and
+ * byte for byte (picture) as the one-struct call gives it with that camera's struct at that frame's size.
+ * Marks the six entry points of the rig forms; libvti.so exports them as it does every other. */
+#define VTI_CHECKER_RIG_API
+/* Host only: vti_measure_pack_cameras for checker settings.  Validates params[0 .. n_cams) with exactly vti_measure_checker's checks
+ * of its one struct (VTI_ERR_ARG; vti_last_error names the index of the first failing camera) and writes one row per camera into
+ * host_table.  A checker table has the size of a measure table of as many rows: nbytes >= vti_measure_cameras_bytes(n_cams).  The
+ * rows are NOT interchangeable with vti_measure_pack_cameras' (other settings); the format is private to the library build, and
+ * equal inputs give equal bytes.  ctx only receives the error text. */
+VTI_CHECKER_RIG_API int32_t vti_checker_pack_cameras(vti_ctx* ctx, const vti_checker_params* params, int32_t n_cams, void* host_table,
+                                                     size_t nbytes);
+/* vti_measure_checker with frame b measured under row dev_camera_of_frame[b] of dev_cameras (16-byte aligned device copy of a table of
+ * vti_checker_pack_cameras); the argument list, the checks and their order are vti_measure_cameras', native 0 or 1.  The kernels
+ * compare dev_camera_of_frame[b] with [0, n_cams) BEFORE they form a table address: a frame whose index is outside reports
+ * VTI_MEASURE_BAD_CAMERA, NaN averages, zero counts, and flags 0 / rank -1 / NaN in the per-slot rows of its instances; the other
+ * frames are unaffected.  The table's contents are trusted, as there. */
+VTI_CHECKER_RIG_API int32_t vti_measure_checker_cameras(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams,
+                                                        const int32_t* dev_camera_of_frame, const uint8_t* dev_masks, int32_t native,
+                                                        const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                                                        const int32_t* dev_offsets, int32_t B, int32_t max_det, int32_t capacity,
+                                                        int32_t H0, int32_t W0, void* dev_scratch, size_t scratch_bytes,
+                                                        double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
+                                                        void* stream);
+/* vti_measure_checker_cameras with H0, W0 of frame b from the frame table (vti_measure_frames' argument list): frame b's results are
+ * bit-identical to those of vti_measure_checker_cameras called with H0[b], W0[b] on the same inputs.  Letterbox bit masks only:
+ * native = 1 is VTI_ERR_UNSUPPORTED (the ragged rows are the next call's).  dev_scratch: >= vti_measure_scratch_bytes(ctx, B,
+ * capacity, largest W0 of the table); the envelope rows are pitched by that W0 and the columns past a frame's own W0 are neither
+ * written nor read. */
+VTI_CHECKER_RIG_API int32_t vti_measure_checker_frames(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams,
+                                                       const int32_t* dev_camera_of_frame, const uint8_t* dev_masks, int32_t native,
+                                                       const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                                                       const int32_t* dev_offsets, const void* host_table, const void* dev_table,
+                                                       int32_t B, int32_t max_det, int32_t capacity, void* dev_scratch,
+                                                       size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
+                                                       int32_t* stitch_i32, void* stream);
+/* The same from the ragged frame-size rows of vti_masks_native_frames (vti_measure_frames_native's argument list: dev_mask_bases i64
+ * [B + 1], capacity_bytes).  Frame b's results are bit-identical to those of vti_measure_checker_cameras with native = 1 at H0[b],
+ * W0[b] on that frame's rows.  LIVENESS: instance i of frame b is live when i < counts[b], its slot index dev_offsets[b] + i is below
+ * `capacity` and its rows end at or before capacity_bytes.  An instance that is not live is what the one-size call makes of a slot at
+ * or past `capacity`: an empty mask that STILL HAS ITS BOX -- with drop_empty = 0 a fabric instance joins the union with its filled
+ * rectangle and a stitch is measured at the centre of its int box; with drop_empty = 1 it does not exist -- and its per-slot rows
+ * are not written. */
+VTI_CHECKER_RIG_API int32_t vti_measure_checker_frames_native(vti_ctx* ctx, const void* dev_cameras, int32_t n_cams,
+                                                              const int32_t* dev_camera_of_frame, const uint8_t* dev_masks,
+                                                              const int64_t* dev_mask_bases, int64_t capacity_bytes,
+                                                              const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                                                              const int32_t* dev_offsets, const void* host_table,
+                                                              const void* dev_table, int32_t B, int32_t max_det, int32_t capacity,
+                                                              void* dev_scratch, size_t scratch_bytes, double* frame_f64,
+                                                              int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
+                                                              void* stream);
+/* vti_annotate_checker with the settings of frame b from row dev_camera_of_frame[b] of a checker table (NULL: row 0 for every frame)
+ * in place of the struct, at the position vti_annotate has them; one frame size, native 0 or 1; the checks are vti_annotate's.  A
+ * frame whose camera index is outside [0, n_cams), or whose status is none of OK, NO_FABRIC, NO_STITCHES, is copied as it is. */
+VTI_CHECKER_RIG_API int32_t vti_annotate_checker_cameras(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t H0, int32_t W0,
+                                                         const void* dev_cameras, int32_t n_cams, const int32_t* dev_camera_of_frame,
+                                                         const uint8_t* dev_masks, int32_t native, const float* dev_dets,
+                                                         const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets,
+                                                         int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                                                         const double* stitch_f64, const int32_t* stitch_i32,
+                                                         const int32_t* host_select, const int32_t* dev_select, int32_t n_sel,
+                                                         int32_t max_points, uint8_t* dev_out, int32_t* dev_status, void* dev_scratch,
+                                                         size_t scratch_bytes, void* stream);
+/* The checker's pictures of frames of differing sizes (vti_annotate_frames' argument list and checks: the in table pair, the out table
+ * pair whose row k must have the size of frame host_select[k], the selection given twice).  Picture k is byte for byte what
+ * vti_annotate_checker_cameras writes for that frame at its size; the gaps between the pictures, the bytes past the last one and
+ * dev_frames are never written.  Letterbox bit masks only: native = 1 is VTI_ERR_UNSUPPORTED; a selected frame above 8192 in either
+ * dimension is VTI_ERR_ARG naming it.  dev_scratch: >= vti_annotate_frames_scratch_bytes(ctx, host_out_table, max_det, max_points). */
+VTI_CHECKER_RIG_API int32_t vti_annotate_checker_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table,
+                                                        const void* dev_table, int32_t B, const void* dev_cameras, int32_t n_cams,
+                                                        const int32_t* dev_camera_of_frame, const uint8_t* dev_masks, int32_t native,
+                                                        const float* dev_dets, const float* dev_xyxy, const int32_t* dev_counts,
+                                                        const int32_t* dev_offsets, int32_t max_det, int32_t capacity,
+                                                        const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                                                        const int32_t* host_select, const int32_t* dev_select, int32_t n_sel,
+                                                        int32_t max_points, const void* host_out_table, const void* dev_out_table,
+                                                        uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes,
+                                                        void* stream);
 
 /* ---- the model-check viewer's picture on device (Utils/check_model.py:155-256, annotate_result) ------------------------------------ */
 /* The frames dev_select[k] of the batch as the viewer shows them, byte for byte the package's overlay.py (render): per instance in

@@ -143,6 +143,17 @@ SIGNATURES = {
                                    _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "vti_annotate_checker": (_I32, [_P, _P, _I32, _I32, _I32, C.POINTER(VtiCheckerParams), _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P,
                                     _P, _P, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    "vti_checker_pack_cameras": (_I32, [_P, C.POINTER(VtiCheckerParams), _I32, _P, _SZ]),
+    "vti_measure_checker_cameras": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _SZ,
+                                           _P, _P, _P, _P, _P]),
+    "vti_measure_checker_frames": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ,
+                                          _P, _P, _P, _P, _P]),
+    "vti_measure_checker_frames_native": (_I32, [_P, _P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ,
+                                                 _P, _P, _P, _P, _P]),
+    "vti_annotate_checker_cameras": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P,
+                                            _P, _P, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    "vti_annotate_checker_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
+                                           _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "vti_overlay_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
     "vti_overlay": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _F, _F, _P, _P, _I32, _I32, _P,
                            _I32, _P, _P, _P, _SZ, _P]),

@@ -269,19 +269,29 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
 // the final set only, the six records of stitch rank j together at 2 + M + 6 j: edge line, edge point, the two width ends, the width
 // line, the centroid (r = 4).  The width markers need both world points (a width from the local-scale estimate sets VTI_STITCH_WIDTH
 // too), so the two ends go through the pixel_to_world that vti_measure_checker used.  c: checker_pack's row, by value.
-template <bool NATIVE>
+// TABLE (vti_annotate_checker_cameras / _frames): c is row cam_of_frame[b] (null: row 0) of the camera table instead, range-checked
+// before the row's address is formed (a frame whose index is outside is copied as it is), and the frame's size and the placement of
+// the in and out frames come from the frame tables when there are any (frame_geo; the union and the point lists keep the pitches of
+// the largest selected frame).
+template <bool NATIVE, bool TABLE = false>
 __global__ __launch_bounds__(kThreads) void annotate_checker_prep_kernel(AnnArgs a, CameraRow c) {
     extern __shared__ int s_env[];              // [W0]: the nearest-resize column table, then the envelope | hit bits [W / 32], [H / 32]
     __shared__ int s_fab[VTI_MEASURE_MAX_DET][5];       // instance i (< 0: a filled box), first and last row, first and last column
     __shared__ int s_nfab, s_w[kThreads / 64];
     const int tid = threadIdx.x, k = blockIdx.x, M = a.max_det;
     const int b = min(max(a.select[k], 0), a.B - 1);
-    const int H0 = a.H0, W0 = a.W0, WW = a.WW;
+    const Geo geo = TABLE ? frame_geo(a, b) : Geo{a.H0, a.W0, a.WW};
+    const int H0 = geo.H0, W0 = geo.W0, WW = geo.WW;
     Rec* recs = a.recs + (size_t)k * nrec(M);
     int* meta = a.meta + (size_t)k * META_INTS;
     for (int i = tid; i < nrec(M); i += kThreads) recs[i] = Rec{K_NOP, 0, 0, 0, 0, 0, 0, 0};
     if (tid < META_INTS) meta[tid] = 0;
     if (tid == 0) { a.status_out[k] = 0; s_nfab = 0; }
+    if (TABLE) {
+        const int ci = a.cam_of_frame ? a.cam_of_frame[b] : 0;
+        if (ci < 0 || ci >= a.n_cams) return;   // uniform; no table address has been formed: a plain copy
+        c = a.table[ci];
+    }
     const int status = a.frame_i32[6 * (size_t)b];
     if (status != VTI_MEASURE_OK && status != VTI_MEASURE_NO_FABRIC && status != VTI_MEASURE_NO_STITCHES) return;   // a plain copy
     const int stitch_id = c.stitch_id, fabric_id = c.fabric_id, drop_empty = c.drop_empty;
@@ -747,26 +757,32 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
     return launch_outline_raster(a, L, fr, st);
 }
 
-hipError_t launch_annotate_checker(const vti_checker_params& p, const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
+hipError_t launch_annotate_checker(const vti_checker_params* p, const void* cameras, int n_cams, const int* cam_of_frame,
+                                   const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
                                    int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det,
                                    int nm, int capacity, int H, int W, const int* frame_i32, const double* stitch_f64,
                                    const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
-                                   void* scratch, hipStream_t st) {
+                                   void* scratch, hipStream_t st, const AnnotateFrames* fr) {
+    if (!p && !cameras) return hipErrorInvalidValue;
+    if (fr && (p || native)) return hipErrorInvalidValue;
     AnnotateLayout L;
     annotate_layout(n_sel, max_det, H0, W0, max_points, L);
-    const AnnArgs a = annotate_args(L, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, nm, capacity, H, W,
-                                    frame_i32, stitch_f64, stitch_i32, select, n_sel, max_points, C_ENVELOPE, out, status, scratch);
+    AnnArgs a = annotate_args(L, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, nm, capacity, H, W,
+                              frame_i32, stitch_f64, stitch_i32, select, n_sel, max_points, C_ENVELOPE, out, status, scratch);
     CameraRow c;
-    checker_pack(p, &c);
-    if (native) {
-        hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, dim3(n_sel), dim3(kThreads), (size_t)W0 * sizeof(int), st, a, c);
-    } else {            // the envelope table and the bits of the source columns and rows the resize reads
-        const size_t lds = ((size_t)W0 + (size_t)((W + 31) / 32) + (size_t)((H + 31) / 32)) * sizeof(int);
-        hipLaunchKernelGGL(annotate_checker_prep_kernel<false>, dim3(n_sel), dim3(kThreads), lds, st, a, c);
-    }
+    memset(&c, 0, sizeof c);
+    if (p) checker_pack(*p, &c);
+    else { a.table = (const CameraRow*)cameras; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
+    if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; }
+    // not native: the envelope table and the bits of the source columns and rows the resize reads
+    const size_t lds = native ? (size_t)W0 * sizeof(int) : ((size_t)W0 + (size_t)((W + 31) / 32) + (size_t)((H + 31) / 32)) * sizeof(int);
+    if (p && native) hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, dim3(n_sel), dim3(kThreads), lds, st, a, c);
+    else if (p) hipLaunchKernelGGL(annotate_checker_prep_kernel<false>, dim3(n_sel), dim3(kThreads), lds, st, a, c);
+    else if (native) hipLaunchKernelGGL((annotate_checker_prep_kernel<true, true>), dim3(n_sel), dim3(kThreads), lds, st, a, c);
+    else hipLaunchKernelGGL((annotate_checker_prep_kernel<false, true>), dim3(n_sel), dim3(kThreads), lds, st, a, c);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_outline_raster(a, L, nullptr, st);
+    return launch_outline_raster(a, L, fr, st);
 }
 
 }  // namespace vti

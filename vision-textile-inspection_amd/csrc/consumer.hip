@@ -787,18 +787,44 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
 // a box contributes max(y1, 0) to the columns it covers: one more `min`.  Needs the per-slot stats (m00 decides mask or box) and,
 // for letterbox slots, the raw emptiness (drop_empty), so it runs after mask_stats_bits_kernel.  The instance list is walked by
 // index i < counts[b]: a slot at or beyond `capacity` is an empty mask, which still has a box.
-template <bool NATIVE>
+// RIG (vti_measure_checker_cameras / _frames / _frames_native): fabric_id and drop_empty come from row cam_of_frame[b] of the camera
+// table, range-checked against n_cams before the row's address is formed (a frame whose index is outside gets an all -1 envelope);
+// with `frames`, H0 and W0 are frame b's, the W0 passed is the largest one (the pitch of the envelope rows, which the grid covers)
+// and a workgroup past the frame's columns returns without writing, as in envelope_bits_kernel.  With `bases` too (NATIVE) the
+// masks are the ragged rows of vti_masks_native_frames: 2 ceil(W0 / 64) words per row from bases[b] on, and the frame's live slots
+// are those that end at or before capacity_bytes; a later one is what a slot at or beyond `capacity` is, an empty mask with a box.
+// Without RIG none of this is compiled in.
+template <bool NATIVE, bool RIG = false>
 __global__ __launch_bounds__(256) void upper_envelope_bits_kernel(const unsigned* __restrict__ bits, const int* __restrict__ offsets,
                                                                   const int* __restrict__ counts, const float* __restrict__ dets,
                                                                   int max_det, int row, int capacity, int cls, int drop_empty, int H,
                                                                   int W, int H0, int W0, const long long* __restrict__ stats,
                                                                   const int* __restrict__ raw, const float* __restrict__ xyxy,
-                                                                  int native_wpr, int* __restrict__ envelope) {
+                                                                  int native_wpr, int* __restrict__ envelope,
+                                                                  const CameraRow* __restrict__ table = nullptr,
+                                                                  const int* __restrict__ cam_of_frame = nullptr, int n_cams = 0,
+                                                                  const FrameRow* __restrict__ frames = nullptr,
+                                                                  const long long* __restrict__ bases = nullptr,
+                                                                  long long capacity_bytes = 0) {
     extern __shared__ int yf[];             // [H] (not NATIVE)
     __shared__ int red[4][64];
     __shared__ int s_sel[256][5];           // slot (-1: a box), first row, last row, first column, last column
     __shared__ int s_nsel;
     const int tid = threadIdx.x, b = blockIdx.y;
+    const int pitch = W0;                   // of the envelope rows: W0, or the largest W0 of a frame table
+    if (RIG) {
+        if (frames) {
+            H0 = frames[b].H0; W0 = frames[b].W0;
+            if ((int)blockIdx.x * 64 >= W0) return;             // columns this frame does not have: nothing is written
+        }
+        const int ci = cam_of_frame[b];
+        if (ci < 0 || ci >= n_cams) {                           // uniform over the workgroup
+            const int xo = blockIdx.x * 64 + tid;
+            if (tid < 64 && xo < W0) envelope[(size_t)b * pitch + xo] = -1;
+            return;
+        }
+        cls = table[ci].fabric_id; drop_empty = table[ci].drop_empty;
+    }
     if (!NATIVE) {
         for (int i = tid; i < H; i += 256) yf[i] = INT_MAX;
         __syncthreads();
@@ -809,9 +835,18 @@ __global__ __launch_bounds__(256) void upper_envelope_bits_kernel(const unsigned
     const int x = blockIdx.x * 64 + (tid & 63), rg = tid >> 6;
     const int xc = x < W0 ? x : W0 - 1;
     const int sx = NATIVE ? xc : nn_src(xc, 1.0 / ((double)W0 / (double)W), W);
-    const int wpr = NATIVE ? native_wpr : W >> 5;
+    const bool ragged = RIG && NATIVE && bases;
+    const int wpr = NATIVE ? (ragged ? 2 * ((W0 + 63) / 64) : native_wpr) : W >> 5;
     const int Hm = NATIVE ? H0 : H;         // rows of a mask slot
     const int s0 = offsets[b], n = min(max(counts[b], 0), max_det);
+    int srel = 0;                           // `bits` is where slot `srel` starts
+    if (ragged) {                           // the instances whose slot ends at or before capacity_bytes; none if the base is no offset
+        const long long base = bases[b], slot_bytes = (long long)Hm * wpr * 4;
+        const long long fit = base >= 0 && !(base & 7) && capacity_bytes > base ? (capacity_bytes - base) / slot_bytes : 0;
+        capacity = (int)min((long long)capacity, (long long)s0 + fit);
+        if (fit > 0) bits += base >> 2;
+        srel = s0;
+    }
     int env = INT_MAX;
     for (int i0 = 0; i0 < n; i0 += 256) {
         __syncthreads();                                       // the previous round's list has been consumed
@@ -849,7 +884,7 @@ __global__ __launch_bounds__(256) void upper_envelope_bits_kernel(const unsigned
                 if (xc >= s_sel[j][3] && xc <= s_sel[j][4]) env = min(env, ya);
                 continue;
             }
-            const unsigned* m = bits + (size_t)s * Hm * wpr + (sx >> 5);
+            const unsigned* m = bits + (size_t)(s - srel) * Hm * wpr + (sx >> 5);
             for (int sy = ya + rg; sy <= yb && (!NATIVE || sy < env); sy += 4) {    // top first: a lane's first hit is its smallest
                 if ((m[(size_t)sy * wpr] >> (sx & 31)) & 1u) {
                     const int y = NATIVE ? sy : yf[sy];
@@ -862,7 +897,7 @@ __global__ __launch_bounds__(256) void upper_envelope_bits_kernel(const unsigned
     __syncthreads();
     if (rg == 0 && x < W0) {
         const int e = min(min(red[0][tid], red[1][tid]), min(red[2][tid], red[3][tid]));
-        envelope[(size_t)b * W0 + x] = e == INT_MAX ? -1 : e;
+        envelope[(size_t)b * pitch + x] = e == INT_MAX ? -1 : e;
     }
 }
 
@@ -872,13 +907,18 @@ struct CheckerArgs {
     const float* dets; const float* xyxy; const int* counts; const int* offsets;
     int max_det, row, capacity, H0, W0;
     double* frame_f64; int* frame_i32; double* stitch_f64; int* stitch_i32;
+    // the rig forms (checker_frames_kernel<true>): a.cam unused, the row is table[cam_of_frame[b]]
+    const CameraRow* table; const int* cam_of_frame; int n_cams;
+    const FrameRow* frames;                                         // per-frame H0, W0 (then W0 above is the envelope pitch), or nullptr
+    const long long* bases; long long capacity_bytes;               // the ragged native rows (with frames), or nullptr
 };
 
 // Centroid and column extent of instance i of frame b (:365-391): the mask's moments and extent, else the int box.  true: from the mask.
-__device__ __forceinline__ bool checker_stitch_geometry(const CheckerArgs& a, int b, int i, int s, double& cx, double& cy, double& left,
-                                                        double& right) {
+// cap: the frame's first slot that is not live.
+__device__ __forceinline__ bool checker_stitch_geometry(const CheckerArgs& a, int cap, int b, int i, int s, double& cx, double& cy,
+                                                        double& left, double& right) {
     const long long* m = a.stats + (size_t)s * 5;
-    if (s >= 0 && s < a.capacity && m[0] > 0) {
+    if (s >= 0 && s < cap && m[0] > 0) {
         cx = (double)m[1] / (double)m[0]; cy = (double)m[2] / (double)m[0];
         left = (double)m[3]; right = (double)m[4];
         return true;
@@ -892,6 +932,11 @@ __device__ __forceinline__ bool checker_stitch_geometry(const CheckerArgs& a, in
 
 // One workgroup per frame, as measure_frames_kernel: 1. stitch list and fabric count, 2. status, 3. centroids and the proximity
 // flag, 4. row selection, 5. the final set, 6. a lane per final stitch: edge, distance, width, 7. the ordered lists and their means.
+// TABLE: the frame's settings are row cam_of_frame[b] of the camera table, copied once before anything is stored (an index outside
+// the table leaves by measure_frames_kernel's BAD_CAMERA path); W0 and the ragged rows' live slots per frame as in
+// upper_envelope_bits_kernel.  Otherwise the row in the launch arguments and one size.  Either way the arithmetic below sees the
+// same values in the same order.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
     extern __shared__ double csm[];        // M = max_det: cy | width | dist | g0 | g1 (f64), then idx | flags | lab0 | lab1 (i32)
     const int M = a.max_det;
@@ -902,10 +947,37 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
     __shared__ int s_ec[4], s_pick[2];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
-    const int W0 = a.W0;
-    const int* env = a.envelope + (size_t)b * W0;
+    const int* env = a.envelope + (size_t)b * a.W0;
     const double NaN = __builtin_nan("");
-    const CameraRow& r = a.cam;
+    int W0 = a.W0, cap = a.capacity;
+    CameraRow row_b;
+    if (TABLE) {
+        if (a.frames) {
+            W0 = a.frames[b].W0;
+            if (a.bases) {                      // the ragged rows: the slots that end at or before capacity_bytes are live
+                const long long base = a.bases[b], slot_bytes = (long long)a.frames[b].H0 * (2 * ((W0 + 63) / 64)) * 4;
+                const long long fit = base >= 0 && !(base & 7) && a.capacity_bytes > base ? (a.capacity_bytes - base) / slot_bytes : 0;
+                cap = (int)min((long long)cap, (long long)s0 + fit);
+            }
+        }
+        const int ci = a.cam_of_frame[b];
+        if (ci < 0 || ci >= a.n_cams) {         // uniform over the workgroup; no table address has been formed
+            for (int i = tid; i < n; i += 256) {
+                const int s = s0 + i;
+                if (s < 0 || s >= cap) continue;
+                if (a.stitch_f64) for (int k = 0; k < 7; ++k) a.stitch_f64[(size_t)s * 7 + k] = NaN;
+                if (a.stitch_i32) { a.stitch_i32[(size_t)s * 2] = 0; a.stitch_i32[(size_t)s * 2 + 1] = -1; }
+            }
+            if (tid == 0) {
+                a.frame_f64[2 * b] = NaN; a.frame_f64[2 * b + 1] = NaN;
+                int* o = a.frame_i32 + 6 * b;
+                o[0] = VTI_MEASURE_BAD_CAMERA; o[1] = o[2] = o[3] = o[4] = o[5] = 0;
+            }
+            return;
+        }
+        row_b = a.table[ci];
+    }
+    const CameraRow& r = TABLE ? row_b : a.cam;
 
     // 1. stitch list and fabric count (:310-336)
     int n_st = 0, n_fab = 0;
@@ -913,7 +985,7 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
         const int i = c0 + tid, s = s0 + i;
         bool st = false, fab = false;
         if (i < n) {
-            const bool live = s >= 0 && s < a.capacity;
+            const bool live = s >= 0 && s < cap;
             const bool raw = live && (a.raw ? a.raw[s] != 0 : a.stats[(size_t)s * 5] > 0);
             const int cls = (int)a.dets[((size_t)b * M + i) * a.row + 5];
             const bool keep = !r.drop_empty || raw;
@@ -945,7 +1017,7 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
     for (int j = tid; j < n_st; j += 256) {
         const int i = s_idx[j], s = s0 + i;
         double cx, cy, left, right;
-        int fl = VTI_STITCH_KEPT | (checker_stitch_geometry(a, b, i, s, cx, cy, left, right) ? VTI_STITCH_MASK : 0);
+        int fl = VTI_STITCH_KEPT | (checker_stitch_geometry(a, cap, b, i, s, cx, cy, left, right) ? VTI_STITCH_MASK : 0);
         if (status == VTI_MEASURE_OK) {
             double med;
             if (env_median(env, W0, (int)rint(cx), r.nb, med)) {           // python round(): half to even; the centre is not clipped
@@ -955,7 +1027,7 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
         }
         s_cy[j] = cy; s_wd[j] = NaN; s_ds[j] = NaN; s_fl[j] = fl;
         lab0[j] = 0;
-        if (s >= 0 && s < a.capacity && a.stitch_f64) {
+        if (s >= 0 && s < cap && a.stitch_f64) {
             double* o = a.stitch_f64 + (size_t)s * 7;
             o[0] = cx; o[1] = cy; o[2] = left; o[3] = right; o[4] = NaN; o[5] = NaN; o[6] = NaN;
         }
@@ -995,7 +1067,7 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
             if (!((fl & VTI_STITCH_SELECTED) && (!near || (fl & VTI_STITCH_NEAR)))) continue;
             const int i = s_idx[j], s = s0 + i;
             double cx, cy, left, right, ed = NaN, ds = NaN, wd = NaN, med;
-            (void)checker_stitch_geometry(a, b, i, s, cx, cy, left, right);
+            (void)checker_stitch_geometry(a, cap, b, i, s, cx, cy, left, right);
             double pc[3];
             const bool okc = pixel_to_world(r.g, cx, cy, pc);
             if (env_median(env, W0, min(max((int)rint(cx), 0), W0 - 1), r.nb, med)) {
@@ -1010,7 +1082,7 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
                 wd = ((right - left) / 10.0) * dist_mm(pr, pc); fl |= VTI_STITCH_WIDTH;
             }
             s_wd[j] = wd; s_ds[j] = ds; s_fl[j] = fl;
-            if (s >= 0 && s < a.capacity && a.stitch_f64) {
+            if (s >= 0 && s < cap && a.stitch_f64) {
                 double* o = a.stitch_f64 + (size_t)s * 7;
                 o[4] = wd; o[5] = ed; o[6] = ds;
             }
@@ -1032,7 +1104,7 @@ __global__ __launch_bounds__(256) void checker_frames_kernel(CheckerArgs a) {
         n_d += td; n_w += tw; n_sel += ts;
         if (j < n_st && a.stitch_i32) {
             const int s = s0 + s_idx[j];
-            if (s >= 0 && s < a.capacity) { a.stitch_i32[(size_t)s * 2] = fl & 63; a.stitch_i32[(size_t)s * 2 + 1] = j; }
+            if (s >= 0 && s < cap) { a.stitch_i32[(size_t)s * 2] = fl & 63; a.stitch_i32[(size_t)s * 2 + 1] = j; }
         }
     }
     __syncthreads();
@@ -1056,11 +1128,18 @@ void checker_pack(const vti_checker_params& p, void* row) {
     memcpy(row, &c, sizeof c);
 }
 
-hipError_t launch_measure_checker(const vti_checker_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
-                                  const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0,
-                                  int W0, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32,
-                                  hipStream_t st) {
+// p: the one camera (vti_measure_checker), or nullptr with a device table of n_cams rows and the frames' indices; frames, bases and
+// capacity_bytes as launch_measure takes them.  The one-struct, one-size call launches the instantiations without RIG / TABLE.
+hipError_t launch_measure_checker(const vti_checker_params* p, const void* table, int n_cams, const int* cam_of_frame,
+                                  const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
+                                  const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
+                                  const FrameRow* frames, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64,
+                                  int* stitch_i32, hipStream_t st, const long long* bases, long long capacity_bytes) {
     if (B == 0) return hipSuccess;
+    if (!p && (!table || !cam_of_frame)) return hipErrorInvalidValue;
+    if (p && frames) return hipErrorInvalidValue;
+    if (frames && native && (!bases || capacity_bytes < 0)) return hipErrorInvalidValue;
+    if (!(frames && native)) bases = nullptr;
     size_t off[3], total;
     measure_scratch_layout(B, capacity, W0, off, total);
     long long* stats = (long long*)((char*)scratch + off[0]);
@@ -1070,36 +1149,56 @@ hipError_t launch_measure_checker(const vti_checker_params& p, const uint8_t* ma
     const int wpr = native ? 2 * ((W0 + 63) / 64) : W / 32;
     CheckerArgs a;
     memset(&a, 0, sizeof a);
-    checker_pack(p, &a.cam);
+    if (p) checker_pack(*p, &a.cam);
+    else { a.table = (const CameraRow*)table; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
     if (!native && ((W & 31) || (H & 31) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024)) return hipErrorInvalidValue;
     if (capacity > 0) {
-        if (native)             // frame-size rows: the identity branch, as vti_measure
+        if (native && frames)   // the ragged frame-size rows, as vti_measure_frames_native
+            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false, true, true>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live,
+                               0, 0, 0, 0, stats, (int*)nullptr, offsets, frames, B, bases, capacity_bytes);
+        else if (native)        // frame-size rows: the identity branch, as vti_measure
             hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
                                32 * wpr, H0, 32 * wpr, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
         else {
             if ((uintptr_t)masks & 15) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
-                               (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, (const int*)nullptr, (const FrameRow*)nullptr, 0);
+            if (frames)
+                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, offsets, frames, B);
+            else
+                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, (const int*)nullptr,
+                                   (const FrameRow*)nullptr, 0);
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (native)
-        hipLaunchKernelGGL(upper_envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets,
+    const dim3 egrid((W0 + 63) / 64, B);
+    if (native && p)
+        hipLaunchKernelGGL(upper_envelope_bits_kernel<true>, egrid, dim3(256), 0, st, (const unsigned*)masks, offsets,
                            counts, dets, max_det, 6 + nm, capacity, a.cam.fabric_id, a.cam.drop_empty, H0, W0, H0, W0, stats,
                            (const int*)nullptr, xyxy, wpr, env);
-    else
-        hipLaunchKernelGGL(upper_envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
+    else if (p)
+        hipLaunchKernelGGL(upper_envelope_bits_kernel<false>, egrid, dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
                            offsets, counts, dets, max_det, 6 + nm, capacity, a.cam.fabric_id, a.cam.drop_empty, H, W, H0, W0, stats, raw,
                            xyxy, 0, env);
+    else if (native)
+        hipLaunchKernelGGL((upper_envelope_bits_kernel<true, true>), egrid, dim3(256), 0, st, (const unsigned*)masks, offsets, counts, dets,
+                           max_det, 6 + nm, capacity, 0, 0, H0, W0, H0, W0, stats, (const int*)nullptr, xyxy, wpr, env, a.table,
+                           a.cam_of_frame, a.n_cams, frames, bases, capacity_bytes);
+    else
+        hipLaunchKernelGGL((upper_envelope_bits_kernel<false, true>), egrid, dim3(256), (size_t)H * 4, st, (const unsigned*)masks, offsets,
+                           counts, dets, max_det, 6 + nm, capacity, 0, 0, H, W, H0, W0, stats, raw, xyxy, 0, env, a.table,
+                           a.cam_of_frame, a.n_cams, frames, (const long long*)nullptr, 0ll);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
     a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
     a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0;
+    a.frames = frames; a.bases = bases; a.capacity_bytes = capacity_bytes;
     a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
     const size_t lds = (size_t)max_det * (5 * sizeof(double) + 4 * sizeof(int));
-    hipLaunchKernelGGL(checker_frames_kernel, dim3(B), dim3(256), lds, st, a);
+    if (p) hipLaunchKernelGGL(checker_frames_kernel<false>, dim3(B), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(checker_frames_kernel<true>, dim3(B), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

@@ -1068,21 +1068,38 @@ int32_t vti_measure(vti_ctx* c, const vti_measure_params* p, const uint8_t* mask
                         scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
 }
 
+// vti_measure_checker and its rig forms, as measure_impl serves vti_measure's: exactly one of p and (table, cam_of_frame) is given;
+// frames, bases and capacity_bytes as there.  Every check comes before the first HIP call.
+static int32_t checker_impl(const char* fn, vti_ctx* c, const vti_checker_params* p, const void* table, int32_t n_cams,
+                            const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
+                            const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity, int32_t H0,
+                            int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
+                            int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr, const int64_t* bases = nullptr,
+                            int64_t capacity_bytes = 0) {
+    if (frames && native == 1 && !bases)
+        return refuse(c, fn, "native masks need frames of one size (vti_measure_checker_cameras)", VTI_ERR_UNSUPPORTED);
+    if (bases && (capacity_bytes < 0 || ((uintptr_t)bases & 7))) return refuse(c, fn, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
+    if (p)
+        if (const char* e = settings_error(*p)) return refuse(c, fn, e);
+    VTI_TRY(measure_args_check(fn, c, VTI_ERR_ARG, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0, scratch,
+                               scratch_bytes, frame_f64, frame_i32));
+    if (B == 0) return VTI_OK;
+    VTI_TRY(check_device(c, fn));
+    const vti_desc& d = c->plan.desc;
+    VTI_HIP(c, launch_measure_checker(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm,
+                                      capacity, d.H, d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32,
+                                      (hipStream_t)stream, (const long long*)bases, capacity_bytes), "measure_checker kernels");
+    return VTI_OK;
+}
+
 int32_t vti_measure_checker(vti_ctx* c, const vti_checker_params* p, const uint8_t* masks, int32_t native, const float* dets,
                             const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det,
                             int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64,
                             int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
     const char* fn = "vti_measure_checker";
     if (!c || !p) return refuse(c, fn, "null ctx or params");
-    if (const char* e = settings_error(*p)) return refuse(c, fn, e);
-    VTI_TRY(measure_args_check(fn, c, VTI_ERR_ARG, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0, scratch,
-                               scratch_bytes, frame_f64, frame_i32));
-    if (B == 0) return VTI_OK;
-    VTI_TRY(check_device(c, fn));
-    const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_measure_checker(*p, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H, d.W, H0, W0, scratch,
-                                      frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream), "measure_checker kernels");
-    return VTI_OK;
+    return checker_impl(fn, c, p, nullptr, 0, nullptr, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0, scratch,
+                        scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
 }
 
 int64_t vti_measure_cameras_bytes(int32_t n_cams) {
@@ -1149,6 +1166,65 @@ int32_t vti_measure_frames_native(vti_ctx* c, const void* cameras, int32_t n_cam
         return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
     return measure_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B,
                         max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
+                        frame_rows(dev_table), mask_bases, capacity_bytes);
+}
+
+// ---- the stitch-distance checker on a rig: the camera table and the frame table forms of vti_measure_checker -------------------
+int32_t vti_checker_pack_cameras(vti_ctx* c, const vti_checker_params* params, int32_t n_cams, void* host_table, size_t nbytes) {
+    if (!params || n_cams < 1 || !host_table) return fail(c, VTI_ERR_ARG, "vti_checker_pack_cameras: null list or table, or n_cams < 1");
+    if ((int64_t)nbytes < vti_measure_cameras_bytes(n_cams))
+        return fail(c, VTI_ERR_ARG, "vti_checker_pack_cameras: table smaller than vti_measure_cameras_bytes()");
+    for (int32_t k = 0; k < n_cams; ++k)
+        if (const char* e = settings_error(params[k])) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "vti_checker_pack_cameras: camera %d: %s", k, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    for (int32_t k = 0; k < n_cams; ++k) checker_pack(params[k], (char*)host_table + (size_t)k * measure_camera_row_bytes());
+    return VTI_OK;
+}
+
+int32_t vti_measure_checker_cameras(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                    int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
+                                    int32_t B, int32_t max_det, int32_t capacity, int32_t H0, int32_t W0, void* scratch,
+                                    size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
+                                    void* stream) {
+    const char* fn = "vti_measure_checker_cameras";
+    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
+    return checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity,
+                        H0, W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
+}
+
+int32_t vti_measure_checker_frames(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                   int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
+                                   const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity,
+                                   void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
+                                   int32_t* stitch_i32, void* stream) {
+    const char* fn = "vti_measure_checker_frames";
+    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    return checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity,
+                        h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
+                        frame_rows(dev_table));
+}
+
+int32_t vti_measure_checker_frames_native(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame,
+                                          const uint8_t* masks, const int64_t* mask_bases, int64_t capacity_bytes, const float* dets,
+                                          const float* xyxy, const int32_t* counts, const int32_t* offsets, const void* host_table,
+                                          const void* dev_table, int32_t B, int32_t max_det, int32_t capacity, void* scratch,
+                                          size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
+                                          int32_t* stitch_i32, void* stream) {
+    const char* fn = "vti_measure_checker_frames_native";
+    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    if (!mask_bases) return refuse(c, fn, "null dev_mask_bases");
+    if (capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
+    if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
+        return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
+    return checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B, max_det, capacity,
+                        h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
                         frame_rows(dev_table), mask_bases, capacity_bytes);
 }
 
@@ -1250,24 +1326,32 @@ int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, i
 }
 
 // ---- vti_annotate_checker: the stitch-distance checker's picture -------------------------------------------------------------
-int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const vti_checker_params* p,
-                             const uint8_t* masks, int32_t native, const float* dets, const float* xyxy, const int32_t* counts,
-                             const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
-                             const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
-                             int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
-                             void* stream) {
-    // every check comes before the first HIP call: vti_annotate's, and vti_measure_checker's of the params
-    const char* fn = "vti_annotate_checker";
-    if (!c || !p) return refuse(c, fn, "null ctx or params");
-    if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-        return refuse(c, fn, "bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+// vti_annotate_checker (p) and vti_annotate_checker_cameras (the checker's camera table): every check comes before the first HIP
+// call: vti_annotate's, and vti_measure_checker's of the params
+static int32_t annotate_checker_impl(const char* fn, vti_ctx* c, const vti_checker_params* p, const void* cameras, int32_t n_cams,
+                                     const int32_t* cam_of_frame, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0,
+                                     const uint8_t* masks, int32_t native, const float* dets, const float* xyxy, const int32_t* counts,
+                                     const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                                     const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select,
+                                     const int32_t* dev_select, int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status,
+                                     void* scratch, size_t scratch_bytes, void* stream) {
+    if (p) {
+        if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
+            return refuse(c, fn, "bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                                 "1 <= H0, W0 <= 8192; native 0 or 1)");
+    } else if (B < 1 || capacity < 0 || n_cams < 1 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
+        return refuse(c, fn, "bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
                              "1 <= H0, W0 <= 8192; native 0 or 1)");
-    if (!frames || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select || !dev_select ||
-        !out || !status || (capacity && !masks))
+    if (!frames || (!p && !cameras) || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
+        !dev_select || !out || !status || (capacity && !masks))
         return refuse(c, fn, "null pointer");
-    if (const char* e = settings_error(*p)) return refuse(c, fn, e);
+    if (p)
+        if (const char* e = settings_error(*p)) return refuse(c, fn, e);
     VTI_TRY(select_check(fn, c, host_select, n_sel, B));
-    if ((uintptr_t)dev_select & 3) return refuse(c, fn, "the selection must be 4-byte aligned");
+    if (p) {
+        if ((uintptr_t)dev_select & 3) return refuse(c, fn, "the selection must be 4-byte aligned");
+    } else if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
+        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
     VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
     if (!native && ((c->plan.desc.W & 31) || (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024))
         return refuse(c, fn, "letterbox size unsuitable for the resize tables");
@@ -1276,10 +1360,37 @@ int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32
                           "vti_annotate_scratch_bytes()"));
     VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_annotate_checker(*p, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, d.nm, capacity, d.H,
-                                       d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status, scratch,
-                                       (hipStream_t)stream), "annotate_checker kernels");
+    VTI_HIP(c, launch_annotate_checker(p, cameras, n_cams, cam_of_frame, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets,
+                                       max_det, d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel,
+                                       max_points, out, status, scratch, (hipStream_t)stream), "annotate_checker kernels");
     return VTI_OK;
+}
+
+int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const vti_checker_params* p,
+                             const uint8_t* masks, int32_t native, const float* dets, const float* xyxy, const int32_t* counts,
+                             const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                             const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
+                             int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
+                             void* stream) {
+    const char* fn = "vti_annotate_checker";
+    if (!c || !p) return refuse(c, fn, "null ctx or params");
+    return annotate_checker_impl(fn, c, p, nullptr, 0, nullptr, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det,
+                                 capacity, frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status,
+                                 scratch, scratch_bytes, stream);
+}
+
+int32_t vti_annotate_checker_cameras(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const void* cameras,
+                                     int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
+                                     const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
+                                     int32_t max_det, int32_t capacity, const int32_t* frame_i32, const double* stitch_f64,
+                                     const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select, int32_t n_sel,
+                                     int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
+                                     void* stream) {
+    const char* fn = "vti_annotate_checker_cameras";
+    if (!c) return refuse(c, fn, "null ctx");
+    return annotate_checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, frames, B, H0, W0, masks, native, dets, xyxy, counts,
+                                 offsets, max_det, capacity, frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel,
+                                 max_points, out, status, scratch, scratch_bytes, stream);
 }
 
 // ---- vti_overlay: the model-check viewer's picture ---------------------------------------------------------------------------
@@ -1393,7 +1504,9 @@ static int32_t selection_walk(const char* fn, vti_ctx* c, const void* host_table
     return VTI_OK;
 }
 
-int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+// vti_annotate_frames and vti_annotate_checker_frames (checker: the table is the checker's, the prep kernel the checker's own)
+static int32_t annotate_frames_impl(const char* fn, const char* out_fn, const char* one_size, bool checker, vti_ctx* c,
+                            const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
                             const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
                             const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
                             int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
@@ -1401,13 +1514,12 @@ int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_
                             const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
                             size_t scratch_bytes, void* stream) {
     // every check comes before the first HIP call
-    const char* fn = "vti_annotate_frames";
     if (!c) return refuse(c, fn, "null ctx");
     FrameTableHeader h;
     VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
     if (n_sel < 1) return refuse(c, fn, "n_sel must be >= 1");
-    VTI_TRY(frames_check("vti_annotate_frames (out table)", c, host_out_table, dev_out_table, n_sel, h));
-    if (native == 1) return refuse(c, fn, "native masks need frames of one size (vti_annotate)", VTI_ERR_UNSUPPORTED);
+    VTI_TRY(frames_check(out_fn, c, host_out_table, dev_out_table, n_sel, h));
+    if (native == 1) return refuse(c, fn, one_size, VTI_ERR_UNSUPPORTED);
     if (capacity < 0 || n_cams < 1 || native != 0 || max_det < 1 || max_det > VTI_MEASURE_MAX_DET || max_points < 0)
         return refuse(c, fn, "bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
     if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
@@ -1427,13 +1539,49 @@ int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_
     VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
     VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, s.mh, s.mw, max_points),
                           "vti_annotate_frames_scratch_bytes()"));
-    VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
+    if (checker && ((d.W & 31) || (size_t)(4 * d.W + 2 * d.H) * 4 > 60 * 1024))
+        return refuse(c, fn, "letterbox size unsuitable for the resize tables");
+    VTI_TRY(check_device(c, fn));
     const AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), s.any_lds, s.any_global, s.max_px};
+    if (checker) {
+        VTI_HIP(c, launch_annotate_checker(nullptr, cameras, n_cams, cam_of_frame, frames, B, s.mh, s.mw, masks, 0, dets, xyxy, counts,
+                                           offsets, max_det, d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select,
+                                           n_sel, max_points, out, status, scratch, (hipStream_t)stream, &fr), "annotate_checker kernels");
+        return VTI_OK;
+    }
     VTI_HIP(c, launch_annotate(frames, B, s.mh, s.mw, cameras, n_cams, cam_of_frame, masks, 0, dets, xyxy, counts, offsets, max_det, d.nm,
                                capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
                                scratch, (hipStream_t)stream, &fr), "annotate kernels");
     return VTI_OK;
+}
+
+
+int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                            const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
+                            const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
+                            int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                            const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                            const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+    return annotate_frames_impl("vti_annotate_frames", "vti_annotate_frames (out table)", "native masks need frames of one size (vti_annotate)", false,
+                               c, frames, host_table, dev_table, B, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det, capacity, frame_i32,
+                               stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, host_out_table, dev_out_table, out, status, scratch,
+                               scratch_bytes, stream);
+}
+
+int32_t vti_annotate_checker_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                            const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
+                            const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
+                            int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                            const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                            const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+    return annotate_frames_impl("vti_annotate_checker_frames", "vti_annotate_checker_frames (out table)",
+                               "native masks need frames of one size (vti_annotate_checker_cameras)", true,
+                               c, frames, host_table, dev_table, B, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det, capacity, frame_i32,
+                               stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, host_out_table, dev_out_table, out, status, scratch,
+                               scratch_bytes, stream);
 }
 
 int32_t vti_overlay_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,

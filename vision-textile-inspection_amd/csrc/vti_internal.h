@@ -358,11 +358,14 @@ hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_
                           int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st, const long long* bases = nullptr,
                           long long capacity_bytes = 0);
 
-// vti_measure_checker (Utils/check_stitch_distance.py): vti_measure's inputs, scratch layout and outputs; one frame size, one camera
-hipError_t launch_measure_checker(const vti_checker_params& p, const uint8_t* masks, int native, const float* dets, const float* xyxy,
-                                  const int* counts, const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0,
-                                  int W0, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64, int* stitch_i32,
-                                  hipStream_t st);
+// vti_measure_checker (Utils/check_stitch_distance.py) and its rig forms: vti_measure's inputs, scratch layout and outputs.
+// p != nullptr: one camera and one frame size; else table, n_cams, cam_of_frame, frames, bases and capacity_bytes as launch_measure
+// takes them (the table's rows are checker_pack's)
+hipError_t launch_measure_checker(const vti_checker_params* p, const void* table, int n_cams, const int* cam_of_frame,
+                                  const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
+                                  const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
+                                  const FrameRow* frames, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64,
+                                  int* stitch_i32, hipStream_t st, const long long* bases = nullptr, long long capacity_bytes = 0);
 // one validated vti_checker_params -> the CameraRow (measure_dev.h) the checker's kernels take by value (host)
 void checker_pack(const vti_checker_params& p, void* row);
 
@@ -401,12 +404,14 @@ hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const v
                            const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
                            int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
 // vti_annotate_checker (the stitch-distance checker's picture): the same scratch and the same outline and raster kernels behind a
-// prep kernel of its own; the rows are vti_measure_checker's, the settings travel by value
-hipError_t launch_annotate_checker(const vti_checker_params& p, const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
+// prep kernel of its own; the rows are vti_measure_checker's.  p != nullptr: the settings travel by value; else they are row
+// cam_of_frame[b] (nullptr: row 0) of the checker's camera table in device memory, and fr is launch_annotate's
+hipError_t launch_annotate_checker(const vti_checker_params* p, const void* cameras, int n_cams, const int* cam_of_frame,
+                                   const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
                                    int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det,
                                    int nm, int capacity, int H, int W, const int* frame_i32, const double* stitch_f64,
                                    const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
-                                   void* scratch, hipStream_t st);
+                                   void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
 
 // stamp.hip: vti_stamp / vti_stamp_frames (the text of the annotated pictures as 1-bit stamps).  The stamp table, host and device
 // copy alike: the header | n_pictures picture rows | n_stamps records.  Picture k owns the records [begin, end); the ranges follow each

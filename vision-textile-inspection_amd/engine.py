@@ -11,7 +11,7 @@ import torch
 
 from . import _lib, rawframes
 from . import overlay as _ov
-from ._lib import VtiConvInfo, VtiDesc, VtiMeasureParams, check, lib
+from ._lib import VtiCheckerParams, VtiConvInfo, VtiDesc, VtiMeasureParams, check, lib
 
 # "h2": split-fp16 storage (every element an fp16 (hi, lo) pair, all products on the fp16 matrix pipe): the dtype whose results
 # meet the reference tolerance (mask IoU >= 0.999, |d box| < 1e-3) at a multiple of the fp32 engine's rate -- include/vti.h
@@ -632,23 +632,86 @@ class Engine:
             check(self._ctx, lib().vti_measure(self._ctx, C.byref(cp), *rest))
         return r
 
-    def measure_checker(self, out, params, H0=None, W0=None, native=False, stitch_rows=True, result=None):
+    def pack_checker_cameras(self, params_list, device=None):
+        """The camera table of the checker's rig calls: one row per measure.CheckerParams (or VtiCheckerParams) of `params_list`,
+        validated and packed by vti_checker_pack_cameras (a VtiError names the failing index) and uploaded once.  -> u8 device tensor
+        to pass as measure_checker(..., params=table, cameras=...) and annotate_checker(...); row k is camera k.  Its rows are not
+        pack_cameras()' rows."""
+        cps = [p.to_c() if hasattr(p, "to_c") else p for p in params_list]
+        n = len(cps)
+        if n < 1:
+            raise ValueError("pack_checker_cameras: at least one camera")
+        arr = (VtiCheckerParams * n)(*cps)
+        nbytes = int(lib().vti_measure_cameras_bytes(n))
+        host = torch.empty(nbytes, dtype=torch.uint8)
+        check(self._ctx, lib().vti_checker_pack_cameras(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
+        return host.to(device or self.device or "cuda")
+
+    def _checker_table(self, who, params_or_table, dev):
+        """A list of CheckerParams or the table of pack_checker_cameras() -> (table, n_cams)."""
+        table = params_or_table if isinstance(params_or_table, torch.Tensor) else self.pack_checker_cameras(params_or_table, dev)
+        row = int(lib().vti_measure_cameras_bytes(1))
+        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
+            raise ValueError(f"{who}: params must be CheckerParams or the u8 table of pack_checker_cameras() on the outputs' device")
+        return table, table.numel() // row
+
+    def measure_checker(self, out, params, H0=None, W0=None, native=False, stitch_rows=True, result=None, cameras=None, frames=None):
         """The stitch-distance checker's per-frame measurement (Utils/check_stitch_distance.py:281-553) for every frame of an output
-        set, as measure() does process_frame's: vti_measure_checker.  params: a measure.CheckerParams (or a VtiCheckerParams).  One
-        frame size (H0, W0), one camera; native, stitch_rows, result and the returned dict of device tensors are measure()'s, with
-        the checker's meanings (include/vti.h): the upper fabric edge, the signed proximity test, widths for the final set only."""
+        set, as measure() does process_frame's: vti_measure_checker.  params: a measure.CheckerParams (or a VtiCheckerParams);
+        native, stitch_rows, result and the returned dict of device tensors are measure()'s, with the checker's meanings
+        (include/vti.h): the upper fabric edge, the signed proximity test, widths for the final set only.
+        cameras (vti_measure_checker_cameras): the camera of every frame, an int32 device tensor [B] (checked on the device: a frame
+        whose index is outside the table reports VTI_MEASURE_BAD_CAMERA) or a host sequence (range-checked here, ValueError); then
+        `params` is the table of pack_checker_cameras() or a list of CheckerParams (packed and uploaded on every call: pack once
+        instead).  frames (vti_measure_checker_frames): a FrameTable in place of H0, W0 -- frame b is measured at its own size;
+        letterbox bit masks, or with native=True the ragged rows of a set from alloc_outputs(native_frames=)
+        (vti_measure_checker_frames_native; the set needs mask_bases).  Without `cameras` the one `params` serves every frame."""
         dets, masks = out["dets"], out["masks"]
         B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
         dev = dets.device
-        if H0 is None or W0 is None:
-            raise ValueError("measure_checker: H0 and W0 are required")
-        cp = params.to_c() if hasattr(params, "to_c") else params
+        ragged = frames is not None and native and "mask_bases" in out
+        if frames is not None:
+            self._check_frames(frames, B=B)
+            if native and not ragged:
+                raise ValueError("measure_checker: frames of differing sizes have letterbox masks only (native=True needs one frame "
+                                 "size, or the ragged set of alloc_outputs(native_frames=) with its mask_bases)")
+            if ragged:
+                self._check_ragged(out, frames, max_det, "measure_checker")
+                if not (dets.is_cuda and masks.is_cuda and out["mask_bases"].is_cuda):
+                    raise ValueError("measure_checker: the output set must be in device memory")
+                capacity = B * max_det
+            if H0 is not None or W0 is not None:
+                raise ValueError("measure_checker: give H0, W0 or frames, not both")
+            H0, W0 = frames.max_H0, frames.max_W0
+            if cameras is None:
+                params, cameras = (params if isinstance(params, (list, tuple, torch.Tensor)) else [params]), [0] * B
+        elif H0 is None or W0 is None:
+            raise ValueError("measure_checker: H0 and W0 (or frames=) are required")
+        if cameras is not None:
+            if isinstance(params, (list, tuple)) and not isinstance(cameras, torch.Tensor):
+                cameras = _camera_index("measure_checker", cameras, B, len(params), "cpu")       # before anything is packed
+            table, n_cams = self._checker_table("measure_checker", params if isinstance(params, (list, tuple, torch.Tensor)) else [params], dev)
+            cameras = _camera_index("measure_checker", cameras, B, n_cams, dev)
+        else:
+            cp = params.to_c() if hasattr(params, "to_c") else params
         r = _measure_result(result, B, capacity, stitch_rows, dev)
         ws = self._scratch("_measure_ws", max(self.measure_scratch_bytes(B, capacity, W0), 256), dev)
-        check(self._ctx, lib().vti_measure_checker(
-            self._ctx, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]),
-            _ptr(out["counts"]), _ptr(out["offsets"]), B, max_det, capacity, int(H0), int(W0), _ptr(ws), ws.numel(),
-            _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")), _stream()))
+        head = (_ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]),
+                _ptr(out["offsets"]))
+        tail = (_ptr(ws), ws.numel(), _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")),
+                _stream())
+        rest = head + (B, max_det, capacity, int(H0), int(W0)) + tail
+        if ragged:
+            check(self._ctx, lib().vti_measure_checker_frames_native(
+                self._ctx, _ptr(table), n_cams, _ptr(cameras), _ptr(masks), _ptr(out["mask_bases"]), masks.numel(), *head[2:],
+                *frames._ptrs(), B, max_det, capacity, *tail))
+        elif frames is not None:
+            check(self._ctx, lib().vti_measure_checker_frames(self._ctx, _ptr(table), n_cams, _ptr(cameras), *head, *frames._ptrs(), B,
+                                                              max_det, capacity, *tail))
+        elif cameras is not None:
+            check(self._ctx, lib().vti_measure_checker_cameras(self._ctx, _ptr(table), n_cams, _ptr(cameras), *rest))
+        else:
+            check(self._ctx, lib().vti_measure_checker(self._ctx, C.byref(cp), *rest))
         return r
 
     # ---- process_frame's annotated frame (measurement.py:219-504): the overlay on a selection of the batch ------------------
@@ -732,42 +795,84 @@ class Engine:
         return r
 
     # ---- the stitch-distance checker's picture (Utils/check_stitch_distance.py:293-545): vti_annotate_checker ------------------
-    def annotate_checker(self, frames, out, meas, params, select, native=False, result=None, max_points=16384):
+    def annotate_checker(self, frames, out, meas, params, select, native=False, result=None, max_points=16384, cameras=None,
+                         table=None):
         """The frames `select` of the batch with the stitch-distance checker's picture drawn on them: vti_annotate_checker, byte for
         byte annotate.rasterise(frame, annotate.checker_display_list(...)).  frames, out, select, native, result, max_points and the
         returned dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]) of device tensors are annotate()'s uniform form (the frames feed
         encode_jpeg as they are); meas: measure_checker(..., stitch_rows=True)'s dict on the same set; params: the CheckerParams (or
-        VtiCheckerParams) of that call.  One frame size, one camera.  Text is the host's: measure.checker_text_items / put_text."""
-        B, H0, W0 = _uniform_frames("annotate_checker", frames)
+        VtiCheckerParams) of that call.  Text is the host's: measure.checker_text_items / put_text.
+        cameras (vti_annotate_checker_cameras): as measure_checker() took them; params is then a list of CheckerParams or the table
+        of pack_checker_cameras().  table (vti_annotate_checker_frames): the FrameTable of a batch whose frames differ in size;
+        `frames` is then the flat u8 device buffer it describes, and the call returns dict(buf, table, shapes, byte_offsets, status)
+        as annotate(table=) does: it feeds encode_jpeg(table=) and stamp(table=) unchanged.  Letterbox masks only with table=."""
+        who = "annotate_checker"
+        if table is not None:
+            self._check_frames(table)
+            if native:
+                raise ValueError("annotate_checker: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
+            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
+                raise ValueError("annotate_checker: with table=, frames must be the flat uint8 frame buffer")
+            B, H0, W0 = table.B, None, None
+        else:
+            B, H0, W0 = _uniform_frames(who, frames)
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
             raise ValueError(f"annotate_checker: {B} frames but an output set of {out['counts'].shape[0]}")
         max_det, capacity = dets.shape[1], masks.shape[0]
-        sel = _select("annotate_checker", select, B)
+        sel = _select(who, select, B)
         n_sel = int(sel.size)
         for key in ("frame_i32", "stitch_f64", "stitch_i32"):
             if meas.get(key) is None:
                 raise ValueError(f"annotate_checker: meas needs {key} (measure_checker(..., stitch_rows=True))")
+        rig = cameras is not None or table is not None or isinstance(params, (list, tuple, torch.Tensor))
+        if rig and isinstance(params, (list, tuple)) and cameras is not None and not isinstance(cameras, torch.Tensor):
+            cameras = _camera_index(who, cameras, B, len(params), "cpu")
         # everything above is about shapes and values; what needs a device comes from here on
         if not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("annotate_checker: frames must be the contiguous device batch predict consumed")
-        cp = params.to_c() if hasattr(params, "to_c") else params
+        if rig:
+            table_c, n_cams = self._checker_table(who, params if isinstance(params, (list, tuple, torch.Tensor)) else [params], dev)
+            if cameras is not None:
+                cameras = _camera_index(who, cameras, B, n_cams, dev, same_device=False)
+        else:
+            cp = params.to_c() if hasattr(params, "to_c") else params
         r = dict(result or {})
         if "status" not in r:
             r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
-        if "frames" not in r:
-            r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
-        need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
-        if need <= 0:
-            raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+        if table is not None:
+            self._check_frames(table, buf=frames)
+            shapes = tuple(table.shapes[int(b)] for b in sel)
+            out_table = self._out_table(shapes, dev)
+            self._selection_out(r, out_table, shapes, dev)
+            need = int(lib().vti_annotate_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
+            if need <= 0:
+                raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
+                                 f"{out_table.max_H0}x{out_table.max_W0}, max_points={max_points}; a drawn frame is at most 8192 x 8192)")
+        else:
+            if "frames" not in r:
+                r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
+            need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
+            if need <= 0:
+                raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
         ws = self._scratch("_annotate_ws", need, dev)
         dev_sel = torch.from_numpy(sel).to(dev)
-        check(self._ctx, lib().vti_annotate_checker(
-            self._ctx, _ptr(frames), B, H0, W0, C.byref(cp), _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets),
-            _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity, _ptr(meas["frame_i32"]),
-            _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(max_points),
-            _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        mid = (_ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity, _ptr(meas["frame_i32"]),
+               _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(max_points))
+        pm = _ptr(masks) if capacity else C.c_void_p(0)
+        if table is not None:
+            check(self._ctx, lib().vti_annotate_checker_frames(
+                self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras), pm, 0, *mid, *out_table._ptrs(),
+                _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        elif rig:
+            check(self._ctx, lib().vti_annotate_checker_cameras(
+                self._ctx, _ptr(frames), B, H0, W0, _ptr(table_c), n_cams, _ptr(cameras), pm, int(bool(native)), *mid,
+                _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        else:
+            check(self._ctx, lib().vti_annotate_checker(
+                self._ctx, _ptr(frames), B, H0, W0, C.byref(cp), pm, int(bool(native)), *mid,
+                _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         return r
 
     # ---- the model-check viewer's picture (Utils/check_model.py:155-256): vti_overlay ------------------------------------------

@@ -497,8 +497,8 @@ class MultiCameraMeasurer(_DeviceStage):
 class StitchDistanceChecker(_DeviceStage):
     """Utils/check_stitch_distance.py's StitchMeasurementApp.process_frame without the camera and the window: model = a vti_amd YOLO,
     params = CheckerParams.  One predict, one vti_measure_checker and one device -> host read per batch; the two smoothing deques
-    (:215-216, :519-530) live here, so consecutive calls continue one stream of frames.  Frames of one size, one camera; the
-    checker's picture (:293-545) is drawn on request, for a selection of the batch (`annotate=`): vti_annotate_checker paints it
+    (:215-216, :519-530) live here, so consecutive calls continue one stream of frames.  Frames of one size, one camera (a rig of
+    several cameras or resolutions: MultiCameraChecker); the checker's picture (:293-545) is drawn on request, for a selection of the batch (`annotate=`): vti_annotate_checker paints it
     on the device batch predict consumed, annotate.checker_display_list states what it holds, checker_text_items gives its text."""
 
     _mixed_sizes = False
@@ -516,23 +516,7 @@ class StitchDistanceChecker(_DeviceStage):
         return eng.annotate_checker(frames, o, res, params, sel, native=native)
 
     def _record(self, f64, i32):
-        """:345-347, :404-406 (the two early returns: nothing appended) and :515-540 (averages -> deques -> medians -> text)."""
-        status = int(i32[0])
-        if status != VTI_MEASURE_OK:
-            text = ERRORS[status]
-            return {'edge_distance_mm': None, 'stitch_width_mm': None, 'stitch_count': 0, 'info_text': text,
-                    'timestamp': datetime.now(), 'error': text}
-        n_found = int(i32[5])
-        smooth_dist = smooth_width = None
-        if not np.isnan(f64[0]):
-            self.frame_buf_dist.append(float(f64[0]))
-            smooth_dist = float(np.median(self.frame_buf_dist))
-        if not np.isnan(f64[1]):
-            self.frame_buf_width.append(float(f64[1]))
-            smooth_width = float(np.median(self.frame_buf_width))
-        return {'edge_distance_mm': smooth_dist, 'stitch_width_mm': smooth_width, 'stitch_count': n_found,
-                'info_text': checker_info_text(smooth_dist, smooth_width, n_found, self.params.min_stitches),
-                'timestamp': datetime.now()}
+        return _checker_record(self.frame_buf_dist, self.frame_buf_width, self.params.min_stitches, f64, i32)
 
     def process_frames(self, frames, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False, annotate=None,
                        encode=None, jpeg_quality=95, burn_text=False, extra_text=None, rasterise=None):
@@ -573,6 +557,98 @@ class StitchDistanceChecker(_DeviceStage):
         except ImportError:
             pass
         return pic, records[0]
+
+
+def _checker_record(buf_dist, buf_width, min_stitches, f64, i32):
+    """One frame's record of the checker from its two smoothing deques: :345-347, :404-406 (the two early returns: nothing appended)
+    and :515-540 (averages -> deques -> medians -> text)."""
+    status = int(i32[0])
+    if status != VTI_MEASURE_OK:
+        text = ERRORS[status]
+        return {'edge_distance_mm': None, 'stitch_width_mm': None, 'stitch_count': 0, 'info_text': text,
+                'timestamp': datetime.now(), 'error': text}
+    n_found = int(i32[5])
+    smooth_dist = smooth_width = None
+    if not np.isnan(f64[0]):
+        buf_dist.append(float(f64[0]))
+        smooth_dist = float(np.median(buf_dist))
+    if not np.isnan(f64[1]):
+        buf_width.append(float(f64[1]))
+        smooth_width = float(np.median(buf_width))
+    return {'edge_distance_mm': smooth_dist, 'stitch_width_mm': smooth_width, 'stitch_count': n_found,
+            'info_text': checker_info_text(smooth_dist, smooth_width, n_found, min_stitches),
+            'timestamp': datetime.now()}
+
+
+class MultiCameraChecker(_DeviceStage):
+    """StitchDistanceChecker for a rig: params_by_camera[c] = camera c's CheckerParams (calibration, class ids, thresholds), the
+    frames of one call may come from any of the cameras and, as a list, differ in size.  One predict, one vti_measure_checker_cameras
+    (a list of differing sizes: vti_measure_checker_frames, with retina_masks vti_measure_checker_frames_native) and one device ->
+    host read per batch; every camera keeps its own pair of smoothing deques, so records, rows, annotated tuples and text items are
+    those of one StitchDistanceChecker per camera, each fed only its camera's frames in the same order."""
+
+    _mixed_sizes = True
+
+    def __init__(self, model, params_by_camera, frame_buffer=8):
+        super().__init__(model)
+        self.params = [dataclasses.replace(p, frame_buffer=int(frame_buffer), drop_empty=bool(model.drop_empty_masks))
+                       for p in params_by_camera]
+        if not self.params:
+            raise ValueError("MultiCameraChecker: at least one camera")
+        self.buffers = [(deque(maxlen=int(frame_buffer)), deque(maxlen=int(frame_buffer))) for _ in self.params]      # (dist, width)
+        self._tables = {}
+
+    def _table(self, eng, device):
+        key = (id(eng), str(device))
+        if key not in self._tables:       # packed, validated and uploaded once per engine and device
+            self._tables[key] = (eng, eng.pack_checker_cameras(self.params, device))
+        return self._tables[key][1]
+
+    def _measure(self, eng, o, params, H0, W0, **kw):
+        return eng.measure_checker(o, params, H0, W0, **kw)
+
+    def _draw(self, eng, frames, o, res, params, sel, cameras, native, table):
+        return eng.annotate_checker(frames, o, res, params, sel, native=native, cameras=cameras, table=table)
+
+    def _records(self, f64, i32, cams):
+        """Frame b's record from camera cams[b]'s deques, in frame order."""
+        return [dict(_checker_record(*self.buffers[c], self.params[c].min_stitches, f64[b], i32[b]), camera=int(c))
+                for b, c in enumerate(cams)]
+
+    def _cameras(self, frames, cameras):
+        """cameras -> host int array, one index into params_by_camera per frame; refused before anything is predicted."""
+        cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)
+        if cams.ndim != 1 or cams.dtype.kind not in "iu":
+            raise ValueError("process_frames: cameras must be integers, one per frame")
+        n = len(frames) if isinstance(frames, (list, tuple)) else (frames.shape[0] if getattr(frames, "ndim", 0) == 4 else None)
+        if n is not None and n != cams.size:
+            raise ValueError(f"process_frames: {n} frames but {cams.size} cameras")
+        if cams.size and (cams.min() < 0 or cams.max() >= len(self.params)):
+            raise ValueError(f"process_frames: camera index outside [0, {len(self.params)})")
+        return cams
+
+    def process_frames(self, frames, cameras, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False,
+                       annotate=None, encode=None, jpeg_quality=95, *, mixed=False, burn_text=False, extra_text=None, rasterise=None):
+        """frames as StitchDistanceChecker.process_frames takes them (a BGR uint8 batch, a list of ndarrays or JPEG files, RawFrames),
+        or a list whose frames differ in size; cameras: one index into params_by_camera per frame (host integers; a wrong length or
+        an index outside is a ValueError before anything is predicted).  Returns what StitchDistanceChecker.process_frames returns --
+        records, with rows=True (records, rows), with annotate (annotated, records[, rows]) -- every record with a 'camera' key and
+        smoothed within its camera in frame order.  mixed (keyword only): True lets a list of differing sizes be combined with
+        annotate and encode (vti_annotate_checker_frames, vti_encode_jpeg_frames, vti_stamp_frames: every picture at its own size,
+        the text placed by its own height), and lets retina_masks=True measure such a list (no annotate then); without it those
+        combinations are refused, as MultiCameraMeasurer refuses them.  burn_text, extra_text, rasterise: as there."""
+        cams = self._cameras(frames, cameras)
+        got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
+                                  bool(mixed), rows=bool(rows), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
+        f64, i32 = got[:2]
+        records = self._records(f64, i32, cams.tolist())
+        full = lambda r, b: dict(r, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
+        if annotate is None:
+            return (records, [full(got[2][b], b) for b in range(len(f64))]) if rows else records
+        h0 = lambda b: got[3][b] if isinstance(got[3], (list, tuple)) else got[3]
+        annotated = _burned(got[2], [checker_text_items(records[b], full(r, b), h0(b)) + _extra_items(extra_text, b, records[b])
+                                     for b, _, r in got[2]], rasterise)
+        return (annotated, records, [full(got[4][b], b) for b in range(len(f64))]) if rows else (annotated, records)
 
 
 def checker_info_text(smooth_dist, smooth_width, n_found, min_stitches):
