@@ -468,6 +468,34 @@ int32_t vti_mask_polygons(vti_ctx* ctx, const uint8_t* dev_masks_bits, int32_t n
                           int32_t row_bytes, int32_t H0, int32_t W0, int32_t strategy, void* dev_scratch, size_t scratch_bytes,
                           int32_t* dev_point_offsets, float* dev_points, int64_t max_points, void* stream);
 
+/* ---- the polygons of a whole batch whose frames differ in size: vti_mask_polygons on the slots of a frame table ---------------- */
+/* The two calls of this section carry this (empty) marker. */
+#define VTI_POLYGONS_FRAMES_API
+/* Host only: device scratch bytes vti_mask_polygons_frames needs for the frames of host_table (0 on a bad argument: NULL, native
+ * outside {0, 1}, not a table of vti_pack_frames for this ctx's canvas, a native frame above H0 * W0 = 2^26).  256 header bytes and
+ * 128 labelling areas, each part of an area sized for the largest geometry of the table by vti_mask_polygons_scratch_bytes' formula:
+ * native = 0: the canvas, so the value of vti_mask_polygons_scratch_bytes(H, W, W/8); native = 1: the maximum over the frames, the
+ * image part counted for the frames that do not fit in LDS. */
+VTI_POLYGONS_FRAMES_API int64_t vti_mask_polygons_frames_scratch_bytes(const vti_ctx* ctx, const void* host_table, int32_t native);
+/* One vti_mask_polygons for the output set of vti_predict_frames (native = 0) or vti_predict_frames_native (native = 1): slot s
+ * belongs to the frame b with dev_offsets[b] <= s < dev_offsets[b+1] (i32 [B+1]; the search ends inside [0, B) whatever the array
+ * holds, and a table address is formed only then) and its vertices are, bit for bit, what vti_mask_polygons writes for that slot
+ *   native = 0: with (H, W, W/8, H0[b], W0[b]) on dev_masks = u8 [capacity, H, W/8], the letterbox bit masks at the ctx's canvas
+ *               (16-byte aligned; dev_mask_bases must be NULL);
+ *   native = 1: with (H0[b], W0[b], 8*ceil(W0[b]/64), H0[b], W0[b]) on instance i of frame b = H0[b] rows of 8*ceil(W0[b]/64) bytes at
+ *               byte dev_mask_bases[b] + i * slot_bytes[b] of dev_masks (8-byte aligned; dev_mask_bases i64 [B+1], 8-byte aligned).
+ *               Every frame needs H0 * W0 <= 2^26.
+ * A slot is live when its index is below min(dev_offsets[B], capacity) and, native = 1, its rows end at or before capacity_bytes; any
+ * other slot is not read and has 0 vertices.  Outputs, status word, strategy and the max_points rule as vti_mask_polygons, with n =
+ * capacity.  dev_scratch: >= vti_mask_polygons_frames_scratch_bytes(), 256-byte aligned.  The table pair is revalidated as by every
+ * *_frames call; 1 <= B <= max_batch.  Every argument check (VTI_ERR_ARG) runs before the first HIP call.  Count and write are
+ * launched once per form the table holds (image in LDS / in the scratch): three launches on `stream`, five when both occur. */
+VTI_POLYGONS_FRAMES_API int32_t vti_mask_polygons_frames(vti_ctx* ctx, const uint8_t* dev_masks, int32_t native,
+        const int64_t* dev_mask_bases, int64_t capacity_bytes, const int32_t* dev_offsets,
+        const void* host_table, const void* dev_table, int32_t B, int32_t capacity, int32_t strategy,
+        void* dev_scratch, size_t scratch_bytes, int32_t* dev_point_offsets, float* dev_points, int64_t max_points,
+        void* stream);
+
 /* ---- process_frame's annotated frame on device (measurement.py:219-504): the overlay on a selection of the batch -------------- */
 /* The reference returns (annotated, measurements); vti_measure gives the second half, this call the first, for the n_sel frames
  * the caller wants a picture of (the ones a limit check flagged, every k-th, ...).  dev_out[k] is frame select[k] of dev_frames

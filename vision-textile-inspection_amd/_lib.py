@@ -135,6 +135,8 @@ SIGNATURES = {
                                          _P, _P, _P, _P, _P]),
     "vti_mask_polygons_scratch_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "vti_mask_polygons": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
+    "vti_mask_polygons_frames_scratch_bytes": (_I64, [_P, _P, _I32]),
+    "vti_mask_polygons_frames": (_I32, [_P, _P, _I32, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _I64, _P]),
     "vti_annotate_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
     "vti_annotate": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32,
                             _I32, _P, _P, _P, _SZ, _P]),

@@ -12,6 +12,33 @@ constexpr int kLdsBytes = 156 * 1024;               // dynamic LDS when the imag
                                                     // the image, then parent[] when the slot's runs fit in the rest
 typedef unsigned long long u64;
 
+constexpr int kFormLds = 1, kFormScratch = 2;       // PolyLayout::forms: where the images of a call's slots are kept
+
+// The labelling area of one H x W mask: parent | runs | row_start | the image when it does not fit the LDS (each part a multiple
+// of 256 bytes).  Host: the sizes the scratch is made of; device: whether a slot of a frame table fits the areas of its call.
+__host__ __device__ inline void poly_parts(int H, int W, PolyLayout& L) {
+    const size_t r_max = (size_t)H * (size_t)((W + 1) / 2);     // at most ceil(W/2) runs per row
+    L.WW = (W + 63) / 64;
+    L.img_bytes = (size_t)H * L.WW * 8;
+    L.in_lds = L.img_bytes <= (size_t)kLdsBytes;
+    L.forms = L.in_lds ? kFormLds : kFormScratch;
+    L.off_runs = (r_max * 4 + 255) & ~(size_t)255;
+    L.off_rows = 2 * L.off_runs;
+    L.off_img = L.off_rows + (((size_t)(H + 1) * 4 + 255) & ~(size_t)255);
+    L.area_bytes = L.off_img + (L.in_lds ? 0 : (L.img_bytes + 255) & ~(size_t)255);
+}
+
+// scale_coords((H, W), pts, (H0, W0)) as polygons.py computes it: gain and pads in double (Python floats), each rounded to f32 once;
+// the vertices then take (c - pad) / gain in f32 with a correctly rounded division and the clip to the frame.  The same IEEE
+// double operations on the host (vti_mask_polygons: one geometry per call) and on the device (vti_mask_polygons_frames: the slot's
+// frame, from its row of the table); the build keeps floating-point contraction off.
+struct PolyMap { float padx, pady, gain, W0, H0; };
+__host__ __device__ inline PolyMap poly_map(int H, int W, int H0, int W0) {
+    const double gy = (double)H / (double)H0, gx = (double)W / (double)W0, gain = gx < gy ? gx : gy;
+    const double padx = ((double)W - (double)W0 * gain) / 2, pady = ((double)H - (double)H0 * gain) / 2;
+    return PolyMap{(float)padx, (float)pady, (float)gain, (float)W0, (float)H0};
+}
+
 // parent[] lives in LDS or in the workgroup's own part of the scratch; every access is atomic (agent scope: past the CU's vector
 // cache when it is global memory)
 __device__ __forceinline__ int ld_p(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

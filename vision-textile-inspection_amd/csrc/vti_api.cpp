@@ -1254,11 +1254,73 @@ int32_t vti_mask_polygons(vti_ctx* c, const uint8_t* masks, int32_t n, const int
     VTI_TRY(scratch_check("vti_mask_polygons", c, scratch, scratch_bytes, vti_mask_polygons_scratch_bytes(c, H, W, row_bytes),
                           "vti_mask_polygons_scratch_bytes()"));
     VTI_TRY(check_device(c, "vti_mask_polygons"));
-    // scale_coords' gain and pad, in double as polygons.py (Python floats); the kernels round each to f32 once
-    const double gain = std::min((double)H / (double)H0, (double)W / (double)W0);
-    const double padx = ((double)W - (double)W0 * gain) / 2, pady = ((double)H - (double)H0 * gain) / 2;
-    VTI_HIP(c, launch_mask_polygons(masks, n, n_live, H, W, row_bytes, gain, padx, pady, H0, W0, strategy, scratch, offsets, points,
+    VTI_HIP(c, launch_mask_polygons(masks, n, n_live, H, W, row_bytes, H0, W0, strategy, scratch, offsets, points,
                                     (long long)max_points, (hipStream_t)stream), "mask_polygons kernels");
+    return VTI_OK;
+}
+
+// ---- the polygons of a batch whose frames differ in size: vti_mask_polygons on the slots of a frame table -------------------------
+// The scratch layout for the frames of a validated host table: the canvas for letterbox masks, else every frame's own size.  Returns
+// the first frame vti_mask_polygons' size limit refuses (native only; the table allows more), or -1.
+static int32_t poly_frames_layout(const vti_ctx* c, const void* host_table, const FrameTableHeader& h, int32_t native, PolyLayout& L) {
+    if (!native) {
+        mask_polygons_layout(c->plan.desc.H, c->plan.desc.W, c->plan.desc.W / 8, L);
+        return -1;
+    }
+    std::vector<int> H0(h.B), W0(h.B);
+    for (int32_t b = 0; b < h.B; ++b) {
+        const FrameRow r = table_row(host_table, b);
+        if (!poly_sizes_ok(r.H0, r.W0, 8 * ((r.W0 + 63) / 64))) return b;
+        H0[b] = r.H0; W0[b] = r.W0;
+    }
+    mask_polygons_layout_frames(H0.data(), W0.data(), h.B, L);
+    return -1;
+}
+
+int64_t vti_mask_polygons_frames_scratch_bytes(const vti_ctx* c, const void* host_table, int32_t native) {
+    if (!c || !host_table || (native != 0 && native != 1)) return 0;
+    FrameTableHeader h;
+    int32_t frame;
+    if (frame_table_problem(c, host_table, -1, h, frame) || h.B > c->plan.desc.max_batch) return 0;
+    PolyLayout L;
+    if (!poly_sizes_ok(h.H, h.W, h.W / 8) || poly_frames_layout(c, host_table, h, native, L) >= 0) return 0;
+    return (int64_t)L.total;
+}
+
+int32_t vti_mask_polygons_frames(vti_ctx* c, const uint8_t* masks, int32_t native, const int64_t* mask_bases, int64_t capacity_bytes,
+                                 const int32_t* offsets, const void* host_table, const void* dev_table, int32_t B, int32_t capacity,
+                                 int32_t strategy, void* scratch, size_t scratch_bytes, int32_t* point_offsets, float* points,
+                                 int64_t max_points, void* stream) {
+    const char* fn = "vti_mask_polygons_frames";
+    // every check comes before the first HIP call
+    if (!c) return refuse(c, fn, "null ctx");
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    if (B > c->plan.desc.max_batch) return refuse(c, fn, "B above max_batch");
+    if (native != 0 && native != 1) return refuse(c, fn, "native must be 0 or 1");
+    if (!native && mask_bases) return refuse(c, fn, "dev_mask_bases must be NULL with native = 0 (letterbox masks have one slot size)");
+    if (native && !mask_bases) return refuse(c, fn, "null dev_mask_bases (native = 1: the ragged rows of vti_masks_native_frames)");
+    if (capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
+    if (capacity < 0 || max_points < 0) return refuse(c, fn, "capacity and max_points must be >= 0");
+    if (strategy != VTI_POLY_LARGEST && strategy != VTI_POLY_CONCAT)
+        return refuse(c, fn, "strategy must be VTI_POLY_LARGEST or VTI_POLY_CONCAT");
+    if (!offsets || !point_offsets || (capacity && !masks) || (max_points && !points)) return refuse(c, fn, "null pointer");
+    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
+    if (((uintptr_t)mask_bases & 7) || ((uintptr_t)offsets & 3) || ((uintptr_t)point_offsets & 3) || ((uintptr_t)points & 3))
+        return refuse(c, fn, "dev_mask_bases must be 8-byte aligned, dev_offsets, dev_point_offsets and dev_points 4-byte aligned");
+    if (!poly_sizes_ok(h.H, h.W, h.W / 8)) return refuse(c, fn, "the canvas is above vti_mask_polygons' limit (H * W <= 2^26)");
+    PolyLayout L;
+    const int32_t big = poly_frames_layout(c, host_table, h, native, L);
+    if (big >= 0) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "frame %d of host_table: H0 * W0 above 2^26 (vti_mask_polygons' limit)", big);
+        return refuse(c, fn, msg);
+    }
+    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, (int64_t)L.total, "vti_mask_polygons_frames_scratch_bytes()"));
+    VTI_TRY(check_device(c, fn));
+    VTI_HIP(c, launch_mask_polygons_frames(masks, (const long long*)mask_bases, capacity_bytes, offsets, frame_rows(dev_table), B, capacity,
+                                           c->plan.desc.H, c->plan.desc.W, L, strategy, scratch, point_offsets, points,
+                                           (long long)max_points, (hipStream_t)stream), "mask_polygons kernels (frames)");
     return VTI_OK;
 }
 

@@ -377,12 +377,22 @@ void checker_pack(const vti_checker_params& p, void* row);
 struct PolyLayout {
     int WW;                    // 64-bit words per image row
     bool in_lds;               // the H x WW image is kept in LDS
+    int forms;                 // bit 0: a geometry of the layout keeps its image in LDS, bit 1: one keeps it in the scratch
     size_t img_bytes, off_runs, off_rows, off_img, area_bytes, total;
 };
 void mask_polygons_layout(int H, int W, int row_bytes, PolyLayout& L);
-hipError_t launch_mask_polygons(const uint8_t* masks, int n, const int* n_live, int H, int W, int row_bytes, double gain,
-                                double padx, double pady, int H0, int W0, int strategy, void* scratch, int* offsets, float* points,
-                                long long max_points, hipStream_t st);
+// The layout for slots of n geometries (vti_mask_polygons_frames: the frames of a table): every part of the area is the largest any of
+// them needs, the image part being that of the geometries whose image does not fit the LDS.  n = 1 is mask_polygons_layout.
+void mask_polygons_layout_frames(const int* H, const int* W, int n, PolyLayout& L);
+// scale_coords' gain and pads come from (H, W) and (H0, W0): polygons_dev.h, poly_map.
+hipError_t launch_mask_polygons(const uint8_t* masks, int n, const int* n_live, int H, int W, int row_bytes, int H0, int W0,
+                                int strategy, void* scratch, int* offsets, float* points, long long max_points, hipStream_t st);
+// vti_mask_polygons_frames.  bases == nullptr: the slots are letterbox masks of H x W (row_bytes W / 8) and slot s of frame b
+// (slot_offsets[b] <= s < slot_offsets[b + 1]) maps to that frame's H0 x W0; else they are vti_masks_native_frames' ragged rows, traced at
+// H0[b] x W0[b].  L: mask_polygons_layout_frames of the host table's geometries.  Live: s < min(slot_offsets[B], capacity).
+hipError_t launch_mask_polygons_frames(const uint8_t* masks, const long long* bases, long long capacity_bytes, const int* slot_offsets,
+                                       const FrameRow* rows, int B, int capacity, int H, int W, const PolyLayout& L, int strategy,
+                                       void* scratch, int* offsets, float* points, long long max_points, hipStream_t st);
 
 // annotate.hip: vti_annotate (process_frame's annotated frame).  The scratch holds, per selected frame: the display list (3 + 7 *
 // max_det records of 32 bytes), 16 ints of counts, the envelope's points int2 [W0], the outline's vertices int2 [max_points], the

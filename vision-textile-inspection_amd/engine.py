@@ -1353,6 +1353,54 @@ class Engine:
             launch(pts)
         return pts[:total], point_offsets
 
+    # ---- the polygons of a batch whose frames differ in size (vti_mask_polygons_frames) ---------------------------------------
+    def mask_polygons_frames_scratch_bytes(self, table, native):
+        self._check_frames(table)
+        return int(lib().vti_mask_polygons_frames_scratch_bytes(self._ctx, C.c_void_p(table.host.data_ptr()), int(bool(native))))
+
+    def mask_polygons_frames(self, out, table, native=False, strategy="largest"):
+        """mask_polygons for every slot of an output set that predict_frames_into() filled, in one call: slot s of frame b
+        (offsets[b] <= s < offsets[b+1]) gets the polygon mask_polygons gives it with that frame's (H0, W0) -- letterbox bit masks,
+        or with native=True the ragged frame-size rows of a set from alloc_outputs(native_frames=table) (any other set is a
+        ValueError).  -> (points f32 [P,2], point_offsets i32 [capacity+1]) as mask_polygons: slots beyond the live ones have empty
+        polygons, `points` is a view of the kept buffer, one host read, a second launch only when that buffer was too small."""
+        if strategy not in POLY_STRATEGIES:
+            raise ValueError(f"strategy must be one of {sorted(POLY_STRATEGIES)}, got {strategy!r}")
+        if native:
+            self._check_ragged(out, table, out["dets"].shape[1], "mask_polygons_frames")
+        masks = out["masks"]
+        B = out["counts"].shape[0]
+        self._check_frames(table, B=B)
+        if not native and (masks.dim() != 3 or tuple(masks.shape[1:]) != (self.H, self.W // 8) or not masks.is_contiguous()):
+            raise ValueError(f"mask_polygons_frames: the masks must be contiguous letterbox bit masks u8 [capacity, {self.H}, {self.W // 8}]")
+        capacity = (B * out["dets"].shape[1] if native else masks.shape[0]) if masks.numel() else 0
+        dev = masks.device
+        need = self.mask_polygons_frames_scratch_bytes(table, native)
+        if need <= 0:
+            raise ValueError("mask_polygons_frames: a frame of the table is above mask_polygons' size limit (H0 * W0 <= 2^26)")
+        ws = self._scratch("_poly_ws", need, dev)
+        pts = getattr(self, "_poly_points", None)
+        if pts is None or pts.device != dev:
+            pts = self._poly_points = torch.empty((1 << 16, 2), dtype=torch.float32, device=dev)
+        point_offsets = torch.empty((capacity + 1,), dtype=torch.int32, device=dev)
+        bases = _ptr(out["mask_bases"]) if native else C.c_void_p(0)
+
+        def launch(buf):
+            check(self._ctx, lib().vti_mask_polygons_frames(
+                self._ctx, _ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), bases, masks.numel() if native else 0,
+                _ptr(out["offsets"]), *table._ptrs(), B, capacity, POLY_STRATEGIES[strategy], _ptr(ws), ws.numel(),
+                _ptr(point_offsets), _ptr(buf), buf.shape[0], _stream()))
+        launch(pts)
+        total, status = torch.cat((point_offsets[capacity:], ws[:4].view(torch.int32))).tolist()
+        if status != _lib.VTI_POLY_OK:
+            raise _lib.VtiError(-4, f"vti_mask_polygons_frames: status word {status} (1: a loop reached its bound, "
+                                    f"2: more than 2^31-1 vertices)")     # -4: VTI_ERR_HIP, an error found on the device
+        if total > pts.shape[0]:                       # the kept buffer was too small: grow it and run again
+            self._poly_points = None
+            pts = self._poly_points = torch.empty((max(total, 2 * pts.shape[0]), 2), dtype=torch.float32, device=dev)
+            launch(pts)
+        return pts[:total], point_offsets
+
     # ---- test hook ---------------------------------------------------------------------
     def debug_conv_output(self, i, B):
         t = self.conv_table()[i]

@@ -423,7 +423,7 @@ class YOLO:
 
     @torch.inference_mode()
     def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
-                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, **_ignored):
+                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, polygons=False, **_ignored):
         """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
         ndarray sources.  retina_masks=True: masks at the frame size, Ultralytics'
         process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes.
@@ -439,9 +439,16 @@ class YOLO:
         RawFrames sources -- one, or a list / tuple of them -- are raw camera buffers (YUYV, UYVY, NV12, NV21, I420, YV12) converted
         on the device (vti_convert_raw): the call is exactly predict on the BGR ndarray(s) rawframes.to_bgr gives, i.e. the frames
         cap.read() delivers without CAP_PROP_CONVERT_RGB = 0, with the same swap_rb meaning.  Members of differing sizes go
-        through the frame table (vti_convert_raw_frames -> vti_predict_frames), members of one size keep the stacked path."""
+        through the frame table (vti_convert_raw_frames -> vti_predict_frames), members of one size keep the stacked path.
+        polygons=True (keyword only, True or False): every Results.masks.xy / .xyn of the batch is made before predict returns --
+        one vti_mask_polygons_frames call for a list whose frames differ in size (on the ragged frame-size rows with
+        retina_masks=True, mixed=True), one vti_mask_polygons call over the live slots for frames of one size, and one copy of the
+        points and offsets to the host; .xy / .xyn then return without touching the device.  Without it they are made per frame
+        on first access, with the same values."""
         if not isinstance(mixed, (bool, np.bool_)):
             raise ValueError(f"predict: mixed must be True or False, got {mixed!r}")
+        if not isinstance(polygons, (bool, np.bool_)):
+            raise ValueError(f"predict: polygons must be True or False, got {polygons!r}")
         files = self._jpeg_files(source)
         info = None
         if files is not None:
@@ -462,9 +469,17 @@ class YOLO:
             B = len(shapes)
         else:
             eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
-            shapes = [(H0, W0)] * B
+            shapes, table = [(H0, W0)] * B, None
         self._raise_if_corrupt(info)
         dets, xyxy, masks = o["dets"], o["xyxy"], o["masks"]
+        poly = None
+        if polygons:                                       # the whole batch's polygons: one call, one copy to the host
+            if table is not None:
+                pts, po = eng.mask_polygons_frames(o, table, native=ragged)
+            else:
+                pts, po = eng.mask_polygons(masks, W0 if retina_masks else W, H0, W0, offsets=o["offsets"])
+            host = torch.cat((pts.reshape(-1).view(torch.int32), po)).cpu().numpy()      # bits as int32, as Masks.xy copies them
+            poly = (host[:pts.numel()].view(np.float32).reshape(-1, 2), host[pts.numel():])
         nonempty = None
         if self.drop_empty_masks and not retina_masks:     # m00 of every live slot straight from the bit-packed masks (vti_mask_stats_bits)
             nonempty = eng.mask_stats_bits(masks, H, W, offsets=o["offsets"])[:, 0] > 0
@@ -494,6 +509,9 @@ class YOLO:
             else:
                 mb, db = mb.clone(), db.clone()
             m = Masks(mb, W0 if retina_masks else W, (H0, W0), eng) if n else None
+            if m is not None and poly is not None:         # slot off[b] + i is instance i; the kept ones, in order
+                which = range(cnt[b]) if keep is None else np.flatnonzero(keep.cpu().numpy()).tolist()
+                m._xy = [poly[0][poly[1][off[b] + i]:poly[1][off[b] + i + 1]] for i in which]
             r = Results((H0, W0), self.names, Boxes(data, (H0, W0)), m, db)
             r._engine = eng
             out.append(r)
