@@ -849,6 +849,49 @@ VTI_STAMP_API int32_t vti_stamp_frames(vti_ctx* ctx, uint8_t* dev_buf, const voi
                                        int32_t n, const void* host_table, const void* dev_table, const uint32_t* dev_bits,
                                        int64_t n_words, void* stream);
 
+/* ---- NMS settings per frame, and Ultralytics' `classes` filter (config.py:69-73 per station; predict(classes=...)) -------------- */
+/* conf, iou, max_det, agnostic and a class set per FRAME in place of per call: the settings live in a table of rows in device
+ * memory and an i32 device array names each frame's row, as the camera tables of the measure calls do.  One row used for every
+ * frame is predict(classes=[...]); one row per camera serves a batch that mixes stations with different thresholds.  Frame b comes
+ * out bit for bit as the table-free call gives it with its row's settings (and max_det = min(row.max_det, the call's max_det)).
+ * The class set is applied where Ultralytics' non_max_suppression applies it: to the class of each anchor's first maximal score,
+ * after the confidence test and BEFORE the 30000 cut, the greedy pass and max_det.  An anchor whose best class is outside the set is
+ * dropped even when another, allowed class of it scores above conf (the single-label rule), an excluded box never suppresses a wanted
+ * one under agnostic NMS and never uses one of the max_det places -- which a filter on the returned rows cannot undo.
+ * LIMITS: 1 <= n_rows <= VTI_NMS_TABLE_MAX_ROWS; a class set needs a model of at most VTI_NMS_TABLE_MAX_CLASSES classes (the width
+ * of a row's bit mask). */
+enum { VTI_NMS_TABLE_MAX_ROWS = 65536, VTI_NMS_TABLE_MAX_CLASSES = 1024 };
+/* Marks the three entry points of the NMS table; libvti.so exports them as it does every other. */
+#define VTI_NMS_TABLE_API
+typedef struct {
+    float conf;              /* 0 <= conf <= 1, finite */
+    int32_t max_det;         /* >= 1; the effective limit is min(this, the call's max_det) */
+    double iou;              /* 0 <= iou <= 1, finite */
+    int32_t agnostic;        /* 0 or 1 */
+    int32_t n_classes;       /* 0: every class; else classes[0 .. n_classes) */
+    const int32_t* classes;  /* host; each in [0, nc); duplicates allowed */
+} vti_nms_params;
+/* Host only: bytes of a table of n_rows rows (0 when n_rows < 1 or above VTI_NMS_TABLE_MAX_ROWS): a header and a row per entry. */
+VTI_NMS_TABLE_API int64_t vti_nms_table_bytes(int32_t n_rows);
+/* Host only: validates params[0 .. n_rows) against the ctx's class count nc and writes the table (nbytes >= the size above).
+ * VTI_ERR_ARG, vti_last_error naming the first failing row and its field: conf or iou outside [0, 1] or not finite, max_det < 1,
+ * agnostic neither 0 nor 1, n_classes < 0, n_classes > 0 with a NULL list, a class outside [0, nc).  A row with a class set on a
+ * model of more than VTI_NMS_TABLE_MAX_CLASSES classes is VTI_ERR_UNSUPPORTED.  A set that names every class packs as no set at all.
+ * Equal inputs give equal bytes; the format is private to the library build.  ctx is required (it gives nc). */
+VTI_NMS_TABLE_API int32_t vti_pack_nms_table(vti_ctx* ctx, const vti_nms_params* params, int32_t n_rows,
+                                             void* host_table, size_t nbytes);
+/* Installs the table: until it is cleared or replaced, EVERY NMS of the ctx -- vti_nms, vti_nms_scored, vti_predict,
+ * vti_predict_frames, vti_predict_frames_native -- takes frame b's settings from row dev_row_of_frame[b] (NULL: row 0 for every
+ * frame); the calls' own conf, iou and agnostic are ignored, their max_det stays the row stride of dev_dets and the upper bound of
+ * every row's limit.  host_table: the bytes vti_pack_nms_table wrote for THIS ctx's nc and these n_rows (the ctx keeps a copy and
+ * revalidates it here: VTI_ERR_ARG naming the row otherwise); NULL clears the table, the other arguments are then ignored.
+ * dev_table: its device copy (16-byte aligned, trusted to hold the same bytes); dev_row_of_frame: i32, at least max_batch entries,
+ * 4-byte aligned.  Both stay caller-owned and must live until the table is cleared or replaced.  The kernels compare
+ * dev_row_of_frame[b] with [0, n_rows) BEFORE they form a table address: a frame whose index is outside gets counts[b] = 0 and
+ * all-zero rows; the other frames are unaffected.  Host only: every check runs before any HIP call, and the setter makes none. */
+VTI_NMS_TABLE_API int32_t vti_set_nms_table(vti_ctx* ctx, const void* host_table, const void* dev_table,
+                                            int32_t n_rows, const int32_t* dev_row_of_frame);
+
 /* ---- JPEG files -> frames on device (cap.read() of a motion-JPEG camera, cv2.imread, Ultralytics' file sources) ----------------- */
 /* n files -> n frames u8 [H0,W0,3], byte for byte the package's jpeg.decode, which is pinned to libjpeg-turbo's output with its
  * defaults (JDCT_ISLOW, fancy upsampling): jdhuff.c, jidctint.c with the dequantisation inside, jdsample.c, jdcolor.c; integer

@@ -51,6 +51,13 @@ class VtiStampDesc(C.Structure):
                 ("bgr", C.c_uint8 * 4), ("reserved", C.c_int32), ("word_offset", C.c_int64)]
 
 
+class VtiNmsParams(C.Structure):
+    """include/vti.h vti_nms_params."""
+    _fields_ = [("conf", C.c_float), ("max_det", C.c_int32), ("iou", C.c_double), ("agnostic", C.c_int32), ("n_classes", C.c_int32),
+                ("classes", C.POINTER(C.c_int32))]
+
+
+VTI_NMS_TABLE_MAX_ROWS, VTI_NMS_TABLE_MAX_CLASSES = 65536, 1024
 VTI_MEASURE_OK, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_BAD_CAMERA = 0, 1, 2, 3
 VTI_STITCH_KEPT, VTI_STITCH_MASK, VTI_STITCH_SELECTED, VTI_STITCH_NEAR, VTI_STITCH_DIST, VTI_STITCH_WIDTH = 1, 2, 4, 8, 16, 32
 VTI_MEASURE_MAX_DET = 1000
@@ -172,6 +179,9 @@ SIGNATURES = {
     "vti_pack_stamps": (_I32, [_P, _P, _P, _I32, _P, _I32, _I64, _P, _SZ]),
     "vti_stamp": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
     "vti_stamp_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _P, _P, _I64, _P]),
+    "vti_nms_table_bytes": (_I64, [_I32]),
+    "vti_pack_nms_table": (_I32, [_P, C.POINTER(VtiNmsParams), _I32, _P, _SZ]),
+    "vti_set_nms_table": (_I32, [_P, _P, _P, _I32, _P]),
     "vti_decode_jpeg_table_bytes": (_I64, [_I32]),
     "vti_decode_jpeg_plan": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     "vti_decode_jpeg": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),

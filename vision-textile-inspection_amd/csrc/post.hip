@@ -251,13 +251,31 @@ static NmsWsLayout nms_layout(int A) {
 size_t nms_workspace_bytes(int B, int A) { return nms_layout(A).per_frame * (size_t)B + align256((size_t)B * 4) + align256((size_t)B * A * 8); }
 float* nms_workspace_best(void* ws, int B, int A) { return (float*)((char*)ws + nms_layout(A).per_frame * (size_t)B + align256((size_t)B * 4)); }
 
+// Ultralytics' `classes` filter of a table row: applied to the class of the anchor's (first) maximal score, after the threshold.
+__device__ __forceinline__ bool nms_class_allowed(const NmsRow* __restrict__ R, int j) {
+    if (!R->filter) return true;
+    return (unsigned)j < (unsigned)(32 * kNmsMaskWords) && ((R->mask[j >> 5] >> (j & 31)) & 1u);
+}
+
 // Stage 1 (whole chip): best class score per anchor (first maximal index); anchors above `conf` are
 // appended to the frame's key list.  Arrival order is arbitrary -- the sort below restores the order.
 // With `best_out` the kernel only records the (score, class) pair of every anchor -- launch_anchor_best: the pairs a plan without
 // fused class towers cannot write from its epilogue.
+// TABLE (vti_set_nms_table): `conf` and the class set are those of frame b's row of the NMS table.  b is blockIdx.y, so the row is
+// uniform per workgroup: its fields are read once, through scalar loads; only the mask word of a candidate's class is per lane,
+// and only anchors above the threshold read it.  A frame whose row index is outside the table contributes no candidate.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void nms_scan_kernel(const float* __restrict__ pred, int A, int nc, int nm, float conf,
-                                                       char* ws, NmsWsLayout L, int* __restrict__ ncand, float* __restrict__ best_out) {
+                                                       char* ws, NmsWsLayout L, int* __restrict__ ncand, float* __restrict__ best_out,
+                                                       NmsTable T) {
     const int b = blockIdx.y;
+    const NmsRow* __restrict__ R = nullptr;
+    if constexpr (TABLE) {
+        const int r = T.row_of_frame ? T.row_of_frame[b] : 0;
+        if ((unsigned)r >= (unsigned)T.n_rows) return;         // compared BEFORE a table address is formed; the whole workgroup leaves
+        R = T.rows + r;
+        conf = R->conf;
+    }
     const int no = 4 + nc + nm;
     float best;
     int j = 0;
@@ -315,7 +333,9 @@ __global__ __launch_bounds__(256) void nms_scan_kernel(const float* __restrict__
         *(float2*)(best_out + ((size_t)b * A + a) * 2) = make_float2(best, (float)(j == 0x7fffffff ? 0 : j));
         return;
     }
-    if (best > conf) {
+    bool cand = best > conf;
+    if constexpr (TABLE) cand = cand && nms_class_allowed(R, j);
+    if (cand) {
         char* wsb = ws + (size_t)b * L.per_frame;
         const int idx = atomicAdd(&ncand[b], 1);
         // ascending key order == score descending, then anchor ascending (stable sort of the
@@ -346,7 +366,7 @@ __device__ unsigned long long g_nms_stamps[4096 * 8];
 // waits on both memory counters and costs several hundred cycles).
 template <typename KeyP, typename BoxP, typename FltP, typename IntP>
 __device__ __forceinline__ void nms_body(const float* __restrict__ P, int A, int nc, int nm, int n, double iou, int max_det,
-                                         int agnostic, float* __restrict__ D, int* __restrict__ counts, int b,
+                                         int stride_det, int agnostic, float* __restrict__ D, int* __restrict__ counts, int b,
                                          const unsigned long long* __restrict__ g_keys_in, KeyP keys, BoxP boxes, FltP area,
                                          IntP keep, IntP kid, IntP kcls, unsigned char* suppressed,
                                          const int* __restrict__ cls_of) {
@@ -499,7 +519,7 @@ __device__ __forceinline__ void nms_body(const float* __restrict__ P, int A, int
     // size of its axis for the box fields, the same word twice otherwise) and a thread issues all of its group before using
     // any: a load behind a data-dependent branch makes hipcc wait for it on the spot (one DRAM round trip per element: 39 k
     // cycles for 217 rows, the crowded frame that sets this kernel's duration).
-    const int nel = kept * row, ntot = max_det * row;
+    const int nel = kept * row, ntot = stride_det * row;      // stride_det >= max_det: the frame's rows in dets (the call's max_det)
     const int no_ = 4 + nc + nm;
     constexpr int OU = 8;
     for (int e0 = tid; e0 < nel; e0 += OU * NMS_THREADS) {
@@ -532,11 +552,15 @@ __device__ __forceinline__ void nms_body(const float* __restrict__ P, int A, int
     if (tid == 0) counts[b] = kept;
 }
 
+// TABLE (vti_set_nms_table): conf, iou, agnostic, the class set and lim = min(row.max_det, max_det) are those of frame b's row, read
+// once per workgroup (b = blockIdx.x: scalar loads).  max_det stays the row stride of dets, the extent of the zero fill and the
+// LDS / global decision.  A frame whose row index is outside the table gets count 0 and zero rows, like a frame without candidates.
+template <bool TABLE>
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restrict__ pred, int A, int nc, int nm,
                                                           float conf, double iou, int max_det, int agnostic,
                                                           float* __restrict__ dets, int* __restrict__ counts,
                                                           char* ws, NmsWsLayout L, int* __restrict__ ncand,
-                                                          const float* __restrict__ best) {
+                                                          const float* __restrict__ best, NmsTable T) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long* lds_keys = (unsigned long long*)smem;             // NMS_LDS_KEYS entries
     f32x4* lds_boxes = (f32x4*)(smem + NMS_LDS_KEYS * 8);                 // NMS_LDS_BOX entries
@@ -551,8 +575,20 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
     unsigned long long* g_keys = (unsigned long long*)(wsb + L.keys);
     const int* cls_of = (const int*)(wsb + L.cls);
     float* D = dets + (size_t)b * max_det * (6 + nm);
+    int lim = max_det;
+    const NmsRow* __restrict__ R = nullptr;
+    bool bad_row = false;
+    if constexpr (TABLE) {
+        const int r = T.row_of_frame ? T.row_of_frame[b] : 0;
+        bad_row = (unsigned)r >= (unsigned)T.n_rows;           // compared BEFORE a table address is formed
+        if (!bad_row) {
+            R = T.rows + r;
+            conf = R->conf; iou = R->iou; agnostic = R->agnostic;
+            lim = min(R->max_det, max_det);
+        }
+    }
     __shared__ int s_cnt;
-    if (best) {
+    if (best && !bad_row) {
         // Stage 1 here, from the per-anchor (max score, class) pairs written beside pred (8 bytes per anchor instead of nc scores):
         // anchors above `conf` go to the frame's key list.  Arrival order is arbitrary -- the sort restores the order.
         if (tid == 0) s_cnt = 0;
@@ -566,7 +602,9 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int a = a0 + tid + u * NMS_THREADS;
-                if (a < A && v[u].x > conf) {
+                bool cand = a < A && v[u].x > conf;
+                if constexpr (TABLE) cand = cand && nms_class_allowed(R, (int)v[u].y);
+                if (cand) {
                     const int idx = atomicAdd(&s_cnt, 1);
                     g_keys[idx] = ((unsigned long long)(~__float_as_uint(v[u].x)) << 32) | (unsigned)a;
                     cls_w[a] = (int)v[u].y;
@@ -576,7 +614,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
         __syncthreads();                          // the block's global writes are visible to the block behind the barrier
         if (tid == 0) ncand[b] = s_cnt;
     }
-    const int n = best ? s_cnt : ncand[b];
+    const int n = bad_row ? 0 : best ? s_cnt : ncand[b];
     if (n == 0) {
         if (tid == 0) counts[b] = 0;
         for (int i = tid; i < max_det * (6 + nm); i += NMS_THREADS) D[i] = 0.f;
@@ -584,13 +622,13 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
     }
     NMS_STAMP(0);
     if (n <= NMS_LDS_BOX && max_det <= NMS_LDS_BOX) {
-        nms_body(P, A, nc, nm, n, iou, max_det, agnostic, D, counts, b, g_keys, lds_keys, lds_boxes, lds_area, lds_keep,
+        nms_body(P, A, nc, nm, n, iou, lim, max_det, agnostic, D, counts, b, g_keys, lds_keys, lds_boxes, lds_area, lds_keep,
                  lds_keep + NMS_LDS_BOX, lds_keep + 2 * NMS_LDS_BOX, suppressed, cls_of);
     } else {
         // pathological candidate counts: everything but the suppressed flags in global scratch.  The keys are
         // sorted in a second scratch array so the unsorted input is not aliased.
         int* g_int = (int*)(wsb + L.keep);          // A ints: keep list; kept ids/classes reuse boxes' tail? no: own arrays below
-        nms_body(P, A, nc, nm, n, iou, max_det, agnostic, D, counts, b, g_keys, (unsigned long long*)(wsb + L.keys2),
+        nms_body(P, A, nc, nm, n, iou, lim, max_det, agnostic, D, counts, b, g_keys, (unsigned long long*)(wsb + L.keys2),
                  (f32x4*)(wsb + L.boxes), (float*)(wsb + L.area), g_int, (int*)(wsb + L.kid), (int*)(wsb + L.kcls), suppressed,
                  cls_of);
     }
@@ -599,13 +637,13 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
 hipError_t launch_anchor_best(const float* pred, int B, int A, int nc, int nm, float* best, hipStream_t st) {
     if (B == 0) return hipSuccess;
     const int apb = (((4 + nc + nm) | nc) & 3) == 0 ? 64 : 256;
-    hipLaunchKernelGGL(nms_scan_kernel, dim3((A + apb - 1) / apb, B), dim3(256), 0, st, pred, A, nc, nm, 0.0f, (char*)nullptr, nms_layout(A),
-                       (int*)nullptr, best);
+    hipLaunchKernelGGL(nms_scan_kernel<false>, dim3((A + apb - 1) / apb, B), dim3(256), 0, st, pred, A, nc, nm, 0.0f, (char*)nullptr,
+                       nms_layout(A), (int*)nullptr, best, NmsTable{});
     return hipGetLastError();
 }
 
 hipError_t launch_nms(const float* pred, const float* best, int B, int A, int nc, int nm, float conf, double iou, int max_det,
-                      int agnostic, float* dets, int* counts, void* ws, hipStream_t st) {
+                      int agnostic, float* dets, int* counts, void* ws, hipStream_t st, NmsTable table) {
     if (B == 0) return hipSuccess;
     const size_t lds = (size_t)NMS_LDS_KEYS * 8 + (size_t)NMS_LDS_BOX * 32 + (((size_t)A + 15) & ~(size_t)15);
     if (lds > 150 * 1024) return hipErrorInvalidValue;   // > ~39k anchors: unsupported
@@ -615,10 +653,18 @@ hipError_t launch_nms(const float* pred, const float* best, int B, int A, int nc
         hipError_t e = hipMemsetAsync(ncand, 0, sizeof(int) * (size_t)B, st);
         if (e != hipSuccess) return e;
         const int apb = (((4 + nc + nm) | nc) & 3) == 0 ? 64 : 256;        // anchors per block: quad-per-anchor / lane-per-anchor
-        hipLaunchKernelGGL(nms_scan_kernel, dim3((A + apb - 1) / apb, B), dim3(256), 0, st, pred, A, nc, nm, conf, (char*)ws, L, ncand, (float*)nullptr);
+        const dim3 grid((A + apb - 1) / apb, B);
+        if (table.rows)
+            hipLaunchKernelGGL(nms_scan_kernel<true>, grid, dim3(256), 0, st, pred, A, nc, nm, conf, (char*)ws, L, ncand, (float*)nullptr, table);
+        else
+            hipLaunchKernelGGL(nms_scan_kernel<false>, grid, dim3(256), 0, st, pred, A, nc, nm, conf, (char*)ws, L, ncand, (float*)nullptr, table);
     }
-    const hipError_t e = launch_lds<nms_kernel>(dim3(B), dim3(NMS_THREADS), lds, st, pred, A, nc, nm, conf, iou, max_det, agnostic,
-                                                dets, counts, (char*)ws, L, ncand, best);
+    // the table-free instantiation is the same source with the scalar arguments: the row reads compile away
+    const hipError_t e = table.rows
+        ? launch_lds<nms_kernel<true>>(dim3(B), dim3(NMS_THREADS), lds, st, pred, A, nc, nm, conf, iou, max_det, agnostic, dets, counts,
+                                       (char*)ws, L, ncand, best, table)
+        : launch_lds<nms_kernel<false>>(dim3(B), dim3(NMS_THREADS), lds, st, pred, A, nc, nm, conf, iou, max_det, agnostic, dets, counts,
+                                        (char*)ws, L, ncand, best, table);
 #ifdef VTI_STAMPS
     {
         (void)hipStreamSynchronize(st);

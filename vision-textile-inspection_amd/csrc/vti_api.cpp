@@ -35,6 +35,9 @@ struct vti_ctx {
     hipEvent_t ev_fork[kNumLanes] = {};
     hipEvent_t ev_join[kNumLanes] = {};
     bool multi_stream = false;
+    // vti_set_nms_table: the ctx's copy of the host bytes (empty: no table) and the caller's device pair
+    std::vector<unsigned char> nms_host;
+    NmsTable nms_table;
 };
 
 static std::string g_create_err;
@@ -696,7 +699,117 @@ static int32_t nms_impl(vti_ctx* c, const char* fn, bool scored, const float* pr
     if (!pred || (scored && !best) || !dets || !counts || max_det < 1) return fail(c, VTI_ERR_ARG, std::string(fn) + ": bad argument");
     if (int32_t drc = check_device(c, fn)) return drc;
     VTI_HIP(c, launch_nms(pred, best, B, c->plan.num_anchors, c->plan.desc.nc, c->plan.desc.nm, conf, iou, max_det, agnostic,
-                          dets, counts, c->ws + c->act_bytes, (hipStream_t)stream), "nms kernel");
+                          dets, counts, c->ws + c->act_bytes, (hipStream_t)stream, c->nms_table), "nms kernel");
+    return VTI_OK;
+}
+
+// ---- the NMS table: settings per frame and Ultralytics' `classes` filter (host only) ---------------------------------------------
+int64_t vti_nms_table_bytes(int32_t n_rows) {
+    if (n_rows < 1 || n_rows > VTI_NMS_TABLE_MAX_ROWS) return 0;
+    return (int64_t)sizeof(NmsTableHeader) + (int64_t)n_rows * (int64_t)sizeof(NmsRow);
+}
+
+// What is wrong with the settings of one packed row (nullptr: nothing); the checks vti_pack_nms_table makes of the struct's numbers.
+static const char* nms_settings_error(float conf, double iou, int32_t max_det, int32_t agnostic) {
+    if (!(conf >= 0.0f && conf <= 1.0f)) return "conf must be finite and in [0, 1]";
+    if (!(iou >= 0.0 && iou <= 1.0)) return "iou must be finite and in [0, 1]";
+    if (max_det < 1) return "max_det must be >= 1";
+    if (agnostic != 0 && agnostic != 1) return "agnostic must be 0 or 1";
+    return nullptr;
+}
+
+int32_t vti_pack_nms_table(vti_ctx* c, const vti_nms_params* params, int32_t n_rows, void* host_table, size_t nbytes) {
+    const char* fn = "vti_pack_nms_table";
+    if (!c) return fail(c, VTI_ERR_ARG, "vti_pack_nms_table: null ctx (the table is packed for its class count)");
+    if (!params || !host_table) return refuse(c, fn, "null params or table");
+    const int64_t need = vti_nms_table_bytes(n_rows);
+    if (!need) return refuse(c, fn, "n_rows must be in 1 .. VTI_NMS_TABLE_MAX_ROWS");
+    if ((int64_t)nbytes < need) return refuse(c, fn, "table smaller than vti_nms_table_bytes()");
+    const int nc = c->plan.desc.nc;
+    char msg[200];
+    for (int32_t k = 0; k < n_rows; ++k) {
+        const vti_nms_params& p = params[k];
+        const char* e = nms_settings_error(p.conf, p.iou, p.max_det, p.agnostic);
+        if (!e && p.n_classes < 0) e = "n_classes must be >= 0";
+        if (!e && p.n_classes > 0 && !p.classes) e = "classes is NULL but n_classes > 0";
+        if (e) {
+            snprintf(msg, sizeof msg, "%s: row %d: %s", fn, k, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+        for (int32_t i = 0; i < p.n_classes; ++i)
+            if (p.classes[i] < 0 || p.classes[i] >= nc) {
+                snprintf(msg, sizeof msg, "%s: row %d: classes[%d] = %d is outside [0, %d)", fn, k, i, p.classes[i], nc);
+                return fail(c, VTI_ERR_ARG, msg);
+            }
+        if (p.n_classes > 0 && nc > VTI_NMS_TABLE_MAX_CLASSES) {
+            snprintf(msg, sizeof msg, "%s: row %d: a class set needs a model of at most %d classes (this one has %d)", fn, k,
+                     VTI_NMS_TABLE_MAX_CLASSES, nc);
+            return fail(c, VTI_ERR_UNSUPPORTED, msg);
+        }
+    }
+    memset(host_table, 0, (size_t)need);
+    NmsTableHeader h = {};
+    h.magic = kNmsTableMagic; h.n_rows = n_rows; h.nc = nc; h.mask_words = kNmsMaskWords;
+    memcpy(host_table, &h, sizeof h);
+    for (int32_t k = 0; k < n_rows; ++k) {
+        const vti_nms_params& p = params[k];
+        NmsRow r = {};
+        r.conf = p.conf; r.max_det = p.max_det; r.iou = p.iou; r.agnostic = p.agnostic;
+        int named = 0;
+        for (int32_t i = 0; i < p.n_classes; ++i) {
+            unsigned& w = r.mask[p.classes[i] >> 5];
+            const unsigned bit = 1u << (p.classes[i] & 31);
+            named += !(w & bit);
+            w |= bit;
+        }
+        if (named > 0 && named < nc) r.filter = 1;
+        else memset(r.mask, 0, sizeof r.mask);      // a set that names every class is no set: the same bytes as n_classes = 0
+        memcpy((char*)host_table + sizeof h + (size_t)k * sizeof r, &r, sizeof r);
+    }
+    return VTI_OK;
+}
+
+int32_t vti_set_nms_table(vti_ctx* c, const void* host_table, const void* dev_table, int32_t n_rows, const int32_t* dev_row_of_frame) {
+    const char* fn = "vti_set_nms_table";
+    if (!c) return VTI_ERR_ARG;
+    if (!host_table) {          // clear: every NMS of the ctx takes its call's own arguments again
+        c->nms_host.clear();
+        c->nms_table = NmsTable{};
+        return VTI_OK;
+    }
+    if (!dev_table || ((uintptr_t)dev_table & 15)) return refuse(c, fn, "dev_table is required and must be 16-byte aligned");
+    if ((uintptr_t)dev_row_of_frame & 3) return refuse(c, fn, "dev_row_of_frame must be 4-byte aligned");
+    const int64_t need = vti_nms_table_bytes(n_rows);
+    if (!need) return refuse(c, fn, "n_rows must be in 1 .. VTI_NMS_TABLE_MAX_ROWS");
+    NmsTableHeader h;
+    memcpy(&h, host_table, sizeof h);
+    if (h.magic != kNmsTableMagic || h.mask_words != kNmsMaskWords) return refuse(c, fn, "host_table is not a table of vti_pack_nms_table");
+    if (h.n_rows != n_rows) return refuse(c, fn, "n_rows is not the row count host_table was packed with");
+    const int nc = c->plan.desc.nc;
+    if (h.nc != nc) return refuse(c, fn, "host_table was packed for a model with another class count");
+    char msg[200];
+    for (int32_t k = 0; k < n_rows; ++k) {
+        NmsRow r;
+        memcpy(&r, (const char*)host_table + sizeof h + (size_t)k * sizeof r, sizeof r);
+        const char* e = nms_settings_error(r.conf, r.iou, r.max_det, r.agnostic);
+        if (!e && (r.filter != 0 && r.filter != 1)) e = "damaged class-set flag";
+        if (!e && r.filter && nc > VTI_NMS_TABLE_MAX_CLASSES) e = "a class set on a model above VTI_NMS_TABLE_MAX_CLASSES classes";
+        int named = 0;
+        for (int j = 0; !e && j < 32 * kNmsMaskWords; ++j)
+            if ((r.mask[j >> 5] >> (j & 31)) & 1u) {
+                if (j >= nc) e = "a class outside [0, nc) in the class set";
+                ++named;
+            }
+        if (!e && (r.filter ? (named < 1 || named >= nc) : named != 0)) e = "class-set flag and mask disagree";
+        if (e) {
+            snprintf(msg, sizeof msg, "%s: row %d: %s", fn, k, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    }
+    c->nms_host.assign((const unsigned char*)host_table, (const unsigned char*)host_table + need);
+    c->nms_table.rows = (const NmsRow*)((const char*)dev_table + sizeof(NmsTableHeader));
+    c->nms_table.row_of_frame = dev_row_of_frame;
+    c->nms_table.n_rows = n_rows;
     return VTI_OK;
 }
 

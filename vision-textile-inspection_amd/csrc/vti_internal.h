@@ -295,6 +295,30 @@ static_assert(sizeof(FrameTableHeader) == 64, "the rows of a frame table stay 64
 void letterbox_geom(int H0, int W0, int H, int W, int& new_h, int& new_w, int& top, int& left);
 void frame_row_fill(int H, int W, int H0, int W0, long long offset, FrameRow& r);      // geometry of one frame on the H x W canvas (host)
 
+// The NMS table (vti_pack_nms_table): an NmsTableHeader, then one NmsRow per row.  The class set is a bit mask of kNmsMaskWords * 32
+// bits (VTI_NMS_TABLE_MAX_CLASSES); filter == 0 means every class and the mask is then all zero, so equal settings pack to equal bytes.
+constexpr int kNmsMaskWords = VTI_NMS_TABLE_MAX_CLASSES / 32;
+struct NmsRow {
+    float conf;
+    int max_det;
+    double iou;
+    int agnostic, filter;
+    int pad[2];                 // zero
+    unsigned mask[kNmsMaskWords];
+};
+static_assert(sizeof(NmsRow) == 32 + 4 * kNmsMaskWords && sizeof(NmsRow) % 16 == 0, "NMS table rows stay 16-byte aligned");
+constexpr int kNmsTableMagic = 0x31544e56;      // "VNT1"
+struct NmsTableHeader {
+    int magic, n_rows, nc, mask_words;
+    int pad[12];
+};
+static_assert(sizeof(NmsTableHeader) == 64, "the rows of an NMS table follow a 64-byte header");
+struct NmsTable {               // what the NMS launch takes: the device rows, the per-frame row index (nullptr: row 0), the row count
+    const NmsRow* rows = nullptr;
+    const int* row_of_frame = nullptr;
+    int n_rows = 0;
+};
+
 // post-processing (post.hip)
 // table == nullptr: B frames of H0 x W0 back to back (vti_letterbox); else frame b is row b of the device table (vti_letterbox_frames)
 hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, const FrameRow* table, uint8_t* out, int H, int W,
@@ -302,8 +326,10 @@ hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, const 
 size_t nms_workspace_bytes(int B, int A);
 // `best`: optional [B, A, 2] floats (max class score, its first class index as a float) that the producer of `pred` wrote beside it
 // (vti_forward_scored): the candidate filter then reads 8 bytes per anchor instead of the nc class scores
+// table.rows != nullptr (vti_set_nms_table): conf, iou, agnostic, the class set and min(row.max_det, max_det) of frame b come from row
+// table.row_of_frame[b] (nullptr: row 0) of the device table; max_det stays the row stride of dets and the upper bound
 hipError_t launch_nms(const float* pred, const float* best, int B, int A, int nc, int nm, float conf, double iou, int max_det,
-                      int agnostic, float* dets, int* counts, void* ws, hipStream_t st);
+                      int agnostic, float* dets, int* counts, void* ws, hipStream_t st, NmsTable table = NmsTable{});
 hipError_t launch_anchor_best(const float* pred, int B, int A, int nc, int nm, float* best, hipStream_t st);   // the same pairs from pred itself
 float* nms_workspace_best(void* ws, int B, int A);       // [B, A, 2] floats at the end of the NMS workspace (vti_predict's own pair buffer)
 hipError_t launch_masks(int dtype, const float* dets, const int* counts, const void* proto, int B, int max_det,

@@ -4,14 +4,16 @@ PyTorch is plumbing here (device memory + the current HIP stream); all arithmeti
 libvti.so's HIP kernels.  Replaces the predictor object Ultralytics builds lazily on the first
 `model.predict(...)` (reference: measurement.py:208-210).
 """
+import contextlib
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
 
 from . import _lib, rawframes
 from . import overlay as _ov
-from ._lib import VtiCheckerParams, VtiConvInfo, VtiDesc, VtiMeasureParams, check, lib
+from ._lib import VtiCheckerParams, VtiConvInfo, VtiDesc, VtiMeasureParams, VtiNmsParams, check, lib
 
 # "h2": split-fp16 storage (every element an fp16 (hi, lo) pair, all products on the fp16 matrix pipe): the dtype whose results
 # meet the reference tolerance (mask IoU >= 0.999, |d box| < 1e-3) at a multiple of the fp32 engine's rate -- include/vti.h
@@ -122,6 +124,24 @@ class StampTable:
         self.host, self.dev, self.bits, self.n_words, self.shapes, self.n_stamps = host, dev, bits, n_words, shapes, n_stamps
         self.n = len(shapes)
         self.up_bytes = host.numel() + 4 * n_words      # what crossed to the device
+
+
+@dataclasses.dataclass(frozen=True)
+class NmsParams:
+    """One row of an NMS table (include/vti.h vti_nms_params): the settings of Ultralytics' non_max_suppression for the frames that
+    name the row.  classes: None for every class, or the class ids to keep (Ultralytics' `classes=`)."""
+    conf: float = 0.25
+    iou: float = 0.7
+    max_det: int = 300
+    agnostic: bool = False
+    classes: tuple = None
+
+
+class NmsTable:
+    """A packed NMS table (vti_pack_nms_table): `host` (the packed bytes, a CPU u8 tensor), `dev` (their device copy), `n_rows`."""
+
+    def __init__(self, host, dev, n_rows):
+        self.host, self.dev, self.n_rows = host, dev, n_rows
 
 
 class Engine:
@@ -258,14 +278,18 @@ class Engine:
         return out
 
     def predict_frames_into(self, buf, table, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True,
-                            mask_mode="logit", packing="bits", native=False):
+                            mask_mode="logit", packing="bits", native=False, nms=None):
         """predict_into for a batch whose frames differ in size: `buf` / `table` as letterbox_frames, `out` from
         alloc_outputs(table.B, ...).  Masks stay at the canvas size; out["xyxy"] is in each frame's own pixels.
         native=True (vti_predict_frames_native): frame-resolution masks in the ragged buffer of a set from
-        alloc_outputs(..., native_frames=table) -- any other set is a ValueError before any call."""
+        alloc_outputs(..., native_frames=table) -- any other set is a ValueError before any call.
+        nms=(NmsTable, rows): the call runs inside nms_table(table, rows)."""
         if native:
             self._check_ragged(out, table, max_det, "predict_frames_into")
         self._check_frames(table, B=out["counts"].shape[0], buf=buf)
+        if nms is not None:
+            with self._nms_scope(nms):
+                return self.predict_frames_into(buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode, packing, native)
         if native:
             check(self._ctx, lib().vti_predict_frames_native(
                 self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
@@ -319,7 +343,9 @@ class Engine:
 
     def nms(self, pred, conf=0.25, iou=0.7, max_det=300, agnostic=False, dets=None, counts=None, best=None):
         """pred: [B, 4+nc+nm, A] (any layout; tensors from forward()/alloc_pred are used in place).  best: the pairs forward(best=...)
-        wrote for THIS pred (vti_nms_scored: the candidate filter reads them instead of the class scores)."""
+        wrote for THIS pred (vti_nms_scored: the candidate filter reads them instead of the class scores).  Inside nms_table() the
+        settings of every frame come from its row of the table; conf, iou and agnostic are then ignored and max_det is the row
+        stride of dets and the upper bound of the rows' limits."""
         pred = self._anchor_major(pred)
         B = pred.shape[0]
         if dets is None:
@@ -334,6 +360,70 @@ class Engine:
             check(self._ctx, lib().vti_nms_scored(self._ctx, _ptr(pred), _ptr(best), B, float(conf), float(iou), int(max_det),
                                                   int(bool(agnostic)), _ptr(dets), _ptr(counts), _stream()))
         return dets, counts
+
+    # ---- NMS settings per frame and the `classes` filter (vti_pack_nms_table, vti_set_nms_table) --------------------------------
+    def pack_nms_table(self, params_list, device=None):
+        """One row per NmsParams of `params_list`, validated and packed by vti_pack_nms_table (a VtiError names the failing row and
+        field) and uploaded once -> NmsTable for nms_table() and the nms= argument of predict_into / predict_frames_into."""
+        rows = list(params_list)
+        n = len(rows)
+        if n < 1:
+            raise ValueError("pack_nms_table: at least one row")
+        keep = []           # the class lists stay alive until the call returns
+        arr = (VtiNmsParams * n)()
+        for k, p in enumerate(rows):
+            cls = None if p.classes is None else [int(c) for c in p.classes]
+            if cls is not None and not cls:
+                raise ValueError(f"pack_nms_table: row {k}: an empty class set keeps nothing; pass classes=None for every class")
+            ids = (C.c_int32 * len(cls))(*cls) if cls else None
+            keep.append(ids)
+            arr[k] = VtiNmsParams(float(p.conf), int(p.max_det), float(p.iou), int(bool(p.agnostic)), len(cls) if cls else 0,
+                                  C.cast(ids, C.POINTER(C.c_int32)) if cls else None)
+        nbytes = int(lib().vti_nms_table_bytes(n))
+        if nbytes <= 0:
+            raise ValueError(f"pack_nms_table: {n} rows are more than a table holds ({_lib.VTI_NMS_TABLE_MAX_ROWS})")
+        host = torch.zeros(nbytes, dtype=torch.uint8)
+        check(self._ctx, lib().vti_pack_nms_table(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
+        return NmsTable(host, host.to(device or self.device or "cuda"), n)
+
+    @contextlib.contextmanager
+    def nms_table(self, table, rows=None):
+        """While the block runs, every NMS of this engine (nms, predict_into, predict_frames_into) takes frame b's conf, iou,
+        max_det, agnostic and class set from row rows[b] of `table` (pack_nms_table); rows=None: row 0 for every frame.  rows: host
+        integers (range-checked here) or an int32 device tensor (checked by the kernel: a frame whose index is outside the table
+        comes back with count 0), one per frame.  The calls' own conf, iou and agnostic are ignored meanwhile and their max_det is
+        the row stride and the upper bound.  The table and the index stay referenced until the block ends, where the table is
+        cleared (vti_set_nms_table)."""
+        if not isinstance(table, NmsTable):
+            raise ValueError("nms_table: table must be the NmsTable of Engine.pack_nms_table()")
+        dev_rows = None
+        if rows is not None:
+            if isinstance(rows, torch.Tensor) and rows.is_cuda:
+                if rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous() or rows.device != table.dev.device:
+                    raise ValueError("nms_table: rows must be a contiguous int32 [B] tensor on the table's device")
+                dev_rows = rows
+            else:
+                host = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows)
+                if host.ndim != 1 or host.dtype.kind not in "iu" or host.size > self.max_batch:
+                    raise ValueError(f"nms_table: rows must be at most {self.max_batch} integers, one per frame")
+                if host.size and (host.min() < 0 or host.max() >= table.n_rows):
+                    raise ValueError(f"nms_table: row index outside [0, {table.n_rows})")
+                dev_rows = torch.from_numpy(host.astype(np.int32)).to(table.dev.device)
+            if dev_rows.numel() < self.max_batch:       # the library may be asked for any B up to max_batch
+                dev_rows = torch.cat((dev_rows, dev_rows.new_zeros(self.max_batch - dev_rows.numel())))
+        check(self._ctx, lib().vti_set_nms_table(self._ctx, C.c_void_p(table.host.data_ptr()), _ptr(table.dev), table.n_rows,
+                                                 _ptr(dev_rows)))
+        try:
+            yield table
+        finally:
+            check(self._ctx, lib().vti_set_nms_table(self._ctx, None, None, 0, None))
+
+    def _nms_scope(self, nms):
+        """nms=(table, rows) of the predict forms -> the context that holds the table for the call; None: nothing to hold."""
+        if nms is None:
+            return contextlib.nullcontext()
+        table, rows = nms
+        return self.nms_table(table, rows)
 
     def masks(self, dets, counts, proto, mode="logit", packing="u8", capacity=None, masks=None, offsets=None):
         """-> (masks u8 [capacity,H,W] or [capacity,H,W/8], offsets i32 [B+1]).  With capacity=None the
@@ -476,10 +566,14 @@ class Engine:
         )
 
     def predict_into(self, frames, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True,
-                     mask_mode="logit", packing="bits", native=False):
+                     mask_mode="logit", packing="bits", native=False, nms=None):
         """Whole pipeline (letterbox -> net -> NMS -> masks -> scale_boxes) on the current stream with
         no host synchronisation; `out` from alloc_outputs().  native=True: scale_boxes -> frame-resolution masks
-        (retina_masks; `out` from alloc_outputs(native_hw=(H0, W0)))."""
+        (retina_masks; `out` from alloc_outputs(native_hw=(H0, W0))).  nms=(NmsTable, rows): the call runs inside
+        nms_table(table, rows) -- per-frame NMS settings and the class filter."""
+        if nms is not None:
+            with self._nms_scope(nms):
+                return self.predict_into(frames, out, conf, iou, max_det, agnostic, swap_rb, mask_mode, packing, native)
         B, H0, W0, _ = frames.shape
         capacity = out["masks"].shape[0]
         if native:

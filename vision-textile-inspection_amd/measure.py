@@ -39,6 +39,7 @@ from . import annotate as _annotate
 from ._lib import (VTI_MEASURE_BAD_CAMERA, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_OK, VTI_STITCH_KEPT,
                    VTI_STITCH_NEAR, VTI_STITCH_SELECTED, VTI_STITCH_WIDTH, VtiCheckerParams, VtiMeasureParams)
 from .consumer import rodrigues
+from .engine import NmsParams
 
 ERRORS = {VTI_MEASURE_NO_FABRIC: "Fabric not detected", VTI_MEASURE_NO_STITCHES: "No stitches detected",
           VTI_MEASURE_BAD_CAMERA: "Unknown camera"}     # the last one is this package's: a device-side index outside the table
@@ -234,15 +235,41 @@ class _DeviceStage:
         """The stage's one measure call on the predict outputs (Engine.measure's contract)."""
         return eng.measure(o, params, H0, W0, **kw)
 
+    @staticmethod
+    def _per_camera_nms(n_cams, conf, iou, max_det):
+        """conf, iou, max_det of a rig's process_frames, each a scalar or a sequence with one entry per camera -> (conf, iou, max_det,
+        nms_rows): all scalars give them back with nms_rows None (the table-free predict); otherwise nms_rows is one NmsParams per
+        camera, max_det the largest one (the row stride of the output set) and conf, iou what the call passes along unused.  A
+        sequence of another length is a ValueError."""
+        seq = lambda v: isinstance(v, (list, tuple, np.ndarray, torch.Tensor)) and np.ndim(v) == 1
+        if not any(seq(v) for v in (conf, iou, max_det)):
+            return conf, iou, max_det, None
+        per = {}
+        for name, v in (("conf", conf), ("iou", iou), ("max_det", max_det)):
+            vals = [x.item() if hasattr(x, "item") else x for x in v] if seq(v) else [v] * n_cams
+            if len(vals) != n_cams:
+                raise ValueError(f"process_frames: {name} has {len(vals)} entries but the rig has {n_cams} cameras "
+                                 "(a scalar, or one entry per camera)")
+            per[name] = vals
+        rows = tuple(NmsParams(float(c), float(i), int(m), False, None) for c, i, m in zip(per["conf"], per["iou"], per["max_det"]))
+        if min(r.max_det for r in rows) < 1:
+            raise ValueError("process_frames: every max_det must be >= 1")
+        return rows[0].conf, rows[0].iou, max(r.max_det for r in rows), rows
+
     @torch.inference_mode()
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
-                       jpeg_quality=95, mixed=False, rows=False, burn_text=False, extra_text=None, rasterise=None):
+                       jpeg_quality=95, mixed=False, rows=False, burn_text=False, extra_text=None, rasterise=None, nms_rows=None):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
         selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0 (frames of
         differing sizes, which `mixed` allows with annotate: the list of every frame's H0).  params /
         cameras as Engine.measure takes them; a callable `params` is called with (engine, device) once the outputs exist (the
         camera table needs both).  rows (without annotate): a third item, every frame's per-slot rows as `_slot_rows` gives them.
-        burn_text: the third item is a _Deferred -- the pictures are drawn but neither copied nor encoded yet."""
+        burn_text: the third item is a _Deferred -- the pictures are drawn but neither copied nor encoded yet.
+        nms_rows (with cameras): one NmsParams per camera -- the predict runs under their NMS table with `cameras` as the row index,
+        and max_det is the output set's row stride."""
+        nms = None
+        if nms_rows is not None:
+            nms = lambda eng, dev: (self.model._nms_table(eng, dev, nms_rows), np.asarray(cameras))
         if encode is not None:
             if encode != "jpeg":
                 raise ValueError(f'process_frames: encode must be None or "jpeg", got {encode!r}')
@@ -269,11 +296,12 @@ class _DeviceStage:
             if retina_masks and (annotate is not None or not mixed):     # mixed + retina_masks measures, but has nothing to draw from
                 raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
             eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False,
-                                                                  keep_frames=annotate is not None, retina_masks=bool(retina_masks))
+                                                                  keep_frames=annotate is not None, retina_masks=bool(retina_masks),
+                                                                  nms=nms)
             B, H0, W0 = len(shapes), None, None
         else:
             eng, o, (B, H0, W0), _ = self.model._predict_outputs(frames, conf, iou, max_det, imgsz, False, False, retina_masks,
-                                                                 keep_frames=annotate is not None)
+                                                                 keep_frames=annotate is not None, nms=nms)
         self.model._raise_if_corrupt(info)
         sel = None
         if annotate is not None:
@@ -475,13 +503,18 @@ class MultiCameraMeasurer(_DeviceStage):
         Returns one record per frame, in frame order, each with a 'camera' key; frames of the same camera are smoothed in frame
         order.  annotate, encode, jpeg_quality, mixed: as StitchMeasurer.process_frames (frames of differing sizes only with
         mixed=True) -> (annotated, records).  burn_text, extra_text, rasterise (keyword only): as StitchMeasurer.process_frames, with
-        mixed=True too (vti_stamp_frames: every picture gets its text at its own size)."""
+        mixed=True too (vti_stamp_frames: every picture gets its text at its own size).
+        conf, iou, max_det: each a scalar, or a sequence with one entry per camera (stations with their own thresholds, config.py:
+        69-73): the one predict then runs under an NMS table of one row per camera with `cameras` as the row index
+        (vti_set_nms_table), every frame comes out as its camera's scalars alone would give it, and the output set is allocated for
+        the largest max_det.  A sequence of another length is a ValueError before anything is predicted."""
 
     def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
                         burn_text=False, extra_text=None, rasterise=None):
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
+        conf, iou, max_det, nms_rows = self._per_camera_nms(len(self.params), conf, iou, max_det)
         got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
-                                  mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
+                                  mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, nms_rows=nms_rows)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         if annotate is None:
@@ -636,10 +669,13 @@ class MultiCameraChecker(_DeviceStage):
         smoothed within its camera in frame order.  mixed (keyword only): True lets a list of differing sizes be combined with
         annotate and encode (vti_annotate_checker_frames, vti_encode_jpeg_frames, vti_stamp_frames: every picture at its own size,
         the text placed by its own height), and lets retina_masks=True measure such a list (no annotate then); without it those
-        combinations are refused, as MultiCameraMeasurer refuses them.  burn_text, extra_text, rasterise: as there."""
+        combinations are refused, as MultiCameraMeasurer refuses them.  burn_text, extra_text, rasterise: as there.
+        conf, iou, max_det: each a scalar or one entry per camera, as MultiCameraMeasurer.process_frames takes them."""
         cams = self._cameras(frames, cameras)
+        conf, iou, max_det, nms_rows = self._per_camera_nms(len(self.params), conf, iou, max_det)
         got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
-                                  bool(mixed), rows=bool(rows), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
+                                  bool(mixed), rows=bool(rows), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise,
+                                  nms_rows=nms_rows)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         full = lambda r, b: dict(r, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])

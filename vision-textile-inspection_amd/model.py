@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import rawframes
-from .engine import Engine, unpack_bits
+from .engine import Engine, NmsParams, unpack_bits
 from .weights import random_weights, unpack_container
 
 
@@ -209,6 +209,7 @@ class YOLO:
         self.max_batch = max_batch
         self._outs = {}
         self._frame_tables = {}
+        self._nms_tables = {}
         self.names = names if names is not None else {i: f"class{i}" for i in range(nc)}
         self._engines = {}
 
@@ -352,14 +353,40 @@ class YOLO:
                 raise ValueError(f"every frame of a list source must be uint8 HxWx3, got shape {x}")
         return [x[:2] for x in shapes]
 
+    @staticmethod
+    def _classes_arg(classes, nc):
+        """Ultralytics' `classes=` -> None (every class) or the sorted tuple of distinct class ids; anything else is a ValueError."""
+        if classes is None:
+            return None
+        if isinstance(classes, torch.Tensor):
+            classes = classes.detach().cpu().numpy()
+        arr = np.asarray(classes)
+        if arr.size == 0:
+            raise ValueError("predict: classes is empty (it would keep nothing); pass None for every class")
+        if arr.dtype.kind not in "iu" or arr.ndim > 1:
+            raise ValueError(f"predict: classes must be None, an int or a sequence of ints, got {classes!r}")
+        ids = sorted({int(c) for c in arr.reshape(-1)})
+        if ids[0] < 0 or ids[-1] >= nc:
+            raise ValueError(f"predict: classes must lie in [0, {nc}), got {classes!r}")
+        return tuple(ids)
+
+    def _nms_table(self, eng, dev, rows):
+        """The NMS table of `rows` (a tuple of NmsParams) on `eng`, packed and uploaded once per (engine, device, settings)."""
+        key = (id(eng), str(dev), rows)
+        ent = self._nms_tables.get(key)
+        if ent is None:
+            self._nms_tables.clear()        # one at a time, as the output set
+            ent = self._nms_tables[key] = (eng, eng.pack_nms_table(rows, dev))
+        return ent[1]
+
     def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, keep_frames=False,
-                                retina_masks=False):
+                                retina_masks=False, nms=None):
         """_predict_outputs for frames of differing sizes: the frames are flattened into one pinned staging buffer, copied with one
         asynchronous H2D and run through one vti_predict_frames on the stride-rounded imgsz canvas.  The packed frame table, the
         staging buffer and its device twin are cached per (engine, shapes).  -> (engine, output set, FrameTable, (H, W)).
         keep_frames: as _predict_outputs -- the flat device buffer this predict consumed stays in _last_frames for a caller that
         draws on it.  retina_masks: vti_predict_frames_native into the ragged output set (Engine.alloc_outputs(native_frames=)),
-        cached per (engine, B, max_det, shapes) as the uniform retina set is per native_hw."""
+        cached per (engine, B, max_det, shapes) as the uniform retina set is per native_hw.  nms: as _predict_outputs."""
         new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
         H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
         B = len(shapes)
@@ -390,15 +417,17 @@ class YOLO:
         if o is None:
             self._outs.clear()
             o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=table if retina_masks else None)
-        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks))
+        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks),
+                                nms=nms(eng, dev) if nms is not None else None)
         if keep_frames:
             self._last_frames = buf
         return eng, o, table, (H, W)
 
-    def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks, keep_frames=False):
+    def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks, keep_frames=False, nms=None):
         """The device half of predict(): enqueues the whole pipeline into the cached output set and returns
         (engine, output set, (B, H0, W0), letterbox (H, W)) without reading anything back (predict() and
-        measure.StitchMeasurer both start here)."""
+        measure.StitchMeasurer both start here).  nms: None, or a callable (engine, device) -> (NmsTable, rows): the NMS then takes
+        frame b's settings from row rows[b] of the table (Engine.nms_table) and max_det is the row stride and the upper bound."""
         if source is None:
             raise ValueError("predict() needs a source")
         frames = self._to_device_batch(source)
@@ -415,7 +444,8 @@ class YOLO:
         if o is None:
             self._outs.clear()              # one cached set at a time: a new shape replaces the old one
             o = self._outs[key] = eng.alloc_outputs(B, max_det, B * max_det, "bits", frames.device, native_hw=native_hw)
-        eng.predict_into(frames, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks))
+        eng.predict_into(frames, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks),
+                         nms=nms(eng, frames.device) if nms is not None else None)
         # the device batch this predict consumed is kept only for a caller that draws on it (measure.py, annotate=): otherwise
         # the model holds no reference to it once the call returns
         self._last_frames = frames if keep_frames else None
@@ -423,7 +453,7 @@ class YOLO:
 
     @torch.inference_mode()
     def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
-                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, polygons=False, **_ignored):
+                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, classes=None, polygons=False, **_ignored):
         """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
         ndarray sources.  retina_masks=True: masks at the frame size, Ultralytics'
         process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes.
@@ -444,7 +474,16 @@ class YOLO:
         one vti_mask_polygons_frames call for a list whose frames differ in size (on the ragged frame-size rows with
         retina_masks=True, mixed=True), one vti_mask_polygons call over the live slots for frames of one size, and one copy of the
         points and offsets to the host; .xy / .xyn then return without touching the device.  Without it they are made per frame
-        on first access, with the same values."""
+        on first access, with the same values.
+        classes (keyword only): None, an int, or a sequence / tensor of ints in [0, nc), as Ultralytics takes it: only anchors whose
+        best class is in the set enter the NMS.  The filter runs on the device where Ultralytics' non_max_suppression has it --
+        after the confidence test, before the greedy pass and max_det -- through a one-row NMS table (vti_set_nms_table); a bad
+        value is a ValueError before a device is touched.  Without it the call takes the table-free path."""
+        classes = self._classes_arg(classes, self.nc)
+        nms = None
+        if classes is not None:
+            row = NmsParams(float(conf), float(iou), int(max_det), bool(agnostic_nms), classes)
+            nms = lambda eng, dev: (self._nms_table(eng, dev, (row,)), None)
         if not isinstance(mixed, (bool, np.bool_)):
             raise ValueError(f"predict: mixed must be True or False, got {mixed!r}")
         if not isinstance(polygons, (bool, np.bool_)):
@@ -465,10 +504,11 @@ class YOLO:
                                  "(frame-resolution masks for mixed sizes are not supported)")
             ragged = bool(retina_masks)
             eng, o, table, (H, W) = self._predict_outputs_frames(source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb,
-                                                                  retina_masks=ragged)
+                                                                  retina_masks=ragged, nms=nms)
             B = len(shapes)
         else:
-            eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks)
+            eng, o, (B, H0, W0), (H, W) = self._predict_outputs(source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks,
+                                                                 nms=nms)
             shapes, table = [(H0, W0)] * B, None
         self._raise_if_corrupt(info)
         dets, xyxy, masks = o["dets"], o["xyxy"], o["masks"]
