@@ -116,27 +116,31 @@ def cases(vti_amd):
     cam_base = dict(m_base, cameras=one, n_cams=2, cams=one)
     cam_faults = [("null ctx", dict(ctx=None)), ("null cameras", dict(cameras=None)), ("null cams", dict(cams=None)), ("n_cams 0", dict(n_cams=0)),
                   ("cameras misaligned", dict(cameras=_at(8))), ("cams misaligned", dict(cams=_at(2)))]
-    yield from entry("vti_measure_cameras", cam_head + m_in + shape + m_out, cam_base, cam_faults + m_ptr_faults + m_size_faults)
     fr_base = dict(cam_base, ht=_hp(t_in), dt=one, nbytes=m_need_frames)
     fr_short = [(c, dict(o, nbytes=m_need_frames - 1) if c == "scratch one byte short" else o) for c, o in m_ptr_faults]
-    yield from entry("vti_measure_frames", cam_head + m_in + ["ht", "dt", "B", "max_det", "cap"] + m_out, fr_base,
-                     cam_faults + table_faults("ht", "dt", "B", t_in, B) + fr_short + [("native 1", dict(native=1))])
-    yield from entry("vti_measure_frames_native",
-                     cam_head + ["masks", "bases", "cbytes"] + m_in[2:] + ["ht", "dt", "B", "max_det", "cap"] + m_out,
-                     dict(fr_base, bases=one, cbytes=1 << 20),
-                     cam_faults + table_faults("ht", "dt", "B", t_in, B) + [(c, o) for c, o in fr_short if "native" not in c and c != "masks misaligned"] +
-                     [("null bases", dict(bases=None)), ("cbytes -1", dict(cbytes=-1)), ("bases misaligned", dict(bases=_at(4))),
-                      ("masks misaligned", dict(masks=_at(4)))])
-
-    two = (vti_amd._lib.VtiMeasureParams * 2)(mp_.to_c(), mp_.to_c())
     cam_bytes = L.vti_measure_cameras_bytes(2)
     cam_table = (C.c_uint8 * cam_bytes)()
-    pack_faults = [("null params", dict(params=None)), ("n_cams 0", dict(n_cams=0)), ("null table", dict(table=None)),
-                   ("table one byte short", dict(nbytes=cam_bytes - 1))]
-    for case, c in _settings_faults(mp_, True):
-        pack_faults.append(("camera 1: " + case, dict(params=(vti_amd._lib.VtiMeasureParams * 2)(mp_.to_c(), c))))
-    yield from entry("vti_measure_pack_cameras", ["ctx", "params", "n_cams", "table", "nbytes"],
-                     dict(ctx=ctx, params=two, n_cams=2, table=cam_table, nbytes=cam_bytes), pack_faults)
+
+    def rig(stem, pack, array, p, measure):
+        """The camera-table and frame-table forms of vti_measure (stem) or vti_measure_checker, and the family's pack call."""
+        yield from entry(stem + "_cameras", cam_head + m_in + shape + m_out, cam_base, cam_faults + m_ptr_faults + m_size_faults)
+        yield from entry(stem + "_frames", cam_head + m_in + ["ht", "dt", "B", "max_det", "cap"] + m_out, fr_base,
+                         cam_faults + table_faults("ht", "dt", "B", t_in, B) + fr_short + [("native 1", dict(native=1))])
+        yield from entry(stem + "_frames_native",
+                         cam_head + ["masks", "bases", "cbytes"] + m_in[2:] + ["ht", "dt", "B", "max_det", "cap"] + m_out,
+                         dict(fr_base, bases=one, cbytes=1 << 20),
+                         cam_faults + table_faults("ht", "dt", "B", t_in, B) + [(c, o) for c, o in fr_short if "native" not in c and c != "masks misaligned"] +
+                         [("null bases", dict(bases=None)), ("cbytes -1", dict(cbytes=-1)), ("bases misaligned", dict(bases=_at(4))),
+                          ("masks misaligned", dict(masks=_at(4)))])
+        pack_faults = [("null params", dict(params=None)), ("n_cams 0", dict(n_cams=0)), ("null table", dict(table=None)),
+                       ("table one byte short", dict(nbytes=cam_bytes - 1))]
+        for case, c in _settings_faults(p, measure):
+            pack_faults.append(("camera 1: " + case, dict(params=array(p.to_c(), c))))
+        yield from entry(pack, ["ctx", "params", "n_cams", "table", "nbytes"],
+                         dict(ctx=ctx, params=array(p.to_c(), p.to_c()), n_cams=2, table=cam_table, nbytes=cam_bytes), pack_faults)
+
+    yield from rig("vti_measure", "vti_measure_pack_cameras", vti_amd._lib.VtiMeasureParams * 2, mp_, True)
+    yield from rig("vti_measure_checker", "vti_checker_pack_cameras", vti_amd._lib.VtiCheckerParams * 2, cp_, False)
 
     # ---- the drawing calls of one frame size -----------------------------------------------------------------------------------
     d_in = ["masks", "native", "dets", "xyxy", "counts", "offsets", "max_det", "cap"]
@@ -168,6 +172,12 @@ def cases(vti_amd):
                      d_faults + nulls(d_ptrs + ["params"]) + meas_faults + [("canvas too large", dict(ctx=wide_eng._ctx))] +
                      [(case, dict(params=C.byref(c))) for case, c in _settings_faults(cp_, False)])
 
+    yield from entry("vti_annotate_checker_cameras",
+                     ["ctx", "frames", "B", "H0", "W0", "cameras", "n_cams", "cams"] + d_in + d_meas + d_sel + ["mp"] + d_out,
+                     dict(d_base, cameras=one, n_cams=2, cams=one),
+                     d_faults + nulls(d_ptrs + ["cameras"]) + meas_faults + [("canvas too large", dict(ctx=wide_eng._ctx))] +
+                     [("n_cams 0", dict(n_cams=0)), ("cameras misaligned", dict(cameras=_at(8))), ("cams misaligned", dict(cams=_at(2)))])
+
     o_need = L.vti_overlay_scratch_bytes(ctx, n_sel, max_det, H0, W0, mp)
     o_mid = ["plates", "pal", "nc", "alpha", "beta"]
     o_base = dict(d_base, plates=one, pal=(C.c_uint8 * 18)(*range(18)), nc=6, alpha=0.3, beta=0.7, mode=3, ann=None, nbytes=o_need)
@@ -198,11 +208,12 @@ def cases(vti_amd):
     af_need = L.vti_annotate_frames_scratch_bytes(ctx, _hp(t_out), max_det, mp)
     f_base = dict(ht=_hp(t_in), dt=one, hot=_hp(t_out), dot=one)
     short = lambda faults, need: [(c, dict(o, nbytes=need - 1) if c == "scratch one byte short" else o) for c, o in faults]
-    yield from entry("vti_annotate_frames", ["ctx", "frames", "ht", "dt", "B", "cameras", "n_cams", "cams"] + d_in + d_meas + d_sel +
-                     ["mp", "hot", "dot"] + d_out, dict(d_base, cameras=one, n_cams=2, cams=one, nbytes=af_need, **f_base),
-                     short(f_faults, af_need) + nulls(d_ptrs + ["cameras"]) + meas_faults +
-                     [("native 1", dict(native=1)), ("n_cams 0", dict(n_cams=0)), ("cameras misaligned", dict(cameras=_at(8))),
-                      ("cams misaligned", dict(cams=_at(2)))])
+    for name in ("vti_annotate_frames", "vti_annotate_checker_frames"):
+        yield from entry(name, ["ctx", "frames", "ht", "dt", "B", "cameras", "n_cams", "cams"] + d_in + d_meas + d_sel +
+                         ["mp", "hot", "dot"] + d_out, dict(d_base, cameras=one, n_cams=2, cams=one, nbytes=af_need, **f_base),
+                         short(f_faults, af_need) + nulls(d_ptrs + ["cameras"]) + meas_faults +
+                         [("native 1", dict(native=1)), ("n_cams 0", dict(n_cams=0)), ("cameras misaligned", dict(cameras=_at(8))),
+                          ("cams misaligned", dict(cams=_at(2)))])
     of_need = L.vti_overlay_frames_scratch_bytes(ctx, _hp(t_out), max_det, mp)
     yield from entry("vti_overlay_frames", ["ctx", "frames", "ht", "dt", "B", "masks", "native", "bases", "cbytes"] + d_in[2:] + o_mid + d_sel +
                      ["mode", "ann", "mp", "hot", "dot"] + d_out, dict(o_base, bases=None, cbytes=0, nbytes=of_need, **f_base),

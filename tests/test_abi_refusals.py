@@ -18,7 +18,7 @@ def calls(lib_built):
 
 def test_the_record_and_the_cases_name_the_same_calls(calls):
     recorded = [(entry, case) for entry, case, _, _ in RECORD["rows"]]
-    assert len(recorded) == len(set(recorded)) >= 300 and set(recorded) == set(calls)
+    assert len(recorded) == len(set(recorded)) >= 741 and set(recorded) == set(calls)
     assert len(RECORD["commit"]) == 40
 
 

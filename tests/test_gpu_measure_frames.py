@@ -177,3 +177,42 @@ def test_multi_camera_measurer_takes_the_mixed_list():
             assert {k: v for k, v in g.items() if k not in ("timestamp", "camera")} == {k: v for k, v in e.items() if k != "timestamp"}, b
             seen += g["edge_distance_mm"] is not None
     assert seen >= 2                                               # the deques are in use, or the carry-over is not tested
+
+
+def test_argument_shapes_measure_newly_takes_equal_the_list_form():
+    """measure() takes what measure_checker() always took: one params object beside `cameras`, and a packed table beside `frames`
+    without `cameras`.  Each equals the list form of the same call byte for byte.  3 frames on a 64 x 96 canvas, at most 4 instances
+    per frame (a fabric and stitches above its lower edge)."""
+    need_gpu()
+    import vti_amd
+    eng = _engine(64, 96, B=4)
+    H, W, B, max_det = 64, 96, 3, 4
+    boxes = [(8, 30, 88, 60, 1), (20, 20, 28, 26, 0), (44, 20, 52, 26, 0), (68, 20, 76, 26, 0)]      # canvas px, class
+    counts = np.array([4, 0, 3], np.int32)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    dets = np.zeros((B, max_det, 38), np.float32)
+    masks = np.zeros((int(offsets[-1]), H, W // 8), np.uint8)
+    for b in range(B):
+        for i in range(counts[b]):
+            x1, y1, x2, y2, cls = boxes[i]
+            dets[b, i, :6] = (x1, y1, x2, y2, 0.9 - 0.01 * i, cls)
+            m = np.zeros((H, W), np.uint8)
+            m[y1:y2, x1:x2] = 1
+            masks[offsets[b] + i] = pack(m, False, W)
+    out = dict(dets=torch.from_numpy(dets).cuda(), counts=torch.from_numpy(counts).cuda(), offsets=torch.from_numpy(offsets).cuda(),
+               masks=torch.from_numpy(masks).cuda())
+    p = vti_amd.MeasureParams(*CALIBS[0], roi_enabled=False, min_stitches=1)
+    # one size: a single params object beside `cameras`
+    out["xyxy"] = eng.scale_boxes(out["dets"], out["counts"], 48, 64)
+    want = _host(eng.measure(out, [p], 48, 64, cameras=[0, 0, 0], result=poisoned(B, 7)))
+    assert want["frame_i32"][0, 1] == 3 and want["frame_i32"][2, 1] == 2 and want["frame_i32"][0, 2] == 1       # stitches and fabric seen
+    got = _host(eng.measure(out, p, 48, 64, cameras=[0, 0, 0], result=poisoned(B, 7)))
+    for k in OUT_KEYS:
+        assert got[k].tobytes() == want[k].tobytes(), k
+    # differing sizes: the packed table beside `frames`, no `cameras`
+    ft, _, _ = eng.pack_frames([(48, 64), (32, 40), (48, 64)], device="cuda")
+    out["xyxy"] = eng.scale_boxes(out["dets"], out["counts"], frames=ft)
+    want = _host(eng.measure(out, [p], frames=ft, result=poisoned(B, 7)))
+    got = _host(eng.measure(out, eng.pack_cameras([p], "cuda"), frames=ft, result=poisoned(B, 7)))
+    for k in OUT_KEYS:
+        assert got[k].tobytes() == want[k].tobytes(), k

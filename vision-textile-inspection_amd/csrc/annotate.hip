@@ -702,20 +702,21 @@ void annotate_layout(int n_sel, int max_det, int H0, int W0, int max_points, Ann
     L.total = L.off_areas + (size_t)n_sel * L.area_bytes;
 }
 
-// The launch arguments both entry points share, and the scratch carved by annotate_layout.
-static AnnArgs annotate_args(const AnnotateLayout& L, const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks, int native,
-                             const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det, int nm,
-                             int capacity, int H, int W, const int* frame_i32, const double* stitch_f64, const int* stitch_i32,
-                             const int* select, int n_sel, int max_points, int outline_colour, uint8_t* out, int* status, void* scratch) {
-    unsigned char* ws = (unsigned char*)scratch;
+// The layout of the scratch and the launch arguments both entry points share: the scratch carved, every field but the checker's row.
+static AnnArgs annotate_args(AnnotateLayout& L, const uint8_t* frames, int H0, int W0, const CameraChoice& cams, const OutputSet& o,
+                             const Canvas& cv, const DrawInputs& d, int outline_colour, const AnnotateFrames* fr) {
+    annotate_layout(d.n_sel, o.max_det, H0, W0, d.max_points, L);
+    unsigned char* ws = (unsigned char*)d.scratch;
     AnnArgs a;
     memset(&a, 0, sizeof a);
-    a.frames = frames; a.out = out; a.status_out = status;
-    a.select = select; a.B = B; a.n_sel = n_sel; a.H0 = H0; a.W0 = W0; a.WW = L.WW;
-    a.masks = masks; a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
-    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H = native ? H0 : H; a.W = native ? W0 : W;
-    a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
-    a.max_points = max_points; a.outline_colour = outline_colour;
+    a.frames = frames; a.out = d.out; a.status_out = d.status;
+    a.select = d.dev_select; a.B = o.B; a.n_sel = d.n_sel; a.H0 = H0; a.W0 = W0; a.WW = L.WW;
+    if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; }
+    a.table = (const CameraRow*)cams.table; a.cam_of_frame = cams.cam_of_frame; a.n_cams = cams.n_cams;
+    a.masks = o.masks; a.dets = o.dets; a.xyxy = o.xyxy; a.counts = o.counts; a.offsets = o.offsets;
+    a.max_det = o.max_det; a.row = 6 + cv.nm; a.capacity = o.capacity; a.H = o.native ? H0 : cv.H; a.W = o.native ? W0 : cv.W;
+    a.frame_i32 = d.frame_i32; a.stitch_f64 = d.stitch_f64; a.stitch_i32 = d.stitch_i32;
+    a.max_points = d.max_points; a.outline_colour = outline_colour;
     a.recs = (Rec*)(ws + L.off_recs); a.meta = (int*)(ws + L.off_meta); a.env_pts = (int2*)(ws + L.off_env);
     a.cont = (int2*)(ws + L.off_cont); a.uni = (u64*)(ws + L.off_union);
     a.areas = ws + L.off_areas; a.area_bytes = L.area_bytes; a.off_runs = L.off_runs; a.off_rows = L.off_rows;
@@ -738,48 +739,36 @@ static hipError_t launch_outline_raster(const AnnArgs& a, const AnnotateLayout& 
     return hipGetLastError();
 }
 
-hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const void* cameras, int n_cams, const int* cam_of_frame,
-                           const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
-                           const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
-                           const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
-                           int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr) {
+hipError_t launch_annotate(const uint8_t* frames, int H0, int W0, const CameraChoice& cams, const OutputSet& o, const Canvas& cv,
+                           const DrawInputs& d, hipStream_t st, const AnnotateFrames* fr) {
     AnnotateLayout L;
-    annotate_layout(n_sel, max_det, H0, W0, max_points, L);
-    AnnArgs a = annotate_args(L, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, nm, capacity, H, W, frame_i32,
-                              stitch_f64, stitch_i32, select, n_sel, max_points, C_OUTLINE, out, status, scratch);
-    a.table = (const CameraRow*)cameras; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams;
-    if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; }
+    const AnnArgs a = annotate_args(L, frames, H0, W0, cams, o, cv, d, C_OUTLINE, fr);
     const size_t env_lds = (size_t)W0 * sizeof(int);
-    if (native) hipLaunchKernelGGL(annotate_prep_kernel<true>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
-    else hipLaunchKernelGGL(annotate_prep_kernel<false>, dim3(n_sel), dim3(kThreads), env_lds, st, a);
+    if (o.native) hipLaunchKernelGGL(annotate_prep_kernel<true>, dim3(d.n_sel), dim3(kThreads), env_lds, st, a);
+    else hipLaunchKernelGGL(annotate_prep_kernel<false>, dim3(d.n_sel), dim3(kThreads), env_lds, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_outline_raster(a, L, fr, st);
 }
 
-hipError_t launch_annotate_checker(const vti_checker_params* p, const void* cameras, int n_cams, const int* cam_of_frame,
-                                   const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
-                                   int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det,
-                                   int nm, int capacity, int H, int W, const int* frame_i32, const double* stitch_f64,
-                                   const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
-                                   void* scratch, hipStream_t st, const AnnotateFrames* fr) {
-    if (!p && !cameras) return hipErrorInvalidValue;
-    if (fr && (p || native)) return hipErrorInvalidValue;
+hipError_t launch_annotate_checker(const vti_checker_params* p, const uint8_t* frames, int H0, int W0, const CameraChoice& cams,
+                                   const OutputSet& o, const Canvas& cv, const DrawInputs& d, hipStream_t st,
+                                   const AnnotateFrames* fr) {
+    if (!p && !cams.table) return hipErrorInvalidValue;
+    if (fr && (p || o.native)) return hipErrorInvalidValue;
     AnnotateLayout L;
-    annotate_layout(n_sel, max_det, H0, W0, max_points, L);
-    AnnArgs a = annotate_args(L, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det, nm, capacity, H, W,
-                              frame_i32, stitch_f64, stitch_i32, select, n_sel, max_points, C_ENVELOPE, out, status, scratch);
+    const AnnArgs a = annotate_args(L, frames, H0, W0, p ? CameraChoice{} : cams, o, cv, d, C_ENVELOPE, fr);
     CameraRow c;
     memset(&c, 0, sizeof c);
     if (p) checker_pack(*p, &c);
-    else { a.table = (const CameraRow*)cameras; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
-    if (fr) { a.rows_in = fr->rows_in; a.rows_out = fr->rows_out; }
     // not native: the envelope table and the bits of the source columns and rows the resize reads
-    const size_t lds = native ? (size_t)W0 * sizeof(int) : ((size_t)W0 + (size_t)((W + 31) / 32) + (size_t)((H + 31) / 32)) * sizeof(int);
-    if (p && native) hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, dim3(n_sel), dim3(kThreads), lds, st, a, c);
-    else if (p) hipLaunchKernelGGL(annotate_checker_prep_kernel<false>, dim3(n_sel), dim3(kThreads), lds, st, a, c);
-    else if (native) hipLaunchKernelGGL((annotate_checker_prep_kernel<true, true>), dim3(n_sel), dim3(kThreads), lds, st, a, c);
-    else hipLaunchKernelGGL((annotate_checker_prep_kernel<false, true>), dim3(n_sel), dim3(kThreads), lds, st, a, c);
+    const size_t lds = o.native ? (size_t)W0 * sizeof(int)
+                                : ((size_t)W0 + (size_t)((cv.W + 31) / 32) + (size_t)((cv.H + 31) / 32)) * sizeof(int);
+    const dim3 grid(d.n_sel), block(kThreads);
+    if (p && o.native) hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, grid, block, lds, st, a, c);
+    else if (p) hipLaunchKernelGGL(annotate_checker_prep_kernel<false>, grid, block, lds, st, a, c);
+    else if (o.native) hipLaunchKernelGGL((annotate_checker_prep_kernel<true, true>), grid, block, lds, st, a, c);
+    else hipLaunchKernelGGL((annotate_checker_prep_kernel<false, true>), grid, block, lds, st, a, c);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_outline_raster(a, L, fr, st);

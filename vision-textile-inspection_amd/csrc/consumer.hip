@@ -707,66 +707,83 @@ void measure_pack_camera(const vti_measure_params& p, void* row) {
     memcpy(row, &c, sizeof c);
 }
 
-// p: the one camera (vti_measure), or nullptr with a device table of n_cams rows and the frames' indices (vti_measure_cameras).
-hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
-                          int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
-                          int nm, int capacity, int H, int W, int H0, int W0, const FrameRow* frames, void* scratch, double* frame_f64,
-                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st, const long long* bases,
-                          long long capacity_bytes) {
-    if (B == 0) return hipSuccess;
-    if (frames && native && (!bases || capacity_bytes < 0)) return hipErrorInvalidValue;
-    if (!(frames && native)) bases = nullptr;
+// ---- what launch_measure and launch_measure_checker do alike -----------------------------------------------------------------------
+// The scratch carved as measure_scratch_layout, and the per-slot moments (and, for letterbox slots, the raw emptiness) launched into it.
+// o.bases is dropped unless the masks are the ragged rows (frame table and native).
+struct MeasureScratch { long long* stats; int* raw; int* env; };
+static int native_words_per_row(int W0) { return 2 * ((W0 + 63) / 64); }       // 32-bit words of a frame-size mask row
+static hipError_t measure_front(OutputSet& o, const Canvas& cv, const FrameSizes& fs, void* scratch, hipStream_t st, MeasureScratch& s) {
+    const int H = cv.H, W = cv.W, H0 = fs.H0, W0 = fs.W0, B = o.B;
+    const FrameRow* frames = fs.rows;
+    if (frames && o.native && (!o.bases || o.capacity_bytes < 0)) return hipErrorInvalidValue;
+    if (!(frames && o.native)) o.bases = nullptr;
     size_t off[3], total;
-    measure_scratch_layout(B, capacity, W0, off, total);
-    long long* stats = (long long*)((char*)scratch + off[0]);
-    int* raw = (int*)((char*)scratch + off[1]);
-    int* env = (int*)((char*)scratch + off[2]);
-    const int* n_live = offsets + B;
-    const int wpr = native ? 2 * ((W0 + 63) / 64) : W / 32;
+    measure_scratch_layout(B, o.capacity, W0, off, total);
+    s.stats = (long long*)((char*)scratch + off[0]);
+    s.raw = (int*)((char*)scratch + off[1]);
+    s.env = (int*)((char*)scratch + off[2]);
+    if (o.capacity == 0) return hipSuccess;
+    const unsigned* masks = (const unsigned*)o.masks;
+    const int* n_live = o.offsets + B;
+    if (o.native && frames) {   // the ragged frame-size rows: H0, W0 and the words per row of the slot's own frame
+        hipLaunchKernelGGL((mask_stats_bits_kernel<2, false, true, true>), dim3(o.capacity), dim3(256), 0, st, masks, n_live,
+                           0, 0, 0, 0, s.stats, (int*)nullptr, o.offsets, frames, B, o.bases, o.capacity_bytes);
+    } else if (o.native) {      // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
+        const int wpr = native_words_per_row(W0);
+        hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(o.capacity), dim3(256), 0, st, masks, n_live, H0,
+                           32 * wpr, H0, 32 * wpr, s.stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
+    } else {
+        if ((W & 31) || (H & 31) || ((uintptr_t)masks & 15) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024) return hipErrorInvalidValue;
+        if (frames)
+            hipLaunchKernelGGL((mask_stats_bits_kernel<4, true, true>), dim3(o.capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                               masks, n_live, H, W, H0, W0, s.stats, s.raw, o.offsets, frames, B);
+        else
+            hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(o.capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
+                               masks, n_live, H, W, H0, W0, s.stats, s.raw, (const int*)nullptr,
+                               (const FrameRow*)nullptr, 0);
+    }
+    return hipGetLastError();
+}
+
+// The fields MeasureArgs and CheckerArgs have in common (everything but the one camera's row and CheckerArgs' ragged part).
+template <class Args>
+static void measure_fill(Args& a, const CameraChoice& cams, const OutputSet& o, const Canvas& cv, const FrameSizes& fs,
+                         const MeasureResult& r, const MeasureScratch& s) {
+    a.table = (const CameraRow*)cams.table; a.cam_of_frame = cams.cam_of_frame; a.n_cams = cams.n_cams;
+    a.stats = s.stats; a.raw = o.native ? nullptr : s.raw; a.envelope = s.env;
+    a.dets = o.dets; a.xyxy = o.xyxy; a.counts = o.counts; a.offsets = o.offsets;
+    a.max_det = o.max_det; a.row = 6 + cv.nm; a.capacity = o.capacity; a.H0 = fs.H0; a.W0 = fs.W0; a.frames = fs.rows;
+    a.frame_f64 = r.frame_f64; a.frame_i32 = r.frame_i32; a.stitch_f64 = r.stitch_f64; a.stitch_i32 = r.stitch_i32;
+}
+
+// p: the one camera (vti_measure), or nullptr with a device table of n_cams rows and the frames' indices (vti_measure_cameras).
+hipError_t launch_measure(const vti_measure_params* p, const CameraChoice& cams, OutputSet o, const Canvas& cv, const FrameSizes& fs,
+                          const MeasureResult& r, hipStream_t st) {
+    if (o.B == 0) return hipSuccess;
+    MeasureScratch s;
+    hipError_t e = measure_front(o, cv, fs, r.scratch, st, s);
+    if (e != hipSuccess) return e;
     MeasureArgs a;
     memset(&a, 0, sizeof a);
     if (p) measure_pack_camera(*p, &a.cam);
-    else { a.table = (const CameraRow*)table; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
+    measure_fill(a, p ? CameraChoice{} : cams, o, cv, fs, r, s);
     const EnvSel sel = {a.cam.fabric_id, a.cam.roi_enabled, {a.cam.roi[0], a.cam.roi[1], a.cam.roi[2], a.cam.roi[3]}};
-    if (capacity > 0) {
-        if (native && frames) { // the ragged frame-size rows: H0, W0 and the words per row of the slot's own frame
-            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false, true, true>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live,
-                               0, 0, 0, 0, stats, (int*)nullptr, offsets, frames, B, bases, capacity_bytes);
-        } else if (native) {    // frame-size rows: the identity branch (H0 = H, W0 = W = 32 * wpr; the pad bits are 0), no tables
-            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
-                               32 * wpr, H0, 32 * wpr, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
-        } else {
-            if ((W & 31) || (H & 31) || ((uintptr_t)masks & 15) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024) return hipErrorInvalidValue;
-            if (frames)
-                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
-                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, offsets, frames, B);
-            else
-                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
-                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, (const int*)nullptr,
-                                   (const FrameRow*)nullptr, 0);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (native)
-        hipLaunchKernelGGL(envelope_bits_kernel<true>, dim3((W0 + 63) / 64, B), dim3(256), 0, st, (const unsigned*)masks, offsets, dets,
-                           max_det, 6 + nm, capacity, sel, H0, W0, H0, W0, env, xyxy, wpr, a.table, a.cam_of_frame, a.n_cams,
-                           frames, bases, capacity_bytes);
+    const unsigned* masks = (const unsigned*)o.masks;
+    const dim3 egrid((fs.W0 + 63) / 64, o.B);
+    if (o.native)
+        hipLaunchKernelGGL(envelope_bits_kernel<true>, egrid, dim3(256), 0, st, masks, o.offsets, o.dets, o.max_det, a.row, o.capacity, sel,
+                           fs.H0, fs.W0, fs.H0, fs.W0, s.env, o.xyxy, native_words_per_row(fs.W0), a.table, a.cam_of_frame, a.n_cams,
+                           fs.rows, o.bases, o.capacity_bytes);
     else {
-        if ((size_t)H * 4 > 60 * 1024) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(envelope_bits_kernel<false>, dim3((W0 + 63) / 64, B), dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
-                           offsets, dets, max_det, 6 + nm, capacity, sel, H, W, H0, W0, env, xyxy, 0, a.table, a.cam_of_frame,
-                           a.n_cams, frames);
+        if ((size_t)cv.H * 4 > 60 * 1024) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(envelope_bits_kernel<false>, egrid, dim3(256), (size_t)cv.H * 4, st, masks, o.offsets, o.dets, o.max_det, a.row,
+                           o.capacity, sel, cv.H, cv.W, fs.H0, fs.W0, s.env, o.xyxy, 0, a.table, a.cam_of_frame, a.n_cams, fs.rows);
     }
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
-    a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
-    a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
-    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0; a.frames = frames;
-    a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
-    const size_t lds = (size_t)max_det * (6 * sizeof(double) + 4 * sizeof(int));
-    if (a.table) hipLaunchKernelGGL(measure_frames_kernel<true>, dim3(B), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(measure_frames_kernel<false>, dim3(B), dim3(256), lds, st, a);
+    const size_t lds = (size_t)o.max_det * (6 * sizeof(double) + 4 * sizeof(int));
+    if (a.table) hipLaunchKernelGGL(measure_frames_kernel<true>, dim3(o.B), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(measure_frames_kernel<false>, dim3(o.B), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
@@ -1128,77 +1145,45 @@ void checker_pack(const vti_checker_params& p, void* row) {
     memcpy(row, &c, sizeof c);
 }
 
-// p: the one camera (vti_measure_checker), or nullptr with a device table of n_cams rows and the frames' indices; frames, bases and
-// capacity_bytes as launch_measure takes them.  The one-struct, one-size call launches the instantiations without RIG / TABLE.
-hipError_t launch_measure_checker(const vti_checker_params* p, const void* table, int n_cams, const int* cam_of_frame,
-                                  const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
-                                  const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
-                                  const FrameRow* frames, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64,
-                                  int* stitch_i32, hipStream_t st, const long long* bases, long long capacity_bytes) {
-    if (B == 0) return hipSuccess;
-    if (!p && (!table || !cam_of_frame)) return hipErrorInvalidValue;
-    if (p && frames) return hipErrorInvalidValue;
-    if (frames && native && (!bases || capacity_bytes < 0)) return hipErrorInvalidValue;
-    if (!(frames && native)) bases = nullptr;
-    size_t off[3], total;
-    measure_scratch_layout(B, capacity, W0, off, total);
-    long long* stats = (long long*)((char*)scratch + off[0]);
-    int* raw = (int*)((char*)scratch + off[1]);
-    int* env = (int*)((char*)scratch + off[2]);
-    const int* n_live = offsets + B;
-    const int wpr = native ? 2 * ((W0 + 63) / 64) : W / 32;
+// p: the one camera (vti_measure_checker), or nullptr with a device table of n_cams rows and the frames' indices; the frame table
+// and the ragged rows as launch_measure takes them.  The one-struct, one-size call launches the instantiations without RIG / TABLE.
+hipError_t launch_measure_checker(const vti_checker_params* p, const CameraChoice& cams, OutputSet o, const Canvas& cv,
+                                  const FrameSizes& fs, const MeasureResult& r, hipStream_t st) {
+    if (o.B == 0) return hipSuccess;
+    if (!p && (!cams.table || !cams.cam_of_frame)) return hipErrorInvalidValue;
+    if (p && fs.rows) return hipErrorInvalidValue;
+    const int H = cv.H, W = cv.W, H0 = fs.H0, W0 = fs.W0;
+    if (!o.native && ((W & 31) || (H & 31) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024)) return hipErrorInvalidValue;
+    MeasureScratch s;
+    hipError_t e = measure_front(o, cv, fs, r.scratch, st, s);
+    if (e != hipSuccess) return e;
     CheckerArgs a;
     memset(&a, 0, sizeof a);
     if (p) checker_pack(*p, &a.cam);
-    else { a.table = (const CameraRow*)table; a.cam_of_frame = cam_of_frame; a.n_cams = n_cams; }
-    if (!native && ((W & 31) || (H & 31) || (size_t)(4 * W + 2 * H) * 4 > 60 * 1024)) return hipErrorInvalidValue;
-    if (capacity > 0) {
-        if (native && frames)   // the ragged frame-size rows, as vti_measure_frames_native
-            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false, true, true>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live,
-                               0, 0, 0, 0, stats, (int*)nullptr, offsets, frames, B, bases, capacity_bytes);
-        else if (native)        // frame-size rows: the identity branch, as vti_measure
-            hipLaunchKernelGGL((mask_stats_bits_kernel<2, false>), dim3(capacity), dim3(256), 0, st, (const unsigned*)masks, n_live, H0,
-                               32 * wpr, H0, 32 * wpr, stats, (int*)nullptr, (const int*)nullptr, (const FrameRow*)nullptr, 0);
-        else {
-            if ((uintptr_t)masks & 15) return hipErrorInvalidValue;
-            if (frames)
-                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
-                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, offsets, frames, B);
-            else
-                hipLaunchKernelGGL((mask_stats_bits_kernel<4, true>), dim3(capacity), dim3(256), (size_t)(4 * W + 2 * H) * 4, st,
-                                   (const unsigned*)masks, n_live, H, W, H0, W0, stats, raw, (const int*)nullptr,
-                                   (const FrameRow*)nullptr, 0);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    const dim3 egrid((W0 + 63) / 64, B);
-    if (native && p)
-        hipLaunchKernelGGL(upper_envelope_bits_kernel<true>, egrid, dim3(256), 0, st, (const unsigned*)masks, offsets,
-                           counts, dets, max_det, 6 + nm, capacity, a.cam.fabric_id, a.cam.drop_empty, H0, W0, H0, W0, stats,
-                           (const int*)nullptr, xyxy, wpr, env);
+    measure_fill(a, p ? CameraChoice{} : cams, o, cv, fs, r, s);
+    a.bases = o.bases; a.capacity_bytes = o.capacity_bytes;
+    const unsigned* masks = (const unsigned*)o.masks;
+    const int wpr = native_words_per_row(W0);
+    const dim3 egrid((W0 + 63) / 64, o.B);
+    if (o.native && p)
+        hipLaunchKernelGGL(upper_envelope_bits_kernel<true>, egrid, dim3(256), 0, st, masks, o.offsets, o.counts, o.dets, o.max_det, a.row,
+                           o.capacity, a.cam.fabric_id, a.cam.drop_empty, H0, W0, H0, W0, s.stats, (const int*)nullptr, o.xyxy, wpr, s.env);
     else if (p)
-        hipLaunchKernelGGL(upper_envelope_bits_kernel<false>, egrid, dim3(256), (size_t)H * 4, st, (const unsigned*)masks,
-                           offsets, counts, dets, max_det, 6 + nm, capacity, a.cam.fabric_id, a.cam.drop_empty, H, W, H0, W0, stats, raw,
-                           xyxy, 0, env);
-    else if (native)
-        hipLaunchKernelGGL((upper_envelope_bits_kernel<true, true>), egrid, dim3(256), 0, st, (const unsigned*)masks, offsets, counts, dets,
-                           max_det, 6 + nm, capacity, 0, 0, H0, W0, H0, W0, stats, (const int*)nullptr, xyxy, wpr, env, a.table,
-                           a.cam_of_frame, a.n_cams, frames, bases, capacity_bytes);
+        hipLaunchKernelGGL(upper_envelope_bits_kernel<false>, egrid, dim3(256), (size_t)H * 4, st, masks, o.offsets, o.counts, o.dets,
+                           o.max_det, a.row, o.capacity, a.cam.fabric_id, a.cam.drop_empty, H, W, H0, W0, s.stats, s.raw, o.xyxy, 0, s.env);
+    else if (o.native)
+        hipLaunchKernelGGL((upper_envelope_bits_kernel<true, true>), egrid, dim3(256), 0, st, masks, o.offsets, o.counts, o.dets,
+                           o.max_det, a.row, o.capacity, 0, 0, H0, W0, H0, W0, s.stats, (const int*)nullptr, o.xyxy, wpr, s.env, a.table,
+                           a.cam_of_frame, a.n_cams, fs.rows, o.bases, o.capacity_bytes);
     else
-        hipLaunchKernelGGL((upper_envelope_bits_kernel<false, true>), egrid, dim3(256), (size_t)H * 4, st, (const unsigned*)masks, offsets,
-                           counts, dets, max_det, 6 + nm, capacity, 0, 0, H, W, H0, W0, stats, raw, xyxy, 0, env, a.table,
-                           a.cam_of_frame, a.n_cams, frames, (const long long*)nullptr, 0ll);
-    hipError_t e = hipGetLastError();
+        hipLaunchKernelGGL((upper_envelope_bits_kernel<false, true>), egrid, dim3(256), (size_t)H * 4, st, masks, o.offsets, o.counts,
+                           o.dets, o.max_det, a.row, o.capacity, 0, 0, H, W, H0, W0, s.stats, s.raw, o.xyxy, 0, s.env, a.table,
+                           a.cam_of_frame, a.n_cams, fs.rows, (const long long*)nullptr, 0ll);
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
-    a.stats = stats; a.raw = native ? nullptr : raw; a.envelope = env;
-    a.dets = dets; a.xyxy = xyxy; a.counts = counts; a.offsets = offsets;
-    a.max_det = max_det; a.row = 6 + nm; a.capacity = capacity; a.H0 = H0; a.W0 = W0;
-    a.frames = frames; a.bases = bases; a.capacity_bytes = capacity_bytes;
-    a.frame_f64 = frame_f64; a.frame_i32 = frame_i32; a.stitch_f64 = stitch_f64; a.stitch_i32 = stitch_i32;
-    const size_t lds = (size_t)max_det * (5 * sizeof(double) + 4 * sizeof(int));
-    if (p) hipLaunchKernelGGL(checker_frames_kernel<false>, dim3(B), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(checker_frames_kernel<true>, dim3(B), dim3(256), lds, st, a);
+    const size_t lds = (size_t)o.max_det * (5 * sizeof(double) + 4 * sizeof(int));
+    if (p) hipLaunchKernelGGL(checker_frames_kernel<false>, dim3(o.B), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(checker_frames_kernel<true>, dim3(o.B), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

@@ -125,6 +125,12 @@ static const char* settings_error(const P& p) {
     return nullptr;
 }
 
+// The checks of one vti_measure_params (vti_measure's struct, every entry of vti_measure_pack_cameras): nullptr when it is valid.
+static const char* measure_params_error(const vti_measure_params& p) {
+    if (const char* e = settings_error(p)) return e;
+    return p.two_row_threshold_px == p.two_row_threshold_px ? nullptr : "NaN threshold";
+}
+
 extern "C" {
 
 int32_t vti_create(const vti_desc* desc, vti_ctx** out) {
@@ -1109,12 +1115,6 @@ int64_t vti_measure_scratch_bytes(const vti_ctx* c, int32_t B, int32_t capacity,
 }
 
 // ---- argument checks that several entry points make: each returns 0, or refuse()'s status with the message "<fn>: <what>" -----
-// The checks of one vti_measure_params (vti_measure's struct, every entry of vti_measure_pack_cameras): nullptr when it is valid.
-static const char* measure_params_error(const vti_measure_params* p) {
-    if (const char* e = settings_error(*p)) return e;
-    return p->two_row_threshold_px == p->two_row_threshold_px ? nullptr : "NaN threshold";
-}
-
 // Mask rows are read with 16-byte loads, native (frame-size) rows with 8-byte loads.
 static int32_t mask_align_check(const char* fn, vti_ctx* c, const uint8_t* masks, int32_t native) {
     if ((uintptr_t)masks & (native ? 7 : 15))
@@ -1130,171 +1130,162 @@ static int32_t scratch_check(const char* fn, vti_ctx* c, const void* scratch, si
     return VTI_OK;
 }
 
-// What vti_measure's family and vti_measure_checker check of the output set, the result rows and the scratch.  `limit`: the status
-// for a max_det or a letterbox size beyond what the kernels serve (include/vti.h: VTI_ERR_UNSUPPORTED in the measure family,
-// VTI_ERR_ARG in the checker).
-static int32_t measure_args_check(const char* fn, vti_ctx* c, int32_t limit, const uint8_t* masks, int32_t native, const float* dets,
-                                  const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det,
-                                  int32_t capacity, int32_t H0, int32_t W0, const void* scratch, size_t scratch_bytes,
-                                  const double* frame_f64, const int32_t* frame_i32) {
-    if (B < 0 || max_det < 1 || capacity < 0 || H0 < 1 || W0 < 1 || (native != 0 && native != 1))
+// What both measurement families check of the output set, the result rows and the scratch.  `limit`: the status for a max_det or a
+// letterbox size beyond what the kernels serve (include/vti.h: VTI_ERR_UNSUPPORTED in the measure family, VTI_ERR_ARG in the checker).
+static int32_t measure_args_check(const char* fn, vti_ctx* c, int32_t limit, const OutputSet& o, int32_t H0, int32_t W0,
+                                  const MeasureResult& r) {
+    if (o.B < 0 || o.max_det < 1 || o.capacity < 0 || H0 < 1 || W0 < 1 || (o.native != 0 && o.native != 1))
         return refuse(c, fn, "bad shape (B, capacity >= 0; max_det, H0, W0 >= 1; native 0 or 1)");
-    if (max_det > VTI_MEASURE_MAX_DET) return refuse(c, fn, "max_det above VTI_MEASURE_MAX_DET", limit);
-    if (B && (!dets || !xyxy || !counts || !offsets || !frame_f64 || !frame_i32 || (capacity && !masks))) return refuse(c, fn, "null pointer");
-    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
-    if (!native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
+    if (o.max_det > VTI_MEASURE_MAX_DET) return refuse(c, fn, "max_det above VTI_MEASURE_MAX_DET", limit);
+    if (o.B && (!o.dets || !o.xyxy || !o.counts || !o.offsets || !r.frame_f64 || !r.frame_i32 || (o.capacity && !o.masks)))
+        return refuse(c, fn, "null pointer");
+    VTI_TRY(mask_align_check(fn, c, o.capacity ? o.masks : nullptr, o.native));
+    if (!o.native && (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024)
         return refuse(c, fn, "letterbox size too large for the resize tables", limit);
-    if ((int64_t)B * W0 > INT32_MAX) return refuse(c, fn, "B * W0 out of range");
-    return scratch_check(fn, c, scratch, scratch_bytes, vti_measure_scratch_bytes(c, B, capacity, W0), "vti_measure_scratch_bytes()", B != 0);
+    if ((int64_t)o.B * W0 > INT32_MAX) return refuse(c, fn, "B * W0 out of range");
+    return scratch_check(fn, c, r.scratch, r.scratch_bytes, vti_measure_scratch_bytes(c, o.B, o.capacity, W0),
+                         "vti_measure_scratch_bytes()", o.B != 0);
 }
 
-// vti_measure / vti_measure_cameras / vti_measure_frames: exactly one of p and (table, cam_of_frame) is given; with `frames` (the rows
-// of a device frame table, already checked against its host copy) H0 and W0 are the table's largest ones.  `bases` (with frames and
-// native = 1 only, vti_measure_frames_native): the masks are vti_masks_native_frames' ragged rows.  Every check comes before the first HIP call.
-static int32_t measure_impl(const char* fn, vti_ctx* c, const vti_measure_params* p, const void* table, int32_t n_cams,
-                            const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
-                            const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity, int32_t H0,
-                            int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
-                            int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr, const int64_t* bases = nullptr,
-                            int64_t capacity_bytes = 0) {
-    if (frames && native == 1 && !bases) return refuse(c, fn, "native masks need frames of one size (vti_measure_cameras)", VTI_ERR_UNSUPPORTED);
-    if (bases && (capacity_bytes < 0 || ((uintptr_t)bases & 7))) return refuse(c, fn, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
+// The camera table and the per-frame camera index of the table forms.
+static int32_t camera_table_check(const char* fn, vti_ctx* c, const CameraChoice& cams) {
+    if (!c || !cams.table || !cams.cam_of_frame) return refuse(c, fn, "null ctx, camera table or camera index");
+    if (cams.n_cams < 1) return refuse(c, fn, "n_cams must be >= 1");
+    if (((uintptr_t)cams.table & 15) || ((uintptr_t)cams.cam_of_frame & 3))
+        return refuse(c, fn, "the camera table must be 16-byte aligned, the index 4-byte aligned");
+    return VTI_OK;
+}
+
+}  // extern "C": the code of the two measurement families is a template over what differs between them
+
+// ---- vti_measure* (process_frame's record) and vti_measure_checker* (the stitch-distance checker's): one implementation -------
+struct MeasureFamily {
+    using Params = vti_measure_params;
+    static constexpr auto error = measure_params_error;
+    static constexpr auto pack = measure_pack_camera;
+    static constexpr auto launch = launch_measure;
+    static constexpr int32_t limit = VTI_ERR_UNSUPPORTED;
+    static constexpr const char* one_size = "native masks need frames of one size (vti_measure_cameras)";
+    static constexpr const char* kernels = "measure kernels";
+};
+struct CheckerFamily {
+    using Params = vti_checker_params;
+    static constexpr auto error = settings_error<vti_checker_params>;
+    static constexpr auto pack = checker_pack;
+    static constexpr auto launch = launch_measure_checker;
+    static constexpr int32_t limit = VTI_ERR_ARG;
+    static constexpr const char* one_size = "native masks need frames of one size (vti_measure_checker_cameras)";
+    static constexpr const char* kernels = "measure_checker kernels";
+};
+
+// Exactly one of p and cams is given; with fs.rows (the rows of a device frame table, already checked against its host copy) fs.H0 and
+// fs.W0 are the table's largest ones.  o.bases (with fs.rows and native = 1 only, the *_frames_native calls): the masks are
+// vti_masks_native_frames' ragged rows.  Every check comes before the first HIP call.
+template <class F>
+static int32_t measure_impl(const char* fn, vti_ctx* c, const typename F::Params* p, const CameraChoice& cams, const OutputSet& o,
+                            const FrameSizes& fs, const MeasureResult& r, void* stream) {
+    if (fs.rows && o.native == 1 && !o.bases) return refuse(c, fn, F::one_size, VTI_ERR_UNSUPPORTED);
+    if (o.bases && (o.capacity_bytes < 0 || ((uintptr_t)o.bases & 7)))
+        return refuse(c, fn, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
     if (p)
-        if (const char* e = measure_params_error(p)) return refuse(c, fn, e);
-    VTI_TRY(measure_args_check(fn, c, VTI_ERR_UNSUPPORTED, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0,
-                               scratch, scratch_bytes, frame_f64, frame_i32));
-    if (B == 0) return VTI_OK;
+        if (const char* e = F::error(*p)) return refuse(c, fn, e);
+    VTI_TRY(measure_args_check(fn, c, F::limit, o, fs.H0, fs.W0, r));
+    if (o.B == 0) return VTI_OK;
     VTI_TRY(check_device(c, fn));
     const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_measure(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm, capacity, d.H,
-                              d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32, (hipStream_t)stream,
-                              (const long long*)bases, capacity_bytes), "measure kernels");
+    VTI_HIP(c, F::launch(p, cams, o, Canvas{d.nm, d.H, d.W}, fs, r, (hipStream_t)stream), F::kernels);
     return VTI_OK;
+}
+
+template <class F>
+static int32_t measure_one(const char* fn, vti_ctx* c, const typename F::Params* p, const OutputSet& o, int32_t H0, int32_t W0,
+                           const MeasureResult& r, void* stream) {
+    if (!c || !p) return refuse(c, fn, "null ctx or params");
+    return measure_impl<F>(fn, c, p, CameraChoice{}, o, FrameSizes{H0, W0, nullptr}, r, stream);
+}
+
+template <class F>
+static int32_t pack_cameras(const char* fn, vti_ctx* c, const typename F::Params* params, int32_t n_cams, void* host_table,
+                            size_t nbytes) {
+    if (!params || n_cams < 1 || !host_table) return refuse(c, fn, "null list or table, or n_cams < 1");
+    if ((int64_t)nbytes < vti_measure_cameras_bytes(n_cams)) return refuse(c, fn, "table smaller than vti_measure_cameras_bytes()");
+    for (int32_t k = 0; k < n_cams; ++k)
+        if (const char* e = F::error(params[k])) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "camera %d: %s", k, e);
+            return refuse(c, fn, msg);
+        }
+    for (int32_t k = 0; k < n_cams; ++k) F::pack(params[k], (char*)host_table + (size_t)k * measure_camera_row_bytes());
+    return VTI_OK;
+}
+
+template <class F>
+static int32_t measure_cameras(const char* fn, vti_ctx* c, const CameraChoice& cams, const OutputSet& o, int32_t H0, int32_t W0,
+                               const MeasureResult& r, void* stream) {
+    VTI_TRY(camera_table_check(fn, c, cams));
+    return measure_impl<F>(fn, c, nullptr, cams, o, FrameSizes{H0, W0, nullptr}, r, stream);
+}
+
+template <class F>
+static int32_t measure_frames(const char* fn, vti_ctx* c, const CameraChoice& cams, const OutputSet& o, const void* host_table,
+                              const void* dev_table, const MeasureResult& r, void* stream) {
+    VTI_TRY(camera_table_check(fn, c, cams));
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, o.B, h));
+    return measure_impl<F>(fn, c, nullptr, cams, o, FrameSizes{h.max_H0, h.max_W0, frame_rows(dev_table)}, r, stream);
+}
+
+template <class F>
+static int32_t measure_frames_native(const char* fn, vti_ctx* c, const CameraChoice& cams, const OutputSet& o, const void* host_table,
+                                     const void* dev_table, const MeasureResult& r, void* stream) {
+    VTI_TRY(camera_table_check(fn, c, cams));
+    FrameTableHeader h;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, o.B, h));
+    if (!o.bases) return refuse(c, fn, "null dev_mask_bases");
+    if (o.capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
+    if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
+        return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
+    return measure_impl<F>(fn, c, nullptr, cams, o, FrameSizes{h.max_H0, h.max_W0, frame_rows(dev_table)}, r, stream);
+}
+
+extern "C" {
+
+int64_t vti_measure_cameras_bytes(int32_t n_cams) {
+    return n_cams < 1 ? 0 : (int64_t)n_cams * (int64_t)measure_camera_row_bytes();
 }
 
 int32_t vti_measure(vti_ctx* c, const vti_measure_params* p, const uint8_t* masks, int32_t native, const float* dets,
                     const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity,
                     int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32,
                     double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    if (!c || !p) return refuse(c, "vti_measure", "null ctx or params");
-    return measure_impl("vti_measure", c, p, nullptr, 0, nullptr, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0,
-                        scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
-}
-
-// vti_measure_checker and its rig forms, as measure_impl serves vti_measure's: exactly one of p and (table, cam_of_frame) is given;
-// frames, bases and capacity_bytes as there.  Every check comes before the first HIP call.
-static int32_t checker_impl(const char* fn, vti_ctx* c, const vti_checker_params* p, const void* table, int32_t n_cams,
-                            const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
-                            const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det, int32_t capacity, int32_t H0,
-                            int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
-                            int32_t* stitch_i32, void* stream, const FrameRow* frames = nullptr, const int64_t* bases = nullptr,
-                            int64_t capacity_bytes = 0) {
-    if (frames && native == 1 && !bases)
-        return refuse(c, fn, "native masks need frames of one size (vti_measure_checker_cameras)", VTI_ERR_UNSUPPORTED);
-    if (bases && (capacity_bytes < 0 || ((uintptr_t)bases & 7))) return refuse(c, fn, "capacity_bytes must be >= 0, dev_mask_bases 8-byte aligned");
-    if (p)
-        if (const char* e = settings_error(*p)) return refuse(c, fn, e);
-    VTI_TRY(measure_args_check(fn, c, VTI_ERR_ARG, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0, scratch,
-                               scratch_bytes, frame_f64, frame_i32));
-    if (B == 0) return VTI_OK;
-    VTI_TRY(check_device(c, fn));
-    const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_measure_checker(p, table, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, d.nm,
-                                      capacity, d.H, d.W, H0, W0, frames, scratch, frame_f64, frame_i32, stitch_f64, stitch_i32,
-                                      (hipStream_t)stream, (const long long*)bases, capacity_bytes), "measure_checker kernels");
-    return VTI_OK;
+    return measure_one<MeasureFamily>("vti_measure", c, p, {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+                                      H0, W0, {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
 }
 
 int32_t vti_measure_checker(vti_ctx* c, const vti_checker_params* p, const uint8_t* masks, int32_t native, const float* dets,
                             const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B, int32_t max_det,
                             int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes, double* frame_f64,
                             int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    const char* fn = "vti_measure_checker";
-    if (!c || !p) return refuse(c, fn, "null ctx or params");
-    return checker_impl(fn, c, p, nullptr, 0, nullptr, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, H0, W0, scratch,
-                        scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
-}
-
-int64_t vti_measure_cameras_bytes(int32_t n_cams) {
-    return n_cams < 1 ? 0 : (int64_t)n_cams * (int64_t)measure_camera_row_bytes();
+    return measure_one<CheckerFamily>("vti_measure_checker", c, p,
+                                      {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0}, H0, W0,
+                                      {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
 }
 
 int32_t vti_measure_pack_cameras(vti_ctx* c, const vti_measure_params* params, int32_t n_cams, void* host_table, size_t nbytes) {
-    if (!params || n_cams < 1 || !host_table) return fail(c, VTI_ERR_ARG, "vti_measure_pack_cameras: null list or table, or n_cams < 1");
-    if ((int64_t)nbytes < vti_measure_cameras_bytes(n_cams))
-        return fail(c, VTI_ERR_ARG, "vti_measure_pack_cameras: table smaller than vti_measure_cameras_bytes()");
-    for (int32_t k = 0; k < n_cams; ++k)
-        if (const char* e = measure_params_error(params + k)) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "vti_measure_pack_cameras: camera %d: %s", k, e);
-            return fail(c, VTI_ERR_ARG, msg);
-        }
-    for (int32_t k = 0; k < n_cams; ++k) measure_pack_camera(params[k], (char*)host_table + (size_t)k * measure_camera_row_bytes());
-    return VTI_OK;
+    return pack_cameras<MeasureFamily>("vti_measure_pack_cameras", c, params, n_cams, host_table, nbytes);
 }
 
-// The camera table and the per-frame camera index of the vti_measure_* table forms.
-static int32_t camera_table_check(const char* fn, vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame) {
-    if (!c || !cameras || !cam_of_frame) return refuse(c, fn, "null ctx, camera table or camera index");
-    if (n_cams < 1) return refuse(c, fn, "n_cams must be >= 1");
-    if (((uintptr_t)cameras & 15) || ((uintptr_t)cam_of_frame & 3))
-        return refuse(c, fn, "the camera table must be 16-byte aligned, the index 4-byte aligned");
-    return VTI_OK;
+int32_t vti_checker_pack_cameras(vti_ctx* c, const vti_checker_params* params, int32_t n_cams, void* host_table, size_t nbytes) {
+    return pack_cameras<CheckerFamily>("vti_checker_pack_cameras", c, params, n_cams, host_table, nbytes);
 }
 
 int32_t vti_measure_cameras(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
                             int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t B,
                             int32_t max_det, int32_t capacity, int32_t H0, int32_t W0, void* scratch, size_t scratch_bytes,
                             double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    VTI_TRY(camera_table_check("vti_measure_cameras", c, cameras, n_cams, cam_of_frame));
-    return measure_impl("vti_measure_cameras", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
-                        max_det, capacity, H0, W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
-}
-
-int32_t vti_measure_frames(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
-                           int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
-                           const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity, void* scratch,
-                           size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
-                           void* stream) {
-    VTI_TRY(camera_table_check("vti_measure_frames", c, cameras, n_cams, cam_of_frame));
-    FrameTableHeader h;
-    VTI_TRY(frames_check("vti_measure_frames", c, host_table, dev_table, B, h));
-    return measure_impl("vti_measure_frames", c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B,
-                        max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
-                        frame_rows(dev_table));
-}
-
-int32_t vti_measure_frames_native(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
-                                  const int64_t* mask_bases, int64_t capacity_bytes, const float* dets, const float* xyxy,
-                                  const int32_t* counts, const int32_t* offsets, const void* host_table, const void* dev_table, int32_t B,
-                                  int32_t max_det, int32_t capacity, void* scratch, size_t scratch_bytes, double* frame_f64,
-                                  int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
-    const char* fn = "vti_measure_frames_native";
-    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
-    FrameTableHeader h;
-    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
-    if (!mask_bases) return refuse(c, fn, "null dev_mask_bases");
-    if (capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
-    if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
-        return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
-    return measure_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B,
-                        max_det, capacity, h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
-                        frame_rows(dev_table), mask_bases, capacity_bytes);
-}
-
-// ---- the stitch-distance checker on a rig: the camera table and the frame table forms of vti_measure_checker -------------------
-int32_t vti_checker_pack_cameras(vti_ctx* c, const vti_checker_params* params, int32_t n_cams, void* host_table, size_t nbytes) {
-    if (!params || n_cams < 1 || !host_table) return fail(c, VTI_ERR_ARG, "vti_checker_pack_cameras: null list or table, or n_cams < 1");
-    if ((int64_t)nbytes < vti_measure_cameras_bytes(n_cams))
-        return fail(c, VTI_ERR_ARG, "vti_checker_pack_cameras: table smaller than vti_measure_cameras_bytes()");
-    for (int32_t k = 0; k < n_cams; ++k)
-        if (const char* e = settings_error(params[k])) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "vti_checker_pack_cameras: camera %d: %s", k, e);
-            return fail(c, VTI_ERR_ARG, msg);
-        }
-    for (int32_t k = 0; k < n_cams; ++k) checker_pack(params[k], (char*)host_table + (size_t)k * measure_camera_row_bytes());
-    return VTI_OK;
+    return measure_cameras<MeasureFamily>("vti_measure_cameras", c, {cameras, n_cams, cam_of_frame},
+                                          {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0}, H0, W0,
+                                          {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
 }
 
 int32_t vti_measure_checker_cameras(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
@@ -1302,10 +1293,19 @@ int32_t vti_measure_checker_cameras(vti_ctx* c, const void* cameras, int32_t n_c
                                     int32_t B, int32_t max_det, int32_t capacity, int32_t H0, int32_t W0, void* scratch,
                                     size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
                                     void* stream) {
-    const char* fn = "vti_measure_checker_cameras";
-    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
-    return checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity,
-                        H0, W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream);
+    return measure_cameras<CheckerFamily>("vti_measure_checker_cameras", c, {cameras, n_cams, cam_of_frame},
+                                          {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0}, H0, W0,
+                                          {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
+}
+
+int32_t vti_measure_frames(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                           int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
+                           const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity, void* scratch,
+                           size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32,
+                           void* stream) {
+    return measure_frames<MeasureFamily>("vti_measure_frames", c, {cameras, n_cams, cam_of_frame},
+                                         {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0}, host_table,
+                                         dev_table, {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
 }
 
 int32_t vti_measure_checker_frames(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
@@ -1313,13 +1313,20 @@ int32_t vti_measure_checker_frames(vti_ctx* c, const void* cameras, int32_t n_ca
                                    const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t capacity,
                                    void* scratch, size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
                                    int32_t* stitch_i32, void* stream) {
-    const char* fn = "vti_measure_checker_frames";
-    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
-    FrameTableHeader h;
-    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
-    return checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, B, max_det, capacity,
-                        h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
-                        frame_rows(dev_table));
+    return measure_frames<CheckerFamily>("vti_measure_checker_frames", c, {cameras, n_cams, cam_of_frame},
+                                         {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0}, host_table,
+                                         dev_table, {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
+}
+
+int32_t vti_measure_frames_native(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                  const int64_t* mask_bases, int64_t capacity_bytes, const float* dets, const float* xyxy,
+                                  const int32_t* counts, const int32_t* offsets, const void* host_table, const void* dev_table, int32_t B,
+                                  int32_t max_det, int32_t capacity, void* scratch, size_t scratch_bytes, double* frame_f64,
+                                  int32_t* frame_i32, double* stitch_f64, int32_t* stitch_i32, void* stream) {
+    return measure_frames_native<MeasureFamily>(
+        "vti_measure_frames_native", c, {cameras, n_cams, cam_of_frame},
+        {masks, 1, dets, xyxy, counts, offsets, B, max_det, capacity, (const long long*)mask_bases, capacity_bytes}, host_table,
+        dev_table, {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
 }
 
 int32_t vti_measure_checker_frames_native(vti_ctx* c, const void* cameras, int32_t n_cams, const int32_t* cam_of_frame,
@@ -1328,17 +1335,10 @@ int32_t vti_measure_checker_frames_native(vti_ctx* c, const void* cameras, int32
                                           const void* dev_table, int32_t B, int32_t max_det, int32_t capacity, void* scratch,
                                           size_t scratch_bytes, double* frame_f64, int32_t* frame_i32, double* stitch_f64,
                                           int32_t* stitch_i32, void* stream) {
-    const char* fn = "vti_measure_checker_frames_native";
-    VTI_TRY(camera_table_check(fn, c, cameras, n_cams, cam_of_frame));
-    FrameTableHeader h;
-    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
-    if (!mask_bases) return refuse(c, fn, "null dev_mask_bases");
-    if (capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
-    if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
-        return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
-    return checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, masks, 1, dets, xyxy, counts, offsets, B, max_det, capacity,
-                        h.max_H0, h.max_W0, scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32, stream,
-                        frame_rows(dev_table), mask_bases, capacity_bytes);
+    return measure_frames_native<CheckerFamily>(
+        "vti_measure_checker_frames_native", c, {cameras, n_cams, cam_of_frame},
+        {masks, 1, dets, xyxy, counts, offsets, B, max_det, capacity, (const long long*)mask_bases, capacity_bytes}, host_table,
+        dev_table, {scratch, scratch_bytes, frame_f64, frame_i32, stitch_f64, stitch_i32}, stream);
 }
 
 static bool poly_sizes_ok(int32_t H, int32_t W, int32_t row_bytes) {
@@ -1470,75 +1470,116 @@ static int32_t meas_rows_check(const char* fn, vti_ctx* c, const int32_t* frame_
     return VTI_OK;
 }
 
+// One walk over the selection of a *_frames drawing call: every host_select[k] is a frame of the batch, at most 8192 x 8192 and of
+// the size of row k of the out table.  `s` receives the largest H0, W0 and pixel count, and from `in_lds(c, row, slot_words)`, the
+// call's layout of one selected frame, which tracers serve the selection and the words of its largest native mask slot.
+struct Selection { int32_t mh = 0, mw = 0; long long max_px = 0, max_slot_words = 1; bool any_lds = false, any_global = false; };
+static int32_t selection_walk(const char* fn, vti_ctx* c, const void* host_table, const void* host_out_table, const int32_t* host_select,
+                              int32_t n_sel, int32_t B, int32_t max_det, int32_t max_points, Selection& s,
+                              bool (*in_lds)(const vti_ctx*, const FrameRow&, long long& slot_words)) {
+    char msg[200];
+    for (int32_t k = 0; k < n_sel; ++k) {
+        VTI_TRY(select_at(fn, c, host_select, k, B));
+        const int32_t b = host_select[k];
+        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
+        if (ri.H0 > 8192 || ri.W0 > 8192) {
+            snprintf(msg, sizeof msg, "frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
+            return refuse(c, fn, msg);
+        }
+        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
+            snprintf(msg, sizeof msg, "row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k, ro.H0, ro.W0, k, b,
+                     ri.H0, ri.W0);
+            return refuse(c, fn, msg);
+        }
+        s.mh = std::max(s.mh, ri.H0); s.mw = std::max(s.mw, ri.W0);
+        s.max_px = std::max(s.max_px, (long long)ri.H0 * ri.W0);
+        long long slot_words = 1;
+        (in_lds(c, ri, slot_words) ? s.any_lds : s.any_global) = true;
+        s.max_slot_words = std::max(s.max_slot_words, slot_words);
+    }
+    if (!annotate_sizes_ok(n_sel, max_det, s.mh, s.mw, max_points)) return refuse(c, fn, "the selection is too large");
+    return VTI_OK;
+}
+
+// ---- vti_annotate (process_frame's picture) and vti_annotate_checker (the stitch-distance checker's) ---------------------------
+// The one-struct call of the checker passes p, every other form a camera table.  `checker`: the prep kernel is the checker's.
+struct AnnotateCall {
+    const char* fn; bool checker; const vti_checker_params* p; const uint8_t* frames;
+    // the *_frames forms: the host tables and what selection_walk() found (then H0, W0 below are s->mh, s->mw)
+    const void* host_table; const void* host_out_table; Selection* s;
+};
+
+// Every check of the drawing calls but those of the frame tables themselves, in the order each entry point has always made them, and
+// all before the first HIP call.  Uniform forms: H0, W0 are the call's; the *_frames forms set them from the selection.
+static int32_t annotate_check(const AnnotateCall& a, vti_ctx* c, int32_t& H0, int32_t& W0, const CameraChoice& cams, const OutputSet& o,
+                              const DrawInputs& d) {
+    const char* fn = a.fn;
+    const vti_desc& desc = c->plan.desc;
+    const bool bad_canvas = a.checker && !o.native && ((desc.W & 31) || (size_t)(4 * desc.W + 2 * desc.H) * 4 > 60 * 1024);
+    const char* unsuitable = "letterbox size unsuitable for the resize tables";
+    if (a.s) {
+        if (o.capacity < 0 || cams.n_cams < 1 || o.native != 0 || o.max_det < 1 || o.max_det > VTI_MEASURE_MAX_DET || d.max_points < 0)
+            return refuse(c, fn, "bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
+    } else if (o.B < 1 || o.capacity < 0 || (!a.p && cams.n_cams < 1) || (o.native != 0 && o.native != 1) ||
+               !annotate_sizes_ok(d.n_sel, o.max_det, H0, W0, d.max_points))
+        return refuse(c, fn, a.p ? "bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                                   "1 <= H0, W0 <= 8192; native 0 or 1)"
+                                 : "bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
+                                   "1 <= H0, W0 <= 8192; native 0 or 1)");
+    if (!a.frames || (!a.p && !cams.table) || !o.dets || !o.xyxy || !o.counts || !o.offsets || !d.frame_i32 || !d.stitch_f64 ||
+        !d.stitch_i32 || !d.host_select || !d.dev_select || !d.out || !d.status || (o.capacity && !o.masks))
+        return refuse(c, fn, "null pointer");
+    if (a.p)
+        if (const char* e = settings_error(*a.p)) return refuse(c, fn, e);
+    if (a.s) {
+        VTI_TRY(selection_walk(fn, c, a.host_table, a.host_out_table, d.host_select, d.n_sel, o.B, o.max_det, d.max_points, *a.s,
+                               [](const vti_ctx*, const FrameRow& r, long long&) {
+                                   AnnotateLayout one;                   // the frame's own bitmap: which tracer serves it
+                                   annotate_layout(1, 1, r.H0, r.W0, 0, one);
+                                   return one.in_lds;
+                               }));
+        H0 = a.s->mh; W0 = a.s->mw;
+        if (((uintptr_t)a.frames & 15) || ((uintptr_t)d.out & 15)) return refuse(c, fn, "dev_frames and dev_out must be 16-byte aligned");
+    } else
+        VTI_TRY(select_check(fn, c, d.host_select, d.n_sel, o.B));
+    if (a.p) {
+        if ((uintptr_t)d.dev_select & 3) return refuse(c, fn, "the selection must be 4-byte aligned");
+    } else if (((uintptr_t)cams.table & 15) || ((uintptr_t)cams.cam_of_frame & 3) || ((uintptr_t)d.dev_select & 3))
+        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
+    VTI_TRY(mask_align_check(fn, c, o.capacity ? o.masks : nullptr, o.native));
+    if (!a.s && bad_canvas) return refuse(c, fn, unsuitable);
+    VTI_TRY(meas_rows_check(fn, c, d.frame_i32, d.stitch_f64, d.stitch_i32, d.status));
+    VTI_TRY(scratch_check(fn, c, d.scratch, d.scratch_bytes, vti_annotate_scratch_bytes(c, d.n_sel, o.max_det, H0, W0, d.max_points),
+                          a.s ? "vti_annotate_frames_scratch_bytes()" : "vti_annotate_scratch_bytes()"));
+    if (a.s && bad_canvas) return refuse(c, fn, unsuitable);
+    return VTI_OK;
+}
+
+// The checks above, then the launches: launch_annotate or launch_annotate_checker.  fr: the device tables of the *_frames forms.
+static int32_t annotate_impl(const AnnotateCall& a, vti_ctx* c, int32_t H0, int32_t W0, const CameraChoice& cams, const OutputSet& o,
+                             const DrawInputs& d, void* stream, AnnotateFrames* fr = nullptr) {
+    VTI_TRY(annotate_check(a, c, H0, W0, cams, o, d));
+    VTI_TRY(check_device(c, a.fn));
+    const Canvas cv{c->plan.desc.nm, c->plan.desc.H, c->plan.desc.W};
+    if (fr) { fr->any_lds = a.s->any_lds; fr->any_global = a.s->any_global; fr->max_px = a.s->max_px; }
+    if (a.checker)
+        VTI_HIP(c, launch_annotate_checker(a.p, a.frames, H0, W0, cams, o, cv, d, (hipStream_t)stream, fr), "annotate_checker kernels");
+    else
+        VTI_HIP(c, launch_annotate(a.frames, H0, W0, cams, o, cv, d, (hipStream_t)stream, fr), "annotate kernels");
+    return VTI_OK;
+}
+
 int32_t vti_annotate(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const void* cameras, int32_t n_cams,
                      const int32_t* cam_of_frame, const uint8_t* masks, int32_t native, const float* dets, const float* xyxy,
                      const int32_t* counts, const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
                      const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
                      int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
                      void* stream) {
-    // every check comes before the first HIP call
-    const char* fn = "vti_annotate";
-    if (!c) return refuse(c, fn, "null ctx");
-    if (B < 1 || capacity < 0 || n_cams < 1 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-        return refuse(c, fn, "bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
-                             "1 <= H0, W0 <= 8192; native 0 or 1)");
-    if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
-        !dev_select || !out || !status || (capacity && !masks))
-        return refuse(c, fn, "null pointer");
-    VTI_TRY(select_check(fn, c, host_select, n_sel, B));
-    if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
-        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
-    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
-    VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
-    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points),
-                          "vti_annotate_scratch_bytes()"));
-    VTI_TRY(check_device(c, fn));
-    const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_annotate(frames, B, H0, W0, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det,
-                               d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
-                               scratch, (hipStream_t)stream), "annotate kernels");
-    return VTI_OK;
-}
-
-// ---- vti_annotate_checker: the stitch-distance checker's picture -------------------------------------------------------------
-// vti_annotate_checker (p) and vti_annotate_checker_cameras (the checker's camera table): every check comes before the first HIP
-// call: vti_annotate's, and vti_measure_checker's of the params
-static int32_t annotate_checker_impl(const char* fn, vti_ctx* c, const vti_checker_params* p, const void* cameras, int32_t n_cams,
-                                     const int32_t* cam_of_frame, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0,
-                                     const uint8_t* masks, int32_t native, const float* dets, const float* xyxy, const int32_t* counts,
-                                     const int32_t* offsets, int32_t max_det, int32_t capacity, const int32_t* frame_i32,
-                                     const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select,
-                                     const int32_t* dev_select, int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status,
-                                     void* scratch, size_t scratch_bytes, void* stream) {
-    if (p) {
-        if (B < 1 || capacity < 0 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-            return refuse(c, fn, "bad size (B, n_sel >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
-                                 "1 <= H0, W0 <= 8192; native 0 or 1)");
-    } else if (B < 1 || capacity < 0 || n_cams < 1 || (native != 0 && native != 1) || !annotate_sizes_ok(n_sel, max_det, H0, W0, max_points))
-        return refuse(c, fn, "bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
-                             "1 <= H0, W0 <= 8192; native 0 or 1)");
-    if (!frames || (!p && !cameras) || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
-        !dev_select || !out || !status || (capacity && !masks))
-        return refuse(c, fn, "null pointer");
-    if (p)
-        if (const char* e = settings_error(*p)) return refuse(c, fn, e);
-    VTI_TRY(select_check(fn, c, host_select, n_sel, B));
-    if (p) {
-        if ((uintptr_t)dev_select & 3) return refuse(c, fn, "the selection must be 4-byte aligned");
-    } else if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
-        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
-    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, native));
-    if (!native && ((c->plan.desc.W & 31) || (size_t)(4 * c->plan.desc.W + 2 * c->plan.desc.H) * 4 > 60 * 1024))
-        return refuse(c, fn, "letterbox size unsuitable for the resize tables");
-    VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
-    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, H0, W0, max_points),
-                          "vti_annotate_scratch_bytes()"));
-    VTI_TRY(check_device(c, fn));
-    const vti_desc& d = c->plan.desc;
-    VTI_HIP(c, launch_annotate_checker(p, cameras, n_cams, cam_of_frame, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets,
-                                       max_det, d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel,
-                                       max_points, out, status, scratch, (hipStream_t)stream), "annotate_checker kernels");
-    return VTI_OK;
+    if (!c) return refuse(c, "vti_annotate", "null ctx");
+    return annotate_impl({"vti_annotate", false, nullptr, frames}, c, H0, W0, {cameras, n_cams, cam_of_frame},
+                         {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+                         {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes},
+                         stream);
 }
 
 int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const vti_checker_params* p,
@@ -1547,11 +1588,11 @@ int32_t vti_annotate_checker(vti_ctx* c, const uint8_t* frames, int32_t B, int32
                              const double* stitch_f64, const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select,
                              int32_t n_sel, int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
                              void* stream) {
-    const char* fn = "vti_annotate_checker";
-    if (!c || !p) return refuse(c, fn, "null ctx or params");
-    return annotate_checker_impl(fn, c, p, nullptr, 0, nullptr, frames, B, H0, W0, masks, native, dets, xyxy, counts, offsets, max_det,
-                                 capacity, frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status,
-                                 scratch, scratch_bytes, stream);
+    if (!c || !p) return refuse(c, "vti_annotate_checker", "null ctx or params");
+    return annotate_impl({"vti_annotate_checker", true, p, frames}, c, H0, W0, {},
+                         {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+                         {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes},
+                         stream);
 }
 
 int32_t vti_annotate_checker_cameras(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, const void* cameras,
@@ -1561,11 +1602,11 @@ int32_t vti_annotate_checker_cameras(vti_ctx* c, const uint8_t* frames, int32_t 
                                      const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select, int32_t n_sel,
                                      int32_t max_points, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes,
                                      void* stream) {
-    const char* fn = "vti_annotate_checker_cameras";
-    if (!c) return refuse(c, fn, "null ctx");
-    return annotate_checker_impl(fn, c, nullptr, cameras, n_cams, cam_of_frame, frames, B, H0, W0, masks, native, dets, xyxy, counts,
-                                 offsets, max_det, capacity, frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel,
-                                 max_points, out, status, scratch, scratch_bytes, stream);
+    if (!c) return refuse(c, "vti_annotate_checker_cameras", "null ctx");
+    return annotate_impl({"vti_annotate_checker_cameras", true, nullptr, frames}, c, H0, W0, {cameras, n_cams, cam_of_frame},
+                         {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+                         {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes},
+                         stream);
 }
 
 // ---- vti_overlay: the model-check viewer's picture ---------------------------------------------------------------------------
@@ -1648,89 +1689,23 @@ int64_t vti_overlay_frames_scratch_bytes(const vti_ctx* c, const void* host_out_
     return n ? vti_overlay_scratch_bytes(c, n, max_det, mh, mw, max_points) : 0;
 }
 
-// One walk over the selection of a *_frames drawing call: every host_select[k] is a frame of the batch, at most 8192 x 8192 and of
-// the size of row k of the out table.  `s` receives the largest H0, W0 and pixel count, and from `in_lds(c, row, slot_words)`, the
-// call's layout of one selected frame, which tracers serve the selection and the words of its largest native mask slot.
-struct Selection { int32_t mh = 0, mw = 0; long long max_px = 0, max_slot_words = 1; bool any_lds = false, any_global = false; };
-static int32_t selection_walk(const char* fn, vti_ctx* c, const void* host_table, const void* host_out_table, const int32_t* host_select,
-                              int32_t n_sel, int32_t B, int32_t max_det, int32_t max_points, Selection& s,
-                              bool (*in_lds)(const vti_ctx*, const FrameRow&, long long& slot_words)) {
-    char msg[200];
-    for (int32_t k = 0; k < n_sel; ++k) {
-        VTI_TRY(select_at(fn, c, host_select, k, B));
-        const int32_t b = host_select[k];
-        const FrameRow ri = table_row(host_table, b), ro = table_row(host_out_table, k);
-        if (ri.H0 > 8192 || ri.W0 > 8192) {
-            snprintf(msg, sizeof msg, "frame %d (host_select[%d]) is %d x %d: H0, W0 must be <= 8192", b, k, ri.H0, ri.W0);
-            return refuse(c, fn, msg);
-        }
-        if (ro.H0 != ri.H0 || ro.W0 != ri.W0) {
-            snprintf(msg, sizeof msg, "row %d of the out table is %d x %d, frame host_select[%d] = %d is %d x %d", k, ro.H0, ro.W0, k, b,
-                     ri.H0, ri.W0);
-            return refuse(c, fn, msg);
-        }
-        s.mh = std::max(s.mh, ri.H0); s.mw = std::max(s.mw, ri.W0);
-        s.max_px = std::max(s.max_px, (long long)ri.H0 * ri.W0);
-        long long slot_words = 1;
-        (in_lds(c, ri, slot_words) ? s.any_lds : s.any_global) = true;
-        s.max_slot_words = std::max(s.max_slot_words, slot_words);
-    }
-    if (!annotate_sizes_ok(n_sel, max_det, s.mh, s.mw, max_points)) return refuse(c, fn, "the selection is too large");
-    return VTI_OK;
-}
-
-// vti_annotate_frames and vti_annotate_checker_frames (checker: the table is the checker's, the prep kernel the checker's own)
+// vti_annotate_frames and vti_annotate_checker_frames (checker: the table is the checker's, the prep kernel the checker's own): the
+// two frame tables, then annotate_impl's checks and launches
 static int32_t annotate_frames_impl(const char* fn, const char* out_fn, const char* one_size, bool checker, vti_ctx* c,
-                            const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
-                            const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
-                            const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
-                            int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
-                            const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
-                            const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
-                            size_t scratch_bytes, void* stream) {
+                                    const uint8_t* frames, const void* host_table, const void* dev_table, const void* host_out_table,
+                                    const void* dev_out_table, const CameraChoice& cams, const OutputSet& o, const DrawInputs& d,
+                                    void* stream) {
     // every check comes before the first HIP call
     if (!c) return refuse(c, fn, "null ctx");
     FrameTableHeader h;
-    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
-    if (n_sel < 1) return refuse(c, fn, "n_sel must be >= 1");
-    VTI_TRY(frames_check(out_fn, c, host_out_table, dev_out_table, n_sel, h));
-    if (native == 1) return refuse(c, fn, one_size, VTI_ERR_UNSUPPORTED);
-    if (capacity < 0 || n_cams < 1 || native != 0 || max_det < 1 || max_det > VTI_MEASURE_MAX_DET || max_points < 0)
-        return refuse(c, fn, "bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
-    if (!frames || !cameras || !dets || !xyxy || !counts || !offsets || !frame_i32 || !stitch_f64 || !stitch_i32 || !host_select ||
-        !dev_select || !out || !status || (capacity && !masks))
-        return refuse(c, fn, "null pointer");
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, o.B, h));
+    if (d.n_sel < 1) return refuse(c, fn, "n_sel must be >= 1");
+    VTI_TRY(frames_check(out_fn, c, host_out_table, dev_out_table, d.n_sel, h));
+    if (o.native == 1) return refuse(c, fn, one_size, VTI_ERR_UNSUPPORTED);
     Selection s;
-    VTI_TRY(selection_walk(fn, c, host_table, host_out_table, host_select, n_sel, B, max_det, max_points, s,
-                           [](const vti_ctx*, const FrameRow& r, long long&) {
-                               AnnotateLayout one;                   // the frame's own bitmap: which tracer serves it
-                               annotate_layout(1, 1, r.H0, r.W0, 0, one);
-                               return one.in_lds;
-                           }));
-    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 15)) return refuse(c, fn, "dev_frames and dev_out must be 16-byte aligned");
-    if (((uintptr_t)cameras & 15) || (cam_of_frame && ((uintptr_t)cam_of_frame & 3)) || ((uintptr_t)dev_select & 3))
-        return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
-    VTI_TRY(mask_align_check(fn, c, capacity ? masks : nullptr, 0));
-    VTI_TRY(meas_rows_check(fn, c, frame_i32, stitch_f64, stitch_i32, status));
-    VTI_TRY(scratch_check(fn, c, scratch, scratch_bytes, vti_annotate_scratch_bytes(c, n_sel, max_det, s.mh, s.mw, max_points),
-                          "vti_annotate_frames_scratch_bytes()"));
-    const vti_desc& d = c->plan.desc;
-    if (checker && ((d.W & 31) || (size_t)(4 * d.W + 2 * d.H) * 4 > 60 * 1024))
-        return refuse(c, fn, "letterbox size unsuitable for the resize tables");
-    VTI_TRY(check_device(c, fn));
-    const AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), s.any_lds, s.any_global, s.max_px};
-    if (checker) {
-        VTI_HIP(c, launch_annotate_checker(nullptr, cameras, n_cams, cam_of_frame, frames, B, s.mh, s.mw, masks, 0, dets, xyxy, counts,
-                                           offsets, max_det, d.nm, capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select,
-                                           n_sel, max_points, out, status, scratch, (hipStream_t)stream, &fr), "annotate_checker kernels");
-        return VTI_OK;
-    }
-    VTI_HIP(c, launch_annotate(frames, B, s.mh, s.mw, cameras, n_cams, cam_of_frame, masks, 0, dets, xyxy, counts, offsets, max_det, d.nm,
-                               capacity, d.H, d.W, frame_i32, stitch_f64, stitch_i32, dev_select, n_sel, max_points, out, status,
-                               scratch, (hipStream_t)stream, &fr), "annotate kernels");
-    return VTI_OK;
+    AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), false, false, 0};
+    return annotate_impl({fn, checker, nullptr, frames, host_table, host_out_table, &s}, c, 0, 0, cams, o, d, stream, &fr);
 }
-
 
 int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
                             const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
@@ -1739,24 +1714,25 @@ int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_
                             const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
                             const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
                             size_t scratch_bytes, void* stream) {
-    return annotate_frames_impl("vti_annotate_frames", "vti_annotate_frames (out table)", "native masks need frames of one size (vti_annotate)", false,
-                               c, frames, host_table, dev_table, B, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det, capacity, frame_i32,
-                               stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, host_out_table, dev_out_table, out, status, scratch,
-                               scratch_bytes, stream);
+    return annotate_frames_impl(
+        "vti_annotate_frames", "vti_annotate_frames (out table)", "native masks need frames of one size (vti_annotate)", false, c, frames,
+        host_table, dev_table, host_out_table, dev_out_table, {cameras, n_cams, cam_of_frame},
+        {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+        {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes}, stream);
 }
 
 int32_t vti_annotate_checker_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
-                            const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks, int32_t native,
-                            const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets, int32_t max_det,
-                            int32_t capacity, const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
-                            const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
-                            const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
-                            size_t scratch_bytes, void* stream) {
-    return annotate_frames_impl("vti_annotate_checker_frames", "vti_annotate_checker_frames (out table)",
-                               "native masks need frames of one size (vti_annotate_checker_cameras)", true,
-                               c, frames, host_table, dev_table, B, cameras, n_cams, cam_of_frame, masks, native, dets, xyxy, counts, offsets, max_det, capacity, frame_i32,
-                               stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, host_out_table, dev_out_table, out, status, scratch,
-                               scratch_bytes, stream);
+                                    const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                    int32_t native, const float* dets, const float* xyxy, const int32_t* counts, const int32_t* offsets,
+                                    int32_t max_det, int32_t capacity, const int32_t* frame_i32, const double* stitch_f64,
+                                    const int32_t* stitch_i32, const int32_t* host_select, const int32_t* dev_select, int32_t n_sel,
+                                    int32_t max_points, const void* host_out_table, const void* dev_out_table, uint8_t* out,
+                                    int32_t* status, void* scratch, size_t scratch_bytes, void* stream) {
+    return annotate_frames_impl(
+        "vti_annotate_checker_frames", "vti_annotate_checker_frames (out table)",
+        "native masks need frames of one size (vti_annotate_checker_cameras)", true, c, frames, host_table, dev_table, host_out_table,
+        dev_out_table, {cameras, n_cams, cam_of_frame}, {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+        {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes}, stream);
 }
 
 int32_t vti_overlay_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,

@@ -374,24 +374,40 @@ void measure_scratch_layout(int B, int capacity, int W0, size_t off[3], size_t& 
 // a camera-table row (vti_measure_pack_cameras): its size and the packing of one validated struct (host)
 size_t measure_camera_row_bytes();
 void measure_pack_camera(const vti_measure_params& p, void* row);
-// p != nullptr: one camera for every frame; else frame b uses row cam_of_frame[b] of the device table (n_cams rows)
-// frames != nullptr: frame b is H0 x W0 of row b of the device frame table, and the W0 passed here is the largest one (the pitch of
-// the envelope rows in the scratch); with native = 1 the masks are then the ragged rows of vti_masks_native_frames: `bases` (i64
-// [B + 1]) and capacity_bytes are required, and a slot that ends past capacity_bytes is an empty mask
-hipError_t launch_measure(const vti_measure_params* p, const void* table, int n_cams, const int* cam_of_frame, const uint8_t* masks,
-                          int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int B, int max_det,
-                          int nm, int capacity, int H, int W, int H0, int W0, const FrameRow* frames, void* scratch, double* frame_f64,
-                          int* frame_i32, double* stitch_f64, int* stitch_i32, hipStream_t st, const long long* bases = nullptr,
-                          long long capacity_bytes = 0);
+
+// ---- what the measure, checker and annotate entry points hand down: each fills these once (host only, never kernel parameters) ----
+// The output set of a predict call.  bases != nullptr: the masks are the ragged rows of vti_masks_native_frames (i64 [B + 1], with a
+// frame table and native = 1 only), and a slot that ends past capacity_bytes is an empty mask.
+struct OutputSet {
+    const uint8_t* masks; int native; const float* dets; const float* xyxy; const int* counts; const int* offsets;
+    int B, max_det, capacity;
+    const long long* bases; long long capacity_bytes;
+};
+// Which camera serves frame b: row cam_of_frame[b] (nullptr: row 0) of a packed device table of n_cams rows.  All zero: the one
+// settings struct of the call serves every frame.
+struct CameraChoice { const void* table; int n_cams; const int* cam_of_frame; };
+struct Canvas { int nm, H, W; };                // of the ctx: mask coefficients per detection, the letterbox size
+// Every frame H0 x W0; or with rows (of a device frame table, already checked against its host copy) frame b has row b's size and
+// H0, W0 are the largest ones (the pitches of the scratch)
+struct FrameSizes { int H0, W0; const FrameRow* rows; };
+// A measurement: the caller's scratch (measure_scratch_layout) and the four output rows
+struct MeasureResult { void* scratch; size_t scratch_bytes; double* frame_f64; int* frame_i32; double* stitch_f64; int* stitch_i32; };
+// What a drawing call takes beside the output set: the measurement's rows, the selection (host_select checked, dev_select its device
+// copy), the pictures and their status, the scratch (annotate_layout)
+struct DrawInputs {
+    const int* frame_i32; const double* stitch_f64; const int* stitch_i32;
+    const int* host_select; const int* dev_select; int n_sel, max_points;
+    uint8_t* out; int* status; void* scratch; size_t scratch_bytes;
+};
+
+// p != nullptr: one camera for every frame; else cams.  fs.rows != nullptr: fs.W0 is also the pitch of the envelope rows in the scratch
+hipError_t launch_measure(const vti_measure_params* p, const CameraChoice& cams, OutputSet o, const Canvas& cv, const FrameSizes& fs,
+                          const MeasureResult& r, hipStream_t st);
 
 // vti_measure_checker (Utils/check_stitch_distance.py) and its rig forms: vti_measure's inputs, scratch layout and outputs.
-// p != nullptr: one camera and one frame size; else table, n_cams, cam_of_frame, frames, bases and capacity_bytes as launch_measure
-// takes them (the table's rows are checker_pack's)
-hipError_t launch_measure_checker(const vti_checker_params* p, const void* table, int n_cams, const int* cam_of_frame,
-                                  const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
-                                  const int* offsets, int B, int max_det, int nm, int capacity, int H, int W, int H0, int W0,
-                                  const FrameRow* frames, void* scratch, double* frame_f64, int* frame_i32, double* stitch_f64,
-                                  int* stitch_i32, hipStream_t st, const long long* bases = nullptr, long long capacity_bytes = 0);
+// p != nullptr: one camera and one frame size; else the arguments as launch_measure takes them (the table's rows are checker_pack's)
+hipError_t launch_measure_checker(const vti_checker_params* p, const CameraChoice& cams, OutputSet o, const Canvas& cv,
+                                  const FrameSizes& fs, const MeasureResult& r, hipStream_t st);
 // one validated vti_checker_params -> the CameraRow (measure_dev.h) the checker's kernels take by value (host)
 void checker_pack(const vti_checker_params& p, void* row);
 
@@ -433,21 +449,15 @@ void annotate_layout(int n_sel, int max_det, int H0, int W0, int max_points, Ann
 // largest selected ones (the pitches of the scratch), native is 0.  any_lds / any_global: a selected frame's union fits / does not fit
 // the tracer's LDS image (which outline instantiations are launched); max_px: the most pixels a selected frame has (the raster grid).
 struct AnnotateFrames { const FrameRow* rows_in; const FrameRow* rows_out; bool any_lds, any_global; long long max_px; };
-// cameras: a packed camera table in device memory; select: the device copy of the (host-checked) selection; native = 1: H, W unused
-hipError_t launch_annotate(const uint8_t* frames, int B, int H0, int W0, const void* cameras, int n_cams, const int* cam_of_frame,
-                           const uint8_t* masks, int native, const float* dets, const float* xyxy, const int* counts,
-                           const int* offsets, int max_det, int nm, int capacity, int H, int W, const int* frame_i32,
-                           const double* stitch_f64, const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out,
-                           int* status, void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
+// frames: u8 [B, H0, W0, 3], or with fr the flat buffer of its rows_in; cams: a packed camera table in device memory
+hipError_t launch_annotate(const uint8_t* frames, int H0, int W0, const CameraChoice& cams, const OutputSet& o, const Canvas& cv,
+                           const DrawInputs& d, hipStream_t st, const AnnotateFrames* fr = nullptr);
 // vti_annotate_checker (the stitch-distance checker's picture): the same scratch and the same outline and raster kernels behind a
-// prep kernel of its own; the rows are vti_measure_checker's.  p != nullptr: the settings travel by value; else they are row
-// cam_of_frame[b] (nullptr: row 0) of the checker's camera table in device memory, and fr is launch_annotate's
-hipError_t launch_annotate_checker(const vti_checker_params* p, const void* cameras, int n_cams, const int* cam_of_frame,
-                                   const uint8_t* frames, int B, int H0, int W0, const uint8_t* masks,
-                                   int native, const float* dets, const float* xyxy, const int* counts, const int* offsets, int max_det,
-                                   int nm, int capacity, int H, int W, const int* frame_i32, const double* stitch_f64,
-                                   const int* stitch_i32, const int* select, int n_sel, int max_points, uint8_t* out, int* status,
-                                   void* scratch, hipStream_t st, const AnnotateFrames* fr = nullptr);
+// prep kernel of its own; the rows are vti_measure_checker's.  p != nullptr: the settings travel by value; else they are cams' row of
+// the checker's camera table in device memory, and fr is launch_annotate's
+hipError_t launch_annotate_checker(const vti_checker_params* p, const uint8_t* frames, int H0, int W0, const CameraChoice& cams,
+                                   const OutputSet& o, const Canvas& cv, const DrawInputs& d, hipStream_t st,
+                                   const AnnotateFrames* fr = nullptr);
 
 // stamp.hip: vti_stamp / vti_stamp_frames (the text of the annotated pictures as 1-bit stamps).  The stamp table, host and device
 // copy alike: the header | n_pictures picture rows | n_stamps records.  Picture k owns the records [begin, end); the ranges follow each

@@ -79,6 +79,27 @@ def _camera_index(who, cameras, B, n_cams, dev, same_device=True):
     return torch.from_numpy(host.astype(np.int32)).to(dev)
 
 
+@dataclasses.dataclass(frozen=True)
+class _Family:
+    """What differs between process_frame's calls (measure, annotate) and the stitch-distance checker's (measure_checker,
+    annotate_checker): the settings struct, the pack call and the entry points of libvti.so."""
+    ctype: type             # the ctypes settings struct
+    params: str             # the name of its dataclass, for messages
+    pack: str               # the Engine method that packs a camera table, and the call behind it
+    pack_fn: str
+    measure_method: str
+    measure: tuple          # one settings struct, a camera table, a frame table, a frame table with ragged native rows
+    annotate: tuple         # one settings struct (None: no such call), a camera table, a frame table
+
+
+_PROCESS_FRAME = _Family(VtiMeasureParams, "MeasureParams", "pack_cameras", "vti_measure_pack_cameras", "measure",
+                         ("vti_measure", "vti_measure_cameras", "vti_measure_frames", "vti_measure_frames_native"),
+                         (None, "vti_annotate", "vti_annotate_frames"))
+_CHECKER = _Family(VtiCheckerParams, "CheckerParams", "pack_checker_cameras", "vti_checker_pack_cameras", "measure_checker",
+                   ("vti_measure_checker", "vti_measure_checker_cameras", "vti_measure_checker_frames", "vti_measure_checker_frames_native"),
+                   ("vti_annotate_checker", "vti_annotate_checker_cameras", "vti_annotate_checker_frames"))
+
+
 class FrameTable:
     """A packed frame table (vti_pack_frames) for a batch whose frames differ in size: `host` (the packed bytes, a CPU u8 tensor)
     and `dev` (their device copy), `shapes` [(H0, W0)] per frame, the frames' `byte_offsets` in the flat frame buffer and its
@@ -639,22 +660,34 @@ class Engine:
         """The camera table of vti_measure_cameras: one row per measure.MeasureParams (or VtiMeasureParams) of `params_list`, validated
         and packed by vti_measure_pack_cameras (a VtiError names the failing index) and uploaded once.  -> u8 device tensor to pass as
         measure(..., params=table, cameras=...); row k is camera k."""
+        return self._pack_cameras(_PROCESS_FRAME, params_list, device)
+
+    def pack_checker_cameras(self, params_list, device=None):
+        """The camera table of the checker's rig calls: one row per measure.CheckerParams (or VtiCheckerParams) of `params_list`,
+        validated and packed by vti_checker_pack_cameras (a VtiError names the failing index) and uploaded once.  -> u8 device tensor
+        to pass as measure_checker(..., params=table, cameras=...) and annotate_checker(...); row k is camera k.  Its rows are not
+        pack_cameras()' rows."""
+        return self._pack_cameras(_CHECKER, params_list, device)
+
+    def _pack_cameras(self, fam, params_list, device):
         cps = [p.to_c() if hasattr(p, "to_c") else p for p in params_list]
         n = len(cps)
         if n < 1:
-            raise ValueError("pack_cameras: at least one camera")
-        arr = (VtiMeasureParams * n)(*cps)
+            raise ValueError(f"{fam.pack}: at least one camera")
+        arr = (fam.ctype * n)(*cps)
         nbytes = int(lib().vti_measure_cameras_bytes(n))
         host = torch.empty(nbytes, dtype=torch.uint8)
-        check(self._ctx, lib().vti_measure_pack_cameras(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
+        check(self._ctx, getattr(lib(), fam.pack_fn)(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
         return host.to(device or self.device or "cuda")
 
-    def _camera_table(self, who, what, params_or_table, dev):
-        """A list of MeasureParams or the table of pack_cameras() -> (table, n_cams); `what` names the argument in the refusal."""
-        table = params_or_table if isinstance(params_or_table, torch.Tensor) else self.pack_cameras(params_or_table, dev)
+    def _camera_table(self, fam, who, params, dev):
+        """One settings object of the family, a list of them or the table of its pack call -> (table, n_cams)."""
+        if not isinstance(params, (list, tuple, torch.Tensor)):
+            params = [params]
+        table = params if isinstance(params, torch.Tensor) else self._pack_cameras(fam, params, dev)
         row = int(lib().vti_measure_cameras_bytes(1))
         if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
-            raise ValueError(f"{who}: {what} of pack_cameras() on the outputs' device")
+            raise ValueError(f"{who}: params must be {fam.params} or the u8 table of {fam.pack}() on the outputs' device")
         return table, table.numel() // row
 
     def _scratch(self, attr, need, dev):
@@ -680,74 +713,7 @@ class Engine:
         bit masks, or with native=True the ragged frame-size rows of a set from alloc_outputs(native_frames=) that
         predict_frames_into(native=True) filled (vti_measure_frames_native; native=True with any other set is a ValueError).
         Without `cameras` the one `params` serves every frame."""
-        dets, masks = out["dets"], out["masks"]
-        B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
-        dev = dets.device
-        ragged = frames is not None and native and "mask_bases" in out
-        if frames is not None:
-            self._check_frames(frames, B=B)
-            if native and not ragged:
-                raise ValueError("measure: frames of differing sizes have letterbox masks only (native=True needs one frame size, "
-                                 "or the ragged set of alloc_outputs(native_frames=))")
-            if ragged:
-                self._check_ragged(out, frames, max_det, "measure")
-                if not (dets.is_cuda and masks.is_cuda and out["mask_bases"].is_cuda):
-                    raise ValueError("measure: the output set must be in device memory")
-                capacity = B * max_det
-            if H0 is not None or W0 is not None:
-                raise ValueError("measure: give H0, W0 or frames, not both")
-            H0, W0 = frames.max_H0, frames.max_W0
-            if cameras is None:
-                params, cameras = (params if isinstance(params, (list, tuple)) else [params]), [0] * B
-        elif H0 is None or W0 is None:
-            raise ValueError("measure: H0 and W0 (or frames=) are required")
-        if cameras is not None:
-            table, n_cams = self._camera_table("measure", "params must be the u8 table", params, dev)
-            cameras = _camera_index("measure", cameras, B, n_cams, dev)
-        else:
-            cp = params.to_c() if hasattr(params, "to_c") else params
-        r = _measure_result(result, B, capacity, stitch_rows, dev)
-        ws = self._scratch("_measure_ws", max(self.measure_scratch_bytes(B, capacity, W0), 256), dev)
-        head = (_ptr(masks) if capacity else C.c_void_p(0), int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]),
-                _ptr(out["offsets"]))
-        tail = (_ptr(ws), ws.numel(), _ptr(r["frame_f64"]), _ptr(r["frame_i32"]), _ptr(r.get("stitch_f64")), _ptr(r.get("stitch_i32")),
-                _stream())
-        rest = head + (B, max_det, capacity, int(H0), int(W0)) + tail
-        if ragged:
-            check(self._ctx, lib().vti_measure_frames_native(
-                self._ctx, _ptr(table), n_cams, _ptr(cameras), _ptr(masks), _ptr(out["mask_bases"]), masks.numel(), *head[2:],
-                *frames._ptrs(), B, max_det, capacity, *tail))
-        elif frames is not None:
-            check(self._ctx, lib().vti_measure_frames(self._ctx, _ptr(table), n_cams, _ptr(cameras), *head, *frames._ptrs(), B, max_det,
-                                                      capacity, *tail))
-        elif cameras is not None:
-            check(self._ctx, lib().vti_measure_cameras(self._ctx, _ptr(table), n_cams, _ptr(cameras), *rest))
-        else:
-            check(self._ctx, lib().vti_measure(self._ctx, C.byref(cp), *rest))
-        return r
-
-    def pack_checker_cameras(self, params_list, device=None):
-        """The camera table of the checker's rig calls: one row per measure.CheckerParams (or VtiCheckerParams) of `params_list`,
-        validated and packed by vti_checker_pack_cameras (a VtiError names the failing index) and uploaded once.  -> u8 device tensor
-        to pass as measure_checker(..., params=table, cameras=...) and annotate_checker(...); row k is camera k.  Its rows are not
-        pack_cameras()' rows."""
-        cps = [p.to_c() if hasattr(p, "to_c") else p for p in params_list]
-        n = len(cps)
-        if n < 1:
-            raise ValueError("pack_checker_cameras: at least one camera")
-        arr = (VtiCheckerParams * n)(*cps)
-        nbytes = int(lib().vti_measure_cameras_bytes(n))
-        host = torch.empty(nbytes, dtype=torch.uint8)
-        check(self._ctx, lib().vti_checker_pack_cameras(self._ctx, arr, n, C.c_void_p(host.data_ptr()), nbytes))
-        return host.to(device or self.device or "cuda")
-
-    def _checker_table(self, who, params_or_table, dev):
-        """A list of CheckerParams or the table of pack_checker_cameras() -> (table, n_cams)."""
-        table = params_or_table if isinstance(params_or_table, torch.Tensor) else self.pack_checker_cameras(params_or_table, dev)
-        row = int(lib().vti_measure_cameras_bytes(1))
-        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < row or table.numel() % row or table.device != dev:
-            raise ValueError(f"{who}: params must be CheckerParams or the u8 table of pack_checker_cameras() on the outputs' device")
-        return table, table.numel() // row
+        return self._measure(_PROCESS_FRAME, "measure", out, params, H0, W0, native, stitch_rows, result, cameras, frames)
 
     def measure_checker(self, out, params, H0=None, W0=None, native=False, stitch_rows=True, result=None, cameras=None, frames=None):
         """The stitch-distance checker's per-frame measurement (Utils/check_stitch_distance.py:281-553) for every frame of an output
@@ -760,6 +726,11 @@ class Engine:
         instead).  frames (vti_measure_checker_frames): a FrameTable in place of H0, W0 -- frame b is measured at its own size;
         letterbox bit masks, or with native=True the ragged rows of a set from alloc_outputs(native_frames=)
         (vti_measure_checker_frames_native; the set needs mask_bases).  Without `cameras` the one `params` serves every frame."""
+        return self._measure(_CHECKER, "measure_checker", out, params, H0, W0, native, stitch_rows, result, cameras, frames)
+
+    def _measure(self, fam, who, out, params, H0, W0, native, stitch_rows, result, cameras, frames):
+        """measure() and measure_checker(): fam's four calls on the arguments both take."""
+        one, with_cameras, with_frames, with_ragged = (getattr(lib(), name) for name in fam.measure)
         dets, masks = out["dets"], out["masks"]
         B, max_det, capacity = out["counts"].shape[0], dets.shape[1], masks.shape[0]
         dev = dets.device
@@ -767,25 +738,25 @@ class Engine:
         if frames is not None:
             self._check_frames(frames, B=B)
             if native and not ragged:
-                raise ValueError("measure_checker: frames of differing sizes have letterbox masks only (native=True needs one frame "
-                                 "size, or the ragged set of alloc_outputs(native_frames=) with its mask_bases)")
+                raise ValueError(f"{who}: frames of differing sizes have letterbox masks only (native=True needs one frame size, "
+                                 "or the ragged set of alloc_outputs(native_frames=) with its mask_bases)")
             if ragged:
-                self._check_ragged(out, frames, max_det, "measure_checker")
+                self._check_ragged(out, frames, max_det, who)
                 if not (dets.is_cuda and masks.is_cuda and out["mask_bases"].is_cuda):
-                    raise ValueError("measure_checker: the output set must be in device memory")
+                    raise ValueError(f"{who}: the output set must be in device memory")
                 capacity = B * max_det
             if H0 is not None or W0 is not None:
-                raise ValueError("measure_checker: give H0, W0 or frames, not both")
+                raise ValueError(f"{who}: give H0, W0 or frames, not both")
             H0, W0 = frames.max_H0, frames.max_W0
             if cameras is None:
-                params, cameras = (params if isinstance(params, (list, tuple, torch.Tensor)) else [params]), [0] * B
+                cameras = [0] * B
         elif H0 is None or W0 is None:
-            raise ValueError("measure_checker: H0 and W0 (or frames=) are required")
+            raise ValueError(f"{who}: H0 and W0 (or frames=) are required")
         if cameras is not None:
             if isinstance(params, (list, tuple)) and not isinstance(cameras, torch.Tensor):
-                cameras = _camera_index("measure_checker", cameras, B, len(params), "cpu")       # before anything is packed
-            table, n_cams = self._checker_table("measure_checker", params if isinstance(params, (list, tuple, torch.Tensor)) else [params], dev)
-            cameras = _camera_index("measure_checker", cameras, B, n_cams, dev)
+                cameras = _camera_index(who, cameras, B, len(params), "cpu")       # before anything is packed
+            table, n_cams = self._camera_table(fam, who, params, dev)
+            cameras = _camera_index(who, cameras, B, n_cams, dev)
         else:
             cp = params.to_c() if hasattr(params, "to_c") else params
         r = _measure_result(result, B, capacity, stitch_rows, dev)
@@ -796,16 +767,14 @@ class Engine:
                 _stream())
         rest = head + (B, max_det, capacity, int(H0), int(W0)) + tail
         if ragged:
-            check(self._ctx, lib().vti_measure_checker_frames_native(
-                self._ctx, _ptr(table), n_cams, _ptr(cameras), _ptr(masks), _ptr(out["mask_bases"]), masks.numel(), *head[2:],
-                *frames._ptrs(), B, max_det, capacity, *tail))
+            check(self._ctx, with_ragged(self._ctx, _ptr(table), n_cams, _ptr(cameras), _ptr(masks), _ptr(out["mask_bases"]), masks.numel(),
+                                         *head[2:], *frames._ptrs(), B, max_det, capacity, *tail))
         elif frames is not None:
-            check(self._ctx, lib().vti_measure_checker_frames(self._ctx, _ptr(table), n_cams, _ptr(cameras), *head, *frames._ptrs(), B,
-                                                              max_det, capacity, *tail))
+            check(self._ctx, with_frames(self._ctx, _ptr(table), n_cams, _ptr(cameras), *head, *frames._ptrs(), B, max_det, capacity, *tail))
         elif cameras is not None:
-            check(self._ctx, lib().vti_measure_checker_cameras(self._ctx, _ptr(table), n_cams, _ptr(cameras), *rest))
+            check(self._ctx, with_cameras(self._ctx, _ptr(table), n_cams, _ptr(cameras), *rest))
         else:
-            check(self._ctx, lib().vti_measure_checker(self._ctx, C.byref(cp), *rest))
+            check(self._ctx, one(self._ctx, C.byref(cp), *rest))
         return r
 
     # ---- process_frame's annotated frame (measurement.py:219-504): the overlay on a selection of the batch ------------------
@@ -827,66 +796,7 @@ class Engine:
         dict(buf=u8 flat, table=the FrameTable of the selection (pack_frames of its shapes; the 16 latest tuples of shapes are kept), shapes,
         byte_offsets, status): picture k is buf[byte_offsets[k]:][:3 * H0 * W0].view(H0, W0, 3), and (buf, table) is what
         encode_jpeg(..., table=) and predict_frames_into take.  `result` may preallocate buf and status.  Letterbox masks only."""
-        if table is not None:
-            self._check_frames(table)
-            if native:
-                raise ValueError("annotate: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
-            if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
-                raise ValueError("annotate: with table=, frames must be the flat uint8 frame buffer")
-            B, H0, W0 = table.B, None, None
-        else:
-            B, H0, W0 = _uniform_frames("annotate", frames)
-        dets, masks = out["dets"], out["masks"]
-        dev = dets.device
-        if out["counts"].shape[0] != B:
-            raise ValueError(f"annotate: {B} frames but an output set of {out['counts'].shape[0]}")
-        max_det, capacity = dets.shape[1], masks.shape[0]
-        sel = _select("annotate", select, B)
-        n_sel = int(sel.size)
-        for key in ("frame_i32", "stitch_f64", "stitch_i32"):
-            if meas.get(key) is None:
-                raise ValueError(f"annotate: meas needs {key} (measure(..., stitch_rows=True))")
-        # everything above is about shapes and values; what needs a device comes from here on
-        if not frames.is_cuda or not frames.is_contiguous():
-            raise ValueError("annotate: frames must be the contiguous device batch predict consumed")
-        if not isinstance(params_or_table, (list, tuple, torch.Tensor)):
-            params_or_table = [params_or_table]
-        table_c, n_cams = self._camera_table("annotate", "params_or_table must be MeasureParams or the u8 table", params_or_table, dev)
-        if cameras is not None:
-            cameras = _camera_index("annotate", cameras, B, n_cams, dev, same_device=False)
-        r = dict(result or {})
-        if "status" not in r:
-            r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
-        if table is not None:
-            self._check_frames(table, buf=frames)
-            shapes = tuple(table.shapes[int(b)] for b in sel)
-            out_table = self._out_table(shapes, dev)                     # the 16 latest selections are kept
-            self._selection_out(r, out_table, shapes, dev)
-            need = int(lib().vti_annotate_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
-            if need <= 0:
-                raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
-                                 f"{out_table.max_H0}x{out_table.max_W0}, max_points={max_points}; a drawn frame is at most 8192 x 8192)")
-        else:
-            if "frames" not in r:
-                r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
-            need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
-            if need <= 0:
-                raise ValueError(f"annotate: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
-        ws = self._scratch("_annotate_ws", need, dev)
-        dev_sel = torch.from_numpy(sel).to(dev)
-        if table is not None:
-            check(self._ctx, lib().vti_annotate_frames(
-                self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras), _ptr(masks) if capacity else C.c_void_p(0),
-                0, _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
-                _ptr(meas["frame_i32"]), _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel),
-                n_sel, int(max_points), *out_table._ptrs(), _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
-            return r
-        check(self._ctx, lib().vti_annotate(
-            self._ctx, _ptr(frames), B, H0, W0, _ptr(table_c), n_cams, _ptr(cameras), _ptr(masks) if capacity else C.c_void_p(0),
-            int(bool(native)), _ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity,
-            _ptr(meas["frame_i32"]), _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel),
-            n_sel, int(max_points), _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
-        return r
+        return self._annotate(_PROCESS_FRAME, "annotate", frames, out, meas, params_or_table, select, cameras, native, result, max_points, table)
 
     # ---- the stitch-distance checker's picture (Utils/check_stitch_distance.py:293-545): vti_annotate_checker ------------------
     def annotate_checker(self, frames, out, meas, params, select, native=False, result=None, max_points=16384, cameras=None,
@@ -900,34 +810,39 @@ class Engine:
         of pack_checker_cameras().  table (vti_annotate_checker_frames): the FrameTable of a batch whose frames differ in size;
         `frames` is then the flat u8 device buffer it describes, and the call returns dict(buf, table, shapes, byte_offsets, status)
         as annotate(table=) does: it feeds encode_jpeg(table=) and stamp(table=) unchanged.  Letterbox masks only with table=."""
-        who = "annotate_checker"
+        return self._annotate(_CHECKER, "annotate_checker", frames, out, meas, params, select, cameras, native, result, max_points, table)
+
+    def _annotate(self, fam, who, frames, out, meas, params, select, cameras, native, result, max_points, table):
+        """annotate() and annotate_checker(): fam's calls on the arguments both take.  Only the checker has a call that takes one
+        settings struct; process_frame's picture always goes through a camera table."""
+        one, with_cameras, with_frames = (name and getattr(lib(), name) for name in fam.annotate)
         if table is not None:
             self._check_frames(table)
             if native:
-                raise ValueError("annotate_checker: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
+                raise ValueError(f"{who}: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
             if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
-                raise ValueError("annotate_checker: with table=, frames must be the flat uint8 frame buffer")
+                raise ValueError(f"{who}: with table=, frames must be the flat uint8 frame buffer")
             B, H0, W0 = table.B, None, None
         else:
             B, H0, W0 = _uniform_frames(who, frames)
         dets, masks = out["dets"], out["masks"]
         dev = dets.device
         if out["counts"].shape[0] != B:
-            raise ValueError(f"annotate_checker: {B} frames but an output set of {out['counts'].shape[0]}")
+            raise ValueError(f"{who}: {B} frames but an output set of {out['counts'].shape[0]}")
         max_det, capacity = dets.shape[1], masks.shape[0]
         sel = _select(who, select, B)
         n_sel = int(sel.size)
         for key in ("frame_i32", "stitch_f64", "stitch_i32"):
             if meas.get(key) is None:
-                raise ValueError(f"annotate_checker: meas needs {key} (measure_checker(..., stitch_rows=True))")
-        rig = cameras is not None or table is not None or isinstance(params, (list, tuple, torch.Tensor))
+                raise ValueError(f"{who}: meas needs {key} ({fam.measure_method}(..., stitch_rows=True))")
+        rig = one is None or cameras is not None or table is not None or isinstance(params, (list, tuple, torch.Tensor))
         if rig and isinstance(params, (list, tuple)) and cameras is not None and not isinstance(cameras, torch.Tensor):
             cameras = _camera_index(who, cameras, B, len(params), "cpu")
         # everything above is about shapes and values; what needs a device comes from here on
         if not frames.is_cuda or not frames.is_contiguous():
-            raise ValueError("annotate_checker: frames must be the contiguous device batch predict consumed")
+            raise ValueError(f"{who}: frames must be the contiguous device batch predict consumed")
         if rig:
-            table_c, n_cams = self._checker_table(who, params if isinstance(params, (list, tuple, torch.Tensor)) else [params], dev)
+            table_c, n_cams = self._camera_table(fam, who, params, dev)
             if cameras is not None:
                 cameras = _camera_index(who, cameras, B, n_cams, dev, same_device=False)
         else:
@@ -938,35 +853,32 @@ class Engine:
         if table is not None:
             self._check_frames(table, buf=frames)
             shapes = tuple(table.shapes[int(b)] for b in sel)
-            out_table = self._out_table(shapes, dev)
+            out_table = self._out_table(shapes, dev)                     # the 16 latest selections are kept
             self._selection_out(r, out_table, shapes, dev)
             need = int(lib().vti_annotate_frames_scratch_bytes(self._ctx, C.c_void_p(out_table.host.data_ptr()), max_det, int(max_points)))
             if need <= 0:
-                raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
+                raise ValueError(f"{who}: unsupported geometry (n_sel={n_sel}, max_det={max_det}, frames up to "
                                  f"{out_table.max_H0}x{out_table.max_W0}, max_points={max_points}; a drawn frame is at most 8192 x 8192)")
         else:
             if "frames" not in r:
                 r["frames"] = torch.empty((n_sel, H0, W0, 3), dtype=torch.uint8, device=dev)
             need = self.annotate_scratch_bytes(n_sel, max_det, H0, W0, max_points)
             if need <= 0:
-                raise ValueError(f"annotate_checker: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
+                raise ValueError(f"{who}: unsupported geometry (n_sel={n_sel}, max_det={max_det}, {H0}x{W0}, max_points={max_points})")
         ws = self._scratch("_annotate_ws", need, dev)
         dev_sel = torch.from_numpy(sel).to(dev)
         mid = (_ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity, _ptr(meas["frame_i32"]),
                _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(max_points))
         pm = _ptr(masks) if capacity else C.c_void_p(0)
         if table is not None:
-            check(self._ctx, lib().vti_annotate_checker_frames(
-                self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras), pm, 0, *mid, *out_table._ptrs(),
-                _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+            check(self._ctx, with_frames(self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras), pm, 0, *mid,
+                                         *out_table._ptrs(), _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         elif rig:
-            check(self._ctx, lib().vti_annotate_checker_cameras(
-                self._ctx, _ptr(frames), B, H0, W0, _ptr(table_c), n_cams, _ptr(cameras), pm, int(bool(native)), *mid,
-                _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+            check(self._ctx, with_cameras(self._ctx, _ptr(frames), B, H0, W0, _ptr(table_c), n_cams, _ptr(cameras), pm, int(bool(native)),
+                                          *mid, _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         else:
-            check(self._ctx, lib().vti_annotate_checker(
-                self._ctx, _ptr(frames), B, H0, W0, C.byref(cp), pm, int(bool(native)), *mid,
-                _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+            check(self._ctx, one(self._ctx, _ptr(frames), B, H0, W0, C.byref(cp), pm, int(bool(native)), *mid,
+                                 _ptr(r["frames"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         return r
 
     # ---- the model-check viewer's picture (Utils/check_model.py:155-256): vti_overlay ------------------------------------------
