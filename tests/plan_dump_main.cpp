@@ -12,12 +12,19 @@
 //       a line "==== second plan"
 //   plan_dump_main runopts
 //       the launch path's switches (RunOptions) as parsed from the environment
+//   plan_dump_main launches SCALE NC NM H W MAX_BATCH DTYPE B SWAP_RB BEST
+//       every launch of one forward of B frames (BEST 1: with the anchor pairs) under the switches of the environment, one line per
+//       launch: the op's index, the launcher, its selector arguments, every field of its block (tests/launch_dump.h), the tensors at
+//       fake addresses; a refusal's text in place of its line; then what vti_conv_at reports of every conv
+//   plan_dump_main cfglaunch DTYPE B H W C1 C2 K S KIND TH TW WN NREP
+//       the launch vti_debug_conv2d would issue for that conv (dense tensors, without and with a residual)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
 #include "../vision-textile-inspection_amd/csrc/vti_internal.h"
+#include "launch_dump.h"
 
 using namespace vti;
 
@@ -73,6 +80,59 @@ static vti_desc desc_of(char** a) {
     return d;
 }
 
+// the row vti_debug_conv2d makes of (.., H, W, C1, C2, K, S, KIND, ..)
+static ConvRow debug_row(const int* v) {
+    const int H = v[2], W = v[3], k = v[6], s = v[7], kind = v[8];
+    ConvRow r;
+    r.name = "debug"; r.c1 = v[4]; r.c2 = v[5]; r.k = k; r.s = s; r.kind = kind; r.h_in = H; r.w_in = W;
+    if (kind == 2) { r.h_out = 2 * H; r.w_out = 2 * W; }
+    else { r.h_out = (H + 2 * (k / 2) - k) / s + 1; r.w_out = (W + 2 * (k / 2) - k) / s + 1; }
+    return r;
+}
+
+static void dump_record(const LaunchRec& L) {
+    switch (L.fn) {
+    case LAUNCH_STEM_L1: launch_dump::print_stem_l1(L.dtype, L.conv, L.persistent); break;
+    case LAUNCH_CONV: launch_dump::print_conv(L.dtype, L.ks, L.stride, L.nrep, L.mode, L.conv, L.lds); break;
+    case LAUNCH_CONVFOLD:
+    case LAUNCH_CONV_PK_FOLD: launch_dump::print_fold(launcher_name(L.fn), L.dtype, L.conv, L.lds); break;
+    case LAUNCH_POOL: launch_dump::print_pool(L.dtype, L.pool); break;
+    case LAUNCH_UP2: launch_dump::print_up2(L.dtype, L.up2); break;
+    case LAUNCH_DECODE:
+    case LAUNCH_BOX_DECODE: launch_dump::print_decode(launcher_name(L.fn), L.dec); break;
+    }
+}
+
+// What vti_forward / vti_forward_scored would launch: the loop of forward_impl without its streams.
+static void dump_launches(const vti_desc& d, const Options& opt, int B, int swap_rb, bool with_best) {
+    Plan P;
+    const std::string err = P.build(d, opt.plan);
+    if (!err.empty()) { printf("vti_create refused: vti_create: %s\n", err.c_str()); return; }
+    std::vector<float> alpha;
+    for (size_t i = 0; i < P.convs.size(); ++i) alpha.push_back(launch_dump::fake_alpha((int)i));
+    const Bindings bind{launch_dump::fake_ws(), launch_dump::fake_wpk(), launch_dump::fake_bias(), alpha.data(), launch_dump::fake_input(),
+                        launch_dump::fake_pred(), launch_dump::fake_proto(), with_best ? launch_dump::fake_best() : nullptr};
+    LaunchRec L;
+    bool refused = false;
+    for (size_t i = 0; i < P.ops.size() && !refused; ++i) {
+        const Op& op = P.ops[i];
+        if (op.kind == OP_FORK || op.kind == OP_JOIN) continue;
+        launch_dump::op_index() = (int)i;
+        if (const char* e = fill_launch(P, op, B, swap_rb, opt.run, bind, L)) { launch_dump::print_refusal(VTI_ERR_UNSUPPORTED, e); refused = true; }
+        else dump_record(L);
+    }
+    if (!refused && with_best && !P.pred_scatter)
+        launch_dump::print_anchor_best(bind.pred, B, P.num_anchors, P.desc.nc, P.desc.nm, bind.best);
+    for (size_t i = 0; i < P.convs.size(); ++i) {
+        const ConvRow& r = P.convs[i];
+        vti_conv_info o;
+        memset(&o, 0, sizeof o);
+        snprintf(o.name, sizeof o.name, "%s", r.name.c_str());
+        conv_geometry(P, (int)i, &o);
+        launch_dump::print_conv_info((int)i, o);
+    }
+}
+
 static void build_and_dump(const vti_desc& d, const PlanOptions& opt) {
     Plan P;
     const std::string err = P.build(d, opt);
@@ -113,14 +173,34 @@ int main(int argc, char** argv) {
     if (argc == 15 && !strcmp(argv[1], "cfg")) {
         int v[13];
         for (int i = 0; i < 13; ++i) v[i] = atoi(argv[2 + i]);
-        const int dtype = v[0], B = v[1], H = v[2], W = v[3], k = v[6], s = v[7], kind = v[8];
-        ConvRow r;
-        r.name = "debug"; r.c1 = v[4]; r.c2 = v[5]; r.k = k; r.s = s; r.kind = kind; r.h_in = H; r.w_in = W;
-        if (kind == 2) { r.h_out = 2 * H; r.w_out = 2 * W; }
-        else { r.h_out = (H + 2 * (k / 2) - k) / s + 1; r.w_out = (W + 2 * (k / 2) - k) / s + 1; }
+        const int dtype = v[0], B = v[1];
+        const ConvRow r = debug_row(v);
         ConvCfg g;
         choose_conv_cfg(options_from_env().plan, dtype, r, r.c1 == 3, B, g, v[9], v[10], v[11], v[12]);
         dump_cfg(g);
+        return 0;
+    }
+    if (argc == 12 && !strcmp(argv[1], "launches")) {
+        dump_launches(desc_of(argv + 2), options_from_env(), atoi(argv[9]), atoi(argv[10]), atoi(argv[11]) != 0);
+        return 0;
+    }
+    if (argc == 15 && !strcmp(argv[1], "cfglaunch")) {
+        int v[13];
+        for (int i = 0; i < 13; ++i) v[i] = atoi(argv[2 + i]);
+        const int dtype = v[0], B = v[1];
+        const ConvRow r = debug_row(v);
+        const Options opt = options_from_env();
+        ConvCfg g;
+        choose_conv_cfg(opt.plan, dtype, r, r.c1 == 3, B, g, v[9], v[10], v[11], v[12]);
+        if (g.TH == 0) { printf("no launch configuration fits\n"); return 0; }
+        launch_dump::op_index() = 0;
+        for (int res = 0; res < 2; ++res) {      // the tensors dense: ld = channels, offsets 0
+            LaunchRec L;
+            conv_record(opt.run, dtype, r, g, B, launch_dump::fake_input(), r.c1, 0, launch_dump::fake_pred(), r.c2, 0,
+                        res ? launch_dump::fake_proto() : nullptr, res ? r.c2 : 0, 0, launch_dump::fake_wpk(), launch_dump::fake_bias(),
+                        launch_dump::fake_alpha(0), false, 0, L);
+            dump_record(L);
+        }
         return 0;
     }
     if (argc == 12 && !strcmp(argv[1], "twice")) {
@@ -139,6 +219,6 @@ int main(int argc, char** argv) {
                r.mask_wgs_per_cu, r.stamp_op.c_str());
         return 0;
     }
-    fprintf(stderr, "usage: plan_dump_main plan|cfg|twice|runopts ... (see the head of tests/plan_dump_main.cpp)\n");
+    fprintf(stderr, "usage: plan_dump_main plan|cfg|twice|runopts|launches|cfglaunch ... (see the head of tests/plan_dump_main.cpp)\n");
     return 2;
 }

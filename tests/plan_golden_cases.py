@@ -105,6 +105,60 @@ def cases():
     return out
 
 
+# ---- the launch parameters of one forward (tests/golden/launch_params.json) --------------------------------------------------------
+LAUNCH_GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_params.json")
+LAUNCH_BASES = [("n", 80, 640, 640, 64, "h2"), ("n", 80, 640, 640, 64, "fp16"), ("n", 80, 640, 640, 64, "fp32"), ("n", 2, 960, 960, 8, "h2"),
+                ("n", 80, 224, 352, 3, "fp32"), ("n", 80, 608, 736, 1, "h2"), ("s", 80, 640, 640, 8, "h2")]      # FULL's, and its PLAIN below
+# switches of the launch path, and planner switches that steer forward_impl into a branch the defaults never take
+LAUNCH_RUN_ENVS = [{"VTI_PK_MAX_WGS": "8"}, {"VTI_PK_STAGGER": "0"}, {"VTI_PK_STAGGER": "3"}, {"VTI_PK_LINEAR_MAP": "1"},
+                   {"VTI_STEM_NOT_PERSISTENT": "1"}]
+LAUNCH_PLAN_ENVS = [dict(PLAIN_PLAN)] + [{n: "1"} for n in ("VTI_NO_PRED_SCATTER", "VTI_NO_DFL_FUSE", "VTI_NO_UPFUSE", "VTI_NO_FOLD",
+                                                           "VTI_NO_PK_FOLD", "VTI_NO_BNECK_TAIL", "VTI_NO_STEM_FUSE3", "VTI_NO_STEM_FUSE",
+                                                           "VTI_PK_FUSED")]
+# 512 frames of 640x640 on h2: tensors past 2^31 bytes.  The planner keeps such convs off the persistent kernels by itself; with its
+# limit raised the launch path meets them: a fused Bottleneck is refused, and without the Bottleneck fusion persistent kernels fall
+# back (pk=0) until the folded upsample is refused
+BIG = ("n", 80, 640, 640, 512, "h2")
+BIG_ENVS = [{}, {"VTI_PK_LIMIT_BYTES": str(1 << 40)}, {"VTI_PK_LIMIT_BYTES": str(1 << 40), "VTI_NO_BNECK": "1"}]
+LAUNCH_FULL = {"n80_640x640_b64_h2@B64_swap1_best1", "n80_640x640_b64_fp16@B64_swap1_best1", "n80_640x640_b64_fp32@B1_swap1_best1",
+               "n80_640x640_b64_h2@B64_swap1_best1+PLAIN", "n80_640x640_b512_h2@B512_swap1_best1+VTI_NO_BNECK=1+VTI_PK_LIMIT_BYTES=1099511627776"}
+
+
+def _env_tag(env):
+    return "+PLAIN" if env == PLAIN_PLAN else "".join(f"+{n}={v}" for n, v in sorted(env.items()))
+
+
+def launch_cases():
+    """[(id, argv, env)]: `launches` prints every launch of one forward (base, B, swap_rb, with / without best), `cfglaunch` the
+    block vti_debug_conv2d would launch for a forced geometry."""
+    out = []
+
+    def add(base, B, swap_rb, best, env):
+        cid = f"{base_id(*base)}@B{B}_swap{swap_rb}_best{best}{_env_tag(env)}"
+        out.append((cid, ["launches"] + plan_argv(*base)[1:] + [str(B), str(swap_rb), str(best)], env))
+
+    h2, fp16 = LAUNCH_BASES[0], LAUNCH_BASES[1]
+    for base in LAUNCH_BASES:
+        for B in sorted({base[4], 1}):
+            add(base, B, 1, 1, {})
+    for B in (64, 1):
+        add(h2, B, 1, 1, dict(PLAIN_PLAN))
+    for swap_rb, best in ((0, 1), (1, 0), (0, 0)):
+        add(h2, 64, swap_rb, best, {})
+    for env in LAUNCH_RUN_ENVS:
+        add(h2, 64, 1, 1, env)
+    for base in (h2, fp16):
+        for env in LAUNCH_PLAN_ENVS:
+            if not (base == h2 and env == PLAIN_PLAN):
+                add(base, 64, 1, 1, env)
+    for env in BIG_ENVS:
+        add(BIG, 512, 1, 1, env)
+    for cid, argv, env in cases():
+        if argv[0] == "cfg":
+            out.append((cid, ["cfglaunch"] + argv[1:], env))
+    return out
+
+
 def build_program(out_dir):
     """Compiles tests/plan_dump_main.cpp the way csrc/Makefile compiles plan.o and links it against the built libvti.so."""
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

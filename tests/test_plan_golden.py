@@ -63,6 +63,34 @@ def test_every_recorded_plan_is_replayed_byte_for_byte(exe, golden):
     assert not bad, f"{len(bad)} of {len(cases)} plans differ:\n" + "\n".join(bad[:20])
 
 
+def test_every_recorded_forward_is_replayed_launch_for_launch(exe):
+    """The launch parameters (csrc/launch.cpp), pinned the same way: tests/golden/launch_params.json holds what the forward launched
+    -- launcher, selector arguments and every field of each block, the tensors at fake addresses -- when forward_impl still filled
+    the blocks inline (recorded from that commit: tests/golden/make_launch_params.py).  The cases: every base at max_batch and at
+    one frame, swap_rb and the anchor pairs on and off, the switches of the launch path, each planner switch that steers the loop
+    into another branch, tensors past 2^31 bytes (persistent kernels falling back, two refusals), and the block of every forced
+    geometry of vti_debug_conv2d.  Between them they reach every launcher."""
+    with open(G.LAUNCH_GOLDEN) as f:
+        golden = json.load(f)
+    cases = G.launch_cases()
+    assert {c[0] for c in cases} == set(golden) and G.LAUNCH_FULL <= set(golden)
+    bad, launchers, refusals = [], set(), set()
+    for cid, argv, env in cases:
+        want = golden[cid]
+        dump = G.run(exe, argv, env)
+        launchers |= set(re.findall(r": (launch_\w+) ", dump))
+        refusals |= set(re.findall(r": refused \(status -?\d+\): (.*)", dump))
+        if _sha(dump) != want["sha256"]:
+            got = {"launches": dump.count(": launch_"), "refused": int(": refused (" in dump)}
+            bad.append(f"{cid}: SHA-256 differs; golden {({k: want[k] for k in got})}, now {got}" +
+                       ("; " + _first_changed_line(want["lines"], dump) if "lines" in want else ""))
+    assert not bad, f"{len(bad)} of {len(cases)} forwards differ:\n" + "\n".join(bad[:20])
+    assert launchers == {"launch_stem_l1", "launch_conv", "launch_convfold", "launch_conv_pk_fold", "launch_sppf_pool", "launch_upsample2x",
+                         "launch_decode", "launch_box_decode", "launch_anchor_best"}, launchers
+    assert refusals == {"fused bottleneck needs the persistent kernel (tensor too large?)",
+                        "folded upsample needs the persistent 1x1 kernel (tensor too large?)"}, refusals
+
+
 BASE_H2 = ("n", 80, 640, 640, 64, "h2")
 BASE_F32 = ("n", 80, 640, 640, 64, "fp32")
 DIRECT = [   # base, the switch in the environment, the same option filled into PlanOptions directly

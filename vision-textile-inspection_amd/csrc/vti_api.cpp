@@ -106,11 +106,6 @@ static bool stamped_launch(ConvParams& p, size_t nwg, bool pk, hipStream_t st, c
     return true;
 }
 
-// workgroups of a conv launch (stamp slots): the persistent grid or one per tile, times the n-groups
-static size_t conv_workgroups(const ConvParams& p, const ConvCfg& g, int B) {
-    const int NTB = g.WN * g.NREP;
-    return (p.pk ? (size_t)p.pk_wgs : (size_t)B * p.tiles_y * p.tiles_x) * ((g.ntiles_n + NTB - 1) / NTB);
-}
 #endif
 
 // The settings that vti_measure_params and vti_checker_params have in common: nullptr when they are valid.
@@ -171,26 +166,7 @@ int32_t vti_conv_at(const vti_ctx* c, int32_t i, vti_conv_info* o) {
     o->c1 = r.c1; o->c2 = r.c2; o->k = r.k; o->s = r.s; o->kind = r.kind;
     o->h_in = r.h_in; o->w_in = r.w_in; o->h_out = r.h_out; o->w_out = r.w_out;
     o->macs = r.macs();
-    for (const Op& op : c->plan.ops) {
-        if (op.kind != OP_CONV && op.kind != OP_CONV0) continue;
-        if (op.conv == i) {
-            o->tile_h = op.cfg.TH; o->tile_w = op.cfg.TW; o->waves_n = op.cfg.WN; o->nrep = op.cfg.NREP;
-            o->lds_bytes = (int32_t)op.cfg.lds; o->persistent = op.cfg.pk;   // 1: conv3_pk, 2: conv1_pk, 3: bneck_pk
-        } else if (op.tail == i) {      // the C2f's closing 1x1 inside its bottleneck's kernel (bneck_pk tail)
-            o->tile_h = op.cfg.TH; o->tile_w = op.cfg.TW; o->waves_n = 1; o->nrep = 2; o->lds_bytes = 0; o->fused = 1; o->persistent = 1;
-        } else if (op.pair == i) {      // second 3x3 of a fused Bottleneck: runs inside the first one's kernel (bneck_pk)
-            o->tile_h = op.cfg.TH; o->tile_w = op.cfg.TW; o->waves_n = 1; o->nrep = op.cfg.NREP; o->lds_bytes = 0; o->fused = 1;
-            o->persistent = 1;
-        } else if (op.fold == i) {      // ConvTranspose folded into the following 3x3 (convfold_kernel): never materialised
-            o->tile_h = op.cfg.TH; o->tile_w = op.cfg.TW; o->persistent = op.cfg.pk; o->waves_n = 4; o->nrep = op.cfg.NREP; o->lds_bytes = 0;   // `fused` stays 0: that flag means "runs inside the PREVIOUS row's kernel"
-        } else if (op.fused_l1 == i) {  // layer 1 inside the stem's kernel (stem_l1_kernel: 16 x 20 output tiles, 2 n-tiles)
-            stem_l1_tile(&o->tile_h, &o->tile_w); o->waves_n = 1; o->nrep = 2; o->lds_bytes = 0; o->fused = 1;
-        } else if (op.fused == i) {     // runs inside its producer's kernel, on that kernel's geometry
-            o->tile_h = op.cfg.TH; o->tile_w = op.cfg.TW; o->waves_n = 1; o->nrep = op.cfg.ntiles2;
-            if (op.fused_l1 >= 0) stem_l1_tile(&o->tile_h, &o->tile_w);
-            o->lds_bytes = 0; o->fused = 1;
-        }
-    }
+    conv_geometry(c->plan, i, o);
     return VTI_OK;
 }
 
@@ -402,90 +378,49 @@ int32_t vti_letterbox_frames(vti_ctx* c, const uint8_t* frames, const void* host
     return VTI_OK;
 }
 
-static void* buf_ptr(vti_ctx* c, int buf, const void* input, void* proto) {
-    if (buf == 0) return (void*)input;
-    if (buf == c->plan.proto_buf_c) return proto;
-    return c->ws + c->plan.bufs[buf].off;
+// The tensors of one forward: the ctx's weights and workspace, the caller's input and outputs.
+static Bindings bindings_of(const vti_ctx* c, const void* input, float* pred, void* proto, float* best) {
+    return Bindings{c->ws, c->d_wpk, c->d_bias, c->alpha.data(), input, pred, proto, best};
 }
 
-// Delay units (x 1024 cycles) of the staggered persistent 3x3 launches.  h2 only by default: -2.6 ... -4.2 % per forward on five of
-// seven boxes (A/B on one box at a time), +0.8 % on the two fastest; fp16: +0.2 ... +1 % on a fast box, fp32: nothing.  VTI_PK_STAGGER=n overrides.
-static int stagger_units(const RunOptions& run, int dtype) { return run.pk_stagger >= 0 ? run.pk_stagger : (dtype == VTI_H2 ? 10 : 0); }
-
-// Stores of n channels at channel offset coff into rows of ld channels: 16-byte vector stores need all three to be multiples of 4.
-static int scalar_store(int n, int ld, int coff) { return (n % 4 || ld % 4 || coff % 4) ? 1 : 0; }
-
-// One conv launch's parameter block from its table row + geometry + tensor views.
-static void fill_conv_params(const RunOptions& run, int conv_elem_size, ConvParams& p, const ConvRow& r, const ConvCfg& g, int B, const void* in, int in_ld,
-                             int in_coff, void* out, int out_ld, int out_coff, const void* res, int res_ld,
-                             int res_coff, const void* wpk, const float* bias, bool out_f32, int swap_rb) {
-    const bool deconv = r.kind == 2;
-    memset(&p, 0, sizeof p);
-    p.in = in; p.out = out; p.wpk = wpk; p.bias = bias;
-    p.B = B; p.Hin = r.h_in; p.Win = r.w_in;
-    p.Hout = deconv ? r.h_in : r.h_out; p.Wout = deconv ? r.w_in : r.w_out;
-    p.Cin = r.c1; p.in_ld = in_ld; p.in_coff = in_coff;
-    p.Cout = g.gemm_n; p.out_ld = out_ld; p.out_coff = out_coff;
-    if (res) { p.res = res; p.res_ld = res_ld; p.res_coff = res_coff; p.has_res = 1; }
-    p.TH = g.TH; p.TW = g.TW;
-    p.tiles_y = (p.Hout + g.TH - 1) / g.TH; p.tiles_x = (p.Wout + g.TW - 1) / g.TW;
-    p.WN = g.WN;
-    p.nt = g.threads;
-    p.wreg = g.pk ? 0 : g.wreg;      // the per-tile kernel's flag; conv1_pk's register-resident weights are pk_wstat == 2
-    p.pk_lin = run.pk_linear_map;       // A/B aid: the linear pixel -> column-tile map of the persistent 3x3 kernels
-    p.act = r.kind == 0; p.out_f32 = out_f32 ? 1 : 0;
-    p.deconv_c = deconv ? r.c2 : 0;
-    p.swap_rb = swap_rb ? 1 : 0;
-    p.nchunks = g.nchunks; p.ntiles_n = g.ntiles_n;
-    p.scalar_store = scalar_store(g.gemm_n, out_ld, out_coff);
-    const bool conv0 = r.c1 == 3;
-    const int ks = deconv ? 1 : r.k, st = deconv ? 1 : r.s;
-    const unsigned PW = conv0 ? (unsigned)g.TW : (unsigned)((g.TW - 1) * st + ks);
-    p.pw_magic = (unsigned)((0x100000000ull + PW - 1) / PW);
-    const unsigned RWD = ((unsigned)(2 * g.TW + 1) * 3 + 6) >> 2;      // stem: dwords per u8 patch row
-    p.rw_magic = (unsigned)((0x100000000ull + RWD - 1) / RWD);
-    p.tw_magic = (unsigned)((0x100000000ull + (unsigned)g.TW - 1) / (unsigned)g.TW);
-    p.wpk_bytes = (unsigned)packed_conv_bytes(r, conv0, g);
-    if (g.pk == 2) {  // persistent 1x1 kernel: tiles are runs of TH * 80 pixels of the flattened [B*H*W] index space
-        const size_t es = conv_elem_size;
-        const size_t npx = (size_t)B * p.Hout * p.Wout;
-        const size_t ib = npx * in_ld * es;
-        const size_t ob = (deconv ? 4 * npx : npx) * out_ld * (out_f32 ? 4 : es);
-        p.pk = (ib < 0x80000000ull && ob < 0x80000000ull && !res) ? 2 : 0;
-        p.in_bytes = (unsigned)ib; p.out_bytes = (unsigned)ob; p.res_bytes = 0;
-        p.pk_depth = g.pk_depth; p.pk_wstat = g.pk_wstat; p.pk_cps = g.pk_cps;
-        p.pk_tiles = (int)((npx + (size_t)g.TH * 80 - 1) / ((size_t)g.TH * 80));
-        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, g.ntiles_n / (g.WN * g.NREP), run.pk_max_wgs);
-        p.pk_xcd = p.pk_wgs >= 8 ? 1 : 0;
-    } else if (g.pk) {   // persistent kernel: workgroups along x walk the B * tiles_y * tiles_x tiles
-        const size_t es = conv_elem_size;
-        const size_t ib = (size_t)B * r.h_in * r.w_in * in_ld * es, ob = (size_t)B * p.Hout * p.Wout * out_ld * (out_f32 ? 4 : es);
-        const size_t rb = res ? (size_t)B * p.Hout * p.Wout * res_ld * es : 0;
-        p.pk = (ib < 0x80000000ull && ob < 0x80000000ull && rb < 0x80000000ull) ? g.pk : 0;   // 2^31 marks out-of-range lanes
-        p.in_bytes = (unsigned)ib; p.out_bytes = (unsigned)ob; p.res_bytes = (unsigned)rb;
-        p.pk_tiles = B * p.tiles_y * p.tiles_x;
-        p.pk_depth = g.pk_depth; p.pk_wstat = g.pk_wstat;
-        const int gy = g.ntiles_n / (g.WN * g.NREP);
-        p.pk_wgs = pk_grid(p.pk_tiles, g.pk_wgpc, gy, run.pk_max_wgs);      // tests: force many tiles per workgroup
-        p.pk_xcd = p.pk_wgs >= 8 ? 1 : 0;
-        // launches that fill the chip start the upper half of their workgroups late (conv_pk.hip: pk_stagger_wait): eligibility here,
-        // the caller scales it by stagger_units(run, dtype)
-        p.pk_stagger = ((g.pk == 1 || g.pk == 4) && p.pk_tiles >= std::max(1, 256 * g.pk_wgpc / gy) && p.pk_wgs >= 16) ? 1 : 0;
+static hipError_t launch_record(const LaunchRec& L, hipStream_t st) {
+    switch (L.fn) {
+    case LAUNCH_STEM_L1: return launch_stem_l1(L.dtype, L.conv, st, L.persistent);
+    case LAUNCH_CONV: return launch_conv(L.dtype, L.ks, L.stride, L.nrep, L.mode, L.conv, L.lds, st);
+    case LAUNCH_CONVFOLD: return launch_convfold(L.dtype, L.conv, L.lds, st);
+    case LAUNCH_CONV_PK_FOLD: return launch_conv_pk_fold(L.dtype, L.conv, L.lds, st);
+    case LAUNCH_POOL: return launch_sppf_pool(L.dtype, L.pool, st);
+    case LAUNCH_UP2: return launch_upsample2x(L.dtype, L.up2, st);
+    case LAUNCH_DECODE: return launch_decode(L.dec, st);
+    case LAUNCH_BOX_DECODE: return launch_box_decode(L.dec, st);
     }
+    return hipErrorInvalidValue;
 }
 
-// The fused 1x1 second stage of an op (op.fused; fold ops and fused towers): its weights, where it writes and how it stores.
-static void fill_stage2(vti_ctx* c, ConvParams& p, const Op& op, const void* input, void* proto) {
-    const Plan& P = c->plan;
-    const ConvCfg& g = op.cfg;
-    const Buf& o2 = P.bufs[op.out2.buf];
-    p.w2 = (const char*)c->d_wpk + g.wpk_off2; p.bias2 = c->d_bias + g.bias_off2; p.alpha2 = c->alpha[op.fused];
-    p.out2 = buf_ptr(c, op.out2.buf, input, proto);
-    p.Cout2 = g.gemm_n2; p.ntiles2 = g.ntiles2; p.out2_ld = o2.C; p.out2_coff = op.out2.coff;
-    p.act2 = P.convs[op.fused].kind == 0; p.out2_f32 = op.out2_f32 ? 1 : 0;
-    p.scalar_store2 = scalar_store(g.gemm_n2, o2.C, op.out2.coff);
-    p.nat2 = op.nat2;           // fp32 NHWC output (e.g. the h2 engine's proto): stage-2 weights are packed with natural rows
-    p.out2_bstride = P.convs[op.conv].h_out * P.convs[op.conv].w_out;     // the op's output grid (fold: the 2x map)
+// Issues one record on a stream.  Diagnostic build, stamp_header != nullptr (the op VTI_STAMP_OP names; "": no header line): a
+// launch_conv record is launched once, stamped; stem + layer 1 is stamped and then launched again.
+static hipError_t issue(LaunchRec& L, hipStream_t st, const char* stamp_header = nullptr) {
+#ifdef VTI_STAMPS
+    if (stamp_header && (L.fn == LAUNCH_CONV || L.fn == LAUNCH_STEM_L1)) {
+        if (L.fn == LAUNCH_STEM_L1) fprintf(stderr, "[stamps] stem + layer 1: 1: patch staged, 2: stem done, 3: layer-1 MFMAs done, 12: end\n");
+        if (stamped_launch(L.conv, launch_workgroups(L), L.fn == LAUNCH_CONV && L.conv.pk != 0, st, *stamp_header ? stamp_header : nullptr,
+                           [&] { return launch_record(L, st); }) && L.fn == LAUNCH_CONV)
+            return hipSuccess;
+    }
+#endif
+    return launch_record(L, st);
+}
+
+// what names an op in a launch error
+static const char* launch_what(const LaunchRec& L) {
+    switch (L.fn) {
+    case LAUNCH_STEM_L1: return "stem + layer 1";
+    case LAUNCH_POOL: return "sppf pool";
+    case LAUNCH_UP2: return "upsample2x";
+    case LAUNCH_DECODE: return "decode";
+    case LAUNCH_BOX_DECODE: return "box decode";
+    default: return L.name;
+    }
 }
 
 static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t swap_rb, float* pred, void* proto, float* best, void* stream);
@@ -507,186 +442,27 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
     if (B == 0) return VTI_OK;
     const Plan& P = c->plan;
     hipStream_t main_st = (hipStream_t)stream;
-    const int dt = P.desc.dtype;
     const RunOptions& run = c->opt.run;
     if (run.list_ops) {        // developer aid: launch order, to label a kernel trace
         int i = 0;
-        for (const Op& op : P.ops) {
-            if (op.kind == OP_FORK || op.kind == OP_JOIN) continue;
-            const bool cv = op.kind == OP_CONV || op.kind == OP_CONV0;
-            fprintf(stderr, "[op %2d] lane %d %s%s%s\n", i++, op.lane,
-                    cv ? P.convs[op.conv].name.c_str() : op.kind == OP_POOL ? "sppf_pool" : op.kind == OP_UP2 ? "upsample2x" : "decode",
-                    cv && op.fused_l1 >= 0 ? (" + " + P.convs[op.fused_l1].name).c_str() : cv && op.fold >= 0 ? (" (folded: " + P.convs[op.fold].name + ")").c_str() : cv && op.pair >= 0 ? (" + " + P.convs[op.pair].name + (op.tail >= 0 ? " + " + P.convs[op.tail].name : "")).c_str() : "",
-                    cv && op.fused >= 0 ? (" + " + P.convs[op.fused].name).c_str() : "");
-        }
+        for (const Op& op : P.ops)
+            if (op.kind != OP_FORK && op.kind != OP_JOIN) fprintf(stderr, "[op %2d] lane %d %s\n", i++, op.lane, op_label(P, op).c_str());
     }
+    const Bindings bind = bindings_of(c, input, pred, proto, best);
+    LaunchRec L;
     for (const Op& op : P.ops) {
-        hipStream_t st = (c->multi_stream && op.lane > 0) ? c->side[op.lane] : main_st;
-        switch (op.kind) {
-        case OP_FORK:
-            if (c->multi_stream) {
-                VTI_HIP(c, hipEventRecord(c->ev_fork[op.lane], main_st), "fork record");
-                VTI_HIP(c, hipStreamWaitEvent(c->side[op.lane], c->ev_fork[op.lane], 0), "fork wait");
-            }
-            break;
-        case OP_JOIN:
-            if (c->multi_stream) {
-                VTI_HIP(c, hipEventRecord(c->ev_join[op.lane], c->side[op.lane]), "join record");
-                VTI_HIP(c, hipStreamWaitEvent(main_st, c->ev_join[op.lane], 0), "join wait");
-            }
-            break;
-        case OP_CONV0:
-        case OP_CONV: {
-            const ConvRow& r = P.convs[op.conv];
-            const ConvCfg& g = op.cfg;
-            const Buf& ib = P.bufs[op.in.buf];
-            const Buf& ob = P.bufs[op.out.buf];
-            if (op.fused_l1 >= 0) {     // stem + layer 1 in one kernel
-                const ConvRow& r1 = P.convs[op.fused_l1];
-                const Buf& o1 = P.bufs[op.out2.buf];
-                ConvParams q;
-                memset(&q, 0, sizeof q);
-                q.in = input; q.B = B; q.Hin = r.h_in; q.Win = r.w_in; q.Hout = r1.h_out; q.Wout = r1.w_out;
-                q.Cin = 16; q.Cout = r1.c2; q.ntiles_n = 2; q.act = 1; q.swap_rb = swap_rb ? 1 : 0;
-                q.out = buf_ptr(c, op.out2.buf, input, proto); q.out_ld = o1.C; q.out_coff = op.out2.coff;
-                q.wpk = (const char*)c->d_wpk + g.wpk_off2; q.bias = c->d_bias + g.bias_off2;     // layer 1
-                q.w0 = (const char*)c->d_wpk + g.wpk_off; q.bias0 = c->d_bias + g.bias_off;       // stem
-                q.alpha = c->alpha[op.fused_l1]; q.alpha0 = c->alpha[op.conv]; q.alpha2 = op.fused >= 0 ? c->alpha[op.fused] : 1.f;
-                if (op.fused >= 0) {    // + the 1x1 conv after layer 1: layer 1 itself is not stored (out2 = that conv's view)
-                    q.out = nullptr;
-                    q.w2 = (const char*)c->d_wpk + g.wpk_off3; q.bias2 = c->d_bias + g.bias_off3;
-                    q.out2 = buf_ptr(c, op.out2.buf, input, proto);
-                    q.Cout2 = g.gemm_n2; q.ntiles2 = g.ntiles2; q.out2_ld = o1.C; q.out2_coff = op.out2.coff;
-                    q.act2 = 1; q.out2_bstride = r1.h_out * r1.w_out;
-                    q.scalar_store2 = scalar_store(g.gemm_n2, o1.C, op.out2.coff);
-                }
-                stem_l1_tile(&q.TH, &q.TW);
-                q.tiles_y = (q.Hout + q.TH - 1) / q.TH; q.tiles_x = (q.Wout + q.TW - 1) / q.TW; q.WN = 1;
-                q.scalar_store = scalar_store(q.Cout, q.out_ld, q.out_coff);
-#ifdef VTI_STAMPS
-                if (r.name == run.stamp_op)
-                    stamped_launch(q, (size_t)stem_l1_grid(dt, B * q.tiles_y * q.tiles_x, !run.stem_not_persistent), false, st,
-                                   ("[stamps] op " + r.name + " + layer 1 (1: patch staged, 2: stem done, 3: layer-1 MFMAs done, 12: end)").c_str(),
-                                   [&] { return launch_stem_l1(dt, q, st, !run.stem_not_persistent); });
-#endif
-                VTI_HIP(c, launch_stem_l1(dt, q, st, !run.stem_not_persistent), "stem + layer 1");
-                break;
-            }
-            if (op.fold >= 0) {         // ConvTranspose2d(2,2) + 3x3 + fused 1x1 as four 2x2 convs on the low-resolution map
-                const ConvRow& ru = P.convs[op.fold];
-                ConvParams q;
-                memset(&q, 0, sizeof q);
-                q.in = buf_ptr(c, op.in.buf, input, proto); q.B = B; q.Hin = ru.h_in; q.Win = ru.w_in; q.Hout = ru.h_in; q.Wout = ru.w_in;
-                q.Cin = ru.c1; q.in_ld = ib.C; q.in_coff = op.in.coff; q.Cout = g.gemm_n; q.act = 1; q.fold = 1; q.pk_lin = run.pk_linear_map;
-                q.TH = g.TH; q.TW = g.TW; q.tiles_y = (q.Hout + g.TH - 1) / g.TH; q.tiles_x = (q.Wout + g.TW - 1) / g.TW; q.WN = 4; q.nt = g.threads;
-                q.nchunks = g.nchunks; q.ntiles_n = g.ntiles_n;
-                q.pw_magic = (unsigned)((0x100000000ull + (unsigned)(g.TW + 2) - 1) / (unsigned)(g.TW + 2));
-                q.tw_magic = (unsigned)((0x100000000ull + (unsigned)g.TW - 1) / (unsigned)g.TW);
-                q.wpk = (const char*)c->d_wpk + g.wpk_off; q.bias = c->d_bias + g.bias_off; q.wpk_bytes = (unsigned)packed_fold_bytes(g);
-                q.alpha = c->alpha[op.conv]; q.alpha0 = 1.f;
-                fill_stage2(c, q, op, input, proto);
-                if (g.pk) {             // persistent schedule: composed weights resident in LDS, tiles walked per XCD
-                    q.pk = 1; q.pk_depth = g.pk_depth; q.in_bytes = (unsigned)((size_t)B * q.Hin * q.Win * q.in_ld * P.esize);
-                    q.pk_tiles = B * q.tiles_y * q.tiles_x;
-                    q.pk_wgs = pk_grid(q.pk_tiles, 1, 1, run.pk_max_wgs);
-                    q.pk_xcd = q.pk_wgs >= 8 ? 1 : 0;
-                    VTI_HIP(c, launch_conv_pk_fold(dt, q, g.lds, st), r.name.c_str());
-                } else {
-                    VTI_HIP(c, launch_convfold(dt, q, g.lds, st), r.name.c_str());
-                }
-                break;
-            }
-            ConvParams p;
-            fill_conv_params(run, P.esize, p, r, g, B, buf_ptr(c, op.in.buf, input, proto), ib.C, op.in.coff,
-                             buf_ptr(c, op.out.buf, input, proto), ob.C, op.out.coff,
-                             op.has_res ? buf_ptr(c, op.res.buf, input, proto) : nullptr,
-                             op.has_res ? P.bufs[op.res.buf].C : 0, op.res.coff,
-                             (const char*)c->d_wpk + g.wpk_off, c->d_bias + g.bias_off, op.out_f32, swap_rb);
-            p.alpha = c->alpha[op.conv]; p.alpha0 = 1.f;
-            p.pk_stagger *= stagger_units(run, dt);
-            p.alpha2 = op.pair >= 0 ? c->alpha[op.pair] : 1.f;
-            if (op.fused >= 0) {
-                fill_stage2(c, p, op, input, proto);
-                if (op.pred_mode) {     // class / coefficient towers write their rows of the anchor-major pred [B, A, no] directly
-                    const int no = 4 + P.desc.nc + P.desc.nm;
-                    p.out2 = pred + (size_t)op.pred_a0 * no;
-                    p.out2_ld = no; p.out2_coff = op.pred_cbase; p.out2_f32 = 1; p.out2_bstride = P.num_anchors;
-                    p.act2 = op.pred_mode == 2 ? 2 : op.pred_mode == 3 ? 3 : 0;
-                    p.dfl_stride = (float)op.dfl_stride;
-                    p.scalar_store2 = scalar_store(g.gemm_n2, no, op.pred_cbase);
-                    p.best = (op.pred_mode == 2 && best) ? best + (size_t)op.pred_a0 * 2 : nullptr;     // class towers: (max, class) per anchor
-                }
-            }
-            if (op.pair >= 0) {         // fused Bottleneck: second conv's weights; p.out / p.res already are the second conv's views
-                p.w2 = (const char*)c->d_wpk + g.wpk_off2;
-                p.bias2 = c->d_bias + g.bias_off2;
-                if (p.pk != 3) return fail(c, VTI_ERR_UNSUPPORTED, "fused bottleneck needs the persistent kernel (tensor too large?)");
-                if (op.tail >= 0) {     // + the C2f's closing 1x1: the patch carries [y0 | y1] (in_coff = y0's offset), y2 is not stored
-                    const Buf& o2 = P.bufs[op.out2.buf];
-                    if (dt == VTI_F16) p.in_coff -= r.c1;          // fp16: one 64-byte slot = [y0 | y1]; h2: the patch stays y1, y0 is read directly
-                    p.alpha0 = c->alpha[op.tail];
-                    p.w0 = (const char*)c->d_wpk + g.wpk_off3; p.bias0 = c->d_bias + g.bias_off3;
-                    p.out2 = buf_ptr(c, op.out2.buf, input, proto); p.out2_ld = o2.C; p.out2_coff = op.out2.coff; p.Cout2 = P.convs[op.tail].c2;
-                    const size_t o2b = (size_t)B * p.Hout * p.Wout * o2.C * P.esize;
-                    if (o2b >= 0x80000000ull) return fail(c, VTI_ERR_UNSUPPORTED, "fused bottleneck tail: output tensor too large");
-                    p.out2_bytes = (unsigned)o2b;
-                }
-            }
-            if (op.up_C > 0) {
-                const Buf& ub = P.bufs[op.up_src.buf];
-                p.in2 = buf_ptr(c, op.up_src.buf, input, proto); p.in2_ld = ub.C; p.in2_coff = op.up_src.coff; p.up_C = op.up_C;
-                p.in2_bytes = (unsigned)((size_t)B * ub.H * ub.W * ub.C * P.esize);
-                if (p.pk != 2) return fail(c, VTI_ERR_UNSUPPORTED, "folded upsample needs the persistent 1x1 kernel (tensor too large?)");
-            }
-            const bool deconv = r.kind == 2;
-            const int ks = deconv ? 1 : r.k, s = deconv ? 1 : r.s;
-#ifdef VTI_STAMPS
-            // diagnostic build: stamp this op of the forward (fused ops included); the stamped launch is the op's launch
-            if (r.name == run.stamp_op &&
-                stamped_launch(p, conv_workgroups(p, g, B), p.pk != 0, st, ("[stamps] op " + r.name).c_str(),
-                               [&] { return launch_conv(dt, ks, s, g.NREP, op.kind == OP_CONV0 ? 1 : 0, p, g.lds, st); }))
-                break;
-#endif
-            VTI_HIP(c, launch_conv(dt, ks, s, g.NREP, op.kind == OP_CONV0 ? 1 : 0, p, g.lds, st), r.name.c_str());
-            break;
+        if (op.kind == OP_FORK || op.kind == OP_JOIN) {       // a side lane starts after / is waited for by the caller's stream
+            if (!c->multi_stream) continue;
+            const bool fork = op.kind == OP_FORK;
+            hipEvent_t ev = fork ? c->ev_fork[op.lane] : c->ev_join[op.lane];
+            VTI_HIP(c, hipEventRecord(ev, fork ? main_st : c->side[op.lane]), fork ? "fork record" : "join record");
+            VTI_HIP(c, hipStreamWaitEvent(fork ? c->side[op.lane] : main_st, ev, 0), fork ? "fork wait" : "join wait");
+            continue;
         }
-        case OP_POOL: {
-            const Buf& ib = P.bufs[op.in.buf];
-            PoolParams p;
-            p.in = buf_ptr(c, op.in.buf, input, proto); p.out = p.in ? (void*)p.in : nullptr;
-            p.B = B; p.H = ib.H; p.W = ib.W; p.C = op.in.C; p.ld = ib.C; p.in_coff = op.in.coff; p.out_coff = op.out.coff;
-            VTI_HIP(c, launch_sppf_pool(dt, p, st), "sppf pool");
-            break;
-        }
-        case OP_UP2: {
-            const Buf& ib = P.bufs[op.in.buf];
-            const Buf& ob = P.bufs[op.out.buf];
-            Up2Params p;
-            p.in = buf_ptr(c, op.in.buf, input, proto); p.out = buf_ptr(c, op.out.buf, input, proto);
-            p.B = B; p.H = ib.H; p.W = ib.W; p.C = op.in.C; p.in_ld = ib.C; p.in_coff = op.in.coff;
-            p.out_ld = ob.C; p.out_coff = op.out.coff;
-            VTI_HIP(c, launch_upsample2x(dt, p, st), "upsample2x");
-            break;
-        }
-        case OP_DECODE: {
-            DecodeParams p;
-            memset(&p, 0, sizeof p);
-            int a0 = 0;
-            for (int l = 0; l < 3; ++l) {
-                const Level& lv = P.levels[l];
-                p.box[l] = (const float*)(c->ws + P.bufs[lv.box_buf].off);
-                p.cls[l] = (const float*)(c->ws + P.bufs[lv.cls_buf].off);
-                p.mc[l] = (const float*)(c->ws + P.bufs[lv.mc_buf].off);
-                p.H[l] = lv.H; p.W[l] = lv.W; p.stride[l] = lv.stride; p.a0[l] = a0;
-                a0 += lv.H * lv.W;
-            }
-            p.B = B; p.A = P.num_anchors; p.nc = P.desc.nc; p.nm = P.desc.nm; p.reg_max = P.desc.reg_max;
-            p.pred = pred;
-            if (P.pred_scatter) VTI_HIP(c, launch_box_decode(p, st), "box decode");
-            else VTI_HIP(c, launch_decode(p, st), "decode");
-            break;
-        }
-        }
+        if (const char* e = fill_launch(P, op, B, swap_rb, run, bind, L)) return fail(c, VTI_ERR_UNSUPPORTED, e);
+        const bool stamp = L.name && run.stamp_op == L.name;        // diagnostic build only
+        VTI_HIP(c, issue(L, (c->multi_stream && op.lane > 0) ? c->side[op.lane] : main_st, stamp ? ("[stamps] op " + op_label(P, op)).c_str() : nullptr),
+                launch_what(L));
     }
     // a plan whose class towers do not write pred themselves (VTI_NO_SCATTER ...) derives the pairs from the finished rows
     if (best && !P.pred_scatter)
@@ -2211,7 +1987,7 @@ int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void
     const View& v = c->plan.conv_out[i];
     if (v.buf < 0) return fail(c, VTI_ERR_UNSUPPORTED, "vti_debug_conv_output: this conv is fused into the next one; its output is never materialised");
     const Buf& b = c->plan.bufs[v.buf];
-    const void* src = buf_ptr(c, v.buf, c->last_input, c->last_proto);
+    const void* src = buf_ptr(c->plan, bindings_of(c, c->last_input, nullptr, c->last_proto, nullptr), v.buf);
     if (!src) return fail(c, VTI_ERR_STATE, "vti_debug_conv_output: run vti_forward first");
     const int is_f32 = (b.elem == EL_F32 || (b.elem == EL_T && c->plan.desc.dtype == VTI_F32)) ? 1
                        : (b.elem == EL_T && c->plan.desc.dtype == VTI_H2) ? 2 : 0;      // 2: h2 pairs
@@ -2256,21 +2032,17 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
     if (e == hipSuccess) e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) {
-        ConvParams p;
-        fill_conv_params(opt.run, dtype == VTI_F16 ? 2 : 4, p, r, g, B, dev_in, in_ld, in_coff, dev_out, out_ld, out_coff, dev_res, res_ld, res_coff, d_w, d_b,
-                         out_f32 != 0, swap_rb);
-        p.alpha = alpha; p.alpha2 = p.alpha0 = 1.f;
-        p.pk_stagger *= stagger_units(opt.run, dtype);
-        const int ks = kind == 2 ? 1 : k, ss = kind == 2 ? 1 : s;
+        LaunchRec L;
+        conv_record(opt.run, dtype, r, g, B, dev_in, in_ld, in_coff, dev_out, out_ld, out_coff, dev_res, res_ld, res_coff, d_w, d_b, alpha,
+                    out_f32 != 0, swap_rb, L);
 #ifdef VTI_STAMPS
         // diagnostic build: one stamped launch after a warm-up (caches, icache), medians of the phase intervals to stderr
-        (void)launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);
-        stamped_launch(p, conv_workgroups(p, g, B), p.pk != 0, st, nullptr,
-                       [&] { return launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st); });
+        (void)issue(L, st);
+        (void)issue(L, st, "");
 #endif
-        e = launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);   // warm-up / the checked run
+        e = issue(L, st);   // warm-up / the checked run
         if (e == hipSuccess) e = hipEventRecord(e0, st);
-        for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_conv(dtype, ks, ss, g.NREP, conv0 ? 1 : 0, p, g.lds, st);
+        for (int i = 1; i < iters && e == hipSuccess; ++i) e = issue(L, st);
         if (e == hipSuccess) e = hipEventRecord(e1, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         float ms = 0.f;

@@ -271,6 +271,36 @@ struct DecodeParams {
 hipError_t launch_decode(const DecodeParams& p, hipStream_t st);
 hipError_t launch_box_decode(const DecodeParams& p, hipStream_t st);   // DFL + dist2bbox only (pred_scatter plans)
 
+// ---- launch parameters (launch.cpp; host only, nothing there sees a context, a stream or an event) ----------------------------
+// The plan decides per conv, once: kernel family, tile, waves, LDS, ring depth, weight offsets (ConvCfg).  Per call, from B, swap_rb,
+// the RunOptions and the tensors of that call: the tile counts, the persistent grid, the byte ranges with their 2^31 fallback, the
+// pointers -- a LaunchRec per op, built on every call.
+struct Bindings {            // the device tensors the parameter blocks of one forward point into
+    char* ws; const void* wpk; const float* bias;      // workspace, packed weights, biases
+    const float* alpha;                                // per conv: accumulator scale of its packed weights (host array)
+    const void* input; float* pred; void* proto; float* best;      // the caller's (best: may be null)
+};
+enum Launcher { LAUNCH_STEM_L1, LAUNCH_CONV, LAUNCH_CONVFOLD, LAUNCH_CONV_PK_FOLD, LAUNCH_POOL, LAUNCH_UP2, LAUNCH_DECODE, LAUNCH_BOX_DECODE };
+struct LaunchRec {           // one launch: the launcher, its selector arguments (those it takes), its block
+    Launcher fn;
+    const char* name;        // conv launchers: the op's conv (names the op in an error and for VTI_STAMP_OP), else null
+    int dtype, ks, stride, nrep, mode;
+    size_t lds;
+    bool persistent;         // launch_stem_l1's
+    ConvParams conv; PoolParams pool; Up2Params up2; DecodeParams dec;      // the one `fn` takes is filled
+};
+// The record of one op (not OP_FORK / OP_JOIN); the text of a VTI_ERR_UNSUPPORTED refusal when the op cannot run, else nullptr
+const char* fill_launch(const Plan& P, const Op& op, int B, int swap_rb, const RunOptions& run, const Bindings& b, LaunchRec& L);
+// The plain launch_conv record of one row with one configuration (vti_debug_conv2d; the base of the forward's conv ops)
+void conv_record(const RunOptions& run, int dtype, const ConvRow& r, const ConvCfg& g, int B, const void* in, int in_ld, int in_coff,
+                 void* out, int out_ld, int out_coff, const void* res, int res_ld, int res_coff, const void* wpk, const float* bias,
+                 float alpha, bool out_f32, int swap_rb, LaunchRec& L);
+void* buf_ptr(const Plan& P, const Bindings& b, int buf);           // where a buffer of the plan lives: input, proto or workspace
+std::string op_label(const Plan& P, const Op& op);                  // "model.0 + model.1 + model.2.cv1": VTI_LIST_OPS, stamped launches
+const char* launcher_name(Launcher fn);
+size_t launch_workgroups(const LaunchRec& L);                       // of a conv launcher's record (diagnostic build: stamp slots)
+void conv_geometry(const Plan& P, int i, vti_conv_info* o);         // vti_conv_at: tile, waves, nrep, LDS and flags of conv i's launch
+
 hipError_t launch_debug_nchw(int elem_is_f32, const void* src, int B, int H, int W, int C, int ld, int coff,
                              float* dst, hipStream_t st);
 
