@@ -722,6 +722,36 @@ __device__ __forceinline__ void mask_slot_owner(const int* __restrict__ offsets,
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= slot) lo = mid; else hi = mid; }
     b = lo; inst = slot - offsets[lo];
 }
+// Start of XCD x's range of the frame-major (frame, tile) list when the list is cut by WORK.  Item (b, t) weighs w_b = n_b + MASK_ITEM_C:
+// n_b = off[b + 1] - off[b] with off = min(offsets, capacity) are the frame's instances that own a slot (the list build and, on
+// average, the listed instances of an item grow with it) and the constant stands for what an item costs whatever it lists
+// (prototype footprint, one list round).  Its exclusive cumulative weight is tiles * (off[b] + C b) + t * w_b -- `offsets` is the
+// prefix sum it needs -- and the total is Wt = tiles * (off[B] + C B).  XCD x owns the items whose cumulative weight lies in
+// [x Wt / 8, (x + 1) Wt / 8): the value returned is the number of items whose cumulative weight is below ceil(x Wt / 8) -- one
+// binary search over the prefix sums and one division, the same in every workgroup.  The ranges of x = 0 .. 7 are disjoint and
+// cover the list (bound(0) = 0, bound(8) = n); a boundary may fall inside a frame, and a range may be empty.
+// C = 32: measured on the bench's detections (profiles/r05_post_balance.txt: 0 / 8 / 16 / 24 / 32 / 40 / 48 / 64 ->
+// 268 / 234 / 222 / 200 / 200 / 210 / 217 / 221 us against 259 us for equal item counts); tools/post_balance.py restates the rule.
+#ifndef MASK_ITEM_C
+#define MASK_ITEM_C 32
+#endif
+__device__ __forceinline__ int mask_weight_bound(const int* __restrict__ offsets, int B, int tiles, int capacity, int x, int n) {
+    constexpr int C = MASK_ITEM_C;
+    static_assert(C >= 0, "weights are not negative");
+    if (x <= 0) return 0;
+    if (x >= 8) return n;
+    const long long wt = (long long)tiles * ((long long)min(offsets[B], capacity) + (long long)C * B);
+    const long long thr = (wt * x + 7) >> 3;                               // items with cumulative weight < thr come before the boundary
+    int lo = 0, hi = B;                                                    // largest b with tiles * (off[b] + C b) < thr (or 0)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)tiles * ((long long)min(offsets[mid], capacity) + (long long)C * mid) < thr) lo = mid; else hi = mid;
+    }
+    const int off_b = min(offsets[lo], capacity), w_b = min(offsets[lo + 1], capacity) - off_b + C;
+    const long long rest = thr - (long long)tiles * ((long long)off_b + (long long)C * lo);      // >= 0
+    const int cnt = w_b <= 0 ? tiles : (int)min((long long)tiles, (rest + w_b - 1) / w_b);       // w_b = 0: weightless items, anywhere
+    return lo * tiles + cnt;
+}
 // tiles [tx0, tx1] x [ty0, ty1] that get a work item: a tile can be non-zero only if one of its bilinear taps lies inside the box
 // (in 1/4-res pixels); the box is expanded by 2 low-res pixels (= 8 output px) to be safe on every side.
 __device__ __forceinline__ bool mask_tile_rect(const float* __restrict__ d, int H, int W, int& tx0, int& tx1, int& ty0, int& ty1) {
@@ -1099,8 +1129,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 3) void masks_group_kerne
     // XCD x (= blockIdx & 7) walks its own contiguous eighth of the frame-major list, round-robin over its workgroups: at any
     // time an XCD works on about one frame, whose prototypes and dets rows sit in ONE L2
     const int nx = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jx = (int)blockIdx.x >> 3;
-    const int per = (n + 7) >> 3;
-    const int it1 = min(n, (xcd + 1) * per);
+    // The eighths are eighths of the WORK, not of the item count (mask_weight_bound): with equal item counts -- eight frames per XCD
+    // at B = 64 -- the XCD that owned the crowded frames finished last while the other seven idled.
+    const int it0 = mask_weight_bound(offsets, B, tiles, capacity, xcd, n);
+    const int it1 = mask_weight_bound(offsets, B, tiles, capacity, xcd + 1, n);
     const float wr = (float)((double)Wp / (double)W), hr = (float)((double)Hp / (double)H);       // as in masks_kernel
     const float sh = (float)Hp / (float)H, sw = (float)Wp / (float)W;
     const float thr = mode == VTI_MASK_SIGMOID ? 0.5f : 0.0f;
@@ -1118,7 +1150,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 3) void masks_group_kerne
     unsigned long long macc[6] = {0, 0, 0, 0, 0, 0}, mprev, mitems = 0, mpairs = 0;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(mprev)::"memory");
 #endif
-    for (int it = xcd * per + jx; it < it1; it += nx) {
+    for (int it = it0 + jx; it < it1; it += nx) {
         const int b = it / tiles, t = it - b * tiles;
         const int ty = t / tiles_x, tx = t - ty * tiles_x;
         const int y0 = ty * MT, x0 = tx * MT;
