@@ -892,6 +892,64 @@ VTI_NMS_TABLE_API int32_t vti_pack_nms_table(vti_ctx* ctx, const vti_nms_params*
 VTI_NMS_TABLE_API int32_t vti_set_nms_table(vti_ctx* ctx, const void* host_table, const void* dev_table,
                                             int32_t n_rows, const int32_t* dev_row_of_frame);
 
+/* ---- predict on a window of each frame: results in frame pixels ------------------------------------------------------------------ */
+/* The reference measures inside a region of interest (config.py roi, measurement.py:249-272) and drops every detection outside it,
+ * yet letterboxes the whole frame.  These calls run the pipeline on a WINDOW (x0, y0, w, h) of each frame, read in place from the
+ * frame buffer of vti_pack_frames' layout, and return everything in FRAME pixels.  They are defined by the calls on contiguous crops:
+ * with crop_b = frame_b[y0:y0+h, x0:x0+w], T_crop the frame table of the crops and T_full that of the full frames on the same canvas,
+ *   canvas, pred, proto, dets, counts   == vti_letterbox_frames / vti_predict_frames_native on (crops, T_crop), byte for byte;
+ *   xyxy                                 == vti_scale_boxes_frames(T_crop) + (float)(x0, y0, x0, y0), one f32 add per coordinate
+ *                                           (rows at or past counts[b] stay zero);
+ *   offsets, mask_bases, slot layout, liveness by capacity_bytes == vti_masks_native_frames on T_full; bit (y, x) of a live slot is
+ *                                           bit (y - y0, x - x0) of the crop's mask inside the window and 0 elsewhere (the crop to the
+ *                                           box uses the window-px box, not the shifted one); live slots are written completely, no
+ *                                           byte after the last live slot is touched.
+ * With the window (0, 0, W0, H0) for every frame every output byte equals vti_predict_frames_native on T_full.  So every consumer of
+ * native = 1 rows or dev_mask_bases (vti_measure_frames_native, vti_annotate_frames, vti_mask_polygons_frames, vti_overlay_frames)
+ * takes the result unchanged, together with T_full.
+ * Marks the entry points of the window family; libvti.so exports them as it does every other. */
+#define VTI_WINDOWS_API
+/* Host only: bytes of a window table of B frames (0 when B < 1): a header and one row per frame. */
+VTI_WINDOWS_API int64_t vti_window_table_bytes(int32_t B);
+/* Host only: vti_pack_frames' checks of the B frames (H0, W0, byte_offset, total_bytes, the canvas H x W), then of each window
+ * windows[b] = {x0, y0, w, h}: x0, y0 >= 0, w, h >= 1, x0 + w <= W0[b], y0 + h <= H0[b], and the window letterboxed onto the canvas
+ * not below 1 px.  VTI_ERR_ARG with the index of the first failing frame in vti_last_error.  Writes the table (nbytes >=
+ * vti_window_table_bytes(B)); equal inputs give equal bytes; the format is private to the library build.  ctx may be NULL (it
+ * receives the error text); with a ctx, B above its max_batch is refused here, as every *_windows call would refuse the table. */
+VTI_WINDOWS_API int32_t vti_pack_windows(vti_ctx* ctx, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0,
+                                         const int64_t* byte_offset, const int32_t* windows, int32_t B, int64_t total_bytes,
+                                         void* host_table, size_t nbytes);
+/* Host only: what row b holds.  out_i32[12] = {h, w, new_h, new_w, top, left, offset lo, offset hi, x0, y0, H0, W0}: the first eight
+ * and out_f64[5] (may be NULL) are what vti_frame_table_info reports for the contiguous crop, with `offset` the byte of the window's
+ * first pixel in the frame buffer -- for a whole-frame window exactly the frame's own row.  b = -1: the header, as
+ * vti_frame_table_info gives it (max_H0, max_W0 of the full frames), the last four zero. */
+VTI_WINDOWS_API int32_t vti_window_table_info(const void* host_table, int32_t b, int32_t out_i32[12], double out_f64[5]);
+/* The *_windows calls take the table twice, as every *_frames call does: host_table is revalidated row by row before the first HIP
+ * call (VTI_ERR_ARG naming the frame), dev_table is its device copy (16-byte aligned, trusted to hold the same bytes).
+ * dev_frames: the frame buffer the table was packed for (16-byte aligned); never written; nothing outside a frame is read, and
+ * bytes right of a window inside its frame only where their resize weight is 0.  dev_input u8 [B,H,W,3], 4-byte aligned. */
+VTI_WINDOWS_API int32_t vti_letterbox_windows(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table,
+                                              int32_t B, uint8_t* dev_input, void* stream);
+/* dev_xyxy f32 [B, max_det, 4] (16-byte aligned): the boxes in FRAME px. */
+VTI_WINDOWS_API int32_t vti_scale_boxes_windows(vti_ctx* ctx, const float* dev_dets, const int32_t* dev_counts, const void* host_table,
+                                                const void* dev_table, int32_t B, int32_t max_det, float* dev_xyxy, void* stream);
+/* Host only: vti_mask_native_frames_bytes of the full frames of the table (0 on a bad argument). */
+VTI_WINDOWS_API int64_t vti_mask_native_windows_bytes(const vti_ctx* ctx, const void* host_table, int32_t max_det);
+/* vti_masks_native_frames' arguments without dev_xyxy: the stage computes each box in window px from dev_dets with scale_boxes' own
+ * expression.  packing must be VTI_PACK_BITS. */
+VTI_WINDOWS_API int32_t vti_masks_native_windows(vti_ctx* ctx, const float* dev_dets, const int32_t* dev_counts, const void* dev_proto,
+                                                 const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t mode,
+                                                 int32_t packing, uint8_t* dev_masks, int64_t capacity_bytes, int32_t* dev_offsets,
+                                                 int64_t* dev_mask_bases, void* stream);
+/* vti_predict_frames_native's arguments with the window table in place of the frame table: letterbox, scored forward, NMS (a set NMS
+ * table applies), scale boxes, masks on one stream with no host synchronisation. */
+VTI_WINDOWS_API int32_t vti_predict_windows(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table, const void* dev_table,
+                                            int32_t B, int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic,
+                                            int32_t mask_mode, int32_t packing, uint8_t* dev_input_scratch, float* dev_pred,
+                                            void* dev_proto, float* dev_dets, int32_t* dev_counts, uint8_t* dev_masks,
+                                            int64_t capacity_bytes, int32_t* dev_offsets, int64_t* dev_mask_bases, float* dev_xyxy,
+                                            void* stream);
+
 /* ---- JPEG files -> frames on device (cap.read() of a motion-JPEG camera, cv2.imread, Ultralytics' file sources) ----------------- */
 /* n files -> n frames u8 [H0,W0,3], byte for byte the package's jpeg.decode, which is pinned to libjpeg-turbo's output with its
  * defaults (JDCT_ISLOW, fancy upsampling): jdhuff.c, jidctint.c with the dequantisation inside, jdsample.c, jdcolor.c; integer

@@ -182,6 +182,15 @@ SIGNATURES = {
     "vti_nms_table_bytes": (_I64, [_I32]),
     "vti_pack_nms_table": (_I32, [_P, C.POINTER(VtiNmsParams), _I32, _P, _SZ]),
     "vti_set_nms_table": (_I32, [_P, _P, _P, _I32, _P]),
+    "vti_window_table_bytes": (_I64, [_I32]),
+    "vti_pack_windows": (_I32, [_P, _I32, _I32, _P, _P, _P, _P, _I32, _I64, _P, _SZ]),
+    "vti_window_table_info": (_I32, [_P, _I32, _P, _P]),
+    "vti_letterbox_windows": (_I32, [_P, _P, _P, _P, _I32, _P, _P]),
+    "vti_scale_boxes_windows": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "vti_mask_native_windows_bytes": (_I64, [_P, _P, _I32]),
+    "vti_masks_native_windows": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P]),
+    "vti_predict_windows": (_I32, [_P, _P, _P, _P, _I32, _I32, _F, _D, _I32, _I32, _I32, _I32,
+                                   _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "vti_decode_jpeg_table_bytes": (_I64, [_I32]),
     "vti_decode_jpeg_plan": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     "vti_decode_jpeg": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),

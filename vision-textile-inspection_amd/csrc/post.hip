@@ -50,7 +50,11 @@ __device__ __forceinline__ LinTap lin_tap(int d, int ssize, double scale, bool h
 // A workgroup owns LB_ROWS canvas rows of one frame.  The resize branch (copy through, exact-2x box mean, bilinear) is chosen per
 // frame, so it is uniform over the workgroup; pad rows and pad pixels are stored without touching the source.  The frame's geometry
 // comes from the launch arguments (TABLE = false: vti_letterbox, B equal frames back to back) or from row blockIdx.y of the frame
-// table (vti_letterbox_frames); the arithmetic is the same, so both write the same bytes.
+// table (vti_letterbox_frames); the arithmetic is the same, so both write the same bytes.  FORM == LB_WINDOWS (vti_letterbox_windows):
+// row blockIdx.y of the window table.  The source is then a window of a frame: its geometry is the crop's, its first byte lies at
+// 3 (y0 W0 + x0) inside the frame (any alignment), its rows are 3 W0 bytes of the FRAME apart, and the load clamp `last` is the
+// FRAME's final dword.  The copy and box-mean branches read the window's own bytes only; the bilinear tap pair may load bytes right
+// of the window, inside the frame, where their weight is 0 (as it loads the next row's at a frame's right edge).
 //   copy / box mean: a thread owns four canvas columns -- 12 output bytes, one store per row -- and reads its 12 / 2 x 24 source
 //     bytes as whole dwords where every address is a multiple of 4 (else byte by byte).
 //   bilinear: a thread owns the columns tid, tid + 256, ... of a 1024-column chunk, so that the lanes of a wave read neighbouring
@@ -75,16 +79,20 @@ __device__ __forceinline__ void lb_six(uintptr_t p, uintptr_t last, unsigned& lo
     hi = __funnelshift_r(d1, d2, sh);
 }
 
-template <bool TABLE>
+enum { LB_ONE = 0, LB_TABLE = 1, LB_WINDOWS = 2 };
+template <int FORM>
 __global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __restrict__ frames, FrameRow one,
-                                                             const FrameRow* __restrict__ table, uint8_t* __restrict__ out,
+                                                             const void* __restrict__ table, uint8_t* __restrict__ out,
                                                              int H, int W) {
+    constexpr bool TABLE = FORM != LB_ONE;
     __shared__ int4 s_ty[LB_ROWS];
     __shared__ __attribute__((aligned(16))) uint8_t s_px[LB_ROWS][LB_CHUNK * 3];
     const int tid = threadIdx.x, b = blockIdx.y, y0 = blockIdx.x * LB_ROWS;
-    const FrameRow r = TABLE ? table[b] : one;
+    const FrameRow r = FORM == LB_WINDOWS ? ((const WindowRow*)table)[b].crop : (FORM == LB_TABLE ? ((const FrameRow*)table)[b] : one);
     const int H0 = r.H0, W0 = r.W0, new_h = r.new_h, new_w = r.new_w, top = r.top, left = r.left;
     const uint8_t* src = frames + (TABLE ? (size_t)r.offset : (size_t)b * H0 * W0 * 3);
+    // the source rows' distance in px: the frame's width, not the window's
+    const int PW = FORM == LB_WINDOWS ? ((const WindowRow*)table)[b].W0 : W0;
     const int rows = min(LB_ROWS, H - y0);
     // OpenCV's resize() turns INTER_LINEAR into INTER_AREA when both scales are exactly 2 (hal::resize: is_area_fast &&
     // iscale_x == 2 && iscale_y == 2): the u8 result is the rounded 2x2 box mean, not the bilinear tap pair
@@ -98,7 +106,11 @@ __global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __re
             s_ty[tid] = make_int4(t.s0, t.s1, t.a0, t.a1);
         }
         const bool out16 = ((uintptr_t)out & 15) == 0;
-        const uintptr_t last = ((uintptr_t)src + (size_t)H0 * W0 * 3 - 1) & ~(uintptr_t)3;
+        uintptr_t last = ((uintptr_t)src + (size_t)H0 * W0 * 3 - 1) & ~(uintptr_t)3;
+        if constexpr (FORM == LB_WINDOWS) {                     // the FRAME's final dword, not the window's
+            const WindowRow& wr = ((const WindowRow*)table)[b];
+            last = ((uintptr_t)frames + (size_t)wr.frame_offset + (size_t)wr.H0 * wr.W0 * 3 - 1) & ~(uintptr_t)3;
+        }
         for (int xb = 0; xb < W; xb += LB_CHUNK) {
             const int ncol = min(LB_CHUNK, W - xb);
             int xs0[4], xa0[4], xa1[4];
@@ -115,7 +127,7 @@ __global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __re
                 const int dy = y0 + rr - top;
                 const bool row_in = dy >= 0 && dy < new_h;
                 const int4 ty = s_ty[rr];
-                const uintptr_t r0 = (uintptr_t)src + (size_t)ty.x * W0 * 3, r1 = (uintptr_t)src + (size_t)ty.y * W0 * 3;
+                const uintptr_t r0 = (uintptr_t)src + (size_t)ty.x * PW * 3, r1 = (uintptr_t)src + (size_t)ty.y * PW * 3;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     if (tid + 256 * k >= ncol) continue;
@@ -151,7 +163,9 @@ __global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __re
     }
     const bool src4 = ((uintptr_t)src & 3) == 0, out4 = ((uintptr_t)out & 3) == 0;
     // whole-dword source reads where every address is a multiple of 4: copy: (dy * W0 + 4 g - left) * 3; box mean: 12 dy new_w + 6 (4 g - left)
-    const bool wide = src4 && (copy ? ((W0 | left) & 3) == 0 : (left & 1) == 0);
+    // (a window's rows are 3 PW bytes apart and start anywhere: PW must be a multiple of 4 as well)
+    bool wide = src4 && (copy ? ((W0 | left) & 3) == 0 : (left & 1) == 0);
+    if constexpr (FORM == LB_WINDOWS) wide = src4 && (PW & 3) == 0 && (copy ? (left & 3) == 0 : (left & 1) == 0);
     for (int g = tid; g < (W >> 2); g += 256) {
         const int dx0 = 4 * g - left;
         const bool inside = dx0 >= 0 && dx0 + 3 < new_w;
@@ -161,7 +175,7 @@ __global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __re
             unsigned w[3] = {0x72727272u, 0x72727272u, 0x72727272u};          // 114
             if (dy >= 0 && dy < new_h && dx0 + 3 >= 0 && dx0 < new_w) {
                 if (copy) {
-                    const uint8_t* s = src + ((long long)dy * W0 + dx0) * 3;
+                    const uint8_t* s = src + ((long long)dy * PW + dx0) * 3;
                     if (wide && inside) {
                         const unsigned* q = (const unsigned*)s;
                         w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
@@ -174,8 +188,8 @@ __global__ __launch_bounds__(256) void letterbox_rows_kernel(const uint8_t* __re
                         }
                     }
                 } else {
-                    const uint8_t* s0 = src + ((long long)(2 * dy) * W0 + 2 * dx0) * 3;
-                    const uint8_t* s1 = s0 + (size_t)W0 * 3;
+                    const uint8_t* s0 = src + ((long long)(2 * dy) * PW + 2 * dx0) * 3;
+                    const uint8_t* s1 = s0 + (size_t)PW * 3;
                     if (wide && inside) {
                         unsigned q0[6], q1[6];
 #pragma unroll
@@ -213,10 +227,10 @@ hipError_t launch_letterbox(const uint8_t* frames, int B, int H0, int W0, const 
     if (W & 3) return hipErrorInvalidValue;
     const dim3 grid((H + LB_ROWS - 1) / LB_ROWS, B);
     FrameRow one = {};
-    if (table) hipLaunchKernelGGL(letterbox_rows_kernel<true>, grid, dim3(256), 0, st, frames, one, table, out, H, W);
+    if (table) hipLaunchKernelGGL(letterbox_rows_kernel<LB_TABLE>, grid, dim3(256), 0, st, frames, one, (const void*)table, out, H, W);
     else {
         frame_row_fill(H, W, H0, W0, 0, one);
-        hipLaunchKernelGGL(letterbox_rows_kernel<false>, grid, dim3(256), 0, st, frames, one, table, out, H, W);
+        hipLaunchKernelGGL(letterbox_rows_kernel<LB_ONE>, grid, dim3(256), 0, st, frames, one, (const void*)table, out, H, W);
     }
     return hipGetLastError();
 }
@@ -1409,6 +1423,17 @@ __host__ __device__ static inline int native_mask_layout_hd(int Hp, int Wp, int 
 }
 int native_mask_layout(int Hp, int Wp, int H0, int W0, int packing, int out[6]) { return native_mask_layout_hd(Hp, Wp, H0, W0, packing, out); }
 
+// scale_boxes + clip_boxes of one detection row: the letterbox box back in the px of the W0 x H0 image the canvas was made from.
+// scale_boxes_kernel (every form) and the window form of masks_native_kernel share it, so both see the same floats.
+__device__ __forceinline__ float4 scale_box(const float* __restrict__ d, float padx, float pady, float gain, float W0, float H0) {
+    float4 o;
+    o.x = fminf(fmaxf((d[0] - padx) / gain, 0.f), W0);
+    o.y = fminf(fmaxf((d[1] - pady) / gain, 0.f), H0);
+    o.z = fminf(fmaxf((d[2] - padx) / gain, 0.f), W0);
+    o.w = fminf(fmaxf((d[3] - pady) / gain, 0.f), H0);
+    return o;
+}
+
 constexpr int NTW = 64;                 // output tile width in frame px: one wave's 64 lanes, 8 bytes of a bit row
 constexpr int NPTS = 512;               // footprint points per tile (the logits of MG instances: MG x NPTS floats of LDS)
 constexpr int NJ = NPTS / 16 / 4;       // MFMA column tiles per wave
@@ -1429,6 +1454,10 @@ struct NativeMaskParams {
     // FRAMES form only (vti_masks_native_frames): the prologue's per-frame values and the prefix of the frames' tile counts
     const struct NativeFrame* nf;       // [B]
     const int* tile_prefix;             // [B + 1]
+};
+// WINDOWS form (vti_masks_native_windows): and the device window table's rows (the origin, and scale_box's gain and pads)
+struct NativeWindowParams : NativeMaskParams {
+    const WindowRow* wrows;             // [B]
 };
 
 // footprint length bound along one axis for `n` output indices at scale s (see native_span), and the cheaper of the two forms
@@ -1528,7 +1557,12 @@ __global__ __launch_bounds__(256) void mask_clear_bytes_kernel(const long long* 
 //   tile_prefix[b]: the prefix sums of the frames' tile counts ceil(W0 / 64) * ceil(H0 / th) (the static work list),
 //   *live_end: the end of the last live slot (the bases are monotone, so the live slots are a prefix of the slot order).
 // A frame whose size native_geom refuses (the host checked every row, so none) gets no tiles and no live slots.
-__global__ __launch_bounds__(256) void mask_frames_plan_kernel(const int* __restrict__ counts, const FrameRow* __restrict__ rows, int B,
+// WINDOWS (vti_masks_native_windows; `rows` are WindowRows): offsets, bases, the slot layout and liveness are those of the FULL
+// frames, so the buffer is the one vti_masks_native_frames lays out for them; the geometry (cropped grid, scales, tile height)
+// is the WINDOW's, nf[b].H0 / W0 are the window's size, and the tiles are th window rows by one 64-bit word of the FRAME's rows:
+// tiles_x counts the words that [x0, x0 + w) touches.
+template <bool WINDOWS>
+__global__ __launch_bounds__(256) void mask_frames_plan_kernel(const int* __restrict__ counts, const void* __restrict__ rows, int B,
                                                                int max_det, int Hp, int Wp, long long capacity_bytes,
                                                                int* __restrict__ offsets, long long* __restrict__ bases,
                                                                int* __restrict__ tile_prefix, NativeFrame* __restrict__ nf,
@@ -1538,10 +1572,21 @@ __global__ __launch_bounds__(256) void mask_frames_plan_kernel(const int* __rest
     for (int b = threadIdx.x; b < B; b += 256) {
         const int c = counts[b];
         NativeFrame f;
-        f.base = 0; f.H0 = rows[b].H0; f.W0 = rows[b].W0; f.n_live = 0; f.pad = 0;
-        const bool ok = native_geom(Hp, Wp, f.H0, f.W0, VTI_PACK_BITS, f.g) == 0;
-        if (!ok) { f.g = NativeGeom{0, 0, 1, 1, 1.f, 1.f, 1, 0, 0, 0, 0}; f.H0 = f.W0 = 0; }
-        f.tiles_x = (f.W0 + NTW - 1) / NTW;
+        f.base = 0; f.n_live = 0; f.pad = 0;
+        bool ok;
+        if constexpr (WINDOWS) {
+            const WindowRow& w = ((const WindowRow*)rows)[b];
+            f.H0 = w.crop.H0; f.W0 = w.crop.W0;
+            int lay[6];
+            ok = native_geom(Hp, Wp, f.H0, f.W0, VTI_PACK_BITS, f.g) == 0 && native_mask_layout_hd(Hp, Wp, w.H0, w.W0, VTI_PACK_BITS, lay) == 0;
+            if (ok) { f.g.row_bytes = lay[4]; f.g.slot_bytes = lay[5]; }
+            f.tiles_x = ((w.x0 + f.W0 - 1) >> 6) - (w.x0 >> 6) + 1;
+        } else {
+            f.H0 = ((const FrameRow*)rows)[b].H0; f.W0 = ((const FrameRow*)rows)[b].W0;
+            ok = native_geom(Hp, Wp, f.H0, f.W0, VTI_PACK_BITS, f.g) == 0;
+            f.tiles_x = (f.W0 + NTW - 1) / NTW;
+        }
+        if (!ok) { f.g = NativeGeom{0, 0, 1, 1, 1.f, 1.f, 1, 0, 0, 0, 0}; f.H0 = f.W0 = 0; f.tiles_x = 0; }
         nf[b] = f;
         s_cnt[b] = c < 0 ? 0 : (c > max_det ? max_det : c);
         s_slot[b] = f.g.slot_bytes;
@@ -1574,8 +1619,15 @@ __global__ __launch_bounds__(256) void mask_frames_plan_kernel(const int* __rest
 //      prototypes, the split-coefficient fp16 pair for fp16 ones), (sigmoid,) logits -> LDS,
 //   4. bilinear upsample (torch's fp32 taps and weights, its evaluation order), crop, threshold: a wave takes 16-row pieces of one
 //      instance, a lane is a column; bits: each row's ballot is 8 bytes, gathered into lane r and stored by 16 lanes at once.
-template <typename T, bool FRAMES = false>
-__global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p) {
+// WINDOWS (a FRAMES form; vti_masks_native_windows): every coordinate above is in WINDOW px -- taps, scales, crop and threshold are
+// those of the contiguous crop -- and only the stores know the frame: window row r lands in frame row y0 + r of the window origin (x0, y0), and a tile's 64 lanes
+// are the bits of ONE 64-bit word of the frame's rows, so lane l is window column 64 word - x0 + l.  The first tile starts at a
+// negative window column and the last may run past the window: such lanes contribute 0 bits, and the footprint is that of the
+// columns [xl, xl + ncols) that do lie in the window.  Each word keeps one writer and is stored whole.  The box is the window-px one,
+// recomputed from the detection row with scale_box (not the shifted frame-px box: the f32 add may move an edge across a px centre).
+template <typename T, bool FRAMES = false, bool WINDOWS = false>
+__global__ __launch_bounds__(256, 2) void masks_native_kernel(typename std::conditional<WINDOWS, NativeWindowParams, NativeMaskParams>::type p) {
+    static_assert(FRAMES || !WINDOWS, "the window form is a FRAMES form");
     constexpr bool F16 = sizeof(T) == 2;
     constexpr int ROW = 6 + 32;
     typedef typename std::conditional<F16, half8, f32x4>::type opv;
@@ -1619,10 +1671,20 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
             if (n_b <= 0) continue;                                        // block-uniform
         }
         const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        const int y0 = ty * th, x0 = tx * NTW;
-        const int ncols = min(NTW, W0 - x0), nrows = min(th, H0 - y0);
+        // x0: the column of lane 0; xl: the tile's first column inside the image; word: the 8-byte piece of the row the tile stores;
+        // oy: the frame row of image row 0 (the non-window forms: x0 == xl == 64 word, oy == 0)
+        int ox = 0, oy = 0;     // the window origin
+        float wpadx = 0.f, wpady = 0.f, wgain = 1.f;
+        if constexpr (WINDOWS) {
+            const WindowRow& w = p.wrows[b];
+            ox = w.x0; oy = w.y0; wpadx = w.crop.padx; wpady = w.crop.pady; wgain = w.crop.gain;
+        }
+        const int word = WINDOWS ? (ox >> 6) + tx : tx;
+        const int y0 = ty * th, x0 = WINDOWS ? word * NTW - ox : tx * NTW;
+        const int xl = WINDOWS ? max(x0, 0) : x0;
+        const int ncols = WINDOWS ? min(x0 + NTW, W0) - xl : min(NTW, W0 - x0), nrows = min(th, H0 - y0);
         int fcb, fw, frb, fh;
-        native_span(x0, ncols, col_contig, sx, inW, fcb, fw);
+        native_span(xl, ncols, col_contig, sx, inW, fcb, fw);
         native_span(y0, nrows, row_contig, sy, inH, frb, fh);
         if (fw * fh > NPTS) fh = NPTS / fw;                                // never (the launcher's bound); keeps `low` in range
         const int npts = fw * fh;
@@ -1636,22 +1698,23 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
                 pt = pt < npts ? pt : npts - 1;                            // past the footprint: a valid address, never stored
                 const int fr = pt / fw, fc = pt - fr * fw;
                 const int py = top + native_src(fr, y0, row_contig, frb, sy, inH);
-                const int px = left + native_src(fc, x0, col_contig, fcb, sx, inW);
+                const int px = left + native_src(fc, xl, col_contig, fcb, sx, inW);
                 const T* pp = proto + ((size_t)(b * p.Hp + py) * p.Wp + px) * 32;
                 if constexpr (F16) pb[j][0] = *(const half8*)(pp + 8 * lg);
                 else { pb[j][0] = *(const f32x4*)(pp + 4 * lg); pb[j][1] = *(const f32x4*)(pp + 16 + 4 * lg); }
             }
         }
         // ---- this lane's column: footprint taps and weights (lanes past the frame take the last column and store nothing)
-        const int xg = x0 + min(ln, ncols - 1);
+        const int xg = WINDOWS ? min(max(x0 + ln, xl), xl + ncols - 1) : x0 + min(ln, ncols - 1);
         const float fx = (float)(x0 + ln);
+        const bool lane_in = WINDOWS ? x0 + ln >= xl && x0 + ln < xl + ncols : ln < ncols;
         int k0, k1;
         float wx1;
         {
             int i0, i1;
             native_tap(xg, sx, inW, i0, i1, wx1);
             if (col_contig) { k0 = i0 - fcb; k1 = i1 - fcb; }
-            else { k0 = 2 * (xg - x0); k1 = k0 + 1; }
+            else { k0 = 2 * (xg - xl); k1 = k0 + 1; }
         }
         const float wx0 = 1.0f - wx1;
         // ... and, lane as row t of the tile, row t's footprint row offsets and weights (read back with readlane per row)
@@ -1665,14 +1728,16 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
             else { ro0 = 2 * (yt - y0) * fw; ro1 = ro0 + fw; }
         }
         const float wy0 = 1.0f - wy1;
-        const float xe = (float)(x0 + ncols - 1), ye = (float)(y0 + nrows - 1);
+        const float xe = (float)(xl + ncols - 1), ye = (float)(y0 + nrows - 1);
         for (int i0 = 0; i0 < n_b; i0 += MROUND) {
             __syncthreads();                                               // previous round / item is done with the shared arrays
             if (wv == 0) {
                 const int i = i0 + ln;
                 const size_t r = (size_t)b * p.max_det + (i < n_b ? i : n_b - 1);
-                const float4 bx = *(const float4*)(p.xyxy + r * 4);
-                const bool hit = i < n_b && bx.x <= xe && bx.z > (float)x0 && bx.y <= ye && bx.w > (float)y0;
+                float4 bx;
+                if constexpr (WINDOWS) bx = scale_box(p.dets + r * ROW, wpadx, wpady, wgain, (float)W0, (float)H0);
+                else bx = *(const float4*)(p.xyxy + r * 4);
+                const bool hit = i < n_b && bx.x <= xe && bx.z > (float)xl && bx.y <= ye && bx.w > (float)y0;
                 const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
                 if (ln == 0) s_n = __builtin_popcountll(bal);
                 if (hit) {
@@ -1728,7 +1793,7 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
                     const int u = pr / npc, c = pr - u * npc;
                     const int slot = off_b + i0 + (int)s_list[g0 + u];         // FRAMES: off_b = 0, the instance's index in its frame
                     const float4 bx = s_box[g0 + u];
-                    const bool colin = ln < ncols && fx >= bx.x && fx < bx.z;
+                    const bool colin = lane_in && fx >= bx.x && fx < bx.z;
                     const float* L = &low[u][0];
                     uint8_t* out = frame_slots + (size_t)slot * slot_bytes;
                     const int r0 = 16 * c, r1 = min(r0 + 16, nrows);
@@ -1744,14 +1809,14 @@ __global__ __launch_bounds__(256, 2) void masks_native_kernel(NativeMaskParams p
                         const float v = h0 * (wx0 * L[o0 + k0] + wx1 * L[o0 + k1]) + h1 * (wx0 * L[o1 + k0] + wx1 * L[o1 + k1]);
                         const bool bit = colin && v > thr;
                         if (!FRAMES && p.packing == VTI_PACK_U8) {
-                            if (ln < ncols) out[(size_t)y * W0 + x0 + ln] = bit ? (uint8_t)1 : (uint8_t)0;
+                            if (lane_in) out[(size_t)y * W0 + x0 + ln] = bit ? (uint8_t)1 : (uint8_t)0;
                         } else {
                             const unsigned long long m = __builtin_amdgcn_ballot_w64(bit);
                             if (ln == r - r0) { wl = (unsigned)m; wh = (unsigned)(m >> 32); }
                         }
                     }
                     if ((FRAMES || p.packing != VTI_PACK_U8) && ln < r1 - r0)                // lane r: row r0 + r, 8 bytes (row_bytes % 8 == 0)
-                        *(uint2*)(out + (size_t)(y0 + r0 + ln) * row_bytes + 8 * tx) = make_uint2(wl, wh);
+                        *(uint2*)(out + (size_t)((WINDOWS ? oy : 0) + y0 + r0 + ln) * row_bytes + 8 * word) = make_uint2(wl, wh);
                 }
                 if (g0 + MG < nlist) __syncthreads();                      // the next group overwrites `low`
             }
@@ -1807,32 +1872,41 @@ long long native_frames_bytes(const void* host_table, int Hp, int Wp, int max_de
 
 size_t masks_native_frames_workspace_bytes(int B) { return 256 + align256((size_t)(B + 1) * sizeof(int)) + (size_t)B * sizeof(NativeFrame); }
 
-hipError_t launch_masks_native_frames(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
-                                      const FrameRow* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
-                                      long long capacity_bytes, int* offsets, long long* bases, void* ws, hipStream_t st) {
+template <bool WINDOWS>
+static hipError_t launch_masks_native_table(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
+                                            const void* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
+                                            long long capacity_bytes, int* offsets, long long* bases, void* ws, hipStream_t st) {
     if (B == 0) return hipSuccess;
     if (capacity_bytes > 0 && ((uintptr_t)masks & 7)) return hipErrorInvalidValue;                            // 8-byte row pieces
     // workspace: live_end i64 (256 bytes) | tile_prefix i32 [B + 1] | NativeFrame [B]
     long long* live_end = (long long*)ws;
     int* tile_prefix = (int*)((char*)ws + 256);
     NativeFrame* nf = (NativeFrame*)((char*)ws + 256 + align256((size_t)(B + 1) * sizeof(int)));
-    hipLaunchKernelGGL(mask_frames_plan_kernel, dim3(1), dim3(256), (size_t)3 * B * sizeof(int), st, counts, rows, B, max_det, Hp, Wp,
-                       capacity_bytes, offsets, bases, tile_prefix, nf, live_end);
+    hipLaunchKernelGGL(mask_frames_plan_kernel<WINDOWS>, dim3(1), dim3(256), (size_t)3 * B * sizeof(int), st, counts, rows, B, max_det, Hp,
+                       Wp, capacity_bytes, offsets, bases, tile_prefix, nf, live_end);
     if (capacity_bytes <= 0) return hipGetLastError();
-    NativeMaskParams p;
+    typename std::conditional<WINDOWS, NativeWindowParams, NativeMaskParams>::type p;
     memset(&p, 0, sizeof p);
     p.dets = dets; p.xyxy = xyxy; p.offsets = offsets; p.proto = proto; p.masks = masks;
     p.B = B; p.max_det = max_det; p.Hp = Hp; p.Wp = Wp; p.th = 1;
     p.mode = mode; p.packing = VTI_PACK_BITS;
     p.nf = nf; p.tile_prefix = tile_prefix;
+    if constexpr (WINDOWS) p.wrows = (const WindowRow*)rows;
     const size_t vecs = (size_t)capacity_bytes / 16;
     const int clear_grid = (int)std::max<size_t>(1, std::min<size_t>((vecs + 255) / 256, 2048));
     hipLaunchKernelGGL(mask_clear_bytes_kernel, dim3(clear_grid), dim3(256), 0, st, live_end, capacity_bytes, masks);
-    const int grid = 256 * (dtype == VTI_F16 ? resident_per_cu<masks_native_kernel<half_t, true>>(256, 2, 4)
-                                              : resident_per_cu<masks_native_kernel<float, true>>(256, 2, 4));
-    if (dtype == VTI_F16) hipLaunchKernelGGL((masks_native_kernel<half_t, true>), dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((masks_native_kernel<float, true>), dim3(grid), dim3(256), 0, st, p);
+    const int grid = 256 * (dtype == VTI_F16 ? resident_per_cu<masks_native_kernel<half_t, true, WINDOWS>>(256, 2, 4)
+                                              : resident_per_cu<masks_native_kernel<float, true, WINDOWS>>(256, 2, 4));
+    if (dtype == VTI_F16) hipLaunchKernelGGL((masks_native_kernel<half_t, true, WINDOWS>), dim3(grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((masks_native_kernel<float, true, WINDOWS>), dim3(grid), dim3(256), 0, st, p);
     return hipGetLastError();
+}
+
+hipError_t launch_masks_native_frames(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
+                                      const FrameRow* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
+                                      long long capacity_bytes, int* offsets, long long* bases, void* ws, hipStream_t st) {
+    return launch_masks_native_table<false>(dtype, dets, xyxy, counts, proto, rows, B, max_det, Hp, Wp, mode, masks, capacity_bytes, offsets,
+                                            bases, ws, st);
 }
 
 // =====================================================================================
@@ -1852,11 +1926,7 @@ __global__ void scale_boxes_kernel(const float* __restrict__ dets, const int* __
             const FrameRow* f = table + b;
             padx = f->padx; pady = f->pady; gain = f->gain; W0 = (float)f->W0; H0 = (float)f->H0;
         }
-        const float* d = dets + (size_t)i * row;
-        o.x = fminf(fmaxf((d[0] - padx) / gain, 0.f), W0);
-        o.y = fminf(fmaxf((d[1] - pady) / gain, 0.f), H0);
-        o.z = fminf(fmaxf((d[2] - padx) / gain, 0.f), W0);
-        o.w = fminf(fmaxf((d[3] - pady) / gain, 0.f), H0);
+        o = scale_box(dets + (size_t)i * row, padx, pady, gain, W0, H0);
     }
     ((float4*)xyxy)[i] = o;
 }
@@ -1996,6 +2066,69 @@ hipError_t launch_mask_stats(const uint8_t* bitmaps, int n, int H0, int W0, long
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(mask_stats_kernel, dim3(n), dim3(1024), 0, st, bitmaps, H0, W0, stats);
     return hipGetLastError();
+}
+
+// =====================================================================================
+// The window forms (vti_*_windows): their launchers stand last, so that their kernels follow the others in the code object
+// =====================================================================================
+hipError_t launch_letterbox_windows(const uint8_t* frames, int B, const WindowRow* rows, uint8_t* out, int H, int W, hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    if (W & 3) return hipErrorInvalidValue;
+    const dim3 grid((H + LB_ROWS - 1) / LB_ROWS, B);
+    FrameRow one = {};
+    hipLaunchKernelGGL(letterbox_rows_kernel<LB_WINDOWS>, grid, dim3(256), 0, st, frames, one, (const void*)rows, out, H, W);
+    return hipGetLastError();
+}
+
+// vti_scale_boxes_windows: the box in the px of frame b's window (scale_box with the crop's row), then one f32 add of the window's
+// origin per coordinate: the box in frame px.
+__global__ void scale_boxes_windows_kernel(const float* __restrict__ dets, const int* __restrict__ counts, int B, int max_det, int row,
+                                           const WindowRow* __restrict__ table, float* __restrict__ xyxy) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * max_det) return;
+    const int b = i / max_det, k = i - b * max_det;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k < counts[b]) {
+        const WindowRow* w = table + b;
+        o = scale_box(dets + (size_t)i * row, w->crop.padx, w->crop.pady, w->crop.gain, (float)w->crop.W0, (float)w->crop.H0);
+        const float fx = (float)w->x0, fy = (float)w->y0;
+        o.x += fx; o.y += fy; o.z += fx; o.w += fy;
+    }
+    ((float4*)xyxy)[i] = o;
+}
+
+hipError_t launch_scale_boxes_windows(const float* dets, const int* counts, int B, int max_det, int nm, const WindowRow* table,
+                                      float* xyxy, hipStream_t st) {
+    if (B * max_det == 0) return hipSuccess;
+    hipLaunchKernelGGL(scale_boxes_windows_kernel, dim3((B * max_det + 255) / 256), dim3(256), 0, st, dets, counts, B, max_det, 6 + nm,
+                       table, xyxy);
+    return hipGetLastError();
+}
+
+hipError_t launch_masks_native_windows(int dtype, const float* dets, const int* counts, const void* proto, const WindowRow* rows, int B,
+                                       int max_det, int Hp, int Wp, int mode, uint8_t* masks, long long capacity_bytes, int* offsets,
+                                       long long* bases, void* ws, hipStream_t st) {
+    return launch_masks_native_table<true>(dtype, dets, nullptr, counts, proto, rows, B, max_det, Hp, Wp, mode, masks, capacity_bytes,
+                                           offsets, bases, ws, st);
+}
+
+// vti_mask_native_windows_bytes / vti_masks_native_windows: native_frames_bytes of the FULL frames of a packed window table, and the
+// tiles of the windows' work list; -1 where a frame or a window has no native layout.
+long long native_windows_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles) {
+    FrameTableHeader h;
+    memcpy(&h, host_table, sizeof h);
+    long long bytes = 0, til = 0;
+    for (int b = 0; b < h.B; ++b) {
+        WindowRow r;
+        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
+        NativeGeom g;
+        int lay[6];
+        if (native_geom(Hp, Wp, r.crop.H0, r.crop.W0, VTI_PACK_BITS, g) || native_mask_layout_hd(Hp, Wp, r.H0, r.W0, VTI_PACK_BITS, lay)) return -1;
+        bytes += (long long)max_det * lay[5];
+        til += (long long)(((r.x0 + r.crop.W0 - 1) >> 6) - (r.x0 >> 6) + 1) * ((r.crop.H0 + g.th - 1) / g.th);
+    }
+    if (tiles) *tiles = til;
+    return bytes;
 }
 
 }  // namespace vti

@@ -712,10 +712,11 @@ int32_t vti_predict(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, in
 }
 
 // vti_predict_frames up to the NMS: the checks on what those stages take, then letterbox -> scored forward -> NMS.
+// `letterbox`: vti_letterbox_frames, or vti_letterbox_windows for a window table.
 static int32_t predict_frames_head(const char* fn, vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table,
                                    int32_t B, int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic,
                                    uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts, const float* xyxy,
-                                   void* stream) {
+                                   void* stream, decltype(&vti_letterbox_frames) letterbox = vti_letterbox_frames) {
     int32_t rc;
     if (!frames || !input_scratch || ((uintptr_t)frames & 15) || ((uintptr_t)input_scratch & 3))
         return fail(c, VTI_ERR_ARG, std::string(fn) + ": dev_frames (16-byte aligned) and dev_input_scratch (4-byte aligned) are required");
@@ -723,7 +724,7 @@ static int32_t predict_frames_head(const char* fn, vti_ctx* c, const uint8_t* fr
         return fail(c, VTI_ERR_ARG, std::string(fn) + ": bad argument (max_det < 1, null dets / counts or dev_xyxy not 16-byte aligned)");
     if ((rc = check_ready(c, B, fn))) return rc;
     const vti_desc& d = c->plan.desc;
-    if ((rc = vti_letterbox_frames(c, frames, host_table, dev_table, B, input_scratch, stream))) return rc;
+    if ((rc = letterbox(c, frames, host_table, dev_table, B, input_scratch, stream))) return rc;
     float* best = nms_workspace_best(c->ws + c->act_bytes, d.max_batch, c->plan.num_anchors);
     if ((rc = vti_forward_scored(c, input_scratch, B, swap_rb, pred, proto, best, stream))) return rc;
     return vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream);
@@ -819,6 +820,220 @@ int32_t vti_predict_frames_native(vti_ctx* c, const uint8_t* frames, const void*
     if ((rc = vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
     return vti_masks_native_frames(c, dets, xyxy, counts, proto, host_table, dev_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE, packing,
                                    masks, capacity_bytes, offsets, mask_bases, stream);
+}
+
+// ---- predict on a window of each frame: the window table ----------------------------------------------------------------------
+int64_t vti_window_table_bytes(int32_t B) {
+    return B < 1 ? 0 : (int64_t)sizeof(FrameTableHeader) + (int64_t)B * (int64_t)sizeof(WindowRow);
+}
+
+// What is wrong with one window of an H0 x W0 frame for the H x W canvas (nullptr: nothing); the frame itself passed frame_error.
+static const char* window_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int32_t x0, int32_t y0, int32_t w, int32_t h) {
+    if (w < 1 || h < 1) return "the window's w and h must be >= 1";
+    if (x0 < 0 || y0 < 0 || x0 > W0 - w || y0 > H0 - h) return "the window does not lie inside its frame";
+    int nh, nw, top, left;
+    letterbox_geom(h, w, H, W, nh, nw, top, left);
+    if (nh < 1 || nw < 1) return "the resized window would be below 1 px";
+    if (top < 0 || left < 0 || top + nh > H || left + nw > W) return "the resized window does not fit the canvas";
+    return nullptr;
+}
+
+static WindowRow window_row(const void* host_table, int32_t k) {
+    WindowRow r;
+    memcpy(&r, (const char*)host_table + sizeof(FrameTableHeader) + (size_t)k * sizeof r, sizeof r);
+    return r;
+}
+
+int32_t vti_pack_windows(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset,
+                         const int32_t* windows, int32_t B, int64_t total_bytes, void* host_table, size_t nbytes) {
+    if (!H0 || !W0 || !byte_offset || !windows || !host_table || B < 1)
+        return fail(c, VTI_ERR_ARG, "vti_pack_windows: null array or table, or B < 1");
+    if (H < 32 || W < 32 || (H & 31) || (W & 31) || total_bytes < 0)
+        return fail(c, VTI_ERR_ARG, "vti_pack_windows: the canvas H, W must be multiples of 32, total_bytes >= 0");
+    if ((int64_t)nbytes < vti_window_table_bytes(B))
+        return fail(c, VTI_ERR_ARG, "vti_pack_windows: table smaller than vti_window_table_bytes()");
+    if (c && B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_pack_windows: B above the ctx's max_batch");
+    for (int32_t b = 0; b < B; ++b) {
+        const int32_t* w = windows + 4 * (size_t)b;
+        const char* e = frame_error(H, W, H0[b], W0[b], byte_offset[b], total_bytes);
+        if (!e) e = window_error(H, W, H0[b], W0[b], w[0], w[1], w[2], w[3]);
+        if (e) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "vti_pack_windows: frame %d: %s", b, e);
+            return fail(c, VTI_ERR_ARG, msg);
+        }
+    }
+    FrameTableHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = kWindowTableMagic; h.B = B; h.H = H; h.W = W; h.total_bytes = total_bytes;
+    for (int32_t b = 0; b < B; ++b) {
+        const int32_t* w = windows + 4 * (size_t)b;
+        WindowRow r;
+        memset(&r, 0, sizeof r);
+        frame_row_fill(H, W, w[3], w[2], byte_offset[b] + 3 * ((int64_t)w[1] * W0[b] + w[0]), r.crop);
+        r.frame_offset = byte_offset[b]; r.H0 = H0[b]; r.W0 = W0[b]; r.x0 = w[0]; r.y0 = w[1];
+        h.max_H0 = std::max(h.max_H0, H0[b]); h.max_W0 = std::max(h.max_W0, W0[b]);
+        memcpy((char*)host_table + sizeof h + (size_t)b * sizeof r, &r, sizeof r);
+    }
+    memcpy(host_table, &h, sizeof h);
+    return VTI_OK;
+}
+
+int32_t vti_window_table_info(const void* host_table, int32_t b, int32_t out_i32[12], double out_f64[5]) {
+    if (!host_table || !out_i32) return VTI_ERR_ARG;
+    const FrameTableHeader h = table_header(host_table);
+    if (h.magic != kWindowTableMagic || h.B < 1 || b < -1 || b >= h.B) return VTI_ERR_ARG;
+    if (b < 0) {
+        const int32_t v[12] = {h.B, h.H, h.W, h.max_H0, h.max_W0, 0, (int32_t)(h.total_bytes & 0xffffffff), (int32_t)(h.total_bytes >> 32),
+                               0, 0, 0, 0};
+        memcpy(out_i32, v, sizeof v);
+        return VTI_OK;
+    }
+    const WindowRow w = window_row(host_table, b);
+    const FrameRow& r = w.crop;
+    const int32_t v[12] = {r.H0, r.W0, r.new_h, r.new_w, r.top, r.left, (int32_t)(r.offset & 0xffffffff), (int32_t)(r.offset >> 32),
+                           w.x0, w.y0, w.H0, w.W0};
+    memcpy(out_i32, v, sizeof v);
+    if (out_f64) { out_f64[0] = r.scale_x; out_f64[1] = r.scale_y; out_f64[2] = r.gain; out_f64[3] = r.padx; out_f64[4] = r.pady; }
+    return VTI_OK;
+}
+
+// frame_table_problem for a window table: every row's frame passes frame_error, its window window_error, and the crop row holds the
+// window's size and first byte (what the kernels form addresses from).
+static const char* window_table_problem(const vti_ctx* c, const void* host_table, int32_t B, FrameTableHeader& h, int32_t& frame) {
+    frame = -1;
+    h = table_header(host_table);
+    if (h.magic != kWindowTableMagic) return "host_table is not a table of vti_pack_windows";
+    if (h.B < 1 || (B >= 0 && h.B != B)) return "the window table was packed for another B";
+    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return "the window table was packed for another canvas (H x W)";
+    for (int32_t b = 0; b < h.B; ++b) {
+        const WindowRow w = window_row(host_table, b);
+        const char* e = frame_error(h.H, h.W, w.H0, w.W0, w.frame_offset, h.total_bytes);
+        if (!e && (w.H0 > h.max_H0 || w.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
+        if (!e) e = window_error(h.H, h.W, w.H0, w.W0, w.x0, w.y0, w.crop.W0, w.crop.H0);
+        if (!e && w.crop.offset != w.frame_offset + 3 * ((int64_t)w.y0 * w.W0 + w.x0)) e = "the window's first byte is not where its origin puts it";
+        if (e) { frame = b; return e; }
+    }
+    return nullptr;
+}
+
+static int32_t windows_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
+    char msg[200];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, VTI_ERR_ARG, msg); };
+    if (!c) return VTI_ERR_ARG;
+    if (!host_table || !dev_table) return bad("null window table (host copy or device copy)");
+    if ((uintptr_t)dev_table & 15) return bad("the device window table must be 16-byte aligned");
+    int32_t frame;
+    if (B < 1) {
+        h = table_header(host_table);
+        return bad(h.magic != kWindowTableMagic ? "host_table is not a table of vti_pack_windows" : "the window table was packed for another B");
+    }
+    if (const char* e = window_table_problem(c, host_table, B, h, frame)) {
+        if (frame < 0) return bad(e);
+        snprintf(msg, sizeof msg, "%s: frame %d of host_table: %s", fn, frame, e);
+        return fail(c, VTI_ERR_ARG, msg);
+    }
+    return VTI_OK;
+}
+
+static const WindowRow* window_rows(const void* dev_table) { return (const WindowRow*)((const char*)dev_table + sizeof(FrameTableHeader)); }
+
+int32_t vti_letterbox_windows(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                              uint8_t* out, void* stream) {
+    FrameTableHeader h;
+    if (int32_t rc = windows_check("vti_letterbox_windows", c, host_table, dev_table, B, h)) return rc;
+    if (!frames || !out) return fail(c, VTI_ERR_ARG, "vti_letterbox_windows: null frames or output");
+    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 3))
+        return fail(c, VTI_ERR_ARG, "vti_letterbox_windows: dev_frames must be 16-byte aligned, dev_input 4-byte aligned");
+    if (B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_letterbox_windows: B above max_batch");
+    if (int32_t drc = check_device(c, "vti_letterbox_windows")) return drc;
+    VTI_HIP(c, launch_letterbox_windows(frames, B, window_rows(dev_table), out, h.H, h.W, (hipStream_t)stream), "letterbox kernel (windows)");
+    return VTI_OK;
+}
+
+int32_t vti_scale_boxes_windows(vti_ctx* c, const float* dets, const int32_t* counts, const void* host_table, const void* dev_table,
+                                int32_t B, int32_t max_det, float* xyxy, void* stream) {
+    FrameTableHeader h;
+    if (int32_t rc = windows_check("vti_scale_boxes_windows", c, host_table, dev_table, B, h)) return rc;
+    if (!dets || !counts || !xyxy || max_det < 1 || ((uintptr_t)xyxy & 15))
+        return fail(c, VTI_ERR_ARG, "vti_scale_boxes_windows: bad argument (null pointer, max_det < 1 or dev_xyxy not 16-byte aligned)");
+    if ((int64_t)B * max_det > INT32_MAX) return fail(c, VTI_ERR_ARG, "vti_scale_boxes_windows: B * max_det out of range");
+    if (int32_t drc = check_device(c, "vti_scale_boxes_windows")) return drc;
+    VTI_HIP(c, launch_scale_boxes_windows(dets, counts, B, max_det, c->plan.desc.nm, window_rows(dev_table), xyxy, (hipStream_t)stream),
+            "scale_boxes kernel (windows)");
+    return VTI_OK;
+}
+
+int64_t vti_mask_native_windows_bytes(const vti_ctx* c, const void* host_table, int32_t max_det) {
+    if (!c || !host_table || max_det < 1) return 0;
+    FrameTableHeader h;
+    int32_t frame;
+    if (window_table_problem(c, host_table, -1, h, frame) || h.B > c->plan.desc.max_batch) return 0;
+    const long long n = native_windows_bytes(host_table, h.H / 4, h.W / 4, max_det, nullptr);
+    return n < 0 ? 0 : n;
+}
+
+// The argument checks of vti_masks_native_windows (everything but the table, which windows_check has passed).
+static int32_t masks_native_windows_check(const char* fn, vti_ctx* c, const float* dets, const int32_t* counts, const void* proto,
+                                          const void* host_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing,
+                                          const uint8_t* masks, int64_t capacity_bytes, const int32_t* offsets, const int64_t* bases) {
+    char msg[200];
+    auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
+    if (!dets || !counts || !proto || !offsets || !bases || max_det < 1 || capacity_bytes < 0 || (capacity_bytes && !masks))
+        return bad(VTI_ERR_ARG, "bad argument (null pointer, max_det < 1 or capacity_bytes < 0)");
+    if (mode != VTI_MASK_LOGIT && mode != VTI_MASK_SIGMOID) return bad(VTI_ERR_ARG, "bad mode");
+    if (packing == VTI_PACK_U8) return bad(VTI_ERR_UNSUPPORTED, "the ragged mask buffer is bit-packed only (VTI_PACK_BITS)");
+    if (packing != VTI_PACK_BITS) return bad(VTI_ERR_ARG, "bad packing");
+    if (((uintptr_t)masks & 7) || ((uintptr_t)bases & 7) || ((uintptr_t)offsets & 3) || ((uintptr_t)dets & 7))
+        return bad(VTI_ERR_ARG, "dev_masks, dev_mask_bases and dev_dets must be 8-byte aligned, dev_offsets 4-byte aligned");
+    const vti_desc& d = c->plan.desc;
+    if (B > d.max_batch) return bad(VTI_ERR_ARG, "B out of range");
+    if (d.nm != 32) return bad(VTI_ERR_UNSUPPORTED, "only nm == 32 prototypes");
+    long long tiles = 0;
+    if (native_windows_bytes(host_table, d.H / 4, d.W / 4, max_det, &tiles) < 0)
+        return bad(VTI_ERR_ARG, "a frame or a window of host_table has no native mask layout (slot below 2 GiB)");
+    if (tiles > INT32_MAX || (int64_t)B * max_det > INT32_MAX) return bad(VTI_ERR_UNSUPPORTED, "too many tiles or slots for one call");
+    return VTI_OK;
+}
+
+int32_t vti_masks_native_windows(vti_ctx* c, const float* dets, const int32_t* counts, const void* proto, const void* host_table,
+                                 const void* dev_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing, uint8_t* masks,
+                                 int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, void* stream) {
+    FrameTableHeader h;
+    if (int32_t rc = windows_check("vti_masks_native_windows", c, host_table, dev_table, B, h)) return rc;
+    if (int32_t rc = masks_native_windows_check("vti_masks_native_windows", c, dets, counts, proto, host_table, B, max_det, mode, packing,
+                                                masks, capacity_bytes, offsets, mask_bases))
+        return rc;
+    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_masks_native_windows: workspace not set");
+    const vti_desc& d = c->plan.desc;
+    void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
+    if (masks_native_frames_workspace_bytes(B) > masks_workspace_bytes(d.max_batch * kMaskSlotsPerFrame, d.H, d.W))
+        return fail(c, VTI_ERR_NOMEM, "vti_masks_native_windows: workspace too small");
+    if (int32_t drc = check_device(c, "vti_masks_native_windows")) return drc;
+    VTI_HIP(c, launch_masks_native_windows(d.dtype, dets, counts, proto, window_rows(dev_table), B, max_det, d.H / 4, d.W / 4, mode, masks,
+                                           capacity_bytes, offsets, (long long*)mask_bases, mws, (hipStream_t)stream),
+            "native mask kernel (windows)");
+    return VTI_OK;
+}
+
+int32_t vti_predict_windows(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B, int32_t swap_rb,
+                            float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode, int32_t packing,
+                            uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts, uint8_t* masks,
+                            int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, float* xyxy, void* stream) {
+    FrameTableHeader h;
+    int32_t rc = windows_check("vti_predict_windows", c, host_table, dev_table, B, h);
+    if (rc) return rc;
+    if (!xyxy) return fail(c, VTI_ERR_ARG, "vti_predict_windows: dev_xyxy is required");
+    if (!pred) return fail(c, VTI_ERR_ARG, "vti_predict_windows: null dev_pred");
+    if ((rc = masks_native_windows_check("vti_predict_windows", c, dets, counts, proto, host_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE,
+                                         packing, masks, capacity_bytes, offsets, mask_bases)))
+        return rc;
+    if ((rc = predict_frames_head("vti_predict_windows", c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic,
+                                  input_scratch, pred, proto, dets, counts, xyxy, stream, vti_letterbox_windows)))
+        return rc;
+    if ((rc = vti_scale_boxes_windows(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
+    return vti_masks_native_windows(c, dets, counts, proto, host_table, dev_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE, packing, masks,
+                                    capacity_bytes, offsets, mask_bases, stream);
 }
 
 int32_t vti_mask_to_frame(vti_ctx* c, const uint8_t* masks, int32_t n, int32_t H, int32_t W, int32_t H0, int32_t W0,

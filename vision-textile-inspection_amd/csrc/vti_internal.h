@@ -322,6 +322,19 @@ struct FrameTableHeader {
     int pad[8];
 };
 static_assert(sizeof(FrameTableHeader) == 64, "the rows of a frame table stay 64-byte aligned");
+// One frame of a windowed predict (vti_pack_windows): `crop` is the row vti_pack_frames would pack for the contiguous copy of the
+// window (H0 x W0 = the window's h x w; offset = the byte of the window's first pixel inside the frame buffer, of any alignment),
+// then the frame the window lies in and the window's origin in it.  A window table is a FrameTableHeader with kWindowTableMagic
+// (max_H0, max_W0: of the full frames) followed by B rows.
+struct WindowRow {
+    FrameRow crop;
+    long long frame_offset;     // of the FRAME's first byte (a multiple of 16)
+    int H0, W0;                 // the frame's size
+    int x0, y0;                 // the window's origin in the frame
+    int pad[10];                // zero
+};
+static_assert(sizeof(WindowRow) == 128, "window table rows are 128 bytes");
+constexpr int kWindowTableMagic = 0x31545756;   // "VWT1"
 void letterbox_geom(int H0, int W0, int H, int W, int& new_h, int& new_w, int& top, int& left);
 void frame_row_fill(int H, int W, int H0, int W0, long long offset, FrameRow& r);      // geometry of one frame on the H x W canvas (host)
 
@@ -381,6 +394,17 @@ size_t masks_native_frames_workspace_bytes(int B);
 hipError_t launch_masks_native_frames(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
                                       const FrameRow* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
                                       long long capacity_bytes, int* offsets, long long* bases, void* ws, hipStream_t st);
+// The window forms (vti_*_windows; rows: the device window table's rows).  Letterbox: the canvas of the contiguous crops, read in
+// place.  Scale boxes: the crop's boxes plus the window's origin (frame px).  Native masks: the ragged buffer of the FULL frames
+// (launch_masks_native_frames' layout, offsets, bases and liveness), each instance's crop mask placed at the window's origin; the
+// boxes are recomputed in window px from `dets`.  native_windows_bytes: native_frames_bytes of the full frames of a host window table.
+hipError_t launch_letterbox_windows(const uint8_t* frames, int B, const WindowRow* rows, uint8_t* out, int H, int W, hipStream_t st);
+hipError_t launch_scale_boxes_windows(const float* dets, const int* counts, int B, int max_det, int nm, const WindowRow* rows,
+                                      float* xyxy, hipStream_t st);
+long long native_windows_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles);
+hipError_t launch_masks_native_windows(int dtype, const float* dets, const int* counts, const void* proto, const WindowRow* rows, int B,
+                                       int max_det, int Hp, int Wp, int mode, uint8_t* masks, long long capacity_bytes, int* offsets,
+                                       long long* bases, void* ws, hipStream_t st);
 // table != nullptr: gain, pads and clip bounds of frame b from row b of the device table (H0, W0 unused)
 hipError_t launch_scale_boxes(const float* dets, const int* counts, int B, int max_det, int nm, int H, int W,
                               int H0, int W0, const FrameRow* table, float* xyxy, hipStream_t st);

@@ -123,6 +123,48 @@ class FrameTable:
         return d
 
 
+class WindowTable:
+    """A packed window table (vti_pack_windows): one window (x0, y0, w, h) of each frame of a batch.  `host` / `dev` as a FrameTable's;
+    `frames` is the FrameTable of the FULL frames on the same canvas (the frame buffer's layout, and what every consumer of the
+    windowed outputs takes), `windows` [(x0, y0, w, h)] per frame."""
+
+    def __init__(self, host, dev, frames, windows):
+        self.host, self.dev, self.frames, self.windows = host, dev, frames, windows
+        self.H, self.W, self.B = frames.H, frames.W, frames.B
+        self.shapes, self.total_bytes = frames.shapes, frames.total_bytes
+
+    def _ptrs(self):
+        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
+
+    def row(self, b):
+        """Host only: what row b holds -> FrameTable.row's dict for the contiguous crop (H0, W0 are the window's h, w; offset is the
+        byte of its first pixel), plus x0, y0 and the frame's frame_H0, frame_W0."""
+        i32, f64 = (C.c_int32 * 12)(), (C.c_double * 5)()
+        check(None, lib().vti_window_table_info(C.c_void_p(self.host.data_ptr()), int(b), i32, f64))
+        d = dict(zip(("H0", "W0", "new_h", "new_w", "top", "left"), (int(v) for v in i32[:6])))
+        d["offset"] = (i32[6] & 0xFFFFFFFF) | (i32[7] << 32)
+        d.update(zip(("x0", "y0", "frame_H0", "frame_W0"), (int(v) for v in i32[8:12])))
+        d.update(zip(("scale_x", "scale_y", "gain", "padx", "pady"), (float(v) for v in f64)))
+        return d
+
+
+def check_window(window, H0, W0, who="window"):
+    """(x0, y0, x1, y1), x1 and y1 exclusive, or None for the whole frame -> (x0, y0, w, h); a ValueError unless it is four integers
+    with 0 <= x0 < x1 <= W0 and 0 <= y0 < y1 <= H0."""
+    if window is None:
+        return 0, 0, int(W0), int(H0)
+    try:
+        vals = list(window)
+    except TypeError:
+        vals = None
+    if vals is None or len(vals) != 4 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError(f"{who} must be None or four integers (x0, y0, x1, y1), got {window!r}")
+    x0, y0, x1, y1 = (int(v) for v in vals)
+    if not (0 <= x0 < x1 <= W0 and 0 <= y0 < y1 <= H0):
+        raise ValueError(f"{who} (x0, y0, x1, y1) = {(x0, y0, x1, y1)} does not lie inside its {H0}x{W0} frame with x0 < x1 and y0 < y1")
+    return x0, y0, x1 - x0, y1 - y0
+
+
 class RawTable:
     """A packed raw table (vti_pack_raw_frames) for raw camera frames that differ in size and / or format: `host` (the packed bytes,
     a CPU u8 tensor) and `dev` (their device copy), `shapes` [(H0, W0)] and `fmts` [VTI_RAW_*] per frame, the frames' `raw_offsets`
@@ -296,6 +338,98 @@ class Engine:
         if out is None:
             out = torch.empty((table.B, self.H, self.W, 3), dtype=torch.uint8, device=buf.device)
         check(self._ctx, lib().vti_letterbox_frames(self._ctx, _ptr(buf), *table._ptrs(), table.B, _ptr(out), _stream()))
+        return out
+
+    # ---- predict on a window of each frame (vti_pack_windows and the *_windows entry points) ----------------------------------
+    def pack_windows(self, shapes, windows, device=None):
+        """shapes: one (H0, W0) per frame; windows: one (x0, y0, w, h) per frame.  Packs the FrameTable of the full frames
+        (pack_frames: it fixes the frame buffer's layout) and the window table beside it, and uploads both.  -> WindowTable; a
+        VtiError names the failing frame."""
+        frames, byte_offsets, total_bytes = self.pack_frames(shapes, device)
+        B = frames.B
+        windows = [tuple(int(v) for v in w) for w in windows]
+        if len(windows) != B or any(len(w) != 4 for w in windows):
+            raise ValueError(f"pack_windows: one (x0, y0, w, h) per frame: {B} frames, got {windows!r}")
+        H0 = (C.c_int32 * B)(*[h for h, _ in frames.shapes])
+        W0 = (C.c_int32 * B)(*[w for _, w in frames.shapes])
+        off = (C.c_int64 * B)(*byte_offsets)
+        win = (C.c_int32 * (4 * B))(*[v for w in windows for v in w])
+        nbytes = int(lib().vti_window_table_bytes(B))
+        host = torch.zeros(nbytes, dtype=torch.uint8)
+        check(self._ctx, lib().vti_pack_windows(self._ctx, self.H, self.W, H0, W0, off, win, B, int(total_bytes),
+                                                C.c_void_p(host.data_ptr()), nbytes))
+        return WindowTable(host, host.to(frames.dev.device), frames, windows)
+
+    def _check_windows(self, table, B=None, buf=None):
+        if not isinstance(table, WindowTable):
+            raise ValueError("windows must be the WindowTable of Engine.pack_windows()")
+        self._check_frames(table.frames, B=B, buf=buf)
+
+    def letterbox_windows(self, buf, table, out=None):
+        """buf: the flat u8 device buffer of the frames of `table` (pack_windows) -> u8 [B,H,W,3], the canvas of the contiguous crops
+        read in place: vti_letterbox_windows."""
+        self._check_windows(table, buf=buf)
+        if out is None:
+            out = torch.empty((table.B, self.H, self.W, 3), dtype=torch.uint8, device=buf.device)
+        check(self._ctx, lib().vti_letterbox_windows(self._ctx, _ptr(buf), *table._ptrs(), table.B, _ptr(out), _stream()))
+        return out
+
+    def scale_boxes_windows(self, dets, counts, table, xyxy=None):
+        """The boxes in FRAME px: scale_boxes(frames=the crops' table) plus the window's origin (vti_scale_boxes_windows)."""
+        B, max_det = dets.shape[0], dets.shape[1]
+        self._check_windows(table, B=B)
+        if xyxy is None:
+            xyxy = torch.empty((B, max_det, 4), dtype=torch.float32, device=dets.device)
+        check(self._ctx, lib().vti_scale_boxes_windows(self._ctx, _ptr(dets), _ptr(counts), *table._ptrs(), B, max_det, _ptr(xyxy), _stream()))
+        return xyxy
+
+    def mask_native_windows_bytes(self, table, max_det):
+        """Host only: mask_native_frames_bytes of the full frames of `table`."""
+        self._check_windows(table)
+        return int(lib().vti_mask_native_windows_bytes(self._ctx, C.c_void_p(table.host.data_ptr()), int(max_det)))
+
+    def masks_native_windows(self, dets, counts, proto, table, mode="logit", masks=None, capacity_bytes=None, offsets=None,
+                             mask_bases=None):
+        """masks_native_frames' ragged buffer for the FULL frames of `table` (pack_windows), every instance's crop mask placed at its
+        window's origin and zeros elsewhere (vti_masks_native_windows; the boxes are recomputed in window px from dets).  `masks`:
+        a flat u8 buffer, by default mask_native_windows_bytes(table, max_det) bytes.  -> (masks, offsets, mask_bases)."""
+        B, max_det = dets.shape[0], dets.shape[1]
+        self._check_windows(table, B=B)
+        if masks is None:
+            masks = torch.empty(self.mask_native_windows_bytes(table, max_det) if capacity_bytes is None else int(capacity_bytes),
+                                dtype=torch.uint8, device=dets.device)
+        elif masks.dtype != torch.uint8 or masks.dim() != 1 or not masks.is_contiguous():
+            raise ValueError("masks_native_windows: masks must be a flat contiguous uint8 tensor")
+        if capacity_bytes is None:
+            capacity_bytes = masks.numel()
+        if not 0 <= int(capacity_bytes) <= masks.numel():
+            raise ValueError(f"masks_native_windows: capacity_bytes must be in [0, {masks.numel()}]")
+        if offsets is None:
+            offsets = torch.empty((B + 1,), dtype=torch.int32, device=dets.device)
+        if mask_bases is None:
+            mask_bases = torch.empty((B + 1,), dtype=torch.int64, device=dets.device)
+        check(self._ctx, lib().vti_masks_native_windows(self._ctx, _ptr(dets), _ptr(counts), _ptr(proto), *table._ptrs(), B, max_det,
+                                                        MASK_MODES[mode], PACKINGS["bits"],
+                                                        _ptr(masks) if int(capacity_bytes) else C.c_void_p(0), int(capacity_bytes),
+                                                        _ptr(offsets), _ptr(mask_bases), _stream()))
+        return masks, offsets, mask_bases
+
+    def predict_windows_into(self, buf, table, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True, mask_mode="logit",
+                             nms=None):
+        """predict_frames_into(native=True) on one window of each frame (vti_predict_windows): `buf` holds the full frames in the layout
+        of table.frames, `out` comes from alloc_outputs(table.B, ..., native_frames=table.frames).  out["xyxy"] is in frame px and the
+        ragged masks are frame-resolution rows with the window's mask at its place, so measure(frames=table.frames, native=True),
+        annotate, overlay and mask_polygons_frames take `out` as they take predict_frames_into's.  nms: as predict_frames_into."""
+        self._check_windows(table, B=out["counts"].shape[0] if isinstance(out, dict) and "counts" in out else None, buf=buf)
+        self._check_ragged(out, table.frames, max_det, "predict_windows_into")
+        if nms is not None:
+            with self._nms_scope(nms):
+                return self.predict_windows_into(buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode)
+        check(self._ctx, lib().vti_predict_windows(
+            self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
+            int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS["bits"], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
+            _ptr(out["dets"]), _ptr(out["counts"]), _ptr(out["masks"]), out["masks"].numel(), _ptr(out["offsets"]),
+            _ptr(out["mask_bases"]), _ptr(out["xyxy"]), _stream()))
         return out
 
     def predict_frames_into(self, buf, table, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True,

@@ -39,7 +39,7 @@ from . import annotate as _annotate
 from ._lib import (VTI_MEASURE_BAD_CAMERA, VTI_MEASURE_NO_FABRIC, VTI_MEASURE_NO_STITCHES, VTI_MEASURE_OK, VTI_STITCH_KEPT,
                    VTI_STITCH_NEAR, VTI_STITCH_SELECTED, VTI_STITCH_WIDTH, VtiCheckerParams, VtiMeasureParams)
 from .consumer import rodrigues
-from .engine import NmsParams
+from .engine import NmsParams, check_window
 
 ERRORS = {VTI_MEASURE_NO_FABRIC: "Fabric not detected", VTI_MEASURE_NO_STITCHES: "No stitches detected",
           VTI_MEASURE_BAD_CAMERA: "Unknown camera"}     # the last one is this package's: a device-side index outside the table
@@ -179,11 +179,19 @@ def _mixed_keyword(public):
     def process_frames(self, *args, mixed=False, burn_text=False, extra_text=None, rasterise=None, **kw):
         if not isinstance(mixed, (bool, np.bool_)):
             raise ValueError(f"process_frames: mixed must be True or False, got {mixed!r}")
+        # the two measurers' keyword-only window (StitchMeasurer: window=, MultiCameraMeasurer: windows=) and window_margin; a class
+        # without _window_keyword does not take them (sig.bind then refuses them as any unknown keyword)
+        wkw, name = {}, getattr(self, "_window_keyword", None)
+        if name is not None:
+            if name in kw:
+                wkw["window"] = kw.pop(name)
+            if "window_margin" in kw:
+                wkw["window_margin"] = kw.pop("window_margin")
         bound = sig.bind(self, *args, **kw)             # a TypeError for a bad call, as calling `public` would give
         bound.apply_defaults()
         named = dict(bound.arguments)
         del named["self"]
-        return self._process_frames(mixed=bool(mixed), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, **named)
+        return self._process_frames(mixed=bool(mixed), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, **named, **wkw)
     return process_frames
 
 
@@ -258,7 +266,8 @@ class _DeviceStage:
 
     @torch.inference_mode()
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
-                       jpeg_quality=95, mixed=False, rows=False, burn_text=False, extra_text=None, rasterise=None, nms_rows=None):
+                       jpeg_quality=95, mixed=False, rows=False, burn_text=False, extra_text=None, rasterise=None, nms_rows=None,
+                       window=None, window_margin=32, window_params=None):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
         selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0 (frames of
         differing sizes, which `mixed` allows with annotate: the list of every frame's H0).  params /
@@ -266,7 +275,10 @@ class _DeviceStage:
         camera table needs both).  rows (without annotate): a third item, every frame's per-slot rows as `_slot_rows` gives them.
         burn_text: the third item is a _Deferred -- the pictures are drawn but neither copied nor encoded yet.
         nms_rows (with cameras): one NmsParams per camera -- the predict runs under their NMS table with `cameras` as the row index,
-        and max_det is the output set's row stride."""
+        and max_det is the output set's row stride.
+        window: None, or what _frame_windows takes -- the predict then sees one window of each frame (vti_predict_windows) and the
+        measurement runs on its frame-px boxes and frame-resolution masks (native rows, whatever retina_masks says);
+        window_params(b): frame b's MeasureParams, for "roi"."""
         nms = None
         if nms_rows is not None:
             nms = lambda eng, dev: (self.model._nms_table(eng, dev, nms_rows), np.asarray(cameras))
@@ -287,7 +299,34 @@ class _DeviceStage:
             frames = self.model._convert_raw(raws)
         shapes = self.model._differing_shapes(frames)
         table = None
-        if shapes is not None:
+        if window is not None:
+            retina_masks = True
+            if shapes is not None:
+                if annotate is not None:
+                    raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
+                wins = self._frame_windows(window, window_margin, shapes, window_params)
+                eng, o, wt, _ = self.model._predict_outputs_windows(frames, shapes, wins, conf, iou, max_det, imgsz, False, False, nms=nms)
+                table, B, H0, W0 = wt.frames, len(shapes), None, None
+            else:
+                if isinstance(frames, (list, tuple)):
+                    frames = torch.stack(list(frames)) if isinstance(frames[0], torch.Tensor) else np.stack([np.asarray(f) for f in frames])
+                shp = tuple(frames.shape) if hasattr(frames, "shape") else np.shape(frames)
+                if len(shp) not in (3, 4) or shp[-1] != 3:
+                    raise ValueError(f"source must be uint8 HxWx3 or BxHxWx3, got shape {shp}")
+                B, (H0, W0) = (1 if len(shp) == 3 else int(shp[0])), (int(shp[-3]), int(shp[-2]))
+                wins = self._frame_windows(window, window_margin, [(H0, W0)] * B, window_params)      # refused before a device is touched
+                batch = self.model._to_device_batch(frames)
+                eng, o, wt, _ = self.model._predict_outputs_windows(batch, [(H0, W0)] * B, wins, conf, iou, max_det, imgsz, False, False,
+                                                                    nms=nms)
+                self.model._last_frames = batch if annotate is not None else None
+                # frames of one size: the ragged buffer IS the uniform native layout (slot offsets[b] + i, all slots live), so the
+                # uniform native measure and annotate calls take it as a view
+                u = o.get("_uniform")
+                if u is None:
+                    rb = eng.mask_native_layout(H0, W0)["row_bytes"]
+                    u = o["_uniform"] = dict(o, masks=o["masks"].view(-1, H0, rb))
+                o = u
+        elif shapes is not None:
             if not self._mixed_sizes:
                 raise ValueError(f"process_frames: {type(self).__name__} needs frames of one size; the frames of this list differ in shape")
             if annotate is not None and not mixed:
@@ -335,6 +374,40 @@ class _DeviceStage:
                                          int(jpeg_quality) if encode else None, table, bool(burn_text)),
                H0 if table is None else [h for h, _ in shapes])
         return got + (self._slot_rows(o, res, np.arange(B)),) if rows else got      # rows next to annotate: a fifth item, every frame's
+
+    @staticmethod
+    def _frame_windows(window, margin, shapes, params_of):
+        """process_frames' window -> [(x0, y0, w, h)] per frame.  window: (x0, y0, x1, y1) for every frame, a list with one entry per
+        frame (None: the whole frame), or "roi": frame b's clamped ROI (measurement.py:220-238, inclusive bounds) grown by `margin` px
+        on every side and clipped to the frame; a disabled or degenerate ROI means the whole frame.  Bad values are a ValueError."""
+        if isinstance(margin, (bool, np.bool_)) or not isinstance(margin, (int, np.integer)) or margin < 0:
+            raise ValueError(f"process_frames: window_margin must be an integer >= 0, got {margin!r}")
+        B = len(shapes)
+
+        def roi(b):
+            h0, w0 = shapes[b]
+            r = _annotate.roi_bounds(h0, w0, params_of(b))
+            if r is None:
+                return None
+            return max(0, r[0] - margin), max(0, r[1] - margin), min(w0, r[2] + 1 + margin), min(h0, r[3] + 1 + margin)
+        if isinstance(window, str):
+            if window != "roi":
+                raise ValueError(f'process_frames: window must be None, "roi", (x0, y0, x1, y1) or one of these per frame, got {window!r}')
+            window = ["roi"] * B
+        per_frame = isinstance(window, (list, tuple)) and len(window) > 0 and all(
+            w is None or isinstance(w, str) or hasattr(w, "__len__") for w in window)
+        if not per_frame:
+            window = [window] * B
+        elif len(window) != B:
+            raise ValueError(f"process_frames: the window list has {len(window)} entries but the batch has {B} frames")
+        out = []
+        for b, w in enumerate(window):
+            if isinstance(w, str):
+                if w != "roi":
+                    raise ValueError(f'process_frames: window of frame {b}: a string must be "roi", got {w!r}')
+                w = roi(b)
+            out.append(check_window(w, shapes[b][0], shapes[b][1], f"process_frames: window of frame {b}"))
+        return out
 
     def _annotated(self, eng, o, res, params, cameras, sel, native, jpeg_quality=None, table=None, burn=False):
         """vti_annotate on the batch predict consumed; the selected pictures in one device -> host copy, and of the per-slot rows only
@@ -449,12 +522,20 @@ class StitchMeasurer(_DeviceStage):
         cv2.putText would have written; the tuple stays (frame index, picture or bytes, items).  extra_text (needs burn_text): {frame
         index: [items in text_items' form]}, or a callable (frame index, the frame's record) -> items for lines that quote the record
         this call builds: the caller's own lines (main.py:297-309), burned in after the frame's own and appended to its items.  rasterise (keyword only): rasterise(canvas, item) in annotate.text_stamps' sense; default cv2.putText
-        (ImportError, before anything is predicted, where OpenCV is not installed).  The records are the same with and without it."""
+        (ImportError, before anything is predicted, where OpenCV is not installed).  The records are the same with and without it.
+        window (keyword only): None, (x0, y0, x1, y1) with x1, y1 exclusive, or "roi" -- the params' ROI clamped to the frame, grown by
+        window_margin (keyword only, default 32) px and clipped to the frame; a disabled ROI means the whole frame.  The network then
+        sees only that window of every frame, read in place (vti_predict_windows), at the canvas predict would pick for the crop;
+        boxes come back in frame px and the masks as frame-resolution rows, and the records are those of the native measurement on
+        them.  annotate and encode work on frames of one size; a list of differing sizes with annotate stays refused."""
+
+    _window_keyword = "window"
 
     def _process_frames(self, frames, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed, burn_text=False,
-                        extra_text=None, rasterise=None):
+                        extra_text=None, rasterise=None, window=None, window_margin=32):
         got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
-                                  burn_text=burn_text, extra_text=extra_text, rasterise=rasterise)
+                                  burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, window=window,
+                                  window_margin=window_margin, window_params=lambda b: self.params)
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
         if annotate is None:
@@ -507,14 +588,25 @@ class MultiCameraMeasurer(_DeviceStage):
         conf, iou, max_det: each a scalar, or a sequence with one entry per camera (stations with their own thresholds, config.py:
         69-73): the one predict then runs under an NMS table of one row per camera with `cameras` as the row index
         (vti_set_nms_table), every frame comes out as its camera's scalars alone would give it, and the output set is allocated for
-        the largest max_det.  A sequence of another length is a ValueError before anything is predicted."""
+        the largest max_det.  A sequence of another length is a ValueError before anything is predicted.
+        windows (keyword only): None, "roi", or a list with one entry per CAMERA -- (x0, y0, x1, y1), "roi" or None (the whole frame):
+        as StitchMeasurer.process_frames' window, every frame taking its camera's; window_margin (keyword only, default 32)."""
+
+    _window_keyword = "windows"
 
     def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
-                        burn_text=False, extra_text=None, rasterise=None):
+                        burn_text=False, extra_text=None, rasterise=None, window=None, window_margin=32):
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
         conf, iou, max_det, nms_rows = self._per_camera_nms(len(self.params), conf, iou, max_det)
+        if window is not None and not isinstance(window, str):                      # one window per CAMERA -> one per frame
+            if not isinstance(window, (list, tuple)) or len(window) != len(self.params):
+                raise ValueError(f"process_frames: windows must be None, \"roi\" or a list with one entry per camera ({len(self.params)})")
+            if cams.ndim != 1 or cams.dtype.kind not in "iu" or (cams.size and (cams.min() < 0 or cams.max() >= len(self.params))):
+                raise ValueError(f"process_frames: cameras must be integers in [0, {len(self.params)})")
+            window = [window[int(c)] for c in cams]
         got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
-                                  mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, nms_rows=nms_rows)
+                                  mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, nms_rows=nms_rows, window=window,
+                                  window_margin=window_margin, window_params=lambda b: self.params[int(cams[b])])
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         if annotate is None:

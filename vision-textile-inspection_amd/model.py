@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import rawframes
-from .engine import Engine, NmsParams, unpack_bits
+from .engine import check_window, Engine, NmsParams, unpack_bits
 from .weights import random_weights, unpack_container
 
 
@@ -392,6 +392,21 @@ class YOLO:
         B = len(shapes)
         eng = self._engine(H, W, B, max_det)
         dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
+        table, buf = self._frame_buffer(eng, source, shapes, dev)
+        okey = (id(eng), B, max_det, tuple(shapes) if retina_masks else None)
+        o = self._outs.get(okey)
+        if o is None:
+            self._outs.clear()
+            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=table if retina_masks else None)
+        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks),
+                                nms=nms(eng, dev) if nms is not None else None)
+        if keep_frames:
+            self._last_frames = buf
+        return eng, o, table, (H, W)
+
+    def _frame_buffer(self, eng, source, shapes, dev):
+        """The frames of a list source (or DecodedFrames / RawBatch) in the flat device buffer of their frame table on `eng`:
+        -> (FrameTable, buffer).  The packed table, the pinned staging buffer and its device twin are cached per (engine, shapes)."""
         key = (id(eng), tuple(shapes))
         ent = self._frame_tables.get(key)
         if ent is None:
@@ -412,16 +427,62 @@ class YOLO:
                     raise ValueError(f"every frame of a list source must be uint8 HxWx3, got {a.dtype}")
                 flat[off:off + 3 * h * w] = a.reshape(-1)
             buf.copy_(stage, non_blocking=True)
-        okey = (id(eng), B, max_det, tuple(shapes) if retina_masks else None)
+        return table, buf
+
+    @staticmethod
+    def _windows_arg(window, shapes):
+        """predict's `window=` for frames of `shapes` -> [(x0, y0, w, h)] per frame: one (x0, y0, x1, y1) for every frame, or a list
+        with one entry per frame (None: the whole frame); x1, y1 exclusive.  Anything else is a ValueError."""
+        B = len(shapes)
+        per_frame = isinstance(window, (list, tuple)) and len(window) > 0 and all(
+            w is None or (not isinstance(w, (str, bytes)) and hasattr(w, "__len__")) for w in window)
+        if not per_frame:
+            window = [window] * B
+        elif len(window) != B:
+            raise ValueError(f"predict: window has {len(window)} entries but the batch has {B} frames")
+        return [check_window(w, h0, w0, f"predict: window of frame {b}") for b, (w, (h0, w0)) in enumerate(zip(window, shapes))]
+
+    def _predict_outputs_windows(self, source, shapes, windows, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, keep_frames=False, nms=None):
+        """_predict_outputs_frames(retina_masks=True) on one window (x0, y0, w, h) of each frame: one vti_predict_windows on the canvas
+        predict() would pick for the contiguous crops -- LetterBox(auto=True) of the window when all windows have one size (a stacked
+        batch of crops), the stride-rounded imgsz canvas otherwise.  source: a device batch u8 [B,H0,W0,3], or what
+        _predict_outputs_frames takes.  -> (engine, ragged output set, WindowTable, (H, W))."""
+        B = len(shapes)
+        sizes = {(w[3], w[2]) for w in windows}
+        if len(sizes) == 1:
+            (h, w), = sizes
+            H, W = letterbox_shape(h, w, imgsz)
+        else:
+            new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+            H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
+        eng = self._engine(H, W, B, max_det)
+        dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
+        key = (id(eng), tuple(shapes), tuple(windows))
+        wt = getattr(self, "_window_tables", {}).get(key)
+        if wt is None:
+            wt = eng.pack_windows(shapes, windows, dev)
+            self._window_tables = {key: wt}      # one rig at a time, as the frame table
+        if isinstance(source, torch.Tensor) and source.dim() == 4:      # a device batch: its bytes are the buffer where frames stay 16-byte aligned
+            H0, W0 = shapes[0]
+            if (3 * H0 * W0) % 16 == 0 or B == 1:
+                buf = source.reshape(-1)
+                if buf.numel() < wt.total_bytes:
+                    buf = torch.cat((buf, buf.new_zeros(wt.total_bytes - buf.numel())))
+            else:
+                buf = torch.empty(wt.total_bytes, dtype=torch.uint8, device=source.device)
+                for b, off in enumerate(wt.frames.byte_offsets):
+                    buf[off:off + 3 * H0 * W0] = source[b].reshape(-1)
+        else:
+            buf = self._frame_buffer(eng, source, shapes, dev)[1]
+        okey = (id(eng), B, max_det, tuple(shapes))
         o = self._outs.get(okey)
         if o is None:
             self._outs.clear()
-            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=table if retina_masks else None)
-        eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks),
-                                nms=nms(eng, dev) if nms is not None else None)
-        if keep_frames:
-            self._last_frames = buf
-        return eng, o, table, (H, W)
+            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=wt.frames)
+        eng.predict_windows_into(buf, wt, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode,
+                                 nms=nms(eng, dev) if nms is not None else None)
+        self._last_frames = buf if keep_frames else None
+        return eng, o, wt, (H, W)
 
     def _predict_outputs(self, source, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, retina_masks, keep_frames=False, nms=None):
         """The device half of predict(): enqueues the whole pipeline into the cached output set and returns
@@ -453,7 +514,8 @@ class YOLO:
 
     @torch.inference_mode()
     def predict(self, source=None, *, verbose=False, conf=0.25, iou=0.7, max_det=300, imgsz=640,
-                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, classes=None, polygons=False, **_ignored):
+                agnostic_nms=False, swap_rb=True, retina_masks=False, mixed=False, window=None, classes=None, polygons=False,
+                **_ignored):
         """Returns list[Results], one per frame.  `swap_rb=True` keeps Ultralytics' channel flip of
         ndarray sources.  retina_masks=True: masks at the frame size, Ultralytics'
         process_mask_native (8.1/8.2 scale_masks), made on the device from the frame-px boxes.
@@ -478,7 +540,14 @@ class YOLO:
         classes (keyword only): None, an int, or a sequence / tensor of ints in [0, nc), as Ultralytics takes it: only anchors whose
         best class is in the set enter the NMS.  The filter runs on the device where Ultralytics' non_max_suppression has it --
         after the confidence test, before the greedy pass and max_det -- through a one-row NMS table (vti_set_nms_table); a bad
-        value is a ValueError before a device is touched.  Without it the call takes the table-free path."""
+        value is a ValueError before a device is touched.  Without it the call takes the table-free path.
+        window (keyword only): (x0, y0, x1, y1) for every frame, or a list with one entry per frame (None: the whole frame); x1 and y1
+        are exclusive.  The network sees only that window of each frame, read in place (vti_predict_windows), and the Results are
+        those of predict(crops, retina_masks=True, mixed=True, ...) on the contiguous crops frame[y0:y1, x0:x1] -- the same canvas,
+        detections and scores -- carried back to the frame: orig_shape is the frame's, boxes are the crop's plus (x0, y0) (one f32
+        add per coordinate), and masks are always frame-resolution rows [n, H0, 8 * ceil(W0 / 64)] with the crop's mask at the
+        window's place and zeros elsewhere; masks.xy / polygons=True trace those rows.  A window that does not lie inside its frame
+        with x0 < x1 and y0 < y1 is a ValueError before a device is touched."""
         classes = self._classes_arg(classes, self.nc)
         nms = None
         if classes is not None:
@@ -498,7 +567,27 @@ class YOLO:
             source = self._convert_raw(raws)
         shapes = self._differing_shapes(source)
         ragged = False
-        if shapes is not None:
+        if window is not None:
+            if shapes is None and not isinstance(source, (DecodedFrames, RawBatch)):
+                if source is None:
+                    raise ValueError("predict() needs a source")
+                if isinstance(source, (list, tuple)) and len(source) and all(isinstance(f, torch.Tensor) for f in source):
+                    source = torch.stack(list(source))
+                if not isinstance(source, torch.Tensor) or source.dim() not in (3, 4) or source.shape[-1] != 3 or source.dtype != torch.uint8:
+                    source = np.stack([np.asarray(f) for f in source]) if isinstance(source, (list, tuple)) else np.asarray(source)
+                    if source.ndim not in (3, 4) or source.shape[-1] != 3 or source.dtype != np.uint8:
+                        raise ValueError(f"source must be uint8 HxWx3 or BxHxWx3, got {source.dtype} {tuple(source.shape)}")
+                nB = 1 if len(source.shape) == 3 else int(source.shape[0])
+                shapes = [tuple(int(v) for v in source.shape[-3:-1])] * nB
+                windows = self._windows_arg(window, shapes)            # refused before a device is touched
+                source = self._to_device_batch(source)
+            else:
+                windows = self._windows_arg(window, shapes)
+            retina_masks, ragged = True, True
+            eng, o, wt, (H, W) = self._predict_outputs_windows(source, shapes, windows, conf, iou, max_det, imgsz, agnostic_nms, swap_rb,
+                                                               nms=nms)
+            table, B = wt.frames, len(shapes)
+        elif shapes is not None:
             if retina_masks and not mixed:
                 raise ValueError("predict: retina_masks=True needs frames of one size; the frames of this list differ in shape "
                                  "(frame-resolution masks for mixed sizes are not supported)")
