@@ -540,9 +540,9 @@ int32_t vti_annotate(vti_ctx* ctx, const uint8_t* dev_frames, int32_t B, int32_t
  * vti_predict_frames directly.  Every byte of each output picture is written and no other: not the gaps between pictures, not the
  * bytes past the last one; dev_frames is never written.  Picture k is byte for byte what vti_annotate writes for that frame when
  * called with H0[b], W0[b] on the same inputs; status, VTI_ANNOTATE_OUTLINE_SKIPPED, the plain copy of a frame with a bad camera,
- * duplicates and any order of the selection are vti_annotate's.  native = 1 is VTI_ERR_UNSUPPORTED (frames of differing sizes have
- * letterbox bit masks only); a SELECTED frame above 8192 in either dimension is VTI_ERR_ARG naming the frame (the table allows 16384,
- * the raster's fixed point does not).  dev_frames and dev_out 16-byte aligned.  Every argument check -- both tables revalidated row by
+ * duplicates and any order of the selection are vti_annotate's.  native = 1 is VTI_ERR_UNSUPPORTED (this call takes letterbox bit
+ * masks only; the ragged frame-size rows are vti_annotate_frames_native's, below); a SELECTED frame above 8192 in either dimension
+ * is VTI_ERR_ARG naming the frame (the table allows 16384, the raster's fixed point does not).  dev_frames and dev_out 16-byte aligned.  Every argument check -- both tables revalidated row by
  * row and the selection included -- runs before the first HIP call; the device copies (tables, selection) are trusted as the other
  * *_frames calls trust theirs.  The scratch regions are pitched by the largest selected frame; what lies in a region beyond a frame's
  * own extent is never read.  Three launches on `stream`, or four when the selection holds both frames whose union fits the tracer's
@@ -670,8 +670,8 @@ VTI_CHECKER_RIG_API int32_t vti_annotate_checker_cameras(vti_ctx* ctx, const uin
 /* The checker's pictures of frames of differing sizes (vti_annotate_frames' argument list and checks: the in table pair, the out table
  * pair whose row k must have the size of frame host_select[k], the selection given twice).  Picture k is byte for byte what
  * vti_annotate_checker_cameras writes for that frame at its size; the gaps between the pictures, the bytes past the last one and
- * dev_frames are never written.  Letterbox bit masks only: native = 1 is VTI_ERR_UNSUPPORTED; a selected frame above 8192 in either
- * dimension is VTI_ERR_ARG naming it.  dev_scratch: >= vti_annotate_frames_scratch_bytes(ctx, host_out_table, max_det, max_points). */
+ * dev_frames are never written.  Letterbox bit masks only: native = 1 is VTI_ERR_UNSUPPORTED (the ragged rows:
+ * vti_annotate_checker_frames_native); a selected frame above 8192 in either dimension is VTI_ERR_ARG naming it.  dev_scratch: >= vti_annotate_frames_scratch_bytes(ctx, host_out_table, max_det, max_points). */
 VTI_CHECKER_RIG_API int32_t vti_annotate_checker_frames(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table,
                                                         const void* dev_table, int32_t B, const void* dev_cameras, int32_t n_cams,
                                                         const int32_t* dev_camera_of_frame, const uint8_t* dev_masks, int32_t native,
@@ -905,7 +905,7 @@ VTI_NMS_TABLE_API int32_t vti_set_nms_table(vti_ctx* ctx, const void* host_table
  *                                           box uses the window-px box, not the shifted one); live slots are written completely, no
  *                                           byte after the last live slot is touched.
  * With the window (0, 0, W0, H0) for every frame every output byte equals vti_predict_frames_native on T_full.  So every consumer of
- * native = 1 rows or dev_mask_bases (vti_measure_frames_native, vti_annotate_frames, vti_mask_polygons_frames, vti_overlay_frames)
+ * native = 1 rows or dev_mask_bases (vti_measure_frames_native, vti_annotate_frames_native, vti_mask_polygons_frames, vti_overlay_frames)
  * takes the result unchanged, together with T_full.
  * Marks the entry points of the window family; libvti.so exports them as it does every other. */
 #define VTI_WINDOWS_API
@@ -949,6 +949,54 @@ VTI_WINDOWS_API int32_t vti_predict_windows(vti_ctx* ctx, const uint8_t* dev_fra
                                             void* dev_proto, float* dev_dets, int32_t* dev_counts, uint8_t* dev_masks,
                                             int64_t capacity_bytes, int32_t* dev_offsets, int64_t* dev_mask_bases, float* dev_xyxy,
                                             void* stream);
+
+/* ---- pictures of frames of differing sizes from their frame-resolution masks ------------------------------------------------------ */
+/* vti_annotate_frames and vti_annotate_checker_frames for the ragged frame-size rows of vti_masks_native_frames /
+ * vti_predict_frames_native / vti_predict_windows, measured by vti_measure_frames_native (checker: vti_measure_checker_frames_native).
+ * The arguments are those of the letterbox forms with two changes: there is no `native` argument, and dev_mask_bases (i64 [B + 1],
+ * 8-byte aligned, required) and capacity_bytes (>= 0) follow dev_masks, as in vti_measure_frames_native.  Instance i of frame b is
+ * H0[b] rows of ceil(W0[b] / 64) 64-bit words from byte dev_mask_bases[b] + i * slot_bytes[b] on.  `capacity` counts slot INDICES
+ * (dev_offsets[b] + i), the rows of stitch_f64 / stitch_i32 the measurement wrote.
+ * Picture k and dev_status[k] are byte for byte what vti_annotate(native = 1) (checker: vti_annotate_checker_cameras(native = 1))
+ * writes for frame b = select[k] when called with H0[b], W0[b] on that frame's run of slots as a uniform [n, H0, row_bytes] buffer,
+ * and `capacity` cuts the slot index as it does there.  A slot that does not end at or before capacity_bytes is what the
+ * measurement of its family made of it.  vti_annotate_frames_native: all zeros in that buffer, its per-slot rows still read --
+ * vti_measure_frames_native wrote them, for the same empty mask.  vti_annotate_checker_frames_native: not in that buffer at all, a
+ * slot at or beyond the uniform call's capacity (an empty mask with its box, no per-slot row) -- vti_measure_checker_frames_native
+ * counts it so and writes no row for it.  No byte of dev_masks at or beyond capacity_bytes is read; a base that is negative or no
+ * multiple of 8 gives its frame no readable slot.
+ * Everything else is vti_annotate_frames': the out table, every byte of each picture written and no other, the plain copy of a frame
+ * with a bad camera, duplicates and any order of the selection, VTI_ANNOTATE_OUTLINE_SKIPPED, the 8192 limit on a SELECTED frame,
+ * three or four launches on `stream`, no host synchronisation.  Every argument check runs before the first HIP call: those of
+ * vti_annotate_frames as they stand; dev_mask_bases non-null and 8-byte aligned; capacity_bytes >= 0; dev_masks 8-byte aligned when
+ * capacity_bytes > 0, and NULL only when capacity_bytes == 0.  The checker form's letterbox "resize tables" canvas check does not
+ * apply (no letterbox mask is resized).  dev_scratch: >= vti_annotate_frames_scratch_bytes(ctx, host_out_table, max_det, max_points).
+ * Marks the two entry points; libvti.so exports them as it does every other. */
+#define VTI_ANNOTATE_NATIVE_API
+VTI_ANNOTATE_NATIVE_API int32_t vti_annotate_frames_native(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table,
+                                                           const void* dev_table, int32_t B, const void* dev_cameras, int32_t n_cams,
+                                                           const int32_t* dev_camera_of_frame, const uint8_t* dev_masks,
+                                                           const int64_t* dev_mask_bases, int64_t capacity_bytes, const float* dev_dets,
+                                                           const float* dev_xyxy, const int32_t* dev_counts, const int32_t* dev_offsets,
+                                                           int32_t max_det, int32_t capacity, const int32_t* frame_i32,
+                                                           const double* stitch_f64, const int32_t* stitch_i32,
+                                                           const int32_t* host_select, const int32_t* dev_select, int32_t n_sel,
+                                                           int32_t max_points, const void* host_out_table, const void* dev_out_table,
+                                                           uint8_t* dev_out, int32_t* dev_status, void* dev_scratch, size_t scratch_bytes,
+                                                           void* stream);
+/* dev_cameras: a table of vti_checker_pack_cameras; frame_i32, stitch_f64, stitch_i32: what vti_measure_checker_frames_native wrote. */
+VTI_ANNOTATE_NATIVE_API int32_t vti_annotate_checker_frames_native(vti_ctx* ctx, const uint8_t* dev_frames, const void* host_table,
+                                                                   const void* dev_table, int32_t B, const void* dev_cameras,
+                                                                   int32_t n_cams, const int32_t* dev_camera_of_frame,
+                                                                   const uint8_t* dev_masks, const int64_t* dev_mask_bases,
+                                                                   int64_t capacity_bytes, const float* dev_dets, const float* dev_xyxy,
+                                                                   const int32_t* dev_counts, const int32_t* dev_offsets, int32_t max_det,
+                                                                   int32_t capacity, const int32_t* frame_i32, const double* stitch_f64,
+                                                                   const int32_t* stitch_i32, const int32_t* host_select,
+                                                                   const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                                                                   const void* host_out_table, const void* dev_out_table,
+                                                                   uint8_t* dev_out, int32_t* dev_status, void* dev_scratch,
+                                                                   size_t scratch_bytes, void* stream);
 
 /* ---- JPEG files -> frames on device (cap.read() of a motion-JPEG camera, cv2.imread, Ultralytics' file sources) ----------------- */
 /* n files -> n frames u8 [H0,W0,3], byte for byte the package's jpeg.decode, which is pinned to libjpeg-turbo's output with its

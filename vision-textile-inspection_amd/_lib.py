@@ -163,6 +163,10 @@ SIGNATURES = {
                                             _P, _P, _I32, _I32, _P, _P, _P, _SZ, _P]),
     "vti_annotate_checker_frames": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
                                            _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vti_annotate_frames_native": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
+                                          _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vti_annotate_checker_frames_native": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _P, _P,
+                                                  _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "vti_overlay_scratch_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32]),
     "vti_overlay": (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _F, _F, _P, _P, _I32, _I32, _P,
                            _I32, _P, _P, _P, _SZ, _P]),

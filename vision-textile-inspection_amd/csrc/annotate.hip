@@ -23,7 +23,8 @@
 // The scratch regions are then PITCHED by the largest selected frame (a frame uses the head of its slice, laid out for its own size;
 // what lies beyond is never read), the outline is launched in both instantiations when the selection needs both (each leaves the
 // frames of the other alone, by the frame's own size), and the raster grid is the largest frame's: workgroups past a frame's last
-// tile leave before the first barrier.
+// tile leave before the first barrier.  vti_annotate_frames_native / vti_annotate_checker_frames_native put the RAGGED form of the
+// two prep kernels in front of them: the masks are then the ragged frame-size rows of vti_masks_native_frames (frame_run below).
 //
 // vti_annotate_checker (the stitch-distance checker's picture, Utils/check_stitch_distance.py:293-545) puts a prep kernel of its own,
 // annotate_checker_prep_kernel, in front of the same outline and raster kernels: the same records, meta, envelope points and union,
@@ -67,6 +68,7 @@ struct AnnArgs {
     int max_points, outline_colour;         // the colour index of the outline's polylines (C_OUTLINE; the checker's: C_ENVELOPE)
     Rec* recs; int* meta; int2* env_pts; int2* cont; u64* uni;
     unsigned char* areas; size_t area_bytes, off_runs, off_rows;
+    const long long* bases; long long capacity_bytes;           // the ragged native rows (the RAGGED prep kernels only), or null
 };
 
 __device__ __forceinline__ int nrec(int max_det) { return 3 + 7 * max_det; }
@@ -77,12 +79,25 @@ __device__ __forceinline__ Geo frame_geo(const AnnArgs& a, int b) {
     const int H0 = min(max(a.rows_in[b].H0, 1), a.H0), W0 = min(max(a.rows_in[b].W0, 1), a.W0);
     return Geo{H0, W0, (W0 + 63) >> 6};
 }
+// RAGGED (vti_annotate_frames_native): frame b's run of slots in the ragged rows of vti_masks_native_frames.  Instance i starts at byte
+// bases[b] + i * slot_bytes, slot_bytes = H0 * WW * 8 (64-bit arithmetic: bases exceed 2^31), and its mask may be read iff i < fit,
+// the slots that end at or before capacity_bytes (none when the base is no offset: negative, or no multiple of 8).  A later one is an
+// all-zero mask whose per-slot rows exist in annotate_prep_kernel (vti_measure_frames_native's rule: it wrote them for an empty mask),
+// and in annotate_checker_prep_kernel what a slot at or beyond `capacity` is (vti_measure_checker_frames_native's rule: it wrote no
+// row for it); no byte at or beyond capacity_bytes is loaded.
+struct Run { const u64* at; long long fit; };
+__device__ __forceinline__ Run frame_run(const AnnArgs& a, int b, int H0, int WW) {
+    const long long base = a.bases[b], slot_bytes = (long long)H0 * WW * 8;
+    const long long fit = base >= 0 && !(base & 7) && a.capacity_bytes > base ? (a.capacity_bytes - base) / slot_bytes : 0;
+    return Run{fit > 0 ? (const u64*)(a.masks + base) : (const u64*)a.masks, fit};
+}
 // coordinates far outside any frame change nothing that is drawn; the clamp keeps the fixed-point arithmetic in range
 __device__ __forceinline__ int clampc(int v) { return min(max(v, -32768), 32767); }
 __device__ __forceinline__ int round_px(double v) { return (int)rint(fmin(fmax(v, -32768.0), 32767.0)); }   // python round(): half to even
 
-template <bool NATIVE>
+template <bool NATIVE, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
+    static_assert(NATIVE || !RAGGED, "the ragged rows are frame-size masks");
     extern __shared__ int s_env[];              // [W0]: the nearest-resize column table, then the envelope
     __shared__ int s_fab[VTI_MEASURE_MAX_DET][3];
     __shared__ int s_nfab, s_w[kThreads / 64];
@@ -110,6 +125,8 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
     // 2. boxes in detection order (measurement.py:249-272); the kept fabric instances that have a mask are listed for the union
     const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
     const int Hm = NATIVE ? H0 : a.H, wpr = NATIVE ? 2 * WW : a.W >> 5;       // rows and 32-bit words per row of a mask slot
+    Run run{nullptr, 0};
+    if (RAGGED) run = frame_run(a, b, H0, WW);
     for (int i = tid; i < n; i += kThreads) {
         const int s = s0 + i;
         const bool live = s >= 0 && s < a.capacity;
@@ -131,6 +148,7 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
                 else { ya = (int)floorf(d[1] - 8.f); yb = (int)ceilf(d[3] + 8.f); }
                 const int pos = atomicAdd(&s_nfab, 1);
                 s_fab[pos][0] = i; s_fab[pos][1] = max(ya, 0); s_fab[pos][2] = min(yb, Hm - 1);
+                if (RAGGED && i >= run.fit) { s_fab[pos][1] = 1; s_fab[pos][2] = 0; }    // cut by capacity_bytes: all zeros, no row is read
             }
         }
     }
@@ -142,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
         int any = 1;
         if (drop_empty) {
             any = 0;
-            const unsigned* m = bits + ((size_t)(s0 + i) * Hm + ya) * wpr;
+            const unsigned* m = RAGGED ? (const unsigned*)run.at + ((size_t)i * Hm + ya) * wpr : bits + ((size_t)(s0 + i) * Hm + ya) * wpr;
             const int nw = yb >= ya ? (yb - ya + 1) * wpr : 0;
             for (int j = tid; j < nw; j += kThreads) any |= m[j] != 0;
             any = __syncthreads_or(any);
@@ -169,7 +187,10 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
     for (int idx = tid; idx < H0 * WW; idx += kThreads) {
         const int y = idx / WW, w = idx - y * WW;
         u64 acc = 0;
-        if (NATIVE) {
+        if (RAGGED) {
+            for (int f = 0; f < nfab; ++f)
+                if (y >= s_fab[f][1] && y <= s_fab[f][2]) acc |= run.at[(size_t)s_fab[f][0] * H0 * WW + idx];
+        } else if (NATIVE) {
             for (int f = 0; f < nfab; ++f)
                 if (y >= s_fab[f][1] && y <= s_fab[f][2]) acc |= ((const u64*)a.masks)[(size_t)(s0 + s_fab[f][0]) * H0 * WW + idx];
         } else {
@@ -273,8 +294,11 @@ __global__ __launch_bounds__(kThreads) void annotate_prep_kernel(AnnArgs a) {
 // before the row's address is formed (a frame whose index is outside is copied as it is), and the frame's size and the placement of
 // the in and out frames come from the frame tables when there are any (frame_geo; the union and the point lists keep the pitches of
 // the largest selected frame).
-template <bool NATIVE, bool TABLE = false>
+// RAGGED (vti_annotate_checker_frames_native): the masks are the ragged rows (frame_run); an instance is live when its slot index is
+// below `capacity` AND its slot ends at or before capacity_bytes, the liveness of vti_measure_checker_frames_native.
+template <bool NATIVE, bool TABLE = false, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void annotate_checker_prep_kernel(AnnArgs a, CameraRow c) {
+    static_assert(!RAGGED || (NATIVE && TABLE), "the ragged rows are frame-size masks of a frame table");
     extern __shared__ int s_env[];              // [W0]: the nearest-resize column table, then the envelope | hit bits [W / 32], [H / 32]
     __shared__ int s_fab[VTI_MEASURE_MAX_DET][5];       // instance i (< 0: a filled box), first and last row, first and last column
     __shared__ int s_nfab, s_w[kThreads / 64];
@@ -298,6 +322,11 @@ __global__ __launch_bounds__(kThreads) void annotate_checker_prep_kernel(AnnArgs
     const int n = min(max(a.counts[b], 0), M), s0 = a.offsets[b];
     const int Hm = NATIVE ? H0 : a.H, wpr = NATIVE ? 2 * WW : a.W >> 5;       // rows and 32-bit words per row of a mask slot
     const double ify = 1.0 / ((double)H0 / (double)a.H), ifx = 1.0 / ((double)W0 / (double)a.W);
+    Run run{nullptr, 0};
+    if (RAGGED) {                               // the frame's first slot that is not live, as vti_measure_checker_frames_native cuts it
+        run = frame_run(a, b, H0, WW);
+        a.capacity = (int)min((long long)a.capacity, (long long)s0 + run.fit);
+    }
     unsigned* s_col = (unsigned*)(s_env + W0);          // source columns / rows that a frame column / row is resized from
     unsigned* s_row = s_col + ((a.W + 31) >> 5);
     if (!NATIVE) {
@@ -355,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void annotate_checker_prep_kernel(AnnArgs
         const int i = s_fab[f][0], ya = s_fab[f][1], yb = s_fab[f][2];
         if (i < 0) continue;                    // uniform
         int raw = 0, res = 0;
-        const unsigned* m = bits + ((size_t)(s0 + i) * Hm + ya) * wpr;
+        const unsigned* m = RAGGED ? (const unsigned*)run.at + ((size_t)i * Hm + ya) * wpr : bits + ((size_t)(s0 + i) * Hm + ya) * wpr;
         const int nw = yb >= ya ? (yb - ya + 1) * wpr : 0;
         for (int j = tid; j < nw; j += kThreads) {
             const unsigned word = m[j];
@@ -396,7 +425,9 @@ __global__ __launch_bounds__(kThreads) void annotate_checker_prep_kernel(AnnArgs
                 continue;
             }
             if (sy < s_fab[f][1] || sy > s_fab[f][2]) continue;
-            if (NATIVE) {
+            if (RAGGED) {
+                acc |= run.at[(size_t)i * H0 * WW + idx];
+            } else if (NATIVE) {
                 acc |= ((const u64*)a.masks)[(size_t)(s0 + i) * H0 * WW + idx];
             } else {
                 const unsigned* srow = bits + ((size_t)(s0 + i) * a.H + sy) * wpr;
@@ -720,6 +751,7 @@ static AnnArgs annotate_args(AnnotateLayout& L, const uint8_t* frames, int H0, i
     a.recs = (Rec*)(ws + L.off_recs); a.meta = (int*)(ws + L.off_meta); a.env_pts = (int2*)(ws + L.off_env);
     a.cont = (int2*)(ws + L.off_cont); a.uni = (u64*)(ws + L.off_union);
     a.areas = ws + L.off_areas; a.area_bytes = L.area_bytes; a.off_runs = L.off_runs; a.off_rows = L.off_rows;
+    if (fr && o.native) { a.bases = o.bases; a.capacity_bytes = o.capacity_bytes; }     // the ragged rows: with frame tables only
     return a;
 }
 
@@ -741,10 +773,12 @@ static hipError_t launch_outline_raster(const AnnArgs& a, const AnnotateLayout& 
 
 hipError_t launch_annotate(const uint8_t* frames, int H0, int W0, const CameraChoice& cams, const OutputSet& o, const Canvas& cv,
                            const DrawInputs& d, hipStream_t st, const AnnotateFrames* fr) {
+    if (fr && o.native && (!o.bases || o.capacity_bytes < 0)) return hipErrorInvalidValue;      // native with tables needs bases
     AnnotateLayout L;
     const AnnArgs a = annotate_args(L, frames, H0, W0, cams, o, cv, d, C_OUTLINE, fr);
     const size_t env_lds = (size_t)W0 * sizeof(int);
-    if (o.native) hipLaunchKernelGGL(annotate_prep_kernel<true>, dim3(d.n_sel), dim3(kThreads), env_lds, st, a);
+    if (a.bases) hipLaunchKernelGGL((annotate_prep_kernel<true, true>), dim3(d.n_sel), dim3(kThreads), env_lds, st, a);
+    else if (o.native) hipLaunchKernelGGL(annotate_prep_kernel<true>, dim3(d.n_sel), dim3(kThreads), env_lds, st, a);
     else hipLaunchKernelGGL(annotate_prep_kernel<false>, dim3(d.n_sel), dim3(kThreads), env_lds, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -755,7 +789,7 @@ hipError_t launch_annotate_checker(const vti_checker_params* p, const uint8_t* f
                                    const OutputSet& o, const Canvas& cv, const DrawInputs& d, hipStream_t st,
                                    const AnnotateFrames* fr) {
     if (!p && !cams.table) return hipErrorInvalidValue;
-    if (fr && (p || o.native)) return hipErrorInvalidValue;
+    if (fr && (p || (o.native && (!o.bases || o.capacity_bytes < 0)))) return hipErrorInvalidValue;     // native with tables needs bases
     AnnotateLayout L;
     const AnnArgs a = annotate_args(L, frames, H0, W0, p ? CameraChoice{} : cams, o, cv, d, C_ENVELOPE, fr);
     CameraRow c;
@@ -765,7 +799,8 @@ hipError_t launch_annotate_checker(const vti_checker_params* p, const uint8_t* f
     const size_t lds = o.native ? (size_t)W0 * sizeof(int)
                                 : ((size_t)W0 + (size_t)((cv.W + 31) / 32) + (size_t)((cv.H + 31) / 32)) * sizeof(int);
     const dim3 grid(d.n_sel), block(kThreads);
-    if (p && o.native) hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, grid, block, lds, st, a, c);
+    if (a.bases) hipLaunchKernelGGL((annotate_checker_prep_kernel<true, true, true>), grid, block, lds, st, a, c);
+    else if (p && o.native) hipLaunchKernelGGL(annotate_checker_prep_kernel<true>, grid, block, lds, st, a, c);
     else if (p) hipLaunchKernelGGL(annotate_checker_prep_kernel<false>, grid, block, lds, st, a, c);
     else if (o.native) hipLaunchKernelGGL((annotate_checker_prep_kernel<true, true>), grid, block, lds, st, a, c);
     else hipLaunchKernelGGL((annotate_checker_prep_kernel<false, true>), grid, block, lds, st, a, c);

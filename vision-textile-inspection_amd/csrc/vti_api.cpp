@@ -1498,6 +1498,7 @@ struct AnnotateCall {
     const char* fn; bool checker; const vti_checker_params* p; const uint8_t* frames;
     // the *_frames forms: the host tables and what selection_walk() found (then H0, W0 below are s->mh, s->mw)
     const void* host_table; const void* host_out_table; Selection* s;
+    bool ragged;                // the *_frames_native forms: the masks are the ragged rows (o.native is 1, o.bases given)
 };
 
 // Every check of the drawing calls but those of the frame tables themselves, in the order each entry point has always made them, and
@@ -1508,8 +1509,10 @@ static int32_t annotate_check(const AnnotateCall& a, vti_ctx* c, int32_t& H0, in
     const vti_desc& desc = c->plan.desc;
     const bool bad_canvas = a.checker && !o.native && ((desc.W & 31) || (size_t)(4 * desc.W + 2 * desc.H) * 4 > 60 * 1024);
     const char* unsuitable = "letterbox size unsuitable for the resize tables";
+    // which masks the kernels may read: the ragged rows are cut by capacity_bytes, every other set by the slot count
+    const bool reads_masks = a.ragged ? o.capacity_bytes > 0 : o.capacity != 0;
     if (a.s) {
-        if (o.capacity < 0 || cams.n_cams < 1 || o.native != 0 || o.max_det < 1 || o.max_det > VTI_MEASURE_MAX_DET || d.max_points < 0)
+        if (o.capacity < 0 || cams.n_cams < 1 || (!a.ragged && o.native != 0) || o.max_det < 1 || o.max_det > VTI_MEASURE_MAX_DET || d.max_points < 0)
             return refuse(c, fn, "bad size (n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; native 0)");
     } else if (o.B < 1 || o.capacity < 0 || (!a.p && cams.n_cams < 1) || (o.native != 0 && o.native != 1) ||
                !annotate_sizes_ok(d.n_sel, o.max_det, H0, W0, d.max_points))
@@ -1518,7 +1521,7 @@ static int32_t annotate_check(const AnnotateCall& a, vti_ctx* c, int32_t& H0, in
                                  : "bad size (B, n_sel, n_cams >= 1; capacity, max_points >= 0; 1 <= max_det <= VTI_MEASURE_MAX_DET; "
                                    "1 <= H0, W0 <= 8192; native 0 or 1)");
     if (!a.frames || (!a.p && !cams.table) || !o.dets || !o.xyxy || !o.counts || !o.offsets || !d.frame_i32 || !d.stitch_f64 ||
-        !d.stitch_i32 || !d.host_select || !d.dev_select || !d.out || !d.status || (o.capacity && !o.masks))
+        !d.stitch_i32 || !d.host_select || !d.dev_select || !d.out || !d.status || (reads_masks && !o.masks))
         return refuse(c, fn, "null pointer");
     if (a.p)
         if (const char* e = settings_error(*a.p)) return refuse(c, fn, e);
@@ -1537,7 +1540,7 @@ static int32_t annotate_check(const AnnotateCall& a, vti_ctx* c, int32_t& H0, in
         if ((uintptr_t)d.dev_select & 3) return refuse(c, fn, "the selection must be 4-byte aligned");
     } else if (((uintptr_t)cams.table & 15) || ((uintptr_t)cams.cam_of_frame & 3) || ((uintptr_t)d.dev_select & 3))
         return refuse(c, fn, "the camera table must be 16-byte aligned, the index arrays 4-byte aligned");
-    VTI_TRY(mask_align_check(fn, c, o.capacity ? o.masks : nullptr, o.native));
+    VTI_TRY(mask_align_check(fn, c, reads_masks ? o.masks : nullptr, o.native));
     if (!a.s && bad_canvas) return refuse(c, fn, unsuitable);
     VTI_TRY(meas_rows_check(fn, c, d.frame_i32, d.stitch_f64, d.stitch_i32, d.status));
     VTI_TRY(scratch_check(fn, c, d.scratch, d.scratch_bytes, vti_annotate_scratch_bytes(c, d.n_sel, o.max_det, H0, W0, d.max_points),
@@ -1682,6 +1685,7 @@ int64_t vti_overlay_frames_scratch_bytes(const vti_ctx* c, const void* host_out_
 
 // vti_annotate_frames and vti_annotate_checker_frames (checker: the table is the checker's, the prep kernel the checker's own): the
 // two frame tables, then annotate_impl's checks and launches
+// one_size == nullptr: the *_frames_native forms (o.native is 1 and o.bases, o.capacity_bytes are the caller's)
 static int32_t annotate_frames_impl(const char* fn, const char* out_fn, const char* one_size, bool checker, vti_ctx* c,
                                     const uint8_t* frames, const void* host_table, const void* dev_table, const void* host_out_table,
                                     const void* dev_out_table, const CameraChoice& cams, const OutputSet& o, const DrawInputs& d,
@@ -1692,10 +1696,16 @@ static int32_t annotate_frames_impl(const char* fn, const char* out_fn, const ch
     VTI_TRY(frames_check(fn, c, host_table, dev_table, o.B, h));
     if (d.n_sel < 1) return refuse(c, fn, "n_sel must be >= 1");
     VTI_TRY(frames_check(out_fn, c, host_out_table, dev_out_table, d.n_sel, h));
-    if (o.native == 1) return refuse(c, fn, one_size, VTI_ERR_UNSUPPORTED);
+    const bool ragged = one_size == nullptr;
+    if (ragged) {
+        if (!o.bases) return refuse(c, fn, "null dev_mask_bases");
+        if ((uintptr_t)o.bases & 7) return refuse(c, fn, "dev_mask_bases must be 8-byte aligned");
+        if (o.capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
+    } else if (o.native == 1)
+        return refuse(c, fn, one_size, VTI_ERR_UNSUPPORTED);
     Selection s;
     AnnotateFrames fr{frame_rows(dev_table), frame_rows(dev_out_table), false, false, 0};
-    return annotate_impl({fn, checker, nullptr, frames, host_table, host_out_table, &s}, c, 0, 0, cams, o, d, stream, &fr);
+    return annotate_impl({fn, checker, nullptr, frames, host_table, host_out_table, &s, ragged}, c, 0, 0, cams, o, d, stream, &fr);
 }
 
 int32_t vti_annotate_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
@@ -1723,6 +1733,36 @@ int32_t vti_annotate_checker_frames(vti_ctx* c, const uint8_t* frames, const voi
         "vti_annotate_checker_frames", "vti_annotate_checker_frames (out table)",
         "native masks need frames of one size (vti_annotate_checker_cameras)", true, c, frames, host_table, dev_table, host_out_table,
         dev_out_table, {cameras, n_cams, cam_of_frame}, {masks, native, dets, xyxy, counts, offsets, B, max_det, capacity, nullptr, 0},
+        {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes}, stream);
+}
+
+int32_t vti_annotate_frames_native(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                                   const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                   const int64_t* mask_bases, int64_t capacity_bytes, const float* dets, const float* xyxy,
+                                   const int32_t* counts, const int32_t* offsets, int32_t max_det, int32_t capacity,
+                                   const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                                   const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                                   const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status, void* scratch,
+                                   size_t scratch_bytes, void* stream) {
+    return annotate_frames_impl(
+        "vti_annotate_frames_native", "vti_annotate_frames_native (out table)", nullptr, false, c, frames, host_table, dev_table,
+        host_out_table, dev_out_table, {cameras, n_cams, cam_of_frame},
+        {masks, 1, dets, xyxy, counts, offsets, B, max_det, capacity, (const long long*)mask_bases, capacity_bytes},
+        {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes}, stream);
+}
+
+int32_t vti_annotate_checker_frames_native(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                                           const void* cameras, int32_t n_cams, const int32_t* cam_of_frame, const uint8_t* masks,
+                                           const int64_t* mask_bases, int64_t capacity_bytes, const float* dets, const float* xyxy,
+                                           const int32_t* counts, const int32_t* offsets, int32_t max_det, int32_t capacity,
+                                           const int32_t* frame_i32, const double* stitch_f64, const int32_t* stitch_i32,
+                                           const int32_t* host_select, const int32_t* dev_select, int32_t n_sel, int32_t max_points,
+                                           const void* host_out_table, const void* dev_out_table, uint8_t* out, int32_t* status,
+                                           void* scratch, size_t scratch_bytes, void* stream) {
+    return annotate_frames_impl(
+        "vti_annotate_checker_frames_native", "vti_annotate_checker_frames_native (out table)", nullptr, true, c, frames, host_table,
+        dev_table, host_out_table, dev_out_table, {cameras, n_cams, cam_of_frame},
+        {masks, 1, dets, xyxy, counts, offsets, B, max_det, capacity, (const long long*)mask_bases, capacity_bytes},
         {frame_i32, stitch_f64, stitch_i32, host_select, dev_select, n_sel, max_points, out, status, scratch, scratch_bytes}, stream);
 }
 

@@ -89,15 +89,16 @@ class _Family:
     pack_fn: str
     measure_method: str
     measure: tuple          # one settings struct, a camera table, a frame table, a frame table with ragged native rows
-    annotate: tuple         # one settings struct (None: no such call), a camera table, a frame table
+    annotate: tuple         # one settings struct (None: no such call), a camera table, a frame table, a frame table with ragged rows
 
 
 _PROCESS_FRAME = _Family(VtiMeasureParams, "MeasureParams", "pack_cameras", "vti_measure_pack_cameras", "measure",
                          ("vti_measure", "vti_measure_cameras", "vti_measure_frames", "vti_measure_frames_native"),
-                         (None, "vti_annotate", "vti_annotate_frames"))
+                         (None, "vti_annotate", "vti_annotate_frames", "vti_annotate_frames_native"))
 _CHECKER = _Family(VtiCheckerParams, "CheckerParams", "pack_checker_cameras", "vti_checker_pack_cameras", "measure_checker",
                    ("vti_measure_checker", "vti_measure_checker_cameras", "vti_measure_checker_frames", "vti_measure_checker_frames_native"),
-                   ("vti_annotate_checker", "vti_annotate_checker_cameras", "vti_annotate_checker_frames"))
+                   ("vti_annotate_checker", "vti_annotate_checker_cameras", "vti_annotate_checker_frames",
+                    "vti_annotate_checker_frames_native"))
 
 
 class FrameTable:
@@ -916,7 +917,7 @@ class Engine:
         return int(lib().vti_annotate_scratch_bytes(self._ctx, int(n_sel), int(max_det), int(H0), int(W0), int(max_points)))
 
     def annotate(self, frames, out, meas, params_or_table, select, cameras=None, native=False, result=None, max_points=16384,
-                 table=None):
+                 table=None, capacity_bytes=None):
         """The frames `select` of the batch with the reference's overlay drawn on them: vti_annotate, byte for byte
         annotate.rasterise(frame, annotate.display_list(...)).  frames: the contiguous uint8 [B,H0,W0,3] BGR device batch predict
         consumed; out: its output set; meas: measure(..., stitch_rows=True)'s dict on the same set; params_or_table: the
@@ -929,12 +930,17 @@ class Engine:
         the table describes (what predict consumed, or DecodedFrames.buf) and frame select[k] is drawn at its own size.  Returns
         dict(buf=u8 flat, table=the FrameTable of the selection (pack_frames of its shapes; the 16 latest tuples of shapes are kept), shapes,
         byte_offsets, status): picture k is buf[byte_offsets[k]:][:3 * H0 * W0].view(H0, W0, 3), and (buf, table) is what
-        encode_jpeg(..., table=) and predict_frames_into take.  `result` may preallocate buf and status.  Letterbox masks only."""
-        return self._annotate(_PROCESS_FRAME, "annotate", frames, out, meas, params_or_table, select, cameras, native, result, max_points, table)
+        encode_jpeg(..., table=) and predict_frames_into take.  `result` may preallocate buf and status.  Letterbox masks, or with
+        native=True (vti_annotate_frames_native) the ragged frame-size rows of a set from alloc_outputs(native_frames=) that
+        predict_frames_into(native=True) or predict_windows_into filled and measure(frames=table, native=True) measured; native=True
+        with any other set is a ValueError.  capacity_bytes (ragged sets only; default: all of out["masks"]): a slot that ends beyond
+        it is an empty mask, as measure() saw it; the slot indices are cut by the rows of meas["stitch_i32"]."""
+        return self._annotate(_PROCESS_FRAME, "annotate", frames, out, meas, params_or_table, select, cameras, native, result, max_points, table,
+                              capacity_bytes)
 
     # ---- the stitch-distance checker's picture (Utils/check_stitch_distance.py:293-545): vti_annotate_checker ------------------
     def annotate_checker(self, frames, out, meas, params, select, native=False, result=None, max_points=16384, cameras=None,
-                         table=None):
+                         table=None, capacity_bytes=None):
         """The frames `select` of the batch with the stitch-distance checker's picture drawn on them: vti_annotate_checker, byte for
         byte annotate.rasterise(frame, annotate.checker_display_list(...)).  frames, out, select, native, result, max_points and the
         returned dict(frames=u8 [n_sel,H0,W0,3], status=i32 [n_sel]) of device tensors are annotate()'s uniform form (the frames feed
@@ -943,17 +949,22 @@ class Engine:
         cameras (vti_annotate_checker_cameras): as measure_checker() took them; params is then a list of CheckerParams or the table
         of pack_checker_cameras().  table (vti_annotate_checker_frames): the FrameTable of a batch whose frames differ in size;
         `frames` is then the flat u8 device buffer it describes, and the call returns dict(buf, table, shapes, byte_offsets, status)
-        as annotate(table=) does: it feeds encode_jpeg(table=) and stamp(table=) unchanged.  Letterbox masks only with table=."""
-        return self._annotate(_CHECKER, "annotate_checker", frames, out, meas, params, select, cameras, native, result, max_points, table)
+        as annotate(table=) does: it feeds encode_jpeg(table=) and stamp(table=) unchanged.  With table=: letterbox masks, or with
+        native=True (vti_annotate_checker_frames_native) the ragged rows of a set from alloc_outputs(native_frames=) that
+        measure_checker(frames=table, native=True) measured; capacity_bytes as annotate() takes it."""
+        return self._annotate(_CHECKER, "annotate_checker", frames, out, meas, params, select, cameras, native, result, max_points, table,
+                              capacity_bytes)
 
-    def _annotate(self, fam, who, frames, out, meas, params, select, cameras, native, result, max_points, table):
+    def _annotate(self, fam, who, frames, out, meas, params, select, cameras, native, result, max_points, table, capacity_bytes=None):
         """annotate() and annotate_checker(): fam's calls on the arguments both take.  Only the checker has a call that takes one
         settings struct; process_frame's picture always goes through a camera table."""
-        one, with_cameras, with_frames = (name and getattr(lib(), name) for name in fam.annotate)
+        one, with_cameras, with_frames, with_ragged = (name and getattr(lib(), name) for name in fam.annotate)
+        ragged = table is not None and bool(native)
         if table is not None:
             self._check_frames(table)
-            if native:
-                raise ValueError(f"{who}: frames of differing sizes have letterbox masks only (native=True needs one frame size)")
+            if ragged and not (isinstance(out, dict) and "mask_bases" in out and out["masks"].dim() == 1):
+                raise ValueError(f"{who}: frames of differing sizes have letterbox masks only (native=True needs one frame size, "
+                                 "or the ragged set of alloc_outputs(native_frames=) with its mask_bases)")
             if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1:
                 raise ValueError(f"{who}: with table=, frames must be the flat uint8 frame buffer")
             B, H0, W0 = table.B, None, None
@@ -969,6 +980,22 @@ class Engine:
         for key in ("frame_i32", "stitch_f64", "stitch_i32"):
             if meas.get(key) is None:
                 raise ValueError(f"{who}: meas needs {key} ({fam.measure_method}(..., stitch_rows=True))")
+        if ragged:
+            self._check_ragged(out, table, max_det, who)
+            bases = out["mask_bases"]
+            if masks.dtype != torch.uint8 or not masks.is_contiguous() or bases.dtype != torch.int64 or tuple(bases.shape) != (B + 1,) \
+                    or not bases.is_contiguous():
+                raise ValueError(f"{who}: the ragged set is the flat uint8 buffer of masks_native_frames with its int64 [{B + 1}] mask_bases")
+            if capacity_bytes is None:
+                capacity_bytes = masks.numel()
+            if isinstance(capacity_bytes, bool) or not isinstance(capacity_bytes, (int, np.integer)) \
+                    or not 0 <= int(capacity_bytes) <= masks.numel():
+                raise ValueError(f"{who}: capacity_bytes must be an integer in [0, {masks.numel()}]")
+            capacity = int(meas["stitch_i32"].shape[0])                 # slot indices: the per-slot rows measure() wrote, not bytes
+            if meas["stitch_f64"].shape[0] < capacity:
+                raise ValueError(f"{who}: meas has {capacity} rows of stitch_i32 but fewer of stitch_f64")
+        elif capacity_bytes is not None:
+            raise ValueError(f"{who}: capacity_bytes belongs to table= with native=True (the ragged frame-size rows)")
         rig = one is None or cameras is not None or table is not None or isinstance(params, (list, tuple, torch.Tensor))
         if rig and isinstance(params, (list, tuple)) and cameras is not None and not isinstance(cameras, torch.Tensor):
             cameras = _camera_index(who, cameras, B, len(params), "cpu")
@@ -986,6 +1013,8 @@ class Engine:
             r["status"] = torch.empty((n_sel,), dtype=torch.int32, device=dev)
         if table is not None:
             self._check_frames(table, buf=frames)
+            if ragged and not (masks.is_cuda and out["mask_bases"].device == dev):
+                raise ValueError(f"{who}: the output set must be in device memory")
             shapes = tuple(table.shapes[int(b)] for b in sel)
             out_table = self._out_table(shapes, dev)                     # the 16 latest selections are kept
             self._selection_out(r, out_table, shapes, dev)
@@ -1004,7 +1033,11 @@ class Engine:
         mid = (_ptr(dets), _ptr(out["xyxy"]), _ptr(out["counts"]), _ptr(out["offsets"]), max_det, capacity, _ptr(meas["frame_i32"]),
                _ptr(meas["stitch_f64"]), _ptr(meas["stitch_i32"]), C.c_void_p(sel.ctypes.data), _ptr(dev_sel), n_sel, int(max_points))
         pm = _ptr(masks) if capacity else C.c_void_p(0)
-        if table is not None:
+        if ragged:
+            check(self._ctx, with_ragged(self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras),
+                                         _ptr(masks) if int(capacity_bytes) else C.c_void_p(0), _ptr(out["mask_bases"]), int(capacity_bytes),
+                                         *mid, *out_table._ptrs(), _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
+        elif table is not None:
             check(self._ctx, with_frames(self._ctx, _ptr(frames), *table._ptrs(), B, _ptr(table_c), n_cams, _ptr(cameras), pm, 0, *mid,
                                          *out_table._ptrs(), _ptr(r["buf"]), _ptr(r["status"]), _ptr(ws), ws.numel(), _stream()))
         elif rig:

@@ -168,17 +168,23 @@ class CameraStream:
                 'timestamp': datetime.now()}
 
 
+def _bool_keyword(name, value):
+    """A keyword-only switch of process_frames: True or False, anything else is a ValueError."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"process_frames: {name} must be True or False, got {value!r}")
+    return bool(value)
+
+
 def _mixed_keyword(public):
-    """process_frames' keyword-only `mixed`, `burn_text`, `extra_text` and `rasterise`.  `public` carries the signature and the documentation -- its parameter list, which ends
+    """process_frames' keyword-only `mixed`, `annotate_native`, `burn_text`, `extra_text` and `rasterise`.  `public` carries the signature and the documentation -- its parameter list, which ends
     in annotate, encode, jpeg_quality for positional callers and for inspect.signature, stays as it was -- and the work is in the
     class's _process_frames, which takes the same parameters by name and the keyword-only ones next to them: arguments all the way
     down, no state on the measurer."""
     sig = inspect.signature(public)
 
     @functools.wraps(public)
-    def process_frames(self, *args, mixed=False, burn_text=False, extra_text=None, rasterise=None, **kw):
-        if not isinstance(mixed, (bool, np.bool_)):
-            raise ValueError(f"process_frames: mixed must be True or False, got {mixed!r}")
+    def process_frames(self, *args, mixed=False, burn_text=False, extra_text=None, rasterise=None, annotate_native=False, **kw):
+        mixed, annotate_native = _bool_keyword("mixed", mixed), _bool_keyword("annotate_native", annotate_native)
         # the two measurers' keyword-only window (StitchMeasurer: window=, MultiCameraMeasurer: windows=) and window_margin; a class
         # without _window_keyword does not take them (sig.bind then refuses them as any unknown keyword)
         wkw, name = {}, getattr(self, "_window_keyword", None)
@@ -191,7 +197,24 @@ def _mixed_keyword(public):
         bound.apply_defaults()
         named = dict(bound.arguments)
         del named["self"]
-        return self._process_frames(mixed=bool(mixed), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, **named, **wkw)
+        return self._process_frames(mixed=mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise,
+                                    annotate_native=annotate_native, **named, **wkw)
+    return process_frames
+
+
+def _annotate_native_keyword(public):
+    """MultiCameraChecker.process_frames' keyword-only `annotate_native`, carried as _mixed_keyword carries its keywords: `public` keeps
+    the parameter list inspect.signature shows, the work is in the class's _process_frames, which takes the keyword next to them."""
+    sig = inspect.signature(public)
+
+    @functools.wraps(public)
+    def process_frames(self, *args, annotate_native=False, **kw):
+        annotate_native = _bool_keyword("annotate_native", annotate_native)
+        bound = sig.bind(self, *args, **kw)             # a TypeError for a bad call, as calling `public` would give
+        bound.apply_defaults()
+        named = dict(bound.arguments)
+        del named["self"]
+        return self._process_frames(annotate_native=annotate_native, **named)
     return process_frames
 
 
@@ -267,7 +290,7 @@ class _DeviceStage:
     @torch.inference_mode()
     def _frame_records(self, frames, params, cameras, conf, iou, max_det, imgsz, retina_masks, annotate=None, encode=None,
                        jpeg_quality=95, mixed=False, rows=False, burn_text=False, extra_text=None, rasterise=None, nms_rows=None,
-                       window=None, window_margin=32, window_params=None):
+                       window=None, window_margin=32, window_params=None, annotate_native=False):
         """-> (f64 [B,2], i32 [B,6]) on the host, and with `annotate` a third item: [(frame index, BGR ndarray, per-slot rows)] of the
         selected frames (encode="jpeg": the JPEG file's bytes in place of the ndarray), and a fourth: their height H0 (frames of
         differing sizes, which `mixed` allows with annotate: the list of every frame's H0).  params /
@@ -278,7 +301,9 @@ class _DeviceStage:
         and max_det is the output set's row stride.
         window: None, or what _frame_windows takes -- the predict then sees one window of each frame (vti_predict_windows) and the
         measurement runs on its frame-px boxes and frame-resolution masks (native rows, whatever retina_masks says);
-        window_params(b): frame b's MeasureParams, for "roi"."""
+        window_params(b): frame b's MeasureParams, for "roi".
+        annotate_native (with mixed, on frames of differing sizes): annotate may go with retina_masks or a window -- the pictures are
+        drawn from the ragged frame-resolution rows (vti_annotate_frames_native).  On frames of one size it changes nothing."""
         nms = None
         if nms_rows is not None:
             nms = lambda eng, dev: (self.model._nms_table(eng, dev, nms_rows), np.asarray(cameras))
@@ -302,10 +327,11 @@ class _DeviceStage:
         if window is not None:
             retina_masks = True
             if shapes is not None:
-                if annotate is not None:
+                if annotate is not None and not (mixed and annotate_native):
                     raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
                 wins = self._frame_windows(window, window_margin, shapes, window_params)
-                eng, o, wt, _ = self.model._predict_outputs_windows(frames, shapes, wins, conf, iou, max_det, imgsz, False, False, nms=nms)
+                eng, o, wt, _ = self.model._predict_outputs_windows(frames, shapes, wins, conf, iou, max_det, imgsz, False, False,
+                                                                    keep_frames=annotate is not None, nms=nms)
                 table, B, H0, W0 = wt.frames, len(shapes), None, None
             else:
                 if isinstance(frames, (list, tuple)):
@@ -332,7 +358,8 @@ class _DeviceStage:
             if annotate is not None and not mixed:
                 raise ValueError("process_frames: annotate needs frames of one size; the frames of this list differ in shape "
                                  "(vti_annotate has no frame-table form)")
-            if retina_masks and (annotate is not None or not mixed):     # mixed + retina_masks measures, but has nothing to draw from
+            # mixed + retina_masks measures; its pictures are drawn from the ragged rows, on request (annotate_native)
+            if retina_masks and (not mixed or (annotate is not None and not annotate_native)):
                 raise ValueError("process_frames: retina_masks=True needs frames of one size; the frames of this list differ in shape")
             eng, o, table, _ = self.model._predict_outputs_frames(frames, shapes, conf, iou, max_det, imgsz, False, False,
                                                                   keep_frames=annotate is not None, retina_masks=bool(retina_masks),
@@ -527,15 +554,20 @@ class StitchMeasurer(_DeviceStage):
         window_margin (keyword only, default 32) px and clipped to the frame; a disabled ROI means the whole frame.  The network then
         sees only that window of every frame, read in place (vti_predict_windows), at the canvas predict would pick for the crop;
         boxes come back in frame px and the masks as frame-resolution rows, and the records are those of the native measurement on
-        them.  annotate and encode work on frames of one size; a list of differing sizes with annotate stays refused."""
+        them.  annotate and encode work on frames of one size; a list of differing sizes with annotate needs annotate_native.
+        annotate_native (keyword only, default False; with mixed=True): True lets a list of differing sizes combine annotate (and
+        encode, burn_text) with retina_masks=True or a window: every selected frame is drawn at its own size from its
+        frame-resolution masks (vti_predict_frames_native or vti_predict_windows -> vti_measure_frames_native ->
+        vti_annotate_frames_native), one copy to the host as with letterbox masks.  Without it those combinations stay refused; on
+        frames of one size it changes nothing."""
 
     _window_keyword = "window"
 
     def _process_frames(self, frames, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed, burn_text=False,
-                        extra_text=None, rasterise=None, window=None, window_margin=32):
+                        extra_text=None, rasterise=None, window=None, window_margin=32, annotate_native=False):
         got = self._frame_records(frames, self._cp, None, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
                                   burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, window=window,
-                                  window_margin=window_margin, window_params=lambda b: self.params)
+                                  window_margin=window_margin, window_params=lambda b: self.params, annotate_native=annotate_native)
         f64, i32 = got[:2]
         records = [self._record(f64[b], i32[b]) for b in range(len(f64))]
         if annotate is None:
@@ -590,12 +622,13 @@ class MultiCameraMeasurer(_DeviceStage):
         (vti_set_nms_table), every frame comes out as its camera's scalars alone would give it, and the output set is allocated for
         the largest max_det.  A sequence of another length is a ValueError before anything is predicted.
         windows (keyword only): None, "roi", or a list with one entry per CAMERA -- (x0, y0, x1, y1), "roi" or None (the whole frame):
-        as StitchMeasurer.process_frames' window, every frame taking its camera's; window_margin (keyword only, default 32)."""
+        as StitchMeasurer.process_frames' window, every frame taking its camera's; window_margin (keyword only, default 32).
+        annotate_native (keyword only): as StitchMeasurer.process_frames."""
 
     _window_keyword = "windows"
 
     def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality, mixed,
-                        burn_text=False, extra_text=None, rasterise=None, window=None, window_margin=32):
+                        burn_text=False, extra_text=None, rasterise=None, window=None, window_margin=32, annotate_native=False):
         cams = np.asarray(cameras.cpu() if isinstance(cameras, torch.Tensor) else cameras)      # Engine.measure range-checks them
         conf, iou, max_det, nms_rows = self._per_camera_nms(len(self.params), conf, iou, max_det)
         if window is not None and not isinstance(window, str):                      # one window per CAMERA -> one per frame
@@ -606,7 +639,8 @@ class MultiCameraMeasurer(_DeviceStage):
             window = [window[int(c)] for c in cams]
         got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
                                   mixed, burn_text=burn_text, extra_text=extra_text, rasterise=rasterise, nms_rows=nms_rows, window=window,
-                                  window_margin=window_margin, window_params=lambda b: self.params[int(cams[b])])
+                                  window_margin=window_margin, window_params=lambda b: self.params[int(cams[b])],
+                                  annotate_native=annotate_native)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         if annotate is None:
@@ -752,6 +786,7 @@ class MultiCameraChecker(_DeviceStage):
             raise ValueError(f"process_frames: camera index outside [0, {len(self.params)})")
         return cams
 
+    @_annotate_native_keyword
     def process_frames(self, frames, cameras, conf=0.20, iou=0.45, max_det=200, imgsz=640, retina_masks=False, rows=False,
                        annotate=None, encode=None, jpeg_quality=95, *, mixed=False, burn_text=False, extra_text=None, rasterise=None):
         """frames as StitchDistanceChecker.process_frames takes them (a BGR uint8 batch, a list of ndarrays or JPEG files, RawFrames),
@@ -762,12 +797,18 @@ class MultiCameraChecker(_DeviceStage):
         annotate and encode (vti_annotate_checker_frames, vti_encode_jpeg_frames, vti_stamp_frames: every picture at its own size,
         the text placed by its own height), and lets retina_masks=True measure such a list (no annotate then); without it those
         combinations are refused, as MultiCameraMeasurer refuses them.  burn_text, extra_text, rasterise: as there.
-        conf, iou, max_det: each a scalar or one entry per camera, as MultiCameraMeasurer.process_frames takes them."""
+        conf, iou, max_det: each a scalar or one entry per camera, as MultiCameraMeasurer.process_frames takes them.
+        annotate_native (keyword only, default False; with mixed=True): True lets retina_masks=True on a list of differing sizes go
+        with annotate -- the pictures are drawn from the frame-resolution masks (vti_measure_checker_frames_native ->
+        vti_annotate_checker_frames_native); without it that combination stays refused, on frames of one size it changes nothing."""
+
+    def _process_frames(self, frames, cameras, conf, iou, max_det, imgsz, retina_masks, rows, annotate, encode, jpeg_quality, mixed,
+                        burn_text, extra_text, rasterise, annotate_native=False):
         cams = self._cameras(frames, cameras)
         conf, iou, max_det, nms_rows = self._per_camera_nms(len(self.params), conf, iou, max_det)
         got = self._frame_records(frames, self._table, cams, conf, iou, max_det, imgsz, retina_masks, annotate, encode, jpeg_quality,
                                   bool(mixed), rows=bool(rows), burn_text=burn_text, extra_text=extra_text, rasterise=rasterise,
-                                  nms_rows=nms_rows)
+                                  nms_rows=nms_rows, annotate_native=annotate_native)
         f64, i32 = got[:2]
         records = self._records(f64, i32, cams.tolist())
         full = lambda r, b: dict(r, status=i32[b, 0], n_stitch=i32[b, 1], n_fabric=i32[b, 2], n_dist=i32[b, 4], n_width=i32[b, 5])
