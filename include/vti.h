@@ -69,6 +69,11 @@ typedef enum {
 /* Storage type of weights and activations.  VTI_H2 = split-fp16: every element is the fp16 pair (hi, lo) of value * 16
  * (22-23 significant bits) and every product runs on the fp16 matrix pipe (two 16x16x32 MFMAs per 16 channels, fp32
  * accumulation): the results meet the reference tolerance (mask IoU >= 0.999, |d box| < 1e-3) like VTI_F32 at ~4x its matrix rate.
+ * Range of a stored VTI_H2 activation: |v| <= 4094, SATURATING (every epilogue clamps before it encodes: 4094 * 16 = 65504 is the
+ * largest fp16; a larger result is stored as +-4094, never as inf or NaN) -- 1/16 of plain fp16's range.  The lo half is a normal
+ * fp16 number down to |v| ~ 8e-3; below that a value has an absolute floor of 2^-28.  Weights carry one power-of-two scale per
+ * conv; channels far below their conv's largest have subnormal lo halves, which the fp16 MFMA keeps (measured: bit for bit).
+ * NaN inputs are not specified.
  * proto is f32 for VTI_H2 and VTI_F32, fp16 for VTI_F16. */
 enum { VTI_F16 = 0, VTI_F32 = 1, VTI_H2 = 2 };
 enum { VTI_MASK_LOGIT = 0,     /* current Ultralytics: crop, bilinear upsample, > 0.0 */

@@ -17,6 +17,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -24,6 +25,7 @@ import torch  # noqa: E402
 from oracle.model import OracleModel  # noqa: E402
 from oracle import parity as op  # noqa: E402
 from oracle.postproc import non_max_suppression, process_mask  # noqa: E402
+import h2_ref  # noqa: E402  (tests/h2_ref.py: the one statement of the h2 scheme)
 
 CONF, IOU, MAX_DET = 0.25, 0.7, 300
 
@@ -32,11 +34,14 @@ def r_fp16(t):
     return t.half().float()
 
 
-def r_h2(t, scale=16.0):
-    s = t * scale
-    hi = s.half().float()
-    lo = (s - hi).half().float()
-    return (hi + lo) / scale
+def r_h2(t):
+    """a stored activation: the saturating (hi + lo) / 16 pair."""
+    return torch.from_numpy(h2_ref.q_act(t.numpy())).to(t.dtype)
+
+
+def r_h2w(w):
+    """one conv's weights: (wh + wl) / SW with the conv's own power-of-two scale."""
+    return torch.from_numpy(h2_ref.q_w(w.numpy())).to(w.dtype)
 
 
 def r_bits(n):
@@ -50,6 +55,7 @@ def r_bits(n):
 ROUND = {"fp32": lambda t: t, "fp16": r_fp16, "h2": r_h2}
 for n in (12, 14, 16, 18, 20):
     ROUND[f"m{n}"] = r_bits(n)
+W_ROUND = dict(ROUND, h2=r_h2w)
 
 
 class PolicyModel(OracleModel):
@@ -60,7 +66,7 @@ class PolicyModel(OracleModel):
         self.policy = policy
         self.inp_round = ROUND[policy("input")[0]]
         for name, (w, b, k, s, kind) in list(self.p.items()):
-            self.p[name] = (ROUND[policy(name)[1]](w), b, k, s, kind)
+            self.p[name] = (W_ROUND[policy(name)[1]](w), b, k, s, kind)
         self._cur = None
 
     def q(self, t):

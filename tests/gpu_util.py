@@ -52,6 +52,29 @@ def storage_ulp(dtype, vmax):
     return 2.0 ** (math.floor(math.log2(max(vmax, 2.0 ** -14))) - (SIG_BITS[dtype] - 1))
 
 
+def h2_oracle(blob, H, W):
+    """The fp32 oracle with the h2 storage's rounding (tests/h2_ref.py) where the h2 engine rounds: every conv's weights as one
+    (wh + wl) / SW per conv, the input and every stored conv output as a saturating (hi + lo) / 16 pair."""
+    import h2_ref
+    from oracle.model import OracleModel
+
+    class H2Oracle(OracleModel):
+        def __init__(self, blob, H, W):
+            super().__init__(blob, H, W, "fp32")
+            for name, (w, b, k, s, kind) in list(self.p.items()):
+                self.p[name] = (torch.from_numpy(h2_ref.q_w(w.numpy())).float(), b, k, s, kind)
+
+        def q(self, t):
+            return torch.from_numpy(h2_ref.q_act(t.numpy())).float()
+
+    return H2Oracle(blob, H, W)
+
+
+def plan_families(table):
+    """The kernel families of a plan: (k, s, kind, fused, persistent) of its conv-table rows."""
+    return {(t["k"], t["s"], t["kind"], bool(t["fused"]), bool(t["persistent"])) for t in table}
+
+
 def clipped_mask(t, B, folded=False, n=None):
     """bool [n, h, w] (the first n of the B frames that ran; default all): the output pixels of conv-table row `t` that the kernel computes in a tile clipped by the map's edge, or
     None where the map divides into whole tiles (or where every pixel sits in a clipped tile, so there is nothing to compare with).

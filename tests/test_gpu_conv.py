@@ -100,6 +100,45 @@ def test_conv_exact_integers(case, dtype, monkeypatch):
         assert (got[..., :oc] == 0).all() and (got[..., oc + c2:] == 0).all()
 
 
+def split_exact_case(case):
+    """h2 only: the operands of `case` with NONZERO lo halves in both operands (h2_ref.split_operands: 60 % of the activations'
+    lo halves, a third of the weights'), asserted split-exact on the host -- every product and partial sum of
+    sum wh (xh + xl) + wl xh is exact in fp32 in any order, and the result is exactly an h2 pair."""
+    import h2_ref
+    k, s, kind, c1, c2, H, W, _, ex = case
+    seed = (hash((k, s, kind, c1, c2, H, W)) + 1) % (2 ** 32)
+    wshape = (c1, c2, k, k) if kind == 2 else (c2, c1, k, k)
+    return h2_ref.split_case(seed, (2, H, W, ex.get("in_ld", c1)), ex.get("in_coff", 0), c1, wshape, k, s, kind, res=bool(ex.get("res")))
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: f"k{c[0]}s{c[1]}kind{c[2]}_{c[3]}to{c[4]}_{c[5]}x{c[6]}_wn{c[7][0]}n{c[7][1]}")
+def test_conv_split_exact_h2(case, monkeypatch):
+    """The cases of test_conv_exact_integers on operands whose lo halves are not zero: the wh * xl and wl * xh products, the
+    operand split and the WL = (lo, 0) operand of every kernel variant, BIT FOR BIT against the scheme (h2_ref.conv_scheme).
+    A hi-only evaluation differs in 98 % of the outputs (test_h2_ref.py), so a lost or misplaced lo operand cannot pass."""
+    need_gpu()
+    import h2_ref
+    import vti_amd
+    k, s, kind, c1, c2, H, W, (wn, nrep), ex = case
+    if "pk_wgs" in ex:
+        monkeypatch.setenv("VTI_PK_MAX_WGS", str(ex["pk_wgs"]))
+    x_full, x, w, b, res, want = split_exact_case(case)
+    out_f32, oc = ex.get("out_f32", False), ex.get("out_coff", 0)
+    out, _, cfg = vti_amd.debug_conv2d(_to_dev(x_full, "h2"), w, b, k, s, kind, "h2", res=None if res is None else _to_dev(res, "h2"),
+                                       in_coff=ex.get("in_coff", 0), c1=c1, out_coff=oc, out_ld=ex.get("out_ld"),
+                                       out_f32=out_f32, waves_n=wn, nrep=nrep)
+    torch.cuda.synchronize()
+    if out_f32:
+        got, ref = out.cpu(), torch.from_numpy(want.astype(np.float32))
+    else:       # the stored dwords themselves
+        got, ref = out.cpu().view(torch.int32), torch.from_numpy(h2_ref.bits(*h2_ref.enc_act(want)))
+    assert torch.equal(got[..., oc:oc + c2], ref), f"cfg={cfg} differing outputs: {(got[..., oc:oc + c2] != ref).float().mean():.3f}"
+    if k == 3 and s == 1 and W >= 20:
+        assert cfg["pk"], cfg
+    if oc:
+        assert (got[..., :oc] == 0).all() and (got[..., oc + c2:] == 0).all()
+
+
 @pytest.mark.parametrize("dtype,tol", [("fp16", 2e-3), ("fp32", 2e-6), ("h2", 4e-6)])
 def test_conv_silu_random(dtype, tol):
     """Random operands + fused bias/SiLU/residual epilogue: within rounding of the CPU op."""

@@ -72,6 +72,44 @@ def test_conv1x1_per_tile_wreg(case, dtype, monkeypatch):
     assert cfg["1"]["lds"] == cfg["0"]["lds"] - wn * nrep * 1024, (cfg["0"], cfg["1"])      # no weight image: the register path ran
 
 
+def split_exact_case(c1, c2, H, W, ex, seed):
+    """h2 only: the case's operands with nonzero lo halves in both operands, asserted split-exact on the host (test_gpu_conv.py)."""
+    import h2_ref
+    return h2_ref.split_case(seed, (2, H, W, ex.get("in_ld", c1)), ex.get("in_coff", 0), c1, (c2, c1, 1, 1), 1, 1, 1)
+
+
+def _split_arms(monkeypatch, c1, c2, H, W, wn, nrep, ex, seed, tile, pk):
+    """Both VTI_CONV1_WREG arms on the split-exact operands: the stored dwords equal the scheme's, bit for bit."""
+    import h2_ref
+    import vti_amd
+    x_full, _, w, b, _, want = split_exact_case(c1, c2, H, W, ex, seed)
+    ref = torch.from_numpy(h2_ref.bits(*h2_ref.enc_act(want)))
+    oc = ex.get("out_coff", 0)
+    xd = _to_dev(x_full, "h2")
+    cfg = {}
+    for arm in ("0", "1"):
+        monkeypatch.setenv("VTI_CONV1_WREG", arm)
+        out, _, cfg[arm] = vti_amd.debug_conv2d(xd, w, b, 1, 1, 1, "h2", in_coff=ex.get("in_coff", 0), c1=c1, out_coff=oc,
+                                                out_ld=ex.get("out_ld"), tile=tile, waves_n=wn, nrep=nrep)
+        torch.cuda.synchronize()
+        got = out.cpu().view(torch.int32)
+        assert bool(cfg[arm]["pk"]) == pk and cfg[arm]["waves_n"] == wn and cfg[arm]["nrep"] == nrep, cfg[arm]
+        assert torch.equal(got[..., oc:oc + c2], ref), f"VTI_CONV1_WREG={arm} cfg={cfg[arm]} differing outputs: {(got[..., oc:oc + c2] != ref).float().mean():.3f}"
+        if oc:
+            assert (got[..., :oc] == 0).all() and (got[..., oc + c2:] == 0).all()
+    return cfg
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}to{c[1]}_{c[2]}x{c[3]}_wn{c[4][0]}n{c[4][1]}{'_slices' if c[5] else ''}")
+def test_conv1x1_per_tile_wreg_split_exact_h2(case, monkeypatch):
+    """The cases above with nonzero lo halves (h2): the lo operands of the LDS-staged and of the register-fed weight fragments."""
+    need_gpu()
+    c1, c2, H, W, (wn, nrep), ex = case
+    monkeypatch.setenv("VTI_NO_PK1", "1")
+    cfg = _split_arms(monkeypatch, c1, c2, H, W, wn, nrep, ex, c1 * 100003 + c2 * 101 + H * 7 + nrep + 1, (0, 0), False)
+    assert cfg["1"]["lds"] == cfg["0"]["lds"] - wn * nrep * 1024, cfg
+
+
 # ---- conv1_pk with the n-group's weights in the compute waves' registers (pk_wstat == 2)
 # (nrep, wn, K chunks) with a register-resident instantiation (conv_pk.hip: Conv1PkWH2 / Conv1PkWF16; none for fp32): the
 # instantiations that compile without spills.  Every other case must run today's kernel, with an unchanged LDS image.
@@ -128,3 +166,16 @@ def test_conv1_pk_wreg(case, dtype, monkeypatch):
         assert cfg["1"]["lds"] < cfg["0"]["lds"], (cfg["0"], cfg["1"])      # no weight image in LDS: the register path ran
     else:
         assert cfg["1"]["lds"] == cfg["0"]["lds"], (cfg["0"], cfg["1"])     # no instantiation for this chunk count: today's kernel
+
+
+@pytest.mark.parametrize("case", PK_CASES, ids=lambda c: f"{c[0]}to{c[1]}_{c[2]}x{c[3]}_wn{c[4][0]}n{c[4][1]}_wgs{c[5]}{'_slices' if c[6] else ''}")
+def test_conv1_pk_wreg_split_exact_h2(case, monkeypatch):
+    """The persistent 1x1's cases with nonzero lo halves (h2): prepared and raw register-resident fragments, and the LDS image."""
+    need_gpu()
+    c1, c2, H, W, (wn, nrep), wgs, ex = case
+    monkeypatch.delenv("VTI_NO_PK1", raising=False)
+    if wgs:
+        monkeypatch.setenv("VTI_PK_MAX_WGS", str(wgs))
+    cfg = _split_arms(monkeypatch, c1, c2, H, W, wn, nrep, ex, c1 * 100003 + c2 * 101 + H * 7 + wgs + 1, (1, 80), True)
+    engages = (nrep, wn, -(-c1 // 16)) in PK_WREG["h2"]
+    assert (cfg["1"]["lds"] < cfg["0"]["lds"]) if engages else (cfg["1"]["lds"] == cfg["0"]["lds"]), cfg

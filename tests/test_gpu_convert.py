@@ -48,12 +48,40 @@ def _scaled_state_dict(eng):
     return sd
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "fp16"])
+def _wide_bn_state_dict(eng):
+    """BatchNorm statistics as trained checkpoints have them, not all alike: bn.weight log-uniform over 2^-3 .. 2^1 and running_var
+    over 2^-6 .. 2^4 per channel, so the folded weights w * gamma / sqrt(var + eps) of ONE conv span ~2^9 between channels and the
+    lo halves of the h2 engine's small channels are subnormal against the conv's single scale SW.  The conv weights carry one
+    gain, tuned on the CPU oracle: at 0.55 every tap's standard deviation is within 0.17 .. 2.0 on the test frame and 16
+    instances clear conf (0.5: 9 instances; 0.7: activations reach 468 and every anchor fires)."""
+    sd = fake_state_dict(eng, seed=3)
+    gen = torch.Generator().manual_seed(4)
+    for k in list(sd):
+        if k.endswith(".bn.weight"):
+            c = sd[k].numel()
+            sd[k] = 2.0 ** (torch.rand(c, generator=gen) * 4 - 3)
+            sd[k.replace(".bn.weight", ".bn.running_var")] = 2.0 ** (torch.rand(c, generator=gen) * 10 - 6)
+        if k.endswith(".conv.weight"):
+            sd[k] = sd[k] * 0.55
+    return sd
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "fp16", "h2"])
 def test_yolo_path_runs_a_converted_checkpoint(tmp_path, dtype):
+    _converted_checkpoint(tmp_path, dtype, _scaled_state_dict)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "h2"])
+def test_yolo_path_runs_a_wide_bn_checkpoint(tmp_path, dtype):
+    """The same route and assertions on BatchNorm statistics with a wide per-channel range (the default h2 engine included)."""
+    _converted_checkpoint(tmp_path, dtype, _wide_bn_state_dict)
+
+
+def _converted_checkpoint(tmp_path, dtype, make_sd):
     need_gpu()
     import vti_amd
     plan = vti_amd.Engine("n", 2, H=256, W=320, max_batch=1)            # the reference's model: 2 classes (config.py:69-70)
-    sd = _scaled_state_dict(plan)
+    sd = make_sd(plan)
     blob = vti_amd.convert_state_dict(sd, plan)
     path = tmp_path / "single_needle_model.vtiw"                        # config.py:67's file name, our container format
     path.write_bytes(blob)
@@ -75,7 +103,7 @@ def test_yolo_path_runs_a_converted_checkpoint(tmp_path, dtype):
     eng = model._engine(256, 320, 1)
     gp, gq = eng.forward(torch.from_numpy(lb[None]).cuda(), True)
     e = (gp.cpu() - pred).abs()
-    if dtype == "fp32":
+    if dtype in ("fp32", "h2"):     # h2: split-fp16 pairs (~22 bits), held to the fp32 engine's bounds
         # folded (w * gamma / sqrt(var + eps) formed in float64, rounded once) vs unfused fp32 conv -> BatchNorm: one more
         # rounding per layer than engine-vs-fused-oracle, hence 2e-2 px here (6e-5 of the 320-px frame) instead of 5e-3
         assert e[:, :4].max() < 2e-2 and e[:, :4].max() / 320 < 1e-3 and e[:, 4:6].max() < 1e-4 and e[:, 6:].max() < 1e-3

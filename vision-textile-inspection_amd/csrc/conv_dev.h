@@ -22,7 +22,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // needs >= 20 significant bits in EVERY stored tensor and weight of these networks.
 struct h2_t { unsigned u; };
 struct h2x4 { u32x4 u; };
-constexpr float H2_SX = 16.0f;          // activation scale: |v| < 4094 representable, lo parts normal down to |v| ~ 8e-3
+constexpr float H2_SX = 16.0f;          // activation scale: |v| <= 4094 representable, lo parts normal down to |v| ~ 8e-3
+constexpr float H2_MAX = 4094.0f;       // h2_enc saturates here
 
 template <typename T> struct Tr;
 template <> struct Tr<half_t> { typedef half8 vec; static constexpr int VEC = 8, KC = 32; static constexpr bool H16 = true, F32 = false, H2 = false; };
@@ -32,7 +33,10 @@ template <> struct Tr<h2_t> { typedef h2x4 vec; static constexpr int VEC = 4, KC
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 // Written as explicit fmas so that each half is ONE instruction (v_fma_mixlo_f16 / v_fma_mixhi_f16 with the fp16 hi as the fp16
 // addend: v * 16 - hi is exact in f32, then rounded to fp16) -- the plain casts cost six (the file is compiled -ffp-contract=off).
+// Saturating: v is clamped to +-H2_MAX first (one v_med3_f32; 4094 * 16 = 65504 is the largest fp16, so hi stays finite and lo = 0
+// at the limit).  Unclamped, hi = inf and lo = fp16(16 v - inf) = -inf, and every later use of the pair is inf - inf = NaN.
 __device__ __forceinline__ unsigned h2_enc(float v) {
+    v = __builtin_amdgcn_fmed3f(v, -H2_MAX, H2_MAX);
     half2v p;
     p[0] = (half_t)__builtin_fmaf(v, H2_SX, 0.0f);
     p[1] = (half_t)__builtin_fmaf(v, H2_SX, -(float)p[0]);

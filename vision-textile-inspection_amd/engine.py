@@ -1622,12 +1622,14 @@ def kmeans1d2(values, counts, max_iters=10):
 
 
 H2_SCALE = 16.0     # conv_dev.h: H2_SX
+H2_MAX = 4094.0     # conv_dev.h: H2_MAX (4094 * 16 = 65504, the largest fp16)
 
 
 def h2_encode(t):
     """float tensor -> the h2 engine's storage: per element the fp16 pair (hi | lo << 16) of value * 16, returned as float32-typed
-    bits (same shape).  Host-side helper for tests and the single-conv debug entry point; the engine itself never needs it."""
-    s = t.float() * H2_SCALE
+    bits (same shape).  Saturating at +-4094 as the kernels' h2_enc is; -0 encodes as +0 (the device's fma(v, 16, +0)).
+    Host-side helper for tests and the single-conv debug entry point; the engine itself never needs it."""
+    s = t.float().clamp(-H2_MAX, H2_MAX) * H2_SCALE + 0.0
     hi = s.half()
     lo = (s - hi.float()).half()
     bits = hi.view(torch.int16).to(torch.int32) & 0xFFFF | (lo.view(torch.int16).to(torch.int32) << 16)
