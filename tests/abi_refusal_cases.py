@@ -1,11 +1,15 @@
-"""The refusals of the measure, annotate, overlay and JPEG-encode entry points, as data: for each entry point a valid baseline call
-built from fake pointers (never dereferenced), and a list of single-fault overrides, one or more per argument check.  cases() yields
-(entry point, case name, call); call() -> (status, message).  Every case is refused before the first HIP call, so nothing here
-launches anything.  tests/golden/make_abi_refusals.py records the answers of one commit's library in tests/golden/abi_refusals.json;
-test_abi_refusals.py replays the cases against the current library and compares byte for byte.  Which fault wins when two are
-present is not part of the record: every case has exactly one."""
+"""The refusals of the measure, annotate, overlay and JPEG-encode entry points, and of everything that packs, reads or predicts through
+a frame table or a window table (vti_pack_frames / vti_pack_windows, the table readers, letterbox, scale_boxes, the ragged native
+masks and the three table predicts), as data: for each entry point a valid baseline call built from fake pointers (never
+dereferenced), and a list of single-fault overrides, one or more per argument check.  cases() yields (entry point, case name,
+call); call() -> (status, message).  Every case is refused before the weights / workspace state check and before the first HIP
+call, so nothing here launches anything; faults that only a launch could find stay out.  tests/golden/make_abi_refusals.py records
+the answers of one commit's library in tests/golden/abi_refusals.json; test_abi_refusals.py replays the cases against the current
+library and compares byte for byte.  Which fault wins when two are present is not part of the record: every case has exactly one."""
 import ctypes as C
 import dataclasses as dc
+
+import torch
 
 from test_oracle_geometry import load_calib
 
@@ -30,6 +34,23 @@ def _corrupt(t, row):
     """A copy of a host frame table whose row `row` has a byte offset that is no multiple of 16."""
     c = t.host.clone()
     c[64 + 64 * row] = 1
+    return c
+
+
+def _corrupt_window(t, row, what):
+    """A copy of a host window table with one thing wrong in row `row` (a WindowRow: the crop's FrameRow, whose first field is the
+    crop's byte offset, then frame_offset i64, H0, W0, x0, y0 i32), everything else kept consistent with it."""
+    c = t.host.clone()
+    i64, i32 = c[64 + 128 * row:][:128].view(torch.int64), c[64 + 128 * row:][:128].view(torch.int32)
+    if what == "frame_offset":          # no multiple of 16; the crop moves with its frame
+        i64[8] += 1
+        i64[0] += 1
+    elif what == "crop offset":         # not where the origin puts it
+        i64[0] += 3
+    elif what == "outside":             # one column past the frame's right edge; the crop moves with its origin
+        (H0, W0), (x0, _, w, _) = t.shapes[row], t.windows[row]
+        i32[20] = W0 - w + 1
+        i64[0] += 3 * (W0 - w + 1 - x0)
     return c
 
 
@@ -75,15 +96,26 @@ def cases(vti_amd):
     def nulls(names):
         return [("null " + n, {n: None}) for n in names]
 
-    def table_faults(ht, dt, B_name, t, B_):
-        """The faults frames_check finds in the table pair (ht, dt) of B_ rows."""
-        oc, _, _ = other.pack_frames(t.shapes, device="cpu")
-        bad, junk = _corrupt(t, min(1, B_ - 1)), (C.c_uint8 * 256)()
+    def table_faults(ht, dt, B_name, t, B_, other_kind=None):
+        """The faults the table check finds in the table pair (ht, dt) of B_ rows; t: the FrameTable or WindowTable of the baseline.
+        other_kind: the same frames' table of the other kind, which the call must refuse as it refuses junk."""
+        windows = isinstance(t, vti_amd.WindowTable)
+        oc = other.pack_windows(t.shapes, t.windows, device="cpu") if windows else other.pack_frames(t.shapes, device="cpu")[0]
+        row, junk = min(1, B_ - 1), (C.c_uint8 * 256)()
+        bad = _corrupt_window(t, row, "frame_offset") if windows else _corrupt(t, row)
         keep.extend([oc, bad, junk])
-        return [(f"null {ht}", {ht: None}), (f"null {dt}", {dt: None}), (f"{dt} misaligned", {dt: _at(8)}),
-                (f"{ht} junk", {ht: C.cast(junk, C.c_void_p)}), (f"{ht} other canvas", {ht: _hp(oc)}),
-                (f"{ht} corrupt row", {ht: C.c_void_p(bad.data_ptr())})] + \
-               ([(f"{B_name} + 1", {B_name: B_ + 1}), (f"{B_name} 0", {B_name: 0})] if B_name else [])
+        faults = [(f"null {ht}", {ht: None}), (f"null {dt}", {dt: None}), (f"{dt} misaligned", {dt: _at(8)}),
+                  (f"{ht} junk", {ht: C.cast(junk, C.c_void_p)}), (f"{ht} other canvas", {ht: _hp(oc)}),
+                  (f"{ht} corrupt row", {ht: C.c_void_p(bad.data_ptr())})]
+        if windows:
+            crop, outside = _corrupt_window(t, row, "crop offset"), _corrupt_window(t, row, "outside")
+            keep.extend([crop, outside])
+            faults += [(f"{ht} crop offset off its origin", {ht: C.c_void_p(crop.data_ptr())}),
+                       (f"{ht} window outside its frame", {ht: C.c_void_p(outside.data_ptr())})]
+        if other_kind is not None:
+            keep.append(other_kind)
+            faults.append((f"{ht} of the other kind", {ht: _hp(other_kind)}))
+        return faults + ([(f"{B_name} + 1", {B_name: B_ + 1}), (f"{B_name} 0", {B_name: 0})] if B_name else [])
 
     t_in, _, _ = eng.pack_frames(SHAPES, device="cpu")
     t_out, _, _ = eng.pack_frames([SHAPES[b] for b in SEL], device="cpu")
@@ -289,3 +321,96 @@ def cases(vti_amd):
                           out_bytes=int(plan["out_off"][-1]), info=C.c_void_p(1 << 22), scratch=ws, nbytes=plan["scratch_bytes"], stream=None),
                      [("null scratch", dict(scratch=None)), ("scratch misaligned", dict(scratch=C.c_void_p((1 << 20) + 64))),
                       ("scratch one byte short", dict(nbytes=plan["scratch_bytes"] - 1))])
+
+    # ---- frame tables and window tables: packing, reading, letterbox, boxes, ragged masks, predict --------------------------------
+    # No "null ctx" cases: the table check answers a null ctx without a message, and vti_last_error(NULL) then returns whatever an
+    # earlier null-ctx call left.  No case for "a frame of host_table has no native mask layout" either: a row that passes the table
+    # check (sides in 1..16384, a canvas of multiples of 32) always has a bit-packed layout (slots of at most 32 MiB).
+    WIN = [(100, 50, 640, 480), (3, 7, 300, 400), (0, 0, 960, 720), (640, 300, 1000, 700)]           # (x0, y0, w, h) per frame of SHAPES
+    eng8 = vti_amd.Engine("n", 2, H=736, W=960, max_batch=8)           # the same canvas: packs window tables of more rows than eng takes
+    w_in = eng.pack_windows(SHAPES, WIN, device="cpu")
+    five = SHAPES + [(600, 800)]
+    t5, _, _ = eng.pack_frames(five, device="cpu")
+    w5 = eng8.pack_windows(five, WIN + [(0, 0, 800, 600)], device="cpu")
+    keep.extend([eng8, w_in, t5, w5])
+    kinds = [("frames", t_in, w_in, t5), ("windows", w_in, t_in, w5)]                                # suffix, table, other kind, 5 rows
+
+    def arr(ctype, v):
+        return (ctype * len(v))(*v)
+
+    offs, total = t_in.byte_offsets, t_in.total_bytes
+    p_order = ["ctx", "H", "W", "H0s", "W0s", "offs", "B", "total", "table", "nbytes"]
+    pw_order = p_order[:6] + ["wins"] + p_order[6:]
+    heights, widths = [h for h, _ in SHAPES], [w for _, w in SHAPES]
+    flat = lambda wins: _i32(*[v for w in wins for v in w])
+    for name, order, table_bytes in (("vti_pack_frames", p_order, L.vti_frame_table_bytes), ("vti_pack_windows", pw_order, L.vti_window_table_bytes)):
+        nb = int(table_bytes(B))
+        out = (C.c_uint8 * int(table_bytes(8)))()
+        p_base = dict(ctx=ctx, H=736, W=960, H0s=_i32(*heights), W0s=_i32(*widths), offs=arr(C.c_int64, offs), wins=flat(WIN), B=B,
+                      total=total, table=out, nbytes=nb)
+        frame1 = lambda h, w, off=offs[1]: dict(H0s=_i32(heights[0], h, *heights[2:]), W0s=_i32(widths[0], w, *widths[2:]),
+                                                offs=arr(C.c_int64, [offs[0], off] + offs[2:]))
+        p_faults = nulls(["H0s", "W0s", "offs", "table"]) + [
+            ("B 0", dict(B=0)), ("H 0", dict(H=0)), ("H 740", dict(H=740)), ("W 950", dict(W=950)), ("total_bytes -1", dict(total=-1)),
+            ("table one byte short", dict(nbytes=nb - 1)), ("frame 1: H0 0", frame1(0, 333)), ("frame 1: W0 16385", frame1(481, 16385)),
+            ("frame 1: offset + 8", frame1(481, 333, offs[1] + 8)), ("frame 3 past total_bytes", dict(total=total - 16)),
+            ("frame 1: resized below 1 px", dict(frame1(1, 16384), wins=flat([WIN[0], (0, 0, 16384, 1)] + WIN[2:])))]
+        if name == "vti_pack_windows":
+            big = dict(H0s=_i32(16384), W0s=_i32(16384), offs=arr(C.c_int64, [0]), B=1, total=3 * 16384 * 16384, nbytes=int(table_bytes(1)))
+            p_faults += nulls(["wins"]) + [
+                ("B above max_batch", dict(H0s=_i32(*heights, 600), W0s=_i32(*widths, 800), offs=arr(C.c_int64, t5.byte_offsets),
+                                           wins=flat(WIN + [(0, 0, 800, 600)]), B=5, total=t5.total_bytes, nbytes=int(table_bytes(5)))),
+                ("window 1: w 0", dict(wins=flat([WIN[0], (3, 7, 0, 400)] + WIN[2:]))),
+                ("window 1: h -1", dict(wins=flat([WIN[0], (3, 7, 300, -1)] + WIN[2:]))),
+                ("window 1: x0 -1", dict(wins=flat([WIN[0], (-1, 7, 300, 400)] + WIN[2:]))),
+                ("window 1: one column past the right edge", dict(wins=flat([WIN[0], (34, 7, 300, 400)] + WIN[2:]))),
+                ("window 1: one row past the bottom edge", dict(wins=flat([WIN[0], (3, 82, 300, 400)] + WIN[2:]))),
+                ("window resized below 1 px", dict(big, wins=_i32(0, 0, 16384, 1)))]
+        yield from entry(name, order, p_base, p_faults)
+
+    yield from entry("vti_window_table_info", ["ht", "b", "i32", "f64"], dict(ctx=None, ht=_hp(w_in), b=1, i32=(C.c_int32 * 12)(), f64=f64),
+                     [("null table", dict(ht=None)), ("null out", dict(i32=None)), ("b -2", dict(b=-2)), ("b B", dict(b=4)),
+                      ("junk table", dict(ht=C.cast(junk, C.c_void_p))), ("a frame table", dict(ht=_hp(t_in)))], message=False)
+
+    above = lambda rows5: ("B above max_batch", dict(ht=_hp(rows5), B=5))
+    n_base = dict(ctx=ctx, dets=one, xyxy=one, counts=one, proto=one, ht=None, dt=one, B=B, max_det=max_det, mode=0, packing=1, masks=one,
+                  cbytes=1 << 20, offsets=one, bases=one, stream=None)
+    n_faults = nulls(["dets", "counts", "proto", "offsets", "bases"]) + [
+        ("max_det 0", dict(max_det=0)), ("cbytes -1", dict(cbytes=-1)), ("cbytes 16 with null masks", dict(cbytes=16, masks=None)),
+        ("packing u8", dict(packing=0)), ("packing 2", dict(packing=2)), ("masks misaligned", dict(masks=_at(4))),
+        ("bases misaligned", dict(bases=_at(4))), ("offsets misaligned", dict(offsets=_at(2))), ("B * max_det", dict(max_det=1 << 30))]
+    pr_head = ["ctx", "frames", "ht", "dt", "B", "swap_rb", "conf", "iou", "max_det", "agnostic", "mode", "packing", "input", "pred", "proto",
+               "dets", "counts", "masks"]
+    pr_base = dict(n_base, frames=one, swap_rb=1, conf=0.25, iou=0.7, agnostic=0, input=one, pred=one, cap=cap)
+    head_faults = nulls(["frames", "input"]) + [("frames misaligned", dict(frames=_at(8))), ("input misaligned", dict(input=_at(2))),
+                                                ("xyxy misaligned", dict(xyxy=_at(8)))]
+    for kind, t, twin, rows5 in kinds:
+        tf = table_faults("ht", "dt", "B", t, B, other_kind=twin)
+        base = dict(n_base, ht=_hp(t))
+        yield from entry("vti_letterbox_" + kind, ["ctx", "frames", "ht", "dt", "B", "out", "stream"], dict(base, frames=one, out=one),
+                         tf + nulls(["frames", "out"]) + [("frames misaligned", dict(frames=_at(8))), ("out misaligned", dict(out=_at(2))),
+                                                          above(rows5)])
+        yield from entry("vti_scale_boxes_" + kind, ["ctx", "dets", "counts", "ht", "dt", "B", "max_det", "xyxy", "stream"], base,
+                         tf + nulls(["dets", "counts", "xyxy"]) + [("max_det 0", dict(max_det=0)), ("xyxy misaligned", dict(xyxy=_at(8))),
+                                                                   ("B * max_det", dict(max_det=1 << 30))])
+        yield from entry(f"vti_mask_native_{kind}_bytes", ["ctx", "ht", "max_det"], base,
+                         [("null ctx", dict(ctx=None)), ("null table", dict(ht=None)), ("max_det 0", dict(max_det=0)),
+                          ("junk table", dict(ht=C.cast(junk, C.c_void_p))), ("a table of the other kind", dict(ht=_hp(twin))),
+                          ("a table of another canvas", dict(ctx=other._ctx)), ("a table of 5 rows", dict(ht=_hp(rows5)))] +
+                         [(c, o) for c, o in tf if c in ("ht corrupt row", "ht crop offset off its origin", "ht window outside its frame")],
+                         message=False)
+        # the ragged masks: vti_masks_native_frames takes the frame-px boxes, vti_masks_native_windows needs 8-byte aligned dets instead
+        own = [("null xyxy", dict(xyxy=None))] if kind == "frames" else [("dets misaligned", dict(dets=_at(4)))]
+        n_order = ["ctx", "dets"] + (["xyxy"] if kind == "frames" else []) + ["counts", "proto", "ht", "dt", "B", "max_det", "mode", "packing",
+                                                                              "masks", "cbytes", "offsets", "bases", "stream"]
+        yield from entry("vti_masks_native_" + kind, n_order, base, tf + n_faults + own + [("mode 2", dict(mode=2)), above(rows5)])
+        # the native predicts: null xyxy and null pred have checks of their own, ahead of the ragged-mask checks and the head's
+        name = "vti_predict_frames_native" if kind == "frames" else "vti_predict_windows"
+        yield from entry(name, pr_head + ["cbytes", "offsets", "bases", "xyxy", "stream"], dict(pr_base, ht=_hp(t)),
+                         tf + n_faults + ([] if kind == "frames" else own) + head_faults +
+                         [("null xyxy", dict(xyxy=None)), ("null pred", dict(pred=None)), ("mode 2", dict(mode=2)),
+                          ("mode native | 2", dict(mode=0x12)), above(rows5)])
+    # vti_predict_frames: canvas-size masks; its own checks end at the head's (dets, counts and max_det only with dev_xyxy)
+    yield from entry("vti_predict_frames", pr_head + ["cap", "offsets", "xyxy", "stream"], dict(pr_base, ht=_hp(t_in)),
+                     table_faults("ht", "dt", "B", t_in, B, other_kind=w_in) + head_faults + nulls(["dets", "counts"]) +
+                     [("max_det 0", dict(max_det=0)), ("mode native", dict(mode=0x10)), above(t5)])

@@ -1487,6 +1487,11 @@ __host__ __device__ static inline int native_geom(int Hp, int Wp, int H0, int W0
     return 0;
 }
 
+// The tiles across one frame of the static work list: 64-px tiles of a W0-px row, and for a window the 64-bit words of the frame's
+// rows that [x0, x0 + w) touches.  The host's worst case (native_table_bytes) and the device's plan count with the same expressions.
+__host__ __device__ static inline int native_tiles_x(int W0) { return (W0 + NTW - 1) / NTW; }
+__host__ __device__ static inline int native_window_tiles_x(int x0, int w) { return ((x0 + w - 1) >> 6) - (x0 >> 6) + 1; }
+
 // Frame b of vti_masks_native_frames as the prologue leaves it in the workspace: its NativeGeom, its size, its first slot's byte
 // offset (bases[b]) and how many of its instances are live by the byte rule (slot end <= capacity_bytes).
 struct NativeFrame {
@@ -1580,11 +1585,11 @@ __global__ __launch_bounds__(256) void mask_frames_plan_kernel(const int* __rest
             int lay[6];
             ok = native_geom(Hp, Wp, f.H0, f.W0, VTI_PACK_BITS, f.g) == 0 && native_mask_layout_hd(Hp, Wp, w.H0, w.W0, VTI_PACK_BITS, lay) == 0;
             if (ok) { f.g.row_bytes = lay[4]; f.g.slot_bytes = lay[5]; }
-            f.tiles_x = ((w.x0 + f.W0 - 1) >> 6) - (w.x0 >> 6) + 1;
+            f.tiles_x = native_window_tiles_x(w.x0, f.W0);
         } else {
             f.H0 = ((const FrameRow*)rows)[b].H0; f.W0 = ((const FrameRow*)rows)[b].W0;
             ok = native_geom(Hp, Wp, f.H0, f.W0, VTI_PACK_BITS, f.g) == 0;
-            f.tiles_x = (f.W0 + NTW - 1) / NTW;
+            f.tiles_x = native_tiles_x(f.W0);
         }
         if (!ok) { f.g = NativeGeom{0, 0, 1, 1, 1.f, 1.f, 1, 0, 0, 0, 0}; f.H0 = f.W0 = 0; f.tiles_x = 0; }
         nf[b] = f;
@@ -1852,23 +1857,45 @@ hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, 
     return hipGetLastError();
 }
 
-// vti_masks_native_frames.  host_table: the packed frame table, its rows already validated (frames_check); the worst-case bytes of
-// max_det slots per frame, and the tiles of the static work list (-1: a frame native_mask_layout cannot describe).
-long long native_frames_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles) {
+// What one packed row adds to the ragged buffer and to the static work list: the bytes of a slot and the tiles of the frame (false:
+// a size native_mask_layout cannot describe).
+static bool native_row_yield(const FrameRow& r, int Hp, int Wp, long long& slot_bytes, long long& tiles) {
+    NativeGeom g;
+    if (native_geom(Hp, Wp, r.H0, r.W0, VTI_PACK_BITS, g)) return false;
+    slot_bytes = g.slot_bytes;
+    tiles = (long long)native_tiles_x(r.W0) * ((r.H0 + g.th - 1) / g.th);
+    return true;
+}
+// A window row: slots of the FULL frame, tiles of th window rows by the 64-bit words of the frame's rows that the window touches.
+static bool native_row_yield(const WindowRow& r, int Hp, int Wp, long long& slot_bytes, long long& tiles) {
+    NativeGeom g;
+    int lay[6];
+    if (native_geom(Hp, Wp, r.crop.H0, r.crop.W0, VTI_PACK_BITS, g) || native_mask_layout_hd(Hp, Wp, r.H0, r.W0, VTI_PACK_BITS, lay)) return false;
+    slot_bytes = lay[5];
+    tiles = (long long)native_window_tiles_x(r.x0, r.crop.W0) * ((r.crop.H0 + g.th - 1) / g.th);
+    return true;
+}
+
+// vti_masks_native_frames / vti_masks_native_windows.  host_table: the packed table of Rows, already validated (table_check); the
+// worst-case bytes of max_det slots per frame, and the tiles of the static work list (-1: a row without a native layout).
+template <class Row>
+long long native_table_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles) {
     FrameTableHeader h;
     memcpy(&h, host_table, sizeof h);
     long long bytes = 0, til = 0;
     for (int b = 0; b < h.B; ++b) {
-        FrameRow r;
+        Row r;
         memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
-        NativeGeom g;
-        if (native_geom(Hp, Wp, r.H0, r.W0, VTI_PACK_BITS, g)) return -1;
-        bytes += (long long)max_det * g.slot_bytes;
-        til += (long long)((r.W0 + NTW - 1) / NTW) * ((r.H0 + g.th - 1) / g.th);
+        long long slot, t;
+        if (!native_row_yield(r, Hp, Wp, slot, t)) return -1;
+        bytes += (long long)max_det * slot;
+        til += t;
     }
     if (tiles) *tiles = til;
     return bytes;
 }
+template long long native_table_bytes<FrameRow>(const void*, int, int, int, long long*);
+template long long native_table_bytes<WindowRow>(const void*, int, int, int, long long*);
 
 size_t masks_native_frames_workspace_bytes(int B) { return 256 + align256((size_t)(B + 1) * sizeof(int)) + (size_t)B * sizeof(NativeFrame); }
 
@@ -2110,25 +2137,6 @@ hipError_t launch_masks_native_windows(int dtype, const float* dets, const int* 
                                        long long* bases, void* ws, hipStream_t st) {
     return launch_masks_native_table<true>(dtype, dets, nullptr, counts, proto, rows, B, max_det, Hp, Wp, mode, masks, capacity_bytes,
                                            offsets, bases, ws, st);
-}
-
-// vti_mask_native_windows_bytes / vti_masks_native_windows: native_frames_bytes of the FULL frames of a packed window table, and the
-// tiles of the windows' work list; -1 where a frame or a window has no native layout.
-long long native_windows_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles) {
-    FrameTableHeader h;
-    memcpy(&h, host_table, sizeof h);
-    long long bytes = 0, til = 0;
-    for (int b = 0; b < h.B; ++b) {
-        WindowRow r;
-        memcpy(&r, (const char*)host_table + sizeof h + (size_t)b * sizeof r, sizeof r);
-        NativeGeom g;
-        int lay[6];
-        if (native_geom(Hp, Wp, r.crop.H0, r.crop.W0, VTI_PACK_BITS, g) || native_mask_layout_hd(Hp, Wp, r.H0, r.W0, VTI_PACK_BITS, lay)) return -1;
-        bytes += (long long)max_det * lay[5];
-        til += (long long)(((r.x0 + r.crop.W0 - 1) >> 6) - (r.x0 >> 6) + 1) * ((r.crop.H0 + g.th - 1) / g.th);
-    }
-    if (tiles) *tiles = til;
-    return bytes;
 }
 
 }  // namespace vti

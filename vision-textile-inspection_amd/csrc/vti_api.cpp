@@ -51,7 +51,7 @@ static int32_t hip_fail(vti_ctx* c, hipError_t e, const char* what) {
     return fail(c, VTI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 // A refused argument: the message is "<fn>: <what>".
-static int32_t refuse(vti_ctx* c, const char* fn, const char* what, int32_t code = VTI_ERR_ARG) {
+static int32_t refuse(vti_ctx* c, const char* fn, const std::string& what, int32_t code = VTI_ERR_ARG) {
     return fail(c, code, std::string(fn) + ": " + what);
 }
 #define VTI_TRY(call) do { if (int32_t rc_ = (call)) return rc_; } while (0)     // a check that refused: its status is the entry point's
@@ -251,16 +251,14 @@ int32_t vti_letterbox(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, 
     return VTI_OK;
 }
 
-// ---- batches whose frames differ in size: the frame table ------------------------------------------------------------------
+}  // extern "C": the calls that take a frame table or a window table are one template over what differs between the two kinds
+
+// ---- batches whose frames differ in size (the frame table) and predicts on a window of each frame (the window table) ----------
 static const int32_t kFrameMaxSide = 16384;      // vti_mask_polygons' limit
 
-int64_t vti_frame_table_bytes(int32_t B) {
-    return B < 1 ? 0 : (int64_t)sizeof(FrameTableHeader) + (int64_t)B * (int64_t)sizeof(FrameRow);
-}
-
-// What is wrong with one frame of a table for the H x W canvas (nullptr: nothing).  vti_pack_frames runs it on its arguments and
-// every *_frames call on the rows of the host table it is given, so each value a kernel forms an address from was checked by the
-// host at the call.
+// What is wrong with one frame of a table for the H x W canvas (nullptr: nothing).  The pack calls run it on their arguments and
+// every call that takes a table on the rows of the host table it is given, so each value a kernel forms an address from was
+// checked by the host at the call.
 static const char* frame_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int64_t offset, int64_t total_bytes) {
     if (H0 < 1 || W0 < 1) return "H0 and W0 must be >= 1";
     if (H0 > kFrameMaxSide || W0 > kFrameMaxSide) return "H0 and W0 must be <= 16384";
@@ -273,34 +271,146 @@ static const char* frame_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int
     return nullptr;
 }
 
-// The header of a host frame table and row k of it.
+// What is wrong with one window of an H0 x W0 frame for the H x W canvas (nullptr: nothing); the frame itself passed frame_error.
+static const char* window_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int32_t x0, int32_t y0, int32_t w, int32_t h) {
+    if (w < 1 || h < 1) return "the window's w and h must be >= 1";
+    if (x0 < 0 || y0 < 0 || x0 > W0 - w || y0 > H0 - h) return "the window does not lie inside its frame";
+    int nh, nw, top, left;
+    letterbox_geom(h, w, H, W, nh, nw, top, left);
+    if (nh < 1 || nw < 1) return "the resized window would be below 1 px";
+    if (top < 0 || left < 0 || top + nh > H || left + nw > W) return "the resized window does not fit the canvas";
+    return nullptr;
+}
+
+// What is wrong with the frame a packed row describes: frame_error, and a size above the header's recorded maximum.
+static const char* packed_frame_error(const FrameTableHeader& h, int32_t H0, int32_t W0, int64_t offset) {
+    const char* e = frame_error(h.H, h.W, H0, W0, offset, h.total_bytes);
+    if (!e && (H0 > h.max_H0 || W0 > h.max_W0)) e = "larger than the table's recorded maximum";
+    return e;
+}
+
+// What differs between the two kinds of table: the row and the magic, the words of the messages, what a pack call takes and
+// writes per frame, what is wrong with a packed row, what vti_*_table_info reports beyond the letterbox row, the launchers, and in
+// the ragged-mask checks one pointer and one alignment (the frame form crops to dev_xyxy, the window form reads dev_dets in pairs).
+struct FrameKind {
+    using Row = FrameRow;
+    static constexpr int magic = kFrameTableMagic;
+    static constexpr bool windowed = false;
+    static constexpr int info_ints = 8;
+    static constexpr const char *noun = "frame", *packer = "vti_pack_frames";
+    static constexpr const char *letterbox_fn = "vti_letterbox_frames", *letterbox_kernel = "letterbox kernel";
+    static constexpr const char *scale_boxes_fn = "vti_scale_boxes_frames", *scale_boxes_kernel = "scale_boxes kernel";
+    static constexpr const char *masks_fn = "vti_masks_native_frames", *masks_kernel = "native mask kernel (frames)";
+    static constexpr const char* predict_fn = "vti_predict_frames_native";
+    static constexpr const char* xyxy_required = "dev_xyxy is required (the masks are cropped to the frame-px boxes)";
+    static constexpr const char* masks_alignment = "dev_masks and dev_mask_bases must be 8-byte aligned, dev_offsets 4-byte aligned";
+    static constexpr const char* no_layout = "a frame of host_table has no native mask layout (slot below 2 GiB)";
+    static const FrameRow& letterbox_row(const FrameRow& r) { return r; }
+    static void info_tail(const FrameRow&, int32_t*) {}
+    static const char* pack_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int64_t offset, int64_t total_bytes, const int32_t*) {
+        return frame_error(H, W, H0, W0, offset, total_bytes);
+    }
+    static void pack_row(int32_t H, int32_t W, int32_t H0, int32_t W0, int64_t offset, const int32_t*, FrameRow& r) {
+        frame_row_fill(H, W, H0, W0, offset, r);
+    }
+    static const char* row_error(const FrameTableHeader& h, const FrameRow& r) { return packed_frame_error(h, r.H0, r.W0, r.offset); }
+    static bool masks_pointer_missing(const float* xyxy) { return !xyxy; }
+    static bool masks_dets_misaligned(const float*) { return false; }
+    static hipError_t letterbox(const uint8_t* frames, int B, const FrameRow* rows, uint8_t* out, int H, int W, hipStream_t st) {
+        return launch_letterbox(frames, B, 0, 0, rows, out, H, W, st);
+    }
+    static hipError_t scale_boxes(const float* dets, const int* counts, int B, int max_det, const vti_desc& d, const FrameRow* rows,
+                                  float* xyxy, hipStream_t st) {
+        return launch_scale_boxes(dets, counts, B, max_det, d.nm, d.H, d.W, 0, 0, rows, xyxy, st);
+    }
+    static constexpr auto masks = launch_masks_native_frames;
+};
+struct WindowKind {
+    using Row = WindowRow;
+    static constexpr int magic = kWindowTableMagic;
+    static constexpr bool windowed = true;       // the pack call takes `windows` and, given a ctx, holds B to its max_batch
+    static constexpr int info_ints = 12;
+    static constexpr const char *noun = "window", *packer = "vti_pack_windows";
+    static constexpr const char *letterbox_fn = "vti_letterbox_windows", *letterbox_kernel = "letterbox kernel (windows)";
+    static constexpr const char *scale_boxes_fn = "vti_scale_boxes_windows", *scale_boxes_kernel = "scale_boxes kernel (windows)";
+    static constexpr const char *masks_fn = "vti_masks_native_windows", *masks_kernel = "native mask kernel (windows)";
+    static constexpr const char* predict_fn = "vti_predict_windows";
+    static constexpr const char* xyxy_required = "dev_xyxy is required";
+    static constexpr const char* masks_alignment =
+        "dev_masks, dev_mask_bases and dev_dets must be 8-byte aligned, dev_offsets 4-byte aligned";
+    static constexpr const char* no_layout = "a frame or a window of host_table has no native mask layout (slot below 2 GiB)";
+    static const FrameRow& letterbox_row(const WindowRow& w) { return w.crop; }
+    static void info_tail(const WindowRow& w, int32_t* v) { v[0] = w.x0; v[1] = w.y0; v[2] = w.H0; v[3] = w.W0; }
+    static const char* pack_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int64_t offset, int64_t total_bytes, const int32_t* w) {
+        const char* e = frame_error(H, W, H0, W0, offset, total_bytes);
+        return e ? e : window_error(H, W, H0, W0, w[0], w[1], w[2], w[3]);
+    }
+    static void pack_row(int32_t H, int32_t W, int32_t H0, int32_t W0, int64_t offset, const int32_t* w, WindowRow& r) {
+        memset(&r, 0, sizeof r);
+        frame_row_fill(H, W, w[3], w[2], offset + 3 * ((int64_t)w[1] * W0 + w[0]), r.crop);
+        r.frame_offset = offset; r.H0 = H0; r.W0 = W0; r.x0 = w[0]; r.y0 = w[1];
+    }
+    // the row's frame passes frame_error, its window window_error, and the crop row holds the window's size and first byte (what the
+    // kernels form addresses from)
+    static const char* row_error(const FrameTableHeader& h, const WindowRow& w) {
+        const char* e = packed_frame_error(h, w.H0, w.W0, w.frame_offset);
+        if (!e) e = window_error(h.H, h.W, w.H0, w.W0, w.x0, w.y0, w.crop.W0, w.crop.H0);
+        if (!e && w.crop.offset != w.frame_offset + 3 * ((int64_t)w.y0 * w.W0 + w.x0)) e = "the window's first byte is not where its origin puts it";
+        return e;
+    }
+    static bool masks_pointer_missing(const float*) { return false; }
+    static bool masks_dets_misaligned(const float* dets) { return (uintptr_t)dets & 7; }
+    static constexpr auto letterbox = launch_letterbox_windows;
+    static hipError_t scale_boxes(const float* dets, const int* counts, int B, int max_det, const vti_desc& d, const WindowRow* rows,
+                                  float* xyxy, hipStream_t st) {
+        return launch_scale_boxes_windows(dets, counts, B, max_det, d.nm, rows, xyxy, st);
+    }
+    static hipError_t masks(int dtype, const float* dets, const float*, const int* counts, const void* proto, const WindowRow* rows, int B,
+                            int max_det, int Hp, int Wp, int mode, uint8_t* out, long long capacity_bytes, int* offsets,
+                            long long* bases, void* ws, hipStream_t st) {
+        return launch_masks_native_windows(dtype, dets, counts, proto, rows, B, max_det, Hp, Wp, mode, out, capacity_bytes, offsets, bases,
+                                           ws, st);
+    }
+};
+
+// The header of a host table, row k of it, and the rows of its device copy.
 static FrameTableHeader table_header(const void* host_table) { FrameTableHeader h; memcpy(&h, host_table, sizeof h); return h; }
-static FrameRow table_row(const void* host_table, int32_t k) {
-    FrameRow r;
+template <class K>
+static typename K::Row host_row(const void* host_table, int32_t k) {
+    typename K::Row r;
     memcpy(&r, (const char*)host_table + sizeof(FrameTableHeader) + (size_t)k * sizeof r, sizeof r);
     return r;
 }
+template <class K>
+static const typename K::Row* dev_rows(const void* dev_table) {
+    return (const typename K::Row*)((const char*)dev_table + sizeof(FrameTableHeader));
+}
 
-int32_t vti_pack_frames(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset, int32_t B,
-                        int64_t total_bytes, void* host_table, size_t nbytes) {
-    if (!H0 || !W0 || !byte_offset || !host_table || B < 1)
-        return fail(c, VTI_ERR_ARG, "vti_pack_frames: null array or table, or B < 1");
+template <class K>
+static int64_t table_bytes(int32_t B) {
+    return B < 1 ? 0 : (int64_t)sizeof(FrameTableHeader) + (int64_t)B * (int64_t)sizeof(typename K::Row);
+}
+
+// `windows`: four ints (x0, y0, w, h) per frame, for a window table only.
+template <class K>
+static int32_t pack_table(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset,
+                          const int32_t* windows, int32_t B, int64_t total_bytes, void* host_table, size_t nbytes) {
+    if (!H0 || !W0 || !byte_offset || (K::windowed && !windows) || !host_table || B < 1)
+        return refuse(c, K::packer, "null array or table, or B < 1");
     if (H < 32 || W < 32 || (H & 31) || (W & 31) || total_bytes < 0)
-        return fail(c, VTI_ERR_ARG, "vti_pack_frames: the canvas H, W must be multiples of 32, total_bytes >= 0");
-    if ((int64_t)nbytes < vti_frame_table_bytes(B))
-        return fail(c, VTI_ERR_ARG, "vti_pack_frames: table smaller than vti_frame_table_bytes()");
+        return refuse(c, K::packer, "the canvas H, W must be multiples of 32, total_bytes >= 0");
+    if ((int64_t)nbytes < table_bytes<K>(B)) return refuse(c, K::packer, std::string("table smaller than vti_") + K::noun + "_table_bytes()");
+    if (K::windowed && c && B > c->plan.desc.max_batch) return refuse(c, K::packer, "B above the ctx's max_batch");
+    auto window = [&](int32_t b) { return K::windowed ? windows + 4 * (size_t)b : nullptr; };
     for (int32_t b = 0; b < B; ++b)
-        if (const char* e = frame_error(H, W, H0[b], W0[b], byte_offset[b], total_bytes)) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "vti_pack_frames: frame %d: %s", b, e);
-            return fail(c, VTI_ERR_ARG, msg);
-        }
+        if (const char* e = K::pack_error(H, W, H0[b], W0[b], byte_offset[b], total_bytes, window(b)))
+            return refuse(c, K::packer, "frame " + std::to_string(b) + ": " + e);
     FrameTableHeader h;
     memset(&h, 0, sizeof h);
-    h.magic = kFrameTableMagic; h.B = B; h.H = H; h.W = W; h.total_bytes = total_bytes;
+    h.magic = K::magic; h.B = B; h.H = H; h.W = W; h.total_bytes = total_bytes;
     for (int32_t b = 0; b < B; ++b) {
-        FrameRow r;
-        frame_row_fill(H, W, H0[b], W0[b], byte_offset[b], r);
+        typename K::Row r;
+        K::pack_row(H, W, H0[b], W0[b], byte_offset[b], window(b), r);
         h.max_H0 = std::max(h.max_H0, H0[b]); h.max_W0 = std::max(h.max_W0, W0[b]);
         memcpy((char*)host_table + sizeof h + (size_t)b * sizeof r, &r, sizeof r);
     }
@@ -308,74 +418,221 @@ int32_t vti_pack_frames(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, con
     return VTI_OK;
 }
 
-int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[8], double out_f64[5]) {
+// b = -1: the header.  Else row b: its letterbox row, then what K::info_tail adds, and the doubles (out_f64 may be null).
+template <class K>
+static int32_t table_info(const void* host_table, int32_t b, int32_t* out_i32, double* out_f64) {
     if (!host_table || !out_i32) return VTI_ERR_ARG;
     const FrameTableHeader h = table_header(host_table);
-    if (h.magic != kFrameTableMagic || h.B < 1 || b < -1 || b >= h.B) return VTI_ERR_ARG;
-    if (b < 0) {
-        const int32_t v[8] = {h.B, h.H, h.W, h.max_H0, h.max_W0, 0, (int32_t)(h.total_bytes & 0xffffffff), (int32_t)(h.total_bytes >> 32)};
-        memcpy(out_i32, v, sizeof v);
-        return VTI_OK;
+    if (h.magic != K::magic || h.B < 1 || b < -1 || b >= h.B) return VTI_ERR_ARG;
+    int32_t v[K::info_ints] = {h.B, h.H, h.W, h.max_H0, h.max_W0, 0, (int32_t)(h.total_bytes & 0xffffffff), (int32_t)(h.total_bytes >> 32)};
+    if (b >= 0) {
+        const typename K::Row row = host_row<K>(host_table, b);
+        const FrameRow& r = K::letterbox_row(row);
+        const int32_t lb[8] = {r.H0, r.W0, r.new_h, r.new_w, r.top, r.left, (int32_t)(r.offset & 0xffffffff), (int32_t)(r.offset >> 32)};
+        memcpy(v, lb, sizeof lb);
+        K::info_tail(row, v + 8);
+        if (out_f64) { out_f64[0] = r.scale_x; out_f64[1] = r.scale_y; out_f64[2] = r.gain; out_f64[3] = r.padx; out_f64[4] = r.pady; }
     }
-    const FrameRow r = table_row(host_table, b);
-    const int32_t v[8] = {r.H0, r.W0, r.new_h, r.new_w, r.top, r.left, (int32_t)(r.offset & 0xffffffff), (int32_t)(r.offset >> 32)};
     memcpy(out_i32, v, sizeof v);
-    if (out_f64) { out_f64[0] = r.scale_x; out_f64[1] = r.scale_y; out_f64[2] = r.gain; out_f64[3] = r.padx; out_f64[4] = r.pady; }
     return VTI_OK;
 }
 
-// What is wrong with a packed host table for this ctx (nullptr: nothing): not a table of vti_pack_frames, packed for another B (B < 0:
-// any B >= 1) or another canvas, or a row that no longer passes frame_error (`frame` then receives its index, else -1).  Fails
-// nothing and records nothing: frames_check and the host-only size queries share it.  `h` receives the header.
-static const char* frame_table_problem(const vti_ctx* c, const void* host_table, int32_t B, FrameTableHeader& h, int32_t& frame) {
+template <class K>
+static std::string not_a_table() { return std::string("host_table is not a table of ") + K::packer; }
+template <class K>
+static std::string packed_for_another(const char* what) { return std::string("the ") + K::noun + " table was packed for another " + what; }
+
+// What is wrong with a packed host table for this ctx (empty: nothing): not a table of K's pack call, packed for another B (B < 0:
+// any B >= 1) or another canvas, or a row that no longer passes K::row_error (`frame` then receives its index, else -1).  Fails
+// nothing and records nothing: table_check and the host-only size queries share it.  `h` receives the header.
+template <class K>
+static std::string table_problem(const vti_ctx* c, const void* host_table, int32_t B, FrameTableHeader& h, int32_t& frame) {
     frame = -1;
     h = table_header(host_table);
-    if (h.magic != kFrameTableMagic) return "host_table is not a table of vti_pack_frames";
-    if (h.B < 1 || (B >= 0 && h.B != B)) return "the frame table was packed for another B";
-    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return "the frame table was packed for another canvas (H x W)";
-    for (int32_t b = 0; b < h.B; ++b) {
-        const FrameRow r = table_row(host_table, b);
-        const char* e = frame_error(h.H, h.W, r.H0, r.W0, r.offset, h.total_bytes);
-        if (!e && (r.H0 > h.max_H0 || r.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
-        if (e) { frame = b; return e; }
-    }
-    return nullptr;
+    if (h.magic != K::magic) return not_a_table<K>();
+    if (h.B < 1 || (B >= 0 && h.B != B)) return packed_for_another<K>("B");
+    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return packed_for_another<K>("canvas (H x W)");
+    for (int32_t b = 0; b < h.B; ++b)
+        if (const char* e = K::row_error(h, host_row<K>(host_table, b))) { frame = b; return e; }
+    return {};
 }
 
-// The checks every *_frames call makes on its table pair before anything else: the host copy is a packed table for this ctx's
-// canvas and this B whose rows still pass frame_error, and the device copy is a 16-byte aligned pointer.  `h` receives the header.
-static int32_t frames_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
-    char msg[200];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, VTI_ERR_ARG, msg); };
+// The checks every call makes on its table pair before anything else: the host copy is a packed table of kind K for this ctx's
+// canvas and this B whose rows still pass K::row_error, and the device copy is a 16-byte aligned pointer.  `h` receives the header.
+template <class K>
+static int32_t table_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
     if (!c) return VTI_ERR_ARG;
-    if (!host_table || !dev_table) return bad("null frame table (host copy or device copy)");
-    if ((uintptr_t)dev_table & 15) return bad("the device frame table must be 16-byte aligned");
-    int32_t frame;
-    if (B < 1) {                            // no table is packed for B < 1 (frame_table_problem reads B < 0 as "any B")
+    if (!host_table || !dev_table) return refuse(c, fn, std::string("null ") + K::noun + " table (host copy or device copy)");
+    if ((uintptr_t)dev_table & 15) return refuse(c, fn, std::string("the device ") + K::noun + " table must be 16-byte aligned");
+    if (B < 1) {                            // no table is packed for B < 1 (table_problem reads B < 0 as "any B")
         h = table_header(host_table);
-        return bad(h.magic != kFrameTableMagic ? "host_table is not a table of vti_pack_frames" : "the frame table was packed for another B");
+        return refuse(c, fn, h.magic != K::magic ? not_a_table<K>() : packed_for_another<K>("B"));
     }
-    if (const char* e = frame_table_problem(c, host_table, B, h, frame)) {
-        if (frame < 0) return bad(e);
-        snprintf(msg, sizeof msg, "%s: frame %d of host_table: %s", fn, frame, e);
-        return fail(c, VTI_ERR_ARG, msg);
-    }
+    int32_t frame;
+    const std::string e = table_problem<K>(c, host_table, B, h, frame);
+    if (e.empty()) return VTI_OK;
+    return refuse(c, fn, frame < 0 ? e : "frame " + std::to_string(frame) + " of host_table: " + e);
+}
+
+// The frame-table forms under the names the other families call them by.
+static FrameRow table_row(const void* host_table, int32_t k) { return host_row<FrameKind>(host_table, k); }
+static const FrameRow* frame_rows(const void* dev_table) { return dev_rows<FrameKind>(dev_table); }
+static int32_t frames_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
+    return table_check<FrameKind>(fn, c, host_table, dev_table, B, h);
+}
+
+template <class K>
+static int32_t letterbox_table(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B, uint8_t* out,
+                               void* stream) {
+    const char* fn = K::letterbox_fn;
+    FrameTableHeader h;
+    VTI_TRY(table_check<K>(fn, c, host_table, dev_table, B, h));
+    if (!frames || !out) return refuse(c, fn, "null frames or output");
+    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 3)) return refuse(c, fn, "dev_frames must be 16-byte aligned, dev_input 4-byte aligned");
+    if (B > c->plan.desc.max_batch) return refuse(c, fn, "B above max_batch");
+    VTI_TRY(check_device(c, fn));
+    VTI_HIP(c, K::letterbox(frames, B, dev_rows<K>(dev_table), out, h.H, h.W, (hipStream_t)stream), K::letterbox_kernel);
     return VTI_OK;
 }
 
-static const FrameRow* frame_rows(const void* dev_table) { return (const FrameRow*)((const char*)dev_table + sizeof(FrameTableHeader)); }
+template <class K>
+static int32_t scale_boxes_table(vti_ctx* c, const float* dets, const int32_t* counts, const void* host_table, const void* dev_table,
+                                 int32_t B, int32_t max_det, float* xyxy, void* stream) {
+    const char* fn = K::scale_boxes_fn;
+    FrameTableHeader h;
+    VTI_TRY(table_check<K>(fn, c, host_table, dev_table, B, h));
+    if (!dets || !counts || !xyxy || max_det < 1 || ((uintptr_t)xyxy & 15))
+        return refuse(c, fn, "bad argument (null pointer, max_det < 1 or dev_xyxy not 16-byte aligned)");
+    if ((int64_t)B * max_det > INT32_MAX) return refuse(c, fn, "B * max_det out of range");
+    VTI_TRY(check_device(c, fn));
+    VTI_HIP(c, K::scale_boxes(dets, counts, B, max_det, c->plan.desc, dev_rows<K>(dev_table), xyxy, (hipStream_t)stream), K::scale_boxes_kernel);
+    return VTI_OK;
+}
+
+// The table predicts up to the NMS: the checks on what those stages take, then letterbox -> scored forward -> NMS.
+template <class K>
+static int32_t predict_table_head(const char* fn, vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table,
+                                  int32_t B, int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic,
+                                  uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts, const float* xyxy,
+                                  void* stream) {
+    if (!frames || !input_scratch || ((uintptr_t)frames & 15) || ((uintptr_t)input_scratch & 3))
+        return refuse(c, fn, "dev_frames (16-byte aligned) and dev_input_scratch (4-byte aligned) are required");
+    if (xyxy && (max_det < 1 || ((uintptr_t)xyxy & 15) || !dets || !counts))
+        return refuse(c, fn, "bad argument (max_det < 1, null dets / counts or dev_xyxy not 16-byte aligned)");
+    VTI_TRY(check_ready(c, B, fn));
+    const vti_desc& d = c->plan.desc;
+    VTI_TRY(letterbox_table<K>(c, frames, host_table, dev_table, B, input_scratch, stream));
+    float* best = nms_workspace_best(c->ws + c->act_bytes, d.max_batch, c->plan.num_anchors);
+    VTI_TRY(vti_forward_scored(c, input_scratch, B, swap_rb, pred, proto, best, stream));
+    return vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream);
+}
+
+// ---- frame-resolution masks through a table: the ragged mask buffer -----------------------------------------------------------
+template <class K>
+static int64_t mask_native_table_bytes(const vti_ctx* c, const void* host_table, int32_t max_det) {
+    if (!c || !host_table || max_det < 1) return 0;
+    FrameTableHeader h;
+    int32_t frame;
+    if (!table_problem<K>(c, host_table, -1, h, frame).empty() || h.B > c->plan.desc.max_batch) return 0;
+    const long long n = native_table_bytes<typename K::Row>(host_table, h.H / 4, h.W / 4, max_det, nullptr);
+    return n < 0 ? 0 : n;
+}
+
+// The argument checks of the ragged-mask calls (everything but the table, which table_check has passed).
+template <class K>
+static int32_t masks_native_table_check(const char* fn, vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts,
+                                        const void* proto, const void* host_table, int32_t B, int32_t max_det, int32_t mode,
+                                        int32_t packing, const uint8_t* masks, int64_t capacity_bytes, const int32_t* offsets,
+                                        const int64_t* bases) {
+    if (!dets || K::masks_pointer_missing(xyxy) || !counts || !proto || !offsets || !bases || max_det < 1 || capacity_bytes < 0 ||
+        (capacity_bytes && !masks))
+        return refuse(c, fn, "bad argument (null pointer, max_det < 1 or capacity_bytes < 0)");
+    if (mode != VTI_MASK_LOGIT && mode != VTI_MASK_SIGMOID) return refuse(c, fn, "bad mode");
+    if (packing == VTI_PACK_U8) return refuse(c, fn, "the ragged mask buffer is bit-packed only (VTI_PACK_BITS)", VTI_ERR_UNSUPPORTED);
+    if (packing != VTI_PACK_BITS) return refuse(c, fn, "bad packing");
+    if (((uintptr_t)masks & 7) || ((uintptr_t)bases & 7) || ((uintptr_t)offsets & 3) || K::masks_dets_misaligned(dets))
+        return refuse(c, fn, K::masks_alignment);
+    const vti_desc& d = c->plan.desc;
+    if (B > d.max_batch) return refuse(c, fn, "B out of range");
+    if (d.nm != 32) return refuse(c, fn, "only nm == 32 prototypes", VTI_ERR_UNSUPPORTED);
+    long long tiles = 0;
+    if (native_table_bytes<typename K::Row>(host_table, d.H / 4, d.W / 4, max_det, &tiles) < 0) return refuse(c, fn, K::no_layout);
+    if (tiles > INT32_MAX || (int64_t)B * max_det > INT32_MAX) return refuse(c, fn, "too many tiles or slots for one call", VTI_ERR_UNSUPPORTED);
+    return VTI_OK;
+}
+
+// `xyxy`: the frame form's frame-px boxes; the window form recomputes its boxes from dets and takes none.
+template <class K>
+static int32_t masks_native_table(vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts, const void* proto,
+                                  const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t mode,
+                                  int32_t packing, uint8_t* masks, int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases,
+                                  void* stream) {
+    const char* fn = K::masks_fn;
+    FrameTableHeader h;
+    VTI_TRY(table_check<K>(fn, c, host_table, dev_table, B, h));
+    VTI_TRY(masks_native_table_check<K>(fn, c, dets, xyxy, counts, proto, host_table, B, max_det, mode, packing, masks, capacity_bytes,
+                                        offsets, mask_bases));
+    if (!c->ws) return refuse(c, fn, "workspace not set", VTI_ERR_STATE);
+    const vti_desc& d = c->plan.desc;
+    void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
+    if (masks_native_frames_workspace_bytes(B) > masks_workspace_bytes(d.max_batch * kMaskSlotsPerFrame, d.H, d.W))
+        return refuse(c, fn, "workspace too small", VTI_ERR_NOMEM);
+    VTI_TRY(check_device(c, fn));
+    VTI_HIP(c, K::masks(d.dtype, dets, xyxy, counts, proto, dev_rows<K>(dev_table), B, max_det, d.H / 4, d.W / 4, mode, masks,
+                        capacity_bytes, offsets, (long long*)mask_bases, mws, (hipStream_t)stream), K::masks_kernel);
+    return VTI_OK;
+}
+
+// Letterbox -> scored forward -> NMS -> boxes in frame px -> ragged frame-resolution masks, every check ahead of the first launch.
+template <class K>
+static int32_t predict_table_native(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                                    int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
+                                    int32_t packing, uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts,
+                                    uint8_t* masks, int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, float* xyxy,
+                                    void* stream) {
+    const char* fn = K::predict_fn;
+    const int32_t mode = mask_mode & ~VTI_MASK_NATIVE;
+    FrameTableHeader h;
+    VTI_TRY(table_check<K>(fn, c, host_table, dev_table, B, h));
+    if (!xyxy) return refuse(c, fn, K::xyxy_required);
+    if (!pred) return refuse(c, fn, "null dev_pred");
+    VTI_TRY(masks_native_table_check<K>(fn, c, dets, xyxy, counts, proto, host_table, B, max_det, mode, packing, masks, capacity_bytes,
+                                        offsets, mask_bases));
+    VTI_TRY(predict_table_head<K>(fn, c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic, input_scratch, pred,
+                                  proto, dets, counts, xyxy, stream));
+    VTI_TRY(scale_boxes_table<K>(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream));
+    return masks_native_table<K>(c, dets, xyxy, counts, proto, host_table, dev_table, B, max_det, mode, packing, masks, capacity_bytes,
+                                 offsets, mask_bases, stream);
+}
+
+extern "C" {
+
+int64_t vti_frame_table_bytes(int32_t B) { return table_bytes<FrameKind>(B); }
+int64_t vti_window_table_bytes(int32_t B) { return table_bytes<WindowKind>(B); }
+
+int32_t vti_pack_frames(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset, int32_t B,
+                        int64_t total_bytes, void* host_table, size_t nbytes) {
+    return pack_table<FrameKind>(c, H, W, H0, W0, byte_offset, nullptr, B, total_bytes, host_table, nbytes);
+}
+int32_t vti_pack_windows(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset,
+                         const int32_t* windows, int32_t B, int64_t total_bytes, void* host_table, size_t nbytes) {
+    return pack_table<WindowKind>(c, H, W, H0, W0, byte_offset, windows, B, total_bytes, host_table, nbytes);
+}
+
+int32_t vti_frame_table_info(const void* host_table, int32_t b, int32_t out_i32[8], double out_f64[5]) {
+    return table_info<FrameKind>(host_table, b, out_i32, out_f64);
+}
+int32_t vti_window_table_info(const void* host_table, int32_t b, int32_t out_i32[12], double out_f64[5]) {
+    return table_info<WindowKind>(host_table, b, out_i32, out_f64);
+}
 
 int32_t vti_letterbox_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
                              uint8_t* out, void* stream) {
-    FrameTableHeader h;
-    if (int32_t rc = frames_check("vti_letterbox_frames", c, host_table, dev_table, B, h)) return rc;
-    if (!frames || !out) return fail(c, VTI_ERR_ARG, "vti_letterbox_frames: null frames or output");
-    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 3))
-        return fail(c, VTI_ERR_ARG, "vti_letterbox_frames: dev_frames must be 16-byte aligned, dev_input 4-byte aligned");
-    if (B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_letterbox_frames: B above max_batch");
-    if (int32_t drc = check_device(c, "vti_letterbox_frames")) return drc;
-    VTI_HIP(c, launch_letterbox(frames, B, 0, 0, frame_rows(dev_table), out, h.H, h.W, (hipStream_t)stream), "letterbox kernel");
-    return VTI_OK;
+    return letterbox_table<FrameKind>(c, frames, host_table, dev_table, B, out, stream);
+}
+int32_t vti_letterbox_windows(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
+                              uint8_t* out, void* stream) {
+    return letterbox_table<WindowKind>(c, frames, host_table, dev_table, B, out, stream);
 }
 
 // The tensors of one forward: the ctx's weights and workspace, the caller's input and outputs.
@@ -669,16 +926,11 @@ int32_t vti_scale_boxes(vti_ctx* c, const float* dets, const int32_t* counts, in
 
 int32_t vti_scale_boxes_frames(vti_ctx* c, const float* dets, const int32_t* counts, const void* host_table, const void* dev_table,
                                int32_t B, int32_t max_det, float* xyxy, void* stream) {
-    FrameTableHeader h;
-    if (int32_t rc = frames_check("vti_scale_boxes_frames", c, host_table, dev_table, B, h)) return rc;
-    if (!dets || !counts || !xyxy || max_det < 1 || ((uintptr_t)xyxy & 15))
-        return fail(c, VTI_ERR_ARG, "vti_scale_boxes_frames: bad argument (null pointer, max_det < 1 or dev_xyxy not 16-byte aligned)");
-    if ((int64_t)B * max_det > INT32_MAX) return fail(c, VTI_ERR_ARG, "vti_scale_boxes_frames: B * max_det out of range");
-    const vti_desc& d = c->plan.desc;
-    if (int32_t drc = check_device(c, "vti_scale_boxes_frames")) return drc;
-    VTI_HIP(c, launch_scale_boxes(dets, counts, B, max_det, d.nm, d.H, d.W, 0, 0, frame_rows(dev_table), xyxy, (hipStream_t)stream),
-            "scale_boxes kernel");
-    return VTI_OK;
+    return scale_boxes_table<FrameKind>(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream);
+}
+int32_t vti_scale_boxes_windows(vti_ctx* c, const float* dets, const int32_t* counts, const void* host_table, const void* dev_table,
+                                int32_t B, int32_t max_det, float* xyxy, void* stream) {
+    return scale_boxes_table<WindowKind>(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream);
 }
 
 int32_t vti_predict(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, int32_t W0, int32_t swap_rb, float conf,
@@ -711,94 +963,40 @@ int32_t vti_predict(vti_ctx* c, const uint8_t* frames, int32_t B, int32_t H0, in
     return VTI_OK;
 }
 
-// vti_predict_frames up to the NMS: the checks on what those stages take, then letterbox -> scored forward -> NMS.
-// `letterbox`: vti_letterbox_frames, or vti_letterbox_windows for a window table.
-static int32_t predict_frames_head(const char* fn, vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table,
-                                   int32_t B, int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic,
-                                   uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts, const float* xyxy,
-                                   void* stream, decltype(&vti_letterbox_frames) letterbox = vti_letterbox_frames) {
-    int32_t rc;
-    if (!frames || !input_scratch || ((uintptr_t)frames & 15) || ((uintptr_t)input_scratch & 3))
-        return fail(c, VTI_ERR_ARG, std::string(fn) + ": dev_frames (16-byte aligned) and dev_input_scratch (4-byte aligned) are required");
-    if (xyxy && (max_det < 1 || ((uintptr_t)xyxy & 15) || !dets || !counts))
-        return fail(c, VTI_ERR_ARG, std::string(fn) + ": bad argument (max_det < 1, null dets / counts or dev_xyxy not 16-byte aligned)");
-    if ((rc = check_ready(c, B, fn))) return rc;
-    const vti_desc& d = c->plan.desc;
-    if ((rc = letterbox(c, frames, host_table, dev_table, B, input_scratch, stream))) return rc;
-    float* best = nms_workspace_best(c->ws + c->act_bytes, d.max_batch, c->plan.num_anchors);
-    if ((rc = vti_forward_scored(c, input_scratch, B, swap_rb, pred, proto, best, stream))) return rc;
-    return vti_nms_scored(c, pred, best, B, conf, iou, max_det, agnostic, dets, counts, stream);
-}
-
+// Canvas-size masks for frames of differing sizes; the frame-resolution ones are vti_predict_frames_native's.
 int32_t vti_predict_frames(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
                            int32_t swap_rb, float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode,
                            int32_t packing, uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts,
                            uint8_t* masks, int32_t capacity, int32_t* offsets, float* xyxy, void* stream) {
+    const char* fn = "vti_predict_frames";
     FrameTableHeader h;
-    int32_t rc = frames_check("vti_predict_frames", c, host_table, dev_table, B, h);
-    if (rc) return rc;
-    if (mask_mode & VTI_MASK_NATIVE)
-        return fail(c, VTI_ERR_UNSUPPORTED, "vti_predict_frames: VTI_MASK_NATIVE needs frames of one size (vti_predict)");
-    if ((rc = predict_frames_head("vti_predict_frames", c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic,
-                                  input_scratch, pred, proto, dets, counts, xyxy, stream)))
-        return rc;
-    if ((rc = vti_masks(c, dets, counts, proto, B, max_det, mask_mode, packing, masks, capacity, offsets, stream))) return rc;
-    if (xyxy && (rc = vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
-    return VTI_OK;
+    VTI_TRY(frames_check(fn, c, host_table, dev_table, B, h));
+    if (mask_mode & VTI_MASK_NATIVE) return refuse(c, fn, "VTI_MASK_NATIVE needs frames of one size (vti_predict)", VTI_ERR_UNSUPPORTED);
+    VTI_TRY(predict_table_head<FrameKind>(fn, c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic, input_scratch,
+                                          pred, proto, dets, counts, xyxy, stream));
+    VTI_TRY(vti_masks(c, dets, counts, proto, B, max_det, mask_mode, packing, masks, capacity, offsets, stream));
+    return xyxy ? vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream) : VTI_OK;
 }
 
-// ---- frame-resolution masks for frames of differing sizes: the ragged mask buffer ---------------------------------------------
+// ---- frame-resolution masks for frames of differing sizes, and for a window of each: the ragged mask buffer ------------------
 int64_t vti_mask_native_frames_bytes(const vti_ctx* c, const void* host_table, int32_t max_det) {
-    if (!c || !host_table || max_det < 1) return 0;
-    FrameTableHeader h;
-    int32_t frame;
-    if (frame_table_problem(c, host_table, -1, h, frame) || h.B > c->plan.desc.max_batch) return 0;
-    const long long n = native_frames_bytes(host_table, h.H / 4, h.W / 4, max_det, nullptr);
-    return n < 0 ? 0 : n;
+    return mask_native_table_bytes<FrameKind>(c, host_table, max_det);
 }
-
-// The argument checks of vti_masks_native_frames (everything but the table, which frames_check has passed).
-static int32_t masks_native_frames_check(const char* fn, vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts,
-                                         const void* proto, const void* host_table, int32_t B, int32_t max_det, int32_t mode,
-                                         int32_t packing, const uint8_t* masks, int64_t capacity_bytes, const int32_t* offsets,
-                                         const int64_t* bases) {
-    char msg[200];
-    auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
-    if (!dets || !xyxy || !counts || !proto || !offsets || !bases || max_det < 1 || capacity_bytes < 0 || (capacity_bytes && !masks))
-        return bad(VTI_ERR_ARG, "bad argument (null pointer, max_det < 1 or capacity_bytes < 0)");
-    if (mode != VTI_MASK_LOGIT && mode != VTI_MASK_SIGMOID) return bad(VTI_ERR_ARG, "bad mode");
-    if (packing == VTI_PACK_U8) return bad(VTI_ERR_UNSUPPORTED, "the ragged mask buffer is bit-packed only (VTI_PACK_BITS)");
-    if (packing != VTI_PACK_BITS) return bad(VTI_ERR_ARG, "bad packing");
-    if (((uintptr_t)masks & 7) || ((uintptr_t)bases & 7) || ((uintptr_t)offsets & 3))
-        return bad(VTI_ERR_ARG, "dev_masks and dev_mask_bases must be 8-byte aligned, dev_offsets 4-byte aligned");
-    const vti_desc& d = c->plan.desc;
-    if (B > d.max_batch) return bad(VTI_ERR_ARG, "B out of range");
-    if (d.nm != 32) return bad(VTI_ERR_UNSUPPORTED, "only nm == 32 prototypes");
-    long long tiles = 0;
-    if (native_frames_bytes(host_table, d.H / 4, d.W / 4, max_det, &tiles) < 0)
-        return bad(VTI_ERR_ARG, "a frame of host_table has no native mask layout (slot below 2 GiB)");
-    if (tiles > INT32_MAX || (int64_t)B * max_det > INT32_MAX) return bad(VTI_ERR_UNSUPPORTED, "too many tiles or slots for one call");
-    return VTI_OK;
+int64_t vti_mask_native_windows_bytes(const vti_ctx* c, const void* host_table, int32_t max_det) {
+    return mask_native_table_bytes<WindowKind>(c, host_table, max_det);
 }
 
 int32_t vti_masks_native_frames(vti_ctx* c, const float* dets, const float* xyxy, const int32_t* counts, const void* proto,
                                 const void* host_table, const void* dev_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing,
                                 uint8_t* masks, int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, void* stream) {
-    FrameTableHeader h;
-    if (int32_t rc = frames_check("vti_masks_native_frames", c, host_table, dev_table, B, h)) return rc;
-    if (int32_t rc = masks_native_frames_check("vti_masks_native_frames", c, dets, xyxy, counts, proto, host_table, B, max_det, mode, packing,
-                                               masks, capacity_bytes, offsets, mask_bases))
-        return rc;
-    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_masks_native_frames: workspace not set");
-    const vti_desc& d = c->plan.desc;
-    void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
-    if (masks_native_frames_workspace_bytes(B) > masks_workspace_bytes(d.max_batch * kMaskSlotsPerFrame, d.H, d.W))
-        return fail(c, VTI_ERR_NOMEM, "vti_masks_native_frames: workspace too small");
-    if (int32_t drc = check_device(c, "vti_masks_native_frames")) return drc;
-    VTI_HIP(c, launch_masks_native_frames(d.dtype, dets, xyxy, counts, proto, frame_rows(dev_table), B, max_det, d.H / 4, d.W / 4, mode,
-                                          masks, capacity_bytes, offsets, (long long*)mask_bases, mws, (hipStream_t)stream),
-            "native mask kernel (frames)");
-    return VTI_OK;
+    return masks_native_table<FrameKind>(c, dets, xyxy, counts, proto, host_table, dev_table, B, max_det, mode, packing, masks,
+                                         capacity_bytes, offsets, mask_bases, stream);
+}
+int32_t vti_masks_native_windows(vti_ctx* c, const float* dets, const int32_t* counts, const void* proto, const void* host_table,
+                                 const void* dev_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing, uint8_t* masks,
+                                 int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, void* stream) {
+    return masks_native_table<WindowKind>(c, dets, nullptr, counts, proto, host_table, dev_table, B, max_det, mode, packing, masks,
+                                          capacity_bytes, offsets, mask_bases, stream);
 }
 
 int32_t vti_predict_frames_native(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
@@ -806,234 +1004,17 @@ int32_t vti_predict_frames_native(vti_ctx* c, const uint8_t* frames, const void*
                                   int32_t packing, uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts,
                                   uint8_t* masks, int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, float* xyxy,
                                   void* stream) {
-    FrameTableHeader h;
-    int32_t rc = frames_check("vti_predict_frames_native", c, host_table, dev_table, B, h);
-    if (rc) return rc;
-    if (!xyxy) return fail(c, VTI_ERR_ARG, "vti_predict_frames_native: dev_xyxy is required (the masks are cropped to the frame-px boxes)");
-    if (!pred) return fail(c, VTI_ERR_ARG, "vti_predict_frames_native: null dev_pred");
-    if ((rc = masks_native_frames_check("vti_predict_frames_native", c, dets, xyxy, counts, proto, host_table, B, max_det,
-                                        mask_mode & ~VTI_MASK_NATIVE, packing, masks, capacity_bytes, offsets, mask_bases)))
-        return rc;
-    if ((rc = predict_frames_head("vti_predict_frames_native", c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic,
-                                  input_scratch, pred, proto, dets, counts, xyxy, stream)))
-        return rc;
-    if ((rc = vti_scale_boxes_frames(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
-    return vti_masks_native_frames(c, dets, xyxy, counts, proto, host_table, dev_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE, packing,
-                                   masks, capacity_bytes, offsets, mask_bases, stream);
+    return predict_table_native<FrameKind>(c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic, mask_mode, packing,
+                                           input_scratch, pred, proto, dets, counts, masks, capacity_bytes, offsets, mask_bases, xyxy,
+                                           stream);
 }
-
-// ---- predict on a window of each frame: the window table ----------------------------------------------------------------------
-int64_t vti_window_table_bytes(int32_t B) {
-    return B < 1 ? 0 : (int64_t)sizeof(FrameTableHeader) + (int64_t)B * (int64_t)sizeof(WindowRow);
-}
-
-// What is wrong with one window of an H0 x W0 frame for the H x W canvas (nullptr: nothing); the frame itself passed frame_error.
-static const char* window_error(int32_t H, int32_t W, int32_t H0, int32_t W0, int32_t x0, int32_t y0, int32_t w, int32_t h) {
-    if (w < 1 || h < 1) return "the window's w and h must be >= 1";
-    if (x0 < 0 || y0 < 0 || x0 > W0 - w || y0 > H0 - h) return "the window does not lie inside its frame";
-    int nh, nw, top, left;
-    letterbox_geom(h, w, H, W, nh, nw, top, left);
-    if (nh < 1 || nw < 1) return "the resized window would be below 1 px";
-    if (top < 0 || left < 0 || top + nh > H || left + nw > W) return "the resized window does not fit the canvas";
-    return nullptr;
-}
-
-static WindowRow window_row(const void* host_table, int32_t k) {
-    WindowRow r;
-    memcpy(&r, (const char*)host_table + sizeof(FrameTableHeader) + (size_t)k * sizeof r, sizeof r);
-    return r;
-}
-
-int32_t vti_pack_windows(vti_ctx* c, int32_t H, int32_t W, const int32_t* H0, const int32_t* W0, const int64_t* byte_offset,
-                         const int32_t* windows, int32_t B, int64_t total_bytes, void* host_table, size_t nbytes) {
-    if (!H0 || !W0 || !byte_offset || !windows || !host_table || B < 1)
-        return fail(c, VTI_ERR_ARG, "vti_pack_windows: null array or table, or B < 1");
-    if (H < 32 || W < 32 || (H & 31) || (W & 31) || total_bytes < 0)
-        return fail(c, VTI_ERR_ARG, "vti_pack_windows: the canvas H, W must be multiples of 32, total_bytes >= 0");
-    if ((int64_t)nbytes < vti_window_table_bytes(B))
-        return fail(c, VTI_ERR_ARG, "vti_pack_windows: table smaller than vti_window_table_bytes()");
-    if (c && B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_pack_windows: B above the ctx's max_batch");
-    for (int32_t b = 0; b < B; ++b) {
-        const int32_t* w = windows + 4 * (size_t)b;
-        const char* e = frame_error(H, W, H0[b], W0[b], byte_offset[b], total_bytes);
-        if (!e) e = window_error(H, W, H0[b], W0[b], w[0], w[1], w[2], w[3]);
-        if (e) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "vti_pack_windows: frame %d: %s", b, e);
-            return fail(c, VTI_ERR_ARG, msg);
-        }
-    }
-    FrameTableHeader h;
-    memset(&h, 0, sizeof h);
-    h.magic = kWindowTableMagic; h.B = B; h.H = H; h.W = W; h.total_bytes = total_bytes;
-    for (int32_t b = 0; b < B; ++b) {
-        const int32_t* w = windows + 4 * (size_t)b;
-        WindowRow r;
-        memset(&r, 0, sizeof r);
-        frame_row_fill(H, W, w[3], w[2], byte_offset[b] + 3 * ((int64_t)w[1] * W0[b] + w[0]), r.crop);
-        r.frame_offset = byte_offset[b]; r.H0 = H0[b]; r.W0 = W0[b]; r.x0 = w[0]; r.y0 = w[1];
-        h.max_H0 = std::max(h.max_H0, H0[b]); h.max_W0 = std::max(h.max_W0, W0[b]);
-        memcpy((char*)host_table + sizeof h + (size_t)b * sizeof r, &r, sizeof r);
-    }
-    memcpy(host_table, &h, sizeof h);
-    return VTI_OK;
-}
-
-int32_t vti_window_table_info(const void* host_table, int32_t b, int32_t out_i32[12], double out_f64[5]) {
-    if (!host_table || !out_i32) return VTI_ERR_ARG;
-    const FrameTableHeader h = table_header(host_table);
-    if (h.magic != kWindowTableMagic || h.B < 1 || b < -1 || b >= h.B) return VTI_ERR_ARG;
-    if (b < 0) {
-        const int32_t v[12] = {h.B, h.H, h.W, h.max_H0, h.max_W0, 0, (int32_t)(h.total_bytes & 0xffffffff), (int32_t)(h.total_bytes >> 32),
-                               0, 0, 0, 0};
-        memcpy(out_i32, v, sizeof v);
-        return VTI_OK;
-    }
-    const WindowRow w = window_row(host_table, b);
-    const FrameRow& r = w.crop;
-    const int32_t v[12] = {r.H0, r.W0, r.new_h, r.new_w, r.top, r.left, (int32_t)(r.offset & 0xffffffff), (int32_t)(r.offset >> 32),
-                           w.x0, w.y0, w.H0, w.W0};
-    memcpy(out_i32, v, sizeof v);
-    if (out_f64) { out_f64[0] = r.scale_x; out_f64[1] = r.scale_y; out_f64[2] = r.gain; out_f64[3] = r.padx; out_f64[4] = r.pady; }
-    return VTI_OK;
-}
-
-// frame_table_problem for a window table: every row's frame passes frame_error, its window window_error, and the crop row holds the
-// window's size and first byte (what the kernels form addresses from).
-static const char* window_table_problem(const vti_ctx* c, const void* host_table, int32_t B, FrameTableHeader& h, int32_t& frame) {
-    frame = -1;
-    h = table_header(host_table);
-    if (h.magic != kWindowTableMagic) return "host_table is not a table of vti_pack_windows";
-    if (h.B < 1 || (B >= 0 && h.B != B)) return "the window table was packed for another B";
-    if (h.H != c->plan.desc.H || h.W != c->plan.desc.W) return "the window table was packed for another canvas (H x W)";
-    for (int32_t b = 0; b < h.B; ++b) {
-        const WindowRow w = window_row(host_table, b);
-        const char* e = frame_error(h.H, h.W, w.H0, w.W0, w.frame_offset, h.total_bytes);
-        if (!e && (w.H0 > h.max_H0 || w.W0 > h.max_W0)) e = "larger than the table's recorded maximum";
-        if (!e) e = window_error(h.H, h.W, w.H0, w.W0, w.x0, w.y0, w.crop.W0, w.crop.H0);
-        if (!e && w.crop.offset != w.frame_offset + 3 * ((int64_t)w.y0 * w.W0 + w.x0)) e = "the window's first byte is not where its origin puts it";
-        if (e) { frame = b; return e; }
-    }
-    return nullptr;
-}
-
-static int32_t windows_check(const char* fn, vti_ctx* c, const void* host_table, const void* dev_table, int32_t B, FrameTableHeader& h) {
-    char msg[200];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, VTI_ERR_ARG, msg); };
-    if (!c) return VTI_ERR_ARG;
-    if (!host_table || !dev_table) return bad("null window table (host copy or device copy)");
-    if ((uintptr_t)dev_table & 15) return bad("the device window table must be 16-byte aligned");
-    int32_t frame;
-    if (B < 1) {
-        h = table_header(host_table);
-        return bad(h.magic != kWindowTableMagic ? "host_table is not a table of vti_pack_windows" : "the window table was packed for another B");
-    }
-    if (const char* e = window_table_problem(c, host_table, B, h, frame)) {
-        if (frame < 0) return bad(e);
-        snprintf(msg, sizeof msg, "%s: frame %d of host_table: %s", fn, frame, e);
-        return fail(c, VTI_ERR_ARG, msg);
-    }
-    return VTI_OK;
-}
-
-static const WindowRow* window_rows(const void* dev_table) { return (const WindowRow*)((const char*)dev_table + sizeof(FrameTableHeader)); }
-
-int32_t vti_letterbox_windows(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B,
-                              uint8_t* out, void* stream) {
-    FrameTableHeader h;
-    if (int32_t rc = windows_check("vti_letterbox_windows", c, host_table, dev_table, B, h)) return rc;
-    if (!frames || !out) return fail(c, VTI_ERR_ARG, "vti_letterbox_windows: null frames or output");
-    if (((uintptr_t)frames & 15) || ((uintptr_t)out & 3))
-        return fail(c, VTI_ERR_ARG, "vti_letterbox_windows: dev_frames must be 16-byte aligned, dev_input 4-byte aligned");
-    if (B > c->plan.desc.max_batch) return fail(c, VTI_ERR_ARG, "vti_letterbox_windows: B above max_batch");
-    if (int32_t drc = check_device(c, "vti_letterbox_windows")) return drc;
-    VTI_HIP(c, launch_letterbox_windows(frames, B, window_rows(dev_table), out, h.H, h.W, (hipStream_t)stream), "letterbox kernel (windows)");
-    return VTI_OK;
-}
-
-int32_t vti_scale_boxes_windows(vti_ctx* c, const float* dets, const int32_t* counts, const void* host_table, const void* dev_table,
-                                int32_t B, int32_t max_det, float* xyxy, void* stream) {
-    FrameTableHeader h;
-    if (int32_t rc = windows_check("vti_scale_boxes_windows", c, host_table, dev_table, B, h)) return rc;
-    if (!dets || !counts || !xyxy || max_det < 1 || ((uintptr_t)xyxy & 15))
-        return fail(c, VTI_ERR_ARG, "vti_scale_boxes_windows: bad argument (null pointer, max_det < 1 or dev_xyxy not 16-byte aligned)");
-    if ((int64_t)B * max_det > INT32_MAX) return fail(c, VTI_ERR_ARG, "vti_scale_boxes_windows: B * max_det out of range");
-    if (int32_t drc = check_device(c, "vti_scale_boxes_windows")) return drc;
-    VTI_HIP(c, launch_scale_boxes_windows(dets, counts, B, max_det, c->plan.desc.nm, window_rows(dev_table), xyxy, (hipStream_t)stream),
-            "scale_boxes kernel (windows)");
-    return VTI_OK;
-}
-
-int64_t vti_mask_native_windows_bytes(const vti_ctx* c, const void* host_table, int32_t max_det) {
-    if (!c || !host_table || max_det < 1) return 0;
-    FrameTableHeader h;
-    int32_t frame;
-    if (window_table_problem(c, host_table, -1, h, frame) || h.B > c->plan.desc.max_batch) return 0;
-    const long long n = native_windows_bytes(host_table, h.H / 4, h.W / 4, max_det, nullptr);
-    return n < 0 ? 0 : n;
-}
-
-// The argument checks of vti_masks_native_windows (everything but the table, which windows_check has passed).
-static int32_t masks_native_windows_check(const char* fn, vti_ctx* c, const float* dets, const int32_t* counts, const void* proto,
-                                          const void* host_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing,
-                                          const uint8_t* masks, int64_t capacity_bytes, const int32_t* offsets, const int64_t* bases) {
-    char msg[200];
-    auto bad = [&](int32_t rc, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(c, rc, msg); };
-    if (!dets || !counts || !proto || !offsets || !bases || max_det < 1 || capacity_bytes < 0 || (capacity_bytes && !masks))
-        return bad(VTI_ERR_ARG, "bad argument (null pointer, max_det < 1 or capacity_bytes < 0)");
-    if (mode != VTI_MASK_LOGIT && mode != VTI_MASK_SIGMOID) return bad(VTI_ERR_ARG, "bad mode");
-    if (packing == VTI_PACK_U8) return bad(VTI_ERR_UNSUPPORTED, "the ragged mask buffer is bit-packed only (VTI_PACK_BITS)");
-    if (packing != VTI_PACK_BITS) return bad(VTI_ERR_ARG, "bad packing");
-    if (((uintptr_t)masks & 7) || ((uintptr_t)bases & 7) || ((uintptr_t)offsets & 3) || ((uintptr_t)dets & 7))
-        return bad(VTI_ERR_ARG, "dev_masks, dev_mask_bases and dev_dets must be 8-byte aligned, dev_offsets 4-byte aligned");
-    const vti_desc& d = c->plan.desc;
-    if (B > d.max_batch) return bad(VTI_ERR_ARG, "B out of range");
-    if (d.nm != 32) return bad(VTI_ERR_UNSUPPORTED, "only nm == 32 prototypes");
-    long long tiles = 0;
-    if (native_windows_bytes(host_table, d.H / 4, d.W / 4, max_det, &tiles) < 0)
-        return bad(VTI_ERR_ARG, "a frame or a window of host_table has no native mask layout (slot below 2 GiB)");
-    if (tiles > INT32_MAX || (int64_t)B * max_det > INT32_MAX) return bad(VTI_ERR_UNSUPPORTED, "too many tiles or slots for one call");
-    return VTI_OK;
-}
-
-int32_t vti_masks_native_windows(vti_ctx* c, const float* dets, const int32_t* counts, const void* proto, const void* host_table,
-                                 const void* dev_table, int32_t B, int32_t max_det, int32_t mode, int32_t packing, uint8_t* masks,
-                                 int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, void* stream) {
-    FrameTableHeader h;
-    if (int32_t rc = windows_check("vti_masks_native_windows", c, host_table, dev_table, B, h)) return rc;
-    if (int32_t rc = masks_native_windows_check("vti_masks_native_windows", c, dets, counts, proto, host_table, B, max_det, mode, packing,
-                                                masks, capacity_bytes, offsets, mask_bases))
-        return rc;
-    if (!c->ws) return fail(c, VTI_ERR_STATE, "vti_masks_native_windows: workspace not set");
-    const vti_desc& d = c->plan.desc;
-    void* mws = c->ws + c->act_bytes + nms_workspace_bytes(d.max_batch, c->plan.num_anchors);
-    if (masks_native_frames_workspace_bytes(B) > masks_workspace_bytes(d.max_batch * kMaskSlotsPerFrame, d.H, d.W))
-        return fail(c, VTI_ERR_NOMEM, "vti_masks_native_windows: workspace too small");
-    if (int32_t drc = check_device(c, "vti_masks_native_windows")) return drc;
-    VTI_HIP(c, launch_masks_native_windows(d.dtype, dets, counts, proto, window_rows(dev_table), B, max_det, d.H / 4, d.W / 4, mode, masks,
-                                           capacity_bytes, offsets, (long long*)mask_bases, mws, (hipStream_t)stream),
-            "native mask kernel (windows)");
-    return VTI_OK;
-}
-
 int32_t vti_predict_windows(vti_ctx* c, const uint8_t* frames, const void* host_table, const void* dev_table, int32_t B, int32_t swap_rb,
                             float conf, double iou, int32_t max_det, int32_t agnostic, int32_t mask_mode, int32_t packing,
                             uint8_t* input_scratch, float* pred, void* proto, float* dets, int32_t* counts, uint8_t* masks,
                             int64_t capacity_bytes, int32_t* offsets, int64_t* mask_bases, float* xyxy, void* stream) {
-    FrameTableHeader h;
-    int32_t rc = windows_check("vti_predict_windows", c, host_table, dev_table, B, h);
-    if (rc) return rc;
-    if (!xyxy) return fail(c, VTI_ERR_ARG, "vti_predict_windows: dev_xyxy is required");
-    if (!pred) return fail(c, VTI_ERR_ARG, "vti_predict_windows: null dev_pred");
-    if ((rc = masks_native_windows_check("vti_predict_windows", c, dets, counts, proto, host_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE,
-                                         packing, masks, capacity_bytes, offsets, mask_bases)))
-        return rc;
-    if ((rc = predict_frames_head("vti_predict_windows", c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic,
-                                  input_scratch, pred, proto, dets, counts, xyxy, stream, vti_letterbox_windows)))
-        return rc;
-    if ((rc = vti_scale_boxes_windows(c, dets, counts, host_table, dev_table, B, max_det, xyxy, stream))) return rc;
-    return vti_masks_native_windows(c, dets, counts, proto, host_table, dev_table, B, max_det, mask_mode & ~VTI_MASK_NATIVE, packing, masks,
-                                    capacity_bytes, offsets, mask_bases, stream);
+    return predict_table_native<WindowKind>(c, frames, host_table, dev_table, B, swap_rb, conf, iou, max_det, agnostic, mask_mode, packing,
+                                            input_scratch, pred, proto, dets, counts, masks, capacity_bytes, offsets, mask_bases, xyxy,
+                                            stream);
 }
 
 int32_t vti_mask_to_frame(vti_ctx* c, const uint8_t* masks, int32_t n, int32_t H, int32_t W, int32_t H0, int32_t W0,
@@ -1234,7 +1215,7 @@ static int32_t measure_frames_native(const char* fn, vti_ctx* c, const CameraCho
     VTI_TRY(frames_check(fn, c, host_table, dev_table, o.B, h));
     if (!o.bases) return refuse(c, fn, "null dev_mask_bases");
     if (o.capacity_bytes < 0) return refuse(c, fn, "capacity_bytes must be >= 0");
-    if (native_frames_bytes(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
+    if (native_table_bytes<FrameRow>(host_table, c->plan.desc.H / 4, c->plan.desc.W / 4, 1, nullptr) < 0)
         return refuse(c, fn, "a frame of host_table has no native mask layout (slot below 2 GiB)");
     return measure_impl<F>(fn, c, nullptr, cams, o, FrameSizes{h.max_H0, h.max_W0, frame_rows(dev_table)}, r, stream);
 }
@@ -1385,7 +1366,7 @@ int64_t vti_mask_polygons_frames_scratch_bytes(const vti_ctx* c, const void* hos
     if (!c || !host_table || (native != 0 && native != 1)) return 0;
     FrameTableHeader h;
     int32_t frame;
-    if (frame_table_problem(c, host_table, -1, h, frame) || h.B > c->plan.desc.max_batch) return 0;
+    if (!table_problem<FrameKind>(c, host_table, -1, h, frame).empty() || h.B > c->plan.desc.max_batch) return 0;
     PolyLayout L;
     if (!poly_sizes_ok(h.H, h.W, h.W / 8) || poly_frames_layout(c, host_table, h, native, L) >= 0) return 0;
     return (int64_t)L.total;

@@ -387,9 +387,11 @@ hipError_t launch_masks_native(int dtype, const float* dets, const float* xyxy, 
                                void* ws, hipStream_t st);
 // vti_masks_native_frames: frame b's slots have the layout native_mask_layout(H0[b], W0[b], VTI_PACK_BITS) gives and lie back to back,
 // frame-major, from bases[b] on (i64 [B + 1], written with offsets by the launch's prologue); a slot is live iff it ends at or before
-// capacity_bytes.  rows: the device frame table's rows.  native_frames_bytes (host): the worst case of max_det slots per frame of a
-// packed host table whose rows were validated, and the tiles of the work list; -1 for a frame native_mask_layout cannot describe.
-long long native_frames_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles);
+// capacity_bytes.  rows: the device frame table's rows.  native_table_bytes<Row> (host; Row: FrameRow or WindowRow): the worst case of
+// max_det slots per frame of a packed host table whose rows were validated -- for a window table, slots of the FULL frames -- and
+// the tiles of the work list; -1 for a row native_mask_layout cannot describe.
+template <class Row>
+long long native_table_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles);
 size_t masks_native_frames_workspace_bytes(int B);
 hipError_t launch_masks_native_frames(int dtype, const float* dets, const float* xyxy, const int* counts, const void* proto,
                                       const FrameRow* rows, int B, int max_det, int Hp, int Wp, int mode, uint8_t* masks,
@@ -397,11 +399,10 @@ hipError_t launch_masks_native_frames(int dtype, const float* dets, const float*
 // The window forms (vti_*_windows; rows: the device window table's rows).  Letterbox: the canvas of the contiguous crops, read in
 // place.  Scale boxes: the crop's boxes plus the window's origin (frame px).  Native masks: the ragged buffer of the FULL frames
 // (launch_masks_native_frames' layout, offsets, bases and liveness), each instance's crop mask placed at the window's origin; the
-// boxes are recomputed in window px from `dets`.  native_windows_bytes: native_frames_bytes of the full frames of a host window table.
+// boxes are recomputed in window px from `dets`.
 hipError_t launch_letterbox_windows(const uint8_t* frames, int B, const WindowRow* rows, uint8_t* out, int H, int W, hipStream_t st);
 hipError_t launch_scale_boxes_windows(const float* dets, const int* counts, int B, int max_det, int nm, const WindowRow* rows,
                                       float* xyxy, hipStream_t st);
-long long native_windows_bytes(const void* host_table, int Hp, int Wp, int max_det, long long* tiles);
 hipError_t launch_masks_native_windows(int dtype, const float* dets, const int* counts, const void* proto, const WindowRow* rows, int B,
                                        int max_det, int Hp, int Wp, int mode, uint8_t* masks, long long capacity_bytes, int* offsets,
                                        long long* bases, void* ws, hipStream_t st);

@@ -101,7 +101,25 @@ _CHECKER = _Family(VtiCheckerParams, "CheckerParams", "pack_checker_cameras", "v
                     "vti_annotate_checker_frames_native"))
 
 
-class FrameTable:
+class _Table:
+    """What the packed tables share: `host` (the packed bytes, a CPU u8 tensor) and `dev` (their device copy).  A FrameTable and a
+    WindowTable also name the entry points of their kind, so that one call path serves both."""
+
+    def _ptrs(self):
+        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
+
+    def _row(self, b, extra=()):
+        """Row b through the kind's vti_*_table_info: the letterbox row, then the ints named by `extra`, then the doubles."""
+        i32, f64 = (C.c_int32 * (8 + len(extra)))(), (C.c_double * 5)()
+        check(None, getattr(lib(), self._info)(C.c_void_p(self.host.data_ptr()), int(b), i32, f64))
+        d = dict(zip(("H0", "W0", "new_h", "new_w", "top", "left"), (int(v) for v in i32[:6])))
+        d["offset"] = (i32[6] & 0xFFFFFFFF) | (i32[7] << 32)
+        d.update(zip(extra, (int(v) for v in i32[8:])))
+        d.update(zip(("scale_x", "scale_y", "gain", "padx", "pady"), (float(v) for v in f64)))
+        return d
+
+
+class FrameTable(_Table):
     """A packed frame table (vti_pack_frames) for a batch whose frames differ in size: `host` (the packed bytes, a CPU u8 tensor)
     and `dev` (their device copy), `shapes` [(H0, W0)] per frame, the frames' `byte_offsets` in the flat frame buffer and its
     `total_bytes`, the canvas `H`, `W` it was packed for and the largest `max_H0`, `max_W0`."""
@@ -111,20 +129,15 @@ class FrameTable:
         self.H, self.W, self.B = H, W, len(shapes)
         self.max_H0, self.max_W0 = max(h for h, _ in shapes), max(w for _, w in shapes)
 
-    def _ptrs(self):
-        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
+    _info, _letterbox, _scale_boxes = "vti_frame_table_info", "vti_letterbox_frames", "vti_scale_boxes_frames"
+    _native_bytes, _masks_native, _predict_native = "vti_mask_native_frames_bytes", "vti_masks_native_frames", "vti_predict_frames_native"
 
     def row(self, b):
         """Host only: what row b holds -> dict(H0, W0, new_h, new_w, top, left, offset, scale_x, scale_y, gain, padx, pady)."""
-        i32, f64 = (C.c_int32 * 8)(), (C.c_double * 5)()
-        check(None, lib().vti_frame_table_info(C.c_void_p(self.host.data_ptr()), int(b), i32, f64))
-        d = dict(zip(("H0", "W0", "new_h", "new_w", "top", "left"), (int(v) for v in i32[:6])))
-        d["offset"] = (i32[6] & 0xFFFFFFFF) | (i32[7] << 32)
-        d.update(zip(("scale_x", "scale_y", "gain", "padx", "pady"), (float(v) for v in f64)))
-        return d
+        return self._row(b)
 
 
-class WindowTable:
+class WindowTable(_Table):
     """A packed window table (vti_pack_windows): one window (x0, y0, w, h) of each frame of a batch.  `host` / `dev` as a FrameTable's;
     `frames` is the FrameTable of the FULL frames on the same canvas (the frame buffer's layout, and what every consumer of the
     windowed outputs takes), `windows` [(x0, y0, w, h)] per frame."""
@@ -134,19 +147,13 @@ class WindowTable:
         self.H, self.W, self.B = frames.H, frames.W, frames.B
         self.shapes, self.total_bytes = frames.shapes, frames.total_bytes
 
-    def _ptrs(self):
-        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
+    _info, _letterbox, _scale_boxes = "vti_window_table_info", "vti_letterbox_windows", "vti_scale_boxes_windows"
+    _native_bytes, _masks_native, _predict_native = "vti_mask_native_windows_bytes", "vti_masks_native_windows", "vti_predict_windows"
 
     def row(self, b):
         """Host only: what row b holds -> FrameTable.row's dict for the contiguous crop (H0, W0 are the window's h, w; offset is the
         byte of its first pixel), plus x0, y0 and the frame's frame_H0, frame_W0."""
-        i32, f64 = (C.c_int32 * 12)(), (C.c_double * 5)()
-        check(None, lib().vti_window_table_info(C.c_void_p(self.host.data_ptr()), int(b), i32, f64))
-        d = dict(zip(("H0", "W0", "new_h", "new_w", "top", "left"), (int(v) for v in i32[:6])))
-        d["offset"] = (i32[6] & 0xFFFFFFFF) | (i32[7] << 32)
-        d.update(zip(("x0", "y0", "frame_H0", "frame_W0"), (int(v) for v in i32[8:12])))
-        d.update(zip(("scale_x", "scale_y", "gain", "padx", "pady"), (float(v) for v in f64)))
-        return d
+        return self._row(b, ("x0", "y0", "frame_H0", "frame_W0"))
 
 
 def check_window(window, H0, W0, who="window"):
@@ -166,7 +173,7 @@ def check_window(window, H0, W0, who="window"):
     return x0, y0, x1 - x0, y1 - y0
 
 
-class RawTable:
+class RawTable(_Table):
     """A packed raw table (vti_pack_raw_frames) for raw camera frames that differ in size and / or format: `host` (the packed bytes,
     a CPU u8 tensor) and `dev` (their device copy), `shapes` [(H0, W0)] and `fmts` [VTI_RAW_*] per frame, the frames' `raw_offsets`
     in the flat raw buffer (multiples of 16), their `frame_bytes` and the buffer's `raw_bytes`."""
@@ -175,9 +182,6 @@ class RawTable:
         self.host, self.dev, self.shapes, self.fmts, self.raw_offsets, self.raw_bytes = host, dev, shapes, fmts, raw_offsets, raw_bytes
         self.n = len(shapes)
         self.frame_bytes = [rawframes.frame_bytes(f, h, w) for f, (h, w) in zip(fmts, shapes)]
-
-    def _ptrs(self):
-        return C.c_void_p(self.host.data_ptr()), C.c_void_p(self.dev.data_ptr())
 
 
 class StampTable:
@@ -336,9 +340,13 @@ class Engine:
     def letterbox_frames(self, buf, table, out=None):
         """buf: flat u8 device buffer holding the frames of `table` (pack_frames) -> u8 [B,H,W,3]: vti_letterbox_frames."""
         self._check_frames(table, buf=buf)
+        return self._letterbox_table(buf, table, out)
+
+    def _letterbox_table(self, buf, table, out):
+        """vti_letterbox_frames or vti_letterbox_windows, by the kind of `table` (checked by the caller)."""
         if out is None:
             out = torch.empty((table.B, self.H, self.W, 3), dtype=torch.uint8, device=buf.device)
-        check(self._ctx, lib().vti_letterbox_frames(self._ctx, _ptr(buf), *table._ptrs(), table.B, _ptr(out), _stream()))
+        check(self._ctx, getattr(lib(), table._letterbox)(self._ctx, _ptr(buf), *table._ptrs(), table.B, _ptr(out), _stream()))
         return out
 
     # ---- predict on a window of each frame (vti_pack_windows and the *_windows entry points) ----------------------------------
@@ -370,50 +378,26 @@ class Engine:
         """buf: the flat u8 device buffer of the frames of `table` (pack_windows) -> u8 [B,H,W,3], the canvas of the contiguous crops
         read in place: vti_letterbox_windows."""
         self._check_windows(table, buf=buf)
-        if out is None:
-            out = torch.empty((table.B, self.H, self.W, 3), dtype=torch.uint8, device=buf.device)
-        check(self._ctx, lib().vti_letterbox_windows(self._ctx, _ptr(buf), *table._ptrs(), table.B, _ptr(out), _stream()))
-        return out
+        return self._letterbox_table(buf, table, out)
 
     def scale_boxes_windows(self, dets, counts, table, xyxy=None):
         """The boxes in FRAME px: scale_boxes(frames=the crops' table) plus the window's origin (vti_scale_boxes_windows)."""
-        B, max_det = dets.shape[0], dets.shape[1]
-        self._check_windows(table, B=B)
-        if xyxy is None:
-            xyxy = torch.empty((B, max_det, 4), dtype=torch.float32, device=dets.device)
-        check(self._ctx, lib().vti_scale_boxes_windows(self._ctx, _ptr(dets), _ptr(counts), *table._ptrs(), B, max_det, _ptr(xyxy), _stream()))
-        return xyxy
+        self._check_windows(table, B=dets.shape[0])
+        return self._scale_boxes_table(dets, counts, table, xyxy)
 
     def mask_native_windows_bytes(self, table, max_det):
         """Host only: mask_native_frames_bytes of the full frames of `table`."""
         self._check_windows(table)
-        return int(lib().vti_mask_native_windows_bytes(self._ctx, C.c_void_p(table.host.data_ptr()), int(max_det)))
+        return self._mask_native_table_bytes(table, max_det)
 
     def masks_native_windows(self, dets, counts, proto, table, mode="logit", masks=None, capacity_bytes=None, offsets=None,
                              mask_bases=None):
         """masks_native_frames' ragged buffer for the FULL frames of `table` (pack_windows), every instance's crop mask placed at its
         window's origin and zeros elsewhere (vti_masks_native_windows; the boxes are recomputed in window px from dets).  `masks`:
         a flat u8 buffer, by default mask_native_windows_bytes(table, max_det) bytes.  -> (masks, offsets, mask_bases)."""
-        B, max_det = dets.shape[0], dets.shape[1]
-        self._check_windows(table, B=B)
-        if masks is None:
-            masks = torch.empty(self.mask_native_windows_bytes(table, max_det) if capacity_bytes is None else int(capacity_bytes),
-                                dtype=torch.uint8, device=dets.device)
-        elif masks.dtype != torch.uint8 or masks.dim() != 1 or not masks.is_contiguous():
-            raise ValueError("masks_native_windows: masks must be a flat contiguous uint8 tensor")
-        if capacity_bytes is None:
-            capacity_bytes = masks.numel()
-        if not 0 <= int(capacity_bytes) <= masks.numel():
-            raise ValueError(f"masks_native_windows: capacity_bytes must be in [0, {masks.numel()}]")
-        if offsets is None:
-            offsets = torch.empty((B + 1,), dtype=torch.int32, device=dets.device)
-        if mask_bases is None:
-            mask_bases = torch.empty((B + 1,), dtype=torch.int64, device=dets.device)
-        check(self._ctx, lib().vti_masks_native_windows(self._ctx, _ptr(dets), _ptr(counts), _ptr(proto), *table._ptrs(), B, max_det,
-                                                        MASK_MODES[mode], PACKINGS["bits"],
-                                                        _ptr(masks) if int(capacity_bytes) else C.c_void_p(0), int(capacity_bytes),
-                                                        _ptr(offsets), _ptr(mask_bases), _stream()))
-        return masks, offsets, mask_bases
+        self._check_windows(table, B=dets.shape[0])
+        return self._masks_native_table("masks_native_windows", table, dets, (counts, proto), mode, masks, capacity_bytes, offsets,
+                                        mask_bases, lambda: self.mask_native_windows_bytes(table, dets.shape[1]))
 
     def predict_windows_into(self, buf, table, out, conf=0.25, iou=0.7, max_det=300, agnostic=False, swap_rb=True, mask_mode="logit",
                              nms=None):
@@ -426,9 +410,14 @@ class Engine:
         if nms is not None:
             with self._nms_scope(nms):
                 return self.predict_windows_into(buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode)
-        check(self._ctx, lib().vti_predict_windows(
+        return self._predict_table_native(buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode, "bits")
+
+    def _predict_table_native(self, buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode, packing):
+        """vti_predict_frames_native or vti_predict_windows, by the kind of `table`, into a ragged output set; the caller has checked
+        both."""
+        check(self._ctx, getattr(lib(), table._predict_native)(
             self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
-            int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS["bits"], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
+            int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
             _ptr(out["dets"]), _ptr(out["counts"]), _ptr(out["masks"]), out["masks"].numel(), _ptr(out["offsets"]),
             _ptr(out["mask_bases"]), _ptr(out["xyxy"]), _stream()))
         return out
@@ -447,12 +436,7 @@ class Engine:
             with self._nms_scope(nms):
                 return self.predict_frames_into(buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode, packing, native)
         if native:
-            check(self._ctx, lib().vti_predict_frames_native(
-                self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
-                int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
-                _ptr(out["dets"]), _ptr(out["counts"]), _ptr(out["masks"]), out["masks"].numel(), _ptr(out["offsets"]),
-                _ptr(out["mask_bases"]), _ptr(out["xyxy"]), _stream()))
-            return out
+            return self._predict_table_native(buf, table, out, conf, iou, max_det, agnostic, swap_rb, mask_mode, packing)
         check(self._ctx, lib().vti_predict_frames(
             self._ctx, _ptr(buf), *table._ptrs(), table.B, int(bool(swap_rb)), float(conf), float(iou), int(max_det),
             int(bool(agnostic)), MASK_MODES[mask_mode], PACKINGS[packing], _ptr(out["input"]), _ptr(out["pred"]), _ptr(out["proto"]),
@@ -627,7 +611,10 @@ class Engine:
     def mask_native_frames_bytes(self, table, max_det):
         """Host only: the bytes of max_det frame-resolution slots for every frame of `table` (the worst case of the ragged buffer)."""
         self._check_frames(table)
-        return int(lib().vti_mask_native_frames_bytes(self._ctx, C.c_void_p(table.host.data_ptr()), int(max_det)))
+        return self._mask_native_table_bytes(table, max_det)
+
+    def _mask_native_table_bytes(self, table, max_det):
+        return int(getattr(lib(), table._native_bytes)(self._ctx, C.c_void_p(table.host.data_ptr()), int(max_det)))
 
     def _check_ragged(self, out, table, max_det, who):
         """`out` is a ragged output set (alloc_outputs(native_frames=)) made for the shapes of `table`."""
@@ -642,27 +629,33 @@ class Engine:
         offsets i32 [B+1], mask_bases i64 [B+1]): instance i of frame b is H0[b] rows of 8*ceil(W0[b]/64) bytes from byte
         mask_bases[b] + i * slot_bytes[b] on (frame_masks() cuts the views).  capacity_bytes=None: all of `masks`, or, when that is
         None too, the counts are read back first to size the buffer exactly."""
+        self._check_frames(table, B=dets.shape[0])
+
+        def exact_bytes():
+            cnt = counts.clamp(0, dets.shape[1]).cpu().tolist()
+            return sum(n * self.mask_native_layout(h, w)["slot_bytes"] for n, (h, w) in zip(cnt, table.shapes))
+        return self._masks_native_table("masks_native_frames", table, dets, (xyxy, counts, proto), mode, masks, capacity_bytes, offsets,
+                                        mask_bases, exact_bytes)
+
+    def _masks_native_table(self, who, table, dets, inputs, mode, masks, capacity_bytes, offsets, mask_bases, default_bytes):
+        """vti_masks_native_frames or vti_masks_native_windows, by the kind of `table` (checked by the caller).  inputs: the device
+        tensors between dets and the table in the call; default_bytes(): the buffer's size when neither masks nor capacity_bytes says."""
         B, max_det = dets.shape[0], dets.shape[1]
-        self._check_frames(table, B=B)
         if masks is None:
-            if capacity_bytes is None:
-                cnt = counts.clamp(0, max_det).cpu().tolist()
-                capacity_bytes = sum(n * self.mask_native_layout(h, w)["slot_bytes"] for n, (h, w) in zip(cnt, table.shapes))
-            masks = torch.empty(int(capacity_bytes), dtype=torch.uint8, device=dets.device)
+            masks = torch.empty(int(default_bytes() if capacity_bytes is None else capacity_bytes), dtype=torch.uint8, device=dets.device)
         elif masks.dtype != torch.uint8 or masks.dim() != 1 or not masks.is_contiguous():
-            raise ValueError("masks_native_frames: masks must be a flat contiguous uint8 tensor")
+            raise ValueError(f"{who}: masks must be a flat contiguous uint8 tensor")
         if capacity_bytes is None:
             capacity_bytes = masks.numel()
         if not 0 <= int(capacity_bytes) <= masks.numel():
-            raise ValueError(f"masks_native_frames: capacity_bytes must be in [0, {masks.numel()}]")
+            raise ValueError(f"{who}: capacity_bytes must be in [0, {masks.numel()}]")
         if offsets is None:
             offsets = torch.empty((B + 1,), dtype=torch.int32, device=dets.device)
         if mask_bases is None:
             mask_bases = torch.empty((B + 1,), dtype=torch.int64, device=dets.device)
-        check(self._ctx, lib().vti_masks_native_frames(self._ctx, _ptr(dets), _ptr(xyxy), _ptr(counts), _ptr(proto), *table._ptrs(), B,
-                                                       max_det, MASK_MODES[mode], PACKINGS["bits"],
-                                                       _ptr(masks) if int(capacity_bytes) else C.c_void_p(0), int(capacity_bytes),
-                                                       _ptr(offsets), _ptr(mask_bases), _stream()))
+        check(self._ctx, getattr(lib(), table._masks_native)(
+            self._ctx, _ptr(dets), *[_ptr(t) for t in inputs], *table._ptrs(), B, max_det, MASK_MODES[mode], PACKINGS["bits"],
+            _ptr(masks) if int(capacity_bytes) else C.c_void_p(0), int(capacity_bytes), _ptr(offsets), _ptr(mask_bases), _stream()))
         return masks, offsets, mask_bases
 
     def frame_masks(self, masks, table, b, base, n):
@@ -678,13 +671,19 @@ class Engine:
         B, max_det = dets.shape[0], dets.shape[1]
         if frames is not None:
             self._check_frames(frames, B=B)
+            return self._scale_boxes_table(dets, counts, frames, xyxy)
         if xyxy is None:
             xyxy = torch.empty((B, max_det, 4), dtype=torch.float32, device=dets.device)
-        if frames is not None:
-            check(self._ctx, lib().vti_scale_boxes_frames(self._ctx, _ptr(dets), _ptr(counts), *frames._ptrs(), B, max_det, _ptr(xyxy),
-                                                          _stream()))
-            return xyxy
         check(self._ctx, lib().vti_scale_boxes(self._ctx, _ptr(dets), _ptr(counts), B, max_det, H0, W0, _ptr(xyxy), _stream()))
+        return xyxy
+
+    def _scale_boxes_table(self, dets, counts, table, xyxy):
+        """vti_scale_boxes_frames or vti_scale_boxes_windows, by the kind of `table` (checked by the caller)."""
+        B, max_det = dets.shape[0], dets.shape[1]
+        if xyxy is None:
+            xyxy = torch.empty((B, max_det, 4), dtype=torch.float32, device=dets.device)
+        check(self._ctx, getattr(lib(), table._scale_boxes)(self._ctx, _ptr(dets), _ptr(counts), *table._ptrs(), B, max_det, _ptr(xyxy),
+                                                            _stream()))
         return xyxy
 
     def alloc_outputs(self, B, max_det, capacity, packing="bits", device=None, native_hw=None, native_frames=None):

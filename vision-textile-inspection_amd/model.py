@@ -209,6 +209,7 @@ class YOLO:
         self.max_batch = max_batch
         self._outs = {}
         self._frame_tables = {}
+        self._window_tables = {}
         self._nms_tables = {}
         self.names = names if names is not None else {i: f"class{i}" for i in range(nc)}
         self._engines = {}
@@ -379,6 +380,23 @@ class YOLO:
             ent = self._nms_tables[key] = (eng, eng.pack_nms_table(rows, dev))
         return ent[1]
 
+    @staticmethod
+    def _canvas(imgsz):
+        """The canvas of frames that differ in size (LetterBox(auto=False)): imgsz rounded up to the stride."""
+        new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+        H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
+        return H, W
+
+    def _ragged_outputs(self, eng, dev, B, max_det, shapes, native_frames):
+        """The cached output set of a table predict.  native_frames: the FrameTable of `shapes` for the ragged set
+        (Engine.alloc_outputs(native_frames=)), cached per (engine, B, max_det, shapes); None for canvas-size masks."""
+        okey = (id(eng), B, max_det, tuple(shapes) if native_frames is not None else None)
+        o = self._outs.get(okey)
+        if o is None:
+            self._outs.clear()
+            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=native_frames)
+        return o
+
     def _predict_outputs_frames(self, source, shapes, conf, iou, max_det, imgsz, agnostic_nms, swap_rb, keep_frames=False,
                                 retina_masks=False, nms=None):
         """_predict_outputs for frames of differing sizes: the frames are flattened into one pinned staging buffer, copied with one
@@ -387,17 +405,12 @@ class YOLO:
         keep_frames: as _predict_outputs -- the flat device buffer this predict consumed stays in _last_frames for a caller that
         draws on it.  retina_masks: vti_predict_frames_native into the ragged output set (Engine.alloc_outputs(native_frames=)),
         cached per (engine, B, max_det, shapes) as the uniform retina set is per native_hw.  nms: as _predict_outputs."""
-        new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
-        H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
+        H, W = self._canvas(imgsz)
         B = len(shapes)
         eng = self._engine(H, W, B, max_det)
         dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
         table, buf = self._frame_buffer(eng, source, shapes, dev)
-        okey = (id(eng), B, max_det, tuple(shapes) if retina_masks else None)
-        o = self._outs.get(okey)
-        if o is None:
-            self._outs.clear()
-            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=table if retina_masks else None)
+        o = self._ragged_outputs(eng, dev, B, max_det, shapes, table if retina_masks else None)
         eng.predict_frames_into(buf, table, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode, "bits", native=bool(retina_masks),
                                 nms=nms(eng, dev) if nms is not None else None)
         if keep_frames:
@@ -449,19 +462,15 @@ class YOLO:
         _predict_outputs_frames takes.  -> (engine, ragged output set, WindowTable, (H, W))."""
         B = len(shapes)
         sizes = {(w[3], w[2]) for w in windows}
-        if len(sizes) == 1:
-            (h, w), = sizes
-            H, W = letterbox_shape(h, w, imgsz)
-        else:
-            new_shape = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
-            H, W = (max(math.ceil(x / 32) * 32, 32) for x in new_shape)
+        H, W = letterbox_shape(*next(iter(sizes)), imgsz) if len(sizes) == 1 else self._canvas(imgsz)
         eng = self._engine(H, W, B, max_det)
         dev = torch.device("cuda", self.device) if isinstance(self.device, int) else torch.device(self.device)
         key = (id(eng), tuple(shapes), tuple(windows))
-        wt = getattr(self, "_window_tables", {}).get(key)
+        wt = self._window_tables.get(key)
         if wt is None:
             wt = eng.pack_windows(shapes, windows, dev)
-            self._window_tables = {key: wt}      # one rig at a time, as the frame table
+            self._window_tables.clear()     # one rig at a time, as the frame table
+            self._window_tables[key] = wt
         if isinstance(source, torch.Tensor) and source.dim() == 4:      # a device batch: its bytes are the buffer where frames stay 16-byte aligned
             H0, W0 = shapes[0]
             if (3 * H0 * W0) % 16 == 0 or B == 1:
@@ -474,11 +483,7 @@ class YOLO:
                     buf[off:off + 3 * H0 * W0] = source[b].reshape(-1)
         else:
             buf = self._frame_buffer(eng, source, shapes, dev)[1]
-        okey = (id(eng), B, max_det, tuple(shapes))
-        o = self._outs.get(okey)
-        if o is None:
-            self._outs.clear()
-            o = self._outs[okey] = eng.alloc_outputs(B, max_det, B * max_det, "bits", dev, native_frames=wt.frames)
+        o = self._ragged_outputs(eng, dev, B, max_det, shapes, wt.frames)
         eng.predict_windows_into(buf, wt, o, conf, iou, max_det, agnostic_nms, swap_rb, self.mask_mode,
                                  nms=nms(eng, dev) if nms is not None else None)
         self._last_frames = buf if keep_frames else None
