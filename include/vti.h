@@ -84,11 +84,18 @@ enum { VTI_PACK_U8 = 0, VTI_PACK_BITS = 1 };
 /* vti_masks work-list size: one call handles at most max_batch * VTI_MASK_SLOTS_PER_FRAME instances (capacity above that is
  * VTI_ERR_UNSUPPORTED); vti_workspace_bytes() is sized for it.  Ultralytics' default max_det is 300, the reference's 200. */
 #define VTI_MASK_SLOTS_PER_FRAME 512
+/* The full decode kernel keeps its anchors' rows of 64 + nc + nm logits (and one word of padding each) in 64 KiB of LDS: 64
+ * anchors per workgroup up to nc + nm = 191, fewer above that, and one row must fit: at most this many class + coefficient
+ * channels.  It runs in the plans whose class / coefficient towers do not write pred themselves (VTI_NO_PRED_SCATTER=1, or towers
+ * that do not end in a fused 1x1 stage, as with 160 classes and more); vti_create refuses such a plan above the limit
+ * (VTI_ERR_ARG, the message names both numbers). */
+#define VTI_DECODE_MAX_CHANNELS 16319
 
 /* Model description: replaces what YOLO(model_path) reads out of the .pt (measurement.py:145). */
 typedef struct {
     char scale;        /* 'n','s','m','l','x' */
-    int32_t nc;        /* classes (reference: 2 -- stitch=0, fabric=1, config.py:69-70) */
+    int32_t nc;        /* classes (reference: 2 -- stitch=0, fabric=1, config.py:69-70); >= 1.  A plan that keeps the full decode
+                          kernel needs nc + nm <= VTI_DECODE_MAX_CHANNELS: vti_create says so otherwise */
     int32_t nm;        /* mask coefficients, 32 */
     int32_t reg_max;   /* DFL bins, 16 */
     int32_t H, W;      /* letterboxed input size, multiples of 32 */
@@ -1104,6 +1111,39 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
                          void* dev_out, int32_t out_ld, int32_t out_coff, int32_t out_f32, int32_t swap_rb,
                          int32_t tile_h, int32_t tile_w, int32_t waves_n, int32_t nrep, int32_t iters,
                          float* ms_out, int32_t* cfg_out, void* stream);
+
+/* ---- the forward pass's non-GEMM kernels, one at a time (kernel unit tests) --------- */
+/* Marks the three single-kernel test hooks; libvti.so exports them as it does every other. */
+#define VTI_DEBUG_OPS_API
+/* Like vti_debug_conv2d these take no context and no weights; unlike it they only enqueue their one launch on `stream`.  Every
+ * refusal below is VTI_ERR_ARG with a message in vti_last_error(NULL), made on the host before anything is launched.  T is the
+ * element of `dtype`: fp16 (2 bytes), fp32 or an h2 pair (4 bytes); a "vector" is 16 bytes: 8 fp16 elements, 4 of the others.
+ *
+ * vti_debug_sppf_pool: the SPPF's three chained MaxPool2d(5, 1, 2) of channels [in_coff, in_coff + C) of dev_in (T NHWC
+ * [B,H,W,ld]) into channels [out_coff, out_coff + 3 C) of dev_out (same shape and pitch): the 5x5, 9x9 and 13x13 window maxima,
+ * C channels each.  dev_out may be dev_in, as in the engine, where the SPPF's concat buffer holds all four slices.  An h2 element
+ * is compared by its value hi + lo and copied bit for bit; which of several elements of equal value is kept is unspecified.
+ * *path_out (may be NULL) receives the kernel the launcher chose: 0 the global-memory kernel, 1 the LDS kernel with one vector
+ * per lane group, 4 the LDS kernel with four.  Refused: a null pointer or one that is not 16-byte aligned, an unknown dtype, a
+ * size below 1, a negative offset, C / ld / an offset that is no multiple of the vector, a slice that does not fit in ld, in and
+ * out slices that overlap in one buffer, two different buffers whose byte ranges overlap, more than 2^31 - 1 elements. */
+VTI_DEBUG_OPS_API int32_t vti_debug_sppf_pool(int32_t dtype, const void* dev_in, void* dev_out, int32_t B, int32_t H, int32_t W, int32_t C,
+                            int32_t ld, int32_t in_coff, int32_t out_coff, int32_t* path_out, void* stream);
+/* vti_debug_upsample2x: nn.Upsample(scale_factor=2, mode="nearest") of channels [in_coff, in_coff + C) of dev_in (T NHWC
+ * [B,H,W,in_ld]) into channels [out_coff, out_coff + C) of dev_out (T NHWC [B,2H,2W,out_ld]); a pure copy, so h2 runs as the
+ * 4-byte type it is.  Refused: as above, with the two buffers' byte ranges always having to be disjoint. */
+VTI_DEBUG_OPS_API int32_t vti_debug_upsample2x(int32_t dtype, const void* dev_in, void* dev_out, int32_t B, int32_t H, int32_t W, int32_t C,
+                             int32_t in_ld, int32_t in_coff, int32_t out_ld, int32_t out_coff, void* stream);
+/* vti_debug_decode: the Detect/Segment decode of three levels.  dev_box[l]: f32 [B, H[l]*W[l], 64] (4 sides x 16 DFL bins),
+ * dev_cls[l]: f32 [B, H[l]*W[l], nc] logits, dev_mc[l]: f32 [B, H[l]*W[l], nm]; dev_pred: f32 [B, A, 4 + nc + nm] with
+ * A = sum H[l]*W[l], levels concatenated.  box_only = 0 runs the full decode kernel (boxes, sigmoid scores, coefficients copied);
+ * box_only = 1 the box-only kernel of the plans whose towers write scores and coefficients themselves: it writes the 4 box
+ * values of every row and nothing else, and never reads dev_cls / dev_mc (they may be NULL).  Refused: a null array or pointer
+ * (box_only = 0: in any of the nine), one that is not 4-byte aligned, box_only outside {0, 1}, a size, stride, B, nc or nm below
+ * 1, more than 2^31 - 1 values in pred, and for box_only = 0 nc + nm > VTI_DECODE_MAX_CHANNELS. */
+VTI_DEBUG_OPS_API int32_t vti_debug_decode(int32_t box_only, const float* const* dev_box, const float* const* dev_cls, const float* const* dev_mc,
+                         const int32_t* H, const int32_t* W, const int32_t* stride, int32_t B, int32_t nc, int32_t nm,
+                         float* dev_pred, void* stream);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,9 @@ SIGNATURES = {
     "vti_debug_conv2d": (_I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32,
                                 _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
                                 _P, _P, _P]),
+    "vti_debug_sppf_pool": (_I32, [_I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "vti_debug_upsample2x": (_I32, [_I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "vti_debug_decode": (_I32, [_I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
 }
 
 _lib = None

@@ -83,6 +83,9 @@ __global__ __launch_bounds__(256) void sppf_pool_kernel(const PoolParams p) {
 // LDS and the three chained 5x5 pools run as separable row/column passes -- exactly the reference's chained
 // MaxPool2d(5,1,2) (max is exact, so fp16/fp32 results are bit-identical to the chained form).  G consecutive lanes
 // touch G x 16 contiguous bytes of one pixel (G = 4: 64-byte segments instead of one 16-byte piece per 1-KiB pixel row).
+constexpr int POOL_MAXIT = 8;                       // load rounds of the 256 lanes
+constexpr int POOL_LDS_VECS = POOL_MAXIT * 256;     // 16-byte pieces of one workgroup's map: twice that (cur + tmp) is 64 KiB of LDS
+
 template <typename T, int G>
 __global__ __launch_bounds__(256) void sppf_pool_lds_kernel(const PoolParams p) {
     using vec = typename V16<T>::vec;
@@ -95,23 +98,19 @@ __global__ __launch_bounds__(256) void sppf_pool_lds_kernel(const PoolParams p) 
     const int b = blockIdx.x / cg, c = blockIdx.x - b * cg;
     const T* in = (const T*)p.in + (size_t)b * HW * p.ld + p.in_coff + c * (N * G);
     T* out = (T*)p.out + (size_t)b * HW * p.ld + p.out_coff + c * (N * G);
-    {   // all loads first (a load consumed inside the loop body is one memory round trip per iteration)
-        constexpr int MAXIT = 8;
-        if (HW * G <= MAXIT * 256) {
-            vec r[MAXIT];
+    {   // all loads first (a load consumed inside the loop body is one memory round trip per iteration); sppf_pool_path
+        // sends no map of more than POOL_LDS_VECS pieces here, so POOL_MAXIT rounds of the 256 lanes cover it
+        vec r[POOL_MAXIT];
 #pragma unroll
-            for (int it = 0; it < MAXIT; ++it) {
-                const int i = threadIdx.x + it * 256;
-                const int ic = i < HW * G ? i : 0;
-                r[it] = *(const vec*)(in + (size_t)(ic / G) * p.ld + (ic % G) * N);
-            }
+        for (int it = 0; it < POOL_MAXIT; ++it) {
+            const int i = threadIdx.x + it * 256;
+            const int ic = i < HW * G ? i : 0;
+            r[it] = *(const vec*)(in + (size_t)(ic / G) * p.ld + (ic % G) * N);
+        }
 #pragma unroll
-            for (int it = 0; it < MAXIT; ++it) {
-                const int i = threadIdx.x + it * 256;
-                if (i < HW * G) cur[i] = r[it];
-            }
-        } else {
-            for (int i = threadIdx.x; i < HW * G; i += 256) cur[i] = *(const vec*)(in + (size_t)(i / G) * p.ld + (i % G) * N);
+        for (int it = 0; it < POOL_MAXIT; ++it) {
+            const int i = threadIdx.x + it * 256;
+            if (i < HW * G) cur[i] = r[it];
         }
     }
     __syncthreads();
@@ -146,19 +145,27 @@ __global__ __launch_bounds__(256) void sppf_pool_lds_kernel(const PoolParams p) 
     }
 }
 
+int sppf_pool_path(int dtype, int H, int W, int C) {
+    const int N = dtype == VTI_F16 ? 8 : 4;
+    const long HW = (long)H * W;
+    if (HW * 4 <= POOL_LDS_VECS && C % (4 * N) == 0) return 4;      // four 16-byte pieces per workgroup: 64-byte global segments
+    return HW <= POOL_LDS_VECS ? 1 : 0;
+}
+
 hipError_t launch_sppf_pool(int dtype, const PoolParams& p, hipStream_t st) {
     const int N = dtype == VTI_F16 ? 8 : 4;
     const long total = (long)p.B * p.H * p.W * (p.C / N);
     if (total == 0) return hipSuccess;
-    const size_t lds1 = (size_t)2 * p.H * p.W * 16;
-    if (lds1 * 4 <= 64 * 1024 && p.C % (4 * N) == 0) {      // four 16-byte pieces per workgroup: 64-byte global segments
+    const int path = sppf_pool_path(dtype, p.H, p.W, p.C);
+    const size_t lds1 = (size_t)2 * p.H * p.W * 16;         // cur + tmp of one piece per pixel
+    if (path == 4) {
         const int grid = p.B * (p.C / (4 * N));
         if (dtype == VTI_F16) hipLaunchKernelGGL((sppf_pool_lds_kernel<half_t, 4>), dim3(grid), dim3(256), lds1 * 4, st, p);
         else if (dtype == VTI_H2) hipLaunchKernelGGL((sppf_pool_lds_kernel<h2e, 4>), dim3(grid), dim3(256), lds1 * 4, st, p);
         else hipLaunchKernelGGL((sppf_pool_lds_kernel<float, 4>), dim3(grid), dim3(256), lds1 * 4, st, p);
         return hipGetLastError();
     }
-    if (lds1 <= 64 * 1024) {
+    if (path == 1) {
         const int grid = p.B * (p.C / N);
         if (dtype == VTI_F16) hipLaunchKernelGGL((sppf_pool_lds_kernel<half_t, 1>), dim3(grid), dim3(256), lds1, st, p);
         else if (dtype == VTI_H2) hipLaunchKernelGGL((sppf_pool_lds_kernel<h2e, 1>), dim3(grid), dim3(256), lds1, st, p);
@@ -204,21 +211,29 @@ hipError_t launch_upsample2x(int dtype, const Up2Params& p, hipStream_t st) {
 //   DFL: softmax over reg_max bins per side, expectation with arange weights -> l,t,r,b
 //   dist2bbox(xywh=True): x1y1 = anchor - lt, x2y2 = anchor + rb, (cxcy, wh) * stride
 //   class scores -> sigmoid; mask coefficients copied.
-// One workgroup per (frame, 64 consecutive anchors of one level).  The anchors' rows of the three
+// One workgroup per (frame, TA consecutive anchors of one level).  The anchors' rows of the three
 // head tensors ([anchor][64 | nc | nm], anchor-major) are contiguous, so they are loaded with
-// coalesced dwords into an LDS tile [64][no_in+1]; the anchor-major pred [B,A,4+nc+nm] rows are then
-// written as one contiguous run.
+// coalesced dwords into an LDS tile [TA][no_in+1]; the anchor-major pred [B,A,4+nc+nm] rows are then
+// written as one contiguous run.  TA is DEC_TA = 64 anchors (4 lanes each) while 64 rows fit into 64 KiB of LDS,
+// i.e. up to nc + nm = 191; wider heads take as many rows as fit (decode_tile_anchors), down to one.
 constexpr int DEC_TA = 64;
+constexpr int DEC_LDS_FLOATS = 64 * 1024 / 4;
+static_assert(DEC_LDS_FLOATS / (64 + VTI_DECODE_MAX_CHANNELS + 1) == 1, "vti.h states the widest head one anchor's row fits for");
 
-__global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p, int tiles0, int tiles1, int tiles_per_frame) {
+static int decode_tile_anchors(int nc, int nm) {
+    const long ta = DEC_LDS_FLOATS / (64L + nc + nm + 1);
+    return (int)(ta < DEC_TA ? ta : DEC_TA);
+}
+
+__global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p, int TA, int tiles0, int tiles1, int tiles_per_frame) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const int b = blockIdx.x / tiles_per_frame;
     int t = blockIdx.x - b * tiles_per_frame;
     int l = 0;
     if (t >= tiles0 + tiles1) { l = 2; t -= tiles0 + tiles1; } else if (t >= tiles0) { l = 1; t -= tiles0; }
     const int W = p.W[l], HW = p.H[l] * W;
-    const int la0 = t * DEC_TA;
-    const int na = min(DEC_TA, HW - la0);
+    const int la0 = t * TA;
+    const int na = min(TA, HW - la0);
     const int nbox = 4 * p.reg_max, nin = nbox + p.nc + p.nm, pitch = nin + 1;
     const int tid = threadIdx.x;
     const size_t pix0 = (size_t)b * HW + la0;
@@ -251,7 +266,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p, int t
     const int no = 4 + p.nc + p.nm;
     float* out = p.pred + ((size_t)b * p.A + p.a0[l] + la0) * no;       // anchor-major pred [B, A, no]: rows are contiguous
     const float st = (float)p.stride[l];
-    for (int i = tid; i < no * DEC_TA; i += 256) {
+    for (int i = tid; i < no * TA; i += 256) {
         const int a = i / no, ch = i - a * no;
         if (a >= na) continue;
         const float* r = tile + a * pitch;
@@ -274,12 +289,14 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p, int t
 hipError_t launch_decode(const DecodeParams& p, hipStream_t st) {
     if ((long)p.B * p.A == 0) return hipSuccess;
     if (p.reg_max != 16) return hipErrorInvalidValue;
+    const int TA = decode_tile_anchors(p.nc, p.nm);
+    if (TA < 1) return hipErrorInvalidValue;              // nc + nm > VTI_DECODE_MAX_CHANNELS: vti_create refuses such a plan
     int tiles[3];
-    for (int l = 0; l < 3; ++l) tiles[l] = (p.H[l] * p.W[l] + DEC_TA - 1) / DEC_TA;
-    const int tpf = tiles[0] + tiles[1] + tiles[2];
-    const size_t lds = (size_t)DEC_TA * (4 * p.reg_max + p.nc + p.nm + 1) * sizeof(float);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;     // nc up to ~150 classes
-    hipLaunchKernelGGL(decode_kernel, dim3((unsigned)(p.B * tpf)), dim3(256), lds, st, p, tiles[0], tiles[1], tpf);
+    for (int l = 0; l < 3; ++l) tiles[l] = (p.H[l] * p.W[l] + TA - 1) / TA;
+    const long tpf = (long)tiles[0] + tiles[1] + tiles[2];
+    if (p.B * tpf > 0x7fffffffL) return hipErrorInvalidValue;
+    const size_t lds = (size_t)TA * (4 * p.reg_max + p.nc + p.nm + 1) * sizeof(float);
+    hipLaunchKernelGGL(decode_kernel, dim3((unsigned)(p.B * tpf)), dim3(256), lds, st, p, TA, tiles[0], tiles[1], (int)tpf);
     return hipGetLastError();
 }
 

@@ -866,6 +866,9 @@ std::string Plan::build(const vti_desc& d, const PlanOptions& opt) {
     pl.fuse_bottlenecks();
     pl.fuse_stem();
     pl.scatter_pred();          // and, behind it, fuse_dfl
+    if (!pred_scatter && d.nc + d.nm > VTI_DECODE_MAX_CHANNELS)     // the full decode kernel's LDS tile (launch_decode)
+        return "nc + nm = " + std::to_string(d.nc + d.nm) + " is above VTI_DECODE_MAX_CHANNELS = " + std::to_string(VTI_DECODE_MAX_CHANNELS) +
+               ", the most the decode kernel of this plan takes (its class / coefficient towers do not write pred themselves)";
     const std::string e = pl.choose_geometry_and_offsets();
     if (!e.empty()) return e;
     pl.fold_upsample();

@@ -126,6 +126,21 @@ static const char* measure_params_error(const vti_measure_params& p) {
     return p.two_row_threshold_px == p.two_row_threshold_px ? nullptr : "NaN threshold";
 }
 
+// The single-kernel debug hooks (vti_debug_sppf_pool, vti_debug_upsample2x):
+// One channel slice [coff, coff + C) of a T NHWC tensor of pitch ld: "" or what is wrong with it (vec = elements per 16 bytes).
+static std::string slice_error(const char* what, int C, int ld, int coff, int vec) {
+    if (C < 1 || ld < 1 || coff < 0) return std::string(what) + ": C and ld must be >= 1, the channel offset >= 0";
+    if (C % vec || ld % vec || coff % vec)
+        return std::string(what) + ": C, ld and the channel offset must be multiples of the 16-byte vector (" + std::to_string(vec) + " elements)";
+    if ((int64_t)coff + C > ld) return std::string(what) + ": channels [" + std::to_string(coff) + ", " + std::to_string((int64_t)coff + C) +
+                                       ") do not fit in ld = " + std::to_string(ld);
+    return "";
+}
+static bool ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+
 extern "C" {
 
 int32_t vti_create(const vti_desc* desc, vti_ctx** out) {
@@ -2290,6 +2305,85 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
     (void)hipFree(d_w);
     if (d_b) (void)hipFree(d_b);
     if (e != hipSuccess) return hip_fail(nullptr, e, "vti_debug_conv2d");
+    return VTI_OK;
+}
+
+// ---- the non-GEMM kernels one at a time: every check on the host, then the one launch ----
+int32_t vti_debug_sppf_pool(int32_t dtype, const void* dev_in, void* dev_out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ld,
+                            int32_t in_coff, int32_t out_coff, int32_t* path_out, void* stream) {
+    auto bad = [](const std::string& m) { return fail(nullptr, VTI_ERR_ARG, "vti_debug_sppf_pool: " + m); };
+    if (dtype != VTI_F16 && dtype != VTI_F32 && dtype != VTI_H2) return bad("bad dtype");
+    if (!dev_in || !dev_out) return bad("null pointer");
+    if (((uintptr_t)dev_in | (uintptr_t)dev_out) & 15) return bad("dev_in and dev_out must be 16-byte aligned");
+    if (B < 1 || H < 1 || W < 1) return bad("B, H and W must be >= 1");
+    const int vec = dtype == VTI_F16 ? 8 : 4, esize = 16 / vec;
+    std::string e = slice_error("in", C, ld, in_coff, vec);
+    if (e.empty() && (int64_t)3 * C > ld) e = "out: 3 C channels do not fit in ld = " + std::to_string(ld);
+    if (e.empty()) e = slice_error("out", 3 * C, ld, out_coff, vec);
+    if (!e.empty()) return bad(e);
+    const int64_t elems = (int64_t)B * H * W * ld;
+    if (elems > INT32_MAX) return bad("more than 2^31 - 1 elements");
+    if (dev_in == dev_out) {
+        if (in_coff < out_coff + 3 * C && out_coff < in_coff + C) return bad("the in and out slices overlap in the one buffer");
+    } else if (ranges_overlap(dev_in, elems * esize, dev_out, elems * esize)) {
+        return bad("dev_in and dev_out must be one buffer or two that do not overlap");
+    }
+    PoolParams p;
+    p.in = dev_in; p.out = dev_out; p.B = B; p.H = H; p.W = W; p.C = C; p.ld = ld; p.in_coff = in_coff; p.out_coff = out_coff;
+    if (path_out) *path_out = sppf_pool_path(dtype, H, W, C);
+    const hipError_t he = launch_sppf_pool(dtype, p, (hipStream_t)stream);
+    if (he != hipSuccess) return hip_fail(nullptr, he, "vti_debug_sppf_pool");
+    return VTI_OK;
+}
+
+int32_t vti_debug_upsample2x(int32_t dtype, const void* dev_in, void* dev_out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t in_ld,
+                             int32_t in_coff, int32_t out_ld, int32_t out_coff, void* stream) {
+    auto bad = [](const std::string& m) { return fail(nullptr, VTI_ERR_ARG, "vti_debug_upsample2x: " + m); };
+    if (dtype != VTI_F16 && dtype != VTI_F32 && dtype != VTI_H2) return bad("bad dtype");
+    if (!dev_in || !dev_out) return bad("null pointer");
+    if (((uintptr_t)dev_in | (uintptr_t)dev_out) & 15) return bad("dev_in and dev_out must be 16-byte aligned");
+    if (B < 1 || H < 1 || W < 1) return bad("B, H and W must be >= 1");
+    const int vec = dtype == VTI_F16 ? 8 : 4, esize = 16 / vec;
+    std::string e = slice_error("in", C, in_ld, in_coff, vec);
+    if (e.empty()) e = slice_error("out", C, out_ld, out_coff, vec);
+    if (!e.empty()) return bad(e);
+    const int64_t in_elems = (int64_t)B * H * W * in_ld, out_elems = (int64_t)B * H * W * 4 * out_ld;
+    if (in_elems > INT32_MAX || out_elems > INT32_MAX) return bad("more than 2^31 - 1 elements");
+    if (ranges_overlap(dev_in, in_elems * esize, dev_out, out_elems * esize)) return bad("dev_in and dev_out overlap");
+    Up2Params p;
+    p.in = dev_in; p.out = dev_out; p.B = B; p.H = H; p.W = W; p.C = C; p.in_ld = in_ld; p.in_coff = in_coff; p.out_ld = out_ld; p.out_coff = out_coff;
+    const hipError_t he = launch_upsample2x(dtype, p, (hipStream_t)stream);
+    if (he != hipSuccess) return hip_fail(nullptr, he, "vti_debug_upsample2x");
+    return VTI_OK;
+}
+
+int32_t vti_debug_decode(int32_t box_only, const float* const* dev_box, const float* const* dev_cls, const float* const* dev_mc,
+                         const int32_t* H, const int32_t* W, const int32_t* stride, int32_t B, int32_t nc, int32_t nm, float* dev_pred,
+                         void* stream) {
+    auto bad = [](const std::string& m) { return fail(nullptr, VTI_ERR_ARG, "vti_debug_decode: " + m); };
+    if (box_only != 0 && box_only != 1) return bad("box_only must be 0 or 1");
+    if (!dev_box || !H || !W || !stride || !dev_pred || (!box_only && (!dev_cls || !dev_mc))) return bad("null pointer");
+    if (B < 1 || nc < 1 || nm < 1) return bad("B, nc and nm must be >= 1");
+    if (!box_only && nc + (int64_t)nm > VTI_DECODE_MAX_CHANNELS)
+        return bad("nc + nm = " + std::to_string(nc + (int64_t)nm) + " is above VTI_DECODE_MAX_CHANNELS = " +
+                   std::to_string(VTI_DECODE_MAX_CHANNELS) + ", the most the full decode kernel takes");
+    DecodeParams p;
+    int64_t A = 0;
+    uintptr_t align = (uintptr_t)dev_pred;
+    for (int l = 0; l < 3; ++l) {
+        if (H[l] < 1 || W[l] < 1 || stride[l] < 1) return bad("level " + std::to_string(l) + ": H, W and stride must be >= 1");
+        if (!dev_box[l] || (!box_only && (!dev_cls[l] || !dev_mc[l]))) return bad("level " + std::to_string(l) + ": null pointer");
+        p.box[l] = dev_box[l]; p.cls[l] = box_only ? nullptr : dev_cls[l]; p.mc[l] = box_only ? nullptr : dev_mc[l];
+        align |= (uintptr_t)p.box[l] | (uintptr_t)p.cls[l] | (uintptr_t)p.mc[l];
+        p.H[l] = H[l]; p.W[l] = W[l]; p.stride[l] = stride[l]; p.a0[l] = (int)A;
+        A += (int64_t)H[l] * W[l];
+        if (A > INT32_MAX) return bad("more than 2^31 - 1 values in pred");
+    }
+    if (align & 3) return bad("every pointer must be 4-byte aligned");
+    if ((int64_t)B * A * (4 + (int64_t)nc + nm) > INT32_MAX || (int64_t)B * A * 64 > INT32_MAX) return bad("more than 2^31 - 1 values in pred");
+    p.B = B; p.A = (int)A; p.nc = nc; p.nm = nm; p.reg_max = 16; p.pred = dev_pred;
+    const hipError_t he = box_only ? launch_box_decode(p, (hipStream_t)stream) : launch_decode(p, (hipStream_t)stream);
+    if (he != hipSuccess) return hip_fail(nullptr, he, "vti_debug_decode");
     return VTI_OK;
 }
 

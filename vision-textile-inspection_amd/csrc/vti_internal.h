@@ -258,6 +258,9 @@ bool bneck_pk_fits(int TH, int NREP);
 
 struct PoolParams { const void* in; void* out; int B, H, W, C, ld, in_coff, out_coff; };
 hipError_t launch_sppf_pool(int dtype, const PoolParams& p, hipStream_t st);
+// The kernel launch_sppf_pool runs for a map (its only decision; vti_debug_sppf_pool reports it): 4 / 1 = the LDS kernel with four /
+// one 16-byte pieces per lane group, 0 = the global-memory kernel.
+int sppf_pool_path(int dtype, int H, int W, int C);
 
 struct Up2Params { const void* in; void* out; int B, H, W, C, in_ld, in_coff, out_ld, out_coff; };
 hipError_t launch_upsample2x(int dtype, const Up2Params& p, hipStream_t st);
@@ -268,7 +271,7 @@ struct DecodeParams {
     int B, A, nc, nm, reg_max;
     float* pred;                          // [B, 4+nc+nm, A]
 };
-hipError_t launch_decode(const DecodeParams& p, hipStream_t st);
+hipError_t launch_decode(const DecodeParams& p, hipStream_t st);         // nc + nm <= VTI_DECODE_MAX_CHANNELS (its LDS tile)
 hipError_t launch_box_decode(const DecodeParams& p, hipStream_t st);   // DFL + dist2bbox only (pred_scatter plans)
 
 // ---- launch parameters (launch.cpp; host only, nothing there sees a context, a stream or an event) ----------------------------

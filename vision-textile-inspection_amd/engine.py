@@ -1683,3 +1683,64 @@ def debug_conv2d(x, w, b, k, s, kind=0, dtype="fp16", res=None, out=None, in_cof
     if rc != 0:
         raise _lib.VtiError(rc, lib().vti_last_error(None).decode())
     return out, ms.value, dict(tile=(cfg[0], cfg[1]), waves_n=cfg[2], nrep=cfg[3], lds=abs(cfg[4]), pk=cfg[4] < 0)
+
+
+def _nhwc(who, t, dtype):
+    """The checks of one NHWC tensor of a single-kernel hook; -> (B, H, W, ld)."""
+    want = torch.float16 if DTYPES[dtype] == _lib.VTI_F16 else torch.float32        # h2: 4-byte pairs, carried as f32 bits
+    if t.dim() != 4 or t.dtype != want or not t.is_contiguous():
+        raise ValueError(f"{who}: expected a contiguous {want} NHWC tensor, got {t.dtype} {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def _check_debug(rc):
+    if rc != 0:
+        raise _lib.VtiError(rc, lib().vti_last_error(None).decode())
+
+
+def debug_sppf_pool(x, c, dtype="fp16", in_coff=0, out=None, out_coff=None):
+    """Run the SPPF's three chained 5x5 max-pools alone (vti_debug_sppf_pool): channels [in_coff, in_coff + c) of x (NHWC
+    [B,H,W,ld] of the engine dtype; h2 as float32-typed bits) -> channels [out_coff, out_coff + 3 c) of `out` (default: x itself at
+    out_coff = in_coff + c, the engine's layout).  Enqueued on the current stream.  -> (out, path): path 0 = the global-memory
+    kernel, 1 / 4 = the LDS kernel with one / four 16-byte pieces per lane group."""
+    B, H, W, ld = _nhwc("debug_sppf_pool", x, dtype)
+    if out is None:
+        out = x
+    if tuple(out.shape) != (B, H, W, ld) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("debug_sppf_pool: out must have x's shape, dtype and layout")
+    if out_coff is None:
+        out_coff = in_coff + c
+    path = C.c_int32(-1)
+    _check_debug(lib().vti_debug_sppf_pool(DTYPES[dtype], _ptr(x), _ptr(out), B, H, W, c, ld, in_coff, out_coff, C.byref(path), _stream()))
+    return out, path.value
+
+
+def debug_upsample2x(x, c, out, dtype="fp16", in_coff=0, out_coff=0):
+    """Run the nearest 2x upsample alone (vti_debug_upsample2x): channels [in_coff, in_coff + c) of x (NHWC [B,H,W,in_ld]) ->
+    channels [out_coff, out_coff + c) of out (NHWC [B,2H,2W,out_ld], same dtype).  Enqueued on the current stream.  -> out."""
+    B, H, W, in_ld = _nhwc("debug_upsample2x", x, dtype)
+    Bo, Ho, Wo, out_ld = _nhwc("debug_upsample2x", out, dtype)
+    if (Bo, Ho, Wo) != (B, 2 * H, 2 * W):
+        raise ValueError(f"debug_upsample2x: out must be [{B},{2 * H},{2 * W},out_ld], got {tuple(out.shape)}")
+    _check_debug(lib().vti_debug_upsample2x(DTYPES[dtype], _ptr(x), _ptr(out), B, H, W, c, in_ld, in_coff, out_ld, out_coff, _stream()))
+    return out
+
+
+def debug_decode(box, cls, mc, levels, strides, nc, nm, pred, box_only=False):
+    """Run the Detect/Segment decode alone (vti_debug_decode).  box / cls / mc: three contiguous f32 device tensors each, level l
+    of shape [B, H_l * W_l, 64 | nc | nm]; levels: three (H_l, W_l); pred: f32 [B, A, 4 + nc + nm], A = sum H_l W_l.  box_only: the
+    box-only kernel, which writes pred[..., :4] and nothing else (cls and mc may be None).  Enqueued on the current stream.  -> pred."""
+    def table(ts, width):
+        if ts is None:
+            return None
+        for t, (h, w) in zip(ts, levels):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, h * w, width):
+                raise ValueError(f"debug_decode: expected contiguous float32 [{B},{h * w},{width}], got {t.dtype} {tuple(t.shape)}")
+        return (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    B = pred.shape[0]
+    A = sum(h * w for h, w in levels)
+    if len(levels) != 3 or pred.dtype != torch.float32 or not pred.is_contiguous() or tuple(pred.shape) != (B, A, 4 + nc + nm):
+        raise ValueError(f"debug_decode: pred must be contiguous float32 [B,{A},{4 + nc + nm}], got {pred.dtype} {tuple(pred.shape)}")
+    hs, ws, st = ((C.c_int32 * 3)(*v) for v in ([h for h, _ in levels], [w for _, w in levels], list(strides)))
+    _check_debug(lib().vti_debug_decode(int(bool(box_only)), table(box, 64), table(cls, nc), table(mc, nm), hs, ws, st, B, nc, nm, _ptr(pred), _stream()))
+    return pred
