@@ -1113,7 +1113,7 @@ int32_t vti_debug_conv2d(int32_t dtype, const void* dev_in, int32_t B, int32_t H
                          float* ms_out, int32_t* cfg_out, void* stream);
 
 /* ---- the forward pass's non-GEMM kernels, one at a time (kernel unit tests) --------- */
-/* Marks the three single-kernel test hooks; libvti.so exports them as it does every other. */
+/* Marks the single-kernel and single-op test hooks; libvti.so exports them as it does every other. */
 #define VTI_DEBUG_OPS_API
 /* Like vti_debug_conv2d these take no context and no weights; unlike it they only enqueue their one launch on `stream`.  Every
  * refusal below is VTI_ERR_ARG with a message in vti_last_error(NULL), made on the host before anything is launched.  T is the
@@ -1144,6 +1144,27 @@ VTI_DEBUG_OPS_API int32_t vti_debug_upsample2x(int32_t dtype, const void* dev_in
 VTI_DEBUG_OPS_API int32_t vti_debug_decode(int32_t box_only, const float* const* dev_box, const float* const* dev_cls, const float* const* dev_mc,
                          const int32_t* H, const int32_t* W, const int32_t* stride, int32_t B, int32_t nc, int32_t nm,
                          float* dev_pred, void* stream);
+
+/* ---- one op of the plan alone, on operands the caller wrote (kernel unit tests of the fused convs) --------- */
+/* vti_debug_set_conv_output: the inverse of vti_debug_conv_output.  Writes dev_nchw, f32 NCHW [B,c2,h_out,w_out], into the view
+ * conv `i`'s output has in the engine's storage, with the storage's own encode: round-to-nearest fp16, the saturating h2 pair
+ * the conv epilogues write, or plain f32.  Only channels [coff, coff + C) of the buffer are touched.  Refused exactly as the
+ * reader refuses: B out of range (VTI_ERR_ARG), no weights / no workspace (VTI_ERR_STATE), `i` out of range or a null pointer
+ * (VTI_ERR_ARG), a conv whose output is never materialised (VTI_ERR_UNSUPPORTED), a view in a caller tensor that no forward or
+ * vti_debug_run_op has named yet (VTI_ERR_STATE).  One copy kernel on `stream`. */
+VTI_DEBUG_OPS_API int32_t vti_debug_set_conv_output(vti_ctx* ctx, int32_t i, int32_t B, const float* dev_nchw, void* stream);
+/* vti_debug_run_op: issues, once and on `stream`, the launch of the ONE op of the plan that computes conv `i` -- whichever role
+ * `i` has in it: the op's own conv, a 1x1 fused into its epilogue, the second 3x3 of a Bottleneck pair, the C2f's closing 1x1 in
+ * the pair's tail, the 3x3 a ConvTranspose is folded into, or layer 1 of the stem kernel.  The launch record is the one
+ * vti_forward builds for that op (same code); no fork / join events, no side streams.  The op reads whatever its input views
+ * hold (vti_debug_set_conv_output) and writes its own outputs, which vti_debug_conv_output then reads.  out_convs (4 ints, may be
+ * NULL) receives the conv indices the op computes, in execution order, the rest -1.  dev_input (u8 [B,H,W,3]) is read by the
+ * stem op only, dev_pred / dev_best ([B,A,4+nc+nm] / [B,A,2] f32) are written by the towers that scatter into pred (dev_best
+ * may be NULL: no pairs), dev_proto by the op that computes proto.cv3; each may be NULL for every other op.  VTI_ERR_ARG with a
+ * message naming the argument: `i` or `B` (1..max_batch) out of range, dev_input NULL for the stem, dev_pred NULL for an op that
+ * writes pred, dev_proto NULL for the op that writes proto; then vti_forward's state errors (no weights, no workspace). */
+VTI_DEBUG_OPS_API int32_t vti_debug_run_op(vti_ctx* ctx, int32_t i, const uint8_t* dev_input, int32_t B, int32_t swap_rb, float* dev_pred,
+                         void* dev_proto, float* dev_best, int32_t* out_convs, void* stream);
 
 #ifdef __cplusplus
 }

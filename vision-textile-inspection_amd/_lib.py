@@ -210,6 +210,8 @@ SIGNATURES = {
     "vti_debug_sppf_pool": (_I32, [_I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "vti_debug_upsample2x": (_I32, [_I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vti_debug_decode": (_I32, [_I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "vti_debug_set_conv_output": (_I32, [_P, _I32, _I32, _P, _P]),
+    "vti_debug_run_op": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 // measurement.py:208-210.  All are HBM/L2-bound streaming kernels: 16 B per lane, coalesced
 // along the NHWC channel axis.
 #include "vti_internal.h"
+#include "conv_dev.h"      // h2_enc: the debug writer stores what the conv epilogues store
 
 namespace vti {
 
@@ -378,6 +379,34 @@ hipError_t launch_debug_nchw(int elem_is_f32, const void* src, int B, int H, int
     if (elem_is_f32 == 2) hipLaunchKernelGGL(debug_nchw_kernel<h2e>, dim3(grid), dim3(256), 0, st, (const h2e*)src, B, H, W, C, ld, coff, dst);
     else if (elem_is_f32) hipLaunchKernelGGL(debug_nchw_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)src, B, H, W, C, ld, coff, dst);
     else hipLaunchKernelGGL(debug_nchw_kernel<half_t>, dim3(grid), dim3(256), 0, st, (const half_t*)src, B, H, W, C, ld, coff, dst);
+    return hipGetLastError();
+}
+
+// ---- test hook, the inverse: f32 NCHW -> NHWC channel slice, with the storage's own encode (fp16: round to nearest even; h2: the
+// saturating pair of the conv epilogues, conv_dev.h's h2_enc; f32: a copy).  Channels outside [coff, coff + C) are not touched.
+template <typename T>
+__global__ void debug_set_nchw_kernel(const float* src, int B, int H, int W, int C, int ld, int coff, T* dst) {
+    const long total = (long)B * C * H * W;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int x = (int)(i % W);
+        long r = i / W;
+        const int y = (int)(r % H); r /= H;
+        const int c = (int)(r % C);
+        const int b = (int)(r / C);
+        const size_t o = ((size_t)(b * H + y) * W + x) * ld + coff + c;
+        if constexpr (sizeof(T) == 4 && !__is_same(T, float)) dst[o].u = h2_enc(src[i]);
+        else dst[o] = (T)src[i];
+    }
+}
+
+hipError_t launch_debug_set_nchw(int elem_is_f32, const float* src, int B, int H, int W, int C, int ld, int coff,
+                                 void* dst, hipStream_t st) {
+    const long total = (long)B * C * H * W;
+    if (total == 0) return hipSuccess;
+    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    if (elem_is_f32 == 2) hipLaunchKernelGGL(debug_set_nchw_kernel<h2e>, dim3(grid), dim3(256), 0, st, src, B, H, W, C, ld, coff, (h2e*)dst);
+    else if (elem_is_f32) hipLaunchKernelGGL(debug_set_nchw_kernel<float>, dim3(grid), dim3(256), 0, st, src, B, H, W, C, ld, coff, (float*)dst);
+    else hipLaunchKernelGGL(debug_set_nchw_kernel<half_t>, dim3(grid), dim3(256), 0, st, src, B, H, W, C, ld, coff, (half_t*)dst);
     return hipGetLastError();
 }
 

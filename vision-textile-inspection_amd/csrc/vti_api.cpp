@@ -695,6 +695,17 @@ static const char* launch_what(const LaunchRec& L) {
     }
 }
 
+// One op of the plan (no OP_FORK / OP_JOIN) on a stream: its launch record into L, then the launch.  The body of vti_forward's
+// loop, and all that vti_debug_run_op launches.
+static int32_t run_op(vti_ctx* c, const Op& op, int32_t B, int32_t swap_rb, const Bindings& bind, hipStream_t st, LaunchRec& L) {
+    const Plan& P = c->plan;
+    const RunOptions& run = c->opt.run;
+    if (const char* e = fill_launch(P, op, B, swap_rb, run, bind, L)) return fail(c, VTI_ERR_UNSUPPORTED, e);
+    const bool stamp = L.name && run.stamp_op == L.name;        // diagnostic build only
+    VTI_HIP(c, issue(L, st, stamp ? ("[stamps] op " + op_label(P, op)).c_str() : nullptr), launch_what(L));
+    return VTI_OK;
+}
+
 static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t swap_rb, float* pred, void* proto, float* best, void* stream);
 
 int32_t vti_forward(vti_ctx* c, const uint8_t* input, int32_t B, int32_t swap_rb, float* pred, void* proto, void* stream) {
@@ -731,10 +742,7 @@ static int32_t forward_impl(vti_ctx* c, const uint8_t* input, int32_t B, int32_t
             VTI_HIP(c, hipStreamWaitEvent(fork ? c->side[op.lane] : main_st, ev, 0), fork ? "fork wait" : "join wait");
             continue;
         }
-        if (const char* e = fill_launch(P, op, B, swap_rb, run, bind, L)) return fail(c, VTI_ERR_UNSUPPORTED, e);
-        const bool stamp = L.name && run.stamp_op == L.name;        // diagnostic build only
-        VTI_HIP(c, issue(L, (c->multi_stream && op.lane > 0) ? c->side[op.lane] : main_st, stamp ? ("[stamps] op " + op_label(P, op)).c_str() : nullptr),
-                launch_what(L));
+        VTI_TRY(run_op(c, op, B, swap_rb, bind, (c->multi_stream && op.lane > 0) ? c->side[op.lane] : main_st, L));
     }
     // a plan whose class towers do not write pred themselves (VTI_NO_SCATTER ...) derives the pairs from the finished rows
     if (best && !P.pred_scatter)
@@ -2231,18 +2239,67 @@ int32_t vti_convert_raw_frames(vti_ctx* c, const uint8_t* raw_buf, int64_t raw_b
     return VTI_OK;
 }
 
-int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void* stream) {
-    int32_t rc = check_ready(c, B, "vti_debug_conv_output");
+// Where conv i's output lives, for vti_debug_conv_output and its inverse (one set of refusals): the view, its storage
+// (elem: 1 f32, 2 h2 pairs, 0 fp16) and the buffer's address.
+static int32_t conv_output_view(vti_ctx* c, const char* fn, int32_t i, int32_t B, const void* user, const View*& v, int& elem, void*& ptr) {
+    int32_t rc = check_ready(c, B, fn);
     if (rc) return rc;
-    if (i < 0 || i >= (int32_t)c->plan.convs.size() || !out) return fail(c, VTI_ERR_ARG, "vti_debug_conv_output: bad argument");
-    const View& v = c->plan.conv_out[i];
-    if (v.buf < 0) return fail(c, VTI_ERR_UNSUPPORTED, "vti_debug_conv_output: this conv is fused into the next one; its output is never materialised");
-    const Buf& b = c->plan.bufs[v.buf];
-    const void* src = buf_ptr(c->plan, bindings_of(c, c->last_input, nullptr, c->last_proto, nullptr), v.buf);
-    if (!src) return fail(c, VTI_ERR_STATE, "vti_debug_conv_output: run vti_forward first");
-    const int is_f32 = (b.elem == EL_F32 || (b.elem == EL_T && c->plan.desc.dtype == VTI_F32)) ? 1
-                       : (b.elem == EL_T && c->plan.desc.dtype == VTI_H2) ? 2 : 0;      // 2: h2 pairs
-    VTI_HIP(c, launch_debug_nchw(is_f32, src, B, b.H, b.W, v.C, b.C, v.coff, out, (hipStream_t)stream), "debug copy");
+    if (i < 0 || i >= (int32_t)c->plan.convs.size() || !user) return refuse(c, fn, "bad argument");
+    v = &c->plan.conv_out[i];
+    if (v->buf < 0) return refuse(c, fn, "this conv is fused into the next one; its output is never materialised", VTI_ERR_UNSUPPORTED);
+    const Buf& b = c->plan.bufs[v->buf];
+    ptr = buf_ptr(c->plan, bindings_of(c, c->last_input, nullptr, c->last_proto, nullptr), v->buf);
+    if (!ptr) return refuse(c, fn, "run vti_forward first", VTI_ERR_STATE);
+    elem = (b.elem == EL_F32 || (b.elem == EL_T && c->plan.desc.dtype == VTI_F32)) ? 1
+           : (b.elem == EL_T && c->plan.desc.dtype == VTI_H2) ? 2 : 0;      // 2: h2 pairs
+    return VTI_OK;
+}
+
+int32_t vti_debug_conv_output(vti_ctx* c, int32_t i, int32_t B, float* out, void* stream) {
+    const View* v; int elem; void* src;
+    VTI_TRY(conv_output_view(c, "vti_debug_conv_output", i, B, out, v, elem, src));
+    const Buf& b = c->plan.bufs[v->buf];
+    VTI_HIP(c, launch_debug_nchw(elem, src, B, b.H, b.W, v->C, b.C, v->coff, out, (hipStream_t)stream), "debug copy");
+    return VTI_OK;
+}
+
+int32_t vti_debug_set_conv_output(vti_ctx* c, int32_t i, int32_t B, const float* in, void* stream) {
+    const View* v; int elem; void* dst;
+    VTI_TRY(conv_output_view(c, "vti_debug_set_conv_output", i, B, in, v, elem, dst));
+    const Buf& b = c->plan.bufs[v->buf];
+    VTI_HIP(c, launch_debug_set_nchw(elem, in, B, b.H, b.W, v->C, b.C, v->coff, dst, (hipStream_t)stream), "debug copy");
+    return VTI_OK;
+}
+
+int32_t vti_debug_run_op(vti_ctx* c, int32_t i, const uint8_t* input, int32_t B, int32_t swap_rb, float* pred, void* proto, float* best,
+                         int32_t* out_convs, void* stream) {
+    const char* fn = "vti_debug_run_op";
+    if (!c) return VTI_ERR_ARG;
+    const Plan& P = c->plan;
+    if (i < 0 || i >= (int32_t)P.convs.size()) return refuse(c, fn, "i out of range (0..vti_num_convs - 1)");
+    if (B < 1 || B > P.desc.max_batch) return refuse(c, fn, "B out of range (1..max_batch)");
+    const Op* op = nullptr;
+    for (const Op& o : P.ops)
+        if ((o.kind == OP_CONV || o.kind == OP_CONV0) && (o.conv == i || o.fused == i || o.pair == i || o.tail == i || o.fold == i || o.fused_l1 == i))
+            op = &o;
+    if (!op) return refuse(c, fn, "no op of the plan computes this conv", VTI_ERR_UNSUPPORTED);
+    // the convs of the op in execution order
+    const int32_t order[4] = {op->fold >= 0 ? op->fold : op->conv, op->fold >= 0 ? op->conv : op->fused_l1 >= 0 ? op->fused_l1 : op->pair,
+                              op->tail, op->fused};
+    if (out_convs) {
+        int n = 0;
+        for (int k = 0; k < 4; ++k) out_convs[k] = -1;
+        for (int k = 0; k < 4; ++k) if (order[k] >= 0) out_convs[n++] = order[k];
+    }
+    auto writes = [&](const View& v) { return v.buf >= 0 && v.buf == P.proto_buf_c; };
+    if (op->kind == OP_CONV0 && !input) return refuse(c, fn, "dev_input is null and the op is the stem");
+    if (op->pred_mode && !pred) return refuse(c, fn, "dev_pred is null and the op writes pred");
+    if ((writes(op->out) || writes(op->out2)) && !proto) return refuse(c, fn, "dev_proto is null and the op writes proto");
+    VTI_TRY(check_ready(c, B, fn));
+    LaunchRec L;
+    VTI_TRY(run_op(c, *op, B, swap_rb, bindings_of(c, input, pred, proto, best), (hipStream_t)stream, L));
+    if (input) c->last_input = input;      // vti_debug_conv_output reads what the op wrote
+    if (proto) c->last_proto = proto;
     return VTI_OK;
 }
 

@@ -306,6 +306,8 @@ void conv_geometry(const Plan& P, int i, vti_conv_info* o);         // vti_conv_
 
 hipError_t launch_debug_nchw(int elem_is_f32, const void* src, int B, int H, int W, int C, int ld, int coff,
                              float* dst, hipStream_t st);
+hipError_t launch_debug_set_nchw(int elem_is_f32, const float* src, int B, int H, int W, int C, int ld, int coff,
+                                 void* dst, hipStream_t st);      // the inverse, encoding as the storage does
 
 // One frame of a batch whose frames differ in size (vti_pack_frames): what the kernels would otherwise recompute per pixel or per
 // box for the ctx's H x W canvas.  A frame table is a FrameTableHeader followed by B rows; vti_letterbox / vti_scale_boxes pass one

@@ -1580,6 +1580,26 @@ class Engine:
         check(self._ctx, lib().vti_debug_conv_output(self._ctx, i, B, _ptr(out), _stream()))
         return out
 
+    def debug_set_conv_output(self, i, values):
+        """The inverse of debug_conv_output (vti_debug_set_conv_output): values, f32 [B,c2,h_out,w_out] on the device, into conv
+        i's output view, encoded as the engine's storage encodes (fp16 rounding, the saturating h2 pair, or f32)."""
+        t = self.conv_table()[i]
+        if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous() or \
+                tuple(values.shape[1:]) != (t["c2"], t["h_out"], t["w_out"]):
+            raise ValueError(f"debug_set_conv_output: expected contiguous float32 [B,{t['c2']},{t['h_out']},{t['w_out']}] on the device, "
+                             f"got {values.dtype} {tuple(values.shape)}")
+        check(self._ctx, lib().vti_debug_set_conv_output(self._ctx, i, values.shape[0], _ptr(values), _stream()))
+
+    def debug_run_op(self, i, B, x=None, swap_rb=False, pred=None, proto=None, best=None):
+        """Launch the ONE op of the plan that computes conv i (vti_debug_run_op), once, on the current stream: it reads what its
+        input views hold (debug_set_conv_output; x, u8 [B,H,W,3], for the stem) and writes its outputs (debug_conv_output reads
+        them; pred f32 [B,A,4+nc+nm], best f32 [B,A,2] and proto for the ops that write those).  -> the conv indices the op
+        computes, in execution order."""
+        convs = (C.c_int32 * 4)()
+        check(self._ctx, lib().vti_debug_run_op(self._ctx, i, _ptr(x), B, int(bool(swap_rb)), _ptr(pred), _ptr(proto), _ptr(best),
+                                                convs, _stream()))
+        return [v for v in convs if v >= 0]
+
     def _check_input(self, t, hw):
         if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or tuple(t.shape[1:3]) != tuple(hw):
             raise ValueError(f"expected uint8 [B,{hw[0]},{hw[1]},3], got {t.dtype} {tuple(t.shape)}")
