@@ -547,6 +547,11 @@ __global__ __launch_bounds__(256) void stem_kernel(const ConvParams p) {
 //   phase 4  the shared epilogue (bias, SiLU, NHWC stores) on layer 1's 8 x 40 output tile -- or, when the plan fused the 1x1
 //            conv that is layer 1's only consumer (model.2.cv1), that conv on layer 1's register tile (conv_stage2): then
 //            layer 1's tensor does not reach HBM either and only the third conv's output is stored
+// Waves (NT / 64 of them; the tile, the LDS image, the packed weights and the grid are the same for both counts): patch rows in
+// phase 1 and 16-window blocks in phase 2 go round the waves; the tile's 20 m-tiles of 16 layer-1 pixels are five per SIMD --
+// 4 waves: wave w owns 5 w .. 5 w + 4; 8 waves: w, w + 8 and, for w < 4, w + 16 (a SIMD hosts waves w and w + 4).  A wave holds
+// both n-tiles of its pixels, so phase 4 works on its register tile whichever m-tiles those are.  Every output element is
+// computed by the same instruction sequence under both counts: the results are bit-identical.
 // ConvParams roles: in = u8 frames [B, Hin, Win, 3]; wpk / bias / out / Cout / Hout / Wout describe LAYER 1;
 // w0 / bias0 = the stem's packed weights / bias; w2 / bias2 / out2 (non-null) = the fused third conv.
 constexpr int SL_TH = 8, SL_TW = 40;       // 35 patch rows of 489 B: the u8 reads are DRAM-bound on segment length (20-wide tiles: 252 B, 2x slower staging)
@@ -567,9 +572,28 @@ size_t stem_l1_lds_bytes(int dtype) {
     return (((size_t)SL_RH * sl_pitch((int)pes) * pes + 15) & ~(size_t)15) + (size_t)SL_NSP * 16 * es;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(const ConvParams p) {     // fp16: the LDS image fits twice per CU -> <= 256 registers
+// Threads per workgroup.  fp16: 256, two workgroups per CU (the LDS image fits twice).  h2: the image fits once, so the second wave of
+// every SIMD comes from the SAME workgroup: 512 threads on the unchanged 8 x 40 tile, LDS image and grid.  fp32 (the parity engine)
+// keeps one 4-wave workgroup per CU.  -DVTI_STEM_NT_H2=256 builds the 4-wave h2 form (make variant VSRC=conv), the A/B arm.
+#ifndef VTI_STEM_NT_H2
+#define VTI_STEM_NT_H2 512
+#endif
+static_assert(VTI_STEM_NT_H2 == 256 || VTI_STEM_NT_H2 == 512, "stem_l1_kernel runs 4 or 8 waves");
+template <typename T> constexpr int stem_l1_nt() { return Tr<T>::H2 ? VTI_STEM_NT_H2 : 256; }
+
+// Occupancy: two waves per SIMD for fp16 (two 4-wave workgroups) and for h2 (one 8-wave workgroup), so both must fit 256 registers
+// (VGPRs + AGPRs); the 4-wave forms of fp32 and h2 have the SIMD's 512 to themselves.
+template <typename T, int NT>
+__global__ __launch_bounds__(NT, NT == 256 && sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(const ConvParams p) {
     using vec = typename Tr<T>::vec;
+    constexpr int NW = NT / 64;                         // waves
+    // 8 waves: a phase fetches its weight fragments once the previous phase's are dead (wA under the staging; w1all and the fused
+    // conv's after phase 2's last MFMA).  All three sets live together are 200 registers: right for one wave per SIMD, too many for two
+    constexpr bool LATE = NW == 8;
+    // ... and layer 1's fragments are not held all at once either (72 registers): a ring of W1D K steps, refilled W1D steps ahead
+    // of its use inside phase 3 (L2 hits; with all of them resident the kernel compiled to 256 registers + 65 spilled)
+    constexpr bool LATE_W1 = LATE;
+    constexpr int W1D = 3;
     constexpr int ES = (int)sizeof(T);
     // the patch's element type: T, except h2 -> plain fp16 holding the bytes' integer values (the stem's weights are w / 255 as hi / lo planes)
     constexpr bool XH = Tr<T>::H2;
@@ -601,9 +625,9 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
     VTI_STAMP(0);
     // ---- phase 1: u8 -> T(v / 255) while staging.  fp16: v * (1/255) rounds to the same half as v / 255 for all 256 byte
     // values (checked exhaustively), so no table and no division; fp32 divides (what torch's `im.float() / 255` does).
-    // wave w stages rows w, w+4, ...; a row is SL_RWD dwords = RC lane-chunks: all row arithmetic is scalar, the column test
+    // wave w stages rows w, w+NW, ...; a row is SL_RWD dwords = RC lane-chunks: all row arithmetic is scalar, the column test
     // is done once per chunk, and every load of the wave is issued (branch-free) before the first one is consumed
-    constexpr int RC = (SL_RWD + 63) / 64, NR = (SL_RH + 3) / 4;
+    constexpr int RC = (SL_RWD + 63) / 64, NR = (SL_RH + NW - 1) / NW;
     unsigned vv[NR][RC];
     const bool aligned = (rowbytes & 3) == 0;
     // straight-line code: every load is unconditional (clamped address) and NOTHING consumes a result here -- a select or a branch
@@ -616,7 +640,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
         const uint8_t* inb_ = (const uint8_t*)p.in + (size_t)b_ * p.Hin * p.Win * 3;
 #pragma unroll
         for (int it = 0; it < NR; ++it) {
-            const int ry = wave + 4 * it;
+            const int ry = wave + NW * it;
             const int y = iy0_ + ry;
             const bool row_ok = ry < SL_RH && (unsigned)y < (unsigned)p.Hin;
 #pragma unroll
@@ -638,9 +662,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
     const uint8_t* inb = (const uint8_t*)p.in + (size_t)b * p.Hin * p.Win * 3;
     // (per tile, not per workgroup: kept across the tile loop these ~190 registers push the kernel to one wave per SIMD for fp16 and into
     // scratch for h2; re-fetched they are L2 hits whose latency hides under the patch conversion)
-    // Every weight fragment of the three convs is fetched NOW (fp16: 48 + 40 + 8 registers), so that the round trips hide under the
-    // patch staging: loaded where they are used, each phase opened with an exposed L2 latency (the stem phase alone spent ~6 k of
-    // its 12 k cycles per workgroup waiting for its 12 fragments).
+    // 4 waves: every weight fragment of the three convs is fetched NOW (fp16: 48 + 40 + 8 registers), so that the round trips hide
+    // under the patch staging: loaded where they are used, each phase opened with an exposed L2 latency (the stem phase alone spent
+    // ~6 k of its 12 k cycles per workgroup waiting for its 12 fragments).  8 waves (LATE): only the stem's here; layer 1's and the
+    // fused conv's follow phase 2 (load_w1, load_s2), where the SIMD's other wave covers their round trip.
     // the pointers are laundered through an empty asm each iteration so that the loop-invariant loads are NOT hoisted out of the tile loop
     const void* w0p = p.w0;
     const void* w1p = p.wpk;
@@ -656,18 +681,30 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
                 for (int c = 0; c < NCH * NWP; ++c) wA[pp][kh][c] = w0[(size_t)((pp * 3 + kh) * NCH * NWP + c) * 64 + lane];
     }
     vec w1all[NS1][2];
-#pragma unroll
-    for (int s1 = 0; s1 < NS1; ++s1)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) w1all[s1][n] = ((const vec*)w1p)[((size_t)s1 * 2 + n) * 64 + lane];
-    const f32x4 bias0_4 = *(const f32x4*)(p.bias0 + g * 4);
     Stage2Regs<T, 2, 2> s2r;
-    if (p.out2) stage2_preload<T, 2, 2>(p, lane, false, s2r);
+    auto load_w1 = [&]() {
+#pragma unroll
+        for (int s1 = 0; s1 < NS1; ++s1)
+#pragma unroll
+            for (int n = 0; n < 2; ++n) w1all[s1][n] = ((const vec*)w1p)[((size_t)s1 * 2 + n) * 64 + lane];
+    };
+    [[maybe_unused]] vec w1q[W1D][2];
+    // (buffer loads: the laundered pointer has lost its address space, and a flat load would tie these to the LDS counter)
+    auto ldw1 = [&](int s1, int n) {
+        const __amdgpu_buffer_rsrc_t rsW1 = __builtin_amdgcn_make_buffer_rsrc((void*)w1p, 0, NS1 * 2 * 1024, 0x00020000);
+        return buf_load16<vec>(rsW1, (unsigned)(lane * 16), (unsigned)((s1 * 2 + n) * 1024));
+    };
+    auto load_s2 = [&]() {
+        if (p.out2) stage2_preload<T, 2, 2>(p, lane, false, s2r);
+    };
+    if constexpr (!LATE) load_w1();
+    const f32x4 bias0_4 = *(const f32x4*)(p.bias0 + g * 4);
+    if constexpr (!LATE) load_s2();
     {
         if (aligned) {
 #pragma unroll
             for (int it = 0; it < NR; ++it) {
-                const int ry = wave + 4 * it;
+                const int ry = wave + NW * it;
                 const int y = iy0 + ry;
                 const bool row_ok = ry < SL_RH && (unsigned)y < (unsigned)p.Hin;
 #pragma unroll
@@ -681,7 +718,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
         } else {                    // ragged width (tests only): assemble byte by byte
 #pragma unroll
             for (int it = 0; it < NR; ++it) {
-                const int ry = wave + 4 * it;
+                const int ry = wave + NW * it;
                 const int y = iy0 + ry;
                 const bool row_ok = ry < SL_RH && (unsigned)y < (unsigned)p.Hin;
 #pragma unroll
@@ -700,7 +737,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
         }
 #pragma unroll
         for (int it = 0; it < NR; ++it) {
-            const int ry = wave + 4 * it;
+            const int ry = wave + NW * it;
 #pragma unroll
             for (int ch = 0; ch < RC; ++ch) {
                 const int rd = lane + 64 * ch;
@@ -725,7 +762,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
         }
     }
     // elements [4 SL_RWD, SL_PITCH) of every row: read by the last stem window of the row, must be finite (zero weights meet them)
-    for (int i = tid; i < SL_RH * ((SL_PITCH - 4 * SL_RWD) / 4); i += 256) {
+    for (int i = tid; i < SL_RH * ((SL_PITCH - 4 * SL_RWD) / 4); i += NT) {
         const int ry = i / ((SL_PITCH - 4 * SL_RWD) / 4), c4 = i - ry * ((SL_PITCH - 4 * SL_RWD) / 4);
         PT* o = cp + (size_t)ry * SL_PITCH + 4 * SL_RWD + 4 * c4;
         o[0] = to_T<PT>(0.f); o[1] = to_T<PT>(0.f); o[2] = to_T<PT>(0.f); o[3] = to_T<PT>(0.f);
@@ -743,7 +780,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
     {
         const f32x4 bias4 = bias0_4;
         constexpr int NBLK = (SL_NWIN + 15) / 16;
-        for (int blk = wave; blk < NBLK; blk += 4) {
+        for (int blk = wave; blk < NBLK; blk += NW) {
             const int wi = blk * 16 + (lane & 15);
             const bool wvalid = wi < SL_NWIN;
             const int wc = wvalid ? wi : SL_NWIN - 1;
@@ -787,32 +824,55 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
             }
         }
     }
+    if constexpr (LATE) {           // wA is dead: layer 1's and the fused conv's fragments, in flight across the barrier
+        asm volatile("" : "+s"(w1p));
+        if constexpr (LATE_W1) {
+#pragma unroll
+            for (int s1 = 0; s1 < W1D; ++s1)
+#pragma unroll
+                for (int n = 0; n < 2; ++n) w1q[s1][n] = ldw1(s1, n);
+        } else load_w1();
+        load_s2();
+    }
     __syncthreads();
     VTI_STAMP(2);
+    // ---- phases 3 and 4 on MR of the tile's 20 m-tiles of 16 pixels.  4 waves: wave w owns m-tiles 5 w .. 5 w + 4.  8 waves: wave w
+    // owns w, w + 8 and (w < 4) w + 16, so the SIMD of waves w and w + 4 still carries five; the missing third m-tile of waves 4-7 is
+    // not computed and masked but absent from their code (MR = 2 behind a wave-uniform branch)
+    auto phase34 = [&](auto mr) {
+    constexpr int MR = decltype(mr)::value;
     // ---- phase 3: layer 1 from the LDS tile
-    int opy[MREP], opx[MREP], sbase[MREP];
-    bool pvalid[MREP];
+    int opy[MR], opx[MR], sbase[MR];
+    bool pvalid[MR];
 #pragma unroll
-    for (int m = 0; m < MREP; ++m) {
-        const int pp = (wave * MREP + m) * 16 + (lane & 15);           // < 320 = TH * TW
+    for (int m = 0; m < MR; ++m) {
+        const int pp = (NW == 8 ? wave + 8 * m : wave * MR + m) * 16 + (lane & 15);           // < 320 = TH * TW
         const int py = pp / SL_TW, px = pp - py * SL_TW;
         opy[m] = oy0 + py; opx[m] = ox0 + px;
         pvalid[m] = opy[m] < p.Hout && opx[m] < p.Wout;
         sbase[m] = ((2 * py) * SL_SW + 2 * px) * 16 * ES;
     }
-    f32x4 acc[MREP][2];
+    f32x4 acc[MR][2];
 #pragma unroll
-    for (int m = 0; m < MREP; ++m) { acc[m][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[m][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+    for (int m = 0; m < MR; ++m) { acc[m][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[m][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
     for (int s = 0; s < NS1; ++s) {
         const int tap = sizeof(T) == 2 ? 2 * s + (g >> 1) : s;
         const int tc = tap < 9 ? tap : 8;                               // the 10th half-step multiplies by zero weights
         const int toff = ((tc / 3) * SL_SW + (tc % 3)) * 16 * ES + (sizeof(T) == 2 ? (g & 1) * 8 : g * 4) * ES;
         vec w1[2];
+        // the ring's loads and the hi / lo unpacking of a fragment stay in their own K step (MFMAs, LDS reads and scalar code may
+        // cross): unfenced, the unpacking is hoisted to right behind its load and every step opens with a wait for a load just issued
+        if constexpr (LATE_W1) __builtin_amdgcn_sched_barrier(0x10c);
 #pragma unroll
-        for (int n = 0; n < 2; ++n) w1[n] = w1all[s][n];
+        for (int n = 0; n < 2; ++n) {
+            if constexpr (LATE_W1) {
+                w1[n] = w1q[s % W1D][n];
+                if (s + W1D < NS1) w1q[s % W1D][n] = ldw1(s + W1D, n);
+            } else w1[n] = w1all[s][n];
+        }
 #pragma unroll
-        for (int m = 0; m < MREP; ++m) {
+        for (int m = 0; m < MR; ++m) {
             const vec x = *(const vec*)(sout + sbase[m] + toff);
 #pragma unroll
             for (int n = 0; n < 2; ++n) acc[m][n] = mma(w1[n], x, acc[m][n]);
@@ -820,15 +880,25 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void stem_l1_kernel(co
     }
     VTI_STAMP(3);
     // ---- phase 4: layer 1's epilogue, or (model.2.cv1 fused) the 1x1 conv on layer 1's register tile
-    if (p.out2) conv_stage2<T, 2, 2, false, true>(p, acc, pvalid, opy, opx, b, lane, &s2r);
-    else conv_epilogue<T, 2>(p, acc, pvalid, opy, opx, b, 0, 0, lane);
+    if (p.out2) conv_stage2<T, 2, 2, false, true, MR>(p, acc, pvalid, opy, opx, b, lane, &s2r);
+    else conv_epilogue<T, 2, MR>(p, acc, pvalid, opy, opx, b, 0, 0, lane);
+    };
+    if constexpr (NW == 8) {
+        static_assert(NW != 8 || SL_TH * SL_TW == 20 * 16, "8 waves: 3 + 2 m-tiles per SIMD");
+        if (__builtin_amdgcn_readfirstlane(wave) < 4) phase34(std::integral_constant<int, 3>{});
+        else phase34(std::integral_constant<int, 2>{});
+    } else {
+        static_assert(SL_TH * SL_TW == NW * MREP * 16, "4 waves: MREP m-tiles each");
+        phase34(std::integral_constant<int, MREP>{});
+    }
     VTI_STAMP(12);
     }       // tiles of this workgroup
 }
 
 void stem_l1_tile(int* th, int* tw) { *th = SL_TH; *tw = SL_TW; }
 
-// persistent grid: as many workgroups as fit the chip at once (one per CU; two where the LDS image fits twice: fp16)
+// persistent grid: as many workgroups as fit the chip at once (one per CU; two where the LDS image fits twice: fp16), whatever
+// their thread count (stem_l1_nt)
 int stem_l1_grid(int dtype, int ntiles, bool persistent) {
     const int wgpc = (int)std::min<size_t>(2, (160 * 1024) / stem_l1_lds_bytes(dtype));
     if (!persistent) return ntiles;          // A/B aid (VTI_STEM_NOT_PERSISTENT): one workgroup per tile, as before
@@ -839,7 +909,11 @@ hipError_t launch_stem_l1(int dtype, const ConvParams& p, hipStream_t st, bool p
     dim3 grid((unsigned)stem_l1_grid(dtype, p.B * p.tiles_y * p.tiles_x, persistent));
     if (grid.x == 0) return hipSuccess;
     const size_t lds = stem_l1_lds_bytes(dtype);
-    return with_conv_type(dtype, [&](auto t) { return launch_lds<stem_l1_kernel<typename decltype(t)::type>>(grid, dim3(256), lds, st, p); });
+    return with_conv_type(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        constexpr int NT = stem_l1_nt<T>();
+        return launch_lds<stem_l1_kernel<T, NT>>(grid, dim3(NT), lds, st, p);
+    });
 }
 
 size_t stem_lds_bytes(int TH, int TW) { return 1024 + (size_t)(2 * TH + 1) * ((((2 * TW + 1) * 3 + 6) >> 2) * 4); }

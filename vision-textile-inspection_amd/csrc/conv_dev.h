@@ -268,9 +268,9 @@ constexpr int MREP = 5;
 // NREP n-tiles, the 4*NREP CONSECUTIVE output channels crun .. crun+4*NREP-1 of its pixel
 // (tile n, element j <-> channel crun + 4n + j).  fp16 outputs therefore go out as 16-byte stores (two tiles
 // at a time) that tile whole 128-byte lines; residuals are read the same way.
-template <typename T, int NREP>
-__device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[MREP][NREP], const bool (&pvalid)[MREP],
-                                              const int (&opy)[MREP], const int (&opx)[MREP], int b, int nt0, int wn,
+template <typename T, int NREP, int MR = MREP>
+__device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[MR][NREP], const bool (&pvalid)[MR],
+                                              const int (&opy)[MR], const int (&opx)[MR], int b, int nt0, int wn,
                                               int lane) {
     // Bias (and the residual of a whole pixel) are loaded up front: a load inside the store loop would make
     // every block wait on vmcnt(0), i.e. on all earlier STORES as well.
@@ -286,7 +286,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
         // common case: T output, vector stores, plain NHWC addressing
         const bool has_res = __builtin_amdgcn_readfirstlane(p.has_res) != 0;
 #pragma unroll
-        for (int m = 0; m < MREP; ++m) {
+        for (int m = 0; m < MR; ++m) {
             if (!pvalid[m]) continue;
             const size_t opix = ((size_t)(b * p.Hout + opy[m])) * p.Wout + opx[m];
             T* op = (T*)p.out + opix * p.out_ld + p.out_coff + crun;
@@ -354,7 +354,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
             // 16*NREP | Cout), so it goes out as 16-byte stores to output pixel (2y+dy, 2x+dx)
             const int qd = crun / p.deconv_c, co = crun - qd * p.deconv_c;
 #pragma unroll
-            for (int m = 0; m < MREP; ++m) {
+            for (int m = 0; m < MR; ++m) {
                 if (!pvalid[m] || crun >= p.Cout) continue;
                 const size_t opix = ((size_t)(b * 2 * p.Hout + 2 * opy[m] + (qd >> 1))) * (2 * p.Wout) + 2 * opx[m] + (qd & 1);
                 T* op = (T*)p.out + opix * p.out_ld + p.out_coff + co;
@@ -375,7 +375,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
     }
     // general case: fp32 head outputs, ragged channel counts (scalar stores), ConvTranspose scatter
 #pragma unroll
-    for (int m = 0; m < MREP; ++m) {
+    for (int m = 0; m < MR; ++m) {
         if (!pvalid[m]) continue;
 #pragma unroll
         for (int n = 0; n < NREP; ++n) {
@@ -463,9 +463,9 @@ __device__ __forceinline__ void stage2_preload(const ConvParams& p, int lane, bo
     for (int n = 0; n < NREP2; ++n) r.bias2[n] = *(const f32x4*)(p.bias2 + crun2 + cstep2 * n);
 }
 
-template <typename T, int NREP, int NREP2, bool FOLD = false, bool PRE = false>
-__device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MREP][NREP], const bool (&pvalid)[MREP],
-                                            const int (&opy)[MREP], const int (&opx)[MREP], int b, int lane,
+template <typename T, int NREP, int NREP2, bool FOLD = false, bool PRE = false, int MR = MREP>
+__device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR][NREP], const bool (&pvalid)[MR],
+                                            const int (&opy)[MR], const int (&opx)[MR], int b, int lane,
                                             const Stage2Regs<T, NREP, NREP2>* pre = nullptr, bool interior = false) {
     const int OW = FOLD ? 2 * p.Wout : p.Wout;        // width of the grid the second stage stores on
     using vec = typename Tr<T>::vec;
@@ -477,15 +477,15 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
     constexpr int KT = sizeof(T) == 2 ? (NREP + 1) / 2 : NREP;
     const __amdgpu_buffer_rsrc_t rsW2 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.w2, 0, (int)(KT * p.ntiles2 * 1024), 0x00020000);
-    f32x4 bias1[FOLD ? MREP : 1][NREP];
+    f32x4 bias1[FOLD ? MR : 1][NREP];
     if (PRE && (!FOLD || interior)) {               // (wave-uniform) every pixel of the tile takes the preloaded vector
 #pragma unroll
-        for (int m = 0; m < (FOLD ? MREP : 1); ++m)
+        for (int m = 0; m < (FOLD ? MR : 1); ++m)
 #pragma unroll
             for (int n = 0; n < NREP; ++n) bias1[m][n] = pre->bias1[n];
     } else if constexpr (FOLD) {
 #pragma unroll
-        for (int m = 0; m < MREP; ++m) {
+        for (int m = 0; m < MR; ++m) {
             const int cy = opy[m] == 0 ? 0 : (opy[m] == 2 * p.Hout - 1 ? 2 : 1), cx = opx[m] == 0 ? 0 : (opx[m] == OW - 1 ? 2 : 1);
             const float* bt = p.bias + (cy * 3 + cx) * (16 * NREP) + (lane >> 4) * 4 * NREP;
 #pragma unroll
@@ -495,9 +495,9 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
 #pragma unroll
         for (int n = 0; n < NREP; ++n) bias1[0][n] = *(const f32x4*)(p.bias + (lane >> 4) * 4 * NREP + 4 * n);
     }
-    f32x4 acc2[MREP][NREP2];
+    f32x4 acc2[MR][NREP2];
 #pragma unroll
-    for (int m = 0; m < MREP; ++m)
+    for (int m = 0; m < MR; ++m)
 #pragma unroll
         for (int n = 0; n < NREP2; ++n) acc2[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -509,7 +509,7 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
             else w2[n] = buf_load16<vec>(rsW2, (unsigned)(((t2 * p.ntiles2 + n) * 64 + lane) * 16), 0u);
         }
 #pragma unroll
-        for (int m = 0; m < MREP; ++m) {
+        for (int m = 0; m < MR; ++m) {
             vec x;
             if constexpr (sizeof(T) == 2) {
 #pragma unroll
@@ -557,7 +557,7 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
             // stores component g of (cx, cy, w, h) * stride: 4 lanes x 4 B = the first 16 bytes of the anchor's pred row.
             const int g = lane >> 4;
 #pragma unroll
-            for (int m = 0; m < MREP; ++m) {
+            for (int m = 0; m < MR; ++m) {
                 float d4[4];
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
@@ -592,7 +592,7 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
         // 16-byte stores and the four lane groups of a pixel write 64 contiguous bytes per instruction
         if (!p.nat2 && !p.out2_f32 && !p.scalar_store2 && (p.Cout2 & 7) == 0 && ((p.out2_ld | p.out2_coff) & 7) == 0) {
 #pragma unroll
-            for (int m = 0; m < MREP; ++m) {
+            for (int m = 0; m < MR; ++m) {
                 if (!pvalid[m]) continue;
                 half_t* op = (half_t*)p.out2 + ((size_t)b * p.out2_bstride + (size_t)opy[m] * OW + opx[m]) * p.out2_ld + p.out2_coff + crun2;
 #pragma unroll
@@ -611,7 +611,7 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
     }
     const bool want_best = p.act2 == 2 && p.best != nullptr;            // wave-uniform
 #pragma unroll
-    for (int m = 0; m < MREP; ++m) {
+    for (int m = 0; m < MR; ++m) {
         // out2_bstride = pixels per frame of the destination: Hout*Wout, or the anchor count when the towers write into pred
         const size_t pix = (size_t)b * p.out2_bstride + (size_t)opy[m] * OW + opx[m];
         const size_t o0 = pix * p.out2_ld + p.out2_coff;
