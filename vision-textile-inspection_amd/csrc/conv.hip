@@ -177,54 +177,34 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void conv_kernel(const ConvP
         __syncthreads();
         if (c < 2) VTI_STAMP(4 + 5 * c);
         constexpr int WD = NREP >= 5 ? 1 : 2;                    // weight fragment sets of the MFMA loop
-        vec wq[WD][NREP];
+        [[maybe_unused]] vec w0[WREG ? NREP : 1];
         if constexpr (WREG) {                                     // the chunk's operands, before their staging set is refilled
 #pragma unroll
-            for (int n = 0; n < NREP; ++n) wq[0][n] = rb[SET][n];
+            for (int n = 0; n < NREP; ++n) w0[n] = rb[SET][n];
         }
         if (c + PD < p.nchunks) issue(c + PD, ra[SET], rb[SET]);   // in flight during the MFMA loop(s) below
         // ---- MFMA over the taps of this chunk, software pipelined over the flat (tap, pixel-tile)
         // sequence: pixel fragments are read two steps ahead and the next tap's weight fragments one
         // whole tap ahead, so LDS latency hides under the 4-5 MFMAs of each step.
         {
-            constexpr int NSTEP = TAPS * MREP;
             // NREP == 5 (80-channel towers) sits at the register limit: it keeps one weight-fragment set and a
             // 2-deep pixel queue so that two waves still fit per SIMD (VGPR + AGPR <= 256).
             constexpr int XD = NREP >= 5 ? 2 : 3;          // pixel fragments in flight
-            vec xq[XD];
             auto ldx = [&](int s_) -> vec {
                 const int tp = s_ / MREP, mm = s_ % MREP;
                 const int toff = ((tp / KS) * PW + (tp % KS)) * 16;
                 return *(const vec*)(smA + abase[mm] + toff);
             };
-            auto ldw = [&](int tp, vec (&w)[NREP]) {
-#pragma unroll
-                for (int n = 0; n < NREP; ++n)
-                    w[n] = *(const vec*)(smB + ((wn * NREP + n) * TAPS + tp) * 1024 + lane * 16);
+            auto ldw = [&](int tp, int n) -> vec {
+                if constexpr (WREG) return w0[n];                  // 1x1: tap 0 is the only one
+                else return *(const vec*)(smB + ((wn * NREP + n) * TAPS + tp) * 1024 + lane * 16);
             };
             // (h2_taps keeps two prepared operand sets: 16 NREP registers more than the plain loop, which spills at NREP = 5 and at
             // NREP = 4 with 256 threads -- those keep the plain loop, whose operand preparation sits in front of each tap's MFMAs; the
             // register-lean h2_taps_nmajor of the persistent kernel was SLOWER here: 235 -> 286 us on the P3 class tower, the fused
             // stage's 100 + 100 accumulators spill either way and its two pixel-fragment sets add to it)
-            if constexpr (Tr<T>::H2 && TAPS > 1 && (NREP <= 3 || (NREP == 4 && NT == 512))) {
-                auto ldw1 = [&](int tp, int n) -> vec { return *(const vec*)(smB + ((wn * NREP + n) * TAPS + tp) * 1024 + lane * 16); };
-                h2_taps<NREP, MREP, TAPS, 3>(acc, ldx, ldw1);
-            } else {
-            if constexpr (!WREG) ldw(0, wq[0]);
-            xq[0] = ldx(0);
-            if (XD > 2 && NSTEP > 1) xq[1] = ldx(1);
-#pragma unroll
-            for (int s_ = 0; s_ < NSTEP; ++s_) {
-                const int tp = s_ / MREP, mm = s_ % MREP;
-                if (s_ + XD - 1 < NSTEP) xq[(s_ + XD - 1) % XD] = ldx(s_ + XD - 1);
-                if (WD == 2 && mm == 0 && tp + 1 < TAPS) ldw(tp + 1, wq[(tp + 1) % WD]);
-                __builtin_amdgcn_sched_barrier(0);      // keep the prefetch reads ahead of this step's MFMAs
-#pragma unroll
-                for (int n = 0; n < NREP; ++n) acc[mm][n] = mma(wq[tp % WD][n], xq[s_ % XD], acc[mm][n]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (WD == 1 && mm == MREP - 1 && tp + 1 < TAPS) ldw(tp + 1, wq[0]);   // reload after the tap's last use
-            }
-            }
+            if constexpr (Tr<T>::H2 && TAPS > 1 && (NREP <= 3 || (NREP == 4 && NT == 512))) h2_taps<NREP, MREP, TAPS, 3>(acc, ldx, ldw);
+            else taps<NREP, MREP, TAPS, XD, WD>(acc, ldx, ldw);
         }
         if (c < 2) VTI_STAMP(5 + 5 * c);
         if (c + 1 < p.nchunks) __syncthreads();   // everyone is done reading LDS before it is refilled
@@ -375,6 +355,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 1 : 2) void convfold_kernel(const C
 #pragma unroll
                 for (int n = 0; n < NREP; ++n) w[n] = *(const vec*)(smB + ((wave * NREP + n) * TAPS + tp) * 1024 + lane * 16);
             };
+            // (own copy of taps<NREP, MREP, TAPS, 3>: through the shared loop's (tap, n) weight lambda
+            // the 256-thread kernels' vgpr_count moves)
             if constexpr (Tr<T>::H2) {
                 auto ldw1 = [&](int tp, int n) -> vec { return *(const vec*)(smB + ((wave * NREP + n) * TAPS + tp) * 1024 + lane * 16); };
                 h2_taps<NREP, MREP, TAPS, 3>(acc, ldx, ldw1);
@@ -975,10 +957,10 @@ static hipError_t launch_t(int ks, int stride, int nrep, int mode, const ConvPar
 
 hipError_t launch_conv(int dtype, int ks, int stride, int nrep, int mode, const ConvParams& p, size_t lds_bytes,
                        hipStream_t st) {
-    if (p.pk == 4) return launch_conv_pk2(dtype, nrep, p, lds_bytes, st);
+    if (p.pk == 4) return launch_conv_pk(dtype, 2, nrep, p, lds_bytes, st);
     if (p.pk == 3) return launch_bneck_pk(dtype, nrep, p, lds_bytes, st);
     if (p.pk == 2) return launch_conv1_pk(dtype, nrep, p, lds_bytes, st);
-    if (p.pk) return launch_conv_pk(dtype, nrep, p, lds_bytes, st);
+    if (p.pk) return launch_conv_pk(dtype, 1, nrep, p, lds_bytes, st);
     const int NTB = p.WN * nrep;
     dim3 grid((unsigned)(p.B * p.tiles_y * p.tiles_x), (unsigned)((p.ntiles_n + NTB - 1) / NTB));
     if (grid.x == 0) return hipSuccess;

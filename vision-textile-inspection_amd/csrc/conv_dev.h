@@ -99,6 +99,41 @@ __device__ __forceinline__ f32x4 mma(h2x4 w, h2x4 x, f32x4 c) {
     return c;
 }
 
+// The MFMA loop of one K chunk for the plain types (and for h2 where h2_taps' prepared operand sets do not fit), over the flat
+// (tap, pixel-tile) sequence of a wave's M x NREP register tile: ldx(s) reads the pixel fragment of step s = tap * M + m, ldw(tap, n)
+// the weight fragment of n-tile n.  Software pipelined: pixel fragments are read XD - 1 steps ahead and the next tap's weight fragments
+// one whole tap ahead, so LDS latency hides under the NREP MFMAs of each step; the sched_barriers keep the prefetch reads ahead of
+// their step's MFMAs.  WD = 1 (register-tight tiles): one weight set, reloaded after the tap's last use.
+template <int NREP, int M, int TAPS, int XD, int WD = 2, class LDX, class LDW>
+__device__ __forceinline__ void taps(f32x4 (&acc)[M][NREP], LDX ldx, LDW ldw) {
+    constexpr int NSTEP = TAPS * M;
+    static_assert(XD - 1 <= NSTEP, "the pixel queue is primed with real steps only");
+    using vec = decltype(ldx(0));
+    vec xq[XD];
+    vec wq[WD][NREP];
+#pragma unroll
+    for (int n = 0; n < NREP; ++n) wq[0][n] = ldw(0, n);
+#pragma unroll
+    for (int i = 0; i < XD - 1; ++i) xq[i] = ldx(i);
+#pragma unroll
+    for (int s_ = 0; s_ < NSTEP; ++s_) {
+        const int tp = s_ / M, mm = s_ % M;
+        if (s_ + XD - 1 < NSTEP) xq[(s_ + XD - 1) % XD] = ldx(s_ + XD - 1);
+        if (WD == 2 && mm == 0 && tp + 1 < TAPS) {
+#pragma unroll
+            for (int n = 0; n < NREP; ++n) wq[(tp + 1) % WD][n] = ldw(tp + 1, n);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int n = 0; n < NREP; ++n) acc[mm][n] = mma(wq[tp % WD][n], xq[s_ % XD], acc[mm][n]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (WD == 1 && mm == M - 1 && tp + 1 < TAPS) {
+#pragma unroll
+            for (int n = 0; n < NREP; ++n) wq[0][n] = ldw(tp + 1, n);
+        }
+    }
+}
+
 // The MFMA loop of one K chunk for h2, over the flat (tap, pixel-tile) sequence of a wave's M x NREP register tile (the loop every
 // 3x3 kernel runs; ldx(s) reads the pixel fragment of step s = tap * M + m, ldw(tap, n) the raw weight fragment of n-tile n).
 // Same software pipeline as the fp16 / fp32 loops -- pixel fragments XD steps ahead, the next tap's weights one tap ahead -- plus
@@ -678,6 +713,38 @@ __device__ __forceinline__ void conv_stage2(const ConvParams& p, f32x4 (&acc)[MR
         }
     }
 }
+
+// ---- what the persistent kernels of conv_pk.hip (conv3_pk, conv1_pk, bneck_pk) share: tile schedule and LDS slot addressing.  (The layouts themselves are described at the top of conv_pk.hip.)
+constexpr int PK_PWP = 24;        // slots per patch row
+constexpr int PK_TW = 20;         // tile width (pixels)
+constexpr int PK_ROWS = 4;        // tile rows per M-wave: 4 x 20 = 80 pixels = MREP m-tiles
+constexpr unsigned PK_OOB = 0x80000000u;      // a buffer offset past every range: loads return zeros, stores are dropped
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// This workgroup's tiles: t, t + tstride, ... below tend.  p.pk_xcd: XCD k (= blockIdx.x & 7) owns tiles [k * per, (k+1) * per), so
+// that neighbouring tiles -- which share halo rows -- meet in one L2.
+__device__ __forceinline__ void pk_tile_range(const ConvParams& p, int& t, int& tend, int& tstride) {
+    if (p.pk_xcd) {
+        const int per = (p.pk_tiles + 7) >> 3, k = blockIdx.x & 7;
+        t = k * per + (int)(blockIdx.x >> 3);
+        tend = min((k + 1) * per, p.pk_tiles);
+        tstride = (int)(gridDim.x >> 3);
+    } else {
+        t = blockIdx.x; tend = p.pk_tiles; tstride = (int)gridDim.x;
+    }
+}
+// tile tt of a 3x3 launch -> frame and origin of its TH x 20 output pixels
+__device__ __forceinline__ void pk_tile_coords(const ConvParams& p, int tt, int& b, int& oy0, int& ox0) {
+    const int tx = tt % p.tiles_x, r = tt / p.tiles_x;
+    const int ty = r % p.tiles_y;
+    b = r / p.tiles_y; oy0 = ty * p.TH; ox0 = tx * PK_TW;
+}
+// Byte address of 16-byte piece `piece` of 64-byte pixel slot `slot` in a swizzled slot image; an MFMA operand read takes the piece
+// of the lane's k-group (lane >> 4).
+__device__ __forceinline__ int pk_piece_addr(int slot, int piece) { return (slot * 64 + piece * 16) ^ ((slot & 4) << 3); }
+__device__ __forceinline__ int pk_slot_addr(int slot, int lane) { return pk_piece_addr(slot, lane >> 4); }
+// Loader lane l fills 16-B position l & 3 of slot (l >> 2) of its piece; that position holds channel piece q (source-side swizzle).
+__device__ __forceinline__ int pk_lane_piece(int lane) { return (lane & 3) ^ (((lane >> 4) & 1) << 1); }
 
 // ---- host-side launch plumbing of the conv families (conv.hip, conv_pk.hip)
 // A family's template instantiations are written down once, as a Combos list of Ints tuples (e.g. (NREP, WN)); the launcher

@@ -33,9 +33,6 @@
 
 namespace vti {
 
-constexpr int PK_PWP = 24;        // slots per patch row
-constexpr int PK_TW = 20;         // tile width (pixels)
-constexpr int PK_ROWS = 4;        // tile rows per M-wave: 4 x 20 = 80 pixels = MREP m-tiles
 constexpr int PK_MAXD = 9;        // patch DMA instructions per wave and step (host checks)
 constexpr int PK_MAXD2 = 13;      // ... of the stride-2 kernel (its patch is ~4x the output tile)
 
@@ -44,8 +41,7 @@ using ConvPkS1 = Combos<Ints<1, 1>, Ints<2, 1>, Ints<3, 1>, Ints<4, 1>, Ints<5, 
                         Ints<2, 4>>;
 using ConvPkS2 = Combos<Ints<1, 4>, Ints<2, 2>, Ints<4, 1>, Ints<2, 1>, Ints<1, 2>>;
 using Conv1Pk = decltype(concat(ConvPkS1{}, Combos<Ints<4, 4>>{}));
-bool conv_pk_instantiated(int nrep, int wn) { return combo_has(ConvPkS1{}, nrep, wn); }
-bool conv_pk2_instantiated(int nrep, int wn) { return combo_has(ConvPkS2{}, nrep, wn); }
+bool conv_pk_instantiated(int S, int nrep, int wn) { return S == 2 ? combo_has(ConvPkS2{}, nrep, wn) : combo_has(ConvPkS1{}, nrep, wn); }
 bool conv1_pk_instantiated(int nrep, int wn) { return combo_has(Conv1Pk{}, nrep, wn); }
 // conv1_pk with the n-group's weights in the compute waves' registers (pk_wstat == 2), (NREP, WN, K chunks): the chunk counts of the
 // n-scale plans that stay inside the register budget of one 8-wave workgroup per CU (256 per wave) WITHOUT spilling (compiler's
@@ -68,17 +64,17 @@ bool conv1_pk_wreg_instantiated(int dtype, int nrep, int wn, int nchunks) {
 // wstat: the weights of ALL K chunks of the workgroup's n-group stay in LDS (any chunk count; K <= 2 chunks are always resident)
 // The host-side geometry of conv3_pk, by stride S: one stage of the patch ring, the LDS image, whether a geometry fits, its ring depth.
 static size_t pk_stage_bytes(int TH, int S) { return S == 2 ? (size_t)(2 * TH + 1) * 2 * PK_PWP * 64 : (size_t)(TH + 2) * PK_PWP * 64; }
-static size_t pk3_lds_bytes(int S, int TH, int WN, int NREP, int nchunks, int depth, int wstat) {
+size_t conv_pk_lds_bytes(int S, int TH, int WN, int NREP, int nchunks, int depth, int wstat) {
     const int nwbuf = wstat ? nchunks : nchunks > 2 ? depth : (nchunks > 1 ? 2 : 1);
     return depth * pk_stage_bytes(TH, S) + (size_t)nwbuf * WN * NREP * 9 * 1024 + (size_t)WN * NREP * 16 * 4;
 }
-static bool pk3_fits(int S, int TH, int WN, int NREP, int nchunks, int wstat) {
-    if (TH % PK_ROWS || (S == 2 && !conv_pk2_instantiated(NREP, WN))) return false;
+bool conv_pk_fits(int S, int TH, int WN, int NREP, int nchunks, int wstat) {
+    if (TH % PK_ROWS || (S == 2 && !conv_pk_instantiated(2, NREP, WN))) return false;
     const int ncomp = (TH / PK_ROWS) * WN;        // compute waves; as many loader waves beside them
     if (ncomp < 1 || ncomp > 4) return false;
     const int ndma = (int)(pk_stage_bytes(TH, S) / 1024);
     if ((ndma + ncomp - 1) / ncomp > (S == 2 ? PK_MAXD2 : PK_MAXD)) return false;
-    return pk3_lds_bytes(S, TH, WN, NREP, nchunks, 2, wstat) <= 160 * 1024;
+    return conv_pk_lds_bytes(S, TH, WN, NREP, nchunks, 2, wstat) <= 160 * 1024;
 }
 // The deepest ring, from 2 up to maxd, whose LDS image (lds_at(depth)) fits the 160 KiB and whose per_step DMA instructions per
 // loader wave and step stay inside the counted-wait range.  The default caps are 2 (in an A/B on one box the deeper rings made the
@@ -90,18 +86,20 @@ static int pk_ring_depth(int maxd, int per_step, F lds_at) {
     return d;
 }
 // 0 = the geometry does not fit at all
-static int pk3_depth(int S, int TH, int WN, int NREP, int nchunks, int wstat, int maxd) {
-    if (!pk3_fits(S, TH, WN, NREP, nchunks, wstat)) return 0;
+int conv_pk_depth(int S, int TH, int WN, int NREP, int nchunks, int wstat, int maxd) {
+    if (!conv_pk_fits(S, TH, WN, NREP, nchunks, wstat)) return 0;
     const int ncomp = (TH / PK_ROWS) * WN;
     const int per_step = ((int)(pk_stage_bytes(TH, S) / 1024) + ncomp - 1) / ncomp + (nchunks > 2 && !wstat ? (WN * NREP * 9 + ncomp - 1) / ncomp : 0);
-    return pk_ring_depth(maxd, per_step, [&](int d) { return pk3_lds_bytes(S, TH, WN, NREP, nchunks, d, wstat); });
+    return pk_ring_depth(maxd, per_step, [&](int d) { return conv_pk_lds_bytes(S, TH, WN, NREP, nchunks, d, wstat); });
 }
-size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat) { return pk3_lds_bytes(1, TH, WN, NREP, nchunks, depth, wstat); }
-size_t conv_pk2_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat) { return pk3_lds_bytes(2, TH, WN, NREP, nchunks, depth, wstat); }
-bool conv_pk_fits(int TH, int WN, int NREP, int nchunks, int wstat) { return pk3_fits(1, TH, WN, NREP, nchunks, wstat); }
-bool conv_pk2_fits(int TH, int WN, int NREP, int nchunks, int wstat) { return pk3_fits(2, TH, WN, NREP, nchunks, wstat); }
-int conv_pk_depth(int TH, int WN, int NREP, int nchunks, int wstat, int maxd) { return pk3_depth(1, TH, WN, NREP, nchunks, wstat, maxd); }
-int conv_pk2_depth(int TH, int WN, int NREP, int nchunks, int wstat, int maxd) { return pk3_depth(2, TH, WN, NREP, nchunks, wstat, maxd); }
+
+// What every persistent launcher checks: a workgroup count (whole XCD octets under pk_xcd), buffers inside the 2 GiB that 32-bit
+// offsets and the out-of-range marker leave, the ring depth, and the caller's LDS size against the kernel's own size function.
+static bool pk_launch_ok(const ConvParams& p, size_t lds_bytes, size_t lds_needed, int depth_lo, int depth_hi, bool needs_out) {
+    if (p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8)) return false;
+    if ((size_t)p.in_bytes >= 0x80000000u || (needs_out && (size_t)p.out_bytes >= 0x80000000u)) return false;
+    return p.pk_depth >= depth_lo && p.pk_depth <= depth_hi && lds_bytes >= lds_needed && lds_bytes <= 160 * 1024;
+}
 
 // LDS-DMA: 64 lanes x 16 B from per-lane buffer offsets to LDS [lds_addr, lds_addr + 1 KiB), lane-linear.
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned lds_addr) {
@@ -144,7 +142,7 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
     constexpr int MAXD = S == 2 ? PK_MAXD2 : PK_MAXD;
     static_assert(S == 1 || (S == 2 && !FOLD && NREP2 == 0), "stride 2: plain epilogue only");
     constexpr int WCHUNK = NTB * TAPS * 1024;
-    constexpr unsigned OOB = 0x80000000u;
+    constexpr unsigned OOB = PK_OOB;
     constexpr bool FAST = !Tr<T>::F32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -167,22 +165,9 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
     for (int i = tid; i < NTB * 16; i += (int)blockDim.x) ((float*)(smem + bias_off))[i] = p.bias[nt0 * 16 + i];
     __syncthreads();
 
-    // ---- this workgroup's tiles: XCD k (= blockIdx.x & 7) owns tiles [k * per, (k+1) * per)
     int t, tend, tstride;
-    if (p.pk_xcd) {
-        const int per = (p.pk_tiles + 7) >> 3, k = blockIdx.x & 7;
-        t = k * per + (int)(blockIdx.x >> 3);
-        tend = min((k + 1) * per, p.pk_tiles);
-        tstride = (int)(gridDim.x >> 3);
-    } else {
-        t = blockIdx.x; tend = p.pk_tiles; tstride = (int)gridDim.x;
-    }
+    pk_tile_range(p, t, tend, tstride);
     if (t >= tend) return;
-    auto tile_coords = [&](int tt, int& b, int& oy0, int& ox0) {
-        const int tx = tt % p.tiles_x, r = tt / p.tiles_x;
-        const int ty = r % p.tiles_y;
-        b = r / p.tiles_y; oy0 = ty * p.TH; ox0 = tx * PK_TW;
-    };
     const int nsteps = ((tend - t + tstride - 1) / tstride) * p.nchunks;
 
     if (wave >= ncomp) {
@@ -192,10 +177,10 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
         // barrier(s) they wait with a COUNTED vmcnt for everything up to DMA(s) while the younger steps stay in flight
         // (every loader wave issues the same number of DMA instructions in every step).  With steps of ~1.3 k MFMA cycles
         // and ~2-4 k cycles of loaded memory latency a single step of look-ahead leaves the compute waves waiting at every barrier.
+        // (conv1_pk and bneck_pk run the same ring protocol in their own loops: behind one shared helper conv1_pk's register counts moved.)
         const int lw = wave - ncomp;
-        // piece i = lw + u * nld fills slots 16i .. 16i+15; lane l -> slot 16i + (l >> 2), 16-B position l & 3,
-        // which holds channel piece q (source-side swizzle)
-        const int q = (lane & 3) ^ (((lane >> 4) & 1) << 1);
+        // piece i = lw + u * nld fills slots 16i .. 16i+15; lane l -> slot 16i + (l >> 2), channel piece q
+        const int q = pk_lane_piece(lane);
         const int cvalid = (p.Cin - q * VEC + KC - 1) / KC;         // chunks in which this lane's channel piece exists
         int dyx[MAXD];
 #pragma unroll
@@ -215,7 +200,7 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
         unsigned voff[MAXD];
         auto setup_voff = [&](int tt) {
             int b, oy0, ox0;
-            tile_coords(tt, b, oy0, ox0);
+            pk_tile_coords(p, tt, b, oy0, ox0);
 #pragma unroll
             for (int u = 0; u < MAXD; ++u) {
                 const int y = S * oy0 - 1 + (dyx[u] >> 8), x = S * ox0 - 1 + (dyx[u] & 255);
@@ -292,7 +277,7 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
             // fold: window column b (= dx < 2) of phase column fpx is patch column px + fpx + b, window row a is patch row py + fpy + a
             const int s = S == 2 ? (2 * ry[m]) * PWP + (dx == 1 ? PK_PWP + px : px + (dx >> 1))      // input (2 y + dy, 2 x + dx), planes
                                  : (ry[m] + fpy) * PK_PWP + px + fpx + dx;
-            xa[m][dx] = (s * 64 + (lane >> 4) * 16) ^ ((s & 4) << 3);
+            xa[m][dx] = pk_slot_addr(s, lane);
         }
     }
     const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
@@ -300,7 +285,7 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
     const bool fast_epi = NREP2 == 0 && !p.scalar_store && !p.out_f32 && !p.deconv_c &&
                           (sizeof(T) != 2 || NREP % 2 || (p.Cout & 7) == 0);    // a 16-B pair must not straddle Cout
     int b, oy0, ox0;
-    tile_coords(t, b, oy0, ox0);
+    pk_tile_coords(p, t, b, oy0, ox0);
     int step = 0;
     // fused stage operands that are the same for every tile: loaded once per launch (fold only; the other fused ops run per tile)
     Stage2Regs<T, NREP, NREP2 ? NREP2 : 1> s2r;
@@ -322,43 +307,21 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
             {
                 const char* sx = smem + cur * stage_bytes;
                 const char* sw = smem + wbuf_off + (stream_w ? cur : c) * WCHUNK + wn * (NREP * TAPS * 1024) + lane * 16;
-                constexpr int NSTEP = TAPS * MREP;
                 // pixel fragments in flight: a step is NREP MFMAs (16 cycles each), an LDS read takes ~100+ cycles with 8 waves on
                 // the CU, so small register tiles need a deeper queue to keep the matrix pipe fed
-                constexpr int XD = NREP >= 5 ? 3 : NREP == 4 ? 5 : NREP == 3 ? 5 : NREP == 2 ? 6 : 8, WD = 2;
-                vec xq[XD];
-                vec wq[WD][NREP];
+                constexpr int XD = NREP >= 5 ? 3 : NREP == 4 ? 5 : NREP == 3 ? 5 : NREP == 2 ? 6 : 8;
                 auto ldx = [&](int s_) -> vec {
                     const int tp = s_ / MREP, mm = s_ % MREP;
                     if constexpr (FOLD) return *(const vec*)(sx + xa[mm][tp & 1] + (tp >> 1) * (PK_PWP * 64));
                     else return *(const vec*)(sx + xa[mm][tp % 3] + (tp / 3) * (PWP * 64));
                 };
-                auto ldw = [&](int tp, vec (&w)[NREP]) {
-#pragma unroll
-                    for (int n = 0; n < NREP; ++n) w[n] = *(const vec*)(sw + (n * TAPS + tp) * 1024);
-                };
-                if constexpr (Tr<T>::H2) {
-                    auto ldw1 = [&](int tp, int n) -> vec { return *(const vec*)(sw + (n * TAPS + tp) * 1024); };
+                auto ldw = [&](int tp, int n) -> vec { return *(const vec*)(sw + (n * TAPS + tp) * 1024); };
 #ifndef H2_XD
 #define H2_XD (NREP >= 4 ? 3 : 4)
 #endif
-                    if constexpr (NREP >= 5) h2_taps_nmajor<NREP, MREP, TAPS>(acc, ldx, ldw1);
-                    else h2_taps<NREP, MREP, TAPS, H2_XD>(acc, ldx, ldw1);
-                } else {
-                ldw(0, wq[0]);
-#pragma unroll
-                for (int i = 0; i < XD - 1; ++i) xq[i] = ldx(i);
-#pragma unroll
-                for (int s_ = 0; s_ < NSTEP; ++s_) {
-                    const int tp = s_ / MREP, mm = s_ % MREP;
-                    if (s_ + XD - 1 < NSTEP) xq[(s_ + XD - 1) % XD] = ldx(s_ + XD - 1);
-                    if (mm == 0 && tp + 1 < TAPS) ldw(tp + 1, wq[(tp + 1) % WD]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int n = 0; n < NREP; ++n) acc[mm][n] = mma(wq[tp % WD][n], xq[s_ % XD], acc[mm][n]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                }
+                if constexpr (Tr<T>::H2 && NREP >= 5) h2_taps_nmajor<NREP, MREP, TAPS>(acc, ldx, ldw);
+                else if constexpr (Tr<T>::H2) h2_taps<NREP, MREP, TAPS, H2_XD>(acc, ldx, ldw);
+                else taps<NREP, MREP, TAPS, XD>(acc, ldx, ldw);
             }
             if (step < 2) VTI_STAMP(3 + 4 * step);
         }
@@ -375,7 +338,6 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
             // residual of the WHOLE tile first (fp16, register tiles up to NREP = 2: 20 registers): loading it per m-tile costs
             // one memory round trip per m-tile (16 -> 16 at 160x160: 58 us with, 43 us without a residual)
             constexpr bool RES_UPFRONT = has_res && sizeof(T) == 2 && NREP <= 2;
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             u32x2 rr[RES_UPFRONT ? MREP : 1][RES_UPFRONT ? NREP : 1];
             if constexpr (RES_UPFRONT) {
 #pragma unroll
@@ -434,7 +396,6 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), rsO, cv ? ob + n * 8 : OOB, 0u, 0);
                     }
                 } else if constexpr (sizeof(T) == 2) {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                     for (int n = 0; n < NREP; ++n) {
                         half4 hv;
@@ -474,7 +435,7 @@ __global__ __launch_bounds__(512) void conv3_pk(const ConvParams p) {
         const int tn = t + tstride;
         if (tn >= tend) break;
         t = tn;
-        tile_coords(t, b, oy0, ox0);
+        pk_tile_coords(p, t, b, oy0, ox0);
     }
 }
 
@@ -518,7 +479,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
     constexpr int VEC = Tr<T>::VEC, KC = Tr<T>::KC, ES = (int)sizeof(T);
     constexpr int NTB = WN * NREP;
     constexpr int WCH = NTB * 1024;
-    constexpr unsigned OOB = 0x80000000u;
+    constexpr unsigned OOB = PK_OOB;
     constexpr bool FAST = !Tr<T>::F32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -544,14 +505,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
     __syncthreads();
 
     int t, tend, tstride;
-    if (p.pk_xcd) {
-        const int per = (p.pk_tiles + 7) >> 3, k = blockIdx.x & 7;
-        t = k * per + (int)(blockIdx.x >> 3);
-        tend = min((k + 1) * per, p.pk_tiles);
-        tstride = (int)(gridDim.x >> 3);
-    } else {
-        t = blockIdx.x; tend = p.pk_tiles; tstride = (int)gridDim.x;
-    }
+    pk_tile_range(p, t, tend, tstride);
     if (t >= tend) return;
     const int ntiles_mine = (tend - t + tstride - 1) / tstride;
     const int nsteps = ntiles_mine * spt;
@@ -559,7 +513,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
     if (wave >= ncomp) {
         // =================== loader waves ===================
         const int lw = wave - ncomp;
-        const int q = (lane & 3) ^ (((lane >> 4) & 1) << 1);            // channel piece of this lane's 16-B position
+        const int q = pk_lane_piece(lane);            // channel piece of this lane's 16-B position
         const int cvalid = (p.Cin - q * VEC + KC - 1) / KC;
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)p.in_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.wpk, 0, (int)p.wpk_bytes, 0x00020000);
@@ -645,7 +599,7 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
 #pragma unroll
     for (int m = 0; m < MREP; ++m) {
         const int sl = wm * 80 + m * 16 + (lane & 15);
-        xa[m] = (sl * 64 + (lane >> 4) * 16) ^ ((sl & 4) << 3);
+        xa[m] = pk_slot_addr(sl, lane);
     }
     const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
     const bool fast_epi = !p.scalar_store && !p.out_f32 && !p.deconv_c && !p.has_res &&
@@ -852,7 +806,6 @@ __global__ __launch_bounds__(512) void conv1_pk(const ConvParams p) {
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), rsO, cv ? ob + n * 8 : OOB, 0u, 0);
                     }
                 } else if constexpr (sizeof(T) == 2) {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                     for (int n = 0; n < NREP; ++n) {
                         half4 hv;
@@ -904,10 +857,8 @@ bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat,
 // 1x1: p.TH = compute waves along M, p.TW = 80 (pixels per wave); workgroups as for the 3x3 kernel
 hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     const int NTB = p.WN * nrep;
-    if (!conv1_pk_fits(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat, p.pk_cps)) return hipErrorInvalidValue;
-    if (lds_bytes < conv1_pk_lds_bytes(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat, p.pk_cps)) return hipErrorInvalidValue;
-    if (p.ntiles_n % NTB || p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8) || p.has_res) return hipErrorInvalidValue;
-    if ((size_t)p.in_bytes >= 0x80000000u || (size_t)p.out_bytes >= 0x80000000u) return hipErrorInvalidValue;
+    if (!conv1_pk_fits(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat, p.pk_cps) || p.ntiles_n % NTB || p.has_res) return hipErrorInvalidValue;
+    if (!pk_launch_ok(p, lds_bytes, conv1_pk_lds_bytes(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat, p.pk_cps), 2, 8, true)) return hipErrorInvalidValue;
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * p.TH * p.WN * 64;
     dim3 grid((unsigned)p.pk_wgs, (unsigned)(p.ntiles_n / NTB));
@@ -938,8 +889,7 @@ int conv_pk_fold_depth(int nchunks, int maxd) {       // steps here are only ~1.
 
 hipError_t launch_conv_pk_fold(int dtype, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     if (p.TH != 4 || p.TW != PK_TW || p.WN != 4 || p.nchunks > 2 || p.ntiles_n != 16 || !p.fold || !p.out2) return hipErrorInvalidValue;
-    if (p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8) || (size_t)p.in_bytes >= 0x80000000u) return hipErrorInvalidValue;
-    if (p.pk_depth < 2 || p.pk_depth > 4 || lds_bytes < conv_pk_fold_lds_bytes(p.nchunks, p.pk_depth) || lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    if (!pk_launch_ok(p, lds_bytes, conv_pk_fold_lds_bytes(p.nchunks, p.pk_depth), 2, 4, false)) return hipErrorInvalidValue;      // (it writes out2)
     if (p.pk_tiles == 0) return hipSuccess;
     dim3 grid((unsigned)p.pk_wgs, 1);
     return combo_dispatch(FoldN2{}, [&](auto c) {
@@ -949,34 +899,21 @@ hipError_t launch_conv_pk_fold(int dtype, const ConvParams& p, size_t lds_bytes,
     }, p.ntiles2);
 }
 
-// stride-2 3x3 on the persistent schedule (p.pk == 4)
-hipError_t launch_conv_pk2(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
+// 3x3 of stride S (1; 2: p.pk == 4): grid.x workgroups (p.pk_wgs) x n-groups; (TH/4) * WN compute + as many loader waves
+hipError_t launch_conv_pk(int dtype, int S, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     const int NTB = p.WN * nrep;
-    if (p.TW != PK_TW || !conv_pk2_fits(p.TH, p.WN, nrep, p.nchunks, p.pk_wstat) || p.ntiles2 > 0) return hipErrorInvalidValue;
-    if (p.pk_depth < 2 || p.pk_depth > 4 || lds_bytes < conv_pk2_lds_bytes(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat) || lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    if (p.ntiles_n % NTB || p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8)) return hipErrorInvalidValue;
-    if ((size_t)p.in_bytes >= 0x80000000u || (size_t)p.out_bytes >= 0x80000000u) return hipErrorInvalidValue;
-    if (p.pk_tiles == 0) return hipSuccess;
-    const int threads = 2 * (p.TH / PK_ROWS) * p.WN * 64;
-    dim3 grid((unsigned)p.pk_wgs, (unsigned)(p.ntiles_n / NTB));
-    return combo_dispatch(ConvPkS2{}, [&](auto c) {
-        return with_conv_type(dtype, [&](auto t) {
-            using C = decltype(c);
-            return launch_lds<conv3_pk<typename decltype(t)::type, C::v[0], C::v[1], 0, false, 2>>(grid, dim3(threads), lds_bytes, st, p);
-        });
-    }, nrep, p.WN);
-}
-
-// grid.x workgroups (p.pk_wgs, a multiple of 8 when p.pk_xcd) x n-groups; (TH/4) * WN compute + as many loader waves
-hipError_t launch_conv_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
-    const int NTB = p.WN * nrep;
-    if (p.TH % PK_ROWS || p.TW != PK_TW || !conv_pk_fits(p.TH, p.WN, nrep, p.nchunks, p.pk_wstat)) return hipErrorInvalidValue;
-    if (p.pk_depth < 2 || p.pk_depth > 4 || lds_bytes < conv_pk_lds_bytes(p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat) || lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    if (p.ntiles_n % NTB || p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8)) return hipErrorInvalidValue;
-    if ((size_t)p.in_bytes >= 0x80000000u || (size_t)p.out_bytes >= 0x80000000u) return hipErrorInvalidValue;
+    if (p.TW != PK_TW || !conv_pk_fits(S, p.TH, p.WN, nrep, p.nchunks, p.pk_wstat) || p.ntiles_n % NTB || (S == 2 && p.ntiles2 > 0)) return hipErrorInvalidValue;
+    if (!pk_launch_ok(p, lds_bytes, conv_pk_lds_bytes(S, p.TH, p.WN, nrep, p.nchunks, p.pk_depth, p.pk_wstat), 2, 4, true)) return hipErrorInvalidValue;
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * (p.TH / PK_ROWS) * p.WN * 64;   // compute waves + as many loader waves
     dim3 grid((unsigned)p.pk_wgs, (unsigned)(p.ntiles_n / NTB));
+    if (S == 2)
+        return combo_dispatch(ConvPkS2{}, [&](auto c) {
+            return with_conv_type(dtype, [&](auto t) {
+                using C = decltype(c);
+                return launch_lds<conv3_pk<typename decltype(t)::type, C::v[0], C::v[1], 0, false, 2>>(grid, dim3(threads), lds_bytes, st, p);
+            });
+        }, nrep, p.WN);
     return with_conv_type(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         if (p.ntiles2 > 0) {
@@ -1040,7 +977,7 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
     using vec = typename Tr<T>::vec;
     constexpr int VEC = Tr<T>::VEC, ES = (int)sizeof(T);
     constexpr int TAPS = 9, R1W = PK_TW + 2;
-    constexpr unsigned OOB = 0x80000000u;
+    constexpr unsigned OOB = PK_OOB;
     constexpr bool FAST = !Tr<T>::F32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -1064,27 +1001,15 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
     __syncthreads();
 
     int t, tend, tstride;
-    if (p.pk_xcd) {
-        const int per = (p.pk_tiles + 7) >> 3, k = blockIdx.x & 7;
-        t = k * per + (int)(blockIdx.x >> 3);
-        tend = min((k + 1) * per, p.pk_tiles);
-        tstride = (int)(gridDim.x >> 3);
-    } else {
-        t = blockIdx.x; tend = p.pk_tiles; tstride = (int)gridDim.x;
-    }
+    pk_tile_range(p, t, tend, tstride);
     if (t >= tend) return;
-    auto tile_coords = [&](int tt, int& b, int& oy0, int& ox0) {
-        const int tx = tt % p.tiles_x, r = tt / p.tiles_x;
-        const int ty = r % p.tiles_y;
-        b = r / p.tiles_y; oy0 = ty * p.TH; ox0 = tx * PK_TW;
-    };
     const int ntiles_mine = (tend - t + tstride - 1) / tstride;
 
     if (wave >= nwm) {
         // =================== loader waves ===================
         const int lw = wave - nwm, nld = nwm;
         const int ndma = PH * PK_PWP / 16;
-        const int q = (lane & 3) ^ (((lane >> 4) & 1) << 1);
+        const int q = pk_lane_piece(lane);
         const bool qok = q * VEC < ((TAIL && !TAILH2) ? 2 * p.Cin : p.Cin);   // one chunk: channel pieces beyond Cin are written as zeros (fp16 tail: y0 | y1)
         int dyx[PK_MAXD];
 #pragma unroll
@@ -1098,7 +1023,7 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
         const __amdgpu_buffer_rsrc_t rsW2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, NREP * TAPS * 1024, 0x00020000);
         auto issue_patch = [&](int tt, int stage) {
             int b, oy0, ox0;
-            tile_coords(tt, b, oy0, ox0);
+            pk_tile_coords(p, tt, b, oy0, ox0);
             const unsigned dst = lds0 + stage * stage_bytes + lw * 1024;
 #pragma unroll
             for (int u = 0; u < PK_MAXD; ++u) {
@@ -1157,12 +1082,12 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
             const int s = yy * PK_PWP + xx + dx;
-            xa1[m][dx] = (s * 64 + g * 16) ^ ((s & 4) << 3);
+            xa1[m][dx] = pk_slot_addr(s, lane);
         }
         const int st = yy * PK_PWP + xx;
         // lane group g owns channels 4 NREP g ..: fp16 NREP 2 / fp32 -> 16-byte piece g; fp16 NREP 1 -> half of piece g >> 1
         const int piece = (sizeof(T) == 2 && NREP == 1) ? (g >> 1) : g;
-        tw1[m] = timg_off + ((st * 64 + piece * 16) ^ ((st & 4) << 3)) + ((sizeof(T) == 2 && NREP == 1) ? (g & 1) * 8 : 0);
+        tw1[m] = timg_off + pk_piece_addr(st, piece) + ((sizeof(T) == 2 && NREP == 1) ? (g & 1) * 8 : 0);
     }
     // phase 2 operand addresses (as conv3_pk, on the T image whose origin is the tile origin - 1)
     int xa2[MREP][3], ry[MREP], rx[MREP], ra[MREP];
@@ -1176,12 +1101,12 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
             const int s = ry[m] * PK_PWP + px + dx;
-            xa2[m][dx] = timg_off + ((s * 64 + g * 16) ^ ((s & 4) << 3));
+            xa2[m][dx] = timg_off + pk_slot_addr(s, lane);
         }
         const int sr = (ry[m] + 2) * PK_PWP + px + 2;       // the pixel itself in the input patch (shortcut)
         const int piece = ((sizeof(T) == 2 && NREP == 1) ? (g >> 1) : g) + ((TAIL && !TAILH2) ? 2 : 0);      // fp16 tail: y1 is the slot's upper half
-        ra[m] = ((sr * 64 + piece * 16) ^ ((sr & 4) << 3)) + ((sizeof(T) == 2 && NREP == 1) ? (g & 1) * 8 : 0);
-        xc[m] = (sr * 64 + g * 16) ^ ((sr & 4) << 3);       // tail: the pixel's [y0 | y1] as an MFMA operand (k-group g = piece g)
+        ra[m] = pk_piece_addr(sr, piece) + ((sizeof(T) == 2 && NREP == 1) ? (g & 1) * 8 : 0);
+        xc[m] = pk_slot_addr(sr, lane);       // tail: the pixel's [y0 | y1] as an MFMA operand (k-group g = piece g)
     }
     [[maybe_unused]] vec wA[2], wB[2];
     [[maybe_unused]] f32x4 b3r[2];
@@ -1218,7 +1143,7 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
     VTI_STAMP(0);
     while (true) {
         int b, oy0, ox0;
-        tile_coords(t, b, oy0, ox0);
+        pk_tile_coords(p, t, b, oy0, ox0);
         const char* sx = smem + (step % D) * stage_bytes;
         [[maybe_unused]] u32x4 y0r[TAILH2 ? MREP : 1];
         if constexpr (TAILH2) {                             // y0 of this wave's pixels: consumed in the tail, a whole tile of MFMAs later
@@ -1242,36 +1167,14 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
 #pragma unroll
                 for (int n = 0; n < NREP; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
             const char* sw = smem + w1_off + lane * 16;
-            constexpr int NSTEP = TAPS * BN_MREP1;
             constexpr int XD = NREP == 2 ? 6 : 8;           // pixel fragments in flight (a step is only NREP MFMAs long)
-            vec xq[XD];
-            vec wq[2][NREP];
             auto ldx = [&](int s_) -> vec {
                 const int tp = s_ / BN_MREP1, mm = s_ % BN_MREP1;
                 return *(const vec*)(sx + xa1[mm][tp % 3] + (tp / 3) * (PK_PWP * 64));
             };
-            auto ldw = [&](int tp, vec (&w)[NREP]) {
-#pragma unroll
-                for (int n = 0; n < NREP; ++n) w[n] = *(const vec*)(sw + (n * TAPS + tp) * 1024);
-            };
-            if constexpr (Tr<T>::H2) {
-                auto ldw1 = [&](int tp, int n) -> vec { return *(const vec*)(sw + (n * TAPS + tp) * 1024); };
-                h2_taps<NREP, BN_MREP1, TAPS, 4>(acc, ldx, ldw1);
-            } else {
-            ldw(0, wq[0]);
-#pragma unroll
-            for (int i = 0; i < XD - 1; ++i) xq[i] = ldx(i);
-#pragma unroll
-            for (int s_ = 0; s_ < NSTEP; ++s_) {
-                const int tp = s_ / BN_MREP1, mm = s_ % BN_MREP1;
-                if (s_ + XD - 1 < NSTEP) xq[(s_ + XD - 1) % XD] = ldx(s_ + XD - 1);
-                if (mm == 0 && tp + 1 < TAPS) ldw(tp + 1, wq[(tp + 1) % 2]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int n = 0; n < NREP; ++n) acc[mm][n] = mma(wq[tp % 2][n], xq[s_ % XD], acc[mm][n]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            }
+            auto ldw = [&](int tp, int n) -> vec { return *(const vec*)(sw + (n * TAPS + tp) * 1024); };
+            if constexpr (Tr<T>::H2) h2_taps<NREP, BN_MREP1, TAPS, 4>(acc, ldx, ldw);
+            else taps<NREP, BN_MREP1, TAPS, XD>(acc, ldx, ldw);
             if (step == 2) VTI_STAMP(3);
             // bias + SiLU, rounded to T, into the T image; a pixel outside the feature map is conv 2's zero padding
 #pragma unroll
@@ -1314,36 +1217,14 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
 #pragma unroll
                 for (int n = 0; n < NREP; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
             const char* sw = smem + w2_off + lane * 16;
-            constexpr int NSTEP = TAPS * MREP;
             constexpr int XD = NREP == 2 ? 6 : 8;
-            vec xq[XD];
-            vec wq[2][NREP];
             auto ldx = [&](int s_) -> vec {
                 const int tp = s_ / MREP, mm = s_ % MREP;
                 return *(const vec*)(smem + xa2[mm][tp % 3] + (tp / 3) * (PK_PWP * 64));
             };
-            auto ldw = [&](int tp, vec (&w)[NREP]) {
-#pragma unroll
-                for (int n = 0; n < NREP; ++n) w[n] = *(const vec*)(sw + (n * TAPS + tp) * 1024);
-            };
-            if constexpr (Tr<T>::H2) {
-                auto ldw1 = [&](int tp, int n) -> vec { return *(const vec*)(sw + (n * TAPS + tp) * 1024); };
-                h2_taps<NREP, MREP, TAPS, 4>(acc, ldx, ldw1);
-            } else {
-            ldw(0, wq[0]);
-#pragma unroll
-            for (int i = 0; i < XD - 1; ++i) xq[i] = ldx(i);
-#pragma unroll
-            for (int s_ = 0; s_ < NSTEP; ++s_) {
-                const int tp = s_ / MREP, mm = s_ % MREP;
-                if (s_ + XD - 1 < NSTEP) xq[(s_ + XD - 1) % XD] = ldx(s_ + XD - 1);
-                if (mm == 0 && tp + 1 < TAPS) ldw(tp + 1, wq[(tp + 1) % 2]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int n = 0; n < NREP; ++n) acc[mm][n] = mma(wq[tp % 2][n], xq[s_ % XD], acc[mm][n]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            }
+            auto ldw = [&](int tp, int n) -> vec { return *(const vec*)(sw + (n * TAPS + tp) * 1024); };
+            if constexpr (Tr<T>::H2) h2_taps<NREP, MREP, TAPS, 4>(acc, ldx, ldw);
+            else taps<NREP, MREP, TAPS, XD>(acc, ldx, ldw);
             if (step == 2) VTI_STAMP(6);
 #pragma unroll
             for (int m = 0; m < MREP; ++m) {
@@ -1411,7 +1292,6 @@ __global__ __launch_bounds__(512) void bneck_pk(const ConvParams p) {
                     for (int j = 0; j < 4; ++j) { hv[j] = (half_t)v[0][j]; hv[4 + j] = (half_t)v[1][j]; }
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), rsO, pv ? ob : OOB, 0u, 0);
                 } else if constexpr (sizeof(T) == 2) {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                     half4 hv;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) hv[j] = (half_t)v[0][j];
@@ -1437,8 +1317,7 @@ using BneckSet = std::conditional_t<Tr<T>::H16, Combos<Ints<1, 1>, Ints<1, 0>, I
 hipError_t launch_bneck_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st) {
     if (p.TW != PK_TW || !bneck_pk_fits(p.TH, nrep) || p.nchunks != 1 || p.Cin != 16 * nrep || p.Cout != 16 * nrep || !p.w2 || !p.bias2)
         return hipErrorInvalidValue;
-    if (p.Hin != p.Hout || p.Win != p.Wout || p.pk_wgs < 1 || (p.pk_xcd && p.pk_wgs % 8)) return hipErrorInvalidValue;
-    if ((size_t)p.in_bytes >= 0x80000000u || (size_t)p.out_bytes >= 0x80000000u) return hipErrorInvalidValue;
+    if (p.Hin != p.Hout || p.Win != p.Wout) return hipErrorInvalidValue;
     const int tail = p.w0 != nullptr;                       // the C2f's closing 1x1 in the same kernel (in_coff is then y0's offset)
     if (tail && ((dtype != VTI_F16 && dtype != VTI_H2) || nrep != 1 || !p.out2 || !p.bias0 || p.Cout2 != 32 || ((p.out2_ld | p.out2_coff) & 7) || (p.in_coff & 7)))
         return hipErrorInvalidValue;
@@ -1446,7 +1325,7 @@ hipError_t launch_bneck_pk(int dtype, int nrep, const ConvParams& p, size_t lds_
     // shortcut = the input (fp16 tail: in_coff was moved down to y0, the shortcut y1 sits Cin above it)
     if (p.has_res && (p.res != p.in || p.res_ld != p.in_ld || p.res_coff != p.in_coff + ((tail && dtype == VTI_F16) ? p.Cin : 0))) return hipErrorInvalidValue;
     if ((p.out_ld | p.out_coff) & (dtype == VTI_F16 ? 7 : 3)) return hipErrorInvalidValue;                              // 16-byte stores
-    if (p.pk_depth < 2 || p.pk_depth > 4 || lds_bytes < bneck_pk_lds_bytes(p.TH, nrep, p.pk_depth) || lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    if (!pk_launch_ok(p, lds_bytes, bneck_pk_lds_bytes(p.TH, nrep, p.pk_depth), 2, 4, true)) return hipErrorInvalidValue;
     if (p.pk_tiles == 0) return hipSuccess;
     const int threads = 2 * (p.TH / PK_ROWS) * 64;
     dim3 grid((unsigned)p.pk_wgs, 1);

@@ -115,10 +115,6 @@ static bool choose_pk3_cfg(const PlanOptions& opt, int dtype, const ConvRow& r, 
     const bool s2 = r.s == 2;
     if (s2 ? opt.no_pk2 : opt.no_pk) return false;
     if (!(r.k == 3 && (s2 ? r.kind == 0 : (r.s == 1 && r.kind != 2))) || r.w_out < 20) return false;
-    const auto instantiated = s2 ? conv_pk2_instantiated : conv_pk_instantiated;
-    const auto fits = s2 ? conv_pk2_fits : conv_pk_fits;
-    size_t (*const lds_bytes)(int, int, int, int, int, int) = s2 ? conv_pk2_lds_bytes : conv_pk_lds_bytes;
-    const auto ring_depth = s2 ? conv_pk2_depth : conv_pk_depth;
     const int patch_cols = s2 ? 41 : 22, patch_slots = s2 ? 48 : 24;
     const int esize = dtype == VTI_F16 ? 2 : 4;
     const bool wide = dtype != VTI_F16 || opt.pk_wide16;       // 4-byte elements (VTI_PK_WIDE16: fp16 too): ingest-priced search with resident-weight variants
@@ -130,7 +126,7 @@ static bool choose_pk3_cfg(const PlanOptions& opt, int dtype, const ConvRow& r, 
         if (fwn && WN != fwn) continue;
         for (int NREP = 1; NREP <= 5; ++NREP) {
             if (fnrep && NREP != fnrep) continue;
-            if (!instantiated(NREP, WN)) continue;
+            if (!conv_pk_instantiated(r.s, NREP, WN)) continue;
             if (dtype == VTI_H2 && NREP == 5 && !fnrep && opt.h2_no_n5) continue;      // A/B aid (h2 at NREP = 5 runs h2_taps_nmajor)
             const int NTB = WN * NREP;
             const int gy = (c.ntiles_n + NTB - 1) / NTB;
@@ -141,8 +137,8 @@ static bool choose_pk3_cfg(const PlanOptions& opt, int dtype, const ConvRow& r, 
                 if (fth && TH != fth) continue;
                 const int patch_rows = s2 ? 2 * TH + 1 : TH + 2;
                 for (int wstat = (wide && !opt.no_pk_wstat && c.nchunks > 2) ? 1 : 0; wstat >= 0; --wstat) {
-                    if (ncomp > 4 || !fits(TH, WN, NREP, c.nchunks, wstat)) continue;
-                    const size_t lds = lds_bytes(TH, WN, NREP, c.nchunks, 2, wstat);
+                    if (ncomp > 4 || !conv_pk_fits(r.s, TH, WN, NREP, c.nchunks, wstat)) continue;
+                    const size_t lds = conv_pk_lds_bytes(r.s, TH, WN, NREP, c.nchunks, 2, wstat);
                     const int wgpc = s2 ? 1 : (int)std::min<size_t>(2, (160 * 1024) / lds);
                     const int tiles_y = (r.h_out + TH - 1) / TH;
                     const long NT = (long)max_batch * tiles_y * tiles_x;
@@ -183,9 +179,9 @@ static bool choose_pk3_cfg(const PlanOptions& opt, int dtype, const ConvRow& r, 
         c.ntiles_n = (c.ntiles_n + c.WN * c.NREP - 1) / (c.WN * c.NREP) * (c.WN * c.NREP);   // whole workgroup n-groups
         // ring depth: a deeper ring (loaders further ahead) when it costs no co-resident workgroup
         c.pk_depth = 2;
-        const int dmax = ring_depth(c.TH, c.WN, c.NREP, c.nchunks, c.pk_wstat, opt.pk_depth);
+        const int dmax = conv_pk_depth(r.s, c.TH, c.WN, c.NREP, c.nchunks, c.pk_wstat, opt.pk_depth);
         for (int dd = 3; dd <= dmax; ++dd) {
-            const size_t l = lds_bytes(c.TH, c.WN, c.NREP, c.nchunks, dd, c.pk_wstat);
+            const size_t l = conv_pk_lds_bytes(r.s, c.TH, c.WN, c.NREP, c.nchunks, dd, c.pk_wstat);
             if ((int)std::min<size_t>(2, (160 * 1024) / l) >= c.pk_wgpc) { c.pk_depth = dd; c.lds = l; }
         }
     }

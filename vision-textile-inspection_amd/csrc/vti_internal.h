@@ -234,18 +234,12 @@ size_t conv_pk_fold_lds_bytes(int nchunks, int depth);
 int conv_pk_fold_depth(int nchunks, int maxd = 3);
 void pack_conv_l1pairs(int dtype, const ConvRow& r1, const float* w, const float* b, uint8_t* dst_w, float* dst_b, float* alpha = nullptr);
 size_t packed_l1pairs_bytes(int dtype);
-// conv_pk.hip: persistent 3x3/s1 kernel
-hipError_t launch_conv_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
-size_t conv_pk_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat = 0);   // wstat: all K chunks' weights resident in LDS
-int conv_pk_depth(int TH, int WN, int NREP, int nchunks, int wstat = 0, int maxd = 2);     // maxd: PlanOptions.pk_depth
-// stride-2 3x3 on the persistent schedule (ConvCfg.pk == 4)
-hipError_t launch_conv_pk2(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
-size_t conv_pk2_lds_bytes(int TH, int WN, int NREP, int nchunks, int depth, int wstat = 0);
-bool conv_pk2_fits(int TH, int WN, int NREP, int nchunks, int wstat = 0);
-bool conv_pk2_instantiated(int nrep, int wn);
-int conv_pk2_depth(int TH, int WN, int NREP, int nchunks, int wstat = 0, int maxd = 2);
-bool conv_pk_fits(int TH, int WN, int NREP, int nchunks, int wstat = 0);
-bool conv_pk_instantiated(int nrep, int wn);
+// conv_pk.hip: persistent 3x3 kernel of stride S (1: ConvCfg.pk == 1, 2: ConvCfg.pk == 4)
+hipError_t launch_conv_pk(int dtype, int S, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
+size_t conv_pk_lds_bytes(int S, int TH, int WN, int NREP, int nchunks, int depth, int wstat = 0);   // wstat: all K chunks' weights resident in LDS
+int conv_pk_depth(int S, int TH, int WN, int NREP, int nchunks, int wstat = 0, int maxd = 2);     // maxd: PlanOptions.pk_depth; 0 = does not fit
+bool conv_pk_fits(int S, int TH, int WN, int NREP, int nchunks, int wstat = 0);
+bool conv_pk_instantiated(int S, int nrep, int wn);
 hipError_t launch_conv1_pk(int dtype, int nrep, const ConvParams& p, size_t lds_bytes, hipStream_t st);
 size_t conv1_pk_lds_bytes(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps = 1);   // cps: K chunks per step
 bool conv1_pk_fits(int nwm, int WN, int NREP, int nchunks, int depth, int wstat, int cps = 1);
